@@ -25,6 +25,8 @@ wall time.  `roofline.achieved` = algorithmic bytes of one step / average step
 duration measured with HIP events on the stream the kernels run on.
 `cpu_baseline` = the pure-Python port (oracle/csparse_oracle.py: the reference is
 pure Python, single-threaded) on a bounded sample of the same generator.
+`ms_per_step` = wall time of the timed region / --steps.  `--dump-outputs DIR`
+writes y of the last timed step to DIR (dump_outputs).
 """
 import argparse
 import json
@@ -70,6 +72,34 @@ def gaxpy_bytes(m, n, nnz):
 def cholsol_bytes(lnz, n, k):
     # forward + backward factor reads, b -> y -> x each read and written
     return 2 * 12 * lnz + 4 * 8 * n * k
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(dirname, lib, _csx, hy, n, rank, world):
+    """--dump-outputs DIR: y after the last timed step (warmup + steps passes of y += A x from y = 0: what a caller of
+    cs_gaxpy receives), float64, as DIR/y.npy (DIR/y_rank<r>.npy at N > 1).  The inputs are seeded, so two builds run
+    with the same arguments can be compared file for file; the values match to rounding, as the kernel's summation
+    order may differ from run to run (config.kernel names the kernel, --mode pins it).  A y larger than its rank's
+    share of DUMP_LIMIT_BYTES is written at a fixed, seeded sample of rows, ascending, their row numbers (as float64)
+    in DIR/y_rows.npy.  Called after the timed region; returns what was written, for the JSON line."""
+    import numpy as np
+    y = np.empty(n)
+    _csx.check(lib.csx_vec_download(hy, _csx.pd(y), n), "vec_download")
+    os.makedirs(dirname, exist_ok=True)
+    tag = "" if world == 1 else "_rank%d" % rank
+    budget = DUMP_LIMIT_BYTES // world - 4096             # room for the .npy headers
+    files = {}
+    if y.nbytes > budget:
+        rows = np.sort(np.random.default_rng(20240601).choice(n, budget // 16, replace=False))
+        y = y[rows]
+        files["y_rows" + tag] = rows.astype(np.float64)
+    files["y" + tag] = y
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": {name + ".npy": [a.dtype.name, len(a)] for name, a in files.items()},
+            "rows_sampled": "y_rows" + tag in files}
 
 
 def cpu_baseline(n_cpu, per_col, budget_s, gen="uniform"):
@@ -271,7 +301,12 @@ def main():
                          "no headline, value = null.  At N > 1 the preflight always runs before the full-size legs.")
     ap.add_argument("--exchange-nrhs", type=int, default=None,
                     help="right-hand sides per GPU in the scatter / gather legs (default: --nrhs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write y of the last one (what cs_gaxpy returns) to DIR as .npy "
+                         "(see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))          # parent: starts the ranks, touches no GPU
@@ -347,6 +382,7 @@ def main():
     barrier()
     wall = max_over_ranks(time.perf_counter() - t0)
     step_ms_events = max_over_ranks(ev_ms.value / args.steps)
+    dumped = dump_outputs(args.dump_outputs, lib, _csx, hy, n, rank, world) if args.dump_outputs else None
     by = gaxpy_bytes(n, n, nnz)
     value = by * args.steps * world / wall / 1e9
     achieved = by / (step_ms_events * 1e-3) / 1e9
@@ -407,6 +443,8 @@ def main():
         "parity_on_the_timed_matrix": {"against": "GAXPY_EXACT (reference summation order, csparse.py:1210-1212)",
                                        "max_rel_err": parity_err, "tolerance": 1e-12, "ok": parity_ok},
     }
+    if dumped:
+        out["dumped_outputs"] = dumped
     if shape.value >= 0:                                  # only when the plan timed its launch shapes (gaxpy.tune_shape)
         out["config"]["plan_launch_shape"] = {"picked": ["4x5", "2x10", "8x4", "2x8"][shape.value],
                                               "ms_when_the_plan_was_built": {k: round(v, 4) for k, v in

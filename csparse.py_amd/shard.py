@@ -229,7 +229,9 @@ class Comm(object):
         if self.csx is not None:
             self._csx.check(self.csx.csx_comm_barrier(), "csx_comm_barrier")
         elif self.dist is not None:
-            self.dist.barrier()
+            # an all-reduce of one CPU value, not dist.barrier(): that asks torch for its accelerator, which starts a HIP
+            # runtime and opens the GPU in every rank, also in ranks that use none (bench.py --rehearse)
+            self.dist.all_reduce(self.torch.zeros(1))
 
     def _reduce(self, value, op):
         if self.csx is not None:
@@ -428,7 +430,7 @@ class Comm(object):
             self.csx.csx_comm_finalize()
             self.csx = None
         if self.dist is not None:
-            self.dist.barrier()
+            self.barrier()
             self.dist.destroy_process_group()
             self.dist = None
 

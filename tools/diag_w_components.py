@@ -1,5 +1,7 @@
 import sys, os, time
-sys.path.insert(0, "/root/repo/csparse.py_amd"); sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/oracle")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("csparse.py_amd", "tests", "", "oracle"):
+    sys.path.insert(0, os.path.join(ROOT, p))
 import numpy as np
 import csparse as cs, _csx
 from test_gpu_configs import _w_matrix

@@ -1,5 +1,6 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo/csparse.py_amd")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "csparse.py_amd"))
 import _csx
 _csx.init(0)
 lib = _csx.lib(); C = _csx.C

@@ -1,5 +1,7 @@
-import sys, time
-sys.path.insert(0, "/root/repo/csparse.py_amd"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in ("csparse.py_amd", "tests"):
+    sys.path.insert(0, os.path.join(ROOT, p))
 import numpy as np, _csx, synth
 _csx.init(0); lib = _csx.lib(); C = _csx.C
 n, Ap32, Ai, Ax, sizes = synth.ragged_cliques(5000000, 8, 64, 20240605)
