@@ -124,6 +124,11 @@ _PROTOS = {
     "csx_gaxpy_sharded_piece": [H, C.c_int, H],
     "csx_gaxpy_sharded_buffers": [H, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(C.c_int64)],
     "csx_gaxpy_sharded_sum": [H, C.c_int, C.c_int, H],
+    "csx_maxtrans": [H, C.c_int64, _i32p, _i32p],
+    "csx_scc": [H, _i32p, _i32p, _i32p],
+    "csx_dmperm": [H, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "csx_dmperm_times": [_f64p],
+    "csx_dmperm_rounds": [C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

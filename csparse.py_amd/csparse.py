@@ -1761,3 +1761,176 @@ def qrsol_factor(A, order=0):
 
 def device_name():
     return _csx.device_info()
+
+
+# ----------------------------------------------- Dulmage-Mendelsohn family ----
+
+class csd(object):
+    """Output of the Dulmage-Mendelsohn decomposition (csparse.py:93-112)."""
+
+    def __init__(self):
+        self.p = []     # size m, row permutation
+        self.q = []     # size n, column permutation
+        self.r = []     # size nb+1, block k is rows r[k] to r[k+1]-1 in A(p,q)
+        self.s = []     # size nb+1, block k is cols s[k] to s[k+1]-1 in A(p,q)
+        self.nb = 0     # number of blocks in the fine decomposition
+        self.rr = []    # coarse row decomposition
+        self.cc = []    # coarse column decomposition
+
+
+def cs_dalloc(m, n):
+    """Allocate a csd (csparse.py:2443): p m, r m+6, q n, s n+6, cc and rr 5."""
+    D = csd()
+    D.p = ialloc(m)
+    D.r = ialloc(m + 6)
+    D.q = ialloc(n)
+    D.s = ialloc(n + 6)
+    D.cc = ialloc(5)
+    D.rr = ialloc(5)
+    return D
+
+
+def _splitmix64(z):
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def randperm_array(n, seed):
+    """cs_randperm as a numpy int32 array (identity for seed 0).
+
+    The generator: index k gets the key (h(k), k) with h(k) = the upper 32 bits of
+    splitmix64(splitmix64(seed mod 2^64) + k); the permutation lists 0..n-1 by ascending key.  seed -1 gives
+    n-1..0.  These keys are also the priorities with which cs_maxtrans / cs_dmperm break ties on the device."""
+    n = int(n)
+    if seed == 0:
+        return np.arange(n, dtype=np.int32)
+    if seed == -1:
+        return np.arange(n - 1, -1, -1, dtype=np.int32)
+    sh = _splitmix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF))
+    with np.errstate(over="ignore"):
+        h = _splitmix64(sh + np.arange(n, dtype=np.uint64)) >> np.uint64(32)
+    return np.argsort(h, kind="stable").astype(np.int32)
+
+
+def cs_randperm(n, seed):
+    """Random permutation (csparse.py:1915): None for seed 0 (identity), n-1..0 for -1, otherwise the
+    permutation randperm_array documents (the reference's own draw cannot run: SURVEY.md D11)."""
+    if seed == 0:
+        return None
+    return randperm_array(n, seed).tolist()
+
+
+def maxtrans_array(A, seed=0):
+    """Maximum matching as a numpy int32 array of length m + n (cs_maxtrans's jimatch); None if A is not CSC."""
+    if not CS_CSC(A):
+        return None
+    m, n = A.m, A.n
+    out = np.empty(m + n, dtype=np.int32)
+    rank = _csx.C.c_int32(0)
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_maxtrans(dA.handle, int(seed), _csx.pi(out), rank), "csx_maxtrans")
+    return out
+
+
+def cs_maxtrans(A, seed):
+    """Maximum transversal (csparse.py:1527): jimatch, length m + n.  jimatch[i] (i < m) is the column matched to
+    row i, jimatch[m + j] the row matched to column j, -1 if unmatched.  The matching has maximum cardinality
+    (the structural rank) and every pair is an entry of A (stored zeros count).  Which maximum matching comes back
+    depends on the seed (cs_randperm's keys set the priorities); it is the same on every call."""
+    out = maxtrans_array(A, seed)
+    return None if out is None else out.tolist()
+
+
+def scc_arrays(A):
+    """(p, r) numpy int32 arrays of cs_scc; r has nb + 1 entries.  None if A is not CSC or not square."""
+    if not CS_CSC(A):
+        return None
+    if A.m != A.n:
+        return None
+    n = A.n
+    p = np.empty(n, dtype=np.int32)
+    r = np.zeros(n + 1, dtype=np.int32)
+    nb = _csx.C.c_int32(0)
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_scc(dA.handle, _csx.pi(p), _csx.pi(r), nb), "csx_scc")
+    return p, r[:nb.value + 1].copy()
+
+
+def cs_scc(A):
+    """Strongly connected components of a square A (csparse.py:1992): a csd with p, r and nb.  A(p,p) is block
+    upper triangular -- for every entry (i, j) the block holding row i comes no later than the block holding
+    column j -- and each diagonal block r[k] .. r[k+1]-1 is strongly connected.  None if A is not CSC or not square."""
+    got = scc_arrays(A)
+    if got is None:
+        return None
+    p, r = got
+    D = cs_dalloc(A.m, 0)
+    D.p = p.tolist()
+    D.r = r.tolist() + [0] * (A.m + 6 - len(r))
+    D.nb = len(r) - 1
+    return D
+
+
+def dmperm_arrays(A, seed=0):
+    """cs_dmperm as numpy int32 arrays: dict(p, q, r, s, rr, cc, nb) with r and s trimmed to nb + 1 entries.
+    None if A is not CSC."""
+    if not CS_CSC(A):
+        return None
+    m, n = A.m, A.n
+    p = np.empty(m, dtype=np.int32)
+    q = np.empty(n, dtype=np.int32)
+    r = np.zeros(m + 6, dtype=np.int32)
+    s = np.zeros(n + 6, dtype=np.int32)
+    rr = np.zeros(5, dtype=np.int32)
+    cc = np.zeros(5, dtype=np.int32)
+    nb = _csx.C.c_int32(0)
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_dmperm(dA.handle, int(seed), _csx.pi(p), _csx.pi(q), _csx.pi(r), _csx.pi(s), nb,
+                                         _csx.pi(rr), _csx.pi(cc)), "csx_dmperm")
+    k = nb.value
+    return dict(p=p, q=q, r=r[:k + 1].copy(), s=s[:k + 1].copy(), rr=rr, cc=cc, nb=k)
+
+
+def dmperm_times():
+    """Device times (ms) of the last cs_dmperm / cs_maxtrans / cs_scc: initial matching, augmentation, coarse
+    decomposition, fine decomposition, whole call."""
+    ms = np.zeros(5)
+    _csx.check(_csx.lib().csx_dmperm_times(_csx.pd(ms)), "csx_dmperm_times")
+    return dict(zip(("matching", "augment", "coarse", "fine", "total"), ms.tolist()))
+
+
+def dmperm_rounds():
+    """Round counts of the last cs_dmperm / cs_maxtrans / cs_scc: augmentation levels (all phases), augmentation
+    phases, trim rounds, colouring rounds (at most 2 (m + n + 1) in all), block order rounds."""
+    r = np.zeros(5, dtype=np.int64)
+    _csx.check(_csx.lib().csx_dmperm_rounds(r.ctypes.data_as(_csx.C.POINTER(_csx.C.c_int64))), "csx_dmperm_rounds")
+    return dict(zip(("augment_levels", "augment_phases", "trim", "colour", "order"), r.tolist()))
+
+
+def cs_dmperm(A, seed):
+    """Dulmage-Mendelsohn decomposition (csparse.py:905), laid out as CSparse's: a csd with p (m), q (n), r, s
+    (nb + 1 used), nb, rr[5], cc[5]; None if A is not CSC.
+
+    cc = [0, |C0|, |C0|+|C1|, |C0|+|C1|+|C2|, n], rr = [0, |R1|, |R1|+|R2|, |R1|+|R2|+|R3|, m], the structural
+    rank is rr[3].  Matched pairs lie on the shifted diagonals of A(p,q): row rr[0]+k with column cc[1]+k, rr[1]+k
+    with cc[2]+k, rr[2]+k with cc[3]+k.  Fine blocks: A(R1, C0 C1) if cc[2] > 0, then the strongly connected
+    components of A(R2, C2) in block upper triangular order, then A(R3 R0, C3) if rr[2] < m; A(p,q) is block upper
+    triangular with respect to r and s.  The coarse sets, the row and column sets of every fine block, nb and the
+    structural rank do not depend on the seed; the matching and the order inside a block do."""
+    got = dmperm_arrays(A, seed)
+    if got is None:
+        return None
+    m, n, k = A.m, A.n, got["nb"]
+    D = cs_dalloc(m, n)
+    D.p = got["p"].tolist()
+    D.q = got["q"].tolist()
+    D.r = got["r"].tolist() + [0] * (m + 6 - (k + 1))
+    D.s = got["s"].tolist() + [0] * (n + 6 - (k + 1))
+    D.nb = k
+    D.rr = got["rr"].tolist()
+    D.cc = got["cc"].tolist()
+    return D

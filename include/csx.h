@@ -449,6 +449,33 @@ int csx_gaxpy_sharded_piece(csx_handle_t plan, int q, csx_handle_t x);
 int csx_gaxpy_sharded_buffers(csx_handle_t plan, void **work, void **recv, int64_t *chunk);
 int csx_gaxpy_sharded_sum(csx_handle_t plan, int rank, int world, csx_handle_t y_mine);
 
+/* ---- Dulmage-Mendelsohn decomposition (csparse.py:905 cs_dmperm, :1527 cs_maxtrans, :1992 cs_scc) ----
+ * Entries are structural: a stored 0.0 counts, pattern-only matrices are accepted.  Outputs go to caller-owned host
+ * buffers.  Deterministic: the same matrix and seed give the same arrays on every call.  seed sets the priority of
+ * rows and columns when ties are broken (0 natural, -1 reversed, otherwise the order of splitmix64 keys, as
+ * csparse.cs_randperm); the matching and the order inside a block depend on it, the sets, nb and sprank do not.
+ * csx_maxtrans: a maximum matching, jimatch[i] (i < m) = column of row i, jimatch[m + j] = row of column j, -1 if
+ *   unmatched (m + n slots); sprank (optional) = its cardinality.
+ * csx_scc: square A only (CSX_EINVAL otherwise).  p (n) and r (n + 1 slots, nb + 1 used): A(p,p) is block upper
+ *   triangular -- for every entry (i, j) the block of row i comes no later than the block of column j -- and every
+ *   diagonal block r[k] .. r[k+1]-1 is strongly connected.
+ * csx_dmperm: p (m), q (n), r (m + 6), s (n + 6), rr (5), cc (5) as cs_dalloc sizes them, unused slots 0.
+ *   cc = [0, |C0|, |C0|+|C1|, |C0|+|C1|+|C2|, n], rr = [0, |R1|, |R1|+|R2|, |R1|+|R2|+|R3|, m], sprank = rr[3];
+ *   row rr[0]+k is matched to column cc[1]+k (R1/C1), rr[1]+k to cc[2]+k (R2/C2), rr[2]+k to cc[3]+k (R3/C3).
+ *   Fine blocks (csparse.py:982-996): A(R1, C0 C1) if cc[2] > 0, the SCCs of A(R2, C2) in block upper triangular
+ *   order, A(R3 R0, C3) if rr[2] < m.
+ * csx_dmperm_times: device times (ms) of the last csx_dmperm / csx_maxtrans / csx_scc: initial matching,
+ *   augmentation, coarse decomposition, fine decomposition (the SCCs), whole call.
+ * csx_dmperm_rounds: round counts of the same call: augmentation levels (all phases), augmentation phases, trim
+ *   rounds, colouring rounds (propagations and backward searches; at most 2 (m + n + 1) in all, else CSX_ERUNTIME), block
+ *   order rounds. */
+int csx_maxtrans(csx_handle_t A, int64_t seed, int32_t *jimatch, int32_t *sprank);
+int csx_scc(csx_handle_t A, int32_t *p, int32_t *r, int32_t *nb);
+int csx_dmperm(csx_handle_t A, int64_t seed, int32_t *p, int32_t *q, int32_t *r, int32_t *s, int32_t *nb, int32_t *rr,
+               int32_t *cc);
+int csx_dmperm_times(double *ms);
+int csx_dmperm_rounds(int64_t *rounds);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
