@@ -1419,130 +1419,24 @@ __global__ __launch_bounds__(256) void k_cholsol_dense(const Tree *__restrict__ 
 }
 
 // ---- dense blocks, the reference's order (the DEFAULT solve of a forest of dense blocks) ------------------
-// Same organisation as k_cholsol_dense (one wave = one block x 64 right-hand sides, a lane's BS unknowns in
-// registers, the packed block staged in LDS by global->LDS DMA and broadcast), but every operation is the
-// reference's: multiply and subtract rounded separately, a true division by the diagonal, and the terms of an
-// unknown taken in the reference's order -- forward: ascending column (the sweep order); backward: ascending row,
-// which in the reversed sweep numbering is DEscending t, so the two passes are two bodies.  x is bit-identical
-// to cs_lsolve + cs_ltsolve for every right-hand side; the fused per-tree kernel it replaces on dense forests took
-// 24.8 ms per 128 right-hand sides on the 5M-row G-spd.
+// One wave = one block x 64 right-hand sides, a lane's BS unknowns in registers, the packed block staged in LDS by
+// global->LDS DMA.  Every operation is the reference's: multiply and subtract rounded separately, a true division by
+// the diagonal, and the terms of an unknown taken in the reference's order -- forward: ascending column (the sweep
+// order); backward: ascending row, which in the reversed sweep numbering is DEscending t, so the two passes are two
+// bodies.  x is bit-identical to cs_lsolve + cs_ltsolve for every right-hand side; the fused per-tree kernel it replaces
+// on dense forests took 24.8 ms per 128 right-hand sides on the 5M-row G-spd.
 #pragma clang fp contract(off)
-// R right-hand sides per lane: the R subtraction chains of a row are independent, so they fill each other's latency, and one
-// broadcast of an L value serves R products (the broadcast -- LDS return path -- and the two separately rounded fp64
-// operations per term are what bound this kernel: 4 + 4 cycles of issue per term and right-hand side).
-template <int BS, bool BACKWARD, int R>
-__device__ __forceinline__ void dense_exact_pass_rows(double (&x)[R][BS], const double *M, const double *D) {
-#pragma unroll
-    for (int sp = 0; sp < BS; sp++) {
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = x[r][sp];
-        if (!BACKWARD) {
-#pragma unroll
-            for (int tt = 0; tt < sp; tt++) {
-                const double mv = M[sp * (sp - 1) / 2 + tt];
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const double t = mv * x[r][tt];
-                    acc[r] = acc[r] - t;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int tt = sp - 1; tt >= 0; tt--) {
-                const double mv = M[sp * (sp - 1) / 2 + tt];
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const double t = mv * x[r][tt];
-                    acc[r] = acc[r] - t;
-                }
-            }
-        }
-        const double dv = D[sp];
-#pragma unroll
-        for (int r = 0; r < R; r++) x[r][sp] = acc[r] / dv;
-        // without a fence the optimiser hoists every row's LDS reads to the top of the pass (they depend on nothing):
-        // 512 VGPRs and spills at BS = 32, 292 VGPRs at BS = 64
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-
-// The same pass with the L values read through a ring (see below); x indexed in reverse for the backward sweep.
-// R right-hand sides per lane: the R subtraction chains of a row are independent, so they fill each other's latency, and one
-// broadcast of an L value serves R products (the broadcast -- LDS return path -- and the two separately rounded fp64
-// operations per term are what bound this kernel: 4 + 4 cycles of issue per term and right-hand side).
-//
-// The L values come through a RING of K registers filled K terms ahead, in program order and fenced term by term
-// (sched_barrier): left to itself the compiler either hoists a whole row's LDS reads (hundreds of VGPRs, spills) or
-// reads each pair of values just before its use -- ds_read_b128, s_waitcnt lgkmcnt(0), two products -- and then every
-// second term pays the LDS latency (the round-2 kernel: 55 cycles per term and wave where 8 are issued).
-template <int BS, bool BACKWARD, int R>
-__device__ __forceinline__ void dense_exact_pass(double (&x)[R][BS], const double *M, const double *D) {
-    constexpr int K = 12;                               // at most 15 LDS reads can be outstanding (lgkmcnt)
-    // The backward sweep runs in sweep positions (position s = row BS - 1 - s): x is indexed through XI instead of being
-    // reversed in place -- a reversal between the passes makes the compiler keep both copies of x alive (390 registers
-    // at BS = 64 instead of 262).
-#define CSX_XI(i) (BACKWARD ? BS - 1 - (i) : (i))
-    double ring[K];
-    int lsp = 1, le = 0;                                // the next term to request: row lsp, position le in its order
-#pragma unroll
-    for (int u = 0; u < K; u++) {
-        ring[u] = 0.0;
-        if (lsp < BS) {
-            ring[u] = M[lsp * (lsp - 1) / 2 + (BACKWARD ? lsp - 1 - le : le)];
-            if (++le == lsp) {
-                lsp++;
-                le = 0;
-            }
-        }
-    }
-    double dnext = D[0];
-    int f = 0;
-#pragma unroll
-    for (int sp = 0; sp < BS; sp++) {
-        double acc[R];
-#pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = x[r][CSX_XI(sp)];
-        const double dv = dnext;
-        if (sp + 1 < BS) dnext = D[sp + 1];
-#pragma unroll
-        for (int e = 0; e < sp; e++) {
-            const int tt = BACKWARD ? sp - 1 - e : e;   // the reference's order: ascending columns forward, descending backward
-            const double mv = ring[f % K];
-            if (lsp < BS) {
-                ring[f % K] = M[lsp * (lsp - 1) / 2 + (BACKWARD ? lsp - 1 - le : le)];
-                if (++le == lsp) {
-                    lsp++;
-                    le = 0;
-                }
-            }
-            f++;
-#pragma unroll
-            for (int r = 0; r < R; r++) {
-                const double t = mv * x[r][CSX_XI(tt)];
-                acc[r] = acc[r] - t;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int r = 0; r < R; r++) x[r][CSX_XI(sp)] = acc[r] / dv;
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#undef CSX_XI
-}
-
-// The same pass with the L values delivered by DPP instead of by broadcast reads.  What bounds the passes above is the LDS
-// return path: a broadcast read hands 64 x 16 bytes to the wave to deliver TWO doubles (8 clk per read on a path the four
-// SIMDs of a CU share: 4.2 ms per 128 right-hand sides at blocks of 64, twice the 2.1 ms the fp64 operations need).  The
-// 64-bit move of this chip takes one DPP control, row_newbcast:k -- every lane receives the value lane k of its ROW of 16
-// lanes holds.  So the 16 lanes of a row read 16 consecutive L values of the matrix row being solved (one ds_read_b64 per
-// 16 terms, the four rows reading the same 128 bytes), and term k is
+// Every lane needs every L value.  Taken by broadcast LDS reads (the kernel's earlier forms, retired: DESIGN.md 4.5), they
+// are bound by the LDS return path: a broadcast read hands 64 x 16 bytes to the wave to deliver TWO doubles (8 clk per read
+// on a path the four SIMDs of a CU share: 4.2 ms per 128 right-hand sides at blocks of 64, twice the 2.1 ms the fp64
+// operations need).  So the L values come by DPP: the 64-bit move of this chip takes one DPP control, row_newbcast:k --
+// every lane receives the value lane k of its ROW of 16 lanes holds.  The 16 lanes of a row read 16 consecutive L values of
+// the matrix row being solved (one ds_read_b64 per 16 terms, the four rows reading the same 128 bytes), and term k is
 //     v_mov_b64_dpp b, Lv row_newbcast:k ;  v_mul_f64 t, b, x_k ;  v_add_f64 acc, acc, -t
 // -- the reference's two separately rounded operations plus one register move; no v_readlane, no scalar load, and a
-// broadcast read for one term in four only (see dense_exact_term_dpp).  (v_mul_f64 / v_add_f64 are VOP3 and have no DPP form on this ISA; v_fmac_f64 has one, but it fuses.)  A row's L
-// values and diagonal are requested while the previous row is being solved.
+// broadcast read for one term in four only (see dense_exact_term_dpp).  (v_mul_f64 / v_add_f64 are VOP3 and have no DPP
+// form on this ISA; v_fmac_f64 has one, but it fuses.)  A row's L values and diagonal are requested while the previous row
+// is being solved.
 template <int K>
 __device__ __forceinline__ double dpp_row_bcast(const double v) {
     return __longlong_as_double(__builtin_amdgcn_mov_dpp(__double_as_longlong(v), 0x150 + K, 0xf, 0xf, true));
@@ -1572,14 +1466,14 @@ constexpr int xl_group(int NS, int G) {
 
 // term E of sweep row SP; the L values of a group of 16 terms die with the group's last term, and the same group of the
 // NEXT row is requested there: four values live instead of eight (168 VGPRs is three waves per SIMD at blocks of 64)
-template <int BS, bool BACKWARD, int MIX, bool PACKED, int SP, int E>
+template <int BS, bool BACKWARD, bool PACKED, int SP, int E>
 __device__ __forceinline__ void dense_exact_term_dpp(const double (&x)[BS], const double *M, const int (&lb)[4], const double (&lv)[4],
                                                      double (&nxt)[4], double &acc) {
     constexpr int G = E >> 4, NS = SP + 1;
     // One term in four takes its L value by a broadcast LDS read instead: two VALU instructions instead of three, on the LDS
     // path the DPP form left idle.  Measured at blocks of 64 (ms per 128 right-hand sides): none 4.81, one in four 4.59, two
     // in four 4.93 -- at half the terms the return path (4 clk per broadcast value and CU) is 80 % busy and its latency shows.
-    constexpr bool via_lds = (E & 3) < MIX;
+    constexpr bool via_lds = (E & 3) == 0;
     const double lbv = via_lds ? M[xl_term<BS, BACKWARD, PACKED>(SP, E)] : dpp_row_bcast<(E & 15)>(lv[G]);
     const double t = lbv * x[BACKWARD ? BS - 1 - E : E];
     acc = acc - t;
@@ -1590,15 +1484,15 @@ __device__ __forceinline__ void dense_exact_term_dpp(const double (&x)[BS], cons
     if constexpr ((E & 3) == (BACKWARD ? 0 : 3) || last_of_group) __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int BS, bool BACKWARD, int MIX, bool PACKED, int SP, int... I>
+template <int BS, bool BACKWARD, bool PACKED, int SP, int... I>
 __device__ __forceinline__ void dense_exact_terms_dpp(const double (&x)[BS], const double *M, const int (&lb)[4], const double (&lv)[4],
                                                       double (&nxt)[4], double &acc, std::integer_sequence<int, I...>) {
     // the reference's order: ascending columns forward, descending (in sweep numbering) backward
-    (dense_exact_term_dpp<BS, BACKWARD, MIX, PACKED, SP, (BACKWARD ? SP - 1 - I : I)>(x, M, lb, lv, nxt, acc), ...);
+    (dense_exact_term_dpp<BS, BACKWARD, PACKED, SP, (BACKWARD ? SP - 1 - I : I)>(x, M, lb, lv, nxt, acc), ...);
 }
 
 // sweep row SP: cur = its L values (lane l: entry 16 g + (l & 15) of the row's terms), dv its diagonal; requests row SP + 1
-template <int BS, bool BACKWARD, int MIX, bool PACKED, int SP>
+template <int BS, bool BACKWARD, bool PACKED, int SP>
 __device__ __forceinline__ void dense_exact_row_dpp(double (&x)[BS], const double *M, const int (&lb)[4], const double *D, const double (&cur)[4],
                                                     double (&nxt)[4], const double dv, double &dnext) {
     constexpr int NS = SP + 1;
@@ -1608,7 +1502,7 @@ __device__ __forceinline__ void dense_exact_row_dpp(double (&x)[BS], const doubl
         dnext = D[xl_diag<BS, BACKWARD, PACKED>(NS)];
     }
     double acc = x[BACKWARD ? BS - 1 - SP : SP];
-    dense_exact_terms_dpp<BS, BACKWARD, MIX, PACKED, SP>(x, M, lb, cur, nxt, acc, std::make_integer_sequence<int, SP>{});
+    dense_exact_terms_dpp<BS, BACKWARD, PACKED, SP>(x, M, lb, cur, nxt, acc, std::make_integer_sequence<int, SP>{});
     double xr = acc / dv;
     // the row's arithmetic is pure: nothing but its data dependences holds it in place, and the instruction selector sank
     // whole rows of it behind the moves of later rows (256 VGPRs and spills at blocks of 16).  An empty volatile asm that
@@ -1618,15 +1512,15 @@ __device__ __forceinline__ void dense_exact_row_dpp(double (&x)[BS], const doubl
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int BS, bool BACKWARD, int MIX, bool PACKED, int... SP>
+template <int BS, bool BACKWARD, bool PACKED, int... SP>
 __device__ __forceinline__ void dense_exact_rows_dpp(double (&x)[BS], const double *M, const int (&lb)[4], const double *D,
                                                      std::integer_sequence<int, SP...>) {
     double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};   // L values of the even / odd sweep rows
     double da = D[xl_diag<BS, BACKWARD, PACKED>(0)], db = 1.0;           // and their diagonals
-    (dense_exact_row_dpp<BS, BACKWARD, MIX, PACKED, SP>(x, M, lb, D, (SP & 1) ? b : a, (SP & 1) ? a : b, (SP & 1) ? db : da, (SP & 1) ? da : db), ...);
+    (dense_exact_row_dpp<BS, BACKWARD, PACKED, SP>(x, M, lb, D, (SP & 1) ? b : a, (SP & 1) ? a : b, (SP & 1) ? db : da, (SP & 1) ? da : db), ...);
 }
 
-template <int BS, bool BACKWARD, int MIX, bool PACKED>
+template <int BS, bool BACKWARD, bool PACKED>
 __device__ __forceinline__ void dense_exact_pass_dpp(double (&x)[BS], const double *M, const double *D, const int lane) {
     const int k = lane & 15;
     int lb[4];
@@ -1635,102 +1529,16 @@ __device__ __forceinline__ void dense_exact_pass_dpp(double (&x)[BS], const doub
         const int c = 16 * g + k < BS ? 16 * g + k : BS - 1;          // (lanes past the block's columns: any address inside the copy)
         lb[g] = !PACKED ? k : (!BACKWARD ? c * BS - c * (c - 1) / 2 - c : -k);
     }
-    dense_exact_rows_dpp<BS, BACKWARD, MIX, PACKED>(x, M, lb, D, std::make_integer_sequence<int, BS>{});
+    dense_exact_rows_dpp<BS, BACKWARD, PACKED>(x, M, lb, D, std::make_integer_sequence<int, BS>{});
 }
 
-// second launch-bound argument = waves per SIMD the register allocation must leave room for: without it the
-// scheduler spends 284-512 VGPRs on hoisted loads (one wave per SIMD, spills at BS = 32).  R = 2 (two right-hand sides
-// per lane, a task = a block x 128 right-hand sides): one wave per SIMD, 2 x BS unknowns in registers.
-template <int BS, int R, bool RING>
-__global__ __launch_bounds__(256, (RING || R == 2 ? 1 : 2)) void k_cholsol_dense_exact(const Tree *__restrict__ trees, int32_t ntrees,
-                                                             const int32_t *__restrict__ nodes,
-                                                             const int32_t *__restrict__ perm,
-                                                             const int32_t *__restrict__ f_ptr,
-                                                             const double *__restrict__ f_val,
-                                                             const int32_t *__restrict__ b_ptr,
-                                                             const double *__restrict__ b_val,
-                                                             const double *__restrict__ diagf,
-                                                             const double *__restrict__ diagb, double *B, int32_t nrhs,
-                                                             int32_t chunks) {
-    constexpr int NT = BS * (BS - 1) / 2;
-    constexpr int MSZ = ((NT + 127) / 128 * 128 > NT + BS) ? (NT + 127) / 128 * 128 : NT + BS;
-    __shared__ __attribute__((aligned(16))) double s_m[4][MSZ];
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t task = (int64_t)blockIdx.x * 4 + w;
-    if (task >= (int64_t)ntrees * chunks) return;          // chunks: groups of 64 R right-hand sides
-    const int32_t t = (int32_t)(task / chunks), h = (int32_t)(task % chunks);
-    const int32_t first = trees[t].first;
-    int32_t rhs[R], rhs_ld[R];
-    bool live[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        rhs[r] = (h * R + r) * 64 + lane;
-        live[r] = rhs[r] < nrhs;
-        rhs_ld[r] = live[r] ? rhs[r] : nrhs - 1;
-    }
-    double *M = s_m[w], *DG = s_m[w] + NT;   // DG overlaps the DMA overrun and is written after it
-    int32_t jrow = 0;
-    if (lane < BS) {
-        jrow = nodes[first + lane];
-        if (perm) jrow = perm[jrow];
-    }
-    double x[R][BS];
-#pragma unroll
-    for (int a = 0; a < BS; a++) {
-        const int32_t row = __builtin_amdgcn_readlane(jrow, a);
-#pragma unroll
-        for (int r = 0; r < R; r++) x[r][a] = B[(int64_t)row * nrhs + rhs_ld[r]];
-    }
-#pragma unroll
-    for (int pass = 0; pass < 2; pass++) {
-        const int32_t *ptr = pass ? b_ptr : f_ptr;
-        const double *val = pass ? b_val : f_val;    // b_val here is the row-reversed dense copy
-        const double *dg = pass ? diagb : diagf;
-        const int32_t base = ptr[first];
-        const double dv = lane < BS ? dg[first + lane] : 1.0;
-#pragma unroll
-        for (int k = 0; k < (NT + 127) / 128; k++)
-            __builtin_amdgcn_global_load_lds((csx_gptr)(val + base + k * 128 + 2 * lane), (csx_lptr)(M + k * 128), 16, 0,
-                                             0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane < BS) DG[lane] = dv;
-        __builtin_amdgcn_wave_barrier();
-        if (RING) {
-            if (pass == 0) dense_exact_pass<BS, false, R>(x, M, DG);
-            else dense_exact_pass<BS, true, R>(x, M, DG);
-        } else {
-            if (pass == 0) dense_exact_pass_rows<BS, false, R>(x, M, DG);
-            else dense_exact_pass_rows<BS, true, R>(x, M, DG);
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (!RING) {
-#pragma unroll
-            for (int a = 0; a < BS / 2; a++) {       // reverse: sweep order of the other pass / back to row order
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const double tmp = x[r][a];
-                    x[r][a] = x[r][BS - 1 - a];
-                    x[r][BS - 1 - a] = tmp;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < BS; a++) {
-        const int32_t row = __builtin_amdgcn_readlane(jrow, a);
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            if (live[r]) B[(int64_t)row * nrhs + rhs[r]] = x[r][a];
-    }
-}
-// The DPP form as a kernel of its own.  Its 158 VGPRs allow three waves per SIMD at blocks of 64, the LDS copy of the block
+// The kernel.  Its 158 VGPRs allow three waves per SIMD at blocks of 64, the LDS copy of the block
 // (16.6 KB) does not if every wave stages its own (4 x 16.6 KB per workgroup: two workgroups per CU).  Waves of a
 // workgroup that solve the SAME block for different right-hand sides share one copy: SHARE = blocks per workgroup
 // (4, 2 or 1), 4 / SHARE waves per block, each staging its share of the DMA; two workgroup barriers per pass.
 // PACKED (round 5; a plan on all the columns of L, equal blocks): f_val = L.x itself, block t at t BS (BS + 1) / 2 -- the block's
 // packed columns are copied ONCE and serve both passes (see xl_term); no programs, no diagonal arrays: the other pointers are unused.
-template <int BS, int SHARE, int MIX, bool PACKED>
+template <int BS, int SHARE, bool PACKED>
 __global__ __launch_bounds__(256, 3) void k_cholsol_dense_exact_dpp(const Tree *__restrict__ trees, int32_t ntrees,
                                                                     const int32_t *__restrict__ nodes, const int32_t *__restrict__ perm,
                                                                     const int32_t *__restrict__ f_ptr, const double *__restrict__ f_val,
@@ -1794,7 +1602,7 @@ __global__ __launch_bounds__(256, 3) void k_cholsol_dense_exact_dpp(const Tree *
                 __syncthreads();
             }
         }
-        dense_exact_pass_dpp<BS, pass == 1, MIX, PACKED>(x, M, DG, lane);
+        dense_exact_pass_dpp<BS, pass == 1, PACKED>(x, M, DG, lane);
     };
     run_pass(std::integral_constant<int, 0>{});
     run_pass(std::integral_constant<int, 1>{});
@@ -2595,30 +2403,29 @@ static int cholsol_exact_classes_build(CholPlan *P) {
 
 static int launch_exact_dpp(int BS, const Tree *trees, int32_t ntrees, const int32_t *nodes, const int32_t *perm, const int32_t *f_ptr,
                             const double *f_val, const int32_t *b_ptr, const double *dense_b, const double *diagk, const double *diagb,
-                            double *B, int32_t nrhs, bool mix, const double *packed_lx = nullptr) {
-    // packed_lx (with mix): L.x of a factor that is nothing but these equal blocks, block t at t BS (BS + 1) / 2 -- no programs needed
+                            double *B, int32_t nrhs, const double *packed_lx = nullptr) {
+    // packed_lx: L.x of a factor that is nothing but these equal blocks, block t at t BS (BS + 1) / 2 -- no programs needed
     hipStream_t s = ctx().stream;
     const int32_t chunks = (nrhs + 63) / 64;
     const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
     const int64_t groups = ((int64_t)ntrees + share - 1) / share * (chunks / (4 / share));
     const dim3 grid((unsigned)groups);
     if (packed_lx) f_val = packed_lx;
-#define CSX_DPP_X(BS_, SH, MX, PK)                                                                                                     \
-    hipLaunchKernelGGL((k_cholsol_dense_exact_dpp<BS_, SH, MX, PK>), grid, dim3(256), 0, s, trees, ntrees, nodes, perm, f_ptr, f_val, \
+#define CSX_DPP_X(BS_, SH, PK)                                                                                                     \
+    hipLaunchKernelGGL((k_cholsol_dense_exact_dpp<BS_, SH, PK>), grid, dim3(256), 0, s, trees, ntrees, nodes, perm, f_ptr, f_val, \
                        b_ptr, dense_b, diagk, diagb, B, nrhs, chunks)
-#define CSX_DPP_S(BS_, MX, PK)                      \
-    if (share == 1) CSX_DPP_X(BS_, 1, MX, PK);      \
-    else if (share == 2) CSX_DPP_X(BS_, 2, MX, PK); \
-    else CSX_DPP_X(BS_, 4, MX, PK)
-#define CSX_DPP_V(BS_)                                \
-    if (mix && packed_lx) { CSX_DPP_S(BS_, 1, true); } \
-    else if (mix) { CSX_DPP_S(BS_, 1, false); }        \
-    else { CSX_DPP_S(BS_, 0, false); }
+#define CSX_DPP_S(BS_, PK)                      \
+    if (share == 1) CSX_DPP_X(BS_, 1, PK);      \
+    else if (share == 2) CSX_DPP_X(BS_, 2, PK); \
+    else CSX_DPP_X(BS_, 4, PK)
+#define CSX_DPP_V(BS_)                    \
+    if (packed_lx) { CSX_DPP_S(BS_, true); } \
+    else { CSX_DPP_S(BS_, false); }
     switch (BS) {
         case 8: CSX_DPP_V(8); break;
         case 16: CSX_DPP_V(16); break;
         case 32: CSX_DPP_V(32); break;
-        case 48: { CSX_DPP_S(48, 1, false); } break;      // (the padded size classes only: programs, the default mix)
+        case 48: { CSX_DPP_S(48, false); } break;      // (the padded size classes only: programs)
         default: CSX_DPP_V(64); break;
     }
 #undef CSX_DPP_V
@@ -2641,7 +2448,7 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
                 const CholPlan::ExactClass &X = P->xc[c];
                 if (X.count > 0)
                     CSX_TRY(launch_exact_dpp(kBS[c], X.trees, X.count, X.nodes, nullptr, X.f_ptr, X.f_val, X.b_ptr, X.dense_b, X.diagk,
-                                             X.diagb, B, nrhs, true));
+                                             X.diagb, B, nrhs));
             }
             return CSX_OK;
         }
@@ -2663,9 +2470,8 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
             // ... unless the kernel asked for takes L.x as it is: the matrix cores (W tiles beside it), and -- round 5 -- the
             // default exact kernel, which copies the block's packed columns to LDS once for both passes
             const bool cores = P->dense_bs && P->relaxed && P->frag_f && ctx().opt.cholsol_dense_blocks;
-            const int wantv = ctx().opt.cholsol_exact_variant;
             const bool lx_aligned = (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0;      // (the copies to LDS move 16 bytes a lane)
-            const bool packed_exact = P->dense_bs && !P->relaxed && ctx().opt.cholsol_dense_blocks && !(wantv >= 1 && wantv <= 6 && wantv != 5) && lx_aligned;
+            const bool packed_exact = P->dense_bs && !P->relaxed && ctx().opt.cholsol_dense_blocks && lx_aligned;
             if (!cores && !packed_exact && !P->f_val) CSX_TRY(cholsol_plan_clique(P, P->dense_bs));
             if (P->clique_zero_pivot) return CSX_EZEROPIVOT;
             if (!ctx().opt.cholsol_dense_blocks) CSX_TRY(cholsol_clique_local(P));
@@ -2676,51 +2482,14 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
         // Forests of dense blocks: the default (exact) order runs the substitution kernel that keeps the reference's
         // operations and their order; the rounding-equal order the FMA / matrix-core kernels.
         if (P->dense_bs && !P->relaxed && ctx().opt.cholsol_dense_blocks) {
-            // Variants ("cholsol.exact_variant"; measurements on G-spd, 5M rows, 128 right-hand sides, in
-            // profiles/r03_ablation.md section 3): 0 / 5 = the L values by DPP row broadcast, one term in four by an LDS
-            // broadcast read (the default for every block size: 4.6 - 4.8 / 3.0 / 2.2 / 2.0 ms at blocks of 64 / 32 / 16 / 8);
-            // 6 = by DPP only; the LDS-broadcast forms they replaced: 1 = one fence per row / one right-hand side per
-            // lane, 2 = the L values through a ring of registers, 3 = rows / two per lane, 4 = ring / two per lane (two per
-            // lane only for blocks <= 32; at blocks of 32 these four compile to scratch).
-            const int want = ctx().opt.cholsol_exact_variant;
-            int variant = 5;
-            if (want >= 1 && want <= 6) variant = want;
-            if (variant >= 5) {
-                // the L values by DPP row broadcast: one right-hand side per lane; waves that solve the same block share its
-                // LDS copy (as many as divide the number of 64-wide chunks of right-hand sides)
-                // (a plan on all the columns of L -- `clique` -- hands the kernel L.x itself)
-                return launch_exact_dpp(P->dense_bs, P->trees, P->ntrees, P->tree_nodes, P->perm, P->f_ptr, P->f_val, P->b_ptr, P->dense_b,
-                                        P->diagk, P->diagb, B, nrhs, variant == 5,
-                                        P->clique && variant == 5 && (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0 ? P->L->x : nullptr);
-            }
-            if (P->dense_bs == 64 && variant > 2) variant -= 2;
-            if (nrhs <= 64 && variant > 2) variant -= 2;
-            const int R = variant > 2 ? 2 : 1;
-            const bool ring = variant == 2 || variant == 4;
-            const int32_t chunks = (nrhs + 64 * R - 1) / (64 * R);
-            const int64_t tasks = (int64_t)P->ntrees * chunks;
-            const dim3 grid((unsigned)((tasks + 3) / 4));
-#define CSX_DENSE_X(BS, RR, RG)                                                                                                 \
-    hipLaunchKernelGGL((k_cholsol_dense_exact<BS, RR, RG>), grid, dim3(256), 0, s, P->trees, P->ntrees, P->tree_nodes, P->perm, \
-                       P->f_ptr, P->f_val, P->b_ptr, P->dense_b, P->diagk, P->diagb, B, nrhs, chunks)
-#define CSX_DENSE_V(BS)                                \
-    if (variant == 1) CSX_DENSE_X(BS, 1, false);       \
-    else if (variant == 2) CSX_DENSE_X(BS, 1, true);   \
-    else if (variant == 3) CSX_DENSE_X(BS, 2, false);  \
-    else CSX_DENSE_X(BS, 2, true)
-            switch (P->dense_bs) {
-                case 8: CSX_DENSE_V(8); break;
-                case 16: CSX_DENSE_V(16); break;
-                case 32: CSX_DENSE_V(32); break;
-                default:
-                    if (variant == 1) CSX_DENSE_X(64, 1, false);
-                    else CSX_DENSE_X(64, 1, true);
-                    break;
-            }
-#undef CSX_DENSE_V
-#undef CSX_DENSE_X
-            CSX_LAUNCH_CHECK();
-            return CSX_OK;
+            // the L values by DPP row broadcast, one term in four by an LDS broadcast read (measurements on G-spd, 5M rows, 128
+            // right-hand sides, profiles/r03_ablation.md section 3: 4.6 - 4.8 / 3.0 / 2.2 / 2.0 ms at blocks of 64 / 32 / 16 / 8);
+            // one right-hand side per lane; waves that solve the same block share its LDS copy (as many as divide the number of
+            // 64-wide chunks of right-hand sides)
+            // (a plan on all the columns of L -- `clique` -- hands the kernel L.x itself)
+            return launch_exact_dpp(P->dense_bs, P->trees, P->ntrees, P->tree_nodes, P->perm, P->f_ptr, P->f_val, P->b_ptr, P->dense_b,
+                                    P->diagk, P->diagb, B, nrhs,
+                                    P->clique && (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0 ? P->L->x : nullptr);
         }
         if (P->dense_bs && P->relaxed && ctx().opt.cholsol_dense_blocks) {
             const int32_t chunks = (nrhs + 63) / 64;

@@ -587,20 +587,17 @@ const OptSlot kOptSlots[] = {
     {"gaxpy.keys24", &Options::gaxpy_keys24, 0},         {"gaxpy.tune_shape", &Options::gaxpy_tune_shape, 0},
     {"tri.row_waves", &Options::tri_row_waves, 0},       {"tri.push", &Options::tri_push, 0},
     {"tri.levels_where", &Options::tri_levels_where, 3}, {"tri.supernodes", &Options::tri_supernodes, 5},
-    {"spgemm.ordered", &Options::spgemm_ordered, 0},     {"spgemm.chunks", &Options::spgemm_chunks, 4},
-    {"lu.etree", &Options::lu_etree, 5},                 {"tri.graph", &Options::tri_graph, 6},
-    {"sort.short_keys", &Options::sort_short_keys, 0},   {"chol.clique", &Options::chol_clique, 0},
-    {"chol.forest", &Options::chol_forest, 0},           {"chol.exact", &Options::chol_exact, 0},
-    {"tri.host_chains", &Options::tri_host_chains, 0},
-                    {"cholsol.exact_variant", &Options::cholsol_exact_variant, 4},
+    {"spgemm.ordered", &Options::spgemm_ordered, 0},     {"lu.etree", &Options::lu_etree, 5},
+    {"tri.graph", &Options::tri_graph, 6},               {"sort.short_keys", &Options::sort_short_keys, 0},
+    {"chol.clique", &Options::chol_clique, 0},           {"chol.forest", &Options::chol_forest, 0},
+    {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
 };
 int normalise(int kind, int value) {
     switch (kind) {
     case 0: return value != 0;
     case 1: return (value == 0 || value == 2) ? value : 1;
-    case 2: return (value == 32 || value == -16 || value == -32) ? value : 16;   // negative: two launches per panel
+    case 2: return value == 32 ? 32 : 16;
     case 3: return (value == 1 || value == 2) ? value : 0;
-    case 4: return value < 0 ? 0 : (value > 64 ? 64 : value);
     case 5: return (value == 0 || value == 2) ? value : 1;
     case 6: return (value == 0 || value == 1) ? value : 2;
     }

@@ -159,9 +159,6 @@ struct Options {
     int tri_supernodes = 1;           // cholsol: supernodal forward / backward solves on factors with supernodes (0 never, 1 yes,
                                       // 2 yes but the triangles by substitution out of LDS instead of on the matrix cores)
     int spgemm_ordered = 0;           // cs_multiply: sum every entry's products in the reference's order (bit-identical x)
-    int spgemm_chunks = 1;            // cs_multiply: column chunks whose compaction overlaps the next chunk's hashing on a second stream
-                                      // (1 = off, the default: measured slower, profiles/r03_ablation.md section 2)
-    int cholsol_exact_variant = 0;    // exact dense-block cholsol: 0 = the measured choice per block size, 1 - 6 force a variant (tests, ablation)
     int lu_etree = 0;                 // cs_lu of one connected matrix on the device, columns scheduled by the column etree:
                                       // 0 never (the default since round 4: measured at best a tie with one host core, on the
                                       // shape it was made for -- profiles/r04_ablation.md), 1 for shallow trees with short

@@ -808,13 +808,13 @@ __global__ __launch_bounds__(256) void k_sg_hash2(int slots_, const int4 *__rest
 
 template <bool VALUES>
 static int launch_hash2(int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
-                        int32_t *tmp_i, double *tmp_x, int cap_per_cu = 8) {
+                        int32_t *tmp_i, double *tmp_x) {
     if (ncols <= 0) return CSX_OK;
     const size_t lds = (size_t)(slots + (slots & 1)) * (VALUES ? 16 : 8) + H2_MAXSEG * 4 + 64;
     auto kern = k_sg_hash2<VALUES>;
     CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256));
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(cap_per_cu, (160 * 1024) / (int64_t)(lds + 256)));
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(lds + 256)));
     const int64_t grid = std::min<int64_t>(ncols, (int64_t)ctx().cus * per_cu);
     const int abl = ablation_env("CSX_SG_ABL") ? std::atoi(ablation_env("CSX_SG_ABL")) : 0;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, ctx().stream, slots, info, ncols, A->p, A->i, A->x,
@@ -823,12 +823,9 @@ static int launch_hash2(int slots, const Csc *A, const Csc *B, const int4 *info,
     return CSX_OK;
 }
 
-// one wave per column: move its rows (and sums) from the product-order buffer to their place in C.  A column's length is
-// count[j] when `count` is given (the chunked path: the NEXT chunk's scan is rewriting Cp[j + 1] of a chunk's last column
-// while that chunk is compacted on the second stream), else Cp[j + 1] - Cp[j].
+// one wave per column: move its rows (and sums) from the product-order buffer to their place in C
 __global__ __launch_bounds__(256) void k_sg_compact(const uint32_t *__restrict__ cols, int32_t ncols,
                                                     const int32_t *__restrict__ toff, const int32_t *__restrict__ Cp,
-                                                    const int32_t *__restrict__ count,
                                                     const int32_t *__restrict__ tmp_i, const double *__restrict__ tmp_x,
                                                     int32_t *__restrict__ Ci, double *__restrict__ Cx) {
     const int lane = threadIdx.x & 63;
@@ -836,7 +833,7 @@ __global__ __launch_bounds__(256) void k_sg_compact(const uint32_t *__restrict__
     if (w >= ncols) return;
     const int32_t j = (int32_t)cols[w];
     const int64_t src = toff[j], dst = Cp[j];
-    const int32_t cnt = count ? count[j] : Cp[j + 1] - Cp[j];
+    const int32_t cnt = Cp[j + 1] - Cp[j];
     int32_t k = lane;
     for (; k + 192 < cnt; k += 256) {   // four loads of each array in flight per lane
         int32_t ri[4];
@@ -867,14 +864,14 @@ static size_t h1_lds_bytes(int slots, bool values) {   // slots = 3/2 * (product
 
 template <bool VALUES>
 static int launch_hash1(int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
-                        int32_t *tmp_i, double *tmp_x, int cap_per_cu = 8) {
+                        int32_t *tmp_i, double *tmp_x) {
     if (ncols <= 0) return CSX_OK;
     const size_t lds = h1_lds_bytes(slots, VALUES);
     auto kern = k_sg_hash1<VALUES>;
     CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 160 * 1024 - 256));
     // exactly the workgroups that are resident at once (LDS-limited, at most 8 x 4 waves per CU)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(cap_per_cu, (160 * 1024) / (int64_t)(lds + 256)));
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(lds + 256)));
     const int64_t grid = std::min<int64_t>(ncols, (int64_t)ctx().cus * per_cu);
     const int abl = ablation_env("CSX_SG_ABL") ? std::atoi(ablation_env("CSX_SG_ABL")) : 0;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, ctx().stream, slots, info, ncols, A->p, A->i, A->x,
@@ -927,151 +924,6 @@ static int run_bins(const Csc *A, const Csc *B, const uint32_t *cols, const int3
         if (hashed)
             for (slots = 1024; slots < 2 * sg_hash_limit(hb); slots <<= 1) {}
         CSX_TRY((launch_bin<NUMERIC, VALUES>(kind, slots, A, B, cols + bin_ptr[b], nb, count, Cp, Ci, Cx, g_tmin, g_val)));
-    }
-    return CSX_OK;
-}
-
-// ---- chunked one-pass path (opt-in, spgemm.chunks >= 2) ----------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sg_chunk_key(int32_t n, int32_t chunk_cols, const uint32_t *__restrict__ bin,
-                                                      uint32_t *__restrict__ key) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) key[j] = (uint32_t)(j / chunk_cols) * (uint32_t)SG_NBINS + bin[j];
-}
-
-// Cp[c0 .. c1] (a chunk's exclusive scan, starting at 0) += base[cur]; base[cur ^ 1] = base[cur] + the chunk's total
-__global__ __launch_bounds__(256) void k_sg_add_base(int32_t *__restrict__ Cp, int32_t c0, int32_t c1,
-                                                     unsigned long long *base, int cur) {
-    const int64_t j = c0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j > c1) return;
-    const unsigned long long b = base[cur], v = b + (unsigned long long)Cp[j];
-    Cp[j] = (int32_t)(v > 0x7FFFFFFFull ? 0x7FFFFFFFull : v);
-    if (j == c1) base[cur ^ 1] = v;
-}
-
-// The chunked form of the one-pass path: columns in ascending chunks; while chunk c + 1 is hashed (an instruction- and
-// LDS-bound kernel that leaves the memory system mostly idle) chunk c -- its counts scanned behind chunk c - 1's end, which
-// IS C.p for those columns -- is compacted into C.i / C.x on a second stream (a pure copy).  C.i / C.x are allocated for
-// the upper bound "one entry per product" (the reference grows C the same way, csparse.py:1630-1631, and trims at the
-// end).  MEASURED SLOWER than the unchunked path on S (1M x 1M, 32 per column: 14.9 ms unchunked; 15.1 / 15.4 / 16.2 ms
-// with 2 / 4 / 8 chunks; with the hash kernels held to three workgroups per CU so that the copy's waves find registers,
-// 16.1 - 16.6 ms): the hash kernel fills the vector registers of every SIMD (122 VGPRs x 4 waves), so the copy's waves
-// only get in at a chunk's tail, and every chunk adds the ramp and tail of five persistent launches (one per bin).  Kept
-// as an option for matrices whose columns sit in one bin; off by default (profiles/r03_ablation.md, section 2).
-// Every non-empty column is in a hash bin (the caller checks).  bin / colid / hprod / count as multiply_device made them.
-static hipStream_t g_sg_stream = nullptr;
-#ifndef SG_OVERLAP_CAP
-#define SG_OVERLAP_CAP 4
-#endif
-
-static int multiply_chunked(const Csc *A, const Csc *B, Csc *C, bool values, const uint32_t *bin, const uint32_t *colid,
-                            const int32_t *hprod, unsigned long long P, int32_t *count) {
-    hipStream_t s = ctx().stream;
-    const int32_t n = B->n;
-    const size_t per = values ? 12 : 4;
-    int64_t nchunks = std::max(2, std::min(ctx().opt.spgemm_chunks, 64));   // opt-in (spgemm.chunks >= 2)
-    nchunks = std::min<int64_t>(nchunks, std::max<int64_t>(2, n / 2048));
-    const int32_t chunk_cols = (int32_t)(((int64_t)n + nchunks - 1) / nchunks);
-    nchunks = ((int64_t)n + chunk_cols - 1) / chunk_cols;
-    if (!g_sg_stream) CSX_HIP(hipStreamCreateWithFlags(&g_sg_stream, hipStreamNonBlocking));
-    DevScope tmp;
-    int32_t *toff = nullptr, *ptr_d = nullptr, *tmp_i = nullptr;
-    uint32_t *key = nullptr, *skey = nullptr, *scol = nullptr;
-    int4 *info = nullptr;
-    double *tmp_x = nullptr;
-    unsigned long long *base = nullptr;
-    CSX_TRY(tmp.alloc(&toff, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&key, (size_t)n));
-    CSX_TRY(tmp.alloc(&skey, (size_t)n));
-    CSX_TRY(tmp.alloc(&scol, (size_t)n));
-    CSX_TRY(tmp.alloc(&info, (size_t)n));
-    CSX_TRY(tmp.alloc(&base, 2));
-    const int32_t nkeys = (int32_t)nchunks * SG_NBINS;
-    CSX_TRY(tmp.alloc(&ptr_d, (size_t)nkeys + 1));
-    int64_t tot = 0;
-    CSX_TRY(scan_exclusive_i32(hprod, toff, n, &tot));
-    hipLaunchKernelGGL(k_sg_chunk_key, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, chunk_cols, bin, key);
-    CSX_TRY(stable_sort_by_key(key, colid, nullptr, n, (uint32_t)nkeys, skey, scol, nullptr));
-    CSX_TRY(boundaries_from_sorted(skey, n, nkeys, ptr_d));
-    std::vector<int32_t> ptr((size_t)nkeys + 1);
-    CSX_HIP(hipMemcpyAsync(ptr.data(), ptr_d, ptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CSX_HIP(hipMemsetAsync(base, 0, 2 * sizeof(unsigned long long), s));
-    CSX_TRY(tmp.alloc(&tmp_i, (size_t)P));
-    if (values) CSX_TRY(tmp.alloc(&tmp_x, (size_t)P));
-    hipLaunchKernelGGL(k_sg_colinfo, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, scol, n, B->p, toff, info);
-    // C.i / C.x for the upper bound (one entry per product); C.p is written chunk by chunk
-    int32_t *Ci = nullptr;
-    double *Cx = nullptr;
-    CSX_TRY(dalloc(&Ci, (size_t)P));
-    C->i = Ci;
-    if (values) {
-        CSX_TRY(dalloc(&Cx, (size_t)P));
-        C->x = Cx;
-    }
-    CSX_HIP(hipStreamSynchronize(s));
-    std::vector<hipEvent_t> ev((size_t)nchunks, nullptr);
-    hipEvent_t done = nullptr;
-    int st = CSX_OK;
-    for (auto &e : ev)
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) st = CSX_ERUNTIME;
-    if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) st = CSX_ERUNTIME;
-    for (int64_t c = 0; c < nchunks && st == CSX_OK; c++) {
-        const int32_t *pc = ptr.data() + c * SG_NBINS;
-        for (int hb = 0; hb < SG_HASH_BINS && st == CSX_OK; hb++) {
-            const int32_t lo = pc[SG_BIN_HASH0 + hb], nb = pc[SG_BIN_HASH0 + hb + 1] - lo;
-            const int slots = sg_hash_limit(hb) * 3 / 2;
-            st = values ? launch_hash1<true>(slots, A, B, info + lo, nb, count, tmp_i, tmp_x, SG_OVERLAP_CAP)
-                        : launch_hash1<false>(slots, A, B, info + lo, nb, count, tmp_i, nullptr, SG_OVERLAP_CAP);
-        }
-        for (int hb = 0; hb < SG_NARROW_BINS && st == CSX_OK; hb++) {
-            const int32_t lo = pc[SG_BIN_NARROW0 + hb], nb = pc[SG_BIN_NARROW0 + hb + 1] - lo;
-            const int slots = sg_hash_limit(hb) * 3 / 2;
-            st = values ? launch_hash2<true>(slots, A, B, info + lo, nb, count, tmp_i, tmp_x, SG_OVERLAP_CAP)
-                        : launch_hash2<false>(slots, A, B, info + lo, nb, count, tmp_i, nullptr, SG_OVERLAP_CAP);
-        }
-        if (st != CSX_OK) break;
-        const int32_t c0 = (int32_t)(c * chunk_cols), c1 = (int32_t)std::min<int64_t>(n, (c + 1) * (int64_t)chunk_cols);
-        st = scan_exclusive_i32(count + c0, C->p + c0, c1 - c0, nullptr);
-        if (st != CSX_OK) break;
-        hipLaunchKernelGGL(k_sg_add_base, dim3((unsigned)((c1 - c0 + 256) / 256)), dim3(256), 0, s, C->p, c0, c1, base, (int)(c & 1));
-        if (hipEventRecord(ev[(size_t)c], s) != hipSuccess || hipStreamWaitEvent(g_sg_stream, ev[(size_t)c], 0) != hipSuccess) {
-            st = CSX_ERUNTIME;
-            break;
-        }
-        const int32_t lo = pc[SG_BIN_HASH0], nh = pc[SG_BIN_NARROW0 + SG_NARROW_BINS] - lo;
-        if (nh > 0)
-            hipLaunchKernelGGL(k_sg_compact, dim3((unsigned)(((int64_t)nh + 3) / 4)), dim3(256), 0, g_sg_stream, scol + lo, nh, toff,
-                               C->p, count, tmp_i, tmp_x, Ci, Cx);
-    }
-    // the context's stream continues behind the last copy (and nothing is freed before it has finished)
-    if (hipEventRecord(done, g_sg_stream) != hipSuccess || hipStreamWaitEvent(s, done, 0) != hipSuccess) st = CSX_ERUNTIME;
-    unsigned long long total = 0;
-    if (hipMemcpyAsync(&total, base + (nchunks & 1), sizeof total, hipMemcpyDeviceToHost, s) != hipSuccess) st = CSX_ERUNTIME;
-    if (hipStreamSynchronize(g_sg_stream) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
-    if (done) (void)hipEventDestroy(done);
-    if (st == CSX_OK && hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
-    CSX_TRY(st);
-    if (total > 0x7FFFFFFFull) {
-        set_error("cs_multiply: the product has %llu entries (int32 indices)", total);
-        return CSX_EINVAL;
-    }
-    C->nnz = (int32_t)total;
-    // Much of the capacity unused (many products per entry): move to arrays of the exact size, as cs_sprealloc(C, 0) does
-    if ((P - total) * per > ((size_t)256 << 20) && P > total + total / 4) {
-        int32_t *Ci2 = nullptr;
-        double *Cx2 = nullptr;
-        CSX_TRY(dalloc(&Ci2, (size_t)total));
-        CSX_HIP(hipMemcpyAsync(Ci2, Ci, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        if (values) {
-            CSX_TRY(dalloc(&Cx2, (size_t)total));
-            CSX_HIP(hipMemcpyAsync(Cx2, Cx, (size_t)total * sizeof(double), hipMemcpyDeviceToDevice, s));
-        }
-        CSX_HIP(hipStreamSynchronize(s));
-        dfree(Ci);
-        dfree(Cx);
-        C->i = Ci2;
-        C->x = Cx2;
     }
     return CSX_OK;
 }
@@ -1449,19 +1301,6 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
         pool_stats(&idle_b, nullptr);   // idle blocks of the caching allocator are reusable
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < (free_b + idle_b) / 3) onepass = true;
     }
-    // all non-empty columns hashed, and a product-order buffer far bigger than the Infinity Cache: take the columns in chunks
-    const bool chunked = st == CSX_OK && onepass && ctx().opt.spgemm_chunks > 1 &&
-                         bin_ptr[SG_BIN_DENSE + 1] == bin_ptr[SG_BIN_DENSE] && bin_ptr[SG_BIN_GLOBAL + 1] == bin_ptr[SG_BIN_GLOBAL] &&
-                         n >= 4096 &&
-                         big[1] * (values ? 24 : 8) < (size_t)0x7FFFFFF0ull * 24;
-    if (chunked) {
-        st = multiply_chunked(A, B, C, values, bin, colid, hprod, big[1], count);
-        if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-        for (void *q : {(void *)hprod, (void *)bin, (void *)colid, (void *)sbin, (void *)scol, (void *)bin_ptr_d, (void *)count,
-                        (void *)too_big})
-            dfree(q);
-        return st;
-    }
     if (st == CSX_OK && onepass) {
         st = dalloc(&toff, (size_t)n + 1);
         int64_t tot = 0;
@@ -1511,7 +1350,7 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
     }
     if (st == CSX_OK && onepass) {
         hipLaunchKernelGGL(k_sg_compact, dim3((unsigned)(((int64_t)nhash + 3) / 4)), dim3(256), 0, s, scol + hash_lo,
-                           nhash, toff, C->p, nullptr, tmp_i, tmp_x, C->i, C->x);
+                           nhash, toff, C->p, tmp_i, tmp_x, C->i, C->x);
         if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
     }
     if (st == CSX_OK) {

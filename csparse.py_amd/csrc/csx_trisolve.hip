@@ -962,9 +962,9 @@ __global__ __launch_bounds__(256) void k_group_caps(int32_t ncomp, int cpw, cons
 // simply runs the reference's column loop: for L and U (column push) the column's entries are spread over the
 // threads (distinct rows, each x[i] still receives its updates in ascending / descending column order), one
 // workgroup barrier per column, the next column's entries already in flight; for L' and U' (column gather) one wave
-// forms a column's products, one per lane, and lane 0 subtracts them in storage order while they rotate towards it
-// (k_tri_colchain).  Bit-identical, every kind.  Right-hand sides are independent workgroups.  L' on bcsstk16: 256
-// threads with the products in LDS and one lane subtracting 9.0 ms; one wave lifting products out with v_readlane
+// forms a column's products, one per lane, and they are subtracted in storage order (k_tri_colchain).  Bit-identical,
+// every kind.  Right-hand sides are independent workgroups.  L' on bcsstk16: 256 threads with the products in LDS and
+// one lane subtracting 9.0 ms; one wave lifting products out with v_readlane
 // 9.6 ms, with the v_readlane of the next eight issued ahead 7.7; products rotated by DPP 7.1; entries requested three
 // columns ahead instead of one 6.6 ms.
 #pragma clang fp contract(off)
@@ -973,38 +973,15 @@ constexpr int TC_MAX_N = 15360;
 constexpr int TR64_RUN = 64, TR64_RUN_MIN = 8;   // levels per two-phase run of narrow levels; shorter runs: one phase
 constexpr int TRW_MAX_RHS = 4, TRW_MIN_ROW = 24;   // a wave per row: at most so many right-hand sides, rows at least so long on average
 
-// The gather kinds (L', U') on ONE wave: every lane forms one product of the column, then lane 0 subtracts them in
-// storage order while the products rotate towards it through the wave (tch_chain) -- no barrier and no LDS round trip
-// for the products between columns.  Lanes past the end of the column hold +0.0, and x - (+0.0) = x for every x, so
-// the chain runs in blocks of eight without a test per term.
-// (Kept for reference and A/B timing: the kernels now hand the products over through LDS, tch_chain_lds below --
-// bcsstk16 L' 6.6 -> 5.9 ms, a band of 200: 3.1 -> 1.8 us per column; what is left is the dependent fp64 subtraction,
-// ~19 cycles per term.)
-__device__ __forceinline__ double tch_chain(double acc, double p, int cnt) {
-    // Only lane 0's chain is the result.  The products are rotated through the wave, one lane per step (DPP
-    // wave_rol:1: lane l receives lane l + 1), so lane 0 meets product 0, 1, 2, ... in order; the two rotations of a
-    // step do not depend on the subtraction, which is the only chain.  (Lifting the products out with v_readlane
-    // costs ~10 cycles per scalar write, 30 cycles per term; rotating in place 26; eight rotations issued ahead into
-    // registers of their own 34: a wave_rol is a long instruction and eight in a row serialise.)
-    int plo = __double2loint(p), phi = __double2hiint(p);
-#pragma unroll
-    for (int g = 0; g < 64; g += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            acc = acc - __hiloint2double(phi, plo);
-            plo = __builtin_amdgcn_update_dpp(plo, plo, 0x134, 0xf, 0xf, false);
-            phi = __builtin_amdgcn_update_dpp(phi, phi, 0x134, 0xf, 0xf, false);
-        }
-        if (g + 8 >= cnt) break;   // uniform
-    }
-    return acc;
-}
-
-// The same chain with the products handed to lane 0 through LDS instead of the DPP rotation: every lane stores its
-// product (one ds_write_b64), then ALL lanes read the products back two at a time from the same addresses (broadcast
-// reads, 16 products per block, the next block requested before this block's subtractions), so the only serial chain
-// is the subtraction itself.  buf: 64 doubles private to the wave, 16-byte aligned.  LDS operations of one wave complete
-// in order, so neither the read-back nor the next call's store needs a barrier.
+// The gather kinds (L', U') on ONE wave: every lane forms one product of the column and stores it to LDS (one
+// ds_write_b64), then ALL lanes read the products back two at a time from the same addresses (broadcast reads, 16
+// products per block, the next block requested before this block's subtractions) and subtract them in storage order,
+// so the only serial chain is the subtraction itself (~19 cycles per term) -- no barrier between columns.  Lanes past
+// the end of the column hold +0.0, and x - (+0.0) = x for every x, so the chain runs in blocks of 16 without a test per
+// term.  (Handing the products to lane 0 by a DPP rotation through the wave instead, the form this replaced: bcsstk16
+// L' 6.6 ms against 5.9, a band of 200 3.1 us per column against 1.8.)  buf: 64 doubles private to the wave, 16-byte
+// aligned.  LDS operations of one wave complete in order, so neither the read-back nor the next call's store needs a
+// barrier.
 __device__ __forceinline__ double tch_chain_lds(double acc, double p, int cnt, double *buf, int lane) {
     buf[lane] = p;
     const double2 *b2 = reinterpret_cast<const double2 *>(buf);

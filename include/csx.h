@@ -77,18 +77,16 @@ int csx_mem_info(int64_t *cached_bytes, int64_t *live_bytes, int64_t *device_fre
  * "tri.chain_walker", "tri.components", "tri.columns", "tri.push", "tri.row_waves", "gaxpy.keys24"; "gaxpy.tune_shape" (default 0); "tri.levels_where" (default 0: level
  * analysis of a triangular plan on the device for big factors and on the host for small ones; 1 = host, 2 = device);
  * "chol.wband" (blocked dense-band cs_chol for chain-like factors: default 1 = for half-widths above 80, 0 = never,
- * 2 = whenever the tree is chain-like) and "chol.wband_nb" (columns per step: 16 (default) or 32; negative: two
- * launches per step instead of one); "chol.supernodes" (default 1); "pool.limit_mb" (cap of the device-memory cache in MB,
+ * 2 = whenever the tree is chain-like) and "chol.wband_nb" (columns per step: 16 (default) or 32; any other value
+ * reads back as 16); "chol.supernodes" (default 1); "pool.limit_mb" (cap of the device-memory cache in MB,
  * 0 = the default quarter of the device).  Round 3: "tri.supernodes" (supernodal schedule of a cholsol plan in the
  * rounding-equal order: 1 = yes, triangles on the matrix cores where their guard allows (default); 2 = yes, triangles by
  * substitution out of LDS, no relaxed supernodes; 0 = never), "tri.graph" (the launches of a supernodal solve captured
  * into a hipGraph and replayed while the block of right-hand sides stays in place: 2 (default) = when a solve is more than
  * 256 launches and the block has been the block of the two solves before it as well (round 5; round 4 captured on the second
  * solve of a block, which cost more than it saved), 1 = always, 0 = never),
- * "cholsol.exact_variant" (the exact dense-block kernel: 0 = default = 5: L values by DPP row broadcast, one term in four
- * by an LDS broadcast read; 6: by DPP only; 1 - 4: the LDS-broadcast forms), "spgemm.ordered" (default 0; 1 = cs_multiply
- * sums every entry's products in the reference's order: bit-identical values, about twenty times the time),
- * "spgemm.chunks" (default 1; >= 2: hash and compaction of column chunks on two streams -- measured slower),
+ * "spgemm.ordered" (default 0; 1 = cs_multiply sums every entry's products in the reference's order: bit-identical
+ * values, about twenty times the time),
  * "sort.short_keys" (default 1: a transpose with values carries 16-bit keys between its radix passes where the matrix allows),
  * "lu.etree" (cs_lu inside one connected matrix by levels of the column elimination tree: 0 = never (default since round
  * 4: at best a tie with one host core), 1 = shallow trees with short columns, 2 = always).  Round 4:

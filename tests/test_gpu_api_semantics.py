@@ -189,3 +189,11 @@ def test_option_blocks_nest_and_restore_what_was_in_force(cs):
         assert get("tri.levels_where") == 0
     assert lib.csx_get_option(b"no.such.option", v) == _csx.EINVAL
     assert lib.csx_set_option(b"no.such.option", 1) == _csx.EINVAL
+    for retired in (b"cholsol.exact_variant", b"spgemm.chunks"):  # options of retired kernel variants are unknown names
+        assert lib.csx_set_option(retired, 1) == _csx.EINVAL
+        assert lib.csx_get_option(retired, v) == _csx.EINVAL
+    with _csx.option("chol.wband_nb", -16):                     # 16 or 32; anything else is 16
+        assert get("chol.wband_nb") == 16
+    with _csx.option("chol.wband_nb", 32):
+        assert get("chol.wband_nb") == 32
+    assert get("chol.wband_nb") == 16

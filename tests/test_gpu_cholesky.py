@@ -482,16 +482,16 @@ def _grid_laplacian(gx, gy, shift=0.01):
 
 
 @pytest.mark.parametrize("gx,gy,wband,nb", [(200, 31, 1, 16), (200, 31, 1, 32), (61, 59, 2, 16), (61, 59, 2, 32),
-                                            (200, 31, 1, -16), (61, 59, 2, -32), (300, 40, 1, 16),
-                                            (33, 17, 2, 32), (7, 80, 2, 16), (300, 2, 1, 32), (300, 2, 2, 16)])
+                                            (300, 40, 1, 16), (33, 17, 2, 32), (7, 80, 2, 16), (300, 2, 1, 32),
+                                            (300, 2, 2, 16)])
 def test_wide_band_chain_factor_blocked_in_a_dense_band_array(cs, gx, gy, wband, nb):
     """Natural-order grid Laplacians: chain elimination tree, band half-width gx.  Wider than the register window
     (gx = 200) the blocked dense-band kernels (csx_cholband.hip) take the factor by themselves; forced (wband = 2)
     they take narrow bands too.  Every element receives its updates in ascending column order, multiply and subtract
     rounded separately: the reference's operation sequence on a chain tree (csparse.py:598-612) -> L.x bit-identical
     to the plain-C oracle, for panel widths 16 and 32, sizes that are no multiple of the panel, and bands wider than
-    what is left of the matrix.  nb > 0: one launch per panel (the next panel factored while the previous one's update
-    of the rest of the window runs); nb < 0: two launches per panel."""
+    what is left of the matrix.  One launch per panel: the next panel factored while the previous one's update of the
+    rest of the window runs."""
     import _csx
     n, p, i, x = _grid_laplacian(gx, gy)
     A = cs.cs_spalloc(n, n, len(i), True, False)
@@ -533,7 +533,7 @@ def test_wide_band_kernels_on_bcsstk16(cs):
     parent, cp = CO.schol(n, p, i)
     Lp, Li, Lx = CO.chol(n, p, i, x, parent, cp)
     S = cs.cs_schol(0, C)
-    for nb in (16, 32, -16):
+    for nb in (16, 32):
         with _csx.option("chol.wband", 2), _csx.option("chol.wband_nb", nb):
             N = cs.cs_chol(C, S)
         assert np.asarray(N.L.x[:Lp[n]]).tobytes() == Lx.tobytes()
@@ -935,11 +935,10 @@ def test_supernodal_schedule_refuses_a_triangle_that_is_not_a_cholesky_factor(cs
 
 
 @pytest.mark.parametrize("bs", [8, 16, 32, 64])
-def test_exact_dense_block_kernel_variants_all_have_the_reference_bits(cs, bs):
-    """The default (exact) order on forests of dense blocks has six kernel variants (the L values by DPP row broadcast, with or
-    without one term in four by an LDS broadcast read -- the default is with -- or by LDS broadcast with one fence per row or through a register ring, one or two right-hand sides
-    per lane; "cholsol.exact_variant" forces one).  Each must be bit-identical to cs_lsolve + cs_ltsolve of the oracle, for 130
-    right-hand sides (two full groups and a partial one; a partial pair for the two-per-lane variants)."""
+def test_exact_dense_block_kernel_has_the_reference_bits(cs, bs):
+    """The default (exact) order on forests of dense blocks (the L values by DPP row broadcast, one term in four by an LDS
+    broadcast read) must be bit-identical to cs_lsolve + cs_ltsolve of the oracle, for 130 right-hand sides (two full
+    groups and a partial one)."""
     import _csx
     nblocks, k = 9, 130
     n = nblocks * bs
@@ -951,14 +950,12 @@ def test_exact_dense_block_kernel_variants_all_have_the_reference_bits(cs, bs):
     Lp, Li, Lx = CO.chol(n, Ap, Ai, Ax, parent, cp)
     B = synth.rhs(n, k, 3)
     ref = {r: CO.ltsolve(n, Lp, Li, Lx, CO.lsolve(n, Lp, Li, Lx, B[:, r])) for r in (0, 63, 64, 127, 128, 129)}
-    for variant in (0, 1, 2, 3, 4, 5, 6):
-        with _csx.option("cholsol.exact_variant", variant):
-            dB = cs.dvec(B)
-            assert F.solve(dB)
-            X = dB.numpy()
-        for r, v in ref.items():
-            assert X[:, r].tobytes() == v.tobytes(), (variant, r)
-    # the default (5: L values by DPP row broadcast) lets the waves that solve one block share its LDS copy: four, two or
+    dB = cs.dvec(B)
+    assert F.solve(dB)
+    X = dB.numpy()
+    for r, v in ref.items():
+        assert X[:, r].tobytes() == v.tobytes(), r
+    # the kernel lets the waves that solve one block share its LDS copy: four, two or
     # one block(s) per workgroup as the number of 64-wide groups of right-hand sides allows (130 -> 3 groups: four blocks,
     # 128 -> 2: two, 256 -> 4: one); 9 blocks leave the last workgroup partly empty in every case.  A right-hand side
     # with zeros and negative zeros in it: the products' signs of zero must come out as the reference's.
