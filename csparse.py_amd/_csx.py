@@ -65,6 +65,7 @@ _PROTOS = {
     "csx_ivec_download": [H, _i32p, C.c_int64],
     "csx_gaxpy": [H, H, H, C.c_int],
     "csx_gaxpy_prepare": [H, C.c_int],
+    "csx_gaxpy_block": [H, H, H, C.c_int32, C.c_int],
     "csx_transpose": [H, C.c_int, C.POINTER(H)],
     "csx_cumsum": [H, H, C.c_int64, C.POINTER(C.c_int64)],
     "csx_multiply": [H, H, C.POINTER(H)],

@@ -511,7 +511,8 @@ def cs_gaxpy(A, x, y, mode=None):
 
     Lists: y is updated in place with the reference's exact summation order.
     dvec x / y: stays on the device; `mode` picks the kernel (default: exact for
-    list calls, the matrix's best plan for device calls)."""
+    list calls, the matrix's best plan for device calls).  A dvec block with k > 1
+    is read as one flat vector here; gaxpy_block takes Y += A X for every column."""
     if not CS_CSC(A) or x is None or y is None:
         return False
     if not _meta(A)[1]:     # pattern only (asked of the device for a device-backed A: no download)
@@ -523,6 +524,49 @@ def cs_gaxpy(A, x, y, mode=None):
     with _Resident(A) as dA:
         _csx.check(_csx.lib().csx_gaxpy(dA.handle, dx.handle, dy.handle, mode), "csx_gaxpy")
     _write_back(yhost, dy, A.m)
+    return True
+
+
+def _block_in(v):
+    """dvec / ndarray / list -> (dvec, rows, k, host object to write back or None)."""
+    if isinstance(v, dvec):
+        return v, v.n, v.k, None
+    a = np.asarray(v)
+    if a.ndim not in (1, 2):
+        raise TypeError("gaxpy_block: blocks are 1-D vectors or 2-D row-major arrays")
+    return dvec(np.ascontiguousarray(a, dtype=np.float64)), a.shape[0], 1 if a.ndim == 1 else a.shape[1], v
+
+
+def gaxpy_block(A, X, Y, mode=None):
+    """Y = A*X + Y for every column of an n-by-k block X and m-by-k block Y (cs_gaxpy, csparse.py:1199-1213, applied
+    to each column), in one device call.  True on success; False for a non-CSC A, X or Y None, or unequal k.
+
+    X, Y: dvec blocks (dvec(n, k)), 2-D row-major float64 ndarrays, or 1-D vectors (k = 1: exactly cs_gaxpy).  Y is
+    updated in place (an ndarray or list Y is written back).  mode: GAXPY_EXACT (every column bit-identical to the
+    reference's cs_gaxpy on it) or GAXPY_AUTO (the fastest route, within rounding); default as cs_gaxpy's: exact
+    when Y is host memory or X is not a dvec, AUTO when both are dvec.  IndexError for blocks with too few rows."""
+    if not CS_CSC(A) or X is None or Y is None:
+        return False
+    if not _meta(A)[1]:     # pattern only
+        raise TypeError("'NoneType' object is not subscriptable")
+    if isinstance(Y, np.ndarray) and Y.dtype != np.float64:
+        raise TypeError("gaxpy_block: an ndarray Y must be float64")
+    dX, xrows, k, _ = _block_in(X)
+    dY, yrows, ky, yhost = _block_in(Y)
+    if k != ky:
+        return False
+    if xrows < A.n or yrows < A.m:
+        raise IndexError("list index out of range")
+    if mode is None:
+        mode = GAXPY_EXACT if (yhost is not None or not isinstance(X, dvec)) else GAXPY_AUTO
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_gaxpy_block(dA.handle, dX.handle, dY.handle, k, mode), "csx_gaxpy_block")
+    if yhost is not None:
+        out = dY.numpy().reshape(yrows, k)[:A.m]
+        if isinstance(yhost, np.ndarray):
+            yhost[:A.m] = out if yhost.ndim == 2 else out[:, 0]
+        else:
+            yhost[:A.m] = out.tolist() if k > 1 else out[:, 0].tolist()
     return True
 
 

@@ -591,6 +591,7 @@ const OptSlot kOptSlots[] = {
     {"tri.graph", &Options::tri_graph, 6},               {"sort.short_keys", &Options::sort_short_keys, 0},
     {"chol.clique", &Options::chol_clique, 0},           {"chol.forest", &Options::chol_forest, 0},
     {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
+    {"gaxpy.block_route", &Options::gaxpy_block_route, 3},
 };
 int normalise(int kind, int value) {
     switch (kind) {

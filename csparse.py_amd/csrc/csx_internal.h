@@ -148,6 +148,7 @@ struct Options {
     int tri_columns = 1;          // tri-solve: small chain-like systems by the column loop, x in LDS
     int gaxpy_keys24 = 1;         // tiled cs_gaxpy plan: 3-byte keys when the matrix allows them
     int gaxpy_tune_shape = 0;    // tiled cs_gaxpy plan: time the launch shapes when the plan is built and keep the fastest
+    int gaxpy_block_route = 0;   // csx_gaxpy_block AUTO: 0 = its own rule, 1 = the block kernel, 2 = the column route
     int tri_row_waves = 1;        // level-scheduled solves: a wave per row for few right-hand sides and long rows
     int tri_levels_where = 0;         // level analysis: 0 = device for big factors, host for small; 1 = host; 2 = device
     int sort_short_keys = 1;          // cs_transpose: 16-bit keys between the radix passes where the matrix allows (0: always 32-bit)

@@ -98,7 +98,8 @@ int csx_mem_info(int64_t *cached_bytes, int64_t *live_bytes, int64_t *device_fre
  * their order, L.x bit-identical; 0, opt-in: fused multiply-adds and refined reciprocal square roots in that kernel -- forests of
  * dense blocks only -- L.x equal to rounding; equal blocks of 16 / 32 / 48 / 64 columns are then factored on the matrix cores, 1.8x
  * the rate), "tri.host_chains" (default 0; 1: csx_tri_solve_list / csx_cholsol_solve_list take one host right-hand side on a
- * chain-like factor to the host).  Unknown name: CSX_EINVAL. */
+ * chain-like factor to the host).  "gaxpy.block_route" (default 0: csx_gaxpy_block AUTO's own rule; 1 = the block kernel,
+ * 2 = the column route).  Unknown name: CSX_EINVAL. */
 int csx_set_option(const char *name, int value);
 int csx_get_option(const char *name, int *value);   /* the value in force (after csx_set_option's normalisation) */
 int csx_timer_start(void);                /* hipEvent on the context's stream */
@@ -153,6 +154,20 @@ int csx_gaxpy_plan_shape(csx_handle_t A, int *shape, double *ms4);
  * summation order (bit-identical), nothing left on the device.  x (values) must be present. */
 int csx_gaxpy_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, const double *x, const double *xv,
                    double *yv);
+/* Y[0..m) x [0..nrhs) += A X, X n-by-nrhs and Y m-by-nrhs, both row-major (csparse.py:1199-1213 applied to
+ * every column).  mode: CSX_GAXPY_EXACT or CSX_GAXPY_AUTO; any other mode is CSX_EINVAL.
+ *   EXACT  every column of Y bit-identical to csx_gaxpy(..., CSX_GAXPY_EXACT) on that column; deterministic.
+ *   AUTO   the block kernel (the same kernel and bits as EXACT) or, for blocks of at most 4 columns on a matrix
+ *          for which csx_gaxpy AUTO uses the LDS-tiled plan, the column route: csx_gaxpy AUTO once per column on
+ *          transposed copies of X and Y (n nrhs + m nrhs doubles of device memory for the call), every column
+ *          bit-identical to csx_gaxpy AUTO on it.  Deterministic wherever csx_gaxpy AUTO is, i.e. except on the
+ *          column route (the tiled plan sums in LDS with atomics).  csx_set_option("gaxpy.block_route", 1 | 2)
+ *          forces the block kernel | the column route (0: the rule above).
+ * nrhs == 1 is csx_gaxpy with the same mode.  Reads A's cached row gather (csx_gaxpy_prepare(A, CSX_GAXPY_EXACT)
+ * builds it ahead of time); AUTO makes csx_gaxpy AUTO's plan decision first, the same way.  CSX_EINVAL for a
+ * pattern-only A, nrhs < 1, X shorter than n nrhs or Y shorter than m nrhs entries, X and Y the same handle or
+ * overlapping device ranges.  m == 0, n == 0 or nnz == 0: nothing to do, CSX_OK. */
+int csx_gaxpy_block(csx_handle_t A, csx_handle_t X, csx_handle_t Y, int32_t nrhs, int mode);
 
 /* cs_transpose, csparse.py:2292-2315: stable counting sort by row. */
 int csx_transpose(csx_handle_t A, int values, csx_handle_t *out);
