@@ -130,6 +130,10 @@ _PROTOS = {
     "csx_dmperm": [H, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
     "csx_dmperm_times": [_f64p],
     "csx_dmperm_rounds": [C.POINTER(C.c_int64)],
+    "csx_btf_split": [H, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, C.POINTER(H), C.POINTER(H)],
+    "csx_btf_plan": [H, H, H, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.POINTER(H)],
+    "csx_btf_solve": [H, H, H, C.c_int32],
+    "csx_btf_info": [H, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

@@ -26,6 +26,7 @@ What runs where
     cs_cumsum, cs_scatter on lists, permutation of a single list) stays Python.
 """
 import os
+import time
 import weakref
 from math import sqrt
 
@@ -1978,3 +1979,92 @@ def cs_dmperm(A, seed):
     D.rr = got["rr"].tolist()
     D.cc = got["cc"].tolist()
     return D
+
+
+# ------------------------------------------------------------ block triangular LU --
+
+class btfn(object):
+    """Factors of btf_factor: C = A(p, q) = D + F with L U = D(pinv, :) (cs_lu of the block-diagonal part D) and F the
+    strictly block upper part, both in C's column storage order.  p, q (n), r (nb + 1: block k is rows / columns r[k] .. r[k+1]-1 of C), levels (nb,
+    highest first) and pinv are numpy int32 arrays; L, U, F are `cs` matrices (device-backed)."""
+
+    def __init__(self):
+        self.L = self.U = self.F = self.D = None
+        self.pinv = self.p = self.q = self.r = self.levels = None
+
+
+def btf_factor(A, tol=1.0, seed=0):
+    """Factor a square, structurally nonsingular A through its block triangular form (KLU's scheme; CSparse's
+    cs_dmsol for the square case): dmperm_arrays(A, seed) gives the strongly connected blocks, the blocks are put in
+    level order (a block's level: 0 without entries outside it in its rows, else 1 + the largest level those reach;
+    highest first), C = A(p, q) is split into its diagonal blocks D and the strictly block upper rest F, and
+    cs_lu(D, cs_sqr(0, D, False), tol) factors the blocks (on the device when D is a batch of small blocks).
+
+    solve(b): b a list (one system) or a dvec n-by-k block (k systems), overwritten with x; True.  Every right-hand side
+    is solved in one order fixed by the factors: c = b(p); blocks from last to first, c_i -= F_ij z_j
+    in cs_gaxpy's order, then the block's part of cs_ipvec(pinv), cs_lsolve(L), cs_usolve(U); x(q) = z.  Lists and
+    blocks give the same bits, every run.  One launch per level for the blocks of at most 96 rows.
+    .factors: a btfn; .info(): the plan's counts; .factor_ms: wall-clock ms of dmperm, split, cs_lu(D), plan.  None when A is not CSC, not square, structurally singular
+    (sprank < n), or cs_lu(D) returns None (a numerically singular block)."""
+    if not CS_CSC(A) or A.m != A.n:
+        return None
+    if not _meta(A)[1]:
+        raise TypeError("'NoneType' object is not subscriptable")
+    n = A.n
+    ms = {}
+    t0 = time.perf_counter()
+    d = dmperm_arrays(A, seed)
+    ms["dmperm"] = 1e3 * (time.perf_counter() - t0)
+    if int(d["rr"][3]) < n:
+        return None
+    nb = d["nb"]
+    t0 = time.perf_counter()
+    p, q = np.empty(n, np.int32), np.empty(n, np.int32)
+    r, levels = np.zeros(nb + 1, np.int32), np.zeros(max(nb, 1), np.int32)
+    nlev = _csx.C.c_int32(0)
+    hD, hF = _csx.new_handle(), _csx.new_handle()
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_btf_split(dA.handle, _csx.pi(d["p"]), _csx.pi(d["q"]), _csx.pi(_csx.i32(d["r"])), nb,
+                                            _csx.pi(p), _csx.pi(q), _csx.pi(r), _csx.pi(levels), nlev, hD, hF),
+                   "csx_btf_split")
+    D = _from_device(hD, lambda nnz: max(nnz, 1))
+    F = _from_device(hF, lambda nnz: max(nnz, 1))
+    ms["split"] = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    N = cs_lu(D, cs_sqr(0, D, False), tol)
+    if N is None:
+        return None
+    L, U = cs_pin(N.L), cs_pin(N.U)
+    ms["lu"] = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    fac = btfn()
+    fac.L, fac.U, fac.F, fac.D = L, U, F, D
+    fac.pinv = np.asarray(N.pinv, dtype=np.int32)
+    fac.p, fac.q, fac.r, fac.levels = p, q, r, levels[:nb].copy()
+    plan = _csx.new_handle()
+    with _Resident(L) as dL, _Resident(U) as dU, _Resident(F) as dF:
+        _csx.check(_csx.lib().csx_btf_plan(dL.handle, dU.handle, dF.handle, _csx.pi(fac.pinv), _csx.pi(p), _csx.pi(q),
+                                           _csx.pi(r), _csx.pi(levels), nb, plan), "csx_btf_plan")
+    ms["plan"] = 1e3 * (time.perf_counter() - t0)
+
+    class _Solver(object):
+        factors = fac
+        factor_ms = ms      # host wall-clock of the four factor steps (each ends with a copy to the host or a sync)
+
+        def __init__(self):
+            self._fin = weakref.finalize(self, _csx.free, plan)
+
+        def info(self):
+            v = np.zeros(8, dtype=np.int64)
+            _csx.check(_csx.lib().csx_btf_info(plan, v.ctypes.data_as(_csx.C.POINTER(_csx.C.c_int64))), "csx_btf_info")
+            return dict(zip(("blocks", "levels", "max_block", "lnz", "unz", "fnz", "large_blocks", "launches"),
+                            v.tolist()))
+
+        def solve(self, b):
+            db, bhost = _vec_in(b, n, "b")
+            work = dvec(n, db.k)
+            _csx.check(_csx.lib().csx_btf_solve(plan, db.handle, work.handle, db.k), "csx_btf_solve")
+            _write_back(bhost, db, n * db.k)
+            return True
+
+    return _Solver()

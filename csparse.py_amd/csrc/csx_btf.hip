@@ -1,0 +1,564 @@
+// Block triangular LU (btf_factor): the split of a square, structurally nonsingular A into the diagonal blocks D and the
+// strictly block upper coupling F of C = A(p, q), the block levels, and the solve of A x = b from cs_lu(D) and F.
+//
+// The order of a solve is fixed by the factors: c = b(p); blocks from last to first, for every row of a
+// block c_i -= F_ij z_j in cs_gaxpy's order (ascending column, storage order inside a column; multiply and subtract
+// rounded separately); then the block's part of cs_ipvec(pinv), cs_lsolve(L), cs_usolve(U), operation for operation;
+// x(q) = z.  Blocks of one level read only z of lower levels, so a level is one launch.
+#include <algorithm>
+
+#include "csx_internal.h"
+#include "csx_sweep.h"
+
+#pragma clang fp contract(off)
+
+namespace csx {
+
+int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed);   // csx_trisolve.hip
+int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);
+
+constexpr int BTF_SMALL = 96;   // rows of the largest block solved with its tile in LDS (csx_lu_blocks' limit)
+
+struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (local indices) and exact triangular plans of them
+    int32_t r0 = 0, nr = 0;
+    Csc L, U;
+    TriPlan *pl = nullptr, *pu = nullptr;
+};
+
+struct BtfPlan {
+    int32_t n = 0, nb = 0, nlevels = 0, max_block = 0;
+    int64_t lnz = 0, unz = 0, fnz = 0;
+    int32_t *p = nullptr, *q = nullptr, *pinv = nullptr, *r = nullptr;
+    // row programs: L without its diagonal (ascending column), U without its diagonal (DESCENDING column), F (ascending
+    // column); the L / U indices are (column - first row of the block) * 64: LDS offsets of the block's X tile
+    int32_t *Lp = nullptr, *Li = nullptr, *Up = nullptr, *Ui = nullptr;
+    double *Lx = nullptr, *Ld = nullptr, *Ux = nullptr, *Ud = nullptr;
+    Csc Ft;                              // F' = the rows of F in cs_gaxpy's order
+    int32_t *small = nullptr;            // small blocks grouped by level (level 0 first), ascending block inside a level
+    std::vector<int32_t> small_ptr;      // [nlevels + 1] into small
+    std::vector<int32_t> small_rows;     // [nlevels] largest small block of the level
+    std::vector<std::vector<int32_t>> large_of_level;   // indices into large
+    std::vector<BtfLarge *> large;
+};
+
+static void free_csc_fields(Csc &A) {
+    dfree(A.p);
+    dfree(A.i);
+    dfree(A.x);
+    A.p = A.i = nullptr;
+    A.x = nullptr;
+}
+
+void free_btfplan(BtfPlan *P) {
+    if (!P) return;
+    for (void *d : {(void *)P->p, (void *)P->q, (void *)P->pinv, (void *)P->r, (void *)P->Lp, (void *)P->Li, (void *)P->Up,
+                    (void *)P->Ui, (void *)P->Lx, (void *)P->Ld, (void *)P->Ux, (void *)P->Ud, (void *)P->small})
+        dfree(d);
+    free_csc_fields(P->Ft);
+    for (BtfLarge *B : P->large) {
+        free_triplan(B->pl);
+        free_triplan(B->pu);
+        free_csc_fields(B->L);
+        free_csc_fields(B->U);
+        delete B;
+    }
+    delete P;
+}
+
+static unsigned grid_for(int64_t count) { return (unsigned)std::max<int64_t>(1, (count + 255) / 256); }
+
+// ------------------------------------------------------------------------------------------------ the split --
+
+// per column j of C: entries whose row lies in column j's block (D) -- the rest are F
+__global__ __launch_bounds__(256) void k_btf_count(int32_t n, const int32_t *__restrict__ Cp, const int32_t *__restrict__ Ci,
+                                                   const int32_t *__restrict__ blk, int32_t *__restrict__ dcnt,
+                                                   int32_t *__restrict__ fcnt) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = blk[j];
+    int32_t d = 0;
+    for (int32_t t = Cp[j]; t < Cp[j + 1]; t++) d += blk[Ci[t]] == b;
+    dcnt[j] = d;
+    fcnt[j] = Cp[j + 1] - Cp[j] - d;
+}
+
+__global__ __launch_bounds__(256) void k_btf_fill(int32_t n, const int32_t *__restrict__ Cp, const int32_t *__restrict__ Ci,
+                                                  const double *__restrict__ Cx, const int32_t *__restrict__ blk,
+                                                  const int32_t *__restrict__ Dp, int32_t *__restrict__ Di,
+                                                  double *__restrict__ Dx, const int32_t *__restrict__ Fp,
+                                                  int32_t *__restrict__ Fi, double *__restrict__ Fx) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const int32_t b = blk[j];
+    int32_t d = Dp[j], f = Fp[j];
+    for (int32_t t = Cp[j]; t < Cp[j + 1]; t++) {
+        const int32_t i = Ci[t];
+        if (blk[i] == b) {
+            Di[d] = i;
+            Dx[d++] = Cx[t];
+        } else {
+            Fi[f] = i;
+            Fx[f++] = Cx[t];
+        }
+    }
+}
+
+static int split_device(const Csc *C, const std::vector<int32_t> &blk_h, Csc *D, Csc *F) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = C->n;
+    DevScope tmp;
+    int32_t *blk = nullptr, *dcnt = nullptr, *fcnt = nullptr;
+    CSX_TRY(tmp.alloc(&blk, (size_t)n + 1));
+    CSX_TRY(tmp.alloc(&dcnt, (size_t)n + 1));
+    CSX_TRY(tmp.alloc(&fcnt, (size_t)n + 1));
+    if (n) CSX_HIP(hipMemcpyAsync(blk, blk_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (n) hipLaunchKernelGGL(k_btf_count, dim3(grid_for(n)), dim3(256), 0, s, n, C->p, C->i, blk, dcnt, fcnt);
+    CSX_LAUNCH_CHECK();
+    for (Csc *M : {D, F}) {
+        M->m = M->n = n;
+        M->owns = true;
+        CSX_TRY(dalloc(&M->p, (size_t)n + 1));
+    }
+    int64_t dnz = 0, fnz = 0;
+    CSX_TRY(scan_exclusive_i32(dcnt, D->p, n, &dnz));
+    CSX_TRY(scan_exclusive_i32(fcnt, F->p, n, &fnz));
+    D->nnz = (int32_t)dnz;
+    F->nnz = (int32_t)fnz;
+    CSX_TRY(dalloc(&D->i, (size_t)dnz));
+    CSX_TRY(dalloc(&D->x, (size_t)dnz));
+    CSX_TRY(dalloc(&F->i, (size_t)fnz));
+    CSX_TRY(dalloc(&F->x, (size_t)fnz));
+    if (n)
+        hipLaunchKernelGGL(k_btf_fill, dim3(grid_for(n)), dim3(256), 0, s, n, C->p, C->i, C->x, blk, D->p, D->i, D->x, F->p,
+                           F->i, F->x);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+// ------------------------------------------------------------------------------------------------- the plan --
+
+// Row i of L' (= column i of Lt, ascending column, the unit diagonal last) -> program row without the diagonal; row i
+// of U' (diagonal first) -> program row in descending column order.  Every column must lie in row i's block and on
+// the right side of the diagonal: *bad = 1 otherwise (the kernels index LDS by these columns).
+__global__ __launch_bounds__(256) void k_btf_strip(int32_t n, int upper, const int32_t *__restrict__ Tp,
+                                                   const int32_t *__restrict__ Ti, const double *__restrict__ Tx,
+                                                   const int32_t *__restrict__ row_r0, const int32_t *__restrict__ row_r1,
+                                                   int32_t *__restrict__ Pp, int32_t *__restrict__ Pi,
+                                                   double *__restrict__ Px, double *__restrict__ Pd, int *bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) {
+        Pp[n] = Tp[n] - n;
+        return;
+    }
+    const int32_t a = Tp[i], e = Tp[i + 1];
+    Pp[i] = a - (int32_t)i;
+    // (a row without its diagonal shifts the program of the rows after it: caught here before anything is written)
+    if (e <= a || (int64_t)a - i < 0 || (int64_t)e - i - 1 > (int64_t)Tp[n] - n || Ti[upper ? a : e - 1] != i) {
+        *bad = 1;
+        return;
+    }
+    const int32_t r0 = row_r0[i], r1 = row_r1[i];
+    Pd[i] = Tx[upper ? a : e - 1];
+    const int32_t cnt = e - a - 1;
+    for (int32_t t = 0; t < cnt; t++) {
+        const int32_t src = upper ? e - 1 - t : a + t;
+        const int32_t j = Ti[src];
+        if (upper ? (j <= i || j >= r1) : (j >= i || j < r0)) *bad = 1;
+        Pi[a - i + t] = (j - r0) * 64;
+        Px[a - i + t] = Tx[src];
+    }
+}
+
+// F's columns in row i must lie in blocks after row i's block, of a lower level (solved by an earlier launch)
+__global__ __launch_bounds__(256) void k_btf_check_f(int32_t n, const int32_t *__restrict__ Fp, const int32_t *__restrict__ Fi,
+                                                     const int32_t *__restrict__ row_r1, const int32_t *__restrict__ row_lev,
+                                                     int *bad) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    for (int32_t t = Fp[i]; t < Fp[i + 1]; t++) {
+        const int32_t j = Fi[t];
+        if (j < row_r1[i] || j >= n || row_lev[j] >= row_lev[i]) *bad = 1;
+    }
+}
+
+// rows of a block's own factor: row index - r0 (col_block_device keeps the global rows)
+__global__ __launch_bounds__(256) void k_btf_shift_rows(int32_t nnz, int32_t r0, int32_t *__restrict__ Ci) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nnz) Ci[t] -= r0;
+}
+
+static int block_factor(const Csc *M, int32_t r0, int32_t nr, Csc *out) {
+    CSX_TRY(col_block_device(M, r0, nr, out));
+    out->m = nr;
+    if (out->nnz)
+        hipLaunchKernelGGL(k_btf_shift_rows, dim3(grid_for(out->nnz)), dim3(256), 0, ctx().stream, out->nnz, r0, out->i);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
+template <class T>
+static int upload(T **d, const T *h, size_t count) {
+    CSX_TRY(dalloc(d, count));
+    if (count) CSX_HIP(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
+    return CSX_OK;
+}
+
+static int strip(const Csc *M, bool upper, const int32_t *row_r0, const int32_t *row_r1, int *bad, int32_t **Pp,
+                 int32_t **Pi, double **Px, double **Pd) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = M->n;
+    Csc T;
+    CSX_TRY(transpose_device(M, true, &T));
+    const int64_t cnt = std::max<int64_t>(0, (int64_t)T.nnz - n);
+    int st = dalloc(Pp, (size_t)n + 1);
+    if (st == CSX_OK) st = dalloc(Pi, (size_t)cnt);
+    if (st == CSX_OK) st = dalloc(Px, (size_t)cnt);
+    if (st == CSX_OK) st = dalloc(Pd, (size_t)n);
+    if (st == CSX_OK) {
+        hipLaunchKernelGGL(k_btf_strip, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, T.p, T.i, T.x,
+                           row_r0, row_r1, *Pp, *Pi, *Px, *Pd, bad);
+        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+    }
+    (void)hipStreamSynchronize(s);
+    free_csc_fields(T);
+    return st;
+}
+
+// ------------------------------------------------------------------------------------------------ the solve --
+
+// Small blocks of one level: one wave per (block, tile of 64 right-hand sides), the block's rows of the tile in LDS,
+// one lane per right-hand side.  Every LDS slot a lane touches is in its own column of the tile: no barrier.
+__global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ blocks, const int32_t *__restrict__ r,
+                                                  const int32_t *__restrict__ p, const int32_t *__restrict__ pinv,
+                                                  const int32_t *__restrict__ Fp, const int32_t *__restrict__ Fi,
+                                                  const double *__restrict__ Fx, const int32_t *__restrict__ Lp,
+                                                  const int32_t *__restrict__ Li, const double *__restrict__ Lx,
+                                                  const double *__restrict__ Ld, const int32_t *__restrict__ Up,
+                                                  const int32_t *__restrict__ Ui, const double *__restrict__ Ux,
+                                                  const double *__restrict__ Ud, const double *__restrict__ B,
+                                                  double *__restrict__ W, int32_t k) {
+    extern __shared__ double X[];
+    const int lane = threadIdx.x;
+    const int32_t b = blocks[blockIdx.x];
+    const int32_t r0 = r[b], nr = r[b + 1] - r0;
+    const int32_t col = (int32_t)blockIdx.y * 64 + lane;
+    const bool on = col < k;
+    // c = b(p), minus the F terms (the z they read is final: lower levels), scattered by pinv into the tile
+    for (int32_t t = 0; t < nr; t++) {
+        const int32_t i = r0 + t;
+        double acc = on ? B[(int64_t)p[i] * k + col] : 0.0;
+        const int32_t qe = Fp[i + 1];
+        for (int32_t q = Fp[i]; q < qe; q += 64) {
+            const TermRegs T = load_terms(Fi, Fx, q, qe, lane);
+            const int ulim = min(64, qe - q);
+            for (int u = 0; u < ulim; u++) {
+                const int32_t j = __builtin_amdgcn_readlane(T.i, u);
+                const double z = on ? W[(int64_t)j * k + col] : 0.0;
+                const double prod = bcast_f64(T.v, u) * z;
+                acc = acc - prod;
+            }
+        }
+        X[(pinv[i] - r0) * 64 + lane] = acc;
+    }
+    // cs_lsolve on the block: rows ascending, terms in ascending column
+    for (int32_t t = 0; t < nr; t++) {
+        const int32_t i = r0 + t;
+        double acc = X[t * 64 + lane];
+        const int32_t qe = Lp[i + 1];
+        for (int32_t q = Lp[i]; q < qe; q += 64) {
+            const TermRegs T = load_terms(Li, Lx, q, qe, lane);
+            acc = apply_terms(acc, T, 0, min(64, qe - q), X, lane);
+        }
+        X[t * 64 + lane] = acc / Ld[i];
+    }
+    // cs_usolve on the block: rows descending, terms in descending column
+    for (int32_t t = nr - 1; t >= 0; t--) {
+        const int32_t i = r0 + t;
+        double acc = X[t * 64 + lane];
+        const int32_t qe = Up[i + 1];
+        for (int32_t q = Up[i]; q < qe; q += 64) {
+            const TermRegs T = load_terms(Ui, Ux, q, qe, lane);
+            acc = apply_terms(acc, T, 0, min(64, qe - q), X, lane);
+        }
+        X[t * 64 + lane] = acc / Ud[i];
+    }
+    if (on)
+        for (int32_t t = 0; t < nr; t++) W[(int64_t)(r0 + t) * k + col] = X[t * 64 + lane];
+}
+
+// The rows of a large block: W(pinv(i)) = b(p(i)) - F(i, :) z, one thread per (row, right-hand side)
+__global__ __launch_bounds__(256) void k_btf_rows(int32_t r0, int32_t nr, const int32_t *__restrict__ p,
+                                                  const int32_t *__restrict__ pinv, const int32_t *__restrict__ Fp,
+                                                  const int32_t *__restrict__ Fi, const double *__restrict__ Fx,
+                                                  const double *__restrict__ B, double *__restrict__ W, int32_t k) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)nr * k) return;
+    const int32_t i = r0 + (int32_t)(g / k), col = (int32_t)(g % k);
+    double acc = B[(int64_t)p[i] * k + col];
+    for (int32_t t = Fp[i]; t < Fp[i + 1]; t++) {
+        const double prod = Fx[t] * W[(int64_t)Fi[t] * k + col];
+        acc = acc - prod;
+    }
+    W[(int64_t)pinv[i] * k + col] = acc;
+}
+
+// x(q) = z
+__global__ __launch_bounds__(256) void k_btf_out(int32_t n, const int32_t *__restrict__ q, const double *__restrict__ W,
+                                                 double *__restrict__ B, int32_t k) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (int64_t)n * k) return;
+    const int32_t t = (int32_t)(g / k), col = (int32_t)(g % k);
+    B[(int64_t)q[t] * k + col] = W[g];
+}
+
+static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32_t k) {
+    hipStream_t s = ctx().stream;
+    const unsigned tiles = (unsigned)((k + 63) / 64);
+    for (int32_t l = 0; l < P->nlevels; l++) {
+        const int32_t a = P->small_ptr[l], e = P->small_ptr[l + 1];
+        if (e > a) {
+            const size_t lds = (size_t)P->small_rows[l] * 64 * sizeof(double);
+            hipLaunchKernelGGL(k_btf_small, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->p,
+                               P->pinv, P->Ft.p, P->Ft.i, P->Ft.x, P->Lp, P->Li, P->Lx, P->Ld, P->Up, P->Ui, P->Ux, P->Ud, B,
+                               W, k);
+            CSX_LAUNCH_CHECK();
+        }
+        for (int32_t li : P->large_of_level[l]) {
+            BtfLarge *G = P->large[li];
+            hipLaunchKernelGGL(k_btf_rows, dim3(grid_for((int64_t)G->nr * k)), dim3(256), 0, s, G->r0, G->nr, P->p, P->pinv,
+                               P->Ft.p, P->Ft.i, P->Ft.x, B, W, k);
+            CSX_LAUNCH_CHECK();
+            double *Wb = W + (int64_t)G->r0 * k;
+            CSX_TRY(tri_solve_raw(G->pl, Wb, k, false));
+            CSX_TRY(tri_solve_raw(G->pu, Wb, k, false));
+        }
+    }
+    if (P->n)
+        hipLaunchKernelGGL(k_btf_out, dim3(grid_for((int64_t)P->n * k)), dim3(256), 0, s, P->n, P->q, W, Bout, k);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
+static bool is_perm(const int32_t *p, int32_t n) {
+    std::vector<char> seen((size_t)n, 0);
+    for (int32_t k = 0; k < n; k++) {
+        if (p[k] < 0 || p[k] >= n || seen[p[k]]) return false;
+        seen[p[k]] = 1;
+    }
+    return true;
+}
+
+static bool is_blocks(const int32_t *r, int32_t nb, int32_t n) {
+    if (nb < 0 || r[0] != 0 || r[nb] != n) return false;
+    for (int32_t b = 0; b < nb; b++)
+        if (r[b + 1] <= r[b]) return false;
+    return true;
+}
+
+}  // namespace csx
+
+using namespace csx;
+
+extern "C" int csx_btf_split(csx_handle_t hA, const int32_t *p, const int32_t *q, const int32_t *r, int32_t nb, int32_t *p_out,
+                             int32_t *q_out, int32_t *r_out, int32_t *level, int32_t *nlevels, csx_handle_t *hD,
+                             csx_handle_t *hF) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !A->x || A->m != A->n || !p || !q || !r || !p_out || !q_out || !r_out || !level || !nlevels || !hD || !hF)
+        return CSX_EINVAL;
+    const int32_t n = A->n;
+    if (!is_perm(p, n) || !is_perm(q, n) || !is_blocks(r, nb, n)) return CSX_EINVAL;
+    hipStream_t s = ctx().stream;
+    std::vector<int32_t> Ap((size_t)n + 1), Ai((size_t)A->nnz);
+    CSX_HIP(hipMemcpyAsync(Ap.data(), A->p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (A->nnz) CSX_HIP(hipMemcpyAsync(Ai.data(), A->i, (size_t)A->nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    // block of every row and column of A in the given order
+    std::vector<int32_t> rowblk((size_t)n), colblk((size_t)n);
+    for (int32_t b = 0; b < nb; b++)
+        for (int32_t k = r[b]; k < r[b + 1]; k++) {
+            rowblk[p[k]] = b;
+            colblk[q[k]] = b;
+        }
+    // edges block(row) -> block(column) of the entries outside the diagonal blocks, grouped by the row's block
+    std::vector<int32_t> eptr((size_t)nb + 1, 0);
+    for (int32_t j = 0; j < n; j++)
+        for (int32_t t = Ap[j]; t < Ap[j + 1]; t++) {
+            const int32_t bi = rowblk[Ai[t]], bj = colblk[j];
+            if (bj < bi) return CSX_EINVAL;   // not block upper triangular in this order
+            if (bj != bi) eptr[bi + 1]++;
+        }
+    for (int32_t b = 0; b < nb; b++) eptr[b + 1] += eptr[b];
+    std::vector<int32_t> edst((size_t)eptr[nb]), fill(eptr.begin(), eptr.end() - 1);
+    for (int32_t j = 0; j < n; j++)
+        for (int32_t t = Ap[j]; t < Ap[j + 1]; t++) {
+            const int32_t bi = rowblk[Ai[t]], bj = colblk[j];
+            if (bj != bi) edst[fill[bi]++] = bj;
+        }
+    // level: 0 without entries outside the block, else 1 + the largest level reached; edges point to later blocks
+    std::vector<int32_t> lev((size_t)nb, 0);
+    int32_t L = nb ? 1 : 0;
+    for (int32_t b = nb - 1; b >= 0; b--) {
+        int32_t v = 0;
+        for (int32_t t = eptr[b]; t < eptr[b + 1]; t++) v = std::max(v, lev[edst[t]] + 1);
+        lev[b] = v;
+        L = std::max(L, v + 1);
+    }
+    // blocks by level, highest first (a block's F reaches lower levels only: later blocks), dmperm's order inside a level
+    std::vector<int32_t> order((size_t)nb);
+    for (int32_t b = 0; b < nb; b++) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return lev[x] > lev[y]; });
+    std::vector<int32_t> pinv_new((size_t)n), blk_new((size_t)n);
+    int32_t k = 0;
+    r_out[0] = 0;
+    for (int32_t nbk = 0; nbk < nb; nbk++) {
+        const int32_t b = order[nbk];
+        for (int32_t t = r[b]; t < r[b + 1]; t++, k++) {
+            p_out[k] = p[t];
+            q_out[k] = q[t];
+            pinv_new[p[t]] = k;
+            blk_new[k] = nbk;
+        }
+        r_out[nbk + 1] = k;
+        level[nbk] = lev[b];
+    }
+    *nlevels = L;
+    csx_handle_t hC = 0;
+    CSX_TRY(csx_permute(hA, pinv_new.data(), q_out, 1, &hC));
+    Csc *D = new Csc(), *F = new Csc();
+    int st = split_device(csc(hC), blk_new, D, F);
+    csx_free(hC);
+    if (st != CSX_OK) {
+        free_csc(D);
+        free_csc(F);
+        return st;
+    }
+    *hD = put(K_CSC, D);
+    *hF = put(K_CSC, F);
+    return CSX_OK;
+}
+
+extern "C" int csx_btf_plan(csx_handle_t hL, csx_handle_t hU, csx_handle_t hF, const int32_t *pinv, const int32_t *p,
+                            const int32_t *q, const int32_t *r, const int32_t *level, int32_t nb, csx_handle_t *out) {
+    CSX_TRY(require_ready());
+    Csc *L = csc(hL), *U = csc(hU), *F = csc(hF);
+    if (!L || !U || !F || !L->x || !U->x || !F->x || !pinv || !p || !q || !r || !level || !out) return CSX_EINVAL;
+    const int32_t n = L->n;
+    if (L->m != n || U->m != n || U->n != n || F->m != n || F->n != n) return CSX_EINVAL;
+    if (!is_perm(pinv, n) || !is_perm(p, n) || !is_perm(q, n) || !is_blocks(r, nb, n)) return CSX_EINVAL;
+    int32_t nlev = 0;
+    for (int32_t b = 0; b < nb; b++) {
+        if (level[b] < 0 || level[b] >= nb || (b && level[b] > level[b - 1])) return CSX_EINVAL;
+        nlev = std::max(nlev, level[b] + 1);
+    }
+    // pivots stay inside their block
+    for (int32_t b = 0; b < nb; b++)
+        for (int32_t i = r[b]; i < r[b + 1]; i++)
+            if (pinv[i] < r[b] || pinv[i] >= r[b + 1]) return CSX_EINVAL;
+    hipStream_t s = ctx().stream;
+    BtfPlan *P = new BtfPlan();
+    P->n = n;
+    P->nb = nb;
+    P->nlevels = nlev;
+    std::vector<int32_t> r0h((size_t)n), r1h((size_t)n), levh((size_t)n);
+    for (int32_t b = 0; b < nb; b++) {
+        P->max_block = std::max(P->max_block, r[b + 1] - r[b]);
+        for (int32_t i = r[b]; i < r[b + 1]; i++) {
+            r0h[i] = r[b];
+            r1h[i] = r[b + 1];
+            levh[i] = level[b];
+        }
+    }
+    // blocks grouped by level, level 0 first
+    std::vector<int32_t> small_h;
+    P->small_ptr.assign(1, 0);
+    P->small_rows.assign((size_t)nlev, 0);
+    P->large_of_level.assign((size_t)nlev, {});
+    // levels fall along the block order (checked above): level l is one run of blocks, found walking from the end
+    int32_t run_end = nb;
+    for (int32_t l = 0; l < nlev; l++) {
+        int32_t run_begin = run_end;
+        while (run_begin > 0 && level[run_begin - 1] == l) run_begin--;
+        for (int32_t b = run_begin; b < run_end; b++) {
+            const int32_t nr = r[b + 1] - r[b];
+            if (nr <= BTF_SMALL) {
+                small_h.push_back(b);
+                P->small_rows[l] = std::max(P->small_rows[l], nr);
+            } else {
+                BtfLarge *G = new BtfLarge();
+                G->r0 = r[b];
+                G->nr = nr;
+                P->large_of_level[l].push_back((int32_t)P->large.size());
+                P->large.push_back(G);
+            }
+        }
+        P->small_ptr.push_back((int32_t)small_h.size());
+        run_end = run_begin;
+    }
+    DevScope tmp;
+    int32_t *row_r0 = nullptr, *row_r1 = nullptr, *row_lev = nullptr;
+    int *bad = nullptr;
+    int st = CSX_OK;
+    auto fail = [&](int code) {
+        free_btfplan(P);
+        return code;
+    };
+    for (auto [d, h] : {std::make_pair(&row_r0, &r0h), std::make_pair(&row_r1, &r1h), std::make_pair(&row_lev, &levh)}) {
+        if ((st = upload(d, h->data(), (size_t)n)) != CSX_OK) return fail(st);
+        tmp.held.push_back(*d);
+    }
+    if ((st = tmp.alloc(&bad, 1)) != CSX_OK) return fail(st);
+    if (hipMemsetAsync(bad, 0, sizeof(int), s) != hipSuccess) return fail(CSX_ERUNTIME);
+    if ((st = upload(&P->p, p, (size_t)n)) || (st = upload(&P->q, q, (size_t)n)) || (st = upload(&P->pinv, pinv, (size_t)n)) ||
+        (st = upload(&P->r, r, (size_t)nb + 1)) || (st = upload(&P->small, small_h.data(), small_h.size())))
+        return fail(st);
+    if ((st = strip(L, false, row_r0, row_r1, bad, &P->Lp, &P->Li, &P->Lx, &P->Ld)) != CSX_OK) return fail(st);
+    if ((st = strip(U, true, row_r0, row_r1, bad, &P->Up, &P->Ui, &P->Ux, &P->Ud)) != CSX_OK) return fail(st);
+    if ((st = transpose_device(F, true, &P->Ft)) != CSX_OK) return fail(st);
+    if (n) hipLaunchKernelGGL(k_btf_check_f, dim3(grid_for(n)), dim3(256), 0, s, n, P->Ft.p, P->Ft.i, row_r1, row_lev, bad);
+    int hbad = 0;
+    if (hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(CSX_ERUNTIME);
+    if (hbad) return fail(CSX_EINVAL);
+    P->lnz = L->nnz;
+    P->unz = U->nnz;
+    P->fnz = F->nnz;
+    for (BtfLarge *G : P->large) {
+        if ((st = block_factor(L, G->r0, G->nr, &G->L)) || (st = block_factor(U, G->r0, G->nr, &G->U)) ||
+            (st = tri_analyse_raw(&G->L, CSX_TRI_L, &G->pl)) || (st = tri_analyse_raw(&G->U, CSX_TRI_U, &G->pu)))
+            return fail(st);
+    }
+    CSX_HIP(hipStreamSynchronize(s));
+    *out = put(K_BTFPLAN, P);
+    return CSX_OK;
+}
+
+extern "C" int csx_btf_solve(csx_handle_t h, csx_handle_t hB, csx_handle_t hW, int32_t nrhs) {
+    CSX_TRY(require_ready());
+    BtfPlan *P = (BtfPlan *)get(h, K_BTFPLAN);
+    Vec *B = vec(hB), *W = vec(hW);
+    if (!P || !B || !W || B == W || nrhs < 1) return CSX_EINVAL;
+    const int64_t need = (int64_t)P->n * nrhs;
+    if (B->len < need || W->len < need) return CSX_EINVAL;
+    return btf_solve(P, (const double *)B->d, (double *)W->d, (double *)B->d, nrhs);
+}
+
+extern "C" int csx_btf_info(csx_handle_t h, int64_t *info) {
+    CSX_TRY(require_ready());
+    BtfPlan *P = (BtfPlan *)get(h, K_BTFPLAN);
+    if (!P || !info) return CSX_EINVAL;
+    int64_t launches = 1;
+    for (int32_t l = 0; l < P->nlevels; l++) launches += (P->small_ptr[l + 1] > P->small_ptr[l]) ? 1 : 0;
+    info[0] = P->nb;
+    info[1] = P->nlevels;
+    info[2] = P->max_block;
+    info[3] = P->lnz;
+    info[4] = P->unz;
+    info[5] = P->fnz;
+    info[6] = (int64_t)P->large.size();
+    info[7] = launches;   // the solve's own launches; every large block adds one plus those of its two triangular plans
+    return CSX_OK;
+}

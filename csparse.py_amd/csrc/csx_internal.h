@@ -43,7 +43,7 @@ void set_error(const char *fmt, ...);
 
 #define CSX_LAUNCH_CHECK() CSX_HIP(hipGetLastError())
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN };
 
 struct Csc;
 
@@ -116,6 +116,7 @@ struct TriPlan;   // csx_trisolve.hip
 struct CholPlan;  // csx_chol.hip
 struct ShardPlan; // csx_comm.hip
 struct SnPlan;    // csx_snsolve.hip
+struct BtfPlan;   // csx_btf.hip
 
 struct Object {
     Kind kind = K_FREE;
@@ -209,6 +210,7 @@ void free_triplan(TriPlan *t);
 void free_cholplan(CholPlan *t);
 void free_shardplan(ShardPlan *t);
 void free_snplan(SnPlan *t);
+void free_btfplan(BtfPlan *t);
 // csx_snsolve.hip: supernodal schedule of a Cholesky-shaped factor for the rounding-equal order of a cholsol plan
 int sn_build(const Csc *L, const int32_t *parent, const int32_t *Lp_h, const int32_t *Gp_h, const int32_t *Gp, const int32_t *Gi,
              const double *Gx, int32_t col_levels, SnPlan **out);

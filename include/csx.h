@@ -489,6 +489,43 @@ int csx_dmperm(csx_handle_t A, int64_t seed, int32_t *p, int32_t *q, int32_t *r,
 int csx_dmperm_times(double *ms);
 int csx_dmperm_rounds(int64_t *rounds);
 
+/* ---- block triangular LU (btf_factor in csparse.py) ---------------------------------------
+ * Definition.  A square, structurally nonsingular A with the fine blocks of csx_dmperm (p, q, r, nb: every block a
+ * strongly connected component, A(p, q) block upper triangular with a zero-free diagonal) is factored as
+ * C = A(p', q') = D + F: D the entries inside the diagonal blocks, F the strictly block upper rest, both in C's column
+ * storage order.  A block's level is 0 when its rows have no entries outside the block, else 1 + the largest level of
+ * the blocks those entries reach; p', q', r' list the blocks by level, highest first, in the given order inside a level
+ * (C stays block upper triangular).  L, U, pinv = cs_lu(D) (unit diagonal first / diagonal last, pivots inside their
+ * block: the caller's dispatch).  A solve of A x = b, for every right-hand side: c = b(p'); blocks from last to first:
+ * c_i -= F_ij z_j for every row i of the block in cs_gaxpy's order (ascending column, storage order within a column;
+ * multiply and subtract rounded separately), then the block's part of cs_ipvec(pinv), cs_lsolve(L), cs_usolve(U),
+ * operation for operation; x(q') = z.  One order, fixed by the factors: every run and every right-hand side of a block
+ * gives the bits of a one-column solve.
+ * csx_btf_split: p, q (n), r (nb + 1) from csx_dmperm; writes p_out, q_out (n), r_out (nb + 1), level (nb, non-increasing),
+ *   *nlevels, and the NEW matrix handles *D and *F.  Level analysis on the host (one pass over A's pattern), the
+ *   permutation and the split on the device.
+ * csx_btf_plan: a NEW plan handle (freed by csx_free) from L, U (cs_lu of D), F and the host arrays pinv (n), p, q (n),
+ *   r (nb + 1), level (nb) that csx_btf_split returned.  The plan keeps copies of everything it reads.  Blocks of at
+ *   most 96 rows are solved one wave per (block, 64 right-hand sides) with the tile in LDS, one launch per level;
+ *   larger blocks by a product with F over their rows and csx_tri_analyse-style exact plans of their own parts of L
+ *   and U (a few launches each).
+ * csx_btf_solve: B (n-by-nrhs, row-major) overwritten with X; work: another block of at least n nrhs entries.  B's rows
+ *   are read before any is written (the last launch writes x(q)).  No atomics.
+ * csx_btf_info: info[8] = blocks, levels, largest block, nnz(L), nnz(U), nnz(F), blocks on the large-block path,
+ *   launches of a solve not counting the large blocks' own.
+ * Errors: CSX_EINVAL for a stale or wrong-kind handle, a non-square or pattern-only matrix, p / q / pinv that are not
+ *   permutations, r not strictly increasing from 0 to n, A(p, q) not block upper triangular, levels that do not fall,
+ *   pivots outside their block, L / U rows without their diagonal or with entries outside the block, F entries that
+ *   reach a block of the same or a higher level, B and work the same vector or shorter than n nrhs, nrhs < 1.
+ * Memory: the plan holds n (4 ints) + nnz(L) + nnz(U) + nnz(F) entries (12 bytes each) + n (2 doubles) on the device,
+ *   and the two parts of every large block's factors with their plans. */
+int csx_btf_split(csx_handle_t A, const int32_t *p, const int32_t *q, const int32_t *r, int32_t nb, int32_t *p_out,
+                  int32_t *q_out, int32_t *r_out, int32_t *level, int32_t *nlevels, csx_handle_t *D, csx_handle_t *F);
+int csx_btf_plan(csx_handle_t L, csx_handle_t U, csx_handle_t F, const int32_t *pinv, const int32_t *p, const int32_t *q,
+                 const int32_t *r, const int32_t *level, int32_t nb, csx_handle_t *plan);
+int csx_btf_solve(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t nrhs);
+int csx_btf_info(csx_handle_t plan, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
