@@ -27,12 +27,6 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C);   // csx_spgemm.hip
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-static int upload_i32(int32_t **d, const int32_t *h, size_t count) {
-    CSX_TRY(dalloc(d, count));
-    if (count) CSX_HIP(hipMemcpyAsync(*d, h, count * sizeof(int32_t), hipMemcpyHostToDevice, ctx().stream));
-    return CSX_OK;
-}
-
 static bool is_permutation(const int32_t *p, int32_t n) {
     std::vector<char> seen((size_t)n, 0);
     for (int32_t k = 0; k < n; k++) {
@@ -66,14 +60,6 @@ __global__ __launch_bounds__(256) void k_selector(int32_t n, int stacked, double
     }
 }
 
-static void drop_fields(Csc *M) {
-    dfree(M->p);
-    dfree(M->i);
-    dfree(M->x);
-    M->p = M->i = nullptr;
-    M->x = nullptr;
-}
-
 static int add_device(const Csc *A, const Csc *B, double alpha, double beta, Csc *C) {
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
@@ -87,28 +73,19 @@ static int add_device(const Csc *A, const Csc *B, double alpha, double beta, Csc
     S.m = 2 * n;
     S.n = n;
     S.nnz = 2 * n;
-    int st = dalloc(&cat.p, (size_t)2 * n + 1);
-    if (st == CSX_OK) st = dalloc(&cat.i, (size_t)tot);
-    if (st == CSX_OK && values) st = dalloc(&cat.x, (size_t)tot);
-    if (st == CSX_OK) st = dalloc(&S.p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&S.i, (size_t)2 * n);
-    if (st == CSX_OK && values) st = dalloc(&S.x, (size_t)2 * n);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_cat_ptr, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, n, A->p, B->p, cat.p);
-        hipLaunchKernelGGL(k_selector, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, n, 1, alpha, beta, S.p, S.i, S.x);
-        hipError_t e = hipSuccess;
-        if (A->nnz) e = hipMemcpyAsync(cat.i, A->i, (size_t)A->nnz * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && B->nnz) e = hipMemcpyAsync(cat.i + A->nnz, B->i, (size_t)B->nnz * 4, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && values && A->nnz) e = hipMemcpyAsync(cat.x, A->x, (size_t)A->nnz * 8, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess && values && B->nnz)
-            e = hipMemcpyAsync(cat.x + A->nnz, B->x, (size_t)B->nnz * 8, hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) st = CSX_ERUNTIME;
-    }
-    if (st == CSX_OK) st = multiply_device(&cat, &S, C);
-    (void)hipStreamSynchronize(s);
-    drop_fields(&cat);
-    drop_fields(&S);
-    return st;
+    CSX_TRY(dalloc(&cat.p, (size_t)2 * n + 1));
+    CSX_TRY(dalloc(&cat.i, (size_t)tot));
+    if (values) CSX_TRY(dalloc(&cat.x, (size_t)tot));
+    CSX_TRY(dalloc(&S.p, (size_t)n + 1));
+    CSX_TRY(dalloc(&S.i, (size_t)2 * n));
+    if (values) CSX_TRY(dalloc(&S.x, (size_t)2 * n));
+    hipLaunchKernelGGL(k_cat_ptr, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, n, A->p, B->p, cat.p);
+    hipLaunchKernelGGL(k_selector, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, n, 1, alpha, beta, S.p, S.i, S.x);
+    if (A->nnz) CSX_HIP(hipMemcpyAsync(cat.i, A->i, (size_t)A->nnz * 4, hipMemcpyDeviceToDevice, s));
+    if (B->nnz) CSX_HIP(hipMemcpyAsync(cat.i + A->nnz, B->i, (size_t)B->nnz * 4, hipMemcpyDeviceToDevice, s));
+    if (values && A->nnz) CSX_HIP(hipMemcpyAsync(cat.x, A->x, (size_t)A->nnz * 8, hipMemcpyDeviceToDevice, s));
+    if (values && B->nnz) CSX_HIP(hipMemcpyAsync(cat.x + A->nnz, B->x, (size_t)B->nnz * 8, hipMemcpyDeviceToDevice, s));
+    return multiply_device(&cat, &S, C);   // (synchronises: cat and S go back to the pool with nothing queued on them)
 }
 
 static int dupl_device(const Csc *A, Csc *C) {
@@ -116,16 +93,11 @@ static int dupl_device(const Csc *A, Csc *C) {
     Csc I;
     I.m = I.n = A->n;
     I.nnz = A->n;
-    int st = dalloc(&I.p, (size_t)A->n + 1);
-    if (st == CSX_OK) st = dalloc(&I.i, (size_t)A->n);
-    if (st == CSX_OK && A->x) st = dalloc(&I.x, (size_t)A->n);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_selector, dim3(blocks_for((int64_t)A->n + 1)), dim3(256), 0, s, A->n, 0, 1.0, 0.0, I.p, I.i, I.x);
-        st = multiply_device(A, &I, C);
-    }
-    (void)hipStreamSynchronize(s);
-    drop_fields(&I);
-    return st;
+    CSX_TRY(dalloc(&I.p, (size_t)A->n + 1));
+    CSX_TRY(dalloc(&I.i, (size_t)A->n));
+    if (A->x) CSX_TRY(dalloc(&I.x, (size_t)A->n));
+    hipLaunchKernelGGL(k_selector, dim3(blocks_for((int64_t)A->n + 1)), dim3(256), 0, s, A->n, 0, 1.0, 0.0, I.p, I.i, I.x);
+    return multiply_device(A, &I, C);
 }
 
 // ---- order-preserving filters --------------------------------------------------------------------------
@@ -184,26 +156,21 @@ static int drop_device(const Csc *A, int mode, double tol, Csc *C) {
     C->m = A->m;
     C->n = n;
     C->owns = true;
-    int32_t *cnt = nullptr;
+    DevBuf<int32_t> cnt;
     int64_t total = 0;
-    int st = dalloc(&cnt, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&C->p, (size_t)n + 1);
-    if (st == CSX_OK) {
-        if (n) hipLaunchKernelGGL(k_filter<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, mode, tol, A->p, A->i, A->x,
-                                  nullptr, cnt, nullptr, nullptr, nullptr, nullptr);
-        st = scan_exclusive_i32(cnt, C->p, n, &total);
-    }
-    if (st == CSX_OK) {
-        C->nnz = (int32_t)total;
-        st = dalloc(&C->i, (size_t)total);
-        if (st == CSX_OK && A->x) st = dalloc(&C->x, (size_t)total);
-    }
-    if (st == CSX_OK && n)
+    CSX_TRY(cnt.alloc((size_t)n + 1));
+    CSX_TRY(dalloc(&C->p, (size_t)n + 1));
+    if (n) hipLaunchKernelGGL(k_filter<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, mode, tol, A->p, A->i, A->x,
+                              nullptr, cnt, nullptr, nullptr, nullptr, nullptr);
+    CSX_TRY(scan_exclusive_i32(cnt, C->p, n, &total));
+    C->nnz = (int32_t)total;
+    CSX_TRY(dalloc(&C->i, (size_t)total));
+    if (A->x) CSX_TRY(dalloc(&C->x, (size_t)total));
+    if (n)
         hipLaunchKernelGGL(k_filter<true>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, mode, tol, A->p, A->i, A->x, nullptr,
                            nullptr, C->p, C->i, C->x, nullptr);
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    dfree(cnt);
-    return st;
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 static int symperm_device(const Csc *A, const int32_t *pinv_h, bool values, Csc *C) {
@@ -212,40 +179,34 @@ static int symperm_device(const Csc *A, const int32_t *pinv_h, bool values, Csc 
     const bool with_values = values && A->x;
     C->m = C->n = n;
     C->owns = true;
-    int32_t *pinv = nullptr, *cnt = nullptr, *optr = nullptr, *ri = nullptr;
-    uint32_t *key = nullptr, *skey = nullptr;
-    double *rx = nullptr;
+    DevBuf<int32_t> pinv, cnt, optr, ri;
+    DevBuf<uint32_t> key, skey;
+    DevBuf<double> rx;
     int64_t total = 0;
-    int st = CSX_OK;
-    if (pinv_h) st = upload_i32(&pinv, pinv_h, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&cnt, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&optr, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&C->p, (size_t)n + 1);
-    if (st == CSX_OK) {
-        if (n) hipLaunchKernelGGL(k_filter<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, (int)KEEP_UPPER, 0.0, A->p, A->i,
-                                  nullptr, pinv, cnt, nullptr, nullptr, nullptr, nullptr);
-        st = scan_exclusive_i32(cnt, optr, n, &total);
-    }
-    if (st == CSX_OK) {
-        C->nnz = (int32_t)total;
-        st = dalloc(&C->i, (size_t)total);
-        if (st == CSX_OK && with_values) st = dalloc(&C->x, (size_t)total);
-        if (st == CSX_OK) st = dalloc(&ri, (size_t)total);
-        if (st == CSX_OK) st = dalloc(&key, (size_t)total);
-        if (st == CSX_OK) st = dalloc(&skey, (size_t)total);
-        if (st == CSX_OK && with_values) st = dalloc(&rx, (size_t)total);
-    }
-    if (st == CSX_OK && total > 0) {
+    if (pinv_h) CSX_TRY(upload(pinv, pinv_h, (size_t)n));
+    CSX_TRY(cnt.alloc((size_t)n + 1));
+    CSX_TRY(optr.alloc((size_t)n + 1));
+    CSX_TRY(dalloc(&C->p, (size_t)n + 1));
+    if (n) hipLaunchKernelGGL(k_filter<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, (int)KEEP_UPPER, 0.0, A->p, A->i,
+                              nullptr, pinv, cnt, nullptr, nullptr, nullptr, nullptr);
+    CSX_TRY(scan_exclusive_i32(cnt, optr, n, &total));
+    C->nnz = (int32_t)total;
+    CSX_TRY(dalloc(&C->i, (size_t)total));
+    if (with_values) CSX_TRY(dalloc(&C->x, (size_t)total));
+    CSX_TRY(ri.alloc((size_t)total));
+    CSX_TRY(key.alloc((size_t)total));
+    CSX_TRY(skey.alloc((size_t)total));
+    if (with_values) CSX_TRY(rx.alloc((size_t)total));
+    if (total > 0) {
         hipLaunchKernelGGL(k_filter<true>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, (int)KEEP_UPPER, 0.0, A->p, A->i,
                            with_values ? A->x : nullptr, pinv, nullptr, optr, ri, rx, key);
-        st = stable_sort_by_key(key, (const uint32_t *)ri, rx, total, (uint32_t)n, skey, (uint32_t *)C->i, C->x);
-        if (st == CSX_OK) st = boundaries_from_sorted(skey, total, n, C->p);
-    } else if (st == CSX_OK) {
-        if (hipMemsetAsync(C->p, 0, ((size_t)n + 1) * sizeof(int32_t), s) != hipSuccess) st = CSX_ERUNTIME;
+        CSX_TRY(stable_sort_by_key(key, (const uint32_t *)ri.get(), rx, total, (uint32_t)n, skey, (uint32_t *)C->i, C->x));
+        CSX_TRY(boundaries_from_sorted(skey, total, n, C->p));
+    } else {
+        CSX_HIP(hipMemsetAsync(C->p, 0, ((size_t)n + 1) * sizeof(int32_t), s));
     }
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    for (void *q : {(void *)pinv, (void *)cnt, (void *)optr, (void *)ri, (void *)key, (void *)skey, (void *)rx}) dfree(q);
-    return st;
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 // ---- cs_permute ----------------------------------------------------------------------------------------
@@ -281,26 +242,20 @@ static int permute_device(const Csc *A, const int32_t *pinv_h, const int32_t *q_
     C->n = n;
     C->nnz = A->nnz;
     C->owns = true;
-    int32_t *pinv = nullptr, *q = nullptr, *len = nullptr;
-    int st = CSX_OK;
-    if (pinv_h) st = upload_i32(&pinv, pinv_h, (size_t)A->m);
-    if (st == CSX_OK && q_h) st = upload_i32(&q, q_h, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&len, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&C->p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&C->i, (size_t)A->nnz);
-    if (st == CSX_OK && with_values) st = dalloc(&C->x, (size_t)A->nnz);
-    if (st == CSX_OK) {
-        if (n) hipLaunchKernelGGL(k_perm_len, dim3(blocks_for(n)), dim3(256), 0, s, n, A->p, q, len);
-        st = scan_exclusive_i32(len, C->p, n, nullptr);
-    }
-    if (st == CSX_OK && n)
+    DevBuf<int32_t> pinv, q, len;
+    if (pinv_h) CSX_TRY(upload(pinv, pinv_h, (size_t)A->m));
+    if (q_h) CSX_TRY(upload(q, q_h, (size_t)n));
+    CSX_TRY(len.alloc((size_t)n + 1));
+    CSX_TRY(dalloc(&C->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&C->i, (size_t)A->nnz));
+    if (with_values) CSX_TRY(dalloc(&C->x, (size_t)A->nnz));
+    if (n) hipLaunchKernelGGL(k_perm_len, dim3(blocks_for(n)), dim3(256), 0, s, n, A->p, q, len);
+    CSX_TRY(scan_exclusive_i32(len, C->p, n, nullptr));
+    if (n)
         hipLaunchKernelGGL(k_perm_fill, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, A->p, A->i, with_values ? A->x : nullptr,
                            pinv, q, C->p, C->i, C->x);
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    dfree(pinv);
-    dfree(q);
-    dfree(len);
-    return st;
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 // ---- cs_compress ---------------------------------------------------------------------------------------
@@ -310,34 +265,26 @@ static int compress_device(int32_t m, int32_t n, int64_t nz, const int32_t *Ti, 
     C->n = n;
     C->nnz = (int32_t)nz;
     C->owns = true;
-    int32_t *di = nullptr, *dj = nullptr;
-    uint32_t *skey = nullptr;
-    double *dx = nullptr;
-    int st = dalloc(&C->p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&C->i, (size_t)nz);
-    if (st == CSX_OK && Tx) st = dalloc(&C->x, (size_t)nz);
-    if (st == CSX_OK && nz == 0) {
-        if (hipMemsetAsync(C->p, 0, ((size_t)n + 1) * sizeof(int32_t), s) != hipSuccess) st = CSX_ERUNTIME;
-        if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-        return st;
+    CSX_TRY(dalloc(&C->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&C->i, (size_t)nz));
+    if (Tx) CSX_TRY(dalloc(&C->x, (size_t)nz));
+    if (nz == 0) {
+        CSX_HIP(hipMemsetAsync(C->p, 0, ((size_t)n + 1) * sizeof(int32_t), s));
+        CSX_HIP(hipStreamSynchronize(s));
+        return CSX_OK;
     }
-    if (st == CSX_OK) st = upload_i32(&di, Ti, (size_t)nz);
-    if (st == CSX_OK) st = upload_i32(&dj, Tj, (size_t)nz);
-    if (st == CSX_OK && Tx) {
-        st = dalloc(&dx, (size_t)nz);
-        if (st == CSX_OK && hipMemcpyAsync(dx, Tx, (size_t)nz * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess)
-            st = CSX_ERUNTIME;
-    }
-    if (st == CSX_OK) st = dalloc(&skey, (size_t)nz);
-    if (st == CSX_OK)
-        st = stable_sort_by_key((const uint32_t *)dj, (const uint32_t *)di, dx, nz, (uint32_t)n, skey, (uint32_t *)C->i, C->x);
-    if (st == CSX_OK) st = boundaries_from_sorted(skey, nz, n, C->p);
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    dfree(di);
-    dfree(dj);
-    dfree(dx);
-    dfree(skey);
-    return st;
+    DevBuf<int32_t> di, dj;
+    DevBuf<uint32_t> skey;
+    DevBuf<double> dx;
+    CSX_TRY(upload(di, Ti, (size_t)nz));
+    CSX_TRY(upload(dj, Tj, (size_t)nz));
+    if (Tx) CSX_TRY(upload(dx, Tx, (size_t)nz));
+    CSX_TRY(skey.alloc((size_t)nz));
+    CSX_TRY(stable_sort_by_key((const uint32_t *)dj.get(), (const uint32_t *)di.get(), dx, nz, (uint32_t)n, skey, (uint32_t *)C->i,
+                               C->x));
+    CSX_TRY(boundaries_from_sorted(skey, nz, n, C->p));
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 // ---- column block (sharding a matrix by columns) ---------------------------------------------
@@ -384,13 +331,9 @@ __global__ __launch_bounds__(256) void k_norm1(int32_t n, const int32_t *__restr
 
 template <class F>
 static int make_csc(csx_handle_t *out, F &&build) {
-    Csc *C = new Csc();
-    const int st = build(C);
-    if (st != CSX_OK) {
-        free_csc(C);
-        return st;
-    }
-    *out = put(K_CSC, C);
+    std::unique_ptr<Csc> C(new Csc());
+    CSX_TRY(build(C.get()));
+    *out = put(K_CSC, C.release());
     return CSX_OK;
 }
 
@@ -461,15 +404,13 @@ extern "C" int csx_norm1(csx_handle_t hA, double *out) {
     Csc *A = csc(hA);
     if (!A || !out || !A->x) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
-    unsigned long long *d = nullptr, h[2] = {0, 0};
-    CSX_TRY(dalloc(&d, 2));
-    int st = CSX_OK;
-    if (hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) st = CSX_ERUNTIME;
-    if (st == CSX_OK && A->n > 0) hipLaunchKernelGGL(k_norm1, dim3(blocks_for(A->n)), dim3(256), 0, s, A->n, A->p, A->x, d);
-    if (st == CSX_OK && (hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess))
-        st = CSX_ERUNTIME;
-    dfree(d);
-    CSX_TRY(st);
+    DevBuf<unsigned long long> d;
+    unsigned long long h[2] = {0, 0};
+    CSX_TRY(d.alloc(2));
+    CSX_HIP(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), s));
+    if (A->n > 0) hipLaunchKernelGGL(k_norm1, dim3(blocks_for(A->n)), dim3(256), 0, s, A->n, A->p, A->x, d);
+    CSX_HIP(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
     double v;
     std::memcpy(&v, &h[0], sizeof v);
     *out = v;

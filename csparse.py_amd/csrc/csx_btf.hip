@@ -20,6 +20,13 @@ int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);
 constexpr int BTF_SMALL = 96;   // rows of the largest block solved with its tile in LDS (csx_lu_blocks' limit)
 
 struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (local indices) and exact triangular plans of them
+    BtfLarge() = default;
+    BtfLarge(const BtfLarge &) = delete;
+    BtfLarge &operator=(const BtfLarge &) = delete;
+    ~BtfLarge() {
+        destroy(pl);
+        destroy(pu);
+    }
     int32_t r0 = 0, nr = 0;
     Csc L, U;
     TriPlan *pl = nullptr, *pu = nullptr;
@@ -28,42 +35,20 @@ struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (loc
 struct BtfPlan {
     int32_t n = 0, nb = 0, nlevels = 0, max_block = 0;
     int64_t lnz = 0, unz = 0, fnz = 0;
-    int32_t *p = nullptr, *q = nullptr, *pinv = nullptr, *r = nullptr;
+    DevBuf<int32_t> p, q, pinv, r;
     // row programs: L without its diagonal (ascending column), U without its diagonal (DESCENDING column), F (ascending
     // column); the L / U indices are (column - first row of the block) * 64: LDS offsets of the block's X tile
-    int32_t *Lp = nullptr, *Li = nullptr, *Up = nullptr, *Ui = nullptr;
-    double *Lx = nullptr, *Ld = nullptr, *Ux = nullptr, *Ud = nullptr;
+    DevBuf<int32_t> Lp, Li, Up, Ui;
+    DevBuf<double> Lx, Ld, Ux, Ud;
     Csc Ft;                              // F' = the rows of F in cs_gaxpy's order
-    int32_t *small = nullptr;            // small blocks grouped by level (level 0 first), ascending block inside a level
+    DevBuf<int32_t> small;               // small blocks grouped by level (level 0 first), ascending block inside a level
     std::vector<int32_t> small_ptr;      // [nlevels + 1] into small
     std::vector<int32_t> small_rows;     // [nlevels] largest small block of the level
     std::vector<std::vector<int32_t>> large_of_level;   // indices into large
-    std::vector<BtfLarge *> large;
+    std::vector<std::unique_ptr<BtfLarge>> large;
 };
 
-static void free_csc_fields(Csc &A) {
-    dfree(A.p);
-    dfree(A.i);
-    dfree(A.x);
-    A.p = A.i = nullptr;
-    A.x = nullptr;
-}
-
-void free_btfplan(BtfPlan *P) {
-    if (!P) return;
-    for (void *d : {(void *)P->p, (void *)P->q, (void *)P->pinv, (void *)P->r, (void *)P->Lp, (void *)P->Li, (void *)P->Up,
-                    (void *)P->Ui, (void *)P->Lx, (void *)P->Ld, (void *)P->Ux, (void *)P->Ud, (void *)P->small})
-        dfree(d);
-    free_csc_fields(P->Ft);
-    for (BtfLarge *B : P->large) {
-        free_triplan(B->pl);
-        free_triplan(B->pu);
-        free_csc_fields(B->L);
-        free_csc_fields(B->U);
-        delete B;
-    }
-    delete P;
-}
+void destroy(BtfPlan *P) { delete P; }
 
 static unsigned grid_for(int64_t count) { return (unsigned)std::max<int64_t>(1, (count + 255) / 256); }
 
@@ -106,11 +91,10 @@ __global__ __launch_bounds__(256) void k_btf_fill(int32_t n, const int32_t *__re
 static int split_device(const Csc *C, const std::vector<int32_t> &blk_h, Csc *D, Csc *F) {
     hipStream_t s = ctx().stream;
     const int32_t n = C->n;
-    DevScope tmp;
-    int32_t *blk = nullptr, *dcnt = nullptr, *fcnt = nullptr;
-    CSX_TRY(tmp.alloc(&blk, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&dcnt, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&fcnt, (size_t)n + 1));
+    DevBuf<int32_t> blk, dcnt, fcnt;
+    CSX_TRY(blk.alloc((size_t)n + 1));
+    CSX_TRY(dcnt.alloc((size_t)n + 1));
+    CSX_TRY(fcnt.alloc((size_t)n + 1));
     if (n) CSX_HIP(hipMemcpyAsync(blk, blk_h.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     if (n) hipLaunchKernelGGL(k_btf_count, dim3(grid_for(n)), dim3(256), 0, s, n, C->p, C->i, blk, dcnt, fcnt);
     CSX_LAUNCH_CHECK();
@@ -198,32 +182,22 @@ static int block_factor(const Csc *M, int32_t r0, int32_t nr, Csc *out) {
     return CSX_OK;
 }
 
-template <class T>
-static int upload(T **d, const T *h, size_t count) {
-    CSX_TRY(dalloc(d, count));
-    if (count) CSX_HIP(hipMemcpyAsync(*d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
-    return CSX_OK;
-}
-
-static int strip(const Csc *M, bool upper, const int32_t *row_r0, const int32_t *row_r1, int *bad, int32_t **Pp,
-                 int32_t **Pi, double **Px, double **Pd) {
+static int strip(const Csc *M, bool upper, const int32_t *row_r0, const int32_t *row_r1, int *bad, DevBuf<int32_t> &Pp,
+                 DevBuf<int32_t> &Pi, DevBuf<double> &Px, DevBuf<double> &Pd) {
     hipStream_t s = ctx().stream;
     const int32_t n = M->n;
     Csc T;
     CSX_TRY(transpose_device(M, true, &T));
     const int64_t cnt = std::max<int64_t>(0, (int64_t)T.nnz - n);
-    int st = dalloc(Pp, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(Pi, (size_t)cnt);
-    if (st == CSX_OK) st = dalloc(Px, (size_t)cnt);
-    if (st == CSX_OK) st = dalloc(Pd, (size_t)n);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_btf_strip, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, T.p, T.i, T.x,
-                           row_r0, row_r1, *Pp, *Pi, *Px, *Pd, bad);
-        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
-    }
-    (void)hipStreamSynchronize(s);
-    free_csc_fields(T);
-    return st;
+    CSX_TRY(Pp.alloc((size_t)n + 1));
+    CSX_TRY(Pi.alloc((size_t)cnt));
+    CSX_TRY(Px.alloc((size_t)cnt));
+    CSX_TRY(Pd.alloc((size_t)n));
+    hipLaunchKernelGGL(k_btf_strip, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, T.p, T.i, T.x,
+                       row_r0, row_r1, Pp, Pi, Px, Pd, bad);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ the solve --
@@ -326,7 +300,7 @@ static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32
             CSX_LAUNCH_CHECK();
         }
         for (int32_t li : P->large_of_level[l]) {
-            BtfLarge *G = P->large[li];
+            BtfLarge *G = P->large[li].get();
             hipLaunchKernelGGL(k_btf_rows, dim3(grid_for((int64_t)G->nr * k)), dim3(256), 0, s, G->r0, G->nr, P->p, P->pinv,
                                P->Ft.p, P->Ft.i, P->Ft.x, B, W, k);
             CSX_LAUNCH_CHECK();
@@ -427,16 +401,12 @@ extern "C" int csx_btf_split(csx_handle_t hA, const int32_t *p, const int32_t *q
     *nlevels = L;
     csx_handle_t hC = 0;
     CSX_TRY(csx_permute(hA, pinv_new.data(), q_out, 1, &hC));
-    Csc *D = new Csc(), *F = new Csc();
-    int st = split_device(csc(hC), blk_new, D, F);
+    std::unique_ptr<Csc> D(new Csc()), F(new Csc());
+    const int st = split_device(csc(hC), blk_new, D.get(), F.get());
     csx_free(hC);
-    if (st != CSX_OK) {
-        free_csc(D);
-        free_csc(F);
-        return st;
-    }
-    *hD = put(K_CSC, D);
-    *hF = put(K_CSC, F);
+    CSX_TRY(st);
+    *hD = put(K_CSC, D.release());
+    *hF = put(K_CSC, F.release());
     return CSX_OK;
 }
 
@@ -458,7 +428,7 @@ extern "C" int csx_btf_plan(csx_handle_t hL, csx_handle_t hU, csx_handle_t hF, c
         for (int32_t i = r[b]; i < r[b + 1]; i++)
             if (pinv[i] < r[b] || pinv[i] >= r[b + 1]) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
-    BtfPlan *P = new BtfPlan();
+    std::unique_ptr<BtfPlan> P(new BtfPlan());
     P->n = n;
     P->nb = nb;
     P->nlevels = nlev;
@@ -487,52 +457,46 @@ extern "C" int csx_btf_plan(csx_handle_t hL, csx_handle_t hU, csx_handle_t hF, c
                 small_h.push_back(b);
                 P->small_rows[l] = std::max(P->small_rows[l], nr);
             } else {
-                BtfLarge *G = new BtfLarge();
-                G->r0 = r[b];
-                G->nr = nr;
                 P->large_of_level[l].push_back((int32_t)P->large.size());
-                P->large.push_back(G);
+                P->large.emplace_back(new BtfLarge());
+                P->large.back()->r0 = r[b];
+                P->large.back()->nr = nr;
             }
         }
         P->small_ptr.push_back((int32_t)small_h.size());
         run_end = run_begin;
     }
-    DevScope tmp;
-    int32_t *row_r0 = nullptr, *row_r1 = nullptr, *row_lev = nullptr;
-    int *bad = nullptr;
-    int st = CSX_OK;
-    auto fail = [&](int code) {
-        free_btfplan(P);
-        return code;
-    };
-    for (auto [d, h] : {std::make_pair(&row_r0, &r0h), std::make_pair(&row_r1, &r1h), std::make_pair(&row_lev, &levh)}) {
-        if ((st = upload(d, h->data(), (size_t)n)) != CSX_OK) return fail(st);
-        tmp.held.push_back(*d);
-    }
-    if ((st = tmp.alloc(&bad, 1)) != CSX_OK) return fail(st);
-    if (hipMemsetAsync(bad, 0, sizeof(int), s) != hipSuccess) return fail(CSX_ERUNTIME);
-    if ((st = upload(&P->p, p, (size_t)n)) || (st = upload(&P->q, q, (size_t)n)) || (st = upload(&P->pinv, pinv, (size_t)n)) ||
-        (st = upload(&P->r, r, (size_t)nb + 1)) || (st = upload(&P->small, small_h.data(), small_h.size())))
-        return fail(st);
-    if ((st = strip(L, false, row_r0, row_r1, bad, &P->Lp, &P->Li, &P->Lx, &P->Ld)) != CSX_OK) return fail(st);
-    if ((st = strip(U, true, row_r0, row_r1, bad, &P->Up, &P->Ui, &P->Ux, &P->Ud)) != CSX_OK) return fail(st);
-    if ((st = transpose_device(F, true, &P->Ft)) != CSX_OK) return fail(st);
+    DevBuf<int32_t> row_r0, row_r1, row_lev;
+    DevBuf<int> bad;
+    CSX_TRY(upload(row_r0, r0h));
+    CSX_TRY(upload(row_r1, r1h));
+    CSX_TRY(upload(row_lev, levh));
+    CSX_TRY(bad.alloc(1));
+    CSX_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    CSX_TRY(upload(P->p, p, (size_t)n));
+    CSX_TRY(upload(P->q, q, (size_t)n));
+    CSX_TRY(upload(P->pinv, pinv, (size_t)n));
+    CSX_TRY(upload(P->r, r, (size_t)nb + 1));
+    CSX_TRY(upload(P->small, small_h));
+    CSX_TRY(strip(L, false, row_r0, row_r1, bad, P->Lp, P->Li, P->Lx, P->Ld));
+    CSX_TRY(strip(U, true, row_r0, row_r1, bad, P->Up, P->Ui, P->Ux, P->Ud));
+    CSX_TRY(transpose_device(F, true, &P->Ft));
     if (n) hipLaunchKernelGGL(k_btf_check_f, dim3(grid_for(n)), dim3(256), 0, s, n, P->Ft.p, P->Ft.i, row_r1, row_lev, bad);
     int hbad = 0;
-    if (hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        return fail(CSX_ERUNTIME);
-    if (hbad) return fail(CSX_EINVAL);
+    CSX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    if (hbad) return CSX_EINVAL;
     P->lnz = L->nnz;
     P->unz = U->nnz;
     P->fnz = F->nnz;
-    for (BtfLarge *G : P->large) {
-        if ((st = block_factor(L, G->r0, G->nr, &G->L)) || (st = block_factor(U, G->r0, G->nr, &G->U)) ||
-            (st = tri_analyse_raw(&G->L, CSX_TRI_L, &G->pl)) || (st = tri_analyse_raw(&G->U, CSX_TRI_U, &G->pu)))
-            return fail(st);
+    for (const std::unique_ptr<BtfLarge> &G : P->large) {
+        CSX_TRY(block_factor(L, G->r0, G->nr, &G->L));
+        CSX_TRY(block_factor(U, G->r0, G->nr, &G->U));
+        CSX_TRY(tri_analyse_raw(&G->L, CSX_TRI_L, &G->pl));
+        CSX_TRY(tri_analyse_raw(&G->U, CSX_TRI_U, &G->pu));
     }
     CSX_HIP(hipStreamSynchronize(s));
-    *out = put(K_BTFPLAN, P);
+    *out = put(K_BTFPLAN, P.release());
     return CSX_OK;
 }
 

@@ -48,7 +48,7 @@ namespace csx {
 
 // csx_cholsym.hip
 int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t **Lp_out,
-                         int32_t **Li_out, int32_t **row_ptr_out, int32_t **row_col_out, int32_t **row_pos_out,
+                         int32_t **Li_out, DevBuf<int32_t> *row_ptr_out, DevBuf<int32_t> *row_col_out, DevBuf<int32_t> *row_pos_out,
                          int32_t *cp_host_out);
 // csx_trisolve.hip
 struct TriPlan;
@@ -407,13 +407,6 @@ __global__ __launch_bounds__(64 * CH_WAVES) void k_chol_dense_trees(const Tree *
     for (int e = lane; e < nent; e += 64) Lx[base + e] = a[e];
 }
 
-template <class T>
-static int upload(T **d, const std::vector<T> &h) {
-    CSX_TRY(dalloc(d, h.size()));
-    if (!h.empty())
-        CSX_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
-    return CSX_OK;
-}
 
 
 // ---- banded factors: the whole window in registers --------------------------------------------------------
@@ -682,89 +675,79 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
     if (ctx().opt.chol_clique && ctx().opt.chol_dense_trees && !pinv && A->nnz > 0) {
         // A forest of cliques on consecutive columns (csx_cholclique.hip): L.p / L.i follow from the counts, the values are
         // one read of A's upper part and one write of L, a block to a wave.  The caller's S must be that forest's.
-        CliqueForest F;
+        std::unique_ptr<CliqueForest> own;   // not cached: this call's finding
         bool ok = false, same = false;
-        int st = CSX_OK;
         const bool cached = A->clique != nullptr && (!A->clique->sparse || ctx().opt.chol_forest);
         if (cached) {
-            // csx_schol's finding for this matrix (dropped by csx_csc_invalidate when the arrays change): a shallow copy; L.p is
-            // copied out of it below instead of taken
-            F = *A->clique;
+            // csx_schol's finding for this matrix (dropped by csx_csc_invalidate when the arrays change): read where it lies; L.p
+            // is copied out of it below instead of taken
             ok = true;
         } else {
-            st = clique_forest(A, &F, &ok);
+            own.reset(new CliqueForest());
+            CSX_TRY(clique_forest(A, own.get(), &ok));
         }
-        if (st == CSX_OK && ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
+        CliqueForest &F = cached ? *A->clique : *own;
+        if (ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
             lap("clique forest");
             // The block kernel is started FIRST; the caller's S (host arrays) is uploaded and compared with the forest's beside it
             // on a stream of its own.  An S that is not A's costs a factor that is thrown away.
             // (the kernel writes L through the forest's own column pointers: an S with another lnz is refused before anything runs)
-            if ((int64_t)L->nnz != F.lnz) {
-                if (!cached) free_clique(&F);
-                return CSX_EINVAL;
-            }
-            CliqueCompare cmp;
-            st = clique_matches_begin(F, parent, cp, &cmp);
-            int *d_notspd = nullptr;
+            if ((int64_t)L->nnz != F.lnz) return CSX_EINVAL;
+            DevBuf<int> d_notspd;
             constexpr int NOTSPD_NONE = 0x7f7f7f7f;     // the flag's idle value: set by a byte fill on the device, no host slot in flight
             int hflag = NOTSPD_NONE;
             bool queued = false;                        // device work of this call may be in flight
-            if (st == CSX_OK) st = dalloc(&L->i, (size_t)L->nnz);
-            if (st == CSX_OK) st = dalloc(&L->x, (size_t)L->nnz);
-            if (st == CSX_OK) st = dalloc(&d_notspd, 1);
-            if (st == CSX_OK && cached) {
-                st = dalloc(&L->p, (size_t)n + 1);
-                if (st == CSX_OK && hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
-                    st = CSX_ERUNTIME;
-            }
-            int32_t *own_cp = nullptr;                  // not cached: L takes the forest's column pointers
-            if (st == CSX_OK) {
-                if (!cached) {
-                    L->p = F.cp;
-                    own_cp = F.cp;
-                }
-                if (hipMemsetAsync(d_notspd, 0x7f, sizeof(int), s) != hipSuccess) st = CSX_ERUNTIME;
+            CliqueCompare cmp;
+            auto factor = [&]() -> int {
+                CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
+                CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
+                CSX_TRY(d_notspd.alloc(1));
+                if (cached) {
+                    CSX_TRY(dalloc(&L->p, (size_t)n + 1));
+                    CSX_HIP(hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+                } else {
+                    L->p = F.cp;                        // not cached: L takes the forest's column pointers (the comparison reads
+                }                                       // them until clique_matches_end; F lets go of them below)
                 queued = true;
-            }
-            lap("allocations");
-            if (st == CSX_OK) (void)hipEventRecord(ev_a, s);
-            if (st == CSX_OK) st = chol_clique_numeric(A, F, L, d_notspd, nullptr, !ctx().opt.chol_exact);
-            if (st == CSX_OK) (void)hipEventRecord(ev_b, s);
-            lap("block kernel");
-            if (st == CSX_OK) st = clique_matches_run(&cmp);
-            lap("S uploaded");
-            if (st == CSX_OK && (hipMemcpyAsync(&hflag, d_notspd, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                                 hipStreamSynchronize(s) != hipSuccess)) {
-                set_error("cs_chol: %s", hipGetErrorString(hipGetLastError()));
-                st = CSX_ERUNTIME;
-            }
+                CSX_HIP(hipMemsetAsync(d_notspd, 0x7f, sizeof(int), s));
+                lap("allocations");
+                (void)hipEventRecord(ev_a, s);
+                CSX_TRY(chol_clique_numeric(A, F, L, d_notspd, nullptr, !ctx().opt.chol_exact));
+                (void)hipEventRecord(ev_b, s);
+                lap("block kernel");
+                CSX_TRY(clique_matches_run(&cmp));
+                lap("S uploaded");
+                if (hipMemcpyAsync(&hflag, d_notspd, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess) {
+                    set_error("cs_chol: %s", hipGetErrorString(hipGetLastError()));
+                    return CSX_ERUNTIME;
+                }
+                return CSX_OK;
+            };
+            int st = clique_matches_begin(F, parent, cp, &cmp);
+            if (st == CSX_OK) st = factor();
             {
                 const int st2 = clique_matches_end(&cmp, &same);    // (always: it waits for the side stream and frees)
                 if (st == CSX_OK) st = st2;
             }
-            if (own_cp) F.cp = nullptr;                 // L owns it now (the caller frees L on any error)
+            if (!cached && L->p == F.cp) (void)F.cp.release();      // L owns them now (the caller frees L on any error)
             // on a failure after work was queued the block kernel may still be writing L.i / L.x, which the caller hands back to
             // the pool: nothing is released before the stream has drained
             if (st != CSX_OK && queued) (void)hipStreamSynchronize(s);
             lap("numeric (blocks) + S compared");
-            if (st == CSX_OK && !same) st = CSX_EINVAL;        // S.cp / S.parent do not belong to A
-            if (st == CSX_OK) {
-                numeric_ms();
-                g_chol_path = F.sparse ? 2 : 1;
-            }
-            dfree(d_notspd);
-            if (!cached) free_clique(&F);
             if (st != CSX_OK) return st;
+            if (!same) return CSX_EINVAL;               // S.cp / S.parent do not belong to A
+            numeric_ms();
+            g_chol_path = F.sparse ? 2 : 1;
             return hflag != NOTSPD_NONE ? CSX_ENOTSPD : CSX_OK;
         }
-        if (!cached) free_clique(&F);
-        if (st != CSX_OK) return st;
         lap("no clique forest");
     }
-    int32_t *d_rp = nullptr, *d_rc = nullptr, *d_rpos = nullptr, *d_pinv = nullptr, *d_win = nullptr;
-    int32_t *d_small_cols = nullptr, *d_level_cols = nullptr, *d_level_ptr = nullptr;
-    Tree *d_trees = nullptr, *d_dense = nullptr;
-    int *d_flags = nullptr;
+    DevBuf<int32_t> d_rp, d_rc, d_rpos, d_pinv, d_win;
+    DevBuf<int32_t> d_small_cols, d_level_cols, d_level_ptr, d_col_level, d_split, d_sn_cols, d_sn_ptr;
+    DevBuf<Tree> d_trees, d_dense;
+    DevBuf<SnDesc> d_sns;
+    DevBuf<int> d_flags;
     CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &d_rp, &d_rc, &d_rpos, nullptr));
     lap("pattern (device)");
     Forest F;
@@ -858,30 +841,28 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
     lap("partition_forest");
     std::vector<int32_t> hpinv;
     if (pinv) hpinv.assign(pinv, pinv + n);
-    int st = dalloc(&L->x, (size_t)L->nnz);
-    if (st == CSX_OK && pinv) st = upload(&d_pinv, hpinv);
-    if (st == CSX_OK) st = dalloc(&d_win, (size_t)L->nnz);
-    if (st == CSX_OK) st = dalloc(&d_flags, 3);   // [0] foreign symbolic data, [1] first non-positive pivot, [2] band width
-    if (st == CSX_OK) st = upload(&d_trees, other_trees);
-    if (st == CSX_OK) st = upload(&d_dense, dense_trees);
-    if (st == CSX_OK) st = upload(&d_small_cols, F.small_cols);
-    if (st == CSX_OK) st = upload(&d_level_cols, F.level_cols);
-    if (st == CSX_OK) st = upload(&d_level_ptr, F.level_ptr);
-    int32_t *d_col_level = nullptr, *d_split = nullptr;
-    if (st == CSX_OK && !col_level_h.empty()) {
-        st = dalloc(&d_split, (size_t)n);
-        if (st == CSX_OK) (void)hipMemsetAsync(d_split, 0x7f, (size_t)n * sizeof(int32_t), s);   // "no inside update seen"
+    CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
+    if (pinv) CSX_TRY(upload(d_pinv, hpinv));
+    CSX_TRY(d_win.alloc((size_t)L->nnz));
+    CSX_TRY(d_flags.alloc(3));   // [0] foreign symbolic data, [1] first non-positive pivot, [2] band width
+    CSX_TRY(upload(d_trees, other_trees));
+    CSX_TRY(upload(d_dense, dense_trees));
+    CSX_TRY(upload(d_small_cols, F.small_cols));
+    CSX_TRY(upload(d_level_cols, F.level_cols));
+    CSX_TRY(upload(d_level_ptr, F.level_ptr));
+    if (!col_level_h.empty()) {
+        CSX_TRY(d_split.alloc((size_t)n));
+        (void)hipMemsetAsync(d_split, 0x7f, (size_t)n * sizeof(int32_t), s);   // "no inside update seen"
+        CSX_TRY(upload(d_col_level, col_level_h));
     }
-    SnDesc *d_sns = nullptr;
-    int32_t *d_sn_cols = nullptr, *d_sn_ptr = nullptr;
-    if (st == CSX_OK && !col_level_h.empty()) st = upload(&d_col_level, col_level_h);
-    if (st == CSX_OK && !sns.empty()) {
-        st = upload(&d_sns, sns);
-        if (st == CSX_OK) st = upload(&d_sn_cols, sn_cols);
-        if (st == CSX_OK) st = upload(&d_sn_ptr, sn_group_ptr);
+    if (!sns.empty()) {
+        CSX_TRY(upload(d_sns, sns));
+        CSX_TRY(upload(d_sn_cols, sn_cols));
+        CSX_TRY(upload(d_sn_ptr, sn_group_ptr));
     }
     int hflags[2] = {0, 0x7fffffff};
-    if (st == CSX_OK) {
+    int st = CSX_OK;
+    {
         (void)hipEventRecord(ev_a, s);
         (void)hipMemsetAsync(d_win, 0xff, (size_t)L->nnz * sizeof(int32_t), s);
         (void)hipMemcpyAsync(d_flags, hflags, sizeof hflags, hipMemcpyHostToDevice, s);
@@ -1004,22 +985,6 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
         }
     }
     lap("numeric (device)");
-    dfree(d_rp);
-    dfree(d_rc);
-    dfree(d_rpos);
-    dfree(d_pinv);
-    dfree(d_win);
-    dfree(d_flags);
-    dfree(d_trees);
-    dfree(d_dense);
-    dfree(d_small_cols);
-    dfree(d_level_cols);
-    dfree(d_level_ptr);
-    dfree(d_col_level);
-    dfree(d_split);
-    dfree(d_sns);
-    dfree(d_sn_cols);
-    dfree(d_sn_ptr);
     if (st != CSX_OK) return st;
     if (hflags[0]) return CSX_EINVAL;                 // S.cp / S.parent do not belong to A
     if (hflags[1] != 0x7fffffff) return CSX_ENOTSPD;  // some pivot d <= 0
@@ -1028,6 +993,15 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
 
 // ---- solve phase ----------------------------------------------------------------------------------
 struct CholPlan {
+    CholPlan() = default;
+    CholPlan(const CholPlan &) = delete;
+    CholPlan &operator=(const CholPlan &) = delete;
+    ~CholPlan() {
+        if (g_exec) (void)hipGraphExecDestroy(g_exec);   // before the arrays its launches read
+        destroy(sn);
+        destroy(fwd);
+        destroy(bwd);
+    }
     hipGraphExec_t g_exec = nullptr;   // "tri.graph": the supernodal solve's launches, captured for the block g_X / g_nrhs
     double *g_X = nullptr;
     int32_t g_nrhs = 0;
@@ -1040,30 +1014,30 @@ struct CholPlan {
     double g_capture_ms = 0.0;
     int32_t n = 0;
     const Csc *L = nullptr;  // not owned; must outlive the plan
-    TriPlan *fwd = nullptr, *bwd = nullptr;
-    int32_t *perm = nullptr;    // device: x[j] = b[perm[j]]  (perm = inverse of pinv), nullptr = identity
-    double *scratch = nullptr;  // n * scratch_rhs doubles for the permuted block (generic path)
+    TriPlan *fwd = nullptr, *bwd = nullptr;   // owned (~CholPlan)
+    DevBuf<int32_t> perm;       // device: x[j] = b[perm[j]]  (perm = inverse of pinv), nullptr = identity
+    DevBuf<double> scratch;     // n * scratch_rhs doubles for the permuted block (generic path)
     int64_t scratch_len = 0;
     // forest-of-small-trees fast path
     bool local = false;
     int32_t ntrees = 0, max_nodes = 0;
-    Tree *trees = nullptr;
-    Tree *trees_by_size = nullptr;   // the same list biggest first: what k_cholsol_local launches by (trees_biggest_first), made at its first launch
-    int32_t *tree_nodes = nullptr, *local_id = nullptr;
+    DevBuf<Tree> trees;
+    DevBuf<Tree> trees_by_size;      // the same list biggest first: what k_cholsol_local launches by (trees_biggest_first), made at its first launch
+    DevBuf<int32_t> tree_nodes, local_id;
     // per-tree solve programs, indexed by position k in tree_nodes (row a of tree t: k = first + a):
     // forward terms [f_ptr[k], f_ptr[k+1]) and backward terms [b_ptr[k], b_ptr[k+1]) as
     // (local row id, value) in the reference's update order, plus the diagonal of that row
-    int32_t *f_ptr = nullptr, *f_idx = nullptr, *b_ptr = nullptr, *b_idx = nullptr;
-    double *f_val = nullptr, *b_val = nullptr, *diagk = nullptr, *diagb = nullptr;
-    int32_t *rev_pos = nullptr;
+    DevBuf<int32_t> f_ptr, f_idx, b_ptr, b_idx;
+    DevBuf<double> f_val, b_val, diagk, diagb;
+    DevBuf<int32_t> rev_pos;
     int dense_bs = 0;  // > 0: every tree is a dense lower-triangular block of this size on contiguous rows
-    double *dense_b = nullptr;  // dense only: backward program with every row reversed (sweep-position order)
+    DevBuf<double> dense_b;     // dense only: backward program with every row reversed (sweep-position order)
     // dense, block size 16/32/64, the matrix cores' operands: the inverses W_ii of the diagonal tiles as A fragments (NB tiles of 256
     // doubles per block; the backward sweep reads them transposed) -- and the off-diagonal tiles, which are L's own numbers and are
     // read where they lie: in L.x (a plan on consecutive columns of L: `clique`), or in `lcopy`, the blocks' packed columns copied
     // out of the programs (a plan the general analysis made: it never assumed an order of the rows inside a column of L)
-    double *frag_f = nullptr;
-    double *lcopy = nullptr;
+    DevBuf<double> frag_f;
+    DevBuf<double> lcopy;
     // exact (default): every right-hand side is solved in the reference's operation order -- substitution
     // kernels, level walker in source order: bit-identical to cs_lsolve + cs_ltsolve.  !exact
     // (csx_cholsol_set_order(plan, 0)): results equal to rounding; dense 16/32/64 blocks go to the matrix cores
@@ -1074,22 +1048,22 @@ struct CholPlan {
     bool clique = false, clique_zero_pivot = false;
     // forests of small trees that are NOT equal dense blocks (cliques of unequal sizes, small sparse trees), rounding-equal order:
     // the trees made dense and bucketed by size class, solved on the matrix cores (csx_trimfma.hip); null: not built / refused
-    RaggedMfma *rag = nullptr;
+    std::unique_ptr<RaggedMfma> rag;
     bool rag_tried = false;
     // csx_cholsol_factor on such a forest in the rounding-equal order: the plan holds the block list and `rag` (built straight from
     // L's columns) and nothing else; a solve the matrix cores do not take (the exact order, the guard's refusal) goes to `full`,
     // the general plan of the same factor, made the first time it is needed
     bool lite = false;
     bool lite_cliques = false;   // ... and every block is a CLIQUE (dense): the exact order can take the padded size classes below
-    CholPlan *full = nullptr;
+    std::unique_ptr<CholPlan> full;
     // exact order on a forest of cliques of UNEQUAL sizes (round 5): the blocks bucketed by size class 8 / 16 / 32 / 64, every block
     // padded at its end with the identity up to its class, the register-resident exact kernel (k_cholsol_dense_exact_dpp) run
     // per class on programs cut out of L.x -- the padding changes no bit (see the kernel)
     struct ExactClass {
         int32_t count = 0;
-        Tree *trees = nullptr;
-        int32_t *nodes = nullptr, *f_ptr = nullptr, *b_ptr = nullptr;
-        double *f_val = nullptr, *dense_b = nullptr, *diagk = nullptr, *diagb = nullptr;
+        DevBuf<Tree> trees;
+        DevBuf<int32_t> nodes, f_ptr, b_ptr;
+        DevBuf<double> f_val, dense_b, diagk, diagb;
     } xc[5];
     bool xc_built = false;
     bool mfma_tried = false;  // fragments were built, or refused by the growth guard
@@ -1098,47 +1072,10 @@ struct CholPlan {
     std::vector<int32_t> parent_h;   // elimination tree of a Cholesky-shaped L (empty: not one)
     int32_t col_levels = 0;          // its height in columns
     bool sn_tried = false;
-    SnPlan *sn = nullptr;
+    SnPlan *sn = nullptr;   // owned (~CholPlan)
 };
 
-void free_cholplan(CholPlan *P) {
-    if (!P) return;
-    if (P->g_exec) (void)hipGraphExecDestroy(P->g_exec);
-    free_snplan(P->sn);
-    ragged_free(P->rag);
-    free_cholplan(P->full);
-    for (auto &c : P->xc) {
-        dfree(c.trees);
-        dfree(c.nodes);
-        dfree(c.f_ptr);
-        dfree(c.b_ptr);
-        dfree(c.f_val);
-        dfree(c.dense_b);
-        dfree(c.diagk);
-        dfree(c.diagb);
-    }
-    free_triplan(P->fwd);
-    free_triplan(P->bwd);
-    dfree(P->perm);
-    dfree(P->scratch);
-    dfree(P->trees);
-    dfree(P->trees_by_size);
-    dfree(P->tree_nodes);
-    dfree(P->local_id);
-    dfree(P->f_ptr);
-    dfree(P->f_idx);
-    dfree(P->f_val);
-    dfree(P->b_ptr);
-    dfree(P->b_idx);
-    dfree(P->b_val);
-    dfree(P->diagk);
-    dfree(P->diagb);
-    dfree(P->rev_pos);
-    dfree(P->dense_b);
-    dfree(P->frag_f);
-    dfree(P->lcopy);
-    delete P;
-}
+void destroy(CholPlan *P) { delete P; }
 
 // G lanes to a column (4 where the columns are short)
 template <int G>
@@ -1945,18 +1882,17 @@ static int cholsol_plan_clique(CholPlan *P, int32_t bs) {
     const Csc *L = P->L;
     const int32_t n = P->n, ntrees = n / bs;
     const int64_t tot = (int64_t)ntrees * (bs * (bs - 1) / 2);
-    DevScope tmp;
-    int *zero = nullptr;
-    CSX_TRY(tmp.alloc(&zero, 1));
+    DevBuf<int> zero;
+    CSX_TRY(zero.alloc(1));
     CSX_HIP(hipMemsetAsync(zero, 0, sizeof(int), s));
-    if (!P->trees) CSX_TRY(dalloc(&P->trees, (size_t)ntrees));          // (a plan csx_cholsol_factor made has its block list already)
-    if (!P->tree_nodes) CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
-    CSX_TRY(dalloc(&P->f_ptr, (size_t)n + 1));
-    CSX_TRY(dalloc(&P->b_ptr, (size_t)n + 1));
-    CSX_TRY(dalloc(&P->diagk, (size_t)n));
-    CSX_TRY(dalloc(&P->diagb, (size_t)n));
-    CSX_TRY(dalloc(&P->f_val, (size_t)tot + 128));
-    CSX_TRY(dalloc(&P->dense_b, (size_t)tot + 128));
+    if (!P->trees) CSX_TRY(P->trees.alloc((size_t)ntrees));          // (a plan csx_cholsol_factor made has its block list already)
+    if (!P->tree_nodes) CSX_TRY(P->tree_nodes.alloc((size_t)n));
+    CSX_TRY(P->f_ptr.alloc((size_t)n + 1));
+    CSX_TRY(P->b_ptr.alloc((size_t)n + 1));
+    CSX_TRY(P->diagk.alloc((size_t)n));
+    CSX_TRY(P->diagb.alloc((size_t)n));
+    CSX_TRY(P->f_val.alloc((size_t)tot + 128));
+    CSX_TRY(P->dense_b.alloc((size_t)tot + 128));
     hipLaunchKernelGGL(k_clique_plan<false>, dim3((unsigned)ntrees), dim3(256), 0, s, ntrees, bs, L->p, L->x, P->trees,
                        P->tree_nodes, P->f_ptr, P->b_ptr, P->f_val, P->dense_b, P->diagk, P->diagb, nullptr, nullptr, nullptr,
                        zero);
@@ -1979,9 +1915,9 @@ static int cholsol_clique_local(CholPlan *P) {
     hipStream_t s = ctx().stream;
     const int32_t bs = P->dense_bs;
     const int64_t tot = (int64_t)P->ntrees * (bs * (bs - 1) / 2);
-    CSX_TRY(dalloc(&P->f_idx, (size_t)tot + 8));
-    CSX_TRY(dalloc(&P->b_idx, (size_t)tot + 8));
-    CSX_TRY(dalloc(&P->b_val, (size_t)tot + 128));
+    CSX_TRY(P->f_idx.alloc((size_t)tot + 8));
+    CSX_TRY(P->b_idx.alloc((size_t)tot + 8));
+    CSX_TRY(P->b_val.alloc((size_t)tot + 128));
     hipLaunchKernelGGL(k_clique_plan<true>, dim3((unsigned)P->ntrees), dim3(256), 0, s, P->ntrees, bs, P->L->p, P->L->x, P->trees,
                        P->tree_nodes, P->f_ptr, P->b_ptr, P->f_val, P->dense_b, P->diagk, P->diagb, P->f_idx, P->b_idx, P->b_val,
                        nullptr);
@@ -1989,10 +1925,11 @@ static int cholsol_clique_local(CholPlan *P) {
     return CSX_OK;
 }
 
-static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
+// *out holds the plan from the start, a failure part way included
+static int cholsol_plan(const Csc *L, const int32_t *pinv, std::unique_ptr<CholPlan> *out) {
     hipStream_t s = ctx().stream;
-    CholPlan *P = new CholPlan();
-    *out = P;
+    out->reset(new CholPlan());
+    CholPlan *P = out->get();
     const int32_t n = L->n;
     P->n = n;
     P->L = L;
@@ -2011,7 +1948,7 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
             if (pinv[k] < 0 || pinv[k] >= n) return CSX_EINVAL;
             perm[(size_t)pinv[k]] = k;
         }
-        CSX_TRY(upload(&P->perm, perm));
+        CSX_TRY(upload(P->perm, perm));
     }
     if (n > 0 && ctx().opt.chol_clique && ctx().opt.cholsol_dense_blocks) {
         int32_t bs = 0;
@@ -2025,11 +1962,10 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
     tri_set_mate(P->bwd, P->fwd);   // the rounding-equal order may run L' in push form on the rows of L
     if (n == 0) return CSX_OK;
     // forest of small trees?  (needs a Cholesky-shaped L: diagonal first, rows ascending)
-    DevScope tmp;   // d_parent, d_flag, flen, blen: released on every exit
-    int32_t *d_parent = nullptr;
-    int *d_flag = nullptr;
-    CSX_TRY(tmp.alloc(&d_parent, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_flag, 1));
+    DevBuf<int32_t> d_parent, nrm, is_start, block_id, start, flen, blen;   // released on every exit
+    DevBuf<int> d_flag, stats;   // stats: [0] spare, [1] roots, [2] widest block
+    CSX_TRY(d_parent.alloc((size_t)n));
+    CSX_TRY(d_flag.alloc(1));
     CSX_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), s));
     const bool short_cols = (int64_t)L->nnz < 8 * (int64_t)n;     // a wave per column of three entries is 61 idle lanes
     if (short_cols)
@@ -2043,12 +1979,10 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
     bool on_device = false;
     Forest F;
     if (ctx().opt.chol_clique && ctx().opt.chol_forest) {
-        int32_t *nrm = nullptr, *is_start = nullptr, *block_id = nullptr, *start = nullptr;
-        int *stats = nullptr;   // [0] spare, [1] roots, [2] widest block
-        CSX_TRY(tmp.alloc(&nrm, (size_t)n));
-        CSX_TRY(tmp.alloc(&is_start, (size_t)n + 1));
-        CSX_TRY(tmp.alloc(&block_id, (size_t)n + 1));
-        CSX_TRY(tmp.alloc(&stats, 4));
+        CSX_TRY(nrm.alloc((size_t)n));
+        CSX_TRY(is_start.alloc((size_t)n + 1));
+        CSX_TRY(block_id.alloc((size_t)n + 1));
+        CSX_TRY(stats.alloc(4));
         CSX_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int), s));
         const unsigned nbk = (unsigned)(((int64_t)n + 255) / 256);
         hipLaunchKernelGGL(k_plan_reach, dim3(nbk), dim3(256), 0, s, n, L->p, L->i, nrm);
@@ -2062,17 +1996,17 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
         CSX_HIP(hipStreamSynchronize(s));
         if (unsorted) return CSX_OK;
         if (hs[1] == nblocks) {                  // one root to a block: the blocks ARE the trees
-            CSX_TRY(tmp.alloc(&start, (size_t)nblocks + 1));
-            CSX_TRY(dalloc(&P->trees, (size_t)nblocks));
+            CSX_TRY(start.alloc((size_t)nblocks + 1));
+            CSX_TRY(P->trees.alloc((size_t)nblocks));
             hipLaunchKernelGGL(k_plan_block_first, dim3(nbk), dim3(256), 0, s, n, is_start, block_id, start);
             hipLaunchKernelGGL(k_plan_trees, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, s, (int32_t)nblocks, start, P->trees,
                                stats);
             CSX_HIP(hipMemcpyAsync(hs, stats, sizeof hs, hipMemcpyDeviceToHost, s));
             CSX_HIP(hipStreamSynchronize(s));
             if (hs[2] <= 256) {
-                CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
-                CSX_TRY(dalloc(&P->local_id, (size_t)n));
-                CSX_TRY(dalloc(&P->rev_pos, (size_t)n));
+                CSX_TRY(P->tree_nodes.alloc((size_t)n));
+                CSX_TRY(P->local_id.alloc((size_t)n));
+                CSX_TRY(P->rev_pos.alloc((size_t)n));
                 hipLaunchKernelGGL(k_plan_nodes, dim3(nbk), dim3(256), 0, s, n, is_start, block_id, start, P->tree_nodes, P->local_id,
                                    P->rev_pos);
                 CSX_LAUNCH_CHECK();
@@ -2081,8 +2015,7 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
                 on_device = true;
                 lap("partition (device)");
             } else {
-                dfree(P->trees);
-                P->trees = nullptr;
+                P->trees.reset();
             }
         }
     }
@@ -2121,13 +2054,13 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
         std::vector<int32_t> local((size_t)n, 0);
         for (const Tree &t : F.small)
             for (int32_t a = 0; a < t.count; a++) local[(size_t)F.small_cols[(size_t)(t.first + a)]] = a;
-        CSX_TRY(upload(&P->trees, F.small));
-        CSX_TRY(upload(&P->tree_nodes, F.small_cols));
-        CSX_TRY(upload(&P->local_id, local));
+        CSX_TRY(upload(P->trees, F.small));
+        CSX_TRY(upload(P->tree_nodes, F.small_cols));
+        CSX_TRY(upload(P->local_id, local));
         std::vector<int32_t> rev((size_t)n, 0);
         for (const Tree &t : F.small)
             for (int32_t a = 0; a < t.count; a++) rev[(size_t)(t.first + a)] = t.first + t.count - 1 - a;
-        CSX_TRY(upload(&P->rev_pos, rev));
+        CSX_TRY(upload(P->rev_pos, rev));
         lap("node lists (host)");
         ntrees = (int32_t)F.small.size();
         max_tree = F.max_tree;
@@ -2135,23 +2068,21 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
     const int32_t *Gp, *Gi;
     const double *Gx, *Gd;
     tri_gather_arrays(P->fwd, &Gp, &Gi, &Gx, &Gd);
-    int32_t *flen = nullptr, *blen = nullptr;
-    CSX_TRY(tmp.alloc(&flen, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&blen, (size_t)n + 1));
-    CSX_TRY(dalloc(&P->f_ptr, (size_t)n + 1));
-    CSX_TRY(dalloc(&P->b_ptr, (size_t)n + 1));
-    CSX_TRY(dalloc(&P->diagk, (size_t)n));
-    CSX_TRY(dalloc(&P->diagb, (size_t)n));
+    CSX_TRY(flen.alloc((size_t)n + 1));
+    CSX_TRY(blen.alloc((size_t)n + 1));
+    CSX_TRY(P->f_ptr.alloc((size_t)n + 1));
+    CSX_TRY(P->b_ptr.alloc((size_t)n + 1));
+    CSX_TRY(P->diagk.alloc((size_t)n));
+    CSX_TRY(P->diagb.alloc((size_t)n));
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
     hipLaunchKernelGGL(k_pack_len, dim3(nb), dim3(256), 0, s, n, P->tree_nodes, P->rev_pos, Gp, L->p, flen, blen);
     int64_t ftot = 0, btot = 0;
-    int st = scan_exclusive_i32(flen, P->f_ptr, n, &ftot);
-    if (st == CSX_OK) st = scan_exclusive_i32(blen, P->b_ptr, n, &btot);
-    CSX_TRY(st);
-    CSX_TRY(dalloc(&P->f_idx, (size_t)ftot + 8));
-    CSX_TRY(dalloc(&P->f_val, (size_t)ftot + 128));
-    CSX_TRY(dalloc(&P->b_idx, (size_t)btot + 8));
-    CSX_TRY(dalloc(&P->b_val, (size_t)btot + 128));
+    CSX_TRY(scan_exclusive_i32(flen, P->f_ptr, n, &ftot));
+    CSX_TRY(scan_exclusive_i32(blen, P->b_ptr, n, &btot));
+    CSX_TRY(P->f_idx.alloc((size_t)ftot + 8));
+    CSX_TRY(P->f_val.alloc((size_t)ftot + 128));
+    CSX_TRY(P->b_idx.alloc((size_t)btot + 8));
+    CSX_TRY(P->b_val.alloc((size_t)btot + 128));
     if (short_cols)
         hipLaunchKernelGGL(k_pack_fill<4>, dim3((unsigned)(((int64_t)n + 63) / 64)), dim3(256), 0, s, n, P->tree_nodes, P->rev_pos,
                            P->local_id, Gp, Gi, Gx, L->p, L->i, L->x, P->f_ptr, P->f_idx, P->f_val, P->b_ptr, P->b_idx, P->b_val,
@@ -2190,7 +2121,7 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, CholPlan **out) {
             int32_t btot_h = 0;
             CSX_HIP(hipMemcpyAsync(&btot_h, P->b_ptr + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             CSX_HIP(hipStreamSynchronize(s));
-            CSX_TRY(dalloc(&P->dense_b, (size_t)btot_h + 128));
+            CSX_TRY(P->dense_b.alloc((size_t)btot_h + 128));
             hipLaunchKernelGGL(k_dense_reverse_rows, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, P->b_ptr,
                                P->b_val, P->dense_b);
             CSX_LAUNCH_CHECK();
@@ -2211,15 +2142,14 @@ constexpr double MFMA_GROWTH_LIMIT = 1e3;
 static int cholsol_build_ragged(CholPlan *P) {
     if (P->rag_tried || !P->local || P->dense_bs || (!P->f_idx && !P->lite) || P->max_nodes > RAG_MAX_ROWS) return CSX_OK;
     P->rag_tried = true;
-    RaggedMfma *R = nullptr;
+    std::unique_ptr<RaggedMfma> R;
     if (P->lite)      // (csx_cholsol_factor's plan of a forest on consecutive columns: straight from L's columns)
         CSX_TRY(ragged_build(P->trees, P->ntrees, P->max_nodes, P->tree_nodes, nullptr, nullptr, nullptr, nullptr, false, &R, P->L));
     else
         CSX_TRY(ragged_build(P->trees, P->ntrees, P->max_nodes, P->tree_nodes, P->f_ptr, P->f_idx, P->f_val, P->diagk, false, &R));
     if (!R) return CSX_OK;
     P->mfma_growth = R->growth;
-    if (R->growth <= RAG_GROWTH_LIMIT) P->rag = R;     // (a NaN fails the comparison: the fused per-tree kernel stays)
-    else ragged_free(R);
+    if (R->growth <= RAG_GROWTH_LIMIT) P->rag = std::move(R);     // (a NaN fails the comparison: the fused per-tree kernel stays)
     return CSX_OK;
 }
 
@@ -2231,39 +2161,34 @@ static int cholsol_build_mfma(CholPlan *P) {
     hipStream_t s = ctx().stream;
     const int nb16 = P->dense_bs / 16;
     const int32_t bs = P->dense_bs;
-    unsigned long long *cond = nullptr, hcond = 0;
-    double *ff = nullptr, *lc = nullptr;
-    int st = dalloc(&cond, 1);
-    if (st == CSX_OK) st = dalloc(&ff, (size_t)P->ntrees * nb16 * 256);
+    DevBuf<unsigned long long> cond;
+    unsigned long long hcond = 0;
+    DevBuf<double> ff, lc;
+    CSX_TRY(cond.alloc(1));
+    CSX_TRY(ff.alloc((size_t)P->ntrees * nb16 * 256));
     // (a plan on consecutive columns of L reads the off-diagonal tiles in L.x; the general analysis' plan gets a packed copy)
     // (... or whose L.x is not 16-byte aligned -- a wrapped pointer: the copies to LDS move 16 bytes a lane)
-    if (st == CSX_OK && (!P->clique || (reinterpret_cast<uintptr_t>(P->L->x) & 15) != 0)) st = dalloc(&lc, (size_t)P->ntrees * (bs * (bs + 1) / 2));
-    if (st == CSX_OK && hipMemsetAsync(cond, 0, sizeof(unsigned long long), s) != hipSuccess) st = CSX_ERUNTIME;
-    if (st == CSX_OK) {
-        const dim3 g((unsigned)P->ntrees);
-        if (nb16 == 1)
-            hipLaunchKernelGGL(k_mfma_frags<1>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
-        else if (nb16 == 2)
-            hipLaunchKernelGGL(k_mfma_frags<2>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
-        else
-            hipLaunchKernelGGL(k_mfma_frags<4>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(&hcond, cond, sizeof hcond, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            st = CSX_ERUNTIME;
-    }
-    dfree(cond);
+    if (!P->clique || (reinterpret_cast<uintptr_t>(P->L->x) & 15) != 0) CSX_TRY(lc.alloc((size_t)P->ntrees * (bs * (bs + 1) / 2)));
+    CSX_HIP(hipMemsetAsync(cond, 0, sizeof(unsigned long long), s));
+    const dim3 g((unsigned)P->ntrees);
+    if (nb16 == 1)
+        hipLaunchKernelGGL(k_mfma_frags<1>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
+    else if (nb16 == 2)
+        hipLaunchKernelGGL(k_mfma_frags<2>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
+    else
+        hipLaunchKernelGGL(k_mfma_frags<4>, g, dim3(64), 0, s, P->trees, P->f_ptr, P->f_val, P->diagk, ff, lc, cond);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(&hcond, cond, sizeof hcond, hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    cond.reset();
     double growth = 0.0;
     std::memcpy(&growth, &hcond, sizeof growth);
     P->mfma_growth = growth;
-    if (st == CSX_OK && growth <= MFMA_GROWTH_LIMIT) {   // (a NaN fails the comparison: substitution stays)
-        P->frag_f = ff;
-        P->lcopy = lc;
-    } else {
-        dfree(ff);
-        dfree(lc);
+    if (growth <= MFMA_GROWTH_LIMIT) {   // (a NaN fails the comparison: substitution stays)
+        P->frag_f = std::move(ff);
+        P->lcopy = std::move(lc);
     }
-    return st;
+    return CSX_OK;
 }
 
 // Supernodal schedule for the rounding-equal order of a big-tree plan (nullptr when the factor gains nothing from it).
@@ -2351,14 +2276,13 @@ static int cholsol_exact_classes_build(CholPlan *P) {
     if (P->xc_built) return CSX_OK;
     hipStream_t s = ctx().stream;
     const int32_t nt = P->ntrees;
-    DevScope tmp;
-    uint32_t *key = nullptr, *id = nullptr, *skey = nullptr, *list = nullptr;
-    int32_t *bounds = nullptr;
-    CSX_TRY(tmp.alloc(&key, (size_t)nt));
-    CSX_TRY(tmp.alloc(&id, (size_t)nt));
-    CSX_TRY(tmp.alloc(&skey, (size_t)nt));
-    CSX_TRY(tmp.alloc(&list, (size_t)nt));
-    CSX_TRY(tmp.alloc(&bounds, 6));
+    DevBuf<uint32_t> key, id, skey, list;
+    DevBuf<int32_t> bounds;
+    CSX_TRY(key.alloc((size_t)nt));
+    CSX_TRY(id.alloc((size_t)nt));
+    CSX_TRY(skey.alloc((size_t)nt));
+    CSX_TRY(list.alloc((size_t)nt));
+    CSX_TRY(bounds.alloc(6));
     hipLaunchKernelGGL(k_xc_class, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, P->trees, nt, key, id);
     CSX_LAUNCH_CHECK();
     CSX_TRY(stable_sort_by_key(key, id, nullptr, nt, 5, skey, list, nullptr));
@@ -2375,14 +2299,14 @@ static int cholsol_exact_classes_build(CholPlan *P) {
         const int BS = kBS[c];
         const size_t rows = (size_t)X.count * BS, terms = (size_t)X.count * (BS * (BS - 1) / 2);
         if (terms > 0x7fffffffull) return CSX_OK;            // (32-bit program offsets: the general plan takes over; nothing built is used)
-        CSX_TRY(dalloc(&X.trees, (size_t)X.count));
-        CSX_TRY(dalloc(&X.nodes, rows));
-        CSX_TRY(dalloc(&X.f_ptr, rows + 1));
-        CSX_TRY(dalloc(&X.b_ptr, rows + 1));
-        CSX_TRY(dalloc(&X.diagk, rows));
-        CSX_TRY(dalloc(&X.diagb, rows));
-        CSX_TRY(dalloc(&X.f_val, terms + 128));
-        CSX_TRY(dalloc(&X.dense_b, terms + 128));
+        CSX_TRY(X.trees.alloc((size_t)X.count));
+        CSX_TRY(X.nodes.alloc(rows));
+        CSX_TRY(X.f_ptr.alloc(rows + 1));
+        CSX_TRY(X.b_ptr.alloc(rows + 1));
+        CSX_TRY(X.diagk.alloc(rows));
+        CSX_TRY(X.diagb.alloc(rows));
+        CSX_TRY(X.f_val.alloc(terms + 128));
+        CSX_TRY(X.dense_b.alloc(terms + 128));
 #define CSX_XCP(B_)                                                                                                                \
     hipLaunchKernelGGL(k_xc_plan<B_>, dim3((unsigned)X.count), dim3(256), 0, s, list + hb[c], P->trees, P->L->p, P->L->x, X.trees, \
                        X.nodes, X.f_ptr, X.b_ptr, X.f_val, X.dense_b, X.diagk, X.diagb, X.count)
@@ -2454,10 +2378,10 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
         }
     }
     if (P->lite) {
-        if (P->relaxed && P->rag && ctx().opt.cholsol_dense_blocks) return ragged_solve(P->rag, P->tree_nodes, nullptr, false, 2, B, nrhs, P->n);
+        if (P->relaxed && P->rag && ctx().opt.cholsol_dense_blocks) return ragged_solve(P->rag.get(), P->tree_nodes, nullptr, false, 2, B, nrhs, P->n);
         if (!P->full) CSX_TRY(cholsol_plan(P->L, nullptr, &P->full));
         P->full->relaxed = false;          // (what `full` is for: the exact order, or the order the guard left)
-        return cholsol_solve(P->full, B, nrhs);
+        return cholsol_solve(P->full.get(), B, nrhs);
     }
     const int32_t *Gp = nullptr, *Gi = nullptr;
     const double *Gx = nullptr, *Gd = nullptr;
@@ -2530,7 +2454,7 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
             return CSX_OK;
         }
         if (P->relaxed && P->rag && ctx().opt.cholsol_dense_blocks)    // trees of any shape, rounding-equal order: on the matrix cores
-            return ragged_solve(P->rag, P->tree_nodes, P->perm, false, 2, B, nrhs, P->n);
+            return ragged_solve(P->rag.get(), P->tree_nodes, P->perm, false, 2, B, nrhs, P->n);
         const size_t per_wave = (size_t)P->max_nodes * 64 * sizeof(double);
         const int waves = tile_waves_per_workgroup(per_wave, CH_WAVES);
         const int32_t chunks = (nrhs + 63) / 64;
@@ -2549,10 +2473,8 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
     if (P->perm) {
         const int64_t need = (int64_t)n * nrhs;
         if (P->scratch_len < need) {
-            dfree(P->scratch);
-            P->scratch = nullptr;
             P->scratch_len = 0;
-            CSX_TRY(dalloc(&P->scratch, (size_t)need));
+            CSX_TRY(P->scratch.alloc((size_t)need));   // (the old block goes back first)
             P->scratch_len = need;
         }
         X = P->scratch;
@@ -2633,13 +2555,9 @@ extern "C" int csx_chol(csx_handle_t hA, const int32_t *parent, const int32_t *c
     Csc *A = csc(hA);
     if (!A || !A->x || A->m != A->n || !parent || !cp || !out) return CSX_EINVAL;
     if (cp[0] != 0 || cp[A->n] < A->n) return CSX_EINVAL;
-    Csc *L = new Csc();
-    int st = chol_device(A, parent, cp, pinv, L);
-    if (st != CSX_OK) {
-        free_csc(L);
-        return st;
-    }
-    *out = put(K_CSC, L);
+    std::unique_ptr<Csc> L(new Csc());
+    CSX_TRY(chol_device(A, parent, cp, pinv, L.get()));
+    *out = put(K_CSC, L.release());
     return CSX_OK;
 }
 
@@ -2652,7 +2570,7 @@ namespace csx {
 static int g_factor_path = -1;
 static double g_factor_ms[3] = {0.0, 0.0, 0.0};   // analysis / numeric kernel (HIP events) / whole call (host clock)
 
-static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, CholPlan **Pout) {   // (A->clique may be replaced)
+static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, std::unique_ptr<CholPlan> *Pout) {   // (A->clique may be replaced)
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
     const auto t_call = std::chrono::steady_clock::now();
@@ -2662,23 +2580,17 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
     if (n > 0 && A->nnz > 0 && ctx().opt.chol_clique && ctx().opt.chol_dense_trees) {
-        CliqueForest F;
+        std::unique_ptr<CliqueForest> own;   // not cached: this call's finding, until the matrix keeps it
         bool ok = false;
         const bool cached = A->clique != nullptr && (!A->clique->sparse || ctx().opt.chol_forest);
         if (cached) {
-            F = *A->clique;
             ok = true;
         } else {
-            CSX_TRY(clique_forest(A, &F, &ok));
+            own.reset(new CliqueForest());
+            CSX_TRY(clique_forest(A, own.get(), &ok));
         }
+        CliqueForest &F = cached ? *A->clique : *own;
         g_factor_ms[0] = since(t_call);
-        struct Release {   // the forest's arrays, unless L took them
-            CliqueForest *F;
-            bool on;
-            ~Release() {
-                if (on) free_clique(F);
-            }
-        } release{&F, ok && !cached};
         if (ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
             const int32_t bs = F.max_bs;
             const bool emit = !exact && !F.sparse && F.min_bs == bs && (bs == 16 || bs == 32 || bs == 64) && ctx().opt.cholsol_dense_blocks;
@@ -2690,19 +2602,14 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
             // many csx_chol (csx_csc_invalidate drops it with every other cached plan)
             CSX_TRY(dalloc(&L->p, (size_t)n + 1));
             CSX_HIP(hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            if (!cached) {
-                free_clique_cache(A->clique);
-                A->clique = new CliqueForest(F);
-                release.on = false;   // the matrix owns the arrays now
-            }
+            if (!cached) A->clique = std::move(own);   // (F stays this finding)
             CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
             // (L.i: allocated below, once it is known whether the kernel writes it -- with the emission it does not: rows j, j + 1, ...
             // in every column of a clique, Csc::rows_pending)
             CholPlan *P = nullptr;
             CliqueEmit em;
-            DevScope tmp;
-            int *d_flags = nullptr;          // [0] first column with a non-positive pivot, [2..3] the guard's measure
-            CSX_TRY(tmp.alloc(&d_flags, 4));
+            DevBuf<int> d_flags;             // [0] first column with a non-positive pivot, [2..3] the guard's measure
+            CSX_TRY(d_flags.alloc(4));
             CSX_HIP(hipMemsetAsync(d_flags, 0x7f, sizeof(int), s));
             CSX_HIP(hipMemsetAsync(d_flags + 2, 0, 2 * sizeof(int), s));
             // cliques of UNEQUAL sizes, rounding-equal order: the block kernel writes the matrix-core operands of csx_trimfma.hip's
@@ -2710,19 +2617,11 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
             // where each block's fragments go)
             const bool emit_ragged = !emit && !exact && !F.sparse && ctx().opt.cholsol_dense_blocks &&
                                      !(F.min_bs == bs && (bs == 8 || bs == 16 || bs == 32 || bs == 64));
-            RaggedMfma *Rg = nullptr;
-            int64_t *frag_off = nullptr;
-            struct RagGuard {
-                RaggedMfma *&R;
-                int64_t *&off;
-                ~RagGuard() {
-                    ragged_free(R);
-                    dfree(off);
-                }
-            } rag_guard{Rg, frag_off};
+            std::unique_ptr<RaggedMfma> Rg;
+            DevBuf<int64_t> frag_off;
             if (emit_ragged) {
-                P = new CholPlan();
-                *Pout = P;
+                Pout->reset(new CholPlan());
+                P = Pout->get();
                 P->n = n;
                 P->L = L;
                 P->lite = true;
@@ -2731,8 +2630,8 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                 P->relaxed = true;
                 P->ntrees = F.nblocks;
                 P->max_nodes = bs;
-                CSX_TRY(dalloc(&P->trees, (size_t)F.nblocks));
-                CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
+                CSX_TRY(P->trees.alloc((size_t)F.nblocks));
+                CSX_TRY(P->tree_nodes.alloc((size_t)n));
                 CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
                 CSX_TRY(ragged_prepare_emit(P->trees, P->ntrees, bs, P->tree_nodes, &Rg, &frag_off));
                 if (Rg) {
@@ -2746,13 +2645,13 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
             const bool emit_any = emit || (emit_ragged && Rg);
             if (!emit_any) CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
             if (emit) {
-                P = new CholPlan();
-                *Pout = P;            // (the caller frees it on any error)
+                Pout->reset(new CholPlan());   // (the caller frees it on any error)
+                P = Pout->get();
                 P->n = n;
                 P->L = L;
-                CSX_TRY(dalloc(&P->frag_f, (size_t)F.nblocks * (size_t)(bs / 16) * 256));   // the W tiles; the rest is L.x
-                CSX_TRY(dalloc(&P->trees, (size_t)F.nblocks));
-                CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
+                CSX_TRY(P->frag_f.alloc((size_t)F.nblocks * (size_t)(bs / 16) * 256));   // the W tiles; the rest is L.x
+                CSX_TRY(P->trees.alloc((size_t)F.nblocks));
+                CSX_TRY(P->tree_nodes.alloc((size_t)n));
                 em.frag = P->frag_f;
                 em.cond_bits = (unsigned long long *)(d_flags + 2);
                 em.trees = P->trees;
@@ -2790,10 +2689,8 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                 P->relaxed = true;
                 P->mfma_tried = true;
                 P->mfma_growth = growth;
-                if (!(growth <= MFMA_GROWTH_LIMIT)) {     // the guard refuses the explicit inverses (a NaN too): substitution, from L.x
-                    dfree(P->frag_f);
-                    P->frag_f = nullptr;
-                }
+                if (!(growth <= MFMA_GROWTH_LIMIT))       // the guard refuses the explicit inverses (a NaN too): substitution, from L.x
+                    P->frag_f.reset();
                 g_factor_path = 3;
             } else if (emit_ragged) {
                 // the plan was made before the kernel ran (above); its matrix-core operands are in place
@@ -2804,10 +2701,8 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                     Rg->growth = growth;
                     P->mfma_growth = growth;
                     P->rag_tried = true;
-                    if (growth <= MFMA_GROWTH_LIMIT) {       // (max|L| max|W| of a block, the equal-block path's measure; a NaN fails)
-                        P->rag = Rg;
-                        Rg = nullptr;
-                    }
+                    if (growth <= MFMA_GROWTH_LIMIT)         // (max|L| max|W| of a block, the equal-block path's measure; a NaN fails)
+                        P->rag = std::move(Rg);
                 } else if (!L->i) {
                     L->rows_pending = true;
                 }
@@ -2818,8 +2713,8 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                 // list from the forest's starts; the matrix-core operands come straight from L's columns (now, or when the order is
                 // switched), the exact order of cliques runs on padded size classes cut out of L.x at the first such solve
                 // (cholsol_exact_classes_build) -- no general plan unless a solve needs one
-                P = new CholPlan();
-                *Pout = P;
+                Pout->reset(new CholPlan());
+                P = Pout->get();
                 P->n = n;
                 P->L = L;
                 P->lite = true;
@@ -2828,23 +2723,23 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                 P->relaxed = !exact;
                 P->ntrees = F.nblocks;
                 P->max_nodes = bs;
-                CSX_TRY(dalloc(&P->trees, (size_t)F.nblocks));
-                CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
+                CSX_TRY(P->trees.alloc((size_t)F.nblocks));
+                CSX_TRY(P->tree_nodes.alloc((size_t)n));
                 CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
                 if (!exact) CSX_TRY(cholsol_build_ragged(P));
                 g_factor_path = F.sparse ? 2 : 1;
             } else {
                 if (!F.sparse && F.min_bs == bs && (bs == 8 || bs == 16 || bs == 32 || bs == 64) && ctx().opt.cholsol_dense_blocks) {
                     // equal dense blocks (the forest's record says so: no k_clique_factor_shape over L.i): the programs straight from L.x
-                    P = new CholPlan();
-                    *Pout = P;
+                    Pout->reset(new CholPlan());
+                    P = Pout->get();
                     P->n = n;
                     P->L = L;
                     if (exact) {
                         // every solve in the reference's order: the default exact kernel reads L.x itself (k_cholsol_dense_exact_dpp<PACKED>),
                         // so the plan is the block list; programs are cut out of L.x only if another kernel is asked for (cholsol_solve)
-                        CSX_TRY(dalloc(&P->trees, (size_t)F.nblocks));
-                        CSX_TRY(dalloc(&P->tree_nodes, (size_t)n));
+                        CSX_TRY(P->trees.alloc((size_t)F.nblocks));
+                        CSX_TRY(P->tree_nodes.alloc((size_t)n));
                         CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
                         P->clique = true;
                         P->clique_zero_pivot = false;      // every pivot is a square root of a positive number
@@ -2857,7 +2752,7 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
                     }
                 } else {
                     CSX_TRY(cholsol_plan(L, nullptr, Pout));
-                    P = *Pout;
+                    P = Pout->get();
                 }
                 if (!exact) {
                     P->relaxed = true;
@@ -2879,8 +2774,8 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, Ch
     CSX_TRY(cholsol_plan(L, nullptr, Pout));
     if (!exact) {
         (*Pout)->relaxed = true;
-        CSX_TRY(cholsol_build_mfma(*Pout));
-        CSX_TRY(cholsol_build_sn(*Pout));
+        CSX_TRY(cholsol_build_mfma(Pout->get()));
+        CSX_TRY(cholsol_build_sn(Pout->get()));
     }
     g_factor_path = 0;
     g_factor_ms[2] = since(t_call);
@@ -2892,16 +2787,11 @@ extern "C" int csx_cholsol_factor(csx_handle_t hA, int exact, csx_handle_t *outL
     CSX_TRY(require_ready());
     Csc *A = csc(hA);
     if (!A || !A->x || A->m != A->n || !outL || !outPlan) return CSX_EINVAL;
-    Csc *L = new Csc();
-    CholPlan *P = nullptr;
-    const int st = cholsol_factor_device(hA, A, exact != 0, L, &P);
-    if (st != CSX_OK) {
-        free_cholplan(P);
-        free_csc(L);
-        return st;
-    }
-    *outL = put(K_CSC, L);
-    *outPlan = put(K_CHOLPLAN, P);
+    std::unique_ptr<Csc> L(new Csc());
+    std::unique_ptr<CholPlan> P;
+    CSX_TRY(cholsol_factor_device(hA, A, exact != 0, L.get(), &P));   // (on failure P goes first: it refers to L)
+    *outL = put(K_CSC, L.release());
+    *outPlan = put(K_CHOLPLAN, P.release());
     return CSX_OK;
 }
 
@@ -2925,13 +2815,9 @@ extern "C" int csx_cholsol_plan(csx_handle_t hL, const int32_t *pinv, csx_handle
     CSX_TRY(require_ready());
     Csc *L = csc(hL);
     if (!L || !L->x || L->m != L->n || !out) return CSX_EINVAL;
-    CholPlan *P = nullptr;
-    int st = cholsol_plan(L, pinv, &P);
-    if (st != CSX_OK) {
-        free_cholplan(P);
-        return st;
-    }
-    *out = put(K_CHOLPLAN, P);
+    std::unique_ptr<CholPlan> P;
+    CSX_TRY(cholsol_plan(L, pinv, &P));
+    *out = put(K_CHOLPLAN, P.release());
     return CSX_OK;
 }
 
@@ -2949,7 +2835,7 @@ extern "C" int csx_cholsol_info(csx_handle_t h, int32_t *local, int32_t *ntrees,
     if (P->lite && !(P->relaxed && P->rag)) {   // the general plan answers (made now if it has to be)
         if (!P->full) CSX_TRY(cholsol_plan(P->L, nullptr, &P->full));
         P->full->relaxed = false;
-        P = P->full;
+        P = P->full.get();
     }
     if (local) *local = P->local ? (P->dense_bs ? (P->relaxed && P->frag_f ? 3 : 2) : (P->relaxed && P->rag ? 5 : 1)) : (P->relaxed && P->sn && sn_usable(P->sn) ? 4 : 0);
     if (ntrees) *ntrees = P->ntrees;

@@ -449,9 +449,8 @@ int chol_supernodes(const void *d_sns, int32_t nsn, int32_t max_w, int32_t max_r
     hipStream_t s = ctx().stream;
     const int32_t npan = (max_w + NB - 1) / NB;
     const int32_t dstride = npan * NB * NB;
-    DevScope tmp;
-    double *dfac = nullptr;
-    CSX_TRY(tmp.alloc(&dfac, (size_t)nsn * dstride));
+    DevBuf<double> dfac;
+    CSX_TRY(dfac.alloc((size_t)nsn * dstride));
     for (int32_t c1 = 0; c1 < max_w; c1 += NB) {
         const int32_t below = max_rows - (c1 + NB);
         const int32_t gA = std::max(1, (below + WB_PANEL_ROWS - 1) / WB_PANEL_ROWS);
@@ -494,15 +493,14 @@ static int wide_band_run_fused(int32_t n, int32_t bw, double *W, double *dfac, i
 int chol_wide_band(int32_t n, int32_t bw, const int32_t *Lp, const int32_t *Li, double *Lx, int *notspd, int nb) {
     hipStream_t s = ctx().stream;
     if (n <= 0) return CSX_OK;
-    DevScope tmp;
-    double *W = nullptr;
+    DevBuf<double> W;
     const size_t count = (size_t)n * ((size_t)bw + 1);
-    CSX_TRY(tmp.alloc(&W, count));
+    CSX_TRY(W.alloc(count));
     CSX_HIP(hipMemsetAsync(W, 0, count * sizeof(double), s));
     const unsigned gw = (unsigned)(((int64_t)n + 3) / 4);
     const int NBv = nb == 32 ? 32 : 16;
-    double *dfac = nullptr;                              // the factored diagonal blocks, panel-major
-    CSX_TRY(tmp.alloc(&dfac, ((size_t)n / NBv + 1) * NBv * NBv));
+    DevBuf<double> dfac;                                 // the factored diagonal blocks, panel-major
+    CSX_TRY(dfac.alloc(((size_t)n / NBv + 1) * NBv * NBv));
     hipLaunchKernelGGL((k_wband_copy<true>), dim3(gw), dim3(256), 0, s, n, bw + 1, Lp, Li, Lx, W, dfac, NBv);
     if (NBv == 32) CSX_TRY(wide_band_run_fused<32>(n, bw, W, dfac, notspd));
     else CSX_TRY(wide_band_run_fused<16>(n, bw, W, dfac, notspd));

@@ -18,24 +18,23 @@ struct CliqueForest {
     bool dense_in_front = false; // ... and is rows u[k] .. k, one each, stored before any lower entry: k_chol_clique skips A.i
     bool sparse = false;         // the blocks are small TREES, not cliques (columns of L shorter than the block): parent / cp come
                                  // from the symbolic elimination on row masks (k_forest_symbolic), k_chol_clique stores compacted
-    int32_t *parent = nullptr;   // device [n]: elimination tree (csparse.py:1136-1169)
-    int32_t *cp = nullptr;       // device [n + 1]: column pointers of L (csparse.py:2069-2071)
-    int32_t *start = nullptr;    // device [nblocks + 1]: first column of every block, then n
-    unsigned long long *colmask = nullptr;   // device [n], sparse only: the rows of column k of L as bits (bit r = row start + r)
-    int32_t *order = nullptr;    // device [nblocks], blocks of UNEQUAL sizes only: the blocks biggest first (stable) -- the order the
+    DevBuf<int32_t> parent;      // device [n]: elimination tree (csparse.py:1136-1169)
+    DevBuf<int32_t> cp;          // device [n + 1]: column pointers of L (csparse.py:2069-2071)
+    DevBuf<int32_t> start;       // device [nblocks + 1]: first column of every block, then n
+    DevBuf<unsigned long long> colmask;   // device [n], sparse only: the rows of column k of L as bits (bit r = row start + r)
+    DevBuf<int32_t> order;       // device [nblocks], blocks of UNEQUAL sizes only: the blocks biggest first (stable) -- the order the
                                  // block kernel takes them in, so that the four waves of a workgroup hold blocks of like size
 };
 
-void free_clique(CliqueForest *F);
-// *ok = A's elimination forest is a set of cliques on consecutive columns (F filled; the caller frees it)
+// *ok = A's elimination forest is a set of cliques on consecutive columns (F filled)
 int clique_forest(const Csc *A, CliqueForest *F, bool *ok);
 // Are the host arrays parent[n], cp[n + 1] F's?  Three steps so that the caller's kernel runs beside the upload: _begin takes
 // the temporaries, _run (after the caller has queued its own work) uploads and compares on a side stream, _end waits and answers.
 struct CliqueCompare {
     const CliqueForest *F = nullptr;
     const int32_t *parent = nullptr, *cp = nullptr;
-    int32_t *dp = nullptr, *dc = nullptr;
-    int *bad = nullptr;
+    DevBuf<int32_t> dp, dc;      // read on the side stream: released by clique_matches_end once it has drained
+    DevBuf<int> bad;
     int h = 1;
     hipEvent_t ev = nullptr;     // recorded on the context's stream when the temporaries were taken: the side stream waits for it
 };

@@ -300,22 +300,6 @@ __global__ __launch_bounds__(256) void k_forest_symbolic(const int32_t *__restri
     if (threadIdx.x == 0) atomicAdd(lnz, s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]);
 }
 
-void free_clique(CliqueForest *F) {
-    dfree(F->parent);
-    dfree(F->cp);
-    dfree(F->start);
-    dfree(F->colmask);
-    dfree(F->order);
-    F->parent = F->cp = F->start = F->order = nullptr;
-    F->colmask = nullptr;
-}
-
-void free_clique_cache(CliqueForest *F) {
-    if (!F) return;
-    free_clique(F);
-    delete F;
-}
-
 __global__ void k_cq_init(int *flags) {
     if (threadIdx.x < 8) flags[threadIdx.x] = threadIdx.x == 6 ? 0x7fffffff : 0;
 }
@@ -333,14 +317,13 @@ __global__ __launch_bounds__(256) void k_cq_size_key(const int32_t *__restrict__
 static int clique_order(CliqueForest *F) {
     if (F->order || F->nblocks <= 0 || (F->min_bs == F->max_bs && !F->sparse)) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    uint32_t *key = nullptr, *id = nullptr;
-    CSX_TRY(tmp.alloc(&key, (size_t)F->nblocks));
-    CSX_TRY(tmp.alloc(&id, (size_t)F->nblocks));
-    CSX_TRY(dalloc(&F->order, (size_t)F->nblocks));
+    DevBuf<uint32_t> key, id;
+    CSX_TRY(key.alloc((size_t)F->nblocks));
+    CSX_TRY(id.alloc((size_t)F->nblocks));
+    CSX_TRY(F->order.alloc((size_t)F->nblocks));
     hipLaunchKernelGGL(k_cq_size_key, dim3((unsigned)((F->nblocks + 255) / 256)), dim3(256), 0, s, F->start, F->nblocks, F->max_bs, key, id);
     CSX_LAUNCH_CHECK();
-    CSX_TRY(stable_sort_by_key(key, id, nullptr, F->nblocks, (uint32_t)F->max_bs + 1, nullptr, (uint32_t *)F->order, nullptr));
+    CSX_TRY(stable_sort_by_key(key, id, nullptr, F->nblocks, (uint32_t)F->max_bs + 1, nullptr, (uint32_t *)F->order.get(), nullptr));
     CSX_HIP(hipStreamSynchronize(s));       // (key / id are temporaries)
     return CSX_OK;
 }
@@ -350,19 +333,18 @@ int clique_forest(const Csc *A, CliqueForest *F, bool *ok) {
     const int32_t n = A->n;
     if (n <= 0 || A->m != A->n) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *u = nullptr, *is_start = nullptr, *block_id = nullptr, *end_of = nullptr, *count = nullptr, *start_all = nullptr;
-    int *flags = nullptr;   // [0] not ascending, [1] not a clique forest, [2] widest block, [3] not "dense and in front"; [4..5] lnz (64 bits),
+    DevBuf<int32_t> u, is_start, block_id, end_of, count, start_all, smin;
+    DevBuf<int> flags;      // [0] not ascending, [1] not a clique forest, [2] widest block, [3] not "dense and in front"; [4..5] lnz (64 bits),
                             // [6] narrowest block, [7] number of blocks
-    CSX_TRY(tmp.alloc(&u, (size_t)n));
-    CSX_TRY(tmp.alloc(&is_start, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&block_id, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&end_of, (size_t)n));
-    CSX_TRY(tmp.alloc(&count, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&start_all, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&flags, 8));
-    CSX_TRY(dalloc(&F->parent, (size_t)n));
-    CSX_TRY(dalloc(&F->cp, (size_t)n + 1));
+    CSX_TRY(u.alloc((size_t)n));
+    CSX_TRY(is_start.alloc((size_t)n + 1));
+    CSX_TRY(block_id.alloc((size_t)n + 1));
+    CSX_TRY(end_of.alloc((size_t)n));
+    CSX_TRY(count.alloc((size_t)n + 1));
+    CSX_TRY(start_all.alloc((size_t)n + 1));
+    CSX_TRY(flags.alloc(8));
+    CSX_TRY(F->parent.alloc((size_t)n));
+    CSX_TRY(F->cp.alloc((size_t)n + 1));
     // Everything a forest of cliques needs is queued BEFORE the host looks at a flag -- one wait for the whole analysis (round 4
     // waited after the rule, after the block count and after lnz).  A matrix that fails the rule has paid for two scans and the counts
     // in vain (0.2 ms at 5M columns) and goes on to the second rule below.
@@ -380,27 +362,26 @@ int clique_forest(const Csc *A, CliqueForest *F, bool *ok) {
         // not a forest of cliques: blocks of consecutive columns closed under their upper entries?  (needs sorted upper parts,
         // like the block kernel; blocks of at most 64 columns)
         if (!ctx().opt.chol_forest || h[0]) {
-            free_clique(F);
+            *F = CliqueForest();
             return CSX_OK;
         }
-        int32_t *smin = nullptr;
-        CSX_TRY(tmp.alloc(&smin, (size_t)n));
+        CSX_TRY(smin.alloc((size_t)n));
         CSX_HIP(hipMemcpyAsync(smin, u, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
         CSX_TRY(suffix_min_i32(smin, n));
         hipLaunchKernelGGL(k_cq_init, dim3(1), dim3(64), 0, s, flags);
         hipLaunchKernelGGL(k_forest_mark, dim3(blocks_for(n)), dim3(256), 0, s, n, u, smin, is_start, flags);
         int64_t nb = 0;
         CSX_TRY(scan_exclusive_i32(is_start, block_id, n, &nb));
-        CSX_TRY(dalloc(&F->start, (size_t)nb + 1));
+        CSX_TRY(F->start.alloc((size_t)nb + 1));
         hipLaunchKernelGGL(k_forest_starts, dim3(blocks_for(n)), dim3(256), 0, s, n, is_start, block_id, F->start);
         hipLaunchKernelGGL(k_forest_widest, dim3(blocks_for(nb)), dim3(256), 0, s, (int32_t)nb, F->start, flags + 2);
         CSX_HIP(hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, s));
         CSX_HIP(hipStreamSynchronize(s));
         if (h[1] || h[2] > CLIQUE_MAX_BLOCK) {      // a negative index, or a block the wave kernel cannot hold
-            free_clique(F);
+            *F = CliqueForest();
             return CSX_OK;
         }
-        CSX_TRY(dalloc(&F->colmask, (size_t)n));
+        CSX_TRY(F->colmask.alloc((size_t)n));
         hipLaunchKernelGGL(k_forest_symbolic, dim3(blocks_for(nb * 64)), dim3(256), 0, s, F->start, (int32_t)nb, A->p, A->i, F->parent,
                            count, F->colmask, (unsigned long long *)(flags + 4));
         CSX_TRY(scan_exclusive_i32(count, F->cp, n, nullptr));
@@ -409,7 +390,7 @@ int clique_forest(const Csc *A, CliqueForest *F, bool *ok) {
         unsigned long long lz = 0;
         std::memcpy(&lz, h + 4, sizeof lz);
         if (lz > 0x7fffffffull) {
-            free_clique(F);
+            *F = CliqueForest();
             return CSX_OK;
         }
         F->n = n;
@@ -427,11 +408,11 @@ int clique_forest(const Csc *A, CliqueForest *F, bool *ok) {
     unsigned long long lnz = 0;
     std::memcpy(&lnz, h + 4, sizeof lnz);
     if (lnz > 0x7fffffffull) {   // L does not fit int32 indices: the general path reports it
-        free_clique(F);
+        *F = CliqueForest();
         return CSX_OK;
     }
     const int32_t nblocks = h[7];
-    CSX_TRY(dalloc(&F->start, (size_t)nblocks + 1));
+    CSX_TRY(F->start.alloc((size_t)nblocks + 1));
     CSX_HIP(hipMemcpyAsync(F->start, start_all, ((size_t)nblocks + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     F->n = n;
     F->nblocks = nblocks;
@@ -457,9 +438,9 @@ __global__ __launch_bounds__(256) void k_clique_compare(int32_t n, const int32_t
 // own (the context's side stream), so that csx_chol can start the block kernel first and pay only for the longer of the two.
 int clique_matches_begin(const CliqueForest &F, const int32_t *parent, const int32_t *cp, CliqueCompare *c) {
     const int32_t n = F.n;
-    CSX_TRY(dalloc(&c->dp, (size_t)n));
-    CSX_TRY(dalloc(&c->dc, (size_t)n + 1));
-    CSX_TRY(dalloc(&c->bad, 1));
+    CSX_TRY(c->dp.alloc((size_t)n));
+    CSX_TRY(c->dc.alloc((size_t)n + 1));
+    CSX_TRY(c->bad.alloc(1));
     c->parent = parent;
     c->cp = cp;
     c->F = &F;
@@ -490,11 +471,9 @@ int clique_matches_end(CliqueCompare *c, bool *same) {
     if (hipStreamSynchronize(ctx().side) != hipSuccess) st = CSX_ERUNTIME;
     if (c->ev) (void)hipEventDestroy(c->ev);
     c->ev = nullptr;
-    dfree(c->dp);
-    dfree(c->dc);
-    dfree(c->bad);
-    c->dp = c->dc = nullptr;
-    c->bad = nullptr;
+    c->dp.reset();
+    c->dc.reset();
+    c->bad.reset();
     if (st == CSX_OK) *same = c->h == 0;
     return st;
 }
@@ -1208,9 +1187,8 @@ int clique_factor_block_size(const Csc *L, int32_t *bs) {
     const int32_t n = L->n;
     if (n <= 0 || L->m != n || !L->x) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int *stats = nullptr;
-    CSX_TRY(tmp.alloc(&stats, 4));
+    DevBuf<int> stats;
+    CSX_TRY(stats.alloc(4));
     int h[4] = {0, 0, 0, 0};
     CSX_HIP(hipMemsetAsync(stats, 0, sizeof h, s));
     hipLaunchKernelGGL(k_clique_factor_shape, dim3(blocks_for((int64_t)n * 16)), dim3(256), 0, s, n, L->nnz, L->p, L->i, stats);

@@ -165,14 +165,14 @@ __global__ __launch_bounds__(256) void k_sym_unpack(int64_t lnz, const double *_
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// On success the five outputs are device arrays owned by the caller (dfree):
+// On success the five outputs are device arrays, Lp and Li raw for the caller's Csc to own:
 //   Lp (n+1), Li (lnz), row_ptr (n+1), row_col (lnz), row_pos (lnz); the row view includes the diagonal
 //   as the LAST entry of each row.
 // Counts-only mode (cs_schol): cp == nullptr and cp_host_out != nullptr -- the column counts of L are
 // computed from the same walks (emit the column of every entry, sort, boundaries) and returned on the
 // host as column pointers; the five device outputs are not produced.
 int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t **Lp_out,
-                         int32_t **Li_out, int32_t **row_ptr_out, int32_t **row_col_out, int32_t **row_pos_out,
+                         int32_t **Li_out, DevBuf<int32_t> *row_ptr_out, DevBuf<int32_t> *row_col_out, DevBuf<int32_t> *row_pos_out,
                          int32_t *cp_host_out) {
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
@@ -193,142 +193,103 @@ int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp,
             seen[(size_t)pinv[j]] = 1;
         }
     }
-    int32_t *d_parent = nullptr, *d_first = nullptr, *d_post = nullptr, *d_postinv = nullptr, *d_pinv = nullptr, *d_cp = nullptr;
-    int32_t *cnt = nullptr, *sptr0 = nullptr, *sptr = nullptr, *items = nullptr;
-    uint32_t *skey = nullptr, *srow = nullptr, *k1 = nullptr, *r1 = nullptr, *rows = nullptr, *posts = nullptr;
-    uint32_t *ev = nullptr, *ek = nullptr, *sv = nullptr, *sk2 = nullptr;
-    int32_t *Lp = nullptr, *Li = nullptr, *row_ptr = nullptr, *row_col = nullptr, *row_pos = nullptr;
-    double *packed = nullptr, *packed_s = nullptr;
-    int *bad = nullptr;
+    DevBuf<int32_t> d_parent, d_first, d_post, d_postinv, d_pinv, d_cp;
+    DevBuf<int32_t> cnt, sptr0, sptr, items;
+    DevBuf<uint32_t> skey, srow, k1, r1, rows, posts;
+    DevBuf<uint32_t> ev, ek, sv, sk2;
+    DevBuf<int32_t> Lp, Li, row_ptr, row_col, row_pos;
+    DevBuf<double> packed, packed_s;
+    DevBuf<int> bad;
     int hbad = 0;
     int64_t ns = 0, total = 0;
-    auto up = [&](int32_t **d, const int32_t *h, size_t count) {
-        int st = dalloc(d, count);
-        if (st == CSX_OK && count &&
-            hipMemcpyAsync(*d, h, count * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
-            st = CSX_ERUNTIME;
-        return st;
-    };
-    int st = up(&d_parent, parent, (size_t)n);
-    if (st == CSX_OK) st = up(&d_first, first.data(), (size_t)n);
-    if (st == CSX_OK) st = up(&d_post, post.data(), (size_t)n);
-    if (st == CSX_OK) st = up(&d_postinv, postinv.data(), (size_t)n);
-    if (st == CSX_OK && !counts_only) st = up(&d_cp, cp, (size_t)n + 1);
-    if (st == CSX_OK && pinv) st = up(&d_pinv, pinv, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&bad, 1);
-    if (st == CSX_OK) st = dalloc(&cnt, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&sptr0, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&sptr, (size_t)n + 1);
-    if (st == CSX_OK) {
-        (void)hipMemsetAsync(bad, 0, sizeof(int), s);
-        hipLaunchKernelGGL(k_sym_starts<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, A->p, A->i, d_pinv,
-                           d_post, cnt, nullptr, nullptr, nullptr, bad);
-        st = scan_exclusive_i32(cnt, sptr0, n, &ns);
-    }
+    CSX_TRY(upload(d_parent, parent, (size_t)n));
+    CSX_TRY(upload(d_first, first));
+    CSX_TRY(upload(d_post, post));
+    CSX_TRY(upload(d_postinv, postinv));
+    if (!counts_only) CSX_TRY(upload(d_cp, cp, (size_t)n + 1));
+    if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
+    CSX_TRY(bad.alloc(1));
+    CSX_TRY(cnt.alloc((size_t)n + 1));
+    CSX_TRY(sptr0.alloc((size_t)n + 1));
+    CSX_TRY(sptr.alloc((size_t)n + 1));
+    (void)hipMemsetAsync(bad, 0, sizeof(int), s);
+    hipLaunchKernelGGL(k_sym_starts<false>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, A->p, A->i, d_pinv,
+                       d_post, cnt, nullptr, nullptr, nullptr, bad);
+    CSX_TRY(scan_exclusive_i32(cnt, sptr0, n, &ns));
     // ---- 1. starts grouped by row, postorder ascending inside a row ----
-    if (st == CSX_OK) st = dalloc(&skey, (size_t)ns);
-    if (st == CSX_OK) st = dalloc(&srow, (size_t)ns);
-    if (st == CSX_OK) st = dalloc(&k1, (size_t)ns);
-    if (st == CSX_OK) st = dalloc(&r1, (size_t)ns);
-    if (st == CSX_OK) st = dalloc(&rows, (size_t)ns);
-    if (st == CSX_OK) st = dalloc(&posts, (size_t)ns);
-    if (st == CSX_OK && ns > 0) {
+    CSX_TRY(skey.alloc((size_t)ns));
+    CSX_TRY(srow.alloc((size_t)ns));
+    CSX_TRY(k1.alloc((size_t)ns));
+    CSX_TRY(r1.alloc((size_t)ns));
+    CSX_TRY(rows.alloc((size_t)ns));
+    CSX_TRY(posts.alloc((size_t)ns));
+    if (ns > 0) {
         hipLaunchKernelGGL(k_sym_starts<true>, dim3(blocks_for((int64_t)n * 64)), dim3(256), 0, s, n, A->p, A->i, d_pinv,
                            d_post, nullptr, sptr0, skey, srow, bad);
-        st = stable_sort_by_key(skey, srow, nullptr, ns, (uint32_t)n, k1, r1, nullptr);
-        if (st == CSX_OK) st = stable_sort_by_key(r1, k1, nullptr, ns, (uint32_t)n, rows, posts, nullptr);
-    }
-    if (st == CSX_OK) {
-        if (ns > 0) st = boundaries_from_sorted(rows, ns, n, sptr);
-        else (void)hipMemsetAsync(sptr, 0, ((size_t)n + 1) * sizeof(int32_t), s);
+        CSX_TRY(stable_sort_by_key(skey, srow, nullptr, ns, (uint32_t)n, k1, r1, nullptr));
+        CSX_TRY(stable_sort_by_key(r1, k1, nullptr, ns, (uint32_t)n, rows, posts, nullptr));
+        CSX_TRY(boundaries_from_sorted(rows, ns, n, sptr));
+    } else {
+        (void)hipMemsetAsync(sptr, 0, ((size_t)n + 1) * sizeof(int32_t), s);
     }
     // ---- 2. count, scan, emit ----
     const int64_t nitems = ns + n;
-    if (st == CSX_OK) st = dalloc(&items, (size_t)nitems + 1);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_sym_diag_items, dim3(blocks_for(n)), dim3(256), 0, s, n, sptr, items);
-        if (ns > 0)
-            hipLaunchKernelGGL(k_sym_walk<false>, dim3(blocks_for(ns)), dim3(256), 0, s, ns, rows, posts, d_postinv, d_first,
-                               d_parent, items, nullptr, nullptr);
-        st = scan_exclusive_i32(items, items, nitems, &total);
-    }
-    if (st == CSX_OK && counts_only) {
-        if (total > 0x7FFFFFFFll) st = CSX_EINVAL;   // L does not fit int32 indices
+    CSX_TRY(items.alloc((size_t)nitems + 1));
+    hipLaunchKernelGGL(k_sym_diag_items, dim3(blocks_for(n)), dim3(256), 0, s, n, sptr, items);
+    if (ns > 0)
+        hipLaunchKernelGGL(k_sym_walk<false>, dim3(blocks_for(ns)), dim3(256), 0, s, ns, rows, posts, d_postinv, d_first,
+                           d_parent, items, nullptr, nullptr);
+    CSX_TRY(scan_exclusive_i32(items, items, nitems, &total));
+    if (counts_only) {
+        if (total > 0x7FFFFFFFll) return CSX_EINVAL;   // L does not fit int32 indices
         lnz = total;
     }
-    if (st == CSX_OK && total != lnz) st = CSX_EINVAL;   // S.cp / S.parent do not describe chol(A)
-    if (st == CSX_OK) st = dalloc(&ev, (size_t)lnz);
-    if (st == CSX_OK && !counts_only) st = dalloc(&ek, (size_t)lnz);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_sym_emit_diag, dim3(blocks_for(n)), dim3(256), 0, s, n, sptr, items, ev, ek);
-        if (ns > 0)
-            hipLaunchKernelGGL(k_sym_walk<true>, dim3(blocks_for(ns)), dim3(256), 0, s, ns, rows, posts, d_postinv, d_first,
-                               d_parent, items, ev, ek);
-    }
-    if (st == CSX_OK && counts_only) {   // column counts: sort the columns alone, boundaries = column pointers
-        st = dalloc(&sv, (size_t)lnz);
-        if (st == CSX_OK) st = dalloc(&Lp, (size_t)n + 1);
-        if (st == CSX_OK) st = stable_sort_by_key(ev, nullptr, nullptr, lnz, (uint32_t)n, sv, nullptr, nullptr);
-        if (st == CSX_OK) st = boundaries_from_sorted(sv, lnz, n, Lp);
-        if (st == CSX_OK &&
-            (hipMemcpyAsync(cp_host_out, Lp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipStreamSynchronize(s) != hipSuccess))
-            st = CSX_ERUNTIME;
-        if (st == CSX_OK && hbad) st = CSX_EINVAL;
-        for (void *p : {(void *)d_parent, (void *)d_first, (void *)d_post, (void *)d_postinv, (void *)d_pinv, (void *)cnt,
-                        (void *)sptr0, (void *)sptr, (void *)items, (void *)skey, (void *)srow, (void *)k1, (void *)r1,
-                        (void *)rows, (void *)posts, (void *)ev, (void *)sv, (void *)Lp, (void *)bad})
-            dfree(p);
-        return st;
+    if (total != lnz) return CSX_EINVAL;   // S.cp / S.parent do not describe chol(A)
+    CSX_TRY(ev.alloc((size_t)lnz));
+    if (!counts_only) CSX_TRY(ek.alloc((size_t)lnz));
+    hipLaunchKernelGGL(k_sym_emit_diag, dim3(blocks_for(n)), dim3(256), 0, s, n, sptr, items, ev, ek);
+    if (ns > 0)
+        hipLaunchKernelGGL(k_sym_walk<true>, dim3(blocks_for(ns)), dim3(256), 0, s, ns, rows, posts, d_postinv, d_first,
+                           d_parent, items, ev, ek);
+    if (counts_only) {   // column counts: sort the columns alone, boundaries = column pointers
+        CSX_TRY(sv.alloc((size_t)lnz));
+        CSX_TRY(Lp.alloc((size_t)n + 1));
+        CSX_TRY(stable_sort_by_key(ev, nullptr, nullptr, lnz, (uint32_t)n, sv, nullptr, nullptr));
+        CSX_TRY(boundaries_from_sorted(sv, lnz, n, Lp));
+        CSX_HIP(hipMemcpyAsync(cp_host_out, Lp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
+        return hbad ? CSX_EINVAL : CSX_OK;
     }
     // ---- 3. L in CSC ----
-    if (st == CSX_OK) st = dalloc(&sv, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&Li, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&Lp, (size_t)n + 1);
-    if (st == CSX_OK) st = stable_sort_by_key(ev, ek, nullptr, lnz, (uint32_t)n, sv, (uint32_t *)Li, nullptr);
-    if (st == CSX_OK) st = boundaries_from_sorted(sv, lnz, n, Lp);
-    if (st == CSX_OK)
-        hipLaunchKernelGGL(k_sym_compare, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, (int64_t)n + 1, Lp, d_cp, bad);
+    CSX_TRY(sv.alloc((size_t)lnz));
+    CSX_TRY(Li.alloc((size_t)lnz));
+    CSX_TRY(Lp.alloc((size_t)n + 1));
+    CSX_TRY(stable_sort_by_key(ev, ek, nullptr, lnz, (uint32_t)n, sv, (uint32_t *)Li.get(), nullptr));
+    CSX_TRY(boundaries_from_sorted(sv, lnz, n, Lp));
+    hipLaunchKernelGGL(k_sym_compare, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, (int64_t)n + 1, Lp, d_cp, bad);
     // ---- 4. row view ----
-    if (st == CSX_OK) st = dalloc(&packed, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&packed_s, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&sk2, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&row_ptr, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&row_col, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&row_pos, (size_t)lnz);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_sym_pack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, sv, packed);
-        st = stable_sort_by_key((const uint32_t *)Li, nullptr, packed, lnz, (uint32_t)n, sk2, nullptr, packed_s);
+    CSX_TRY(packed.alloc((size_t)lnz));
+    CSX_TRY(packed_s.alloc((size_t)lnz));
+    CSX_TRY(sk2.alloc((size_t)lnz));
+    CSX_TRY(row_ptr.alloc((size_t)n + 1));
+    CSX_TRY(row_col.alloc((size_t)lnz));
+    CSX_TRY(row_pos.alloc((size_t)lnz));
+    hipLaunchKernelGGL(k_sym_pack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, sv, packed);
+    CSX_TRY(stable_sort_by_key((const uint32_t *)Li.get(), nullptr, packed, lnz, (uint32_t)n, sk2, nullptr, packed_s));
+    CSX_TRY(boundaries_from_sorted(sk2, lnz, n, row_ptr));
+    hipLaunchKernelGGL(k_sym_unpack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, packed_s, row_col, row_pos);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("cs_chol (pattern): %s", hipGetErrorString(hipGetLastError()));
+        return CSX_ERUNTIME;
     }
-    if (st == CSX_OK) st = boundaries_from_sorted(sk2, lnz, n, row_ptr);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_sym_unpack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, packed_s, row_col, row_pos);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_error("cs_chol (pattern): %s", hipGetErrorString(hipGetLastError()));
-            st = CSX_ERUNTIME;
-        }
-    }
-    if (st == CSX_OK && hbad) st = CSX_EINVAL;
-    for (void *p : {(void *)d_parent, (void *)d_first, (void *)d_post, (void *)d_postinv, (void *)d_pinv, (void *)d_cp,
-                    (void *)cnt, (void *)sptr0, (void *)sptr, (void *)items, (void *)skey, (void *)srow, (void *)k1,
-                    (void *)r1, (void *)rows, (void *)posts, (void *)ev, (void *)ek, (void *)sv, (void *)sk2,
-                    (void *)packed, (void *)packed_s, (void *)bad})
-        dfree(p);
-    if (st != CSX_OK) {
-        dfree(Lp);
-        dfree(Li);
-        dfree(row_ptr);
-        dfree(row_col);
-        dfree(row_pos);
-        return st;
-    }
-    *Lp_out = Lp;
-    *Li_out = Li;
-    *row_ptr_out = row_ptr;
-    *row_col_out = row_col;
-    *row_pos_out = row_pos;
+    if (hbad) return CSX_EINVAL;
+    *Lp_out = Lp.release();   // L's from here
+    *Li_out = Li.release();
+    *row_ptr_out = std::move(row_ptr);
+    *row_col_out = std::move(row_col);
+    *row_pos_out = std::move(row_pos);
     return CSX_OK;
 }
 
@@ -379,32 +340,25 @@ static int etree_by_components(const Csc *A, int32_t *parent_host, bool *done, b
     const int32_t n = A->n;
     if (n < ETREE_COMP_MIN_COUNT) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *root = nullptr, *d_parent = nullptr, *d_anc = nullptr;
-    uint32_t *nodes = nullptr;
-    CSX_TRY(tmp.alloc(&root, (size_t)n));
+    DevBuf<int32_t> root, d_parent, d_anc;
+    DevBuf<uint32_t> nodes;
+    DevBuf<Tree> comps;
+    CSX_TRY(root.alloc((size_t)n));
     CSX_TRY(connected_components(n, A->p, A->i, 0, 0, 0, root, bad_index));
     if (*bad_index) return CSX_OK;
-    CSX_TRY(tmp.alloc(&nodes, (size_t)n));
-    Tree *comps = nullptr;
+    CSX_TRY(nodes.alloc((size_t)n));
     int32_t ncomp = 0, maxc = 0;
-    int st = group_by_root(n, root, nodes, nullptr, &comps, &ncomp, &maxc);
-    if (st == CSX_OK && ncomp >= ETREE_COMP_MIN_COUNT && maxc <= ETREE_COMP_MAX) {
-        st = tmp.alloc(&d_parent, (size_t)n);
-        if (st == CSX_OK) st = tmp.alloc(&d_anc, (size_t)n);
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_etree_components, dim3((unsigned)((ncomp + 63) / 64)), dim3(64), 0, s, ncomp, comps, nodes,
-                               A->p, A->i, d_parent, d_anc);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(parent_host, d_parent, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
-            else
-                *done = true;
-        }
-    }
-    dfree(comps);
-    return st;
+    CSX_TRY(group_by_root(n, root, nodes, nullptr, &comps, &ncomp, &maxc));
+    if (ncomp < ETREE_COMP_MIN_COUNT || maxc > ETREE_COMP_MAX) return CSX_OK;
+    CSX_TRY(d_parent.alloc((size_t)n));
+    CSX_TRY(d_anc.alloc((size_t)n));
+    hipLaunchKernelGGL(k_etree_components, dim3((unsigned)((ncomp + 63) / 64)), dim3(64), 0, s, ncomp, comps, nodes,
+                       A->p, A->i, d_parent, d_anc);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(parent_host, d_parent, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    *done = true;
+    return CSX_OK;
 }
 
 extern "C" int csx_schol(csx_handle_t hA, int32_t *parent, int32_t *cp) {
@@ -420,25 +374,18 @@ extern "C" int csx_schol(csx_handle_t hA, int32_t *parent, int32_t *cp) {
     if (ctx().opt.chol_clique) {
         // a forest of cliques on consecutive columns (block-diagonal with dense blocks): tree and counts follow from the
         // smallest upper row of every column, one pass over A's pattern (csx_cholclique.hip)
-        CliqueForest F;
+        std::unique_ptr<CliqueForest> F(new CliqueForest());
         bool ok = false;
-        int st = clique_forest(A, &F, &ok);
-        if (st == CSX_OK && ok) {
-            if (hipMemcpyAsync(parent, F.parent, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(cp, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
-        if (st == CSX_OK && ok) {             // kept on the matrix for the csx_chol that follows (csx_csc_invalidate drops it)
-            free_clique_cache(A->clique);
-            A->clique = new CliqueForest(F);
+        CSX_TRY(clique_forest(A, F.get(), &ok));
+        if (ok) {
+            CSX_HIP(hipMemcpyAsync(parent, F->parent, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            CSX_HIP(hipMemcpyAsync(cp, F->cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            CSX_HIP(hipStreamSynchronize(s));
+            A->clique = std::move(F);         // kept on the matrix for the csx_chol that follows (csx_csc_invalidate drops it)
             return CSX_OK;
         }
-        free_clique(&F);
-        if (st != CSX_OK) return st;
     }
-    free_clique_cache(A->clique);             // no finding under the options in force: none of an earlier call either
-    A->clique = nullptr;
+    A->clique.reset();                        // no finding under the options in force: none of an earlier call either
     bool on_device = false, bad_index = false;
     CSX_TRY(etree_by_components(A, parent, &on_device, &bad_index));
     if (bad_index) return CSX_EINVAL;

@@ -148,18 +148,12 @@ struct ShardPlan {
     csx_handle_t hblock = 0;             // the rank's column block (m x count): NOT owned, so kept as its handle and resolved
                                          // at every call -- a block freed behind the plan's back is CSX_EINVAL, not a dangling pointer
     int32_t m = 0, n = 0, chunk = 0;     // rows, columns; rows per rank = ceil(m / world)
-    std::vector<Csc *> pieces;           // world row pieces of the block (owned; empty when world == 1)
-    double *work = nullptr;              // world * chunk partial y
-    double *recv = nullptr;              // (world - 1) * chunk pieces received
+    std::vector<std::unique_ptr<Csc>> pieces;   // world row pieces of the block (empty when world == 1)
+    DevBuf<double> work;                 // world * chunk partial y
+    DevBuf<double> recv;                 // (world - 1) * chunk pieces received
 };
 
-void free_shardplan(ShardPlan *P) {
-    if (!P) return;
-    for (Csc *c : P->pieces) free_csc(c);
-    dfree(P->work);
-    dfree(P->recv);
-    delete P;
-}
+void destroy(ShardPlan *P) { delete P; }
 
 }  // namespace csx
 
@@ -190,6 +184,7 @@ int csx_comm_init(int rank, int world, const uint8_t *id128) {
     }
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !id128)) return CSX_EINVAL;
     Comm c;
+    DevBuf<double> stage;
     c.rank = rank;
     c.world = world;
     auto build = [&]() -> int {
@@ -203,7 +198,7 @@ int csx_comm_init(int rank, int world, const uint8_t *id128) {
         CSX_HIP(hipStreamCreateWithFlags(&c.xs, hipStreamNonBlocking));
         CSX_HIP(hipEventCreateWithFlags(&c.ev_k, hipEventDisableTiming));
         CSX_HIP(hipEventCreateWithFlags(&c.ev_x, hipEventDisableTiming));
-        CSX_TRY(dalloc(&c.stage_d, 1024));
+        CSX_TRY(stage.alloc(1024));
         return CSX_OK;
     };
     const int st = build();
@@ -212,9 +207,9 @@ int csx_comm_init(int rank, int world, const uint8_t *id128) {
         if (c.ev_k) (void)hipEventDestroy(c.ev_k);
         if (c.ev_x) (void)hipEventDestroy(c.ev_x);
         if (c.xs) (void)hipStreamDestroy(c.xs);
-        dfree(c.stage_d);
         return st;
     }
+    c.stage_d = stage.release();   // g_comm is static: it holds the block raw, csx_comm_finalize gives it back
     c.up = true;
     g_comm = c;
     return CSX_OK;
@@ -228,7 +223,7 @@ int csx_comm_finalize(void) {
     (void)hipEventDestroy(g_comm.ev_k);
     (void)hipEventDestroy(g_comm.ev_x);
     (void)hipStreamDestroy(g_comm.xs);
-    dfree(g_comm.stage_d);
+    DevBuf<double> stage(g_comm.stage_d);   // released on return
     g_comm = Comm();
     return CSX_OK;
 }
@@ -268,9 +263,8 @@ int csx_comm_bcast_host(void *buf, int64_t bytes, int root) {
     if (bytes < 0 || (bytes > 0 && !buf) || root < 0 || root >= g_comm.world) return CSX_EINVAL;
     if (!g_comm.rccl || bytes == 0) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    char *d = nullptr;
-    CSX_TRY(tmp.alloc(&d, (size_t)bytes));
+    DevBuf<char> d;
+    CSX_TRY(d.alloc((size_t)bytes));
     if (g_comm.rank == root) CSX_HIP(hipMemcpyAsync(d, buf, (size_t)bytes, hipMemcpyHostToDevice, s));
     CSX_NCCL(g_rccl.Broadcast(d, d, (size_t)bytes, ncclChar, root, g_comm.comm, s));
     if (g_comm.rank != root) CSX_HIP(hipMemcpyAsync(buf, d, (size_t)bytes, hipMemcpyDeviceToHost, s));
@@ -425,39 +419,31 @@ int csx_gaxpy_sharded_plan_for(csx_handle_t hblock, int world, csx_handle_t *out
 static int sharded_plan(csx_handle_t hblock, int W, csx_handle_t *out) {
     Csc *A = csc(hblock);
     if (!A || !out || !A->x) return CSX_EINVAL;
-    ShardPlan *P = new ShardPlan();
+    std::unique_ptr<ShardPlan> P(new ShardPlan());
     P->hblock = hblock;
     P->m = A->m;
     P->n = A->n;
     P->chunk = (A->m + W - 1) / W;
-    int st = dalloc(&P->work, (size_t)std::max<int64_t>((int64_t)P->chunk * W, 1));
-    if (st == CSX_OK && W > 1) st = dalloc(&P->recv, (size_t)std::max<int64_t>((int64_t)P->chunk * (W - 1), 1));
-    if (st == CSX_OK && W > 1) {
+    CSX_TRY(P->work.alloc((size_t)std::max<int64_t>((int64_t)P->chunk * W, 1)));
+    if (W > 1) {
+        CSX_TRY(P->recv.alloc((size_t)std::max<int64_t>((int64_t)P->chunk * (W - 1), 1)));
         // rows of A_r as columns (stable transpose), cut, transposed back: piece q = rows [q chunk, ...) of A_r, rebased
         Csc T;
-        st = transpose_device(A, true, &T);
-        for (int q = 0; q < W && st == CSX_OK; q++) {
+        CSX_TRY(transpose_device(A, true, &T));
+        for (int q = 0; q < W; q++) {
             const int32_t r0 = std::min<int64_t>((int64_t)q * P->chunk, A->m);
             const int32_t cnt = (int32_t)std::min<int64_t>(P->chunk, (int64_t)A->m - r0);
-            Csc Tq;
-            st = col_block_device(&T, r0, cnt, &Tq);
-            Csc *piece = new Csc();
-            if (st == CSX_OK) st = transpose_device(&Tq, true, piece);
-            dfree(Tq.p);
-            dfree(Tq.i);
-            dfree(Tq.x);
-            P->pieces.push_back(piece);
-            if (st == CSX_OK && piece->nnz) st = gaxpy_prepare_device(piece, CSX_GAXPY_AUTO);
+            P->pieces.emplace_back(new Csc());
+            Csc *piece = P->pieces.back().get();
+            {
+                Csc Tq;
+                CSX_TRY(col_block_device(&T, r0, cnt, &Tq));
+                CSX_TRY(transpose_device(&Tq, true, piece));
+            }
+            if (piece->nnz) CSX_TRY(gaxpy_prepare_device(piece, CSX_GAXPY_AUTO));
         }
-        dfree(T.p);
-        dfree(T.i);
-        dfree(T.x);
     }
-    if (st != CSX_OK) {
-        free_shardplan(P);
-        return st;
-    }
-    *out = put(K_SHARDPLAN, P);
+    *out = put(K_SHARDPLAN, P.release());
     return CSX_OK;
 }
 
@@ -510,7 +496,7 @@ int csx_gaxpy_sharded(csx_handle_t hplan, csx_handle_t hx, csx_handle_t hy, int 
     CSX_HIP(hipStreamWaitEvent(g_comm.xs, g_comm.ev_k, 0));
     for (int step = 1; step <= W; step++) {
         const int q = (rank + step) % W;                 // the piece computed now; step == W: my own
-        CSX_TRY(gaxpy_device(P->pieces[q], xd, P->work + (int64_t)q * chunk, CSX_GAXPY_AUTO));
+        CSX_TRY(gaxpy_device(P->pieces[q].get(), xd, P->work + (int64_t)q * chunk, CSX_GAXPY_AUTO));
         if (step == W) break;
         const int from = (rank - step + W) % W;          // who computes MY piece at this step
         CSX_HIP(hipEventRecord(g_comm.ev_k, s));
@@ -542,7 +528,7 @@ int csx_gaxpy_sharded_piece(csx_handle_t hplan, int q, csx_handle_t hx) {
     if (!P || !x || x->len < P->n || q < 0 || q >= (int)P->pieces.size()) return CSX_EINVAL;
     double *dst = P->work + (int64_t)q * P->chunk;
     CSX_HIP(hipMemsetAsync(dst, 0, (size_t)P->chunk * sizeof(double), ctx().stream));
-    return gaxpy_device(P->pieces[q], (const double *)x->d, dst, CSX_GAXPY_AUTO);
+    return gaxpy_device(P->pieces[q].get(), (const double *)x->d, dst, CSX_GAXPY_AUTO);
 }
 
 int csx_gaxpy_sharded_buffers(csx_handle_t hplan, void **work, void **recv, int64_t *chunk) {

@@ -102,9 +102,8 @@ int connected_components(int32_t n, const int32_t *ptr, const int32_t *idx, int 
     hipStream_t s = ctx().stream;
     *malformed = false;
     if (n == 0) return CSX_OK;
-    DevScope tmp;
-    int *flags = nullptr;
-    CSX_TRY(tmp.alloc(&flags, 4));
+    DevBuf<int> flags;
+    CSX_TRY(flags.alloc(4));
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256), nbw = (unsigned)(((int64_t)n + 3) / 4);
     hipLaunchKernelGGL(k_cc_init, dim3(nb), dim3(256), 0, s, n, root);
     int hflags[2] = {0, 0};
@@ -125,32 +124,30 @@ int connected_components(int32_t n, const int32_t *ptr, const int32_t *idx, int 
 }
 
 // nodes[k]: the vertices grouped by root, ascending inside a group (stable sort); comps[c] = (first, count)
-// into nodes (allocated here, caller frees); comp_of_pos[k] = component of position k (optional).
-int group_by_root(int32_t n, const int32_t *root, uint32_t *nodes, int32_t *comp_of_pos, Tree **comps_out,
+// into nodes (allocated here); comp_of_pos[k] = component of position k (optional).
+int group_by_root(int32_t n, const int32_t *root, uint32_t *nodes, int32_t *comp_of_pos, DevBuf<Tree> *comps_out,
                   int32_t *ncomp_out, int32_t *max_count) {
     hipStream_t s = ctx().stream;
-    *comps_out = nullptr;
+    comps_out->reset();
     *ncomp_out = 0;
     *max_count = 0;
     if (n == 0) return CSX_OK;
-    DevScope tmp;
-    uint32_t *iota = nullptr, *sroot = nullptr;
-    int32_t *head = nullptr, *hscan = nullptr;
-    int *stat = nullptr;
-    CSX_TRY(tmp.alloc(&iota, (size_t)n));
-    CSX_TRY(tmp.alloc(&sroot, (size_t)n));
-    CSX_TRY(tmp.alloc(&head, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&hscan, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&stat, 1));
+    DevBuf<uint32_t> iota, sroot;
+    DevBuf<int32_t> head, hscan;
+    DevBuf<int> stat;
+    CSX_TRY(iota.alloc((size_t)n));
+    CSX_TRY(sroot.alloc((size_t)n));
+    CSX_TRY(head.alloc((size_t)n + 1));
+    CSX_TRY(hscan.alloc((size_t)n + 1));
+    CSX_TRY(stat.alloc(1));
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
     hipLaunchKernelGGL(k_iota_u32, dim3(nb), dim3(256), 0, s, n, iota);
     CSX_TRY(stable_sort_by_key((const uint32_t *)root, iota, nullptr, n, (uint32_t)n, sroot, nodes, nullptr));
     hipLaunchKernelGGL(k_cc_heads, dim3(nb), dim3(256), 0, s, n, sroot, head);
     int64_t ncomp = 0;
     CSX_TRY(scan_exclusive_i32(head, hscan, n, &ncomp));
-    Tree *comps = nullptr;
-    CSX_TRY(dalloc(&comps, (size_t)ncomp));
-    *comps_out = comps;
+    CSX_TRY(comps_out->alloc((size_t)ncomp));
+    Tree *comps = *comps_out;
     CSX_HIP(hipMemsetAsync(stat, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_cc_first, dim3(nb), dim3(256), 0, s, n, head, hscan, comps);
     hipLaunchKernelGGL(k_cc_count, dim3((unsigned)((ncomp + 255) / 256)), dim3(256), 0, s, n, (int32_t)ncomp, comps, stat);
@@ -177,30 +174,24 @@ __global__ __launch_bounds__(256) void k_comp_gather(const Tree *__restrict__ co
 }
 
 
-int trees_biggest_first(const Tree *trees, int32_t ntrees, int32_t max_count, Tree **out) {
-    *out = nullptr;
+int trees_biggest_first(const Tree *trees, int32_t ntrees, int32_t max_count, DevBuf<Tree> *out) {
+    out->reset();
     if (ntrees <= 0) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    uint32_t *key = nullptr, *id = nullptr, *list = nullptr;
-    CSX_TRY(tmp.alloc(&key, (size_t)ntrees));
-    CSX_TRY(tmp.alloc(&id, (size_t)ntrees));
-    CSX_TRY(tmp.alloc(&list, (size_t)ntrees));
-    Tree *o = nullptr;
-    CSX_TRY(dalloc(&o, (size_t)ntrees));
+    DevBuf<uint32_t> key, id, list;
+    CSX_TRY(key.alloc((size_t)ntrees));
+    CSX_TRY(id.alloc((size_t)ntrees));
+    CSX_TRY(list.alloc((size_t)ntrees));
+    DevBuf<Tree> o;
+    CSX_TRY(o.alloc((size_t)ntrees));
     const unsigned g = (unsigned)((ntrees + 255) / 256);
     hipLaunchKernelGGL(k_comp_size_key, dim3(g), dim3(256), 0, s, trees, ntrees, max_count, key, id);
-    int st = hipGetLastError() == hipSuccess ? CSX_OK : CSX_ERUNTIME;
-    if (st == CSX_OK) st = stable_sort_by_key(key, id, nullptr, ntrees, (uint32_t)max_count + 1, nullptr, list, nullptr);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_comp_gather, dim3(g), dim3(256), 0, s, trees, list, ntrees, o);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;     // (list is a temporary)
-    }
-    if (st != CSX_OK) {
-        dfree(o);
-        return st;
-    }
-    *out = o;
+    CSX_LAUNCH_CHECK();
+    CSX_TRY(stable_sort_by_key(key, id, nullptr, ntrees, (uint32_t)max_count + 1, nullptr, list, nullptr));
+    hipLaunchKernelGGL(k_comp_gather, dim3(g), dim3(256), 0, s, trees, list, ntrees, o);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipStreamSynchronize(s));     // (list is a temporary)
+    *out = std::move(o);
     return CSX_OK;
 }
 

@@ -8,6 +8,7 @@
 #include <string>
 #include <unordered_map>
 
+#include "csx_cholclique.h"
 #include "csx_internal.h"
 
 namespace csx {
@@ -224,57 +225,25 @@ void dfree(void *p) {
     (void)hipFree(p);
 }
 
-void free_gather(Gather *g) {
-    if (!g) return;
-    dfree(g->ptr);
-    dfree(g->idx);
-    dfree(g->val);
-    delete g;
-}
+Csc::Csc() = default;
 
-void free_tiled(TiledPlan *t) {
-    if (!t) return;
-    dfree(t->tile_ptr);
-    dfree(t->tile_len);
-    dfree(t->tile_key);
-    dfree(t->tile_key24);
-    dfree(t->tile_base);
-    dfree(t->tile_val);
-    delete t;
-}
-
-void free_csc(Csc *A) {
-    if (!A) return;
-    if (A->owns) {
-        dfree(A->p);
-        dfree(A->i);
-        dfree(A->x);
+Csc::~Csc() {
+    if (owns) {
+        dfree(p);
+        dfree(i);
+        dfree(x);
     }
-    free_gather(A->rows);
-    free_tiled(A->tiled);
-    if (A->house) {
-        dfree(A->house->cols);
-        delete A->house;
-    }
-    free_clique_cache(A->clique);
-    delete A;
-}
-
-static void free_vec(Vec *v) {
-    if (!v) return;
-    if (v->owns) dfree(v->d);
-    delete v;
 }
 
 static void free_object(Object &o) {
     switch (o.kind) {
-        case K_CSC: free_csc((Csc *)o.ptr); break;
+        case K_CSC: delete (Csc *)o.ptr; break;
         case K_VEC:
-        case K_IVEC: free_vec((Vec *)o.ptr); break;
-        case K_TRIPLAN: free_triplan((TriPlan *)o.ptr); break;
-        case K_CHOLPLAN: free_cholplan((CholPlan *)o.ptr); break;
-        case K_SHARDPLAN: free_shardplan((ShardPlan *)o.ptr); break;
-        case K_BTFPLAN: free_btfplan((BtfPlan *)o.ptr); break;
+        case K_IVEC: delete (Vec *)o.ptr; break;
+        case K_TRIPLAN: destroy((TriPlan *)o.ptr); break;
+        case K_CHOLPLAN: destroy((CholPlan *)o.ptr); break;
+        case K_SHARDPLAN: destroy((ShardPlan *)o.ptr); break;
+        case K_BTFPLAN: destroy((BtfPlan *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it
@@ -436,18 +405,14 @@ int csx_timer_stop(double *ms) {
 int csx_csc_alloc(int32_t m, int32_t n, int32_t nnz, int values, csx_handle_t *out) {
     CSX_TRY(require_ready());
     if (m < 0 || n < 0 || nnz < 0 || !out) return CSX_EINVAL;
-    Csc *A = new Csc();
+    std::unique_ptr<Csc> A(new Csc());
     A->m = m;
     A->n = n;
     A->nnz = nnz;
-    int st = dalloc(&A->p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&A->i, (size_t)nnz);
-    if (st == CSX_OK && values) st = dalloc(&A->x, (size_t)nnz);
-    if (st != CSX_OK) {
-        free_csc(A);
-        return st;
-    }
-    *out = put(K_CSC, A);
+    CSX_TRY(dalloc(&A->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&A->i, (size_t)nnz));
+    if (values) CSX_TRY(dalloc(&A->x, (size_t)nnz));
+    *out = put(K_CSC, A.release());
     return CSX_OK;
 }
 
@@ -505,9 +470,9 @@ __global__ void k_csc_validate(int32_t m, int32_t n, int32_t nnz, const int32_t 
 int csc_validate(Csc *A) {
     if (A->trusted) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *bad = nullptr, h = 0;
-    CSX_TRY(tmp.alloc(&bad, 1));
+    DevBuf<int32_t> bad;
+    int32_t h = 0;
+    CSX_TRY(bad.alloc(1));
     CSX_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
     const int64_t work = std::max<int64_t>((int64_t)A->n, (int64_t)A->nnz);
     const unsigned grid = (unsigned)std::min<int64_t>(4096, (work + 255) / 256 + 1);
@@ -648,17 +613,10 @@ int csx_csc_invalidate(csx_handle_t h) {
     if (!A) return CSX_EINVAL;
     (void)hipStreamSynchronize(ctx().stream);
     if (!A->owns) A->trusted = false;   // the caller changed its arrays: check them again
-    free_gather(A->rows);
-    A->rows = nullptr;
-    free_tiled(A->tiled);
-    A->tiled = nullptr;
-    if (A->house) {
-        dfree(A->house->cols);
-        delete A->house;
-        A->house = nullptr;
-    }
-    free_clique_cache(A->clique);
-    A->clique = nullptr;
+    A->rows.reset();
+    A->tiled.reset();
+    A->house.reset();
+    A->clique.reset();
     return CSX_OK;
 }
 
@@ -667,15 +625,11 @@ int csx_csc_invalidate(csx_handle_t h) {
 static int vec_new(Kind k, int64_t len, size_t elem, csx_handle_t *out, Vec **pv) {
     CSX_TRY(require_ready());
     if (len < 0 || !out) return CSX_EINVAL;
-    Vec *v = new Vec();
+    std::unique_ptr<Vec> v(new Vec());
     v->len = len;
-    int st = dmalloc(&v->d, (size_t)len * elem);
-    if (st != CSX_OK) {
-        delete v;
-        return st;
-    }
-    *out = put(k, v);
-    *pv = v;
+    CSX_TRY(dmalloc(&v->d, (size_t)len * elem));
+    *pv = v.get();
+    *out = put(k, v.release());
     return CSX_OK;
 }
 

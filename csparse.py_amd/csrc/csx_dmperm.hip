@@ -501,9 +501,16 @@ __global__ void k_fine_apply(int32_t nc, const uint32_t *__restrict__ ps, const 
     p[rr1 + k] = rv[ps[k]];
 }
 
+// What one csx_maxtrans / csx_scc / csx_dmperm call holds until it returns: the control block, the events, and the
+// work arrays of maxtrans_device and scc_device
 struct Work {
-    DevScope mem;
-    Ctl *ctl = nullptr;
+    DevBuf<Ctl> ctl;
+    DevBuf<uint64_t> rbid, rend;                                  // maxtrans_device
+    DevBuf<int32_t> cfr, croot, rvis, rpar;
+    DevBuf<int32_t> deg, flev, blev, comp, bfr, mlev, head, hscan;   // scc_device
+    DevBuf<uint64_t> color;
+    DevBuf<uint32_t> iota, ord, key;
+    DevBuf<int> stats;
     Ctl h{};
     hipEvent_t ev[6] = {};
     ~Work() {
@@ -533,7 +540,7 @@ int maxtrans_device(const Csc *A, int64_t seed, int32_t *jm, int32_t *im, Work &
     CSX_LAUNCH_CHECK();
     if (m == 0 || n == 0 || A->nnz == 0) return CSX_OK;
     // zero-free diagonal: the diagonal is a matching of cardinality min(m, n)
-    int *missing = &W.ctl->pad[0];
+    int *missing = &W.ctl.get()->pad[0];
     CSX_TRY(reset_ctl(W.ctl));
     hipLaunchKernelGGL(k_diag_check, grid_of(k), dim3(256), 0, s, k, A->p, A->i, missing);
     CSX_HIP(hipMemcpyAsync(&W.h, W.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, s));
@@ -544,14 +551,14 @@ int maxtrans_device(const Csc *A, int64_t seed, int32_t *jm, int32_t *im, Work &
         CSX_HIP(hipEventRecord(W.ev[1], s));
         return CSX_OK;
     }
-    uint64_t *rbid = nullptr, *rend = nullptr;
-    int32_t *cfr = nullptr, *croot = nullptr, *rvis = nullptr, *rpar = nullptr;
-    CSX_TRY(W.mem.alloc(&rbid, (size_t)m));
-    CSX_TRY(W.mem.alloc(&rend, (size_t)n));
-    CSX_TRY(W.mem.alloc(&cfr, (size_t)n));
-    CSX_TRY(W.mem.alloc(&croot, (size_t)n));
-    CSX_TRY(W.mem.alloc(&rvis, (size_t)m));
-    CSX_TRY(W.mem.alloc(&rpar, (size_t)m));
+    CSX_TRY(W.rbid.alloc((size_t)m));
+    CSX_TRY(W.rend.alloc((size_t)n));
+    CSX_TRY(W.cfr.alloc((size_t)n));
+    CSX_TRY(W.croot.alloc((size_t)n));
+    CSX_TRY(W.rvis.alloc((size_t)m));
+    CSX_TRY(W.rpar.alloc((size_t)m));
+    uint64_t *rbid = W.rbid, *rend = W.rend;
+    int32_t *cfr = W.cfr, *croot = W.croot, *rvis = W.rvis, *rpar = W.rpar;
     hipLaunchKernelGGL(k_fill64, grid_of(m), dim3(256), 0, s, rbid, (int64_t)m, KEY_NONE);
     hipLaunchKernelGGL(k_fill64, grid_of(n), dim3(256), 0, s, rend, (int64_t)n, KEY_NONE);
     hipLaunchKernelGGL(k_fill, grid_of(m), dim3(256), 0, s, rvis, (int64_t)m, -1);
@@ -593,23 +600,24 @@ int scc_device(const Graph &G, int64_t budget, uint32_t *ps, int32_t *rs, int32_
     *nb_out = 0;
     if (nv == 0) return CSX_OK;
     const dim3 g = grid_of(nv), b(256);
-    int32_t *deg, *flev, *blev, *comp, *bfr, *mlev, *head, *hscan;
-    uint64_t *color;
-    uint32_t *iota, *ord, *key;
-    int *stats;
-    CSX_TRY(W.mem.alloc(&deg, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&flev, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&blev, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&comp, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&color, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&bfr, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&mlev, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&head, (size_t)nv + 1));
-    CSX_TRY(W.mem.alloc(&hscan, (size_t)nv + 1));
-    CSX_TRY(W.mem.alloc(&iota, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&ord, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&key, (size_t)nv));
-    CSX_TRY(W.mem.alloc(&stats, 4));
+    CSX_TRY(W.deg.alloc((size_t)nv));
+    CSX_TRY(W.flev.alloc((size_t)nv));
+    CSX_TRY(W.blev.alloc((size_t)nv));
+    CSX_TRY(W.comp.alloc((size_t)nv));
+    CSX_TRY(W.color.alloc((size_t)nv));
+    CSX_TRY(W.bfr.alloc((size_t)nv));
+    CSX_TRY(W.mlev.alloc((size_t)nv));
+    CSX_TRY(W.head.alloc((size_t)nv + 1));
+    CSX_TRY(W.hscan.alloc((size_t)nv + 1));
+    CSX_TRY(W.iota.alloc((size_t)nv));
+    CSX_TRY(W.ord.alloc((size_t)nv));
+    CSX_TRY(W.key.alloc((size_t)nv));
+    CSX_TRY(W.stats.alloc(4));
+    int32_t *deg = W.deg, *flev = W.flev, *blev = W.blev, *comp = W.comp, *bfr = W.bfr, *mlev = W.mlev, *head = W.head,
+            *hscan = W.hscan;
+    uint64_t *color = W.color;
+    uint32_t *iota = W.iota, *ord = W.ord, *key = W.key;
+    int *stats = W.stats;
     CSX_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(int), s));
     const int64_t bound = (int64_t)nv + 1;
     // trim: sources to the front, sinks to the back, in peel order
@@ -722,19 +730,10 @@ int row_view(Csc *A, Csc &tmp, const int32_t **Tp, const int32_t **Ti) {
     return CSX_OK;
 }
 
-struct TmpCsc {
-    Csc c;
-    ~TmpCsc() {
-        dfree(c.p);
-        dfree(c.i);
-        dfree(c.x);
-    }
-};
-
 int begin(Work &W) {
     for (int64_t &r : g_rounds) r = 0;
     for (hipEvent_t &e : W.ev) CSX_HIP(hipEventCreate(&e));
-    CSX_TRY(W.mem.alloc(&W.ctl, 1));
+    CSX_TRY(W.ctl.alloc(1));
     CSX_HIP(hipEventRecord(W.ev[0], ctx().stream));
     for (int k = 1; k < 5; k++) CSX_HIP(hipEventRecord(W.ev[k], ctx().stream));   // stages that do not run take 0 ms
     return CSX_OK;
@@ -776,8 +775,8 @@ extern "C" int csx_maxtrans(csx_handle_t hA, int64_t seed, int32_t *jimatch, int
     const int32_t m = A->m, n = A->n;
     Work W;
     CSX_TRY(begin(W));
-    int32_t *jim = nullptr;
-    CSX_TRY(W.mem.alloc(&jim, (size_t)m + n));
+    DevBuf<int32_t> jim;
+    CSX_TRY(jim.alloc((size_t)m + n));
     CSX_TRY(maxtrans_device(A, seed, jim, jim + m, W));
     CSX_HIP(hipEventRecord(W.ev[2], s));
     CSX_HIP(hipMemcpyAsync(jimatch, jim, ((size_t)m + n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -801,15 +800,15 @@ extern "C" int csx_scc(csx_handle_t hA, int32_t *p, int32_t *r, int32_t *nb) {
     if (n == 0) return CSX_OK;
     Work W;
     CSX_TRY(begin(W));
-    TmpCsc T;
+    Csc T;
     const int32_t *Tp = nullptr, *Ti = nullptr;
-    CSX_TRY(row_view(A, T.c, &Tp, &Ti));
-    int32_t *ident = nullptr, *rs = nullptr;
-    uint32_t *ps = nullptr;
-    CSX_TRY(W.mem.alloc(&ident, (size_t)n));
-    CSX_TRY(W.mem.alloc(&rs, (size_t)n + 1));
-    CSX_TRY(W.mem.alloc(&ps, (size_t)n));
-    hipLaunchKernelGGL(k_iota, grid_of(n), dim3(256), 0, s, (uint32_t *)ident, (int64_t)n);
+    CSX_TRY(row_view(A, T, &Tp, &Ti));
+    DevBuf<int32_t> ident, rs;
+    DevBuf<uint32_t> ps;
+    CSX_TRY(ident.alloc((size_t)n));
+    CSX_TRY(rs.alloc((size_t)n + 1));
+    CSX_TRY(ps.alloc((size_t)n));
+    hipLaunchKernelGGL(k_iota, grid_of(n), dim3(256), 0, s, (uint32_t *)ident.get(), (int64_t)n);
     Graph G{n, A->p, A->i, Tp, Ti, ident, ident, ident, ident};
     CSX_HIP(hipEventRecord(W.ev[3], s));
     int32_t nb1 = 0;
@@ -831,27 +830,27 @@ extern "C" int csx_dmperm(csx_handle_t hA, int64_t seed, int32_t *p, int32_t *q,
     const int32_t m = A->m, n = A->n;
     Work W;
     CSX_TRY(begin(W));
-    int32_t *jm, *im, *colset, *rowset, *cfr, *rfr, *dp, *flag, *pos;
-    uint32_t *cls, *iota, *dq;
-    int *cnt;
-    CSX_TRY(W.mem.alloc(&jm, (size_t)m));
-    CSX_TRY(W.mem.alloc(&im, (size_t)n));
-    CSX_TRY(W.mem.alloc(&colset, (size_t)n));
-    CSX_TRY(W.mem.alloc(&rowset, (size_t)m));
-    CSX_TRY(W.mem.alloc(&cfr, (size_t)n));
-    CSX_TRY(W.mem.alloc(&rfr, (size_t)m));
-    CSX_TRY(W.mem.alloc(&dp, (size_t)m));
-    CSX_TRY(W.mem.alloc(&flag, (size_t)m + 1));
-    CSX_TRY(W.mem.alloc(&pos, (size_t)m + 1));
-    CSX_TRY(W.mem.alloc(&cls, (size_t)n));
-    CSX_TRY(W.mem.alloc(&iota, (size_t)n));
-    CSX_TRY(W.mem.alloc(&dq, (size_t)n));
-    CSX_TRY(W.mem.alloc(&cnt, 4));
+    DevBuf<int32_t> jm, im, colset, rowset, cfr, rfr, dp, flag, pos;
+    DevBuf<uint32_t> cls, iota, dq;
+    DevBuf<int> cnt;
+    CSX_TRY(jm.alloc((size_t)m));
+    CSX_TRY(im.alloc((size_t)n));
+    CSX_TRY(colset.alloc((size_t)n));
+    CSX_TRY(rowset.alloc((size_t)m));
+    CSX_TRY(cfr.alloc((size_t)n));
+    CSX_TRY(rfr.alloc((size_t)m));
+    CSX_TRY(dp.alloc((size_t)m));
+    CSX_TRY(flag.alloc((size_t)m + 1));
+    CSX_TRY(pos.alloc((size_t)m + 1));
+    CSX_TRY(cls.alloc((size_t)n));
+    CSX_TRY(iota.alloc((size_t)n));
+    CSX_TRY(dq.alloc((size_t)n));
+    CSX_TRY(cnt.alloc(4));
     CSX_TRY(maxtrans_device(A, seed, jm, im, W));
     CSX_HIP(hipEventRecord(W.ev[2], s));
     // coarse decomposition (csparse.py's two cs_bfs calls)
     const int64_t bound = (int64_t)m + n + 1;
-    TmpCsc T;
+    Csc T;
     const int32_t *Tp = nullptr, *Ti = nullptr;
     hipLaunchKernelGGL(k_fill, grid_of(m), dim3(256), 0, s, rowset, (int64_t)m, -1);
     hipLaunchKernelGGL(k_c1_seed, grid_of(n), dim3(256), 0, s, n, im, colset, cfr);
@@ -866,7 +865,7 @@ extern "C" int csx_dmperm(csx_handle_t hA, int64_t seed, int32_t *p, int32_t *q,
     hipLaunchKernelGGL(k_unmatched_flag, grid_of(m), dim3(256), 0, s, m, jm, flag);
     int64_t n_unmatched_rows = 0;
     if (m > 0) CSX_TRY(scan_exclusive_i32(flag, pos, m, &n_unmatched_rows));
-    if (m > 0 && n > 0 && A->nnz > 0) CSX_TRY(row_view(A, T.c, &Tp, &Ti));
+    if (m > 0 && n > 0 && A->nnz > 0) CSX_TRY(row_view(A, T, &Tp, &Ti));
     if (n_unmatched_rows > 0 && Tp) {
         hipLaunchKernelGGL(k_c2_seed, grid_of(m), dim3(256), 0, s, m, jm, rowset, rfr);
         CSX_TRY(reset_ctl(W.ctl));
@@ -908,14 +907,14 @@ extern "C" int csx_dmperm(csx_handle_t hA, int64_t seed, int32_t *p, int32_t *q,
     std::vector<int32_t> rs_h;
     int32_t nb1 = 0;
     if (nc > 0) {
-        int32_t *cv, *rv, *vc, *vr, *rs;
-        uint32_t *ps;
-        CSX_TRY(W.mem.alloc(&cv, (size_t)nc));
-        CSX_TRY(W.mem.alloc(&rv, (size_t)nc));
-        CSX_TRY(W.mem.alloc(&vc, (size_t)n));
-        CSX_TRY(W.mem.alloc(&vr, (size_t)m));
-        CSX_TRY(W.mem.alloc(&rs, (size_t)nc + 1));
-        CSX_TRY(W.mem.alloc(&ps, (size_t)nc));
+        DevBuf<int32_t> cv, rv, vc, vr, rs;
+        DevBuf<uint32_t> ps;
+        CSX_TRY(cv.alloc((size_t)nc));
+        CSX_TRY(rv.alloc((size_t)nc));
+        CSX_TRY(vc.alloc((size_t)n));
+        CSX_TRY(vr.alloc((size_t)m));
+        CSX_TRY(rs.alloc((size_t)nc + 1));
+        CSX_TRY(ps.alloc((size_t)nc));
         hipLaunchKernelGGL(k_fill, grid_of(n), dim3(256), 0, s, vc, (int64_t)n, -1);
         hipLaunchKernelGGL(k_fill, grid_of(m), dim3(256), 0, s, vr, (int64_t)m, -1);
         hipLaunchKernelGGL(k_fine_maps, grid_of(nc), dim3(256), 0, s, nc, dq, cc[2], dp, rr[1], cv, rv, vc, vr);

@@ -230,23 +230,21 @@ __global__ __launch_bounds__(256) void k_row_span(int32_t rows, int32_t stride, 
 
 static int wants_tiled(const Csc *A, bool *yes) {
     *yes = false;
-    const Gather *g = A->rows;
+    const Gather *g = A->rows.get();
     // small problems: x fits one XCD's L2 (every XCD gathers from all of x), or too few entries to matter
     if ((int64_t)A->n * 8 <= (4ll << 20) || A->nnz < (1 << 24) || !g) return CSX_OK;
     hipStream_t s = ctx().stream;
-    unsigned long long *d = nullptr;
-    CSX_TRY(dalloc(&d, 2));
+    DevBuf<unsigned long long> d;
+    CSX_TRY(d.alloc(2));
     CSX_HIP(hipMemsetAsync(d, 0, 16, s));
     const int32_t stride = g->rows > (1 << 16) ? g->rows >> 16 : 1;
     const int64_t samples = ((int64_t)g->rows + stride - 1) / stride;
     hipLaunchKernelGGL(k_row_span, dim3((unsigned)((samples + 255) / 256)), dim3(256), 0, s, g->rows, stride, g->ptr,
                        g->idx, d, (unsigned int *)(d + 1));
     unsigned long long h[2] = {0, 0};
-    int st = CSX_OK;
-    if (hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-        st = CSX_ERUNTIME;
-    dfree(d);
-    CSX_TRY(st);
+    CSX_HIP(hipMemcpyAsync(h, d, 16, hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    d.reset();
     const unsigned int cnt = (unsigned int)(h[1] & 0xffffffffu);
     if (!cnt) return CSX_OK;
     const double mean_span_bytes = (double)h[0] / cnt * 8.0;
@@ -377,7 +375,7 @@ int csx::gaxpy_device(Csc *A, const double *xd, double *yd, int mode) {
         }
         case CSX_GAXPY_WAVE:
             CSX_TRY(build_row_gather(A));
-            return run_rows(A->rows, A->nnz, xd, yd);
+            return run_rows(A->rows.get(), A->nnz, xd, yd);
         case CSX_GAXPY_TILED:
             CSX_TRY(gaxpy_tiled_prepare(A));
             return gaxpy_tiled_run(A, xd, yd);

@@ -142,10 +142,9 @@ static int run_block(const Gather *g, int32_t nrhs, const double *X, double *Y) 
 
 // nrhs passes of the matrix's own single-vector plan on transposed copies of X and Y.
 static int run_columns(Csc *A, int32_t nrhs, const double *X, double *Y) {
-    DevScope t;
-    double *xc = nullptr, *yc = nullptr;
-    CSX_TRY(t.alloc(&xc, (size_t)A->n * nrhs));
-    CSX_TRY(t.alloc(&yc, (size_t)A->m * nrhs));
+    DevBuf<double> xc, yc;
+    CSX_TRY(xc.alloc((size_t)A->n * nrhs));
+    CSX_TRY(yc.alloc((size_t)A->m * nrhs));
     CSX_TRY(block_transpose(A->n, nrhs, X, xc));
     CSX_TRY(block_transpose(A->m, nrhs, Y, yc));
     for (int32_t c = 0; c < nrhs; c++)
@@ -184,5 +183,5 @@ extern "C" int csx_gaxpy_block(csx_handle_t hA, csx_handle_t hX, csx_handle_t hY
         if (route == 2) return run_columns(A, nrhs, xd, yd);
     }
     CSX_TRY(build_row_gather(A));
-    return run_block(A->rows, nrhs, xd, yd);
+    return run_block(A->rows.get(), nrhs, xd, yd);
 }

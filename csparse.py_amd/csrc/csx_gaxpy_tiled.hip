@@ -357,97 +357,80 @@ int gaxpy_tiled_prepare(Csc *A) {
     const int64_t ntiles = (int64_t)nrb * nslab;
     if (ntiles > 0x3fffffffll || nslab >= (1 << 22)) return CSX_EINVAL;
 
-    TiledPlan *t = new TiledPlan();
+    std::unique_ptr<TiledPlan> t(new TiledPlan());
     t->rb_bits = rb_bits;
     t->row_block = row_block;
     t->nrb = nrb;
     t->nslab = nslab;
     t->slab_cols = (int32_t)slab_cols;
-    int32_t *col = nullptr, *sptr = nullptr, *gptr = nullptr;
-    uint32_t *tid = nullptr, *packed = nullptr, *stid = nullptr, *skey = nullptr;
-    double *sval = nullptr;
-    int64_t ngroups = 0;
-    int st = dalloc(&col, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&tid, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&packed, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&stid, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&skey, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&sval, (size_t)A->nnz);
-    if (st == CSX_OK) st = dalloc(&sptr, (size_t)ntiles + 1);
-    if (st == CSX_OK) st = dalloc(&gptr, (size_t)ntiles + 1);
-    if (st == CSX_OK) st = dalloc(&t->tile_ptr, (size_t)nrb + 1);
-    if (st == CSX_OK) st = expand_columns(A->p, A->n, A->nnz, col);
-    if (st == CSX_OK && A->nnz > 0) {
-        int64_t blocks = ((int64_t)A->nnz + 255) / 256;
-        hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)blocks), dim3(256), 0, s, (int64_t)A->nnz, A->i, col, rb_bits,
-                           row_block, t->slab_cols, t->nslab, tid, packed);
-        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
-    }
-    if (st == CSX_OK) st = stable_sort_by_key(tid, packed, A->x, A->nnz, (uint32_t)ntiles, stid, skey, sval);
-    if (st == CSX_OK) st = boundaries_from_sorted(stid, A->nnz, (int32_t)ntiles, sptr);
-    const unsigned tb = (unsigned)((ntiles + 256) / 256);
-    if (st == CSX_OK) {
+    {
+        DevBuf<int32_t> col, sptr, gptr;
+        DevBuf<uint32_t> tid, packed, stid, skey;
+        DevBuf<double> sval;
+        int64_t ngroups = 0;
+        CSX_TRY(col.alloc((size_t)A->nnz));
+        CSX_TRY(tid.alloc((size_t)A->nnz));
+        CSX_TRY(packed.alloc((size_t)A->nnz));
+        CSX_TRY(stid.alloc((size_t)A->nnz));
+        CSX_TRY(skey.alloc((size_t)A->nnz));
+        CSX_TRY(sval.alloc((size_t)A->nnz));
+        CSX_TRY(sptr.alloc((size_t)ntiles + 1));
+        CSX_TRY(gptr.alloc((size_t)ntiles + 1));
+        CSX_TRY(t->tile_ptr.alloc((size_t)nrb + 1));
+        CSX_TRY(expand_columns(A->p, A->n, A->nnz, col));
+        if (A->nnz > 0) {
+            int64_t blocks = ((int64_t)A->nnz + 255) / 256;
+            hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)blocks), dim3(256), 0, s, (int64_t)A->nnz, A->i, col, rb_bits,
+                               row_block, t->slab_cols, t->nslab, tid, packed);
+            CSX_LAUNCH_CHECK();
+        }
+        CSX_TRY(stable_sort_by_key(tid, packed, A->x, A->nnz, (uint32_t)ntiles, stid, skey, sval));
+        CSX_TRY(boundaries_from_sorted(stid, A->nnz, (int32_t)ntiles, sptr));
+        const unsigned tb = (unsigned)((ntiles + 256) / 256);
         hipLaunchKernelGGL(k_padded_lengths, dim3(tb), dim3(256), 0, s, ntiles, sptr, gptr);
-        st = scan_exclusive_i32(gptr, gptr, ntiles, &ngroups);
-    }
-    // 3-byte keys when every 64-entry run is narrower than 512 columns (and the row fits 15 bits: always, LDS bounds it)
-    bool k24 = false;
-    if (st == CSX_OK && ngroups > 0 && rb_bits <= 15 && ctx().opt.gaxpy_keys24) {
-        int *flag = nullptr;
-        int h = 1;
-        st = dalloc(&flag, 1);
-        if (st == CSX_OK) {
+        CSX_TRY(scan_exclusive_i32(gptr, gptr, ntiles, &ngroups));
+        // 3-byte keys when every 64-entry run is narrower than 512 columns (and the row fits 15 bits: always, LDS bounds it)
+        bool k24 = false;
+        if (ngroups > 0 && rb_bits <= 15 && ctx().opt.gaxpy_keys24) {
+            DevBuf<int> flag;
+            int h = 1;
+            CSX_TRY(flag.alloc(1));
             (void)hipMemsetAsync(flag, 0, sizeof(int), s);
             hipLaunchKernelGGL(k_run_span, dim3((unsigned)(((int64_t)A->nnz + 255) / 256)), dim3(256), 0, s, (int64_t)A->nnz,
                                stid, sptr, skey, rb_bits, flag);
-            if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
+            CSX_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+            CSX_HIP(hipStreamSynchronize(s));
+            k24 = h == 0;
         }
-        dfree(flag);
-        k24 = st == CSX_OK && h == 0;
-    }
-    if (st == CSX_OK) st = dalloc(&t->tile_len, (size_t)ngroups);  // group_info
-    if (st == CSX_OK && !k24) st = dalloc(&t->tile_key, (size_t)ngroups * TL_GROUP);
-    if (st == CSX_OK && k24) st = dalloc(&t->tile_key24, (size_t)ngroups * TL_GROUP * 3 + 16);
-    if (st == CSX_OK && k24) st = dalloc(&t->tile_base, (size_t)ngroups * 4);
-    if (st == CSX_OK) st = dalloc(&t->tile_val, (size_t)ngroups * TL_GROUP);
-    if (st == CSX_OK && ngroups > 0) {
-        // padding slots: column 0 of the slab / offset 0 of the run, dummy row, value 0 -> adds 0 * x into an unused LDS slot
-        if (k24) {
-            hipLaunchKernelGGL(k_fill_key24, dim3(2048), dim3(256), 0, s, t->tile_key24, (int64_t)ngroups * TL_GROUP,
-                               (uint32_t)row_block);
-            (void)hipMemsetAsync(t->tile_base, 0, (size_t)ngroups * 4 * sizeof(uint32_t), s);
-        } else {
-            hipLaunchKernelGGL(k_fill_keys, dim3(2048), dim3(256), 0, s, t->tile_key, (int64_t)ngroups * TL_GROUP,
-                               (uint32_t)row_block);
+        CSX_TRY(t->tile_len.alloc((size_t)ngroups));  // group_info
+        if (!k24) CSX_TRY(t->tile_key.alloc((size_t)ngroups * TL_GROUP));
+        if (k24) CSX_TRY(t->tile_key24.alloc((size_t)ngroups * TL_GROUP * 3 + 16));
+        if (k24) CSX_TRY(t->tile_base.alloc((size_t)ngroups * 4));
+        CSX_TRY(t->tile_val.alloc((size_t)ngroups * TL_GROUP));
+        if (ngroups > 0) {
+            // padding slots: column 0 of the slab / offset 0 of the run, dummy row, value 0 -> adds 0 * x into an unused LDS slot
+            if (k24) {
+                hipLaunchKernelGGL(k_fill_key24, dim3(2048), dim3(256), 0, s, t->tile_key24, (int64_t)ngroups * TL_GROUP,
+                                   (uint32_t)row_block);
+                (void)hipMemsetAsync(t->tile_base, 0, (size_t)ngroups * 4 * sizeof(uint32_t), s);
+            } else {
+                hipLaunchKernelGGL(k_fill_keys, dim3(2048), dim3(256), 0, s, t->tile_key, (int64_t)ngroups * TL_GROUP,
+                                   (uint32_t)row_block);
+            }
+            (void)hipMemsetAsync(t->tile_val, 0, (size_t)ngroups * TL_GROUP * sizeof(double), s);
+            hipLaunchKernelGGL(k_group_info, dim3(tb), dim3(256), 0, s, ntiles, nslab, sptr, gptr, (uint32_t *)t->tile_len.get());
+            hipLaunchKernelGGL(k_interleave, dim3((unsigned)(((int64_t)A->nnz + 255) / 256)), dim3(256), 0, s,
+                               (int64_t)A->nnz, stid, sptr, gptr, skey, sval, t->tile_key, t->tile_val);
+            if (k24)
+                hipLaunchKernelGGL(k_interleave24, dim3((unsigned)(((int64_t)A->nnz + 255) / 256)), dim3(256), 0, s,
+                                   (int64_t)A->nnz, stid, sptr, gptr, skey, rb_bits, t->tile_key24, t->tile_base);
         }
-        (void)hipMemsetAsync(t->tile_val, 0, (size_t)ngroups * TL_GROUP * sizeof(double), s);
-        hipLaunchKernelGGL(k_group_info, dim3(tb), dim3(256), 0, s, ntiles, nslab, sptr, gptr, (uint32_t *)t->tile_len);
-        hipLaunchKernelGGL(k_interleave, dim3((unsigned)(((int64_t)A->nnz + 255) / 256)), dim3(256), 0, s,
-                           (int64_t)A->nnz, stid, sptr, gptr, skey, sval, t->tile_key, t->tile_val);
-        if (k24)
-            hipLaunchKernelGGL(k_interleave24, dim3((unsigned)(((int64_t)A->nnz + 255) / 256)), dim3(256), 0, s,
-                               (int64_t)A->nnz, stid, sptr, gptr, skey, rb_bits, t->tile_key24, t->tile_base);
-    }
-    if (st == CSX_OK) {
         hipLaunchKernelGGL(k_rb_group_ptr, dim3((unsigned)((nrb + 256) / 256)), dim3(256), 0, s, nrb, nslab, gptr,
                            t->tile_ptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
+        CSX_LAUNCH_CHECK();
+        CSX_HIP(hipStreamSynchronize(s));
     }
-    dfree(col);
-    dfree(tid);
-    dfree(packed);
-    dfree(stid);
-    dfree(skey);
-    dfree(sval);
-    dfree(sptr);
-    dfree(gptr);
-    if (st != CSX_OK) {
-        free_tiled(t);
-        return st;
-    }
-    A->tiled = t;
+    A->tiled = std::move(t);
 #ifndef CSX_ABLATION
     // Off by default ("gaxpy.tune_shape"): on every box and run seen 4 x 5 was the fastest or within the noise of the
     // fastest, and a choice made from two short timings is itself noisy (under the profiler it picked 8 x 4, which
@@ -464,12 +447,11 @@ constexpr int TL_NSHAPES = 4;
 static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shape);
 
 static int gaxpy_tiled_pick_shape(Csc *A) {
-    TiledPlan *t = A->tiled;
+    TiledPlan *t = A->tiled.get();
     if ((int64_t)A->nnz < (int64_t)1 << 24) return CSX_OK;      // small matrices: the default shape, no 10 ms of tuning
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    double *x = nullptr, *y = nullptr;
-    if (tmp.alloc(&x, (size_t)A->n) != CSX_OK || tmp.alloc(&y, (size_t)A->m) != CSX_OK) return CSX_OK;   // no room: default
+    DevBuf<double> x, y;
+    if (x.alloc((size_t)A->n) != CSX_OK || y.alloc((size_t)A->m) != CSX_OK) return CSX_OK;   // no room: default
     CSX_HIP(hipMemsetAsync(x, 0, (size_t)A->n * sizeof(double), s));   // the gathers go where they always go; values do not matter
     CSX_HIP(hipMemsetAsync(y, 0, (size_t)A->m * sizeof(double), s));
     hipEvent_t e0, e1;
@@ -502,7 +484,7 @@ static int gaxpy_tiled_pick_shape(Csc *A) {
 int gaxpy_tiled_run(const Csc *A, const double *x, double *y) { return gaxpy_tiled_launch(A, x, y, A->tiled->shape); }
 
 static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shape) {
-    const TiledPlan *t = A->tiled;
+    const TiledPlan *t = A->tiled.get();
     hipStream_t s = ctx().stream;
     const size_t lds = (((size_t)(t->row_block + 1) * sizeof(double)) + 15) & ~(size_t)15;  // + dummy row
     const int32_t nwg = ctx().cus > 0 ? ctx().cus : 256;
@@ -512,8 +494,9 @@ static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shap
         CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gaxpy_tiled<V, NW, NG, K24>),                  \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, TL_LDS_BYTES));                      \
         hipLaunchKernelGGL((k_gaxpy_tiled<V, NW, NG, K24>), dim3(grid), dim3(64 * NW), lds, s, t->tile_ptr,          \
-                           (const uint32_t *)t->tile_len,                                                            \
-                           K24 ? reinterpret_cast<const uint32_t *>(t->tile_key24) : t->tile_key, t->tile_base,      \
+                           (const uint32_t *)t->tile_len.get(),                                                      \
+                           K24 ? reinterpret_cast<const uint32_t *>(t->tile_key24.get()) : t->tile_key.get(),        \
+                           t->tile_base,                                                                             \
                            t->tile_val, x, y, A->m, t->nrb, t->row_block, t->slab_cols, t->rb_bits);                 \
     }
 #define CSX_TILED_LAUNCH(V, NW, NG)                                                                                  \

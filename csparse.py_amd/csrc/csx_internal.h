@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -43,6 +44,53 @@ void set_error(const char *fmt, ...);
 
 #define CSX_LAUNCH_CHECK() CSX_HIP(hipGetLastError())
 
+// device allocation helpers (bytes may be 0 -> still returns a valid pointer)
+int dmalloc(void **p, size_t bytes);
+template <class T>
+inline int dalloc(T **p, size_t count) { return dmalloc((void **)p, count * sizeof(T)); }
+void dfree(void *p);
+void pool_trim();                               // release every idle block to the driver
+void pool_stats(size_t *cached, size_t *live);  // bytes idle in the cache / handed out
+void pool_set_limit(size_t bytes);              // cap of the cache (0: the default quarter of the device)
+
+// Owner of one device array from the pool: dfree'd when the buffer is destroyed, reset or allocated again.  Move-only, host
+// only.  It converts to T *, so launches, copies and kernel-argument structs take it where they took the raw pointer.
+template <class T>
+class DevBuf {
+  public:
+    DevBuf() = default;
+    explicit DevBuf(T *owned) : p_(owned) {}   // takes over a block from dmalloc
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(o.release()) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.release();
+        }
+        return *this;
+    }
+    ~DevBuf() { dfree(p_); }
+    int alloc(size_t count) {   // count may be 0 (still a valid pointer)
+        reset();
+        return dalloc(&p_, count);
+    }
+    void reset() {
+        dfree(p_);
+        p_ = nullptr;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    T *release() {   // for an owner that records its ownership itself (Csc, Vec)
+        T *p = p_;
+        p_ = nullptr;
+        return p;
+    }
+
+  private:
+    T *p_ = nullptr;
+};
+
 enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN };
 
 struct Csc;
@@ -52,9 +100,8 @@ struct Csc;
 // reference updates that row.
 struct Gather {
     int32_t rows = 0;
-    int32_t *ptr = nullptr;
-    int32_t *idx = nullptr;
-    double *val = nullptr;
+    DevBuf<int32_t> ptr, idx;
+    DevBuf<double> val;
 };
 
 // LDS-resident SpMV plan (csx_gaxpy_tiled.hip): entries regrouped into (row block, column slab)
@@ -64,14 +111,14 @@ struct TiledPlan {
     int32_t nrb = 0;               // number of row blocks
     int32_t nslab = 0;             // number of column slabs
     int32_t slab_cols = 0;         // columns per slab
-    int32_t *tile_ptr = nullptr;   // [nrb + 1] first group of every row block
-    int32_t *tile_len = nullptr;   // [ngroups] group info: (slab << 9) | entries in the group
-    uint32_t *tile_key = nullptr;  // packed (local col << rb_bits) | local row; null when the 3-byte keys are in use
-    double *tile_val = nullptr;
+    DevBuf<int32_t> tile_ptr;      // [nrb + 1] first group of every row block
+    DevBuf<int32_t> tile_len;      // [ngroups] group info: (slab << 9) | entries in the group
+    DevBuf<uint32_t> tile_key;     // packed (local col << rb_bits) | local row; null when the 3-byte keys are in use
+    DevBuf<double> tile_val;
     int rb_bits = 0;
     // 3-byte keys (row | column offset << 15), used when every run of 64 column-sorted entries spans < 512 columns:
-    uint8_t *tile_key24 = nullptr; // [ngroups * 768]
-    uint32_t *tile_base = nullptr; // [ngroups * 4] slab-local column of the first entry of each 64-entry run
+    DevBuf<uint8_t> tile_key24;    // [ngroups * 768]
+    DevBuf<uint32_t> tile_base;    // [ngroups * 4] slab-local column of the first entry of each 64-entry run
     // launch shape (waves per workgroup x groups per wave and step), picked when the plan is built by timing the
     // candidates on this device (gaxpy_tiled_prepare); -1: the default shape
     int shape = -1;
@@ -83,12 +130,18 @@ struct TiledPlan {
 struct HouseLevels {
     int32_t nlevels = 0;
     std::vector<int32_t> ptr;      // host: [nlevels + 1] into cols
-    int32_t *cols = nullptr;       // device: columns ordered by level, ascending inside a level
+    DevBuf<int32_t> cols;          // device: columns ordered by level, ascending inside a level
 };
 
 struct CliqueForest;   // csx_cholclique.h
 
+// A matrix's arrays are the library's (dfree'd by ~Csc) unless `owns` is false (csx_csc_wrap: the caller's).  Not copyable:
+// a copy would free them twice.
 struct Csc {
+    Csc();    // (both in csx_core.hip, where CliqueForest is complete)
+    ~Csc();
+    Csc(const Csc &) = delete;
+    Csc &operator=(const Csc &) = delete;
     int32_t m = 0, n = 0, nnz = 0;
     int32_t *p = nullptr;
     int32_t *i = nullptr;
@@ -96,17 +149,25 @@ struct Csc {
     bool owns = true;
     bool trusted = true;  // structure made or checked by the library; false for csx_csc_wrap until csc_validate has passed
     // cached plans (built on demand, freed with the matrix)
-    Gather *rows = nullptr;   // stable transpose = rows of A in ascending column order
-    TiledPlan *tiled = nullptr;
-    HouseLevels *house = nullptr;   // csx_happly's level schedule (pattern only; dropped by csx_csc_invalidate too)
-    CliqueForest *clique = nullptr; // csx_schol's finding "a forest of cliques on consecutive columns" (tree, counts, block list on the
-                                    // device), kept for the csx_chol that follows; pattern only, dropped by csx_csc_invalidate too
+    std::unique_ptr<Gather> rows;         // stable transpose = rows of A in ascending column order
+    std::unique_ptr<TiledPlan> tiled;
+    std::unique_ptr<HouseLevels> house;   // csx_happly's level schedule (pattern only; dropped by csx_csc_invalidate too)
+    std::unique_ptr<CliqueForest> clique; // csx_schol's finding "a forest of cliques on consecutive columns" (tree, counts, block list
+                                          // on the device), kept for the csx_chol that follows; pattern only, dropped by
+                                          // csx_csc_invalidate too
     bool rows_pending = false;      // i == nullptr ON PURPOSE: every column holds the consecutive rows j, j + 1, ... (the factor of a
                                     // forest of cliques, csx_cholsol_factor), so i[] follows from p[] alone and is written by
                                     // csc_fill_rows the first time a handle to the matrix is resolved (csc() below)
 };
 
+// d is the library's (dfree'd by ~Vec) unless `owns` is false (csx_vec_wrap: the caller's)
 struct Vec {
+    Vec() = default;
+    ~Vec() {
+        if (owns) dfree(d);
+    }
+    Vec(const Vec &) = delete;
+    Vec &operator=(const Vec &) = delete;
     int64_t len = 0;
     void *d = nullptr;
     bool owns = true;
@@ -117,6 +178,12 @@ struct CholPlan;  // csx_chol.hip
 struct ShardPlan; // csx_comm.hip
 struct SnPlan;    // csx_snsolve.hip
 struct BtfPlan;   // csx_btf.hip
+// delete p, in the file where the type is complete (csx_free)
+void destroy(TriPlan *p);
+void destroy(CholPlan *p);
+void destroy(ShardPlan *p);
+void destroy(BtfPlan *p);
+void destroy(SnPlan *p);
 
 struct Object {
     Kind kind = K_FREE;
@@ -193,24 +260,22 @@ inline Csc *csc(csx_handle_t h) {
 inline Vec *vec(csx_handle_t h) { return (Vec *)get(h, K_VEC); }
 inline Vec *ivec(csx_handle_t h) { return (Vec *)get(h, K_IVEC); }
 
-// device allocation helpers (bytes may be 0 -> still returns a valid pointer)
-int dmalloc(void **p, size_t bytes);
 template <class T>
-inline int dalloc(T **p, size_t count) { return dmalloc((void **)p, count * sizeof(T)); }
-void dfree(void *p);
-void pool_trim();                               // release every idle block to the driver
-void pool_stats(size_t *cached, size_t *live);  // bytes idle in the cache / handed out
-void pool_set_limit(size_t bytes);              // cap of the cache (0: the default quarter of the device)
+int upload(DevBuf<T> &d, const T *h, size_t count) {
+    CSX_TRY(d.alloc(count));
+    if (count) CSX_HIP(hipMemcpyAsync(d.get(), h, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
+    return CSX_OK;
+}
+template <class T>
+int upload(DevBuf<T> &d, const std::vector<T> &h) { return upload(d, h.data(), h.size()); }
+// h = d[0 .. count), synchronising the context's stream
+inline int download_i32(std::vector<int32_t> &h, const int32_t *d, size_t count) {
+    h.resize(count);
+    if (count) CSX_HIP(hipMemcpyAsync(h.data(), d, count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx().stream));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return CSX_OK;
+}
 
-void free_gather(Gather *g);
-void free_clique_cache(CliqueForest *F);   // csx_cholclique.hip
-void free_tiled(TiledPlan *t);
-void free_csc(Csc *A);
-void free_triplan(TriPlan *t);
-void free_cholplan(CholPlan *t);
-void free_shardplan(ShardPlan *t);
-void free_snplan(SnPlan *t);
-void free_btfplan(BtfPlan *t);
 // csx_snsolve.hip: supernodal schedule of a Cholesky-shaped factor for the rounding-equal order of a cholsol plan
 int sn_build(const Csc *L, const int32_t *parent, const int32_t *Lp_h, const int32_t *Gp_h, const int32_t *Gp, const int32_t *Gi,
              const double *Gx, int32_t col_levels, SnPlan **out);
@@ -221,20 +286,6 @@ int sn_prepare(SnPlan *P, int32_t nrhs);   // work space of a solve with nrhs ri
 void sn_info(const SnPlan *P, int32_t *nsn, int32_t *levels, int32_t *max_w);
 void sn_info2(const SnPlan *P, int32_t *matrix_cores, double *growth);
 bool sn_usable(const SnPlan *P);   // with the options in force (a plan with relaxed supernodes needs the matrix-core triangles)
-
-// Device temporaries of a host function with several exits: freed when the guard leaves scope.
-struct DevScope {
-    std::vector<void *> held;
-    ~DevScope() {
-        for (void *p : held) dfree(p);
-    }
-    template <class T>
-    int alloc(T **p, size_t count) {
-        const int st = dalloc(p, count);
-        if (st == CSX_OK) held.push_back((void *)*p);
-        return st;
-    }
-};
 
 // ---- device primitives (csx_scan.hip, csx_sort.hip) ----
 // out[k] = sum(in[0..k-1]) for k in [0, n]; out has n+1 slots; in may alias out

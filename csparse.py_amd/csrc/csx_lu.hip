@@ -357,37 +357,32 @@ extern "C" int csx_lu_blocks(csx_handle_t hA, double tol, csx_handle_t *hL, csx_
     const int32_t n = A->n;
     if (n < LU_MIN_COMPONENTS) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *root = nullptr, *comp_of_pos = nullptr, *local_id = nullptr, *lcount = nullptr, *ucount = nullptr,
-            *d_pinv = nullptr;
-    uint32_t *nodes = nullptr;
-    int *flags = nullptr;
+    DevBuf<int32_t> root, comp_of_pos, local_id, lcount, ucount, d_pinv, sLi, sUi, sLp, sUp;
+    DevBuf<uint32_t> nodes;
+    DevBuf<double> sLx, sUx;
+    DevBuf<int> flags;
+    DevBuf<Tree> comps;
     bool bad = false;
-    CSX_TRY(tmp.alloc(&root, (size_t)n));
+    CSX_TRY(root.alloc((size_t)n));
     CSX_TRY(connected_components(n, A->p, A->i, 0, 0, 0, root, &bad));
     if (bad) return CSX_EINVAL;
-    CSX_TRY(tmp.alloc(&nodes, (size_t)n));
-    CSX_TRY(tmp.alloc(&comp_of_pos, (size_t)n));
-    Tree *comps = nullptr;
+    CSX_TRY(nodes.alloc((size_t)n));
+    CSX_TRY(comp_of_pos.alloc((size_t)n));
     int32_t ncomp = 0, maxc = 0;
-    int st = group_by_root(n, root, nodes, comp_of_pos, &comps, &ncomp, &maxc);
-    tmp.held.push_back(comps);
-    CSX_TRY(st);
+    CSX_TRY(group_by_root(n, root, nodes, comp_of_pos, &comps, &ncomp, &maxc));
     if (ncomp < LU_MIN_COMPONENTS || maxc > LU_MAX_M) return CSX_OK;
     const int32_t ld = maxc;                            // a component of m rows owns a strip of m * ld >= m * m entries
-    int32_t *sLi = nullptr, *sUi = nullptr, *sLp = nullptr, *sUp = nullptr;
-    double *sLx = nullptr, *sUx = nullptr;
-    CSX_TRY(tmp.alloc(&local_id, (size_t)n));
-    CSX_TRY(tmp.alloc(&lcount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&ucount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&d_pinv, (size_t)n));
-    CSX_TRY(tmp.alloc(&sLi, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sLx, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sUi, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sUx, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sLp, (size_t)n + ncomp + 1));
-    CSX_TRY(tmp.alloc(&sUp, (size_t)n + ncomp + 1));
-    CSX_TRY(tmp.alloc(&flags, 2));
+    CSX_TRY(local_id.alloc((size_t)n));
+    CSX_TRY(lcount.alloc((size_t)n + 1));
+    CSX_TRY(ucount.alloc((size_t)n + 1));
+    CSX_TRY(d_pinv.alloc((size_t)n));
+    CSX_TRY(sLi.alloc((size_t)n * ld));
+    CSX_TRY(sLx.alloc((size_t)n * ld));
+    CSX_TRY(sUi.alloc((size_t)n * ld));
+    CSX_TRY(sUx.alloc((size_t)n * ld));
+    CSX_TRY(sLp.alloc((size_t)n + ncomp + 1));
+    CSX_TRY(sUp.alloc((size_t)n + ncomp + 1));
+    CSX_TRY(flags.alloc(2));
     int hflags[2] = {0x7fffffff, 0};
     CSX_HIP(hipMemcpyAsync(flags, hflags, sizeof hflags, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_lu_local_id, dim3((unsigned)((ncomp + 3) / 4)), dim3(256), 0, s, ncomp, comps, nodes, local_id);
@@ -400,36 +395,26 @@ extern "C" int csx_lu_blocks(csx_handle_t hA, double tol, csx_handle_t *hL, csx_
     CSX_HIP(hipMemcpyAsync(hflags, flags, sizeof hflags, hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
     if (hflags[0] != 0x7fffffff) return CSX_ENOTSPD;    // a singular block: the reference returns None
-    Csc *L = new Csc(), *U = new Csc();
+    std::unique_ptr<Csc> L(new Csc()), U(new Csc());
     L->m = L->n = U->m = U->n = n;
     int64_t lnz = 0, unz = 0;
-    st = dalloc(&L->p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&U->p, (size_t)n + 1);
-    if (st == CSX_OK) st = scan_exclusive_i32(lcount, L->p, n, &lnz);
-    if (st == CSX_OK) st = scan_exclusive_i32(ucount, U->p, n, &unz);
-    if (st == CSX_OK) {
-        L->nnz = (int32_t)lnz;
-        U->nnz = (int32_t)unz;
-        st = dalloc(&L->i, (size_t)lnz);
-    }
-    if (st == CSX_OK) st = dalloc(&L->x, (size_t)lnz);
-    if (st == CSX_OK) st = dalloc(&U->i, (size_t)unz);
-    if (st == CSX_OK) st = dalloc(&U->x, (size_t)unz);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_lu_fill, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, comp_of_pos, comps, nodes, ld, sLi,
-                           sLx, sUi, sUx, sLp, sUp, L->p, L->i, L->x, U->p, U->i, U->x);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(pinv_host, d_pinv, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            st = CSX_ERUNTIME;
-    }
-    if (st != CSX_OK) {
-        free_csc(L);
-        free_csc(U);
-        return st;
-    }
-    *hL = put(K_CSC, L);
-    *hU = put(K_CSC, U);
+    CSX_TRY(dalloc(&L->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&U->p, (size_t)n + 1));
+    CSX_TRY(scan_exclusive_i32(lcount, L->p, n, &lnz));
+    CSX_TRY(scan_exclusive_i32(ucount, U->p, n, &unz));
+    L->nnz = (int32_t)lnz;
+    U->nnz = (int32_t)unz;
+    CSX_TRY(dalloc(&L->i, (size_t)lnz));
+    CSX_TRY(dalloc(&L->x, (size_t)lnz));
+    CSX_TRY(dalloc(&U->i, (size_t)unz));
+    CSX_TRY(dalloc(&U->x, (size_t)unz));
+    hipLaunchKernelGGL(k_lu_fill, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, comp_of_pos, comps, nodes, ld, sLi,
+                       sLx, sUi, sUx, sLp, sUp, L->p, L->i, L->x, U->p, U->i, U->x);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(pinv_host, d_pinv, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    *hL = put(K_CSC, L.release());
+    *hU = put(K_CSC, U.release());
     *done = 1;
     return CSX_OK;
 }
@@ -447,41 +432,35 @@ extern "C" int csx_qr_blocks(csx_handle_t hA, const int32_t *parent_host, const 
     for (int32_t i = 0; i < n; i++)
         if (parent_host[i] >= n || pinv_host[i] >= n || leftmost_host[i] >= n) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *root = nullptr, *comp_of_pos = nullptr, *local_id = nullptr, *vcount = nullptr, *rcount = nullptr,
-            *d_parent = nullptr, *d_pinv = nullptr, *d_left = nullptr;
-    uint32_t *nodes = nullptr;
-    double *d_beta = nullptr;
-    int *flags = nullptr;
+    DevBuf<int32_t> root, comp_of_pos, local_id, vcount, rcount, d_parent, d_pinv, d_left, sVi, sRi, sVp, sRp;
+    DevBuf<uint32_t> nodes;
+    DevBuf<double> d_beta, sVx, sRx;
+    DevBuf<int> flags;
+    DevBuf<Tree> comps;
     bool bad = false;
-    CSX_TRY(tmp.alloc(&root, (size_t)n));
+    CSX_TRY(root.alloc((size_t)n));
     CSX_TRY(connected_components(n, A->p, A->i, 0, 0, 0, root, &bad));
     if (bad) return CSX_EINVAL;
-    CSX_TRY(tmp.alloc(&nodes, (size_t)n));
-    CSX_TRY(tmp.alloc(&comp_of_pos, (size_t)n));
-    Tree *comps = nullptr;
+    CSX_TRY(nodes.alloc((size_t)n));
+    CSX_TRY(comp_of_pos.alloc((size_t)n));
     int32_t ncomp = 0, maxc = 0;
-    int st = group_by_root(n, root, nodes, comp_of_pos, &comps, &ncomp, &maxc);
-    tmp.held.push_back(comps);
-    CSX_TRY(st);
+    CSX_TRY(group_by_root(n, root, nodes, comp_of_pos, &comps, &ncomp, &maxc));
     if (ncomp < QR_MIN_COMPONENTS || maxc > QR_MAX_M) return CSX_OK;
     const int32_t ld = maxc;
-    int32_t *sVi = nullptr, *sRi = nullptr, *sVp = nullptr, *sRp = nullptr;
-    double *sVx = nullptr, *sRx = nullptr;
-    CSX_TRY(tmp.alloc(&local_id, (size_t)n));
-    CSX_TRY(tmp.alloc(&vcount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&rcount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&d_parent, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_pinv, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_left, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_beta, (size_t)n));
-    CSX_TRY(tmp.alloc(&sVi, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sVx, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sRi, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sRx, (size_t)n * ld));
-    CSX_TRY(tmp.alloc(&sVp, (size_t)n + ncomp + 1));
-    CSX_TRY(tmp.alloc(&sRp, (size_t)n + ncomp + 1));
-    CSX_TRY(tmp.alloc(&flags, 2));
+    CSX_TRY(local_id.alloc((size_t)n));
+    CSX_TRY(vcount.alloc((size_t)n + 1));
+    CSX_TRY(rcount.alloc((size_t)n + 1));
+    CSX_TRY(d_parent.alloc((size_t)n));
+    CSX_TRY(d_pinv.alloc((size_t)n));
+    CSX_TRY(d_left.alloc((size_t)n));
+    CSX_TRY(d_beta.alloc((size_t)n));
+    CSX_TRY(sVi.alloc((size_t)n * ld));
+    CSX_TRY(sVx.alloc((size_t)n * ld));
+    CSX_TRY(sRi.alloc((size_t)n * ld));
+    CSX_TRY(sRx.alloc((size_t)n * ld));
+    CSX_TRY(sVp.alloc((size_t)n + ncomp + 1));
+    CSX_TRY(sRp.alloc((size_t)n + ncomp + 1));
+    CSX_TRY(flags.alloc(2));
     CSX_HIP(hipMemsetAsync(flags, 0, 2 * sizeof(int), s));
     CSX_HIP(hipMemcpyAsync(d_parent, parent_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CSX_HIP(hipMemcpyAsync(d_pinv, pinv_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -498,36 +477,26 @@ extern "C" int csx_qr_blocks(csx_handle_t hA, const int32_t *parent_host, const 
     CSX_HIP(hipMemcpyAsync(hflags, flags, sizeof hflags, hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
     if (hflags[0]) return CSX_OK;                       // the analysis does not follow the blocks: host code
-    Csc *V = new Csc(), *R = new Csc();
+    std::unique_ptr<Csc> V(new Csc()), R(new Csc());
     V->m = V->n = R->m = R->n = n;
     int64_t vnz = 0, rnz = 0;
-    st = dalloc(&V->p, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&R->p, (size_t)n + 1);
-    if (st == CSX_OK) st = scan_exclusive_i32(vcount, V->p, n, &vnz);
-    if (st == CSX_OK) st = scan_exclusive_i32(rcount, R->p, n, &rnz);
-    if (st == CSX_OK) {
-        V->nnz = (int32_t)vnz;
-        R->nnz = (int32_t)rnz;
-        st = dalloc(&V->i, (size_t)vnz);
-    }
-    if (st == CSX_OK) st = dalloc(&V->x, (size_t)vnz);
-    if (st == CSX_OK) st = dalloc(&R->i, (size_t)rnz);
-    if (st == CSX_OK) st = dalloc(&R->x, (size_t)rnz);
-    if (st == CSX_OK) {
-        hipLaunchKernelGGL(k_lu_fill, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, comp_of_pos, comps, nodes, ld, sVi,
-                           sVx, sRi, sRx, sVp, sRp, V->p, V->i, V->x, R->p, R->i, R->x);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(beta_host, d_beta, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            st = CSX_ERUNTIME;
-    }
-    if (st != CSX_OK) {
-        free_csc(V);
-        free_csc(R);
-        return st;
-    }
-    *hV = put(K_CSC, V);
-    *hR = put(K_CSC, R);
+    CSX_TRY(dalloc(&V->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&R->p, (size_t)n + 1));
+    CSX_TRY(scan_exclusive_i32(vcount, V->p, n, &vnz));
+    CSX_TRY(scan_exclusive_i32(rcount, R->p, n, &rnz));
+    V->nnz = (int32_t)vnz;
+    R->nnz = (int32_t)rnz;
+    CSX_TRY(dalloc(&V->i, (size_t)vnz));
+    CSX_TRY(dalloc(&V->x, (size_t)vnz));
+    CSX_TRY(dalloc(&R->i, (size_t)rnz));
+    CSX_TRY(dalloc(&R->x, (size_t)rnz));
+    hipLaunchKernelGGL(k_lu_fill, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, comp_of_pos, comps, nodes, ld, sVi,
+                       sVx, sRi, sRx, sVp, sRp, V->p, V->i, V->x, R->p, R->i, R->x);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(beta_host, d_beta, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    *hV = put(K_CSC, V.release());
+    *hR = put(K_CSC, R.release());
     *done = 1;
     return CSX_OK;
 }

@@ -254,102 +254,102 @@ extern "C" int csx_lu_etree(csx_handle_t hA, double tol, csx_handle_t *hL, csx_h
     int64_t slots = (int64_t)std::max<size_t>(64, budget / ((size_t)n * 21));
     slots = std::min<int64_t>(slots, ((int64_t)widest + 63) / 64 * 64);
     slots = slots / 64 * 64;
-    DevScope tmp;
+    DevBuf<int32_t> d_order, lcount, ucount, pinv, Lstart, Lend, Ustart, Uend, wi;
+    DevBuf<unsigned long long> next;
+    DevBuf<int> flags;
+    DevBuf<double> wx;
+    DevBuf<unsigned char> ws;
+    CSX_TRY(upload(d_order, order));
+    CSX_TRY(pinv.alloc((size_t)n));
+    CSX_TRY(Lstart.alloc((size_t)n));
+    CSX_TRY(Lend.alloc((size_t)n));
+    CSX_TRY(Ustart.alloc((size_t)n));
+    CSX_TRY(Uend.alloc((size_t)n));
+    CSX_TRY(lcount.alloc((size_t)n + 1));
+    CSX_TRY(ucount.alloc((size_t)n + 1));
+    CSX_TRY(next.alloc(2));
+    CSX_TRY(flags.alloc(2));
+    CSX_TRY(wx.alloc((size_t)slots * n));
+    CSX_TRY(wi.alloc((size_t)slots * 3 * n));
+    CSX_TRY(ws.alloc((size_t)slots * n));
+    CSX_HIP(hipMemsetAsync(wx, 0, (size_t)slots * n * sizeof(double), s));
+    CSX_HIP(hipMemsetAsync(ws, 0, (size_t)slots * n, s));
     LuArgs a{};
     a.n = n;
     a.Ap = A->p;
     a.Ai = A->i;
     a.Ax = A->x;
     a.tol = tol;
-    int32_t *d_order = nullptr, *lcount = nullptr, *ucount = nullptr;
-    CSX_TRY(tmp.alloc(&d_order, (size_t)n));
-    CSX_HIP(hipMemcpyAsync(d_order, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    CSX_TRY(tmp.alloc(&a.pinv, (size_t)n));
-    CSX_TRY(tmp.alloc(&a.Lstart, (size_t)n));
-    CSX_TRY(tmp.alloc(&a.Lend, (size_t)n));
-    CSX_TRY(tmp.alloc(&a.Ustart, (size_t)n));
-    CSX_TRY(tmp.alloc(&a.Uend, (size_t)n));
-    CSX_TRY(tmp.alloc(&lcount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&ucount, (size_t)n + 1));
-    CSX_TRY(tmp.alloc(&a.next, 2));
-    CSX_TRY(tmp.alloc(&a.flags, 2));
-    CSX_TRY(tmp.alloc(&a.wx, (size_t)slots * n));
-    CSX_TRY(tmp.alloc(&a.wi, (size_t)slots * 3 * n));
-    CSX_TRY(tmp.alloc(&a.ws, (size_t)slots * n));
-    CSX_HIP(hipMemsetAsync(a.wx, 0, (size_t)slots * n * sizeof(double), s));
-    CSX_HIP(hipMemsetAsync(a.ws, 0, (size_t)slots * n, s));
+    a.pinv = pinv;
+    a.Lstart = Lstart;
+    a.Lend = Lend;
+    a.Ustart = Ustart;
+    a.Uend = Uend;
+    a.next = next;
+    a.flags = flags;
+    a.wx = wx;
+    a.wi = wi;
+    a.ws = ws;
     unsigned long long cap = (unsigned long long)A->nnz * 16 + (unsigned long long)n * 4;
     for (int attempt = 0; attempt < 4; attempt++, cap *= 4) {
         cap = std::min<unsigned long long>(cap, 0x7FFFFFF0ull);
         a.lcap = a.ucap = cap;
-        int st = dalloc(&a.Li, (size_t)cap);
-        if (st == CSX_OK) st = dalloc(&a.Lx, (size_t)cap);
-        if (st == CSX_OK) st = dalloc(&a.Ui, (size_t)cap);
-        if (st == CSX_OK) st = dalloc(&a.Ux, (size_t)cap);
+        DevBuf<int32_t> Li, Ui;   // the strips, made again bigger for another attempt
+        DevBuf<double> Lx, Ux;
+        CSX_TRY(Li.alloc((size_t)cap));
+        CSX_TRY(Lx.alloc((size_t)cap));
+        CSX_TRY(Ui.alloc((size_t)cap));
+        CSX_TRY(Ux.alloc((size_t)cap));
+        a.Li = Li;
+        a.Lx = Lx;
+        a.Ui = Ui;
+        a.Ux = Ux;
         int hflags[2] = {0x7fffffff, 0};
-        if (st == CSX_OK &&
-            (hipMemsetAsync(a.pinv, 0xFF, (size_t)n * sizeof(int32_t), s) != hipSuccess ||
-             hipMemsetAsync(a.next, 0, 2 * sizeof(unsigned long long), s) != hipSuccess ||
-             hipMemcpyAsync(a.flags, hflags, sizeof hflags, hipMemcpyHostToDevice, s) != hipSuccess))
-            st = CSX_ERUNTIME;
-        for (int32_t l = 0; l < nlev && st == CSX_OK; l++)
+        CSX_HIP(hipMemsetAsync(a.pinv, 0xFF, (size_t)n * sizeof(int32_t), s));
+        CSX_HIP(hipMemsetAsync(a.next, 0, 2 * sizeof(unsigned long long), s));
+        CSX_HIP(hipMemcpyAsync(a.flags, hflags, sizeof hflags, hipMemcpyHostToDevice, s));
+        for (int32_t l = 0; l < nlev; l++)
             for (int32_t f = lev_ptr[(size_t)l]; f < lev_ptr[(size_t)l + 1]; f += (int32_t)slots) {
                 const int32_t cnt = (int32_t)std::min<int64_t>(slots, (int64_t)lev_ptr[(size_t)l + 1] - f);
                 hipLaunchKernelGGL(k_lu_level, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, s, a, d_order, f, cnt);
             }
-        if (st == CSX_OK &&
-            (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, a.flags, sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipStreamSynchronize(s) != hipSuccess))
-            st = CSX_ERUNTIME;
-        bool again = false;
-        if (st == CSX_OK && hflags[0] != 0x7fffffff) st = CSX_ENOTSPD;     // singular: the reference returns None (csparse.py:1423)
-        else if (st == CSX_OK && hflags[1]) again = cap < 0x7FFFFFF0ull;   // the strips were too small
-        if (st == CSX_OK && hflags[1] && !again) st = CSX_EINVAL;
-        if (st == CSX_OK && !again) {
-            // assemble in column order
-            Csc *L = new Csc(), *U = new Csc();
-            L->m = L->n = U->m = U->n = n;
-            int64_t lnz = 0, unz = 0;
-            st = dalloc(&L->p, (size_t)n + 1);
-            if (st == CSX_OK) st = dalloc(&U->p, (size_t)n + 1);
-            const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
-            hipLaunchKernelGGL(k_lu_counts, dim3(nb), dim3(256), 0, s, n, a.Lstart, a.Lend, lcount);
-            hipLaunchKernelGGL(k_lu_counts, dim3(nb), dim3(256), 0, s, n, a.Ustart, a.Uend, ucount);
-            if (st == CSX_OK) st = scan_exclusive_i32(lcount, L->p, n, &lnz);
-            if (st == CSX_OK) st = scan_exclusive_i32(ucount, U->p, n, &unz);
-            if (st == CSX_OK) {
-                L->nnz = (int32_t)lnz;
-                U->nnz = (int32_t)unz;
-                st = dalloc(&L->i, (size_t)lnz);
-                if (st == CSX_OK) st = dalloc(&L->x, (size_t)lnz);
-                if (st == CSX_OK) st = dalloc(&U->i, (size_t)unz);
-                if (st == CSX_OK) st = dalloc(&U->x, (size_t)unz);
-            }
-            if (st == CSX_OK) {
-                const unsigned nw = (unsigned)(((int64_t)n + 3) / 4);
-                hipLaunchKernelGGL(k_lu_assemble, dim3(nw), dim3(256), 0, s, n, a.Lstart, (const int32_t *)nullptr, a.Li, a.Lx, a.pinv, L->p,
-                                   L->i, L->x);
-                hipLaunchKernelGGL(k_lu_assemble, dim3(nw), dim3(256), 0, s, n, a.Ustart, (const int32_t *)nullptr, a.Ui, a.Ux,
-                                   (const int32_t *)nullptr, U->p, U->i, U->x);
-                if (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(pinv_host, a.pinv, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess)
-                    st = CSX_ERUNTIME;
-            }
-            if (st == CSX_OK) {
-                *hL = put(K_CSC, L);
-                *hU = put(K_CSC, U);
-                *done = 1;
-            } else {
-                free_csc(L);
-                free_csc(U);
-            }
+        CSX_LAUNCH_CHECK();
+        CSX_HIP(hipMemcpyAsync(hflags, a.flags, sizeof hflags, hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
+        if (hflags[0] != 0x7fffffff) return CSX_ENOTSPD;     // singular: the reference returns None (csparse.py:1423)
+        if (hflags[1]) {                                    // the strips were too small
+            if (cap < 0x7FFFFFF0ull) continue;
+            return CSX_EINVAL;
         }
-        dfree(a.Li);
-        dfree(a.Lx);
-        dfree(a.Ui);
-        dfree(a.Ux);
-        if (!again) return st;
+        // assemble in column order
+        std::unique_ptr<Csc> L(new Csc()), U(new Csc());
+        L->m = L->n = U->m = U->n = n;
+        int64_t lnz = 0, unz = 0;
+        CSX_TRY(dalloc(&L->p, (size_t)n + 1));
+        CSX_TRY(dalloc(&U->p, (size_t)n + 1));
+        const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
+        hipLaunchKernelGGL(k_lu_counts, dim3(nb), dim3(256), 0, s, n, a.Lstart, a.Lend, lcount);
+        hipLaunchKernelGGL(k_lu_counts, dim3(nb), dim3(256), 0, s, n, a.Ustart, a.Uend, ucount);
+        CSX_TRY(scan_exclusive_i32(lcount, L->p, n, &lnz));
+        CSX_TRY(scan_exclusive_i32(ucount, U->p, n, &unz));
+        L->nnz = (int32_t)lnz;
+        U->nnz = (int32_t)unz;
+        CSX_TRY(dalloc(&L->i, (size_t)lnz));
+        CSX_TRY(dalloc(&L->x, (size_t)lnz));
+        CSX_TRY(dalloc(&U->i, (size_t)unz));
+        CSX_TRY(dalloc(&U->x, (size_t)unz));
+        const unsigned nw = (unsigned)(((int64_t)n + 3) / 4);
+        hipLaunchKernelGGL(k_lu_assemble, dim3(nw), dim3(256), 0, s, n, a.Lstart, (const int32_t *)nullptr, a.Li, a.Lx, a.pinv, L->p,
+                           L->i, L->x);
+        hipLaunchKernelGGL(k_lu_assemble, dim3(nw), dim3(256), 0, s, n, a.Ustart, (const int32_t *)nullptr, a.Ui, a.Ux,
+                           (const int32_t *)nullptr, U->p, U->i, U->x);
+        CSX_LAUNCH_CHECK();
+        CSX_HIP(hipMemcpyAsync(pinv_host, a.pinv, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
+        *hL = put(K_CSC, L.release());
+        *hU = put(K_CSC, U.release());
+        *done = 1;
+        return CSX_OK;
     }
     return CSX_EINVAL;
 }

@@ -63,13 +63,6 @@ __global__ __launch_bounds__(64) void k_happly_level(const int32_t *__restrict__
 
 constexpr int32_t HAPPLY_MAX_LEVELS = 4096;   // beyond that (a chain of dependent reflections) one launch walks them all
 
-static int download_i32(std::vector<int32_t> &h, const int32_t *d, size_t count) {
-    h.resize(count);
-    if (count) CSX_HIP(hipMemcpyAsync(h.data(), d, count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx().stream));
-    CSX_HIP(hipStreamSynchronize(ctx().stream));
-    return CSX_OK;
-}
-
 // level[k] = 1 + the highest level among the earlier reflections that share a row with k (host, O(nnz V))
 static int house_levels(Csc *V) {
     if (V->house) return CSX_OK;
@@ -85,24 +78,19 @@ static int house_levels(Csc *V) {
         for (int32_t p = hp[(size_t)k]; p < hp[(size_t)k + 1]; p++) rowlev[(size_t)hi[(size_t)p]] = lv + 1;
         nlev = std::max(nlev, lv + 1);
     }
-    HouseLevels *H = new HouseLevels();
+    std::unique_ptr<HouseLevels> H(new HouseLevels());
     H->nlevels = nlev;
     H->ptr.assign((size_t)nlev + 1, 0);
     for (int32_t k = 0; k < V->n; k++) H->ptr[(size_t)level[(size_t)k] + 1]++;
     for (int32_t l = 0; l < nlev; l++) H->ptr[(size_t)l + 1] += H->ptr[(size_t)l];
     std::vector<int32_t> fill(H->ptr.begin(), H->ptr.end() - 1), cols((size_t)V->n);
     for (int32_t k = 0; k < V->n; k++) cols[(size_t)fill[(size_t)level[(size_t)k]]++] = k;
-    int st = dalloc(&H->cols, (size_t)std::max<int32_t>(V->n, 1));
-    if (st == CSX_OK && V->n > 0 &&
-        (hipMemcpyAsync(H->cols, cols.data(), (size_t)V->n * sizeof(int32_t), hipMemcpyHostToDevice, ctx().stream) != hipSuccess ||
-         hipStreamSynchronize(ctx().stream) != hipSuccess))
-        st = CSX_ERUNTIME;
-    if (st != CSX_OK) {
-        dfree(H->cols);
-        delete H;
-        return st;
+    CSX_TRY(H->cols.alloc((size_t)std::max<int32_t>(V->n, 1)));
+    if (V->n > 0) {
+        CSX_HIP(hipMemcpyAsync(H->cols, cols.data(), (size_t)V->n * sizeof(int32_t), hipMemcpyHostToDevice, ctx().stream));
+        CSX_HIP(hipStreamSynchronize(ctx().stream));
     }
-    V->house = H;
+    V->house = std::move(H);
     return CSX_OK;
 }
 
@@ -118,7 +106,7 @@ extern "C" int csx_happly(csx_handle_t hV, csx_handle_t hbeta, csx_handle_t hX, 
     if (nrhs == 0 || V->n == 0) return CSX_OK;
     hipStream_t s = ctx().stream;
     CSX_TRY(house_levels(V));
-    const HouseLevels *H = V->house;
+    const HouseLevels *H = V->house.get();
     if (H->nlevels > HAPPLY_MAX_LEVELS || H->nlevels == V->n) {   // nothing to run side by side: one launch
         hipLaunchKernelGGL(k_happly, dim3((unsigned)((nrhs + 63) / 64)), dim3(64), 0, s, V->n, V->p, V->i, V->x,
                            (const double *)b->d, (double *)x->d, nrhs, transpose);

@@ -66,33 +66,33 @@ struct SnStep {
 
 struct SnDir {
     std::vector<SnStep> steps;       // host
-    SnTask *tasks = nullptr;         // device
-    int32_t *comb = nullptr;         // device: lines with partial slots, by step
-    int32_t *narrow = nullptr;       // device: virtual supernode ids by step
-    int32_t *medium = nullptr;       // device
-    int32_t *wide = nullptr;         // device
-    int32_t *part_ptr = nullptr;     // device [n + 1]: partial slots of a row / column
-    int4 *tri4 = nullptr;            // device: (first column, width, first fragment, 0) of every virtual supernode, by step
+    DevBuf<SnTask> tasks;            // device
+    DevBuf<int32_t> comb;            // device: lines with partial slots, by step
+    DevBuf<int32_t> narrow;          // device: virtual supernode ids by step
+    DevBuf<int32_t> medium;          // device
+    DevBuf<int32_t> wide;            // device
+    DevBuf<int32_t> part_ptr;        // device [n + 1]: partial slots of a row / column
+    DevBuf<int4> tri4;               // device: (first column, width, first fragment, 0) of every virtual supernode, by step
     std::vector<int4> tri_h;         // the same on the host: a step of one triangle passes its entry with the launch
     int32_t nslots = 0;
 };
 
 struct SnPlan {
     int32_t n = 0, nsn = 0, max_w = 0, nleaf = 0, nleafcols = 0;
-    int32_t *vs_a = nullptr, *vs_w = nullptr;   // device: first column and width of every virtual supernode (chunk)
+    DevBuf<int32_t> vs_a, vs_w;                 // device: first column and width of every virtual supernode (chunk)
     // leaf subtrees: columns by subtree (ascending inside), packed forward / backward programs by position in leaf_cols
-    int32_t *leaf_ptr = nullptr, *leaf_cols = nullptr;
-    int32_t *lf_ptr = nullptr, *lf_idx = nullptr, *lb_ptr = nullptr, *lb_idx = nullptr;
-    double *lf_val = nullptr, *lb_val = nullptr, *ldiag = nullptr;
-    SnTask *leaf_tasks = nullptr;               // backward: the leaf columns' rows outside their subtrees, in pieces
+    DevBuf<int32_t> leaf_ptr, leaf_cols;
+    DevBuf<int32_t> lf_ptr, lf_idx, lb_ptr, lb_idx;
+    DevBuf<double> lf_val, lb_val, ldiag;
+    DevBuf<SnTask> leaf_tasks;                  // backward: the leaf columns' rows outside their subtrees, in pieces
     int32_t nleaftasks = 0, nleafslots = 0;
-    int32_t *lslot_ptr = nullptr;               // [nleafcols + 1] partial slots of a leaf column (after the backward plan's slots)
+    DevBuf<int32_t> lslot_ptr;                  // [nleafcols + 1] partial slots of a leaf column (after the backward plan's slots)
     SnDir fwd, bwd;
-    double *partial = nullptr;
+    DevBuf<double> partial;
     int64_t partial_len = 0;
-    int4 *leaf4 = nullptr;                      // (first position in leaf_cols, columns, first fragment, 0) of every leaf subtree
+    DevBuf<int4> leaf4;                         // (first position in leaf_cols, columns, first fragment, 0) of every leaf subtree
     int64_t frag_toff = 0;                      // the transposed tiles (backward sweep) lie this many doubles behind the forward ones
-    double *frags = nullptr;                    // matrix-core fragments of every virtual supernode's and leaf subtree's triangle
+    DevBuf<double> frags;                       // matrix-core fragments of every virtual supernode's and leaf subtree's triangle
     bool mfma = false;                          // fragments built and every block inverse tame: k_sn_mfma solves the triangles
     double growth = 0.0;                        // the guard's measure (k_sn_frags)
     int chunk = 64;                             // columns per chunk of a wide supernode / per relaxed run (128: matrix cores only)
@@ -100,33 +100,9 @@ struct SnPlan {
     int64_t generation = 0;                     // counts the moves of `partial` (a captured solve holds its address)
 };
 
-void free_snplan(SnPlan *P) {
-    if (!P) return;
-    for (void *p : {(void *)P->vs_a, (void *)P->vs_w, (void *)P->leaf_ptr, (void *)P->leaf_cols, (void *)P->lf_ptr, (void *)P->lf_idx,
-                    (void *)P->lb_ptr, (void *)P->lb_idx, (void *)P->lf_val, (void *)P->lb_val, (void *)P->ldiag, (void *)P->leaf_tasks,
-                    (void *)P->lslot_ptr, (void *)P->partial, (void *)P->frags, (void *)P->leaf4})
-        dfree(p);
-    for (SnDir *d : {&P->fwd, &P->bwd}) {
-        dfree(d->tasks);
-        dfree(d->comb);
-        dfree(d->narrow);
-        dfree(d->medium);
-        dfree(d->wide);
-        dfree(d->part_ptr);
-        dfree(d->tri4);
-    }
-    delete P;
-}
+void destroy(SnPlan *P) { delete P; }
 
 namespace {
-
-template <class T>
-int up(T **d, const std::vector<T> &h) {
-    CSX_TRY(dalloc(d, std::max<size_t>(h.size(), 1)));
-    if (!h.empty())
-        CSX_HIP(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
-    return CSX_OK;
-}
 
 // sum over q in [b, e) of val[q] * X[idx[q], r]: lane = right-hand side, a term's index and value handed round by
 // v_readlane, sixteen row loads of X in flight ahead of the multiply-adds
@@ -992,7 +968,7 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
     // (each step is two or three dependent launches of ~10 us: a chain of a thousand narrow supernodes -- bcsstk16 in natural
     // order: ~1 500 steps for 4 810 column levels -- took 38 ms this way against 3.5 ms for the chain walkers)
     if (est_steps * 8 > col_levels) return CSX_OK;
-    SnPlan *P = new SnPlan();
+    std::unique_ptr<SnPlan> P(new SnPlan());
     P->n = n;
     P->chunk = chunk;
     P->nsn = nsn;
@@ -1000,7 +976,6 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
     P->nleaf = nleaf;
     P->nleafcols = (int32_t)leaf_cols.size();
     hipStream_t s = ctx().stream;
-    int st = CSX_OK;
     {   // is L shaped like a Cholesky factor with these supernodes and subtrees?
         std::vector<int32_t> snc((size_t)n), fl((size_t)n), bl((size_t)n);
         for (int32_t j = 0; j < n; j++) {
@@ -1009,29 +984,21 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
             fl[(size_t)j] = S >= 0 ? height[(size_t)S] : -1;
             bl[(size_t)j] = S >= 0 ? depth[(size_t)S] : 0x7fffffff;
         }
-        DevScope tmp;
-        int32_t *d_sn = nullptr, *d_j = nullptr, *d_f = nullptr, *d_b = nullptr;
-        int *d_bad = nullptr, h_bad = 0;
-        const std::pair<int32_t **, std::vector<int32_t> *> ups[] = {{&d_sn, &snc}, {&d_j, &joins}, {&d_f, &fl}, {&d_b, &bl}};
-        for (const auto &pr : ups) {
-            if (st == CSX_OK) st = tmp.alloc(pr.first, (size_t)n);
-            if (st == CSX_OK && hipMemcpyAsync(*pr.first, pr.second->data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
-        if (st == CSX_OK) st = tmp.alloc(&d_bad, 1);
-        if (st == CSX_OK && hipMemsetAsync(d_bad, 0, sizeof(int), s) != hipSuccess) st = CSX_ERUNTIME;
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_sn_verify, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, L->i, d_sn, d_j, d_f, d_b,
-                               d_bad);
-            if (hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
+        DevBuf<int32_t> d_sn, d_j, d_f, d_b;
+        DevBuf<int> d_bad;
+        int h_bad = 0;
+        CSX_TRY(upload(d_sn, snc));
+        CSX_TRY(upload(d_j, joins.data(), (size_t)n));
+        CSX_TRY(upload(d_f, fl));
+        CSX_TRY(upload(d_b, bl));
+        CSX_TRY(d_bad.alloc(1));
+        CSX_HIP(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_sn_verify, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, L->i, d_sn, d_j, d_f, d_b,
+                           d_bad);
+        CSX_HIP(hipMemcpyAsync(&h_bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
         if (say) std::fprintf(stderr, "sn_build: verify %s\n", h_bad ? "FAILED" : "ok");
-        if (st != CSX_OK || h_bad) {            // not such a factor: the level-scheduled plans stay in charge
-            free_snplan(P);
-            return st;
-        }
+        if (h_bad) return CSX_OK;               // not such a factor: the level-scheduled plans stay in charge
     }
     // how much of every row / column lies inside its supernode
     std::vector<int32_t> fin_h((size_t)n, 0), bin_h((size_t)n, 0);
@@ -1049,26 +1016,16 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
                 sa[(size_t)(first[(size_t)S] + v)] = first[(size_t)S];
                 se[(size_t)(first[(size_t)S] + v)] = first[(size_t)S] + width[(size_t)S];
             }
-        DevScope tmp;
-        int32_t *d_a = nullptr, *d_e = nullptr, *d_f = nullptr, *d_b = nullptr;
-        for (int32_t **a : {&d_a, &d_e, &d_f, &d_b})
-            if (st == CSX_OK) st = tmp.alloc(a, (size_t)n);
-        if (st == CSX_OK &&
-            (hipMemcpyAsync(d_a, sa.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-             hipMemcpyAsync(d_e, se.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess))
-            st = CSX_ERUNTIME;
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_sn_incount, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, d_a, d_e, Gp, Gi, L->p, L->i, d_f,
-                               d_b);
-            if (hipMemcpyAsync(fin_h.data(), d_f, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(bin_h.data(), d_b, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
-        if (st != CSX_OK) {
-            free_snplan(P);
-            return st;
-        }
+        DevBuf<int32_t> d_a, d_e, d_f, d_b;
+        CSX_TRY(upload(d_a, sa));
+        CSX_TRY(upload(d_e, se));
+        CSX_TRY(d_f.alloc((size_t)n));
+        CSX_TRY(d_b.alloc((size_t)n));
+        hipLaunchKernelGGL(k_sn_incount, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, d_a, d_e, Gp, Gi, L->p, L->i, d_f,
+                           d_b);
+        CSX_HIP(hipMemcpyAsync(fin_h.data(), d_f, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipMemcpyAsync(bin_h.data(), d_b, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
     }
     // partial slots of the backward schedule (a column whose rows below its supernode are cut into pieces): counted here
     // because the leaf columns' slots are numbered behind them
@@ -1079,50 +1036,41 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
             if (c > SN_WHOLE) bwd_slots += (c + SN_SEG - 1) / SN_SEG;
         }
     // ---- leaf subtrees: packed programs ----
-    st = up(&P->leaf_ptr, leaf_ptr);
-    if (st == CSX_OK) st = up(&P->leaf_cols, leaf_cols);
-    if (st == CSX_OK && P->nleafcols > 0) {
-        DevScope tmp;
-        int32_t *d_sub = nullptr, *d_local = nullptr, *lenf = nullptr, *lenb = nullptr, *split = nullptr, *ntask = nullptr,
-                *nslot = nullptr, *task_ptr = nullptr;
+    CSX_TRY(upload(P->leaf_ptr, leaf_ptr));
+    CSX_TRY(upload(P->leaf_cols, leaf_cols));
+    if (P->nleafcols > 0) {
+        DevBuf<int32_t> d_sub, d_local, lenf, lenb, split, ntask, nslot, task_ptr;
         const int32_t nc = P->nleafcols;
-        st = tmp.alloc(&d_sub, (size_t)n);
-        if (st == CSX_OK) st = tmp.alloc(&d_local, (size_t)n);
-        for (int32_t **a : {&lenf, &lenb, &split, &ntask, &nslot, &task_ptr})
-            if (st == CSX_OK) st = tmp.alloc(a, (size_t)nc + 1);
-        if (st == CSX_OK) st = dalloc(&P->lf_ptr, (size_t)nc + 1);
-        if (st == CSX_OK) st = dalloc(&P->lb_ptr, (size_t)nc + 1);
-        if (st == CSX_OK) st = dalloc(&P->lslot_ptr, (size_t)nc + 1);
-        if (st == CSX_OK) st = dalloc(&P->ldiag, (size_t)nc);
-        if (st == CSX_OK &&
-            (hipMemcpyAsync(d_sub, sub_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-             hipMemcpyAsync(d_local, local_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess))
-            st = CSX_ERUNTIME;
+        CSX_TRY(d_sub.alloc((size_t)n));
+        CSX_TRY(d_local.alloc((size_t)n));
+        for (DevBuf<int32_t> *a : {&lenf, &lenb, &split, &ntask, &nslot, &task_ptr}) CSX_TRY(a->alloc((size_t)nc + 1));
+        CSX_TRY(P->lf_ptr.alloc((size_t)nc + 1));
+        CSX_TRY(P->lb_ptr.alloc((size_t)nc + 1));
+        CSX_TRY(P->lslot_ptr.alloc((size_t)nc + 1));
+        CSX_TRY(P->ldiag.alloc((size_t)nc));
+        CSX_HIP(hipMemcpyAsync(d_sub, sub_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        CSX_HIP(hipMemcpyAsync(d_local, local_of.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         int64_t ftot = 0, btot = 0, ttot = 0, stot = 0;
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_sn_leaf_meta, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, nc, P->leaf_cols, d_sub, Gp, L->p,
-                               L->i, L->x, lenf, lenb, split, ntask, nslot, P->ldiag);
-            st = scan_exclusive_i32(lenf, P->lf_ptr, nc, &ftot);
-            if (st == CSX_OK) st = scan_exclusive_i32(lenb, P->lb_ptr, nc, &btot);
-            if (st == CSX_OK) st = scan_exclusive_i32(ntask, task_ptr, nc, &ttot);
-            if (st == CSX_OK) st = scan_exclusive_i32(nslot, P->lslot_ptr, nc, &stot);
-        }
+        hipLaunchKernelGGL(k_sn_leaf_meta, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, nc, P->leaf_cols, d_sub, Gp, L->p,
+                           L->i, L->x, lenf, lenb, split, ntask, nslot, P->ldiag);
+        CSX_TRY(scan_exclusive_i32(lenf, P->lf_ptr, nc, &ftot));
+        CSX_TRY(scan_exclusive_i32(lenb, P->lb_ptr, nc, &btot));
+        CSX_TRY(scan_exclusive_i32(ntask, task_ptr, nc, &ttot));
+        CSX_TRY(scan_exclusive_i32(nslot, P->lslot_ptr, nc, &stot));
         P->nleaftasks = (int32_t)ttot;
         P->nleafslots = (int32_t)stot;
-        if (st == CSX_OK) st = dalloc(&P->leaf_tasks, (size_t)ttot + 1);
+        CSX_TRY(P->leaf_tasks.alloc((size_t)ttot + 1));
         // the leaf columns' partial slots come behind the backward schedule's own (bwd_slots: counted above)
-        if (st == CSX_OK)
-            hipLaunchKernelGGL(k_sn_leaf_tasks, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, nc, P->leaf_cols, L->p, split,
-                               task_ptr, P->lslot_ptr, bwd_slots, P->leaf_tasks);
-        if (st == CSX_OK) st = dalloc(&P->lf_idx, (size_t)ftot + 64);
-        if (st == CSX_OK) st = dalloc(&P->lf_val, (size_t)ftot + 64);
-        if (st == CSX_OK) st = dalloc(&P->lb_idx, (size_t)btot + 64);
-        if (st == CSX_OK) st = dalloc(&P->lb_val, (size_t)btot + 64);
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_sn_leaf_fill, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, s, nc, P->leaf_cols, d_local, Gp, Gi,
-                               Gx, L->p, L->i, L->x, P->lf_ptr, P->lf_idx, P->lf_val, P->lb_ptr, P->lb_idx, P->lb_val);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-        }
+        hipLaunchKernelGGL(k_sn_leaf_tasks, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, nc, P->leaf_cols, L->p, split,
+                           task_ptr, P->lslot_ptr, bwd_slots, P->leaf_tasks);
+        CSX_TRY(P->lf_idx.alloc((size_t)ftot + 64));
+        CSX_TRY(P->lf_val.alloc((size_t)ftot + 64));
+        CSX_TRY(P->lb_idx.alloc((size_t)btot + 64));
+        CSX_TRY(P->lb_val.alloc((size_t)btot + 64));
+        hipLaunchKernelGGL(k_sn_leaf_fill, dim3((unsigned)(((int64_t)nc + 3) / 4)), dim3(256), 0, s, nc, P->leaf_cols, d_local, Gp, Gi,
+                           Gx, L->p, L->i, L->x, P->lf_ptr, P->lf_idx, P->lf_val, P->lb_ptr, P->lb_idx, P->lb_val);
+        CSX_LAUNCH_CHECK();
+        CSX_HIP(hipStreamSynchronize(s));
     }
     // ---- virtual supernodes: every supernode cut into chunks of `chunk` columns ----
     std::vector<int32_t> vs_a, vs_w, vs0((size_t)nsn + 1, 0);
@@ -1136,8 +1084,8 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
     vs0[(size_t)nsn] = (int32_t)vs_a.size();
     std::vector<int32_t> vs_f(vs_a.size() + 1, 0);      // first fragment (64 doubles each) of every virtual supernode
     for (size_t c = 0; c < vs_a.size(); c++) vs_f[c + 1] = vs_f[c] + sn_tiles((vs_w[c] + 15) / 16) * 4;
-    if (st == CSX_OK) st = up(&P->vs_a, vs_a);
-    if (st == CSX_OK) st = up(&P->vs_w, vs_w);
+    CSX_TRY(upload(P->vs_a, vs_a));
+    CSX_TRY(upload(P->vs_w, vs_w));
     auto build = [&](SnDir &D, const std::vector<int32_t> &level, bool forward) -> int {
         int32_t Lv = 0;
         for (int32_t S = 0; S < nsn; S++) Lv = std::max(Lv, level[(size_t)S] + 1);
@@ -1222,25 +1170,25 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
                 D.steps.push_back(stp);
             }
         }
-        CSX_TRY(up(&D.tasks, tasks));
-        CSX_TRY(up(&D.comb, comb));
-        CSX_TRY(up(&D.narrow, narrow));
-        CSX_TRY(up(&D.medium, medium));
-        CSX_TRY(up(&D.wide, wide));
-        CSX_TRY(up(&D.part_ptr, part));
-        CSX_TRY(up(&D.tri4, tri));
+        CSX_TRY(upload(D.tasks, tasks));
+        CSX_TRY(upload(D.comb, comb));
+        CSX_TRY(upload(D.narrow, narrow));
+        CSX_TRY(upload(D.medium, medium));
+        CSX_TRY(upload(D.wide, wide));
+        CSX_TRY(upload(D.part_ptr, part));
+        CSX_TRY(upload(D.tri4, tri));
         D.tri_h = std::move(tri);
         return CSX_OK;
     };
-    if (st == CSX_OK) st = build(P->fwd, height, true);
-    if (st == CSX_OK) st = build(P->bwd, depth, false);
-    if (st == CSX_OK && P->bwd.nslots != bwd_slots) {
+    CSX_TRY(build(P->fwd, height, true));
+    CSX_TRY(build(P->bwd, depth, false));
+    if (P->bwd.nslots != bwd_slots) {
         set_error("sn_build: slot count mismatch (%d / %d)", P->bwd.nslots, bwd_slots);
-        st = CSX_ERUNTIME;
+        return CSX_ERUNTIME;
     }
     // ---- matrix-core fragments of every triangle (every virtual supernode is in exactly one forward step) ----
     double growth = 0.0;
-    if (st == CSX_OK && ctx().opt.tri_supernodes == 1) {
+    if (ctx().opt.tri_supernodes == 1) {
         const size_t nv = vs_a.size();
         std::vector<int4> leaf4((size_t)nleaf);
         int64_t at = vs_f.back();
@@ -1253,14 +1201,14 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
         if (nfrag * 1024 <= free_b / 4 && at < 0x7fffffff) {
-            DevScope tmp;
-            unsigned long long *d_cond = nullptr, h_cond = 0;
-            st = dalloc(&P->frags, 2 * nfrag * 64 + 64);
+            DevBuf<unsigned long long> d_cond;
+            unsigned long long h_cond = 0;
+            CSX_TRY(P->frags.alloc(2 * nfrag * 64 + 64));
             P->frag_toff = (int64_t)nfrag * 64;
-            if (st == CSX_OK) st = up(&P->leaf4, leaf4);
-            if (st == CSX_OK) st = tmp.alloc(&d_cond, 1);
-            if (st == CSX_OK && hipMemsetAsync(d_cond, 0, sizeof(unsigned long long), s) != hipSuccess) st = CSX_ERUNTIME;
-            if (st == CSX_OK) {
+            CSX_TRY(upload(P->leaf4, leaf4));
+            CSX_TRY(d_cond.alloc(1));
+            CSX_HIP(hipMemsetAsync(d_cond, 0, sizeof(unsigned long long), s));
+            {
                 static bool frag_lds_set = false;
                 if (!frag_lds_set) {
                     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sn_frags<false, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1282,39 +1230,30 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
                 if (nleaf > 0)
                     hipLaunchKernelGGL((k_sn_frags<true, 64>), dim3((unsigned)nleaf), dim3(64), sn_frags_lds<64>(), s, P->leaf4, nleaf, L->p,
                                        L->i, L->x, P->lb_ptr, P->lb_idx, P->lb_val, P->ldiag, P->frags, P->frag_toff, d_cond);
-                if (hipMemcpyAsync(&h_cond, d_cond, sizeof(h_cond), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess)
-                    st = CSX_ERUNTIME;
+                CSX_HIP(hipMemcpyAsync(&h_cond, d_cond, sizeof(h_cond), hipMemcpyDeviceToHost, s));
+                CSX_HIP(hipStreamSynchronize(s));
             }
-            if (st == CSX_OK) {
+            {
                 std::memcpy(&growth, &h_cond, sizeof(double));
                 // the largest || |W_ii| |L_ii| ||_inf over all diagonal blocks (k_sn_frags): past 1e3 -- an error of
                 // ~1e-13 per block -- the triangles stay with substitution (k_sn_tri); a zero pivot reports infinity
                 P->growth = growth;
                 P->mfma = growth <= 1e3;
-                if (!P->mfma) {
-                    dfree(P->frags);
-                    P->frags = nullptr;
-                }
+                if (!P->mfma) P->frags.reset();
             }
         }
     }
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    if (st == CSX_OK && (P->has_relaxed || P->chunk > 64) && !P->mfma) {
+    CSX_HIP(hipStreamSynchronize(s));
+    if ((P->has_relaxed || P->chunk > 64) && !P->mfma) {
         // relaxed supernodes exist only as matrix-core fragments (the substitution kernel reads dense trapezoids): without
         // them -- a diagonal block past the guard, no memory for the fragments -- the level-scheduled plans keep the factor
         if (say) std::fprintf(stderr, "sn_build: relaxed supernodes but no matrix-core triangles (%.3g): no supernodal plan\n", growth);
-        free_snplan(P);
         return CSX_OK;
-    }
-    if (st != CSX_OK) {
-        free_snplan(P);
-        return st;
     }
     if (say)
         std::fprintf(stderr, "sn_build: %d forward steps, %d backward steps, triangles %s (largest || |W_ii| |L_ii| || = %.3g)\n", (int)P->fwd.steps.size(),
                      (int)P->bwd.steps.size(), P->mfma ? "on the matrix cores" : "by substitution", growth);
-    *out = P;
+    *out = P.release();
     return CSX_OK;
 }
 
@@ -1353,10 +1292,8 @@ int64_t sn_generation(const SnPlan *P) { return P->generation; }
 int sn_prepare(SnPlan *P, int32_t nrhs) {
     const int64_t need = (int64_t)std::max(P->fwd.nslots, P->bwd.nslots + P->nleafslots) * nrhs;
     if (P->partial_len < need) {
-        dfree(P->partial);
-        P->partial = nullptr;
         P->partial_len = 0;
-        CSX_TRY(dalloc(&P->partial, (size_t)need));
+        CSX_TRY(P->partial.alloc((size_t)need));   // (the old block goes back first)
         P->partial_len = need;
         P->generation++;
     }

@@ -90,16 +90,13 @@ int scan_exclusive_i32(const int32_t *in, int32_t *out, int64_t n, int64_t *tota
         return CSX_OK;
     }
     int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    int32_t *sums = nullptr;
+    DevBuf<int32_t> sums;   // (freed with no wait: the pool's blocks are used on the context's stream only, whoever gets this one
+                            // next queues behind the scan)
     if (nb > 1) {
-        CSX_TRY(dalloc(&sums, (size_t)nb + 1));
+        CSX_TRY(sums.alloc((size_t)nb + 1));
         hipLaunchKernelGGL(k_scan_block_sums, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, n, sums);
         CSX_LAUNCH_CHECK();
-        int st = scan_exclusive_i32(sums, sums, nb, nullptr);
-        if (st != CSX_OK) {
-            dfree(sums);
-            return st;
-        }
+        CSX_TRY(scan_exclusive_i32(sums, sums, nb, nullptr));
     }
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, in, out, n, sums);
     CSX_LAUNCH_CHECK();
@@ -109,7 +106,6 @@ int scan_exclusive_i32(const int32_t *in, int32_t *out, int64_t n, int64_t *tota
         CSX_HIP(hipStreamSynchronize(s));
         *total_host = t;
     }
-    dfree(sums);   // (no wait: the pool's blocks are used on the context's stream only, whoever gets this one next queues behind the scan)
     return CSX_OK;
 }
 
@@ -651,23 +647,16 @@ int suffix_min_i32(int32_t *p, int64_t n) {
     if (n <= 0) return CSX_OK;
     hipStream_t s = ctx().stream;
     const int64_t nb = (n + SM_TILE - 1) / SM_TILE;
-    int32_t *bm = nullptr;
+    DevBuf<int32_t> bm;
     if (nb > 1) {
-        CSX_TRY(dalloc(&bm, (size_t)nb));
+        CSX_TRY(bm.alloc((size_t)nb));
         hipLaunchKernelGGL(k_sufmin_block, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, p, n, bm);
-        const int st = suffix_min_i32(bm, nb);
-        if (st != CSX_OK) {
-            dfree(bm);
-            return st;
-        }
+        CSX_TRY(suffix_min_i32(bm, nb));
     }
     hipLaunchKernelGGL(k_sufmin_apply, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, p, n, bm, nb);
-    int st = hipGetLastError() == hipSuccess ? CSX_OK : CSX_ERUNTIME;
-    if (bm) {
-        if (hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;  // bm is freed below
-        dfree(bm);
-    }
-    return st;
+    CSX_LAUNCH_CHECK();
+    if (bm) CSX_HIP(hipStreamSynchronize(s));  // bm is freed on return
+    return CSX_OK;
 }
 
 __global__ void k_ptr_init(int32_t *ptr, int32_t nkeys, int32_t count) {
@@ -703,34 +692,33 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
     const bool k16 = xp != nullptr && packed && passes == 3 && optr != nullptr && out_key == nullptr && bits - w0 <= 16 &&
                      (uint64_t)ex->expand_n <= (1ull << (32 - w0)) && ctx().opt.sort_short_keys;
 
-    DevScope scope;
-    int32_t *hist = nullptr, *part = nullptr;
-    uint32_t *desc = nullptr;
-    uint32_t *tk[2] = {nullptr, nullptr}, *ta[2] = {nullptr, nullptr};
-    double *tv[2] = {nullptr, nullptr};
-    Pay *tp[2] = {nullptr, nullptr};
-    int st = scope.alloc(&hist, (size_t)RS_BINS * nblocks);
-    if (st == CSX_OK) st = scope.alloc(&part, (size_t)RS_BINS * (nchunks + 1));
+    DevBuf<int32_t> hist, part;
+    DevBuf<uint32_t> desc;
+    DevBuf<uint32_t> tk[2], ta[2];
+    DevBuf<double> tv[2];
+    DevBuf<Pay> tp[2];
+    DevBuf<uint16_t> tk16[2];
+    CSX_TRY(hist.alloc((size_t)RS_BINS * nblocks));
+    CSX_TRY(part.alloc((size_t)RS_BINS * (nchunks + 1)));
     int32_t *const dbase = part + (size_t)RS_BINS * nchunks;
-    if (st == CSX_OK && xp) st = scope.alloc(&desc, (size_t)nblocks * RS_DESC_WORDS);
+    if (xp) CSX_TRY(desc.alloc((size_t)nblocks * RS_DESC_WORDS));
     const int ntmp = passes > 2 ? 2 : passes - 1;
-    uint16_t *tk16[2] = {nullptr, nullptr};
-    for (int t = 0; t < ntmp && st == CSX_OK; t++) {
-        if (k16) st = scope.alloc(&tk16[t], (size_t)count + 8);
-        else st = scope.alloc(&tk[t], (size_t)count);
+    for (int t = 0; t < ntmp; t++) {
+        if (k16) CSX_TRY(tk16[t].alloc((size_t)count + 8));
+        else CSX_TRY(tk[t].alloc((size_t)count));
         if (packed) {
-            if (st == CSX_OK) st = scope.alloc(&tp[t], (size_t)count);
+            CSX_TRY(tp[t].alloc((size_t)count));
         } else {
-            if (st == CSX_OK && has_a) st = scope.alloc(&ta[t], (size_t)count);
-            if (st == CSX_OK && has_v) st = scope.alloc(&tv[t], (size_t)count);
+            if (has_a) CSX_TRY(ta[t].alloc((size_t)count));
+            if (has_v) CSX_TRY(tv[t].alloc((size_t)count));
         }
     }
-    if (st == CSX_OK && xp) {
+    if (xp) {
         hipLaunchKernelGGL(k_rs_tiledesc_head, dim3((nblocks + 255) / 256), dim3(256), 0, s, xp, ex->expand_n, count, nblocks,
                            desc);
         hipLaunchKernelGGL(k_rs_tiledesc_starts, dim3((unsigned)(((int64_t)ex->expand_n + 255) / 256)), dim3(256), 0, s, xp,
                            ex->expand_n, count, desc);
-        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+        CSX_LAUNCH_CHECK();
     }
     RsArgs g{};
     g.key = key;
@@ -743,7 +731,7 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
     g.flat = ablation_env("CSX_SORT_FLAT") ? 1 : 0;
     bool in_aos = false;
     int shift = 0;
-    for (int ps = 0; ps < passes && st == CSX_OK; ps++) {
+    for (int ps = 0; ps < passes; ps++) {
         const bool last = ps == passes - 1;
         const int width = bits / passes + (ps < bits % passes ? 1 : 0);   // digits as even as the key allows
         const bool out_aos = packed && !last;
@@ -773,7 +761,7 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
         else if (has_a) launch_scatter<true, false>(false, false, dim3(nblocks), s, g);
         else if (has_v) launch_scatter<false, true>(false, false, dim3(nblocks), s, g);
         else launch_scatter<false, false>(false, false, dim3(nblocks), s, g);
-        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+        CSX_LAUNCH_CHECK();
         g.key = g.okey;
         g.key16 = g.okey16;
         g.a = g.oa;
@@ -783,10 +771,9 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
         in_aos = out_aos;
         shift += width;
     }
-    if (st == CSX_OK && optr) st = suffix_min_i32(optr, (int64_t)ex->nkeys + 1);
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;   // the temporaries go back now
-    if (st == CSX_ERUNTIME) set_error("stable_sort_by_key: HIP failure (%s)", hipGetErrorString(hipGetLastError()));
-    return st;
+    if (optr) CSX_TRY(suffix_min_i32(optr, (int64_t)ex->nkeys + 1));
+    CSX_HIP(hipStreamSynchronize(s));   // the temporaries go back now
+    return CSX_OK;
 }
 
 int stable_sort_by_key(const uint32_t *key, const uint32_t *a, const double *v, int64_t count, uint32_t key_limit,

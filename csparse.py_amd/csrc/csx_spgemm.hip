@@ -1210,11 +1210,12 @@ static int values_in_reference_order(const Csc *A, const Csc *B, Csc *C) {
     if (!C->x || C->nnz == 0) return CSX_OK;
     hipStream_t s = ctx().stream;
     const int32_t n = C->n, m = C->m;
-    DevScope tmp;
-    int *flag = nullptr, h[4] = {0, 0, 0, 0};
-    uint8_t *dup = nullptr;
-    CSX_TRY(tmp.alloc(&flag, 4));
-    CSX_TRY(tmp.alloc(&dup, (size_t)A->n + 1));
+    DevBuf<int> flag;
+    int h[4] = {0, 0, 0, 0};
+    DevBuf<uint8_t> dup;
+    DevBuf<int32_t> gmap;
+    CSX_TRY(flag.alloc(4));
+    CSX_TRY(dup.alloc((size_t)A->n + 1));
     CSX_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(int), s));
     hipLaunchKernelGGL(k_sg_count_classes, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, C->p, flag);
     CSX_HIP(hipMemcpyAsync(h, flag, sizeof h, hipMemcpyDeviceToHost, s));
@@ -1235,8 +1236,7 @@ static int values_in_reference_order(const Csc *A, const Csc *B, Csc *C) {
 #undef CSX_ORD
     if (h[3]) {
         const int64_t waves = std::min<int64_t>(n, 128);
-        int32_t *gmap = nullptr;
-        CSX_TRY(tmp.alloc(&gmap, (size_t)waves * (size_t)m));
+        CSX_TRY(gmap.alloc((size_t)waves * (size_t)m));
         hipLaunchKernelGGL(k_sg_values_ordered<true>, dim3((unsigned)waves), dim3(64), 0, s, n, m, A->p, A->i, A->x, B->p, B->i, B->x,
                            C->p, C->i, C->x, gmap);
     }
@@ -1260,122 +1260,95 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
         if (values) CSX_TRY(dalloc(&C->x, 0));
         return CSX_OK;
     }
-    uint32_t *bin = nullptr, *colid = nullptr, *sbin = nullptr, *scol = nullptr, *g_tmin = nullptr;
-    int32_t *bin_ptr_d = nullptr, *count = nullptr, *hprod = nullptr, *toff = nullptr, *tmp_i = nullptr;
-    int4 *info = nullptr;
-    double *g_val = nullptr, *tmp_x = nullptr;
-    unsigned long long *too_big = nullptr;  // [0] columns with >= 2^32 products, [1] products in hash-bin columns
-    int st = dalloc(&bin, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&colid, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&sbin, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&scol, (size_t)n);
-    if (st == CSX_OK) st = dalloc(&bin_ptr_d, SG_NBINS + 1);
-    if (st == CSX_OK) st = dalloc(&count, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&hprod, (size_t)n + 1);
-    if (st == CSX_OK) st = dalloc(&too_big, 2);
+    DevBuf<uint32_t> bin, colid, sbin, scol, g_tmin;
+    DevBuf<int32_t> bin_ptr_d, count, hprod, toff, tmp_i;
+    DevBuf<int4> info;
+    DevBuf<double> g_val, tmp_x;
+    DevBuf<unsigned long long> too_big;  // [0] columns with >= 2^32 products, [1] products in hash-bin columns
+    CSX_TRY(bin.alloc((size_t)n));
+    CSX_TRY(colid.alloc((size_t)n));
+    CSX_TRY(sbin.alloc((size_t)n));
+    CSX_TRY(scol.alloc((size_t)n));
+    CSX_TRY(bin_ptr_d.alloc(SG_NBINS + 1));
+    CSX_TRY(count.alloc((size_t)n + 1));
+    CSX_TRY(hprod.alloc((size_t)n + 1));
+    CSX_TRY(too_big.alloc(2));
     int32_t bin_ptr[SG_NBINS + 1] = {0};
     unsigned long long big[2] = {0, 0};
-    if (st == CSX_OK) {
-        (void)hipMemsetAsync(too_big, 0, 2 * sizeof(unsigned long long), s);
-        (void)hipMemsetAsync(count, 0, ((size_t)n + 1) * sizeof(int32_t), s);
-        hipLaunchKernelGGL(k_sg_products, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, B->p, B->i, m,
-                           bin, colid, hprod, too_big);
-        hipLaunchKernelGGL(k_sum_i32, dim3(512), dim3(256), 0, s, hprod, (int64_t)n, too_big + 1);
-        st = stable_sort_by_key(bin, colid, nullptr, n, SG_NBINS, sbin, scol, nullptr);
-    }
-    if (st == CSX_OK) st = boundaries_from_sorted(sbin, n, SG_NBINS, bin_ptr_d);
-    if (st == CSX_OK) {
-        if (hipMemcpyAsync(bin_ptr, bin_ptr_d, (SG_NBINS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipMemcpyAsync(big, too_big, sizeof big, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess)
-            st = CSX_ERUNTIME;
-    }
-    if (st == CSX_OK && big[0]) st = CSX_EINVAL;  // a column with >= 2^32 products
+    (void)hipMemsetAsync(too_big, 0, 2 * sizeof(unsigned long long), s);
+    (void)hipMemsetAsync(count, 0, ((size_t)n + 1) * sizeof(int32_t), s);
+    hipLaunchKernelGGL(k_sg_products, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, B->p, B->i, m,
+                       bin, colid, hprod, too_big);
+    hipLaunchKernelGGL(k_sum_i32, dim3(512), dim3(256), 0, s, hprod, (int64_t)n, too_big + 1);
+    CSX_TRY(stable_sort_by_key(bin, colid, nullptr, n, SG_NBINS, sbin, scol, nullptr));
+    CSX_TRY(boundaries_from_sorted(sbin, n, SG_NBINS, bin_ptr_d));
+    CSX_HIP(hipMemcpyAsync(bin_ptr, bin_ptr_d, (SG_NBINS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipMemcpyAsync(big, too_big, sizeof big, hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    if (big[0]) return CSX_EINVAL;  // a column with >= 2^32 products
     // one-pass path for the hash bins when its product-order buffer (12 B per product) is affordable
     const int32_t hash_lo = bin_ptr[SG_BIN_HASH0], nhash = bin_ptr[SG_BIN_NARROW0 + SG_NARROW_BINS] - hash_lo;
     bool onepass = false;
-    if (st == CSX_OK && nhash > 0 && big[1] < 0x7FFFFFF0ull && ctx().opt.spgemm_one_pass) {
+    if (nhash > 0 && big[1] < 0x7FFFFFF0ull && ctx().opt.spgemm_one_pass) {
         size_t free_b = 0, total_b = 0;
         const size_t need = (size_t)big[1] * (values ? 12 : 4);
         size_t idle_b = 0;
         pool_stats(&idle_b, nullptr);   // idle blocks of the caching allocator are reusable
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < (free_b + idle_b) / 3) onepass = true;
     }
-    if (st == CSX_OK && onepass) {
-        st = dalloc(&toff, (size_t)n + 1);
+    if (onepass) {
+        CSX_TRY(toff.alloc((size_t)n + 1));
         int64_t tot = 0;
-        if (st == CSX_OK) st = scan_exclusive_i32(hprod, toff, n, &tot);
-        if (st == CSX_OK) st = dalloc(&tmp_i, (size_t)big[1]);
-        if (st == CSX_OK && values) st = dalloc(&tmp_x, (size_t)big[1]);
-        if (st == CSX_OK) st = dalloc(&info, (size_t)nhash);
-        if (st == CSX_OK)
-            hipLaunchKernelGGL(k_sg_colinfo, dim3((unsigned)((nhash + 255) / 256)), dim3(256), 0, s, scol + hash_lo, nhash,
-                               B->p, toff, info);
-        for (int hb = 0; hb < SG_HASH_BINS && st == CSX_OK; hb++) {
+        CSX_TRY(scan_exclusive_i32(hprod, toff, n, &tot));
+        CSX_TRY(tmp_i.alloc((size_t)big[1]));
+        if (values) CSX_TRY(tmp_x.alloc((size_t)big[1]));
+        CSX_TRY(info.alloc((size_t)nhash));
+        hipLaunchKernelGGL(k_sg_colinfo, dim3((unsigned)((nhash + 255) / 256)), dim3(256), 0, s, scol + hash_lo, nhash,
+                           B->p, toff, info);
+        for (int hb = 0; hb < SG_HASH_BINS; hb++) {
             const int32_t lo = bin_ptr[SG_BIN_HASH0 + hb], nb = bin_ptr[SG_BIN_HASH0 + hb + 1] - lo;
             const int slots = sg_hash_limit(hb) * 3 / 2;   // load factor <= 2/3
-            st = values ? launch_hash1<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
-                        : launch_hash1<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr);
+            CSX_TRY(values ? launch_hash1<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
+                           : launch_hash1<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
         }
-        for (int hb = 0; hb < SG_NARROW_BINS && st == CSX_OK; hb++) {
+        for (int hb = 0; hb < SG_NARROW_BINS; hb++) {
             const int32_t lo = bin_ptr[SG_BIN_NARROW0 + hb], nb = bin_ptr[SG_BIN_NARROW0 + hb + 1] - lo;
             const int slots = sg_hash_limit(hb) * 3 / 2;
-            st = values ? launch_hash2<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
-                        : launch_hash2<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr);
+            CSX_TRY(values ? launch_hash2<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
+                           : launch_hash2<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
         }
     }
     const int32_t nglobal = bin_ptr[SG_BIN_GLOBAL + 1] - bin_ptr[SG_BIN_GLOBAL];
-    if (st == CSX_OK && nglobal > 0) {
+    if (nglobal > 0) {
         const size_t wgs = (size_t)std::min<int32_t>(nglobal, SG_GLOBAL_WGS);
-        st = dalloc(&g_tmin, wgs * (size_t)m);
-        if (st == CSX_OK && values) st = dalloc(&g_val, wgs * (size_t)m);
-        if (st == CSX_OK) {
-            hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, g_tmin, (int64_t)(wgs * (size_t)m), SG_UNSET);
-            if (values) (void)hipMemsetAsync(g_val, 0, wgs * (size_t)m * sizeof(double), s);
-        }
+        CSX_TRY(g_tmin.alloc(wgs * (size_t)m));
+        if (values) CSX_TRY(g_val.alloc(wgs * (size_t)m));
+        hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, g_tmin, (int64_t)(wgs * (size_t)m), SG_UNSET);
+        if (values) (void)hipMemsetAsync(g_val, 0, wgs * (size_t)m * sizeof(double), s);
     }
     // symbolic: distinct rows per column -> C.p
-    if (st == CSX_OK)
-        st = run_bins<false, false>(A, B, scol, bin_ptr, count, nullptr, nullptr, nullptr, g_tmin, nullptr, onepass);
+    CSX_TRY((run_bins<false, false>(A, B, scol, bin_ptr, count, nullptr, nullptr, nullptr, g_tmin, nullptr, onepass)));
     int64_t total = 0;
-    if (st == CSX_OK) st = scan_exclusive_i32(count, C->p, n, &total);
-    if (st == CSX_OK && total > 0x7FFFFFFFll) {
+    CSX_TRY(scan_exclusive_i32(count, C->p, n, &total));
+    if (total > 0x7FFFFFFFll) {
         set_error("cs_multiply: the product has %lld entries (int32 indices)", (long long)total);
-        st = CSX_EINVAL;
+        return CSX_EINVAL;
     }
-    if (st == CSX_OK) {
-        C->nnz = (int32_t)total;
-        st = dalloc(&C->i, (size_t)total);
-        if (st == CSX_OK && values) st = dalloc(&C->x, (size_t)total);
-    }
-    if (st == CSX_OK && onepass) {
+    C->nnz = (int32_t)total;
+    CSX_TRY(dalloc(&C->i, (size_t)total));
+    if (values) CSX_TRY(dalloc(&C->x, (size_t)total));
+    if (onepass) {
         hipLaunchKernelGGL(k_sg_compact, dim3((unsigned)(((int64_t)nhash + 3) / 4)), dim3(256), 0, s, scol + hash_lo,
                            nhash, toff, C->p, tmp_i, tmp_x, C->i, C->x);
-        if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+        CSX_LAUNCH_CHECK();
     }
-    if (st == CSX_OK) {
-        if (values) st = run_bins<true, true>(A, B, scol, bin_ptr, count, C->p, C->i, C->x, g_tmin, g_val, onepass);
-        else st = run_bins<true, false>(A, B, scol, bin_ptr, count, C->p, C->i, nullptr, g_tmin, nullptr, onepass);
-    }
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) {
+    if (values) CSX_TRY((run_bins<true, true>(A, B, scol, bin_ptr, count, C->p, C->i, C->x, g_tmin, g_val, onepass)));
+    else CSX_TRY((run_bins<true, false>(A, B, scol, bin_ptr, count, C->p, C->i, nullptr, g_tmin, nullptr, onepass)));
+    if (hipStreamSynchronize(s) != hipSuccess) {
         set_error("cs_multiply: %s", hipGetErrorString(hipGetLastError()));
-        st = CSX_ERUNTIME;
+        return CSX_ERUNTIME;
     }
-    dfree(hprod);
-    dfree(toff);
-    dfree(tmp_i);
-    dfree(tmp_x);
-    dfree(info);
-    dfree(bin);
-    dfree(colid);
-    dfree(sbin);
-    dfree(scol);
-    dfree(bin_ptr_d);
-    dfree(count);
-    dfree(too_big);
-    dfree(g_tmin);
-    dfree(g_val);
-    return st;
+    return CSX_OK;
 }
 
 }  // namespace csx
@@ -1386,13 +1359,9 @@ extern "C" int csx_multiply(csx_handle_t hA, csx_handle_t hB, csx_handle_t *out)
     CSX_TRY(require_ready());
     Csc *A = csc(hA), *B = csc(hB);
     if (!A || !B || !out || A->n != B->m) return CSX_EINVAL;
-    Csc *C = new Csc();
-    int st = multiply_device(A, B, C);
-    if (st == CSX_OK && ctx().opt.spgemm_ordered) st = values_in_reference_order(A, B, C);
-    if (st != CSX_OK) {
-        free_csc(C);
-        return st;
-    }
-    *out = put(K_CSC, C);
+    std::unique_ptr<Csc> C(new Csc());
+    CSX_TRY(multiply_device(A, B, C.get()));
+    if (ctx().opt.spgemm_ordered) CSX_TRY(values_in_reference_order(A, B, C.get()));
+    *out = put(K_CSC, C.release());
     return CSX_OK;
 }

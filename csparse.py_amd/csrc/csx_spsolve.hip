@@ -131,113 +131,89 @@ extern "C" int csx_spsolve(csx_handle_t hG, csx_handle_t hB, const int32_t *pinv
         for (int32_t j = 0; j < n; j++)
             if (pinv_host[j] >= n) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
-    Csc *X = new Csc();
+    std::unique_ptr<Csc> X(new Csc());
     X->m = n;
     X->n = nb;
     X->owns = true;
-    int st = dalloc(&X->p, (size_t)nb + 1);
+    CSX_TRY(dalloc(&X->p, (size_t)nb + 1));
     struct Piece {
-        int32_t *i;
-        double *x;
+        DevBuf<int32_t> i;
+        DevBuf<double> x;
         int32_t k0, nc;
         int64_t nnz;
     };
     std::vector<Piece> pieces;
-    DevScope tmp;
-    int32_t *d_pinv = nullptr, *xi = nullptr, *top = nullptr, *cnt = nullptr;
-    unsigned char *mark = nullptr;
-    double *xw = nullptr;
+    DevBuf<int32_t> d_pinv, xi, top, cnt;
+    DevBuf<unsigned char> mark;
+    DevBuf<double> xw;
     int64_t total = 0;
-    if (st == CSX_OK && (n == 0 || nb == 0)) {
+    if (n == 0 || nb == 0) {
         CSX_HIP(hipMemsetAsync(X->p, 0, ((size_t)nb + 1) * sizeof(int32_t), s));
-    } else if (st == CSX_OK) {
-        if (pinv_host) {
-            st = tmp.alloc(&d_pinv, (size_t)n);
-            if (st == CSX_OK && hipMemcpyAsync(d_pinv, pinv_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
+    } else {
+        if (pinv_host) CSX_TRY(upload(d_pinv, pinv_host, (size_t)n));
         const size_t per_lane = (size_t)n * (8 + 1 + (with_values ? 8 : 0));
         size_t budget = SPS_BUDGET, free_b = 0, total_b = 0, idle_b = 0;
         pool_stats(&idle_b, nullptr);   // idle blocks of the caching allocator are reusable
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) budget = std::min(budget, (free_b + idle_b) / 4);
         int64_t lanes = (int64_t)std::max<size_t>(64, budget / std::max<size_t>(per_lane, 1));
         lanes = std::min<int64_t>(std::min<int64_t>(lanes, SPS_MAX_LANES), ((int64_t)nb + 63) / 64 * 64);
-        if (st == CSX_OK) st = tmp.alloc(&xi, (size_t)lanes * 2 * n);
-        if (st == CSX_OK) st = tmp.alloc(&mark, (size_t)lanes * n);
-        if (st == CSX_OK && with_values) st = tmp.alloc(&xw, (size_t)lanes * n);
-        if (st == CSX_OK) st = tmp.alloc(&top, (size_t)lanes);
-        if (st == CSX_OK) st = tmp.alloc(&cnt, (size_t)lanes + 1);
-        if (st == CSX_OK && hipMemsetAsync(mark, 0, (size_t)lanes * n, s) != hipSuccess) st = CSX_ERUNTIME;
-        for (int32_t k0 = 0; k0 < nb && st == CSX_OK; k0 += (int32_t)lanes) {
+        CSX_TRY(xi.alloc((size_t)lanes * 2 * n));
+        CSX_TRY(mark.alloc((size_t)lanes * n));
+        if (with_values) CSX_TRY(xw.alloc((size_t)lanes * n));
+        CSX_TRY(top.alloc((size_t)lanes));
+        CSX_TRY(cnt.alloc((size_t)lanes + 1));
+        CSX_HIP(hipMemsetAsync(mark, 0, (size_t)lanes * n, s));
+        for (int32_t k0 = 0; k0 < nb; k0 += (int32_t)lanes) {
             const int32_t nc = (int32_t)std::min<int64_t>(lanes, (int64_t)nb - k0);
             const unsigned grid = (unsigned)((nc + 63) / 64);
             hipLaunchKernelGGL(k_sps_reach, dim3(grid), dim3(64), 0, s, n, G->p, G->i, d_pinv, B->p, B->i, k0, nc, xi, mark, top,
                                cnt);
-            if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+            CSX_LAUNCH_CHECK();
             int64_t piece_nnz = 0;
             // this chunk's column pointers straight into X.p (relative to the chunk; shifted below)
-            if (st == CSX_OK) st = scan_exclusive_i32(cnt, X->p + k0, nc, &piece_nnz);
-            if (st != CSX_OK) break;
+            CSX_TRY(scan_exclusive_i32(cnt, X->p + k0, nc, &piece_nnz));
             if (total + piece_nnz > 0x7fffffff) {
                 set_error("csx_spsolve: more than 2^31 - 1 entries in X");
-                st = CSX_ERUNTIME;
-                break;
+                return CSX_ERUNTIME;
             }
-            Piece pc{nullptr, nullptr, k0, nc, piece_nnz};
-            st = dalloc(&pc.i, (size_t)piece_nnz);
-            if (st == CSX_OK && with_values) st = dalloc(&pc.x, (size_t)piece_nnz);
-            pieces.push_back(pc);
-            if (st != CSX_OK) break;
+            pieces.push_back(Piece{{}, {}, k0, nc, piece_nnz});
+            Piece &pc = pieces.back();
+            CSX_TRY(pc.i.alloc((size_t)piece_nnz));
+            if (with_values) CSX_TRY(pc.x.alloc((size_t)piece_nnz));
             if (with_values)
                 hipLaunchKernelGGL(k_sps_numeric<true>, dim3(grid), dim3(64), 0, s, n, G->p, G->i, G->x, d_pinv, lo, B->p, B->i,
                                    B->x, k0, nc, xi, xw, top, X->p + k0, pc.i, pc.x);
             else
                 hipLaunchKernelGGL(k_sps_numeric<false>, dim3(grid), dim3(64), 0, s, n, G->p, G->i, G->x, d_pinv, lo, B->p, B->i,
                                    B->x, k0, nc, xi, xw, top, X->p + k0, pc.i, pc.x);
-            if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
-            if (st == CSX_OK && total > 0)
+            CSX_LAUNCH_CHECK();
+            if (total > 0)
                 hipLaunchKernelGGL(k_sps_shift, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, s, X->p + k0, (int64_t)nc,
                                    (int32_t)total);
             total += piece_nnz;
         }
-        if (st == CSX_OK) {
-            const int32_t t32 = (int32_t)total;
-            if (hipMemcpyAsync(X->p + nb, &t32, sizeof t32, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess)
-                st = CSX_ERUNTIME;
-        }
+        const int32_t t32 = (int32_t)total;
+        CSX_HIP(hipMemcpyAsync(X->p + nb, &t32, sizeof t32, hipMemcpyHostToDevice, s));
+        CSX_HIP(hipStreamSynchronize(s));
     }
     // one chunk: its arrays are X's; several: concatenate
-    if (st == CSX_OK) {
-        X->nnz = (int32_t)total;
-        if (pieces.size() == 1) {
-            X->i = pieces[0].i;
-            X->x = pieces[0].x;
-            pieces.clear();
-        } else {
-            st = dalloc(&X->i, (size_t)total);
-            if (st == CSX_OK && with_values) st = dalloc(&X->x, (size_t)total);
-            int64_t off = 0;
-            for (const Piece &pc : pieces) {
-                if (st != CSX_OK) break;
-                if (pc.nnz && hipMemcpyAsync(X->i + off, pc.i, (size_t)pc.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s) != hipSuccess)
-                    st = CSX_ERUNTIME;
-                if (pc.nnz && with_values &&
-                    hipMemcpyAsync(X->x + off, pc.x, (size_t)pc.nnz * sizeof(double), hipMemcpyDeviceToDevice, s) != hipSuccess)
-                    st = CSX_ERUNTIME;
-                off += pc.nnz;
-            }
+    X->nnz = (int32_t)total;
+    if (pieces.size() == 1) {
+        X->i = pieces[0].i.release();
+        X->x = pieces[0].x.release();
+    } else {
+        CSX_TRY(dalloc(&X->i, (size_t)total));
+        if (with_values) CSX_TRY(dalloc(&X->x, (size_t)total));
+        int64_t off = 0;
+        for (const Piece &pc : pieces) {
+            if (pc.nnz) CSX_HIP(hipMemcpyAsync(X->i + off, pc.i, (size_t)pc.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            if (pc.nnz && with_values)
+                CSX_HIP(hipMemcpyAsync(X->x + off, pc.x, (size_t)pc.nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+            off += pc.nnz;
         }
     }
-    if (hipStreamSynchronize(s) != hipSuccess && st == CSX_OK) st = CSX_ERUNTIME;
-    for (const Piece &pc : pieces) {
-        dfree(pc.i);
-        dfree(pc.x);
-    }
-    if (st != CSX_OK) {
-        free_csc(X);
-        return st;
-    }
-    *out = put(K_CSC, X);
+    CSX_HIP(hipStreamSynchronize(s));
+    pieces.clear();
+    *out = put(K_CSC, X.release());
     return CSX_OK;
 }

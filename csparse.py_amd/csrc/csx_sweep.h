@@ -19,7 +19,7 @@ struct Tree {
 // csx_components.hip
 int connected_components(int32_t n, const int32_t *ptr, const int32_t *idx, int sf, int sl, int order, int32_t *root,
                          bool *malformed);
-int group_by_root(int32_t n, const int32_t *root, uint32_t *nodes, int32_t *comp_of_pos, Tree **comps_out,
+int group_by_root(int32_t n, const int32_t *root, uint32_t *nodes, int32_t *comp_of_pos, DevBuf<Tree> *comps_out,
                   int32_t *ncomp_out, int32_t *max_count);
 
 // A wave of the fused sweeps owns an X tile of `per_wave` bytes of LDS.  Waves per workgroup (1 .. maxw) that put the most
@@ -28,7 +28,7 @@ int group_by_root(int32_t n, const int32_t *root, uint32_t *nodes, int32_t *comp
 // a copy of a component list ordered biggest first (stable; counts in [0, max_count]): the order single-wave-per-component kernels launch
 // by -- workgroups go to the XCDs and shader engines in a fixed rotation, so a periodic pattern of big and small components in launch
 // order becomes an imbalance between engines (csx_trisolve.hip: analyse_components)
-int trees_biggest_first(const Tree *trees, int32_t ntrees, int32_t max_count, Tree **out);
+int trees_biggest_first(const Tree *trees, int32_t ntrees, int32_t max_count, DevBuf<Tree> *out);
 
 inline int tile_waves_per_workgroup(size_t per_wave, int maxw) {
     const size_t cu = 160 * 1024 - 1024;

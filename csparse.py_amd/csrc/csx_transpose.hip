@@ -32,29 +32,24 @@ int transpose_device(const Csc *A, bool values, Csc *C) {
     // one stable sort of the entries by row: columns are derived from positions in its first pass, the column
     // pointers of the result come out of its last pass
     SortExtra ex{A->p, A->n, C->p, A->m};
-    int st = stable_sort_by_key_ex((const uint32_t *)A->i, nullptr, with_values ? A->x : nullptr, A->nnz, (uint32_t)A->m,
-                                   nullptr, (uint32_t *)C->i, C->x, &ex);
-    if (st == CSX_OK && hipStreamSynchronize(s) != hipSuccess) st = CSX_ERUNTIME;
-    return st;
+    CSX_TRY(stable_sort_by_key_ex((const uint32_t *)A->i, nullptr, with_values ? A->x : nullptr, A->nnz, (uint32_t)A->m,
+                                  nullptr, (uint32_t *)C->i, C->x, &ex));
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
 }
 
 int build_row_gather(Csc *A) {
     if (A->rows) return CSX_OK;
     if (!A->x) return CSX_EINVAL;
     Csc T;
-    int st = transpose_device(A, true, &T);
-    if (st != CSX_OK) {
-        dfree(T.p);
-        dfree(T.i);
-        dfree(T.x);
-        return st;
-    }
-    Gather *g = new Gather();
+    CSX_TRY(transpose_device(A, true, &T));
+    std::unique_ptr<Gather> g(new Gather());
     g->rows = A->m;
-    g->ptr = T.p;
-    g->idx = T.i;
-    g->val = T.x;
-    A->rows = g;
+    g->ptr = DevBuf<int32_t>(T.p);   // T's arrays change hands
+    g->idx = DevBuf<int32_t>(T.i);
+    g->val = DevBuf<double>(T.x);
+    T.owns = false;
+    A->rows = std::move(g);
     return CSX_OK;
 }
 
@@ -66,12 +61,8 @@ extern "C" int csx_transpose(csx_handle_t hA, int values, csx_handle_t *out) {
     CSX_TRY(require_ready());
     Csc *A = csc(hA);
     if (!A || !out) return CSX_EINVAL;
-    Csc *C = new Csc();
-    int st = transpose_device(A, values != 0, C);
-    if (st != CSX_OK) {
-        free_csc(C);
-        return st;
-    }
-    *out = put(K_CSC, C);
+    std::unique_ptr<Csc> C(new Csc());
+    CSX_TRY(transpose_device(A, values != 0, C.get()));
+    *out = put(K_CSC, C.release());
     return CSX_OK;
 }

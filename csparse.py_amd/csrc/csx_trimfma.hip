@@ -563,33 +563,24 @@ __global__ __launch_bounds__(256, 2) void k_rag_mfma(const int4 *__restrict__ de
         }
 }
 
-void ragged_free(RaggedMfma *R) {
-    if (!R) return;
-    dfree(R->desc);
-    dfree(R->list);
-    dfree(R->frag);
-    delete R;
-}
-
 // the class-ordered list, the descriptors and room for the fragments (not yet written)
 static int ragged_skeleton(const Tree *trees, int32_t ntrees, const int32_t *nodes, RaggedMfma *R) {
     hipStream_t s = ctx().stream;
     R->ntrees = ntrees;
-    DevScope tmp;
-    uint32_t *key = nullptr, *id = nullptr, *skey = nullptr;
-    int32_t *bounds = nullptr;
-    CSX_TRY(tmp.alloc(&key, (size_t)ntrees));
-    CSX_TRY(tmp.alloc(&id, (size_t)ntrees));
-    CSX_TRY(tmp.alloc(&skey, (size_t)ntrees));
-    CSX_TRY(tmp.alloc(&bounds, 2 * RAG_CLASSES + 1));         // (+ per class: "a component's rows are not consecutive")
+    DevBuf<uint32_t> key, id, skey;
+    DevBuf<int32_t> bounds;
+    CSX_TRY(key.alloc((size_t)ntrees));
+    CSX_TRY(id.alloc((size_t)ntrees));
+    CSX_TRY(skey.alloc((size_t)ntrees));
+    CSX_TRY(bounds.alloc(2 * RAG_CLASSES + 1));         // (+ per class: "a component's rows are not consecutive")
     CSX_HIP(hipMemsetAsync(bounds + RAG_CLASSES + 1, 0, RAG_CLASSES * sizeof(int32_t), s));
-    CSX_TRY(dalloc(&R->list, (size_t)ntrees));
+    CSX_TRY(R->list.alloc((size_t)ntrees));
     hipLaunchKernelGGL(k_rag_class, dim3((unsigned)((ntrees + 255) / 256)), dim3(256), 0, s, trees, ntrees, key, id);
     CSX_LAUNCH_CHECK();
-    CSX_TRY(stable_sort_by_key(key, id, nullptr, ntrees, RAG_CLASSES, skey, (uint32_t *)R->list, nullptr));
+    CSX_TRY(stable_sort_by_key(key, id, nullptr, ntrees, RAG_CLASSES, skey, (uint32_t *)R->list.get(), nullptr));
     CSX_TRY(boundaries_from_sorted(skey, ntrees, RAG_CLASSES, bounds));
-    CSX_TRY(dalloc((int4 **)&R->desc, (size_t)ntrees));
-    hipLaunchKernelGGL(k_rag_desc, dim3((unsigned)((ntrees + 255) / 256)), dim3(256), 0, s, R->list, ntrees, trees, nodes, (int4 *)R->desc,
+    CSX_TRY(R->desc.alloc((size_t)ntrees));
+    hipLaunchKernelGGL(k_rag_desc, dim3((unsigned)((ntrees + 255) / 256)), dim3(256), 0, s, R->list, ntrees, trees, nodes, R->desc,
                        bounds + RAG_CLASSES + 1);
     CSX_LAUNCH_CHECK();
     int32_t hb[2 * RAG_CLASSES + 1];
@@ -603,7 +594,7 @@ static int ragged_skeleton(const Tree *trees, int32_t ntrees, const int32_t *nod
         total += (size_t)(R->cls_start[c + 1] - R->cls_start[c]) * (size_t)rag_frags_of(c + 1) * 64;
     }
     R->cls_frag[RAG_CLASSES] = total;
-    CSX_TRY(dalloc(&R->frag, total));
+    CSX_TRY(R->frag.alloc(total));
     return CSX_OK;
 }
 
@@ -621,48 +612,36 @@ __global__ __launch_bounds__(256) void k_rag_fragoff(const int32_t *__restrict__
     off[list[q]] = b.frag[c] + (q - b.start[c]) * (int64_t)((nb * (nb - 1) / 2 + nb) * 4 * 64);
 }
 
-int ragged_prepare_emit(const Tree *trees, int32_t ntrees, int32_t max_rows, const int32_t *nodes, RaggedMfma **out, int64_t **frag_off) {
-    *out = nullptr;
-    *frag_off = nullptr;
+int ragged_prepare_emit(const Tree *trees, int32_t ntrees, int32_t max_rows, const int32_t *nodes, std::unique_ptr<RaggedMfma> *out,
+                        DevBuf<int64_t> *frag_off) {
+    out->reset();
+    frag_off->reset();
     if (ntrees <= 0 || max_rows > RAG_MAX_ROWS) return CSX_OK;
-    RaggedMfma *R = new RaggedMfma();
-    struct Guard {
-        RaggedMfma *R;
-        ~Guard() { ragged_free(R); }
-    } guard{R};
-    CSX_TRY(ragged_skeleton(trees, ntrees, nodes, R));
-    int64_t *off = nullptr;
-    CSX_TRY(dalloc(&off, (size_t)ntrees));
+    std::unique_ptr<RaggedMfma> R(new RaggedMfma());
+    CSX_TRY(ragged_skeleton(trees, ntrees, nodes, R.get()));
+    DevBuf<int64_t> off;
+    CSX_TRY(off.alloc((size_t)ntrees));
     RagBases b;
     for (int c = 0; c <= RAG_CLASSES; c++) {
         b.start[c] = R->cls_start[c];
         b.frag[c] = (int64_t)R->cls_frag[c];
     }
     hipLaunchKernelGGL(k_rag_fragoff, dim3((unsigned)((ntrees + 255) / 256)), dim3(256), 0, ctx().stream, R->list, ntrees, b, off);
-    if (hipGetLastError() != hipSuccess) {
-        dfree(off);
-        return CSX_ERUNTIME;
-    }
-    guard.R = nullptr;
-    *out = R;
-    *frag_off = off;
+    CSX_LAUNCH_CHECK();
+    *out = std::move(R);
+    *frag_off = std::move(off);
     return CSX_OK;
 }
 
 int ragged_build(const Tree *trees, int32_t ntrees, int32_t max_rows, const int32_t *nodes, const int32_t *ptr, const int32_t *idx,
-                 const double *val, const double *diag, bool reverse, RaggedMfma **out, const Csc *from_factor) {
-    *out = nullptr;
+                 const double *val, const double *diag, bool reverse, std::unique_ptr<RaggedMfma> *out, const Csc *from_factor) {
+    out->reset();
     if (ntrees <= 0 || max_rows > RAG_MAX_ROWS) return CSX_OK;
     hipStream_t s = ctx().stream;
-    RaggedMfma *R = new RaggedMfma();
-    struct Guard {
-        RaggedMfma *R;
-        ~Guard() { ragged_free(R); }
-    } guard{R};
-    CSX_TRY(ragged_skeleton(trees, ntrees, nodes, R));
-    DevScope tmp;
-    unsigned long long *cond = nullptr;
-    CSX_TRY(tmp.alloc(&cond, 1));
+    std::unique_ptr<RaggedMfma> R(new RaggedMfma());
+    CSX_TRY(ragged_skeleton(trees, ntrees, nodes, R.get()));
+    DevBuf<unsigned long long> cond;
+    CSX_TRY(cond.alloc(1));
     CSX_HIP(hipMemsetAsync(cond, 0, sizeof(unsigned long long), s));
     for (int c = 0; c < RAG_CLASSES; c++) {
         const int32_t cnt = R->cls_start[c + 1] - R->cls_start[c];
@@ -689,8 +668,7 @@ int ragged_build(const Tree *trees, int32_t ntrees, int32_t max_rows, const int3
     CSX_HIP(hipMemcpyAsync(&hcond, cond, sizeof hcond, hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
     std::memcpy(&R->growth, &hcond, sizeof R->growth);
-    guard.R = nullptr;
-    *out = R;
+    *out = std::move(R);
     return CSX_OK;
 }
 

@@ -51,16 +51,17 @@ struct TriPlan {
     bool sequential = false, zero_pivot = false;
     bool scheduled = false, forward = true;  // level sets are computed on first use
     int32_t gnnz = 0;
-    bool owns_g = false;
     int skip_first = 0, skip_last = 0;
-    int32_t *ptr = nullptr, *idx = nullptr;
+    int32_t *ptr = nullptr, *idx = nullptr;   // the gather arrays: own_* (L, U: the stripped transpose) or the analysed matrix's (L', U')
     double *val = nullptr;
-    double *diag = nullptr;
-    int32_t *order = nullptr, *level_ptr = nullptr;  // device
+    DevBuf<int32_t> own_ptr, own_idx;
+    DevBuf<double> own_val;
+    DevBuf<double> diag;
+    DevBuf<int32_t> order, level_ptr;  // device
     // blocked chain walker (k_tri_chain): per position in `order` the number of leading terms that come from
     // before the row's 16-row block, and per term the block slot of its source (-1: outside the block)
-    int32_t *npre = nullptr, *nin = nullptr;   // nin: number of in-block sources of the row (relaxed order)
-    int8_t *tslot = nullptr;
+    DevBuf<int32_t> npre, nin;   // nin: number of in-block sources of the row (relaxed order)
+    DevBuf<int8_t> tslot;
     bool chain_ok = false;
     std::vector<int32_t> level_ptr_h;
     std::vector<Segment> segs;
@@ -70,11 +71,11 @@ struct TriPlan {
     // solved by one wave with its X tile in LDS.  Built on the device (analyse_components).
     bool comp_tried = false, comp_ok = false;
     int32_t ncomp = 0, comp_max = 0;
-    Tree *comps = nullptr;           // [ncomp] (first, count) into comp_nodes
-    Tree *comps_by_size = nullptr;   // the same list, biggest first (stable): what the many-right-hand-side sweeps launch by
-    int32_t *comp_nodes = nullptr;   // [n] rows grouped by component, ascending inside one
-    int32_t *prog_ptr = nullptr, *prog_idx = nullptr;   // per sweep position: terms (local row * 64, value)
-    double *prog_val = nullptr, *prog_diag = nullptr;
+    DevBuf<Tree> comps;              // [ncomp] (first, count) into comp_nodes
+    DevBuf<Tree> comps_by_size;      // the same list, biggest first (stable): what the many-right-hand-side sweeps launch by
+    DevBuf<int32_t> comp_nodes;      // [n] rows grouped by component, ascending inside one
+    DevBuf<int32_t> prog_ptr, prog_idx;   // per sweep position: terms (local row * 64, value)
+    DevBuf<double> prog_val, prog_diag;
     int col_state = 0;               // k_tri_columns: 0 not examined, 1 usable, 2 not (duplicate rows in a column)
     // windowed column kernels (k_tri_wcolumns / k_tri_wcolchain): band half-width of T (max |row - column|, -1: not
     // measured yet) and the number of columns with an entry next to the diagonal (a chain link)
@@ -82,9 +83,9 @@ struct TriPlan {
     TriPlan *mate = nullptr;         // plan of the transposed solve on the same matrix (cholsol: L for L'), not owned
     std::vector<int32_t> level_hint; // levels proposed by the caller (cholsol: elimination-tree heights / depths); verified before use
     // two-phase runs of narrow levels (k_tri_run_prefix64): level of every row, and per row where its chain resumes
-    int32_t *level_of = nullptr, *resume = nullptr;
-    int32_t *cptr = nullptr, *cidx = nullptr;   // push kinds (L, U): per sweep position the COLUMN's entries
-    double *cval = nullptr, *cdiag = nullptr;
+    DevBuf<int32_t> level_of, resume;
+    DevBuf<int32_t> cptr, cidx;      // push kinds (L, U): per sweep position the COLUMN's entries
+    DevBuf<double> cval, cdiag;
     int32_t push_terms = 0;          // most terms of one component (0: no push program)
     int few_cpw = 0;                 // components per wave of the all-in-LDS kernel (0: its tiles do not fit)
     int32_t few_rows = 0, few_terms = 0;
@@ -95,39 +96,11 @@ struct TriPlan {
     std::vector<int32_t> hTp, hTi;
     std::vector<double> hTx;
     bool rounding_equal = false, rag_tried = false;
-    RaggedMfma *rag = nullptr;
+    std::unique_ptr<RaggedMfma> rag;
     double rag_growth = 0.0;
 };
 
-void free_triplan(TriPlan *t) {
-    if (!t) return;
-    if (t->owns_g) {
-        dfree(t->ptr);
-        dfree(t->idx);
-        dfree(t->val);
-    }
-    dfree(t->diag);
-    dfree(t->order);
-    dfree(t->level_ptr);
-    dfree(t->npre);
-    dfree(t->nin);
-    dfree(t->tslot);
-    dfree(t->level_of);
-    dfree(t->resume);
-    dfree(t->comps);
-    dfree(t->comps_by_size);
-    dfree(t->comp_nodes);
-    dfree(t->prog_ptr);
-    dfree(t->prog_idx);
-    dfree(t->prog_val);
-    dfree(t->prog_diag);
-    dfree(t->cptr);
-    dfree(t->cidx);
-    dfree(t->cval);
-    dfree(t->cdiag);
-    ragged_free(t->rag);
-    delete t;
-}
+void destroy(TriPlan *t) { delete t; }
 
 constexpr int NARROW = 512;   // (rows in level) * nrhs at or below this: level joins a one-workgroup run
 
@@ -1599,39 +1572,37 @@ static int analyse_components(TriPlan *P) {
     const int32_t n = P->n;
     if (n < COMP_MIN_COUNT) return CSX_OK;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    int32_t *root = nullptr, *local_id = nullptr, *len = nullptr, *comp_of_pos = nullptr;
-    uint32_t *srow = nullptr;
-    int *flags = nullptr;
-    CSX_TRY(tmp.alloc(&root, (size_t)n));
-    CSX_TRY(tmp.alloc(&flags, 4));
+    DevBuf<int32_t> root, local_id, len, comp_of_pos, clen;
+    DevBuf<uint32_t> srow;
+    DevBuf<int> flags;
+    CSX_TRY(root.alloc((size_t)n));
+    CSX_TRY(flags.alloc(4));
     bool malformed = false;
     CSX_TRY(connected_components(n, P->ptr, P->idx, P->skip_first, P->skip_last, P->forward ? 1 : 2, root, &malformed));
     if (malformed) return CSX_OK;         // the literal transcription of the reference loop handles it
-    Tree *comps = nullptr;
     int32_t ncomp = 0, maxc = 0;
-    CSX_TRY(tmp.alloc(&srow, (size_t)n));
-    CSX_TRY(tmp.alloc(&comp_of_pos, (size_t)n));
-    CSX_TRY(group_by_root(n, root, srow, comp_of_pos, &comps, &ncomp, &maxc));
-    P->comps = comps;
+    CSX_TRY(srow.alloc((size_t)n));
+    CSX_TRY(comp_of_pos.alloc((size_t)n));
+    CSX_TRY(group_by_root(n, root, srow, comp_of_pos, &P->comps, &ncomp, &maxc));
+    const Tree *comps = P->comps;
     if (ncomp < COMP_MIN_COUNT || maxc > COMP_MAX_ROWS) return CSX_OK;
     const unsigned nbw = (unsigned)(((int64_t)n + 3) / 4);
     int hflags[4] = {maxc, 0, 0, 0};
     P->ncomp = (int32_t)ncomp;
     P->comp_max = hflags[0];
-    CSX_TRY(tmp.alloc(&local_id, (size_t)n));
-    CSX_TRY(tmp.alloc(&len, (size_t)n + 1));
+    CSX_TRY(local_id.alloc((size_t)n));
+    CSX_TRY(len.alloc((size_t)n + 1));
     const unsigned ncw = (unsigned)((ncomp + 3) / 4);
     hipLaunchKernelGGL(k_cc_local_id, dim3(ncw), dim3(256), 0, s, P->ncomp, comps, srow, local_id);
     hipLaunchKernelGGL(k_prog_len, dim3(ncw), dim3(256), 0, s, P->ncomp, comps, srow, P->ptr, P->skip_first, P->skip_last,
                        P->forward ? 1 : 0, len);
-    CSX_TRY(dalloc(&P->prog_ptr, (size_t)n + 1));
+    CSX_TRY(P->prog_ptr.alloc((size_t)n + 1));
     int64_t total = 0;
     CSX_TRY(scan_exclusive_i32(len, P->prog_ptr, n, &total));
-    CSX_TRY(dalloc(&P->prog_idx, (size_t)total + 64));
-    CSX_TRY(dalloc(&P->prog_val, (size_t)total + 64));
-    CSX_TRY(dalloc(&P->prog_diag, (size_t)n));
-    CSX_TRY(dalloc(&P->comp_nodes, (size_t)n));
+    CSX_TRY(P->prog_idx.alloc((size_t)total + 64));
+    CSX_TRY(P->prog_val.alloc((size_t)total + 64));
+    CSX_TRY(P->prog_diag.alloc((size_t)n));
+    CSX_TRY(P->comp_nodes.alloc((size_t)n));
     hipLaunchKernelGGL(k_prog_fill, dim3(nbw), dim3(256), 0, s, n, comp_of_pos, comps, srow, local_id, P->ptr, P->idx, P->val,
                        P->diag, P->skip_first, P->forward ? 1 : 0, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag);
     CSX_HIP(hipMemcpyAsync(P->comp_nodes, srow, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -1645,15 +1616,14 @@ static int analyse_components(TriPlan *P) {
         CSX_HIP(hipMemcpyAsync(&hdup, flags, sizeof(int), hipMemcpyDeviceToHost, s));
         CSX_HIP(hipStreamSynchronize(s));
         if (!hdup) {
-            int32_t *clen = nullptr;
-            CSX_TRY(tmp.alloc(&clen, (size_t)n + 1));
+            CSX_TRY(clen.alloc((size_t)n + 1));
             hipLaunchKernelGGL(k_push_len, dim3(ncw), dim3(256), 0, s, P->ncomp, comps, srow, P->Tp, P->forward ? 1 : 0, clen);
-            CSX_TRY(dalloc(&P->cptr, (size_t)n + 1));
+            CSX_TRY(P->cptr.alloc((size_t)n + 1));
             int64_t ctotal = 0;
             CSX_TRY(scan_exclusive_i32(clen, P->cptr, n, &ctotal));
-            CSX_TRY(dalloc(&P->cidx, (size_t)ctotal + 64));
-            CSX_TRY(dalloc(&P->cval, (size_t)ctotal + 64));
-            CSX_TRY(dalloc(&P->cdiag, (size_t)n));
+            CSX_TRY(P->cidx.alloc((size_t)ctotal + 64));
+            CSX_TRY(P->cval.alloc((size_t)ctotal + 64));
+            CSX_TRY(P->cdiag.alloc((size_t)n));
             CSX_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
             hipLaunchKernelGGL(k_push_fill, dim3(nbw), dim3(256), 0, s, n, comp_of_pos, comps, srow, local_id, P->Tp, P->Ti,
                                P->Tx, P->forward ? 1 : 0, P->cptr, P->cidx, P->cval, P->cdiag, flags);
@@ -1694,12 +1664,11 @@ static int analyse_components(TriPlan *P) {
 static int components_ragged(TriPlan *P) {
     if (P->rag_tried) return CSX_OK;
     P->rag_tried = true;
-    RaggedMfma *R = nullptr;
+    std::unique_ptr<RaggedMfma> R;
     CSX_TRY(ragged_build(P->comps, P->ncomp, P->comp_max, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, !P->forward, &R));
     if (R) {
         P->rag_growth = R->growth;
-        if (R->growth <= RAG_GROWTH_LIMIT) P->rag = R;     // (a NaN fails the comparison)
-        else ragged_free(R);
+        if (R->growth <= RAG_GROWTH_LIMIT) P->rag = std::move(R);     // (a NaN fails the comparison)
     }
     return CSX_OK;
 }
@@ -1719,7 +1688,7 @@ static int solve_components(TriPlan *P, double *X, int32_t nrhs, const TriIO *io
     if (P->rounding_equal && nrhs > 8) {
         // the caller granted rounding (csx_tri_set_order): dense components on the matrix cores, one sweep in position order
         CSX_TRY(components_ragged(P));
-        if (P->rag) return ragged_solve(P->rag, P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
+        if (P->rag) return ragged_solve(P->rag.get(), P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
     }
     // L, U with up to 8 right-hand sides: one wave per component, column-push form (W, L + U pair: 43 us at 1 RHS,
     // 78 us at 8; at 64 the entry-parallel lanes are gone and it loses to k_tri_local, 483 against 272 us)
@@ -1812,13 +1781,6 @@ static int solve_components(TriPlan *P, double *X, int32_t nrhs, const TriIO *io
 }
 
 // ---- analysis ---------------------------------------------------------------------
-static int download_i32(std::vector<int32_t> &h, const int32_t *d, size_t count) {
-    h.resize(count);
-    if (count) CSX_HIP(hipMemcpyAsync(h.data(), d, count * sizeof(int32_t), hipMemcpyDeviceToHost, ctx().stream));
-    CSX_HIP(hipStreamSynchronize(ctx().stream));
-    return CSX_OK;
-}
-
 // Level of every unknown from the gather structure.  forward: inputs have smaller
 // index.  Returns false if some input does not precede its unknown (malformed).
 static bool compute_levels(int32_t n, const std::vector<int32_t> &ptr, const std::vector<int32_t> &idx, int sf, int sl,
@@ -1839,30 +1801,30 @@ static bool compute_levels(int32_t n, const std::vector<int32_t> &ptr, const std
     return true;
 }
 
+// *out is set on success only
 static int analyse(const Csc *T, int kind, TriPlan **out) {
     hipStream_t s = ctx().stream;
     const int32_t n = T->n;
-    TriPlan *P = new TriPlan();
-    *out = P;
+    std::unique_ptr<TriPlan> P(new TriPlan());
     P->kind = kind;
     P->n = n;
     P->Tp = T->p;
     P->Ti = T->i;
     P->Tx = T->x;
-    if (n == 0) return CSX_OK;
-    int *flag = nullptr;
-    CSX_TRY(dalloc(&flag, 2));
+    if (n == 0) {
+        *out = P.release();
+        return CSX_OK;
+    }
+    DevBuf<int> flag;
+    CSX_TRY(flag.alloc(2));
     CSX_HIP(hipMemsetAsync(flag, 0, 2 * sizeof(int), s));
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
     hipLaunchKernelGGL(k_check_columns, dim3(nb), dim3(256), 0, s, n, T->p, flag);
     int hflag[2] = {0, 0};
     CSX_HIP(hipMemcpyAsync(hflag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
-    if (hflag[0]) {  // a column without entries has no diagonal: the reference would index past it
-        dfree(flag);
-        return CSX_EINVAL;
-    }
-    CSX_TRY(dalloc(&P->diag, (size_t)n));
+    if (hflag[0]) return CSX_EINVAL;  // a column without entries has no diagonal: the reference would index past it
+    CSX_TRY(P->diag.alloc((size_t)n));
     const bool forward = (kind == CSX_TRI_L || kind == CSX_TRI_UT);
     if (kind == CSX_TRI_LT || kind == CSX_TRI_UT) {
         P->ptr = T->p;
@@ -1872,13 +1834,14 @@ static int analyse(const Csc *T, int kind, TriPlan **out) {
         P->skip_last = kind == CSX_TRI_UT ? 1 : 0;
         hipLaunchKernelGGL(k_diag_direct, dim3(nb), dim3(256), 0, s, n, T->p, T->x, kind == CSX_TRI_UT ? 1 : 0, P->diag);
     } else {
-        Csc S;  // stripped copy
-        S.m = S.n = n;
-        S.nnz = T->nnz - n;
-        int st = dalloc(&S.p, (size_t)n + 1);
-        if (st == CSX_OK) st = dalloc(&S.i, (size_t)S.nnz);
-        if (st == CSX_OK) st = dalloc(&S.x, (size_t)S.nnz);
-        if (st == CSX_OK) {
+        Csc G;
+        {
+            Csc S;  // stripped copy
+            S.m = S.n = n;
+            S.nnz = T->nnz - n;
+            CSX_TRY(dalloc(&S.p, (size_t)n + 1));
+            CSX_TRY(dalloc(&S.i, (size_t)S.nnz));
+            CSX_TRY(dalloc(&S.x, (size_t)S.nnz));
             int64_t blocks = std::min<int64_t>(((int64_t)n + 4) / 4, 65536);
             const bool short_cols = (int64_t)T->nnz < 8 * (int64_t)n;
             if (kind == CSX_TRI_L && short_cols)
@@ -1890,24 +1853,16 @@ static int analyse(const Csc *T, int kind, TriPlan **out) {
             else
                 hipLaunchKernelGGL(k_strip_last_reverse, dim3((unsigned)blocks), dim3(256), 0, s, n, T->p, T->i, T->x,
                                    S.p, S.i, S.x, P->diag);
-            if (hipGetLastError() != hipSuccess) st = CSX_ERUNTIME;
+            CSX_LAUNCH_CHECK();
+            CSX_TRY(transpose_device(&S, true, &G));
         }
-        Csc G;
-        if (st == CSX_OK) st = transpose_device(&S, true, &G);
-        dfree(S.p);
-        dfree(S.i);
-        dfree(S.x);
-        if (st != CSX_OK) {
-            dfree(G.p);
-            dfree(G.i);
-            dfree(G.x);
-            dfree(flag);
-            return st;
-        }
-        P->ptr = G.p;
-        P->idx = G.i;
-        P->val = G.x;
-        P->owns_g = true;
+        P->own_ptr = DevBuf<int32_t>(G.p);   // G's arrays change hands
+        P->own_idx = DevBuf<int32_t>(G.i);
+        P->own_val = DevBuf<double>(G.x);
+        G.owns = false;
+        P->ptr = P->own_ptr;
+        P->idx = P->own_idx;
+        P->val = P->own_val;
         if (kind == CSX_TRI_U && G.nnz > 0) {
             hipLaunchKernelGGL(k_reverse_index, dim3((unsigned)(((int64_t)G.nnz + 255) / 256)), dim3(256), 0, s,
                                (int64_t)G.nnz, n, P->idx);
@@ -1916,10 +1871,11 @@ static int analyse(const Csc *T, int kind, TriPlan **out) {
     hipLaunchKernelGGL(k_any_zero, dim3(nb), dim3(256), 0, s, n, P->diag, flag + 1);
     CSX_HIP(hipMemcpyAsync(hflag, flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
-    dfree(flag);
+    flag.reset();
     P->zero_pivot = hflag[1] != 0;
     P->gnnz = (kind == CSX_TRI_LT || kind == CSX_TRI_UT) ? T->nnz : T->nnz - n;
     P->forward = forward;
+    *out = P.release();
     return CSX_OK;
 }
 
@@ -2037,29 +1993,28 @@ __global__ __launch_bounds__(256) void k_lv_verify(int32_t n, const int32_t *__r
 static int schedule_from_levels(TriPlan *P, const int32_t *level, int32_t L) {
     hipStream_t s = ctx().stream;
     const int32_t n = P->n;
-    DevScope tmp;
-    int32_t *pos_of = nullptr;
-    uint32_t *rows = nullptr, *slevel = nullptr, *order = nullptr;
-    unsigned long long *sums = nullptr;
+    DevBuf<int32_t> pos_of;
+    DevBuf<uint32_t> rows, slevel;
+    DevBuf<unsigned long long> sums;
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256);
     P->nlevels = L;
     // rows by level, ascending row inside a level (stable sort of 0..n-1 by level)
-    CSX_TRY(tmp.alloc(&rows, (size_t)n));
-    CSX_TRY(tmp.alloc(&slevel, (size_t)n));
-    CSX_TRY(dalloc(&order, (size_t)n));
-    P->order = (int32_t *)order;
+    CSX_TRY(rows.alloc((size_t)n));
+    CSX_TRY(slevel.alloc((size_t)n));
+    CSX_TRY(P->order.alloc((size_t)n));
+    uint32_t *order = (uint32_t *)P->order.get();
     hipLaunchKernelGGL(k_iota_u32_tri, dim3(nb), dim3(256), 0, s, n, rows);
     CSX_TRY(stable_sort_by_key((const uint32_t *)level, rows, nullptr, n, (uint32_t)L, slevel, order, nullptr));
-    CSX_TRY(dalloc(&P->level_ptr, (size_t)L + 1));
+    CSX_TRY(P->level_ptr.alloc((size_t)L + 1));
     CSX_TRY(boundaries_from_sorted(slevel, n, L, P->level_ptr));
     P->level_ptr_h.resize((size_t)L + 1);
     CSX_HIP(hipMemcpyAsync(P->level_ptr_h.data(), P->level_ptr, ((size_t)L + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     // chain-walker tables
-    CSX_TRY(tmp.alloc(&pos_of, (size_t)n));
-    CSX_TRY(tmp.alloc(&sums, 2));
-    CSX_TRY(dalloc(&P->npre, (size_t)n));
-    CSX_TRY(dalloc(&P->nin, (size_t)n));
-    CSX_TRY(dalloc(&P->tslot, (size_t)P->gnnz + 1));
+    CSX_TRY(pos_of.alloc((size_t)n));
+    CSX_TRY(sums.alloc(2));
+    CSX_TRY(P->npre.alloc((size_t)n));
+    CSX_TRY(P->nin.alloc((size_t)n));
+    CSX_TRY(P->tslot.alloc((size_t)P->gnnz + 1));
     CSX_HIP(hipMemsetAsync(sums, 0, 2 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_lv_pos_of, dim3(nb), dim3(256), 0, s, n, order, pos_of);
     hipLaunchKernelGGL(k_lv_chain_tables, dim3(nb), dim3(256), 0, s, n, order, pos_of, P->ptr, P->idx, P->skip_first,
@@ -2085,11 +2040,10 @@ static int schedule_from_hint(TriPlan *P, bool *done) {
         if (v < 0) return CSX_OK;
         L = std::max(L, v + 1);
     }
-    DevScope tmp;
-    int32_t *level = nullptr;
-    int *stats = nullptr;
-    CSX_TRY(tmp.alloc(&level, (size_t)n));
-    CSX_TRY(tmp.alloc(&stats, 1));
+    DevBuf<int32_t> level;
+    DevBuf<int> stats;
+    CSX_TRY(level.alloc((size_t)n));
+    CSX_TRY(stats.alloc(1));
     CSX_HIP(hipMemcpyAsync(level, P->level_hint.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CSX_HIP(hipMemsetAsync(stats, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_lv_verify, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, P->ptr, P->idx, P->skip_first,
@@ -2109,11 +2063,10 @@ static int schedule_on_device(TriPlan *P, bool *done) {
     *done = false;
     hipStream_t s = ctx().stream;
     const int32_t n = P->n;
-    DevScope tmp;
-    int32_t *level = nullptr;
-    int *stats = nullptr;
-    CSX_TRY(tmp.alloc(&level, (size_t)n));
-    CSX_TRY(tmp.alloc(&stats, 2));
+    DevBuf<int32_t> level;
+    DevBuf<int> stats;
+    CSX_TRY(level.alloc((size_t)n));
+    CSX_TRY(stats.alloc(2));
     const unsigned nb = (unsigned)(((int64_t)n + 255) / 256), nbw = (unsigned)(((int64_t)n + 3) / 4);
     hipLaunchKernelGGL(k_lv_init, dim3(nb), dim3(256), 0, s, n, level);
     int64_t resolved = 0;
@@ -2156,8 +2109,7 @@ static int ensure_schedule(TriPlan *P) {
         bool done = false;
         CSX_TRY(schedule_on_device(P, &done));
         if (done) return CSX_OK;
-        dfree(P->order);          // gave up part way (deeper than LV_MAX_ROUNDS): start over on the host
-        P->order = nullptr;
+        P->order.reset();          // gave up part way (deeper than LV_MAX_ROUNDS): start over on the host
     }
     std::vector<int32_t> hptr, hidx;
     CSX_TRY(download_i32(hptr, P->ptr, (size_t)n + 1));
@@ -2175,8 +2127,8 @@ static int ensure_schedule(TriPlan *P) {
     for (int32_t l = 0; l < P->nlevels; l++) P->level_ptr_h[(size_t)l + 1] += P->level_ptr_h[(size_t)l];
     std::vector<int32_t> order((size_t)n), fill(P->level_ptr_h.begin(), P->level_ptr_h.end() - 1);
     for (int32_t r = 0; r < n; r++) order[(size_t)fill[(size_t)level[r]]++] = r;
-    CSX_TRY(dalloc(&P->order, (size_t)n));
-    CSX_TRY(dalloc(&P->level_ptr, (size_t)P->nlevels + 1));
+    CSX_TRY(P->order.alloc((size_t)n));
+    CSX_TRY(P->level_ptr.alloc((size_t)P->nlevels + 1));
     CSX_HIP(hipMemcpyAsync(P->order, order.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CSX_HIP(hipMemcpyAsync(P->level_ptr, P->level_ptr_h.data(), ((size_t)P->nlevels + 1) * sizeof(int32_t),
                            hipMemcpyHostToDevice, s));
@@ -2205,10 +2157,10 @@ static int ensure_schedule(TriPlan *P) {
     // solves: the in-block sources are a row's LAST terms); when they come first (L' x = b in the
     // reference's order) nearly every term would wait in phase B and the level walker is the better one
     P->chain_ok = all_terms > 0 && suffix_terms * 4 <= all_terms;
-    CSX_TRY(dalloc(&P->npre, (size_t)n));
-    CSX_TRY(dalloc(&P->nin, (size_t)n));
+    CSX_TRY(P->npre.alloc((size_t)n));
+    CSX_TRY(P->nin.alloc((size_t)n));
     CSX_HIP(hipMemcpyAsync(P->nin, hnin.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    CSX_TRY(dalloc(&P->tslot, (size_t)P->gnnz + 1));
+    CSX_TRY(P->tslot.alloc((size_t)P->gnnz + 1));
     CSX_HIP(hipMemcpyAsync(P->npre, hnpre.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
     CSX_HIP(hipMemcpyAsync(P->tslot, hslot.data(), (size_t)P->gnnz + 1, hipMemcpyHostToDevice, s));
     CSX_HIP(hipStreamSynchronize(s));
@@ -2243,10 +2195,9 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
     // a window of x otherwise.
     if (ctx().opt.tri_columns) {
         if (P->band < 0) {
-            DevScope tmp;
-            int *o = nullptr;
+            DevBuf<int> o;
             int h[3] = {0, 0, 0};
-            CSX_TRY(tmp.alloc(&o, 3));
+            CSX_TRY(o.alloc(3));
             CSX_HIP(hipMemsetAsync(o, 0, 3 * sizeof(int), s));
             hipLaunchKernelGGL(k_tri_band, dim3((unsigned)std::min<int64_t>(((int64_t)P->n + 3) / 4, 2048)), dim3(256), 0, s, P->n, P->Tp, P->Ti,
                                (P->kind == CSX_TRI_L || P->kind == CSX_TRI_LT) ? 1 : 0, o);
@@ -2273,7 +2224,7 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
             const bool push = P->kind == CSX_TRI_L || P->kind == CSX_TRI_U;
             const TriPlan *M = P->mate;
             // rounding-equal order, L' (any size): the rows of L (the mate's gather arrays) pushed as the columns of L'
-            const bool mate_push = !push && relaxed && P->kind == CSX_TRI_LT && M && M->kind == CSX_TRI_L && M->owns_g &&
+            const bool mate_push = !push && relaxed && P->kind == CSX_TRI_LT && M && M->kind == CSX_TRI_L && M->own_ptr &&
                                    M->col_state == 1 && M->n == P->n;
             if ((big && push && P->col_state == 1) || mate_push) {
                 const int32_t *cp = mate_push ? M->ptr : P->Tp, *ci = mate_push ? M->idx : P->Ti;
@@ -2339,10 +2290,9 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
         if (P->col_state == 0) {
             P->col_state = 1;
             if (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U) {   // gather structure of a push kind = stable transpose
-                DevScope tmp;
-                int *flag = nullptr;
+                DevBuf<int> flag;
                 int h = 0;
-                CSX_TRY(tmp.alloc(&flag, 1));
+                CSX_TRY(flag.alloc(1));
                 CSX_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
                 hipLaunchKernelGGL(k_adjacent_equal, dim3((unsigned)(((int64_t)P->n + 3) / 4)), dim3(256), 0, s, P->n, P->ptr,
                                    P->idx, flag);
@@ -2397,8 +2347,8 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
         if (by_rows64 && g.one_wg) {
             // runs of narrow levels in two phases, TR64_RUN levels at a time (see k_tri_run_prefix64)
             if (!P->level_of && g.l1 - g.l0 >= TR64_RUN_MIN) {
-                CSX_TRY(dalloc(&P->level_of, (size_t)P->n));
-                CSX_TRY(dalloc(&P->resume, (size_t)P->n));
+                CSX_TRY(P->level_of.alloc((size_t)P->n));
+                CSX_TRY(P->resume.alloc((size_t)P->n));
                 hipLaunchKernelGGL(k_tri_level_of, dim3((unsigned)(((int64_t)P->n + 255) / 256)), dim3(256), 0, s, P->nlevels,
                                    P->level_ptr, P->order, P->n, P->level_of);
             }
@@ -2425,8 +2375,8 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
                                P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         } else if (by_rows && g.one_wg) {
             if (!P->level_of && g.l1 - g.l0 >= TR64_RUN_MIN) {
-                CSX_TRY(dalloc(&P->level_of, (size_t)P->n));
-                CSX_TRY(dalloc(&P->resume, (size_t)P->n));
+                CSX_TRY(P->level_of.alloc((size_t)P->n));
+                CSX_TRY(P->resume.alloc((size_t)P->n));
                 hipLaunchKernelGGL(k_tri_level_of, dim3((unsigned)(((int64_t)P->n + 255) / 256)), dim3(256), 0, s, P->nlevels,
                                    P->level_ptr, P->order, P->n, P->level_of);
             }
@@ -2489,11 +2439,7 @@ extern "C" int csx_tri_analyse(csx_handle_t hT, int kind, csx_handle_t *out) {
     Csc *T = csc(hT);
     if (!T || !out || !T->x || T->m != T->n || kind < 0 || kind > 3) return CSX_EINVAL;
     TriPlan *P = nullptr;
-    int st = analyse(T, kind, &P);
-    if (st != CSX_OK) {
-        free_triplan(P);
-        return st;
-    }
+    CSX_TRY(analyse(T, kind, &P));
     *out = put(K_TRIPLAN, P);
     return CSX_OK;
 }
@@ -2686,16 +2632,15 @@ extern "C" int csx_lusol_solve(csx_handle_t hL, csx_handle_t hU, csx_handle_t hp
             CSX_TRY(components_ragged(PU));
         }
         if (PL->comp_ok && PU->comp_ok && PL->rag && PU->rag) {
-            DevScope tmp;
-            int32_t *invp = nullptr;
+            DevBuf<int32_t> invp;
             if (pinv) {
-                CSX_TRY(tmp.alloc(&invp, (size_t)n));
+                CSX_TRY(invp.alloc((size_t)n));
                 CSX_HIP(hipMemsetAsync(invp, 0, (size_t)n * sizeof(int32_t), s));      // (not a permutation: rows never named read row 0)
                 hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, pinv, n, invp);
                 CSX_LAUNCH_CHECK();
             }
-            CSX_TRY(ragged_solve_io(PL->rag, PL->comp_nodes, invp, nullptr, !PL->forward, 1, b, x, nrhs, n));
-            CSX_TRY(ragged_solve_io(PU->rag, PU->comp_nodes, nullptr, q, !PU->forward, 1, x, b, nrhs, n));
+            CSX_TRY(ragged_solve_io(PL->rag.get(), PL->comp_nodes, invp, nullptr, !PL->forward, 1, b, x, nrhs, n));
+            CSX_TRY(ragged_solve_io(PU->rag.get(), PU->comp_nodes, nullptr, q, !PU->forward, 1, x, b, nrhs, n));
             if (fused) *fused = 1;
             return CSX_OK;
         }
@@ -2706,10 +2651,9 @@ extern "C" int csx_lusol_solve(csx_handle_t hL, csx_handle_t hU, csx_handle_t hp
         CSX_TRY(analyse_components(PL));
         CSX_TRY(analyse_components(PU));
         if (PL->comp_ok && PU->comp_ok) {
-            DevScope tmp;
-            int32_t *invp = nullptr;
+            DevBuf<int32_t> invp;
             if (pinv) {
-                CSX_TRY(tmp.alloc(&invp, (size_t)n));
+                CSX_TRY(invp.alloc((size_t)n));
                 CSX_HIP(hipMemsetAsync(invp, 0, (size_t)n * sizeof(int32_t), s));
                 hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, pinv, n, invp);
                 CSX_LAUNCH_CHECK();

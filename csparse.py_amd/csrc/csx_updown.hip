@@ -76,13 +76,12 @@ extern "C" int csx_updown(csx_handle_t hL, int sigma, int32_t cnz, const int32_t
     for (int32_t j = 0; j < n; j++)
         if (parent[j] < -1 || parent[j] >= n) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
-    DevScope tmp;
-    double *w = nullptr;
-    int32_t *d_parent = nullptr;
-    int *d_res = nullptr;
-    CSX_TRY(tmp.alloc(&w, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_parent, (size_t)n));
-    CSX_TRY(tmp.alloc(&d_res, 1));
+    DevBuf<double> w;
+    DevBuf<int32_t> d_parent;
+    DevBuf<int> d_res;
+    CSX_TRY(w.alloc((size_t)n));
+    CSX_TRY(d_parent.alloc((size_t)n));
+    CSX_TRY(d_res.alloc(1));
     // w = 0 everywhere (the reference's xalloc), then w = C; later duplicates of a row win, as in the reference
     std::vector<double> hw((size_t)n, 0.0);
     for (int32_t q = 0; q < cnz; q++) hw[(size_t)Ci[q]] = Cx[q];
@@ -95,9 +94,7 @@ extern "C" int csx_updown(csx_handle_t hL, int sigma, int32_t cnz, const int32_t
     CSX_HIP(hipStreamSynchronize(s));
     *ok = res;
     // the factor's values changed: plans cached on it are stale
-    free_gather(L->rows);
-    L->rows = nullptr;
-    free_tiled(L->tiled);
-    L->tiled = nullptr;
+    L->rows.reset();
+    L->tiled.reset();
     return CSX_OK;
 }
