@@ -79,6 +79,7 @@ _PROTOS = {
     "csx_tri_components": [H, _i32p],
     "csx_permute_vec": [H, H, H, C.c_int32, C.c_int32, C.c_int],
     "csx_lusol_solve": [H, H, H, H, H, H, C.c_int32, C.POINTER(C.c_int)],
+    "csx_lusol_solve_trans": [H, H, H, H, H, H, C.c_int32, C.POINTER(C.c_int)],
     "csx_schol_host": [C.c_int32, _i32p, _i32p, _i32p, _i32p],
     "csx_counts_host": [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, C.c_int, _i32p],
     "csx_chol": [H, _i32p, _i32p, _i32p, C.POINTER(H)],
@@ -133,6 +134,7 @@ _PROTOS = {
     "csx_btf_split": [H, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, C.POINTER(H), C.POINTER(H)],
     "csx_btf_plan": [H, H, H, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.POINTER(H)],
     "csx_btf_solve": [H, H, H, C.c_int32],
+    "csx_btf_solve_trans": [H, H, H, C.c_int32],
     "csx_btf_info": [H, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

@@ -1416,6 +1416,43 @@ def cs_lusol(order, A, b, tol):
     return True
 
 
+def _condest(norm_a, solve, n):
+    """cond_1(A) = |A|_1 |A^-1|_1 estimated with |A|_1 = norm_a and Hager-Higham's estimator of |A^-1|_1 as LAPACK's dlacn2
+    runs it (Higham 1988, ITMAX = 5): solve(v, trans) returns A^-1 v (trans False) or A^-T v (trans True) for a numpy
+    n-vector.  sign(0) = +1; ties of the largest |z_j| go to the lowest j.  0.0 for n = 0."""
+    if n == 0:
+        return 0.0
+
+    def sgn(v):
+        return np.where(v >= 0.0, 1.0, -1.0)
+
+    y = solve(np.full(n, 1.0 / n), False)
+    if n == 1:
+        return float(norm_a) * abs(float(y[0]))
+    est = float(np.sum(np.abs(y)))
+    xi = sgn(y)
+    j = int(np.argmax(np.abs(solve(xi, True))))
+    it = 2
+    while True:
+        e = np.zeros(n)
+        e[j] = 1.0
+        y = solve(e, False)
+        est_old, est = est, float(np.sum(np.abs(y)))
+        s = sgn(y)
+        if np.array_equal(s, xi) or est <= est_old:      # repeated sign vector: converged; no increase: cycling
+            break
+        xi = s
+        z = solve(xi, True)
+        j_last, j = j, int(np.argmax(np.abs(z)))
+        if z[j_last] != abs(z[j]) and it < 5:
+            it += 1
+            continue
+        break
+    alt = np.where(np.arange(n) % 2 == 0, 1.0, -1.0) * (1.0 + np.arange(n) / (n - 1.0))
+    temp = 2.0 * (float(np.sum(np.abs(solve(alt, False)))) / (3.0 * n))
+    return float(norm_a) * max(est, temp)
+
+
 def lusol_factor(A, order=0, tol=1.0, exact=None):
     """Factor once for many solves -- the batched form of cs_lusol (csparse.py:1456-1478): cs_sqr + cs_lu once, then
     solve(b) runs the reference's sequence x = b(p); L \\ x; U \\ x; b(q) = x (:1474-1477) on the device for a list (one
@@ -1427,7 +1464,13 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
     (csx_tri_set_order; refused when an inverse of a diagonal tile is large); exact=True: every solve bit-identical to
     cs_lusol on that column; exact=False: every solve rounding-equal.  cs_lusol, the reference's driver, is always exact.
     solve(b, comm=..., nrhs=K) shards the block by right-hand-side block over the ranks of a shard.Comm, every rank
-    holding this factor; see cholsol_factor.  None when A is not square CSC or singular."""
+    holding this factor; see cholsol_factor.
+    solve(b, trans=True) solves A' x = b on the same factors (L U = A(p, q)): y = b(q) (cs_pvec), U' y = y
+    (cs_utsolve), L' y = y (cs_ltsolve), x = y(pinv) (cs_pvec) -- the exact order is that sequence operation for operation,
+    under the same rule for lists, blocks and `exact`; through comm= as well.
+    condest(): an estimate of cond_1(A) = |A|_1 |A^-1|_1: cs_norm(A) (cached) times Hager-Higham's estimate of |A^-1|_1
+    (LAPACK dlacn2's iteration) from exact-order single right-hand-side solves, forward and transposed.
+    None when A is not square CSC or singular."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     S = cs_sqr(order, A, False)
@@ -1444,22 +1487,28 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
 
         def __init__(self):
             self._fin = weakref.finalize(self, lambda hs: [_csx.free(h) for h in hs if h is not None], [keep_p, keep_q])
+            self._A, self._norm = A, None
 
-        def _block(self, blk, in_exact_order=True):
+        def _block(self, blk, in_exact_order=True, trans=False):
             # x(pinv) = b, L x = x, U x = x, b(q) = x (csparse.py:1470-1473) as ONE library call: in the rounding-equal order on
-            # forests of small components the two permutations ride on the two sweeps (csx_lusol_solve)
+            # forests of small components the two permutations ride on the two sweeps (csx_lusol_solve); trans: y = b(q),
+            # U' y = y, L' y = y, x = y(pinv) (csx_lusol_solve_trans)
             lib = _csx.lib()
             x = dvec(n, blk.k)
             with _Resident(L) as dL, _Resident(U) as dU:
-                pl, pu = _plan(dL, TRI_L), _plan(dU, TRI_U)      # (shared with the list-level cs_lsolve / cs_usolve on this factor: the order is set per solve)
+                # (shared with the list-level cs_lsolve / cs_usolve / cs_ltsolve / cs_utsolve on this factor: the order is set per solve)
+                if trans:
+                    p1, p2, fn, name = _plan(dU, TRI_UT), _plan(dL, TRI_LT), lib.csx_lusol_solve_trans, "csx_lusol_solve_trans"
+                else:
+                    p1, p2, fn, name = _plan(dL, TRI_L), _plan(dU, TRI_U), lib.csx_lusol_solve, "csx_lusol_solve"
                 fused = _csx.C.c_int(0)
                 try:
-                    for plan in (pl, pu):
+                    for plan in (p1, p2):
                         _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
-                    _csx.check(lib.csx_lusol_solve(pl, pu, hp, hq, blk.handle, x.handle, blk.k, _csx.C.byref(fused)), "csx_lusol_solve")
+                    _csx.check(fn(p1, p2, hp, hq, blk.handle, x.handle, blk.k, _csx.C.byref(fused)), name)
                 finally:
-                    lib.csx_tri_set_order(pl, 1)
-                    lib.csx_tri_set_order(pu, 1)
+                    lib.csx_tri_set_order(p1, 1)
+                    lib.csx_tri_set_order(p2, 1)
             self.last_fused = bool(fused.value)
             return blk
 
@@ -1476,18 +1525,24 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
                     out[name] = {"matrix_cores": bool(mc.value), "growth": g.value}
             return out
 
-        def solve(self, b, comm=None, nrhs=None):
+        def solve(self, b, comm=None, nrhs=None, trans=False):
+            trans = bool(trans)
             if comm is not None and comm.world > 1:
                 # every rank solves in the order the ROOT's right-hand side asks for
                 ex = comm.broadcast_object((exact if exact is not None else not isinstance(b, dvec)) if comm.rank == 0 else None, 0)
-                out, bhost = _solve_blocks_sharded(comm, b, nrhs, n, n, lambda blk: self._block(blk, ex))
+                out, bhost = _solve_blocks_sharded(comm, b, nrhs, n, n, lambda blk: self._block(blk, ex, trans))
                 if out is not None:
                     _write_back(bhost, out, n * out.k)
                 return True
             db, bhost = _vec_in(b, n, "b")
-            self._block(db, exact if exact is not None else not isinstance(b, dvec))
+            self._block(db, exact if exact is not None else not isinstance(b, dvec), trans)
             _write_back(bhost, db, n * db.k)
             return True
+
+        def condest(self):
+            if self._norm is None:
+                self._norm = cs_norm(self._A)
+            return _condest(self._norm, lambda v, t: self._block(dvec(v), True, t).numpy(), n)
 
     return _Solver()
 
@@ -2004,6 +2059,10 @@ def btf_factor(A, tol=1.0, seed=0):
     is solved in one order fixed by the factors: c = b(p); blocks from last to first, c_i -= F_ij z_j
     in cs_gaxpy's order, then the block's part of cs_ipvec(pinv), cs_lsolve(L), cs_usolve(U); x(q) = z.  Lists and
     blocks give the same bits, every run.  One launch per level for the blocks of at most 96 rows.
+    solve(b, trans=True) solves A' x = b: C' w = b(q) block lower triangular, x(p) = w; blocks highest level
+    first, for every column j c_j = b(q_j) - F(:, j)' w in F's column storage order, then the block's part of
+    cs_utsolve(U), cs_ltsolve(L), cs_pvec(pinv).  One order here too; its programs are made on the first transposed solve.
+    condest(): an estimate of cond_1(A): cs_norm(A) (cached) times Hager-Higham's estimate of |A^-1|_1 (LAPACK dlacn2).
     .factors: a btfn; .info(): the plan's counts; .factor_ms: wall-clock ms of dmperm, split, cs_lu(D), plan.  None when A is not CSC, not square, structurally singular
     (sprank < n), or cs_lu(D) returns None (a numerically singular block)."""
     if not CS_CSC(A) or A.m != A.n:
@@ -2053,6 +2112,10 @@ def btf_factor(A, tol=1.0, seed=0):
 
         def __init__(self):
             self._fin = weakref.finalize(self, _csx.free, plan)
+            # the plan makes the transposed solve's programs from these three on its first call: held while it lives, even
+            # when a read of fac.L / .U / .F has turned a lazily downloaded factor into host lists
+            self._keep = (L._dev, U._dev, F._dev)
+            self._A, self._norm = A, None
 
         def info(self):
             v = np.zeros(8, dtype=np.int64)
@@ -2060,11 +2123,25 @@ def btf_factor(A, tol=1.0, seed=0):
             return dict(zip(("blocks", "levels", "max_block", "lnz", "unz", "fnz", "large_blocks", "launches"),
                             v.tolist()))
 
-        def solve(self, b):
+        def solve(self, b, trans=False):
             db, bhost = _vec_in(b, n, "b")
             work = dvec(n, db.k)
-            _csx.check(_csx.lib().csx_btf_solve(plan, db.handle, work.handle, db.k), "csx_btf_solve")
+            if trans:
+                _csx.check(_csx.lib().csx_btf_solve_trans(plan, db.handle, work.handle, db.k), "csx_btf_solve_trans")
+            else:
+                _csx.check(_csx.lib().csx_btf_solve(plan, db.handle, work.handle, db.k), "csx_btf_solve")
             _write_back(bhost, db, n * db.k)
             return True
+
+        def condest(self):
+            if self._norm is None:
+                self._norm = cs_norm(self._A)
+
+            def one(v, t):
+                d = dvec(v)
+                self.solve(d, t)
+                return d.numpy()
+
+            return _condest(self._norm, one, n)
 
     return _Solver()

@@ -5,6 +5,11 @@
 // block c_i -= F_ij z_j in cs_gaxpy's order (ascending column, storage order inside a column; multiply and subtract
 // rounded separately); then the block's part of cs_ipvec(pinv), cs_lsolve(L), cs_usolve(U), operation for operation;
 // x(q) = z.  Blocks of one level read only z of lower levels, so a level is one launch.
+//
+// The transposed solve A' x = b: C' is block LOWER triangular, so C' w = b(q), x(p) = w runs the blocks
+// from first to last (highest level first): for every column j of a block c_j = b(q_j) - F(:, j)' w in F's column storage
+// order; then the block's part of cs_utsolve(U), cs_ltsolve(L), cs_pvec(pinv).  The same kernels run it (TRANS = true) on
+// programs built from the factors' own columns the first time it is asked for.
 #include <algorithm>
 
 #include "csx_internal.h"
@@ -26,10 +31,13 @@ struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (loc
     ~BtfLarge() {
         destroy(pl);
         destroy(pu);
+        destroy(put);
+        destroy(plt);
     }
     int32_t r0 = 0, nr = 0;
     Csc L, U;
     TriPlan *pl = nullptr, *pu = nullptr;
+    TriPlan *put = nullptr, *plt = nullptr;   // U' and L' (transposed solves, made on the first one)
 };
 
 struct BtfPlan {
@@ -46,6 +54,15 @@ struct BtfPlan {
     std::vector<int32_t> small_rows;     // [nlevels] largest small block of the level
     std::vector<std::vector<int32_t>> large_of_level;   // indices into large
     std::vector<std::unique_ptr<BtfLarge>> large;
+    // the transposed solve (btf_trans_plan, made on its first call from the factors the plan was made from -- held by the
+    // caller, looked up by handle then): column programs of U without its diagonal (storage order: the diagonal is last) and
+    // of L without its diagonal (storage order: the diagonal is first), indices as LDS offsets like the row programs; F's
+    // columns with their rows mapped through pinv (the work block holds v, w_i = v(pinv_i))
+    csx_handle_t hL = 0, hU = 0, hF = 0;
+    std::vector<int32_t> r_h, level_h;   // [nb + 1], [nb]
+    bool trans_ready = false;
+    DevBuf<int32_t> UTp, UTi, LTp, LTi, Fcp, Fci;
+    DevBuf<double> UTx, UTd, LTx, LTd, Fcx;
 };
 
 void destroy(BtfPlan *P) { delete P; }
@@ -122,9 +139,12 @@ static int split_device(const Csc *C, const std::vector<int32_t> &blk_h, Csc *D,
 
 // ------------------------------------------------------------------------------------------------- the plan --
 
-// Row i of L' (= column i of Lt, ascending column, the unit diagonal last) -> program row without the diagonal; row i
-// of U' (diagonal first) -> program row in descending column order.  Every column must lie in row i's block and on
-// the right side of the diagonal: *bad = 1 otherwise (the kernels index LDS by these columns).
+// TRANS = false, T the transpose of a factor: row i of L' (= column i of Lt, ascending column, the unit diagonal last) ->
+// program row without the diagonal; row i of U' (diagonal first) -> program row in descending column order.
+// TRANS = true, T the factor itself: column i of U (diagonal last) and column i of L (diagonal first) -> program row
+// without the diagonal, the other entries in storage order.  Every index must lie in row i's block and on the right side of
+// the diagonal: *bad = 1 otherwise (the kernels index LDS by these indices).
+template <bool TRANS>
 __global__ __launch_bounds__(256) void k_btf_strip(int32_t n, int upper, const int32_t *__restrict__ Tp,
                                                    const int32_t *__restrict__ Ti, const double *__restrict__ Tx,
                                                    const int32_t *__restrict__ row_r0, const int32_t *__restrict__ row_r1,
@@ -138,18 +158,20 @@ __global__ __launch_bounds__(256) void k_btf_strip(int32_t n, int upper, const i
     }
     const int32_t a = Tp[i], e = Tp[i + 1];
     Pp[i] = a - (int32_t)i;
+    const bool diag_first = TRANS ? !upper : upper;     // where the diagonal sits in T's column i
+    const bool above = TRANS ? !upper : upper;          // the other indices lie after i (else before)
     // (a row without its diagonal shifts the program of the rows after it: caught here before anything is written)
-    if (e <= a || (int64_t)a - i < 0 || (int64_t)e - i - 1 > (int64_t)Tp[n] - n || Ti[upper ? a : e - 1] != i) {
+    if (e <= a || (int64_t)a - i < 0 || (int64_t)e - i - 1 > (int64_t)Tp[n] - n || Ti[diag_first ? a : e - 1] != i) {
         *bad = 1;
         return;
     }
     const int32_t r0 = row_r0[i], r1 = row_r1[i];
-    Pd[i] = Tx[upper ? a : e - 1];
+    Pd[i] = Tx[diag_first ? a : e - 1];
     const int32_t cnt = e - a - 1;
     for (int32_t t = 0; t < cnt; t++) {
-        const int32_t src = upper ? e - 1 - t : a + t;
+        const int32_t src = TRANS ? (diag_first ? a + 1 + t : a + t) : (upper ? e - 1 - t : a + t);
         const int32_t j = Ti[src];
-        if (upper ? (j <= i || j >= r1) : (j >= i || j < r0)) *bad = 1;
+        if (above ? (j <= i || j >= r1) : (j >= i || j < r0)) *bad = 1;
         Pi[a - i + t] = (j - r0) * 64;
         Px[a - i + t] = Tx[src];
     }
@@ -164,6 +186,24 @@ __global__ __launch_bounds__(256) void k_btf_check_f(int32_t n, const int32_t *_
     for (int32_t t = Fp[i]; t < Fp[i + 1]; t++) {
         const int32_t j = Fi[t];
         if (j < row_r1[i] || j >= n || row_lev[j] >= row_lev[i]) *bad = 1;
+    }
+}
+
+// F's columns for the transposed solve: rows mapped through pinv; every row in a block of a higher level than column j's
+// (solved by an earlier launch when the levels run highest first)
+__global__ __launch_bounds__(256) void k_btf_tcols(int32_t n, const int32_t *__restrict__ Fp, const int32_t *__restrict__ Fi,
+                                                   const int32_t *__restrict__ pinv, const int32_t *__restrict__ row_lev,
+                                                   int32_t *__restrict__ Fci, int *bad) {
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    for (int32_t t = Fp[j]; t < Fp[j + 1]; t++) {
+        const int32_t i = Fi[t];
+        if (i < 0 || i >= n || row_lev[i] <= row_lev[j]) {
+            *bad = 1;
+            Fci[t] = 0;
+        } else {
+            Fci[t] = pinv[i];
+        }
     }
 }
 
@@ -182,19 +222,25 @@ static int block_factor(const Csc *M, int32_t r0, int32_t nr, Csc *out) {
     return CSX_OK;
 }
 
-static int strip(const Csc *M, bool upper, const int32_t *row_r0, const int32_t *row_r1, int *bad, DevBuf<int32_t> &Pp,
-                 DevBuf<int32_t> &Pi, DevBuf<double> &Px, DevBuf<double> &Pd) {
+// trans = false: row programs of M' (M transposed here); trans = true: column programs of M itself
+static int strip(const Csc *M, bool upper, bool trans, const int32_t *row_r0, const int32_t *row_r1, int *bad,
+                 DevBuf<int32_t> &Pp, DevBuf<int32_t> &Pi, DevBuf<double> &Px, DevBuf<double> &Pd) {
     hipStream_t s = ctx().stream;
     const int32_t n = M->n;
     Csc T;
-    CSX_TRY(transpose_device(M, true, &T));
-    const int64_t cnt = std::max<int64_t>(0, (int64_t)T.nnz - n);
+    if (!trans) CSX_TRY(transpose_device(M, true, &T));
+    const Csc *S = trans ? M : &T;
+    const int64_t cnt = std::max<int64_t>(0, (int64_t)S->nnz - n);
     CSX_TRY(Pp.alloc((size_t)n + 1));
     CSX_TRY(Pi.alloc((size_t)cnt));
     CSX_TRY(Px.alloc((size_t)cnt));
     CSX_TRY(Pd.alloc((size_t)n));
-    hipLaunchKernelGGL(k_btf_strip, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, T.p, T.i, T.x,
-                       row_r0, row_r1, Pp, Pi, Px, Pd, bad);
+    if (trans)
+        hipLaunchKernelGGL(k_btf_strip<true>, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, S->p, S->i,
+                           S->x, row_r0, row_r1, Pp, Pi, Px, Pd, bad);
+    else
+        hipLaunchKernelGGL(k_btf_strip<false>, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, n, upper ? 1 : 0, S->p, S->i,
+                           S->x, row_r0, row_r1, Pp, Pi, Px, Pd, bad);
     CSX_LAUNCH_CHECK();
     CSX_HIP(hipStreamSynchronize(s));
     return CSX_OK;
@@ -204,6 +250,10 @@ static int strip(const Csc *M, bool upper, const int32_t *row_r0, const int32_t 
 
 // Small blocks of one level: one wave per (block, tile of 64 right-hand sides), the block's rows of the tile in LDS,
 // one lane per right-hand side.  Every LDS slot a lane touches is in its own column of the tile: no barrier.
+// A solve: p the load map, (Fp, Fi, Fx) F's rows, (Lp ..) L's row programs (ascending), (Up ..) U's (descending), the
+// entries scattered by pinv.  TRANS: p = q, F's columns with rows through pinv, U''s then L''s programs in their places,
+// no scatter (W then holds v, w = v(pinv)).
+template <bool TRANS>
 __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ blocks, const int32_t *__restrict__ r,
                                                   const int32_t *__restrict__ p, const int32_t *__restrict__ pinv,
                                                   const int32_t *__restrict__ Fp, const int32_t *__restrict__ Fi,
@@ -220,6 +270,7 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
     const int32_t col = (int32_t)blockIdx.y * 64 + lane;
     const bool on = col < k;
     // c = b(p), minus the F terms (the z they read is final: lower levels), scattered by pinv into the tile
+    // (TRANS: c = b(q) minus F(:, j)' w, w final: higher levels; slot t)
     for (int32_t t = 0; t < nr; t++) {
         const int32_t i = r0 + t;
         double acc = on ? B[(int64_t)p[i] * k + col] : 0.0;
@@ -234,9 +285,9 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
                 acc = acc - prod;
             }
         }
-        X[(pinv[i] - r0) * 64 + lane] = acc;
+        X[(TRANS ? t : pinv[i] - r0) * 64 + lane] = acc;
     }
-    // cs_lsolve on the block: rows ascending, terms in ascending column
+    // cs_lsolve on the block: rows ascending, terms in ascending column (TRANS: cs_utsolve, terms in storage order)
     for (int32_t t = 0; t < nr; t++) {
         const int32_t i = r0 + t;
         double acc = X[t * 64 + lane];
@@ -247,7 +298,7 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
         }
         X[t * 64 + lane] = acc / Ld[i];
     }
-    // cs_usolve on the block: rows descending, terms in descending column
+    // cs_usolve on the block: rows descending, terms in descending column (TRANS: cs_ltsolve, terms in storage order)
     for (int32_t t = nr - 1; t >= 0; t--) {
         const int32_t i = r0 + t;
         double acc = X[t * 64 + lane];
@@ -263,6 +314,8 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
 }
 
 // The rows of a large block: W(pinv(i)) = b(p(i)) - F(i, :) z, one thread per (row, right-hand side)
+// (TRANS: W(j) = b(q(j)) - F(:, j)' w, p = q and F's columns)
+template <bool TRANS>
 __global__ __launch_bounds__(256) void k_btf_rows(int32_t r0, int32_t nr, const int32_t *__restrict__ p,
                                                   const int32_t *__restrict__ pinv, const int32_t *__restrict__ Fp,
                                                   const int32_t *__restrict__ Fi, const double *__restrict__ Fx,
@@ -275,16 +328,17 @@ __global__ __launch_bounds__(256) void k_btf_rows(int32_t r0, int32_t nr, const 
         const double prod = Fx[t] * W[(int64_t)Fi[t] * k + col];
         acc = acc - prod;
     }
-    W[(int64_t)pinv[i] * k + col] = acc;
+    W[(int64_t)(TRANS ? i : pinv[i]) * k + col] = acc;
 }
 
-// x(q) = z
-__global__ __launch_bounds__(256) void k_btf_out(int32_t n, const int32_t *__restrict__ q, const double *__restrict__ W,
-                                                 double *__restrict__ B, int32_t k) {
+// x(q) = z   (TRANS: x(p) = w = v(pinv), q = p)
+template <bool TRANS>
+__global__ __launch_bounds__(256) void k_btf_out(int32_t n, const int32_t *__restrict__ q, const int32_t *__restrict__ pinv,
+                                                 const double *__restrict__ W, double *__restrict__ B, int32_t k) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= (int64_t)n * k) return;
     const int32_t t = (int32_t)(g / k), col = (int32_t)(g % k);
-    B[(int64_t)q[t] * k + col] = W[g];
+    B[(int64_t)q[t] * k + col] = TRANS ? W[(int64_t)pinv[t] * k + col] : W[g];
 }
 
 static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32_t k) {
@@ -294,15 +348,15 @@ static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32
         const int32_t a = P->small_ptr[l], e = P->small_ptr[l + 1];
         if (e > a) {
             const size_t lds = (size_t)P->small_rows[l] * 64 * sizeof(double);
-            hipLaunchKernelGGL(k_btf_small, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->p,
+            hipLaunchKernelGGL(k_btf_small<false>, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->p,
                                P->pinv, P->Ft.p, P->Ft.i, P->Ft.x, P->Lp, P->Li, P->Lx, P->Ld, P->Up, P->Ui, P->Ux, P->Ud, B,
                                W, k);
             CSX_LAUNCH_CHECK();
         }
         for (int32_t li : P->large_of_level[l]) {
             BtfLarge *G = P->large[li].get();
-            hipLaunchKernelGGL(k_btf_rows, dim3(grid_for((int64_t)G->nr * k)), dim3(256), 0, s, G->r0, G->nr, P->p, P->pinv,
-                               P->Ft.p, P->Ft.i, P->Ft.x, B, W, k);
+            hipLaunchKernelGGL(k_btf_rows<false>, dim3(grid_for((int64_t)G->nr * k)), dim3(256), 0, s, G->r0, G->nr, P->p,
+                               P->pinv, P->Ft.p, P->Ft.i, P->Ft.x, B, W, k);
             CSX_LAUNCH_CHECK();
             double *Wb = W + (int64_t)G->r0 * k;
             CSX_TRY(tri_solve_raw(G->pl, Wb, k, false));
@@ -310,7 +364,82 @@ static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32
         }
     }
     if (P->n)
-        hipLaunchKernelGGL(k_btf_out, dim3(grid_for((int64_t)P->n * k)), dim3(256), 0, s, P->n, P->q, W, Bout, k);
+        hipLaunchKernelGGL(k_btf_out<false>, dim3(grid_for((int64_t)P->n * k)), dim3(256), 0, s, P->n, P->q, nullptr, W, Bout,
+                           k);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
+// The transposed solve's programs, from the factors the plan was made from (CSX_EINVAL when one of them is gone or does not
+// pass the checks).  Nothing of it exists until the first transposed solve: btf_factor's time and memory stay as they were.
+static int btf_trans_plan(BtfPlan *P) {
+    if (P->trans_ready) return CSX_OK;
+    Csc *L = csc(P->hL), *U = csc(P->hU), *F = csc(P->hF);
+    const int32_t n = P->n, nb = P->nb;
+    if (!L || !U || !F || !L->x || !U->x || !F->x || L->n != n || U->n != n || F->n != n || L->m != n || U->m != n || F->m != n)
+        return CSX_EINVAL;
+    hipStream_t s = ctx().stream;
+    std::vector<int32_t> r0h((size_t)n), r1h((size_t)n), levh((size_t)n);
+    for (int32_t b = 0; b < nb; b++)
+        for (int32_t i = P->r_h[b]; i < P->r_h[b + 1]; i++) {
+            r0h[i] = P->r_h[b];
+            r1h[i] = P->r_h[b + 1];
+            levh[i] = P->level_h[b];
+        }
+    DevBuf<int32_t> row_r0, row_r1, row_lev;
+    DevBuf<int> bad;
+    CSX_TRY(upload(row_r0, r0h));
+    CSX_TRY(upload(row_r1, r1h));
+    CSX_TRY(upload(row_lev, levh));
+    CSX_TRY(bad.alloc(1));
+    CSX_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    CSX_TRY(strip(U, true, true, row_r0, row_r1, bad, P->UTp, P->UTi, P->UTx, P->UTd));
+    CSX_TRY(strip(L, false, true, row_r0, row_r1, bad, P->LTp, P->LTi, P->LTx, P->LTd));
+    CSX_TRY(P->Fcp.alloc((size_t)n + 1));
+    CSX_TRY(P->Fci.alloc((size_t)F->nnz));
+    CSX_TRY(P->Fcx.alloc((size_t)F->nnz));
+    CSX_HIP(hipMemcpyAsync(P->Fcp, F->p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (F->nnz) CSX_HIP(hipMemcpyAsync(P->Fcx, F->x, (size_t)F->nnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n) hipLaunchKernelGGL(k_btf_tcols, dim3(grid_for(n)), dim3(256), 0, s, n, F->p, F->i, P->pinv, row_lev, P->Fci, bad);
+    CSX_LAUNCH_CHECK();
+    int hbad = 0;
+    CSX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    if (hbad) return CSX_EINVAL;
+    for (const std::unique_ptr<BtfLarge> &G : P->large) {
+        if (!G->put) CSX_TRY(tri_analyse_raw(&G->U, CSX_TRI_UT, &G->put));
+        if (!G->plt) CSX_TRY(tri_analyse_raw(&G->L, CSX_TRI_LT, &G->plt));
+    }
+    CSX_HIP(hipStreamSynchronize(s));
+    P->trans_ready = true;
+    return CSX_OK;
+}
+
+static int btf_solve_trans(BtfPlan *P, const double *B, double *W, double *Bout, int32_t k) {
+    hipStream_t s = ctx().stream;
+    const unsigned tiles = (unsigned)((k + 63) / 64);
+    for (int32_t l = P->nlevels - 1; l >= 0; l--) {
+        const int32_t a = P->small_ptr[l], e = P->small_ptr[l + 1];
+        if (e > a) {
+            const size_t lds = (size_t)P->small_rows[l] * 64 * sizeof(double);
+            hipLaunchKernelGGL(k_btf_small<true>, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->q,
+                               P->pinv, P->Fcp, P->Fci, P->Fcx, P->UTp, P->UTi, P->UTx, P->UTd, P->LTp, P->LTi, P->LTx, P->LTd,
+                               B, W, k);
+            CSX_LAUNCH_CHECK();
+        }
+        for (int32_t li : P->large_of_level[l]) {
+            BtfLarge *G = P->large[li].get();
+            hipLaunchKernelGGL(k_btf_rows<true>, dim3(grid_for((int64_t)G->nr * k)), dim3(256), 0, s, G->r0, G->nr, P->q,
+                               P->pinv, P->Fcp, P->Fci, P->Fcx, B, W, k);
+            CSX_LAUNCH_CHECK();
+            double *Wb = W + (int64_t)G->r0 * k;
+            CSX_TRY(tri_solve_raw(G->put, Wb, k, false));
+            CSX_TRY(tri_solve_raw(G->plt, Wb, k, false));
+        }
+    }
+    if (P->n)
+        hipLaunchKernelGGL(k_btf_out<true>, dim3(grid_for((int64_t)P->n * k)), dim3(256), 0, s, P->n, P->p, P->pinv, W, Bout,
+                           k);
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
@@ -478,8 +607,8 @@ extern "C" int csx_btf_plan(csx_handle_t hL, csx_handle_t hU, csx_handle_t hF, c
     CSX_TRY(upload(P->pinv, pinv, (size_t)n));
     CSX_TRY(upload(P->r, r, (size_t)nb + 1));
     CSX_TRY(upload(P->small, small_h));
-    CSX_TRY(strip(L, false, row_r0, row_r1, bad, P->Lp, P->Li, P->Lx, P->Ld));
-    CSX_TRY(strip(U, true, row_r0, row_r1, bad, P->Up, P->Ui, P->Ux, P->Ud));
+    CSX_TRY(strip(L, false, false, row_r0, row_r1, bad, P->Lp, P->Li, P->Lx, P->Ld));
+    CSX_TRY(strip(U, true, false, row_r0, row_r1, bad, P->Up, P->Ui, P->Ux, P->Ud));
     CSX_TRY(transpose_device(F, true, &P->Ft));
     if (n) hipLaunchKernelGGL(k_btf_check_f, dim3(grid_for(n)), dim3(256), 0, s, n, P->Ft.p, P->Ft.i, row_r1, row_lev, bad);
     int hbad = 0;
@@ -489,6 +618,11 @@ extern "C" int csx_btf_plan(csx_handle_t hL, csx_handle_t hU, csx_handle_t hF, c
     P->lnz = L->nnz;
     P->unz = U->nnz;
     P->fnz = F->nnz;
+    P->hL = hL;
+    P->hU = hU;
+    P->hF = hF;
+    P->r_h.assign(r, r + nb + 1);
+    P->level_h.assign(level, level + nb);
     for (const std::unique_ptr<BtfLarge> &G : P->large) {
         CSX_TRY(block_factor(L, G->r0, G->nr, &G->L));
         CSX_TRY(block_factor(U, G->r0, G->nr, &G->U));
@@ -508,6 +642,17 @@ extern "C" int csx_btf_solve(csx_handle_t h, csx_handle_t hB, csx_handle_t hW, i
     const int64_t need = (int64_t)P->n * nrhs;
     if (B->len < need || W->len < need) return CSX_EINVAL;
     return btf_solve(P, (const double *)B->d, (double *)W->d, (double *)B->d, nrhs);
+}
+
+extern "C" int csx_btf_solve_trans(csx_handle_t h, csx_handle_t hB, csx_handle_t hW, int32_t nrhs) {
+    CSX_TRY(require_ready());
+    BtfPlan *P = (BtfPlan *)get(h, K_BTFPLAN);
+    Vec *B = vec(hB), *W = vec(hW);
+    if (!P || !B || !W || B == W || nrhs < 1) return CSX_EINVAL;
+    const int64_t need = (int64_t)P->n * nrhs;
+    if (B->len < need || W->len < need) return CSX_EINVAL;
+    CSX_TRY(btf_trans_plan(P));
+    return btf_solve_trans(P, (const double *)B->d, (double *)W->d, (double *)B->d, nrhs);
 }
 
 extern "C" int csx_btf_info(csx_handle_t h, int64_t *info) {

@@ -2601,6 +2601,112 @@ __global__ __launch_bounds__(256) void k_invert_perm(const int32_t *__restrict__
     if (k < n && (uint32_t)p[k] < (uint32_t)n) inv[p[k]] = (int32_t)k;      // (an entry out of range is the caller's error: no write outside)
 }
 
+// The body of csx_lusol_solve and csx_lusol_solve_trans: B (n-by-nrhs) -> P1 then P2 solved, B overwritten.  The rows of the
+// first sweep are B's rows through `load` (row i reads B(load[i]); null: row i), the rows of the second sweep are written to
+// B through `store` (row i to B(store[i])).  load_inv: the map to load is the inverse of this permutation (made here, on
+// the device, by k_invert_perm); store_inv likewise.  The three tiers: (1) rounding-equal order, nrhs > 8, both factors
+// forests of small components: the two ragged matrix-core sweeps with the maps fused in; (2) exact order, nrhs > 32: the two
+// in-LDS sweeps with the same maps; (3) otherwise a k_permute gather, the two triangular solves, a k_permute scatter or gather.
+static int lusol_two_sweeps(TriPlan *P1, TriPlan *P2, const int32_t *load, bool load_inv, const int32_t *store, bool store_inv,
+                            double *b, double *x, int32_t nrhs, int *fused) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = P1->n;
+    const int64_t total = (int64_t)n * nrhs;
+    // the maps as the fused sweeps take them (row i of the first sweep reads B(lmap[i]); row i of the second writes B(smap[i]))
+    DevBuf<int32_t> inv;
+    const int32_t *lmap = load_inv ? nullptr : load, *smap = store_inv ? nullptr : store;
+    auto make_maps = [&]() -> int {
+        const int32_t *src = load_inv ? load : store_inv ? store : nullptr;
+        if (!src) return CSX_OK;
+        CSX_TRY(inv.alloc((size_t)n));
+        CSX_HIP(hipMemsetAsync(inv, 0, (size_t)n * sizeof(int32_t), s));      // (not a permutation: rows never named read row 0)
+        hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, src, n, inv);
+        CSX_LAUNCH_CHECK();
+        if (load_inv) lmap = inv;
+        else smap = inv;
+        return CSX_OK;
+    };
+    if (ctx().opt.tri_components && P1->rounding_equal && P2->rounding_equal && nrhs > 8) {
+        CSX_TRY(analyse_components(P1));
+        CSX_TRY(analyse_components(P2));
+        if (P1->comp_ok && P2->comp_ok) {
+            CSX_TRY(components_ragged(P1));
+            CSX_TRY(components_ragged(P2));
+        }
+        if (P1->comp_ok && P2->comp_ok && P1->rag && P2->rag) {
+            CSX_TRY(make_maps());
+            CSX_TRY(ragged_solve_io(P1->rag.get(), P1->comp_nodes, lmap, nullptr, !P1->forward, 1, b, x, nrhs, n));
+            CSX_TRY(ragged_solve_io(P2->rag.get(), P2->comp_nodes, nullptr, smap, !P2->forward, 1, x, b, nrhs, n));
+            if (fused) *fused = 1;
+            return CSX_OK;
+        }
+    }
+    if (ctx().opt.tri_components && !P1->rounding_equal && !P2->rounding_equal && nrhs > 32) {
+        // the exact order on forests of small components: the same fusion through the in-LDS sweeps (k_tri_local reads and writes a
+        // component's rows through the row maps); the arithmetic and its order are those of the separate steps, bit for bit
+        CSX_TRY(analyse_components(P1));
+        CSX_TRY(analyse_components(P2));
+        if (P1->comp_ok && P2->comp_ok) {
+            CSX_TRY(make_maps());
+            bool took = false;
+            const TriIO io1{b, lmap, nullptr};
+            CSX_TRY(solve_components(P1, x, nrhs, &io1, &took));
+            if (took) {
+                const TriIO io2{x, nullptr, smap};
+                CSX_TRY(solve_components(P2, b, nrhs, &io2, &took));     // (same plan shape, same nrhs: taken too)
+                if (took) {
+                    if (fused) *fused = 1;
+                    return CSX_OK;
+                }
+                // (not taken after all: x holds the first sweep's solution of the permuted block -- finish with the separate steps)
+                CSX_TRY(tri_solve_raw(P2, x, nrhs, false));
+                hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, store, (const double *)x, b, n,
+                                   nrhs, store_inv ? 0 : 1);
+                CSX_LAUNCH_CHECK();
+                return CSX_OK;
+            }
+        }
+    }
+    hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, load, (const double *)b, x, n, nrhs,
+                       load_inv ? 1 : 0);
+    CSX_LAUNCH_CHECK();
+    static const bool relaxed_env = ablation_env("CSX_TRI_RELAXED") != nullptr;   // experiments only
+    CSX_TRY(tri_solve_raw(P1, x, nrhs, relaxed_env));
+    CSX_TRY(tri_solve_raw(P2, x, nrhs, relaxed_env));
+    hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, store, (const double *)x, b, n, nrhs,
+                       store_inv ? 0 : 1);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
+// The checks common to both entry points (kind1 / kind2: the kinds the plans must have, 0: any); *P1, *P2, *pinv, *q, *b, *x
+// set when *go comes back true, false when there is nothing to do.
+static int lusol_args(csx_handle_t h1, csx_handle_t h2, int kind1, int kind2, csx_handle_t hpinv, csx_handle_t hq, csx_handle_t hB,
+                      csx_handle_t hWork, int32_t nrhs, int *fused, TriPlan **P1, TriPlan **P2, const int32_t **pinv, const int32_t **q, double **b,
+                      double **x, bool *go) {
+    CSX_TRY(require_ready());
+    *go = false;
+    TriPlan *A = (TriPlan *)get(h1, K_TRIPLAN), *B2 = (TriPlan *)get(h2, K_TRIPLAN);
+    Vec *B = vec(hB), *W = vec(hWork);
+    Vec *pv = hpinv ? ivec(hpinv) : nullptr, *qv = hq ? ivec(hq) : nullptr;
+    if (fused) *fused = 0;
+    if (!A || !B2 || !B || !W || nrhs < 0 || A->n != B2->n || B->d == W->d) return CSX_EINVAL;
+    if ((kind1 && A->kind != kind1) || (kind2 && B2->kind != kind2)) return CSX_EINVAL;
+    const int32_t n = A->n;
+    if ((hpinv && (!pv || pv->len < n)) || (hq && (!qv || qv->len < n))) return CSX_EINVAL;
+    if (B->len < (int64_t)n * nrhs || W->len < (int64_t)n * nrhs) return CSX_EINVAL;
+    if (n == 0 || nrhs == 0) return CSX_OK;
+    if (A->zero_pivot || B2->zero_pivot) return CSX_EZEROPIVOT;
+    *P1 = A;
+    *P2 = B2;
+    *pinv = pv ? (const int32_t *)pv->d : nullptr;
+    *q = qv ? (const int32_t *)qv->d : nullptr;
+    *b = (double *)B->d;
+    *x = (double *)W->d;
+    *go = true;
+    return CSX_OK;
+}
+
 // cs_lusol's solve phase for a block of right-hand sides (csparse.py:1470-1473): x = P b (cs_ipvec with pinv), L x = x, U x = x,
 // b = Q x (cs_ipvec with q), B overwritten with the solutions.  When both factors are forests of small components in the
 // rounding-equal order (csx_tri_set_order) the permutations are FUSED into the sweeps: the sweep over L gathers its rows out of B
@@ -2609,79 +2715,27 @@ __global__ __launch_bounds__(256) void k_invert_perm(const int32_t *__restrict__
 // after the other, exactly what csx_permute_vec + csx_tri_solve + csx_tri_solve + csx_permute_vec do.  *fused says which.
 extern "C" int csx_lusol_solve(csx_handle_t hL, csx_handle_t hU, csx_handle_t hpinv, csx_handle_t hq, csx_handle_t hB,
                                csx_handle_t hWork, int32_t nrhs, int *fused) {
-    CSX_TRY(require_ready());
-    TriPlan *PL = (TriPlan *)get(hL, K_TRIPLAN), *PU = (TriPlan *)get(hU, K_TRIPLAN);
-    Vec *B = vec(hB), *W = vec(hWork);
-    Vec *pv = hpinv ? ivec(hpinv) : nullptr, *qv = hq ? ivec(hq) : nullptr;
-    if (fused) *fused = 0;
-    if (!PL || !PU || !B || !W || nrhs < 0 || PL->n != PU->n || B->d == W->d) return CSX_EINVAL;
-    const int32_t n = PL->n;
-    if ((hpinv && (!pv || pv->len < n)) || (hq && (!qv || qv->len < n))) return CSX_EINVAL;
-    if (B->len < (int64_t)n * nrhs || W->len < (int64_t)n * nrhs) return CSX_EINVAL;
-    if (n == 0 || nrhs == 0) return CSX_OK;
-    if (PL->zero_pivot || PU->zero_pivot) return CSX_EZEROPIVOT;
-    hipStream_t s = ctx().stream;
-    const int32_t *pinv = pv ? (const int32_t *)pv->d : nullptr, *q = qv ? (const int32_t *)qv->d : nullptr;
-    double *b = (double *)B->d, *x = (double *)W->d;
-    const int64_t total = (int64_t)n * nrhs;
-    if (ctx().opt.tri_components && PL->rounding_equal && PU->rounding_equal && nrhs > 8) {
-        CSX_TRY(analyse_components(PL));
-        CSX_TRY(analyse_components(PU));
-        if (PL->comp_ok && PU->comp_ok) {
-            CSX_TRY(components_ragged(PL));
-            CSX_TRY(components_ragged(PU));
-        }
-        if (PL->comp_ok && PU->comp_ok && PL->rag && PU->rag) {
-            DevBuf<int32_t> invp;
-            if (pinv) {
-                CSX_TRY(invp.alloc((size_t)n));
-                CSX_HIP(hipMemsetAsync(invp, 0, (size_t)n * sizeof(int32_t), s));      // (not a permutation: rows never named read row 0)
-                hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, pinv, n, invp);
-                CSX_LAUNCH_CHECK();
-            }
-            CSX_TRY(ragged_solve_io(PL->rag.get(), PL->comp_nodes, invp, nullptr, !PL->forward, 1, b, x, nrhs, n));
-            CSX_TRY(ragged_solve_io(PU->rag.get(), PU->comp_nodes, nullptr, q, !PU->forward, 1, x, b, nrhs, n));
-            if (fused) *fused = 1;
-            return CSX_OK;
-        }
-    }
-    if (ctx().opt.tri_components && !PL->rounding_equal && !PU->rounding_equal && nrhs > 32) {
-        // the exact order on forests of small components: the same fusion through the in-LDS sweeps (k_tri_local reads and writes a
-        // component's rows through the row maps); the arithmetic and its order are those of the separate steps, bit for bit
-        CSX_TRY(analyse_components(PL));
-        CSX_TRY(analyse_components(PU));
-        if (PL->comp_ok && PU->comp_ok) {
-            DevBuf<int32_t> invp;
-            if (pinv) {
-                CSX_TRY(invp.alloc((size_t)n));
-                CSX_HIP(hipMemsetAsync(invp, 0, (size_t)n * sizeof(int32_t), s));
-                hipLaunchKernelGGL(k_invert_perm, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, pinv, n, invp);
-                CSX_LAUNCH_CHECK();
-            }
-            bool took = false;
-            const TriIO ioL{b, invp, nullptr};
-            CSX_TRY(solve_components(PL, x, nrhs, &ioL, &took));
-            if (took) {
-                const TriIO ioU{x, nullptr, q};
-                CSX_TRY(solve_components(PU, b, nrhs, &ioU, &took));     // (same plan shape, same nrhs: taken too)
-                if (took) {
-                    if (fused) *fused = 1;
-                    return CSX_OK;
-                }
-                // (not taken after all: x holds L's solution of the permuted block -- finish with the separate steps)
-                CSX_TRY(tri_solve_raw(PU, x, nrhs, false));
-                hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, (const double *)x, b, n, nrhs, 1);
-                CSX_LAUNCH_CHECK();
-                return CSX_OK;
-            }
-        }
-    }
-    hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pinv, (const double *)b, x, n, nrhs, 1);
-    CSX_LAUNCH_CHECK();
-    static const bool relaxed_env = ablation_env("CSX_TRI_RELAXED") != nullptr;   // experiments only
-    CSX_TRY(tri_solve_raw(PL, x, nrhs, relaxed_env));
-    CSX_TRY(tri_solve_raw(PU, x, nrhs, relaxed_env));
-    hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, (const double *)x, b, n, nrhs, 1);
-    CSX_LAUNCH_CHECK();
-    return CSX_OK;
+    TriPlan *PL = nullptr, *PU = nullptr;
+    const int32_t *pinv = nullptr, *q = nullptr;
+    double *b = nullptr, *x = nullptr;
+    bool go = false;
+    CSX_TRY(lusol_args(hL, hU, 0, 0, hpinv, hq, hB, hWork, nrhs, fused, &PL, &PU, &pinv, &q, &b, &x, &go));
+    if (!go) return CSX_OK;
+    // row i of L's sweep reads B(p(i)), p = inverse(pinv); row i of U's sweep is written to B(q(i))
+    return lusol_two_sweeps(PL, PU, pinv, true, q, false, b, x, nrhs, fused);
+}
+
+// The transposed solve A' x = b on the same factors (L U = A(p, q)): y = b(q) (cs_pvec with q), U' y = y, L' y = y, x = y(pinv)
+// (cs_pvec with pinv).  planUT: a CSX_TRI_UT plan of U, planLT: a CSX_TRI_LT plan of L.  The same three tiers as csx_lusol_solve:
+// the sweep over U' loads its rows through q, the sweep over L' stores its rows through p = inverse(pinv).
+extern "C" int csx_lusol_solve_trans(csx_handle_t hUT, csx_handle_t hLT, csx_handle_t hpinv, csx_handle_t hq, csx_handle_t hB,
+                                     csx_handle_t hWork, int32_t nrhs, int *fused) {
+    TriPlan *PUT = nullptr, *PLT = nullptr;
+    const int32_t *pinv = nullptr, *q = nullptr;
+    double *b = nullptr, *x = nullptr;
+    bool go = false;
+    CSX_TRY(lusol_args(hUT, hLT, CSX_TRI_UT, CSX_TRI_LT, hpinv, hq, hB, hWork, nrhs, fused, &PUT, &PLT, &pinv, &q, &b, &x, &go));
+    if (!go) return CSX_OK;
+    // row i of U''s sweep reads B(q(i)); row i of L''s sweep is written to B(p(i)): x(p) = y, i.e. x = y(pinv)
+    return lusol_two_sweeps(PUT, PLT, q, false, pinv, true, b, x, nrhs, fused);
 }

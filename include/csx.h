@@ -224,6 +224,12 @@ int csx_permute_vec(csx_handle_t p, csx_handle_t b, csx_handle_t x, int32_t n, i
  * sweeps (four passes over the block instead of eight): *fused = 1.  Otherwise the four steps run one after the other. */
 int csx_lusol_solve(csx_handle_t planL, csx_handle_t planU, csx_handle_t pinv, csx_handle_t q, csx_handle_t b, csx_handle_t work,
                     int32_t nrhs, int *fused);
+/* The transposed solve A' x = b on the same factors (L U = A(p, q)): y = b(q) (cs_pvec), cs_utsolve(U),
+ * cs_ltsolve(L), x = y(pinv) (cs_pvec).  planUT / planLT: csx_tri_analyse plans of U (CSX_TRI_UT) and L (CSX_TRI_LT); the
+ * rest as csx_lusol_solve, the same validation and errors (CSX_EINVAL also for plans of another kind).  Fused (*fused = 1)
+ * in the same cases: the sweep over U' loads its rows through q, the sweep over L' stores them through p = inverse(pinv). */
+int csx_lusol_solve_trans(csx_handle_t planUT, csx_handle_t planLT, csx_handle_t pinv, csx_handle_t q, csx_handle_t b,
+                          csx_handle_t work, int32_t nrhs, int *fused);
 
 /* cs_schol (natural order), csparse.py:2051-2072: host C++ symbolic analysis of
  * the upper triangle of a host CSC pattern.  parent[n], cp[n+1]. */
@@ -505,7 +511,9 @@ int csx_dmperm_rounds(int64_t *rounds);
  *   *nlevels, and the NEW matrix handles *D and *F.  Level analysis on the host (one pass over A's pattern), the
  *   permutation and the split on the device.
  * csx_btf_plan: a NEW plan handle (freed by csx_free) from L, U (cs_lu of D), F and the host arrays pinv (n), p, q (n),
- *   r (nb + 1), level (nb) that csx_btf_split returned.  The plan keeps copies of everything it reads.  Blocks of at
+ *   r (nb + 1), level (nb) that csx_btf_split returned.  The plan keeps copies of everything the forward solve reads, and
+ *   the handles L, U, F for the transposed solve's programs (made on its first call: the caller keeps the three alive
+ *   while it may ask for one).  Blocks of at
  *   most 96 rows are solved one wave per (block, 64 right-hand sides) with the tile in LDS, one launch per level;
  *   larger blocks by a product with F over their rows and csx_tri_analyse-style exact plans of their own parts of L
  *   and U (a few launches each).
@@ -524,6 +532,12 @@ int csx_btf_split(csx_handle_t A, const int32_t *p, const int32_t *q, const int3
 int csx_btf_plan(csx_handle_t L, csx_handle_t U, csx_handle_t F, const int32_t *pinv, const int32_t *p, const int32_t *q,
                  const int32_t *r, const int32_t *level, int32_t nb, csx_handle_t *plan);
 int csx_btf_solve(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t nrhs);
+/* csx_btf_solve_trans: B overwritten with the X of A' X = B: C' w = b(q) block lower triangular, blocks by
+ *   level from the highest; per column j of a block c_j = b(q_j) - F(:, j)' w in F's column storage order, then the block's
+ *   part of cs_utsolve(U), cs_ltsolve(L), cs_pvec(pinv); x(p) = w.  The first call builds the column programs of U, L and F
+ *   from the plan's L, U, F handles (CSX_EINVAL when one is gone, when a column of U lacks its diagonal last or one of L its
+ *   diagonal first, or an index leaves its block or its side); the same kernels as csx_btf_solve, one launch per level. */
+int csx_btf_solve_trans(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t nrhs);
 int csx_btf_info(csx_handle_t plan, int64_t *info);
 
 /* ---- synthetic inputs of the benchmark configs, generated on
