@@ -1,12 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the CSparse.py hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 Headline (BASELINE.json metric): cs_gaxpy achieved HBM GB/s on the 5M x 5M,
-64-nnz-per-column matrix ("G-rand"), plus batched cs_cholsol
-solves/s on the 5M x 5M 64-nnz/row SPD matrix ("G-spd").  One "step" is one
+64-nnz-per-column matrix ("G-rand").  One "step" is one
 cs_gaxpy pass y += A x over the whole matrix.
+
+A plain run does what the headline needs and nothing more: it generates the
+matrix, picks the kernel (--mode auto: the faster of tiled and wave over three
+passes), warms up, times the steps, writes --dump-outputs and prints the line.
+Everything else is behind --full: the timed kernel checked against the
+reference-order kernel on the timed matrix, the spread of the headline over
+more trials, the other row draw, cs_gaxpy on G-spd, batched cs_cholsol solves/s
+on the 5M x 5M 64-nnz/row SPD matrix ("G-spd"), the exchange legs and the
+column-sharded SpMV at N > 1, BASELINE's other configs (bench_configs.py) and
+the CPU baselines.
 
 N > 1, one rank per GPU: either the driver starts the ranks (`python -m
 torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, WORLD_SIZE set) or
@@ -16,15 +25,15 @@ silent 1-GPU run.  The path shards as independent matrices / right-hand-side blo
 (SURVEY 8e): every rank owns its own matrix and its own RHS block, no collective in
 the timed headline region, which is bracketed by barriers and timed by the slowest
 rank ("weak").  The exchange steps SURVEY 8e names are measured as their own legs
-and reported under "exchange": factor once on rank 0 + RCCL broadcast of L.p / L.i /
-L.x against factoring redundantly, the RHS blocks leaving the root, the solution
-blocks gathered to the root.
+and reported under "exchange" (--full): factor once on rank 0 + RCCL broadcast of
+L.p / L.i / L.x against factoring redundantly, the RHS blocks leaving the root, the
+solution blocks gathered to the root.
 
 Rank 0 prints one JSON line.  `value` = algorithmic bytes of all ranks' steps /
 wall time.  `roofline.achieved` = algorithmic bytes of one step / average step
 duration measured with HIP events on the stream the kernels run on.
-`cpu_baseline` = the pure-Python port (oracle/csparse_oracle.py: the reference is
-pure Python, single-threaded) on a bounded sample of the same generator.
+`cpu_baseline` (--full) = the pure-Python port (oracle/csparse_oracle.py: the
+reference is pure Python, single-threaded) on a bounded sample of the same generator.
 `ms_per_step` = wall time of the timed region / --steps.  `--dump-outputs DIR`
 writes y of the last timed step to DIR (dump_outputs).
 """
@@ -280,6 +289,10 @@ def main():
     ap.add_argument("--per-col", type=int, default=64)
     ap.add_argument("--nrhs", type=int, default=128, help="right-hand sides per GPU for batched cs_cholsol")
     ap.add_argument("--mode", default="auto", choices=["auto", "wave", "tiled", "atomic"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every check and leg beside it (parity on the timed matrix, "
+                         "headline trials, other row draw, G-spd, cholsol, exchange, other configs, CPU baselines); "
+                         "--nrhs, --cpu-*, --skip-*, --force-sharded, --extras-deadline and --exchange-nrhs shape those")
     ap.add_argument("--cpu-n", type=int, default=100000)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-chol-blocks", type=int, default=2000, help="G-spd blocks in the CPU baseline of the cholsol leg")
@@ -291,7 +304,7 @@ def main():
     ap.add_argument("--force-sharded", action="store_true", help="run the column-sharded SpMV code path at N = 1 too")
     ap.add_argument("--gen", default="uniform", choices=["uniform", "stratified"],
                     help="G-rand row draw of the headline matrix: SURVEY 8d's uniform distinct rows (default) or one "
-                         "row per stratum of n/per_col rows (round 1's generator); the other one is timed beside it")
+                         "row per stratum of n/per_col rows (round 1's generator); --full times the other one beside it")
     ap.add_argument("--rehearse", action="store_true",
                     help="launcher and exchange plumbing only, on CPU tensors (gloo): no GPU, no kernels, value = null")
     ap.add_argument("--extras-deadline", type=float, default=420.0,
@@ -307,6 +320,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.force_sharded and not args.full:
+        ap.error("--force-sharded runs legs of --full: add --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))          # parent: starts the ranks, touches no GPU
@@ -389,27 +404,6 @@ def main():
     tr = measured_traffic({"tiled": "k_gaxpy_tiled<0,", "wave": "k_gaxpy_rows", "atomic": "k_gaxpy_atomic"}[chosen],
                           n=n, nnz=nnz, kernel="gaxpy_" + chosen)
 
-    # parity of the timed kernel ON THE TIMED MATRIX, after the timed region: one pass of the chosen kernel from y = 0
-    # against one pass of the reference-order kernel (GAXPY_EXACT: thread per row, terms in ascending (column, position)
-    # order, multiply and add rounded separately -- bit-identical to csparse.py:1210-1212, tests/test_gpu_parity.py).
-    hy1, hy2 = _csx.new_handle(), _csx.new_handle()
-    _csx.check(lib.csx_vec_alloc(n, hy1), "vec_alloc")
-    _csx.check(lib.csx_vec_alloc(n, hy2), "vec_alloc")
-    _csx.check(lib.csx_gaxpy(hA, hx, hy1, mode), "gaxpy check")
-    _csx.check(lib.csx_gaxpy(hA, hx, hy2, cs.GAXPY_EXACT), "gaxpy exact")
-    ya, ye = np.empty(n), np.empty(n)
-    _csx.check(lib.csx_vec_download(hy1, _csx.pd(ya), n), "vec_download")
-    _csx.check(lib.csx_vec_download(hy2, _csx.pd(ye), n), "vec_download")
-    for h in (hy1, hy2):
-        _csx.free(h)
-    nzr = ye > 0                                          # all-positive data; a row may be empty under the uniform draw
-    parity_err = float(np.max(np.abs(ya[nzr] - ye[nzr]) / ye[nzr])) if nzr.any() else 0.0
-    parity_ok = bool(np.all(np.isfinite(ye)) and np.all(ya[~nzr] == 0) and parity_err < 1e-12)
-    if not (parity_ok or os.environ.get("CSX_TILED_VARIANT")):
-        raise SystemExit("bench.py: the timed kernel disagrees with the reference-order kernel on the timed matrix "
-                         "(max relative error %.3e)" % parity_err)
-    del ya, ye
-
     try:
         rccl_ranks = comm.info()
     except Exception as e:                                # reported, never fatal
@@ -440,8 +434,6 @@ def main():
                      "step_ms_hip_events": round(step_ms_events, 4)},
         "gaxpy_trials_ms": {k: round(v["ms"], 4) for k, v in trial.items()},
         "gaxpy_prepare_s": {k: round(v["prepare_s"], 3) for k, v in trial.items()},
-        "parity_on_the_timed_matrix": {"against": "GAXPY_EXACT (reference summation order, csparse.py:1210-1212)",
-                                       "max_rel_err": parity_err, "tolerance": 1e-12, "ok": parity_ok},
     }
     if dumped:
         out["dumped_outputs"] = dumped
@@ -449,6 +441,36 @@ def main():
         out["config"]["plan_launch_shape"] = {"picked": ["4x5", "2x10", "8x4", "2x8"][shape.value],
                                               "ms_when_the_plan_was_built": {k: round(v, 4) for k, v in
                                                                              zip(("4x5", "2x10", "8x4", "2x8"), shape_ms)}}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        for h in (hA, hx, hy):
+            _csx.free(h)
+        comm.close()
+        return
+
+    # parity of the timed kernel ON THE TIMED MATRIX, after the timed region: one pass of the chosen kernel from y = 0
+    # against one pass of the reference-order kernel (GAXPY_EXACT: thread per row, terms in ascending (column, position)
+    # order, multiply and add rounded separately -- bit-identical to csparse.py:1210-1212, tests/test_gpu_parity.py).
+    hy1, hy2 = _csx.new_handle(), _csx.new_handle()
+    _csx.check(lib.csx_vec_alloc(n, hy1), "vec_alloc")
+    _csx.check(lib.csx_vec_alloc(n, hy2), "vec_alloc")
+    _csx.check(lib.csx_gaxpy(hA, hx, hy1, mode), "gaxpy check")
+    _csx.check(lib.csx_gaxpy(hA, hx, hy2, cs.GAXPY_EXACT), "gaxpy exact")
+    ya, ye = np.empty(n), np.empty(n)
+    _csx.check(lib.csx_vec_download(hy1, _csx.pd(ya), n), "vec_download")
+    _csx.check(lib.csx_vec_download(hy2, _csx.pd(ye), n), "vec_download")
+    for h in (hy1, hy2):
+        _csx.free(h)
+    nzr = ye > 0                                          # all-positive data; a row may be empty under the uniform draw
+    parity_err = float(np.max(np.abs(ya[nzr] - ye[nzr]) / ye[nzr])) if nzr.any() else 0.0
+    parity_ok = bool(np.all(np.isfinite(ye)) and np.all(ya[~nzr] == 0) and parity_err < 1e-12)
+    if not (parity_ok or os.environ.get("CSX_TILED_VARIANT")):
+        raise SystemExit("bench.py: the timed kernel disagrees with the reference-order kernel on the timed matrix "
+                         "(max relative error %.3e)" % parity_err)
+    del ya, ye
+    out["parity_on_the_timed_matrix"] = {"against": "GAXPY_EXACT (reference summation order, csparse.py:1210-1212)",
+                                         "max_rel_err": parity_err, "tolerance": 1e-12, "ok": parity_ok}
     # the spread of the headline with the device's state: three more trials of the same K steps, each behind a different
     # kernel (a transposing sort, the exact kernel, nothing), HIP-event timed.  `value` stays the contract's timed region.
     spread = []

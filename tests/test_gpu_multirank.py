@@ -26,7 +26,7 @@ def _clean_env(**kw):
 
 def test_bench_two_ranks_on_one_device():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "200000", "--steps", "3",
-                        "--warmup", "1", "--nrhs", "64"],
+                        "--warmup", "1", "--nrhs", "64", "--full"],
                        env=_clean_env(CSX_SINGLE_DEVICE="1", CSX_COMM_BACKEND="gloo"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -53,7 +53,7 @@ def test_exchange_legs_on_a_real_rccl_group_of_one():
     """CSX_FORCE_DIST: a real torch.distributed process group (backend nccl = RCCL) with one member, so the
     exchange legs run through RCCL's API on device tensors that are views of libcsx buffers."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", "200000", "--steps", "2",
-                        "--warmup", "1", "--nrhs", "64", "--force-sharded", "--skip-cpu", "--skip-configs"],
+                        "--warmup", "1", "--nrhs", "64", "--full", "--force-sharded", "--skip-cpu", "--skip-configs"],
                        env=_clean_env(CSX_FORCE_DIST="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                                       MASTER_ADDR="127.0.0.1", MASTER_PORT="29671"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
