@@ -136,6 +136,12 @@ _PROTOS = {
     "csx_btf_solve": [H, H, H, C.c_int32],
     "csx_btf_solve_trans": [H, H, H, C.c_int32],
     "csx_btf_info": [H, C.POINTER(C.c_int64)],
+    "csx_btf_refactor": [H, H, H, H, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int64)],
+    "csx_btf_refactor_dx": [H, _f64p],
+    "csx_lu_refactor_plan": [H, H, H, _i32p, _i32p, C.POINTER(H)],
+    "csx_lu_refactor": [H, H, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int64)],
+    "csx_lu_refactor_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p,
+                             C.POINTER(C.c_int), _f64p],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

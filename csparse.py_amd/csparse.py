@@ -1453,6 +1453,66 @@ def _condest(norm_a, solve, n):
     return float(norm_a) * max(est, temp)
 
 
+def _refactor_input(A, A2):
+    """A2 of a refactor of a factor of A: a CSC `cs` with A's m, n and entry count (its pattern is compared with A's on the
+    device) or nnz(A) values in A's storage order (numpy, list or dvec; copied).  ValueError otherwise."""
+    nnz = _meta(A)[0]
+    if isinstance(A2, cs):
+        if not CS_CSC(A2) or A2.m != A.m or A2.n != A.n or _meta(A2) != (nnz, True):
+            raise ValueError("refactor: A2 does not have the pattern of the factored matrix")
+        return A2
+    v = A2.copy() if isinstance(A2, dvec) else dvec(np.asarray(A2, dtype=np.float64).ravel())
+    if v.n * v.k != nnz:
+        raise ValueError("refactor: %d values given, the factored matrix has %d entries" % (v.n * v.k, nnz))
+    return v
+
+
+def _refactor_call(A2, fn, ok):
+    """fn(handle of A2) -> status; ok = -1 after it: A2's pattern or length is not A's -> ValueError"""
+    if isinstance(A2, dvec):
+        st = fn(A2.handle)
+    else:
+        with _Resident(A2) as d:
+            st = fn(d.handle)
+    _csx.check(st, "refactor")
+    if ok.value == -1:
+        raise ValueError("refactor: A2 does not have the pattern of the factored matrix")
+
+
+def _refactored(M, dev):
+    """The values behind `cs` M (device copy dev) were replaced by a refactor: the triangular-solve plans cached on it hold the
+    old ones and go (solvers re-plan), and host lists already read from it are updated in place, as cs_updown does."""
+    for h in dev.plans.values():
+        _csx.free(h)
+    dev.plans.clear()
+    dev.version += 1
+    if not M._lazy and M._x is not None:
+        _, _, nnz, _ = dev.info()
+        x = np.empty(max(nnz, 1), dtype=np.float64)
+        _csx.check(_csx.lib().csx_csc_download(dev.handle, None, None, _csx.pd(x)), "csx_csc_download")
+        M._x[:nnz] = x[:nnz].tolist()
+
+
+def _refactor_norm(A, A2):
+    """cs_norm of the matrix a refactor installed, for condest(): A2 when it is a `cs`; else A's pattern with the values A2
+    (a dvec in A's storage order) -- column sums on the device over A's pattern, nothing copied to the host"""
+    if isinstance(A2, cs):
+        return cs_norm(A2)
+    C = _csx.C
+    with _Resident(A) as dA:
+        m, n, nnz, _ = dA.info()
+        dp, di, dx = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _csx.check(_csx.lib().csx_csc_ptrs(dA.handle, dp, di, dx), "csx_csc_ptrs")
+        h = _csx.new_handle()
+        _csx.check(_csx.lib().csx_csc_wrap(m, n, nnz, dp, di, C.c_void_p(A2.device_ptr()), h), "csx_csc_wrap")
+        try:
+            out = C.c_double(0.0)
+            _csx.check(_csx.lib().csx_norm1(h, out), "csx_norm1")
+        finally:
+            _csx.free(h)
+    return out.value
+
+
 def lusol_factor(A, order=0, tol=1.0, exact=None):
     """Factor once for many solves -- the batched form of cs_lusol (csparse.py:1456-1478): cs_sqr + cs_lu once, then
     solve(b) runs the reference's sequence x = b(p); L \\ x; U \\ x; b(q) = x (:1474-1477) on the device for a list (one
@@ -1470,6 +1530,13 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
     under the same rule for lists, blocks and `exact`; through comm= as well.
     condest(): an estimate of cond_1(A) = |A|_1 |A^-1|_1: cs_norm(A) (cached) times Hager-Higham's estimate of |A^-1|_1
     (LAPACK dlacn2's iteration) from exact-order single right-hand-side solves, forward and transposed.
+    refactor(A2): new values, the same pivots: A2 a CSC `cs` with A's exact pattern, or nnz(A) values in A's
+    storage order (numpy, list or dvec); ValueError for another pattern or length.  L and U get the values cs_lu's own loop
+    gives with this pinv (byte-equal to cs_lu(A2) whenever it would pivot the same), on the device for connected components
+    of at most 96 rows, on the host for the rest.  True on success; False when a kept pivot is 0 or not finite, and then
+    nothing changes.  The triangular-solve plans hold copies of the values: they are rebuilt by the next solve.
+    refactor_info(): the last refactor's pivot_ratio (min over the columns of |u_kk| / the largest candidate of its column),
+    device_columns, host_columns and ms.
     None when A is not square CSC or singular."""
     if not CS_CSC(A) or A.m != A.n:
         return None
@@ -1487,7 +1554,8 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
 
         def __init__(self):
             self._fin = weakref.finalize(self, lambda hs: [_csx.free(h) for h in hs if h is not None], [keep_p, keep_q])
-            self._A, self._norm = A, None
+            self._A2, self._norm = A, None         # the matrix condest() is about: A, or the last refactor's A2
+            self._rplan, self._rinfo = None, None
 
         def _block(self, blk, in_exact_order=True, trans=False):
             # x(pinv) = b, L x = x, U x = x, b(q) = x (csparse.py:1470-1473) as ONE library call: in the rounding-equal order on
@@ -1541,8 +1609,34 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
 
         def condest(self):
             if self._norm is None:
-                self._norm = cs_norm(self._A)
+                self._norm = _refactor_norm(A, self._A2)
             return _condest(self._norm, lambda v, t: self._block(dvec(v), True, t).numpy(), n)
+
+        def refactor(self, A2):
+            t0 = time.perf_counter()
+            A2 = _refactor_input(A, A2)
+            if self._rplan is None:
+                # the refactor's schedule and maps, on the first call only: nothing of it exists for a solver never refactored
+                h = _csx.new_handle()
+                q = None if S.q is None else _csx.i32(S.q)
+                with _Resident(L) as dL, _Resident(U) as dU, _Resident(A) as dA:
+                    _csx.check(_csx.lib().csx_lu_refactor_plan(dL.handle, dU.handle, dA.handle,
+                                                               None if q is None else _csx.pi(q), _csx.pi(_csx.i32(N.pinv)), h),
+                               "csx_lu_refactor_plan")
+                self._rplan = h
+                weakref.finalize(self, _csx.free, h)
+            ok, ratio, cols = _csx.C.c_int(0), _csx.C.c_double(0.0), (_csx.C.c_int64 * 2)()
+            _refactor_call(A2, lambda h: _csx.lib().csx_lu_refactor(self._rplan, h, ok, ratio, cols), ok)
+            if ok.value:
+                for M in (L, U):
+                    _refactored(M, M._dev)
+                self._A2, self._norm = A2, None
+            self._rinfo = {"ok": bool(ok.value), "pivot_ratio": ratio.value, "device_columns": int(cols[0]),
+                           "host_columns": int(cols[1]), "ms": 1e3 * (time.perf_counter() - t0)}
+            return bool(ok.value)
+
+        def refactor_info(self):
+            return dict(self._rinfo) if self._rinfo is not None else None
 
     return _Solver()
 
@@ -2063,8 +2157,16 @@ def btf_factor(A, tol=1.0, seed=0):
     first, for every column j c_j = b(q_j) - F(:, j)' w in F's column storage order, then the block's part of
     cs_utsolve(U), cs_ltsolve(L), cs_pvec(pinv).  One order here too; its programs are made on the first transposed solve.
     condest(): an estimate of cond_1(A): cs_norm(A) (cached) times Hager-Higham's estimate of |A^-1|_1 (LAPACK dlacn2).
-    .factors: a btfn; .info(): the plan's counts; .factor_ms: wall-clock ms of dmperm, split, cs_lu(D), plan.  None when A is not CSC, not square, structurally singular
-    (sprank < n), or cs_lu(D) returns None (a numerically singular block)."""
+    .factors: a btfn; .info(): the plan's counts; .factor_ms: wall-clock ms of dmperm, split, cs_lu(D), plan.
+    refactor(A2): new values, the same p, q, r, levels and pivots: A2 a CSC `cs` with A's exact pattern, or
+    nnz(A) values in A's storage order (numpy, list or dvec); ValueError for another pattern or length.  D and F are gathered
+    from A2 as the split does, L and U get the values cs_lu's own loop gives with this pinv (byte-equal to a fresh factor's
+    whenever cs_lu(D2) would pivot the same): one wave per block of at most 96 rows, the host for larger blocks.  The forward
+    programs are refreshed in place; the transposed ones are made again by the next transposed solve.  True on success;
+    False when a kept pivot is 0 or not finite, and then nothing changes.  The first call builds the maps and the schedule.
+    refactor_info(): the last refactor's pivot_ratio, device_columns, host_columns and ms.
+    None when A is not CSC, not square, structurally singular (sprank < n), or cs_lu(D) returns None (a numerically
+    singular block)."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     if not _meta(A)[1]:
@@ -2115,7 +2217,8 @@ def btf_factor(A, tol=1.0, seed=0):
             # the plan makes the transposed solve's programs from these three on its first call: held while it lives, even
             # when a read of fac.L / .U / .F has turned a lazily downloaded factor into host lists
             self._keep = (L._dev, U._dev, F._dev)
-            self._A, self._norm = A, None
+            self._A2, self._norm = A, None         # the matrix condest() is about: A, or the last refactor's A2
+            self._prepared, self._rinfo = False, None
 
         def info(self):
             v = np.zeros(8, dtype=np.int64)
@@ -2135,7 +2238,7 @@ def btf_factor(A, tol=1.0, seed=0):
 
         def condest(self):
             if self._norm is None:
-                self._norm = cs_norm(self._A)
+                self._norm = _refactor_norm(A, self._A2)
 
             def one(v, t):
                 d = dvec(v)
@@ -2143,5 +2246,41 @@ def btf_factor(A, tol=1.0, seed=0):
                 return d.numpy()
 
             return _condest(self._norm, one, n)
+
+        def refactor(self, A2):
+            t0 = time.perf_counter()
+            A2 = _refactor_input(A, A2)
+            ok, ratio, cols = _csx.C.c_int(0), _csx.C.c_double(0.0), (_csx.C.c_int64 * 2)()
+            # D's device copy, when it still has one (a host cs_lu of D reads D's lists, which lets it go): D2 is written there
+            dD = D._dev
+            hD = dD.handle if dD is not None else 0
+
+            def call(h2):
+                if self._prepared:
+                    st = _csx.lib().csx_btf_refactor(plan, 0, h2, hD, ok, ratio, cols)
+                else:
+                    with _Resident(A) as dA:      # the first call reads A's pattern: the maps and the schedule
+                        st = _csx.lib().csx_btf_refactor(plan, dA.handle, h2, hD, ok, ratio, cols)
+                self._prepared = self._prepared or st == _csx.OK
+                return st
+
+            _refactor_call(A2, call, ok)
+            if ok.value:
+                for M, dev in zip((L, U, F), self._keep):
+                    _refactored(M, dev)
+                if dD is not None:
+                    _refactored(D, dD)
+                elif D._x is not None:       # D's lists are its only copy: they get D2's values
+                    nnz = D._p[n]
+                    x = np.empty(max(nnz, 1), dtype=np.float64)
+                    _csx.check(_csx.lib().csx_btf_refactor_dx(plan, _csx.pd(x)), "csx_btf_refactor_dx")
+                    D._x[:nnz] = x[:nnz].tolist()
+                self._A2, self._norm = A2, None
+            self._rinfo = {"ok": bool(ok.value), "pivot_ratio": ratio.value, "device_columns": int(cols[0]),
+                           "host_columns": int(cols[1]), "ms": 1e3 * (time.perf_counter() - t0)}
+            return bool(ok.value)
+
+        def refactor_info(self):
+            return dict(self._rinfo) if self._rinfo is not None else None
 
     return _Solver()

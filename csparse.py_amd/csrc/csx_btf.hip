@@ -40,6 +40,24 @@ struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (loc
     TriPlan *put = nullptr, *plt = nullptr;   // U' and L' (transposed solves, made on the first one)
 };
 
+// What only a refactor needs (csx_btf_refactor), made on its first call: A's pattern, the maps from A's entries to D's and F's,
+// the maps from L.x / U.x / F.x to the slots of the forward programs, the schedule, and scratch for the new values
+struct BtfRefactor {
+    BtfRefactor() = default;
+    BtfRefactor(const BtfRefactor &) = delete;
+    BtfRefactor &operator=(const BtfRefactor &) = delete;
+    ~BtfRefactor() { destroy(R); }
+    int32_t anz = 0;
+    DevBuf<int32_t> p0, i0;                         // A's pattern
+    DevBuf<int32_t> dmap, fmap;                     // entry t of D / F is entry map[t] of A
+    Csc Dq;                                         // D's pattern; x holds the gathered values of the current A2
+    DevBuf<int32_t> lxmap, ldmap, uxmap, udmap, ftmap;   // program slot -> entry of L.x / U.x / F.x
+    DevBuf<double> Fx, Lx, Ux;                      // scratch: committed only when every pivot passed
+    DevBuf<int> flag;
+    std::vector<int32_t> Lp, Up;                    // host copies (the large blocks' ranges of L.x / U.x)
+    Refactor *R = nullptr;
+};
+
 struct BtfPlan {
     int32_t n = 0, nb = 0, nlevels = 0, max_block = 0;
     int64_t lnz = 0, unz = 0, fnz = 0;
@@ -63,6 +81,7 @@ struct BtfPlan {
     bool trans_ready = false;
     DevBuf<int32_t> UTp, UTi, LTp, LTi, Fcp, Fci;
     DevBuf<double> UTx, UTd, LTx, LTd, Fcx;
+    std::unique_ptr<BtfRefactor> rf;   // csx_btf_refactor's, from its first call
 };
 
 void destroy(BtfPlan *P) { delete P; }
@@ -460,6 +479,100 @@ static bool is_blocks(const int32_t *r, int32_t nb, int32_t n) {
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------- the refactor --
+
+// per position: first and one-past-last row of its block, its block's level
+static void block_rows(const BtfPlan *P, std::vector<int32_t> &r0h, std::vector<int32_t> &r1h, std::vector<int32_t> &levh) {
+    r0h.resize((size_t)P->n);
+    r1h.resize((size_t)P->n);
+    levh.resize((size_t)P->n);
+    for (int32_t b = 0; b < P->nb; b++)
+        for (int32_t i = P->r_h[b]; i < P->r_h[b + 1]; i++) {
+            r0h[i] = P->r_h[b];
+            r1h[i] = P->r_h[b + 1];
+            levh[i] = P->level_h[b];
+        }
+}
+
+// program slot -> entry maps of a factor: its forward program built from an index-valued copy
+static int program_maps(const Csc *M, bool upper, const int32_t *row_r0, const int32_t *row_r1, int *bad, DevBuf<int32_t> &xmap,
+                        DevBuf<int32_t> &dmap) {
+    csx_handle_t hI = 0;
+    CSX_TRY(rf_index_copy(M, &hI));
+    DevBuf<int32_t> Pp, Pi;
+    DevBuf<double> Px, Pd;
+    const int st = strip(csc(hI), upper, false, row_r0, row_r1, bad, Pp, Pi, Px, Pd);
+    csx_free(hI);
+    CSX_TRY(st);
+    CSX_TRY(rf_index_map(Px, std::max<int64_t>(0, (int64_t)M->nnz - M->n), xmap));
+    CSX_TRY(rf_index_map(Pd, M->n, dmap));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return CSX_OK;
+}
+
+static int btf_refactor_prepare(BtfPlan *P, Csc *A, Csc *L, Csc *U, Csc *F) {
+    const int32_t n = P->n;
+    if (A->m != n || A->n != n) return CSX_EINVAL;
+    hipStream_t s = ctx().stream;
+    std::unique_ptr<BtfRefactor> B(new BtfRefactor());
+    B->anz = A->nnz;
+    CSX_TRY(rf_keep_pattern(A, B->p0, B->i0));
+    std::vector<int32_t> p_h, q_h, pinv_h, pinv_new((size_t)n), blk((size_t)n);
+    CSX_TRY(download_i32(p_h, P->p, (size_t)n));
+    CSX_TRY(download_i32(q_h, P->q, (size_t)n));
+    CSX_TRY(download_i32(pinv_h, P->pinv, (size_t)n));
+    for (int32_t k = 0; k < n; k++) pinv_new[p_h[k]] = k;
+    for (int32_t b = 0; b < P->nb; b++)
+        for (int32_t i = P->r_h[b]; i < P->r_h[b + 1]; i++) blk[i] = b;
+    // csx_btf_split's steps on an index-valued copy of A: D's and F's values say which entry of A each one is
+    csx_handle_t hI = 0, hC = 0;
+    CSX_TRY(rf_index_copy(A, &hI));
+    int st = csx_permute(hI, pinv_new.data(), q_h.data(), 1, &hC);
+    csx_free(hI);
+    CSX_TRY(st);
+    Csc Fi;
+    st = split_device(csc(hC), blk, &B->Dq, &Fi);
+    csx_free(hC);
+    CSX_TRY(st);
+    if (Fi.nnz != F->nnz || B->Dq.nnz + Fi.nnz != A->nnz) return CSX_EINVAL;
+    CSX_TRY(rf_index_map(B->Dq.x, B->Dq.nnz, B->dmap));
+    CSX_TRY(rf_index_map(Fi.x, Fi.nnz, B->fmap));
+    // the forward programs' slots, and F' (cs_gaxpy's row order) of F's entries
+    std::vector<int32_t> r0h, r1h, levh;
+    block_rows(P, r0h, r1h, levh);
+    DevBuf<int32_t> row_r0, row_r1;
+    DevBuf<int> bad;
+    CSX_TRY(upload(row_r0, r0h));
+    CSX_TRY(upload(row_r1, r1h));
+    CSX_TRY(bad.alloc(1));
+    CSX_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    CSX_TRY(program_maps(L, false, row_r0, row_r1, bad, B->lxmap, B->ldmap));
+    CSX_TRY(program_maps(U, true, row_r0, row_r1, bad, B->uxmap, B->udmap));
+    csx_handle_t hFi = 0;
+    CSX_TRY(rf_index_copy(F, &hFi));
+    Csc Ft;
+    st = transpose_device(csc(hFi), true, &Ft);
+    csx_free(hFi);
+    CSX_TRY(st);
+    if (Ft.nnz != P->Ft.nnz) return CSX_EINVAL;
+    CSX_TRY(rf_index_map(Ft.x, Ft.nnz, B->ftmap));
+    int hbad = 0;
+    CSX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    if (hbad) return CSX_EINVAL;
+    // the schedule: a group is a diagonal block
+    CSX_TRY(refactor_build(&B->Dq, pinv_h.data(), L, U, blk, &B->R));
+    CSX_TRY(download_i32(B->Lp, L->p, (size_t)n + 1));
+    CSX_TRY(download_i32(B->Up, U->p, (size_t)n + 1));
+    CSX_TRY(B->Fx.alloc((size_t)F->nnz));
+    CSX_TRY(B->Lx.alloc((size_t)L->nnz));
+    CSX_TRY(B->Ux.alloc((size_t)U->nnz));
+    CSX_TRY(B->flag.alloc(1));
+    CSX_HIP(hipStreamSynchronize(s));
+    P->rf = std::move(B);
+    return CSX_OK;
+}
+
 }  // namespace csx
 
 using namespace csx;
@@ -669,5 +782,121 @@ extern "C" int csx_btf_info(csx_handle_t h, int64_t *info) {
     info[5] = P->fnz;
     info[6] = (int64_t)P->large.size();
     info[7] = launches;   // the solve's own launches; every large block adds one plus those of its two triangular plans
+    return CSX_OK;
+}
+
+extern "C" int csx_btf_refactor(csx_handle_t h, csx_handle_t hA, csx_handle_t hA2, csx_handle_t hD, int *ok, double *ratio,
+                                int64_t *cols) {
+    CSX_TRY(require_ready());
+    BtfPlan *P = (BtfPlan *)get(h, K_BTFPLAN);
+    if (!P || !ok || !ratio) return CSX_EINVAL;
+    Csc *L = csc(P->hL), *U = csc(P->hU), *F = csc(P->hF);
+    if (!L || !U || !F || !L->x || !U->x || !F->x || L->n != P->n || U->n != P->n || F->n != P->n || L->nnz != P->lnz ||
+        U->nnz != P->unz || F->nnz != P->fnz)
+        return CSX_EINVAL;
+    Csc *D = hD ? csc(hD) : nullptr;
+    if (hD && (!D || !D->x || D->n != P->n)) return CSX_EINVAL;
+    if (!P->rf) {
+        Csc *A = csc(hA);
+        if (!A) return CSX_EINVAL;
+        CSX_TRY(btf_refactor_prepare(P, A, L, U, F));
+    }
+    BtfRefactor *B = P->rf.get();
+    if (D && D->nnz != B->Dq.nnz) return CSX_EINVAL;
+    const double *x2 = nullptr;
+    CSX_TRY(rf_values(hA2, P->n, P->n, B->anz, B->p0, B->i0, B->flag, &x2));
+    if (!x2) {
+        *ok = -1;   // another pattern: nothing changes
+        return CSX_OK;
+    }
+    hipStream_t s = ctx().stream;
+    CSX_TRY(rf_gather(B->Dq.nnz, B->dmap, x2, B->Dq.x));
+    CSX_TRY(rf_gather(F->nnz, B->fmap, x2, B->Fx));
+    CSX_TRY(refactor_run(B->R, &B->Dq, B->Dq.x, L, U, B->Lx, B->Ux, ok, ratio));
+    refactor_counts(B->R, cols);
+    if (!*ok) return CSX_OK;
+    // the large blocks' own factors and triangular plans from the new values, into temporaries: an error here leaves
+    // everything as it was
+    const int64_t nlarge = (int64_t)P->large.size();
+    std::vector<std::unique_ptr<Csc>> nL((size_t)nlarge), nU((size_t)nlarge);
+    std::vector<TriPlan *> npl((size_t)nlarge, nullptr), npu((size_t)nlarge, nullptr);
+    struct PlansGuard {   // frees the temporaries' plans unless they were committed
+        std::vector<TriPlan *> &a, &b;
+        ~PlansGuard() {
+            for (TriPlan *t : a) destroy(t);
+            for (TriPlan *t : b) destroy(t);
+        }
+    } guard{npl, npu};
+    if (nlarge) {
+        Csc vL, vU;   // views of the new values on the factors' patterns (arrays not owned)
+        vL.owns = vU.owns = false;
+        vL.m = vL.n = vU.m = vU.n = P->n;
+        vL.nnz = L->nnz;
+        vU.nnz = U->nnz;
+        vL.p = L->p;
+        vL.i = L->i;
+        vL.x = B->Lx;
+        vU.p = U->p;
+        vU.i = U->i;
+        vU.x = B->Ux;
+        for (int64_t g = 0; g < nlarge; g++) {
+            const BtfLarge *G = P->large[g].get();
+            nL[g].reset(new Csc());
+            nU[g].reset(new Csc());
+            CSX_TRY(block_factor(&vL, G->r0, G->nr, nL[g].get()));
+            CSX_TRY(block_factor(&vU, G->r0, G->nr, nU[g].get()));
+            CSX_TRY(tri_analyse_raw(nL[g].get(), CSX_TRI_L, &npl[g]));
+            CSX_TRY(tri_analyse_raw(nU[g].get(), CSX_TRI_U, &npu[g]));
+        }
+    }
+    // commit: the factors, F and D, then everything the solves read (copies and gathers on the stream)
+    const auto d2d = [&](double *dst, const double *src, int64_t cnt) {
+        return cnt > 0 ? hipMemcpyAsync(dst, src, (size_t)cnt * sizeof(double), hipMemcpyDeviceToDevice, s) : hipSuccess;
+    };
+    CSX_HIP(d2d(L->x, B->Lx, L->nnz));
+    CSX_HIP(d2d(U->x, B->Ux, U->nnz));
+    CSX_HIP(d2d(F->x, B->Fx, F->nnz));
+    if (D) CSX_HIP(d2d(D->x, B->Dq.x, D->nnz));
+    const int32_t n = P->n;
+    CSX_TRY(rf_gather(std::max<int64_t>(0, (int64_t)P->lnz - n), B->lxmap, L->x, P->Lx));
+    CSX_TRY(rf_gather(n, B->ldmap, L->x, P->Ld));
+    CSX_TRY(rf_gather(std::max<int64_t>(0, (int64_t)P->unz - n), B->uxmap, U->x, P->Ux));
+    CSX_TRY(rf_gather(n, B->udmap, U->x, P->Ud));
+    CSX_TRY(rf_gather(P->Ft.nnz, B->ftmap, F->x, P->Ft.x));
+    for (int64_t g = 0; g < nlarge; g++) {
+        BtfLarge *G = P->large[g].get();
+        // (the same patterns: the new arrays take the old ones' place, the old ones go with the temporaries)
+        std::swap(G->L.p, nL[g]->p);
+        std::swap(G->L.i, nL[g]->i);
+        std::swap(G->L.x, nL[g]->x);
+        std::swap(G->U.p, nU[g]->p);
+        std::swap(G->U.i, nU[g]->i);
+        std::swap(G->U.x, nU[g]->x);
+        for (TriPlan **T : {&G->pl, &G->pu, &G->put, &G->plt}) {
+            destroy(*T);
+            *T = nullptr;
+        }
+        G->pl = npl[g];
+        G->pu = npu[g];
+        npl[g] = npu[g] = nullptr;
+    }
+    P->trans_ready = false;   // the transposed programs are made again, from the new values, by the next transposed solve
+    for (Csc *M : {L, U, F, D})
+        if (M) {
+            M->rows.reset();
+            M->tiled.reset();
+        }
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+extern "C" int csx_btf_refactor_dx(csx_handle_t h, double *Dx) {
+    CSX_TRY(require_ready());
+    BtfPlan *P = (BtfPlan *)get(h, K_BTFPLAN);
+    if (!P || !P->rf || !Dx) return CSX_EINVAL;
+    hipStream_t s = ctx().stream;
+    if (P->rf->Dq.nnz)
+        CSX_HIP(hipMemcpyAsync(Dx, P->rf->Dq.x, (size_t)P->rf->Dq.nnz * sizeof(double), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
     return CSX_OK;
 }

@@ -244,6 +244,7 @@ static void free_object(Object &o) {
         case K_CHOLPLAN: destroy((CholPlan *)o.ptr); break;
         case K_SHARDPLAN: destroy((ShardPlan *)o.ptr); break;
         case K_BTFPLAN: destroy((BtfPlan *)o.ptr); break;
+        case K_LUREFPLAN: destroy((LuRefPlan *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it

@@ -825,3 +825,80 @@ extern "C" int csx_sqr_host(int32_t m, int32_t n, const int32_t *Ap, const int32
     *rnz_out = rnz;
     return CSX_OK;
 }
+
+// ---- refactor: cs_lu's numeric steps with the pivots and the patterns of L and U kept ----------------
+// Column k (in the factorisation's column order) in pivot-row space: x = 0 on the rows of U(:,k) and L(:,k), x[pinv[i]] =
+// A(i,k) in storage order (assignment, as cs_spsolve); for every entry J of U(:,k) but the last, in storage order: U.x = x[J],
+// x[L.i[t]] -= L.x[t] x[J] over L(:,J) after its unit diagonal; the pivot x[k] goes last into U(:,k) and L(:,k) = x / pivot
+// after the unit diagonal.  The stored order is the topological order cs_lu solved in, so L and U come out byte-equal to
+// cs_lu's whenever it would choose the same pivots.  x: n zeros on entry, left zero.  *ok = 0 at the first pivot that is 0 or
+// not finite (the columns before it are written).  *ratio = min over the columns of |pivot| / max |x_i| over L(:,k)'s rows
+// (pivot included) -- 1.0 when every kept pivot is a largest candidate.
+namespace csx {
+int lu_refactor_columns(int32_t n, const int32_t *cols, int32_t ncols, const int32_t *Ap, const int32_t *Ai,
+                        const double *Ax, const int32_t *pinv, const int32_t *Lp, const int32_t *Li, double *Lx,
+                        const int32_t *Up, const int32_t *Ui, double *Ux, double *x, int *ok, double *ratio) {
+#pragma clang fp contract(off)
+    *ok = 1;
+    double rmin = 1.0;
+    for (int32_t c = 0; c < ncols; c++) {
+        const int32_t k = cols ? cols[c] : c;
+        const int32_t ue = Up[k + 1] - 1;
+        if (ue < Up[k] || Ui[ue] != k || Lp[k + 1] <= Lp[k] || Li[Lp[k]] != k) return CSX_EINVAL;
+        for (int32_t t = Up[k]; t <= ue; t++) x[Ui[t]] = 0.0;
+        for (int32_t t = Lp[k]; t < Lp[k + 1]; t++) x[Li[t]] = 0.0;
+        for (int32_t t = Ap[k]; t < Ap[k + 1]; t++) x[pinv[Ai[t]]] = Ax[t];
+        for (int32_t t = Up[k]; t < ue; t++) {
+            const int32_t J = Ui[t];
+            if (J >= k) return CSX_EINVAL;
+            const double xj = x[J];
+            Ux[t] = xj;
+            for (int32_t s = Lp[J] + 1; s < Lp[J + 1]; s++) {
+                const double prod = Lx[s] * xj;
+                x[Li[s]] = x[Li[s]] - prod;
+            }
+        }
+        const double piv = x[k];
+        Ux[ue] = piv;
+        double big = std::fabs(piv);
+        for (int32_t s = Lp[k] + 1; s < Lp[k + 1]; s++) big = std::fmax(big, std::fabs(x[Li[s]]));
+        const bool bad = piv == 0.0 || !std::isfinite(piv);
+        if (!bad) rmin = std::fmin(rmin, std::fabs(piv) / big);
+        Lx[Lp[k]] = 1.0;
+        for (int32_t s = Lp[k] + 1; s < Lp[k + 1]; s++) Lx[s] = x[Li[s]] / piv;
+        for (int32_t t = Up[k]; t <= ue; t++) x[Ui[t]] = 0.0;
+        for (int32_t t = Lp[k]; t < Lp[k + 1]; t++) x[Li[t]] = 0.0;
+        if (bad) {
+            *ok = 0;
+            break;
+        }
+    }
+    *ratio = rmin;
+    return CSX_OK;
+}
+}  // namespace csx
+
+extern "C" int csx_lu_refactor_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv,
+                                    const int32_t *Lp, const int32_t *Li, double *Lx, const int32_t *Up, const int32_t *Ui,
+                                    double *Ux, int *ok, double *ratio) {
+    if (n < 0 || !Ap || !Ai || !Ax || !pinv || !Lp || !Li || !Lx || !Up || !Ui || !Ux || !ok || !ratio) return CSX_EINVAL;
+    // every index inside [0, n), the patterns' pointers from 0 and non-decreasing, A(:,k)'s rows in L(:,k) or U(:,k)
+    std::vector<int32_t> mark((size_t)n, -1);
+    if (Ap[0] != 0 || Lp[0] != 0 || Up[0] != 0) return CSX_EINVAL;
+    for (int32_t i = 0; i < n; i++)
+        if (pinv[i] < 0 || pinv[i] >= n || mark[pinv[i]] >= 0) return CSX_EINVAL;
+        else mark[pinv[i]] = n;
+    for (int32_t k = 0; k < n; k++) {
+        if (Ap[k + 1] < Ap[k] || Lp[k + 1] < Lp[k] || Up[k + 1] < Up[k]) return CSX_EINVAL;
+        for (int32_t t = Lp[k]; t < Lp[k + 1]; t++)
+            if (Li[t] < k || Li[t] >= n) return CSX_EINVAL;
+            else mark[Li[t]] = k;
+        for (int32_t t = Up[k]; t < Up[k + 1]; t++)
+            if (Ui[t] < 0 || Ui[t] > k) return CSX_EINVAL;
+            else mark[Ui[t]] = k;
+        for (int32_t t = Ap[k]; t < Ap[k + 1]; t++)
+            if (Ai[t] < 0 || Ai[t] >= n || mark[pinv[Ai[t]]] != k) return CSX_EINVAL;
+    }
+    std::vector<double> x((size_t)n, 0.0);
+    return csx::lu_refactor_columns(n, nullptr, n, Ap, Ai, Ax, pinv, Lp, Li, Lx, Up, Ui, Ux, x.data(), ok, ratio);
+}

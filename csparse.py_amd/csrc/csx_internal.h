@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN };
 
 struct Csc;
 
@@ -184,6 +184,10 @@ void destroy(CholPlan *p);
 void destroy(ShardPlan *p);
 void destroy(BtfPlan *p);
 void destroy(SnPlan *p);
+struct Refactor;   // csx_refactor.hip
+struct LuRefPlan;  // csx_refactor.hip
+void destroy(Refactor *p);
+void destroy(LuRefPlan *p);
 
 struct Object {
     Kind kind = K_FREE;
@@ -324,6 +328,23 @@ int transpose_device(const Csc *A, bool values, Csc *C);  // C fields allocated 
 int gaxpy_device(Csc *A, const double *x, double *y, int mode);                 // csx_gaxpy.hip: y += A x, raw pointers
 int gaxpy_prepare_device(Csc *A, int mode);                                     // ... the plan `mode` needs, cached on A
 int col_block_device(const Csc *A, int32_t first, int32_t count, Csc *C);      // csx_assemble.hip: columns [first, first + count)
+
+// ---- refactor (csx_refactor.hip) ----
+// The schedule of a refactor of cs_lu's L, U with new values: A in the factorisation's column order (pattern), pinv (host),
+// gid (host: the group of every position; empty = the connected components of L + U).  refactor_run writes the new values
+// into Lx, Ux (device scratch) and synchronises; refactor_counts: columns on the device / on the host.
+int refactor_build(const Csc *A, const int32_t *pinv, const Csc *L, const Csc *U, const std::vector<int32_t> &gid,
+                   Refactor **out);
+int refactor_run(Refactor *R, const Csc *A, const double *Ax, const Csc *L, const Csc *U, double *Lx, double *Ux, int *ok,
+                 double *ratio);
+void refactor_counts(const Refactor *R, int64_t *cols);
+int rf_gather(int64_t cnt, const int32_t *map, const double *src, double *dst);   // dst[t] = src[map[t]]
+int rf_index_copy(const Csc *A, csx_handle_t *out);                                // A's pattern, x[t] = t
+int rf_index_map(const double *x, int64_t cnt, DevBuf<int32_t> &map);             // map[t] = (int) x[t]
+int rf_keep_pattern(const Csc *A, DevBuf<int32_t> &p, DevBuf<int32_t> &i);
+// the values of A2 (a matrix with the pattern p0 / i0, or a vector of nnz values), CSX_EINVAL for anything else
+int rf_values(csx_handle_t A2, int32_t m, int32_t n, int32_t nnz, const int32_t *p0, const int32_t *i0, int *flag,
+              const double **x);
 
 // Workgroup barrier that orders LDS only.  __syncthreads() carries a fence over global memory as well: it waits for
 // every global load the wave has in flight (s_waitcnt vmcnt(0)), which puts the latency of software-pipelined loads

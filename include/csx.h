@@ -540,6 +540,46 @@ int csx_btf_solve(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t 
 int csx_btf_solve_trans(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t nrhs);
 int csx_btf_info(csx_handle_t plan, int64_t *info);
 
+/* ---- refactor: new values, the same pivots (btf_factor / lusol_factor .refactor) -----------------
+ * Definition.  Given cs_lu's L, U, pinv of a matrix and new values A2 of the same pattern, column k of the factorisation (in
+ * its column order) is recomputed in pivot-row space: x = 0 on the rows of U(:,k) and L(:,k); x[pinv[i]] = A2(i, k) in
+ * storage order (assignment, as cs_spsolve); for every entry J of U(:,k) but the last, in storage order: U.x = x[J],
+ * x[L.i[t]] -= L.x[t] x[J] for t over L(:,J) after its unit diagonal (multiply and subtract rounded separately); the pivot
+ * x[k] goes last into U(:,k); L.x = x / pivot after the unit diagonal.  The stored order is the order cs_lu solved in: L and
+ * U are byte-equal to cs_lu(A2)'s whenever it chooses the same pinv.  *ok = 0 when a pivot is 0 or not finite; *ratio = the
+ * minimum over the columns of |pivot| / max |x_i| over L(:,k)'s rows (pivot included): 1.0 when every kept pivot is a
+ * largest candidate of its column.
+ * csx_lu_refactor_host: the rule on host arrays for all n columns, A's column k = column k of the factorisation; writes
+ *   Lx and Ux (the caller's, the patterns' lengths).  CSX_EINVAL when an index leaves [0, n), pinv is not a permutation, a
+ *   column of U lacks its diagonal last or one of L its diagonal first, or A(:,k) has a row outside L(:,k) and U(:,k).
+ * Device path (csx_btf_refactor, csx_lu_refactor): the columns fall into groups that do not depend on one another (btf: the
+ *   diagonal blocks; lusol: the connected components of the pattern of L + U); a group of at most 96 rows whose columns of A
+ *   have no duplicate rows is refactored by one wave with x in LDS, the others by the host loop.  A2 is checked against A's
+ *   pattern on the device (CSX_EINVAL for a different one); its values are gathered through maps built on the first call.
+ *   Nothing the solves read changes unless *ok = 1, and an error status before the commit (an allocation, a plan of a large
+ *   block) leaves everything as it was; *ok = -1 (CSX_OK) when A2's pattern or length differs from A's, nothing changed.
+ *   cols (or NULL): [0] columns refactored on the device, [1] on the host.  The host groups run while the launch does.
+ * csx_btf_refactor: plan from csx_btf_plan; A: the matrix the plan was factored from, read on the FIRST call only (its pattern
+ *   and the maps; 0 afterwards); A2: a matrix with A's pattern or a vector of nnz(A) values in A's storage order; D: the D of
+ *   csx_btf_split (its values are replaced too) or 0.  On success L, U, F (the plan's handles) and D hold the new values, the
+ *   forward programs are refreshed in place, the large blocks re-make their triangular plans, and the transposed programs are
+ *   made again on the next transposed solve.  Cached plans of L, U, F, D (csx_gaxpy's, the triangular solves') are stale:
+ *   csx_csc_invalidate them.
+ * csx_btf_refactor_dx: D2's values of the last csx_btf_refactor call (nnz(D) doubles, D's storage order) into host Dx: for a D
+ *   whose device copy is gone (then pass D = 0 to csx_btf_refactor).
+ * csx_lu_refactor_plan: a NEW plan handle (csx_free) for L, U (device, cs_lu's, kept alive by the caller), A (the matrix they
+ *   were factored from: pattern only), q (n, the factorisation's column order, or NULL: natural) and pinv (host, n).
+ * csx_lu_refactor: A2 as above; on success L's and U's values are replaced (plans made from them are stale). */
+int csx_lu_refactor_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv,
+                         const int32_t *Lp, const int32_t *Li, double *Lx, const int32_t *Up, const int32_t *Ui, double *Ux,
+                         int *ok, double *ratio);
+int csx_btf_refactor(csx_handle_t plan, csx_handle_t A, csx_handle_t A2, csx_handle_t D, int *ok, double *ratio,
+                     int64_t *cols);
+int csx_btf_refactor_dx(csx_handle_t plan, double *Dx);
+int csx_lu_refactor_plan(csx_handle_t L, csx_handle_t U, csx_handle_t A, const int32_t *q, const int32_t *pinv,
+                         csx_handle_t *plan);
+int csx_lu_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, double *ratio, int64_t *cols);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
