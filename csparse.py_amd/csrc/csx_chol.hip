@@ -634,18 +634,21 @@ static void partition_forest(int32_t n, const int32_t *parent, Forest &F) {
 static int g_chol_path = -1;
 static double g_chol_numeric_ms = 0.0;
 
+// a call's two timing events, destroyed on every way out of it
+struct EvGuard {
+    hipEvent_t &a, &b;
+    ~EvGuard() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
 static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, Csc *L) {
     hipStream_t s = ctx().stream;
     g_chol_path = -1;
     g_chol_numeric_ms = 0.0;
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    struct EvGuard {
-        hipEvent_t &a, &b;
-        ~EvGuard() {
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-        }
-    } ev_guard{ev_a, ev_b};
+    EvGuard ev_guard{ev_a, ev_b};
     if (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess) return CSX_ERUNTIME;
     auto numeric_ms = [&]() {   // after the stream has been synchronised
         float ms = 0.0f;
@@ -993,7 +996,7 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
 
 // ---- solve phase ----------------------------------------------------------------------------------
 struct CholPlan {
-    CholPlan() = default;
+    explicit CholPlan(const Csc *L_) : n(L_->n), L(L_) {}
     CholPlan(const CholPlan &) = delete;
     CholPlan &operator=(const CholPlan &) = delete;
     ~CholPlan() {
@@ -1056,16 +1059,18 @@ struct CholPlan {
     bool lite = false;
     bool lite_cliques = false;   // ... and every block is a CLIQUE (dense): the exact order can take the padded size classes below
     std::unique_ptr<CholPlan> full;
-    // exact order on a forest of cliques of UNEQUAL sizes (round 5): the blocks bucketed by size class 8 / 16 / 32 / 64, every block
-    // padded at its end with the identity up to its class, the register-resident exact kernel (k_cholsol_dense_exact_dpp) run
+    // exact order on a forest of cliques of UNEQUAL sizes (round 5): the blocks bucketed by size class 8 / 16 / 32 / 48 / 64, every
+    // block padded at its end with the identity up to its class, the register-resident exact kernel (k_cholsol_dense_exact_dpp) run
     // per class on programs cut out of L.x -- the padding changes no bit (see the kernel)
+    // (a class of 48 since late in round 5: a block of 33 .. 48 columns padded to 64 did 1.8 times the terms it does padded to 48)
+    static constexpr int xc_bs[5] = {8, 16, 32, 48, 64};
     struct ExactClass {
         int32_t count = 0;
         DevBuf<Tree> trees;
         DevBuf<int32_t> nodes, f_ptr, b_ptr;
         DevBuf<double> f_val, dense_b, diagk, diagb;
     } xc[5];
-    bool xc_built = false;
+    bool xc_tried = false, xc_built = false;   // a build that was tried and gave up leaves the exact order to `full`
     bool mfma_tried = false;  // fragments were built, or refused by the growth guard
     double mfma_growth = 0.0; // max|inv(L_ii)| max|L| over the forest (the guard's measure)
     // big trees, rounding-equal order: supernodal schedule (csx_snsolve.hip), built the first time the plan is relaxed
@@ -1076,6 +1081,11 @@ struct CholPlan {
 };
 
 void destroy(CholPlan *P) { delete P; }
+
+// the block sizes of the dense-block solve kernels (the W-tile emission of the block kernel takes 16, 32 and 64 only), and a
+// forest of cliques all of one such size
+static bool dense_block_size(int32_t bs) { return bs == 8 || bs == 16 || bs == 32 || bs == 64; }
+static bool equal_dense_blocks(const CliqueForest &F) { return !F.sparse && F.min_bs == F.max_bs && dense_block_size(F.max_bs); }
 
 // G lanes to a column (4 where the columns are short)
 template <int G>
@@ -1928,11 +1938,9 @@ static int cholsol_clique_local(CholPlan *P) {
 // *out holds the plan from the start, a failure part way included
 static int cholsol_plan(const Csc *L, const int32_t *pinv, std::unique_ptr<CholPlan> *out) {
     hipStream_t s = ctx().stream;
-    out->reset(new CholPlan());
+    out->reset(new CholPlan(L));
     CholPlan *P = out->get();
     const int32_t n = L->n;
-    P->n = n;
-    P->L = L;
     const bool timing = getenv("CSX_CHOL_TIMING") != nullptr;
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
@@ -1953,7 +1961,7 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, std::unique_ptr<CholP
     if (n > 0 && ctx().opt.chol_clique && ctx().opt.cholsol_dense_blocks) {
         int32_t bs = 0;
         CSX_TRY(clique_factor_block_size(L, &bs));
-        if (bs == 8 || bs == 16 || bs == 32 || bs == 64) return cholsol_plan_clique(P, bs);
+        if (dense_block_size(bs)) return cholsol_plan_clique(P, bs);
     }
     CSX_TRY(tri_analyse_raw(L, CSX_TRI_L, &P->fwd));
     lap("analysis of L");
@@ -2100,7 +2108,7 @@ static int cholsol_plan(const Csc *L, const int32_t *pinv, std::unique_ptr<CholP
     // dense blocks? same size, contiguous rows, column c of a block holding exactly bs - c entries
     // (a forest partitioned on the device is no forest of equal dense blocks: cholsol_plan_clique would have taken it)
     const int32_t bs = on_device ? 0 : F.max_tree;
-    if (bs == 8 || bs == 16 || bs == 32 || bs == 64) {
+    if (dense_block_size(bs)) {
         std::vector<int32_t> hLp((size_t)n + 1);
         CSX_HIP(hipMemcpyAsync(hLp.data(), L->p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         CSX_HIP(hipStreamSynchronize(s));
@@ -2217,6 +2225,13 @@ static int cholsol_build_sn(CholPlan *P) {
     return st;
 }
 
+// the rounding-equal order: the operands of its kernels are built the first time a plan is put in it
+static int cholsol_relax(CholPlan *P) {
+    P->relaxed = true;
+    CSX_TRY(cholsol_build_mfma(P));
+    return cholsol_build_sn(P);
+}
+
 // ---- exact order on forests of cliques of unequal sizes: padded size classes ------------------------------------------------
 __global__ __launch_bounds__(256) void k_xc_class(const Tree *__restrict__ trees, int32_t ntrees, uint32_t *__restrict__ key,
                                                   uint32_t *__restrict__ id) {
@@ -2273,7 +2288,8 @@ __global__ __launch_bounds__(256) void k_xc_plan(const uint32_t *__restrict__ li
 }
 
 static int cholsol_exact_classes_build(CholPlan *P) {
-    if (P->xc_built) return CSX_OK;
+    if (P->xc_tried) return CSX_OK;
+    P->xc_tried = true;
     hipStream_t s = ctx().stream;
     const int32_t nt = P->ntrees;
     DevBuf<uint32_t> key, id, skey, list;
@@ -2290,13 +2306,11 @@ static int cholsol_exact_classes_build(CholPlan *P) {
     int32_t hb[6] = {0, 0, 0, 0, 0, 0};
     CSX_HIP(hipMemcpyAsync(hb, bounds, sizeof hb, hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
-    // (a class of 48 since late in round 5: a block of 33 .. 48 columns padded to 64 did 1.8 times the terms it does padded to 48)
-    static const int kBS[5] = {8, 16, 32, 48, 64};
     for (int c = 0; c < 5; c++) {
         CholPlan::ExactClass &X = P->xc[c];
         X.count = hb[c + 1] - hb[c];
         if (X.count <= 0) continue;
-        const int BS = kBS[c];
+        const int BS = CholPlan::xc_bs[c];
         const size_t rows = (size_t)X.count * BS, terms = (size_t)X.count * (BS * (BS - 1) / 2);
         if (terms > 0x7fffffffull) return CSX_OK;            // (32-bit program offsets: the general plan takes over; nothing built is used)
         CSX_TRY(X.trees.alloc((size_t)X.count));
@@ -2359,53 +2373,84 @@ static int launch_exact_dpp(int BS, const Tree *trees, int32_t ntrees, const int
     return CSX_OK;
 }
 
+// The kernels a solve can take, with the path code csx_cholsol_info reports for each (include/csx.h).  cholsol_route picks one from
+// the plan and the options alone -- it builds nothing and launches nothing: cholsol_solve takes what it says, the info reports it.
+enum class CholRoute {
+    ExactClasses,   // 2  lite plan of cliques, exact order: padded size classes on the register-resident exact kernel
+    RaggedLite,     // 5  lite plan, rounding-equal order: the trees on the matrix cores, operands from L's columns (csx_trimfma.hip)
+    Full,           // -  lite plan, anything else: the general plan of the same factor (`full`, in the exact order) and its route
+    DenseExact,     // 2  equal dense blocks, exact order: launch_exact_dpp
+    DenseMfma,      // 3  equal dense blocks, rounding-equal order, on the matrix cores: k_cholsol_mfma
+    DenseFma,       // 2  ... blocks of 8, or inverses the guard refused: FMA substitution, k_cholsol_dense
+    Ragged,         // 5  small trees of any shape, rounding-equal order, on the matrix cores (the general plan's programs)
+    Local,          // 1  small trees, the fused per-tree kernel: k_cholsol_local
+    Supernodal,     // 4  a big tree, rounding-equal order: the supernodal schedule (csx_snsolve.hip)
+    Levels,         // 0  level-scheduled triangular solves: tri_solve_raw
+};
+static const int32_t kCholRoutePath[] = {2, 5, -1, 2, 3, 2, 5, 1, 4, 0};   // the codes above
+
+static CholRoute cholsol_route(const CholPlan *P) {
+    const bool dense = ctx().opt.cholsol_dense_blocks != 0, ragged = P->relaxed && P->rag && dense;
+    if (P->lite)   // (the exact classes are made by the first solve that takes them)
+        return ragged ? CholRoute::RaggedLite
+                      : P->lite_cliques && dense && (!P->xc_tried || P->xc_built) ? CholRoute::ExactClasses : CholRoute::Full;
+    if (P->local) {
+        if (P->dense_bs && dense) return !P->relaxed ? CholRoute::DenseExact : P->frag_f ? CholRoute::DenseMfma : CholRoute::DenseFma;
+        return ragged ? CholRoute::Ragged : CholRoute::Local;
+    }
+    return P->relaxed && P->sn && ctx().opt.tri_supernodes && sn_usable(P->sn) ? CholRoute::Supernodal : CholRoute::Levels;
+}
+
+// *P, a lite plan, replaced by its general plan, made the first time a solve or csx_cholsol_info needs it -- after L's row indices
+// if the factor left them to be made (Csc::rows_pending): the general analysis reads L.i
+static int cholsol_full(CholPlan **out) {
+    CholPlan *P = *out;
+    if (!P->full) {
+        CSX_TRY(csc_fill_rows(const_cast<Csc *>(P->L)));   // (the plan borrows L; this writes L.i and changes no value of L)
+        std::unique_ptr<CholPlan> F;
+        CSX_TRY(cholsol_plan(P->L, nullptr, &F));         // (kept only when whole)
+        P->full = std::move(F);
+    }
+    P->full->relaxed = false;          // (what `full` is for: the exact order, or the order the guard left)
+    *out = P->full.get();
+    return CSX_OK;
+}
+
 static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
     hipStream_t s = ctx().stream;
     const int32_t n = P->n;
     if (n == 0 || nrhs == 0) return CSX_OK;
-    if (P->lite && P->lite_cliques && !(P->relaxed && P->rag) && ctx().opt.cholsol_dense_blocks) {
-        // the exact order on cliques of unequal sizes: size classes padded with the identity, the register-resident exact kernel
-        CSX_TRY(cholsol_exact_classes_build(P));
-        if (P->xc_built) {
-            static const int kBS[5] = {8, 16, 32, 48, 64};
+    // what the route reads and has not been made yet, in this order: the exact classes, a clique plan's programs, `full` (below)
+    if (cholsol_route(P) == CholRoute::ExactClasses) CSX_TRY(cholsol_exact_classes_build(P));
+    const CholRoute route = cholsol_route(P);   // (Full when that build gave up)
+    if (P->clique) {
+        // a plan csx_cholsol_factor made holds the matrix-core operands only (written by the block kernel beside L.x); what the
+        // substitution kernels read is cut out of L.x the first time one of them is asked for
+        // ... unless the kernel asked for takes L.x as it is: the matrix cores (W tiles beside it), and -- round 5 -- the
+        // default exact kernel, which copies the block's packed columns to LDS once for both passes
+        const bool lx_aligned = (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0;      // (the copies to LDS move 16 bytes a lane)
+        if (route != CholRoute::DenseMfma && !(route == CholRoute::DenseExact && lx_aligned) && !P->f_val)
+            CSX_TRY(cholsol_plan_clique(P, P->dense_bs));
+        if (P->clique_zero_pivot) return CSX_EZEROPIVOT;
+        if (route == CholRoute::Local) CSX_TRY(cholsol_clique_local(P));
+    } else if (P->local && !P->lite) {
+        CSX_TRY(tri_solve_raw(P->fwd, B, 0, false));    // zero pivots found by the analysis: reported like the reference (ZeroDivisionError)
+    }
+    switch (route) {
+        case CholRoute::ExactClasses: {
             for (int c = 0; c < 5; c++) {
                 const CholPlan::ExactClass &X = P->xc[c];
                 if (X.count > 0)
-                    CSX_TRY(launch_exact_dpp(kBS[c], X.trees, X.count, X.nodes, nullptr, X.f_ptr, X.f_val, X.b_ptr, X.dense_b, X.diagk,
-                                             X.diagb, B, nrhs));
+                    CSX_TRY(launch_exact_dpp(CholPlan::xc_bs[c], X.trees, X.count, X.nodes, nullptr, X.f_ptr, X.f_val, X.b_ptr, X.dense_b,
+                                             X.diagk, X.diagb, B, nrhs));
             }
             return CSX_OK;
         }
-    }
-    if (P->lite) {
-        if (P->relaxed && P->rag && ctx().opt.cholsol_dense_blocks) return ragged_solve(P->rag.get(), P->tree_nodes, nullptr, false, 2, B, nrhs, P->n);
-        if (!P->full) CSX_TRY(cholsol_plan(P->L, nullptr, &P->full));
-        P->full->relaxed = false;          // (what `full` is for: the exact order, or the order the guard left)
-        return cholsol_solve(P->full.get(), B, nrhs);
-    }
-    const int32_t *Gp = nullptr, *Gi = nullptr;
-    const double *Gx = nullptr, *Gd = nullptr;
-    if (!P->clique) tri_gather_arrays(P->fwd, &Gp, &Gi, &Gx, &Gd);
-    if (P->local && (Gd != nullptr || P->clique)) {
-        // zero pivots were detected by the analysis; report like the reference (ZeroDivisionError)
-        if (P->clique) {
-            // a plan csx_cholsol_factor made holds the matrix-core operands only (written by the block kernel beside L.x); what the
-            // substitution kernels read is cut out of L.x the first time one of them is asked for
-            // ... unless the kernel asked for takes L.x as it is: the matrix cores (W tiles beside it), and -- round 5 -- the
-            // default exact kernel, which copies the block's packed columns to LDS once for both passes
-            const bool cores = P->dense_bs && P->relaxed && P->frag_f && ctx().opt.cholsol_dense_blocks;
-            const bool lx_aligned = (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0;      // (the copies to LDS move 16 bytes a lane)
-            const bool packed_exact = P->dense_bs && !P->relaxed && ctx().opt.cholsol_dense_blocks && lx_aligned;
-            if (!cores && !packed_exact && !P->f_val) CSX_TRY(cholsol_plan_clique(P, P->dense_bs));
-            if (P->clique_zero_pivot) return CSX_EZEROPIVOT;
-            if (!ctx().opt.cholsol_dense_blocks) CSX_TRY(cholsol_clique_local(P));
-        } else {
-            int st = tri_solve_raw(P->fwd, B, 0, false);
-            if (st != CSX_OK) return st;
-        }
-        // Forests of dense blocks: the default (exact) order runs the substitution kernel that keeps the reference's
-        // operations and their order; the rounding-equal order the FMA / matrix-core kernels.
-        if (P->dense_bs && !P->relaxed && ctx().opt.cholsol_dense_blocks) {
+        case CholRoute::RaggedLite: return ragged_solve(P->rag.get(), P->tree_nodes, nullptr, false, 2, B, nrhs, P->n);
+        case CholRoute::Full:
+            CSX_TRY(cholsol_full(&P));
+            return cholsol_solve(P, B, nrhs);
+        case CholRoute::DenseExact:
             // the L values by DPP row broadcast, one term in four by an LDS broadcast read (measurements on G-spd, 5M rows, 128
             // right-hand sides, profiles/r03_ablation.md section 3: 4.6 - 4.8 / 3.0 / 2.2 / 2.0 ms at blocks of 64 / 32 / 16 / 8);
             // one right-hand side per lane; waves that solve the same block share its LDS copy (as many as divide the number of
@@ -2414,32 +2459,32 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
             return launch_exact_dpp(P->dense_bs, P->trees, P->ntrees, P->tree_nodes, P->perm, P->f_ptr, P->f_val, P->b_ptr, P->dense_b,
                                     P->diagk, P->diagb, B, nrhs,
                                     P->clique && (reinterpret_cast<uintptr_t>(P->L->x) & 15) == 0 ? P->L->x : nullptr);
-        }
-        if (P->dense_bs && P->relaxed && ctx().opt.cholsol_dense_blocks) {
+        case CholRoute::DenseMfma: {
             const int32_t chunks = (nrhs + 63) / 64;
-            const int64_t tasks = (int64_t)P->ntrees * chunks;
-            const dim3 grid((unsigned)((tasks + 3) / 4));
-            if (P->frag_f) {
-                // (equal dense blocks on ALL the columns of L -- `clique` -- lie in L.x as they do in a copy: block t at t bs (bs + 1) / 2)
-                const double *lv = P->lcopy ? P->lcopy : P->L->x;
-                const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
-                const dim3 g2((unsigned)(((int64_t)P->ntrees + share - 1) / share * (chunks / (4 / share))));
+            // (equal dense blocks on ALL the columns of L -- `clique` -- lie in L.x as they do in a copy: block t at t bs (bs + 1) / 2)
+            const double *lv = P->lcopy ? P->lcopy : P->L->x;
+            const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
+            const dim3 g2((unsigned)(((int64_t)P->ntrees + share - 1) / share * (chunks / (4 / share))));
 #define CSX_MF_X(NB_, SH) \
     hipLaunchKernelGGL((k_cholsol_mfma<NB_, SH>), g2, dim3(256), 0, s, P->trees, P->ntrees, P->tree_nodes, P->perm, lv, P->frag_f, B, nrhs, chunks)
 #define CSX_MF(NB_)                       \
     if (share == 1) CSX_MF_X(NB_, 1);     \
     else if (share == 2) CSX_MF_X(NB_, 2); \
     else CSX_MF_X(NB_, 4)
-                switch (P->dense_bs) {
-                    case 16: CSX_MF(1); break;
-                    case 32: CSX_MF(2); break;
-                    default: CSX_MF(4); break;
-                }
+            switch (P->dense_bs) {
+                case 16: CSX_MF(1); break;
+                case 32: CSX_MF(2); break;
+                default: CSX_MF(4); break;
+            }
 #undef CSX_MF
 #undef CSX_MF_X
-                CSX_LAUNCH_CHECK();
-                return CSX_OK;
-            }
+            CSX_LAUNCH_CHECK();
+            return CSX_OK;
+        }
+        case CholRoute::DenseFma: {
+            const int32_t chunks = (nrhs + 63) / 64;
+            const int64_t tasks = (int64_t)P->ntrees * chunks;
+            const dim3 grid((unsigned)((tasks + 3) / 4));
 #define CSX_DENSE(BS)                                                                                          \
     hipLaunchKernelGGL(k_cholsol_dense<BS>, grid, dim3(256), 0, s, P->trees, P->ntrees, P->tree_nodes, P->perm, \
                        P->f_ptr, P->f_val, P->b_ptr, P->dense_b, P->diagk, P->diagb, B, nrhs, chunks)
@@ -2453,22 +2498,25 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
             CSX_LAUNCH_CHECK();
             return CSX_OK;
         }
-        if (P->relaxed && P->rag && ctx().opt.cholsol_dense_blocks)    // trees of any shape, rounding-equal order: on the matrix cores
-            return ragged_solve(P->rag.get(), P->tree_nodes, P->perm, false, 2, B, nrhs, P->n);
-        const size_t per_wave = (size_t)P->max_nodes * 64 * sizeof(double);
-        const int waves = tile_waves_per_workgroup(per_wave, CH_WAVES);
-        const int32_t chunks = (nrhs + 63) / 64;
-        const int64_t tasks = (int64_t)P->ntrees * chunks;
-        const size_t lds = per_wave * (size_t)waves;
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cholsol_local),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-        if (!P->trees_by_size) CSX_TRY(trees_biggest_first(P->trees, P->ntrees, P->max_nodes, &P->trees_by_size));
-        hipLaunchKernelGGL(k_cholsol_local, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(64 * waves), lds, s,
-                           P->trees_by_size, P->ntrees, P->tree_nodes, P->perm, P->f_ptr, P->f_idx, P->f_val, P->b_ptr, P->b_idx,
-                           P->b_val, P->diagk, P->diagb, B, nrhs, chunks, P->max_nodes, waves);
-        CSX_LAUNCH_CHECK();
-        return CSX_OK;
+        case CholRoute::Ragged: return ragged_solve(P->rag.get(), P->tree_nodes, P->perm, false, 2, B, nrhs, P->n);
+        case CholRoute::Local: {
+            const size_t per_wave = (size_t)P->max_nodes * 64 * sizeof(double);
+            const int waves = tile_waves_per_workgroup(per_wave, CH_WAVES);
+            const int32_t chunks = (nrhs + 63) / 64;
+            const int64_t tasks = (int64_t)P->ntrees * chunks;
+            const size_t lds = per_wave * (size_t)waves;
+            CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_cholsol_local),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+            if (!P->trees_by_size) CSX_TRY(trees_biggest_first(P->trees, P->ntrees, P->max_nodes, &P->trees_by_size));
+            hipLaunchKernelGGL(k_cholsol_local, dim3((unsigned)((tasks + waves - 1) / waves)), dim3(64 * waves), lds, s,
+                               P->trees_by_size, P->ntrees, P->tree_nodes, P->perm, P->f_ptr, P->f_idx, P->f_val, P->b_ptr, P->b_idx,
+                               P->b_val, P->diagk, P->diagb, B, nrhs, chunks, P->max_nodes, waves);
+            CSX_LAUNCH_CHECK();
+            return CSX_OK;
+        }
+        case CholRoute::Supernodal: case CholRoute::Levels: break;
     }
+    // the two triangular solves of the general plan, the rows permuted in and out around them
     double *X = B;
     if (P->perm) {
         const int64_t need = (int64_t)n * nrhs;
@@ -2480,7 +2528,10 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
         X = P->scratch;
         hipLaunchKernelGGL(k_perm_rows, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, s, P->perm, B, X, n, nrhs, 1);
     }
-    if (P->relaxed && P->sn && ctx().opt.tri_supernodes && sn_usable(P->sn)) {
+    if (route == CholRoute::Supernodal) {
+        const int32_t *Gp, *Gi;
+        const double *Gx, *Gd;
+        tri_gather_arrays(P->fwd, &Gp, &Gi, &Gx, &Gd);
         CSX_TRY(tri_solve_raw(P->fwd, X, 0, false));          // a zero pivot found by the analysis: ZeroDivisionError
         // "tri.graph": 1 = always; 2 (the default) = when a solve is many launches -- more than 256: a natural-order grid
         // factor is 5 624 -- and this block has been the block of the two solves before this one as well (round 4 captured on
@@ -2570,6 +2621,21 @@ namespace csx {
 static int g_factor_path = -1;
 static double g_factor_ms[3] = {0.0, 0.0, 0.0};   // analysis / numeric kernel (HIP events) / whole call (host clock)
 
+// a plan on L that is the block list of the forest F so far (every block one tree, on consecutive columns); `lite`: and nothing else
+// ever but what its solves need (see CholPlan::lite)
+static int cholsol_plan_blocks(Csc *L, const CliqueForest &F, bool lite, std::unique_ptr<CholPlan> *out) {
+    out->reset(new CholPlan(L));   // (the caller frees it on any error)
+    CholPlan *P = out->get();
+    P->lite = lite;
+    P->lite_cliques = lite && !F.sparse;
+    P->local = true;
+    P->ntrees = F.nblocks;
+    P->max_nodes = F.max_bs;
+    CSX_TRY(P->trees.alloc((size_t)F.nblocks));
+    CSX_TRY(P->tree_nodes.alloc((size_t)P->n));
+    return ragged_blocks(F.start, F.nblocks, P->n, P->trees, P->tree_nodes);
+}
+
 static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, std::unique_ptr<CholPlan> *Pout) {   // (A->clique may be replaced)
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
@@ -2593,7 +2659,7 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
         g_factor_ms[0] = since(t_call);
         if (ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
             const int32_t bs = F.max_bs;
-            const bool emit = !exact && !F.sparse && F.min_bs == bs && (bs == 16 || bs == 32 || bs == 64) && ctx().opt.cholsol_dense_blocks;
+            const bool emit = !exact && equal_dense_blocks(F) && bs >= 16 && ctx().opt.cholsol_dense_blocks;
             L->m = L->n = n;
             L->nnz = (int32_t)F.lnz;
             L->owns = true;
@@ -2612,32 +2678,21 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
             CSX_TRY(d_flags.alloc(4));
             CSX_HIP(hipMemsetAsync(d_flags, 0x7f, sizeof(int), s));
             CSX_HIP(hipMemsetAsync(d_flags + 2, 0, 2 * sizeof(int), s));
+            em.cond_bits = (unsigned long long *)(d_flags + 2);   // (read by the kernel only with an emission)
             // cliques of UNEQUAL sizes, rounding-equal order: the block kernel writes the matrix-core operands of csx_trimfma.hip's
             // size classes itself (the class-ordered list, descriptors and fragment storage are made first: the kernel needs to know
             // where each block's fragments go)
-            const bool emit_ragged = !emit && !exact && !F.sparse && ctx().opt.cholsol_dense_blocks &&
-                                     !(F.min_bs == bs && (bs == 8 || bs == 16 || bs == 32 || bs == 64));
+            const bool emit_ragged = !emit && !exact && !F.sparse && ctx().opt.cholsol_dense_blocks && !equal_dense_blocks(F);
             std::unique_ptr<RaggedMfma> Rg;
             DevBuf<int64_t> frag_off;
             if (emit_ragged) {
-                Pout->reset(new CholPlan());
+                CSX_TRY(cholsol_plan_blocks(L, F, true, Pout));
                 P = Pout->get();
-                P->n = n;
-                P->L = L;
-                P->lite = true;
-                P->lite_cliques = true;
-                P->local = true;
                 P->relaxed = true;
-                P->ntrees = F.nblocks;
-                P->max_nodes = bs;
-                CSX_TRY(P->trees.alloc((size_t)F.nblocks));
-                CSX_TRY(P->tree_nodes.alloc((size_t)n));
-                CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
                 CSX_TRY(ragged_prepare_emit(P->trees, P->ntrees, bs, P->tree_nodes, &Rg, &frag_off));
                 if (Rg) {
                     em.frag = Rg->frag;
                     em.frag_off = frag_off;
-                    em.cond_bits = (unsigned long long *)(d_flags + 2);
                     em.list = Rg->list;
                     for (int c = 0; c <= RAG_CLASSES; c++) em.cls_start[c] = Rg->cls_start[c];
                 }
@@ -2645,23 +2700,18 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
             const bool emit_any = emit || (emit_ragged && Rg);
             if (!emit_any) CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
             if (emit) {
-                Pout->reset(new CholPlan());   // (the caller frees it on any error)
+                Pout->reset(new CholPlan(L));   // (the caller frees it on any error)
                 P = Pout->get();
-                P->n = n;
-                P->L = L;
                 CSX_TRY(P->frag_f.alloc((size_t)F.nblocks * (size_t)(bs / 16) * 256));   // the W tiles; the rest is L.x
                 CSX_TRY(P->trees.alloc((size_t)F.nblocks));
                 CSX_TRY(P->tree_nodes.alloc((size_t)n));
                 em.frag = P->frag_f;
-                em.cond_bits = (unsigned long long *)(d_flags + 2);
                 em.trees = P->trees;
                 em.tree_nodes = P->tree_nodes;
             }
             hipEvent_t ev_a = nullptr, ev_b = nullptr;
-            if (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess) {
-                if (ev_a) (void)hipEventDestroy(ev_a);
-                return CSX_ERUNTIME;
-            }
+            EvGuard ev_guard{ev_a, ev_b};
+            if (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess) return CSX_ERUNTIME;
             (void)hipEventRecord(ev_a, s);
             int st = chol_clique_numeric(A, F, L, d_flags, emit_any ? &em : nullptr, !ctx().opt.chol_exact);
             (void)hipEventRecord(ev_b, s);
@@ -2670,18 +2720,15 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
             if (hipStreamSynchronize(s) != hipSuccess) st = st == CSX_OK ? CSX_ERUNTIME : st;   // (also on failure: L's arrays go back to the pool)
             float ms = 0.0f;
             if (st == CSX_OK && hipEventElapsedTime(&ms, ev_a, ev_b) == hipSuccess) g_factor_ms[1] = ms;
-            (void)hipEventDestroy(ev_a);
-            (void)hipEventDestroy(ev_b);
             CSX_TRY(st);
             if (h[0] != 0x7f7f7f7f) return CSX_ENOTSPD;
             g_chol_path = F.sparse ? 2 : 1;
             g_chol_numeric_ms = g_factor_ms[1];
+            L->rows_pending = L->i == nullptr;   // (emitted) rows j, j + 1, ... in every column: made from L.p when a handle to L is resolved
+            double growth = 0.0;                 // (emitted) the guard's measure of the matrix-core operands
+            std::memcpy(&growth, h + 2, sizeof growth);
             if (emit) {
-                L->rows_pending = true;       // rows j, j + 1, ... in every column: made from L.p when a handle to L is resolved
-                double growth = 0.0;
-                std::memcpy(&growth, h + 2, sizeof growth);
-                P->clique = true;
-                P->clique_zero_pivot = false;  // every pivot is a square root of a positive number
+                P->clique = true;              // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
                 P->ntrees = F.nblocks;
                 P->max_nodes = bs;
                 P->local = true;
@@ -2695,70 +2742,39 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
             } else if (emit_ragged) {
                 // the plan was made before the kernel ran (above); its matrix-core operands are in place
                 if (Rg) {
-                    L->rows_pending = L->i == nullptr;
-                    double growth = 0.0;
-                    std::memcpy(&growth, h + 2, sizeof growth);
                     Rg->growth = growth;
                     P->mfma_growth = growth;
                     P->rag_tried = true;
                     if (growth <= MFMA_GROWTH_LIMIT)         // (max|L| max|W| of a block, the equal-block path's measure; a NaN fails)
                         P->rag = std::move(Rg);
-                } else if (!L->i) {
-                    L->rows_pending = true;
                 }
                 g_factor_path = 1;
-            } else if (ctx().opt.cholsol_dense_blocks && (!exact || !F.sparse) &&
-                       !(!F.sparse && F.min_bs == bs && (bs == 8 || bs == 16 || bs == 32 || bs == 64))) {
-                // a forest of UNEQUAL cliques (either order) or of small sparse trees (rounding-equal order): the plan is the block
-                // list from the forest's starts; the matrix-core operands come straight from L's columns (now, or when the order is
-                // switched), the exact order of cliques runs on padded size classes cut out of L.x at the first such solve
-                // (cholsol_exact_classes_build) -- no general plan unless a solve needs one
-                Pout->reset(new CholPlan());
-                P = Pout->get();
-                P->n = n;
-                P->L = L;
-                P->lite = true;
-                P->lite_cliques = !F.sparse;
-                P->local = true;
-                P->relaxed = !exact;
-                P->ntrees = F.nblocks;
-                P->max_nodes = bs;
-                CSX_TRY(P->trees.alloc((size_t)F.nblocks));
-                CSX_TRY(P->tree_nodes.alloc((size_t)n));
-                CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
-                if (!exact) CSX_TRY(cholsol_build_ragged(P));
-                g_factor_path = F.sparse ? 2 : 1;
             } else {
-                if (!F.sparse && F.min_bs == bs && (bs == 8 || bs == 16 || bs == 32 || bs == 64) && ctx().opt.cholsol_dense_blocks) {
-                    // equal dense blocks (the forest's record says so: no k_clique_factor_shape over L.i): the programs straight from L.x
-                    Pout->reset(new CholPlan());
+                if (ctx().opt.cholsol_dense_blocks && (!exact || !F.sparse) && !equal_dense_blocks(F)) {
+                    // a forest of UNEQUAL cliques (either order) or of small sparse trees (rounding-equal order): the plan is the block
+                    // list; the matrix-core operands come straight from L's columns (now, or when the order is switched), the exact order
+                    // of cliques runs on padded size classes cut out of L.x at its first solve -- no general plan unless a solve needs one
+                    CSX_TRY(cholsol_plan_blocks(L, F, true, Pout));
                     P = Pout->get();
-                    P->n = n;
-                    P->L = L;
+                } else if (equal_dense_blocks(F) && ctx().opt.cholsol_dense_blocks) {
+                    // equal dense blocks (the forest's record says so: no k_clique_factor_shape over L.i): the programs straight from L.x
                     if (exact) {
                         // every solve in the reference's order: the default exact kernel reads L.x itself (k_cholsol_dense_exact_dpp<PACKED>),
                         // so the plan is the block list; programs are cut out of L.x only if another kernel is asked for (cholsol_solve)
-                        CSX_TRY(P->trees.alloc((size_t)F.nblocks));
-                        CSX_TRY(P->tree_nodes.alloc((size_t)n));
-                        CSX_TRY(ragged_blocks(F.start, F.nblocks, n, P->trees, P->tree_nodes));
-                        P->clique = true;
-                        P->clique_zero_pivot = false;      // every pivot is a square root of a positive number
-                        P->ntrees = F.nblocks;
-                        P->max_nodes = bs;
-                        P->local = true;
+                        CSX_TRY(cholsol_plan_blocks(L, F, false, Pout));
+                        P = Pout->get();
+                        P->clique = true;              // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
                         P->dense_bs = bs;
                     } else {
+                        Pout->reset(new CholPlan(L));
+                        P = Pout->get();
                         CSX_TRY(cholsol_plan_clique(P, bs));
                     }
                 } else {
                     CSX_TRY(cholsol_plan(L, nullptr, Pout));
                     P = Pout->get();
                 }
-                if (!exact) {
-                    P->relaxed = true;
-                    CSX_TRY(cholsol_build_mfma(P));
-                    CSX_TRY(cholsol_build_sn(P));
-                }
+                if (!exact) CSX_TRY(cholsol_relax(P));
                 g_factor_path = F.sparse ? 2 : 1;
             }
             g_factor_ms[2] = since(t_call);
@@ -2772,11 +2788,7 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
     CSX_TRY(chol_device(A, parent.data(), cp.data(), nullptr, L));
     g_factor_ms[1] = g_chol_numeric_ms;
     CSX_TRY(cholsol_plan(L, nullptr, Pout));
-    if (!exact) {
-        (*Pout)->relaxed = true;
-        CSX_TRY(cholsol_build_mfma(Pout->get()));
-        CSX_TRY(cholsol_build_sn(Pout->get()));
-    }
+    if (!exact) CSX_TRY(cholsol_relax(Pout->get()));
     g_factor_path = 0;
     g_factor_ms[2] = since(t_call);
     return CSX_OK;
@@ -2824,20 +2836,8 @@ extern "C" int csx_cholsol_plan(csx_handle_t hL, const int32_t *pinv, csx_handle
 extern "C" int csx_cholsol_info(csx_handle_t h, int32_t *local, int32_t *ntrees, int32_t *max_nodes) {
     CholPlan *P = (CholPlan *)get(h, K_CHOLPLAN);
     if (!P) return CSX_EINVAL;
-    // 0 level-scheduled, 1 fused in LDS, 2 dense blocks (substitution), 3 dense blocks on the matrix cores, 4 supernodal schedule,
-    // 5 small trees of any shape made dense by size class on the matrix cores (csx_trimfma.hip)
-    if (P->lite && P->lite_cliques && !(P->relaxed && P->rag) && ctx().opt.cholsol_dense_blocks) {
-        if (local) *local = 2;               // dense-block substitution (padded size classes), the exact order
-        if (ntrees) *ntrees = P->ntrees;
-        if (max_nodes) *max_nodes = P->max_nodes;
-        return CSX_OK;
-    }
-    if (P->lite && !(P->relaxed && P->rag)) {   // the general plan answers (made now if it has to be)
-        if (!P->full) CSX_TRY(cholsol_plan(P->L, nullptr, &P->full));
-        P->full->relaxed = false;
-        P = P->full.get();
-    }
-    if (local) *local = P->local ? (P->dense_bs ? (P->relaxed && P->frag_f ? 3 : 2) : (P->relaxed && P->rag ? 5 : 1)) : (P->relaxed && P->sn && sn_usable(P->sn) ? 4 : 0);
+    if (cholsol_route(P) == CholRoute::Full) CSX_TRY(cholsol_full(&P));   // the general plan answers (made now if it has to be)
+    if (local) *local = kCholRoutePath[(int)cholsol_route(P)];
     if (ntrees) *ntrees = P->ntrees;
     if (max_nodes) *max_nodes = P->max_nodes;
     return CSX_OK;
@@ -2847,9 +2847,8 @@ extern "C" int csx_cholsol_set_order(csx_handle_t h, int exact) {
     CSX_TRY(require_ready());
     CholPlan *P = (CholPlan *)get(h, K_CHOLPLAN);
     if (!P) return CSX_EINVAL;
-    P->relaxed = exact == 0;
-    if (P->relaxed) CSX_TRY(cholsol_build_mfma(P));
-    if (P->relaxed) CSX_TRY(cholsol_build_sn(P));
+    if (!exact) return cholsol_relax(P);
+    P->relaxed = false;
     return CSX_OK;
 }
 

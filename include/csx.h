@@ -289,13 +289,16 @@ int csx_cholsol_factor(csx_handle_t A, int exact, csx_handle_t *L, csx_handle_t 
  * csx_cholsol_plan behind the one entry).  *analysis_ms: host clock up to the end of the symbolic analysis; *numeric_ms: HIP-event
  * time of the numeric kernel(s); *call_ms: host clock of the whole call.  Any pointer may be NULL. */
 int csx_cholsol_factor_info(int32_t *path, double *analysis_ms, double *numeric_ms, double *call_ms);
-/* *path, for the plan's current order (csx_cholsol_set_order): 0 = level-scheduled generic, 1 = fused per-tree
- * kernel (X tile in LDS; the only forest path of the default, exact order), 2 = dense-block FMA substitution,
- * 3 = dense blocks as a blocked TRSM on the matrix cores (fp64 MFMA; blocks of 16/32/64 whose block inverses
- * are benign); 4 = supernodal schedule of a big elimination tree (csx_cholsol_sn_info); 5 = a forest of small trees that are not
- * equal dense blocks (cliques of unequal sizes, small sparse trees, at most 80 columns each) made dense tree by tree, bucketed by
- * size class (16 / 32 / 48 / 64 / 80) and solved on the matrix cores (round 5; guard: || |inv(T_ii)| |T_ii| ||_inf <= 1e3 for every
- * diagonal tile); 2 - 5 only in the rounding-equal order */
+/* *path: the route the plan's next solve takes, in its current order (csx_cholsol_set_order) and under the options in force --
+ * with "cholsol.dense_blocks" = 0 a forest of dense blocks reports 1, not 2 or 3.  0 = level-scheduled generic, 1 = fused
+ * per-tree kernel (X tile in LDS), 2 = dense-block substitution (the reference's operations in the exact order -- cliques of
+ * unequal sizes padded to size classes included -- FMA in the rounding-equal order), 3 = dense blocks as a blocked TRSM on the
+ * matrix cores (fp64 MFMA; blocks of 16/32/64 whose block inverses are benign); 4 = supernodal schedule of a big elimination
+ * tree (csx_cholsol_sn_info); 5 = a forest of small trees that are not equal dense blocks (cliques of unequal sizes, small sparse
+ * trees, at most 80 columns each) made dense tree by tree, bucketed by size class (16 / 32 / 48 / 64 / 80) and solved on the
+ * matrix cores (round 5; guard: || |inv(T_ii)| |T_ii| ||_inf <= 1e3 for every diagonal tile); 3 - 5 only in the rounding-equal
+ * order.  A plan of csx_cholsol_factor whose solve goes to the general plan of the same factor reports that plan's route, trees
+ * and largest tree (the general plan is made by this call if no solve has made it yet). */
 int csx_cholsol_info(csx_handle_t plan, int32_t *path, int32_t *ntrees, int32_t *max_nodes);
 int csx_cholsol_solve(csx_handle_t plan, csx_handle_t B, int32_t nrhs);
 /* exact = 1 (the default of every plan): every right-hand side is solved in the reference's operation order,

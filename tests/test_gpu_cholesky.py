@@ -153,10 +153,12 @@ def test_gspd_factor_and_batched_solve(cs, nblocks, bs, k):
     for r, ref in refs.items():
         assert X[:, r].tobytes() == ref.tobytes(), r
     # the fused per-tree kernel (what forests of non-dense trees use) gives the same bits
+    fused = {"fused_local": True, "dense_block": 0, "matrix_cores": False, "trees": nblocks, "max_nodes": bs}
     with _csx.option("cholsol.dense_blocks", 0):
         dB1 = cs.dvec(B)
         assert F.solve(dB1) is True
         assert dB1.numpy().tobytes() == X.tobytes()
+        assert F.info() == fused                  # csx_cholsol_info under the option: the route the solve took
     # rounding-equal order: blocked TRSM on the matrix cores for 16/32/64 blocks, FMA substitution for 8
     Ff = cs.cholsol_factor(A, exact=False)
     assert Ff.info()["dense_block"] == bs and Ff.info()["matrix_cores"] is (bs >= 16)
@@ -170,6 +172,7 @@ def test_gspd_factor_and_batched_solve(cs, nblocks, bs, k):
         dB2 = cs.dvec(B)
         assert Ff.solve(dB2) is True
         assert dB2.numpy().tobytes() == X.tobytes()
+        assert Ff.info() == fused
     # residual of the whole block against A (symmetric, full storage)
     R = np.stack([CO.gaxpy(n, n, Ap, Ai, Ax, X[:, r], -B[:, r]) for r in (0, k - 1)], axis=1)
     assert np.max(np.abs(R)) < 1e-12 * np.max(np.abs(B)) * bs

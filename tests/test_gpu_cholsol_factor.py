@@ -141,6 +141,32 @@ def test_one_call_equals_the_three_calls(cs, case, exact):
         _csx.free(h)
 
 
+def test_general_plan_of_a_factor_whose_rows_are_pending(cs):
+    """Through the C ABI only: csx_cholsol_factor on cliques of unequal sizes in the rounding-equal order, where the block kernel
+    writes the matrix-core operands and leaves L.i to be made (Csc::rows_pending), and the L handle is not touched.  With
+    "cholsol.dense_blocks" = 0 the info and the solve go to the general plan of the same factor, which reads L.i: the rows are
+    made first.  The info names the route the solve takes (the fused per-tree kernel, path 1); the solve is cs_lsolve +
+    cs_ltsolve on L bit for bit."""
+    import _csx
+    rng = np.random.default_rng(3)
+    sizes = list(rng.integers(1, 65, 260)) + [64, 1, 2, 16, 17, 48, 49]
+    n, Ap, Ai, Ax = _blocks(sizes, 21)              # tests/test_gpu_trimfma.py's unequal cliques
+    A = cs.cs_pin(_host_cs(cs, n, n, Ap, Ai, Ax))
+    st, hL, plan, path = _fused(A, False)
+    assert st == _csx.OK and path == 1
+    k = 70
+    B = synth.rhs(n, k, 2)
+    with _csx.option("cholsol.dense_blocks", 0):
+        assert _info(plan) == (1, len(sizes), 64)
+        X = _solve(plan, B)
+    p, i, x = _download(hL)                         # only now
+    for r in (0, 35, k - 1):
+        ref = CO.ltsolve(n, p, i, x, CO.lsolve(n, p, i, x, B[:, r]))
+        assert X[:, r].tobytes() == ref.tobytes(), r
+    for h in (plan, hL):
+        _csx.free(h)
+
+
 def test_not_positive_definite_and_the_guard(cs):
     import _csx
     lib = _csx.lib()

@@ -238,6 +238,8 @@ def test_cholsol_forests_of_small_trees_on_the_matrix_cores(cs, shape):
         dB1 = cs.dvec(B)
         assert F.solve(dB1) is True
         assert dB1.numpy().reshape(n, k)[:, 35].tobytes() == ref.tobytes()
+        _csx.check(_csx.lib().csx_cholsol_info(F.plan_handle, path, None, None))
+        assert path.value == 1                             # csx_cholsol_info under the option: the route the solve took
 
 
 @pytest.mark.parametrize("k", [1, 70, 128, 200])
@@ -271,6 +273,8 @@ def test_exact_order_on_unequal_cliques_by_padded_size_classes(cs, k):
         dB1 = cs.dvec(B if k > 1 else B[:, 0].copy())
         assert F.solve(dB1) is True
         assert dB1.numpy().tobytes() == dB.numpy().tobytes()
+        _csx.check(_csx.lib().csx_cholsol_info(F.plan_handle, path, None, None))
+        assert path.value == 1                              # csx_cholsol_info under the option: the route the solve took
 
 
 @pytest.mark.parametrize("nrhs", [9, 70, 128, 192])
