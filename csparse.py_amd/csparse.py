@@ -1055,6 +1055,95 @@ def cs_updown(L, sigma, C, parent):
     return bool(ok.value)
 
 
+_UPDOWN_INFO = [None]
+
+
+def _updown_sigma(sigma, k):
+    """+1, -1 or k values each +1 / -1 -> int32 array of k; ValueError otherwise"""
+    if isinstance(sigma, (int, float, np.integer, np.floating)):
+        sg = np.full(k, int(sigma) if sigma in (1, -1) else 0, dtype=np.int32)
+        bad = sigma not in (1, -1)
+    else:
+        v = np.asarray(sigma, dtype=np.float64).ravel()
+        bad = len(v) != k or not np.all((v == 1.0) | (v == -1.0))
+        sg = v.astype(np.int32) if not bad else None
+    if bad:
+        raise ValueError("updown_block: sigma must be +1, -1 or a sequence of %d values, each +1 or -1" % k)
+    return sg
+
+
+def _updown_block_call(L, sg, C, parent, flags):
+    """csx_updown_block on L (in place, as cs_updown: plans freed, version bumped, host lists updated) -> applied"""
+    n = L.n
+    par = None
+    if parent is not None:
+        if len(parent) < n:
+            raise ValueError("updown_block: parent is not the elimination tree of L")
+        par = _csx.i32(parent[:n])
+    applied = _csx.C.c_int32(0)
+    t0 = time.perf_counter()
+    lazy = L._lazy
+    with _Resident(L) as dL, _Resident(C) as dC:
+        st = _csx.lib().csx_updown_block(dL.handle, dC.handle, _csx.pi(sg), None if par is None else _csx.pi(par), flags, applied)
+        if st == _csx.EINVAL:
+            raise IndexError("list index out of range")
+        _csx.check(st, "csx_updown_block")
+        a = applied.value
+        if a == -2:
+            raise ValueError("updown_block: parent is not the elimination tree of L")
+        changed = a > 0 or (0 <= a < C.n and not flags & 1)
+        if changed:
+            for h in dL.plans.values():          # triangular-solve plans hold copies of the old values
+                _csx.free(h)
+            dL.plans.clear()
+            dL.version += 1                      # cholsol_factor solvers built on this factor re-plan at their next solve
+            if not lazy and L._x is not None:    # the caller holds L.x: update that list in place, like the reference
+                _, _, nnz, _ = dL.info()
+                x = np.empty(max(nnz, 1), dtype=np.float64)
+                _csx.check(_csx.lib().csx_csc_download(dL.handle, None, None, _csx.pd(x)), "csx_csc_download")
+                L._x[:nnz] = x[:nnz].tolist()
+    ch, uc, gr, ms = _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_double(0.0)
+    _csx.check(_csx.lib().csx_updown_block_info(ch, uc, gr, ms), "csx_updown_block_info")
+    _UPDOWN_INFO[0] = {"columns": C.n, "applied": a, "chunks": ch.value, "union_columns": uc.value, "groups": gr.value,
+                       "kernel_ms": ms.value, "wall_ms": 1e3 * (time.perf_counter() - t0)}
+    return a
+
+
+def updown_block(L, sigma, C, parent=None):
+    """k rank-1 updates / downdates at once: L L' + sum_t sigma_t w_t w_t', w_t = column t of the n-by-k CSC C, read as cs_updown
+    (csparse.py:2318-2365) reads its C (a later duplicate row wins; rows off the path of f_t = min row of C(:,t) never read).
+    L (cs_chol's: diagonal first, rows ascending; list-backed or on the device) is changed in place exactly as
+        for t in range(k):
+            if not cs_updown(L, sigma[t], C[:, t], parent): break
+    changes it, byte for byte, in ONE device pass over the union of the terms' elimination-tree paths.
+    sigma: +1, -1, or k values each +1 / -1.  parent: None (read from L on the device) or L's elimination tree (checked).
+    Returns the number of columns applied in full: k on success, t when the downdate of column t is not positive definite (L
+    is then the loop's partial state).  An empty column is a success that changes nothing.  IndexError for a row out of range;
+    ValueError for a bad sigma, C.m != L.n or a parent that is not L's tree (L unchanged).  updown_info(): the last call's
+    columns, chunks, union columns, groups, kernel ms and wall ms."""
+    if not CS_CSC(L) or not CS_CSC(C):
+        raise ValueError("updown_block: L and C must be CSC matrices")
+    if not _meta(L)[1]:
+        raise TypeError("'NoneType' object is not subscriptable")
+    if C.m != L.n or L.m != L.n:
+        raise ValueError("updown_block: C has %d rows, L has %d columns" % (C.m, L.n))
+    k = C.n
+    sg = _updown_sigma(sigma, k)
+    if k == 0:
+        _UPDOWN_INFO[0] = {"columns": 0, "applied": 0, "chunks": 0, "union_columns": 0, "groups": 0, "kernel_ms": 0.0,
+                           "wall_ms": 0.0}
+        return 0
+    if not _meta(C)[1]:
+        raise TypeError("'NoneType' object is not subscriptable")
+    return _updown_block_call(L, sg, C, parent, 0)
+
+
+def updown_info():
+    """the last updown_block's (or cholsol_factor update / downdate's) columns, applied, chunks, union columns, groups,
+    kernel ms and wall ms"""
+    return dict(_UPDOWN_INFO[0]) if _UPDOWN_INFO[0] is not None else None
+
+
 def _solve_blocks_sharded(comm, b, nrhs, rows_in, rows_out, solve_block):
     """A batch of right-hand sides sharded by column block over the ranks of `comm` (independent units, no
     collective inside a block's solve).  The root (rank 0) passes b, a dvec rows_in-by-K block (or a list: K = 1); the
@@ -1301,6 +1390,42 @@ def cholsol_factor(A, order=0, exact=None):
             _csx.check(_csx.lib().csx_cholsol_solve(self._plan_for(isinstance(b, dvec)), db.handle, db.k), "csx_cholsol_solve")
             _write_back(bhost, db, n * db.k)
             return True
+
+        def _updown(self, C, sigma):
+            if not CS_CSC(C) or C.m != n:
+                raise ValueError("update / downdate: C must be a CSC matrix with %d rows" % n)
+            if pinv is not None and C.n > 0:      # L L' = P A P': rows of A are rows pinv[i] of L
+                with _Resident(C) as dC:
+                    h = _csx.new_handle()
+                    st = _csx.lib().csx_permute(dC.handle, _csx.pi(pinv), None, 1, h)
+                if st == _csx.EINVAL:
+                    raise IndexError("list index out of range")
+                _csx.check(st, "csx_permute")
+                C = _from_device(h, lambda nnz: max(nnz, 1))
+            sg = np.full(C.n, sigma, dtype=np.int32)
+            if C.n == 0:
+                _UPDOWN_INFO[0] = {"columns": 0, "applied": 0, "chunks": 0, "union_columns": 0, "groups": 0,
+                                   "kernel_ms": 0.0, "wall_ms": 0.0}
+                return True
+            a = _updown_block_call(N.L, sg, C, None, 3)
+            if a == -1:
+                raise ValueError("update / downdate: a column of C reaches outside the pattern of L(:, f)")
+            return a == C.n
+
+        def update(self, C):
+            """L L' + C C' in place (C: n-by-k CSC in A's row numbering; rows through pinv for order >= 1), in one pass
+            (updown_block).  Every row of C(:,t) must lie in the pattern of L(:, f_t), f_t its first row in L's numbering
+            (the factor's pattern does not change): ValueError otherwise, nothing changed.  True.  The plans are rebuilt
+            from the new values at the next solve; updown_info() reports the call."""
+            return self._updown(C, 1)
+
+        def downdate(self, C):
+            """L L' - C C' in place, as update(C).  All or nothing: False when a downdate is not positive definite, and then
+            L.x and the solves are exactly as before."""
+            return self._updown(C, -1)
+
+        def updown_info(self):
+            return updown_info()
 
         def _solve_sharded(self, b, comm, nrhs):
             # every rank solves in the order the ROOT's right-hand side asks for

@@ -355,6 +355,23 @@ int csx_csc_col_block(csx_handle_t A, int32_t first, int32_t count, csx_handle_t
 int csx_updown(csx_handle_t L, int sigma, int32_t cnz, const int32_t *Ci, const double *Cx, const int32_t *parent,
                int *ok);
 
+/* updown_block: the k rank-1 terms L L' + sigma[t] w_t w_t', w_t = column t of C (device, n x k; rows
+ * assigned in storage order, a later duplicate wins; rows off the path of f_t = min row of C(:,t) never read), applied to the
+ * device factor L (diagonal first, rows ascending) in ONE pass over the union of their elimination-tree paths.  L.x comes out
+ * byte-equal to `for t in 0..k-1: if (!cs_updown(L, sigma[t], C(:,t))) break`.  sigma: host, k values, each +1 or -1.
+ * parent: host, n, or NULL: the tree is read from L (parent[j] = the row of the second entry of column j, -1 for none); a
+ *   given parent is checked against it on the device.
+ * flags: 1 all or nothing (a downdate that is not positive definite leaves L as it was), 2 check that every row of C(:,t) lies
+ *   in the pattern of L(:, f_t).
+ * *applied: k on success (empty columns are successes that change nothing); t when the downdate of column t is not positive
+ *   definite (without flag 1 L is then the loop's partial state; with it, unchanged); -1 the pattern check failed (nothing
+ *   changed); -2 parent is not L's elimination tree (nothing changed).  CSX_EINVAL for a row out of range, a sigma other than
+ *   +1 / -1, C->m != n, or an L that is not Cholesky-shaped along the paths (nothing changed).
+ * csx_updown_block_info: the last call's chunks (64 terms of a tree per chunk), union columns and groups (trees, summed over
+ *   the chunks) and the time of its block kernels. */
+int csx_updown_block(csx_handle_t L, csx_handle_t C, const int32_t *sigma, const int32_t *parent, int flags, int32_t *applied);
+int csx_updown_block_info(int32_t *chunks, int32_t *union_columns, int32_t *groups, double *kernel_ms);
+
 /* cs_lu, csparse.py:1370-1451 (+ cs_spsolve :2078-2113), natural column order: host C++
  * left-looking LU with threshold partial pivoting.  It produces the L (unit diagonal first)
  * and U (diagonal last) that cs_lsolve / cs_usolve consume in cs_lusol (csparse.py:1474-1477).
