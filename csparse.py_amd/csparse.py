@@ -25,6 +25,7 @@ What runs where
   * Host-side glue that the reference also does in Python (triplet assembly,
     cs_cumsum, cs_scatter on lists, permutation of a single list) stays Python.
 """
+import math
 import os
 import time
 import weakref
@@ -1144,6 +1145,56 @@ def updown_info():
     return dict(_UPDOWN_INFO[0]) if _UPDOWN_INFO[0] is not None else None
 
 
+_SPARSEINV_INFO = [None]
+
+
+def _last_error():
+    return _csx.lib().csx_last_error().decode("utf-8", "replace")
+
+
+def sparseinv(L):
+    """Z = inv(L L') on the pattern of the Cholesky factor L (cs_chol's: diagonal first and positive, rows ascending;
+    list-backed or on the device), by the Takahashi recurrence: a device-backed `cs` with L's p and i whose x
+    holds the lower triangle of the symmetric inverse at those positions, byte-equal to
+        for j = n-1 .. 0, d = L(j,j), S = rows of column j below the diagonal in storage order:
+            for i in S: Z(i,j) = (-sum_{k in S} L(k,j) * Zs(i,k)) / d          (Zs(a,b) = the stored Z(max(a,b), min(a,b)))
+            Z(j,j) = (1/d - sum_{k in S} L(k,j) * Z(k,j)) / d
+    with every product and sum rounded on its own.  L is not changed.  ValueError with the library's message for a matrix that
+    is not such a factor (rectangular, no values, an empty column, a diagonal that is not first, positive and finite, rows out
+    of order, a pattern that is not a Cholesky pattern).  sparseinv_info(): the last call's depths, widest depth, terms and
+    kernel ms."""
+    if not CS_CSC(L):
+        raise ValueError("sparseinv: L must be a CSC matrix")
+    t0 = time.perf_counter()
+    h = _csx.new_handle()
+    with _Resident(L) as dL:
+        st = _csx.lib().csx_chol_inverse(dL.handle, h)
+    if st == _csx.EINVAL:
+        raise ValueError("sparseinv: " + _last_error())
+    _csx.check(st, "csx_chol_inverse")
+    d, w, t, ms = _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_int64(0), _csx.C.c_double(0.0)
+    _csx.check(_csx.lib().csx_chol_inverse_info(d, w, t, ms), "csx_chol_inverse_info")
+    _SPARSEINV_INFO[0] = {"n": L.n, "depths": d.value, "widest": w.value, "terms": t.value, "kernel_ms": ms.value,
+                          "wall_ms": 1e3 * (time.perf_counter() - t0)}
+    return _from_device(h, lambda nnz: max(nnz, 1))
+
+
+def sparseinv_info():
+    """the last sparseinv's (or cholsol_factor inverse / inverse_diag's) n, depths of the elimination forest (= launches unless
+    runs of one-column depths were walked), columns in the widest depth, terms (sum of |S_j|^2), kernel ms and wall ms"""
+    return dict(_SPARSEINV_INFO[0]) if _SPARSEINV_INFO[0] is not None else None
+
+
+def _first_entries(M):
+    """value of the first entry of every column of a device-backed matrix (csx_csc_diag) as a numpy array"""
+    out = dvec(M.n)
+    st = _csx.lib().csx_csc_diag(M._dev.handle, out.handle)
+    if st == _csx.EINVAL:
+        raise ValueError(_last_error())
+    _csx.check(st, "csx_csc_diag")
+    return out.numpy()
+
+
 def _solve_blocks_sharded(comm, b, nrhs, rows_in, rows_out, solve_block):
     """A batch of right-hand sides sharded by column block over the ranks of `comm` (independent units, no
     collective inside a block's solve).  The root (rank 0) passes b, a dvec rows_in-by-K block (or a list: K = 1); the
@@ -1426,6 +1477,21 @@ def cholsol_factor(A, order=0, exact=None):
 
         def updown_info(self):
             return updown_info()
+
+        def inverse(self):
+            """Z = inv(L L') on the pattern of L (sparseinv): a device-backed `cs` in L's numbering -- for order >= 1 its rows
+            and columns are those of P A P' (symbolic.pinv maps A's).  Computed from the factor as it stands (after update /
+            downdate / cs_updown: the new values); nothing is kept between calls."""
+            return sparseinv(N.L)
+
+        def inverse_diag(self):
+            """diag(inv(A)) as a numpy array, entry i = inv(A)(i,i) in A's numbering"""
+            d = _first_entries(self.inverse())
+            return d if pinv is None else d[pinv]
+
+        def logdet(self):
+            """log det A = 2 sum_j log L(j,j), the sum correctly rounded (math.fsum)"""
+            return 2.0 * math.fsum(np.log(_first_entries(N.L)).tolist())
 
         def _solve_sharded(self, b, comm, nrhs):
             # every rank solves in the order the ROOT's right-hand side asks for

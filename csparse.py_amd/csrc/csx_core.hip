@@ -558,7 +558,7 @@ const OptSlot kOptSlots[] = {
     {"tri.graph", &Options::tri_graph, 6},               {"sort.short_keys", &Options::sort_short_keys, 0},
     {"chol.clique", &Options::chol_clique, 0},           {"chol.forest", &Options::chol_forest, 0},
     {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
-    {"gaxpy.block_route", &Options::gaxpy_block_route, 3},
+    {"gaxpy.block_route", &Options::gaxpy_block_route, 3}, {"sparseinv.walk", &Options::sparseinv_walk, 0},
 };
 int normalise(int kind, int value) {
     switch (kind) {
@@ -617,6 +617,7 @@ int csx_csc_invalidate(csx_handle_t h) {
     A->rows.reset();
     A->tiled.reset();
     A->house.reset();
+    A->inv.reset();
     A->clique.reset();
     return CSX_OK;
 }

@@ -133,6 +133,17 @@ struct HouseLevels {
     DevBuf<int32_t> cols;          // device: columns ordered by level, ascending inside a level
 };
 
+// Order in which the columns of a Cholesky factor take their entries of the inverse (csx_sparseinv.hip): the columns of one
+// depth of the elimination forest (roots 0) are independent.
+struct InvSchedule {
+    int32_t ndepths = 0;
+    int32_t widest = 0;            // columns in the widest depth
+    int64_t terms = 0;             // sum over the columns of (entries below the diagonal)^2
+    std::vector<int32_t> ptr;      // host: [ndepths + 1] into cols
+    std::vector<int32_t> rows;     // host: [ndepths] the most entries below the diagonal of a column of that depth
+    DevBuf<int32_t> cols;          // device: columns ordered by depth, ascending inside a depth
+};
+
 struct CliqueForest;   // csx_cholclique.h
 
 // A matrix's arrays are the library's (dfree'd by ~Csc) unless `owns` is false (csx_csc_wrap: the caller's).  Not copyable:
@@ -152,6 +163,8 @@ struct Csc {
     std::unique_ptr<Gather> rows;         // stable transpose = rows of A in ascending column order
     std::unique_ptr<TiledPlan> tiled;
     std::unique_ptr<HouseLevels> house;   // csx_happly's level schedule (pattern only; dropped by csx_csc_invalidate too)
+    std::unique_ptr<InvSchedule> inv;     // csx_chol_inverse's depth schedule (pattern only, so it outlives csx_updown_block; dropped by
+                                          // csx_csc_invalidate too)
     std::unique_ptr<CliqueForest> clique; // csx_schol's finding "a forest of cliques on consecutive columns" (tree, counts, block list
                                           // on the device), kept for the csx_chol that follows; pattern only, dropped by
                                           // csx_csc_invalidate too
@@ -232,6 +245,8 @@ struct Options {
     int tri_supernodes = 1;           // cholsol: supernodal forward / backward solves on factors with supernodes (0 never, 1 yes,
                                       // 2 yes but the triangles by substitution out of LDS instead of on the matrix cores)
     int spgemm_ordered = 0;           // cs_multiply: sum every entry's products in the reference's order (bit-identical x)
+    int sparseinv_walk = 1;           // csx_chol_inverse: a run of depths of one column each is walked by one workgroup in one
+                                      // launch (0: one launch per depth, same bits)
     int lu_etree = 0;                 // cs_lu of one connected matrix on the device, columns scheduled by the column etree:
                                       // 0 never (the default since round 4: measured at best a tie with one host core, on the
                                       // shape it was made for -- profiles/r04_ablation.md), 1 for shallow trees with short

@@ -372,6 +372,25 @@ int csx_updown(csx_handle_t L, int sigma, int32_t cnz, const int32_t *Ci, const 
 int csx_updown_block(csx_handle_t L, csx_handle_t C, const int32_t *sigma, const int32_t *parent, int flags, int32_t *applied);
 int csx_updown_block_info(int32_t *chunks, int32_t *union_columns, int32_t *groups, double *kernel_ms);
 
+/* sparseinv: the entries of inv(L L') on the pattern of the device Cholesky factor L (square, values,
+ * every column non-empty with its diagonal first, positive and finite, rows strictly ascending: cs_chol's), by the Takahashi
+ * recurrence.  *Z: a new device matrix with copies of L.p, L.i; Z.x holds the lower triangle of the symmetric inverse,
+ * byte-equal to the loop (d = L(j,j), S_j = the rows below the diagonal of column j in storage order, Zs(a,b) = the stored
+ * Z(max(a,b), min(a,b)), every product and sum rounded on its own)
+ *   for j = n-1 .. 0:  for i in S_j: Z(i,j) = (-sum_{k in S_j} L(k,j) * Zs(i,k)) / d;
+ *                      Z(j,j) = (1/d - sum_{k in S_j} L(k,j) * Z(k,j)) / d.
+ * One launch per depth of the elimination forest read off L (parent[j] = the row of the second entry of column j); the
+ * schedule is cached on L with its pattern.  CSX_EINVAL, a message in csx_last_error() and no Z for an L that fails the
+ * checks above (made on the device before any value is written) or whose pattern is not a Cholesky pattern (a pair i, k of
+ * one column that is stored in neither column; nothing is read out of range).  L is never changed.
+ * csx_chol_inverse_info: the last call's depths, columns in the widest depth, terms (sum of |S_j|^2) and the device time of
+ *   its launches between two events; all zero when that call failed.
+ * csx_csc_diag: out[j] = the value of the first entry of column j of M (0.0 for an empty column), out a device vector of at
+ *   least n entries: the diagonal of a Cholesky factor or of Z. */
+int csx_chol_inverse(csx_handle_t L, csx_handle_t *Z);
+int csx_chol_inverse_info(int32_t *depths, int32_t *widest, int64_t *terms, double *kernel_ms);
+int csx_csc_diag(csx_handle_t M, csx_handle_t out);
+
 /* cs_lu, csparse.py:1370-1451 (+ cs_spsolve :2078-2113), natural column order: host C++
  * left-looking LU with threshold partial pivoting.  It produces the L (unit diagonal first)
  * and U (diagonal last) that cs_lsolve / cs_usolve consume in cs_lusol (csparse.py:1474-1477).
