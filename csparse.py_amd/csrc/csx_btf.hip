@@ -19,9 +19,6 @@
 
 namespace csx {
 
-int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed);   // csx_trisolve.hip
-int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);
-
 constexpr int BTF_SMALL = 96;   // rows of the largest block solved with its tile in LDS (csx_lu_blocks' limit)
 
 struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (local indices) and exact triangular plans of them

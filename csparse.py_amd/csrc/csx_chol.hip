@@ -50,15 +50,6 @@ namespace csx {
 int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t **Lp_out,
                          int32_t **Li_out, DevBuf<int32_t> *row_ptr_out, DevBuf<int32_t> *row_col_out, DevBuf<int32_t> *row_pos_out,
                          int32_t *cp_host_out);
-// csx_trisolve.hip
-struct TriPlan;
-int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed);
-int tri_solve_host_raw(TriPlan *P, double *x, bool *taken);
-int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);
-void tri_set_mate(TriPlan *P, TriPlan *mate);
-void tri_set_level_hint(TriPlan *P, std::vector<int32_t> &&level);
-void tri_gather_arrays(const TriPlan *P, const int32_t **ptr, const int32_t **idx, const double **val,
-                       const double **diag);
 
 constexpr int CH_ACC = 1024;        // column entries kept in LDS per wave
 constexpr int CH_WAVES = 4;         // waves per workgroup in the column kernels

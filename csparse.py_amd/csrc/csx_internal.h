@@ -197,6 +197,13 @@ void destroy(CholPlan *p);
 void destroy(ShardPlan *p);
 void destroy(BtfPlan *p);
 void destroy(SnPlan *p);
+// csx_trisolve.hip, for the plans that are built on triangular plans (cholsol, btf_factor, lusol_factor)
+int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);          // *out is set on success only
+int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed);
+int tri_solve_host_raw(TriPlan *P, double *x, bool *taken);          // "tri.host_chains"
+void tri_set_mate(TriPlan *P, TriPlan *mate);
+void tri_set_level_hint(TriPlan *P, std::vector<int32_t> &&level);
+void tri_gather_arrays(const TriPlan *P, const int32_t **ptr, const int32_t **idx, const double **val, const double **diag);
 struct Refactor;   // csx_refactor.hip
 struct LuRefPlan;  // csx_refactor.hip
 void destroy(Refactor *p);

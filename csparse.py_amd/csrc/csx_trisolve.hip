@@ -1561,6 +1561,68 @@ __global__ __launch_bounds__(256) void k_adjacent_equal(int32_t n, const int32_t
 constexpr int COMP_MAX_ROWS = 256;    // X tile of one component: rows x 64 lanes x 8 B <= 128 KiB of LDS
 constexpr int COMP_MIN_COUNT = 64;    // fewer components than this: level scheduling fills the chip better
 
+// ---- which kernels a solve launches -------------------------------------------------------------------------------------------
+// tri_route picks the route from the plan, the number of right-hand sides, the order and the options; tri_launch runs what it says.
+// csx_lusol_solve asks about both of its factors before it launches anything.
+enum class TriRoute {
+    // a forest of small dependency components ("tri.components", analyse_components): one sweep over all of them
+    Ragged,       // rounding-equal order, more than 8 right-hand sides, the guard passed: dense, on the matrix cores (ragged_solve)
+    CompPush,     // L, U, up to 8 right-hand sides ("tri.push"), no row twice in a column, a component fits LDS: k_tri_comp_push
+    FewLds,       // up to 32 right-hand sides, programs and X of a wave's components fit LDS: k_tri_few_lds
+    Few,          // up to 32 right-hand sides, the programs read from memory: k_tri_few
+    Local,        // more: a wave per (component, 64 right-hand sides), its X tile in LDS: k_tri_local
+    // a proper triangle that is a chain by its links ("tri.columns", measure_band): a workgroup per right-hand side, no level analysis
+    WColumns,     // L, U whose x does not fit LDS, no row twice in a column; and L' of any size in the relaxed order, on the mate's
+                  // (L's) gather arrays: k_tri_wcolumns<256>, <1024> above 192 entries a column
+    WColChain,    // L', U' whose x does not fit LDS: k_tri_wcolchain<KIND, 2>, <KIND, 12> above 160 entries a column
+    Columns,      // L, U with x in LDS, no row twice in a column -- a chain by its links or by its levels: k_tri_columns
+    ColChain,     // L', U' likewise: k_tri_colchain
+    Sequential,   // a structure the reference would mis-solve: the reference's own loop, k_tri_sequential
+    Levels,       // everything else: the level schedule, walk_levels
+};
+
+// the route and what was worked out to choose it (only the fields of the route taken are set)
+struct TriRouting {
+    TriRoute route = TriRoute::Levels;
+    size_t lds = 0;                      // dynamic LDS of the launch
+    unsigned grid = 0;                   // component sweeps: workgroups
+    int G = 0;                           // CompPush, Few: lanes of a component, the right-hand sides rounded up to a power of two
+    int waves = 0;                       // Few, Local: waves of a workgroup
+    int32_t tile_rows = 0, chunks = 0;   // Few: rows of a wave's X tile; Local: blocks of 64 right-hand sides
+    uint32_t window = 0;                 // WColumns, WColChain: entries of x in the LDS window (a power of two)
+    int threads = 0, rounds = 0;         // column loops: threads of a workgroup; WColChain: 2 or 12 rounds fetched ahead
+    bool mate = false;                   // WColumns: on the mate's gather arrays
+};
+
+// "raise the dynamic-LDS limit, then launch", on the library's stream.  Which instance of a kernel template a plan takes
+// (direction, kind, width) is a runtime value: the callers pick the instance with ?: and each launch is written once.
+template <typename... A>
+static int launch_lds(void (*kernel)(A...), int lds_limit, dim3 grid, dim3 block, size_t lds, std::common_type_t<A>... args) {
+    CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit));
+    hipLaunchKernelGGL(kernel, grid, block, lds, ctx().stream, args...);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
+// P->col_state, found the first time someone asks: may the entries of a column of T be pushed by lanes side by side (k_tri_comp_push,
+// k_tri_columns, k_tri_wcolumns)?  Only the push kinds (L, U) have such lanes; their gather structure is the stable transpose, which
+// the probe reads.  The gather kinds (L', U') walk a column in order whatever it holds.
+static int ensure_col_state(TriPlan *P) {
+    if (P->col_state) return CSX_OK;
+    int dup = 0;
+    if (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U) {
+        hipStream_t s = ctx().stream;
+        DevBuf<int> flag;
+        CSX_TRY(flag.alloc(1));
+        CSX_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_adjacent_equal, dim3((unsigned)(((int64_t)P->n + 3) / 4)), dim3(256), 0, s, P->n, P->ptr, P->idx, flag);
+        CSX_HIP(hipMemcpyAsync(&dup, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
+    }
+    P->col_state = dup ? 2 : 1;
+    return CSX_OK;
+}
+
 static size_t few_lds_bytes(int32_t rows, int32_t terms, int G) {
     return (size_t)(terms > 0 ? terms : 1) * 16 + (size_t)rows * (16 + 8 * (size_t)G) + 64;
 }
@@ -1610,12 +1672,8 @@ static int analyse_components(TriPlan *P) {
     if (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U) {
         // column program for k_tri_comp_push -- unless some column holds the same row twice (the reference's own LU
         // factors do): the lanes of a column would race on it; the gather kernels keep such entries in order
-        int hdup = 0;
-        CSX_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
-        hipLaunchKernelGGL(k_adjacent_equal, dim3(nbw), dim3(256), 0, s, n, P->ptr, P->idx, flags);
-        CSX_HIP(hipMemcpyAsync(&hdup, flags, sizeof(int), hipMemcpyDeviceToHost, s));
-        CSX_HIP(hipStreamSynchronize(s));
-        if (!hdup) {
+        CSX_TRY(ensure_col_state(P));
+        if (P->col_state == 1) {
             CSX_TRY(clen.alloc((size_t)n + 1));
             hipLaunchKernelGGL(k_push_len, dim3(ncw), dim3(256), 0, s, P->ncomp, comps, srow, P->Tp, P->forward ? 1 : 0, clen);
             CSX_TRY(P->cptr.alloc((size_t)n + 1));
@@ -1673,111 +1731,38 @@ static int components_ragged(TriPlan *P) {
     return CSX_OK;
 }
 
-// io (csx_lusol_solve, exact order): the block read and its row map, the row map of the block written (X); honoured by the kernel
-// of MANY right-hand sides only -- *io_taken says whether (false: nothing was launched, the caller runs the separate steps)
-struct TriIO {
-    const double *src;
-    const int32_t *load_rows, *store_rows;
-};
-static int solve_components(TriPlan *P, double *X, int32_t nrhs, const TriIO *io = nullptr, bool *io_taken = nullptr) {
-    hipStream_t s = ctx().stream;
-    if (io) {
-        *io_taken = false;
-        if ((P->rounding_equal && nrhs > 8) || nrhs <= 32) return CSX_OK;      // (other kernels' territory)
+// Route Local: dst <- the sweep of src (src == dst: in place).  Row j of a component is read from row load_rows[j] of src and
+// written to row store_rows[j] of dst (null: row j) -- the fused permutations of csx_lusol_solve.
+static int sweep_local(TriPlan *P, const TriRouting &R, const double *src, double *dst, const int32_t *load_rows,
+                       const int32_t *store_rows, int32_t nrhs);   // (below: the code object lays the kernel instances out in the
+                                                                   // order this file first names them, kept as it was)
+
+// the component sweeps, one launch per route
+static int sweep_components(TriPlan *P, const TriRouting &R, double *X, int32_t nrhs) {
+    switch (R.route) {
+        case TriRoute::Ragged: return ragged_solve(P->rag.get(), P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
+        case TriRoute::CompPush:
+            return launch_lds(P->forward ? k_tri_comp_push<true> : k_tri_comp_push<false>, 160 * 1024 - 256, dim3(R.grid), dim3(64),
+                              R.lds, P->comps, P->ncomp, P->comp_nodes, P->cptr, P->cidx, P->cval, P->cdiag, X, nrhs, R.G, P->comp_max,
+                              P->push_terms);
+        case TriRoute::FewLds:
+            return launch_lds(P->forward ? k_tri_few_lds<true, 4> : k_tri_few_lds<false, 4>, 160 * 1024 - 256, dim3(R.grid), dim3(64),
+                              R.lds, P->comps, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs,
+                              P->few_rows, P->few_terms);
+        case TriRoute::Few:
+            return launch_lds(P->forward ? k_tri_few<true> : k_tri_few<false>, 160 * 1024 - 256, dim3(R.grid), dim3(256), R.lds,
+                              P->comps, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs, R.G,
+                              R.tile_rows, R.waves);
+        case TriRoute::Local: return sweep_local(P, R, X, X, nullptr, nullptr, nrhs);
+        default: return CSX_EINVAL;
     }
-    if (P->rounding_equal && nrhs > 8) {
-        // the caller granted rounding (csx_tri_set_order): dense components on the matrix cores, one sweep in position order
-        CSX_TRY(components_ragged(P));
-        if (P->rag) return ragged_solve(P->rag.get(), P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
-    }
-    // L, U with up to 8 right-hand sides: one wave per component, column-push form (W, L + U pair: 43 us at 1 RHS,
-    // 78 us at 8; at 64 the entry-parallel lanes are gone and it loses to k_tri_local, 483 against 272 us)
-    if (nrhs <= 8 && P->push_terms > 0 && ctx().opt.tri_push) {
-        int G = 1;
-        while (G < nrhs) G <<= 1;
-        const size_t lds = (size_t)P->push_terms * 16 + (size_t)P->comp_max * (16 + 8 * (size_t)G) + 64;
-        if (lds <= 120 * 1024) {
-            if (P->forward) {
-                CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_comp_push<true>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                hipLaunchKernelGGL(k_tri_comp_push<true>, dim3((unsigned)P->ncomp), dim3(64), lds, s, P->comps, P->ncomp,
-                                   P->comp_nodes, P->cptr, P->cidx, P->cval, P->cdiag, X, nrhs, G, P->comp_max, P->push_terms);
-            } else {
-                CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_comp_push<false>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                hipLaunchKernelGGL(k_tri_comp_push<false>, dim3((unsigned)P->ncomp), dim3(64), lds, s, P->comps, P->ncomp,
-                                   P->comp_nodes, P->cptr, P->cidx, P->cval, P->cdiag, X, nrhs, G, P->comp_max, P->push_terms);
-            }
-            CSX_LAUNCH_CHECK();
-            return CSX_OK;
-        }
-    }
-    if (nrhs <= 32 && P->few_cpw) {   // lanes = (component, right-hand side) pairs, programs and X in LDS
-        const int cpw = P->few_cpw;
-        const size_t lds = few_lds_bytes(P->few_rows, P->few_terms, 64 / cpw);
-        const dim3 grid((unsigned)((P->ncomp + cpw - 1) / cpw));
-#define CSX_FEW(FWD, CPW)                                                                                            \
-    hipLaunchKernelGGL((k_tri_few_lds<FWD, CPW>), grid, dim3(64), lds, s, P->comps, P->ncomp, P->comp_nodes, P->prog_ptr, \
-                       P->prog_idx, P->prog_val, P->prog_diag, X, nrhs, P->few_rows, P->few_terms)
-        if (P->forward) {
-            CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_few_lds<true, 4>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            CSX_FEW(true, 4);
-        } else {
-            CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_few_lds<false, 4>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            CSX_FEW(false, 4);
-        }
-#undef CSX_FEW
-        CSX_LAUNCH_CHECK();
-        return CSX_OK;
-    }
-    if (nrhs <= 32) {   // the same with the programs read from memory (components too big for the LDS copy)
-        int G = 1;
-        while (G < nrhs) G <<= 1;
-        const int cpw = 64 / G;
-        const int32_t tile_rows = P->comp_max | 1;
-        const size_t per_wave_f = (size_t)64 * tile_rows * sizeof(double);
-        int wv = (int)std::min<size_t>(4, (128 * 1024) / per_wave_f);
-        if (wv < 1) wv = 1;
-        const int64_t waves_needed = ((int64_t)P->ncomp + cpw - 1) / cpw;
-        const dim3 grid((unsigned)((waves_needed + wv - 1) / wv));
-        if (P->forward) {
-            CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_few<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            hipLaunchKernelGGL(k_tri_few<true>, grid, dim3(256), per_wave_f * wv, s, P->comps, P->ncomp, P->comp_nodes,
-                               P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs, G, tile_rows, wv);
-        } else {
-            CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_few<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            hipLaunchKernelGGL(k_tri_few<false>, grid, dim3(256), per_wave_f * wv, s, P->comps, P->ncomp, P->comp_nodes,
-                               P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs, G, tile_rows, wv);
-        }
-        CSX_LAUNCH_CHECK();
-        return CSX_OK;
-    }
-    const size_t per_wave = (size_t)P->comp_max * 64 * sizeof(double);
-    const int waves = tile_waves_per_workgroup(per_wave, TL_WAVES_MAX);
-    const int32_t chunks = (nrhs + 63) / 64;
-    const int64_t tasks = (int64_t)P->ncomp * chunks;
-    const size_t lds = per_wave * (size_t)waves;
-    const dim3 grid((unsigned)((tasks + waves - 1) / waves));
-    if (P->forward) {
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_local<true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-        hipLaunchKernelGGL(k_tri_local<true>, grid, dim3(64 * waves), lds, s, P->comps_by_size, P->ncomp, P->comp_nodes,
-                           P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, io ? io->src : (const double *)X, X,
-                           io ? io->load_rows : nullptr, io ? io->store_rows : nullptr, nrhs, chunks, P->comp_max, waves);
-    } else {
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_local<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-        hipLaunchKernelGGL(k_tri_local<false>, grid, dim3(64 * waves), lds, s, P->comps_by_size, P->ncomp, P->comp_nodes,
-                           P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, io ? io->src : (const double *)X, X,
-                           io ? io->load_rows : nullptr, io ? io->store_rows : nullptr, nrhs, chunks, P->comp_max, waves);
-    }
-    CSX_LAUNCH_CHECK();
-    if (io) *io_taken = true;
-    return CSX_OK;
+}
+
+static int sweep_local(TriPlan *P, const TriRouting &R, const double *src, double *dst, const int32_t *load_rows,
+                       const int32_t *store_rows, int32_t nrhs) {
+    return launch_lds(P->forward ? k_tri_local<true> : k_tri_local<false>, 160 * 1024 - 256, dim3(R.grid), dim3(64 * R.waves), R.lds,
+                      P->comps_by_size, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, src, dst,
+                      load_rows, store_rows, nrhs, R.chunks, P->comp_max, R.waves);
 }
 
 // ---- analysis ---------------------------------------------------------------------
@@ -2184,167 +2169,155 @@ static void make_segments(TriPlan *P, int nrhs) {
     }
 }
 
-int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
+// One pass over the pattern tells a banded chain from the rest: band width, share of columns with a neighbour link, proper
+// triangle -- and for a proper L or U whether its columns may be pushed.
+static int measure_band(TriPlan *P) {
+    if (P->band >= 0) return CSX_OK;
     hipStream_t s = ctx().stream;
-    if (P->zero_pivot) return CSX_EZEROPIVOT;
-    if (P->n == 0 || nrhs == 0) return CSX_OK;
-    if (ctx().opt.tri_components) CSX_TRY(analyse_components(P));
-    if (P->comp_ok && ctx().opt.tri_components) return solve_components(P, X, nrhs);
-    // One pass over the pattern tells a banded chain from the rest: band width, share of columns with a neighbour link,
-    // proper triangle.  Such a system goes to the column loops without any level analysis -- x in LDS when it fits,
-    // a window of x otherwise.
-    if (ctx().opt.tri_columns) {
-        if (P->band < 0) {
-            DevBuf<int> o;
-            int h[3] = {0, 0, 0};
-            CSX_TRY(o.alloc(3));
-            CSX_HIP(hipMemsetAsync(o, 0, 3 * sizeof(int), s));
-            hipLaunchKernelGGL(k_tri_band, dim3((unsigned)std::min<int64_t>(((int64_t)P->n + 3) / 4, 2048)), dim3(256), 0, s, P->n, P->Tp, P->Ti,
-                               (P->kind == CSX_TRI_L || P->kind == CSX_TRI_LT) ? 1 : 0, o);
-            CSX_HIP(hipMemcpyAsync(h, o, sizeof h, hipMemcpyDeviceToHost, s));
-            CSX_HIP(hipStreamSynchronize(s));
-            P->band = h[2] ? 0x7fffffff : h[0];     // not a proper triangle: the schedule's literal loop handles it
-            P->links = h[1];
-            if (P->band != 0x7fffffff && (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U)) {
-                int hd = 0;                          // the same row twice in a column: the lanes of a column would race
-                CSX_HIP(hipMemsetAsync(o, 0, sizeof(int), s));
-                hipLaunchKernelGGL(k_adjacent_equal, dim3((unsigned)(((int64_t)P->n + 3) / 4)), dim3(256), 0, s, P->n, P->ptr,
-                                   P->idx, o);
-                CSX_HIP(hipMemcpyAsync(&hd, o, sizeof(int), hipMemcpyDeviceToHost, s));
-                CSX_HIP(hipStreamSynchronize(s));
-                P->col_state = hd ? 2 : 1;
+    DevBuf<int> o;
+    int h[3] = {0, 0, 0};
+    CSX_TRY(o.alloc(3));
+    CSX_HIP(hipMemsetAsync(o, 0, 3 * sizeof(int), s));
+    hipLaunchKernelGGL(k_tri_band, dim3((unsigned)std::min<int64_t>(((int64_t)P->n + 3) / 4, 2048)), dim3(256), 0, s, P->n, P->Tp, P->Ti,
+                       (P->kind == CSX_TRI_L || P->kind == CSX_TRI_LT) ? 1 : 0, o);
+    CSX_HIP(hipMemcpyAsync(h, o, sizeof h, hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    P->band = h[2] ? 0x7fffffff : h[0];     // not a proper triangle: the schedule's literal loop handles it
+    P->links = h[1];
+    if (P->band != 0x7fffffff && (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U)) CSX_TRY(ensure_col_state(P));
+    return CSX_OK;
+}
+
+// Runs the plan's lazy analyses as far as the decision needs them, in this order: components, band and links, the level schedule
+// (not for a small chain), the column state, the schedule after all.  Launches no solve kernel.
+static int tri_route(TriPlan *P, int32_t nrhs, bool relaxed, TriRouting *R) {
+    const Options &opt = ctx().opt;
+    *R = TriRouting();
+    if (opt.tri_components) CSX_TRY(analyse_components(P));
+    if (P->comp_ok && opt.tri_components) {
+        if (P->rounding_equal && nrhs > 8) {
+            // the caller granted rounding (csx_tri_set_order): dense components on the matrix cores, one sweep in position order
+            CSX_TRY(components_ragged(P));
+            if (P->rag) {
+                R->route = TriRoute::Ragged;
+                return CSX_OK;
             }
         }
+        R->G = 1;
+        while (R->G < nrhs) R->G <<= 1;
+        // L, U with up to 8 right-hand sides: one wave per component, column-push form (W, L + U pair: 43 us at 1 RHS,
+        // 78 us at 8; at 64 the entry-parallel lanes are gone and it loses to k_tri_local, 483 against 272 us)
+        if (nrhs <= 8 && P->push_terms > 0 && opt.tri_push) {
+            R->lds = (size_t)P->push_terms * 16 + (size_t)P->comp_max * (16 + 8 * (size_t)R->G) + 64;
+            if (R->lds <= 120 * 1024) {
+                R->route = TriRoute::CompPush;
+                R->grid = (unsigned)P->ncomp;
+                return CSX_OK;
+            }
+        }
+        if (nrhs <= 32 && P->few_cpw) {   // lanes = (component, right-hand side) pairs, programs and X in LDS
+            R->route = TriRoute::FewLds;
+            R->lds = few_lds_bytes(P->few_rows, P->few_terms, 64 / P->few_cpw);
+            R->grid = (unsigned)((P->ncomp + P->few_cpw - 1) / P->few_cpw);
+            return CSX_OK;
+        }
+        if (nrhs <= 32) {   // the same with the programs read from memory (components too big for the LDS copy)
+            const int cpw = 64 / R->G;
+            R->route = TriRoute::Few;
+            R->tile_rows = P->comp_max | 1;
+            const size_t per_wave = (size_t)64 * R->tile_rows * sizeof(double);
+            R->waves = std::max(1, (int)std::min<size_t>(4, (128 * 1024) / per_wave));
+            const int64_t waves_needed = ((int64_t)P->ncomp + cpw - 1) / cpw;
+            R->lds = per_wave * R->waves;
+            R->grid = (unsigned)((waves_needed + R->waves - 1) / R->waves);
+            return CSX_OK;
+        }
+        const size_t per_wave = (size_t)P->comp_max * 64 * sizeof(double);
+        R->route = TriRoute::Local;
+        R->waves = tile_waves_per_workgroup(per_wave, TL_WAVES_MAX);
+        R->chunks = (nrhs + 63) / 64;
+        R->lds = per_wave * (size_t)R->waves;
+        R->grid = (unsigned)(((int64_t)P->ncomp * R->chunks + R->waves - 1) / R->waves);
+        return CSX_OK;
+    }
+    // A proper triangle whose columns nearly all hand on to their neighbour is a chain whatever its level sets say.  Such a system
+    // goes to the column loops without any level analysis -- x in LDS when it fits, a window of x otherwise.
+    bool chain = false;
+    const bool push = P->kind == CSX_TRI_L || P->kind == CSX_TRI_U;
+    const bool small = P->n <= TC_MAX_N;    // x of one right-hand side fits LDS; above, only the window kernels apply
+    if (opt.tri_columns) {
+        CSX_TRY(measure_band(P));
+        chain = P->band != 0x7fffffff && (int64_t)P->links * 12 > (int64_t)P->n * 11;
         uint32_t Wn = 64;
-        while ((int64_t)Wn < (int64_t)P->band + 4 && Wn < (1u << 20)) Wn <<= 1;
-        const bool chainlike = (int64_t)P->links * 12 > (int64_t)P->n * 11;   // nearly every column hands on to its neighbour
-        if (chainlike && P->band != 0x7fffffff && (size_t)Wn * sizeof(double) <= 128 * 1024) {
-            const size_t lds = (size_t)Wn * sizeof(double);
-            const bool big = P->n > TC_MAX_N;       // x of one right-hand side does not fit LDS: only the window kernels apply
-            const bool push = P->kind == CSX_TRI_L || P->kind == CSX_TRI_U;
+        while (chain && (int64_t)Wn < (int64_t)P->band + 4 && Wn < (1u << 20)) Wn <<= 1;
+        if (chain && (size_t)Wn * sizeof(double) <= 128 * 1024) {
             const TriPlan *M = P->mate;
             // rounding-equal order, L' (any size): the rows of L (the mate's gather arrays) pushed as the columns of L'
-            const bool mate_push = !push && relaxed && P->kind == CSX_TRI_LT && M && M->kind == CSX_TRI_L && M->own_ptr &&
-                                   M->col_state == 1 && M->n == P->n;
-            if ((big && push && P->col_state == 1) || mate_push) {
-                const int32_t *cp = mate_push ? M->ptr : P->Tp, *ci = mate_push ? M->idx : P->Ti;
-                const double *cx = mate_push ? M->val : P->Tx, *cd = mate_push ? M->diag : P->diag;
-                const int sf = (!mate_push && P->kind == CSX_TRI_L) ? 1 : 0, sl = (!mate_push && P->kind == CSX_TRI_U) ? 1 : 0;
-                const int asc = (!mate_push && P->kind == CSX_TRI_L) ? 1 : 0;
-                const int64_t terms = mate_push ? (int64_t)M->gnnz : (int64_t)P->gnnz;
-                if (terms > (int64_t)192 * P->n) {
-                    CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_wcolumns<1024>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                    hipLaunchKernelGGL(k_tri_wcolumns<1024>, dim3((unsigned)nrhs), dim3(1024), lds, s, P->n, cp, ci, cx, cd, sf,
-                                       sl, asc, Wn - 1, X, nrhs);
-                } else {
-                    CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_wcolumns<256>),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-                    hipLaunchKernelGGL(k_tri_wcolumns<256>, dim3((unsigned)nrhs), dim3(256), lds, s, P->n, cp, ci, cx, cd, sf, sl,
-                                       asc, Wn - 1, X, nrhs);
-                }
-                CSX_LAUNCH_CHECK();
+            R->mate = !push && relaxed && P->kind == CSX_TRI_LT && M && M->kind == CSX_TRI_L && M->own_ptr && M->col_state == 1 &&
+                      M->n == P->n;
+            R->window = Wn;
+            R->lds = (size_t)Wn * sizeof(double);
+            if ((!small && push && P->col_state == 1) || R->mate) {
+                R->route = TriRoute::WColumns;
+                R->threads = (int64_t)(R->mate ? M->gnnz : P->gnnz) > (int64_t)192 * P->n ? 1024 : 256;
                 return CSX_OK;
             }
-            if (big && !push) {
-#define CSX_WCH(K, R)                                                                                              \
-    {                                                                                                              \
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_wcolchain<K, R>),                        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));               \
-        hipLaunchKernelGGL((k_tri_wcolchain<K, R>), dim3((unsigned)nrhs), dim3(64), lds, s, P->n, P->Tp, P->Ti, P->Tx, \
-                           Wn - 1, X, nrhs);                                                                       \
-    }
-                const bool wide = (int64_t)P->gnnz > (int64_t)160 * P->n;   // columns of more than two rounds on average
-                if (P->kind == CSX_TRI_LT) {
-                    if (wide) CSX_WCH(CSX_TRI_LT, 12) else CSX_WCH(CSX_TRI_LT, 2)
-                } else {
-                    if (wide) CSX_WCH(CSX_TRI_UT, 12) else CSX_WCH(CSX_TRI_UT, 2)
-                }
-#undef CSX_WCH
-                CSX_LAUNCH_CHECK();
+            if (!small && !push) {
+                R->route = TriRoute::WColChain;
+                R->rounds = (int64_t)P->gnnz > (int64_t)160 * P->n ? 12 : 2;   // columns of more than two rounds on average
                 return CSX_OK;
             }
         }
     }
-    // a proper triangle whose columns nearly all hand on to their neighbour is a chain whatever its level sets say
-    const bool chain_by_links = ctx().opt.tri_columns && P->band >= 0 && P->band != 0x7fffffff &&
-                                (int64_t)P->links * 12 > (int64_t)P->n * 11;
-    auto schedule_or_literal = [&](bool *done) -> int {
-        *done = false;
+    if (!(chain && small)) {
         CSX_TRY(ensure_schedule(P));
         if (P->sequential) {
-            hipLaunchKernelGGL(k_tri_sequential, dim3((unsigned)((nrhs + 63) / 64)), dim3(64), 0, s, P->kind, P->n, P->Tp,
-                               P->Ti, P->Tx, X, nrhs);
-            CSX_LAUNCH_CHECK();
-            *done = true;
-        }
-        return CSX_OK;
-    };
-    bool done = false;
-    if (!(chain_by_links && P->n <= TC_MAX_N)) {
-        CSX_TRY(schedule_or_literal(&done));
-        if (done) return CSX_OK;
-    }
-    // small and chain-like: the column loop, one wave per right-hand side, beats any schedule
-    if (ctx().opt.tri_columns && P->n <= TC_MAX_N && (chain_by_links || (int64_t)P->nlevels * 12 > P->n)) {
-        if (P->col_state == 0) {
-            P->col_state = 1;
-            if (P->kind == CSX_TRI_L || P->kind == CSX_TRI_U) {   // gather structure of a push kind = stable transpose
-                DevBuf<int> flag;
-                int h = 0;
-                CSX_TRY(flag.alloc(1));
-                CSX_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-                hipLaunchKernelGGL(k_adjacent_equal, dim3((unsigned)(((int64_t)P->n + 3) / 4)), dim3(256), 0, s, P->n, P->ptr,
-                                   P->idx, flag);
-                CSX_HIP(hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-                CSX_HIP(hipStreamSynchronize(s));
-                if (h) P->col_state = 2;
-            }
-        }
-        if (P->col_state == 1 && ((size_t)P->n + 8) * sizeof(double) <= 150 * 1024) {
-            const size_t lds = ((size_t)P->n + 8) * sizeof(double);
-#define CSX_TC(K)                                                                                                  \
-    {                                                                                                              \
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_columns<K>),                             \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));                \
-        hipLaunchKernelGGL(k_tri_columns<K>, dim3((unsigned)nrhs), dim3(TC_THREADS), lds, s, P->n, P->Tp, P->Ti, P->Tx, \
-                           X, nrhs);                                                                               \
-    }
-#define CSX_TCH(K)                                                                                                 \
-    {                                                                                                              \
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_tri_colchain<K>),                               \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));               \
-        hipLaunchKernelGGL(k_tri_colchain<K>, dim3((unsigned)nrhs), dim3(64), (size_t)P->n * sizeof(double), s, P->n, P->Tp, \
-                           P->Ti, P->Tx, X, nrhs);                                                                 \
-    }
-            switch (P->kind) {
-                case CSX_TRI_L: CSX_TC(CSX_TRI_L) break;
-                case CSX_TRI_LT: CSX_TCH(CSX_TRI_LT) break;
-                case CSX_TRI_U: CSX_TC(CSX_TRI_U) break;
-                default: CSX_TCH(CSX_TRI_UT) break;
-            }
-#undef CSX_TC
-#undef CSX_TCH
-            CSX_LAUNCH_CHECK();
+            R->route = TriRoute::Sequential;
             return CSX_OK;
         }
     }
-    if (!P->scheduled) {                 // the column loops did not apply after all (duplicate rows, x too long for LDS)
-        CSX_TRY(schedule_or_literal(&done));
-        if (done) return CSX_OK;
+    // small and chain-like: the column loop, one wave per right-hand side, beats any schedule
+    if (opt.tri_columns && small && (chain || (int64_t)P->nlevels * 12 > P->n)) {
+        CSX_TRY(ensure_col_state(P));
+        if (P->col_state == 1 && ((size_t)P->n + 8) * sizeof(double) <= 150 * 1024) {
+            R->route = push ? TriRoute::Columns : TriRoute::ColChain;
+            R->lds = ((size_t)P->n + (push ? 8 : 0)) * sizeof(double);
+            R->threads = push ? TC_THREADS : 64;
+            return CSX_OK;
+        }
     }
+    CSX_TRY(ensure_schedule(P));   // the column loops did not apply after all (duplicate rows, x too long for LDS)
+    if (P->sequential) R->route = TriRoute::Sequential;
+    return CSX_OK;
+}
+
+// The level schedule.  Wide levels are one launch each, runs of narrow ones a single workgroup's (make_segments); the flavour is
+// chosen once per solve: a thread per (row, right-hand side), or for long rows a wave per row (few right-hand sides) or a wave
+// per (row, 64 right-hand sides) (many).
+struct RowWaveKernels {   // the two wave flavours take the same arguments
+    decltype(&k_tri_level_rows) level;
+    decltype(&k_tri_run_prefix_rows) prefix;
+    decltype(&k_tri_levels_rows_one_wg) one_wg;
+};
+
+static int walk_levels(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
+    hipStream_t s = ctx().stream;
     // the exact chain walker is already the fast one when in-block sources come last: relax only the others
     relaxed = relaxed && !P->chain_ok;
     make_segments(P, nrhs);
     const bool no_chain = !ctx().opt.tri_chain_walker;
+    const bool long_rows = P->n > 0 && (int64_t)P->gnnz >= (int64_t)TRW_MIN_ROW * P->n && ctx().opt.tri_row_waves;
     // few right-hand sides and long rows: a wave per row (k_tri_level_rows) instead of a thread per (row, right-hand side)
-    const bool by_rows = nrhs <= TRW_MAX_RHS && P->n > 0 && (int64_t)P->gnnz >= (int64_t)TRW_MIN_ROW * P->n &&
-                         ctx().opt.tri_row_waves;
+    const bool by_rows = long_rows && nrhs <= TRW_MAX_RHS;
     // many right-hand sides and long rows: a wave per (row, 64 right-hand sides) (k_tri_level_rows64)
-    const bool by_rows64 = nrhs >= TR64_MIN_RHS && P->n > 0 && (int64_t)P->gnnz >= (int64_t)TRW_MIN_ROW * P->n &&
-                           ctx().opt.tri_row_waves;
+    const bool by_rows64 = long_rows && nrhs >= TR64_MIN_RHS;
+    const RowWaveKernels K = by_rows64 ? RowWaveKernels{k_tri_level_rows64, k_tri_run_prefix64, k_tri_levels_rows64_one_wg}
+                                       : RowWaveKernels{k_tri_level_rows, k_tri_run_prefix_rows, k_tri_levels_rows_one_wg};
+    const int64_t waves_per_row = by_rows64 ? (nrhs + 63) / 64 : 1;
     for (const Segment &g : P->segs) {
-        if (by_rows64 && g.one_wg) {
+        const int32_t first = P->level_ptr_h[(size_t)g.l0];
+        const int32_t count = P->level_ptr_h[(size_t)g.l0 + 1] - first;   // (of the segment's one level, unless one_wg)
+        if ((by_rows || by_rows64) && g.one_wg) {
             // runs of narrow levels in two phases, TR64_RUN levels at a time (see k_tri_run_prefix64)
             if (!P->level_of && g.l1 - g.l0 >= TR64_RUN_MIN) {
                 CSX_TRY(P->level_of.alloc((size_t)P->n));
@@ -2356,49 +2329,19 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
                 const int32_t b = std::min(g.l1, a + TR64_RUN);
                 const bool two_phase = b - a >= TR64_RUN_MIN;
                 if (two_phase) {
-                    const int32_t first = P->level_ptr_h[(size_t)a], count = P->level_ptr_h[(size_t)b] - first;
-                    const int64_t waves = (int64_t)count * ((nrhs + 63) / 64);
-                    hipLaunchKernelGGL(k_tri_run_prefix64, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, first,
-                                       count, a, P->level_of, P->ptr, P->idx, P->val, P->skip_first, P->skip_last, X, nrhs,
-                                       P->resume);
+                    const int32_t run_first = P->level_ptr_h[(size_t)a], run_count = P->level_ptr_h[(size_t)b] - run_first;
+                    const int64_t waves = (int64_t)run_count * waves_per_row;
+                    hipLaunchKernelGGL(K.prefix, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, run_first, run_count, a,
+                                       P->level_of, P->ptr, P->idx, P->val, P->skip_first, P->skip_last, X, nrhs, P->resume);
                 }
-                hipLaunchKernelGGL(k_tri_levels_rows64_one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, a, b, P->ptr,
-                                   P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs,
-                                   two_phase ? P->resume : nullptr);
+                hipLaunchKernelGGL(K.one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, a, b, P->ptr, P->idx, P->val, P->diag,
+                                   P->skip_first, P->skip_last, X, nrhs, two_phase ? P->resume : nullptr);
                 a = b;
             }
-        } else if (by_rows64) {
-            const int32_t first = P->level_ptr_h[(size_t)g.l0];
-            const int32_t count = P->level_ptr_h[(size_t)g.l0 + 1] - first;
-            const int64_t waves = (int64_t)count * ((nrhs + 63) / 64);
-            hipLaunchKernelGGL(k_tri_level_rows64, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, first, count,
-                               P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
-        } else if (by_rows && g.one_wg) {
-            if (!P->level_of && g.l1 - g.l0 >= TR64_RUN_MIN) {
-                CSX_TRY(P->level_of.alloc((size_t)P->n));
-                CSX_TRY(P->resume.alloc((size_t)P->n));
-                hipLaunchKernelGGL(k_tri_level_of, dim3((unsigned)(((int64_t)P->n + 255) / 256)), dim3(256), 0, s, P->nlevels,
-                                   P->level_ptr, P->order, P->n, P->level_of);
-            }
-            for (int32_t a = g.l0; a < g.l1;) {
-                const int32_t b = std::min(g.l1, a + TR64_RUN);
-                const bool two_phase = b - a >= TR64_RUN_MIN;
-                if (two_phase) {
-                    const int32_t first = P->level_ptr_h[(size_t)a], count = P->level_ptr_h[(size_t)b] - first;
-                    hipLaunchKernelGGL(k_tri_run_prefix_rows, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, P->order, first,
-                                       count, a, P->level_of, P->ptr, P->idx, P->val, P->skip_first, P->skip_last, X, nrhs,
-                                       P->resume);
-                }
-                hipLaunchKernelGGL(k_tri_levels_rows_one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, a, b, P->ptr,
-                                   P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs,
-                                   two_phase ? P->resume : nullptr);
-                a = b;
-            }
-        } else if (by_rows) {
-            const int32_t first = P->level_ptr_h[(size_t)g.l0];
-            const int32_t count = P->level_ptr_h[(size_t)g.l0 + 1] - first;
-            hipLaunchKernelGGL(k_tri_level_rows, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, s, P->order, first, count,
-                               P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
+        } else if (by_rows || by_rows64) {
+            const int64_t waves = (int64_t)count * waves_per_row;
+            hipLaunchKernelGGL(K.level, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, first, count, P->ptr, P->idx,
+                               P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         } else if (g.one_wg && !no_chain && (P->chain_ok || relaxed)) {
             hipLaunchKernelGGL(k_tri_chain, dim3(1), dim3(64 * CHB), 0, s, P->order, P->level_ptr_h[(size_t)g.l0],
                                P->level_ptr_h[(size_t)g.l1], P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last,
@@ -2407,8 +2350,6 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
             hipLaunchKernelGGL(k_tri_levels_one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, g.l0, g.l1, P->ptr,
                                P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         } else {
-            const int32_t first = P->level_ptr_h[(size_t)g.l0];
-            const int32_t count = P->level_ptr_h[(size_t)g.l0 + 1] - first;
             const int64_t threads = (int64_t)count * nrhs;
             hipLaunchKernelGGL(k_tri_level, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, P->order, first,
                                count, P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
@@ -2417,6 +2358,61 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
+
+// one launch per route, with what tri_route worked out
+static int tri_launch(TriPlan *P, const TriRouting &R, double *X, int32_t nrhs, bool relaxed) {
+    const dim3 per_rhs((unsigned)nrhs);
+    switch (R.route) {
+        case TriRoute::Ragged:
+        case TriRoute::CompPush:
+        case TriRoute::FewLds:
+        case TriRoute::Few:
+        case TriRoute::Local: return sweep_components(P, R, X, nrhs);
+        case TriRoute::WColumns: {
+            // the columns pushed: T's own, or (mate) the rows of L as the columns of L' -- whole, in storage order, diagonal apart
+            const TriPlan *M = P->mate;
+            const int own_l = !R.mate && P->kind == CSX_TRI_L, own_u = !R.mate && P->kind == CSX_TRI_U;
+            return launch_lds(R.threads == 1024 ? k_tri_wcolumns<1024> : k_tri_wcolumns<256>, 160 * 1024 - 256, per_rhs,
+                              dim3(R.threads), R.lds, P->n, R.mate ? M->ptr : P->Tp, R.mate ? M->idx : P->Ti, R.mate ? M->val : P->Tx,
+                              R.mate ? M->diag : P->diag, own_l, own_u, own_l, R.window - 1, X, nrhs);
+        }
+        case TriRoute::WColChain: {
+            const bool lt = P->kind == CSX_TRI_LT;
+            return launch_lds(lt ? (R.rounds == 12 ? k_tri_wcolchain<CSX_TRI_LT, 12> : k_tri_wcolchain<CSX_TRI_LT, 2>)
+                                 : (R.rounds == 12 ? k_tri_wcolchain<CSX_TRI_UT, 12> : k_tri_wcolchain<CSX_TRI_UT, 2>),
+                              160 * 1024 - 1024, per_rhs, dim3(64), R.lds, P->n, P->Tp, P->Ti, P->Tx, R.window - 1, X, nrhs);
+        }
+        case TriRoute::Columns:
+        case TriRoute::ColChain:
+            return launch_lds(P->kind == CSX_TRI_L || P->kind == CSX_TRI_LT
+                                  ? (P->kind == CSX_TRI_L ? k_tri_columns<CSX_TRI_L> : k_tri_colchain<CSX_TRI_LT>)
+                                  : (P->kind == CSX_TRI_U ? k_tri_columns<CSX_TRI_U> : k_tri_colchain<CSX_TRI_UT>),
+                              R.route == TriRoute::Columns ? 160 * 1024 - 256 : 160 * 1024 - 1024, per_rhs, dim3(R.threads), R.lds, P->n,
+                              P->Tp, P->Ti, P->Tx, X, nrhs);
+        case TriRoute::Sequential:
+            hipLaunchKernelGGL(k_tri_sequential, dim3((unsigned)((nrhs + 63) / 64)), dim3(64), 0, ctx().stream, P->kind, P->n, P->Tp,
+                               P->Ti, P->Tx, X, nrhs);
+            CSX_LAUNCH_CHECK();
+            return CSX_OK;
+        case TriRoute::Levels: break;
+    }
+    return walk_levels(P, X, nrhs, relaxed);
+}
+
+int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
+    if (P->zero_pivot) return CSX_EZEROPIVOT;
+    if (P->n == 0 || nrhs == 0) return CSX_OK;
+    TriRouting R;
+    CSX_TRY(tri_route(P, nrhs, relaxed, &R));
+    return tri_launch(P, R, X, nrhs, relaxed);
+}
+
+// the relaxed order for every csx_tri_solve and csx_lusol_solve of the process: the ablation build's switch (experiments only)
+static bool tri_relaxed_env() {
+    static const bool on = ablation_env("CSX_TRI_RELAXED") != nullptr;
+    return on;
+}
+
 
 int tri_analyse_raw(const Csc *T, int kind, TriPlan **out) { return analyse(T, kind, out); }
 void tri_set_mate(TriPlan *P, TriPlan *mate) { P->mate = mate; }
@@ -2577,8 +2573,7 @@ extern "C" int csx_tri_solve(csx_handle_t h, csx_handle_t hX, int32_t nrhs) {
     TriPlan *P = (TriPlan *)get(h, K_TRIPLAN);
     Vec *X = vec(hX);
     if (!P || !X || nrhs < 0 || X->len < (int64_t)P->n * nrhs) return CSX_EINVAL;
-    static const bool relaxed_env = ablation_env("CSX_TRI_RELAXED") != nullptr;   // experiments only
-    return tri_solve_raw(P, (double *)X->d, nrhs, relaxed_env);
+    return tri_solve_raw(P, (double *)X->d, nrhs, tri_relaxed_env());
 }
 
 extern "C" int csx_permute_vec(csx_handle_t hp, csx_handle_t hb, csx_handle_t hx, int32_t n, int32_t nrhs,
@@ -2626,53 +2621,32 @@ static int lusol_two_sweeps(TriPlan *P1, TriPlan *P2, const int32_t *load, bool 
         else smap = inv;
         return CSX_OK;
     };
-    if (ctx().opt.tri_components && P1->rounding_equal && P2->rounding_equal && nrhs > 8) {
-        CSX_TRY(analyse_components(P1));
-        CSX_TRY(analyse_components(P2));
-        if (P1->comp_ok && P2->comp_ok) {
-            CSX_TRY(components_ragged(P1));
-            CSX_TRY(components_ragged(P2));
-        }
-        if (P1->comp_ok && P2->comp_ok && P1->rag && P2->rag) {
-            CSX_TRY(make_maps());
+    // which tier: what each factor's solve of this block would run, asked before anything is launched
+    const bool relaxed = tri_relaxed_env();
+    TriRouting r1, r2;
+    CSX_TRY(tri_route(P1, nrhs, relaxed, &r1));
+    CSX_TRY(tri_route(P2, nrhs, relaxed, &r2));
+    const bool ragged = P1->rounding_equal && P2->rounding_equal && r1.route == TriRoute::Ragged && r2.route == TriRoute::Ragged;
+    // the exact order on forests of small components: the same fusion through the in-LDS sweeps (k_tri_local reads and writes a
+    // component's rows through the row maps); the arithmetic and its order are those of the separate steps, bit for bit
+    const bool local = !P1->rounding_equal && !P2->rounding_equal && r1.route == TriRoute::Local && r2.route == TriRoute::Local;
+    if (ragged || local) {
+        CSX_TRY(make_maps());
+        if (ragged) {
             CSX_TRY(ragged_solve_io(P1->rag.get(), P1->comp_nodes, lmap, nullptr, !P1->forward, 1, b, x, nrhs, n));
             CSX_TRY(ragged_solve_io(P2->rag.get(), P2->comp_nodes, nullptr, smap, !P2->forward, 1, x, b, nrhs, n));
-            if (fused) *fused = 1;
-            return CSX_OK;
+        } else {
+            CSX_TRY(sweep_local(P1, r1, b, x, lmap, nullptr, nrhs));
+            CSX_TRY(sweep_local(P2, r2, x, b, nullptr, smap, nrhs));
         }
-    }
-    if (ctx().opt.tri_components && !P1->rounding_equal && !P2->rounding_equal && nrhs > 32) {
-        // the exact order on forests of small components: the same fusion through the in-LDS sweeps (k_tri_local reads and writes a
-        // component's rows through the row maps); the arithmetic and its order are those of the separate steps, bit for bit
-        CSX_TRY(analyse_components(P1));
-        CSX_TRY(analyse_components(P2));
-        if (P1->comp_ok && P2->comp_ok) {
-            CSX_TRY(make_maps());
-            bool took = false;
-            const TriIO io1{b, lmap, nullptr};
-            CSX_TRY(solve_components(P1, x, nrhs, &io1, &took));
-            if (took) {
-                const TriIO io2{x, nullptr, smap};
-                CSX_TRY(solve_components(P2, b, nrhs, &io2, &took));     // (same plan shape, same nrhs: taken too)
-                if (took) {
-                    if (fused) *fused = 1;
-                    return CSX_OK;
-                }
-                // (not taken after all: x holds the first sweep's solution of the permuted block -- finish with the separate steps)
-                CSX_TRY(tri_solve_raw(P2, x, nrhs, false));
-                hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, store, (const double *)x, b, n,
-                                   nrhs, store_inv ? 0 : 1);
-                CSX_LAUNCH_CHECK();
-                return CSX_OK;
-            }
-        }
+        if (fused) *fused = 1;
+        return CSX_OK;
     }
     hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, load, (const double *)b, x, n, nrhs,
                        load_inv ? 1 : 0);
     CSX_LAUNCH_CHECK();
-    static const bool relaxed_env = ablation_env("CSX_TRI_RELAXED") != nullptr;   // experiments only
-    CSX_TRY(tri_solve_raw(P1, x, nrhs, relaxed_env));
-    CSX_TRY(tri_solve_raw(P2, x, nrhs, relaxed_env));
+    CSX_TRY(tri_launch(P1, r1, x, nrhs, relaxed));
+    CSX_TRY(tri_launch(P2, r2, x, nrhs, relaxed));
     hipLaunchKernelGGL(k_permute, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, store, (const double *)x, b, n, nrhs,
                        store_inv ? 0 : 1);
     CSX_LAUNCH_CHECK();
