@@ -147,6 +147,12 @@ _PROTOS = {
     "csx_lu_refactor": [H, H, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int64)],
     "csx_lu_refactor_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p,
                              C.POINTER(C.c_int), _f64p],
+    "csx_assemble_plan_host": [C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "csx_assemble_host": [C.c_int32, _i32p, _i32p, _f64p, _f64p],
+    "csx_assemble_plan": [C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, C.POINTER(H)],
+    "csx_assemble_matrix": [H, H, C.POINTER(H)],
+    "csx_assemble": [H, H, H],
+    "csx_assemble_plan_info": [H, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

@@ -676,6 +676,96 @@ def cs_dupl(A):
     return True
 
 
+class _AssemblyPlan(object):
+    """What assembly_plan returns: see there."""
+
+    def __init__(self, T):
+        nz = T.nz
+        if len(T.i) < nz or len(T.p) < nz or (T.x is not None and len(T.x) < nz):
+            raise IndexError("list index out of range")
+        rows, cols = _csx.i32(T.i[:nz]), _csx.i32(T.p[:nz])
+        h = _csx.new_handle()
+        st = _csx.lib().csx_assemble_plan(T.m, T.n, nz, _csx.pi(rows), _csx.pi(cols), h)
+        if st == _csx.EINVAL and T.m >= 0 and T.n >= 0 and 0 <= nz <= 2 ** 31 - 1:
+            raise IndexError("list index out of range")   # the sizes are legal: an index is not
+        _csx.check(st, "csx_assemble_plan")
+        self._handle = h
+        self._fin = weakref.finalize(self, _csx.free, h)
+        self.m, self.n, self.nz = T.m, T.n, nz
+        self.nnz = self.info()["nnz"]
+        self._x0 = None if T.x is None else np.array(T.x[:nz], dtype=np.float64)   # T's values, until .matrix is made
+        self._matrix = None
+
+    def info(self):
+        """nz, nnz, max_dup (the most triplets of one slot), long_slots (slots folded by a wave of their own), build_us (the
+        host build of the plan) and kernel_us (the last assemble / update launch, between two events)"""
+        out = (_csx.C.c_int64 * 6)()
+        _csx.check(_csx.lib().csx_assemble_plan_info(self._handle, out), "csx_assemble_plan_info")
+        return dict(zip(("nz", "nnz", "max_dup", "long_slots", "build_us", "kernel_us"), (int(v) for v in out)))
+
+    def _values(self, values, what):
+        """list / numpy / dvec of exactly nz numbers -> a dvec (the caller's own when it is one: it is only read)"""
+        if values is None:
+            raise ValueError("%s: no values" % what)
+        v = values if isinstance(values, dvec) else dvec(np.asarray(values, dtype=np.float64).ravel())
+        if v.n * v.k != self.nz:
+            raise ValueError("%s: %d values given, the plan has %d triplets" % (what, v.n * v.k, self.nz))
+        return v
+
+    def _new_matrix(self, v):
+        h = _csx.new_handle()
+        _csx.check(_csx.lib().csx_assemble_matrix(self._handle, v.handle if v is not None else 0, h), "csx_assemble_matrix")
+        return h
+
+    @property
+    def matrix(self):
+        if self._matrix is None:
+            v = None if self._x0 is None else dvec(self._x0)
+            self._matrix = cs_pin(_from_device(self._new_matrix(v), lambda nnz: nnz))   # cs_dupl trims: nzmax = nnz
+            self._x0 = None
+        return self._matrix
+
+    def assemble(self, values):
+        v = self._values(values, "assemble")
+        out = dvec(self.nnz)
+        _csx.check(_csx.lib().csx_assemble(self._handle, v.handle, out.handle), "csx_assemble")
+        return out
+
+    def update(self, values=None):
+        v = self._values(values, "update")
+        M = self.matrix
+        if M._dev is None:      # unpinned or invalidated by the caller since: resident again, from its lists
+            cs_pin(M)
+        dev = M._dev
+        if not dev.info()[3]:   # pattern only so far: the first values allocate them
+            M._dev = _DevMatrix(self._new_matrix(v))
+            if not M._lazy:
+                M._x = [0.0] * self.nnz   # (filled by _refactored below)
+            dev = M._dev
+        else:
+            _csx.check(_csx.lib().csx_assemble(self._handle, v.handle, dev.handle), "csx_assemble")
+        _refactored(M, dev)
+        return M
+
+
+def assembly_plan(T):
+    """The plan of cs_dupl(cs_compress(T)) for a triplet list whose (i, j) stay and whose values change every step
+    (include/csx.h "assembly plan").  Only T.m, T.n, T.nz, T.i, T.p are read for the plan (a pattern-only T is
+    fine); IndexError for an index out of range, as cs_compress; None when T is not a triplet matrix.  The plan has
+    m, n, nz, nnz and info(), and
+      .matrix            cs_dupl(cs_compress(T)) as a device-resident pinned `cs` (nzmax = nnz, as cs_dupl leaves it) with T's values,
+                         or pattern only when T has none; made on first use, once.
+      .assemble(values)  values: list, numpy array or dvec of exactly nz numbers, in T's triplet order (ValueError otherwise;
+                         never modified, never aliased).  A NEW dvec of nnz values in .matrix's storage order -- the reference's
+                         bits -- which is what lusol_factor(P.matrix).refactor(...) and btf_factor(P.matrix).refactor(...) take.
+      .update(values)    the same values straight into .matrix, in place: the plans cached on it go, solvers built on it
+                         re-plan, host lists already read from it are refreshed in place.  Returns .matrix.  The first update
+                         of a pattern-only .matrix gives it its values; update() without values is a ValueError."""
+    if not CS_TRIPLET(T):
+        return None
+    return _AssemblyPlan(T)
+
+
 def cs_fkeep(A, fkeep, other):
     """Keep the entries for which fkeep(i, j, aij, other) is true, in place; returns the new number of
     entries, -1 on bad input (csparse.py:1172-1196).  The predicate is a Python callable, so this generic

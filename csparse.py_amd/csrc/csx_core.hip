@@ -245,6 +245,7 @@ static void free_object(Object &o) {
         case K_SHARDPLAN: destroy((ShardPlan *)o.ptr); break;
         case K_BTFPLAN: destroy((BtfPlan *)o.ptr); break;
         case K_LUREFPLAN: destroy((LuRefPlan *)o.ptr); break;
+        case K_ASMPLAN: destroy((AsmPlan *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it
@@ -559,6 +560,7 @@ const OptSlot kOptSlots[] = {
     {"chol.clique", &Options::chol_clique, 0},           {"chol.forest", &Options::chol_forest, 0},
     {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
     {"gaxpy.block_route", &Options::gaxpy_block_route, 3}, {"sparseinv.walk", &Options::sparseinv_walk, 0},
+    {"assemble.long", &Options::assemble_long, 7},
 };
 int normalise(int kind, int value) {
     switch (kind) {
@@ -568,6 +570,7 @@ int normalise(int kind, int value) {
     case 3: return (value == 1 || value == 2) ? value : 0;
     case 5: return (value == 0 || value == 2) ? value : 1;
     case 6: return (value == 0 || value == 1) ? value : 2;
+    case 7: return value < 1 ? 1 : value;
     }
     return value;
 }

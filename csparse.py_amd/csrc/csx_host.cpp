@@ -902,3 +902,76 @@ extern "C" int csx_lu_refactor_host(int32_t n, const int32_t *Ap, const int32_t 
     std::vector<double> x((size_t)n, 0.0);
     return csx::lu_refactor_columns(n, nullptr, n, Ap, Ai, Ax, pinv, Lp, Li, Lx, Up, Ui, Ux, x.data(), ok, ratio);
 }
+
+// ---- assembly plan (include/csx.h has the definition) ------------------------------------------------
+// The reference's two loops on the indices alone.  cs_compress: a stable counting sort of the triplets by column.  cs_dupl:
+// down every column, a row seen before in this column (where[r] >= the column's first slot) lands in the slot of its first
+// occurrence, any other row opens the next slot.  What the loops did to the values is kept as lists: slot s is the fold of
+// the triplets src[sp[s] .. sp[s + 1]), ascending (the order the counting sort keeps and cs_dupl adds in).
+extern "C" int csx_assemble_plan_host(int32_t m, int32_t n, int64_t nz, const int32_t *Ti, const int32_t *Tj, int32_t *Cp,
+                                      int32_t *Ci, int32_t *sp, int32_t *src, int32_t *nnz_out) {
+    if (m < 0 || n < 0 || nz < 0 || nz > INT32_MAX || !Cp || !sp || !nnz_out || (nz > 0 && (!Ti || !Tj || !Ci || !src)))
+        return CSX_EINVAL;
+    for (int64_t k = 0; k < nz; k++)
+        if (Ti[k] < 0 || Ti[k] >= m || Tj[k] < 0 || Tj[k] >= n) return CSX_EINVAL;   // the reference would raise IndexError
+    const int32_t cnt = (int32_t)nz;
+    // the counting sort: src[q] = the triplet at position q of cs_compress's result (src is scratch until the last loop)
+    std::vector<int32_t> next((size_t)n + 1, 0);
+    for (int32_t k = 0; k < cnt; k++) next[(size_t)Tj[k] + 1]++;
+    for (int32_t j = 0; j < n; j++) next[(size_t)j + 1] += next[j];
+    std::vector<int32_t> colp(next);   // column pointers of the compressed form
+    for (int32_t k = 0; k < cnt; k++) src[next[Tj[k]]++] = k;
+    // the first-occurrence scan: slot[k] = where triplet k lands, sp[s + 1] = how many land in slot s
+    std::vector<int32_t> where((size_t)m, -1), slot((size_t)cnt);
+    int32_t nnz = 0;
+    sp[0] = 0;
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t start = nnz;
+        for (int32_t q = colp[j]; q < colp[(size_t)j + 1]; q++) {
+            const int32_t k = src[q], r = Ti[k];
+            if (where[r] >= start) {
+                sp[(size_t)where[r] + 1]++;
+                slot[k] = where[r];
+            } else {
+                where[r] = nnz;
+                Ci[nnz] = r;
+                sp[(size_t)nnz + 1] = 1;
+                slot[k] = nnz++;
+            }
+        }
+        Cp[j] = start;
+    }
+    Cp[n] = nnz;
+    for (int32_t s = 0; s < nnz; s++) sp[(size_t)s + 1] += sp[s];
+    // grouped by slot, ascending inside a slot: the triplets in their own order, each to the next free place of its slot
+    std::vector<int32_t> fill(sp, sp + nnz);
+    for (int32_t k = 0; k < cnt; k++) src[fill[slot[k]]++] = k;
+    *nnz_out = nnz;
+    return CSX_OK;
+}
+
+// Cx[s] = ((Tx[t0] + Tx[t1]) + Tx[t2]) + ... over src[sp[s] .. sp[s + 1]): the first term assigned, one addition per further
+// term (no multiply: nothing to contract)
+extern "C" int csx_assemble_host(int32_t nnz, const int32_t *sp, const int32_t *src, const double *Tx, double *Cx) {
+    if (nnz < 0 || !sp || (nnz > 0 && (!src || !Tx || !Cx))) return CSX_EINVAL;
+    for (int32_t s = 0; s < nnz; s++) {
+        if (sp[s + 1] <= sp[s]) return CSX_EINVAL;
+        double acc = Tx[src[sp[s]]];
+        for (int32_t t = sp[s] + 1; t < sp[s + 1]; t++) acc = acc + Tx[src[t]];
+        Cx[s] = acc;
+    }
+    return CSX_OK;
+}
+
+namespace csx {
+// the longest slot; *longs: the slots of more than thr terms, ascending
+int32_t assemble_slot_stats(int32_t nnz, const int32_t *sp, int32_t thr, std::vector<int32_t> *longs) {
+    int32_t longest = 0;
+    for (int32_t s = 0; s < nnz; s++) {
+        const int32_t len = sp[s + 1] - sp[s];
+        longest = std::max(longest, len);
+        if (len > thr) longs->push_back(s);
+    }
+    return longest;
+}
+}  // namespace csx

@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN };
 
 struct Csc;
 
@@ -208,6 +208,8 @@ struct Refactor;   // csx_refactor.hip
 struct LuRefPlan;  // csx_refactor.hip
 void destroy(Refactor *p);
 void destroy(LuRefPlan *p);
+struct AsmPlan;    // csx_assemble_plan.hip
+void destroy(AsmPlan *p);
 
 struct Object {
     Kind kind = K_FREE;
@@ -254,6 +256,8 @@ struct Options {
     int spgemm_ordered = 0;           // cs_multiply: sum every entry's products in the reference's order (bit-identical x)
     int sparseinv_walk = 1;           // csx_chol_inverse: a run of depths of one column each is walked by one workgroup in one
                                       // launch (0: one launch per depth, same bits)
+    int assemble_long = 64;           // csx_assemble_plan: a slot of more than this many terms is folded by a wave of its own, a shorter
+                                      // one by one lane (read when a plan is built; >= 1)
     int lu_etree = 0;                 // cs_lu of one connected matrix on the device, columns scheduled by the column etree:
                                       // 0 never (the default since round 4: measured at best a tie with one host core, on the
                                       // shape it was made for -- profiles/r04_ablation.md), 1 for shallow trees with short

@@ -619,6 +619,41 @@ int csx_lu_refactor_plan(csx_handle_t L, csx_handle_t U, csx_handle_t A, const i
                          csx_handle_t *plan);
 int csx_lu_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, double *ratio, int64_t *cols);
 
+/* ---- assembly plan: new triplet values into a fixed CSC pattern (assembly_plan) --------------------
+ * Definition.  Given the triplets (Ti[k], Tj[k]), k = 0 .. nz-1, of an m-by-n matrix, let C = cs_dupl(cs_compress(T)) as the
+ * reference computes it.
+ * Pattern: C.p and C.i are the reference's: columns in order, inside a column the rows in order of first appearance in the
+ *   triplet list (cs_compress is a stable counting sort by column, cs_dupl keeps the first occurrence in place).
+ * Plan: for every stored slot s of C, the triplets that land in it, ascending: sp[0 .. nnz] (slot pointers) and src[0 .. nz)
+ *   (triplet indices grouped by slot), both int32.
+ * Values: C.x[s] = (((v[t0]) + v[t1]) + v[t2]) + ... over src[sp[s] .. sp[s+1]), in that order, one IEEE double addition per
+ *   term.  The first term is ASSIGNED, not added to zero (the reference does Ax[nz] = Ax[p] for a first occurrence): a slot
+ *   whose terms are all -0.0 is -0.0.  No atomics, no reassociation; the same bits on every run.
+ * csx_assemble_plan_host: the rule on host arrays -- a counting sort by column, then a first-occurrence scan with m marks;
+ *   sequential, O(nz + m + n).  The caller's Cp, Ci, sp, src have room for n+1, nz, nz+1, nz entries; *nnz: the slots.
+ *   CSX_EINVAL for an index outside [0, m) x [0, n) or nz > 2^31 - 1; nz = 0, n = 0 and empty columns are legal.
+ * csx_assemble_host: the fold on host arrays: Cx[0 .. nnz) from Tx through sp, src.
+ * csx_assemble_plan: Ti, Tj HOST arrays; runs the host rule once and uploads p, i, sp, src: a NEW plan handle (csx_free) that
+ *   owns them -- 4 nz + 4 (nnz + 1) bytes beside the pattern (sp is not kept when nz == nnz: nothing reads it).  The slots
+ *   are classified: one of more than "assemble.long" terms (csx_set_option, read here; default 64) is folded by a wave of its
+ *   own -- 64 sources loaded per step, added in index order -- a shorter one by one lane; with no duplicates at all the
+ *   fold is the permuted copy out[s] = Tx[src[s]].
+ * csx_assemble_matrix: a NEW CSC handle with the plan's pattern (copied: plan and matrix have independent lifetimes), its
+ *   values assembled from the vector Tx, or pattern only when Tx is 0.
+ * csx_assemble: Tx a device vector of at least nz doubles; out a device vector of at least nnz doubles (not Tx), or a CSC
+ *   handle with the plan's m, n, nnz and values, whose x is overwritten in place (the SpMV plans cached on it are dropped;
+ *   triangular-solve plans made from it are stale).  CSX_EINVAL on a size mismatch, nothing written.  One launch queued on
+ *   the context's stream; no host synchronisation.
+ * csx_assemble_plan_info: info[6] = nz, nnz, the most terms of a slot, the slots folded by a wave, microseconds of the host
+ *   build, microseconds of the last launch (between two events; waits for it). */
+int csx_assemble_plan_host(int32_t m, int32_t n, int64_t nz, const int32_t *Ti, const int32_t *Tj, int32_t *Cp, int32_t *Ci,
+                           int32_t *sp, int32_t *src, int32_t *nnz);
+int csx_assemble_host(int32_t nnz, const int32_t *sp, const int32_t *src, const double *Tx, double *Cx);
+int csx_assemble_plan(int32_t m, int32_t n, int64_t nz, const int32_t *Ti, const int32_t *Tj, csx_handle_t *plan);
+int csx_assemble_matrix(csx_handle_t plan, csx_handle_t Tx, csx_handle_t *A);
+int csx_assemble(csx_handle_t plan, csx_handle_t Tx, csx_handle_t out);
+int csx_assemble_plan_info(csx_handle_t plan, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
