@@ -560,7 +560,7 @@ const OptSlot kOptSlots[] = {
     {"chol.clique", &Options::chol_clique, 0},           {"chol.forest", &Options::chol_forest, 0},
     {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
     {"gaxpy.block_route", &Options::gaxpy_block_route, 3}, {"sparseinv.walk", &Options::sparseinv_walk, 0},
-    {"assemble.long", &Options::assemble_long, 7},
+    {"assemble.long", &Options::assemble_long, 7},         {"gaxpy.shape", &Options::gaxpy_shape, 8},
 };
 int normalise(int kind, int value) {
     switch (kind) {
@@ -571,6 +571,7 @@ int normalise(int kind, int value) {
     case 5: return (value == 0 || value == 2) ? value : 1;
     case 6: return (value == 0 || value == 1) ? value : 2;
     case 7: return value < 1 ? 1 : value;
+    case 8: return (value >= 0 && value <= 3) ? value : -1;
     }
     return value;
 }

@@ -24,6 +24,8 @@ namespace csx {
 
 int gaxpy_tiled_prepare(Csc *A);                                 // csx_gaxpy_tiled.hip
 int gaxpy_tiled_run(const Csc *A, const double *x, double *y);   // csx_gaxpy_tiled.hip
+int gaxpy_tiled_shape(const TiledPlan *t);                       // ... the launch shape in force
+int gaxpy_tiled_group_counts(const TiledPlan *t, std::vector<int32_t> &groups);
 
 #pragma clang fp contract(off)
 __global__ __launch_bounds__(256) void k_gaxpy_exact(int32_t rows, const int32_t *__restrict__ ptr,
@@ -352,6 +354,46 @@ extern "C" int csx_gaxpy_plan_shape(csx_handle_t hA, int *shape, double *ms4) {
     if (shape) *shape = A->tiled->shape;
     if (ms4)
         for (int k = 0; k < 4; k++) ms4[k] = A->tiled->shape_ms[k];
+    return CSX_OK;
+}
+
+/* The geometry of the tiled plan, for tests that must know which edge of the kernel they reached: info[10] = rows per row
+ * block, row blocks, column slabs, columns per slab, bits of the row field of a 4-byte key, groups of 256 entries (padding
+ * included), bytes per key (3 or 4), the launch shape in force (0..3: "gaxpy.shape" if set, otherwise the plan's own), and the
+ * fewest and the most groups of a row block. */
+extern "C" int csx_gaxpy_plan_geometry(csx_handle_t hA, int64_t *info) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !A->tiled || !info) return CSX_EINVAL;
+    const TiledPlan *t = A->tiled.get();
+    std::vector<int32_t> groups;
+    CSX_TRY(gaxpy_tiled_group_counts(t, groups));
+    int32_t lo = groups.empty() ? 0 : groups[0], hi = lo;
+    for (int32_t g : groups) {
+        lo = g < lo ? g : lo;
+        hi = g > hi ? g : hi;
+    }
+    info[0] = t->row_block;
+    info[1] = t->nrb;
+    info[2] = t->nslab;
+    info[3] = t->slab_cols;
+    info[4] = t->rb_bits;
+    info[5] = t->ngroups;
+    info[6] = t->tile_key24 ? 3 : 4;
+    info[7] = gaxpy_tiled_shape(t);
+    info[8] = lo;
+    info[9] = hi;
+    return CSX_OK;
+}
+
+/* groups[b] = groups of 256 entries of row block b, for every one of the plan's row blocks (info[1] above). */
+extern "C" int csx_gaxpy_plan_groups(csx_handle_t hA, int32_t *groups) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !A->tiled || !groups) return CSX_EINVAL;
+    std::vector<int32_t> g;
+    CSX_TRY(gaxpy_tiled_group_counts(A->tiled.get(), g));
+    for (size_t b = 0; b < g.size(); b++) groups[b] = g[b];
     return CSX_OK;
 }
 

@@ -402,6 +402,7 @@ int gaxpy_tiled_prepare(Csc *A) {
             CSX_HIP(hipStreamSynchronize(s));
             k24 = h == 0;
         }
+        t->ngroups = ngroups;
         CSX_TRY(t->tile_len.alloc((size_t)ngroups));  // group_info
         if (!k24) CSX_TRY(t->tile_key.alloc((size_t)ngroups * TL_GROUP));
         if (k24) CSX_TRY(t->tile_key24.alloc((size_t)ngroups * TL_GROUP * 3 + 16));
@@ -481,7 +482,28 @@ static int gaxpy_tiled_pick_shape(Csc *A) {
     return CSX_OK;
 }
 
-int gaxpy_tiled_run(const Csc *A, const double *x, double *y) { return gaxpy_tiled_launch(A, x, y, A->tiled->shape); }
+// The launch shape in force: "gaxpy.shape" when it names one (read here, at launch time: one plan runs at any of the
+// four), otherwise the plan's own (the tuner's pick, or 4 x 5 when it was not timed).
+int gaxpy_tiled_shape(const TiledPlan *t) {
+    const int forced = ctx().opt.gaxpy_shape;
+    if (forced >= 0 && forced < TL_NSHAPES) return forced;
+    return t->shape >= 0 && t->shape < TL_NSHAPES ? t->shape : 0;
+}
+
+int gaxpy_tiled_run(const Csc *A, const double *x, double *y) {
+    return gaxpy_tiled_launch(A, x, y, gaxpy_tiled_shape(A->tiled.get()));
+}
+
+// csx_gaxpy_plan_geometry / csx_gaxpy_plan_groups: groups[b] = groups of 256 entries of row block b (nrb counts)
+int gaxpy_tiled_group_counts(const TiledPlan *t, std::vector<int32_t> &groups) {
+    std::vector<int32_t> ptr((size_t)t->nrb + 1);
+    hipStream_t s = ctx().stream;
+    CSX_HIP(hipMemcpyAsync(ptr.data(), t->tile_ptr, ptr.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    groups.resize((size_t)t->nrb);
+    for (int32_t b = 0; b < t->nrb; b++) groups[b] = ptr[b + 1] - ptr[b];
+    return CSX_OK;
+}
 
 static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shape) {
     const TiledPlan *t = A->tiled.get();

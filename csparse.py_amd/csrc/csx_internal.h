@@ -111,6 +111,7 @@ struct TiledPlan {
     int32_t nrb = 0;               // number of row blocks
     int32_t nslab = 0;             // number of column slabs
     int32_t slab_cols = 0;         // columns per slab
+    int64_t ngroups = 0;           // groups of 256 entries over all tiles (padding included)
     DevBuf<int32_t> tile_ptr;      // [nrb + 1] first group of every row block
     DevBuf<int32_t> tile_len;      // [ngroups] group info: (slab << 9) | entries in the group
     DevBuf<uint32_t> tile_key;     // packed (local col << rb_bits) | local row; null when the 3-byte keys are in use
@@ -242,6 +243,8 @@ struct Options {
     int tri_columns = 1;          // tri-solve: small chain-like systems by the column loop, x in LDS
     int gaxpy_keys24 = 1;         // tiled cs_gaxpy plan: 3-byte keys when the matrix allows them
     int gaxpy_tune_shape = 0;    // tiled cs_gaxpy plan: time the launch shapes when the plan is built and keep the fastest
+    int gaxpy_shape = -1;        // tiled cs_gaxpy: -1 = the plan's own launch shape, 0..3 = that shape; read at every launch, so
+                                 // one plan can be run at all four (any other value reads back as -1)
     int gaxpy_block_route = 0;   // csx_gaxpy_block AUTO: 0 = its own rule, 1 = the block kernel, 2 = the column route
     int tri_row_waves = 1;        // level-scheduled solves: a wave per row for few right-hand sides and long rows
     int tri_levels_where = 0;         // level analysis: 0 = device for big factors, host for small; 1 = host; 2 = device

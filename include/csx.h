@@ -74,7 +74,8 @@ int csx_mem_info(int64_t *cached_bytes, int64_t *live_bytes, int64_t *device_fre
  * Every setting computes correct results; no environment variable changes which kernel runs or what it computes
  * (the environment is read for the allocator's cap above and for CSX_CHOL_TIMING=1, which prints cs_chol's phase
  * times to stderr).  Names (default 1): "chol.dense_trees", "chol.band", "cholsol.dense_blocks", "spgemm.one_pass",
- * "tri.chain_walker", "tri.components", "tri.columns", "tri.push", "tri.row_waves", "gaxpy.keys24"; "gaxpy.tune_shape" (default 0); "tri.levels_where" (default 0: level
+ * "tri.chain_walker", "tri.components", "tri.columns", "tri.push", "tri.row_waves", "gaxpy.keys24"; "gaxpy.tune_shape" (default 0);
+ * "gaxpy.shape" (default -1: a tiled csx_gaxpy launches the plan's own shape; 0..3 = that shape, read at every launch); "tri.levels_where" (default 0: level
  * analysis of a triangular plan on the device for big factors and on the host for small ones; 1 = host, 2 = device);
  * "chol.wband" (blocked dense-band cs_chol for chain-like factors: default 1 = for half-widths above 80, 0 = never,
  * 2 = whenever the tree is chain-like) and "chol.wband_nb" (columns per step: 16 (default) or 32; any other value
@@ -150,6 +151,16 @@ int csx_gaxpy_plan_info(csx_handle_t A, int *has_rows, int *has_tiled, int *key_
  * *shape = 0 (4 x 5), 1 (2 x 10), 2 (8 x 4), 3 (2 x 8), or -1 (not timed: 4 x 5); ms4[0..3] = the candidates' ms per
  * pass (0 when not timed).  CSX_EINVAL without a tiled plan. */
 int csx_gaxpy_plan_shape(csx_handle_t A, int *shape, double *ms4);
+/* csx_set_option("gaxpy.shape", s) (default -1: the plan's own shape; 0..3 = that shape whatever the plan picked; any other
+ * value reads back as -1) is read at every tiled csx_gaxpy, not when the plan is built: one plan runs at all four shapes,
+ * with the same results up to the order of the LDS additions.  The tuner times every candidate whatever it says.
+ * csx_gaxpy_plan_geometry: info[10] = rows per row block, row blocks, column slabs, columns per slab, bits of the row
+ * field of a 4-byte key, groups of 256 entries (padding included), bytes per key (3 or 4), the launch shape in force (0..3:
+ * "gaxpy.shape" if set, otherwise the plan's own, 0 when it was not timed), the fewest and the most groups of a row block.
+ * csx_gaxpy_plan_groups: groups[b] = groups of row block b, for all info[1] row blocks.  Both CSX_EINVAL without a tiled
+ * plan. */
+int csx_gaxpy_plan_geometry(csx_handle_t A, int64_t *info);
+int csx_gaxpy_plan_groups(csx_handle_t A, int32_t *groups);
 /* One-shot form for host arrays (the reference's list signature): y[0..m) += A x in the reference's
  * summation order (bit-identical), nothing left on the device.  x (values) must be present. */
 int csx_gaxpy_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, const double *x, const double *xv,
