@@ -147,6 +147,9 @@ _PROTOS = {
     "csx_btf_refactor_dx": [H, _f64p],
     "csx_lu_refactor_plan": [H, H, H, _i32p, _i32p, C.POINTER(H)],
     "csx_lu_refactor": [H, H, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int64)],
+    "csx_chol_refactor_plan": [H, H, _i32p, C.POINTER(H)],
+    "csx_chol_refactor": [H, H, C.POINTER(C.c_int), _i32p],
+    "csx_chol_refactor_info": [C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "csx_lu_refactor_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p,
                              C.POINTER(C.c_int), _f64p],
     "csx_assemble_plan_host": [C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],

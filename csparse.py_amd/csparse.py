@@ -1427,7 +1427,10 @@ def cholsol_factor(A, order=0, exact=None):
       cores (blocked TRSM with explicit tile inverses, refused when an inverse is large), a big elimination tree to the
       supernodal schedule.  (G-spd, 128 right-hand sides: 2.4 ms against 4.8; bcsstk16: 0.4 ms against 6.6.)
     exact=True: every solve, blocks too, bit-identical to the reference's order.   exact=False: every solve rounding-equal.
-    cs_cholsol, the reference's own driver, is always exact."""
+    cs_cholsol, the reference's own driver, is always exact.
+    refactor(A2): new values on A's pattern with the analysis kept: L.x becomes the factor of A2, byte-equal to a
+    fresh cholsol_factor(A2, order, exact)'s (to rounding only under "chol.exact" = 0 with exact other than True); False, and nothing changed, when A2 is not positive definite; ValueError for
+    another pattern.  refactor_info(): the last refactor's route, launch counts and times."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     first_plan = None
@@ -1488,6 +1491,7 @@ def cholsol_factor(A, order=0, exact=None):
             self._exact_now = start_exact            # the order the plan is in
             self._box = [self.plan_handle]
             self._fin = weakref.finalize(self, lambda box: _csx.free(box[0]), self._box)
+            self._rplan, self._rinfo = None, None    # refactor(): made by its first call
 
         def _current(self):
             """The plan copies part of L's values (forward gather arrays, fragments): after cs_updown(F.L, ...) changed
@@ -1582,6 +1586,41 @@ def cholsol_factor(A, order=0, exact=None):
         def logdet(self):
             """log det A = 2 sum_j log L(j,j), the sum correctly rounded (math.fsum)"""
             return 2.0 * math.fsum(np.log(_first_entries(N.L)).tolist())
+
+        def refactor(self, A2):
+            """New values on the kept analysis: A2 a CSC `cs` with A's exact pattern, or nnz(A) values in A's
+            storage order (numpy, list or dvec), in A's own numbering whatever the order; ValueError for another pattern or
+            length.  L.x becomes the factor of A2, byte-equal to a fresh cholsol_factor(A2, order, exact)'s under the options
+            in force (under "chol.exact" = 0 with exact other than True: equal to rounding, the fresh factor's block kernel
+            being the emitting one); L.p, L.i and the ordering stay.  True on success; False when A2 is not positive
+            definite, and then L and the solves are exactly as before.  The first call makes the plan (a solver never
+            refactored carries nothing of it); the solve plans are rebuilt from the new values at the next solve, as after
+            update().  Legal after update / downdate / cs_updown: the refactor overwrites L from A2."""
+            t0 = time.perf_counter()
+            A2 = _refactor_input(A, A2)
+            if self._rplan is None:
+                h = _csx.new_handle()
+                with _Resident(A) as dA:
+                    _csx.check(_csx.lib().csx_chol_refactor_plan(dA.handle, dev.handle, _csx.pi(pinv), h),
+                               "csx_chol_refactor_plan")
+                self._rplan = h
+                weakref.finalize(self, lambda hp, keep: _csx.free(hp), h, dev)   # (the plan borrows L: freed before dev can go)
+            ok, info = _csx.C.c_int(0), np.zeros(8, dtype=np.int32)
+            _refactor_call(A2, lambda h2: _csx.lib().csx_chol_refactor(self._rplan, h2, ok, _csx.pi(info)), ok)
+            if ok.value:
+                _refactored(N.L, dev)
+            num, call = _csx.C.c_double(0.0), _csx.C.c_double(0.0)
+            _csx.check(_csx.lib().csx_chol_refactor_info(num, call), "csx_chol_refactor_info")
+            self._rinfo = {"ok": bool(ok.value), "route": "forest" if info[0] else "general", "levels": int(info[1]),
+                           "supernodes": int(info[2]), "trees": int(info[3]), "dense_trees": int(info[4]), "band": int(info[5]),
+                           "first": bool(info[6]), "numeric_ms": num.value, "ms": 1e3 * (time.perf_counter() - t0)}
+            return bool(ok.value)
+
+        def refactor_info(self):
+            """None before the first refactor; else the last one's ok, route ("general" / "forest"), levels (launches of the
+            level walk), supernodes, trees, dense_trees, band (0 none, 1 register window, 2 blocked dense band), first (this
+            call made the plan's scratch), numeric_ms (HIP events around the numeric kernels) and ms (the whole call)."""
+            return dict(self._rinfo) if self._rinfo is not None else None
 
         def _solve_sharded(self, b, comm, nrhs):
             # every rank solves in the order the ROOT's right-hand side asks for

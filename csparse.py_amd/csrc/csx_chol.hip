@@ -92,12 +92,6 @@ __global__ __launch_bounds__(256) void k_chol_winner(int32_t n, const int32_t *_
     }
 }
 
-__global__ __launch_bounds__(256) void k_chol_init(int64_t lnz, const int32_t *__restrict__ win,
-                                                   const double *__restrict__ Ax, double *__restrict__ Lx) {
-    int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q < lnz) Lx[q] = win[q] >= 0 ? Ax[win[q]] : 0.0;
-}
-
 // ---- one column ---------------------------------------------------------------------------------
 // acc_v / acc_r: wave-private LDS (CH_ACC doubles / ints).  Columns longer than CH_ACC keep their
 // sums in Lx itself (global), the row search then runs on Li in global memory.
@@ -634,6 +628,367 @@ struct EvGuard {
     }
 };
 
+// ---- the general path in two steps: analysis (kept by a refactor plan, csx_chol_refactor.hip) and run ------------------
+// Everything the numeric kernels read beside L.p / L.i and the values: the row view, the entry map, the schedule (small
+// trees, level lists, supernode groups) and the band decision.  csx_chol builds one, runs it once and lets it go; a refactor
+// plan keeps it and runs it for every new set of values.
+struct CholAnalysis {
+    int32_t n = 0, lnz = 0;
+    DevBuf<int32_t> rp, rc, rpos;      // row view of L: for row j the columns k ascending, the diagonal last, and where L(j,k) lies
+    DevBuf<int32_t> win;               // per slot of L: the entry of A that lands there (of duplicates the last), -1 for fill
+    DevBuf<int32_t> pinv;              // the caller's pinv on the device while the entry map is made
+    DevBuf<int32_t> small_cols, level_cols, level_ptr, col_level, split, sn_cols, sn_ptr;
+    DevBuf<Tree> trees, dense;
+    DevBuf<SnDesc> sns;
+    DevBuf<int> flags;                 // [0] an entry of A without a slot in L, [1] first non-positive pivot, [2] band width
+    std::vector<int32_t> level_ptr_h;  // the level lists without the supernodes' columns
+    std::vector<int32_t> sn_group_ptr{0}, sn_group_first{0}, sn_group_maxw, sn_group_maxrows;
+    std::vector<int32_t> sn_group_at;  // level -> group index, -1 none (read only: a run does not consume it)
+    int32_t ntrees = 0, ndense = 0, nsn = 0;
+    int64_t big_cols = 0;              // columns of trees too big for the tree kernels
+    bool has_levels = false;
+    int band = 0;                      // 0 none, 1 register window, 2 blocked dense band: decided ONCE, by chol_analysis_map
+    int band_hb = 0, band_nb = 16;     // half-bandwidth, columns per step of the blocked band
+    int32_t run_launches = 0;          // launches of the level walk of the last run
+    struct Host {                      // the sources of the schedule uploads, alive until the stream has been synchronised
+        std::vector<Tree> trees, dense;
+        std::vector<int32_t> small_cols, level_cols, col_level, sn_cols;
+        std::vector<SnDesc> sns;
+    } host;
+    bool host_live = false;            // uploads from `host` may be in flight
+    ~CholAnalysis() {
+        if (host_live) (void)hipStreamSynchronize(ctx().stream);   // (an error between the schedule and the run)
+    }
+};
+
+void destroy(CholAnalysis *An) { delete An; }
+
+// host part: the forest partition, dense small trees, fundamental supernodes; and their upload
+static int chol_analysis_schedule(CholAnalysis *An, int32_t n, int32_t lnz, const int32_t *parent, const int32_t *cp) {
+    An->n = n;
+    An->lnz = lnz;
+    Forest F;
+    partition_forest(n, parent, F);
+    // small trees that are dense blocks on consecutive columns take the LDS block kernel
+    std::vector<Tree> dense_trees, other_trees;
+    for (const Tree &tr : F.small) {
+        bool dense = tr.count <= CD_MAX;
+        const int32_t c0 = F.small_cols[(size_t)tr.first];
+        for (int32_t a = 0; dense && a < tr.count; a++) {
+            const int32_t c = F.small_cols[(size_t)tr.first + a];
+            dense = c == c0 + a && cp[c + 1] - cp[c] == tr.count - a;
+        }
+        (dense ? dense_trees : other_trees).push_back(tr);
+    }
+    if (!ctx().opt.chol_dense_trees) {
+        other_trees = F.small;
+        dense_trees.clear();
+    }
+    // ---- fundamental supernodes of the big trees: w >= 8 consecutive columns, each the ONLY child of the next, column
+    // counts falling by one (the separators of a nested-dissection ordering).  They leave the level lists: when the
+    // walk below reaches the level of a supernode's first column, every update from outside it is available (all of
+    // them come from below that first column), so its columns take them in one launch and the trapezoid is then
+    // factored densely in place (chol_supernodes).
+    An->big_cols = (int64_t)F.level_cols.size();
+    std::vector<int32_t> col_level_h;                      // level of every column of a big tree, -1 elsewhere
+    std::vector<SnDesc> sns;                               // grouped by the level of their first column
+    std::vector<int32_t> sn_cols;
+    if (!F.level_cols.empty()) {
+        const int32_t nlev0 = (int32_t)F.level_ptr.size() - 1;
+        col_level_h.assign((size_t)n, -1);
+        for (int32_t lv = 0; lv < nlev0; lv++)
+            for (int32_t q = F.level_ptr[(size_t)lv]; q < F.level_ptr[(size_t)lv + 1]; q++) col_level_h[(size_t)F.level_cols[(size_t)q]] = lv;
+        An->sn_group_at.assign((size_t)nlev0 + 1, -1);
+        if (ctx().opt.chol_supernodes) {
+            std::vector<int32_t> nchild((size_t)n, 0);
+            for (int32_t j = 0; j < n; j++)
+                if (parent[j] >= 0) nchild[(size_t)parent[j]]++;
+            std::vector<std::pair<int32_t, SnDesc>> found;     // (start level, supernode)
+            std::vector<char> member((size_t)n, 0);
+            for (int32_t j = 0; j < n;) {
+                if (col_level_h[(size_t)j] < 0) {
+                    j++;
+                    continue;
+                }
+                const int32_t a = j;
+                while (j + 1 < n && parent[j] == j + 1 && nchild[(size_t)j + 1] == 1 &&
+                       cp[j + 2] - cp[j + 1] == cp[j + 1] - cp[j] - 1)
+                    j++;
+                const int32_t w = j - a + 1;
+                if (w >= SN_MIN_WIDTH) {
+                    found.push_back({col_level_h[(size_t)a], SnDesc{a, w, cp[a + 1] - cp[a] - w}});
+                    for (int32_t c = a; c <= j; c++) member[(size_t)c] = 1;
+                }
+                j++;
+            }
+            if (!found.empty()) {
+                std::stable_sort(found.begin(), found.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+                for (size_t f = 0; f < found.size(); f++) {
+                    const int32_t lv = found[f].first;
+                    if (f == 0 || lv != found[f - 1].first) {
+                        if (f) {
+                            An->sn_group_ptr.push_back((int32_t)sn_cols.size());
+                            An->sn_group_first.push_back((int32_t)sns.size());
+                        }
+                        An->sn_group_at[(size_t)lv] = (int32_t)An->sn_group_maxw.size();
+                        An->sn_group_maxw.push_back(0);
+                        An->sn_group_maxrows.push_back(0);
+                    }
+                    const SnDesc &d = found[f].second;
+                    sns.push_back(d);
+                    for (int32_t c = d.a; c < d.a + d.w; c++) sn_cols.push_back(c);
+                    An->sn_group_maxw.back() = std::max(An->sn_group_maxw.back(), d.w);
+                    An->sn_group_maxrows.back() = std::max(An->sn_group_maxrows.back(), d.w + d.r);
+                }
+                An->sn_group_ptr.push_back((int32_t)sn_cols.size());
+                An->sn_group_first.push_back((int32_t)sns.size());
+                // the level lists without the supernodes' columns
+                std::vector<int32_t> cols2, ptr2{0};
+                for (int32_t lv = 0; lv < nlev0; lv++) {
+                    for (int32_t q = F.level_ptr[(size_t)lv]; q < F.level_ptr[(size_t)lv + 1]; q++)
+                        if (!member[(size_t)F.level_cols[(size_t)q]]) cols2.push_back(F.level_cols[(size_t)q]);
+                    ptr2.push_back((int32_t)cols2.size());
+                }
+                F.level_cols.swap(cols2);
+                F.level_ptr.swap(ptr2);
+            }
+        }
+    }
+    An->ntrees = (int32_t)other_trees.size();
+    An->ndense = (int32_t)dense_trees.size();
+    An->nsn = (int32_t)sns.size();
+    An->has_levels = !col_level_h.empty();
+    // the uploads are queued from host vectors that stay with the analysis (no wait here: the stream is synchronised by
+    // whoever reads a result back first, as before; a kept analysis lets them go after that)
+    CholAnalysis::Host &H = An->host;
+    An->host_live = true;
+    H.trees = std::move(other_trees);
+    H.dense = std::move(dense_trees);
+    H.small_cols = std::move(F.small_cols);
+    H.level_cols = std::move(F.level_cols);
+    H.col_level = std::move(col_level_h);
+    H.sns = std::move(sns);
+    H.sn_cols = std::move(sn_cols);
+    An->level_ptr_h = std::move(F.level_ptr);
+    CSX_TRY(upload(An->trees, H.trees));
+    CSX_TRY(upload(An->dense, H.dense));
+    CSX_TRY(upload(An->small_cols, H.small_cols));
+    CSX_TRY(upload(An->level_cols, H.level_cols));
+    CSX_TRY(upload(An->level_ptr, An->level_ptr_h));
+    if (An->has_levels) CSX_TRY(upload(An->col_level, H.col_level));
+    if (!H.sns.empty()) {
+        CSX_TRY(upload(An->sns, H.sns));
+        CSX_TRY(upload(An->sn_cols, H.sn_cols));
+        CSX_TRY(upload(An->sn_ptr, An->sn_group_ptr));
+    }
+    return CSX_OK;
+}
+
+// the arrays a run writes
+static int chol_analysis_alloc(CholAnalysis *An) {
+    CSX_TRY(An->win.alloc((size_t)An->lnz));
+    CSX_TRY(An->flags.alloc(3));
+    if (An->has_levels) CSX_TRY(An->split.alloc((size_t)An->n));
+    return CSX_OK;
+}
+
+// The entry map (which entry of A lands in which slot of L; flags[0] when one has no slot) and the band decision, taken here
+// once under the options in force -- the free-memory test of the blocked dense band included -- so that no later run of this
+// analysis changes route.  Queued on the stream; synchronises only to read the band width of a chain-like factor.
+static int chol_analysis_map(CholAnalysis *An, const Csc *A, const int32_t *pinv, const int32_t *Lp, const int32_t *Li) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = An->n;
+    if (pinv) CSX_TRY(upload(An->pinv, pinv, (size_t)n));
+    (void)hipMemsetAsync(An->win, 0xff, (size_t)An->lnz * sizeof(int32_t), s);
+    (void)hipMemsetAsync(An->flags, 0, sizeof(int), s);
+    hipLaunchKernelGGL(k_chol_winner, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, A->i,
+                       pinv ? An->pinv.get() : nullptr, Lp, Li, An->win.get(), An->flags.get());
+    // a chain-like big tree whose factor is a narrow band: the register-window kernel does the whole matrix
+    An->band = 0;
+    const int32_t nlev_all = (int32_t)An->level_ptr_h.size() - 1;
+    if (ctx().opt.chol_band && An->big_cols * 2 > n && (int64_t)nlev_all * 4 > An->big_cols) {
+        int hb = 0;
+        (void)hipMemsetAsync(An->flags + 2, 0, sizeof(int), s);
+        hipLaunchKernelGGL(k_band_width, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, Lp, Li, An->flags + 2);
+        CSX_HIP(hipMemcpyAsync(&hb, An->flags + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));
+        const int need = hb + 1;
+        An->band_hb = hb;
+        // wide bands (and, by option, every band): blocked factorisation in a dense band array, if that array fits
+        const int wb = ctx().opt.chol_wband;
+        // ... and only when the band is mostly FULL (bcsstk16: 89 %, a grid in natural order: 100 %): the dense band
+        // array does n x band^2 work whatever the factor holds (an arrow matrix has band n and a sparse factor)
+        const bool full_band = (double)An->lnz >= 0.5 * (double)n * ((double)hb + 1.0);
+        if ((wb == 2 || (wb == 1 && need > 80)) && full_band) {   // narrower: the register window costs about the same per column
+            size_t free_b = 0, total_b = 0, idle_b = 0, live_b = 0;
+            pool_stats(&idle_b, &live_b);
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && chol_wide_band_bytes(n, hb) < (free_b + idle_b) / 2) {
+                An->band = 2;
+                An->band_nb = ctx().opt.chol_wband_nb;
+            }
+        }
+        if (An->band == 0 && need <= 176) An->band = 1;
+    }
+    return CSX_OK;
+}
+
+// L.x of the values Ax (A's storage order) into Lx (lnz doubles: the factor's own array or a scratch array), on the kept
+// analysis.  Every piece of per-run state is set here: the pivot flag, split[] (what k_chol_coop's two phases hand over).
+// done (or null): recorded after the last launch.  Synchronises; hflags: [0] as chol_analysis_map left it, [1] the first
+// column with a non-positive pivot or 0x7fffffff.
+static int chol_analysis_run(CholAnalysis *An, const int32_t *Lp, const int32_t *Li, const double *Ax, double *Lx,
+                             hipEvent_t done, int *hflags) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = An->n;
+    const int32_t *d_rp = An->rp, *d_rc = An->rc, *d_rpos = An->rpos;
+    int *d_flags = An->flags;
+    const std::vector<int32_t> &level_ptr = An->level_ptr_h;
+    const std::vector<int32_t> &sn_group_at = An->sn_group_at;
+    int st = CSX_OK;
+    An->run_launches = 0;
+    (void)hipMemsetD32Async((hipDeviceptr_t)(d_flags + 1), 0x7fffffff, 1, s);
+    if (An->has_levels) (void)hipMemsetAsync(An->split, 0x7f, (size_t)n * sizeof(int32_t), s);   // "no inside update seen"
+    st = chol_scatter(An->lnz, An->win, Ax, Lx);
+    const bool banded = An->band != 0;
+    if (st == CSX_OK && An->band == 2) st = chol_wide_band(n, An->band_hb, Lp, Li, Lx, d_flags + 1, An->band_nb);
+#define CSX_BAND(BWV) \
+    hipLaunchKernelGGL((k_chol_band<BWV, 1024>), dim3(1), dim3(1024), 0, s, n, Lp, Li, Lx, d_rp, d_rc, d_rpos, d_flags + 1)
+    if (st == CSX_OK && An->band == 1) {
+        const int need = An->band_hb + 1;
+        if (need <= 48) CSX_BAND(48);
+        else if (need <= 80) CSX_BAND(80);
+        else if (need <= 112) CSX_BAND(112);
+        else if (need <= 144) CSX_BAND(144);
+        else CSX_BAND(176);
+    }
+#undef CSX_BAND
+    const int32_t nd = banded ? 0 : An->ndense;
+    if (st == CSX_OK && nd > 0)
+        hipLaunchKernelGGL(k_chol_dense_trees, dim3((unsigned)((nd + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0, s,
+                           An->dense.get(), nd, An->small_cols.get(), Lp, Lx, d_flags + 1);
+    const int32_t nt = banded ? 0 : An->ntrees;
+    if (st == CSX_OK && nt > 0)
+        hipLaunchKernelGGL(k_chol_trees, dim3((unsigned)((nt + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0, s,
+                           An->trees.get(), nt, An->small_cols.get(), Lp, Li, Lx, d_rp, d_rc, d_rpos, d_flags + 1);
+    const int32_t nlev = banded || st != CSX_OK ? 0 : (int32_t)level_ptr.size() - 1;
+    const int32_t *d_level_cols = An->level_cols, *d_level_ptr = An->level_ptr, *d_col_level = An->col_level;
+    const int32_t *d_sn_cols = An->sn_cols, *d_sn_ptr = An->sn_ptr;
+    int32_t *d_split = An->split;
+    int32_t l = 0;
+    const size_t cc_lds = (size_t)CC_ACC * 12 + (n <= CC_MAP ? (size_t)n * 4 : 0) + 64;
+    if (nlev > 0)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chol_coop), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  160 * 1024 - 256);
+    while (l < nlev) {
+        if (!sn_group_at.empty() && sn_group_at[(size_t)l] >= 0) {
+            // supernodes whose first column sits at this level: outside updates for all their columns at once
+            // (k_chol_coop, first phase), then the dense trapezoids in place
+            const int32_t g = sn_group_at[(size_t)l];
+            hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)(An->sn_group_ptr[(size_t)g + 1] - An->sn_group_ptr[(size_t)g])),
+                               dim3(64 * CC_WAVES), cc_lds, s, d_sn_cols, d_sn_ptr, g, g + 1, Lp, Li, Lx, d_rp, d_rc,
+                               d_rpos, n, d_flags + 1, d_col_level, 1, l, d_split);
+            An->run_launches++;
+            st = chol_supernodes(An->sns + An->sn_group_first[(size_t)g],
+                                 An->sn_group_first[(size_t)g + 1] - An->sn_group_first[(size_t)g], An->sn_group_maxw[(size_t)g],
+                                 An->sn_group_maxrows[(size_t)g], Lp, Lx, d_flags + 1);
+            if (st != CSX_OK) break;   // (returned below, after the stream has drained: nothing of this Lx is committed)
+        }
+        const int32_t cnt = level_ptr[(size_t)l + 1] - level_ptr[(size_t)l];
+        if (cnt == 0) {                          // all of this level's columns belong to supernodes
+            l++;
+            continue;
+        }
+        if (cnt > CH_NARROW) {
+            hipLaunchKernelGGL(k_chol_level, dim3((unsigned)((cnt + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0,
+                               s, d_level_cols + level_ptr[(size_t)l], cnt, Lp, Li, Lx, d_rp, d_rc, d_rpos, d_flags + 1);
+            An->run_launches++;
+            l++;
+            continue;
+        }
+        // a narrow level with more than one column: its columns go to as many workgroups in one launch; a run of
+        // single-column levels (a chain) is walked by one workgroup without coming back to the host
+        auto width = [&](int32_t lv) { return level_ptr[(size_t)lv + 1] - level_ptr[(size_t)lv]; };
+        int32_t e = l + 1;                       // the run of narrow levels, at most CC_RUN_MAX of them at a time:
+        while (e < nlev && e - l < CC_RUN_MAX && width(e) <= CH_NARROW && sn_group_at[(size_t)e] < 0) e++;   // the shorter, the less is left inside
+        const bool two_phase = e - l >= CC_RUN_MIN && level_ptr[(size_t)e] > level_ptr[(size_t)l];
+        if (two_phase) {                         // updates from below the run, for all of its columns at once
+            hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)(level_ptr[(size_t)e] - level_ptr[(size_t)l])),
+                               dim3(64 * CC_WAVES), cc_lds, s, d_level_cols, d_level_ptr, l, e, Lp, Li, Lx, d_rp, d_rc,
+                               d_rpos, n, d_flags + 1, d_col_level, 1, l, d_split);
+            An->run_launches++;
+        }
+        for (int32_t a = l; a < e;) {
+            // a level with several columns: a workgroup each in one launch; single-column levels in a row (a chain):
+            // one workgroup walks them without coming back to the host
+            if (width(a) == 0) {                 // emptied by the supernodes
+                a++;
+                continue;
+            }
+            int32_t b = a + 1;
+            if (width(a) == 1)
+                while (b < e && width(b) == 1) b++;
+            hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)width(a)), dim3(64 * CC_WAVES), cc_lds, s, d_level_cols, d_level_ptr,
+                               a, b, Lp, Li, Lx, d_rp, d_rc, d_rpos, n, d_flags + 1, d_col_level, two_phase ? 2 : 0, l,
+                               d_split);
+            An->run_launches++;
+            a = b;
+        }
+        l = e;
+    }
+    if (done) (void)hipEventRecord(done, s);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(hflags, d_flags, 2 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("cs_chol: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(s);   // the caller may hand Lx back to the pool
+        return CSX_ERUNTIME;
+    }
+    return st;
+}
+
+// ---- the analysis of a factor that exists (csx_chol_refactor_plan) ------------------------------------------------------
+int chol_analysis_of_factor(const Csc *A, const int32_t *pinv, const Csc *L, const int32_t *parent_h, const int32_t *Lp_h,
+                            CholAnalysis **out, bool *foreign) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = L->n;
+    std::unique_ptr<CholAnalysis> An(new CholAnalysis());
+    {
+        DevBuf<int32_t> col;
+        CSX_TRY(col.alloc((size_t)L->nnz));
+        CSX_TRY(expand_columns(L->p, n, L->nnz, col));
+        CSX_TRY(chol_row_view(n, L->nnz, (const uint32_t *)col.get(), L->i, &An->rp, &An->rc, &An->rpos));
+    }
+    CSX_TRY(chol_analysis_schedule(An.get(), n, L->nnz, parent_h, Lp_h));
+    CSX_TRY(chol_analysis_alloc(An.get()));
+    CSX_TRY(chol_analysis_map(An.get(), A, pinv, L->p, L->i));
+    int bad = 0;
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(&bad, An->flags.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    An->pinv.reset();   // (read by the entry map only)
+    An->host = CholAnalysis::Host();   // (the uploads have landed)
+    An->host_live = false;
+    *foreign = bad != 0;
+    *out = An.release();
+    return CSX_OK;
+}
+
+int chol_analysis_refactor(CholAnalysis *An, const Csc *L, const double *Ax, double *Lx, hipEvent_t done, bool *notspd) {
+    int hflags[2] = {0, 0x7fffffff};
+    CSX_TRY(chol_analysis_run(An, L->p, L->i, Ax, Lx, done, hflags));
+    *notspd = hflags[1] != 0x7fffffff;
+    return CSX_OK;
+}
+
+void chol_analysis_info(const CholAnalysis *An, int32_t *info) {
+    const bool banded = An->band != 0;
+    info[1] = An->run_launches;
+    info[2] = banded ? 0 : An->nsn;
+    info[3] = banded ? 0 : An->ntrees;
+    info[4] = banded ? 0 : An->ndense;
+    info[5] = An->band;
+}
+
 static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, Csc *L) {
     hipStream_t s = ctx().stream;
     g_chol_path = -1;
@@ -737,246 +1092,20 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
         }
         lap("no clique forest");
     }
-    DevBuf<int32_t> d_rp, d_rc, d_rpos, d_pinv, d_win;
-    DevBuf<int32_t> d_small_cols, d_level_cols, d_level_ptr, d_col_level, d_split, d_sn_cols, d_sn_ptr;
-    DevBuf<Tree> d_trees, d_dense;
-    DevBuf<SnDesc> d_sns;
-    DevBuf<int> d_flags;
-    CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &d_rp, &d_rc, &d_rpos, nullptr));
+    CholAnalysis An;
+    CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &An.rp, &An.rc, &An.rpos, nullptr));
     lap("pattern (device)");
-    Forest F;
-    partition_forest(n, parent, F);
-    // small trees that are dense blocks on consecutive columns take the LDS block kernel
-    std::vector<Tree> dense_trees, other_trees;
-    for (const Tree &tr : F.small) {
-        bool dense = tr.count <= CD_MAX;
-        const int32_t c0 = F.small_cols[(size_t)tr.first];
-        for (int32_t a = 0; dense && a < tr.count; a++) {
-            const int32_t c = F.small_cols[(size_t)tr.first + a];
-            dense = c == c0 + a && cp[c + 1] - cp[c] == tr.count - a;
-        }
-        (dense ? dense_trees : other_trees).push_back(tr);
-    }
-    if (!ctx().opt.chol_dense_trees) {
-        other_trees = F.small;
-        dense_trees.clear();
-    }
-    // ---- fundamental supernodes of the big trees: w >= 8 consecutive columns, each the ONLY child of the next, column
-    // counts falling by one (the separators of a nested-dissection ordering).  They leave the level lists: when the
-    // walk below reaches the level of a supernode's first column, every update from outside it is available (all of
-    // them come from below that first column), so its columns take them in one launch and the trapezoid is then
-    // factored densely in place (chol_supernodes).
-    const int64_t big_cols_all = (int64_t)F.level_cols.size();   // columns of trees too big for the tree kernels
-    std::vector<int32_t> col_level_h;                      // level of every column of a big tree, -1 elsewhere
-    std::vector<SnDesc> sns;                               // grouped by the level of their first column
-    std::vector<int32_t> sn_cols, sn_group_ptr{0}, sn_group_first{0}, sn_group_maxw, sn_group_maxrows;
-    std::vector<int32_t> sn_group_at;                      // level -> group index, -1 none
-    if (!F.level_cols.empty()) {
-        const int32_t nlev0 = (int32_t)F.level_ptr.size() - 1;
-        col_level_h.assign((size_t)n, -1);
-        for (int32_t lv = 0; lv < nlev0; lv++)
-            for (int32_t q = F.level_ptr[(size_t)lv]; q < F.level_ptr[(size_t)lv + 1]; q++) col_level_h[(size_t)F.level_cols[(size_t)q]] = lv;
-        sn_group_at.assign((size_t)nlev0 + 1, -1);
-        if (ctx().opt.chol_supernodes) {
-            std::vector<int32_t> nchild((size_t)n, 0);
-            for (int32_t j = 0; j < n; j++)
-                if (parent[j] >= 0) nchild[(size_t)parent[j]]++;
-            std::vector<std::pair<int32_t, SnDesc>> found;     // (start level, supernode)
-            std::vector<char> member((size_t)n, 0);
-            for (int32_t j = 0; j < n;) {
-                if (col_level_h[(size_t)j] < 0) {
-                    j++;
-                    continue;
-                }
-                const int32_t a = j;
-                while (j + 1 < n && parent[j] == j + 1 && nchild[(size_t)j + 1] == 1 &&
-                       cp[j + 2] - cp[j + 1] == cp[j + 1] - cp[j] - 1)
-                    j++;
-                const int32_t w = j - a + 1;
-                if (w >= SN_MIN_WIDTH) {
-                    found.push_back({col_level_h[(size_t)a], SnDesc{a, w, cp[a + 1] - cp[a] - w}});
-                    for (int32_t c = a; c <= j; c++) member[(size_t)c] = 1;
-                }
-                j++;
-            }
-            if (!found.empty()) {
-                std::stable_sort(found.begin(), found.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
-                for (size_t f = 0; f < found.size(); f++) {
-                    const int32_t lv = found[f].first;
-                    if (f == 0 || lv != found[f - 1].first) {
-                        if (f) {
-                            sn_group_ptr.push_back((int32_t)sn_cols.size());
-                            sn_group_first.push_back((int32_t)sns.size());
-                        }
-                        sn_group_at[(size_t)lv] = (int32_t)sn_group_maxw.size();
-                        sn_group_maxw.push_back(0);
-                        sn_group_maxrows.push_back(0);
-                    }
-                    const SnDesc &d = found[f].second;
-                    sns.push_back(d);
-                    for (int32_t c = d.a; c < d.a + d.w; c++) sn_cols.push_back(c);
-                    sn_group_maxw.back() = std::max(sn_group_maxw.back(), d.w);
-                    sn_group_maxrows.back() = std::max(sn_group_maxrows.back(), d.w + d.r);
-                }
-                sn_group_ptr.push_back((int32_t)sn_cols.size());
-                sn_group_first.push_back((int32_t)sns.size());
-                // the level lists without the supernodes' columns
-                std::vector<int32_t> cols2, ptr2{0};
-                for (int32_t lv = 0; lv < nlev0; lv++) {
-                    for (int32_t q = F.level_ptr[(size_t)lv]; q < F.level_ptr[(size_t)lv + 1]; q++)
-                        if (!member[(size_t)F.level_cols[(size_t)q]]) cols2.push_back(F.level_cols[(size_t)q]);
-                    ptr2.push_back((int32_t)cols2.size());
-                }
-                F.level_cols.swap(cols2);
-                F.level_ptr.swap(ptr2);
-            }
-        }
-    }
+    CSX_TRY(chol_analysis_schedule(&An, n, L->nnz, parent, cp));
     lap("partition_forest");
-    std::vector<int32_t> hpinv;
-    if (pinv) hpinv.assign(pinv, pinv + n);
     CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
-    if (pinv) CSX_TRY(upload(d_pinv, hpinv));
-    CSX_TRY(d_win.alloc((size_t)L->nnz));
-    CSX_TRY(d_flags.alloc(3));   // [0] foreign symbolic data, [1] first non-positive pivot, [2] band width
-    CSX_TRY(upload(d_trees, other_trees));
-    CSX_TRY(upload(d_dense, dense_trees));
-    CSX_TRY(upload(d_small_cols, F.small_cols));
-    CSX_TRY(upload(d_level_cols, F.level_cols));
-    CSX_TRY(upload(d_level_ptr, F.level_ptr));
-    if (!col_level_h.empty()) {
-        CSX_TRY(d_split.alloc((size_t)n));
-        (void)hipMemsetAsync(d_split, 0x7f, (size_t)n * sizeof(int32_t), s);   // "no inside update seen"
-        CSX_TRY(upload(d_col_level, col_level_h));
-    }
-    if (!sns.empty()) {
-        CSX_TRY(upload(d_sns, sns));
-        CSX_TRY(upload(d_sn_cols, sn_cols));
-        CSX_TRY(upload(d_sn_ptr, sn_group_ptr));
-    }
+    CSX_TRY(chol_analysis_alloc(&An));
+    (void)hipEventRecord(ev_a, s);
     int hflags[2] = {0, 0x7fffffff};
-    int st = CSX_OK;
-    {
-        (void)hipEventRecord(ev_a, s);
-        (void)hipMemsetAsync(d_win, 0xff, (size_t)L->nnz * sizeof(int32_t), s);
-        (void)hipMemcpyAsync(d_flags, hflags, sizeof hflags, hipMemcpyHostToDevice, s);
-        hipLaunchKernelGGL(k_chol_winner, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, A->i, d_pinv,
-                           L->p, L->i, d_win, d_flags);
-        hipLaunchKernelGGL(k_chol_init, dim3((unsigned)(((int64_t)L->nnz + 255) / 256)), dim3(256), 0, s,
-                           (int64_t)L->nnz, d_win, A->x, L->x);
-        // a chain-like big tree whose factor is a narrow band: the register-window kernel does the whole matrix
-        bool banded = false;
-        const int32_t nlev_all = (int32_t)F.level_ptr.size() - 1;
-        const int64_t big_cols = big_cols_all;
-        if (ctx().opt.chol_band && big_cols * 2 > n && (int64_t)nlev_all * 4 > big_cols) {
-            int hb = 0;
-            (void)hipMemsetAsync(d_flags + 2, 0, sizeof(int), s);
-            hipLaunchKernelGGL(k_band_width, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, L->p, L->i,
-                               d_flags + 2);
-            (void)hipMemcpyAsync(&hb, d_flags + 2, sizeof(int), hipMemcpyDeviceToHost, s);
-            (void)hipStreamSynchronize(s);
-            const int need = hb + 1;
-            // wide bands (and, by option, every band): blocked factorisation in a dense band array, if that array fits
-            const int wb = ctx().opt.chol_wband;
-            // ... and only when the band is mostly FULL (bcsstk16: 89 %, a grid in natural order: 100 %): the dense band
-            // array does n x band^2 work whatever the factor holds (an arrow matrix has band n and a sparse factor)
-            const bool full_band = (double)L->nnz >= 0.5 * (double)n * ((double)hb + 1.0);
-            if ((wb == 2 || (wb == 1 && need > 80)) && full_band) {   // narrower: the register window costs about the same per column
-                size_t free_b = 0, total_b = 0, idle_b = 0, live_b = 0;
-                pool_stats(&idle_b, &live_b);
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess &&
-                    chol_wide_band_bytes(n, hb) < (free_b + idle_b) / 2) {
-                    st = chol_wide_band(n, hb, L->p, L->i, L->x, d_flags + 1, ctx().opt.chol_wband_nb);
-                    banded = true;
-                }
-            }
-#define CSX_BAND(BWV)                                                                                                \
-    hipLaunchKernelGGL((k_chol_band<BWV, 1024>), dim3(1), dim3(1024), 0, s, n, L->p, L->i, L->x, d_rp, d_rc, d_rpos, \
-                       d_flags + 1)
-            if (banded) {}
-            else if (need <= 48) { CSX_BAND(48); banded = true; }
-            else if (need <= 80) { CSX_BAND(80); banded = true; }
-            else if (need <= 112) { CSX_BAND(112); banded = true; }
-            else if (need <= 144) { CSX_BAND(144); banded = true; }
-            else if (need <= 176) { CSX_BAND(176); banded = true; }
-#undef CSX_BAND
-        }
-        const int32_t nd = banded ? 0 : (int32_t)dense_trees.size();
-        if (nd > 0)
-            hipLaunchKernelGGL(k_chol_dense_trees, dim3((unsigned)((nd + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0,
-                               s, d_dense, nd, d_small_cols, L->p, L->x, d_flags + 1);
-        const int32_t nt = banded ? 0 : (int32_t)other_trees.size();
-        if (nt > 0)
-            hipLaunchKernelGGL(k_chol_trees, dim3((unsigned)((nt + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0, s,
-                               d_trees, nt, d_small_cols, L->p, L->i, L->x, d_rp, d_rc, d_rpos, d_flags + 1);
-        const int32_t nlev = banded ? 0 : (int32_t)F.level_ptr.size() - 1;
-        int32_t l = 0;
-        const size_t cc_lds = (size_t)CC_ACC * 12 + (n <= CC_MAP ? (size_t)n * 4 : 0) + 64;
-        if (nlev > 0)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_chol_coop), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      160 * 1024 - 256);
-        while (l < nlev) {
-            if (!banded && !sn_group_at.empty() && sn_group_at[(size_t)l] >= 0) {
-                // supernodes whose first column sits at this level: outside updates for all their columns at once
-                // (k_chol_coop, first phase), then the dense trapezoids in place
-                const int32_t g = sn_group_at[(size_t)l];
-                sn_group_at[(size_t)l] = -1;
-                hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)(sn_group_ptr[(size_t)g + 1] - sn_group_ptr[(size_t)g])),
-                                   dim3(64 * CC_WAVES), cc_lds, s, d_sn_cols, d_sn_ptr, g, g + 1, L->p, L->i, L->x, d_rp, d_rc,
-                                   d_rpos, n, d_flags + 1, d_col_level, 1, l, d_split);
-                if (chol_supernodes(d_sns + sn_group_first[(size_t)g], sn_group_first[(size_t)g + 1] - sn_group_first[(size_t)g],
-                                    sn_group_maxw[(size_t)g], sn_group_maxrows[(size_t)g], L->p, L->x, d_flags + 1) != CSX_OK)
-                    break;
-            }
-            const int32_t cnt = F.level_ptr[(size_t)l + 1] - F.level_ptr[(size_t)l];
-            if (cnt == 0) {                          // all of this level's columns belong to supernodes
-                l++;
-                continue;
-            }
-            if (cnt > CH_NARROW) {
-                hipLaunchKernelGGL(k_chol_level, dim3((unsigned)((cnt + CH_WAVES - 1) / CH_WAVES)), dim3(64 * CH_WAVES), 0,
-                                   s, d_level_cols + F.level_ptr[(size_t)l], cnt, L->p, L->i, L->x, d_rp, d_rc, d_rpos,
-                                   d_flags + 1);
-                l++;
-                continue;
-            }
-            // a narrow level with more than one column: its columns go to as many workgroups in one launch; a run of
-            // single-column levels (a chain) is walked by one workgroup without coming back to the host
-            auto width = [&](int32_t lv) { return F.level_ptr[(size_t)lv + 1] - F.level_ptr[(size_t)lv]; };
-            int32_t e = l + 1;                       // the run of narrow levels, at most CC_RUN_MAX of them at a time:
-            while (e < nlev && e - l < CC_RUN_MAX && width(e) <= CH_NARROW && sn_group_at[(size_t)e] < 0) e++;   // the shorter, the less is left inside
-            const bool two_phase = e - l >= CC_RUN_MIN && F.level_ptr[(size_t)e] > F.level_ptr[(size_t)l];
-            if (two_phase)                           // updates from below the run, for all of its columns at once
-                hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)(F.level_ptr[(size_t)e] - F.level_ptr[(size_t)l])),
-                                   dim3(64 * CC_WAVES), cc_lds, s, d_level_cols, d_level_ptr, l, e, L->p, L->i, L->x, d_rp, d_rc,
-                                   d_rpos, n, d_flags + 1, d_col_level, 1, l, d_split);
-            for (int32_t a = l; a < e;) {
-                // a level with several columns: a workgroup each in one launch; single-column levels in a row (a chain):
-                // one workgroup walks them without coming back to the host
-                if (width(a) == 0) {                 // emptied by the supernodes
-                    a++;
-                    continue;
-                }
-                int32_t b = a + 1;
-                if (width(a) == 1)
-                    while (b < e && width(b) == 1) b++;
-                hipLaunchKernelGGL(k_chol_coop, dim3((unsigned)width(a)), dim3(64 * CC_WAVES), cc_lds, s, d_level_cols, d_level_ptr,
-                                   a, b, L->p, L->i, L->x, d_rp, d_rc, d_rpos, n, d_flags + 1, d_col_level, two_phase ? 2 : 0, l,
-                                   d_split);
-                a = b;
-            }
-            l = e;
-        }
-        (void)hipEventRecord(ev_b, s);
-        if (hipGetLastError() != hipSuccess ||
-            hipMemcpyAsync(hflags, d_flags, sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            set_error("cs_chol: %s", hipGetErrorString(hipGetLastError()));
-            st = CSX_ERUNTIME;
-        } else {
-            numeric_ms();
-            g_chol_path = 0;
-        }
+    int st = chol_analysis_map(&An, A, pinv, L->p, L->i);
+    if (st == CSX_OK) st = chol_analysis_run(&An, L->p, L->i, A->x, L->x, ev_b, hflags);
+    if (st == CSX_OK) {
+        numeric_ms();
+        g_chol_path = 0;
     }
     lap("numeric (device)");
     if (st != CSX_OK) return st;

@@ -488,7 +488,7 @@ static int wide_band_run_fused(int32_t n, int32_t bw, double *W, double *dfac, i
     return CSX_OK;
 }
 
-// L.x holds A scattered into the pattern of L (k_chol_init); on return it holds the factor.  *notspd (device)
+// L.x holds A scattered into the pattern of L (chol_scatter); on return it holds the factor.  *notspd (device)
 // receives the first column with a non-positive pivot (atomicMin), as in the other kernels.  nb: 16 or 32.
 int chol_wide_band(int32_t n, int32_t bw, const int32_t *Lp, const int32_t *Li, double *Lx, int *notspd, int nb) {
     hipStream_t s = ctx().stream;

@@ -63,7 +63,7 @@ static bool postorder_intervals(int32_t n, const int32_t *parent, std::vector<in
 }
 
 // ---- 1. starts ---------------------------------------------------------------------------------------
-// one wave per column c of A: entries with pinv[i] < pinv[c]
+// one wave per column c of A: its entries above the diagonal, as (row, start) = (max, min) of the permuted pair
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_sym_starts(int32_t n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Ai,
                                                     const int32_t *__restrict__ pinv, const int32_t *__restrict__ post,
@@ -83,16 +83,20 @@ __global__ __launch_bounds__(256) void k_sym_starts(int32_t n, const int32_t *__
             i = Ai[p];
             if (i < 0 || i >= n) {
                 *bad = 1;
+            } else if (pinv) {
+                // the upper triangle of A is what counts (csparse.py:2220-2255): entry (i, c), i < c, is entry (min, max) of P A P';
+                // lower entries are ignored, as cs_chol ignores them, so a matrix stored as its upper triangle alone is whole
+                up = i < c;
+                if (up) i = pinv[i];
             } else {
-                if (pinv) i = pinv[i];
                 up = i < k;
             }
         }
         const unsigned long long bal = __ballot(up);
         if (FILL && up) {
             const int32_t q = run + __popcll(bal & ((1ull << lane) - 1ull));
-            skey[q] = (uint32_t)post[i];
-            srow[q] = (uint32_t)k;
+            skey[q] = (uint32_t)post[min(i, k)];
+            srow[q] = (uint32_t)max(i, k);
         }
         run += __popcll(bal);
     }
@@ -165,6 +169,27 @@ __global__ __launch_bounds__(256) void k_sym_unpack(int64_t lnz, const double *_
 
 static inline unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
+// The row view of a factor's pattern: col[q] = column of entry q of L (column-major), Li its rows.  A stable sort of the entries
+// by row: for row j the columns k ascending, the diagonal last, and the position of L(j,k) in L.i / L.x.  Queued on the
+// context's stream; the temporaries go back to the pool in stream order.
+int chol_row_view(int32_t n, int64_t lnz, const uint32_t *col, const int32_t *Li, DevBuf<int32_t> *row_ptr, DevBuf<int32_t> *row_col,
+                  DevBuf<int32_t> *row_pos) {
+    hipStream_t s = ctx().stream;
+    DevBuf<double> packed, packed_s;
+    DevBuf<uint32_t> sk2;
+    CSX_TRY(packed.alloc((size_t)lnz));
+    CSX_TRY(packed_s.alloc((size_t)lnz));
+    CSX_TRY(sk2.alloc((size_t)lnz));
+    CSX_TRY(row_ptr->alloc((size_t)n + 1));
+    CSX_TRY(row_col->alloc((size_t)lnz));
+    CSX_TRY(row_pos->alloc((size_t)lnz));
+    hipLaunchKernelGGL(k_sym_pack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, col, packed.get());
+    CSX_TRY(stable_sort_by_key((const uint32_t *)Li, nullptr, packed, lnz, (uint32_t)n, sk2, nullptr, packed_s));
+    CSX_TRY(boundaries_from_sorted(sk2, lnz, n, row_ptr->get()));
+    hipLaunchKernelGGL(k_sym_unpack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, packed_s.get(), row_col->get(), row_pos->get());
+    return CSX_OK;
+}
+
 // On success the five outputs are device arrays, Lp and Li raw for the caller's Csc to own:
 //   Lp (n+1), Li (lnz), row_ptr (n+1), row_col (lnz), row_pos (lnz); the row view includes the diagonal
 //   as the LAST entry of each row.
@@ -196,9 +221,8 @@ int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp,
     DevBuf<int32_t> d_parent, d_first, d_post, d_postinv, d_pinv, d_cp;
     DevBuf<int32_t> cnt, sptr0, sptr, items;
     DevBuf<uint32_t> skey, srow, k1, r1, rows, posts;
-    DevBuf<uint32_t> ev, ek, sv, sk2;
+    DevBuf<uint32_t> ev, ek, sv;
     DevBuf<int32_t> Lp, Li, row_ptr, row_col, row_pos;
-    DevBuf<double> packed, packed_s;
     DevBuf<int> bad;
     int hbad = 0;
     int64_t ns = 0, total = 0;
@@ -269,16 +293,7 @@ int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp,
     CSX_TRY(boundaries_from_sorted(sv, lnz, n, Lp));
     hipLaunchKernelGGL(k_sym_compare, dim3(blocks_for((int64_t)n + 1)), dim3(256), 0, s, (int64_t)n + 1, Lp, d_cp, bad);
     // ---- 4. row view ----
-    CSX_TRY(packed.alloc((size_t)lnz));
-    CSX_TRY(packed_s.alloc((size_t)lnz));
-    CSX_TRY(sk2.alloc((size_t)lnz));
-    CSX_TRY(row_ptr.alloc((size_t)n + 1));
-    CSX_TRY(row_col.alloc((size_t)lnz));
-    CSX_TRY(row_pos.alloc((size_t)lnz));
-    hipLaunchKernelGGL(k_sym_pack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, sv, packed);
-    CSX_TRY(stable_sort_by_key((const uint32_t *)Li.get(), nullptr, packed, lnz, (uint32_t)n, sk2, nullptr, packed_s));
-    CSX_TRY(boundaries_from_sorted(sk2, lnz, n, row_ptr));
-    hipLaunchKernelGGL(k_sym_unpack, dim3(blocks_for(lnz)), dim3(256), 0, s, lnz, packed_s, row_col, row_pos);
+    CSX_TRY(chol_row_view(n, lnz, sv, Li, &row_ptr, &row_col, &row_pos));
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&hbad, bad, sizeof hbad, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         set_error("cs_chol (pattern): %s", hipGetErrorString(hipGetLastError()));

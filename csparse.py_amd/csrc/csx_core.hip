@@ -246,6 +246,7 @@ static void free_object(Object &o) {
         case K_BTFPLAN: destroy((BtfPlan *)o.ptr); break;
         case K_LUREFPLAN: destroy((LuRefPlan *)o.ptr); break;
         case K_ASMPLAN: destroy((AsmPlan *)o.ptr); break;
+        case K_CHOLREFPLAN: destroy((CholRefPlan *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it

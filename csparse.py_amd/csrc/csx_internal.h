@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN };
 
 struct Csc;
 
@@ -211,6 +211,10 @@ void destroy(Refactor *p);
 void destroy(LuRefPlan *p);
 struct AsmPlan;    // csx_assemble_plan.hip
 void destroy(AsmPlan *p);
+struct CholAnalysis;  // csx_chol.hip
+struct CholRefPlan;   // csx_chol_refactor.hip
+void destroy(CholAnalysis *p);
+void destroy(CholRefPlan *p);
 
 struct Object {
     Kind kind = K_FREE;
@@ -374,6 +378,22 @@ int rf_keep_pattern(const Csc *A, DevBuf<int32_t> &p, DevBuf<int32_t> &i);
 // the values of A2 (a matrix with the pattern p0 / i0, or a vector of nnz values), CSX_EINVAL for anything else
 int rf_values(csx_handle_t A2, int32_t m, int32_t n, int32_t nnz, const int32_t *p0, const int32_t *i0, int *flag,
               const double **x);
+
+// ---- Cholesky refactor (csx_chol.hip, csx_chol_refactor.hip) ----
+// The general path's analysis of a factor that exists: tree and counts read off L (host copies Lp_h, and parent_h made by the
+// caller), row view from L's pattern, entry map from A's pattern (A: p / i only) through pinv (host, or null).  *foreign: an
+// upper entry of A has no slot in L.  Synchronises.
+int chol_analysis_of_factor(const Csc *A, const int32_t *pinv, const Csc *L, const int32_t *parent_h, const int32_t *Lp_h,
+                            CholAnalysis **out, bool *foreign);
+// Lx (lnz doubles, not necessarily L's own) <- the factor of the values Ax on the kept analysis; *notspd: some pivot <= 0.
+// done (or null) is recorded after the last launch.  Synchronises.
+int chol_analysis_refactor(CholAnalysis *An, const Csc *L, const double *Ax, double *Lx, hipEvent_t done, bool *notspd);
+void chol_analysis_info(const CholAnalysis *An, int32_t *info);   // info[1..5] of csx_chol_refactor
+// Lx[q] = win[q] >= 0 ? Ax[win[q]] : 0 over the lnz slots of L (csx_chol_refactor.hip)
+int chol_scatter(int64_t lnz, const int32_t *win, const double *Ax, double *Lx);
+// csx_cholsym.hip: the row view of a factor's pattern (col[q] = the column of entry q)
+int chol_row_view(int32_t n, int64_t lnz, const uint32_t *col, const int32_t *Li, DevBuf<int32_t> *row_ptr, DevBuf<int32_t> *row_col,
+                  DevBuf<int32_t> *row_pos);
 
 // Workgroup barrier that orders LDS only.  __syncthreads() carries a fence over global memory as well: it waits for
 // every global load the wave has in flight (s_waitcnt vmcnt(0)), which puts the latency of software-pipelined loads

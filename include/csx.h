@@ -630,6 +630,39 @@ int csx_lu_refactor_plan(csx_handle_t L, csx_handle_t U, csx_handle_t A, const i
                          csx_handle_t *plan);
 int csx_lu_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, double *ratio, int64_t *cols);
 
+/* ---- Cholesky refactor: new values on the kept analysis (cholsol_factor .refactor) ---------------
+ * Definition.  Given the factor L of cs_chol (L L' = P A P', diagonal first, rows ascending) of a matrix A and new values A2 on
+ * A's pattern, L.x is replaced by the values cs_chol gives for A2 with the same S: the same kernels in the same order as a
+ * fresh csx_chol / csx_cholsol_factor under the options in force, so L.x is byte-equal to that fresh factor's -- with one
+ * exception: under "chol.exact" = 0 (opt-in) a csx_cholsol_factor made with exact = 0 lets its block kernel emit the
+ * matrix-core solve's operands, which for cliques of unequal sizes is another kernel (the blocked factorisation per size
+ * class) than the refactor's; L.x then agrees with the fresh factor's to rounding, which is all that option promises of L.x.
+ * L.p and L.i are never written, and L.x keeps its address (solve plans borrow it).
+ * csx_chol_refactor_plan: a NEW plan handle (csx_free) for A (the matrix L was factored from: only its pattern is read, its
+ *   upper triangle counts, lower entries are ignored as cs_chol ignores them), L (device; BORROWED like a cholsol plan borrows
+ *   it: free the plan before L) and pinv (host, n, or NULL: natural order).  The elimination tree and the column counts are
+ *   read off L (parent[j] = the row of the second entry of column j, cp = L.p): no S is passed.  The plan keeps a copy of A's
+ *   pattern and, on the general route, what csx_chol builds and lets go: the row view of L, the entry map (for every slot of L
+ *   the entry of A that lands there, of duplicates the last, -1 for fill), the forest partition, the level lists, the supernode
+ *   groups and the band decision (taken here once, the free-memory test of the blocked dense band included: a refactor does not
+ *   change route); about 16 bytes of int32 arrays per entry of L.  On the forest route (pinv NULL and A's elimination forest
+ *   is cliques or small sparse trees on consecutive columns: paths 1 / 2 / 3 of csx_cholsol_factor_info) it keeps that forest
+ *   instead; the block kernel runs without an emission, in the arithmetic "chol.exact" asks for at the call.  CSX_EINVAL with a message in csx_last_error() when an upper entry of A has no slot in L or L is not
+ *   Cholesky-shaped.
+ * csx_chol_refactor: A2 a matrix with A's pattern or a vector of nnz(A) values in A's storage order.  *ok = -1 (CSX_OK): another
+ *   pattern or length, nothing changed.  *ok = 0: A2 is not positive definite; L.x and everything the solves read are byte
+ *   for byte as before.  *ok = 1: L.x holds the factor of A2.  The new factor is computed in a scratch array of nnz(L) doubles
+ *   (made by the first call, kept) and copied over L.x only when no pivot failed; an error status before that copy leaves
+ *   everything as it was.  Plans made from L (csx_cholsol_plan, the triangular solves') hold stale values afterwards: the
+ *   caller makes them again, as after csx_updown.  info (8 values, or NULL): [0] route: 0 general, 1 forest; [1] launches of
+ *   the level walk; [2] supernodes; [3] small trees given to the tree kernel; [4] dense trees; [5] band kernel: 0 none,
+ *   1 register window, 2 blocked dense band; [6] 1 when this call made the plan's scratch arrays; [7] 0.
+ * csx_chol_refactor_info: the last csx_chol_refactor that ran: HIP-event time from the scatter of the values to the last
+ *   launch, and the host clock over the whole call, pattern check and commit included.  CSX_EINVAL before the first. */
+int csx_chol_refactor_plan(csx_handle_t A, csx_handle_t L, const int32_t *pinv, csx_handle_t *plan);
+int csx_chol_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, int32_t *info);
+int csx_chol_refactor_info(double *numeric_ms, double *call_ms);
+
 /* ---- assembly plan: new triplet values into a fixed CSC pattern (assembly_plan) --------------------
  * Definition.  Given the triplets (Ti[k], Tj[k]), k = 0 .. nz-1, of an m-by-n matrix, let C = cs_dupl(cs_compress(T)) as the
  * reference computes it.
