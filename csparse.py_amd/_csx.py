@@ -158,6 +158,14 @@ _PROTOS = {
     "csx_assemble_matrix": [H, H, C.POINTER(H)],
     "csx_assemble": [H, H, H],
     "csx_assemble_plan_info": [H, C.POINTER(C.c_int64)],
+    "csx_multiply_plan_count": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int64)],
+    "csx_multiply_plan_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
+    "csx_multiply_fold_host": [C.c_int32, _i32p, _i32p, _f64p, _f64p, _f64p],
+    "csx_multiply_plan": [H, H, C.POINTER(H)],
+    "csx_multiply_plan_matrix": [H, H, H, H, C.POINTER(H)],
+    "csx_multiply_plan_run": [H, H, H, H, H],
+    "csx_multiply_plan_info": [H, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

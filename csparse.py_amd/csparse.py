@@ -25,6 +25,7 @@ What runs where
   * Host-side glue that the reference also does in Python (triplet assembly,
     cs_cumsum, cs_scatter on lists, permutation of a single list) stays Python.
 """
+import contextlib
 import math
 import os
 import time
@@ -764,6 +765,119 @@ def assembly_plan(T):
     if not CS_TRIPLET(T):
         return None
     return _AssemblyPlan(T)
+
+
+class _MultiplyPlan(object):
+    """What multiply_plan returns: see there."""
+
+    _INFO = ("m", "n", "nnz", "products", "max_products", "long_slots", "build_us", "kernel_us")
+
+    def __init__(self, A, B):
+        self._A, self._B = A, B            # kept alive: None for ax / bx means their current values
+        self._anz, self._bnz = _meta(A)[0], _meta(B)[0]
+        h = _csx.new_handle()
+        with _Resident(A) as dA, _Resident(B) as dB:
+            st = _csx.lib().csx_multiply_plan(dA.handle, dB.handle, h)
+        if st == _csx.EINVAL:
+            raise ValueError(_last_error())
+        _csx.check(st, "csx_multiply_plan")
+        self._handle = h
+        self._fin = weakref.finalize(self, _csx.free, h)
+        self.k = A.n
+        info = self.info()
+        self.m, self.n, self.nnz, self.products = info["m"], info["n"], info["nnz"], info["products"]
+        self._matrix = None
+
+    def info(self):
+        """m, n, nnz, products, max_products (the most products of one slot), long_slots (slots folded by a wave of their own),
+        build_us (the host build of the plan) and kernel_us (the last step between two events: both launches when scaled)"""
+        out = (_csx.C.c_int64 * 8)()
+        _csx.check(_csx.lib().csx_multiply_plan_info(self._handle, out), "csx_multiply_plan_info")
+        return dict(zip(self._INFO, (int(v) for v in out)))
+
+    @staticmethod
+    def _vector(values, count, what):
+        """list / numpy / dvec of exactly count numbers -> a dvec (the caller's own when it is one: it is only read)"""
+        v = values if isinstance(values, dvec) else dvec(np.asarray(values, dtype=np.float64).ravel())
+        if v.n * v.k != count:
+            raise ValueError("multiply plan: %d numbers given for %s, %d expected" % (v.n * v.k, what, count))
+        return v
+
+    def _step(self, ax, bx, scale, call):
+        """call(handle of Ax, handle of Bx, handle of d or 0) with the operands resident for its duration"""
+        for M, given, nz, what in ((self._A, ax, self._anz, "A"), (self._B, bx, self._bnz, "B")):
+            if given is None and _meta(M) != (nz, True):
+                raise ValueError("multiply plan: %s has no values (or another entry count) and none are given" % what)
+        va = None if ax is None else self._vector(ax, self._anz, "ax")
+        vb = None if bx is None else self._vector(bx, self._bnz, "bx")
+        d = None if scale is None else self._vector(scale, self.k, "scale")
+        with contextlib.ExitStack() as held:   # an operand whose values are given is not made resident for them
+            ha = va.handle if va is not None else held.enter_context(_Resident(self._A)).handle
+            hb = vb.handle if vb is not None else held.enter_context(_Resident(self._B)).handle
+            return call(ha, hb, d.handle if d is not None else 0)
+
+    def _new_matrix(self, ax, bx, scale):
+        """a new matrix handle with the plan's pattern and the values of a step"""
+        h = _csx.new_handle()
+        _csx.check(self._step(ax, bx, scale, lambda a, b, d: _csx.lib().csx_multiply_plan_matrix(self._handle, a, b, d, h)),
+                   "csx_multiply_plan_matrix")
+        return h
+
+    @property
+    def matrix(self):
+        if self._matrix is None:
+            if _meta(self._A)[1] and _meta(self._B)[1]:
+                h = self._new_matrix(None, None, None)
+            else:                                          # as cs_multiply of a pattern-only operand: pattern only
+                h = _csx.new_handle()
+                _csx.check(_csx.lib().csx_multiply_plan_matrix(self._handle, 0, 0, 0, h), "csx_multiply_plan_matrix")
+            self._matrix = cs_pin(_from_device(h, lambda nnz: nnz))   # cs_multiply trims: nzmax = nnz
+        return self._matrix
+
+    def multiply(self, ax=None, bx=None, scale=None):
+        out = dvec(self.nnz)
+        _csx.check(self._step(ax, bx, scale, lambda a, b, d: _csx.lib().csx_multiply_plan_run(self._handle, a, b, d, out.handle)),
+                   "csx_multiply_plan_run")
+        return out
+
+    def update(self, ax=None, bx=None, scale=None):
+        M = self.matrix
+        if M._dev is None:      # unpinned or invalidated by the caller since: resident again, from its lists
+            cs_pin(M)
+        dev = M._dev
+        if not dev.info()[3]:   # pattern only so far: the first values allocate them
+            M._dev = _DevMatrix(self._new_matrix(ax, bx, scale))
+            if not M._lazy:
+                M._x = [0.0] * self.nnz   # (filled by _refactored below)
+            dev = M._dev
+        else:
+            _csx.check(self._step(ax, bx, scale,
+                                  lambda a, b, d: _csx.lib().csx_multiply_plan_run(self._handle, a, b, d, dev.handle)),
+                       "csx_multiply_plan_run")
+        _refactored(M, dev)
+        return M
+
+
+def multiply_plan(A, B):
+    """The plan of cs_multiply(A, B) for operands whose patterns stay and whose values change every step (include/csx.h
+    "multiply plan").  Only the patterns are read for the plan; None where cs_multiply returns None (an operand
+    that is not CSC, A.n != B.m); ValueError when the products do not fit int32.  The plan keeps A and B alive, has m, n, k,
+    nnz, products and info(), and
+      .matrix                       cs_multiply(A, B) as a device-resident pinned `cs` (nzmax = nnz) with the reference's bits from
+                                    A's and B's values at first use, or pattern only when either has none; made once.
+      .multiply(ax, bx, scale)      ax / bx: list, numpy array or dvec of exactly nnz(A) / nnz(B) numbers in storage order, None
+                                    = the operand's current values; scale: None or exactly k numbers d, C = A diag(d) B.  A NEW
+                                    dvec of nnz values in .matrix's storage order -- the reference's bits -- which is what
+                                    cholsol_factor(P.matrix).refactor(...) takes.  ValueError on a wrong length, or when an
+                                    operand has no values and none are given.  Inputs are never modified or aliased.
+      .update(ax, bx, scale)        the same values straight into .matrix, in place: the plans cached on it go, solvers built on
+                                    it re-plan, host lists already read from it are refreshed in place.  Returns .matrix.
+    A `cs` operand is trusted to still have the pattern the plan was made from: only its shape and entry count are checked."""
+    if not CS_CSC(A) or not CS_CSC(B):
+        return None
+    if A.n != B.m:
+        return None
+    return _MultiplyPlan(A, B)
 
 
 def cs_fkeep(A, fkeep, other):

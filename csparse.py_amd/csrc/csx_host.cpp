@@ -975,3 +975,128 @@ int32_t assemble_slot_stats(int32_t nnz, const int32_t *sp, int32_t thr, std::ve
     return longest;
 }
 }  // namespace csx
+
+// ---- multiply plan (include/csx.h has the definition) -------------------------------------------------
+// cs_multiply's two nested loops on the indices alone.  Column j of C: down B(:,j) in storage order, down A(:, B.i[ib]) in
+// storage order; a row met for the first time in this column (where[r] < the column's first slot) opens the next slot, any
+// other product lands in the slot of its row.  What the loops did to the values is kept as lists: slot s is the fold of the
+// products pair[2t], pair[2t + 1] = (ia, ib), t in sp[s] .. sp[s + 1], in the order the loops met them.
+namespace {
+// pointers from 0 and non-decreasing, every index inside [0, rows)
+bool pattern_ok(int32_t rows, int32_t cols, const int32_t *p, const int32_t *i) {
+    if (!p || p[0] != 0) return false;
+    for (int32_t j = 0; j < cols; j++)
+        if (p[j + 1] < p[j]) return false;
+    if (p[cols] > 0 && !i) return false;
+    for (int32_t t = 0; t < p[cols]; t++)
+        if (i[t] < 0 || i[t] >= rows) return false;
+    return true;
+}
+
+// The walk itself.  Cp / Ci / sp / pair may all be null (csx_multiply_plan_count).  A column's slots are consecutive and so
+// are their products, so each column is counted, then placed, with no array of the products' size beside pair.
+int multiply_plan_walk(int32_t m, int32_t n, const int32_t *Ap, const int32_t *Ai, const int32_t *Bp, const int32_t *Bi,
+                       int32_t *Cp, int32_t *Ci, int32_t *sp, int32_t *pair, int64_t *nnz_out, int64_t *products_out) {
+    std::vector<int64_t> where((size_t)m, -1);
+    std::vector<int32_t> rows;   // of the column in hand: its slots' rows ...
+    std::vector<int64_t> fill;   // ... and their product counts, then the next free place of each slot
+    int64_t nnz = 0, products = 0;
+    for (int32_t j = 0; j < n; j++) {
+        const int64_t start = nnz;
+        rows.clear();
+        fill.clear();
+        for (int32_t ib = Bp[j]; ib < Bp[j + 1]; ib++) {
+            const int32_t c = Bi[ib];
+            for (int32_t ia = Ap[c]; ia < Ap[c + 1]; ia++) {
+                const int32_t r = Ai[ia];
+                if (where[r] < start) {
+                    where[r] = nnz++;
+                    rows.push_back(r);
+                    fill.push_back(1);
+                } else {
+                    fill[(size_t)(where[r] - start)]++;
+                }
+            }
+        }
+        if (Cp) {
+            if (nnz > INT32_MAX || (!rows.empty() && (!Ci || !pair))) return CSX_EINVAL;   // (Ci, pair may be null while empty)
+            Cp[j] = (int32_t)start;
+            for (size_t q = 0; q < rows.size(); q++) {
+                const int64_t len = fill[q];
+                Ci[start + (int64_t)q] = rows[q];
+                if (products + len > INT32_MAX) {
+                    csx::set_error("multiply plan: more than 2^31 - 1 products do not fit its int32 pointers");
+                    return CSX_EINVAL;
+                }
+                sp[start + (int64_t)q] = (int32_t)products;
+                fill[q] = products;
+                products += len;
+            }
+            for (int32_t ib = Bp[j]; ib < Bp[j + 1]; ib++) {
+                const int32_t c = Bi[ib];
+                for (int32_t ia = Ap[c]; ia < Ap[c + 1]; ia++) {
+                    const int64_t t = fill[(size_t)(where[Ai[ia]] - start)]++;
+                    pair[2 * t] = ia;
+                    pair[2 * t + 1] = ib;
+                }
+            }
+        } else {
+            for (int64_t len : fill) products += len;
+        }
+    }
+    if (Cp) {
+        Cp[n] = (int32_t)nnz;
+        sp[nnz] = (int32_t)products;
+    }
+    *nnz_out = nnz;
+    *products_out = products;
+    return CSX_OK;
+}
+}  // namespace
+
+extern "C" int csx_multiply_plan_count(int32_t m, int32_t k, int32_t n, const int32_t *Ap, const int32_t *Ai, const int32_t *Bp,
+                                       const int32_t *Bi, int64_t *nnz, int64_t *products) {
+    if (m < 0 || k < 0 || n < 0 || !nnz || !products) return CSX_EINVAL;
+    if (!pattern_ok(m, k, Ap, Ai) || !pattern_ok(k, n, Bp, Bi)) return CSX_EINVAL;   // the reference would raise IndexError
+    return multiply_plan_walk(m, n, Ap, Ai, Bp, Bi, nullptr, nullptr, nullptr, nullptr, nnz, products);
+}
+
+extern "C" int csx_multiply_plan_host(int32_t m, int32_t k, int32_t n, const int32_t *Ap, const int32_t *Ai, const int32_t *Bp,
+                                      const int32_t *Bi, int32_t *Cp, int32_t *Ci, int32_t *sp, int32_t *pair) {
+    if (m < 0 || k < 0 || n < 0 || !Cp || !sp) return CSX_EINVAL;
+    if (!pattern_ok(m, k, Ap, Ai) || !pattern_ok(k, n, Bp, Bi)) return CSX_EINVAL;
+    int64_t nnz = 0, products = 0;
+    return multiply_plan_walk(m, n, Ap, Ai, Bp, Bi, Cp, Ci, sp, pair, &nnz, &products);
+}
+
+// Cx[s] = ((b0 a0) + b1 a1) + ... over the slot's products: every product rounded on its own, the first assigned, one
+// addition per further product -- never a fused multiply-add
+extern "C" int csx_multiply_fold_host(int32_t nnz, const int32_t *sp, const int32_t *pair, const double *Ax, const double *Bx,
+                                      double *Cx) {
+#pragma clang fp contract(off)
+    if (nnz < 0 || !sp || (nnz > 0 && (!pair || !Ax || !Bx || !Cx))) return CSX_EINVAL;
+    for (int32_t s = 0; s < nnz; s++) {
+        if (sp[s + 1] <= sp[s]) return CSX_EINVAL;
+        int64_t t = sp[s];
+        double acc = Bx[pair[2 * t + 1]] * Ax[pair[2 * t]];
+        for (t++; t < sp[s + 1]; t++) {
+            const double term = Bx[pair[2 * t + 1]] * Ax[pair[2 * t]];
+            acc = acc + term;
+        }
+        Cx[s] = acc;
+    }
+    return CSX_OK;
+}
+
+namespace csx {
+// the most products of a slot; *longs: the slots of more than thr products, ascending
+int32_t multiply_slot_stats(int32_t nnz, const int32_t *sp, int32_t thr, std::vector<int32_t> *longs) {
+    int32_t longest = 0;
+    for (int32_t s = 0; s < nnz; s++) {
+        const int32_t len = sp[s + 1] - sp[s];
+        longest = std::max(longest, len);
+        if (len > thr) longs->push_back(s);
+    }
+    return longest;
+}
+}  // namespace csx

@@ -698,6 +698,59 @@ int csx_assemble_matrix(csx_handle_t plan, csx_handle_t Tx, csx_handle_t *A);
 int csx_assemble(csx_handle_t plan, csx_handle_t Tx, csx_handle_t out);
 int csx_assemble_plan_info(csx_handle_t plan, int64_t *info);
 
+/* ---- multiply plan: new values into the fixed pattern of A*B (multiply_plan) -----------------------
+ * Definition.  A is m-by-k, B is k-by-n, both CSC; row indices inside a column in any order, duplicates inside a column legal,
+ * exactly as csx_multiply accepts them.  Let C = cs_multiply(A, B) as the reference computes it.
+ * Pattern: C.p and C.i are the reference's: columns in order, inside a column the rows in first-touch order, trimmed to nnz.
+ * Plan: for every stored slot s of C, the products that land in it, in the reference's order: sp[0 .. nnz] (slot pointers) and
+ *   pair[2t], pair[2t+1] = (ia, ib): product t is A.x[ia] times B.x[ib]; all int32.  Inside a slot of column j the order is: ib
+ *   ascending through the STORED order of B(:,j) (p in B.p[j] .. B.p[j+1]), and for equal ib, ia ascending through A's column
+ *   B.i[ib] -- the order of the reference's two nested loops, not an order of row indices.  products = sp[nnz] must fit in
+ *   int32: CSX_EINVAL with a message in csx_last_error() otherwise.
+ * Values:   beta_t = B.x[ib_t]                    (unscaled)
+ *           beta_t = d[B.i[ib_t]] * B.x[ib_t]     (scaled by d, a vector of k doubles: C = A diag(d) B; one rounding)
+ *           term_t = beta_t * A.x[ia_t]           (one rounding; NEVER fused with the addition that follows)
+ *           C.x[s] = term_0;  then  C.x[s] = C.x[s] + term_t  for the slot's remaining products, in order.
+ *   The first term is ASSIGNED (the reference does x[i] = beta * Ax[p] on first touch): a slot whose terms are all -0.0 is
+ *   -0.0.  The scaled form is, by definition, cs_multiply(A, B2) with B2.x[p] = d[B.i[p]] * B.x[p].  For finite values the
+ *   bytes are the reference's, the same on every run; NaN payloads are not promised.  No atomics, no hash table, no
+ *   reassociation.
+ * csx_multiply_plan_count: the two sizes on host arrays, *nnz and *products, as int64 (products may exceed int32 here).
+ * csx_multiply_plan_host: the rule on host arrays by the reference's own loops on the indices alone -- an m-sized mark array
+ *   for first touch, then a pass that drops each product at the next free place of its slot; sequential,
+ *   O(products + m + n + nnz(A) + nnz(B)).  The caller's Cp, Ci, sp, pair have room for n+1, nnz, nnz+1, 2 products entries
+ *   (sizes from csx_multiply_plan_count).  CSX_EINVAL for an index out of range, pointers that do not start at 0 or decrease,
+ *   or products > 2^31 - 1.  k = 0, n = 0, empty columns and products = 0 are legal.  (A.n != B.m cannot be said here: there
+ *   is one k.  csx_multiply_plan refuses it.)
+ * csx_multiply_fold_host: the value rule on host arrays: Cx[0 .. nnz) from Ax, Bx through sp, pair.  The scaled form is this
+ *   function on B2.x.
+ * csx_multiply_plan: A, B device CSC handles (only their patterns are read; CSX_EINVAL when A.n != B.m); runs the host rule once
+ *   and uploads p, i, sp, pair: a NEW plan handle (csx_free) that owns them and a copy of B.i -- 8 bytes per product + 4 per
+ *   slot beside the pattern.  A and B themselves are not kept.  The slots are classified: one of more than "multiply.long"
+ *   products (csx_set_option, read here; default 64, unmeasured) is folded by a wave of its own -- 64 pairs loaded per step,
+ *   every lane forming one term, the terms added in index order -- a shorter one by one lane.
+ * csx_multiply_plan_run: Ax / Bx are each a CSC handle with values, or a device vector of EXACTLY nnz(A) / nnz(B) doubles in
+ *   storage order.  A CSC handle must have the operand's shape (m-by-k for Ax, k-by-n for Bx) and entry count; those are
+ *   checked, its PATTERN IS NOT: the caller vouches for it (csx_chol_refactor's A2 is the same convention, except that there
+ *   the pattern is compared).  d is 0 or a vector of at least k doubles.  out is a vector of at least nnz doubles, aliasing no
+ *   input, or a CSC handle with the plan's m, n, nnz and values, whose x is overwritten in place (the SpMV plans cached on it
+ *   are dropped; triangular-solve plans made from it are stale).  CSX_EINVAL on a size mismatch, nothing written.  One launch,
+ *   two when scaled (d[B.i[p]] * B.x[p] into a scratch vector of nnz(B) doubles the plan makes at its first scaled step and
+ *   keeps; the same fold then reads it in place of B.x), queued on the context's stream; no host synchronisation.
+ * csx_multiply_plan_matrix: a NEW CSC handle with the plan's pattern (copied: plan and matrix have independent lifetimes), its
+ *   values folded from Ax, Bx, d as above, or pattern only when Ax and Bx are both 0.
+ * csx_multiply_plan_info: info[8] = m, n, nnz, products, the most products of a slot, the slots folded by a wave, microseconds
+ *   of the host build, microseconds of the last step (between two events, both launches when scaled; waits for it). */
+int csx_multiply_plan_count(int32_t m, int32_t k, int32_t n, const int32_t *Ap, const int32_t *Ai, const int32_t *Bp,
+                            const int32_t *Bi, int64_t *nnz, int64_t *products);
+int csx_multiply_plan_host(int32_t m, int32_t k, int32_t n, const int32_t *Ap, const int32_t *Ai, const int32_t *Bp,
+                           const int32_t *Bi, int32_t *Cp, int32_t *Ci, int32_t *sp, int32_t *pair);
+int csx_multiply_fold_host(int32_t nnz, const int32_t *sp, const int32_t *pair, const double *Ax, const double *Bx, double *Cx);
+int csx_multiply_plan(csx_handle_t A, csx_handle_t B, csx_handle_t *plan);
+int csx_multiply_plan_matrix(csx_handle_t plan, csx_handle_t Ax, csx_handle_t Bx, csx_handle_t d, csx_handle_t *C);
+int csx_multiply_plan_run(csx_handle_t plan, csx_handle_t Ax, csx_handle_t Bx, csx_handle_t d, csx_handle_t out);
+int csx_multiply_plan_info(csx_handle_t plan, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
