@@ -677,8 +677,64 @@ def cs_dupl(A):
     return True
 
 
-class _AssemblyPlan(object):
-    """What assembly_plan returns: see there."""
+class _FoldPlan(object):
+    """What the plans of new values into a fixed pattern share (assembly_plan, multiply_plan; csx_fold.h): the handle, info(),
+    the exact-length check of given values, the .matrix made once, and the tail of .update().  A plan sets _INFO (the fields
+    of its info call, in the library's order) and _INFO_CALL, and defines _first_matrix(), _new_matrix(*values) and
+    _run(out handle, *values)."""
+
+    def _own(self, h):
+        self._handle = h
+        self._fin = weakref.finalize(self, _csx.free, h)
+        self._matrix = None
+
+    def info(self):
+        out = (_csx.C.c_int64 * len(self._INFO))()
+        _csx.check(getattr(_csx.lib(), self._INFO_CALL)(self._handle, out), self._INFO_CALL)
+        return dict(zip(self._INFO, (int(v) for v in out)))
+
+    @staticmethod
+    def _vector(values, count, complaint):
+        """list / numpy / dvec of exactly count numbers -> a dvec (the caller's own when it is one: it is only read);
+        complaint: the ValueError's text, with a %d for the count given"""
+        v = values if isinstance(values, dvec) else dvec(np.asarray(values, dtype=np.float64).ravel())
+        if v.n * v.k != count:
+            raise ValueError(complaint % (v.n * v.k))
+        return v
+
+    @property
+    def matrix(self):
+        if self._matrix is None:
+            self._matrix = cs_pin(_from_device(self._first_matrix(), lambda nnz: nnz))   # the reference trims: nzmax = nnz
+        return self._matrix
+
+    def _fresh(self, *values):
+        out = dvec(self.nnz)
+        self._run(out.handle, *values)
+        return out
+
+    def _update(self, *values):
+        M = self.matrix
+        if M._dev is None:      # unpinned or invalidated by the caller since: resident again, from its lists
+            cs_pin(M)
+        dev = M._dev
+        if not dev.info()[3]:   # pattern only so far: the first values allocate them
+            M._dev = dev = _DevMatrix(self._new_matrix(*values))
+            if not M._lazy:
+                M._x = [0.0] * self.nnz   # (filled by _refactored below)
+        else:
+            self._run(dev.handle, *values)
+        _refactored(M, dev)
+        return M
+
+
+class _AssemblyPlan(_FoldPlan):
+    """What assembly_plan returns: see there.  info(): nz, nnz, max_dup (the most triplets of one slot), long_slots (slots
+    folded by a wave of their own), build_us (the host build of the plan) and kernel_us (the last assemble / update launch,
+    between two events)."""
+
+    _INFO = ("nz", "nnz", "max_dup", "long_slots", "build_us", "kernel_us")
+    _INFO_CALL = "csx_assemble_plan_info"
 
     def __init__(self, T):
         nz = T.nz
@@ -690,63 +746,34 @@ class _AssemblyPlan(object):
         if st == _csx.EINVAL and T.m >= 0 and T.n >= 0 and 0 <= nz <= 2 ** 31 - 1:
             raise IndexError("list index out of range")   # the sizes are legal: an index is not
         _csx.check(st, "csx_assemble_plan")
-        self._handle = h
-        self._fin = weakref.finalize(self, _csx.free, h)
+        self._own(h)
         self.m, self.n, self.nz = T.m, T.n, nz
         self.nnz = self.info()["nnz"]
         self._x0 = None if T.x is None else np.array(T.x[:nz], dtype=np.float64)   # T's values, until .matrix is made
-        self._matrix = None
-
-    def info(self):
-        """nz, nnz, max_dup (the most triplets of one slot), long_slots (slots folded by a wave of their own), build_us (the
-        host build of the plan) and kernel_us (the last assemble / update launch, between two events)"""
-        out = (_csx.C.c_int64 * 6)()
-        _csx.check(_csx.lib().csx_assemble_plan_info(self._handle, out), "csx_assemble_plan_info")
-        return dict(zip(("nz", "nnz", "max_dup", "long_slots", "build_us", "kernel_us"), (int(v) for v in out)))
 
     def _values(self, values, what):
-        """list / numpy / dvec of exactly nz numbers -> a dvec (the caller's own when it is one: it is only read)"""
         if values is None:
             raise ValueError("%s: no values" % what)
-        v = values if isinstance(values, dvec) else dvec(np.asarray(values, dtype=np.float64).ravel())
-        if v.n * v.k != self.nz:
-            raise ValueError("%s: %d values given, the plan has %d triplets" % (what, v.n * v.k, self.nz))
-        return v
+        return self._vector(values, self.nz, "%s: %%d values given, the plan has %d triplets" % (what, self.nz))
 
     def _new_matrix(self, v):
         h = _csx.new_handle()
         _csx.check(_csx.lib().csx_assemble_matrix(self._handle, v.handle if v is not None else 0, h), "csx_assemble_matrix")
         return h
 
-    @property
-    def matrix(self):
-        if self._matrix is None:
-            v = None if self._x0 is None else dvec(self._x0)
-            self._matrix = cs_pin(_from_device(self._new_matrix(v), lambda nnz: nnz))   # cs_dupl trims: nzmax = nnz
-            self._x0 = None
-        return self._matrix
+    def _first_matrix(self):
+        h = self._new_matrix(None if self._x0 is None else dvec(self._x0))
+        self._x0 = None
+        return h
+
+    def _run(self, hout, v):
+        _csx.check(_csx.lib().csx_assemble(self._handle, v.handle, hout), "csx_assemble")
 
     def assemble(self, values):
-        v = self._values(values, "assemble")
-        out = dvec(self.nnz)
-        _csx.check(_csx.lib().csx_assemble(self._handle, v.handle, out.handle), "csx_assemble")
-        return out
+        return self._fresh(self._values(values, "assemble"))
 
     def update(self, values=None):
-        v = self._values(values, "update")
-        M = self.matrix
-        if M._dev is None:      # unpinned or invalidated by the caller since: resident again, from its lists
-            cs_pin(M)
-        dev = M._dev
-        if not dev.info()[3]:   # pattern only so far: the first values allocate them
-            M._dev = _DevMatrix(self._new_matrix(v))
-            if not M._lazy:
-                M._x = [0.0] * self.nnz   # (filled by _refactored below)
-            dev = M._dev
-        else:
-            _csx.check(_csx.lib().csx_assemble(self._handle, v.handle, dev.handle), "csx_assemble")
-        _refactored(M, dev)
-        return M
+        return self._update(self._values(values, "update"))
 
 
 def assembly_plan(T):
@@ -767,10 +794,13 @@ def assembly_plan(T):
     return _AssemblyPlan(T)
 
 
-class _MultiplyPlan(object):
-    """What multiply_plan returns: see there."""
+class _MultiplyPlan(_FoldPlan):
+    """What multiply_plan returns: see there.  info(): m, n, nnz, products, max_products (the most products of one slot),
+    long_slots (slots folded by a wave of their own), build_us (the host build of the plan) and kernel_us (the last step
+    between two events: both launches when scaled)."""
 
     _INFO = ("m", "n", "nnz", "products", "max_products", "long_slots", "build_us", "kernel_us")
+    _INFO_CALL = "csx_multiply_plan_info"
 
     def __init__(self, A, B):
         self._A, self._B = A, B            # kept alive: None for ax / bx means their current values
@@ -781,36 +811,19 @@ class _MultiplyPlan(object):
         if st == _csx.EINVAL:
             raise ValueError(_last_error())
         _csx.check(st, "csx_multiply_plan")
-        self._handle = h
-        self._fin = weakref.finalize(self, _csx.free, h)
+        self._own(h)
         self.k = A.n
         info = self.info()
         self.m, self.n, self.nnz, self.products = info["m"], info["n"], info["nnz"], info["products"]
-        self._matrix = None
-
-    def info(self):
-        """m, n, nnz, products, max_products (the most products of one slot), long_slots (slots folded by a wave of their own),
-        build_us (the host build of the plan) and kernel_us (the last step between two events: both launches when scaled)"""
-        out = (_csx.C.c_int64 * 8)()
-        _csx.check(_csx.lib().csx_multiply_plan_info(self._handle, out), "csx_multiply_plan_info")
-        return dict(zip(self._INFO, (int(v) for v in out)))
-
-    @staticmethod
-    def _vector(values, count, what):
-        """list / numpy / dvec of exactly count numbers -> a dvec (the caller's own when it is one: it is only read)"""
-        v = values if isinstance(values, dvec) else dvec(np.asarray(values, dtype=np.float64).ravel())
-        if v.n * v.k != count:
-            raise ValueError("multiply plan: %d numbers given for %s, %d expected" % (v.n * v.k, what, count))
-        return v
 
     def _step(self, ax, bx, scale, call):
         """call(handle of Ax, handle of Bx, handle of d or 0) with the operands resident for its duration"""
         for M, given, nz, what in ((self._A, ax, self._anz, "A"), (self._B, bx, self._bnz, "B")):
             if given is None and _meta(M) != (nz, True):
                 raise ValueError("multiply plan: %s has no values (or another entry count) and none are given" % what)
-        va = None if ax is None else self._vector(ax, self._anz, "ax")
-        vb = None if bx is None else self._vector(bx, self._bnz, "bx")
-        d = None if scale is None else self._vector(scale, self.k, "scale")
+        va, vb, d = (None if given is None else
+                     self._vector(given, count, "multiply plan: %%d numbers given for %s, %d expected" % (what, count))
+                     for given, count, what in ((ax, self._anz, "ax"), (bx, self._bnz, "bx"), (scale, self.k, "scale")))
         with contextlib.ExitStack() as held:   # an operand whose values are given is not made resident for them
             ha = va.handle if va is not None else held.enter_context(_Resident(self._A)).handle
             hb = vb.handle if vb is not None else held.enter_context(_Resident(self._B)).handle
@@ -823,39 +836,22 @@ class _MultiplyPlan(object):
                    "csx_multiply_plan_matrix")
         return h
 
-    @property
-    def matrix(self):
-        if self._matrix is None:
-            if _meta(self._A)[1] and _meta(self._B)[1]:
-                h = self._new_matrix(None, None, None)
-            else:                                          # as cs_multiply of a pattern-only operand: pattern only
-                h = _csx.new_handle()
-                _csx.check(_csx.lib().csx_multiply_plan_matrix(self._handle, 0, 0, 0, h), "csx_multiply_plan_matrix")
-            self._matrix = cs_pin(_from_device(h, lambda nnz: nnz))   # cs_multiply trims: nzmax = nnz
-        return self._matrix
+    def _first_matrix(self):
+        if _meta(self._A)[1] and _meta(self._B)[1]:
+            return self._new_matrix(None, None, None)
+        h = _csx.new_handle()                          # as cs_multiply of a pattern-only operand: pattern only
+        _csx.check(_csx.lib().csx_multiply_plan_matrix(self._handle, 0, 0, 0, h), "csx_multiply_plan_matrix")
+        return h
+
+    def _run(self, hout, ax, bx, scale):
+        _csx.check(self._step(ax, bx, scale, lambda a, b, d: _csx.lib().csx_multiply_plan_run(self._handle, a, b, d, hout)),
+                   "csx_multiply_plan_run")
 
     def multiply(self, ax=None, bx=None, scale=None):
-        out = dvec(self.nnz)
-        _csx.check(self._step(ax, bx, scale, lambda a, b, d: _csx.lib().csx_multiply_plan_run(self._handle, a, b, d, out.handle)),
-                   "csx_multiply_plan_run")
-        return out
+        return self._fresh(ax, bx, scale)
 
     def update(self, ax=None, bx=None, scale=None):
-        M = self.matrix
-        if M._dev is None:      # unpinned or invalidated by the caller since: resident again, from its lists
-            cs_pin(M)
-        dev = M._dev
-        if not dev.info()[3]:   # pattern only so far: the first values allocate them
-            M._dev = _DevMatrix(self._new_matrix(ax, bx, scale))
-            if not M._lazy:
-                M._x = [0.0] * self.nnz   # (filled by _refactored below)
-            dev = M._dev
-        else:
-            _csx.check(self._step(ax, bx, scale,
-                                  lambda a, b, d: _csx.lib().csx_multiply_plan_run(self._handle, a, b, d, dev.handle)),
-                       "csx_multiply_plan_run")
-        _refactored(M, dev)
-        return M
+        return self._update(ax, bx, scale)
 
 
 def multiply_plan(A, B):

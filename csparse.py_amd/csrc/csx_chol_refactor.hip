@@ -58,12 +58,6 @@ __global__ __launch_bounds__(256) void k_chol_shape(int32_t n, const int32_t *__
     }
 }
 
-__global__ __launch_bounds__(256) void k_chol_rf_differ(int64_t cnt, const int32_t *__restrict__ a, const int32_t *__restrict__ b,
-                                                        int *differ) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < cnt && a[t] != b[t]) *differ = 1;
-}
-
 struct CholRefPlan {
     csx_handle_t hL = 0;
     int32_t n = 0, anz = 0, lnz = 0;
@@ -136,13 +130,8 @@ static int chol_refactor_plan(Csc *A, Csc *L, const int32_t *pinv, CholRefPlan *
         bool ok = false;
         CSX_TRY(clique_forest(A, F.get(), &ok));
         if (ok && F->ascending && F->max_bs <= CLIQUE_MAX_BLOCK && F->lnz == (int64_t)L->nnz) {
-            CSX_HIP(hipMemsetAsync(P->flag, 0, sizeof(int), s));
-            hipLaunchKernelGGL(k_chol_rf_differ, dim3((unsigned)(((int64_t)n + 256) / 256)), dim3(256), 0, s, (int64_t)n + 1,
-                               L->p, F->cp.get(), P->flag.get());
-            CSX_LAUNCH_CHECK();
             int differ = 0;
-            CSX_HIP(hipMemcpyAsync(&differ, P->flag.get(), sizeof(int), hipMemcpyDeviceToHost, s));
-            CSX_HIP(hipStreamSynchronize(s));
+            CSX_TRY(rf_differ((int64_t)n + 1, L->p, F->cp.get(), P->flag.get(), &differ));
             if (differ) {
                 set_error("csx_chol_refactor_plan: an upper entry of A has no slot in L (L is not the factor of A's pattern)");
                 return CSX_EINVAL;

@@ -488,6 +488,22 @@ int csc_validate(Csc *A) {
     A->trusted = true;
     return CSX_OK;
 }
+
+int csc_copy_pattern(int32_t m, int32_t n, int32_t nnz, const int32_t *p, const int32_t *i, bool values,
+                     std::unique_ptr<Csc> *out) {
+    hipStream_t s = ctx().stream;
+    std::unique_ptr<Csc> C(new Csc());
+    C->m = m;
+    C->n = n;
+    C->nnz = nnz;
+    CSX_TRY(dalloc(&C->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&C->i, (size_t)nnz));
+    if (values) CSX_TRY(dalloc(&C->x, (size_t)nnz));
+    CSX_HIP(hipMemcpyAsync(C->p, p, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (nnz) CSX_HIP(hipMemcpyAsync(C->i, i, (size_t)nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    *out = std::move(C);
+    return CSX_OK;
+}
 }  // namespace csx
 
 extern "C" {

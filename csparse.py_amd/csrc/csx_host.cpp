@@ -963,19 +963,6 @@ extern "C" int csx_assemble_host(int32_t nnz, const int32_t *sp, const int32_t *
     return CSX_OK;
 }
 
-namespace csx {
-// the longest slot; *longs: the slots of more than thr terms, ascending
-int32_t assemble_slot_stats(int32_t nnz, const int32_t *sp, int32_t thr, std::vector<int32_t> *longs) {
-    int32_t longest = 0;
-    for (int32_t s = 0; s < nnz; s++) {
-        const int32_t len = sp[s + 1] - sp[s];
-        longest = std::max(longest, len);
-        if (len > thr) longs->push_back(s);
-    }
-    return longest;
-}
-}  // namespace csx
-
 // ---- multiply plan (include/csx.h has the definition) -------------------------------------------------
 // cs_multiply's two nested loops on the indices alone.  Column j of C: down B(:,j) in storage order, down A(:, B.i[ib]) in
 // storage order; a row met for the first time in this column (where[r] < the column's first slot) opens the next slot, any
@@ -1087,16 +1074,3 @@ extern "C" int csx_multiply_fold_host(int32_t nnz, const int32_t *sp, const int3
     }
     return CSX_OK;
 }
-
-namespace csx {
-// the most products of a slot; *longs: the slots of more than thr products, ascending
-int32_t multiply_slot_stats(int32_t nnz, const int32_t *sp, int32_t thr, std::vector<int32_t> *longs) {
-    int32_t longest = 0;
-    for (int32_t s = 0; s < nnz; s++) {
-        const int32_t len = sp[s + 1] - sp[s];
-        longest = std::max(longest, len);
-        if (len > thr) longs->push_back(s);
-    }
-    return longest;
-}
-}  // namespace csx

@@ -209,7 +209,7 @@ struct Refactor;   // csx_refactor.hip
 struct LuRefPlan;  // csx_refactor.hip
 void destroy(Refactor *p);
 void destroy(LuRefPlan *p);
-struct AsmPlan;    // csx_assemble_plan.hip
+struct AsmPlan;    // csx_assemble_plan.hip (both built on FoldCore, csx_fold.h)
 void destroy(AsmPlan *p);
 struct MulPlan;    // csx_multiply_plan.hip
 void destroy(MulPlan *p);
@@ -362,6 +362,10 @@ int build_row_gather(Csc *A);   // fills A->rows (values required)
 // Structure check of a matrix whose arrays the library did not make (csx_csc_wrap): p non-decreasing from 0 to nnz,
 // every row index in [0, m), in one device pass.  CSX_EINVAL (IndexError in Python) otherwise; remembered in A->trusted.
 int csc_validate(Csc *A);
+// *out: a new matrix, not yet a handle, with the pattern p / i (device; copied on the context's stream) and, when `values`,
+// room for nnz values that the caller fills
+int csc_copy_pattern(int32_t m, int32_t n, int32_t nnz, const int32_t *p, const int32_t *i, bool values,
+                     std::unique_ptr<Csc> *out);
 int transpose_device(const Csc *A, bool values, Csc *C);  // C fields allocated here
 int gaxpy_device(Csc *A, const double *x, double *y, int mode);                 // csx_gaxpy.hip: y += A x, raw pointers
 int gaxpy_prepare_device(Csc *A, int mode);                                     // ... the plan `mode` needs, cached on A
@@ -380,6 +384,9 @@ int rf_gather(int64_t cnt, const int32_t *map, const double *src, double *dst); 
 int rf_index_copy(const Csc *A, csx_handle_t *out);                                // A's pattern, x[t] = t
 int rf_index_map(const double *x, int64_t cnt, DevBuf<int32_t> &map);             // map[t] = (int) x[t]
 int rf_keep_pattern(const Csc *A, DevBuf<int32_t> &p, DevBuf<int32_t> &i);
+// *differ: a[0 .. cnt) != b[0 .. cnt) somewhere, or a2 / b2 over cnt2; flag: one int of device scratch; synchronises
+int rf_differ(int64_t cnt, const int32_t *a, const int32_t *b, int *flag, int *differ, int64_t cnt2 = 0,
+              const int32_t *a2 = nullptr, const int32_t *b2 = nullptr);
 // the values of A2 (a matrix with the pattern p0 / i0, or a vector of nnz values), CSX_EINVAL for anything else
 int rf_values(csx_handle_t A2, int32_t m, int32_t n, int32_t nnz, const int32_t *p0, const int32_t *i0, int *flag,
               const double **x);

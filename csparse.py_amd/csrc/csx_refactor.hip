@@ -176,18 +176,10 @@ int rf_gather(int64_t cnt, const int32_t *map, const double *src, double *dst) {
 // a new matrix handle: A's pattern, x[t] = t (exact in binary64): run through the pattern builders, its values say where
 // every entry of the result came from
 int rf_index_copy(const Csc *A, csx_handle_t *out) {
-    hipStream_t s = ctx().stream;
-    std::unique_ptr<Csc> C(new Csc());
-    C->m = A->m;
-    C->n = A->n;
-    C->nnz = A->nnz;
-    CSX_TRY(dalloc(&C->p, (size_t)A->n + 1));
-    CSX_TRY(dalloc(&C->i, (size_t)A->nnz));
-    CSX_TRY(dalloc(&C->x, (size_t)A->nnz));
-    CSX_HIP(hipMemcpyAsync(C->p, A->p, ((size_t)A->n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    std::unique_ptr<Csc> C;
+    CSX_TRY(csc_copy_pattern(A->m, A->n, A->nnz, A->p, A->i, true, &C));
     if (A->nnz) {
-        CSX_HIP(hipMemcpyAsync(C->i, A->i, (size_t)A->nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_rf_iota, dim3(grid_for(A->nnz)), dim3(256), 0, s, (int64_t)A->nnz, C->x);
+        hipLaunchKernelGGL(k_rf_iota, dim3(grid_for(A->nnz)), dim3(256), 0, ctx().stream, (int64_t)A->nnz, C->x);
         CSX_LAUNCH_CHECK();
     }
     *out = put(K_CSC, C.release());
@@ -212,6 +204,20 @@ int rf_keep_pattern(const Csc *A, DevBuf<int32_t> &p, DevBuf<int32_t> &i) {
     return CSX_OK;
 }
 
+// *differ: a[0 .. cnt) is not b[0 .. cnt), or a2[0 .. cnt2) is not b2[0 .. cnt2) (cnt2 may be 0).  flag: one int of device
+// scratch.  Synchronises.
+int rf_differ(int64_t cnt, const int32_t *a, const int32_t *b, int *flag, int *differ, int64_t cnt2, const int32_t *a2,
+              const int32_t *b2) {
+    hipStream_t s = ctx().stream;
+    CSX_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
+    if (cnt) hipLaunchKernelGGL(k_rf_differ, dim3(grid_for(cnt)), dim3(256), 0, s, cnt, a, b, flag);
+    if (cnt2) hipLaunchKernelGGL(k_rf_differ, dim3(grid_for(cnt2)), dim3(256), 0, s, cnt2, a2, b2, flag);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipMemcpyAsync(differ, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
 // The values of A2 (a matrix with the kept pattern, or a vector of nnz values): *x; *x = nullptr (CSX_OK) when A2's pattern or
 // length differs from A's; CSX_EINVAL for a handle that is neither or a matrix without values.  flag: one int of scratch.
 int rf_values(csx_handle_t hA2, int32_t m, int32_t n, int32_t nnz, const int32_t *p0, const int32_t *i0, int *flag,
@@ -221,14 +227,8 @@ int rf_values(csx_handle_t hA2, int32_t m, int32_t n, int32_t nnz, const int32_t
         if (!A2->x) return CSX_EINVAL;
         if (A2->m != m || A2->n != n || A2->nnz != nnz) return CSX_OK;
         if (!A2->trusted) CSX_TRY(csc_validate(A2));
-        hipStream_t s = ctx().stream;
-        CSX_HIP(hipMemsetAsync(flag, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_rf_differ, dim3(grid_for((int64_t)n + 1)), dim3(256), 0, s, (int64_t)n + 1, A2->p, p0, flag);
-        if (nnz) hipLaunchKernelGGL(k_rf_differ, dim3(grid_for(nnz)), dim3(256), 0, s, (int64_t)nnz, A2->i, i0, flag);
-        CSX_LAUNCH_CHECK();
         int differ = 0;
-        CSX_HIP(hipMemcpyAsync(&differ, flag, sizeof(int), hipMemcpyDeviceToHost, s));
-        CSX_HIP(hipStreamSynchronize(s));
+        CSX_TRY(rf_differ((int64_t)n + 1, A2->p, p0, flag, &differ, nnz, A2->i, i0));
         if (!differ) *x = A2->x;
         return CSX_OK;
     }
