@@ -166,6 +166,12 @@ _PROTOS = {
     "csx_multiply_plan_matrix": [H, H, H, H, C.POINTER(H)],
     "csx_multiply_plan_run": [H, H, H, H, H],
     "csx_multiply_plan_info": [H, C.POINTER(C.c_int64)],
+    "csx_add_plan_host": [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_i32p), C.POINTER(_i32p), _i32p, _i32p, _i32p, _i32p, _i32p],
+    "csx_add_fold_host": [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _f64p, C.POINTER(_f64p), _f64p],
+    "csx_add_plan": [C.c_int32, C.POINTER(H), C.POINTER(H)],
+    "csx_add_plan_matrix": [H, _f64p, C.POINTER(H), C.POINTER(H)],
+    "csx_add_plan_run": [H, _f64p, C.POINTER(H), H],
+    "csx_add_plan_info": [H, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],

@@ -678,10 +678,10 @@ def cs_dupl(A):
 
 
 class _FoldPlan(object):
-    """What the plans of new values into a fixed pattern share (assembly_plan, multiply_plan; csx_fold.h): the handle, info(),
-    the exact-length check of given values, the .matrix made once, and the tail of .update().  A plan sets _INFO (the fields
-    of its info call, in the library's order) and _INFO_CALL, and defines _first_matrix(), _new_matrix(*values) and
-    _run(out handle, *values)."""
+    """What the three plans of new values into a fixed pattern share (assembly_plan, multiply_plan, add_plan; csx_fold.h): the
+    handle, info(), the exact-length check of given values, the .matrix made once, and the tail of .update().  A plan sets
+    _INFO (the fields of its info call, in the library's order) and _INFO_CALL, and defines _first_matrix(),
+    _new_matrix(*values) and _run(out handle, *values); one whose reference does not trim its result defines _nzmax(nnz)."""
 
     def _own(self, h):
         self._handle = h
@@ -702,10 +702,14 @@ class _FoldPlan(object):
             raise ValueError(complaint % (v.n * v.k))
         return v
 
+    @staticmethod
+    def _nzmax(nnz):
+        return nnz   # the reference trims: nzmax = nnz
+
     @property
     def matrix(self):
         if self._matrix is None:
-            self._matrix = cs_pin(_from_device(self._first_matrix(), lambda nnz: nnz))   # the reference trims: nzmax = nnz
+            self._matrix = cs_pin(_from_device(self._first_matrix(), self._nzmax))
         return self._matrix
 
     def _fresh(self, *values):
@@ -721,7 +725,7 @@ class _FoldPlan(object):
         if not dev.info()[3]:   # pattern only so far: the first values allocate them
             M._dev = dev = _DevMatrix(self._new_matrix(*values))
             if not M._lazy:
-                M._x = [0.0] * self.nnz   # (filled by _refactored below)
+                M._x = [0.0] * M.nzmax    # (filled by _refactored below)
         else:
             self._run(dev.handle, *values)
         _refactored(M, dev)
@@ -874,6 +878,115 @@ def multiply_plan(A, B):
     if A.n != B.m:
         return None
     return _MultiplyPlan(A, B)
+
+
+class _AddPlan(_FoldPlan):
+    """What add_plan returns: see there.  info(): k, m, n, nnz, terms, max_terms (the most terms of one slot), long_slots (slots
+    folded by a wave of their own; 0 for an aligned plan), aligned (1: every operand has the sum's pattern in the sum's order,
+    the step streams the values and reads no index), build_us (the host build of the plan), kernel_us (the last step between
+    two events) and nzmax (what the reference's chain of cs_add leaves: it does not trim)."""
+
+    _INFO = ("k", "m", "n", "nnz", "terms", "max_terms", "long_slots", "aligned", "build_us", "kernel_us", "nzmax")
+    _INFO_CALL = "csx_add_plan_info"
+
+    def __init__(self, operands, coef):
+        self._ops = tuple(operands)        # kept alive: None for an operand's values means its current ones
+        self.k = len(self._ops)
+        self._nz = [_meta(A)[0] for A in self._ops]
+        self._coef = self._coefficients(coef, None)
+        h = _csx.new_handle()
+        with contextlib.ExitStack() as held:
+            handles = [held.enter_context(_Resident(A)).handle for A in self._ops]
+            st = _csx.lib().csx_add_plan(self.k, (_csx.H * self.k)(*(v.value for v in handles)), h)
+        if st == _csx.EINVAL:
+            raise ValueError(_last_error())
+        _csx.check(st, "csx_add_plan")
+        self._own(h)
+        info = self.info()
+        self.m, self.n, self.nnz, self.terms = info["m"], info["n"], info["nnz"], info["terms"]
+        self._room = max(info["nzmax"], 1)   # (cs_spalloc allocates at least one entry)
+
+    def _nzmax(self, nnz):
+        return self._room
+
+    def _coefficients(self, coef, default):
+        if coef is None:
+            coef = default if default is not None else [1.0] * self.k
+        c = np.asarray([float(v) for v in coef], dtype=np.float64)
+        if c.size != self.k:
+            raise ValueError("add plan: %d coefficients given for %d operands" % (c.size, self.k))
+        return c
+
+    def _step(self, coef, values, call):
+        """call(k host doubles, k handles) with the operands whose values are not given resident for its duration"""
+        c = self._coefficients(coef, self._coef)
+        if values is None:
+            values = [None] * self.k
+        if len(values) != self.k:
+            raise ValueError("add plan: values for %d operands given, the plan has %d" % (len(values), self.k))
+        for r, (A, given, nz) in enumerate(zip(self._ops, values, self._nz)):
+            if given is None and _meta(A) != (nz, True):
+                raise ValueError("add plan: operand %d has no values (or another entry count) and none are given" % r)
+        vecs = [None if given is None else
+                self._vector(given, nz, "add plan: %%d numbers given for operand %d, %d expected" % (r, nz))
+                for r, (given, nz) in enumerate(zip(values, self._nz))]
+        with contextlib.ExitStack() as held:   # an operand whose values are given is not made resident for them
+            handles = [v.handle if v is not None else held.enter_context(_Resident(A)).handle
+                       for v, A in zip(vecs, self._ops)]
+            return call(_csx.pd(c), (_csx.H * self.k)(*(v.value for v in handles)))
+
+    def _new_matrix(self, coef, values):
+        """a new matrix handle with the plan's pattern and the values of a step"""
+        h = _csx.new_handle()
+        _csx.check(self._step(coef, values, lambda c, x: _csx.lib().csx_add_plan_matrix(self._handle, c, x, h)),
+                   "csx_add_plan_matrix")
+        return h
+
+    def _first_matrix(self):
+        if all(_meta(A)[1] for A in self._ops):
+            return self._new_matrix(None, None)
+        h = _csx.new_handle()                          # as cs_add of a pattern-only operand: pattern only
+        _csx.check(_csx.lib().csx_add_plan_matrix(self._handle, None, None, h), "csx_add_plan_matrix")
+        return h
+
+    def _run(self, hout, coef, values):
+        _csx.check(self._step(coef, values, lambda c, x: _csx.lib().csx_add_plan_run(self._handle, c, x, hout)),
+                   "csx_add_plan_run")
+
+    def add(self, coef=None, values=None):
+        return self._fresh(coef, values)
+
+    def update(self, coef=None, values=None):
+        return self._update(coef, values)
+
+
+def add_plan(A, B, *more, coef=None):
+    """The plan of c0*A + c1*B + c2*more[0] + ... for operands whose patterns stay and whose values and coefficients change every
+    step (include/csx.h "add plan"): the reference's chain cs_add(cs_add(A, B, c0, c1), more[0], 1, c2) ...,
+    cs_add itself for two operands.  Only the patterns are read for the plan; None where cs_add returns None (an operand that is
+    not CSC, shapes that differ); ValueError for more than 8 operands or when the operands' entries together do not fit int32.
+    coef: one number per operand (default all 1.0), the plan's own coefficients.  The plan keeps its operands alive, has
+    m, n, k, nnz, terms and info(), and
+      .matrix                 the chain as a device-resident pinned `cs` with the reference's bits from the operands' values at
+                              first use (nzmax as the chain leaves it: cs_add does not trim), or pattern only when any operand
+                              has no values; made once.
+      .add(coef, values)      coef: k numbers (Python ints are fine), None = the plan's own; values: None, or k items, each None
+                              (that operand's current values) or a list, numpy array or dvec of exactly nnz(operand) numbers in
+                              storage order.  A NEW dvec of nnz values in .matrix's storage order -- the reference's bits --
+                              which is what cholsol_factor / lusol_factor / btf_factor(P.matrix).refactor(...) take.
+                              ValueError on a wrong length or count, or when an operand has no values and none are given.
+                              Inputs are never modified or aliased.
+      .update(coef, values)   the same values straight into .matrix, in place: the plans cached on it go, solvers built on it
+                              re-plan, host lists already read from it are refreshed in place.  Returns .matrix.
+    A `cs` operand is trusted to still have the pattern the plan was made from: only its shape and entry count are checked."""
+    operands = (A, B) + tuple(more)
+    if any(not CS_CSC(M) for M in operands):
+        return None
+    if any(M.m != A.m or M.n != A.n for M in operands):
+        return None
+    if len(operands) > 8:
+        raise ValueError("add_plan: %d operands, at most 8" % len(operands))
+    return _AddPlan(operands, coef)
 
 
 def cs_fkeep(A, fkeep, other):

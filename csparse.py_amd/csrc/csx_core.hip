@@ -248,6 +248,7 @@ static void free_object(Object &o) {
         case K_ASMPLAN: destroy((AsmPlan *)o.ptr); break;
         case K_CHOLREFPLAN: destroy((CholRefPlan *)o.ptr); break;
         case K_MULPLAN: destroy((MulPlan *)o.ptr); break;
+        case K_ADDPLAN: destroy((AddPlan *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it
@@ -579,7 +580,7 @@ const OptSlot kOptSlots[] = {
     {"chol.exact", &Options::chol_exact, 0},             {"tri.host_chains", &Options::tri_host_chains, 0},
     {"gaxpy.block_route", &Options::gaxpy_block_route, 3}, {"sparseinv.walk", &Options::sparseinv_walk, 0},
     {"assemble.long", &Options::assemble_long, 7},         {"gaxpy.shape", &Options::gaxpy_shape, 8},
-    {"multiply.long", &Options::multiply_long, 7},
+    {"multiply.long", &Options::multiply_long, 7},         {"add.long", &Options::add_long, 7},
 };
 int normalise(int kind, int value) {
     switch (kind) {

@@ -1,10 +1,11 @@
 // The ordered fold shared by the plans that put new values into a fixed pattern (assembly_plan; multiply_plan,
-// §18).  Every stored slot s of C is a serial, never-reassociated sum over a list fixed when the plan is built:
+// §18; add_plan, §19).  Every stored slot s of C is a serial, never-reassociated sum over a list fixed when the plan is built:
 //
 //     out[s] = ((term(t0) + term(t0 + 1)) + term(t0 + 2)) + ...      over t = sp[s] .. sp[s + 1], the first term assigned
 //
 // -- no atomics, no reassociation.  What a term is, is the plan's (a struct passed to the kernel by value): Tx[src[t]] for
-// assembly, Bx[pair[t].y] * Ax[pair[t].x] rounded on its own for the product.  Two classes of work, one kernel:
+// assembly, Bx[pair[t].y] * Ax[pair[t].x] rounded on its own for the product, c_r * x_r[..] rounded on its own for the sum.  Two
+// classes of work, one kernel:
 //   * short slots: one lane per slot; adjacent lanes read adjacent stretches of the plan's lists, the loads of up to four terms
 //     are in flight together (Term::four), the additions follow in order;
 //   * long slots (more than `thr` terms): one WAVE per slot.  A lane walking such a slot alone would pay a chain of dependent
@@ -13,7 +14,7 @@
 //     computes it), and the terms are added in index order through v_readlane, every lane keeping the same running sum.  The
 //     sum itself stays the serial chain the definition makes it.  The blocks of the long slots come FIRST in the grid, so the
 //     longest chains start first and run beside the short slots.
-// FoldCore is the host side both plans share: the pattern of C, the slot pointers, the long list, the two events of a step.
+// FoldCore is the host side the plans share: the pattern of C, the slot pointers, the long list, the two events of a step.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -179,6 +180,14 @@ struct FoldCore {
         return CSX_OK;
     }
 };
+
+// The values an operand handle of a step stands for: a CSC handle with values and the operand's shape and entry count (its pattern
+// is NOT compared), or a vector of exactly nz doubles.  null: neither.
+inline const double *fold_operand_values(csx_handle_t h, int32_t rows, int32_t cols, int32_t nz) {
+    if (Csc *M = csc(h)) return (M->x && M->m == rows && M->n == cols && M->nnz == nz) ? M->x : nullptr;
+    if (Vec *v = vec(h)) return v->len == nz ? (const double *)v->d : nullptr;
+    return nullptr;
+}
 
 // after a step has written C's values in place (C may be null: the step wrote a vector)
 inline void fold_wrote(Csc *C) {

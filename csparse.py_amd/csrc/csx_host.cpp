@@ -1074,3 +1074,80 @@ extern "C" int csx_multiply_fold_host(int32_t nnz, const int32_t *sp, const int3
     }
     return CSX_OK;
 }
+
+// ---- add plan (include/csx.h has the definition) ------------------------------------------------------
+// cs_add's loop on the indices alone, for k operands: column j of C is cs_scatter of A_0(:,j), then A_1(:,j), ... in stored
+// order; a row met for the first time in this column (where[r] < the column's first slot) opens the next slot, any other entry
+// lands in the slot of its row.  What the loops did to the values is kept as lists: slot s is the fold of the entries
+// src[sp[s] .. sp[s + 1]) -- positions in the concatenation of the operands' value arrays -- in the order the loops met them.
+// A column's slots are consecutive and so are their terms, so each column is counted, then placed.
+extern "C" int csx_add_plan_host(int32_t m, int32_t n, int32_t k, const int32_t *const *Ap, const int32_t *const *Ai, int32_t *Cp,
+                                 int32_t *Ci, int32_t *sp, int32_t *src, int32_t *nnz_out) {
+    if (m < 0 || n < 0 || k < 2 || k > 8 || !Ap || !Ai || !Cp || !sp || !nnz_out) return CSX_EINVAL;
+    int64_t off[9] = {0};
+    for (int32_t r = 0; r < k; r++) {
+        if (!pattern_ok(m, n, Ap[r], Ai[r])) return CSX_EINVAL;   // the reference would raise IndexError
+        off[r + 1] = off[r] + Ap[r][n];
+    }
+    if (off[k] > INT32_MAX) {
+        csx::set_error("add plan: %lld terms do not fit its int32 pointers", (long long)off[k]);
+        return CSX_EINVAL;
+    }
+    if (off[k] > 0 && (!Ci || !src)) return CSX_EINVAL;
+    std::vector<int32_t> where((size_t)m, -1);
+    std::vector<int32_t> fill;   // of the column in hand: its slots' term counts, then the next free place of each slot
+    int32_t nnz = 0, terms = 0;
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t start = nnz;
+        fill.clear();
+        for (int32_t r = 0; r < k; r++)
+            for (int32_t e = Ap[r][j]; e < Ap[r][j + 1]; e++) {
+                const int32_t row = Ai[r][e];
+                if (where[row] < start) {
+                    where[row] = nnz;
+                    Ci[nnz++] = row;
+                    fill.push_back(1);
+                } else {
+                    fill[(size_t)(where[row] - start)]++;
+                }
+            }
+        Cp[j] = start;
+        for (size_t q = 0; q < fill.size(); q++) {
+            const int32_t len = fill[q];
+            sp[(size_t)start + q] = terms;
+            fill[q] = terms;
+            terms += len;
+        }
+        for (int32_t r = 0; r < k; r++)
+            for (int32_t e = Ap[r][j]; e < Ap[r][j + 1]; e++) src[fill[(size_t)(where[Ai[r][e]] - start)]++] = (int32_t)off[r] + e;
+    }
+    Cp[n] = nnz;
+    sp[nnz] = terms;
+    *nnz_out = nnz;
+    return CSX_OK;
+}
+
+// Cx[s] = ((c x) + c' x') + ... over the slot's terms: term t is coef[r] * X[r][src[t] - off[r]] for the operand r that holds
+// position src[t] (off[r] <= src[t] < off[r + 1]), rounded on its own, the first assigned, one addition per further term --
+// never a fused multiply-add
+extern "C" int csx_add_fold_host(int32_t nnz, int32_t k, const int32_t *sp, const int32_t *src, const int32_t *off,
+                                 const double *coef, const double *const *X, double *Cx) {
+#pragma clang fp contract(off)
+    if (nnz < 0 || k < 2 || k > 8 || !sp || !off || !coef || !X || (nnz > 0 && (!src || !Cx))) return CSX_EINVAL;
+    for (int32_t r = 0; r < k; r++)
+        if (off[r + 1] < off[r] || (off[r + 1] > off[r] && !X[r])) return CSX_EINVAL;
+    for (int32_t s = 0; s < nnz; s++) {
+        if (sp[s + 1] <= sp[s]) return CSX_EINVAL;
+        double acc = 0.0;
+        for (int32_t t = sp[s]; t < sp[s + 1]; t++) {
+            const int32_t g = src[t];
+            if (g < off[0] || g >= off[k]) return CSX_EINVAL;
+            int32_t r = 0;
+            while (g >= off[r + 1]) r++;
+            const double term = coef[r] * X[r][g - off[r]];
+            acc = t == sp[s] ? term : acc + term;
+        }
+        Cx[s] = acc;
+    }
+    return CSX_OK;
+}

@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN };
 
 struct Csc;
 
@@ -209,10 +209,12 @@ struct Refactor;   // csx_refactor.hip
 struct LuRefPlan;  // csx_refactor.hip
 void destroy(Refactor *p);
 void destroy(LuRefPlan *p);
-struct AsmPlan;    // csx_assemble_plan.hip (both built on FoldCore, csx_fold.h)
+struct AsmPlan;    // csx_assemble_plan.hip (all three built on FoldCore, csx_fold.h)
 void destroy(AsmPlan *p);
 struct MulPlan;    // csx_multiply_plan.hip
 void destroy(MulPlan *p);
+struct AddPlan;    // csx_add_plan.hip
+void destroy(AddPlan *p);
 struct CholAnalysis;  // csx_chol.hip
 struct CholRefPlan;   // csx_chol_refactor.hip
 void destroy(CholAnalysis *p);
@@ -270,6 +272,9 @@ struct Options {
     int multiply_long = 64;           // csx_multiply_plan: a slot of more than this many products is folded by a wave of its own, a
                                       // shorter one by one lane (read when a plan is built; >= 1).  The default is assemble.long's,
                                       // UNMEASURED for products
+    int add_long = 64;                // csx_add_plan: a slot of more than this many terms is folded by a wave of its own, a shorter
+                                      // one by one lane (read when a plan is built; >= 1).  The default is assemble.long's,
+                                      // UNMEASURED for the terms of a sum
     int lu_etree = 0;                 // cs_lu of one connected matrix on the device, columns scheduled by the column etree:
                                       // 0 never (the default since round 4: measured at best a tie with one host core, on the
                                       // shape it was made for -- profiles/r04_ablation.md), 1 for shallow trees with short

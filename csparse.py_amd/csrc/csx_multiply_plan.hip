@@ -68,19 +68,11 @@ static int multiply_launch(MulPlan *P, const double *Ax, const double *Bx, const
     return c.end();
 }
 
-// The values an operand handle stands for: a CSC handle with values and the operand's shape and entry count (its pattern is NOT
-// compared), or a vector of exactly nz doubles.  null: neither.
-static const double *operand_values(csx_handle_t h, int32_t rows, int32_t cols, int32_t nz) {
-    if (Csc *M = csc(h)) return (M->x && M->m == rows && M->n == cols && M->nnz == nz) ? M->x : nullptr;
-    if (Vec *v = vec(h)) return v->len == nz ? (const double *)v->d : nullptr;
-    return nullptr;
-}
-
 // Ax, Bx, d of a step, checked; d stays null when hd is 0
 static int multiply_inputs(const MulPlan *P, csx_handle_t hAx, csx_handle_t hBx, csx_handle_t hd, const double **Ax,
                            const double **Bx, const double **d) {
-    *Ax = operand_values(hAx, P->core.m, P->k, P->anz);
-    *Bx = operand_values(hBx, P->k, P->core.n, P->bnz);
+    *Ax = fold_operand_values(hAx, P->core.m, P->k, P->anz);
+    *Bx = fold_operand_values(hBx, P->k, P->core.n, P->bnz);
     *d = nullptr;
     if (!*Ax || !*Bx) return CSX_EINVAL;
     if (hd) {

@@ -751,6 +751,60 @@ int csx_multiply_plan_matrix(csx_handle_t plan, csx_handle_t Ax, csx_handle_t Bx
 int csx_multiply_plan_run(csx_handle_t plan, csx_handle_t Ax, csx_handle_t Bx, csx_handle_t d, csx_handle_t out);
 int csx_multiply_plan_info(csx_handle_t plan, int64_t *info);
 
+/* ---- add plan: new values into the fixed pattern of a sum of matrices (add_plan) ---------------------
+ * Definition.  Operands A_0 .. A_{k-1}, 2 <= k <= 8, all m-by-n CSC; row indices inside a column in any order, duplicates
+ * inside a column legal, exactly as csx_add accepts them.  Coefficients c_0 .. c_{k-1}.  Let C be the reference's chain
+ *   C_1 = cs_add(A_0, A_1, c_0, c_1),   C_r = cs_add(C_{r-1}, A_r, 1, c_r) for r >= 2,   C = C_{k-1}
+ * (for k = 2, cs_add itself).
+ * Pattern: C.p and C.i are the reference's: columns in order, inside column j the rows in first-touch order through A_0(:,j) as
+ *   stored, then A_1(:,j), and so on.
+ * Plan: for every stored slot s of C, the operand entries that land in it, in operand order, then stored position inside the
+ *   operand's column -- the order in which the reference's loops touch them: sp[0 .. nnz] (slot pointers) and src[0 .. terms),
+ *   both int32.  src[t] is an index into the concatenation of the operands' value arrays: entry e of A_r is off[r] + e,
+ *   off[r] = sum of nnz(A_q) over q < r.  terms = sum of nnz(A_r) must fit in int32: CSX_EINVAL with a message in
+ *   csx_last_error() otherwise.
+ * Values:   term_t = c_r * A_r.x[e]               (one rounding; NEVER fused with the addition that follows)
+ *           C.x[s] = term_0;  then  C.x[s] = C.x[s] + term_t  for the slot's remaining terms, in list order.
+ *   The first term is ASSIGNED (cs_scatter does x[i] = beta * Ax[p] on first touch): a slot whose terms are all -0.0 is -0.0.
+ *   For k > 2 this is the chain bit for bit: a sum so far has no duplicates, so each of its entries is the first term of its
+ *   slot in the next cs_add, and the chain's 1 * x is exact for every finite x and keeps the sign of zero.  For finite values
+ *   the bytes are the reference's, the same on every run; NaN payloads are not promised.  No atomics, no reassociation.
+ * csx_add_plan_host: the rule on host arrays by the reference's own two loops on the indices alone -- an m-sized mark array for
+ *   first touch and a sequential walk that counts, then places, the terms of each column; O(terms + m + n).  Ap, Ai: k
+ *   pointers to the operands' p and i.  The caller's Cp, Ci, sp, src have room for n+1, terms, terms+1, terms entries; *nnz:
+ *   the slots.  CSX_EINVAL for an index out of range, pointers that do not start at 0 or decrease, k outside 2 .. 8, or
+ *   terms > 2^31 - 1.  n = 0, m = 0, empty columns and empty operands are legal.
+ * csx_add_fold_host: the value rule on host arrays: Cx[0 .. nnz) from the k value arrays X[r] and coefficients coef[r] through
+ *   sp, src and off[0 .. k].
+ * csx_add_plan: k device CSC handles of one shape (only their patterns are read; the same handle may appear more than once:
+ *   A + A; CSX_EINVAL on a shape mismatch); runs the host rule once and uploads the lists: a NEW plan handle (csx_free).  The
+ *   operands themselves are not kept.  The step is one of two classes, decided here:
+ *     aligned -- every operand has exactly C's pattern in C's order (nnz(A_r) = nnz for all r and src restricted to each operand
+ *       is the identity: K + sigma M).  The step reads no index at all: out[s] = (c_0 x_0[s] + c_1 x_1[s]) + ..., streamed with
+ *       16-byte accesses; 8 (k + 1) nnz bytes.  The plan keeps only the pattern.
+ *     general -- the ordered fold: 4 bytes per term + 4 per slot beside the pattern.  A slot of more than "add.long" terms
+ *       (csx_set_option, read here; default 64, unmeasured) is folded by a wave of its own -- 64 terms loaded per step, every
+ *       lane forming one term, the terms added in index order -- a shorter one by one lane.
+ * csx_add_plan_run: coef: k HOST doubles.  X: k handles, each a CSC handle with values, or a device vector of EXACTLY nnz(A_r)
+ *   doubles in storage order.  A CSC handle must have the plan's shape and the operand's entry count; those are checked, its
+ *   PATTERN IS NOT: the caller vouches for it (the convention of csx_multiply_plan_run).  out is a vector of at least nnz
+ *   doubles, aliasing no input, or a CSC handle with the plan's m, n, nnz and values, whose x is overwritten in place (the SpMV
+ *   plans cached on it are dropped; triangular-solve plans made from it are stale).  CSX_EINVAL on a mismatch, nothing written.
+ *   One launch queued on the context's stream; no host synchronisation, no allocation.
+ * csx_add_plan_matrix: a NEW CSC handle with the plan's pattern (copied: plan and matrix have independent lifetimes), its
+ *   values those of a step on coef, X, or pattern only when X is NULL (coef is not read then).
+ * csx_add_plan_info: info[11] = k, m, n, nnz, terms, the most terms of a slot, the slots folded by a wave (0 when aligned),
+ *   aligned (0 / 1), microseconds of the host build, microseconds of the last step (between two events; waits for it), and the
+ *   nzmax the reference's chain leaves (cs_add does not trim: the entries of the last cs_add's two operands). */
+int csx_add_plan_host(int32_t m, int32_t n, int32_t k, const int32_t *const *Ap, const int32_t *const *Ai, int32_t *Cp,
+                      int32_t *Ci, int32_t *sp, int32_t *src, int32_t *nnz);
+int csx_add_fold_host(int32_t nnz, int32_t k, const int32_t *sp, const int32_t *src, const int32_t *off, const double *coef,
+                      const double *const *X, double *Cx);
+int csx_add_plan(int32_t k, const csx_handle_t *operands, csx_handle_t *plan);
+int csx_add_plan_matrix(csx_handle_t plan, const double *coef, const csx_handle_t *X, csx_handle_t *C);
+int csx_add_plan_run(csx_handle_t plan, const double *coef, const csx_handle_t *X, csx_handle_t out);
+int csx_add_plan_info(csx_handle_t plan, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
