@@ -66,6 +66,10 @@ _PROTOS = {
     "csx_gaxpy": [H, H, H, C.c_int],
     "csx_gaxpy_prepare": [H, C.c_int],
     "csx_gaxpy_block": [H, H, H, C.c_int32, C.c_int],
+    "csx_residual_block": [H, H, H, H, C.c_int32, C.c_int, _f64p, _f64p],
+    "csx_residual_host": [C.c_int32, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p],
+    "csx_block_add_cols": [H, H, H, C.c_int64, C.c_int32, _i32p],
+    "csx_block_select_cols": [H, H, C.c_int64, C.c_int32, _i32p],
     "csx_transpose": [H, C.c_int, C.POINTER(H)],
     "csx_cumsum": [H, H, C.c_int64, C.POINTER(C.c_int64)],
     "csx_multiply": [H, H, C.POINTER(H)],

@@ -573,6 +573,53 @@ def gaxpy_block(A, X, Y, mode=None):
     return True
 
 
+def _block_shape(v):
+    """dvec / ndarray / list -> (dvec or float64 ndarray, rows, k); nothing is uploaded"""
+    if isinstance(v, dvec):
+        return v, v.n, v.k
+    a = np.asarray(v, dtype=np.float64)
+    if a.ndim not in (1, 2):
+        raise TypeError("blocks are 1-D vectors or 2-D row-major arrays")
+    return np.ascontiguousarray(a), a.shape[0], 1 if a.ndim == 1 else a.shape[1]
+
+
+def _residual_into(hA, dX, dB, dR, k, trans):
+    """csx_residual_block into dR (a dvec, or None: omega and rnorm only) -> (omega, rnorm)"""
+    omega, rnorm = np.empty(k, dtype=np.float64), np.empty(k, dtype=np.float64)
+    _csx.check(_csx.lib().csx_residual_block(hA, dX.handle, dB.handle, dR.handle if dR is not None else 0, k,
+                                             1 if trans else 0, _csx.pd(omega), _csx.pd(rnorm)), "csx_residual_block")
+    return omega, rnorm
+
+
+def residual_block(A, X, B, trans=False, residual=True):
+    """(R, omega, rnorm) of a block of solutions: R = B - A X (trans=True: B - A' X) as a new dvec (None when
+    residual=False), omega[c] = max_i |r_ic| / (|A| |x_c| + |b_c|)_i the componentwise backward error of column c (0 / 0
+    counts as 0; Oettli-Prager: x_c solves a system whose entries differ from A's and b_c's by at most omega[c] of
+    themselves) and rnorm[c] = max_i |r_ic|, numpy arrays of k doubles -- one pass over the matrix, one order of operations
+    fixed by the matrix: a run is deterministic, a NaN in a column shows in that column's omega and rnorm.
+    trans=True reads A's stored columns as the rows of A': no plan, no transpose.
+
+    X, B: dvec blocks, 2-D row-major arrays, or 1-D vectors / lists (one column).  False for a non-CSC A, X or B None, or
+    unequal k; IndexError for blocks with too few rows; TypeError for a pattern-only A."""
+    if not CS_CSC(A) or X is None or B is None:
+        return False
+    if not _meta(A)[1]:     # pattern only
+        raise TypeError("'NoneType' object is not subscriptable")
+    X, xrows, k = _block_shape(X)
+    B, brows, kb = _block_shape(B)
+    if k != kb or k < 1:
+        return False
+    rows, cols = (A.n, A.m) if trans else (A.m, A.n)
+    if xrows < cols or brows < rows:
+        raise IndexError("list index out of range")
+    dX = X if isinstance(X, dvec) else dvec(X)
+    dB = B if isinstance(B, dvec) else dvec(B)
+    dR = dvec(rows, k) if residual else None
+    with _Resident(A) as dA:
+        omega, rnorm = _residual_into(dA.handle, dX, dB, dR, k, trans)
+    return dR, omega, rnorm
+
+
 def cs_gaxpy_prepare(A, mode=GAXPY_AUTO):
     """Build the SpMV plan of a pinned matrix ahead of time (outside timed regions)."""
     cs_pin(A)
@@ -2056,6 +2103,105 @@ def _refactor_norm(A, A2):
     return out.value
 
 
+class _Refinable(object):
+    """backward_error() and refine() of the solvers of lusol_factor and btf_factor, measured against the matrix
+    the solver stands for: A, or the values of the last successful refactor() on A's pattern (self._A2).  The solver calls
+    _refine_init(A, n), gives _solve_block(blk, trans, from_list) -- its own solve of a dvec block under its own order rule --
+    and calls _operator_changed() after a successful refactor."""
+
+    EPS = 2.0 ** -52
+
+    def _refine_init(self, A, n):
+        self._rA, self._rn = A, n
+        self._op = {"handle": None, "keep": None}     # A's pattern wrapped with the refactor's values (a dvec), while they hold
+        self._operator_builds = 0
+        weakref.finalize(self, lambda op: _csx.free(op["handle"]), self._op)
+
+    def _operator_changed(self):
+        _csx.free(self._op["handle"])
+        self._op["handle"], self._op["keep"] = None, None
+
+    @contextlib.contextmanager
+    def _operator(self):
+        """the handle of the matrix the solver stands for"""
+        A2 = self._A2
+        if isinstance(A2, cs):
+            with _Resident(A2) as d:
+                yield d.handle
+            return
+        if self._op["handle"] is None:
+            # kept until the next successful refactor: the row gather cached on it is built once per set of values
+            A, C = self._rA, _csx.C
+            dev = A._dev if A._dev is not None else _DevMatrix(_upload(A))
+            m, n, nnz, _ = dev.info()
+            dp, di, dx = C.c_void_p(), C.c_void_p(), C.c_void_p()
+            _csx.check(_csx.lib().csx_csc_ptrs(dev.handle, dp, di, dx), "csx_csc_ptrs")
+            h = _csx.new_handle()
+            _csx.check(_csx.lib().csx_csc_wrap(m, n, nnz, dp, di, C.c_void_p(A2.device_ptr()), h), "csx_csc_wrap")
+            self._op["handle"], self._op["keep"] = h, (dev, A2)
+            self._operator_builds += 1
+        yield self._op["handle"].value
+
+    def backward_error(self, x, b, trans=False):
+        """omega of x as a solution of A x = b (trans: A' x = b) per column, a float for one host vector"""
+        n = self._rn
+        X, xrows, k = _block_shape(x)
+        B, brows, kb = _block_shape(b)
+        if k != kb or k < 1:
+            raise ValueError("backward_error: x and b have different numbers of columns")
+        if xrows < n or brows < n:
+            raise IndexError("list index out of range")
+        single = not isinstance(x, dvec) and X.ndim == 1
+        dX = X if isinstance(X, dvec) else dvec(X)
+        dB = B if isinstance(B, dvec) else dvec(B)
+        with self._operator() as hA:
+            omega, _ = _residual_into(hA, dX, dB, None, k, trans)
+        return float(omega[0]) if single else omega
+
+    def refine(self, b, maxit=5, trans=False):
+        """solve, then at most maxit steps of iterative refinement on the columns whose backward error is above 2^-52; b is
+        overwritten with x.  A step is kept only where it lowers the column's omega (strictly), and a column stops once a
+        step fails to halve it: omega <= omega0 always, a rejected step leaves the column bit for bit as it was."""
+        n, eps, trans = self._rn, self.EPS, bool(trans)
+        db, bhost = _vec_in(b, n, "b")
+        k = db.k
+        from_list = not isinstance(b, dvec)
+        lib = _csx.lib()
+
+        def mask(v):
+            return _csx.pi(_csx.i32(v))
+
+        B = db.copy()
+        X = db
+        with self._operator() as hA, np.errstate(invalid="ignore"):
+            self._solve_block(X, trans, from_list)
+            R = dvec(n, k)
+            w, rn = _residual_into(hA, X, B, R, k, trans)
+            w0 = w.copy()
+            steps, solves = np.zeros(k, dtype=np.int64), 1
+            live = w > eps                                   # a NaN column is never live
+            Xc = Rc = D = None
+            for _ in range(int(maxit)):
+                if not live.any():
+                    break
+                if Xc is None:
+                    Xc, Rc, D = dvec(n, k), dvec(n, k), dvec(n, k)
+                _csx.check(lib.csx_vec_copy(R.handle, D.handle), "csx_vec_copy")
+                self._solve_block(D, trans, from_list)
+                solves += 1
+                _csx.check(lib.csx_block_add_cols(X.handle, D.handle, Xc.handle, n, k, mask(live)), "csx_block_add_cols")
+                wc, rnc = _residual_into(hA, Xc, B, Rc, k, trans)
+                accept = live & (wc < w)
+                if accept.any():
+                    _csx.check(lib.csx_block_select_cols(Xc.handle, X.handle, n, k, mask(accept)), "csx_block_select_cols")
+                    _csx.check(lib.csx_block_select_cols(Rc.handle, R.handle, n, k, mask(accept)), "csx_block_select_cols")
+                steps += accept
+                live = accept & (wc > eps) & (2.0 * wc <= w)
+                w, rn = np.where(accept, wc, w), np.where(accept, rnc, rn)
+        _write_back(bhost, db, n * k)
+        return {"omega0": w0, "omega": w, "rnorm": rn, "steps": steps, "solves": solves}
+
+
 def lusol_factor(A, order=0, tol=1.0, exact=None):
     """Factor once for many solves -- the batched form of cs_lusol (csparse.py:1456-1478): cs_sqr + cs_lu once, then
     solve(b) runs the reference's sequence x = b(p); L \\ x; U \\ x; b(q) = x (:1474-1477) on the device for a list (one
@@ -2080,6 +2226,9 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
     nothing changes.  The triangular-solve plans hold copies of the values: they are rebuilt by the next solve.
     refactor_info(): the last refactor's pivot_ratio (min over the columns of |u_kk| / the largest candidate of its column),
     device_columns, host_columns and ms.
+    backward_error(x, b, trans=False): the componentwise backward error of x per column, against A or the last refactor's values;
+    refine(b, maxit=5, trans=False): solve, then iterative refinement while it lowers that error; b is overwritten with x
+    (_Refinable).
     None when A is not square CSC or singular."""
     if not CS_CSC(A) or A.m != A.n:
         return None
@@ -2092,13 +2241,17 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
     hp, keep_p = _perm_handle(N.pinv, n)
     hq, keep_q = _perm_handle(S.q, n)
 
-    class _Solver(object):
+    class _Solver(_Refinable):
         factors, symbolic = N, S
 
         def __init__(self):
             self._fin = weakref.finalize(self, lambda hs: [_csx.free(h) for h in hs if h is not None], [keep_p, keep_q])
             self._A2, self._norm = A, None         # the matrix condest() is about: A, or the last refactor's A2
             self._rplan, self._rinfo = None, None
+            self._refine_init(A, n)
+
+        def _solve_block(self, blk, trans, from_list):
+            return self._block(blk, exact if exact is not None else from_list, trans)
 
         def _block(self, blk, in_exact_order=True, trans=False):
             # x(pinv) = b, L x = x, U x = x, b(q) = x (csparse.py:1470-1473) as ONE library call: in the rounding-equal order on
@@ -2174,6 +2327,7 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
                 for M in (L, U):
                     _refactored(M, M._dev)
                 self._A2, self._norm = A2, None
+                self._operator_changed()
             self._rinfo = {"ok": bool(ok.value), "pivot_ratio": ratio.value, "device_columns": int(cols[0]),
                            "host_columns": int(cols[1]), "ms": 1e3 * (time.perf_counter() - t0)}
             return bool(ok.value)
@@ -2708,6 +2862,7 @@ def btf_factor(A, tol=1.0, seed=0):
     programs are refreshed in place; the transposed ones are made again by the next transposed solve.  True on success;
     False when a kept pivot is 0 or not finite, and then nothing changes.  The first call builds the maps and the schedule.
     refactor_info(): the last refactor's pivot_ratio, device_columns, host_columns and ms.
+    backward_error(x, b, trans=False) and refine(b, maxit=5, trans=False): as on lusol_factor's solver.
     None when A is not CSC, not square, structurally singular (sprank < n), or cs_lu(D) returns None (a numerically
     singular block)."""
     if not CS_CSC(A) or A.m != A.n:
@@ -2751,7 +2906,7 @@ def btf_factor(A, tol=1.0, seed=0):
                                            _csx.pi(r), _csx.pi(levels), nb, plan), "csx_btf_plan")
     ms["plan"] = 1e3 * (time.perf_counter() - t0)
 
-    class _Solver(object):
+    class _Solver(_Refinable):
         factors = fac
         factor_ms = ms      # host wall-clock of the four factor steps (each ends with a copy to the host or a sync)
 
@@ -2762,6 +2917,10 @@ def btf_factor(A, tol=1.0, seed=0):
             self._keep = (L._dev, U._dev, F._dev)
             self._A2, self._norm = A, None         # the matrix condest() is about: A, or the last refactor's A2
             self._prepared, self._rinfo = False, None
+            self._refine_init(A, n)
+
+        def _solve_block(self, blk, trans, from_list):
+            return self.solve(blk, trans)      # one order for lists and blocks
 
         def info(self):
             v = np.zeros(8, dtype=np.int64)
@@ -2819,6 +2978,7 @@ def btf_factor(A, tol=1.0, seed=0):
                     _csx.check(_csx.lib().csx_btf_refactor_dx(plan, _csx.pd(x)), "csx_btf_refactor_dx")
                     D._x[:nnz] = x[:nnz].tolist()
                 self._A2, self._norm = A2, None
+                self._operator_changed()
             self._rinfo = {"ok": bool(ok.value), "pivot_ratio": ratio.value, "device_columns": int(cols[0]),
                            "host_columns": int(cols[1]), "ms": 1e3 * (time.perf_counter() - t0)}
             return bool(ok.value)

@@ -1151,3 +1151,54 @@ extern "C" int csx_add_fold_host(int32_t nnz, int32_t k, const int32_t *sp, cons
     }
     return CSX_OK;
 }
+
+// csx_residual_block's value rule on host arrays (csx_residual.hip): R = B - op(A) X for row-major blocks of nrhs
+// columns, omega[c] = max_i |r| / (|op(A)| |X| + |B|), rnorm[c] = max_i |r|.  Row i's terms in ascending (column, storage
+// position) order for op(A) = A -- a sweep over the columns in storage order gives every row exactly that order -- and in the
+// storage order of column i of A for op(A) = A'.  Product rounded, then the subtraction: never a fused multiply-add.  The maxima
+// over the bit patterns of the non-negative doubles (NaN above inf, any order).  R may be B (or NULL).
+extern "C" int csx_residual_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, const double *x, int32_t nrhs, int trans,
+                                 const double *X, const double *B, double *R, double *omega, double *rnorm) {
+#pragma clang fp contract(off)
+    if (m < 0 || n < 0 || nrhs < 1 || !p || p[0] != 0) return CSX_EINVAL;
+    const int32_t nnz = p[n];
+    if (nnz < 0 || (nnz > 0 && (!i || !x))) return CSX_EINVAL;
+    const int32_t rows = trans ? n : m, cols = trans ? m : n;
+    if ((rows > 0 && !B) || (rows > 0 && cols > 0 && nnz > 0 && !X)) return CSX_EINVAL;
+    for (int32_t j = 0; j < n; j++)
+        if (p[j + 1] < p[j]) return CSX_EINVAL;
+    for (int32_t q = 0; q < nnz; q++)
+        if (i[q] < 0 || i[q] >= m) return CSX_EINVAL;
+    const size_t k = (size_t)nrhs;
+    std::vector<double> r((size_t)rows * k), d((size_t)rows * k);
+    for (size_t t = 0; t < r.size(); t++) {
+        r[t] = B[t];
+        d[t] = std::fabs(B[t]);
+    }
+    for (int32_t j = 0; j < n; j++)
+        for (int32_t q = p[j]; q < p[j + 1]; q++) {
+            const double a = x[q], aa = std::fabs(a);
+            const size_t out = (size_t)(trans ? j : i[q]) * k, in = (size_t)(trans ? i[q] : j) * k;
+            for (size_t c = 0; c < k; c++) {
+                const double t = a * X[in + c];
+                r[out + c] = r[out + c] - t;
+                const double u = aa * std::fabs(X[in + c]);
+                d[out + c] = d[out + c] + u;
+            }
+        }
+    std::vector<uint64_t> wmax(k, 0), amax(k, 0);
+    for (size_t t = 0; t < r.size(); t++) {
+        const double ar = std::fabs(r[t]);
+        const double ratio = (ar == 0.0 && d[t] == 0.0) ? 0.0 : ar / d[t];
+        const double av = std::fabs(ratio);
+        uint64_t wb, ab;
+        std::memcpy(&wb, &av, 8);
+        std::memcpy(&ab, &ar, 8);
+        wmax[t % k] = std::max(wmax[t % k], wb);
+        amax[t % k] = std::max(amax[t % k], ab);
+    }
+    if (omega) std::memcpy(omega, wmax.data(), k * 8);
+    if (rnorm) std::memcpy(rnorm, amax.data(), k * 8);
+    if (R) std::memcpy(R, r.data(), r.size() * 8);
+    return CSX_OK;
+}

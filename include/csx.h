@@ -180,6 +180,34 @@ int csx_gaxpy_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, con
  * overlapping device ranges.  m == 0, n == 0 or nnz == 0: nothing to do, CSX_OK. */
 int csx_gaxpy_block(csx_handle_t A, csx_handle_t X, csx_handle_t Y, int32_t nrhs, int mode);
 
+/* ---- residual and componentwise backward error of a block of solutions ----
+ * R = B - op(A) X for row-major blocks of nrhs columns, with the componentwise backward error of every column.
+ * trans == 0: op(A) = A (m x n): X has >= n nrhs, B and R >= m nrhs entries; reads A's cached row gather
+ *             (built on demand, as csx_gaxpy_block does).
+ * trans != 0: op(A) = A' (n x m): X has >= m nrhs, B and R >= n nrhs entries; reads A.p / A.i / A.x as they are stored:
+ *             no plan is built or needed.
+ * R == 0: the residual is not stored (omega / rnorm only).  omega, rnorm: host arrays of nrhs doubles, either may be NULL.
+ * One order, fixed by the matrix, the same on the device and on the host: for output row i of op(A) and column c the
+ * row's terms (a_q, j_q) in the row gather's order (ascending (column, storage position); trans == 0) or in the storage
+ * order of column i of A (trans != 0):
+ *     r = B[i,c];    for each term:  t = a_q * X[j_q,c]      (rounded);   r = r - t   (rounded)
+ *     d = |B[i,c]|;  for each term:  u = |a_q| * |X[j_q,c]|  (rounded);   d = d + u   (rounded)
+ *     ratio[i,c] = 0 when |r| == 0 and d == 0, else |r| / d   (IEEE division; NaN and inf propagate)
+ *     omega[c] = max_i ratio[i,c],  rnorm[c] = max_i |r|      (0 for an operator without rows)
+ * The maxima are taken over the bit patterns of the non-negative doubles: a NaN in a column makes its omega and rnorm
+ * NaN, and no run depends on an order.  R may be the same handle as B (in place).  CSX_EINVAL for a pattern-only A,
+ * nrhs < 1, short blocks, R or B the same handle as X, overlapping device ranges (R and B: anything but the same
+ * range).  m == 0, n == 0 or nnz == 0 are legal: R = B, omega by the 0 / 0 rule, rnorm = max |B|. */
+int csx_residual_block(csx_handle_t A, csx_handle_t X, csx_handle_t B, csx_handle_t R, int32_t nrhs, int trans,
+                       double *omega, double *rnorm);
+/* the same rule on host arrays (no device); R may be B or NULL */
+int csx_residual_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, const double *x, int32_t nrhs, int trans,
+                      const double *X, const double *B, double *R /* or NULL */, double *omega, double *rnorm);
+/* out[i, c] = mask[c] ? X[i, c] + D[i, c] : X[i, c]   (one rounding);   dst[i, c] = src[i, c] where mask[c].
+ * mask: nrhs host int32, uploaded by the call.  Blocks of rows x nrhs, row-major; out may be X or D, src and dst apart. */
+int csx_block_add_cols(csx_handle_t X, csx_handle_t D, csx_handle_t out, int64_t rows, int32_t nrhs, const int32_t *mask);
+int csx_block_select_cols(csx_handle_t src, csx_handle_t dst, int64_t rows, int32_t nrhs, const int32_t *mask);
+
 /* cs_transpose, csparse.py:2292-2315: stable counting sort by row. */
 int csx_transpose(csx_handle_t A, int values, csx_handle_t *out);
 
