@@ -68,6 +68,9 @@ _PROTOS = {
     "csx_gaxpy_block": [H, H, H, C.c_int32, C.c_int],
     "csx_residual_block": [H, H, H, H, C.c_int32, C.c_int, _f64p, _f64p],
     "csx_residual_host": [C.c_int32, C.c_int32, _i32p, _i32p, _f64p, C.c_int32, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p],
+    "csx_residual_sym_block": [H, H, H, H, C.c_int32, _f64p, _f64p],
+    "csx_residual_sym_host": [C.c_int32, _i32p, _i32p, _f64p, C.c_int32, _f64p, _f64p, _f64p, _f64p, _f64p],
+    "csx_norm1_sym": [H, _f64p],
     "csx_block_add_cols": [H, H, H, C.c_int64, C.c_int32, _i32p],
     "csx_block_select_cols": [H, H, C.c_int64, C.c_int32, _i32p],
     "csx_transpose": [H, C.c_int, C.POINTER(H)],

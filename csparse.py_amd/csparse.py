@@ -441,6 +441,12 @@ class _Resident(object):
         return False
 
 
+@contextlib.contextmanager
+def _resident_handle(A):
+    with _Resident(A) as d:
+        yield d.handle
+
+
 def cs_pin(A):
     """Keep A resident on the device (and cache its analyses) until cs_unpin /
     its host lists are reassigned.  In-place edits of A.p / A.i / A.x after
@@ -591,18 +597,33 @@ def _residual_into(hA, dX, dB, dR, k, trans):
     return omega, rnorm
 
 
-def residual_block(A, X, B, trans=False, residual=True):
+def _residual_sym_into(hA, dX, dB, dR, k, trans=False):
+    """csx_residual_sym_block into dR (a dvec, or None: omega and rnorm only) -> (omega, rnorm); trans has no effect"""
+    omega, rnorm = np.empty(k, dtype=np.float64), np.empty(k, dtype=np.float64)
+    _csx.check(_csx.lib().csx_residual_sym_block(hA, dX.handle, dB.handle, dR.handle if dR is not None else 0, k,
+                                                 _csx.pd(omega), _csx.pd(rnorm)), "csx_residual_sym_block")
+    return omega, rnorm
+
+
+def residual_block(A, X, B, trans=False, residual=True, sym=False):
     """(R, omega, rnorm) of a block of solutions: R = B - A X (trans=True: B - A' X) as a new dvec (None when
     residual=False), omega[c] = max_i |r_ic| / (|A| |x_c| + |b_c|)_i the componentwise backward error of column c (0 / 0
     counts as 0; Oettli-Prager: x_c solves a system whose entries differ from A's and b_c's by at most omega[c] of
     themselves) and rnorm[c] = max_i |r_ic|, numpy arrays of k doubles -- one pass over the matrix, one order of operations
     fixed by the matrix: a run is deterministic, a NaN in a column shows in that column's omega and rnorm.
     trans=True reads A's stored columns as the rows of A': no plan, no transpose.
+    sym=True: A is square and stands for the symmetric matrix S a Cholesky factorisation sees in it -- its stored entries with
+    row <= column, mirrored; whatever lies strictly below the diagonal is ignored, so an upper-triangle-only storage, a full one
+    and one with other values below give the same bytes (duplicates in the upper triangle are summed, where
+    cs_chol keeps the last).  trans has no effect then (S = S').  A fully stored symmetric A with sorted columns gives the
+    bytes of the general call.
 
-    X, B: dvec blocks, 2-D row-major arrays, or 1-D vectors / lists (one column).  False for a non-CSC A, X or B None, or
-    unequal k; IndexError for blocks with too few rows; TypeError for a pattern-only A."""
-    if not CS_CSC(A) or X is None or B is None:
+    X, B: dvec blocks, 2-D row-major arrays, or 1-D vectors / lists (one column).  False for a non-CSC A, X or B None,
+    unequal k, or sym=True with a non-square A; IndexError for blocks with too few rows; TypeError for a pattern-only A."""
+    if not CS_CSC(A) or X is None or B is None or (sym and A.m != A.n):
         return False
+    if sym:
+        trans = False
     if not _meta(A)[1]:     # pattern only
         raise TypeError("'NoneType' object is not subscriptable")
     X, xrows, k = _block_shape(X)
@@ -616,7 +637,7 @@ def residual_block(A, X, B, trans=False, residual=True):
     dB = B if isinstance(B, dvec) else dvec(B)
     dR = dvec(rows, k) if residual else None
     with _Resident(A) as dA:
-        omega, rnorm = _residual_into(dA.handle, dX, dB, dR, k, trans)
+        omega, rnorm = (_residual_sym_into if sym else _residual_into)(dA.handle, dX, dB, dR, k, trans)
     return dR, omega, rnorm
 
 
@@ -1700,7 +1721,11 @@ def cholsol_factor(A, order=0, exact=None):
     cs_cholsol, the reference's own driver, is always exact.
     refactor(A2): new values on A's pattern with the analysis kept: L.x becomes the factor of A2, byte-equal to a
     fresh cholsol_factor(A2, order, exact)'s (to rounding only under "chol.exact" = 0 with exact other than True); False, and nothing changed, when A2 is not positive definite; ValueError for
-    another pattern.  refactor_info(): the last refactor's route, launch counts and times."""
+    another pattern.  refactor_info(): the last refactor's route, launch counts and times.
+    backward_error(x, b, A=None), refine(b, maxit=5, A=None), condest(A=None), operator_info(): the componentwise backward
+    error of x, iterative refinement and a 1-norm condition estimate against the SYMMETRIC matrix in the upper triangle of the
+    operator (_Refinable): the factored matrix or the last refactor's values, or A= for any other square matrix
+    of order n -- a stale factor against a new matrix, or the matrix after update().  See the methods."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     first_plan = None
@@ -1740,8 +1765,9 @@ def cholsol_factor(A, order=0, exact=None):
             _csx.check(_csx.lib().csx_cholsol_set_order(h, 0), "csx_cholsol_set_order")
         return h
 
-    class _Solver(object):
+    class _Solver(_Refinable):
         L = N.L
+        _residual_into = staticmethod(_residual_sym_into)
 
         @property
         def symbolic(self):
@@ -1762,6 +1788,68 @@ def cholsol_factor(A, order=0, exact=None):
             self._box = [self.plan_handle]
             self._fin = weakref.finalize(self, lambda box: _csx.free(box[0]), self._box)
             self._rplan, self._rinfo = None, None    # refactor(): made by its first call
+            self._A2 = A                             # the matrix the factor stands for: A, or the last refactor's A2
+            self._stands = dev.version               # ... while the factor's version is this one (update / downdate move it)
+            self._source = None                      # operator_info(): what the last measurement was taken against
+            self._refine_init(A, n)
+
+        def _solve_block(self, blk, trans, from_list):
+            _csx.check(_csx.lib().csx_cholsol_solve(self._plan_for(not from_list), blk.handle, blk.k), "csx_cholsol_solve")
+            return blk
+
+        def _operator_for(self, A_given):
+            """the context manager of the operator's handle: A_given's, or the factored / refactored matrix's"""
+            if A_given is not None:
+                if not CS_CSC(A_given) or A_given.m != n or A_given.n != n:
+                    raise ValueError("A= must be a square CSC matrix of order %d" % n)
+                if not _meta(A_given)[1]:
+                    raise TypeError("A= is a pattern-only matrix")
+                self._source = "given"
+                return _resident_handle(A_given)
+            if self._stands != dev.version:
+                raise RuntimeError("the factor was changed in place (update / downdate / cs_updown) and no longer stands for "
+                                   "the factored matrix: pass the matrix it stands for now as A=, or refactor()")
+            self._source = "factored" if self._A2 is A else "refactored"
+            return self._operator()
+
+        def backward_error(self, x, b, A=None):
+            """omega of x as a solution of S x = b per column (a float for one host vector), S the symmetric matrix in the
+            upper triangle of the operator: the factored matrix, or the values of the last successful refactor(), in A's own
+            numbering whatever the order; or A=, a square CSC matrix of order n with values (ValueError for another shape,
+            TypeError for a pattern-only one) -- pin it (cs_pin) to keep its row gather between calls.  RuntimeError for
+            A=None after update / downdate / cs_updown changed the factor: it stands for another matrix then, until the
+            next successful refactor()."""
+            return self._backward_error(x, b, False, self._operator_for(A))
+
+        def refine(self, b, maxit=5, A=None):
+            """solve, then at most maxit steps of iterative refinement against the operator (see backward_error) on the
+            columns whose backward error is above 2^-52; b is overwritten with x.  With A= a nearby matrix this is the
+            stale-factor iteration: the factor preconditions, A is solved.  _Refinable.refine's loop and result."""
+            return self._refine(b, maxit, False, self._operator_for(A))
+
+        def condest(self, A=None):
+            """an estimate of cond_1(S) = |S|_1 |S^-1|_1 of the operator (see backward_error): csx_norm1_sym times
+            Hager-Higham's estimate of the inverse's norm from single right-hand-side solves on this factor.  The estimate
+            is a lower bound, and no condition number is below 1: the result is never below 1.0 (0.0 for n = 0) -- a solve
+            divides by every pivot twice, so for a well-conditioned matrix the product can round to just under 1"""
+            with self._operator_for(A) as hA:
+                out = _csx.C.c_double(0.0)
+                _csx.check(_csx.lib().csx_norm1_sym(hA, out), "csx_norm1_sym")
+
+            def one(v, t):
+                x = v.tolist()
+                self.solve(x)
+                return np.asarray(x, dtype=np.float64)
+
+            est = _condest(out.value, one, n)
+            return est if n == 0 else max(est, 1.0)     # (a NaN stays a NaN)
+
+        def operator_info(self):
+            """source: what the last backward_error / refine / condest measured against ("factored", "refactored" or "given";
+            before the first, what A=None would take); builds: how often the refactor's values were wrapped over A's pattern
+            (once per set of values given as values rather than as a matrix)"""
+            src = self._source or ("factored" if self._A2 is A else "refactored")
+            return {"source": src, "builds": self._operator_builds}
 
         def _current(self):
             """The plan copies part of L's values (forward gather arrays, fragments): after cs_updown(F.L, ...) changed
@@ -1879,6 +1967,8 @@ def cholsol_factor(A, order=0, exact=None):
             _refactor_call(A2, lambda h2: _csx.lib().csx_chol_refactor(self._rplan, h2, ok, _csx.pi(info)), ok)
             if ok.value:
                 _refactored(N.L, dev)
+                self._A2, self._stands, self._source = A2, dev.version, None
+                self._operator_changed()
             num, call = _csx.C.c_double(0.0), _csx.C.c_double(0.0)
             _csx.check(_csx.lib().csx_chol_refactor_info(num, call), "csx_chol_refactor_info")
             self._rinfo = {"ok": bool(ok.value), "route": "forest" if info[0] else "general", "levels": int(info[1]),
@@ -2107,9 +2197,12 @@ class _Refinable(object):
     """backward_error() and refine() of the solvers of lusol_factor and btf_factor, measured against the matrix
     the solver stands for: A, or the values of the last successful refactor() on A's pattern (self._A2).  The solver calls
     _refine_init(A, n), gives _solve_block(blk, trans, from_list) -- its own solve of a dvec block under its own order rule --
-    and calls _operator_changed() after a successful refactor."""
+    and calls _operator_changed() after a successful refactor.  _residual_into(hA, dX, dB, dR, k, trans) -> (omega, rnorm) is
+    the residual of that operator: csx_residual_block here; the cholsol solver, whose operator is the symmetric matrix in the
+    upper triangle, gives csx_residual_sym_block."""
 
     EPS = 2.0 ** -52
+    _residual_into = staticmethod(_residual_into)
 
     def _refine_init(self, A, n):
         self._rA, self._rn = A, n
@@ -2144,6 +2237,9 @@ class _Refinable(object):
 
     def backward_error(self, x, b, trans=False):
         """omega of x as a solution of A x = b (trans: A' x = b) per column, a float for one host vector"""
+        return self._backward_error(x, b, trans, self._operator())
+
+    def _backward_error(self, x, b, trans, operator):
         n = self._rn
         X, xrows, k = _block_shape(x)
         B, brows, kb = _block_shape(b)
@@ -2154,14 +2250,17 @@ class _Refinable(object):
         single = not isinstance(x, dvec) and X.ndim == 1
         dX = X if isinstance(X, dvec) else dvec(X)
         dB = B if isinstance(B, dvec) else dvec(B)
-        with self._operator() as hA:
-            omega, _ = _residual_into(hA, dX, dB, None, k, trans)
+        with operator as hA:
+            omega, _ = self._residual_into(hA, dX, dB, None, k, trans)
         return float(omega[0]) if single else omega
 
     def refine(self, b, maxit=5, trans=False):
         """solve, then at most maxit steps of iterative refinement on the columns whose backward error is above 2^-52; b is
         overwritten with x.  A step is kept only where it lowers the column's omega (strictly), and a column stops once a
         step fails to halve it: omega <= omega0 always, a rejected step leaves the column bit for bit as it was."""
+        return self._refine(b, maxit, trans, self._operator())
+
+    def _refine(self, b, maxit, trans, operator):
         n, eps, trans = self._rn, self.EPS, bool(trans)
         db, bhost = _vec_in(b, n, "b")
         k = db.k
@@ -2173,10 +2272,10 @@ class _Refinable(object):
 
         B = db.copy()
         X = db
-        with self._operator() as hA, np.errstate(invalid="ignore"):
+        with operator as hA, np.errstate(invalid="ignore"):
             self._solve_block(X, trans, from_list)
             R = dvec(n, k)
-            w, rn = _residual_into(hA, X, B, R, k, trans)
+            w, rn = self._residual_into(hA, X, B, R, k, trans)
             w0 = w.copy()
             steps, solves = np.zeros(k, dtype=np.int64), 1
             live = w > eps                                   # a NaN column is never live
@@ -2190,7 +2289,7 @@ class _Refinable(object):
                 self._solve_block(D, trans, from_list)
                 solves += 1
                 _csx.check(lib.csx_block_add_cols(X.handle, D.handle, Xc.handle, n, k, mask(live)), "csx_block_add_cols")
-                wc, rnc = _residual_into(hA, Xc, B, Rc, k, trans)
+                wc, rnc = self._residual_into(hA, Xc, B, Rc, k, trans)
                 accept = live & (wc < w)
                 if accept.any():
                     _csx.check(lib.csx_block_select_cols(Xc.handle, X.handle, n, k, mask(accept)), "csx_block_select_cols")

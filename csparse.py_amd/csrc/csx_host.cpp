@@ -1202,3 +1202,56 @@ extern "C" int csx_residual_host(int32_t m, int32_t n, const int32_t *p, const i
     if (R) std::memcpy(R, r.data(), r.size() * 8);
     return CSX_OK;
 }
+
+// csx_residual_sym_block's value rule on host arrays (csx_residual_sym.hip): R = B - S X with S the stored
+// entries of A with row <= column, mirrored.  Row i's terms: first the entries of stored column i with A.i[q] <= i, in storage
+// order; then the entries of row i with column > i in ascending (column, storage position) order.  One sweep over the columns
+// in storage order gives every row exactly that: column j's kept entries go to row j first (rows below j have not been swept
+// to yet, rows above took theirs before), then its strictly upper entries go to their own rows, which have had their phase 1
+// and the columns before j.  Strictly lower entries are skipped, never added as zeros.  Otherwise as csx_residual_host.
+extern "C" int csx_residual_sym_host(int32_t n, const int32_t *p, const int32_t *i, const double *x, int32_t nrhs, const double *X,
+                                     const double *B, double *R, double *omega, double *rnorm) {
+#pragma clang fp contract(off)
+    if (n < 0 || nrhs < 1 || !p || p[0] != 0) return CSX_EINVAL;
+    const int32_t nnz = p[n];
+    if (nnz < 0 || (nnz > 0 && (!i || !x))) return CSX_EINVAL;
+    if ((n > 0 && !B) || (n > 0 && nnz > 0 && !X)) return CSX_EINVAL;
+    for (int32_t j = 0; j < n; j++)
+        if (p[j + 1] < p[j]) return CSX_EINVAL;
+    for (int32_t q = 0; q < nnz; q++)
+        if (i[q] < 0 || i[q] >= n) return CSX_EINVAL;
+    const size_t k = (size_t)nrhs;
+    std::vector<double> r((size_t)n * k), d((size_t)n * k);
+    for (size_t t = 0; t < r.size(); t++) {
+        r[t] = B[t];
+        d[t] = std::fabs(B[t]);
+    }
+    for (int32_t j = 0; j < n; j++)
+        for (int phase = 0; phase < 2; phase++)
+            for (int32_t q = p[j]; q < p[j + 1]; q++) {
+                if (phase == 0 ? i[q] > j : i[q] >= j) continue;
+                const double a = x[q], aa = std::fabs(a);
+                const size_t out = (size_t)(phase == 0 ? j : i[q]) * k, in = (size_t)(phase == 0 ? i[q] : j) * k;
+                for (size_t c = 0; c < k; c++) {
+                    const double t = a * X[in + c];
+                    r[out + c] = r[out + c] - t;
+                    const double u = aa * std::fabs(X[in + c]);
+                    d[out + c] = d[out + c] + u;
+                }
+            }
+    std::vector<uint64_t> wmax(k, 0), amax(k, 0);
+    for (size_t t = 0; t < r.size(); t++) {
+        const double ar = std::fabs(r[t]);
+        const double ratio = (ar == 0.0 && d[t] == 0.0) ? 0.0 : ar / d[t];
+        const double av = std::fabs(ratio);
+        uint64_t wb, ab;
+        std::memcpy(&wb, &av, 8);
+        std::memcpy(&ab, &ar, 8);
+        wmax[t % k] = std::max(wmax[t % k], wb);
+        amax[t % k] = std::max(amax[t % k], ab);
+    }
+    if (omega) std::memcpy(omega, wmax.data(), k * 8);
+    if (rnorm) std::memcpy(rnorm, amax.data(), k * 8);
+    if (R) std::memcpy(R, r.data(), r.size() * 8);
+    return CSX_OK;
+}

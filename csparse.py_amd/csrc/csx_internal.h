@@ -364,6 +364,9 @@ int boundaries_from_sorted(const uint32_t *sorted_key, int64_t count, int32_t nk
 
 // ---- building blocks shared across files ----
 int build_row_gather(Csc *A);   // fills A->rows (values required)
+// csx_residual.hip: h[0 .. width) (host) = the maxima, as unsigned integers, over the `count` rows of part (device, count x width,
+// not written); synchronises the context's stream
+int max_partials_host(const uint64_t *part, int64_t count, int32_t width, uint64_t *h);
 // Structure check of a matrix whose arrays the library did not make (csx_csc_wrap): p non-decreasing from 0 to nnz,
 // every row index in [0, m), in one device pass.  CSX_EINVAL (IndexError in Python) otherwise; remembered in A->trusted.
 int csc_validate(Csc *A);

@@ -203,33 +203,43 @@ static void launch_residual(unsigned blocks, int32_t rows, int32_t nrhs, const i
 #undef CSX_RES
 }
 
-// the residual of `rows` gathered rows and the maxima of every column (host arrays, either may be null)
-static int run_residual(int32_t rows, int32_t nrhs, const int32_t *ptr, const int32_t *idx, const double *val, const double *X,
-                        const double *B, double *R, double *omega, double *rnorm) {
+// h[0 .. width) = the maxima over the `count` rows of part (count x width bit patterns, left as they are); synchronises
+int max_partials_host(const uint64_t *part, int64_t count, int32_t width, uint64_t *h) {
     hipStream_t s = ctx().stream;
-    const int32_t width = 2 * nrhs;
-    const int64_t blocks = ((int64_t)rows + RES_TILE - 1) / RES_TILE;
-    const int64_t second = (blocks + 255) / 256;
     DevBuf<uint64_t> pa, pb;
-    CSX_TRY(pa.alloc((size_t)blocks * width));
-    CSX_TRY(pb.alloc((size_t)second * width));
-    if (R) launch_residual<true>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
-    else launch_residual<false>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
-    CSX_LAUNCH_CHECK();
-    if (!omega && !rnorm) return CSX_OK;
-    uint64_t *in = pa, *out = pb;
-    int64_t count = blocks;
+    const uint64_t *in = part;
+    if (count > 1) {
+        CSX_TRY(pa.alloc((size_t)((count + 255) / 256) * width));
+        CSX_TRY(pb.alloc((size_t)((count + 65535) / 65536) * width));
+    }
+    uint64_t *out = pa, *spare = pb;
     while (count > 1) {
         const int64_t next = (count + 255) / 256;
         hipLaunchKernelGGL(k_max_partials, dim3((unsigned)next, (unsigned)((width + 63) / 64)), dim3(256), 0, s, count, width,
                            in, out);
         CSX_LAUNCH_CHECK();
-        std::swap(in, out);
+        in = out;
+        std::swap(out, spare);
         count = next;
     }
-    std::vector<uint64_t> h((size_t)width);
-    CSX_HIP(hipMemcpyAsync(h.data(), in, (size_t)width * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipMemcpyAsync(h, in, (size_t)width * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+// the residual of `rows` gathered rows and the maxima of every column (host arrays, either may be null)
+static int run_residual(int32_t rows, int32_t nrhs, const int32_t *ptr, const int32_t *idx, const double *val, const double *X,
+                        const double *B, double *R, double *omega, double *rnorm) {
+    const int32_t width = 2 * nrhs;
+    const int64_t blocks = ((int64_t)rows + RES_TILE - 1) / RES_TILE;
+    DevBuf<uint64_t> pa;
+    CSX_TRY(pa.alloc((size_t)blocks * width));
+    if (R) launch_residual<true>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
+    else launch_residual<false>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
+    CSX_LAUNCH_CHECK();
+    if (!omega && !rnorm) return CSX_OK;
+    std::vector<uint64_t> h((size_t)width);
+    CSX_TRY(max_partials_host(pa, blocks, width, h.data()));
     static_assert(sizeof(double) == sizeof(uint64_t), "bit patterns of doubles");
     if (omega) std::memcpy(omega, h.data(), (size_t)nrhs * sizeof(double));
     if (rnorm) std::memcpy(rnorm, h.data() + nrhs, (size_t)nrhs * sizeof(double));

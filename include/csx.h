@@ -203,6 +203,36 @@ int csx_residual_block(csx_handle_t A, csx_handle_t X, csx_handle_t B, csx_handl
 /* the same rule on host arrays (no device); R may be B or NULL */
 int csx_residual_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, const double *x, int32_t nrhs, int trans,
                       const double *X, const double *B, double *R /* or NULL */, double *omega, double *rnorm);
+/* ---- the same for the symmetric matrix a Cholesky factorisation sees in A ----
+ * R = B - S X for row-major blocks of nrhs columns (each >= n nrhs entries), with the componentwise backward error of every
+ * column, where S is what csx_chol reads of the n x n matrix A: the stored entries with row <= column, mirrored below the
+ * diagonal.  The strictly lower entries of A are never used as values, so a matrix stored as its upper triangle, stored in
+ * full, or carrying other values below the diagonal give the same bytes.  A's columns may be unsorted and hold duplicates
+ * (summed, as a matrix sums them; csx_chol keeps the last duplicate of an entry, so the two agree only on matrices without
+ * duplicates in the upper triangle).  Reads A.p / A.i / A.x as stored AND A's cached row gather (built on demand).
+ * One order, the same on the device and on the host: for output row i and column c the terms (a, j) are
+ *     phase 1: the entries q of stored column i, in storage order, with A.i[q] <= i:  (A.x[q], A.i[q])
+ *     phase 2: the entries of row i in the row gather's order (ascending (column, storage position)) with column > i:
+ *              (value, column)
+ * and with them
+ *     r = B[i,c];    for each term:  t = a * X[j,c]      (rounded);   r = r - t   (rounded)
+ *     d = |B[i,c]|;  for each term:  u = |a| * |X[j,c]|  (rounded);   d = d + u   (rounded)
+ *     ratio[i,c] = 0 when |r| == 0 and d == 0, else |r| / d   (IEEE division; NaN and inf propagate)
+ *     omega[c] = max_i ratio[i,c],  rnorm[c] = max_i |r|      (0 for n == 0)
+ * An entry that fails its phase's test is skipped, never added as a zero.  A strictly upper entry is used twice (once per
+ * phase, in two rows), a diagonal entry once.  For a fully stored symmetric matrix with sorted columns the terms of every
+ * row are those of csx_residual_block(trans = 0), and so are the bytes.  The maxima are taken over the bit patterns of
+ * the non-negative doubles.  R == 0, R the same handle as B, omega and rnorm as in csx_residual_block.  CSX_EINVAL for
+ * m != n, a pattern-only A, nrhs < 1, short blocks, R or B the same handle as X, overlapping device ranges (R and B:
+ * anything but the same range).  n == 0 is legal; nnz == 0: R = B. */
+int csx_residual_sym_block(csx_handle_t A, csx_handle_t X, csx_handle_t B, csx_handle_t R, int32_t nrhs, double *omega,
+                           double *rnorm);
+/* the same rule on host arrays (no device; the row order is built by the call); R may be B or NULL */
+int csx_residual_sym_host(int32_t n, const int32_t *p, const int32_t *i, const double *x, int32_t nrhs, const double *X,
+                          const double *B, double *R /* or NULL */, double *omega, double *rnorm);
+/* *out = |S|_1 = max_i sum |a| over row i's terms, in the rule's order (phase 1, then phase 2; sequential, rounded), the
+ * maximum over the bit patterns.  CSX_EINVAL for m != n or a pattern-only A; 0.0 for n == 0. */
+int csx_norm1_sym(csx_handle_t A, double *out);
 /* out[i, c] = mask[c] ? X[i, c] + D[i, c] : X[i, c]   (one rounding);   dst[i, c] = src[i, c] where mask[c].
  * mask: nrhs host int32, uploaded by the call.  Blocks of rows x nrhs, row-major; out may be X or D, src and dst apart. */
 int csx_block_add_cols(csx_handle_t X, csx_handle_t D, csx_handle_t out, int64_t rows, int32_t nrhs, const int32_t *mask);
