@@ -179,6 +179,14 @@ _PROTOS = {
     "csx_add_plan_matrix": [H, _f64p, C.POINTER(H), C.POINTER(H)],
     "csx_add_plan_run": [H, _f64p, C.POINTER(H), H],
     "csx_add_plan_info": [H, C.POINTER(C.c_int64)],
+    "csx_ldl_factor": [H, _i32p, _i32p, _i32p, C.c_double, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_ldl_refactor": [H, H, C.c_double, C.POINTER(C.c_int)],
+    "csx_ldl_parts": [H, C.POINTER(H), C.POINTER(H)],
+    "csx_ldl_info": [H, C.POINTER(C.c_int64)],
+    "csx_ldl_stats": [H, _f64p],
+    "csx_ldl_window": [C.POINTER(C.c_int32)],
+    "csx_block_div_rows": [H, H, C.c_int64, C.c_int32],
+    "csx_ldl_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -249,6 +257,13 @@ def load():
         lib.csx_host_free.argtypes = [_vp]
         _lib = lib
     return _lib
+
+
+def ldl_window():
+    """entries of a column that the LDL' column kernels keep in LDS (csx_ldl.hip LDL_ACC), asked of the library; no GPU needed"""
+    out = C.c_int32(0)
+    check(load().csx_ldl_window(C.byref(out)), "csx_ldl_window")
+    return out.value
 
 
 def exported_symbols():

@@ -1765,9 +1765,8 @@ def cholsol_factor(A, order=0, exact=None):
             _csx.check(_csx.lib().csx_cholsol_set_order(h, 0), "csx_cholsol_set_order")
         return h
 
-    class _Solver(_Refinable):
+    class _Solver(_SymRefinable):
         L = N.L
-        _residual_into = staticmethod(_residual_sym_into)
 
         @property
         def symbolic(self):
@@ -1796,60 +1795,6 @@ def cholsol_factor(A, order=0, exact=None):
         def _solve_block(self, blk, trans, from_list):
             _csx.check(_csx.lib().csx_cholsol_solve(self._plan_for(not from_list), blk.handle, blk.k), "csx_cholsol_solve")
             return blk
-
-        def _operator_for(self, A_given):
-            """the context manager of the operator's handle: A_given's, or the factored / refactored matrix's"""
-            if A_given is not None:
-                if not CS_CSC(A_given) or A_given.m != n or A_given.n != n:
-                    raise ValueError("A= must be a square CSC matrix of order %d" % n)
-                if not _meta(A_given)[1]:
-                    raise TypeError("A= is a pattern-only matrix")
-                self._source = "given"
-                return _resident_handle(A_given)
-            if self._stands != dev.version:
-                raise RuntimeError("the factor was changed in place (update / downdate / cs_updown) and no longer stands for "
-                                   "the factored matrix: pass the matrix it stands for now as A=, or refactor()")
-            self._source = "factored" if self._A2 is A else "refactored"
-            return self._operator()
-
-        def backward_error(self, x, b, A=None):
-            """omega of x as a solution of S x = b per column (a float for one host vector), S the symmetric matrix in the
-            upper triangle of the operator: the factored matrix, or the values of the last successful refactor(), in A's own
-            numbering whatever the order; or A=, a square CSC matrix of order n with values (ValueError for another shape,
-            TypeError for a pattern-only one) -- pin it (cs_pin) to keep its row gather between calls.  RuntimeError for
-            A=None after update / downdate / cs_updown changed the factor: it stands for another matrix then, until the
-            next successful refactor()."""
-            return self._backward_error(x, b, False, self._operator_for(A))
-
-        def refine(self, b, maxit=5, A=None):
-            """solve, then at most maxit steps of iterative refinement against the operator (see backward_error) on the
-            columns whose backward error is above 2^-52; b is overwritten with x.  With A= a nearby matrix this is the
-            stale-factor iteration: the factor preconditions, A is solved.  _Refinable.refine's loop and result."""
-            return self._refine(b, maxit, False, self._operator_for(A))
-
-        def condest(self, A=None):
-            """an estimate of cond_1(S) = |S|_1 |S^-1|_1 of the operator (see backward_error): csx_norm1_sym times
-            Hager-Higham's estimate of the inverse's norm from single right-hand-side solves on this factor.  The estimate
-            is a lower bound, and no condition number is below 1: the result is never below 1.0 (0.0 for n = 0) -- a solve
-            divides by every pivot twice, so for a well-conditioned matrix the product can round to just under 1"""
-            with self._operator_for(A) as hA:
-                out = _csx.C.c_double(0.0)
-                _csx.check(_csx.lib().csx_norm1_sym(hA, out), "csx_norm1_sym")
-
-            def one(v, t):
-                x = v.tolist()
-                self.solve(x)
-                return np.asarray(x, dtype=np.float64)
-
-            est = _condest(out.value, one, n)
-            return est if n == 0 else max(est, 1.0)     # (a NaN stays a NaN)
-
-        def operator_info(self):
-            """source: what the last backward_error / refine / condest measured against ("factored", "refactored" or "given";
-            before the first, what A=None would take); builds: how often the refactor's values were wrapped over A's pattern
-            (once per set of values given as values rather than as a matrix)"""
-            src = self._source or ("factored" if self._A2 is A else "refactored")
-            return {"source": src, "builds": self._operator_builds}
 
         def _current(self):
             """The plan copies part of L's values (forward gather arrays, fragments): after cs_updown(F.L, ...) changed
@@ -1994,6 +1939,164 @@ def cholsol_factor(A, order=0, exact=None):
             if out is not None:
                 _write_back(bhost, out, n * out.k)
             return True
+
+    return _Solver()
+
+
+# ------------------------------------------------------------------- LDL' ----
+
+_LDL_INFO = ("n", "lnz", "levels", "launches", "pos", "neg", "perturbed", "breakdown", "kernel_us", "level_launches",
+             "run_launches", "long_columns", "window")
+
+
+def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
+    """Factor a symmetric INDEFINITE matrix once for many solves: L D L' = P A P' with unit lower triangular L on the pattern
+    of the Cholesky factor and diagonal D, 1x1 pivots in the static order of `order` (0 natural, 1 nested dissection), no
+    pivot search.  A is read as cs_chol reads it: the stored entries with row <= column, of duplicates the
+    last.  K - sigma M with sigma inside the spectrum, quasi-definite KKT systems: the route that today goes through
+    lusol_factor.  Static pivoting is not backward stable by itself: follow solve() with refine() and read backward_error().
+    perturb: a pivot with |d| < tau = perturb |S|_1 (csx_norm1_sym) is replaced by copysign(tau, d) and counted
+    (info()["perturbed"]); 0.0 (default): none, and a zero or non-finite pivot is a breakdown.
+    None for a non-CSC or non-square A, and None on breakdown.  Otherwise a solver:
+    solve(b): b a list (one system) or a dvec n-by-k block, overwritten: cs_ipvec(pinv), cs_lsolve(L), X[i,:] /= d[i]
+      (csx_block_div_rows), cs_ltsolve(L), cs_pvec(pinv), the two sweeps under lusol_factor's rule for `exact`: a list in the
+      reference's order, a block in the rounding-equal order, True / False force one order for both.
+    refactor(A2): new values on the kept analysis, A2 as for cholsol_factor's refactor: True; False with L, D and the solves
+      exactly as before on breakdown; ValueError for another pattern or length.  L.x and d are byte-equal to a fresh
+      ldlsol_factor(A2, order, perturb)'s.
+    backward_error(x, b, A=None), refine(b, maxit=5, A=None), condest(A=None), operator_info(): as on cholsol_factor (_SymRefinable).
+    inertia(): (positive, negative) pivots = eigenvalues of A by Sylvester's law (exact arithmetic; perturbed pivots keep the
+      sign they had).  logdet(): (sign, log |det A|), the sum correctly rounded.  info(): n, lnz, levels (height levels of the
+      elimination tree), launches (numeric launches of the last run: level_launches of the wave-per-column kernel +
+      run_launches of the one-workgroup walker of narrow levels), pos, neg, perturbed, breakdown (smallest broken column of the
+      last run, -1 none), kernel_us, long_columns (columns of the last run that the kernels updated in place: longer than the LDS `window`), min_abs_d,
+      max_abs_d, max_abs_l.  factors: .L (a pinned `cs`, unit diagonal stored) and .D (a dvec); symbolic: S."""
+    if not CS_CSC(A) or A.m != A.n:
+        return None
+    perturb = float(perturb)
+    if not perturb >= 0.0:
+        raise ValueError("ldlsol_factor: perturb must be >= 0")
+    S = cs_schol(order, A, _arrays=True)
+    if S is None:
+        return None
+    n = A.n
+    pinv = None if S.pinv is None else _csx.i32(S.pinv)
+    lib = _csx.lib()
+
+    def threshold(hA):
+        if perturb == 0.0:
+            return 0.0
+        out = _csx.C.c_double(0.0)
+        _csx.check(lib.csx_norm1_sym(hA, out), "csx_norm1_sym")
+        return perturb * out.value
+
+    hF, ok = _csx.new_handle(), _csx.C.c_int(0)
+    with _Resident(A) as dA:
+        _csx.check(lib.csx_ldl_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(pinv),
+                                      threshold(dA.handle), hF, ok), "csx_ldl_factor")
+    if not ok.value:
+        return None
+    hL, hd = _csx.new_handle(), _csx.new_handle()
+    _csx.check(lib.csx_ldl_parts(hF, hL, hd), "csx_ldl_parts")
+    # L and d are the factor's (borrowed handles): the wrappers free the plans cached on L and the factor, never L or d
+    N = csn()
+    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
+    dev = N.L._dev
+    dev._fin.detach()
+    dev._fin = weakref.finalize(dev, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), dev.plans, hF)
+    N.D = dvec(n, 1, _handle=hd)
+    N.D._fin.detach()
+    N.D._keep = dev
+    N.U, N.pinv, N.B = None, None, None
+    hp, keep_p = _perm_handle(pinv, n)
+
+    class _Solver(_SymRefinable):
+        factors = N
+
+        @property
+        def symbolic(self):
+            for name in ("parent", "cp", "pinv"):
+                v = getattr(S, name)
+                if v is not None and not isinstance(v, list):
+                    setattr(S, name, v.tolist())
+            return S
+
+        def __init__(self):
+            self._dev = dev                          # keeps L, d and the factor alive
+            self._fin = weakref.finalize(self, _csx.free, keep_p)
+            self._A2, self._stands, self._source = A, dev.version, None
+            self._refine_init(A, n)
+
+        def _solve_block(self, blk, trans, from_list):
+            return self._block(blk, exact if exact is not None else from_list)
+
+        def _block(self, blk, in_exact_order):
+            k = blk.k
+            x = blk
+            if pinv is not None:
+                x = dvec(n, k)
+                _csx.check(lib.csx_permute_vec(hp, blk.handle, x.handle, n, k, 1), "csx_permute_vec")
+            p1, p2 = _plan(dev, TRI_L), _plan(dev, TRI_LT)
+            try:
+                for plan in (p1, p2):
+                    _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+                _csx.check(lib.csx_tri_solve(p1, x.handle, k), "csx_tri_solve")
+                _csx.check(lib.csx_block_div_rows(x.handle, hd, n, k), "csx_block_div_rows")
+                _csx.check(lib.csx_tri_solve(p2, x.handle, k), "csx_tri_solve")
+            finally:
+                lib.csx_tri_set_order(p1, 1)         # (shared with the list-level cs_lsolve / cs_ltsolve on this factor)
+                lib.csx_tri_set_order(p2, 1)
+            if pinv is not None:
+                _csx.check(lib.csx_permute_vec(hp, x.handle, blk.handle, n, k, 0), "csx_permute_vec")
+            return blk
+
+        def solve(self, b):
+            db, bhost = _vec_in(b, n, "b")
+            self._block(db, exact if exact is not None else not isinstance(b, dvec))
+            _write_back(bhost, db, n * db.k)
+            return True
+
+        def refactor(self, A2):
+            A2 = _refactor_input(A, A2)
+            ok = _csx.C.c_int(0)
+            tau = 0.0
+            if perturb > 0.0:                        # |S|_1 of the operand
+                if isinstance(A2, cs):
+                    with _Resident(A2) as d2:
+                        tau = threshold(d2.handle)
+                else:
+                    with _Resident(A) as dA:
+                        h2 = _wrap_values(dA, A2)
+                        try:
+                            tau = threshold(h2)
+                        finally:
+                            _csx.free(h2)
+            _refactor_call(A2, lambda h2: lib.csx_ldl_refactor(hF, h2, tau, ok), ok)
+            if ok.value == 1:
+                _refactored(N.L, dev)
+                self._A2, self._stands, self._source = A2, dev.version, None
+                self._operator_changed()
+            return ok.value == 1
+
+        def info(self):
+            raw = (_csx.C.c_int64 * len(_LDL_INFO))()
+            st = (_csx.C.c_double * 3)()
+            _csx.check(lib.csx_ldl_info(hF, raw), "csx_ldl_info")
+            _csx.check(lib.csx_ldl_stats(hF, st), "csx_ldl_stats")
+            out = {name: int(v) for name, v in zip(_LDL_INFO, raw)}
+            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
+            return out
+
+        def inertia(self):
+            """(positive, negative) pivots of the committed factor"""
+            i = self.info()
+            return i["pos"], i["neg"]
+
+        def logdet(self):
+            """(sign, log |det A|): the sign of the product of the pivots, and sum_j log |d_j| correctly rounded (math.fsum)"""
+            d = N.D.numpy().reshape(-1)
+            sign = -1.0 if int(np.sum(d < 0.0)) % 2 else 1.0
+            return sign, math.fsum(np.log(np.abs(d)).tolist())
 
     return _Solver()
 
@@ -2173,20 +2276,27 @@ def _refactored(M, dev):
         M._x[:nnz] = x[:nnz].tolist()
 
 
+def _wrap_values(dev, values):
+    """a NEW handle (the caller frees it) of the pattern of the device matrix dev with the values of the dvec `values` in its
+    storage order: nothing is copied, dev and values must outlive it"""
+    C = _csx.C
+    m, n, nnz, _ = dev.info()
+    dp, di, dx = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _csx.check(_csx.lib().csx_csc_ptrs(dev.handle, dp, di, dx), "csx_csc_ptrs")
+    h = _csx.new_handle()
+    _csx.check(_csx.lib().csx_csc_wrap(m, n, nnz, dp, di, C.c_void_p(values.device_ptr()), h), "csx_csc_wrap")
+    return h
+
+
 def _refactor_norm(A, A2):
     """cs_norm of the matrix a refactor installed, for condest(): A2 when it is a `cs`; else A's pattern with the values A2
     (a dvec in A's storage order) -- column sums on the device over A's pattern, nothing copied to the host"""
     if isinstance(A2, cs):
         return cs_norm(A2)
-    C = _csx.C
     with _Resident(A) as dA:
-        m, n, nnz, _ = dA.info()
-        dp, di, dx = C.c_void_p(), C.c_void_p(), C.c_void_p()
-        _csx.check(_csx.lib().csx_csc_ptrs(dA.handle, dp, di, dx), "csx_csc_ptrs")
-        h = _csx.new_handle()
-        _csx.check(_csx.lib().csx_csc_wrap(m, n, nnz, dp, di, C.c_void_p(A2.device_ptr()), h), "csx_csc_wrap")
+        h = _wrap_values(dA, A2)
         try:
-            out = C.c_double(0.0)
+            out = _csx.C.c_double(0.0)
             _csx.check(_csx.lib().csx_norm1(h, out), "csx_norm1")
         finally:
             _csx.free(h)
@@ -2224,14 +2334,9 @@ class _Refinable(object):
             return
         if self._op["handle"] is None:
             # kept until the next successful refactor: the row gather cached on it is built once per set of values
-            A, C = self._rA, _csx.C
+            A = self._rA
             dev = A._dev if A._dev is not None else _DevMatrix(_upload(A))
-            m, n, nnz, _ = dev.info()
-            dp, di, dx = C.c_void_p(), C.c_void_p(), C.c_void_p()
-            _csx.check(_csx.lib().csx_csc_ptrs(dev.handle, dp, di, dx), "csx_csc_ptrs")
-            h = _csx.new_handle()
-            _csx.check(_csx.lib().csx_csc_wrap(m, n, nnz, dp, di, C.c_void_p(A2.device_ptr()), h), "csx_csc_wrap")
-            self._op["handle"], self._op["keep"] = h, (dev, A2)
+            self._op["handle"], self._op["keep"] = _wrap_values(dev, A2), (dev, A2)
             self._operator_builds += 1
         yield self._op["handle"].value
 
@@ -2299,6 +2404,71 @@ class _Refinable(object):
                 w, rn = np.where(accept, wc, w), np.where(accept, rnc, rn)
         _write_back(bhost, db, n * k)
         return {"omega0": w0, "omega": w, "rnorm": rn, "steps": steps, "solves": solves}
+
+
+class _SymRefinable(_Refinable):
+    """backward_error / refine / condest / operator_info of the solvers of a SYMMETRIC matrix held in the upper triangle
+    (cholsol_factor, ldlsol_factor), measured with csx_residual_sym_block against the factored matrix, the
+    last refactor's values, or A=.  The solver sets, beside _refine_init(A, n): _dev (the factor's _DevMatrix: its version moves
+    when the values change in place), _A2 (the matrix the factor stands for), _stands (the version at which it does) and
+    _source (None), and gives solve(list)."""
+
+    _residual_into = staticmethod(_residual_sym_into)
+
+    def _operator_for(self, A_given):
+        """the context manager of the operator's handle: A_given's, or the factored / refactored matrix's"""
+        if A_given is not None:
+            if not CS_CSC(A_given) or A_given.m != self._rn or A_given.n != self._rn:
+                raise ValueError("A= must be a square CSC matrix of order %d" % self._rn)
+            if not _meta(A_given)[1]:
+                raise TypeError("A= is a pattern-only matrix")
+            self._source = "given"
+            return _resident_handle(A_given)
+        if self._stands != self._dev.version:
+            raise RuntimeError("the factor was changed in place (update / downdate / cs_updown) and no longer stands for "
+                               "the factored matrix: pass the matrix it stands for now as A=, or refactor()")
+        self._source = "factored" if self._A2 is self._rA else "refactored"
+        return self._operator()
+
+    def backward_error(self, x, b, A=None):
+        """omega of x as a solution of S x = b per column (a float for one host vector), S the symmetric matrix in the
+        upper triangle of the operator: the factored matrix, or the values of the last successful refactor(), in A's own
+        numbering whatever the order; or A=, a square CSC matrix of order n with values (ValueError for another shape,
+        TypeError for a pattern-only one) -- pin it (cs_pin) to keep its row gather between calls.  RuntimeError for
+        A=None after update / downdate / cs_updown changed the factor: it stands for another matrix then, until the
+        next successful refactor()."""
+        return self._backward_error(x, b, False, self._operator_for(A))
+
+    def refine(self, b, maxit=5, A=None):
+        """solve, then at most maxit steps of iterative refinement against the operator (see backward_error) on the
+        columns whose backward error is above 2^-52; b is overwritten with x.  With A= a nearby matrix this is the
+        stale-factor iteration: the factor preconditions, A is solved.  _Refinable.refine's loop and result."""
+        return self._refine(b, maxit, False, self._operator_for(A))
+
+    def condest(self, A=None):
+        """an estimate of cond_1(S) = |S|_1 |S^-1|_1 of the operator (see backward_error): csx_norm1_sym times
+        Hager-Higham's estimate of the inverse's norm from single right-hand-side solves on this factor.  The estimate
+        is a lower bound, and no condition number is below 1: the result is never below 1.0 (0.0 for n = 0) -- a solve
+        divides by every pivot twice, so for a well-conditioned matrix the product can round to just under 1"""
+        with self._operator_for(A) as hA:
+            out = _csx.C.c_double(0.0)
+            _csx.check(_csx.lib().csx_norm1_sym(hA, out), "csx_norm1_sym")
+
+        def one(v, t):
+            x = v.tolist()
+            self.solve(x)
+            return np.asarray(x, dtype=np.float64)
+
+        n = self._rn
+        est = _condest(out.value, one, n)
+        return est if n == 0 else max(est, 1.0)     # (a NaN stays a NaN)
+
+    def operator_info(self):
+        """source: what the last backward_error / refine / condest measured against ("factored", "refactored" or "given";
+        before the first, what A=None would take); builds: how often the refactor's values were wrapped over A's pattern
+        (once per set of values given as values rather than as a matrix)"""
+        src = self._source or ("factored" if self._A2 is self._rA else "refactored")
+        return {"source": src, "builds": self._operator_builds}
 
 
 def lusol_factor(A, order=0, tol=1.0, exact=None):

@@ -92,6 +92,20 @@ __global__ __launch_bounds__(256) void k_chol_winner(int32_t n, const int32_t *_
     }
 }
 
+// the entry map alone, for the other factorisations on the Cholesky pattern (csx_ldl.hip): win (lnz slots) <- the entry of A
+// that lands in each slot of L, -1 for fill; *bad (device) is set when an upper entry of A has no slot.  pinv: device or null.
+// Queued on the context's stream.
+int chol_entry_map(const Csc *A, const int32_t *pinv, const int32_t *Lp, const int32_t *Li, int32_t lnz, int32_t *win, int *bad) {
+    hipStream_t s = ctx().stream;
+    CSX_HIP(hipMemsetAsync(win, 0xff, (size_t)lnz * sizeof(int32_t), s));
+    CSX_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    if (A->n > 0)
+        hipLaunchKernelGGL(k_chol_winner, dim3((unsigned)(((int64_t)A->n + 3) / 4)), dim3(256), 0, s, A->n, A->p, A->i, pinv, Lp, Li,
+                           win, bad);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
+
 // ---- one column ---------------------------------------------------------------------------------
 // acc_v / acc_r: wave-private LDS (CH_ACC doubles / ints).  Columns longer than CH_ACC keep their
 // sums in Lx itself (global), the row search then runs on Li in global memory.

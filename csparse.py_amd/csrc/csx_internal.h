@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR };
 
 struct Csc;
 
@@ -219,6 +219,8 @@ struct CholAnalysis;  // csx_chol.hip
 struct CholRefPlan;   // csx_chol_refactor.hip
 void destroy(CholAnalysis *p);
 void destroy(CholRefPlan *p);
+struct LdlFactor;     // csx_ldl.hip
+void destroy(LdlFactor *p);
 
 struct Object {
     Kind kind = K_FREE;
@@ -411,6 +413,14 @@ int chol_analysis_refactor(CholAnalysis *An, const Csc *L, const double *Ax, dou
 void chol_analysis_info(const CholAnalysis *An, int32_t *info);   // info[1..5] of csx_chol_refactor
 // Lx[q] = win[q] >= 0 ? Ax[win[q]] : 0 over the lnz slots of L (csx_chol_refactor.hip)
 int chol_scatter(int64_t lnz, const int32_t *win, const double *Ax, double *Lx);
+// csx_chol.hip: the entry map alone (k_chol_winner): win[q] = the entry of A that lands in slot q of L, -1 for fill; *bad
+// (device) set when an upper entry of A has no slot; pinv device or null; queued on the context's stream
+int chol_entry_map(const Csc *A, const int32_t *pinv, const int32_t *Lp, const int32_t *Li, int32_t lnz, int32_t *win, int *bad);
+// csx_cholsym.hip: the pattern of chol(P A P') under the caller's S (host parent, cp, pinv) with its row view; CSX_EINVAL when S
+// is not A's
+int chol_symbolic_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t **Lp_out,
+                         int32_t **Li_out, DevBuf<int32_t> *row_ptr_out, DevBuf<int32_t> *row_col_out, DevBuf<int32_t> *row_pos_out,
+                         int32_t *cp_host_out);
 // csx_cholsym.hip: the row view of a factor's pattern (col[q] = the column of entry q)
 int chol_row_view(int32_t n, int64_t lnz, const uint32_t *col, const int32_t *Li, DevBuf<int32_t> *row_ptr, DevBuf<int32_t> *row_col,
                   DevBuf<int32_t> *row_pos);

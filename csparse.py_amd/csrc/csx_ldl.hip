@@ -1,0 +1,464 @@
+// LDL' with static 1x1 pivots for symmetric indefinite matrices (the definition is the comment of
+// csx_ldl_factor in include/csx.h).  L D L' = C = upper(P A P') on the pattern of the Cholesky factor: without a pivot search
+// the pattern of L is cs_chol's, so the symbolic step (chol_symbolic_device), the entry map (chol_entry_map) and the scatter
+// (chol_scatter) are csx_chol's own; the numeric kernels here are the left-looking column of chol_column with d[k] carried
+// beside L(j,k), no square root, and the pivot rule (perturbation below tau, breakdown at 0 or a non-finite pivot).
+//   k_ldl_level   one wave per column of a height level of the elimination tree
+//   k_ldl_run     one workgroup walks a run of levels of at most LDL_WAVES columns each (a chain), a barrier per level
+//   k_ldl_stats   inertia, min / max |d|, max |l| off the diagonal in one pass
+//   k_block_div_rows  X[i, :] /= d[i], the D step of a solve
+// Every sum is updated in ascending k by one wave, one update after the other: L.x and d are byte-equal to csx_ldl_host.
+// A factor or refactor runs into scratch arrays and is committed only when no column broke down.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "csx_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace csx {
+
+constexpr int LDL_ACC = 512;    // column entries kept in LDS per wave (24 KB a workgroup); longer columns are updated in place in global memory
+constexpr int LDL_WAVES = 4;    // waves per workgroup (csx_chol.hip's CH_WAVES)
+constexpr int LDL_NONE = 0x7fffffff;
+
+__device__ __forceinline__ int32_t ldl_find_row(const int32_t *rows, int32_t len, int32_t r) {
+    int32_t lo = 0, hi = len - 1;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (rows[mid] < r) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Column j of L and d[j].  On entry Lx[Lp[j] ..] holds C(:, j) in the slots of L (0.0 in fill slots), and every column k < j
+// with L(j,k) in the pattern is finished (L(:,k) and d[k] final).  acc_v / acc_r: wave-private LDS (LDL_ACC entries).
+// flags[0]: the smallest broken column (atomicMin), flags[1]: perturbed pivots, flags[2]: columns that took the in-place path
+// (integer atomicAdd both).
+__device__ __forceinline__ void ldl_column(int32_t j, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li, double *Lx,
+                                           double *d, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
+                                           const int32_t *__restrict__ row_pos, double tau, double *acc_v, int32_t *acc_r,
+                                           int lane, int *flags) {
+    const int32_t base = Lp[j], len = Lp[j + 1] - base;
+    const bool in_lds = len <= LDL_ACC;
+    if (in_lds) {
+        for (int32_t t = lane; t < len; t += 64) {
+            acc_v[t] = Lx[base + t];
+            acc_r[t] = Li[base + t];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal L(j,j)
+    // Updates are applied in order, but fetched eight at a time (chol_column): lane u reads the descriptor of update u --
+    // position of L(j,k), end of column k, w = L(j,k) d[k] -- and the heads of the eight columns are requested together.
+    constexpr int UQ = 8;
+    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
+        int32_t posq = 0, kendq = 0;
+        double wq = 0.0;
+        if (lane < UQ && q0 + lane < qe) {
+            const int32_t kq = row_col[q0 + lane];
+            posq = row_pos[q0 + lane];
+            kendq = Lp[kq + 1];
+            wq = Lx[posq] * d[kq];
+        }
+        int32_t pos_[UQ], kend_[UQ], r_[UQ];
+        double w_[UQ], v_[UQ];
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            pos_[u] = __builtin_amdgcn_readlane(posq, u);
+            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
+            w_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wq), u),
+                                     __builtin_amdgcn_readlane(__double2loint(wq), u));
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            const int32_t p = pos_[u] + lane;
+            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
+            r_[u] = Li[pp];
+            v_[u] = Lx[pp];
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            if (pos_[u] + lane < kend_[u]) {
+                const double v = v_[u] * w_[u];
+                if (in_lds) {
+                    const int32_t t = ldl_find_row(acc_r, len, r_[u]);
+                    acc_v[t] = acc_v[t] - v;
+                } else {
+                    const int32_t t = base + ldl_find_row(Li + base, len, r_[u]);
+                    Lx[t] = Lx[t] - v;
+                }
+            }
+            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
+                const double v = Lx[p] * w_[u];
+                if (in_lds) {
+                    const int32_t t = ldl_find_row(acc_r, len, Li[p]);
+                    acc_v[t] = acc_v[t] - v;
+                } else {
+                    const int32_t t = base + ldl_find_row(Li + base, len, Li[p]);
+                    Lx[t] = Lx[t] - v;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
+        }
+    }
+    double dj = in_lds ? acc_v[0] : Lx[base];
+    const bool small = tau > 0.0 && fabs(dj) < tau;
+    if (small) dj = copysign(tau, dj);
+    if (lane == 0) {
+        if (small) atomicAdd(flags + 1, 1);
+        if (!in_lds) atomicAdd(flags + 2, 1);
+        if (dj == 0.0 || !isfinite(dj)) atomicMin(flags, j);
+        d[j] = dj;
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int32_t t = lane; t < len; t += 64) {
+        const double v = in_lds ? acc_v[t] : Lx[base + t];
+        Lx[base + t] = t == 0 ? 1.0 : v / dj;
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+#define LDL_SHARED                                  \
+    __shared__ double s_acc_v[LDL_WAVES][LDL_ACC];  \
+    __shared__ int32_t s_acc_r[LDL_WAVES][LDL_ACC];
+
+// one wave per column of a level
+__global__ __launch_bounds__(64 * LDL_WAVES) void k_ldl_level(const int32_t *__restrict__ cols, int32_t count,
+                                                             const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
+                                                             double *Lx, double *d, const int32_t *__restrict__ row_ptr,
+                                                             const int32_t *__restrict__ row_col,
+                                                             const int32_t *__restrict__ row_pos, double tau, int *flags) {
+    LDL_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * LDL_WAVES + w;
+    if (c >= count) return;
+    ldl_column(cols[c], Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, s_acc_v[w], s_acc_r[w], lane, flags);
+}
+
+// One workgroup walks the levels [l0, l1), each of at most LDL_WAVES columns: wave w takes column w of the level, a barrier
+// between levels makes the finished columns visible to the next.  The trip counts are the level pointers, the same for every
+// wave, so every wave reaches every barrier.
+__global__ __launch_bounds__(64 * LDL_WAVES) void k_ldl_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
+                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Lp,
+                                                           const int32_t *__restrict__ Li, double *Lx, double *d,
+                                                           const int32_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ row_col,
+                                                           const int32_t *__restrict__ row_pos, double tau, int *flags) {
+    LDL_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int32_t l = l0; l < l1; l++) {
+        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
+        if (w < cnt) ldl_column(cols[b + w], Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, s_acc_v[w], s_acc_r[w], lane, flags);
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ uint64_t abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
+
+// One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|
+// off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (csx_residual.hip's rule: a NaN ranks above inf).
+__global__ __launch_bounds__(256) void k_ldl_stats(int32_t n, const int32_t *__restrict__ Lp, const double *__restrict__ Lx,
+                                                   const double *__restrict__ d, unsigned long long *st) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (j >= n) return;
+    uint64_t lmax = 0;
+    for (int32_t p = Lp[j] + 1 + lane; p < Lp[j + 1]; p += 64) {
+        const uint64_t v = abs_bits(Lx[p]);
+        lmax = v > lmax ? v : lmax;
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t v = (uint64_t)__shfl_xor((unsigned long long)lmax, off);
+        lmax = v > lmax ? v : lmax;
+    }
+    if (lane == 0) {
+        const double dj = d[j];
+        if (dj > 0.0) atomicAdd(st + 0, 1ull);
+        if (dj < 0.0) atomicAdd(st + 1, 1ull);
+        atomicMin(st + 2, (unsigned long long)abs_bits(dj));
+        atomicMax(st + 3, (unsigned long long)abs_bits(dj));
+        if (lmax) atomicMax(st + 4, (unsigned long long)lmax);
+    }
+}
+
+// X[i, c] = X[i, c] / d[i] over a row-major rows x nrhs block; PAIR: two columns per thread through 16-byte accesses
+// (nrhs even and X 16-byte aligned: a pair never straddles a row)
+template <bool PAIR>
+__global__ __launch_bounds__(256) void k_block_div_rows(double *__restrict__ X, const double *__restrict__ d, int64_t rows,
+                                                        int32_t nrhs) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t total = rows * nrhs;
+    if (PAIR) {
+        double2 *X2 = reinterpret_cast<double2 *>(X);
+        for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; 2 * e < total; e += stride) {
+            const double di = d[(2 * e) / nrhs];
+            double2 v = X2[e];
+            v.x = v.x / di;
+            v.y = v.y / di;
+            X2[e] = v;
+        }
+    } else {
+        for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) X[e] = X[e] / d[e / nrhs];
+    }
+}
+
+struct LdlFactor {
+    int32_t n = 0, anz = 0, lnz = 0;
+    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
+    DevBuf<int32_t> rp, rc, rpos;           // row view of L (chol_symbolic_device)
+    DevBuf<int32_t> win;                    // the entry map
+    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the elimination tree: columns by level, ascending inside one
+    std::vector<int32_t> level_ptr_h;
+    csx_handle_t hL = 0, hd = 0;            // the committed factor: owned here, lent out by csx_ldl_parts
+    DevBuf<double> Lx, dd;                  // scratch of a run: committed only when no column broke down
+    DevBuf<int> flags;                      // [0] smallest broken column, [1] perturbed pivots, [2] columns updated in place
+    DevBuf<unsigned long long> stats;       // k_ldl_stats
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    // csx_ldl_info / csx_ldl_stats
+    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0;   // long_cols: counted by the kernels of the last run
+    int64_t pos = 0, neg = 0, perturbed = 0, breakdown = -1, kernel_us = 0;
+    double min_d = 0.0, max_d = 0.0, max_l = 0.0;
+    LdlFactor() = default;
+    LdlFactor(const LdlFactor &) = delete;
+    LdlFactor &operator=(const LdlFactor &) = delete;
+    ~LdlFactor() {
+        if (hL) (void)csx_free(hL);
+        if (hd) (void)csx_free(hd);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+    }
+};
+
+void destroy(LdlFactor *F) { delete F; }
+
+// height levels: a leaf is at level 0, a column one above its highest child (parent[j] > j: one ascending pass)
+static void ldl_levels(int32_t n, const int32_t *parent, std::vector<int32_t> &ptr, std::vector<int32_t> &cols) {
+    std::vector<int32_t> level((size_t)n, 0);
+    int32_t nlev = 0;
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t up = parent[j];
+        if (up >= 0) level[(size_t)up] = std::max(level[(size_t)up], level[(size_t)j] + 1);
+        nlev = std::max(nlev, level[(size_t)j] + 1);
+    }
+    ptr.assign((size_t)nlev + 1, 0);
+    for (int32_t j = 0; j < n; j++) ptr[(size_t)level[(size_t)j] + 1]++;
+    for (int32_t l = 0; l < nlev; l++) ptr[(size_t)l + 1] += ptr[(size_t)l];
+    cols.resize((size_t)n);
+    std::vector<int32_t> next(ptr.begin(), ptr.end() - 1);
+    for (int32_t j = 0; j < n; j++) cols[(size_t)next[(size_t)level[(size_t)j]]++] = j;
+}
+
+// The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
+// into L.x / d when no column broke down.  *ok: 1 committed, 0 breakdown (L, d untouched).  Synchronises.
+static int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
+    hipStream_t s = ctx().stream;
+    Csc *L = csc(F->hL);
+    Vec *dv = vec(F->hd);
+    if (!L || !dv || !L->x || L->nnz != F->lnz || dv->len != F->n) return CSX_EINVAL;
+    const int32_t n = F->n;
+    F->launches = F->level_launches = F->run_launches = 0;
+    const int hinit[3] = {LDL_NONE, 0, 0};
+    const unsigned long long sinit[5] = {0ull, 0ull, ~0ull, 0ull, 0ull};
+    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(chol_scatter(F->lnz, F->win, Ax, F->Lx));
+    const std::vector<int32_t> &lp = F->level_ptr_h;
+    const int32_t nlev = (int32_t)lp.size() - 1;
+    for (int32_t l = 0; l < nlev;) {
+        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
+        if (cnt > LDL_WAVES) {
+            hipLaunchKernelGGL(k_ldl_level, dim3((unsigned)((cnt + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, s,
+                               F->level_cols + lp[(size_t)l], cnt, L->p, L->i, F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(),
+                               F->rpos.get(), tau, F->flags.get());
+            F->level_launches++;
+            l++;
+            continue;
+        }
+        int32_t e = l + 1;   // a run of narrow levels: one workgroup, no way back to the host
+        while (e < nlev && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
+        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), l, e, L->p, L->i,
+                           F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(), F->rpos.get(), tau, F->flags.get());
+        F->run_launches++;
+        l = e;
+    }
+    F->launches = F->level_launches + F->run_launches;
+    if (n > 0)
+        hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, F->Lx.get(), F->dd.get(),
+                           F->stats.get());
+    (void)hipEventRecord(F->ev_b, s);
+    int hflags[3] = {LDL_NONE, 0, 0};
+    unsigned long long hst[5] = {0, 0, 0, 0, 0};
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("csx_ldl: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(s);
+        return CSX_ERUNTIME;
+    }
+    float ms = 0.0f;
+    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    F->perturbed = hflags[1];
+    F->long_cols = hflags[2];
+    F->breakdown = hflags[0] == LDL_NONE ? -1 : hflags[0];
+    *ok = F->breakdown < 0 ? 1 : 0;
+    if (!*ok) return CSX_OK;
+    F->pos = (int64_t)hst[0];
+    F->neg = (int64_t)hst[1];
+    if (n == 0) hst[2] = 0;
+    std::memcpy(&F->min_d, &hst[2], 8);
+    std::memcpy(&F->max_d, &hst[3], 8);
+    std::memcpy(&F->max_l, &hst[4], 8);
+    if (F->lnz) CSX_HIP(hipMemcpyAsync(L->x, F->Lx.get(), (size_t)F->lnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n) CSX_HIP(hipMemcpyAsync(dv->d, F->dd.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    L->rows.reset();    // (copies of the old values)
+    L->tiled.reset();
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+static int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, LdlFactor *F) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = A->n;
+    F->n = n;
+    F->anz = A->nnz;
+    F->lnz = cp[n];
+    if (cp[0] != 0 || F->lnz < n) return CSX_EINVAL;
+    if (!A->trusted) CSX_TRY(csc_validate(A));
+    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
+    CSX_TRY(F->flags.alloc(3));
+    CSX_TRY(F->stats.alloc(5));
+    CSX_HIP(hipEventCreate(&F->ev_a));
+    CSX_HIP(hipEventCreate(&F->ev_b));
+    std::unique_ptr<Csc> L(new Csc());
+    L->m = L->n = n;
+    L->nnz = F->lnz;
+    if (n == 0) {
+        CSX_TRY(dalloc(&L->p, 1));
+        CSX_HIP(hipMemsetAsync(L->p, 0, sizeof(int32_t), s));
+        CSX_TRY(dalloc(&L->i, 0));
+        F->level_ptr_h.assign(1, 0);
+    } else {
+        CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &F->rp, &F->rc, &F->rpos, nullptr));   // (checks S and pinv)
+        std::vector<int32_t> cols;
+        ldl_levels(n, parent, F->level_ptr_h, cols);
+        CSX_TRY(upload(F->level_cols, cols));
+        CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+        CSX_TRY(F->win.alloc((size_t)F->lnz));
+        DevBuf<int32_t> d_pinv;
+        if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
+        CSX_TRY(chol_entry_map(A, pinv ? d_pinv.get() : nullptr, L->p, L->i, F->lnz, F->win, F->flags));
+        int bad = 0;
+        CSX_HIP(hipMemcpyAsync(&bad, F->flags.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));   // (cols, level_ptr_h and pinv have landed too)
+        if (bad) {
+            set_error("csx_ldl_factor: an upper entry of A has no slot in L (S is not A's)");
+            return CSX_EINVAL;
+        }
+    }
+    CSX_TRY(dalloc(&L->x, (size_t)F->lnz));
+    CSX_TRY(F->Lx.alloc((size_t)F->lnz));
+    CSX_TRY(F->dd.alloc((size_t)n));
+    std::unique_ptr<Vec> dv(new Vec());
+    dv->len = n;
+    CSX_TRY(dmalloc(&dv->d, (size_t)n * sizeof(double)));
+    F->hL = put(K_CSC, L.release());
+    F->hd = put(K_VEC, dv.release());
+    return CSX_OK;
+}
+
+}  // namespace csx
+
+using namespace csx;
+
+extern "C" int csx_ldl_factor(csx_handle_t hA, const int32_t *parent, const int32_t *cp, const int32_t *pinv, double tau,
+                              csx_handle_t *out, int *ok) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !out || !ok || !A->x || A->m != A->n || !cp || (A->n > 0 && !parent) || !(tau >= 0.0)) return CSX_EINVAL;
+    *out = 0;
+    *ok = 0;
+    std::unique_ptr<LdlFactor> F(new LdlFactor());
+    CSX_TRY(ldl_build(A, parent, cp, pinv, F.get()));
+    CSX_TRY(ldl_run(F.get(), A->x, tau, ok));
+    if (*ok) *out = put(K_LDLFACTOR, F.release());
+    return CSX_OK;
+}
+
+extern "C" int csx_ldl_refactor(csx_handle_t h, csx_handle_t hA2, double tau, int *ok) {
+    CSX_TRY(require_ready());
+    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
+    if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
+    *ok = -1;
+    const double *x2 = nullptr;
+    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
+    if (!x2) {
+        set_error("csx_ldl_refactor: A2 does not have the pattern (or the length) of the factored matrix");
+        return CSX_EINVAL;   // nothing changes
+    }
+    return ldl_run(F, x2, tau, ok);
+}
+
+extern "C" int csx_ldl_parts(csx_handle_t h, csx_handle_t *L, csx_handle_t *d) {
+    CSX_TRY(require_ready());
+    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
+    if (!F || !L || !d) return CSX_EINVAL;
+    *L = F->hL;
+    *d = F->hd;
+    return CSX_OK;
+}
+
+extern "C" int csx_ldl_info(csx_handle_t h, int64_t *info) {
+    CSX_TRY(require_ready());
+    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
+    if (!F || !info) return CSX_EINVAL;
+    info[0] = F->n;
+    info[1] = F->lnz;
+    info[2] = (int64_t)F->level_ptr_h.size() - 1;
+    info[3] = F->launches;
+    info[4] = F->pos;
+    info[5] = F->neg;
+    info[6] = F->perturbed;
+    info[7] = F->breakdown;
+    info[8] = F->kernel_us;
+    info[9] = F->level_launches;
+    info[10] = F->run_launches;
+    info[11] = F->long_cols;
+    info[12] = LDL_ACC;
+    return CSX_OK;
+}
+
+extern "C" int csx_ldl_window(int32_t *entries) {   // (no device needed)
+    if (!entries) return CSX_EINVAL;
+    *entries = LDL_ACC;
+    return CSX_OK;
+}
+
+extern "C" int csx_ldl_stats(csx_handle_t h, double *out) {
+    CSX_TRY(require_ready());
+    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
+    if (!F || !out) return CSX_EINVAL;
+    out[0] = F->min_d;
+    out[1] = F->max_d;
+    out[2] = F->max_l;
+    return CSX_OK;
+}
+
+extern "C" int csx_block_div_rows(csx_handle_t hX, csx_handle_t hd, int64_t rows, int32_t nrhs) {
+    CSX_TRY(require_ready());
+    Vec *X = vec(hX), *d = vec(hd);
+    if (!X || !d || rows < 0 || nrhs < 1 || d->len < rows || X->len / nrhs < rows) return CSX_EINVAL;
+    const int64_t total = rows * nrhs;
+    if (total == 0) return CSX_OK;
+    const bool pair = nrhs % 2 == 0 && ((uintptr_t)X->d & 15) == 0;
+    const int64_t items = pair ? total / 2 : total;
+    const int64_t most = (int64_t)std::max(ctx().cus, 1) * 16;
+    const unsigned blocks = (unsigned)std::min<int64_t>((items + 255) / 256, most);
+    if (pair) hipLaunchKernelGGL(k_block_div_rows<true>, dim3(blocks), dim3(256), 0, ctx().stream, (double *)X->d, (const double *)d->d, rows, nrhs);
+    else hipLaunchKernelGGL(k_block_div_rows<false>, dim3(blocks), dim3(256), 0, ctx().stream, (double *)X->d, (const double *)d->d, rows, nrhs);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}

@@ -863,6 +863,57 @@ int csx_add_plan_matrix(csx_handle_t plan, const double *coef, const csx_handle_
 int csx_add_plan_run(csx_handle_t plan, const double *coef, const csx_handle_t *X, csx_handle_t out);
 int csx_add_plan_info(csx_handle_t plan, int64_t *info);
 
+/* ---- LDL' with static 1x1 pivots: symmetric indefinite matrices (ldlsol_factor) ------------------------
+ * Definition.  A is a square CSC matrix with values, pinv a permutation or NULL, S = (parent, cp) the symbolic Cholesky analysis
+ * of P A P' (csx_schol).  C = upper(P A P') exactly as cs_chol reads it: the stored entries with row <= column, of duplicates the
+ * last, lower entries ignored.  L has the pattern of the Cholesky factor (L.p = cp; rows ascending, the diagonal first in each
+ * column) and an EXPLICIT unit diagonal; d is a vector of n doubles; L diag(d) L' = C up to rounding.  No pivot search: the
+ * order is the caller's, the pivots are 1x1.
+ * Values, compiled without contraction on host and device:
+ *   for every column j (any order that puts descendants in the elimination tree first):
+ *     acc[r] = C(r, j) for the rows r of column j of L (0.0 in fill slots)
+ *     for every column k < j with L(j,k) in the pattern, k ASCENDING:
+ *       w = L(j,k) * d[k]                                          (rounded)
+ *       for every stored p of column k from the slot of L(j,k) to the column's end:
+ *         acc[L.i[p]] = acc[L.i[p]] - L.x[p] * w                   (product rounded, then the subtraction rounded)
+ *     d[j] = acc[j]
+ *     if tau > 0 and |d[j]| < tau:  d[j] = copysign(tau, d[j]), counted as a perturbed pivot
+ *     if d[j] == 0 or d[j] is not finite:  breakdown at j (the smallest such j is reported)
+ *     L(j,j) = 1.0;  L(r,j) = acc[r] / d[j]                        (IEEE division)
+ *   On the device one wave owns a column and applies its updates one after another: L.x and d are byte-equal to
+ *   csx_ldl_host, the same on every run.  No floating-point atomics.
+ * csx_ldl_factor: *ok = 1 and a NEW factor handle (csx_free) that keeps the analysis (pattern and row view of L, entry map,
+ *   height levels of the elimination tree) and owns L and d; *ok = 0 and *F = 0 on breakdown.  tau is the perturbation
+ *   threshold (0: none).  CSX_EINVAL for a pattern-only or non-square A, an S or pinv that does not belong to A, tau < 0 or NaN.
+ * csx_ldl_refactor: new values on the kept analysis: A2 a CSC handle with A's shape, entry count and pattern (compared), or a
+ *   vector of exactly nnz(A) values in A's storage order; CSX_EINVAL (*ok = -1, nothing changed) otherwise.  The factor is
+ *   computed into scratch arrays and copied over L.x and d only when no column broke down (*ok = 1); on breakdown (*ok = 0) L,
+ *   d and every plan made from them are exactly as before.  L.x and d keep their addresses.
+ * csx_ldl_parts: BORROWED handles of L (CSC) and d (vector of n doubles): the factor owns them, the caller must not free them,
+ *   and they die with the factor.
+ * csx_ldl_info: info[13] = n, entries of L, height levels of the tree, numeric launches of the last run, positive pivots, negative
+ *   pivots (both of the committed factor), perturbed pivots of the last run, the smallest broken column of the last run or -1,
+ *   microseconds of the last run between two events, then: launches of the level kernel, launches of the run walker (one
+ *   workgroup walking consecutive levels of at most 4 columns), the columns of the last run that took the in-place path (longer
+ *   than the LDS window, updated in global memory; counted by the kernels), the LDS window in entries.
+ * csx_ldl_window: the LDS window in entries, without a device or a factor.
+ * csx_ldl_stats: out[3] = min |d|, max |d|, max |l| off the diagonal of the committed factor (0.0 where there is none).
+ * csx_block_div_rows: X[i, c] = X[i, c] / d[i] for the first `rows` rows of a row-major block of nrhs columns (X a vector of at
+ *   least rows nrhs doubles, d of at least rows; CSX_EINVAL otherwise); queued on the context's stream.
+ * csx_ldl_host: the rule on host arrays, no device: Lp / Li the pattern of L, Lx (Lp[n] doubles) and d (n doubles) written;
+ *   info[4] = positive pivots, negative pivots, perturbed pivots, the smallest broken column or -1 (then Lx and d are not a
+ *   factorisation).  CSX_EINVAL for a malformed pattern, an upper entry of A without a slot in L, tau < 0 or NaN. */
+int csx_ldl_factor(csx_handle_t A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, double tau, csx_handle_t *F,
+                   int *ok);
+int csx_ldl_refactor(csx_handle_t F, csx_handle_t A2, double tau, int *ok);
+int csx_ldl_parts(csx_handle_t F, csx_handle_t *L, csx_handle_t *d);
+int csx_ldl_info(csx_handle_t F, int64_t *info);
+int csx_ldl_stats(csx_handle_t F, double *out);
+int csx_ldl_window(int32_t *entries);
+int csx_block_div_rows(csx_handle_t X, csx_handle_t d, int64_t rows, int32_t nrhs);
+int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
+                 const int32_t *Li, double tau, double *Lx, double *d, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
