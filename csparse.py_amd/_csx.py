@@ -187,6 +187,13 @@ _PROTOS = {
     "csx_ldl_window": [C.POINTER(C.c_int32)],
     "csx_block_div_rows": [H, H, C.c_int64, C.c_int32],
     "csx_ldl_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
+    "csx_slu_factor": [H, _i32p, _i32p, _i32p, _i32p, C.c_double, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_slu_refactor": [H, H, C.c_double, C.POINTER(C.c_int)],
+    "csx_slu_parts": [H, C.POINTER(H), C.POINTER(H)],
+    "csx_slu_info": [H, C.POINTER(C.c_int64)],
+    "csx_slu_stats": [H, _f64p],
+    "csx_slu_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "csx_slu_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -264,6 +271,14 @@ def ldl_window():
     out = C.c_int32(0)
     check(load().csx_ldl_window(C.byref(out)), "csx_ldl_window")
     return out.value
+
+
+def slu_window():
+    """(entries of a column that the static-pivot LU column kernels keep in LDS, levels one launch of its walker takes)
+    (csx_slu.hip SLU_ACC, SLU_RUN_LEVELS), asked of the library; no GPU needed"""
+    a, b = C.c_int32(0), C.c_int32(0)
+    check(load().csx_slu_window(C.byref(a), C.byref(b)), "csx_slu_window")
+    return a.value, b.value
 
 
 def exported_symbols():

@@ -2607,6 +2607,209 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
     return _Solver()
 
 
+# ------------------------------------------------------ LU, static pivots ----
+
+_SLU_INFO = ("n", "lnz", "levels", "launches", "level_launches", "run_launches", "perturbed", "breakdown", "kernel_us",
+             "long_columns", "window", "run_levels", "pos", "neg")
+
+
+def _perm_parity(p):
+    """+1.0 / -1.0: the sign of the permutation p (a sequence of 0..n-1), from its cycles"""
+    p = np.asarray(p, dtype=np.int64)
+    seen = np.zeros(len(p), dtype=bool)
+    even = True
+    for s in range(len(p)):
+        k, length = s, 0
+        while not seen[k]:
+            seen[k] = True
+            k = int(p[k])
+            length += 1
+        if length and length % 2 == 0:
+            even = not even
+    return 1.0 if even else -1.0
+
+
+def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
+    """Factor a general UNSYMMETRIC matrix in one connected piece once for many solves, on the device, without a pivot search
+    (DESIGN.md §23): L U = P A(prow, :) P' with L unit lower triangular and U = Ut' upper triangular, both on the Cholesky pattern
+    of the pattern of A1 + A1', A1 = A(prow, :).
+    match: a maximum matching (maxtrans_array(A, seed): the row matched to column j becomes row j) puts a zero-free diagonal in
+      place: None (default) matches only when some diagonal entry of A is not stored, True always, False never.  None is
+      returned for a structurally singular A.  The matching is unweighted: it knows nothing of the values.
+    order: 0 natural, 1 nested dissection of A1 + A1' (cs_schol's), applied symmetrically.
+    perturb: a pivot with |d| < tau = perturb |A|_1 is replaced by copysign(tau, d) and counted (info()["perturbed"]).  It is
+      RELATIVE TO |A|_1 AND NOT A DEFAULT: 0.0 (default) perturbs nothing, and a zero or non-finite pivot is a breakdown.  On a
+      badly scaled matrix (fs_183_1: |A|_1 = 8e8) 1e-10 perturbs half the pivots and refinement does not recover.
+    Static pivoting is not backward stable by itself: follow solve() with refine() and read backward_error().  Of duplicate
+    entries the factorisation takes the last (as cs_lu does) while a residual sums them: sum them first (cs_dupl).
+    None for a non-CSC or non-square A, and None on breakdown.  Otherwise a solver:
+    solve(b, trans=False): b a list (one system) or a dvec n-by-k block, overwritten: x(pinv o prow^-1) = b, cs_lsolve(L),
+      cs_ltsolve(Ut), x = x(pinv); trans=True (A' x = b): x(pinv) = b, cs_lsolve(Ut), cs_ltsolve(L), x = x(pinv o prow^-1).  The
+      sweeps follow lusol_factor's rule for `exact`.
+    refactor(A2): new values on the kept analysis (and the kept matching), A2 as for lusol_factor's refactor: True; False with
+      L, Ut and the solves exactly as before on breakdown; ValueError for another pattern or length.  L.x and Ut.x are byte-equal
+      to a fresh factor's under the same prow and order.
+    backward_error(x, b, trans=False), refine(b, maxit=5, trans=False): _Refinable's; condest(): cond_1(A) estimated from
+      exact-order solves; logdet(): (sign, log |det A|), the sign with both permutations' parities; info(): n, lnz, levels,
+      launches = level_launches + run_launches of the last run, perturbed, breakdown, kernel_us, long_columns (updated in place:
+      longer than the LDS `window`), run_levels (levels per walker launch), pos, neg (pivot signs), min_abs_d, max_abs_d,
+      max_abs_l, max_abs_u, matched.  factors: .L, .U (= Ut: column k is row k of U, the pivot first), .prow, .pinv."""
+    if not CS_CSC(A) or A.m != A.n:
+        return None
+    perturb = float(perturb)
+    if not perturb >= 0.0:
+        raise ValueError("slusol_factor: perturb must be >= 0")
+    n = A.n
+    if not _meta(A)[1]:
+        raise TypeError("'NoneType' object is not subscriptable")
+    if match is None:
+        p, i = _pattern_np(A)
+        cols = np.repeat(np.arange(n, dtype=np.int32), np.diff(p))
+        match = int(np.unique(cols[i[:len(cols)] == cols]).size) < n
+    prow = None
+    if match:
+        prow = maxtrans_array(A, seed)[n:]
+        if n and int(prow.min()) < 0:
+            return None                              # structurally singular
+        prow = np.ascontiguousarray(prow, dtype=np.int32)
+    # B: the pattern of A1 + A1' (the values do not matter), for the ordering and the counts
+    A1 = A
+    if prow is not None:
+        prinv = np.empty(n, dtype=np.int32)
+        prinv[prow] = np.arange(n, dtype=np.int32)
+        A1 = cs_permute(A, prinv, None, False)
+    B = cs_add(A1, cs_transpose(A1, False), 1.0, 1.0)
+    S = cs_schol(order, B, _arrays=True) if B is not None else None
+    if S is None:
+        return None
+    pinv = None if S.pinv is None else _csx.i32(S.pinv)
+    lib = _csx.lib()
+
+    def threshold(hA):
+        if perturb == 0.0:
+            return 0.0
+        out = _csx.C.c_double(0.0)
+        _csx.check(lib.csx_norm1(hA, out), "csx_norm1")
+        return perturb * out.value
+
+    hF, ok = _csx.new_handle(), _csx.C.c_int(0)
+    with _Resident(A) as dA:
+        _csx.check(lib.csx_slu_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(prow), _csx.pi(pinv),
+                                      threshold(dA.handle), hF, ok), "csx_slu_factor")
+    if not ok.value:
+        return None
+    hL, hU = _csx.new_handle(), _csx.new_handle()
+    _csx.check(lib.csx_slu_parts(hF, hL, hU), "csx_slu_parts")
+    # L and Ut are the factor's (borrowed handles): the wrappers free the plans cached on them and the factor, never L or Ut
+    N = csn()
+    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
+    N.U = cs_pin(_from_device(hU, lambda nnz: max(nnz, 1)))
+    devL, devU = N.L._dev, N.U._dev
+    devL._fin.detach()
+    devL._fin = weakref.finalize(devL, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), devL.plans, hF)
+    devU._fin.detach()
+    devU._fin = weakref.finalize(devU, _DevMatrix._release, None, devU.plans)
+    devU._keep = devL                                # Ut lives in the factor that L's wrapper frees
+    N.prow = None if prow is None else prow.tolist()
+    N.pinv, N.B = None if pinv is None else pinv.tolist(), None
+    # the two permutations of a solve: x(comb) = b before the forward sweeps, x = x(pinv) after them (swapped for A')
+    comb = pinv
+    if prow is not None:
+        comb = prinv if pinv is None else pinv[prinv]
+    hc, keep_c = _perm_handle(comb, n)
+    hp, keep_p = _perm_handle(pinv, n)
+    sign_perm = (_perm_parity(prow) if prow is not None else 1.0)    # (P C P' keeps the determinant)
+
+    class _Solver(_Refinable):
+        factors = N
+
+        @property
+        def symbolic(self):
+            for name in ("parent", "cp", "pinv"):
+                v = getattr(S, name)
+                if v is not None and not isinstance(v, list):
+                    setattr(S, name, v.tolist())
+            return S
+
+        def __init__(self):
+            self._devs = (devL, devU)                # keep L, Ut and the factor alive
+            self._fin = weakref.finalize(self, lambda hs: [_csx.free(h) for h in hs if h is not None], [keep_c, keep_p])
+            self._A2, self._norm = A, None
+            self._refine_init(A, n)
+
+        def _solve_block(self, blk, trans, from_list):
+            return self._block(blk, exact if exact is not None else from_list, trans)
+
+        def _block(self, blk, in_exact_order=True, trans=False):
+            k = blk.k
+            (h_in, p_in), (h_out, p_out) = ((hp, pinv), (hc, comb)) if trans else ((hc, comb), (hp, pinv))
+            x = blk
+            if p_in is not None:
+                x = dvec(n, k)
+                _csx.check(lib.csx_permute_vec(h_in, blk.handle, x.handle, n, k, 1), "csx_permute_vec")
+            p1, p2 = (_plan(devU, TRI_L), _plan(devL, TRI_LT)) if trans else (_plan(devL, TRI_L), _plan(devU, TRI_LT))
+            try:
+                for plan in (p1, p2):
+                    _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+                _csx.check(lib.csx_tri_solve(p1, x.handle, k), "csx_tri_solve")
+                _csx.check(lib.csx_tri_solve(p2, x.handle, k), "csx_tri_solve")
+            finally:
+                lib.csx_tri_set_order(p1, 1)         # (shared with the list-level cs_lsolve / cs_ltsolve on these factors)
+                lib.csx_tri_set_order(p2, 1)
+            if p_out is not None:
+                y = blk if x is not blk else dvec(n, k)
+                _csx.check(lib.csx_permute_vec(h_out, x.handle, y.handle, n, k, 0), "csx_permute_vec")
+                if y is not blk:
+                    _csx.check(lib.csx_vec_copy(y.handle, blk.handle), "csx_vec_copy")
+            elif x is not blk:
+                _csx.check(lib.csx_vec_copy(x.handle, blk.handle), "csx_vec_copy")
+            return blk
+
+        def solve(self, b, trans=False):
+            db, bhost = _vec_in(b, n, "b")
+            self._block(db, exact if exact is not None else not isinstance(b, dvec), bool(trans))
+            _write_back(bhost, db, n * db.k)
+            return True
+
+        def refactor(self, A2):
+            A2 = _refactor_input(A, A2)
+            ok = _csx.C.c_int(0)
+            tau = perturb * _refactor_norm(A, A2) if perturb > 0.0 else 0.0
+            _refactor_call(A2, lambda h2: lib.csx_slu_refactor(hF, h2, tau, ok), ok)
+            if ok.value == 1:
+                _refactored(N.L, devL)
+                _refactored(N.U, devU)
+                self._A2, self._norm = A2, None
+                self._operator_changed()
+            return ok.value == 1
+
+        def condest(self):
+            if self._norm is None:
+                self._norm = _refactor_norm(A, self._A2)
+            return _condest(self._norm, lambda v, t: self._block(dvec(v), True, t).numpy(), n)
+
+        def info(self):
+            raw = (_csx.C.c_int64 * len(_SLU_INFO))()
+            st = (_csx.C.c_double * 4)()
+            _csx.check(lib.csx_slu_info(hF, raw), "csx_slu_info")
+            _csx.check(lib.csx_slu_stats(hF, st), "csx_slu_stats")
+            out = {name: int(v) for name, v in zip(_SLU_INFO, raw)}
+            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2], max_abs_u=st[3], matched=prow is not None)
+            return out
+
+        def logdet(self):
+            """(sign, log |det A|): det A = det(prow) * the product of the pivots (the symmetric permutation cancels); the sum
+            of log |d_j| correctly rounded (math.fsum)"""
+            Lp = np.empty(n + 1, dtype=np.int32)
+            x = np.empty(max(devU.info()[2], 1), dtype=np.float64)
+            _csx.check(lib.csx_csc_download(devU.handle, _csx.pi(Lp), None, _csx.pd(x)), "csx_csc_download")
+            d = x[Lp[:n]]
+            sign = sign_perm * (-1.0 if int(np.sum(d < 0.0)) % 2 else 1.0)
+            return sign, math.fsum(np.log(np.abs(d)).tolist())
+
+    return _Solver()
+
+
 # -------------------------------------------------------------------- QR ----
 # cs_qr: host C++ (csx_qr_host), on the device for batches of small independent blocks (csx_qr_blocks); the Q' x step of
 # the solve (cs_happly for every reflection) and the triangular solves on the device (SURVEY 8f N4).

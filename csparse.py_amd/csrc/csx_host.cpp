@@ -1335,3 +1335,90 @@ extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, con
     info[3] = broke;
     return CSX_OK;
 }
+
+// csx_slu_factor's value rule on host arrays (csx_slu.hip): L U = C = P A(prow, :) P' on the given pattern (rows
+// ascending, the diagonal first), no pivot search.  Entry (i, j) of A is C(i2, j2), i2 = pinv[prinv[i]], j2 = pinv[j]; of
+// duplicates the last counts.  Lx: unit lower L; Utx: column k = row k of U, the pivot first.  Columns ascending; column j takes
+// the updates of the columns k < j with (j,k) in the pattern in ascending k (the row view), each from the slot of row j to the
+// end of column k: every product rounded, then every subtraction rounded.  info[4] = positive pivots, negative pivots, perturbed
+// pivots, the smallest column whose pivot is 0 or not finite (-1: none).
+extern "C" int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *prow, const int32_t *pinv,
+                            const int32_t *Lp, const int32_t *Li, double tau, double *Lx, double *Utx, int64_t *info) {
+#pragma clang fp contract(off)
+    if (n < 0 || !Ap || !Lp || !info || Ap[0] != 0 || Lp[0] != 0 || !(tau >= 0.0)) return CSX_EINVAL;
+    const int32_t anz = Ap[n], lnz = Lp[n];
+    if (anz < 0 || lnz < n || (anz > 0 && (!Ai || !Ax)) || (n > 0 && (!Li || !Lx || !Utx))) return CSX_EINVAL;
+    std::vector<int32_t> prinv((size_t)n, -1), seen((size_t)n, 0);
+    for (int32_t j = 0; j < n; j++) {
+        if (Ap[j + 1] < Ap[j] || Lp[j + 1] <= Lp[j] || Li[Lp[j]] != j) return CSX_EINVAL;
+        for (int32_t q = Lp[j] + 1; q < Lp[j + 1]; q++)
+            if (Li[q] <= Li[q - 1] || Li[q] >= n) return CSX_EINVAL;
+        if (pinv && (pinv[j] < 0 || pinv[j] >= n || seen[(size_t)pinv[j]]++)) return CSX_EINVAL;
+        const int32_t r = prow ? prow[j] : j;
+        if (r < 0 || r >= n || prinv[(size_t)r] >= 0) return CSX_EINVAL;
+        prinv[(size_t)r] = j;
+    }
+    // the two entry maps (k_slu_entry_map's): slot <- the last stored entry of A that lands there
+    std::vector<int32_t> winL((size_t)lnz, -1), winU((size_t)lnz, -1);
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t j2 = pinv ? pinv[j] : j;
+        for (int32_t q = Ap[j]; q < Ap[j + 1]; q++) {
+            if (Ai[q] < 0 || Ai[q] >= n) return CSX_EINVAL;
+            const int32_t i1 = prinv[(size_t)Ai[q]];
+            const int32_t i2 = pinv ? pinv[i1] : i1;
+            const int32_t c = std::min(i2, j2), r = std::max(i2, j2);
+            const int32_t *b = Li + Lp[c], *e = Li + Lp[c + 1];
+            const int32_t *at = std::lower_bound(b, e, r);
+            if (at == e || *at != r) return CSX_EINVAL;   // the pattern does not contain this entry
+            if (i2 >= j2) winL[(size_t)(at - Li)] = q;
+            if (i2 <= j2) winU[(size_t)(at - Li)] = q;
+        }
+    }
+    for (int32_t q = 0; q < lnz; q++) {
+        Lx[q] = winL[(size_t)q] >= 0 ? Ax[winL[(size_t)q]] : 0.0;
+        Utx[q] = winU[(size_t)q] >= 0 ? Ax[winU[(size_t)q]] : 0.0;
+    }
+    // the row view: for row j the slots of (j,k), k ascending
+    std::vector<int32_t> rp((size_t)n + 1, 0), rpos((size_t)lnz);
+    for (int32_t q = 0; q < lnz; q++) rp[(size_t)Li[q] + 1]++;
+    for (int32_t j = 0; j < n; j++) rp[(size_t)j + 1] += rp[(size_t)j];
+    {
+        std::vector<int32_t> next(rp.begin(), rp.end() - 1);
+        for (int32_t k = 0; k < n; k++)
+            for (int32_t q = Lp[k]; q < Lp[k + 1]; q++) rpos[(size_t)next[(size_t)Li[q]]++] = q;
+    }
+    std::vector<int32_t> slot((size_t)n, -1);
+    int64_t pos = 0, neg = 0, perturbed = 0, broke = -1;
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t base = Lp[j], end = Lp[j + 1];
+        for (int32_t q = base; q < end; q++) slot[(size_t)Li[q]] = q;
+        for (int32_t t = rp[(size_t)j]; t < rp[(size_t)j + 1] - 1; t++) {   // (the row ends with the diagonal)
+            const int32_t at = rpos[(size_t)t];
+            const int32_t k = (int32_t)(std::upper_bound(Lp, Lp + n + 1, at) - Lp) - 1;
+            const double l = Lx[at], u = Utx[at];
+            for (int32_t q = at; q < Lp[k + 1]; q++) {
+                const int32_t s = slot[(size_t)Li[q]];
+                if (s < base) return CSX_EINVAL;          // not the pattern of a Cholesky factor
+                const double a = Lx[q] * u, b = Utx[q] * l;
+                Lx[s] = Lx[s] - a;
+                Utx[s] = Utx[s] - b;
+            }
+        }
+        double dj = Utx[base];
+        if (tau > 0.0 && std::fabs(dj) < tau) {
+            dj = std::copysign(tau, dj);
+            perturbed++;
+        }
+        if ((dj == 0.0 || !std::isfinite(dj)) && broke < 0) broke = j;
+        pos += dj > 0.0;
+        neg += dj < 0.0;
+        Utx[base] = dj;
+        Lx[base] = 1.0;
+        for (int32_t q = base + 1; q < end; q++) Lx[q] = Lx[q] / dj;
+    }
+    info[0] = pos;
+    info[1] = neg;
+    info[2] = perturbed;
+    info[3] = broke;
+    return CSX_OK;
+}

@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR };
 
 struct Csc;
 
@@ -221,6 +221,8 @@ void destroy(CholAnalysis *p);
 void destroy(CholRefPlan *p);
 struct LdlFactor;     // csx_ldl.hip
 void destroy(LdlFactor *p);
+struct SluFactor;     // csx_slu.hip
+void destroy(SluFactor *p);
 
 struct Object {
     Kind kind = K_FREE;

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "csx_internal.h"
+#include "csx_ldl.h"
 
 #pragma clang fp contract(off)
 
@@ -22,16 +23,6 @@ namespace csx {
 constexpr int LDL_ACC = 512;    // column entries kept in LDS per wave (24 KB a workgroup); longer columns are updated in place in global memory
 constexpr int LDL_WAVES = 4;    // waves per workgroup (csx_chol.hip's CH_WAVES)
 constexpr int LDL_NONE = 0x7fffffff;
-
-__device__ __forceinline__ int32_t ldl_find_row(const int32_t *rows, int32_t len, int32_t r) {
-    int32_t lo = 0, hi = len - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (rows[mid] < r) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // Column j of L and d[j].  On entry Lx[Lp[j] ..] holds C(:, j) in the slots of L (0.0 in fill slots), and every column k < j
 // with L(j,k) in the pattern is finished (L(:,k) and d[k] final).  acc_v / acc_r: wave-private LDS (LDL_ACC entries).
@@ -233,23 +224,6 @@ struct LdlFactor {
 };
 
 void destroy(LdlFactor *F) { delete F; }
-
-// height levels: a leaf is at level 0, a column one above its highest child (parent[j] > j: one ascending pass)
-static void ldl_levels(int32_t n, const int32_t *parent, std::vector<int32_t> &ptr, std::vector<int32_t> &cols) {
-    std::vector<int32_t> level((size_t)n, 0);
-    int32_t nlev = 0;
-    for (int32_t j = 0; j < n; j++) {
-        const int32_t up = parent[j];
-        if (up >= 0) level[(size_t)up] = std::max(level[(size_t)up], level[(size_t)j] + 1);
-        nlev = std::max(nlev, level[(size_t)j] + 1);
-    }
-    ptr.assign((size_t)nlev + 1, 0);
-    for (int32_t j = 0; j < n; j++) ptr[(size_t)level[(size_t)j] + 1]++;
-    for (int32_t l = 0; l < nlev; l++) ptr[(size_t)l + 1] += ptr[(size_t)l];
-    cols.resize((size_t)n);
-    std::vector<int32_t> next(ptr.begin(), ptr.end() - 1);
-    for (int32_t j = 0; j < n; j++) cols[(size_t)next[(size_t)level[(size_t)j]]++] = j;
-}
 
 // The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
 // into L.x / d when no column broke down.  *ok: 1 committed, 0 breakdown (L, d untouched).  Synchronises.

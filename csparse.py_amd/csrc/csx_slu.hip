@@ -1,0 +1,545 @@
+// L U with static pivots for general unsymmetric matrices in one connected piece (the definition is the comment
+// of csx_slu_factor in include/csx.h).  L U = C = P A(prow, :) P' on the Cholesky pattern of the pattern of A1 + A1', A1 =
+// A(prow, :): a matching has put a zero-free diagonal in place, the symmetric order is the caller's, and there is no pivot
+// search, so the pattern is known before the values are.  L (unit lower, the 1.0 stored) and Ut (column k = row k of U, the pivot
+// first) are two value arrays on that one pattern; the numeric kernel is ldl_column (csx_ldl.hip) with a second accumulator.
+//   k_slu_sym_rows / k_slu_sym_ptr / k_slu_sym_fill   the pattern whose upper triangle is that of A1 + A1', for the symbolic step
+//   k_slu_entry_map   slot of L and slot of Ut of every entry of A (of duplicates the last)
+//   k_slu_level   one wave per column of a height level of the elimination tree
+//   k_slu_run     one workgroup walks at most SLU_RUN_LEVELS levels of at most SLU_WAVES columns each, a barrier per level
+//   k_slu_stats   min / max |d|, max |l|, max |u| off the diagonal, pivot signs in one pass
+// Every sum is updated in ascending k by one wave, one update after the other: L.x and Ut.x are byte-equal to csx_slu_host.
+// A factor or refactor runs into scratch arrays and is committed only when no column broke down.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "csx_internal.h"
+#include "csx_ldl.h"
+
+#pragma clang fp contract(off)
+
+namespace csx {
+
+constexpr int SLU_ACC = 512;          // column entries kept in LDS per wave (8 + 8 + 4 bytes each: 40 KB a workgroup); longer columns are updated in place
+constexpr int SLU_WAVES = 4;          // waves per workgroup
+constexpr int SLU_RUN_LEVELS = 256;   // levels one launch of the walker takes: a longer run is several launches
+constexpr int SLU_NONE = 0x7fffffff;
+
+// ---- analysis ------------------------------------------------------------------------------------------------------------------
+
+// rows of A1 = A(prow, :): row i of A is row prinv[i] of A1; the entry order inside a column stays, so A's values are A1's
+__global__ __launch_bounds__(256) void k_slu_sym_rows(int64_t nnz, const int32_t *__restrict__ Ai, const int32_t *__restrict__ prinv,
+                                                      int32_t *__restrict__ out) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < nnz) out[q] = prinv[Ai[q]];
+}
+
+__global__ __launch_bounds__(256) void k_slu_sym_ptr(int32_t n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Tp,
+                                                     int32_t *__restrict__ Mp) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c <= n) Mp[c] = Ap[c] + Tp[c];
+}
+
+// column c of M = column c of A1, then column c of A1': its entries above the diagonal are those of A1 + A1' (the symbolic step
+// reads nothing else; duplicates start no second walk)
+__global__ __launch_bounds__(256) void k_slu_sym_fill(int32_t n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Ai,
+                                                      const int32_t *__restrict__ Tp, const int32_t *__restrict__ Ti,
+                                                      int32_t *__restrict__ Mi) {
+    const int lane = threadIdx.x & 63;
+    const int64_t c = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (c >= n) return;
+    const int32_t a = Ap[c], la = Ap[c + 1] - a, b = Tp[c], lb = Tp[c + 1] - b;
+    int32_t *out = Mi + a + b;
+    for (int32_t t = lane; t < la; t += 64) out[t] = Ai[a + t];
+    for (int32_t t = lane; t < lb; t += 64) out[la + t] = Ti[b + t];
+}
+
+// Entry q of A at (i, j) is C(i2, j2), i2 = pinv[prinv[i]], j2 = pinv[j]: on or below the diagonal it is the start of L(i2, j2),
+// on or above it the start of U(i2, j2) = Ut(j2, i2).  Of duplicates the last wins (cs_lu's scatter, k_chol_winner).
+__global__ __launch_bounds__(256) void k_slu_entry_map(int32_t n, const int32_t *__restrict__ Ap, const int32_t *__restrict__ Ai,
+                                                       const int32_t *__restrict__ prinv, const int32_t *__restrict__ pinv,
+                                                       const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
+                                                       int32_t *winL, int32_t *winU, int *bad) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (j >= n) return;
+    const int32_t j2 = pinv ? pinv[j] : (int32_t)j;
+    for (int32_t p = Ap[j] + lane; p < Ap[j + 1]; p += 64) {
+        const int32_t i1 = prinv ? prinv[Ai[p]] : Ai[p];
+        const int32_t i2 = pinv ? pinv[i1] : i1;
+        const int32_t c = min(i2, j2), r = max(i2, j2);
+        const int32_t b = Lp[c], len = Lp[c + 1] - b;
+        const int32_t t = ldl_find_row(Li + b, len, r);
+        if (Li[b + t] != r) {
+            *bad = 1;   // the symbolic pattern does not contain this entry
+            continue;
+        }
+        if (i2 >= j2) atomicMax(&winL[b + t], p);
+        if (i2 <= j2) atomicMax(&winU[b + t], p);
+    }
+}
+
+// ---- one column -----------------------------------------------------------------------------------------------------------------
+// Column j of L and of Ut.  On entry Lx[Lp[j] ..] holds C(:, j) and Ux[Lp[j] ..] holds C(j, :) in the slots of the pattern (0.0 in
+// fill and one-sided slots), and every column k < j with (j,k) in the pattern is finished.  acc_l / acc_u / acc_r: wave-private
+// LDS (SLU_ACC entries).  flags[0]: the smallest broken column (atomicMin), flags[1]: perturbed pivots, flags[2]: columns that
+// took the in-place path (integer atomicAdd both).
+__device__ __forceinline__ void slu_column(int32_t j, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li, double *Lx,
+                                           double *Ux, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
+                                           const int32_t *__restrict__ row_pos, double tau, double *acc_l, double *acc_u,
+                                           int32_t *acc_r, int lane, int *flags) {
+    const int32_t base = Lp[j], len = Lp[j + 1] - base;
+    const bool in_lds = len <= SLU_ACC;
+    if (in_lds) {
+        for (int32_t t = lane; t < len; t += 64) {
+            acc_l[t] = Lx[base + t];
+            acc_u[t] = Ux[base + t];
+            acc_r[t] = Li[base + t];
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal
+    // Updates are applied in order, but fetched eight at a time (ldl_column): lane u reads the descriptor of update u -- the slot
+    // of row j in column k, the end of column k, l = L(j,k), u = Ut(j,k) -- and the heads of the eight columns are requested
+    // together, both value arrays at once.
+    constexpr int UQ = 8;
+    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
+        int32_t posq = 0, kendq = 0;
+        double lq = 0.0, uq = 0.0;
+        if (lane < UQ && q0 + lane < qe) {
+            const int32_t kq = row_col[q0 + lane];
+            posq = row_pos[q0 + lane];
+            kendq = Lp[kq + 1];
+            lq = Lx[posq];
+            uq = Ux[posq];
+        }
+        int32_t pos_[UQ], kend_[UQ], r_[UQ];
+        double l_[UQ], u_[UQ], vl_[UQ], vu_[UQ];
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            pos_[u] = __builtin_amdgcn_readlane(posq, u);
+            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
+            l_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lq), u),
+                                     __builtin_amdgcn_readlane(__double2loint(lq), u));
+            u_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(uq), u),
+                                     __builtin_amdgcn_readlane(__double2loint(uq), u));
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            const int32_t p = pos_[u] + lane;
+            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
+            r_[u] = Li[pp];
+            vl_[u] = Lx[pp];
+            vu_[u] = Ux[pp];
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            if (pos_[u] + lane < kend_[u]) {
+                const double a = vl_[u] * u_[u], b = vu_[u] * l_[u];
+                if (in_lds) {
+                    const int32_t t = ldl_find_row(acc_r, len, r_[u]);   // one search serves both sums
+                    acc_l[t] = acc_l[t] - a;
+                    acc_u[t] = acc_u[t] - b;
+                } else {
+                    const int32_t t = base + ldl_find_row(Li + base, len, r_[u]);
+                    Lx[t] = Lx[t] - a;
+                    Ux[t] = Ux[t] - b;
+                }
+            }
+            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
+                const double a = Lx[p] * u_[u], b = Ux[p] * l_[u];
+                if (in_lds) {
+                    const int32_t t = ldl_find_row(acc_r, len, Li[p]);
+                    acc_l[t] = acc_l[t] - a;
+                    acc_u[t] = acc_u[t] - b;
+                } else {
+                    const int32_t t = base + ldl_find_row(Li + base, len, Li[p]);
+                    Lx[t] = Lx[t] - a;
+                    Ux[t] = Ux[t] - b;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
+        }
+    }
+    double dj = in_lds ? acc_u[0] : Ux[base];
+    const bool small = tau > 0.0 && fabs(dj) < tau;
+    if (small) dj = copysign(tau, dj);
+    if (lane == 0) {
+        if (small) atomicAdd(flags + 1, 1);
+        if (!in_lds) atomicAdd(flags + 2, 1);
+        if (dj == 0.0 || !isfinite(dj)) atomicMin(flags, j);
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int32_t t = lane; t < len; t += 64) {
+        const double vl = in_lds ? acc_l[t] : Lx[base + t];
+        const double vu = in_lds ? acc_u[t] : Ux[base + t];
+        Lx[base + t] = t == 0 ? 1.0 : vl / dj;
+        Ux[base + t] = t == 0 ? dj : vu;
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+
+#define SLU_SHARED                                  \
+    __shared__ double s_acc_l[SLU_WAVES][SLU_ACC];  \
+    __shared__ double s_acc_u[SLU_WAVES][SLU_ACC];  \
+    __shared__ int32_t s_acc_r[SLU_WAVES][SLU_ACC];
+
+// one wave per column of a level
+__global__ __launch_bounds__(64 * SLU_WAVES) void k_slu_level(const int32_t *__restrict__ cols, int32_t count,
+                                                             const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
+                                                             double *Lx, double *Ux, const int32_t *__restrict__ row_ptr,
+                                                             const int32_t *__restrict__ row_col,
+                                                             const int32_t *__restrict__ row_pos, double tau, int *flags) {
+    SLU_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * SLU_WAVES + w;
+    if (c >= count) return;
+    slu_column(cols[c], Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, s_acc_l[w], s_acc_u[w], s_acc_r[w], lane, flags);
+}
+
+// One workgroup walks the levels [l0, l1), l1 - l0 <= SLU_RUN_LEVELS, each of at most SLU_WAVES columns: wave w takes column w of
+// the level, a barrier between levels makes the finished columns visible to the next.  The trip counts are the level pointers,
+// the same for every wave, so every wave reaches every barrier.
+__global__ __launch_bounds__(64 * SLU_WAVES) void k_slu_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
+                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Lp,
+                                                           const int32_t *__restrict__ Li, double *Lx, double *Ux,
+                                                           const int32_t *__restrict__ row_ptr,
+                                                           const int32_t *__restrict__ row_col,
+                                                           const int32_t *__restrict__ row_pos, double tau, int *flags) {
+    SLU_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int32_t l = l0; l < l1; l++) {
+        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
+        if (w < cnt)
+            slu_column(cols[b + w], Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, s_acc_l[w], s_acc_u[w], s_acc_r[w], lane, flags);
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ uint64_t slu_abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
+
+// One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|,
+// st[5] max |u| off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (k_ldl_stats' rule)
+__global__ __launch_bounds__(256) void k_slu_stats(int32_t n, const int32_t *__restrict__ Lp, const double *__restrict__ Lx,
+                                                   const double *__restrict__ Ux, unsigned long long *st) {
+    const int lane = threadIdx.x & 63;
+    const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (j >= n) return;
+    uint64_t lmax = 0, umax = 0;
+    for (int32_t p = Lp[j] + 1 + lane; p < Lp[j + 1]; p += 64) {
+        const uint64_t a = slu_abs_bits(Lx[p]), b = slu_abs_bits(Ux[p]);
+        lmax = a > lmax ? a : lmax;
+        umax = b > umax ? b : umax;
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t a = (uint64_t)__shfl_xor((unsigned long long)lmax, off);
+        const uint64_t b = (uint64_t)__shfl_xor((unsigned long long)umax, off);
+        lmax = a > lmax ? a : lmax;
+        umax = b > umax ? b : umax;
+    }
+    if (lane == 0) {
+        const double dj = Ux[Lp[j]];
+        if (dj > 0.0) atomicAdd(st + 0, 1ull);
+        if (dj < 0.0) atomicAdd(st + 1, 1ull);
+        atomicMin(st + 2, (unsigned long long)slu_abs_bits(dj));
+        atomicMax(st + 3, (unsigned long long)slu_abs_bits(dj));
+        if (lmax) atomicMax(st + 4, (unsigned long long)lmax);
+        if (umax) atomicMax(st + 5, (unsigned long long)umax);
+    }
+}
+
+struct SluFactor {
+    int32_t n = 0, anz = 0, lnz = 0;
+    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
+    DevBuf<int32_t> rp, rc, rpos;           // row view of the pattern (chol_symbolic_device)
+    DevBuf<int32_t> winL, winU;             // the two entry maps
+    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the elimination tree: columns by level, ascending inside one
+    std::vector<int32_t> level_ptr_h;
+    csx_handle_t hL = 0, hU = 0;            // the committed factor: owned here, lent out by csx_slu_parts; Ut borrows L's p and i
+    DevBuf<double> utx;                     // Ut's values (Ut itself owns nothing)
+    DevBuf<double> Lx, Ux;                  // scratch of a run: committed only when no column broke down
+    DevBuf<int> flags;                      // [0] smallest broken column, [1] perturbed pivots, [2] columns updated in place
+    DevBuf<unsigned long long> stats;       // k_slu_stats
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    // csx_slu_info / csx_slu_stats
+    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0;   // long_cols: counted by the kernels of the last run
+    int64_t pos = 0, neg = 0, perturbed = 0, breakdown = -1, kernel_us = 0;
+    double min_d = 0.0, max_d = 0.0, max_l = 0.0, max_u = 0.0;
+    SluFactor() = default;
+    SluFactor(const SluFactor &) = delete;
+    SluFactor &operator=(const SluFactor &) = delete;
+    ~SluFactor() {
+        if (hU) (void)csx_free(hU);
+        if (hL) (void)csx_free(hL);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+    }
+};
+
+void destroy(SluFactor *F) { delete F; }
+
+static inline unsigned slu_blocks(int64_t items) { return (unsigned)((items + 255) / 256); }
+
+// The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
+// into L.x / Ut.x when no column broke down.  *ok: 1 committed, 0 breakdown (L, Ut untouched).  Synchronises.
+static int slu_run(SluFactor *F, const double *Ax, double tau, int *ok) {
+    hipStream_t s = ctx().stream;
+    Csc *L = csc(F->hL), *U = csc(F->hU);
+    if (!L || !U || !L->x || !U->x || L->nnz != F->lnz || U->nnz != F->lnz) return CSX_EINVAL;
+    const int32_t n = F->n;
+    F->launches = F->level_launches = F->run_launches = 0;
+    const int hinit[3] = {SLU_NONE, 0, 0};
+    const unsigned long long sinit[6] = {0ull, 0ull, ~0ull, 0ull, 0ull, 0ull};
+    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(chol_scatter(F->lnz, F->winL, Ax, F->Lx));
+    CSX_TRY(chol_scatter(F->lnz, F->winU, Ax, F->Ux));
+    const std::vector<int32_t> &lp = F->level_ptr_h;
+    const int32_t nlev = (int32_t)lp.size() - 1;
+    for (int32_t l = 0; l < nlev;) {
+        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
+        if (cnt > SLU_WAVES) {
+            hipLaunchKernelGGL(k_slu_level, dim3((unsigned)((cnt + SLU_WAVES - 1) / SLU_WAVES)), dim3(64 * SLU_WAVES), 0, s,
+                               F->level_cols + lp[(size_t)l], cnt, L->p, L->i, F->Lx.get(), F->Ux.get(), F->rp.get(), F->rc.get(),
+                               F->rpos.get(), tau, F->flags.get());
+            F->level_launches++;
+            l++;
+            continue;
+        }
+        int32_t e = l + 1;   // a run of narrow levels: one workgroup, at most SLU_RUN_LEVELS levels a launch
+        while (e < nlev && lp[(size_t)e + 1] - lp[(size_t)e] <= SLU_WAVES) e++;
+        for (int32_t a = l; a < e; a += SLU_RUN_LEVELS) {
+            hipLaunchKernelGGL(k_slu_run, dim3(1), dim3(64 * SLU_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), a,
+                               std::min(a + SLU_RUN_LEVELS, e), L->p, L->i, F->Lx.get(), F->Ux.get(), F->rp.get(), F->rc.get(),
+                               F->rpos.get(), tau, F->flags.get());
+            F->run_launches++;
+        }
+        l = e;
+    }
+    F->launches = F->level_launches + F->run_launches;
+    if (n > 0)
+        hipLaunchKernelGGL(k_slu_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, F->Lx.get(), F->Ux.get(),
+                           F->stats.get());
+    (void)hipEventRecord(F->ev_b, s);
+    int hflags[3] = {SLU_NONE, 0, 0};
+    unsigned long long hst[6] = {0, 0, 0, 0, 0, 0};
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("csx_slu: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(s);
+        return CSX_ERUNTIME;
+    }
+    float ms = 0.0f;
+    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    F->perturbed = hflags[1];
+    F->long_cols = hflags[2];
+    F->breakdown = hflags[0] == SLU_NONE ? -1 : hflags[0];
+    *ok = F->breakdown < 0 ? 1 : 0;
+    if (!*ok) return CSX_OK;
+    F->pos = (int64_t)hst[0];
+    F->neg = (int64_t)hst[1];
+    if (n == 0) hst[2] = 0;
+    std::memcpy(&F->min_d, &hst[2], 8);
+    std::memcpy(&F->max_d, &hst[3], 8);
+    std::memcpy(&F->max_l, &hst[4], 8);
+    std::memcpy(&F->max_u, &hst[5], 8);
+    if (F->lnz) {
+        CSX_HIP(hipMemcpyAsync(L->x, F->Lx.get(), (size_t)F->lnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+        CSX_HIP(hipMemcpyAsync(U->x, F->Ux.get(), (size_t)F->lnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
+    for (Csc *M : {L, U}) {   // (copies of the old values)
+        M->rows.reset();
+        M->tiled.reset();
+    }
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+// M (pattern only): column c = column c of A1 followed by column c of A1', A1 = A(prow, :); a1i: A1's row indices (A's when
+// prinv is null)
+static int slu_symmetrised(const Csc *A, const int32_t *prinv, DevBuf<int32_t> &a1i, Csc *M) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = A->n, anz = A->nnz;
+    const int32_t *rows = A->i;
+    if (prinv) {
+        CSX_TRY(a1i.alloc((size_t)anz));
+        if (anz) hipLaunchKernelGGL(k_slu_sym_rows, dim3(slu_blocks(anz)), dim3(256), 0, s, (int64_t)anz, A->i, prinv, a1i.get());
+        CSX_LAUNCH_CHECK();
+        rows = a1i.get();
+    }
+    Csc A1, T;
+    A1.owns = false;
+    A1.m = A1.n = n;
+    A1.nnz = anz;
+    A1.p = A->p;
+    A1.i = const_cast<int32_t *>(rows);
+    CSX_TRY(transpose_device(&A1, false, &T));
+    M->m = M->n = n;
+    M->nnz = 2 * anz;
+    CSX_TRY(dalloc(&M->p, (size_t)n + 1));
+    CSX_TRY(dalloc(&M->i, (size_t)M->nnz));
+    hipLaunchKernelGGL(k_slu_sym_ptr, dim3(slu_blocks((int64_t)n + 1)), dim3(256), 0, s, n, A->p, T.p, M->p);
+    hipLaunchKernelGGL(k_slu_sym_fill, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, rows, T.p, T.i, M->i);
+    CSX_LAUNCH_CHECK();
+    CSX_HIP(hipStreamSynchronize(s));   // T goes out of scope
+    return CSX_OK;
+}
+
+static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *prow, const int32_t *pinv, SluFactor *F) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = A->n;
+    F->n = n;
+    F->anz = A->nnz;
+    F->lnz = cp[n];
+    if (cp[0] != 0 || F->lnz < n || A->nnz > 0x3fffffff) return CSX_EINVAL;
+    std::vector<int32_t> prinv;
+    if (prow) {   // must be a permutation of 0..n-1
+        prinv.assign((size_t)n, -1);
+        for (int32_t k = 0; k < n; k++) {
+            if (prow[k] < 0 || prow[k] >= n || prinv[(size_t)prow[k]] >= 0) {
+                set_error("csx_slu_factor: prow is not a permutation");
+                return CSX_EINVAL;
+            }
+            prinv[(size_t)prow[k]] = k;
+        }
+    }
+    if (!A->trusted) CSX_TRY(csc_validate(A));
+    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
+    CSX_TRY(F->flags.alloc(3));
+    CSX_TRY(F->stats.alloc(6));
+    CSX_HIP(hipEventCreate(&F->ev_a));
+    CSX_HIP(hipEventCreate(&F->ev_b));
+    std::unique_ptr<Csc> L(new Csc());
+    L->m = L->n = n;
+    L->nnz = F->lnz;
+    if (n == 0) {
+        CSX_TRY(dalloc(&L->p, 1));
+        CSX_HIP(hipMemsetAsync(L->p, 0, sizeof(int32_t), s));
+        CSX_TRY(dalloc(&L->i, 0));
+        F->level_ptr_h.assign(1, 0);
+    } else {
+        DevBuf<int32_t> d_prinv, d_pinv, a1i;
+        if (prow) CSX_TRY(upload(d_prinv, prinv));
+        Csc M;
+        CSX_TRY(slu_symmetrised(A, prow ? d_prinv.get() : nullptr, a1i, &M));
+        CSX_TRY(chol_symbolic_device(&M, parent, cp, pinv, &L->p, &L->i, &F->rp, &F->rc, &F->rpos, nullptr));   // (checks S and pinv)
+        std::vector<int32_t> cols;
+        ldl_levels(n, parent, F->level_ptr_h, cols);
+        CSX_TRY(upload(F->level_cols, cols));
+        CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+        CSX_TRY(F->winL.alloc((size_t)F->lnz));
+        CSX_TRY(F->winU.alloc((size_t)F->lnz));
+        if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
+        CSX_HIP(hipMemsetAsync(F->winL, 0xff, (size_t)F->lnz * sizeof(int32_t), s));
+        CSX_HIP(hipMemsetAsync(F->winU, 0xff, (size_t)F->lnz * sizeof(int32_t), s));
+        CSX_HIP(hipMemsetAsync(F->flags, 0, sizeof(int), s));
+        hipLaunchKernelGGL(k_slu_entry_map, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, A->i,
+                           prow ? d_prinv.get() : nullptr, pinv ? d_pinv.get() : nullptr, L->p, L->i, F->winL.get(), F->winU.get(),
+                           F->flags.get());
+        CSX_LAUNCH_CHECK();
+        int bad = 0;
+        CSX_HIP(hipMemcpyAsync(&bad, F->flags.get(), sizeof(int), hipMemcpyDeviceToHost, s));
+        CSX_HIP(hipStreamSynchronize(s));   // (cols, level_ptr_h and the permutations have landed too)
+        if (bad) {
+            set_error("csx_slu_factor: an entry of A has no slot in the pattern (S is not A's)");
+            return CSX_EINVAL;
+        }
+    }
+    CSX_TRY(dalloc(&L->x, (size_t)F->lnz));
+    CSX_TRY(F->utx.alloc((size_t)F->lnz));
+    CSX_TRY(F->Lx.alloc((size_t)F->lnz));
+    CSX_TRY(F->Ux.alloc((size_t)F->lnz));
+    std::unique_ptr<Csc> U(new Csc());
+    U->owns = false;   // L's pattern, the factor's values
+    U->m = U->n = n;
+    U->nnz = F->lnz;
+    U->p = L->p;
+    U->i = L->i;
+    U->x = F->utx.get();
+    F->hL = put(K_CSC, L.release());
+    F->hU = put(K_CSC, U.release());
+    return CSX_OK;
+}
+
+}  // namespace csx
+
+using namespace csx;
+
+extern "C" int csx_slu_factor(csx_handle_t hA, const int32_t *parent, const int32_t *cp, const int32_t *prow, const int32_t *pinv,
+                              double tau, csx_handle_t *out, int *ok) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !out || !ok || !A->x || A->m != A->n || !cp || (A->n > 0 && !parent) || !(tau >= 0.0)) return CSX_EINVAL;
+    *out = 0;
+    *ok = 0;
+    std::unique_ptr<SluFactor> F(new SluFactor());
+    CSX_TRY(slu_build(A, parent, cp, prow, pinv, F.get()));
+    CSX_TRY(slu_run(F.get(), A->x, tau, ok));
+    if (*ok) *out = put(K_SLUFACTOR, F.release());
+    return CSX_OK;
+}
+
+extern "C" int csx_slu_refactor(csx_handle_t h, csx_handle_t hA2, double tau, int *ok) {
+    CSX_TRY(require_ready());
+    SluFactor *F = (SluFactor *)get(h, K_SLUFACTOR);
+    if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
+    *ok = -1;
+    const double *x2 = nullptr;
+    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
+    if (!x2) {
+        set_error("csx_slu_refactor: A2 does not have the pattern (or the length) of the factored matrix");
+        return CSX_EINVAL;   // nothing changes
+    }
+    return slu_run(F, x2, tau, ok);
+}
+
+extern "C" int csx_slu_parts(csx_handle_t h, csx_handle_t *L, csx_handle_t *Ut) {
+    CSX_TRY(require_ready());
+    SluFactor *F = (SluFactor *)get(h, K_SLUFACTOR);
+    if (!F || !L || !Ut) return CSX_EINVAL;
+    *L = F->hL;
+    *Ut = F->hU;
+    return CSX_OK;
+}
+
+extern "C" int csx_slu_info(csx_handle_t h, int64_t *info) {
+    CSX_TRY(require_ready());
+    SluFactor *F = (SluFactor *)get(h, K_SLUFACTOR);
+    if (!F || !info) return CSX_EINVAL;
+    info[0] = F->n;
+    info[1] = F->lnz;
+    info[2] = (int64_t)F->level_ptr_h.size() - 1;
+    info[3] = F->launches;
+    info[4] = F->level_launches;
+    info[5] = F->run_launches;
+    info[6] = F->perturbed;
+    info[7] = F->breakdown;
+    info[8] = F->kernel_us;
+    info[9] = F->long_cols;
+    info[10] = SLU_ACC;
+    info[11] = SLU_RUN_LEVELS;
+    info[12] = F->pos;
+    info[13] = F->neg;
+    return CSX_OK;
+}
+
+extern "C" int csx_slu_window(int32_t *entries, int32_t *run_levels) {   // (no device needed)
+    if (!entries || !run_levels) return CSX_EINVAL;
+    *entries = SLU_ACC;
+    *run_levels = SLU_RUN_LEVELS;
+    return CSX_OK;
+}
+
+extern "C" int csx_slu_stats(csx_handle_t h, double *out) {
+    CSX_TRY(require_ready());
+    SluFactor *F = (SluFactor *)get(h, K_SLUFACTOR);
+    if (!F || !out) return CSX_EINVAL;
+    out[0] = F->min_d;
+    out[1] = F->max_d;
+    out[2] = F->max_l;
+    out[3] = F->max_u;
+    return CSX_OK;
+}

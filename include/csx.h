@@ -914,6 +914,55 @@ int csx_block_div_rows(csx_handle_t X, csx_handle_t d, int64_t rows, int32_t nrh
 int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
                  const int32_t *Li, double tau, double *Lx, double *d, int64_t *info);
 
+/* ---- L U with static pivots: general unsymmetric matrices in one connected piece (slusol_factor) --------
+ * Definition.  A is a square CSC matrix with values; prow a row permutation or NULL, A1 = A(prow, :) (row k of A1 is row prow[k]
+ * of A: a matching puts a zero-free diagonal there); pinv a symmetric permutation or NULL, C = P A1 P' (C(pinv[i], pinv[j]) =
+ * A1(i, j)); S = (parent, cp) the symbolic Cholesky analysis of the pattern of A1 + A1' under pinv (csx_schol of that pattern).
+ * Of duplicate entries of A the last counts.  L and Ut are two matrices on ONE pattern, the Cholesky pattern of S (L.p = Ut.p =
+ * cp; rows ascending, the diagonal first): L is unit lower triangular with the 1.0 stored, column k of Ut is row k of U with the
+ * pivot U(k,k) first, so U = Ut'.  L U = C up to rounding.  No pivot search.
+ * Values, compiled without contraction on host and device:
+ *   for every column j (any order that puts descendants in the elimination tree first):
+ *     accL[r] = C(r, j), accU[r] = C(j, r) for the rows r >= j of column j of the pattern (0.0 in fill and one-sided slots)
+ *     for every column k < j with (j,k) in the pattern, k ASCENDING:
+ *       l = L(j,k), u = Ut(j,k)
+ *       for every stored p of column k from the slot of row j to the column's end, r = L.i[p]:
+ *         accL[r] = accL[r] - L.x[p] * u;  accU[r] = accU[r] - Ut.x[p] * l      (product rounded, then the subtraction rounded)
+ *     d = accU[j]                                                               (accL[j] has the same bits)
+ *     if tau > 0 and |d| < tau:  d = copysign(tau, d), counted as a perturbed pivot
+ *     if d == 0 or d is not finite:  breakdown at j (the smallest such j is reported)
+ *     Ut(j,j) = d, Ut(r,j) = accU[r];  L(j,j) = 1.0, L(r,j) = accL[r] / d        (r > j; IEEE division)
+ *   On the device one wave owns a column and applies its updates one after another: L.x and Ut.x are byte-equal to csx_slu_host,
+ *   the same on every run.  No floating-point atomics.
+ * csx_slu_factor: *ok = 1 and a NEW factor handle (csx_free) that keeps the analysis (pattern and row view, the two entry maps,
+ *   A's pattern, height levels of the elimination tree) and owns L and Ut; *ok = 0 and *F = 0 on breakdown.  tau: the
+ *   perturbation threshold (0: none).  CSX_EINVAL for a pattern-only or non-square A, an S or pinv that does not belong to the
+ *   pattern of A1 + A1', a prow that is not a permutation, tau < 0 or NaN.
+ * csx_slu_refactor: new values on the kept analysis, A2 as for csx_ldl_refactor (*ok = -1 and CSX_EINVAL for a foreign pattern
+ *   or length, nothing changed); computed into scratch and copied over L.x and Ut.x only without a breakdown (*ok = 1); on
+ *   breakdown (*ok = 0) both factors and every plan made from them are exactly as before.  The addresses never change.
+ * csx_slu_parts: BORROWED handles of L and Ut (CSC, sharing p and i): the factor owns them, they die with it.
+ * csx_slu_info: info[14] = n, entries of the pattern, height levels, numeric launches of the last run, launches of the level
+ *   kernel, launches of the run walker (one workgroup walking at most `run cap` consecutive levels of at most 4 columns each per
+ *   launch), perturbed pivots of the last run, the smallest broken column of the last run or -1, microseconds of the last run
+ *   between two events, the columns of the last run updated in place (longer than the LDS window; counted by the kernels), the
+ *   LDS window in entries, the run cap in levels, positive pivots, negative pivots (both of the committed factor).
+ * csx_slu_stats: out[4] = min |d|, max |d|, max |l|, max |u| off the diagonal of the committed factor (0.0 where there is none).
+ * csx_slu_window: the LDS window in entries and the run cap in levels, without a device or a factor.
+ * csx_slu_host: the rule on host arrays, no device: Lp / Li the pattern, Lx and Utx (Lp[n] doubles each) written; info[4] =
+ *   positive pivots, negative pivots, perturbed pivots, the smallest broken column or -1 (then Lx and Utx are not a
+ *   factorisation).  CSX_EINVAL for a malformed pattern, a prow or pinv that is not a permutation, an entry of C without a slot,
+ *   tau < 0 or NaN. */
+int csx_slu_factor(csx_handle_t A, const int32_t *parent, const int32_t *cp, const int32_t *prow, const int32_t *pinv, double tau,
+                   csx_handle_t *F, int *ok);
+int csx_slu_refactor(csx_handle_t F, csx_handle_t A2, double tau, int *ok);
+int csx_slu_parts(csx_handle_t F, csx_handle_t *L, csx_handle_t *Ut);
+int csx_slu_info(csx_handle_t F, int64_t *info);
+int csx_slu_stats(csx_handle_t F, double *out);
+int csx_slu_window(int32_t *entries, int32_t *run_levels);
+int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *prow, const int32_t *pinv,
+                 const int32_t *Lp, const int32_t *Li, double tau, double *Lx, double *Utx, int64_t *info);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
