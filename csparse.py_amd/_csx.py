@@ -194,6 +194,16 @@ _PROTOS = {
     "csx_slu_stats": [H, _f64p],
     "csx_slu_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "csx_slu_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
+    "csx_hqr_symbolic_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                              _i32p, _i32p, _i32p, _i32p],
+    "csx_hqr_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
+                     _i32p, _i32p, _f64p, _i32p, _i32p, _f64p, _f64p],
+    "csx_hqr_factor": [H, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_hqr_refactor": [H, H, C.POINTER(C.c_int)],
+    "csx_hqr_parts": [H, C.POINTER(H), C.POINTER(H), C.POINTER(H)],
+    "csx_hqr_info": [H, C.POINTER(C.c_int64)],
+    "csx_hqr_stats": [H, _f64p],
+    "csx_hqr_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -278,6 +288,14 @@ def slu_window():
     (csx_slu.hip SLU_ACC, SLU_RUN_LEVELS), asked of the library; no GPU needed"""
     a, b = C.c_int32(0), C.c_int32(0)
     check(load().csx_slu_window(C.byref(a), C.byref(b)), "csx_slu_window")
+    return a.value, b.value
+
+
+def hqr_window():
+    """(slots of a column that the Householder QR column kernels keep in LDS, levels one launch of its walker takes)
+    (csx_hqr.hip HQR_ACC, HQR_RUN_LEVELS), asked of the library; no GPU needed"""
+    a, b = C.c_int32(0), C.c_int32(0)
+    check(load().csx_hqr_window(C.byref(a), C.byref(b)), "csx_hqr_window")
     return a.value, b.value
 
 

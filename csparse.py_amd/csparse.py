@@ -3122,6 +3122,189 @@ def qrsol_factor(A, order=0):
     return _Solver()
 
 
+_HQR_INFO = ("m", "n", "m2", "vnz", "rnz", "levels", "launches", "level_launches", "run_launches", "long_columns",
+             "zero_diagonals", "breakdown", "kernel_us", "window", "run_levels")
+
+
+def hqrsol_factor(A, order=0):
+    """Factor once by sparse Householder QR ON THE DEVICE, for a matrix in one connected piece: cs_sqr on the
+    host, then V, R and beta by csx_hqr_factor -- a wave per column over the height levels of the column elimination tree, on
+    patterns known before a value is read.  m >= n factors A (least squares); m < n factors A' (cs_transpose on the device) and
+    solves minimum-norm; order goes to cs_sqr as in qrsol_factor.  Householder QR searches for no pivot and is backward stable
+    as it stands: no perturbation, no matching; the only breakdown is a non-finite diagonal of R.
+    V.p, V.i, R.p, R.i are cs_qr's exactly.  V.x, R.x and beta are byte-equal to csx_hqr_host and the same on every run, but
+    equal to cs_qr's ONLY TO ROUNDING: a reflection's dot product is 64 strided partial sums and a fixed tree here, entry by
+    entry there.  R is stored n-by-n (nothing of cs_qr's m2-by-n R lies below row n).
+    None for a non-CSC A, a failed ordering, or a breakdown.  Otherwise a solver:
+    solve(b, trans=False): m >= n: cs_qrsol's first sequence, x(pinv) = b, Q' x, R \\ x, x(q) (qrsol_factor's); m < n: its second,
+      x = b(q), R' \\ x, Q x, x(pinv), the minimum-norm solution; trans=True (square A only: A' x = b) is the second sequence on
+      A's own factors.  b a list (overwritten with x, True returned) or a dvec block of as many rows as the system has equations
+      (a new dvec of the unknowns returned); every column of a block is byte-equal to the list solve.
+    refactor(A2): new values on the kept analysis, A2 as for lusol_factor's refactor: True; False with the factors and the
+      solves exactly as before on breakdown; ValueError for another pattern or length.  Byte-equal to a fresh factor.
+    backward_error(x, b, trans=False), refine(b, maxit=5, trans=False), condest(): _Refinable's and _condest, for a SQUARE A;
+      ValueError for a rectangular one (least-squares refinement is not offered).  logabsdet(): the sum of log |r_kk| (math.fsum),
+      square A.  info(): m, n, m2 of the factored matrix, vnz, rnz, levels, launches = level_launches + run_launches of the
+      last run, long_columns (updated in place: more slots than the LDS `window`), run_levels, zero_diagonals, breakdown,
+      kernel_us, min_abs_r, max_abs_r, transposed.  factors: .L = V, .U = R, .B = beta; symbolic: cs_sqr's S."""
+    if not CS_CSC(A) or order not in (0, 1, 2, 3):
+        return None
+    if not _meta(A)[1]:
+        raise TypeError("'NoneType' object is not subscriptable")
+    tall = A.m >= A.n
+    Cm = A if tall else cs_transpose(A, True)
+    S = cs_sqr(order, Cm, True) if Cm is not None else None
+    if S is None:
+        return None
+    m, n, m2 = Cm.m, Cm.n, S.m2
+    square = A.m == A.n
+    lib = _csx.lib()
+    q = None if S.q is None else _csx.i32(S.q)
+    pinv = _csx.i32(S.pinv[:m])
+    hF, ok = _csx.new_handle(), _csx.C.c_int(0)
+    with _Resident(Cm) as dC:
+        st = lib.csx_hqr_factor(dC.handle, _csx.pi(q), _csx.pi(_csx.i32(S.parent)), _csx.pi(pinv), _csx.pi(_csx.i32(S.leftmost)),
+                                m2, hF, ok)
+    _csx.check(st, "csx_hqr_factor")
+    if not ok.value:
+        return None
+    hV, hR, hB = _csx.new_handle(), _csx.new_handle(), _csx.new_handle()
+    _csx.check(lib.csx_hqr_parts(hF, hV, hR, hB), "csx_hqr_parts")
+    # V, R and beta are the factor's (borrowed handles): the wrappers free the plans cached on them and the factor, never the parts
+    N = csn()
+    N.L = cs_pin(_from_device(hV, lambda nnz: max(nnz, 1)))
+    N.U = cs_pin(_from_device(hR, lambda nnz: max(nnz, 1)))
+    devV, devR = N.L._dev, N.U._dev
+    devV._fin.detach()
+    devV._fin = weakref.finalize(devV, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), devV.plans, hF)
+    devR._fin.detach()
+    devR._fin = weakref.finalize(devR, _DevMatrix._release, None, devR.plans)
+    devR._keep = devV                                # R lives in the factor that V's wrapper frees
+    N.pinv = None
+
+    def read_beta():
+        out = np.zeros(max(n, 1))
+        if n:
+            _csx.check(lib.csx_vec_download(hB, _csx.pd(out), n), "csx_vec_download")
+        return out[:n].tolist()
+
+    N.B = read_beta()
+    hq, keep_q = _perm_handle(q, n)
+    hp, keep_p = _perm_handle(pinv, m)
+    tmap = []                                        # m < n: A's storage order -> A''s, made by the first refactor with values
+
+    class _Solver(_Refinable):
+        factors, symbolic = N, S
+
+        def __init__(self):
+            self._devs = (devV, devR)                # keep V, R and the factor alive
+            self._fin = weakref.finalize(self, lambda hs: [_csx.free(h) for h in hs if h is not None], [keep_q, keep_p])
+            self._A2, self._norm = A, None
+            self._refine_init(A, A.n)
+
+        def _block(self, db, second):
+            """db: the right-hand sides as a dvec block; second: cs_qrsol's second sequence (R' \\ x, Q x) on these factors"""
+            k = db.k
+            X = dvec(m2, k)                          # zeros: the fictitious rows stay zero
+            if not second:
+                _csx.check(lib.csx_permute_vec(hp, db.handle, X.handle, m, k, 1), "csx_permute_vec")     # x(pinv) = b
+                _csx.check(lib.csx_happly(devV.handle, hB, X.handle, k, 1), "csx_happly")
+                _csx.check(lib.csx_tri_solve(_plan(devR, TRI_U), X.handle, k), "csx_tri_solve")          # the first n rows
+                out = dvec(n, k)
+                _csx.check(lib.csx_permute_vec(hq, X.handle, out.handle, n, k, 1), "csx_permute_vec")    # x(q) = x
+            else:
+                _csx.check(lib.csx_permute_vec(hq, db.handle, X.handle, n, k, 0), "csx_permute_vec")     # x = b(q)
+                _csx.check(lib.csx_tri_solve(_plan(devR, TRI_UT), X.handle, k), "csx_tri_solve")
+                _csx.check(lib.csx_happly(devV.handle, hB, X.handle, k, 0), "csx_happly")
+                out = dvec(m, k)
+                _csx.check(lib.csx_permute_vec(hp, X.handle, out.handle, m, k, 0), "csx_permute_vec")    # x = x(pinv)
+            return out
+
+        def _solve_block(self, blk, trans, from_list):
+            out = self._block(blk, bool(trans))
+            _csx.check(lib.csx_vec_copy(out.handle, blk.handle), "csx_vec_copy")
+            return blk
+
+        def solve(self, b, trans=False):
+            if trans and not square:
+                raise ValueError("hqrsol_factor: trans=True needs a square matrix")
+            second = bool(trans) or not tall
+            rows_in, rows_out = (n, m) if second else (m, n)
+            host = None if isinstance(b, dvec) else b
+            if host is not None and len(host) < rows_in:
+                raise IndexError("list index out of range")
+            db = b if host is None else dvec(np.asarray(b[:rows_in], dtype=np.float64))
+            if db.n < rows_in:
+                raise IndexError("list index out of range")
+            out = self._block(db, second)
+            if host is not None:
+                host[:rows_out] = out.numpy().reshape(-1)[:rows_out].tolist()
+                return True
+            return out
+
+        def refactor(self, A2):
+            A2 = _refactor_input(A, A2)
+            given = A2
+            if not tall:                             # the factored matrix is A': its values in ITS storage order
+                if isinstance(A2, cs):
+                    given = cs_transpose(A2, True)
+                else:
+                    if not tmap:
+                        nnz = _meta(A)[0]
+                        I = cs_spalloc(A.m, A.n, nnz, True, False)
+                        ap, ai = _pattern_np(A)
+                        I.p, I.i, I.x = ap.tolist(), (ai.tolist() or [0]), (np.arange(nnz, dtype=np.float64).tolist() or [0.0])
+                        tmap.append(np.asarray(cs_transpose(I, True).x[:nnz], dtype=np.int64))
+                    given = dvec(A2.numpy().reshape(-1)[tmap[0]])
+            ok = _csx.C.c_int(0)
+            _refactor_call(given, lambda h2: lib.csx_hqr_refactor(hF, h2, ok), ok)
+            if ok.value == 1:
+                _refactored(N.L, devV)
+                _refactored(N.U, devR)
+                N.B[:] = read_beta()
+                self._A2, self._norm = A2, None
+                self._operator_changed()
+            return ok.value == 1
+
+        def _square_only(self, what):
+            if not square:
+                raise ValueError("hqrsol_factor: %s needs a square matrix (least-squares refinement is not offered)" % what)
+
+        def backward_error(self, x, b, trans=False):
+            self._square_only("backward_error")
+            return _Refinable.backward_error(self, x, b, trans)
+
+        def refine(self, b, maxit=5, trans=False):
+            self._square_only("refine")
+            return _Refinable.refine(self, b, maxit, trans)
+
+        def condest(self):
+            self._square_only("condest")
+            if self._norm is None:
+                self._norm = _refactor_norm(A, self._A2)
+            return _condest(self._norm, lambda v, t: self._block(dvec(v), bool(t)).numpy().reshape(-1), n)
+
+        def logabsdet(self):
+            """log |det A| of a square A: the sum of log |r_kk| correctly rounded (math.fsum); -inf with a zero diagonal"""
+            self._square_only("logabsdet")
+            Rp = np.empty(n + 1, dtype=np.int32)
+            x = np.empty(max(devR.info()[2], 1), dtype=np.float64)
+            _csx.check(lib.csx_csc_download(devR.handle, _csx.pi(Rp), None, _csx.pd(x)), "csx_csc_download")
+            with np.errstate(divide="ignore"):
+                return math.fsum(np.log(np.abs(x[Rp[1:] - 1])).tolist())
+
+        def info(self):
+            raw = (_csx.C.c_int64 * len(_HQR_INFO))()
+            st = (_csx.C.c_double * 2)()
+            _csx.check(lib.csx_hqr_info(hF, raw), "csx_hqr_info")
+            _csx.check(lib.csx_hqr_stats(hF, st), "csx_hqr_stats")
+            out = {name: int(v) for name, v in zip(_HQR_INFO, raw)}
+            out.update(min_abs_r=st[0], max_abs_r=st[1], transposed=not tall)
+            return out
+
+    return _Solver()
+
+
 def device_name():
     return _csx.device_info()
 

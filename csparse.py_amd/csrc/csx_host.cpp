@@ -1422,3 +1422,165 @@ extern "C" int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, con
     info[3] = broke;
     return CSX_OK;
 }
+
+// ---- Householder QR on a pattern known before the values (csx_hqr.hip) ----------------------------------------
+// The loop of csx_qr_host with the values left out: V.p, V.i (the diagonal first, then the rows in the order that loop finds
+// them) and R.p, R.i (the order the reflections are applied in, the diagonal last) -- csx_qr_host's own on the same analysis.
+// Unlike that loop it trusts nothing: CSX_EINVAL for an analysis that is not this matrix's (an index out of range, a walk that
+// leaves the tree below k, a row without a slot, a column whose rows never reached its parent), so that what passes has the
+// two properties the device schedule stands on: every c in R(:,k) is a descendant of k, and every row of V(:,c) is a slot of
+// R(:,k) or V(:,k).
+namespace csx {
+int hqr_symbolic(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q, const int32_t *parent,
+                 const int32_t *pinv, const int32_t *leftmost, std::vector<int32_t> &Vp, std::vector<int32_t> &Vi,
+                 std::vector<int32_t> &Rp, std::vector<int32_t> &Ri) {
+    if (m < 0 || n < 0 || m < n || m2 < m || !Ap || Ap[0] != 0 || (n > 0 && !parent) || (m > 0 && (!pinv || !leftmost)))
+        return CSX_EINVAL;
+    for (int32_t k = 0; k < n; k++)
+        if (Ap[k + 1] < Ap[k] || (parent[k] != -1 && (parent[k] <= k || parent[k] >= n))) return CSX_EINVAL;
+    if (Ap[n] > 0 && !Ai) return CSX_EINVAL;
+    {
+        std::vector<char> seen((size_t)m2, 0), seenq((size_t)n, 0);
+        for (int32_t i = 0; i < m; i++)
+            if (pinv[i] < 0 || pinv[i] >= m2 || seen[(size_t)pinv[i]]++) return CSX_EINVAL;
+        for (int32_t k = 0; q && k < n; k++)
+            if (q[k] < 0 || q[k] >= n || seenq[(size_t)q[k]]++) return CSX_EINVAL;
+    }
+    std::vector<int32_t> stamp((size_t)m2, -1);      // stamp[r] == k: row / column r already collected for column k
+    std::vector<int32_t> order((size_t)n > 0 ? (size_t)n : 1), path((size_t)n > 0 ? (size_t)n : 1);
+    std::vector<char> passed((size_t)n, 0);          // V(:,c)'s rows have reached V(:,parent[c])
+    constexpr size_t LIMIT = 0x7ffffff0;
+    Vp.assign((size_t)n + 1, 0);
+    Rp.assign((size_t)n + 1, 0);
+    Vi.clear();
+    Ri.clear();
+    for (int32_t k = 0; k < n; k++) {
+        if (Vi.size() > LIMIT || Ri.size() > LIMIT) return CSX_EINVAL;
+        Rp[(size_t)k] = (int32_t)Ri.size();
+        Vp[(size_t)k] = (int32_t)Vi.size();
+        stamp[(size_t)k] = k;                        // the diagonal position leads V(:,k)
+        Vi.push_back(k);
+        int32_t front = n;                           // order[front..n) = reflections to apply, children before parents
+        const int32_t col = q ? q[k] : k;
+        for (int32_t p = Ap[col]; p < Ap[col + 1]; p++) {
+            if (Ai[p] < 0 || Ai[p] >= m) return CSX_EINVAL;
+            int32_t len = 0;
+            for (int32_t c = leftmost[Ai[p]];; c = parent[c]) {
+                if (c < 0 || c > k) return CSX_EINVAL;      // the walk must end in k
+                if (stamp[(size_t)c] == k) break;
+                path[(size_t)len++] = c;
+                stamp[(size_t)c] = k;
+            }
+            while (len > 0) order[(size_t)--front] = path[(size_t)--len];
+            const int32_t r = pinv[Ai[p]];
+            if (r < k && stamp[(size_t)r] != k) return CSX_EINVAL;   // a row above the diagonal that is no entry of R(:,k)
+            if (r > k && stamp[(size_t)r] < k) {     // a row below the diagonal not yet in V(:,k)'s pattern
+                Vi.push_back(r);
+                stamp[(size_t)r] = k;
+            }
+        }
+        for (int32_t t = front; t < n; t++) {
+            const int32_t c = order[(size_t)t];
+            Ri.push_back(c);
+            if (parent[c] == k) {                    // V(:,c)'s rows below c pass on to V(:,k)
+                passed[(size_t)c] = 1;
+                for (int32_t p = Vp[(size_t)c] + 1; p < Vp[(size_t)c + 1]; p++) {
+                    const int32_t r = Vi[(size_t)p];
+                    if (r < k) return CSX_EINVAL;
+                    if (stamp[(size_t)r] < k) {
+                        stamp[(size_t)r] = k;
+                        Vi.push_back(r);
+                    }
+                }
+            } else if (!passed[(size_t)c]) {
+                return CSX_EINVAL;
+            }
+        }
+        Ri.push_back(k);
+    }
+    Rp[(size_t)n] = (int32_t)Ri.size();
+    Vp[(size_t)n] = (int32_t)Vi.size();
+    return CSX_OK;
+}
+}  // namespace csx
+
+extern "C" int csx_hqr_symbolic_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q,
+                                     const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t vcap,
+                                     int32_t rcap, int32_t *Vp, int32_t *Vi, int32_t *Rp, int32_t *Ri) {
+    if (!Vp || !Rp || (n > 0 && (!Vi || !Ri))) return CSX_EINVAL;
+    std::vector<int32_t> vp, vi, rp, ri;
+    CSX_TRY(csx::hqr_symbolic(m, n, m2, Ap, Ai, q, parent, pinv, leftmost, vp, vi, rp, ri));
+    if ((int64_t)vi.size() > vcap || (int64_t)ri.size() > rcap) return CSX_EINVAL;
+    std::memcpy(Vp, vp.data(), vp.size() * sizeof(int32_t));
+    std::memcpy(Rp, rp.data(), rp.size() * sizeof(int32_t));
+    if (!vi.empty()) std::memcpy(Vi, vi.data(), vi.size() * sizeof(int32_t));
+    if (!ri.empty()) std::memcpy(Ri, ri.data(), ri.size() * sizeof(int32_t));
+    return CSX_OK;
+}
+
+// cs_house on (head, tail2), statement for statement as csx_qr_host: *v0 the new head of the vector, *b beta, returns s
+static inline double hqr_house(double head, double tail2, double *v0, double *b) {
+#pragma clang fp contract(off)
+    double s;
+    if (tail2 == 0.0) {
+        s = std::fabs(head);
+        *b = head <= 0.0 ? 2.0 : 0.0;
+        *v0 = 1.0;
+    } else {
+        s = std::sqrt(head * head + tail2);
+        *v0 = head <= 0.0 ? head - s : -tail2 / (head + s);
+        *b = -1.0 / (s * *v0);
+    }
+    return s;
+}
+
+// part[0] after the fixed tree over 64 partial sums (what a wave's butterfly leaves in every lane)
+static inline double hqr_tree(double *part) {
+#pragma clang fp contract(off)
+    for (int s = 32; s >= 1; s >>= 1)
+        for (int l = 0; l < s; l++) part[l] = part[l] + part[l + s];
+    return part[0];
+}
+
+// csx_hqr_factor's value rule on host arrays (csx_hqr.hip; the statement is the comment of csx_hqr_factor in
+// include/csx.h): csx_qr_host's arguments and csx_qr_host's patterns; a reflection's dot product and the squared tail of a
+// column are summed in 64 strided partial sums and a fixed tree, every product rounded before it is added or subtracted.
+extern "C" int csx_hqr_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const double *Ax,
+                            const int32_t *q, const int32_t *parent, const int32_t *pinv, const int32_t *leftmost,
+                            int32_t vcap, int32_t rcap, int32_t *Vp, int32_t *Vi, double *Vx, int32_t *Rp, int32_t *Ri,
+                            double *Rx, double *beta) {
+#pragma clang fp contract(off)
+    CSX_TRY(csx_hqr_symbolic_host(m, n, m2, Ap, Ai, q, parent, pinv, leftmost, vcap, rcap, Vp, Vi, Rp, Ri));
+    if ((Ap[n] > 0 && !Ax) || (n > 0 && (!Vx || !Rx || !beta))) return CSX_EINVAL;
+    std::vector<double> work((size_t)m2, 0.0);
+    double part[64];
+    for (int32_t k = 0; k < n; k++) {
+        const int32_t col = q ? q[k] : k;
+        for (int32_t p = Ap[col]; p < Ap[col + 1]; p++) work[(size_t)pinv[Ai[p]]] = Ax[p];
+        for (int32_t t = Rp[k]; t < Rp[k + 1] - 1; t++) {
+            const int32_t c = Ri[t];
+            for (int l = 0; l < 64; l++) part[l] = 0.0;
+            for (int32_t p = Vp[c]; p < Vp[c + 1]; p++) {
+                const int l = (p - Vp[c]) & 63;
+                part[l] = part[l] + Vx[p] * work[(size_t)Vi[p]];
+            }
+            const double tau = hqr_tree(part) * beta[c];
+            for (int32_t p = Vp[c]; p < Vp[c + 1]; p++) work[(size_t)Vi[p]] = work[(size_t)Vi[p]] - Vx[p] * tau;
+            Rx[t] = work[(size_t)c];
+            work[(size_t)c] = 0.0;
+        }
+        const int32_t vstart = Vp[k];
+        for (int32_t p = vstart; p < Vp[k + 1]; p++) {
+            Vx[p] = work[(size_t)Vi[p]];
+            work[(size_t)Vi[p]] = 0.0;
+        }
+        for (int l = 0; l < 64; l++) part[l] = 0.0;
+        for (int32_t p = vstart + 1; p < Vp[k + 1]; p++) {
+            const int l = (p - vstart - 1) & 63;
+            part[l] = part[l] + Vx[p] * Vx[p];
+        }
+        const double tail2 = hqr_tree(part);
+        Rx[Rp[k + 1] - 1] = hqr_house(Vx[vstart], tail2, &Vx[vstart], &beta[k]);
+    }
+    return CSX_OK;
+}

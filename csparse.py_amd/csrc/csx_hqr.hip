@@ -1,0 +1,514 @@
+// Sparse Householder QR of a matrix in one connected piece (the definition is the comment of csx_hqr_factor in
+// include/csx.h).  Householder QR searches for no pivot: the patterns of V and R follow from cs_sqr's analysis and the column
+// elimination tree before a value is read (csx_hqr_symbolic_host), and column k reads only V(:,c) and beta[c] of its descendants
+// c.  So the columns of one height level of the tree are independent, as in csx_ldl.hip and csx_slu.hip.
+//   k_hqr_level   one wave per column of a height level
+//   k_hqr_run     one workgroup walks at most HQR_RUN_LEVELS levels of at most HQR_WAVES columns each, a barrier per level
+//   k_hqr_stats   min / max |r_kk| and the number of exact zeros on R's diagonal
+// Every row a reflection of column k touches is a slot of R(:,k) or of V(:,k): the column's own slots are its accumulators, in
+// wave-private LDS up to HQR_ACC slots and in place in the scratch arrays beyond.  A reflection's dot product is 64 strided
+// partial sums and a butterfly, a fixed order: V.x, R.x and beta are byte-equal to csx_hqr_host, the same on every run.
+// A factor or refactor runs into scratch arrays and is committed only when no diagonal of R came out non-finite.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "csx_internal.h"
+#include "csx_ldl.h"
+
+#pragma clang fp contract(off)
+
+namespace csx {
+
+constexpr int HQR_ACC = 512;          // slots of a column kept in LDS per wave (8 + 4 + 4 bytes each: 32 KB a workgroup); a longer column is updated in place
+constexpr int HQR_WAVES = 4;          // waves per workgroup
+constexpr int HQR_RUN_LEVELS = 256;   // levels one launch of the walker takes (csx_slu.hip's constant): a longer run is several launches
+constexpr int64_t HQR_RUN_WORK = 1 << 24;   // ... and at most this many slot updates (its levels' longest columns summed), so that no
+                                            // launch of one workgroup holds the device for long
+constexpr int HQR_NONE = 0x7fffffff;
+
+// what one lane wrote, every lane of the wave may read
+__device__ __forceinline__ void hqr_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// part[l] + part[l ^ s] for s = 32 .. 1: addition is commutative, so every lane ends with the bytes the fixed tree
+// part[l] = part[l] + part[l + s], l < s, leaves in part[0]
+__device__ __forceinline__ double hqr_butterfly(double part) {
+    for (int s = 32; s >= 1; s >>= 1) part = part + __shfl_xor(part, s);
+    return part;
+}
+
+// ---- one column -----------------------------------------------------------------------------------------------------------------
+// Column k of R and of V.  On entry Rx[Rp[k] ..] and Vx[Vp[k] ..] hold A(:, q[k]) in the column's slots (+0.0 elsewhere) and every
+// descendant of k is finished (its V.x, beta in Vx, beta).  The slots in their natural order -- R's entries before the diagonal,
+// then V's -- are the accumulators; Srow[Sp[k] ..] lists their rows ascending and Sdst the natural slot of each (R.i and V.i are
+// not sorted).  acc / srow / sdst: wave-private LDS (HQR_ACC entries).  flags[0]: the smallest column with a non-finite diagonal
+// (atomicMin), flags[1]: columns that took the in-place path (integer atomicAdd).
+__device__ __forceinline__ void hqr_column(int32_t k, const int32_t *__restrict__ Vp, const int32_t *__restrict__ Vi, double *Vx,
+                                           const int32_t *__restrict__ Rp, const int32_t *__restrict__ Ri, double *Rx, double *beta,
+                                           const int32_t *__restrict__ Sp, const int32_t *__restrict__ Srow,
+                                           const int32_t *__restrict__ Sdst, double *acc, int32_t *srow, int32_t *sdst, int lane,
+                                           int *flags) {
+    const int32_t rb = Rp[k], nr = Rp[k + 1] - rb - 1;   // reflections to apply = entries of R(:,k) before the diagonal
+    const int32_t vb = Vp[k], nv = Vp[k + 1] - vb;
+    const int32_t sb = Sp[k], len = nr + nv;
+    const bool in_lds = len <= HQR_ACC;
+    const int32_t *rows = in_lds ? srow : Srow + sb;
+    const int32_t *dst = in_lds ? sdst : Sdst + sb;
+    if (in_lds) {
+        for (int32_t t = lane; t < len; t += 64) {
+            acc[t] = t < nr ? Rx[rb + t] : Vx[vb + (t - nr)];
+            srow[t] = Srow[sb + t];
+            sdst[t] = Sdst[sb + t];
+        }
+    }
+    hqr_wave_sync();
+    // the accumulator of natural slot s
+    auto at = [&](int32_t s) -> double * { return in_lds ? acc + s : (s < nr ? Rx + rb + s : Vx + vb + (s - nr)); };
+    auto slot_of = [&](int32_t row) -> int32_t { return dst[ldl_find_row(rows, len, row)]; };
+    // Reflections are applied in order, but fetched eight at a time (as ldl_column fetches its updates): lane u reads the
+    // descriptor of reflection t0 + u -- c, the bounds of V(:,c), beta[c], all final -- and the first 64 entries of the eight
+    // columns are requested together and their slots found before the first of them is applied; what is left per reflection is
+    // LDS traffic and the butterfly.  The order of the arithmetic is untouched.
+    constexpr int UQ = 8;
+    for (int32_t t0 = 0; t0 < nr; t0 += UQ) {
+        int32_t cbq = 0, ceq = 0;
+        double bq = 0.0;
+        if (lane < UQ && t0 + lane < nr) {
+            const int32_t cq = Ri[rb + t0 + lane];
+            cbq = Vp[cq];
+            ceq = Vp[cq + 1];
+            bq = beta[cq];
+        }
+        int32_t cb_[UQ], ce_[UQ], s_[UQ];
+        double b_[UQ], v_[UQ];
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            cb_[u] = __builtin_amdgcn_readlane(cbq, u);
+            ce_[u] = __builtin_amdgcn_readlane(ceq, u);      // 0 for an absent reflection: no entries
+            b_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(bq), u),
+                                     __builtin_amdgcn_readlane(__double2loint(bq), u));
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            const int32_t p = cb_[u] + lane;
+            const int32_t pp = p < ce_[u] ? p : cb_[u];      // a valid address either way
+            s_[u] = Vi[pp];
+            v_[u] = Vx[pp];
+        }
+#pragma unroll
+        for (int u = 0; u < UQ; u++) s_[u] = slot_of(s_[u]);  // (rows and their slots do not change while the column is reduced)
+#pragma unroll
+        for (int u = 0; u < UQ; u++) {
+            if (t0 + u >= nr) break;
+            const int32_t cb = cb_[u], ce = ce_[u];
+            const bool head = cb + lane < ce;
+            double part = 0.0;
+            if (head) part = part + v_[u] * *at(s_[u]);
+            for (int32_t p = cb + 64 + lane; p < ce; p += 64) part = part + Vx[p] * *at(slot_of(Vi[p]));
+            const double tau = hqr_butterfly(part) * b_[u];
+            if (head) {
+                double *a = at(s_[u]);
+                *a = *a - v_[u] * tau;
+            }
+            for (int32_t p = cb + 64 + lane; p < ce; p += 64) {
+                double *a = at(slot_of(Vi[p]));
+                *a = *a - Vx[p] * tau;
+            }
+            hqr_wave_sync();   // one reflection after the other: they touch the same rows
+            if (in_lds && lane == 0) Rx[rb + t0 + u] = acc[t0 + u];   // R(c,k): row c is slot t, and no later reflection touches it
+        }
+    }
+    // V(:,k) = what is left below the diagonal; tail2 over everything after the head
+    double part = 0.0;
+    for (int32_t j = 1 + lane; j < nv; j += 64) {
+        const double v = *at(nr + j);
+        if (in_lds) Vx[vb + j] = v;
+        part = part + v * v;
+    }
+    const double tail2 = hqr_butterfly(part);
+    const double head = *at(nr);
+    double s, b, v0;   // cs_house, statement for statement as csx_qr_host
+    if (tail2 == 0.0) {
+        s = fabs(head);
+        b = head <= 0.0 ? 2.0 : 0.0;
+        v0 = 1.0;
+    } else {
+        s = __dsqrt_rn(head * head + tail2);
+        v0 = head <= 0.0 ? head - s : -tail2 / (head + s);
+        b = -1.0 / (s * v0);
+    }
+    hqr_wave_sync();       // every lane has read the head before it is replaced
+    if (lane == 0) {
+        Vx[vb] = v0;
+        Rx[rb + nr] = s;
+        beta[k] = b;
+        if (!isfinite(s)) atomicMin(flags, k);
+        if (!in_lds) atomicAdd(flags + 1, 1);
+    }
+    hqr_wave_sync();
+}
+
+#define HQR_SHARED                                 \
+    __shared__ double s_acc[HQR_WAVES][HQR_ACC];   \
+    __shared__ int32_t s_row[HQR_WAVES][HQR_ACC];  \
+    __shared__ int32_t s_dst[HQR_WAVES][HQR_ACC];
+
+// one wave per column of a level
+__global__ __launch_bounds__(64 * HQR_WAVES) void k_hqr_level(const int32_t *__restrict__ cols, int32_t count,
+                                                             const int32_t *__restrict__ Vp, const int32_t *__restrict__ Vi,
+                                                             double *Vx, const int32_t *__restrict__ Rp,
+                                                             const int32_t *__restrict__ Ri, double *Rx, double *beta,
+                                                             const int32_t *__restrict__ Sp, const int32_t *__restrict__ Srow,
+                                                             const int32_t *__restrict__ Sdst, int *flags) {
+    HQR_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * HQR_WAVES + w;
+    if (c >= count) return;
+    hqr_column(cols[c], Vp, Vi, Vx, Rp, Ri, Rx, beta, Sp, Srow, Sdst, s_acc[w], s_row[w], s_dst[w], lane, flags);
+}
+
+// One workgroup walks the levels [l0, l1), l1 - l0 <= HQR_RUN_LEVELS, each of at most HQR_WAVES columns: wave w takes column w of
+// the level, a barrier between levels makes the finished columns visible to the next.  The trip counts are the level pointers,
+// the same for every wave, so every wave reaches every barrier.
+__global__ __launch_bounds__(64 * HQR_WAVES) void k_hqr_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
+                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Vp,
+                                                           const int32_t *__restrict__ Vi, double *Vx,
+                                                           const int32_t *__restrict__ Rp, const int32_t *__restrict__ Ri,
+                                                           double *Rx, double *beta, const int32_t *__restrict__ Sp,
+                                                           const int32_t *__restrict__ Srow, const int32_t *__restrict__ Sdst,
+                                                           int *flags) {
+    HQR_SHARED
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int32_t l = l0; l < l1; l++) {
+        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
+        if (w < cnt) hqr_column(cols[b + w], Vp, Vi, Vx, Rp, Ri, Rx, beta, Sp, Srow, Sdst, s_acc[w], s_row[w], s_dst[w], lane, flags);
+        __syncthreads();
+    }
+}
+
+// One lane per column: st[0] min |r_kk|, st[1] max |r_kk| -- extrema of the bit patterns of fabs taken as unsigned integers
+// (k_ldl_stats' rule) -- st[2] the number of exact zeros (integer adds); a wave reduces before its lane 0 touches st
+__global__ __launch_bounds__(256) void k_hqr_stats(int32_t n, const int32_t *__restrict__ Rp, const double *__restrict__ Rx,
+                                                   unsigned long long *st) {
+    const int lane = threadIdx.x & 63;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long lo = ~0ull, hi = 0ull, zeros = 0ull;
+    if (k < n) {
+        const double d = Rx[Rp[k + 1] - 1];
+        lo = hi = (unsigned long long)__double_as_longlong(fabs(d));
+        zeros = d == 0.0 ? 1ull : 0ull;
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long a = __shfl_xor(lo, off), b = __shfl_xor(hi, off), z = __shfl_xor(zeros, off);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+        zeros += z;
+    }
+    if (lane == 0 && lo != ~0ull) {
+        atomicMin(st + 0, lo);
+        atomicMax(st + 1, hi);
+        if (zeros) atomicAdd(st + 2, zeros);
+    }
+}
+
+struct HqrLaunch {
+    bool wide;         // k_hqr_level on level l0, or k_hqr_run over the levels [l0, l1)
+    int32_t l0, l1;
+};
+
+struct HqrFactor {
+    int32_t m = 0, n = 0, m2 = 0, anz = 0, vnz = 0, rnz = 0;
+    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
+    DevBuf<int32_t> sp, srow, sdst;         // per column the rows of its slots ascending, and the natural slot of each
+    DevBuf<int32_t> winV, winR;             // entry maps: the entry of A that lands in a slot of V / of R (-1: none)
+    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the column elimination tree
+    std::vector<int32_t> level_ptr_h;
+    std::vector<HqrLaunch> schedule;        // the launches of a run, in order
+    csx_handle_t hV = 0, hR = 0, hB = 0;    // the committed factor: owned here, lent out by csx_hqr_parts
+    DevBuf<double> beta;                    // the committed beta (hB's vector borrows it)
+    DevBuf<double> Vx, Rx, bx;              // scratch of a run: committed only when no column broke down
+    DevBuf<int> flags;                      // [0] smallest broken column, [1] columns updated in place
+    DevBuf<unsigned long long> stats;       // k_hqr_stats
+    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0, zeros = 0, breakdown = -1, kernel_us = 0;
+    double min_r = 0.0, max_r = 0.0;
+    HqrFactor() = default;
+    HqrFactor(const HqrFactor &) = delete;
+    HqrFactor &operator=(const HqrFactor &) = delete;
+    ~HqrFactor() {
+        if (hB) (void)csx_free(hB);
+        if (hR) (void)csx_free(hR);
+        if (hV) (void)csx_free(hV);
+        if (ev_a) (void)hipEventDestroy(ev_a);
+        if (ev_b) (void)hipEventDestroy(ev_b);
+    }
+};
+
+void destroy(HqrFactor *F) { delete F; }
+
+// The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
+// into V.x / R.x / beta when no column broke down.  *ok: 1 committed, 0 breakdown (the factor untouched).  Synchronises.
+static int hqr_run(HqrFactor *F, const double *Ax, int *ok) {
+    hipStream_t s = ctx().stream;
+    Csc *V = csc(F->hV), *R = csc(F->hR);
+    if (!V || !R || !V->x || !R->x || V->nnz != F->vnz || R->nnz != F->rnz) return CSX_EINVAL;
+    const int32_t n = F->n;
+    F->launches = F->level_launches = F->run_launches = 0;
+    const int hinit[2] = {HQR_NONE, 0};
+    const unsigned long long sinit[3] = {~0ull, 0ull, 0ull};
+    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
+    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(chol_scatter(F->vnz, F->winV, Ax, F->Vx));
+    CSX_TRY(chol_scatter(F->rnz, F->winR, Ax, F->Rx));
+    const std::vector<int32_t> &lp = F->level_ptr_h;
+    for (const HqrLaunch &L : F->schedule) {
+        if (L.wide) {
+            const int32_t cnt = lp[(size_t)L.l0 + 1] - lp[(size_t)L.l0];
+            hipLaunchKernelGGL(k_hqr_level, dim3((unsigned)((cnt + HQR_WAVES - 1) / HQR_WAVES)), dim3(64 * HQR_WAVES), 0, s,
+                               F->level_cols + lp[(size_t)L.l0], cnt, V->p, V->i, F->Vx.get(), R->p, R->i, F->Rx.get(), F->bx.get(),
+                               F->sp.get(), F->srow.get(), F->sdst.get(), F->flags.get());
+            F->level_launches++;
+        } else {
+            hipLaunchKernelGGL(k_hqr_run, dim3(1), dim3(64 * HQR_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), L.l0, L.l1,
+                               V->p, V->i, F->Vx.get(), R->p, R->i, F->Rx.get(), F->bx.get(), F->sp.get(), F->srow.get(),
+                               F->sdst.get(), F->flags.get());
+            F->run_launches++;
+        }
+    }
+    F->launches = F->level_launches + F->run_launches;
+    if (n > 0)
+        hipLaunchKernelGGL(k_hqr_stats, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, R->p, F->Rx.get(),
+                           F->stats.get());
+    (void)hipEventRecord(F->ev_b, s);
+    int hflags[2] = {HQR_NONE, 0};
+    unsigned long long hst[3] = {0, 0, 0};
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        set_error("csx_hqr: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipStreamSynchronize(s);
+        return CSX_ERUNTIME;
+    }
+    float ms = 0.0f;
+    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    F->long_cols = hflags[1];
+    F->breakdown = hflags[0] == HQR_NONE ? -1 : hflags[0];
+    *ok = F->breakdown < 0 ? 1 : 0;
+    if (!*ok) return CSX_OK;
+    if (n == 0) hst[0] = 0;
+    std::memcpy(&F->min_r, &hst[0], 8);
+    std::memcpy(&F->max_r, &hst[1], 8);
+    F->zeros = (int64_t)hst[2];
+    if (F->vnz) CSX_HIP(hipMemcpyAsync(V->x, F->Vx.get(), (size_t)F->vnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (F->rnz) CSX_HIP(hipMemcpyAsync(R->x, F->Rx.get(), (size_t)F->rnz * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n) CSX_HIP(hipMemcpyAsync(F->beta.get(), F->bx.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    for (Csc *M : {V, R}) {   // (copies of the old values; V's reflection levels are pattern only and stay)
+        M->rows.reset();
+        M->tiled.reset();
+    }
+    CSX_HIP(hipStreamSynchronize(s));
+    return CSX_OK;
+}
+
+static int hqr_build(Csc *A, const int32_t *q, const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t m2,
+                     HqrFactor *F) {
+    hipStream_t s = ctx().stream;
+    const int32_t m = A->m, n = A->n;
+    F->m = m;
+    F->n = n;
+    F->m2 = m2;
+    F->anz = A->nnz;
+    if (!A->trusted) CSX_TRY(csc_validate(A));
+    std::vector<int32_t> ap, ai, vp, vi, rp, ri;
+    CSX_TRY(download_i32(ap, A->p, (size_t)n + 1));
+    CSX_TRY(download_i32(ai, A->i, (size_t)A->nnz));
+    if (hqr_symbolic(m, n, m2, ap.data(), ai.data(), q, parent, pinv, leftmost, vp, vi, rp, ri) != CSX_OK) {
+        set_error("csx_hqr_factor: the symbolic analysis is not this matrix's");
+        return CSX_EINVAL;
+    }
+    F->vnz = vp[(size_t)n];
+    F->rnz = rp[(size_t)n];
+    // the entry maps (of duplicates the last stored) and the sorted view of every column's slots
+    std::vector<int32_t> winV((size_t)F->vnz, -1), winR((size_t)F->rnz, -1), where((size_t)m2, -1);
+    std::vector<int32_t> sp((size_t)n + 1, 0), srow((size_t)F->vnz + (size_t)F->rnz - (size_t)n), sdst(srow.size());
+    std::vector<std::pair<int32_t, int32_t>> tmp;
+    for (int32_t k = 0; k < n; k++) {
+        const int32_t rb = rp[(size_t)k], nr = rp[(size_t)k + 1] - rb - 1, vb = vp[(size_t)k], nv = vp[(size_t)k + 1] - vb;
+        for (int32_t t = 0; t < nr; t++) where[(size_t)ri[(size_t)(rb + t)]] = t;          // columns c < k: R's slots
+        for (int32_t j = 0; j < nv; j++) where[(size_t)vi[(size_t)(vb + j)]] = nr + j;     // rows >= k: V's slots
+        const int32_t col = q ? q[k] : k;
+        for (int32_t p = ap[(size_t)col]; p < ap[(size_t)col + 1]; p++) {
+            const int32_t slot = where[(size_t)pinv[ai[(size_t)p]]];   // (hqr_symbolic has seen that the row has one)
+            if (slot < nr) winR[(size_t)(rb + slot)] = p;
+            else winV[(size_t)(vb + slot - nr)] = p;
+        }
+        const int32_t sb = rb - k + vb;
+        sp[(size_t)k] = sb;
+        tmp.clear();
+        for (int32_t t = 0; t < nr; t++) tmp.emplace_back(ri[(size_t)(rb + t)], t);
+        for (int32_t j = 0; j < nv; j++) tmp.emplace_back(vi[(size_t)(vb + j)], nr + j);
+        std::sort(tmp.begin(), tmp.end());
+        for (size_t t = 0; t < tmp.size(); t++) {
+            srow[(size_t)sb + t] = tmp[t].first;
+            sdst[(size_t)sb + t] = tmp[t].second;
+        }
+    }
+    sp[(size_t)n] = F->rnz - n + F->vnz;
+    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
+    CSX_TRY(F->flags.alloc(2));
+    CSX_TRY(F->stats.alloc(3));
+    CSX_HIP(hipEventCreate(&F->ev_a));
+    CSX_HIP(hipEventCreate(&F->ev_b));
+    std::vector<int32_t> cols;
+    if (n > 0) ldl_levels(n, parent, F->level_ptr_h, cols);
+    else F->level_ptr_h.assign(1, 0);
+    {
+        // the launches: a level of more than HQR_WAVES columns is one launch of a wave per column; a run of narrower levels is
+        // walked by one workgroup, cut after HQR_RUN_LEVELS levels or HQR_RUN_WORK slot updates
+        const std::vector<int32_t> &lp = F->level_ptr_h;
+        const int32_t nlev = (int32_t)lp.size() - 1;
+        auto level_work = [&](int32_t l) {
+            int64_t most = 0;
+            for (int32_t t = lp[(size_t)l]; t < lp[(size_t)l + 1]; t++) {
+                const int32_t k = cols[(size_t)t];
+                int64_t w = 0;
+                for (int32_t u = rp[(size_t)k]; u < rp[(size_t)k + 1] - 1; u++) w += vp[(size_t)ri[(size_t)u] + 1] - vp[(size_t)ri[(size_t)u]];
+                most = std::max(most, w);
+            }
+            return most;
+        };
+        for (int32_t l = 0; l < nlev;) {
+            if (lp[(size_t)l + 1] - lp[(size_t)l] > HQR_WAVES) {
+                F->schedule.push_back({true, l, l + 1});
+                l++;
+                continue;
+            }
+            int32_t e = l;
+            int64_t work = 0;
+            while (e < nlev && e - l < HQR_RUN_LEVELS && lp[(size_t)e + 1] - lp[(size_t)e] <= HQR_WAVES) {
+                const int64_t w = level_work(e);
+                if (e > l && work + w > HQR_RUN_WORK) break;
+                work += w;
+                e++;
+            }
+            F->schedule.push_back({false, l, e});
+            l = e;
+        }
+    }
+    CSX_TRY(upload(F->level_cols, cols));
+    CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+    CSX_TRY(upload(F->sp, sp));
+    CSX_TRY(upload(F->srow, srow));
+    CSX_TRY(upload(F->sdst, sdst));
+    CSX_TRY(upload(F->winV, winV));
+    CSX_TRY(upload(F->winR, winR));
+    std::unique_ptr<Csc> V, R;
+    {
+        DevBuf<int32_t> dvp, dvi, drp, dri;
+        CSX_TRY(upload(dvp, vp));
+        CSX_TRY(upload(dvi, vi));
+        CSX_TRY(upload(drp, rp));
+        CSX_TRY(upload(dri, ri));
+        CSX_TRY(csc_copy_pattern(m2, n, F->vnz, dvp.get(), dvi.get(), true, &V));
+        CSX_TRY(csc_copy_pattern(n, n, F->rnz, drp.get(), dri.get(), true, &R));   // nothing of R lies below row n
+        CSX_HIP(hipStreamSynchronize(s));   // (the host vectors and the staging buffers have landed)
+    }
+    CSX_TRY(F->beta.alloc((size_t)std::max(n, 1)));
+    CSX_TRY(F->bx.alloc((size_t)std::max(n, 1)));
+    CSX_TRY(F->Vx.alloc((size_t)F->vnz));
+    CSX_TRY(F->Rx.alloc((size_t)F->rnz));
+    std::unique_ptr<Vec> B(new Vec());
+    B->len = n;
+    B->d = F->beta.get();
+    B->owns = false;
+    F->hV = put(K_CSC, V.release());
+    F->hR = put(K_CSC, R.release());
+    F->hB = put(K_VEC, B.release());
+    return CSX_OK;
+}
+
+}  // namespace csx
+
+using namespace csx;
+
+extern "C" int csx_hqr_factor(csx_handle_t hA, const int32_t *q, const int32_t *parent, const int32_t *pinv, const int32_t *leftmost,
+                              int32_t m2, csx_handle_t *out, int *ok) {
+    CSX_TRY(require_ready());
+    Csc *A = csc(hA);
+    if (!A || !out || !ok || !A->x || A->m < A->n || m2 < A->m || (A->n > 0 && !parent) || (A->m > 0 && (!pinv || !leftmost)))
+        return CSX_EINVAL;
+    *out = 0;
+    *ok = 0;
+    std::unique_ptr<HqrFactor> F(new HqrFactor());
+    CSX_TRY(hqr_build(A, q, parent, pinv, leftmost, m2, F.get()));
+    CSX_TRY(hqr_run(F.get(), A->x, ok));
+    if (*ok) *out = put(K_HQRFACTOR, F.release());
+    return CSX_OK;
+}
+
+extern "C" int csx_hqr_refactor(csx_handle_t h, csx_handle_t hA2, int *ok) {
+    CSX_TRY(require_ready());
+    HqrFactor *F = (HqrFactor *)get(h, K_HQRFACTOR);
+    if (!F || !ok) return CSX_EINVAL;
+    *ok = -1;
+    const double *x2 = nullptr;
+    CSX_TRY(rf_values(hA2, F->m, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
+    if (!x2) {
+        set_error("csx_hqr_refactor: A2 does not have the pattern (or the length) of the factored matrix");
+        return CSX_EINVAL;   // nothing changes
+    }
+    return hqr_run(F, x2, ok);
+}
+
+extern "C" int csx_hqr_parts(csx_handle_t h, csx_handle_t *V, csx_handle_t *R, csx_handle_t *beta) {
+    CSX_TRY(require_ready());
+    HqrFactor *F = (HqrFactor *)get(h, K_HQRFACTOR);
+    if (!F || !V || !R || !beta) return CSX_EINVAL;
+    *V = F->hV;
+    *R = F->hR;
+    *beta = F->hB;
+    return CSX_OK;
+}
+
+extern "C" int csx_hqr_info(csx_handle_t h, int64_t *info) {
+    CSX_TRY(require_ready());
+    HqrFactor *F = (HqrFactor *)get(h, K_HQRFACTOR);
+    if (!F || !info) return CSX_EINVAL;
+    info[0] = F->m;
+    info[1] = F->n;
+    info[2] = F->m2;
+    info[3] = F->vnz;
+    info[4] = F->rnz;
+    info[5] = (int64_t)F->level_ptr_h.size() - 1;
+    info[6] = F->launches;
+    info[7] = F->level_launches;
+    info[8] = F->run_launches;
+    info[9] = F->long_cols;
+    info[10] = F->zeros;
+    info[11] = F->breakdown;
+    info[12] = F->kernel_us;
+    info[13] = HQR_ACC;
+    info[14] = HQR_RUN_LEVELS;
+    return CSX_OK;
+}
+
+extern "C" int csx_hqr_stats(csx_handle_t h, double *out) {
+    CSX_TRY(require_ready());
+    HqrFactor *F = (HqrFactor *)get(h, K_HQRFACTOR);
+    if (!F || !out) return CSX_EINVAL;
+    out[0] = F->min_r;
+    out[1] = F->max_r;
+    return CSX_OK;
+}
+
+extern "C" int csx_hqr_window(int32_t *entries, int32_t *run_levels) {   // (no device needed)
+    if (!entries || !run_levels) return CSX_EINVAL;
+    *entries = HQR_ACC;
+    *run_levels = HQR_RUN_LEVELS;
+    return CSX_OK;
+}

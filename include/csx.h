@@ -963,6 +963,58 @@ int csx_slu_window(int32_t *entries, int32_t *run_levels);
 int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *prow, const int32_t *pinv,
                  const int32_t *Lp, const int32_t *Li, double tau, double *Lx, double *Utx, int64_t *info);
 
+/* ---- sparse Householder QR of a matrix in one connected piece, on the device (csx_hqr.hip) ----
+ * A (m-by-n, m >= n, values) with cs_sqr's analysis of A(:, q): q (column order, n entries, or null), parent (column
+ * elimination tree), pinv (row permutation, rows of A to 0 .. m2-1), leftmost (m entries), m2 (rows including fictitious ones).
+ * Householder QR searches for no pivot, so the patterns are known before the values: V (m2-by-n, the diagonal first in every
+ * column, then the rows in the order csx_qr_host finds them) and R (n-by-n, the entries in the order the reflections are
+ * applied in, the diagonal last) have csx_qr_host's p and i exactly.  The values, compiled without contraction on host and device:
+ *   for every column k (any order that puts descendants in the column elimination tree first):
+ *     the slots of R(:,k) and V(:,k) = +0.0; A(:, q[k]) scattered at pinv[row], of duplicate entries the last stored
+ *     for every c = R.i[t], t over the column's entries before its diagonal, in stored order:
+ *       part[l] = +0.0, l = 0 .. 63
+ *       for p = V.p[c] + l, step 64:  part[l] = part[l] + V.x[p] * work[V.i[p]]        (product rounded, then the sum)
+ *       for s = 32, 16, 8, 4, 2, 1:   part[l] = part[l] + part[l + s] for l < s
+ *       tau = part[0] * beta[c]
+ *       work[V.i[p]] = work[V.i[p]] - V.x[p] * tau for every p of column c             (product rounded, then the subtraction)
+ *       R.x[t] = work[c]
+ *     V.x[p] = work[V.i[p]] for the column's slots
+ *     tail2 = the same 64 strided sums and tree over V.x[p]^2, p after the head (lane l: V.p[k] + 1 + l, step 64)
+ *     cs_house on (head, tail2), statement for statement as csx_qr_host (IEEE sqrt and division): the head of V(:,k), beta[k], and
+ *     s = R's diagonal
+ *   V.x, R.x and beta are byte-equal to csx_hqr_host, the same on every run, and equal to csx_qr_host's (cs_qr's) to rounding only:
+ *   that loop sums a reflection's dot product entry by entry.  No floating-point atomics.
+ * csx_hqr_symbolic_host: the patterns alone on host arrays, no device: csx_qr_host's loop without the values, Vp / Rp n + 1
+ *   entries, Vi / Ri up to vcap / rcap.  CSX_EINVAL for m < n, capacities too small, or an analysis that is not this matrix's.
+ * csx_hqr_host: the rule on host arrays, no device; csx_qr_host's arguments.
+ * csx_hqr_factor: *ok = 1 and a NEW factor handle (csx_free) that keeps the analysis (A's pattern, the two entry maps, the sorted
+ *   view of every column's slots, height levels of the tree) and owns V, R and beta; *ok = 0 and *F = 0 when a diagonal of R is
+ *   not finite (the only breakdown).  CSX_EINVAL for a pattern-only A, m < n, or symbolic arrays that are not A's.
+ * csx_hqr_refactor: new values on the kept analysis, A2 as for csx_ldl_refactor (*ok = -1 and CSX_EINVAL for a foreign pattern
+ *   or length, nothing changed); computed into scratch and copied over V.x, R.x and beta only without a breakdown (*ok = 1); on
+ *   breakdown (*ok = 0) the factor and every plan made from it are exactly as before.  The addresses never change.
+ * csx_hqr_parts: BORROWED handles of V, R (CSC) and beta (a vector of n doubles): the factor owns them, they die with it.
+ * csx_hqr_info: info[15] = m, n, m2, entries of V, entries of R, height levels, numeric launches of the last run, launches of
+ *   the level kernel, launches of the run walker (one workgroup walking at most `run cap` consecutive levels of at most 4
+ *   columns each per launch), the columns of the last run updated in place (more slots than the LDS window; counted by the
+ *   kernels), exact zeros on R's diagonal (committed factor), the smallest broken column of the last run or -1, microseconds of
+ *   the last run between two events, the LDS window in slots, the run cap in levels.
+ * csx_hqr_stats: out[2] = min |r_kk|, max |r_kk| of the committed factor (0.0 for n = 0).
+ * csx_hqr_window: the LDS window in slots and the run cap in levels, without a device or a factor. */
+int csx_hqr_symbolic_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q,
+                          const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t vcap, int32_t rcap,
+                          int32_t *Vp, int32_t *Vi, int32_t *Rp, int32_t *Ri);
+int csx_hqr_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *q,
+                 const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t vcap, int32_t rcap, int32_t *Vp,
+                 int32_t *Vi, double *Vx, int32_t *Rp, int32_t *Ri, double *Rx, double *beta);
+int csx_hqr_factor(csx_handle_t A, const int32_t *q, const int32_t *parent, const int32_t *pinv, const int32_t *leftmost,
+                   int32_t m2, csx_handle_t *F, int *ok);
+int csx_hqr_refactor(csx_handle_t F, csx_handle_t A2, int *ok);
+int csx_hqr_parts(csx_handle_t F, csx_handle_t *V, csx_handle_t *R, csx_handle_t *beta);
+int csx_hqr_info(csx_handle_t F, int64_t *info);
+int csx_hqr_stats(csx_handle_t F, double *out);
+int csx_hqr_window(int32_t *entries, int32_t *run_levels);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
