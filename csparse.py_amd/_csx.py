@@ -187,6 +187,13 @@ _PROTOS = {
     "csx_ldl_window": [C.POINTER(C.c_int32)],
     "csx_block_div_rows": [H, H, C.c_int64, C.c_int32],
     "csx_ldl_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
+    "csx_schur_factor": [H, _i32p, _i32p, _i32p, C.c_int32, C.c_double, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_schur_refactor": [H, H, C.c_double, C.POINTER(C.c_int)],
+    "csx_schur_parts": [H, C.POINTER(H), C.POINTER(H), C.POINTER(H)],
+    "csx_schur_info": [H, C.POINTER(C.c_int64)],
+    "csx_schur_stats": [H, _f64p],
+    "csx_schur_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, C.c_int32, C.c_double, _f64p, _f64p, _f64p,
+                       C.POINTER(C.c_int64)],
     "csx_slu_factor": [H, _i32p, _i32p, _i32p, _i32p, C.c_double, C.POINTER(H), C.POINTER(C.c_int)],
     "csx_slu_refactor": [H, H, C.c_double, C.POINTER(C.c_int)],
     "csx_slu_parts": [H, C.POINTER(H), C.POINTER(H)],

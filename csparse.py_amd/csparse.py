@@ -2101,6 +2101,251 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
     return _Solver()
 
 
+# ------------------------------------------------- Schur complement ----
+
+_SCHUR_INFO = ("n", "n1", "ns", "lnz", "levels", "launches", "level_launches", "run_launches", "schur_launches", "schur_chunks",
+               "pos", "neg", "perturbed", "breakdown", "kernel_us", "long_columns", "window")
+
+
+def _schur_order(A, keep, order):
+    """perm (int32, new -> old): the interior indices first -- ascending (order 0) or by a nested dissection of the pattern of
+    A(interior, interior) (order 1) -- then `keep` in the caller's order"""
+    n = A.n
+    inside = np.ones(n, dtype=bool)
+    inside[keep] = False
+    interior = np.flatnonzero(inside).astype(np.int32)
+    n1 = len(interior)
+    if order == 1 and n1 > 0:
+        p, i = _pattern_np(A)
+        cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(p))
+        rows = i.astype(np.int64)
+        both = inside[rows] & inside[cols]
+        local = np.cumsum(inside) - 1                          # old index -> index among the interior
+        sp = np.zeros(n1 + 1, dtype=np.int32)
+        sp[1:] = np.cumsum(np.bincount(local[cols[both]], minlength=n1))
+        si = _csx.i32(local[rows[both]])                       # (entries stay in column order: `local` is monotone)
+        perm = np.empty(n1, dtype=np.int32)
+        if _csx.load().csx_order_nd_host(n1, _csx.pi(sp), _csx.pi(si), _csx.pi(perm)) != _csx.OK:
+            return None
+        interior = interior[perm]
+    return np.concatenate([interior, np.asarray(keep, dtype=np.int32)]).astype(np.int32)
+
+
+def schur_factor(A, keep, order=0, perturb=0.0, exact=None):
+    """Eliminate all of a symmetric matrix but the indices `keep` and return what is left: the partial L D L' of P A P' with the
+    Schur complement S = A22 - A21 inv(A11) A12 of the kept set on the device.  A is read as cs_chol reads it
+    (stored entries with row <= column, of duplicates the last).  keep: ns distinct indices; P numbers the n1 = n - ns interior
+    indices first (order 0: ascending; 1: nested dissection of the pattern of A(interior, interior)), then keep in the caller's
+    order.  P A P' = Lp blockdiag(D1, S) Lp' with Lp unit lower triangular -- its first n1 columns those of the LDL' of P A P',
+    rows >= n1 included, its last ns columns those of the identity -- 1x1 pivots in that static order, no pivot search.
+    perturb: as for ldlsol_factor, on the interior pivots.  Only an interior pivot can break down: a zero or non-finite diagonal
+    of S is data.  None for a non-CSC or non-square A and on an interior breakdown; ValueError for duplicate or out-of-range
+    keep or perturb < 0.  Otherwise a solver:
+    schur: the ns-by-ns dvec S (symmetric, both triangles the same bytes).  factors: .L = Lp (a pinned `cs`), .D (dvec of n1).
+    symbolic: the analysis of P A P' with .pinv.  keep: the list.
+    condense(b): b a list of n or an n-by-k dvec, not modified -> (g, state): state an n-by-k dvec in the permuted order holding
+      [inv(D1) inv(L11) b1; g], g = b2 - L21 inv(L11) b1 the right-hand side of S x2 = g (ns-by-k: a list for a list b, a dvec
+      for a block): cs_ipvec(pinv), cs_lsolve(Lp), csx_block_div_rows on the first n1 rows.
+    expand(state, x2): x2 ns-by-k (list, numpy or dvec) -> x in A's numbering (a list for a list x2, else an n-by-k dvec): rows
+      >= n1 of a copy of state become x2, cs_ltsolve(Lp), cs_pvec(pinv).
+    solve(b, interface): condense, x2 = interface(g as numpy ns-by-k), expand; b overwritten; True.  No dense solver is added:
+      `interface` is the caller's solve of S x2 = g.
+    The two sweeps follow lusol_factor's rule for `exact`: a list in the reference's order, a block in the rounding-equal order,
+    True / False force one order for both.
+    refactor(A2): new values on the kept analysis, as on ldlsol_factor: True; False with Lp, D, S and the solves exactly as before
+      on an interior breakdown; ValueError for another pattern or length.
+    inertia(): (positive, negative) pivots of A11; with the inertia of S it is A's (Haynsworth).  logdet(): (sign, log |det A11|).
+    info(): n, n1, ns, lnz (of Lp), levels (of the interior tree), launches, level_launches, run_launches (the walker, cut at
+      256 levels), schur_launches, schur_chunks ((column, chunk of `window` rows) pairs of the trailing-column kernel), pos, neg,
+      perturbed, breakdown, kernel_us, long_columns, window, min_abs_d, max_abs_d, max_abs_l."""
+    if not CS_CSC(A) or A.m != A.n:
+        return None
+    perturb = float(perturb)
+    if not perturb >= 0.0:
+        raise ValueError("schur_factor: perturb must be >= 0")
+    if order not in (0, 1):
+        return None
+    n = A.n
+    keep = [int(v) for v in keep]
+    if any(v < 0 or v >= n for v in keep) or len(set(keep)) != len(keep):
+        raise ValueError("schur_factor: keep must hold distinct indices of A")
+    ns = len(keep)
+    n1 = n - ns
+    perm = _schur_order(A, keep, order)
+    if perm is None:
+        return None
+    pinv = np.empty(n, dtype=np.int32)
+    pinv[perm] = np.arange(n, dtype=np.int32)
+    S = cs_schol(0, cs_symperm(A, pinv, False), _arrays=True)
+    if S is None:
+        return None
+    S.pinv = pinv
+    lib = _csx.lib()
+
+    def threshold(hA):
+        if perturb == 0.0:
+            return 0.0
+        out = _csx.C.c_double(0.0)
+        _csx.check(lib.csx_norm1_sym(hA, out), "csx_norm1_sym")
+        return perturb * out.value
+
+    hF, ok = _csx.new_handle(), _csx.C.c_int(0)
+    with _Resident(A) as dA:
+        _csx.check(lib.csx_schur_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(pinv), n1,
+                                        threshold(dA.handle), hF, ok), "csx_schur_factor")
+    if not ok.value:
+        return None
+    hL, hd, hS = _csx.new_handle(), _csx.new_handle(), _csx.new_handle()
+    _csx.check(lib.csx_schur_parts(hF, hL, hd, hS), "csx_schur_parts")
+    # Lp, d and S are the factor's (borrowed handles): the wrappers free the plans cached on Lp and the factor, nothing else
+    N = csn()
+    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
+    dev = N.L._dev
+    dev._fin.detach()
+    dev._fin = weakref.finalize(dev, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), dev.plans, hF)
+    N.D = dvec(n1, 1, _handle=hd)
+    N.D._fin.detach()
+    N.D._keep = dev
+    N.U, N.pinv, N.B = None, None, None
+    Sd = dvec(ns, max(ns, 1), _handle=hS)
+    Sd._fin.detach()
+    Sd._keep = dev
+    hp, keep_p = _perm_handle(pinv, n)
+
+    def tail(x, k):
+        """a NEW handle (the caller frees it) of rows n1 .. n - 1 of the n-by-k block x: nothing is copied"""
+        h = _csx.new_handle()
+        _csx.check(lib.csx_vec_wrap(_csx.C.c_void_p(x.device_ptr() + 8 * n1 * k), ns * k, h), "csx_vec_wrap")
+        return h
+
+    class _Solver(object):
+        factors = N
+        schur = Sd
+
+        @property
+        def symbolic(self):
+            for name in ("parent", "cp", "pinv"):
+                v = getattr(S, name)
+                if v is not None and not isinstance(v, list):
+                    setattr(S, name, v.tolist())
+            return S
+
+        def __init__(self):
+            self._dev = dev                          # keeps Lp, d, S and the factor alive
+            self._fin = weakref.finalize(self, _csx.free, keep_p)
+            self.keep = list(keep)
+
+        def _sweep(self, kind, x, k, in_exact_order):
+            plan = _plan(dev, kind)
+            try:
+                _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+                _csx.check(lib.csx_tri_solve(plan, x.handle, k), "csx_tri_solve")
+            finally:
+                lib.csx_tri_set_order(plan, 1)       # (shared with the list-level cs_lsolve / cs_ltsolve on this factor)
+
+        def _condense(self, blk, in_exact_order):
+            k = blk.k
+            x = dvec(n, k)
+            _csx.check(lib.csx_permute_vec(hp, blk.handle, x.handle, n, k, 1), "csx_permute_vec")
+            self._sweep(TRI_L, x, k, in_exact_order)
+            _csx.check(lib.csx_block_div_rows(x.handle, hd, n1, k), "csx_block_div_rows")
+            g = dvec(ns, k)
+            if ns:
+                h = tail(x, k)
+                try:
+                    _csx.check(lib.csx_vec_copy(h, g.handle), "csx_vec_copy")
+                finally:
+                    _csx.free(h)
+            return g, x
+
+        def _expand(self, state, x2, in_exact_order, out=None):
+            if not isinstance(state, dvec) or state.n != n:
+                raise ValueError("expand: state is not a condense() of this factor")
+            k = state.k
+            x = state.copy()
+            if ns:
+                h = tail(x, k)
+                try:
+                    if isinstance(x2, dvec):
+                        if x2.n * x2.k != ns * k:
+                            raise ValueError("expand: x2 is not ns-by-k")
+                        _csx.check(lib.csx_vec_copy(x2.handle, h), "csx_vec_copy")
+                    else:
+                        a = np.ascontiguousarray(np.asarray(x2, dtype=np.float64)).reshape(-1)
+                        if a.size != ns * k:
+                            raise ValueError("expand: x2 is not ns-by-k")
+                        _csx.check(lib.csx_vec_write(h, _csx.pd(a), a.size), "csx_vec_write")
+                finally:
+                    _csx.free(h)
+            self._sweep(TRI_LT, x, k, in_exact_order)
+            out = dvec(n, k) if out is None else out
+            _csx.check(lib.csx_permute_vec(hp, x.handle, out.handle, n, k, 0), "csx_permute_vec")
+            return out
+
+        def condense(self, b):
+            from_list = not isinstance(b, dvec)
+            db, _ = _vec_in(b, n, "b")
+            g, state = self._condense(db, exact if exact is not None else from_list)
+            return (g.numpy().reshape(-1).tolist() if from_list else g), state
+
+        def expand(self, state, x2):
+            from_list = isinstance(x2, list)
+            x = self._expand(state, x2, exact if exact is not None else from_list)
+            return x.numpy().reshape(-1).tolist() if from_list else x
+
+        def solve(self, b, interface):
+            from_list = not isinstance(b, dvec)
+            in_exact_order = exact if exact is not None else from_list
+            db, bhost = _vec_in(b, n, "b")
+            g, state = self._condense(db, in_exact_order)
+            x2 = np.asarray(interface(g.numpy().reshape(ns, db.k)), dtype=np.float64)
+            self._expand(state, x2, in_exact_order, out=db)
+            _write_back(bhost, db, n * db.k)
+            return True
+
+        def refactor(self, A2):
+            A2 = _refactor_input(A, A2)
+            ok = _csx.C.c_int(0)
+            tau = 0.0
+            if perturb > 0.0:                        # |S|_1 of the operand
+                if isinstance(A2, cs):
+                    with _Resident(A2) as d2:
+                        tau = threshold(d2.handle)
+                else:
+                    with _Resident(A) as dA:
+                        h2 = _wrap_values(dA, A2)
+                        try:
+                            tau = threshold(h2)
+                        finally:
+                            _csx.free(h2)
+            _refactor_call(A2, lambda h2: lib.csx_schur_refactor(hF, h2, tau, ok), ok)
+            if ok.value == 1:
+                _refactored(N.L, dev)
+            return ok.value == 1
+
+        def info(self):
+            raw = (_csx.C.c_int64 * len(_SCHUR_INFO))()
+            st = (_csx.C.c_double * 3)()
+            _csx.check(lib.csx_schur_info(hF, raw), "csx_schur_info")
+            _csx.check(lib.csx_schur_stats(hF, st), "csx_schur_stats")
+            out = {name: int(v) for name, v in zip(_SCHUR_INFO, raw)}
+            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
+            return out
+
+        def inertia(self):
+            """(positive, negative) pivots of A11 in the committed factor"""
+            i = self.info()
+            return i["pos"], i["neg"]
+
+        def logdet(self):
+            """(sign, log |det A11|): the sign of the product of the pivots, and sum_j log |d_j| correctly rounded (math.fsum)"""
+            d = N.D.numpy().reshape(-1)
+            sign = -1.0 if int(np.sum(d < 0.0)) % 2 else 1.0
+            return sign, math.fsum(np.log(np.abs(d)).tolist())
+
+    return _Solver()
+
+
 # -------------------------------------------------------------------- LU ----
 
 def _cs_from_arrays(m, n, p, i, x):

@@ -1263,12 +1263,15 @@ extern "C" int csx_residual_sym_host(int32_t n, const int32_t *p, const int32_t 
 // by one sweep over the columns -- each from the slot of L(j,k) to the end of column k: w = L(j,k) d[k] rounded, then every
 // product rounded and every subtraction rounded.  info[4] = positive pivots, negative pivots, perturbed pivots, the smallest
 // column whose pivot is 0 or not finite (-1: none; L.x and d are then not a factorisation).
-extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
-                            const int32_t *Li, double tau, double *Lx, double *d, int64_t *info) {
+// The first ncols columns of that rule on the work array Lx (Lp[n] doubles: C scattered into every slot of the pattern, then
+// the columns j < ncols factored; the columns beyond hold C still).  rp / rpos: the row view, for csx_schur_host.
+static int ldl_host_columns(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
+                            const int32_t *Li, int32_t ncols, double tau, double *Lx, double *d, int64_t *info,
+                            std::vector<int32_t> &rp, std::vector<int32_t> &rpos) {
 #pragma clang fp contract(off)
     if (n < 0 || !Ap || !Lp || !info || Ap[0] != 0 || Lp[0] != 0 || !(tau >= 0.0)) return CSX_EINVAL;
     const int32_t anz = Ap[n], lnz = Lp[n];
-    if (anz < 0 || lnz < n || (anz > 0 && (!Ai || !Ax)) || (n > 0 && (!Li || !Lx || !d))) return CSX_EINVAL;
+    if (anz < 0 || lnz < n || (anz > 0 && (!Ai || !Ax)) || (n > 0 && (!Li || !Lx || (ncols > 0 && !d)))) return CSX_EINVAL;
     for (int32_t j = 0; j < n; j++) {
         if (Ap[j + 1] < Ap[j] || Lp[j + 1] <= Lp[j] || Li[Lp[j]] != j) return CSX_EINVAL;
         for (int32_t q = Lp[j] + 1; q < Lp[j + 1]; q++)
@@ -1293,7 +1296,8 @@ extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, con
     }
     for (int32_t q = 0; q < lnz; q++) Lx[q] = win[(size_t)q] >= 0 ? Ax[win[(size_t)q]] : 0.0;
     // the row view: for row j the slots of L(j,k), k ascending
-    std::vector<int32_t> rp((size_t)n + 1, 0), rpos((size_t)lnz);
+    rp.assign((size_t)n + 1, 0);
+    rpos.resize((size_t)lnz);
     for (int32_t q = 0; q < lnz; q++) rp[(size_t)Li[q] + 1]++;
     for (int32_t j = 0; j < n; j++) rp[(size_t)j + 1] += rp[(size_t)j];
     {
@@ -1303,7 +1307,7 @@ extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, con
     }
     std::vector<int32_t> slot((size_t)n, -1);
     int64_t pos = 0, neg = 0, perturbed = 0, broke = -1;
-    for (int32_t j = 0; j < n; j++) {
+    for (int32_t j = 0; j < ncols; j++) {
         const int32_t base = Lp[j], end = Lp[j + 1];
         for (int32_t q = base; q < end; q++) slot[(size_t)Li[q]] = q;
         for (int32_t t = rp[(size_t)j]; t < rp[(size_t)j + 1] - 1; t++) {   // (the row ends with the diagonal)
@@ -1333,6 +1337,51 @@ extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, con
     info[1] = neg;
     info[2] = perturbed;
     info[3] = broke;
+    return CSX_OK;
+}
+
+extern "C" int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
+                            const int32_t *Li, double tau, double *Lx, double *d, int64_t *info) {
+    std::vector<int32_t> rp, rpos;
+    return ldl_host_columns(n, Ap, Ai, Ax, pinv, Lp, Li, n, tau, Lx, d, info, rp, rpos);
+}
+
+// csx_schur_factor's value rule on host arrays (csx_schur.hip; the definition is the comment of csx_schur_factor in
+// include/csx.h): the columns j < n1 by the rule above on the FULL pattern Lfp / Lfi, then every column j >= n1 takes the
+// updates of the row view of row j with k < n1 in ascending k into sums indexed by the row itself -- no pivot, no division --
+// and lands in both triangles of S.  Lpx: the values of Lp (the first Lfp[n1] of the factored work array, then ns times 1.0).
+extern "C" int csx_schur_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lfp,
+                              const int32_t *Lfi, int32_t n1, double tau, double *Lpx, double *d, double *S, int64_t *info) {
+#pragma clang fp contract(off)
+    if (n < 0 || n1 < 0 || n1 > n || !Lfp || Lfp[0] != 0 || Lfp[n] < n) return CSX_EINVAL;
+    const int64_t ns = (int64_t)n - n1;
+    if (ns * ns >= ((int64_t)1 << 31) || (ns > 0 && (!S || !Lpx)) || (n1 > 0 && !Lpx)) return CSX_EINVAL;
+    std::vector<double> W((size_t)std::max(Lfp[n], 1));
+    std::vector<int32_t> rp, rpos;
+    const int st = ldl_host_columns(n, Ap, Ai, Ax, pinv, Lfp, Lfi, n1, tau, W.data(), d, info, rp, rpos);
+    if (st != CSX_OK) return st;
+    const int32_t head = Lfp[n1];
+    for (int32_t q = 0; q < head; q++) Lpx[q] = W[(size_t)q];
+    for (int64_t t = 0; t < ns; t++) Lpx[head + t] = 1.0;
+    std::vector<double> acc((size_t)n);
+    for (int32_t j = n1; j < n; j++) {
+        for (int32_t r = j; r < n; r++) acc[(size_t)r] = 0.0;
+        for (int32_t q = Lfp[j]; q < Lfp[j + 1]; q++) acc[(size_t)Lfi[q]] = W[(size_t)q];
+        for (int32_t t = rp[(size_t)j]; t < rp[(size_t)j + 1] - 1; t++) {
+            const int32_t at = rpos[(size_t)t];
+            const int32_t k = (int32_t)(std::upper_bound(Lfp, Lfp + n + 1, at) - Lfp) - 1;
+            if (k >= n1) break;                           // (k ascending: the trailing columns take no update from each other)
+            const double w = W[(size_t)at] * d[k];
+            for (int32_t q = at; q < Lfp[k + 1]; q++) {
+                const double v = W[(size_t)q] * w;
+                acc[(size_t)Lfi[q]] = acc[(size_t)Lfi[q]] - v;
+            }
+        }
+        for (int32_t r = j; r < n; r++) {
+            S[(int64_t)(r - n1) * ns + (j - n1)] = acc[(size_t)r];
+            S[(int64_t)(j - n1) * ns + (r - n1)] = acc[(size_t)r];
+        }
+    }
     return CSX_OK;
 }
 

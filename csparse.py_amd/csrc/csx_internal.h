@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR };
 
 struct Csc;
 
@@ -225,6 +225,8 @@ struct SluFactor;     // csx_slu.hip
 void destroy(SluFactor *p);
 struct HqrFactor;     // csx_hqr.hip
 void destroy(HqrFactor *p);
+struct SchurFactor;   // csx_schur.hip
+void destroy(SchurFactor *p);
 // csx_host.cpp: csx_hqr_symbolic_host on vectors that grow (no capacities)
 int hqr_symbolic(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q, const int32_t *parent,
                  const int32_t *pinv, const int32_t *leftmost, std::vector<int32_t> &Vp, std::vector<int32_t> &Vi,

@@ -20,10 +20,6 @@
 
 namespace csx {
 
-constexpr int LDL_ACC = 512;    // column entries kept in LDS per wave (24 KB a workgroup); longer columns are updated in place in global memory
-constexpr int LDL_WAVES = 4;    // waves per workgroup (csx_chol.hip's CH_WAVES)
-constexpr int LDL_NONE = 0x7fffffff;
-
 // Column j of L and d[j].  On entry Lx[Lp[j] ..] holds C(:, j) in the slots of L (0.0 in fill slots), and every column k < j
 // with L(j,k) in the pattern is finished (L(:,k) and d[k] final).  acc_v / acc_r: wave-private LDS (LDL_ACC entries).
 // flags[0]: the smallest broken column (atomicMin), flags[1]: perturbed pivots, flags[2]: columns that took the in-place path
@@ -225,6 +221,34 @@ struct LdlFactor {
 
 void destroy(LdlFactor *F) { delete F; }
 
+void ldl_launch_levels(const std::vector<int32_t> &lp, const int32_t *level_cols, const int32_t *level_ptr, const int32_t *Lp,
+                       const int32_t *Li, double *Lx, double *d, const int32_t *row_ptr, const int32_t *row_col,
+                       const int32_t *row_pos, double tau, int *flags, int32_t run_cap, int64_t *level_launches,
+                       int64_t *run_launches) {
+    hipStream_t s = ctx().stream;
+    const int32_t nlev = (int32_t)lp.size() - 1;
+    for (int32_t l = 0; l < nlev;) {
+        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
+        if (cnt > LDL_WAVES) {
+            hipLaunchKernelGGL(k_ldl_level, dim3((unsigned)((cnt + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, s,
+                               level_cols + lp[(size_t)l], cnt, Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, flags);
+            ++*level_launches;
+            l++;
+            continue;
+        }
+        int32_t e = l + 1;   // a run of narrow levels: one workgroup, no way back to the host
+        while (e < nlev && e - l < run_cap && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
+        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, level_cols, level_ptr, l, e, Lp, Li, Lx, d, row_ptr,
+                           row_col, row_pos, tau, flags);
+        ++*run_launches;
+        l = e;
+    }
+}
+
+void ldl_launch_stats(int32_t n, const int32_t *Lp, const double *Lx, const double *d, unsigned long long *st) {
+    if (n > 0) hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, ctx().stream, n, Lp, Lx, d, st);
+}
+
 // The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
 // into L.x / d when no column broke down.  *ok: 1 committed, 0 breakdown (L, d untouched).  Synchronises.
 static int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
@@ -240,29 +264,10 @@ static int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
     CSX_HIP(hipEventRecord(F->ev_a, s));
     CSX_TRY(chol_scatter(F->lnz, F->win, Ax, F->Lx));
-    const std::vector<int32_t> &lp = F->level_ptr_h;
-    const int32_t nlev = (int32_t)lp.size() - 1;
-    for (int32_t l = 0; l < nlev;) {
-        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
-        if (cnt > LDL_WAVES) {
-            hipLaunchKernelGGL(k_ldl_level, dim3((unsigned)((cnt + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, s,
-                               F->level_cols + lp[(size_t)l], cnt, L->p, L->i, F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(),
-                               F->rpos.get(), tau, F->flags.get());
-            F->level_launches++;
-            l++;
-            continue;
-        }
-        int32_t e = l + 1;   // a run of narrow levels: one workgroup, no way back to the host
-        while (e < nlev && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
-        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), l, e, L->p, L->i,
-                           F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(), F->rpos.get(), tau, F->flags.get());
-        F->run_launches++;
-        l = e;
-    }
+    ldl_launch_levels(F->level_ptr_h, F->level_cols.get(), F->level_ptr.get(), L->p, L->i, F->Lx.get(), F->dd.get(), F->rp.get(),
+                      F->rc.get(), F->rpos.get(), tau, F->flags.get(), LDL_RUN_UNCAPPED, &F->level_launches, &F->run_launches);
     F->launches = F->level_launches + F->run_launches;
-    if (n > 0)
-        hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, F->Lx.get(), F->dd.get(),
-                           F->stats.get());
+    ldl_launch_stats(n, L->p, F->Lx.get(), F->dd.get(), F->stats.get());
     (void)hipEventRecord(F->ev_b, s);
     int hflags[3] = {LDL_NONE, 0, 0};
     unsigned long long hst[5] = {0, 0, 0, 0, 0};

@@ -914,6 +914,54 @@ int csx_block_div_rows(csx_handle_t X, csx_handle_t d, int64_t rows, int32_t nrh
 int csx_ldl_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lp,
                  const int32_t *Li, double tau, double *Lx, double *d, int64_t *info);
 
+/* ---- Partial LDL' with the Schur complement of a kept index set (schur_factor) ---------------------------
+ * Definition.  A is a square CSC matrix with values, read as cs_chol reads it: the stored entries with row <= column, of
+ * duplicates the last, lower entries ignored.  pinv is a permutation (or NULL) that numbers the n1 INTERIOR indices first and the
+ * ns = n - n1 KEPT indices last (the caller's order among them); C = upper(P A P'); S_sym = (parent, cp) is the FULL symbolic
+ * Cholesky analysis of P A P' (csx_schol of the permuted matrix), whose pattern Lf (rows ascending, the diagonal first) carries
+ * the row view that the trailing columns need.
+ * Values, compiled without contraction on host and device:
+ *   columns j < n1: exactly csx_ldl_factor's rule (pivot rule, tau, breakdown) -- the first n1 columns of the LDL' of C
+ *   columns j >= n1 (no pivot, no division, any order, independent of each other):
+ *     acc[r] = C(r, j) for r >= j (0.0 where nothing is stored)
+ *     for every k < n1 with L(j,k) in the pattern, k ASCENDING:
+ *       w = L(j,k) * d[k]                                          (rounded)
+ *       for every stored p of column k from the slot of L(j,k) to the column's end:
+ *         acc[L.i[p]] = acc[L.i[p]] - L.x[p] * w                   (product rounded, then the subtraction rounded)
+ *     S(r - n1, j - n1) = S(j - n1, r - n1) = acc[r]               (+0.0 outside the pattern)
+ * Outputs.  Lp: an n x n CSC matrix, columns < n1 the columns of L (unit diagonal stored, rows >= n1 included), every column
+ * >= n1 the single entry 1.0: Lp.p[j] = cp[j] for j <= n1, Lp.p[j] = cp[n1] + j - n1 beyond.  d: n1 doubles.  S: ns ns doubles,
+ * symmetric, both triangles the same bytes.  P A P' = Lp blockdiag(diag(d), S) Lp' up to rounding.  Only an interior pivot can
+ * break down: a zero or non-finite diagonal of S is data.
+ *   On the device the interior columns are csx_ldl_factor's launches over the height levels of the first n1 columns (the walker of
+ *   narrow levels cut at 256 levels a launch); the trailing columns are one launch, one wave per (column j, chunk of at most
+ *   `window` consecutive rows of j .. n - 1), the chunk's sums in LDS, every update of row j with k < n1 applied in ascending k.
+ *   Lp.x, d and S are byte-equal to csx_schur_host, the same on every run.  No floating-point atomics.
+ * csx_schur_factor: *ok = 1 and a NEW factor handle (csx_free) that keeps the analysis and owns Lp, d and S; *ok = 0 and *F = 0 on
+ *   an interior breakdown.  CSX_EINVAL for a pattern-only or non-square A, an S_sym or pinv that does not belong to A, n1 outside
+ *   0 .. n, ns ns >= 2^31, tau < 0 or NaN.
+ * csx_schur_refactor: new values on the kept analysis, A2 as for csx_ldl_refactor (*ok = -1 and CSX_EINVAL for a foreign pattern
+ *   or length, nothing changed).  Everything is computed into scratch arrays; Lp.x, d and S are overwritten only when no interior
+ *   column broke down (*ok = 1), and keep their addresses; on breakdown (*ok = 0) they and every plan made from Lp are as before.
+ * csx_schur_parts: BORROWED handles of Lp (CSC), d (vector of n1 doubles) and S (vector of ns ns doubles): the factor owns them.
+ * csx_schur_info: info[17] = n, n1, ns, entries of Lp, height levels of the interior tree, numeric launches of the last run
+ *   (level + run + schur), launches of the level kernel, launches of the walker, launches of the trailing-column kernel, its
+ *   (column, chunk) pairs, positive pivots, negative pivots (of the committed d), perturbed pivots of the last run, the smallest
+ *   broken column of the last run or -1, microseconds of the last run between two events, interior columns of the last run
+ *   updated in place (longer than the LDS window), the LDS window in entries.
+ * csx_schur_stats: out[3] = min |d|, max |d|, max |l| off the diagonal over the interior columns of the committed factor.
+ * csx_schur_host: the rule on host arrays, no device: Lfp / Lfi the FULL pattern Lf; Lpx (Lfp[n1] + ns doubles, the values of
+ *   Lp), d (n1 doubles) and S (ns ns doubles) written; info[4] as csx_ldl_host's, over the interior.  CSX_EINVAL for a malformed
+ *   pattern, an upper entry of A without a slot, n1 outside 0 .. n, ns ns >= 2^31, tau < 0 or NaN. */
+int csx_schur_factor(csx_handle_t A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t n1, double tau,
+                     csx_handle_t *F, int *ok);
+int csx_schur_refactor(csx_handle_t F, csx_handle_t A2, double tau, int *ok);
+int csx_schur_parts(csx_handle_t F, csx_handle_t *Lp, csx_handle_t *d, csx_handle_t *S);
+int csx_schur_info(csx_handle_t F, int64_t *info);
+int csx_schur_stats(csx_handle_t F, double *out);
+int csx_schur_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *pinv, const int32_t *Lfp,
+                   const int32_t *Lfi, int32_t n1, double tau, double *Lpx, double *d, double *S, int64_t *info);
+
 /* ---- L U with static pivots: general unsymmetric matrices in one connected piece (slusol_factor) --------
  * Definition.  A is a square CSC matrix with values; prow a row permutation or NULL, A1 = A(prow, :) (row k of A1 is row prow[k]
  * of A: a matching puts a zero-free diagonal there); pinv a symmetric permutation or NULL, C = P A1 P' (C(pinv[i], pinv[j]) =
