@@ -1773,11 +1773,7 @@ def cholsol_factor(A, order=0, exact=None):
             nonlocal S
             if S is None:
                 S = _symbolic_of_factor(N.L)
-            for name in ("parent", "cp", "pinv"):
-                v = getattr(S, name)
-                if v is not None and not isinstance(v, list):
-                    setattr(S, name, v.tolist())
-            return S
+            return _symbolic_lists(S)
 
         def __init__(self):
             self._dev = dev                      # keeps the device factor alive (see above)
@@ -1943,9 +1939,141 @@ def cholsol_factor(A, order=0, exact=None):
     return _Solver()
 
 
+# ------------------------------------- what the static-pivot solvers share ----
+
+def _symbolic_lists(S):
+    """S with parent / cp / pinv as lists, as cs_schol returns them -- made when a solver's `symbolic` is first read: at 5M
+    columns the three conversions take 0.3 s, sixty times the analysis itself"""
+    for name in ("parent", "cp", "pinv"):
+        v = getattr(S, name)
+        if v is not None and not isinstance(v, list):
+            setattr(S, name, v.tolist())
+    return S
+
+
+def _perturb_tau(perturb, norm, dev, values=None):
+    """tau = perturb |M|_1 by the library's `norm` (csx_norm1_sym, csx_norm1), 0.0 for perturb == 0: M the device matrix dev, or
+    its pattern with `values` (a dvec in its storage order; nothing is copied)"""
+    if perturb == 0.0:
+        return 0.0
+    out = _csx.C.c_double(0.0)
+    h = dev.handle if values is None else _wrap_values(dev, values)
+    try:
+        _csx.check(norm(h, out), norm.__name__)
+    finally:
+        if values is not None:
+            _csx.free(h)
+    return perturb * out.value
+
+
+def _refactor_tau(perturb, norm, A, A2):
+    """_perturb_tau of the operand of a refactor (_refactor_input's A2) of a factor of A"""
+    if perturb == 0.0:
+        return 0.0
+    if isinstance(A2, cs):
+        with _Resident(A2) as d2:
+            return _perturb_tau(perturb, norm, d2)
+    with _Resident(A) as dA:
+        return _perturb_tau(perturb, norm, dA, A2)
+
+
+def _adopt_factor(hF, hL, mats=(), vecs=()):
+    """Python faces of the parts that a device factor hF lends out (its *_parts call): the wrappers free the plans cached on the
+    matrices and the factor, never a part.  hL: the matrix whose wrapper frees the factor, after its plans; mats: further matrix
+    handles, vecs: (handle, n, k) of dense parts -- both keep hL's wrapper alive.  -> [pinned `cs` of hL and of mats], [dvec]"""
+    def pinned(h):
+        M = cs_pin(_from_device(h, lambda nnz: max(nnz, 1)))
+        M._dev._fin.detach()
+        return M
+
+    L = pinned(hL)
+    dev = L._dev
+    dev._fin = weakref.finalize(dev, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), dev.plans, hF)
+    Ms, vs = [L], []
+    for h in mats:
+        M = pinned(h)
+        M._dev._fin = weakref.finalize(M._dev, _DevMatrix._release, None, M._dev.plans)
+        M._dev._keep = dev
+        Ms.append(M)
+    for h, n, k in vecs:
+        v = dvec(n, k, _handle=h)
+        v._fin.detach()
+        v._keep = dev
+        vs.append(v)
+    return Ms, vs
+
+
+def _in_order(plans, in_exact_order, sweeps):
+    """sweeps() with the triangular-solve plans in the reference's order (1) or the rounding-equal one (0); order 1 is put back
+    whatever happens: the plans are shared with the list-level cs_lsolve / cs_ltsolve / cs_usolve / cs_utsolve on the same factors"""
+    lib = _csx.lib()
+    try:
+        for plan in plans:
+            _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+        return sweeps()
+    finally:
+        for plan in plans:
+            lib.csx_tri_set_order(plan, 1)
+
+
+class _LdlSolver(object):
+    """What the solvers of ldlsol_factor and schur_factor share: both stand on one partial LDL' in the library (DESIGN.md §22, §25:
+    the LDL' factor is the partial one with nothing kept).  The solver calls _ldl_init and names its entry points: _INFO, the
+    names of the info[] layout, and _CALLS, the library's refactor / info / stats functions.  _after_refactor(A2): its own
+    bookkeeping after a successful refactor."""
+
+    _INFO, _CALLS = (), ()
+
+    def _ldl_init(self, A, S, perturb, hF, N, dev):
+        self._A, self._S, self._perturb, self._hF = A, S, perturb, hF
+        self.factors = N
+        self._dev = dev                              # keeps the parts and the factor alive
+
+    @property
+    def symbolic(self):
+        return _symbolic_lists(self._S)
+
+    def _after_refactor(self, A2):
+        pass
+
+    def refactor(self, A2):
+        lib = _csx.lib()
+        A2 = _refactor_input(self._A, A2)
+        ok = _csx.C.c_int(0)
+        tau = _refactor_tau(self._perturb, lib.csx_norm1_sym, self._A, A2)     # |S|_1 of the operand
+        fn = getattr(lib, self._CALLS[0])
+        _refactor_call(A2, lambda h2: fn(self._hF, h2, tau, ok), ok)
+        if ok.value == 1:
+            _refactored(self.factors.L, self._dev)
+            self._after_refactor(A2)
+        return ok.value == 1
+
+    def info(self):
+        lib = _csx.lib()
+        raw = (_csx.C.c_int64 * len(self._INFO))()
+        st = (_csx.C.c_double * 3)()
+        _csx.check(getattr(lib, self._CALLS[1])(self._hF, raw), self._CALLS[1])
+        _csx.check(getattr(lib, self._CALLS[2])(self._hF, st), self._CALLS[2])
+        out = {name: int(v) for name, v in zip(self._INFO, raw)}
+        out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
+        return out
+
+    def inertia(self):
+        """(positive, negative) pivots of the committed factor (of A11 for a partial one)"""
+        i = self.info()
+        return i["pos"], i["neg"]
+
+    def logdet(self):
+        """(sign, log |det A|) (of A11 for a partial factor): the sign of the product of the pivots, and sum_j log |d_j|
+        correctly rounded (math.fsum)"""
+        d = self.factors.D.numpy().reshape(-1)
+        sign = -1.0 if int(np.sum(d < 0.0)) % 2 else 1.0
+        return sign, math.fsum(np.log(np.abs(d)).tolist())
+
+
 # ------------------------------------------------------------------- LDL' ----
 
-_LDL_INFO = ("n", "lnz", "levels", "launches", "pos", "neg", "perturbed", "breakdown", "kernel_us", "level_launches",
+_LDL_INFO =("n", "lnz", "levels", "launches", "pos", "neg", "perturbed", "breakdown", "kernel_us", "level_launches",
              "run_launches", "long_columns", "window")
 
 
@@ -1982,47 +2110,25 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
     n = A.n
     pinv = None if S.pinv is None else _csx.i32(S.pinv)
     lib = _csx.lib()
-
-    def threshold(hA):
-        if perturb == 0.0:
-            return 0.0
-        out = _csx.C.c_double(0.0)
-        _csx.check(lib.csx_norm1_sym(hA, out), "csx_norm1_sym")
-        return perturb * out.value
-
     hF, ok = _csx.new_handle(), _csx.C.c_int(0)
     with _Resident(A) as dA:
         _csx.check(lib.csx_ldl_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(pinv),
-                                      threshold(dA.handle), hF, ok), "csx_ldl_factor")
+                                      _perturb_tau(perturb, lib.csx_norm1_sym, dA), hF, ok), "csx_ldl_factor")
     if not ok.value:
         return None
     hL, hd = _csx.new_handle(), _csx.new_handle()
     _csx.check(lib.csx_ldl_parts(hF, hL, hd), "csx_ldl_parts")
-    # L and d are the factor's (borrowed handles): the wrappers free the plans cached on L and the factor, never L or d
     N = csn()
-    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
+    (N.L,), (N.D,) = _adopt_factor(hF, hL, vecs=[(hd, n, 1)])
     dev = N.L._dev
-    dev._fin.detach()
-    dev._fin = weakref.finalize(dev, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), dev.plans, hF)
-    N.D = dvec(n, 1, _handle=hd)
-    N.D._fin.detach()
-    N.D._keep = dev
     N.U, N.pinv, N.B = None, None, None
     hp, keep_p = _perm_handle(pinv, n)
 
-    class _Solver(_SymRefinable):
-        factors = N
-
-        @property
-        def symbolic(self):
-            for name in ("parent", "cp", "pinv"):
-                v = getattr(S, name)
-                if v is not None and not isinstance(v, list):
-                    setattr(S, name, v.tolist())
-            return S
+    class _Solver(_LdlSolver, _SymRefinable):
+        _INFO, _CALLS = _LDL_INFO, ("csx_ldl_refactor", "csx_ldl_info", "csx_ldl_stats")
 
         def __init__(self):
-            self._dev = dev                          # keeps L, d and the factor alive
+            self._ldl_init(A, S, perturb, hF, N, dev)
             self._fin = weakref.finalize(self, _csx.free, keep_p)
             self._A2, self._stands, self._source = A, dev.version, None
             self._refine_init(A, n)
@@ -2037,15 +2143,13 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
                 x = dvec(n, k)
                 _csx.check(lib.csx_permute_vec(hp, blk.handle, x.handle, n, k, 1), "csx_permute_vec")
             p1, p2 = _plan(dev, TRI_L), _plan(dev, TRI_LT)
-            try:
-                for plan in (p1, p2):
-                    _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+
+            def sweeps():
                 _csx.check(lib.csx_tri_solve(p1, x.handle, k), "csx_tri_solve")
                 _csx.check(lib.csx_block_div_rows(x.handle, hd, n, k), "csx_block_div_rows")
                 _csx.check(lib.csx_tri_solve(p2, x.handle, k), "csx_tri_solve")
-            finally:
-                lib.csx_tri_set_order(p1, 1)         # (shared with the list-level cs_lsolve / cs_ltsolve on this factor)
-                lib.csx_tri_set_order(p2, 1)
+
+            _in_order((p1, p2), in_exact_order, sweeps)
             if pinv is not None:
                 _csx.check(lib.csx_permute_vec(hp, x.handle, blk.handle, n, k, 0), "csx_permute_vec")
             return blk
@@ -2056,47 +2160,9 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
             _write_back(bhost, db, n * db.k)
             return True
 
-        def refactor(self, A2):
-            A2 = _refactor_input(A, A2)
-            ok = _csx.C.c_int(0)
-            tau = 0.0
-            if perturb > 0.0:                        # |S|_1 of the operand
-                if isinstance(A2, cs):
-                    with _Resident(A2) as d2:
-                        tau = threshold(d2.handle)
-                else:
-                    with _Resident(A) as dA:
-                        h2 = _wrap_values(dA, A2)
-                        try:
-                            tau = threshold(h2)
-                        finally:
-                            _csx.free(h2)
-            _refactor_call(A2, lambda h2: lib.csx_ldl_refactor(hF, h2, tau, ok), ok)
-            if ok.value == 1:
-                _refactored(N.L, dev)
-                self._A2, self._stands, self._source = A2, dev.version, None
-                self._operator_changed()
-            return ok.value == 1
-
-        def info(self):
-            raw = (_csx.C.c_int64 * len(_LDL_INFO))()
-            st = (_csx.C.c_double * 3)()
-            _csx.check(lib.csx_ldl_info(hF, raw), "csx_ldl_info")
-            _csx.check(lib.csx_ldl_stats(hF, st), "csx_ldl_stats")
-            out = {name: int(v) for name, v in zip(_LDL_INFO, raw)}
-            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
-            return out
-
-        def inertia(self):
-            """(positive, negative) pivots of the committed factor"""
-            i = self.info()
-            return i["pos"], i["neg"]
-
-        def logdet(self):
-            """(sign, log |det A|): the sign of the product of the pivots, and sum_j log |d_j| correctly rounded (math.fsum)"""
-            d = N.D.numpy().reshape(-1)
-            sign = -1.0 if int(np.sum(d < 0.0)) % 2 else 1.0
-            return sign, math.fsum(np.log(np.abs(d)).tolist())
+        def _after_refactor(self, A2):
+            self._A2, self._stands, self._source = A2, dev.version, None
+            self._operator_changed()
 
     return _Solver()
 
@@ -2181,35 +2247,18 @@ def schur_factor(A, keep, order=0, perturb=0.0, exact=None):
         return None
     S.pinv = pinv
     lib = _csx.lib()
-
-    def threshold(hA):
-        if perturb == 0.0:
-            return 0.0
-        out = _csx.C.c_double(0.0)
-        _csx.check(lib.csx_norm1_sym(hA, out), "csx_norm1_sym")
-        return perturb * out.value
-
     hF, ok = _csx.new_handle(), _csx.C.c_int(0)
     with _Resident(A) as dA:
         _csx.check(lib.csx_schur_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(pinv), n1,
-                                        threshold(dA.handle), hF, ok), "csx_schur_factor")
+                                        _perturb_tau(perturb, lib.csx_norm1_sym, dA), hF, ok), "csx_schur_factor")
     if not ok.value:
         return None
     hL, hd, hS = _csx.new_handle(), _csx.new_handle(), _csx.new_handle()
     _csx.check(lib.csx_schur_parts(hF, hL, hd, hS), "csx_schur_parts")
-    # Lp, d and S are the factor's (borrowed handles): the wrappers free the plans cached on Lp and the factor, nothing else
     N = csn()
-    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
+    (N.L,), (N.D, Sd) = _adopt_factor(hF, hL, vecs=[(hd, n1, 1), (hS, ns, max(ns, 1))])
     dev = N.L._dev
-    dev._fin.detach()
-    dev._fin = weakref.finalize(dev, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), dev.plans, hF)
-    N.D = dvec(n1, 1, _handle=hd)
-    N.D._fin.detach()
-    N.D._keep = dev
     N.U, N.pinv, N.B = None, None, None
-    Sd = dvec(ns, max(ns, 1), _handle=hS)
-    Sd._fin.detach()
-    Sd._keep = dev
     hp, keep_p = _perm_handle(pinv, n)
 
     def tail(x, k):
@@ -2218,30 +2267,18 @@ def schur_factor(A, keep, order=0, perturb=0.0, exact=None):
         _csx.check(lib.csx_vec_wrap(_csx.C.c_void_p(x.device_ptr() + 8 * n1 * k), ns * k, h), "csx_vec_wrap")
         return h
 
-    class _Solver(object):
-        factors = N
+    class _Solver(_LdlSolver):
+        _INFO, _CALLS = _SCHUR_INFO, ("csx_schur_refactor", "csx_schur_info", "csx_schur_stats")
         schur = Sd
 
-        @property
-        def symbolic(self):
-            for name in ("parent", "cp", "pinv"):
-                v = getattr(S, name)
-                if v is not None and not isinstance(v, list):
-                    setattr(S, name, v.tolist())
-            return S
-
         def __init__(self):
-            self._dev = dev                          # keeps Lp, d, S and the factor alive
+            self._ldl_init(A, S, perturb, hF, N, dev)
             self._fin = weakref.finalize(self, _csx.free, keep_p)
             self.keep = list(keep)
 
         def _sweep(self, kind, x, k, in_exact_order):
             plan = _plan(dev, kind)
-            try:
-                _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
-                _csx.check(lib.csx_tri_solve(plan, x.handle, k), "csx_tri_solve")
-            finally:
-                lib.csx_tri_set_order(plan, 1)       # (shared with the list-level cs_lsolve / cs_ltsolve on this factor)
+            _in_order((plan,), in_exact_order, lambda: _csx.check(lib.csx_tri_solve(plan, x.handle, k), "csx_tri_solve"))
 
         def _condense(self, blk, in_exact_order):
             k = blk.k
@@ -2302,46 +2339,6 @@ def schur_factor(A, keep, order=0, perturb=0.0, exact=None):
             self._expand(state, x2, in_exact_order, out=db)
             _write_back(bhost, db, n * db.k)
             return True
-
-        def refactor(self, A2):
-            A2 = _refactor_input(A, A2)
-            ok = _csx.C.c_int(0)
-            tau = 0.0
-            if perturb > 0.0:                        # |S|_1 of the operand
-                if isinstance(A2, cs):
-                    with _Resident(A2) as d2:
-                        tau = threshold(d2.handle)
-                else:
-                    with _Resident(A) as dA:
-                        h2 = _wrap_values(dA, A2)
-                        try:
-                            tau = threshold(h2)
-                        finally:
-                            _csx.free(h2)
-            _refactor_call(A2, lambda h2: lib.csx_schur_refactor(hF, h2, tau, ok), ok)
-            if ok.value == 1:
-                _refactored(N.L, dev)
-            return ok.value == 1
-
-        def info(self):
-            raw = (_csx.C.c_int64 * len(_SCHUR_INFO))()
-            st = (_csx.C.c_double * 3)()
-            _csx.check(lib.csx_schur_info(hF, raw), "csx_schur_info")
-            _csx.check(lib.csx_schur_stats(hF, st), "csx_schur_stats")
-            out = {name: int(v) for name, v in zip(_SCHUR_INFO, raw)}
-            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
-            return out
-
-        def inertia(self):
-            """(positive, negative) pivots of A11 in the committed factor"""
-            i = self.info()
-            return i["pos"], i["neg"]
-
-        def logdet(self):
-            """(sign, log |det A11|): the sign of the product of the pivots, and sum_j log |d_j| correctly rounded (math.fsum)"""
-            d = N.D.numpy().reshape(-1)
-            sign = -1.0 if int(np.sum(d < 0.0)) % 2 else 1.0
-            return sign, math.fsum(np.log(np.abs(d)).tolist())
 
     return _Solver()
 
@@ -2780,13 +2777,8 @@ def lusol_factor(A, order=0, tol=1.0, exact=None):
                 else:
                     p1, p2, fn, name = _plan(dL, TRI_L), _plan(dU, TRI_U), lib.csx_lusol_solve, "csx_lusol_solve"
                 fused = _csx.C.c_int(0)
-                try:
-                    for plan in (p1, p2):
-                        _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
-                    _csx.check(fn(p1, p2, hp, hq, blk.handle, x.handle, blk.k, _csx.C.byref(fused)), name)
-                finally:
-                    lib.csx_tri_set_order(p1, 1)
-                    lib.csx_tri_set_order(p2, 1)
+                _in_order((p1, p2), in_exact_order,
+                          lambda: _csx.check(fn(p1, p2, hp, hq, blk.handle, x.handle, blk.k, _csx.C.byref(fused)), name))
             self.last_fused = bool(fused.value)
             return blk
 
@@ -2929,32 +2921,17 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
         return None
     pinv = None if S.pinv is None else _csx.i32(S.pinv)
     lib = _csx.lib()
-
-    def threshold(hA):
-        if perturb == 0.0:
-            return 0.0
-        out = _csx.C.c_double(0.0)
-        _csx.check(lib.csx_norm1(hA, out), "csx_norm1")
-        return perturb * out.value
-
     hF, ok = _csx.new_handle(), _csx.C.c_int(0)
     with _Resident(A) as dA:
         _csx.check(lib.csx_slu_factor(dA.handle, _csx.pi(_csx.i32(S.parent)), _csx.pi(_csx.i32(S.cp)), _csx.pi(prow), _csx.pi(pinv),
-                                      threshold(dA.handle), hF, ok), "csx_slu_factor")
+                                      _perturb_tau(perturb, lib.csx_norm1, dA), hF, ok), "csx_slu_factor")
     if not ok.value:
         return None
     hL, hU = _csx.new_handle(), _csx.new_handle()
     _csx.check(lib.csx_slu_parts(hF, hL, hU), "csx_slu_parts")
-    # L and Ut are the factor's (borrowed handles): the wrappers free the plans cached on them and the factor, never L or Ut
     N = csn()
-    N.L = cs_pin(_from_device(hL, lambda nnz: max(nnz, 1)))
-    N.U = cs_pin(_from_device(hU, lambda nnz: max(nnz, 1)))
+    (N.L, N.U), _ = _adopt_factor(hF, hL, mats=[hU])     # (Ut lives in the factor that L's wrapper frees)
     devL, devU = N.L._dev, N.U._dev
-    devL._fin.detach()
-    devL._fin = weakref.finalize(devL, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), devL.plans, hF)
-    devU._fin.detach()
-    devU._fin = weakref.finalize(devU, _DevMatrix._release, None, devU.plans)
-    devU._keep = devL                                # Ut lives in the factor that L's wrapper frees
     N.prow = None if prow is None else prow.tolist()
     N.pinv, N.B = None if pinv is None else pinv.tolist(), None
     # the two permutations of a solve: x(comb) = b before the forward sweeps, x = x(pinv) after them (swapped for A')
@@ -2968,13 +2945,7 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
     class _Solver(_Refinable):
         factors = N
 
-        @property
-        def symbolic(self):
-            for name in ("parent", "cp", "pinv"):
-                v = getattr(S, name)
-                if v is not None and not isinstance(v, list):
-                    setattr(S, name, v.tolist())
-            return S
+        symbolic = property(lambda self: _symbolic_lists(S))
 
         def __init__(self):
             self._devs = (devL, devU)                # keep L, Ut and the factor alive
@@ -2993,14 +2964,12 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
                 x = dvec(n, k)
                 _csx.check(lib.csx_permute_vec(h_in, blk.handle, x.handle, n, k, 1), "csx_permute_vec")
             p1, p2 = (_plan(devU, TRI_L), _plan(devL, TRI_LT)) if trans else (_plan(devL, TRI_L), _plan(devU, TRI_LT))
-            try:
-                for plan in (p1, p2):
-                    _csx.check(lib.csx_tri_set_order(plan, 1 if in_exact_order else 0), "csx_tri_set_order")
+
+            def sweeps():
                 _csx.check(lib.csx_tri_solve(p1, x.handle, k), "csx_tri_solve")
                 _csx.check(lib.csx_tri_solve(p2, x.handle, k), "csx_tri_solve")
-            finally:
-                lib.csx_tri_set_order(p1, 1)         # (shared with the list-level cs_lsolve / cs_ltsolve on these factors)
-                lib.csx_tri_set_order(p2, 1)
+
+            _in_order((p1, p2), in_exact_order, sweeps)
             if p_out is not None:
                 y = blk if x is not blk else dvec(n, k)
                 _csx.check(lib.csx_permute_vec(h_out, x.handle, y.handle, n, k, 0), "csx_permute_vec")
@@ -3019,7 +2988,7 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
         def refactor(self, A2):
             A2 = _refactor_input(A, A2)
             ok = _csx.C.c_int(0)
-            tau = perturb * _refactor_norm(A, A2) if perturb > 0.0 else 0.0
+            tau = _refactor_tau(perturb, lib.csx_norm1, A, A2)
             _refactor_call(A2, lambda h2: lib.csx_slu_refactor(hF, h2, tau, ok), ok)
             if ok.value == 1:
                 _refactored(N.L, devL)
@@ -3415,16 +3384,9 @@ def hqrsol_factor(A, order=0):
         return None
     hV, hR, hB = _csx.new_handle(), _csx.new_handle(), _csx.new_handle()
     _csx.check(lib.csx_hqr_parts(hF, hV, hR, hB), "csx_hqr_parts")
-    # V, R and beta are the factor's (borrowed handles): the wrappers free the plans cached on them and the factor, never the parts
     N = csn()
-    N.L = cs_pin(_from_device(hV, lambda nnz: max(nnz, 1)))
-    N.U = cs_pin(_from_device(hR, lambda nnz: max(nnz, 1)))
+    (N.L, N.U), _ = _adopt_factor(hF, hV, mats=[hR])     # (R and beta live in the factor that V's wrapper frees)
     devV, devR = N.L._dev, N.U._dev
-    devV._fin.detach()
-    devV._fin = weakref.finalize(devV, lambda plans, h: (_DevMatrix._release(None, plans), _csx.free(h)), devV.plans, hF)
-    devR._fin.detach()
-    devR._fin = weakref.finalize(devR, _DevMatrix._release, None, devR.plans)
-    devR._keep = devV                                # R lives in the factor that V's wrapper frees
     N.pinv = None
 
     def read_beta():

@@ -249,10 +249,10 @@ static void free_object(Object &o) {
         case K_CHOLREFPLAN: destroy((CholRefPlan *)o.ptr); break;
         case K_MULPLAN: destroy((MulPlan *)o.ptr); break;
         case K_ADDPLAN: destroy((AddPlan *)o.ptr); break;
-        case K_LDLFACTOR: destroy((LdlFactor *)o.ptr); break;
+        case K_LDLFACTOR:
+        case K_SCHURFACTOR: destroy((LdlFactor *)o.ptr); break;
         case K_SLUFACTOR: destroy((SluFactor *)o.ptr); break;
         case K_HQRFACTOR: destroy((HqrFactor *)o.ptr); break;
-        case K_SCHURFACTOR: destroy((SchurFactor *)o.ptr); break;
         default: break;
     }
     o.kind = K_FREE;   // the generation stays: the next put() of this slot bumps it

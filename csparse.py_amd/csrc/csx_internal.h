@@ -219,14 +219,12 @@ struct CholAnalysis;  // csx_chol.hip
 struct CholRefPlan;   // csx_chol_refactor.hip
 void destroy(CholAnalysis *p);
 void destroy(CholRefPlan *p);
-struct LdlFactor;     // csx_ldl.hip
+struct LdlFactor;     // csx_ldl.h: the one partial-LDL' factor behind K_LDLFACTOR and K_SCHURFACTOR (csx_ldl.hip, csx_schur.hip)
 void destroy(LdlFactor *p);
 struct SluFactor;     // csx_slu.hip
 void destroy(SluFactor *p);
 struct HqrFactor;     // csx_hqr.hip
 void destroy(HqrFactor *p);
-struct SchurFactor;   // csx_schur.hip
-void destroy(SchurFactor *p);
 // csx_host.cpp: csx_hqr_symbolic_host on vectors that grow (no capacities)
 int hqr_symbolic(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q, const int32_t *parent,
                  const int32_t *pinv, const int32_t *leftmost, std::vector<int32_t> &Vp, std::vector<int32_t> &Vi,

@@ -9,6 +9,9 @@
 //   k_block_div_rows  X[i, :] /= d[i], the D step of a solve
 // Every sum is updated in ascending k by one wave, one update after the other: L.x and d are byte-equal to csx_ldl_host.
 // A factor or refactor runs into scratch arrays and is committed only when no column broke down.
+// The host side is the partial elimination of the first n1 columns (LdlFactor, ldl_build, ldl_run, ldl_refactor: csx_ldl.h):
+// csx_ldl_factor is n1 = n with the walker uncapped, csx_schur_factor (csx_schur.hip) its own n1 with the walker cut; the
+// trailing columns are csx_schur.hip's kernel behind schur_launch_cols.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -192,89 +195,62 @@ __global__ __launch_bounds__(256) void k_block_div_rows(double *__restrict__ X, 
     }
 }
 
-struct LdlFactor {
-    int32_t n = 0, anz = 0, lnz = 0;
-    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
-    DevBuf<int32_t> rp, rc, rpos;           // row view of L (chol_symbolic_device)
-    DevBuf<int32_t> win;                    // the entry map
-    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the elimination tree: columns by level, ascending inside one
-    std::vector<int32_t> level_ptr_h;
-    csx_handle_t hL = 0, hd = 0;            // the committed factor: owned here, lent out by csx_ldl_parts
-    DevBuf<double> Lx, dd;                  // scratch of a run: committed only when no column broke down
-    DevBuf<int> flags;                      // [0] smallest broken column, [1] perturbed pivots, [2] columns updated in place
-    DevBuf<unsigned long long> stats;       // k_ldl_stats
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    // csx_ldl_info / csx_ldl_stats
-    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0;   // long_cols: counted by the kernels of the last run
-    int64_t pos = 0, neg = 0, perturbed = 0, breakdown = -1, kernel_us = 0;
-    double min_d = 0.0, max_d = 0.0, max_l = 0.0;
-    LdlFactor() = default;
-    LdlFactor(const LdlFactor &) = delete;
-    LdlFactor &operator=(const LdlFactor &) = delete;
-    ~LdlFactor() {
-        if (hL) (void)csx_free(hL);
-        if (hd) (void)csx_free(hd);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-    }
-};
-
 void destroy(LdlFactor *F) { delete F; }
 
-void ldl_launch_levels(const std::vector<int32_t> &lp, const int32_t *level_cols, const int32_t *level_ptr, const int32_t *Lp,
-                       const int32_t *Li, double *Lx, double *d, const int32_t *row_ptr, const int32_t *row_col,
-                       const int32_t *row_pos, double tau, int *flags, int32_t run_cap, int64_t *level_launches,
-                       int64_t *run_launches) {
+// The numeric launches of the first n1 columns over their height levels: a level of more than LDL_WAVES columns is one launch of
+// the wave-per-column kernel, a run of narrower levels goes to the one-workgroup walker, at most F->run_cap levels a launch.
+static void ldl_launch_levels(LdlFactor *F, double tau) {
     hipStream_t s = ctx().stream;
+    const std::vector<int32_t> &lp = F->level_ptr_h;
     const int32_t nlev = (int32_t)lp.size() - 1;
     for (int32_t l = 0; l < nlev;) {
         const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
         if (cnt > LDL_WAVES) {
             hipLaunchKernelGGL(k_ldl_level, dim3((unsigned)((cnt + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, s,
-                               level_cols + lp[(size_t)l], cnt, Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, flags);
-            ++*level_launches;
+                               F->level_cols.get() + lp[(size_t)l], cnt, F->Lp, F->Li, F->Lx.get(), F->dd.get(), F->rp.get(),
+                               F->rc.get(), F->rpos.get(), tau, F->flags.get());
+            F->level_launches++;
             l++;
             continue;
         }
         int32_t e = l + 1;   // a run of narrow levels: one workgroup, no way back to the host
-        while (e < nlev && e - l < run_cap && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
-        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, level_cols, level_ptr, l, e, Lp, Li, Lx, d, row_ptr,
-                           row_col, row_pos, tau, flags);
-        ++*run_launches;
+        while (e < nlev && e - l < F->run_cap && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
+        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), l, e, F->Lp, F->Li,
+                           F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(), F->rpos.get(), tau, F->flags.get());
+        F->run_launches++;
         l = e;
     }
 }
 
-void ldl_launch_stats(int32_t n, const int32_t *Lp, const double *Lx, const double *d, unsigned long long *st) {
-    if (n > 0) hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, ctx().stream, n, Lp, Lx, d, st);
-}
-
-// The factor of the values Ax (A's storage order) into the scratch arrays, with the statistics of what was computed; commits
-// into L.x / d when no column broke down.  *ok: 1 committed, 0 breakdown (L, d untouched).  Synchronises.
-static int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
+int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     hipStream_t s = ctx().stream;
     Csc *L = csc(F->hL);
-    Vec *dv = vec(F->hd);
-    if (!L || !dv || !L->x || L->nnz != F->lnz || dv->len != F->n) return CSX_EINVAL;
-    const int32_t n = F->n;
-    F->launches = F->level_launches = F->run_launches = 0;
+    Vec *dv = vec(F->hd), *Sv = vec(F->hS);
+    const int64_t ns = F->ns;
+    if (!L || !dv || !Sv || !L->x || L->nnz != F->head + ns || dv->len != F->n1 || Sv->len != ns * ns) return CSX_EINVAL;
+    const int32_t n1 = F->n1;
+    F->level_launches = F->run_launches = F->schur_launches = 0;
     const int hinit[3] = {LDL_NONE, 0, 0};
     const unsigned long long sinit[5] = {0ull, 0ull, ~0ull, 0ull, 0ull};
     CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
     CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
     CSX_HIP(hipEventRecord(F->ev_a, s));
     CSX_TRY(chol_scatter(F->lnz, F->win, Ax, F->Lx));
-    ldl_launch_levels(F->level_ptr_h, F->level_cols.get(), F->level_ptr.get(), L->p, L->i, F->Lx.get(), F->dd.get(), F->rp.get(),
-                      F->rc.get(), F->rpos.get(), tau, F->flags.get(), LDL_RUN_UNCAPPED, &F->level_launches, &F->run_launches);
-    F->launches = F->level_launches + F->run_launches;
-    ldl_launch_stats(n, L->p, F->Lx.get(), F->dd.get(), F->stats.get());
+    ldl_launch_levels(F, tau);
+    if (F->chunks > 0) {
+        schur_launch_cols(F);
+        F->schur_launches = 1;
+    }
+    if (n1 > 0)
+        hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n1 + 3) / 4)), dim3(256), 0, s, n1, F->Lp, F->Lx.get(), F->dd.get(),
+                           F->stats.get());
     (void)hipEventRecord(F->ev_b, s);
     int hflags[3] = {LDL_NONE, 0, 0};
     unsigned long long hst[5] = {0, 0, 0, 0, 0};
     if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
-        set_error("csx_ldl: %s", hipGetErrorString(hipGetLastError()));
+        set_error("%s: %s", F->who, hipGetErrorString(hipGetLastError()));
         (void)hipStreamSynchronize(s);
         return CSX_ERUNTIME;
     }
@@ -287,65 +263,130 @@ static int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     if (!*ok) return CSX_OK;
     F->pos = (int64_t)hst[0];
     F->neg = (int64_t)hst[1];
-    if (n == 0) hst[2] = 0;
+    if (n1 == 0) hst[2] = 0;
     std::memcpy(&F->min_d, &hst[2], 8);
     std::memcpy(&F->max_d, &hst[3], 8);
     std::memcpy(&F->max_l, &hst[4], 8);
-    if (F->lnz) CSX_HIP(hipMemcpyAsync(L->x, F->Lx.get(), (size_t)F->lnz * sizeof(double), hipMemcpyDeviceToDevice, s));
-    if (n) CSX_HIP(hipMemcpyAsync(dv->d, F->dd.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    // (the ns unit values behind L->x[head) were written by ldl_build and never change)
+    if (F->head) CSX_HIP(hipMemcpyAsync(L->x, F->Lx.get(), (size_t)F->head * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (n1) CSX_HIP(hipMemcpyAsync(dv->d, F->dd.get(), (size_t)n1 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (ns) CSX_HIP(hipMemcpyAsync(Sv->d, F->Sx.get(), (size_t)(ns * ns) * sizeof(double), hipMemcpyDeviceToDevice, s));
     L->rows.reset();    // (copies of the old values)
     L->tiled.reset();
     CSX_HIP(hipStreamSynchronize(s));
     return CSX_OK;
 }
 
-static int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, LdlFactor *F) {
+int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t n1, int32_t run_cap, const char *who,
+              LdlFactor *F) {
     hipStream_t s = ctx().stream;
-    const int32_t n = A->n;
+    const int32_t n = A->n, ns = n - n1;
     F->n = n;
+    F->n1 = n1;
+    F->ns = ns;
+    F->run_cap = run_cap;
+    F->who = who;
     F->anz = A->nnz;
     F->lnz = cp[n];
     if (cp[0] != 0 || F->lnz < n) return CSX_EINVAL;
+    for (int32_t j = 0; j < n; j++)
+        if (cp[j + 1] <= cp[j]) return CSX_EINVAL;
+    F->head = cp[n1];
     if (!A->trusted) CSX_TRY(csc_validate(A));
     CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
     CSX_TRY(F->flags.alloc(3));
     CSX_TRY(F->stats.alloc(5));
     CSX_HIP(hipEventCreate(&F->ev_a));
     CSX_HIP(hipEventCreate(&F->ev_b));
+    const int64_t lpnz = (int64_t)F->head + ns;
     std::unique_ptr<Csc> L(new Csc());
     L->m = L->n = n;
-    L->nnz = F->lnz;
+    L->nnz = (int32_t)lpnz;
+    CSX_TRY(dalloc(&L->x, (size_t)lpnz));
+    std::vector<int32_t> cols, lp, tail;   // (host lists of the copies queued below: alive until the stream is synchronised)
+    const std::vector<double> ones((size_t)ns, 1.0);
     if (n == 0) {
         CSX_TRY(dalloc(&L->p, 1));
         CSX_HIP(hipMemsetAsync(L->p, 0, sizeof(int32_t), s));
         CSX_TRY(dalloc(&L->i, 0));
+        F->Lp = L->p;
+        F->Li = L->i;
         F->level_ptr_h.assign(1, 0);
     } else {
-        CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &F->rp, &F->rc, &F->rpos, nullptr));   // (checks S and pinv)
-        std::vector<int32_t> cols;
-        ldl_levels(n, parent, F->level_ptr_h, cols);
+        int32_t *fp = nullptr, *fi = nullptr;
+        const int st = chol_symbolic_device(A, parent, cp, pinv, &fp, &fi, &F->rp, &F->rc, &F->rpos, nullptr);   // (checks S and pinv)
+        if (ns == 0) {   // Lp's pattern is the full pattern
+            L->p = fp;
+            L->i = fi;
+        } else {
+            F->fp = DevBuf<int32_t>(fp);
+            F->fi = DevBuf<int32_t>(fi);
+        }
+        CSX_TRY(st);
+        F->Lp = fp;
+        F->Li = fi;
+        // the height levels of the first n1 columns: the tree cut at n1 (a parent among the kept columns is no parent); a column's
+        // level depends on its children alone, so the cut leaves the levels below it as they are, and at n1 == n it cuts nothing
+        std::vector<int32_t> cut((size_t)n1);
+        for (int32_t j = 0; j < n1; j++) cut[(size_t)j] = parent[j] < n1 ? parent[j] : -1;
+        ldl_levels(n1, cut.data(), F->level_ptr_h, cols);
         CSX_TRY(upload(F->level_cols, cols));
         CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
         CSX_TRY(F->win.alloc((size_t)F->lnz));
         DevBuf<int32_t> d_pinv;
         if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
-        CSX_TRY(chol_entry_map(A, pinv ? d_pinv.get() : nullptr, L->p, L->i, F->lnz, F->win, F->flags));
+        CSX_TRY(chol_entry_map(A, pinv ? d_pinv.get() : nullptr, fp, fi, F->lnz, F->win, F->flags));
+        if (ns) {   // Lp: the interior columns of the full pattern, then one unit diagonal entry per kept column
+            lp.resize((size_t)n + 1);
+            tail.resize((size_t)ns);
+            for (int32_t j = 0; j <= n; j++) lp[(size_t)j] = j <= n1 ? cp[j] : F->head + (j - n1);
+            for (int32_t t = 0; t < ns; t++) tail[(size_t)t] = n1 + t;
+            CSX_TRY(dalloc(&L->p, (size_t)n + 1));
+            CSX_TRY(dalloc(&L->i, (size_t)lpnz));
+            CSX_HIP(hipMemcpyAsync(L->p, lp.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            if (F->head) CSX_HIP(hipMemcpyAsync(L->i, fi, (size_t)F->head * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            CSX_HIP(hipMemcpyAsync(L->i + F->head, tail.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            CSX_HIP(hipMemcpyAsync(L->x + F->head, ones.data(), (size_t)ns * sizeof(double), hipMemcpyHostToDevice, s));
+        }
         int bad = 0;
         CSX_HIP(hipMemcpyAsync(&bad, F->flags.get(), sizeof(int), hipMemcpyDeviceToHost, s));
-        CSX_HIP(hipStreamSynchronize(s));   // (cols, level_ptr_h and pinv have landed too)
+        CSX_HIP(hipStreamSynchronize(s));   // (every host list above has landed too)
         if (bad) {
-            set_error("csx_ldl_factor: an upper entry of A has no slot in L (S is not A's)");
+            set_error("%s_factor: an upper entry of A has no slot in L (S is not A's)", who);
             return CSX_EINVAL;
         }
     }
-    CSX_TRY(dalloc(&L->x, (size_t)F->lnz));
     CSX_TRY(F->Lx.alloc((size_t)F->lnz));
-    CSX_TRY(F->dd.alloc((size_t)n));
-    std::unique_ptr<Vec> dv(new Vec());
-    dv->len = n;
-    CSX_TRY(dmalloc(&dv->d, (size_t)n * sizeof(double)));
+    CSX_TRY(F->dd.alloc((size_t)n1));
+    CSX_TRY(F->Sx.alloc((size_t)ns * (size_t)ns));
+    std::unique_ptr<Vec> dv(new Vec()), Sv(new Vec());
+    dv->len = n1;
+    CSX_TRY(dmalloc(&dv->d, (size_t)n1 * sizeof(double)));
+    Sv->len = (int64_t)ns * ns;
+    CSX_TRY(dmalloc(&Sv->d, (size_t)ns * (size_t)ns * sizeof(double)));
     F->hL = put(K_CSC, L.release());
     F->hd = put(K_VEC, dv.release());
+    F->hS = put(K_VEC, Sv.release());
+    return CSX_OK;
+}
+
+int ldl_refactor(LdlFactor *F, csx_handle_t hA2, double tau, int *ok) {
+    if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
+    *ok = -1;
+    const double *x2 = nullptr;
+    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
+    if (!x2) {
+        set_error("%s_refactor: A2 does not have the pattern (or the length) of the factored matrix", F->who);
+        return CSX_EINVAL;   // nothing changes
+    }
+    return ldl_run(F, x2, tau, ok);
+}
+
+int ldl_stats(const LdlFactor *F, double *out) {
+    if (!F || !out) return CSX_EINVAL;
+    out[0] = F->min_d;
+    out[1] = F->max_d;
+    out[2] = F->max_l;
     return CSX_OK;
 }
 
@@ -361,7 +402,7 @@ extern "C" int csx_ldl_factor(csx_handle_t hA, const int32_t *parent, const int3
     *out = 0;
     *ok = 0;
     std::unique_ptr<LdlFactor> F(new LdlFactor());
-    CSX_TRY(ldl_build(A, parent, cp, pinv, F.get()));
+    CSX_TRY(ldl_build(A, parent, cp, pinv, A->n, LDL_RUN_UNCAPPED, "csx_ldl", F.get()));   // nothing kept
     CSX_TRY(ldl_run(F.get(), A->x, tau, ok));
     if (*ok) *out = put(K_LDLFACTOR, F.release());
     return CSX_OK;
@@ -369,16 +410,7 @@ extern "C" int csx_ldl_factor(csx_handle_t hA, const int32_t *parent, const int3
 
 extern "C" int csx_ldl_refactor(csx_handle_t h, csx_handle_t hA2, double tau, int *ok) {
     CSX_TRY(require_ready());
-    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
-    if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
-    *ok = -1;
-    const double *x2 = nullptr;
-    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
-    if (!x2) {
-        set_error("csx_ldl_refactor: A2 does not have the pattern (or the length) of the factored matrix");
-        return CSX_EINVAL;   // nothing changes
-    }
-    return ldl_run(F, x2, tau, ok);
+    return ldl_refactor((LdlFactor *)get(h, K_LDLFACTOR), hA2, tau, ok);
 }
 
 extern "C" int csx_ldl_parts(csx_handle_t h, csx_handle_t *L, csx_handle_t *d) {
@@ -397,7 +429,7 @@ extern "C" int csx_ldl_info(csx_handle_t h, int64_t *info) {
     info[0] = F->n;
     info[1] = F->lnz;
     info[2] = (int64_t)F->level_ptr_h.size() - 1;
-    info[3] = F->launches;
+    info[3] = F->level_launches + F->run_launches;
     info[4] = F->pos;
     info[5] = F->neg;
     info[6] = F->perturbed;
@@ -418,12 +450,7 @@ extern "C" int csx_ldl_window(int32_t *entries) {   // (no device needed)
 
 extern "C" int csx_ldl_stats(csx_handle_t h, double *out) {
     CSX_TRY(require_ready());
-    LdlFactor *F = (LdlFactor *)get(h, K_LDLFACTOR);
-    if (!F || !out) return CSX_EINVAL;
-    out[0] = F->min_d;
-    out[1] = F->max_d;
-    out[2] = F->max_l;
-    return CSX_OK;
+    return ldl_stats((const LdlFactor *)get(h, K_LDLFACTOR), out);
 }
 
 extern "C" int csx_block_div_rows(csx_handle_t hX, csx_handle_t hd, int64_t rows, int32_t nrhs) {

@@ -1,6 +1,7 @@
 """schur_factor on the device on the cases of tests/schur_cases.py: Lp.p, Lp.i, Lp.x, d, S, the inertia and the
 statistics byte-equal to csx_schur_host (which tests/test_schur_cpu.py holds to the Python restatement) for every case, order and
-value set; ldlsol_factor's bytes for ns = 0; which launches ran; refactor against a fresh factor, a breaking refactor that
+value set; ldlsol_factor's bytes for ns = 0 -- the two stand on one core: the walker's cap stays the entry point's,
+the two handle kinds stay apart, Lp.x keeps its unit tail through every refactor, the two info() faces; which launches ran; refactor against a fresh factor, a breaking refactor that
 changes nothing, and a refactor after it; condense / expand of lists against the plain-Python restatement and exact blocks
 against the lists; rounding-equal blocks through solve(b, interface) held to twice the backward error of the exact route; the
 CSX_EINVAL cases of the C ABI."""
@@ -149,6 +150,84 @@ def test_which_launches_ran(cs):
     sc = SC.BY_NAME["grid-cross-1"]
     i = _factor(cs, sc).info()
     assert i["schur_chunks"] == sc.ns and i["level_launches"] >= 1 and i["long_columns"] == 0
+
+
+def test_the_walker_cap_is_the_entry_points(cs):
+    """257 levels of one column: ldlsol_factor's walker takes them in one launch, schur_factor's is cut at 256 -- with nothing kept
+    too.  257 is the smallest size at which one cap for both would show."""
+    import ldl_cases as LC
+    A = LC.BY_NAME["chain"].matrix(cs)
+    G, F = cs.ldlsol_factor(A, 0), cs.schur_factor(A, [], 0)
+    g, f = G.info(), F.info()
+    assert (g["levels"], g["run_launches"], g["level_launches"]) == (257, 1, 0)
+    assert (f["levels"], f["run_launches"], f["level_launches"]) == (257, 2, 0)
+    assert _download(cs, F.factors.L)[2].tobytes() == _download(cs, G.factors.L)[2].tobytes()
+    assert F.factors.D.numpy().tobytes() == G.factors.D.numpy().tobytes()
+
+
+def test_handle_kinds_stay_apart(cs):
+    """an ldl handle is no schur handle and the reverse: CSX_EINVAL from info, parts, stats and refactor, `ok` of a refactor untouched"""
+    import _csx
+    lib, C = _csx.lib(), _csx.C
+    sc = SC.BY_NAME["grid-line-0"]
+    A = cs.cs_pin(sc.matrix(cs))
+    S = cs.schur_factor(A, sc.keep, 0).symbolic
+    parent, cp, pinv = (_csx.pi(_csx.i32(v)) for v in (S.parent, S.cp, S.pinv))
+    hl, hs, ok = _csx.new_handle(), _csx.new_handle(), C.c_int(0)
+    try:
+        assert lib.csx_ldl_factor(A._dev.handle, parent, cp, pinv, 0.0, hl, ok) == _csx.OK and ok.value == 1
+        assert lib.csx_schur_factor(A._dev.handle, parent, cp, pinv, sc.n1, 0.0, hs, ok) == _csx.OK and ok.value == 1
+        raw, st = (C.c_int64 * 32)(), np.zeros(3)
+        a, b, c = _csx.new_handle(), _csx.new_handle(), _csx.new_handle()
+        assert lib.csx_ldl_info(hl, raw) == _csx.OK and lib.csx_schur_info(hs, raw) == _csx.OK
+        assert lib.csx_schur_info(hl, raw) == _csx.EINVAL and lib.csx_ldl_info(hs, raw) == _csx.EINVAL
+        assert lib.csx_schur_parts(hl, a, b, c) == _csx.EINVAL and lib.csx_ldl_parts(hs, a, b) == _csx.EINVAL
+        assert lib.csx_schur_stats(hl, _csx.pd(st)) == _csx.EINVAL and lib.csx_ldl_stats(hs, _csx.pd(st)) == _csx.EINVAL
+        for fn, h in ((lib.csx_schur_refactor, hl), (lib.csx_ldl_refactor, hs)):
+            ok.value = 7
+            assert fn(h, A._dev.handle, 0.0, ok) == _csx.EINVAL and ok.value == 7
+    finally:
+        _csx.free(hl)
+        _csx.free(hs)
+
+
+@pytest.mark.parametrize("name", ["one-keep-all", "grid-line-0"])
+def test_the_unit_tail_survives_every_path(cs, name):
+    """the last ns values of Lp.x are 1.0 and Lp.x is the host rule's of the values last committed: after a refactor, a breaking
+    refactor and a refactor again.  one-keep-all: n1 = 0, Lp.x is the tail alone."""
+    sc = SC.BY_NAME[name]
+    F = _factor(cs, sc, "A")
+
+    def is_committed(which):
+        x = _download(cs, F.factors.L)[2]
+        assert x[len(x) - sc.ns:].tolist() == [1.0] * sc.ns
+        assert x.tobytes() == SO.reference(sc, which)[0].tobytes()
+
+    is_committed("A")
+    assert F.refactor(sc.case.A2[0]) is True
+    is_committed(0)
+    if sc.n1:
+        assert F.refactor(sc.case.breaking(SO.first_column(sc))) is False
+        is_committed(0)
+    else:
+        assert F.refactor(sc.kept_zero()) is True        # no interior column, nothing can break: a zero kept diagonal is data
+        is_committed("kept-zero")
+        assert _S(F, sc).tolist() == [[0.0]]
+    assert F.refactor(sc.matrix(cs, sc.case.A2[1])) is True
+    is_committed(1)
+
+
+def test_info_faces(cs):
+    sc = SC.BY_NAME["kkt-sqd"]
+    A = sc.matrix(cs)
+    F, G = cs.schur_factor(A, [], 1), cs.ldlsol_factor(A, 1)
+    stats = ["min_abs_d", "max_abs_d", "max_abs_l"]
+    assert list(G.info()) == ["n", "lnz", "levels", "launches", "pos", "neg", "perturbed", "breakdown", "kernel_us", "level_launches",
+                              "run_launches", "long_columns", "window"] + stats
+    assert list(F.info()) == ["n", "n1", "ns", "lnz", "levels", "launches", "level_launches", "run_launches", "schur_launches",
+                              "schur_chunks", "pos", "neg", "perturbed", "breakdown", "kernel_us", "long_columns", "window"] + stats
+    assert F.inertia() == G.inertia() and F.logdet() == G.logdet()
+    assert sum(F.inertia()) == sc.n
 
 
 def _lists(sc, F, cols, x2):
