@@ -37,6 +37,8 @@ _PROTOS = {
     "csx_cholsol_set_order": [H, C.c_int],
     "csx_cholsol_growth": [H, _f64p],
     "csx_cholsol_sn_info": [H, _i32p, _i32p, _i32p, _i32p, _f64p],
+    "csx_cholsol_sn_geometry": [H, C.POINTER(C.c_int64), C.c_int32, _i32p],
+    "csx_cholsol_sn_launches": [H, C.POINTER(C.c_int64), C.c_int32, _i32p],
     "csx_csc_invalidate": [H],
     "csx_set_option": [C.c_char_p, C.c_int],
     "csx_get_option": [C.c_char_p, C.POINTER(C.c_int)],
@@ -304,6 +306,40 @@ def hqr_window():
     a, b = C.c_int32(0), C.c_int32(0)
     check(load().csx_hqr_window(C.byref(a), C.byref(b)), "csx_hqr_window")
     return a.value, b.value
+
+
+SN_GEOMETRY_PLAN = ("chunk", "has_relaxed", "matrix_cores", "leaf_subtrees", "leaf_cols", "leaf_tasks", "leaf_slots",
+                    "fundamental", "relaxed")
+SN_GEOMETRY_DIR = ("steps", "tasks", "max_step_tasks", "cut_lines", "slots", "narrow", "medium", "wide", "one_triangle_steps")
+SN_LAUNCHES = ("outside_wg", "outside", "thin1", "thin2", "thin4", "thin8", "thin16", "thin32", "combine", "mfma_w128",
+               "mfma_leaf_ct1", "mfma_leaf_ct4", "mfma_ct1", "mfma_ct4", "tri16", "tri32", "tri64", "leaf", "use0")
+
+
+def _sn_fields(fn, plan, what):
+    n = C.c_int32(0)
+    check(fn(plan, None, 0, C.byref(n)), what)
+    out = (C.c_int64 * n.value)()
+    check(fn(plan, out, n.value, C.byref(n)), what)
+    return list(out)
+
+
+def cholsol_sn_geometry(plan):
+    """csx_cholsol_sn_geometry as a dict: the plan-wide fields, then "fwd" and "bwd" (include/csx.h has the order)"""
+    v = _sn_fields(lib().csx_cholsol_sn_geometry, plan, "csx_cholsol_sn_geometry")
+    a, b = len(SN_GEOMETRY_PLAN), len(SN_GEOMETRY_DIR)
+    assert len(v) == a + 2 * b
+    g = dict(zip(SN_GEOMETRY_PLAN, v[:a]))
+    g["fwd"] = dict(zip(SN_GEOMETRY_DIR, v[a:a + b]))
+    g["bwd"] = dict(zip(SN_GEOMETRY_DIR, v[a + b:]))
+    return g
+
+
+def cholsol_sn_launches(plan):
+    """csx_cholsol_sn_launches as {"fwd": {kernel: launches}, "bwd": {...}}: what the plan's last solve enqueued"""
+    v = _sn_fields(lib().csx_cholsol_sn_launches, plan, "csx_cholsol_sn_launches")
+    k = len(SN_LAUNCHES)
+    assert len(v) == 2 * k
+    return {"fwd": dict(zip(SN_LAUNCHES, v[:k])), "bwd": dict(zip(SN_LAUNCHES, v[k:]))}
 
 
 def exported_symbols():

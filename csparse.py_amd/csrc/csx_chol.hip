@@ -3011,6 +3011,21 @@ extern "C" int csx_cholsol_sn_info(csx_handle_t h, int32_t *supernodes, int32_t 
     return CSX_OK;
 }
 
+// read-backs of the supernodal schedule for the tests: out[0 .. min(cap, *count)) written, *count = the number of fields
+extern "C" int csx_cholsol_sn_geometry(csx_handle_t h, int64_t *out, int32_t cap, int32_t *count) {
+    CholPlan *P = (CholPlan *)get(h, K_CHOLPLAN);
+    if (!P || !P->sn || !count || cap < 0 || (cap > 0 && !out)) return CSX_EINVAL;
+    *count = sn_geometry(P->sn, out, cap);
+    return CSX_OK;
+}
+
+extern "C" int csx_cholsol_sn_launches(csx_handle_t h, int64_t *out, int32_t cap, int32_t *count) {
+    CholPlan *P = (CholPlan *)get(h, K_CHOLPLAN);
+    if (!P || !P->sn || !count || cap < 0 || (cap > 0 && !out)) return CSX_EINVAL;
+    *count = sn_launches(P->sn, out, cap);
+    return CSX_OK;
+}
+
 // "tri.host_chains" (opt-in): the solve phase of cs_cholsol (csparse.py:640-643) for ONE host right-hand side when L is a chain:
 // x = P b, L \ x, L' \ x, b = P' x with the reference's loops on the host (csx_tri_solve_list's rule, applied to both sweeps)
 extern "C" int csx_cholsol_solve_list(csx_handle_t h, double *b, int *taken) {

@@ -342,6 +342,8 @@ int64_t sn_generation(const SnPlan *P);   // changes whenever sn_prepare moved t
 int sn_prepare(SnPlan *P, int32_t nrhs);   // work space of a solve with nrhs right-hand sides (sn_solve calls it; a capture calls it first)
 void sn_info(const SnPlan *P, int32_t *nsn, int32_t *levels, int32_t *max_w);
 void sn_info2(const SnPlan *P, int32_t *matrix_cores, double *growth);
+int sn_geometry(const SnPlan *P, int64_t *out, int32_t cap);   // fields of csx_cholsol_sn_geometry; returns how many there are
+int sn_launches(const SnPlan *P, int64_t *out, int32_t cap);   // counters of csx_cholsol_sn_launches; returns how many there are
 bool sn_usable(const SnPlan *P);   // with the options in force (a plan with relaxed supernodes needs the matrix-core triangles)
 
 // ---- device primitives (csx_scan.hip, csx_sort.hip) ----

@@ -48,6 +48,19 @@ constexpr int SN_PANEL = 16;
 constexpr int SN_CHUNK = 64;     // columns per chunk of a wide supernode
 constexpr int SN_LEAF = 64;      // columns of a leaf subtree (its x tile: SN_LEAF x 64 doubles of LDS per wave)
 
+// the kernels a sweep can enqueue, in the order csx_cholsol_sn_launches reports them (include/csx.h)
+enum SnLaunch {
+    SNL_OUTSIDE_WG, SNL_OUTSIDE, SNL_THIN1, SNL_THIN2, SNL_THIN4, SNL_THIN8, SNL_THIN16, SNL_THIN32, SNL_COMBINE,
+    SNL_MFMA_W128,        // k_sn_mfma<., false, 1, 8>
+    SNL_MFMA_LEAF_CT1,    // k_sn_mfma<., true, 1, 4>
+    SNL_MFMA_LEAF_CT4,    // k_sn_mfma<., true, 4, 4>
+    SNL_MFMA_CT1,         // k_sn_mfma<., false, 1, 4>
+    SNL_MFMA_CT4,         // k_sn_mfma<., false, 4, 4>
+    SNL_TRI16, SNL_TRI32, SNL_TRI64, SNL_LEAF,
+    SNL_USE0,             // of the k_sn_mfma launches above: those of one triangle whose descriptor went with the launch
+    SNL_COUNT
+};
+
 struct SnTask {
     int32_t line;   // row (forward) or column (backward)
     int32_t b, e;   // term range
@@ -98,6 +111,8 @@ struct SnPlan {
     int chunk = 64;                             // columns per chunk of a wide supernode / per relaxed run (128: matrix cores only)
     bool has_relaxed = false;                   // some supernodes are runs of a chain, not dense trapezoids: matrix cores only
     int64_t generation = 0;                     // counts the moves of `partial` (a captured solve holds its address)
+    int32_t nsn_relaxed = 0;                    // supernodes that are relaxed runs (the others are fundamental)
+    int64_t launches[2][SNL_COUNT] = {};        // kernels the last forward / backward sweep enqueued, by SnLaunch (csx_cholsol_sn_launches)
 };
 
 void destroy(SnPlan *P) { delete P; }
@@ -975,6 +990,8 @@ static int sn_build_with(const Csc *L, const int32_t *parent, const int32_t *Lp_
     P->max_w = max_w;
     P->nleaf = nleaf;
     P->nleafcols = (int32_t)leaf_cols.size();
+    for (int32_t S = 0; S < nsn; S++)
+        if (width[(size_t)S] > 1 && joins[(size_t)first[(size_t)S] + 1] == 2) P->nsn_relaxed++;
     hipStream_t s = ctx().stream;
     {   // is L shaped like a Cholesky factor with these supernodes and subtrees?
         std::vector<int32_t> snc((size_t)n), fl((size_t)n), bl((size_t)n);
@@ -1285,6 +1302,33 @@ void sn_info2(const SnPlan *P, int32_t *matrix_cores, double *growth) {
     if (growth) *growth = P->growth;
 }
 
+// csx_cholsol_sn_geometry: what the build decided, in the order include/csx.h documents; returns the number of fields
+int sn_geometry(const SnPlan *P, int64_t *out, int32_t cap) {
+    std::vector<int64_t> g = {P->chunk, P->has_relaxed ? 1 : 0, P->mfma ? 1 : 0, P->nleaf, P->nleafcols, P->nleaftasks, P->nleafslots,
+                              P->nsn - P->nsn_relaxed, P->nsn_relaxed};
+    for (const SnDir *D : {&P->fwd, &P->bwd}) {
+        int64_t tasks = 0, most = 0, cut = 0, narrow = 0, medium = 0, wide = 0, one = 0;
+        for (const SnStep &t : D->steps) {
+            tasks += t.tc;
+            most = std::max<int64_t>(most, t.tc);
+            cut += t.cc;
+            narrow += t.sc;
+            medium += t.mc;
+            wide += t.bc;
+            one += t.qc == 1;
+        }
+        for (int64_t v : {(int64_t)D->steps.size(), tasks, most, cut, (int64_t)D->nslots, narrow, medium, wide, one}) g.push_back(v);
+    }
+    for (size_t k = 0; k < g.size() && (int32_t)k < cap; k++) out[k] = g[k];
+    return (int)g.size();
+}
+
+// csx_cholsol_sn_launches: SNL_COUNT counters of the last forward sweep, then those of the last backward sweep
+int sn_launches(const SnPlan *P, int64_t *out, int32_t cap) {
+    for (int k = 0; k < 2 * SNL_COUNT && k < cap; k++) out[k] = P->launches[k / SNL_COUNT][k % SNL_COUNT];
+    return 2 * SNL_COUNT;
+}
+
 /* X (n x nrhs, row-major) <- inv(L) X (forward) or inv(L') X.  G*: the forward plan's row-major copy of L (off-diagonal
  * terms of every row in ascending column order, diagonal apart); L: the factor. */
 int64_t sn_generation(const SnPlan *P) { return P->generation; }
@@ -1322,6 +1366,8 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
     const int32_t *idx = forward ? Gi : L->i;
     const double *val = forward ? Gx : L->x;
     const bool cores = P->mfma && ctx().opt.tri_supernodes == 1;
+    int64_t *const launched = P->launches[forward ? 0 : 1];
+    std::fill(launched, launched + SNL_COUNT, (int64_t)0);
     // a launch of many tasks: a wave per (task, 64 right-hand sides), or R lanes per task for up to 32 right-hand sides
     auto many_tasks = [&](const SnTask *tasks, int32_t t0, int32_t tc, const int32_t *ti, const double *tv, bool short_tasks) {
         // (lanes per task pay when the tasks are many and SHORT: a lane walks its task one dependent gather after the other --
@@ -1331,6 +1377,7 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
             int R = 1;
             while (R < nrhs) R *= 2;
             const unsigned grid = (unsigned)(((int64_t)tc * R + 255) / 256);
+            launched[SNL_THIN1 + __builtin_ctz((unsigned)R)]++;      // R = 1 .. 32: SNL_THIN1 .. SNL_THIN32
             switch (R) {
                 case 1: hipLaunchKernelGGL(k_sn_outside_thin<1>, dim3(grid), dim3(256), 0, s, tasks, t0, tc, ti, tv, X, P->partial, nrhs); break;
                 case 2: hipLaunchKernelGGL(k_sn_outside_thin<2>, dim3(grid), dim3(256), 0, s, tasks, t0, tc, ti, tv, X, P->partial, nrhs); break;
@@ -1341,6 +1388,7 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
             }
         } else {
             const int64_t waves = (int64_t)tc * nblk;
+            launched[SNL_OUTSIDE]++;
             hipLaunchKernelGGL(k_sn_outside, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, tasks, t0, tc, ti, tv, X, P->partial, nrhs);
         }
     };
@@ -1354,23 +1402,30 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
         const unsigned grid = (unsigned)((int64_t)count * nblk);
         const int tiles = std::min(4, (nrhs + 15) / 16);
         constexpr size_t lds4 = (size_t)sn_tiles(4) * 256 * sizeof(double), lds8 = (size_t)sn_tiles(8) * 256 * sizeof(double);
+        launched[SNL_USE0] += use0;
         if (!G && P->chunk > 64) {          // triangles of up to 128 columns: eight block rows of X, one column tile per wave
+            launched[SNL_MFMA_W128]++;
             hipLaunchKernelGGL((k_sn_mfma<F, false, 1, 8>), dim3(grid), dim3(64 * tiles), lds8, s, list, first, ent0, use0, rows, P->frags,
                                P->frag_toff, X, nrhs);
         } else if ((int64_t)count * nblk <= 512) {
+            launched[G ? SNL_MFMA_LEAF_CT1 : SNL_MFMA_CT1]++;
             hipLaunchKernelGGL((k_sn_mfma<F, G, 1, 4>), dim3(grid), dim3(64 * tiles), lds4, s, list, first, ent0, use0, rows, P->frags, P->frag_toff,
                                X, nrhs);
         } else {
+            launched[G ? SNL_MFMA_LEAF_CT4 : SNL_MFMA_CT4]++;
             hipLaunchKernelGGL((k_sn_mfma<F, G, 4, 4>), dim3(grid), dim3(64), lds4, s, list, first, ent0, use0, rows, P->frags, P->frag_toff, X, nrhs);
         }
     };
     if (forward && P->nleaf && cores)
         triangles(std::true_type{}, std::true_type{}, P->leaf4, nullptr, 0, P->nleaf, P->leaf_cols);
-    else if (forward && P->nleaf)
+    else if (forward && P->nleaf) {
+        launched[SNL_LEAF]++;
         hipLaunchKernelGGL(k_sn_leaf<true>, dim3((unsigned)(P->nleaf * nblk)), dim3(64), 0, s, P->leaf_ptr, P->leaf_cols, P->lf_ptr,
                            P->lf_idx, P->lf_val, P->ldiag, (const int32_t *)nullptr, (const double *)nullptr, X, nrhs);
+    }
     for (const SnStep &t : D.steps) {
         if (t.tc > 0 && t.tc <= 16384) {      // (by the step's size alone: the same sums for any number of right-hand sides)
+            launched[SNL_OUTSIDE_WG]++;
             hipLaunchKernelGGL(k_sn_outside_wg, dim3((unsigned)((int64_t)t.tc * nblk)), dim3(256), 0, s, D.tasks, t.t0, t.tc, idx, val, X,
                                P->partial, nrhs);
         } else if (t.tc > 0) {
@@ -1378,6 +1433,7 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
         }
         if (t.cc > 0) {
             const int64_t waves = (int64_t)t.cc * nblk;
+            launched[SNL_COMBINE]++;
             hipLaunchKernelGGL(k_sn_combine, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, D.comb, t.c0, t.cc, D.part_ptr, 0,
                                P->partial, X, nrhs);
         }
@@ -1387,25 +1443,37 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
                 else triangles(std::false_type{}, std::false_type{}, D.tri4, &D.tri_h, t.q0, t.qc, nullptr);
             }
         } else if (forward) {
-            if (t.sc > 0)
+            if (t.sc > 0) {
+                launched[SNL_TRI16]++;
                 hipLaunchKernelGGL((k_sn_tri<1, SN_PANEL, true>), dim3((unsigned)(t.sc * nblk)), dim3(64), sn_tri_lds<SN_PANEL>(), s, D.narrow,
                                    t.s0, P->vs_a, P->vs_w, Gp, Gx, Gd, (const int32_t *)nullptr, P->partial, X, nrhs);
-            if (t.mc > 0)
+            }
+            if (t.mc > 0) {
+                launched[SNL_TRI32]++;
                 hipLaunchKernelGGL((k_sn_tri<2, 32, true>), dim3((unsigned)(t.mc * nblk)), dim3(128), sn_tri_lds<32>(), s, D.medium, t.m0,
                                    P->vs_a, P->vs_w, Gp, Gx, Gd, (const int32_t *)nullptr, P->partial, X, nrhs);
-            if (t.bc > 0)
+            }
+            if (t.bc > 0) {
+                launched[SNL_TRI64]++;
                 hipLaunchKernelGGL((k_sn_tri<4, SN_CHUNK, true>), dim3((unsigned)(t.bc * nblk)), dim3(256), sn_tri_lds<SN_CHUNK>(), s, D.wide,
                                    t.b0, P->vs_a, P->vs_w, Gp, Gx, Gd, (const int32_t *)nullptr, P->partial, X, nrhs);
+            }
         } else {
-            if (t.sc > 0)
+            if (t.sc > 0) {
+                launched[SNL_TRI16]++;
                 hipLaunchKernelGGL((k_sn_tri<1, SN_PANEL, false>), dim3((unsigned)(t.sc * nblk)), dim3(64), sn_tri_lds<SN_PANEL>(), s, D.narrow,
                                    t.s0, P->vs_a, P->vs_w, L->p, L->x, (const double *)nullptr, (const int32_t *)nullptr, P->partial, X, nrhs);
-            if (t.mc > 0)
+            }
+            if (t.mc > 0) {
+                launched[SNL_TRI32]++;
                 hipLaunchKernelGGL((k_sn_tri<2, 32, false>), dim3((unsigned)(t.mc * nblk)), dim3(128), sn_tri_lds<32>(), s, D.medium, t.m0,
                                    P->vs_a, P->vs_w, L->p, L->x, (const double *)nullptr, (const int32_t *)nullptr, P->partial, X, nrhs);
-            if (t.bc > 0)
+            }
+            if (t.bc > 0) {
+                launched[SNL_TRI64]++;
                 hipLaunchKernelGGL((k_sn_tri<4, SN_CHUNK, false>), dim3((unsigned)(t.bc * nblk)), dim3(256), sn_tri_lds<SN_CHUNK>(), s, D.wide,
                                    t.b0, P->vs_a, P->vs_w, L->p, L->x, (const double *)nullptr, (const int32_t *)nullptr, P->partial, X, nrhs);
+            }
         }
     }
     if (!forward && P->nleaf) {
@@ -1413,14 +1481,17 @@ int sn_solve(SnPlan *P, bool forward, const int32_t *Gp, const int32_t *Gi, cons
         if (waves > 0) many_tasks(P->leaf_tasks, 0, P->nleaftasks, L->i, L->x, true);   // a leaf column's few rows above its subtree
         if (P->nleafslots > 0) {                                // the leaf columns that were cut into pieces
             const int64_t cw = (int64_t)P->nleafcols * nblk;
+            launched[SNL_COMBINE]++;
             hipLaunchKernelGGL(k_sn_combine, dim3((unsigned)((cw + 3) / 4)), dim3(256), 0, s, P->leaf_cols, 0, P->nleafcols, P->lslot_ptr, 1,
                                P->partial + (int64_t)P->bwd.nslots * nrhs, X, nrhs);
         }
         if (cores)
             triangles(std::false_type{}, std::true_type{}, P->leaf4, nullptr, 0, P->nleaf, P->leaf_cols);
-        else
+        else {
+            launched[SNL_LEAF]++;
             hipLaunchKernelGGL(k_sn_leaf<false>, dim3((unsigned)(P->nleaf * nblk)), dim3(64), 0, s, P->leaf_ptr, P->leaf_cols, P->lb_ptr,
                                P->lb_idx, P->lb_val, P->ldiag, (const int32_t *)nullptr, (const double *)nullptr, X, nrhs);
+        }
     }
     CSX_LAUNCH_CHECK();
     return CSX_OK;

@@ -388,6 +388,24 @@ int csx_cholsol_growth(csx_handle_t plan, double *growth);
  * may be NULL. */
 int csx_cholsol_sn_info(csx_handle_t plan, int32_t *supernodes, int32_t *steps, int32_t *max_width, int32_t *matrix_cores,
                         double *growth);
+/* Read-backs of the supernodal schedule for tests that must show which edge of it an input reached.  Both write
+ * out[0 .. min(cap, *count)) and set *count to the number of fields; EINVAL when the plan holds no supernodal schedule.
+ * csx_cholsol_sn_geometry, what the build decided (27 fields):
+ *   0 columns per chunk (128 or 64), 1 whether some supernodes are relaxed runs, 2 whether the fragments for the matrix
+ *   cores were built and passed the guard, 3 leaf subtrees, 4 leaf columns, 5 leaf tasks (pieces of the leaf columns' rows
+ *   outside their subtrees), 6 leaf partial slots, 7 fundamental supernodes, 8 relaxed supernodes;
+ *   then for the forward sweep (9 - 17) and for the backward sweep (18 - 26): steps, tasks of all steps, tasks of the
+ *   largest step, lines cut into pieces, partial slots, chunks of at most 16 columns, of 17 to 32, of more, steps of
+ *   exactly one triangle.
+ * csx_cholsol_sn_launches, the kernels the plan's last forward sweep enqueued (fields 0 - 18) and its last backward sweep
+ * (19 - 37); a replayed graph enqueues none, so count under "tri.graph" = 0:
+ *   0 k_sn_outside_wg, 1 k_sn_outside, 2 - 7 k_sn_outside_thin<1 | 2 | 4 | 8 | 16 | 32>, 8 k_sn_combine,
+ *   9 k_sn_mfma<., false, 1, 8> (chunks of 128), 10 k_sn_mfma<., true, 1, 4> and 11 k_sn_mfma<., true, 4, 4> (leaf subtrees),
+ *   12 k_sn_mfma<., false, 1, 4> and 13 k_sn_mfma<., false, 4, 4> (chunks of 64), 14 k_sn_tri<1, 16, .>, 15 k_sn_tri<2, 32, .>,
+ *   16 k_sn_tri<4, 64, .>, 17 k_sn_leaf, 18 of the k_sn_mfma launches: those of one triangle whose descriptor went with
+ *   the launch. */
+int csx_cholsol_sn_geometry(csx_handle_t plan, int64_t *out, int32_t cap, int32_t *count);
+int csx_cholsol_sn_launches(csx_handle_t plan, int64_t *out, int32_t cap, int32_t *count);
 
 /* "tri.graph": how many times this plan's supernodal solve has been captured into a hipGraph so far, and the host time of the
  * last capture + instantiate in ms (the option's default, 2, captures on the third consecutive solve of one block).  Either

@@ -678,7 +678,10 @@ def test_supernodal_solves_in_the_rounding_equal_order(cs, case):
     SUPERNODE (csx_snsolve.hip: outside terms by a wave per piece of a row, the dense triangle in panels of 16) instead
     of by column.  Against the plain-C oracle's cs_lsolve + cs_ltsolve on the same L at 1e-10 (BASELINE's tolerance),
     for 1, 3, 64 and 70 right-hand sides (a partial second chunk); the exact order of the same factor stays bit-identical;
-    the same bits from run to run (partial sums are added in a fixed order); switched off -> the level-scheduled path."""
+    the same bits from run to run (partial sums are added in a fixed order); switched off -> the level-scheduled path.
+    These are matrices as they come: which kernels and cuts of the schedule they reach is not asserted here.
+    tests/test_gpu_snsolve.py runs a synthetic factor for every edge of the schedule (tests/sn_cases.py) and reads back
+    what the plan decided and what each solve launched."""
     import _csx
     # "@natural": order 0 -- the factor of a banded matrix is ONE chain of the elimination tree in which no two columns share
     # their rows: the schedule is made of RELAXED supernodes (runs of 64 columns of the chain, their triangles made dense

@@ -15,10 +15,19 @@ import scipy.sparse.linalg as spla
 
 EPS = 2.0 ** -52
 X_RTOL = 1e-10           # BASELINE.json north_star
+# The supernodal solve against the oracle on the synthetic factors of tests/sn_cases.py, as the largest
+# |x_i - ref_i| / (EPS * terms_i) with cholsolve_terms' terms: 8 x the largest value measured on an MI355X over the cases
+# on the near side of the growth guard (4423.03, case bwd513; profiles/snsolve_edges.jsonl has every case).  The results
+# are the same bits on every run, so the factor of 8 covers other seeds and a legitimate regrouping of the sums, not noise.
+SN_EPS_UNITS = 8 * 4423.03
 
 
 def componentwise(v, ref, terms=None):
-    """SURVEY 8d's measure; terms[i] = sum of the magnitudes of the terms ref[i] was formed from (None: |ref| alone)."""
+    """SURVEY 8d's measure; terms[i] = sum of the magnitudes of the terms ref[i] was formed from (None: |ref| alone).
+    Its limit: a component that cancelled to, say, 1e-8 of its terms is still held to 1e-10 of ITSELF (the floor is one
+    rounding of the terms, eps * terms), which is a hundredth of a rounding of those terms -- less than any order of
+    summation, the reference's included, can keep.  Among a few thousand components that does not occur; among 250 000
+    of a solution to a random right-hand side it does (tests/test_gpu_snsolve.py, manufactured_rhs)."""
     v, ref = np.asarray(v, float), np.asarray(ref, float)
     scale = np.abs(ref) if terms is None else np.maximum(np.abs(ref), EPS * np.asarray(terms, float))
     scale = np.where(scale > 0.0, scale, 1.0)
