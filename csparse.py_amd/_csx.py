@@ -213,6 +213,7 @@ _PROTOS = {
     "csx_hqr_info": [H, C.POINTER(C.c_int64)],
     "csx_hqr_stats": [H, _f64p],
     "csx_hqr_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "csx_level_schedule": [C.c_int32, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64, _i32p, C.POINTER(C.c_int32)],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -286,7 +287,7 @@ def load():
 
 
 def ldl_window():
-    """entries of a column that the LDL' column kernels keep in LDS (csx_ldl.hip LDL_ACC), asked of the library; no GPU needed"""
+    """entries of a column that the LDL' column kernels keep in LDS (csx_ldl.h LDL_ACC), asked of the library; no GPU needed"""
     out = C.c_int32(0)
     check(load().csx_ldl_window(C.byref(out)), "csx_ldl_window")
     return out.value
@@ -294,7 +295,7 @@ def ldl_window():
 
 def slu_window():
     """(entries of a column that the static-pivot LU column kernels keep in LDS, levels one launch of its walker takes)
-    (csx_slu.hip SLU_ACC, SLU_RUN_LEVELS), asked of the library; no GPU needed"""
+    (csx_slu.hip SLU_ACC, csx_levelwalk.h WALK_RUN_LEVELS), asked of the library; no GPU needed"""
     a, b = C.c_int32(0), C.c_int32(0)
     check(load().csx_slu_window(C.byref(a), C.byref(b)), "csx_slu_window")
     return a.value, b.value
@@ -302,10 +303,22 @@ def slu_window():
 
 def hqr_window():
     """(slots of a column that the Householder QR column kernels keep in LDS, levels one launch of its walker takes)
-    (csx_hqr.hip HQR_ACC, HQR_RUN_LEVELS), asked of the library; no GPU needed"""
+    (csx_hqr.hip HQR_ACC, csx_levelwalk.h WALK_RUN_LEVELS), asked of the library; no GPU needed"""
     a, b = C.c_int32(0), C.c_int32(0)
     check(load().csx_hqr_window(C.byref(a), C.byref(b)), "csx_hqr_window")
     return a.value, b.value
+
+
+def level_schedule(level_ptr, waves, run_levels, work=None, run_work=0):
+    """the launches [(wide, first level, end level)] of the level walk of ldlsol / schur / slusol / hqrsol_factor over the levels
+    level_ptr (csx_level_schedule; csx_levelwalk.h); work: a figure per level, or none; no GPU needed"""
+    lp = i32(level_ptr)
+    nlev = len(lp) - 1
+    out, count = np.zeros(3 * max(nlev, 1), np.int32), C.c_int32(0)
+    w = None if work is None else np.ascontiguousarray(work, np.int64)
+    check(load().csx_level_schedule(nlev, pi(lp), waves, run_levels, None if w is None else w.ctypes.data_as(C.POINTER(C.c_int64)),
+                                    run_work, pi(out), C.byref(count)), "csx_level_schedule")
+    return [(bool(out[3 * t]), int(out[3 * t + 1]), int(out[3 * t + 2])) for t in range(count.value)]
 
 
 SN_GEOMETRY_PLAN = ("chunk", "has_relaxed", "matrix_cores", "leaf_subtrees", "leaf_cols", "leaf_tasks", "leaf_slots",

@@ -2016,6 +2016,20 @@ def _in_order(plans, in_exact_order, sweeps):
             lib.csx_tri_set_order(plan, 1)
 
 
+def _factor_info(hF, info_call, names, stats_call, stat_names, **more):
+    """info() of ldlsol / schur / slusol / hqrsol_factor: the integers `names` of info_call, then the doubles stat_names of
+    stats_call (both in the library's order), then `more`"""
+    lib = _csx.lib()
+    raw = (_csx.C.c_int64 * len(names))()
+    st = (_csx.C.c_double * len(stat_names))()
+    _csx.check(getattr(lib, info_call)(hF, raw), info_call)
+    _csx.check(getattr(lib, stats_call)(hF, st), stats_call)
+    out = {name: int(v) for name, v in zip(names, raw)}
+    out.update(zip(stat_names, st))
+    out.update(more)
+    return out
+
+
 class _LdlSolver(object):
     """What the solvers of ldlsol_factor and schur_factor share: both stand on one partial LDL' in the library (DESIGN.md §22, §25:
     the LDL' factor is the partial one with nothing kept).  The solver calls _ldl_init and names its entry points: _INFO, the
@@ -2049,14 +2063,7 @@ class _LdlSolver(object):
         return ok.value == 1
 
     def info(self):
-        lib = _csx.lib()
-        raw = (_csx.C.c_int64 * len(self._INFO))()
-        st = (_csx.C.c_double * 3)()
-        _csx.check(getattr(lib, self._CALLS[1])(self._hF, raw), self._CALLS[1])
-        _csx.check(getattr(lib, self._CALLS[2])(self._hF, st), self._CALLS[2])
-        out = {name: int(v) for name, v in zip(self._INFO, raw)}
-        out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2])
-        return out
+        return _factor_info(self._hF, self._CALLS[1], self._INFO, self._CALLS[2], ("min_abs_d", "max_abs_d", "max_abs_l"))
 
     def inertia(self):
         """(positive, negative) pivots of the committed factor (of A11 for a partial one)"""
@@ -3003,13 +3010,8 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
             return _condest(self._norm, lambda v, t: self._block(dvec(v), True, t).numpy(), n)
 
         def info(self):
-            raw = (_csx.C.c_int64 * len(_SLU_INFO))()
-            st = (_csx.C.c_double * 4)()
-            _csx.check(lib.csx_slu_info(hF, raw), "csx_slu_info")
-            _csx.check(lib.csx_slu_stats(hF, st), "csx_slu_stats")
-            out = {name: int(v) for name, v in zip(_SLU_INFO, raw)}
-            out.update(min_abs_d=st[0], max_abs_d=st[1], max_abs_l=st[2], max_abs_u=st[3], matched=prow is not None)
-            return out
+            return _factor_info(hF, "csx_slu_info", _SLU_INFO, "csx_slu_stats", ("min_abs_d", "max_abs_d", "max_abs_l", "max_abs_u"),
+                                matched=prow is not None)
 
         def logdet(self):
             """(sign, log |det A|): det A = det(prow) * the product of the pivots (the symmetric permutation cancels); the sum
@@ -3501,13 +3503,7 @@ def hqrsol_factor(A, order=0):
                 return math.fsum(np.log(np.abs(x[Rp[1:] - 1])).tolist())
 
         def info(self):
-            raw = (_csx.C.c_int64 * len(_HQR_INFO))()
-            st = (_csx.C.c_double * 2)()
-            _csx.check(lib.csx_hqr_info(hF, raw), "csx_hqr_info")
-            _csx.check(lib.csx_hqr_stats(hF, st), "csx_hqr_stats")
-            out = {name: int(v) for name, v in zip(_HQR_INFO, raw)}
-            out.update(min_abs_r=st[0], max_abs_r=st[1], transposed=not tall)
-            return out
+            return _factor_info(hF, "csx_hqr_info", _HQR_INFO, "csx_hqr_stats", ("min_abs_r", "max_abs_r"), transposed=not tall)
 
     return _Solver()
 

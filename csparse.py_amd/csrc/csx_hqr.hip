@@ -2,8 +2,8 @@
 // include/csx.h).  Householder QR searches for no pivot: the patterns of V and R follow from cs_sqr's analysis and the column
 // elimination tree before a value is read (csx_hqr_symbolic_host), and column k reads only V(:,c) and beta[c] of its descendants
 // c.  So the columns of one height level of the tree are independent, as in csx_ldl.hip and csx_slu.hip.
-//   k_hqr_level   one wave per column of a height level
-//   k_hqr_run     one workgroup walks at most HQR_RUN_LEVELS levels of at most HQR_WAVES columns each, a barrier per level
+//   hqr_column    one wave's column, behind the policy HqrColumn of the level walk (csx_levelwalk.h: k_level, k_run, the
+//                 schedule with the walker cut at WALK_RUN_LEVELS levels or HQR_RUN_WORK slot updates a launch)
 //   k_hqr_stats   min / max |r_kk| and the number of exact zeros on R's diagonal
 // Every row a reflection of column k touches is a slot of R(:,k) or of V(:,k): the column's own slots are its accumulators, in
 // wave-private LDS up to HQR_ACC slots and in place in the scratch arrays beyond.  A reflection's dot product is 64 strided
@@ -14,18 +14,15 @@
 #include <cstring>
 
 #include "csx_internal.h"
-#include "csx_ldl.h"
+#include "csx_levelwalk.h"
 
 #pragma clang fp contract(off)
 
 namespace csx {
 
-constexpr int HQR_ACC = 512;          // slots of a column kept in LDS per wave (8 + 4 + 4 bytes each: 32 KB a workgroup); a longer column is updated in place
-constexpr int HQR_WAVES = 4;          // waves per workgroup
-constexpr int HQR_RUN_LEVELS = 256;   // levels one launch of the walker takes (csx_slu.hip's constant): a longer run is several launches
-constexpr int64_t HQR_RUN_WORK = 1 << 24;   // ... and at most this many slot updates (its levels' longest columns summed), so that no
-                                            // launch of one workgroup holds the device for long
-constexpr int HQR_NONE = 0x7fffffff;
+constexpr int HQR_ACC = 512;   // slots of a column kept in LDS per wave (8 + 4 + 4 bytes each: 32 KB a workgroup); a longer column is updated in place
+constexpr int64_t HQR_RUN_WORK = 1 << 24;   // slot updates one launch of the walker takes at most (its levels' longest columns
+                                            // summed), so that no launch of one workgroup holds the device for long
 
 // what one lane wrote, every lane of the wave may read
 __device__ __forceinline__ void hqr_wave_sync() {
@@ -152,43 +149,20 @@ __device__ __forceinline__ void hqr_column(int32_t k, const int32_t *__restrict_
     hqr_wave_sync();
 }
 
-#define HQR_SHARED                                 \
-    __shared__ double s_acc[HQR_WAVES][HQR_ACC];   \
-    __shared__ int32_t s_row[HQR_WAVES][HQR_ACC];  \
-    __shared__ int32_t s_dst[HQR_WAVES][HQR_ACC];
-
-// one wave per column of a level
-__global__ __launch_bounds__(64 * HQR_WAVES) void k_hqr_level(const int32_t *__restrict__ cols, int32_t count,
-                                                             const int32_t *__restrict__ Vp, const int32_t *__restrict__ Vi,
-                                                             double *Vx, const int32_t *__restrict__ Rp,
-                                                             const int32_t *__restrict__ Ri, double *Rx, double *beta,
-                                                             const int32_t *__restrict__ Sp, const int32_t *__restrict__ Srow,
-                                                             const int32_t *__restrict__ Sdst, int *flags) {
-    HQR_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t c = (int64_t)blockIdx.x * HQR_WAVES + w;
-    if (c >= count) return;
-    hqr_column(cols[c], Vp, Vi, Vx, Rp, Ri, Rx, beta, Sp, Srow, Sdst, s_acc[w], s_row[w], s_dst[w], lane, flags);
-}
-
-// One workgroup walks the levels [l0, l1), l1 - l0 <= HQR_RUN_LEVELS, each of at most HQR_WAVES columns: wave w takes column w of
-// the level, a barrier between levels makes the finished columns visible to the next.  The trip counts are the level pointers,
-// the same for every wave, so every wave reaches every barrier.
-__global__ __launch_bounds__(64 * HQR_WAVES) void k_hqr_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
-                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Vp,
-                                                           const int32_t *__restrict__ Vi, double *Vx,
-                                                           const int32_t *__restrict__ Rp, const int32_t *__restrict__ Ri,
-                                                           double *Rx, double *beta, const int32_t *__restrict__ Sp,
-                                                           const int32_t *__restrict__ Srow, const int32_t *__restrict__ Sdst,
-                                                           int *flags) {
-    HQR_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int32_t l = l0; l < l1; l++) {
-        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
-        if (w < cnt) hqr_column(cols[b + w], Vp, Vi, Vx, Rp, Ri, Rx, beta, Sp, Srow, Sdst, s_acc[w], s_row[w], s_dst[w], lane, flags);
-        __syncthreads();
+// the level walk's policy (csx_levelwalk.h): hqr_column behind k_level / k_run, with the kernels' argument types and LDS arrays
+struct HqrColumn {
+    using Args = ColumnArgs<const int32_t *__restrict__, const int32_t *__restrict__, double *, const int32_t *__restrict__,
+                            const int32_t *__restrict__, double *, double *, const int32_t *__restrict__, const int32_t *__restrict__,
+                            const int32_t *__restrict__, int *>;
+    static __device__ __forceinline__ void column(int32_t k, int w, int lane, const int32_t *Vp, const int32_t *Vi, double *Vx,
+                                                  const int32_t *Rp, const int32_t *Ri, double *Rx, double *beta, const int32_t *Sp,
+                                                  const int32_t *Srow, const int32_t *Sdst, int *flags) {
+        __shared__ double acc[WALK_WAVES][HQR_ACC];
+        __shared__ int32_t row[WALK_WAVES][HQR_ACC];
+        __shared__ int32_t dst[WALK_WAVES][HQR_ACC];
+        hqr_column(k, Vp, Vi, Vx, Rp, Ri, Rx, beta, Sp, Srow, Sdst, acc[w], row[w], dst[w], lane, flags);
     }
-}
+};
 
 // One lane per column: st[0] min |r_kk|, st[1] max |r_kk| -- extrema of the bit patterns of fabs taken as unsigned integers
 // (k_ldl_stats' rule) -- st[2] the number of exact zeros (integer adds); a wave reduces before its lane 0 touches st
@@ -215,36 +189,20 @@ __global__ __launch_bounds__(256) void k_hqr_stats(int32_t n, const int32_t *__r
     }
 }
 
-struct HqrLaunch {
-    bool wide;         // k_hqr_level on level l0, or k_hqr_run over the levels [l0, l1)
-    int32_t l0, l1;
-};
-
-struct HqrFactor {
-    int32_t m = 0, n = 0, m2 = 0, anz = 0, vnz = 0, rnz = 0;
-    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
+struct HqrFactor : LevelFactor {            // (the levels are those of the column elimination tree)
+    int32_t m2 = 0, vnz = 0, rnz = 0;
     DevBuf<int32_t> sp, srow, sdst;         // per column the rows of its slots ascending, and the natural slot of each
     DevBuf<int32_t> winV, winR;             // entry maps: the entry of A that lands in a slot of V / of R (-1: none)
-    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the column elimination tree
-    std::vector<int32_t> level_ptr_h;
-    std::vector<HqrLaunch> schedule;        // the launches of a run, in order
     csx_handle_t hV = 0, hR = 0, hB = 0;    // the committed factor: owned here, lent out by csx_hqr_parts
     DevBuf<double> beta;                    // the committed beta (hB's vector borrows it)
     DevBuf<double> Vx, Rx, bx;              // scratch of a run: committed only when no column broke down
-    DevBuf<int> flags;                      // [0] smallest broken column, [1] columns updated in place
-    DevBuf<unsigned long long> stats;       // k_hqr_stats
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0, zeros = 0, breakdown = -1, kernel_us = 0;
+    // flags: [1] columns updated in place; stats: k_hqr_stats' three words
+    int64_t zeros = 0;
     double min_r = 0.0, max_r = 0.0;
-    HqrFactor() = default;
-    HqrFactor(const HqrFactor &) = delete;
-    HqrFactor &operator=(const HqrFactor &) = delete;
     ~HqrFactor() {
         if (hB) (void)csx_free(hB);
         if (hR) (void)csx_free(hR);
         if (hV) (void)csx_free(hV);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
     }
 };
 
@@ -257,48 +215,19 @@ static int hqr_run(HqrFactor *F, const double *Ax, int *ok) {
     Csc *V = csc(F->hV), *R = csc(F->hR);
     if (!V || !R || !V->x || !R->x || V->nnz != F->vnz || R->nnz != F->rnz) return CSX_EINVAL;
     const int32_t n = F->n;
-    F->launches = F->level_launches = F->run_launches = 0;
-    const int hinit[2] = {HQR_NONE, 0};
+    const int hinit[2] = {WALK_NONE, 0};
     const unsigned long long sinit[3] = {~0ull, 0ull, 0ull};
-    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(walk_begin(F, hinit, 2, sinit, 3));
     CSX_TRY(chol_scatter(F->vnz, F->winV, Ax, F->Vx));
     CSX_TRY(chol_scatter(F->rnz, F->winR, Ax, F->Rx));
-    const std::vector<int32_t> &lp = F->level_ptr_h;
-    for (const HqrLaunch &L : F->schedule) {
-        if (L.wide) {
-            const int32_t cnt = lp[(size_t)L.l0 + 1] - lp[(size_t)L.l0];
-            hipLaunchKernelGGL(k_hqr_level, dim3((unsigned)((cnt + HQR_WAVES - 1) / HQR_WAVES)), dim3(64 * HQR_WAVES), 0, s,
-                               F->level_cols + lp[(size_t)L.l0], cnt, V->p, V->i, F->Vx.get(), R->p, R->i, F->Rx.get(), F->bx.get(),
-                               F->sp.get(), F->srow.get(), F->sdst.get(), F->flags.get());
-            F->level_launches++;
-        } else {
-            hipLaunchKernelGGL(k_hqr_run, dim3(1), dim3(64 * HQR_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), L.l0, L.l1,
-                               V->p, V->i, F->Vx.get(), R->p, R->i, F->Rx.get(), F->bx.get(), F->sp.get(), F->srow.get(),
-                               F->sdst.get(), F->flags.get());
-            F->run_launches++;
-        }
-    }
-    F->launches = F->level_launches + F->run_launches;
+    walk_levels<HqrColumn>(F, HqrColumn::Args(), V->p, V->i, F->Vx, R->p, R->i, F->Rx, F->bx, F->sp, F->srow, F->sdst, F->flags);
     if (n > 0)
         hipLaunchKernelGGL(k_hqr_stats, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, R->p, F->Rx.get(),
                            F->stats.get());
-    (void)hipEventRecord(F->ev_b, s);
-    int hflags[2] = {HQR_NONE, 0};
+    int hflags[2] = {WALK_NONE, 0};
     unsigned long long hst[3] = {0, 0, 0};
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("csx_hqr: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipStreamSynchronize(s);
-        return CSX_ERUNTIME;
-    }
-    float ms = 0.0f;
-    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    CSX_TRY(walk_end(F, hflags, 2, hst, 3, ok));
     F->long_cols = hflags[1];
-    F->breakdown = hflags[0] == HQR_NONE ? -1 : hflags[0];
-    *ok = F->breakdown < 0 ? 1 : 0;
     if (!*ok) return CSX_OK;
     if (n == 0) hst[0] = 0;
     std::memcpy(&F->min_r, &hst[0], 8);
@@ -319,10 +248,7 @@ static int hqr_build(Csc *A, const int32_t *q, const int32_t *parent, const int3
                      HqrFactor *F) {
     hipStream_t s = ctx().stream;
     const int32_t m = A->m, n = A->n;
-    F->m = m;
-    F->n = n;
     F->m2 = m2;
-    F->anz = A->nnz;
     if (!A->trusted) CSX_TRY(csc_validate(A));
     std::vector<int32_t> ap, ai, vp, vi, rp, ri;
     CSX_TRY(download_i32(ap, A->p, (size_t)n + 1));
@@ -359,49 +285,22 @@ static int hqr_build(Csc *A, const int32_t *q, const int32_t *parent, const int3
         }
     }
     sp[(size_t)n] = F->rnz - n + F->vnz;
-    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
-    CSX_TRY(F->flags.alloc(2));
-    CSX_TRY(F->stats.alloc(3));
-    CSX_HIP(hipEventCreate(&F->ev_a));
-    CSX_HIP(hipEventCreate(&F->ev_b));
+    CSX_TRY(walk_init(F, A, "csx_hqr", 2, 3));
     std::vector<int32_t> cols;
-    if (n > 0) ldl_levels(n, parent, F->level_ptr_h, cols);
-    else F->level_ptr_h.assign(1, 0);
-    {
-        // the launches: a level of more than HQR_WAVES columns is one launch of a wave per column; a run of narrower levels is
-        // walked by one workgroup, cut after HQR_RUN_LEVELS levels or HQR_RUN_WORK slot updates
-        const std::vector<int32_t> &lp = F->level_ptr_h;
-        const int32_t nlev = (int32_t)lp.size() - 1;
-        auto level_work = [&](int32_t l) {
-            int64_t most = 0;
-            for (int32_t t = lp[(size_t)l]; t < lp[(size_t)l + 1]; t++) {
-                const int32_t k = cols[(size_t)t];
-                int64_t w = 0;
-                for (int32_t u = rp[(size_t)k]; u < rp[(size_t)k + 1] - 1; u++) w += vp[(size_t)ri[(size_t)u] + 1] - vp[(size_t)ri[(size_t)u]];
-                most = std::max(most, w);
-            }
-            return most;
-        };
-        for (int32_t l = 0; l < nlev;) {
-            if (lp[(size_t)l + 1] - lp[(size_t)l] > HQR_WAVES) {
-                F->schedule.push_back({true, l, l + 1});
-                l++;
-                continue;
-            }
-            int32_t e = l;
-            int64_t work = 0;
-            while (e < nlev && e - l < HQR_RUN_LEVELS && lp[(size_t)e + 1] - lp[(size_t)e] <= HQR_WAVES) {
-                const int64_t w = level_work(e);
-                if (e > l && work + w > HQR_RUN_WORK) break;
-                work += w;
-                e++;
-            }
-            F->schedule.push_back({false, l, e});
-            l = e;
+    height_levels(n, parent, F->level_ptr_h, cols);
+    // the work of a level the walker may take: the slot updates of its longest column, every reflection's entries summed
+    std::vector<int64_t> work((size_t)F->levels(), 0);
+    for (int32_t l = 0; l < F->levels(); l++) {
+        const int32_t b = F->level_ptr_h[(size_t)l], e = F->level_ptr_h[(size_t)l + 1];
+        if (e - b > WALK_WAVES) continue;   // (a wide level: a launch of its own whatever it costs)
+        for (int32_t t = b; t < e; t++) {
+            const int32_t k = cols[(size_t)t];
+            int64_t w = 0;
+            for (int32_t u = rp[(size_t)k]; u < rp[(size_t)k + 1] - 1; u++) w += vp[(size_t)ri[(size_t)u] + 1] - vp[(size_t)ri[(size_t)u]];
+            work[(size_t)l] = std::max(work[(size_t)l], w);
         }
     }
-    CSX_TRY(upload(F->level_cols, cols));
-    CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+    CSX_TRY(walk_set_levels(F, cols, WALK_RUN_LEVELS, work.data(), HQR_RUN_WORK));
     CSX_TRY(upload(F->sp, sp));
     CSX_TRY(upload(F->srow, srow));
     CSX_TRY(upload(F->sdst, sdst));
@@ -455,14 +354,7 @@ extern "C" int csx_hqr_refactor(csx_handle_t h, csx_handle_t hA2, int *ok) {
     CSX_TRY(require_ready());
     HqrFactor *F = (HqrFactor *)get(h, K_HQRFACTOR);
     if (!F || !ok) return CSX_EINVAL;
-    *ok = -1;
-    const double *x2 = nullptr;
-    CSX_TRY(rf_values(hA2, F->m, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
-    if (!x2) {
-        set_error("csx_hqr_refactor: A2 does not have the pattern (or the length) of the factored matrix");
-        return CSX_EINVAL;   // nothing changes
-    }
-    return hqr_run(F, x2, ok);
+    return walk_refactor(F, hA2, ok, [&](const double *x2) { return hqr_run(F, x2, ok); });
 }
 
 extern "C" int csx_hqr_parts(csx_handle_t h, csx_handle_t *V, csx_handle_t *R, csx_handle_t *beta) {
@@ -484,8 +376,8 @@ extern "C" int csx_hqr_info(csx_handle_t h, int64_t *info) {
     info[2] = F->m2;
     info[3] = F->vnz;
     info[4] = F->rnz;
-    info[5] = (int64_t)F->level_ptr_h.size() - 1;
-    info[6] = F->launches;
+    info[5] = F->levels();
+    info[6] = F->launches();
     info[7] = F->level_launches;
     info[8] = F->run_launches;
     info[9] = F->long_cols;
@@ -493,7 +385,7 @@ extern "C" int csx_hqr_info(csx_handle_t h, int64_t *info) {
     info[11] = F->breakdown;
     info[12] = F->kernel_us;
     info[13] = HQR_ACC;
-    info[14] = HQR_RUN_LEVELS;
+    info[14] = WALK_RUN_LEVELS;
     return CSX_OK;
 }
 
@@ -509,6 +401,6 @@ extern "C" int csx_hqr_stats(csx_handle_t h, double *out) {
 extern "C" int csx_hqr_window(int32_t *entries, int32_t *run_levels) {   // (no device needed)
     if (!entries || !run_levels) return CSX_EINVAL;
     *entries = HQR_ACC;
-    *run_levels = HQR_RUN_LEVELS;
+    *run_levels = WALK_RUN_LEVELS;
     return CSX_OK;
 }

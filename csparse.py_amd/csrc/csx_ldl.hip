@@ -3,15 +3,15 @@
 // the pattern of L is cs_chol's, so the symbolic step (chol_symbolic_device), the entry map (chol_entry_map) and the scatter
 // (chol_scatter) are csx_chol's own; the numeric kernels here are the left-looking column of chol_column with d[k] carried
 // beside L(j,k), no square root, and the pivot rule (perturbation below tau, breakdown at 0 or a non-finite pivot).
-//   k_ldl_level   one wave per column of a height level of the elimination tree
-//   k_ldl_run     one workgroup walks a run of levels of at most LDL_WAVES columns each (a chain), a barrier per level
+//   ldl_column    one wave's column, behind the policy LdlColumn of the level walk (csx_levelwalk.h: k_level, k_run, the schedule)
 //   k_ldl_stats   inertia, min / max |d|, max |l| off the diagonal in one pass
 //   k_block_div_rows  X[i, :] /= d[i], the D step of a solve
 // Every sum is updated in ascending k by one wave, one update after the other: L.x and d are byte-equal to csx_ldl_host.
 // A factor or refactor runs into scratch arrays and is committed only when no column broke down.
 // The host side is the partial elimination of the first n1 columns (LdlFactor, ldl_build, ldl_run, ldl_refactor: csx_ldl.h):
 // csx_ldl_factor is n1 = n with the walker uncapped, csx_schur_factor (csx_schur.hip) its own n1 with the walker cut; the
-// trailing columns are csx_schur.hip's kernel behind schur_launch_cols.
+// trailing columns are csx_schur.hip's kernel behind schur_launch_cols.  csx_level_schedule, the walk's scheduler on host
+// arrays, is exported here.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -111,42 +111,18 @@ __device__ __forceinline__ void ldl_column(int32_t j, const int32_t *__restrict_
     __builtin_amdgcn_wave_barrier();
 }
 
-#define LDL_SHARED                                  \
-    __shared__ double s_acc_v[LDL_WAVES][LDL_ACC];  \
-    __shared__ int32_t s_acc_r[LDL_WAVES][LDL_ACC];
-
-// one wave per column of a level
-__global__ __launch_bounds__(64 * LDL_WAVES) void k_ldl_level(const int32_t *__restrict__ cols, int32_t count,
-                                                             const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
-                                                             double *Lx, double *d, const int32_t *__restrict__ row_ptr,
-                                                             const int32_t *__restrict__ row_col,
-                                                             const int32_t *__restrict__ row_pos, double tau, int *flags) {
-    LDL_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t c = (int64_t)blockIdx.x * LDL_WAVES + w;
-    if (c >= count) return;
-    ldl_column(cols[c], Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, s_acc_v[w], s_acc_r[w], lane, flags);
-}
-
-// One workgroup walks the levels [l0, l1), each of at most LDL_WAVES columns: wave w takes column w of the level, a barrier
-// between levels makes the finished columns visible to the next.  The trip counts are the level pointers, the same for every
-// wave, so every wave reaches every barrier.
-__global__ __launch_bounds__(64 * LDL_WAVES) void k_ldl_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
-                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Lp,
-                                                           const int32_t *__restrict__ Li, double *Lx, double *d,
-                                                           const int32_t *__restrict__ row_ptr,
-                                                           const int32_t *__restrict__ row_col,
-                                                           const int32_t *__restrict__ row_pos, double tau, int *flags) {
-    LDL_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int32_t l = l0; l < l1; l++) {
-        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
-        if (w < cnt) ldl_column(cols[b + w], Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, s_acc_v[w], s_acc_r[w], lane, flags);
-        __syncthreads();
+// the level walk's policy (csx_levelwalk.h): ldl_column behind k_level / k_run, with the kernels' argument types and LDS arrays
+struct LdlColumn {
+    using Args = ColumnArgs<const int32_t *__restrict__, const int32_t *__restrict__, double *, double *, const int32_t *__restrict__,
+                            const int32_t *__restrict__, const int32_t *__restrict__, double, int *>;
+    static __device__ __forceinline__ void column(int32_t j, int w, int lane, const int32_t *Lp, const int32_t *Li, double *Lx,
+                                                  double *d, const int32_t *row_ptr, const int32_t *row_col, const int32_t *row_pos,
+                                                  double tau, int *flags) {
+        __shared__ double acc_v[WALK_WAVES][LDL_ACC];
+        __shared__ int32_t acc_r[WALK_WAVES][LDL_ACC];
+        ldl_column(j, Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, acc_v[w], acc_r[w], lane, flags);
     }
-}
-
-__device__ __forceinline__ uint64_t abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
+};
 
 // One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|
 // off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (csx_residual.hip's rule: a NaN ranks above inf).
@@ -197,31 +173,6 @@ __global__ __launch_bounds__(256) void k_block_div_rows(double *__restrict__ X, 
 
 void destroy(LdlFactor *F) { delete F; }
 
-// The numeric launches of the first n1 columns over their height levels: a level of more than LDL_WAVES columns is one launch of
-// the wave-per-column kernel, a run of narrower levels goes to the one-workgroup walker, at most F->run_cap levels a launch.
-static void ldl_launch_levels(LdlFactor *F, double tau) {
-    hipStream_t s = ctx().stream;
-    const std::vector<int32_t> &lp = F->level_ptr_h;
-    const int32_t nlev = (int32_t)lp.size() - 1;
-    for (int32_t l = 0; l < nlev;) {
-        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
-        if (cnt > LDL_WAVES) {
-            hipLaunchKernelGGL(k_ldl_level, dim3((unsigned)((cnt + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, s,
-                               F->level_cols.get() + lp[(size_t)l], cnt, F->Lp, F->Li, F->Lx.get(), F->dd.get(), F->rp.get(),
-                               F->rc.get(), F->rpos.get(), tau, F->flags.get());
-            F->level_launches++;
-            l++;
-            continue;
-        }
-        int32_t e = l + 1;   // a run of narrow levels: one workgroup, no way back to the host
-        while (e < nlev && e - l < F->run_cap && lp[(size_t)e + 1] - lp[(size_t)e] <= LDL_WAVES) e++;
-        hipLaunchKernelGGL(k_ldl_run, dim3(1), dim3(64 * LDL_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), l, e, F->Lp, F->Li,
-                           F->Lx.get(), F->dd.get(), F->rp.get(), F->rc.get(), F->rpos.get(), tau, F->flags.get());
-        F->run_launches++;
-        l = e;
-    }
-}
-
 int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     hipStream_t s = ctx().stream;
     Csc *L = csc(F->hL);
@@ -229,14 +180,12 @@ int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     const int64_t ns = F->ns;
     if (!L || !dv || !Sv || !L->x || L->nnz != F->head + ns || dv->len != F->n1 || Sv->len != ns * ns) return CSX_EINVAL;
     const int32_t n1 = F->n1;
-    F->level_launches = F->run_launches = F->schur_launches = 0;
-    const int hinit[3] = {LDL_NONE, 0, 0};
+    F->schur_launches = 0;
+    const int hinit[3] = {WALK_NONE, 0, 0};
     const unsigned long long sinit[5] = {0ull, 0ull, ~0ull, 0ull, 0ull};
-    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(walk_begin(F, hinit, 3, sinit, 5));
     CSX_TRY(chol_scatter(F->lnz, F->win, Ax, F->Lx));
-    ldl_launch_levels(F, tau);
+    walk_levels<LdlColumn>(F, LdlColumn::Args(), F->Lp, F->Li, F->Lx, F->dd, F->rp, F->rc, F->rpos, tau, F->flags);
     if (F->chunks > 0) {
         schur_launch_cols(F);
         F->schur_launches = 1;
@@ -244,22 +193,11 @@ int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     if (n1 > 0)
         hipLaunchKernelGGL(k_ldl_stats, dim3((unsigned)(((int64_t)n1 + 3) / 4)), dim3(256), 0, s, n1, F->Lp, F->Lx.get(), F->dd.get(),
                            F->stats.get());
-    (void)hipEventRecord(F->ev_b, s);
-    int hflags[3] = {LDL_NONE, 0, 0};
+    int hflags[3] = {WALK_NONE, 0, 0};
     unsigned long long hst[5] = {0, 0, 0, 0, 0};
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("%s: %s", F->who, hipGetErrorString(hipGetLastError()));
-        (void)hipStreamSynchronize(s);
-        return CSX_ERUNTIME;
-    }
-    float ms = 0.0f;
-    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    CSX_TRY(walk_end(F, hflags, 3, hst, 5, ok));
     F->perturbed = hflags[1];
     F->long_cols = hflags[2];
-    F->breakdown = hflags[0] == LDL_NONE ? -1 : hflags[0];
-    *ok = F->breakdown < 0 ? 1 : 0;
     if (!*ok) return CSX_OK;
     F->pos = (int64_t)hst[0];
     F->neg = (int64_t)hst[1];
@@ -277,27 +215,19 @@ int ldl_run(LdlFactor *F, const double *Ax, double tau, int *ok) {
     return CSX_OK;
 }
 
-int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t n1, int32_t run_cap, const char *who,
+int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, int32_t n1, int32_t run_levels, const char *who,
               LdlFactor *F) {
     hipStream_t s = ctx().stream;
     const int32_t n = A->n, ns = n - n1;
-    F->n = n;
     F->n1 = n1;
     F->ns = ns;
-    F->run_cap = run_cap;
-    F->who = who;
-    F->anz = A->nnz;
     F->lnz = cp[n];
     if (cp[0] != 0 || F->lnz < n) return CSX_EINVAL;
     for (int32_t j = 0; j < n; j++)
         if (cp[j + 1] <= cp[j]) return CSX_EINVAL;
     F->head = cp[n1];
     if (!A->trusted) CSX_TRY(csc_validate(A));
-    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
-    CSX_TRY(F->flags.alloc(3));
-    CSX_TRY(F->stats.alloc(5));
-    CSX_HIP(hipEventCreate(&F->ev_a));
-    CSX_HIP(hipEventCreate(&F->ev_b));
+    CSX_TRY(walk_init(F, A, who, 3, 5));
     const int64_t lpnz = (int64_t)F->head + ns;
     std::unique_ptr<Csc> L(new Csc());
     L->m = L->n = n;
@@ -329,9 +259,8 @@ int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *p
         // level depends on its children alone, so the cut leaves the levels below it as they are, and at n1 == n it cuts nothing
         std::vector<int32_t> cut((size_t)n1);
         for (int32_t j = 0; j < n1; j++) cut[(size_t)j] = parent[j] < n1 ? parent[j] : -1;
-        ldl_levels(n1, cut.data(), F->level_ptr_h, cols);
-        CSX_TRY(upload(F->level_cols, cols));
-        CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+        height_levels(n1, cut.data(), F->level_ptr_h, cols);
+        CSX_TRY(walk_set_levels(F, cols, run_levels));
         CSX_TRY(F->win.alloc((size_t)F->lnz));
         DevBuf<int32_t> d_pinv;
         if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
@@ -372,14 +301,7 @@ int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *p
 
 int ldl_refactor(LdlFactor *F, csx_handle_t hA2, double tau, int *ok) {
     if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
-    *ok = -1;
-    const double *x2 = nullptr;
-    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
-    if (!x2) {
-        set_error("%s_refactor: A2 does not have the pattern (or the length) of the factored matrix", F->who);
-        return CSX_EINVAL;   // nothing changes
-    }
-    return ldl_run(F, x2, tau, ok);
+    return walk_refactor(F, hA2, ok, [&](const double *x2) { return ldl_run(F, x2, tau, ok); });
 }
 
 int ldl_stats(const LdlFactor *F, double *out) {
@@ -402,7 +324,7 @@ extern "C" int csx_ldl_factor(csx_handle_t hA, const int32_t *parent, const int3
     *out = 0;
     *ok = 0;
     std::unique_ptr<LdlFactor> F(new LdlFactor());
-    CSX_TRY(ldl_build(A, parent, cp, pinv, A->n, LDL_RUN_UNCAPPED, "csx_ldl", F.get()));   // nothing kept
+    CSX_TRY(ldl_build(A, parent, cp, pinv, A->n, WALK_RUN_UNCAPPED, "csx_ldl", F.get()));   // nothing kept
     CSX_TRY(ldl_run(F.get(), A->x, tau, ok));
     if (*ok) *out = put(K_LDLFACTOR, F.release());
     return CSX_OK;
@@ -428,8 +350,8 @@ extern "C" int csx_ldl_info(csx_handle_t h, int64_t *info) {
     if (!F || !info) return CSX_EINVAL;
     info[0] = F->n;
     info[1] = F->lnz;
-    info[2] = (int64_t)F->level_ptr_h.size() - 1;
-    info[3] = F->level_launches + F->run_launches;
+    info[2] = F->levels();
+    info[3] = F->launches();
     info[4] = F->pos;
     info[5] = F->neg;
     info[6] = F->perturbed;
@@ -445,6 +367,21 @@ extern "C" int csx_ldl_info(csx_handle_t h, int64_t *info) {
 extern "C" int csx_ldl_window(int32_t *entries) {   // (no device needed)
     if (!entries) return CSX_EINVAL;
     *entries = LDL_ACC;
+    return CSX_OK;
+}
+
+extern "C" int csx_level_schedule(int32_t nlev, const int32_t *level_ptr, int32_t waves, int32_t run_levels, const int64_t *work,
+                                  int64_t run_work, int32_t *launches, int32_t *count) {   // (no device needed)
+    if (nlev < 0 || !level_ptr || waves < 1 || run_levels < 1 || !count || (nlev > 0 && !launches)) return CSX_EINVAL;
+    for (int32_t l = 0; l < nlev; l++)
+        if (level_ptr[l + 1] < level_ptr[l]) return CSX_EINVAL;
+    const std::vector<LevelLaunch> S = level_schedule(level_ptr, nlev, waves, run_levels, work, run_work);
+    for (size_t t = 0; t < S.size(); t++) {
+        launches[3 * t] = S[t].wide ? 1 : 0;
+        launches[3 * t + 1] = S[t].l0;
+        launches[3 * t + 2] = S[t].l1;
+    }
+    *count = (int32_t)S.size();
     return CSX_OK;
 }
 

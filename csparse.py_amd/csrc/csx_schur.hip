@@ -2,10 +2,11 @@
 // in include/csx.h).  The permutation numbers the n1 interior indices first and the ns kept ones last; the symbolic analysis,
 // the entry map and the scatter are csx_chol's on the FULL pattern Lf of chol(P A P'), whose row view is what the trailing
 // columns need.  The factor object, its build, run, commit and refactor are csx_ldl.hip's (LdlFactor, ldl_build, ldl_run,
-// ldl_refactor: csx_ldl.h) -- the LDL' factor is this one at n1 = n; what is here is what only ns > 0 needs:
+// ldl_refactor: csx_ldl.h), the interior columns' launches the level walk's (csx_levelwalk.h) with the walker cut at
+// WALK_RUN_LEVELS -- the LDL' factor is this one at n1 = n; what is here is what only ns > 0 needs:
 //   k_schur_cols    the trailing columns, one wide level: one wave per (column j, chunk of at most LDL_ACC consecutive rows of
 //                   j .. n - 1), the chunk's sums in wave-private LDS indexed by row - chunk start
-// with its chunk list, the walker's cut and the entry points.
+// with its chunk list and the entry points.
 // Every sum is updated in ascending k by one wave, one update after the other: Lp.x, d and S are byte-equal to csx_schur_host.
 #include <algorithm>
 #include <vector>
@@ -17,20 +18,18 @@
 
 namespace csx {
 
-constexpr int32_t SCHUR_RUN_LEVELS = 256;   // levels one launch of the walker takes (csx_slu.hip's SLU_RUN_LEVELS)
-
 // Wave c takes rows [row0, min(row0 + LDL_ACC, n)) of column j = ch_col[c] of the permuted matrix, j >= n1.  Lx: the scratch
 // values on the full pattern -- C in the slots of the trailing columns, the finished L in the interior ones; d: the interior
 // pivots.  The row view of row j lists its columns k ascending and ends with the diagonal; the first k >= n1 ends the updates.
-__global__ __launch_bounds__(64 * LDL_WAVES) void k_schur_cols(const int32_t *__restrict__ ch_col, const int32_t *__restrict__ ch_row0,
+__global__ __launch_bounds__(64 * WALK_WAVES) void k_schur_cols(const int32_t *__restrict__ ch_col, const int32_t *__restrict__ ch_row0,
                                                               int64_t count, int32_t n, int32_t n1, const int32_t *__restrict__ Lp,
                                                               const int32_t *__restrict__ Li, const double *__restrict__ Lx,
                                                               const double *__restrict__ d, const int32_t *__restrict__ row_ptr,
                                                               const int32_t *__restrict__ row_col,
                                                               const int32_t *__restrict__ row_pos, double *__restrict__ S) {
-    __shared__ double s_acc[LDL_WAVES][LDL_ACC];
+    __shared__ double s_acc[WALK_WAVES][LDL_ACC];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t c = (int64_t)blockIdx.x * LDL_WAVES + w;
+    const int64_t c = (int64_t)blockIdx.x * WALK_WAVES + w;
     if (c >= count) return;
     double *acc = s_acc[w];
     const int32_t j = ch_col[c], r0 = ch_row0[c];
@@ -47,7 +46,7 @@ __global__ __launch_bounds__(64 * LDL_WAVES) void k_schur_cols(const int32_t *__
     // position of L(j,k), end of column k, w = L(j,k) d[k] -- and the heads of the eight columns are requested together.
     constexpr int UQ = 8;
     for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0, kq = LDL_NONE;
+        int32_t posq = 0, kendq = 0, kq = WALK_NONE;
         double wq = 0.0;
         if (lane < UQ && q0 + lane < qe) {
             kq = row_col[q0 + lane];
@@ -101,7 +100,7 @@ __global__ __launch_bounds__(64 * LDL_WAVES) void k_schur_cols(const int32_t *__
 }
 
 void schur_launch_cols(const LdlFactor *F) {
-    hipLaunchKernelGGL(k_schur_cols, dim3((unsigned)((F->chunks + LDL_WAVES - 1) / LDL_WAVES)), dim3(64 * LDL_WAVES), 0, ctx().stream,
+    hipLaunchKernelGGL(k_schur_cols, dim3((unsigned)((F->chunks + WALK_WAVES - 1) / WALK_WAVES)), dim3(64 * WALK_WAVES), 0, ctx().stream,
                        F->ch_col.get(), F->ch_row0.get(), F->chunks, F->n, F->n1, F->Lp, F->Li, F->Lx.get(), F->dd.get(), F->rp.get(),
                        F->rc.get(), F->rpos.get(), F->Sx.get());
 }
@@ -134,7 +133,7 @@ extern "C" int csx_schur_factor(csx_handle_t hA, const int32_t *parent, const in
     *out = 0;
     *ok = 0;
     std::unique_ptr<LdlFactor> F(new LdlFactor());
-    CSX_TRY(ldl_build(A, parent, cp, pinv, n1, SCHUR_RUN_LEVELS, "csx_schur", F.get()));
+    CSX_TRY(ldl_build(A, parent, cp, pinv, n1, WALK_RUN_LEVELS, "csx_schur", F.get()));
     CSX_TRY(schur_chunks(F.get()));
     CSX_TRY(ldl_run(F.get(), A->x, tau, ok));
     if (*ok) *out = put(K_SCHURFACTOR, F.release());
@@ -164,8 +163,8 @@ extern "C" int csx_schur_info(csx_handle_t h, int64_t *info) {
     info[1] = F->n1;
     info[2] = F->ns;
     info[3] = (int64_t)F->head + F->ns;
-    info[4] = (int64_t)F->level_ptr_h.size() - 1;
-    info[5] = F->level_launches + F->run_launches + F->schur_launches;
+    info[4] = F->levels();
+    info[5] = F->launches() + F->schur_launches;
     info[6] = F->level_launches;
     info[7] = F->run_launches;
     info[8] = F->schur_launches;

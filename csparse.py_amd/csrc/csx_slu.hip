@@ -5,8 +5,8 @@
 // first) are two value arrays on that one pattern; the numeric kernel is ldl_column (csx_ldl.hip) with a second accumulator.
 //   k_slu_sym_rows / k_slu_sym_ptr / k_slu_sym_fill   the pattern whose upper triangle is that of A1 + A1', for the symbolic step
 //   k_slu_entry_map   slot of L and slot of Ut of every entry of A (of duplicates the last)
-//   k_slu_level   one wave per column of a height level of the elimination tree
-//   k_slu_run     one workgroup walks at most SLU_RUN_LEVELS levels of at most SLU_WAVES columns each, a barrier per level
+//   slu_column    one wave's column, behind the policy SluColumn of the level walk (csx_levelwalk.h: k_level, k_run, the
+//                 schedule with the walker cut at WALK_RUN_LEVELS levels a launch)
 //   k_slu_stats   min / max |d|, max |l|, max |u| off the diagonal, pivot signs in one pass
 // Every sum is updated in ascending k by one wave, one update after the other: L.x and Ut.x are byte-equal to csx_slu_host.
 // A factor or refactor runs into scratch arrays and is committed only when no column broke down.
@@ -15,16 +15,13 @@
 #include <cstring>
 
 #include "csx_internal.h"
-#include "csx_ldl.h"
+#include "csx_levelwalk.h"
 
 #pragma clang fp contract(off)
 
 namespace csx {
 
-constexpr int SLU_ACC = 512;          // column entries kept in LDS per wave (8 + 8 + 4 bytes each: 40 KB a workgroup); longer columns are updated in place
-constexpr int SLU_WAVES = 4;          // waves per workgroup
-constexpr int SLU_RUN_LEVELS = 256;   // levels one launch of the walker takes: a longer run is several launches
-constexpr int SLU_NONE = 0x7fffffff;
+constexpr int SLU_ACC = 512;   // column entries kept in LDS per wave (8 + 8 + 4 bytes each: 40 KB a workgroup); longer columns are updated in place
 
 // ---- analysis ------------------------------------------------------------------------------------------------------------------
 
@@ -180,44 +177,19 @@ __device__ __forceinline__ void slu_column(int32_t j, const int32_t *__restrict_
     __builtin_amdgcn_wave_barrier();
 }
 
-#define SLU_SHARED                                  \
-    __shared__ double s_acc_l[SLU_WAVES][SLU_ACC];  \
-    __shared__ double s_acc_u[SLU_WAVES][SLU_ACC];  \
-    __shared__ int32_t s_acc_r[SLU_WAVES][SLU_ACC];
-
-// one wave per column of a level
-__global__ __launch_bounds__(64 * SLU_WAVES) void k_slu_level(const int32_t *__restrict__ cols, int32_t count,
-                                                             const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
-                                                             double *Lx, double *Ux, const int32_t *__restrict__ row_ptr,
-                                                             const int32_t *__restrict__ row_col,
-                                                             const int32_t *__restrict__ row_pos, double tau, int *flags) {
-    SLU_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t c = (int64_t)blockIdx.x * SLU_WAVES + w;
-    if (c >= count) return;
-    slu_column(cols[c], Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, s_acc_l[w], s_acc_u[w], s_acc_r[w], lane, flags);
-}
-
-// One workgroup walks the levels [l0, l1), l1 - l0 <= SLU_RUN_LEVELS, each of at most SLU_WAVES columns: wave w takes column w of
-// the level, a barrier between levels makes the finished columns visible to the next.  The trip counts are the level pointers,
-// the same for every wave, so every wave reaches every barrier.
-__global__ __launch_bounds__(64 * SLU_WAVES) void k_slu_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
-                                                           int32_t l0, int32_t l1, const int32_t *__restrict__ Lp,
-                                                           const int32_t *__restrict__ Li, double *Lx, double *Ux,
-                                                           const int32_t *__restrict__ row_ptr,
-                                                           const int32_t *__restrict__ row_col,
-                                                           const int32_t *__restrict__ row_pos, double tau, int *flags) {
-    SLU_SHARED
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int32_t l = l0; l < l1; l++) {
-        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
-        if (w < cnt)
-            slu_column(cols[b + w], Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, s_acc_l[w], s_acc_u[w], s_acc_r[w], lane, flags);
-        __syncthreads();
+// the level walk's policy (csx_levelwalk.h): slu_column behind k_level / k_run, with the kernels' argument types and LDS arrays
+struct SluColumn {
+    using Args = ColumnArgs<const int32_t *__restrict__, const int32_t *__restrict__, double *, double *, const int32_t *__restrict__,
+                            const int32_t *__restrict__, const int32_t *__restrict__, double, int *>;
+    static __device__ __forceinline__ void column(int32_t j, int w, int lane, const int32_t *Lp, const int32_t *Li, double *Lx,
+                                                  double *Ux, const int32_t *row_ptr, const int32_t *row_col,
+                                                  const int32_t *row_pos, double tau, int *flags) {
+        __shared__ double acc_l[WALK_WAVES][SLU_ACC];
+        __shared__ double acc_u[WALK_WAVES][SLU_ACC];
+        __shared__ int32_t acc_r[WALK_WAVES][SLU_ACC];
+        slu_column(j, Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, acc_l[w], acc_u[w], acc_r[w], lane, flags);
     }
-}
-
-__device__ __forceinline__ uint64_t slu_abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
+};
 
 // One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|,
 // st[5] max |u| off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (k_ldl_stats' rule)
@@ -228,7 +200,7 @@ __global__ __launch_bounds__(256) void k_slu_stats(int32_t n, const int32_t *__r
     if (j >= n) return;
     uint64_t lmax = 0, umax = 0;
     for (int32_t p = Lp[j] + 1 + lane; p < Lp[j + 1]; p += 64) {
-        const uint64_t a = slu_abs_bits(Lx[p]), b = slu_abs_bits(Ux[p]);
+        const uint64_t a = abs_bits(Lx[p]), b = abs_bits(Ux[p]);
         lmax = a > lmax ? a : lmax;
         umax = b > umax ? b : umax;
     }
@@ -242,38 +214,27 @@ __global__ __launch_bounds__(256) void k_slu_stats(int32_t n, const int32_t *__r
         const double dj = Ux[Lp[j]];
         if (dj > 0.0) atomicAdd(st + 0, 1ull);
         if (dj < 0.0) atomicAdd(st + 1, 1ull);
-        atomicMin(st + 2, (unsigned long long)slu_abs_bits(dj));
-        atomicMax(st + 3, (unsigned long long)slu_abs_bits(dj));
+        atomicMin(st + 2, (unsigned long long)abs_bits(dj));
+        atomicMax(st + 3, (unsigned long long)abs_bits(dj));
         if (lmax) atomicMax(st + 4, (unsigned long long)lmax);
         if (umax) atomicMax(st + 5, (unsigned long long)umax);
     }
 }
 
-struct SluFactor {
-    int32_t n = 0, anz = 0, lnz = 0;
-    DevBuf<int32_t> p0, i0;                 // A's pattern: every A2 of a refactor is checked against it
+struct SluFactor : LevelFactor {
+    int32_t lnz = 0;
     DevBuf<int32_t> rp, rc, rpos;           // row view of the pattern (chol_symbolic_device)
     DevBuf<int32_t> winL, winU;             // the two entry maps
-    DevBuf<int32_t> level_cols, level_ptr;  // height levels of the elimination tree: columns by level, ascending inside one
-    std::vector<int32_t> level_ptr_h;
     csx_handle_t hL = 0, hU = 0;            // the committed factor: owned here, lent out by csx_slu_parts; Ut borrows L's p and i
     DevBuf<double> utx;                     // Ut's values (Ut itself owns nothing)
     DevBuf<double> Lx, Ux;                  // scratch of a run: committed only when no column broke down
-    DevBuf<int> flags;                      // [0] smallest broken column, [1] perturbed pivots, [2] columns updated in place
-    DevBuf<unsigned long long> stats;       // k_slu_stats
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    // flags: [1] perturbed pivots, [2] columns updated in place; stats: k_slu_stats' six words
     // csx_slu_info / csx_slu_stats
-    int64_t launches = 0, level_launches = 0, run_launches = 0, long_cols = 0;   // long_cols: counted by the kernels of the last run
-    int64_t pos = 0, neg = 0, perturbed = 0, breakdown = -1, kernel_us = 0;
+    int64_t pos = 0, neg = 0, perturbed = 0;
     double min_d = 0.0, max_d = 0.0, max_l = 0.0, max_u = 0.0;
-    SluFactor() = default;
-    SluFactor(const SluFactor &) = delete;
-    SluFactor &operator=(const SluFactor &) = delete;
     ~SluFactor() {
         if (hU) (void)csx_free(hU);
         if (hL) (void)csx_free(hL);
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
     }
 };
 
@@ -288,56 +249,20 @@ static int slu_run(SluFactor *F, const double *Ax, double tau, int *ok) {
     Csc *L = csc(F->hL), *U = csc(F->hU);
     if (!L || !U || !L->x || !U->x || L->nnz != F->lnz || U->nnz != F->lnz) return CSX_EINVAL;
     const int32_t n = F->n;
-    F->launches = F->level_launches = F->run_launches = 0;
-    const int hinit[3] = {SLU_NONE, 0, 0};
+    const int hinit[3] = {WALK_NONE, 0, 0};
     const unsigned long long sinit[6] = {0ull, 0ull, ~0ull, 0ull, 0ull, 0ull};
-    CSX_HIP(hipMemcpyAsync(F->flags, hinit, sizeof hinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipMemcpyAsync(F->stats, sinit, sizeof sinit, hipMemcpyHostToDevice, s));
-    CSX_HIP(hipEventRecord(F->ev_a, s));
+    CSX_TRY(walk_begin(F, hinit, 3, sinit, 6));
     CSX_TRY(chol_scatter(F->lnz, F->winL, Ax, F->Lx));
     CSX_TRY(chol_scatter(F->lnz, F->winU, Ax, F->Ux));
-    const std::vector<int32_t> &lp = F->level_ptr_h;
-    const int32_t nlev = (int32_t)lp.size() - 1;
-    for (int32_t l = 0; l < nlev;) {
-        const int32_t cnt = lp[(size_t)l + 1] - lp[(size_t)l];
-        if (cnt > SLU_WAVES) {
-            hipLaunchKernelGGL(k_slu_level, dim3((unsigned)((cnt + SLU_WAVES - 1) / SLU_WAVES)), dim3(64 * SLU_WAVES), 0, s,
-                               F->level_cols + lp[(size_t)l], cnt, L->p, L->i, F->Lx.get(), F->Ux.get(), F->rp.get(), F->rc.get(),
-                               F->rpos.get(), tau, F->flags.get());
-            F->level_launches++;
-            l++;
-            continue;
-        }
-        int32_t e = l + 1;   // a run of narrow levels: one workgroup, at most SLU_RUN_LEVELS levels a launch
-        while (e < nlev && lp[(size_t)e + 1] - lp[(size_t)e] <= SLU_WAVES) e++;
-        for (int32_t a = l; a < e; a += SLU_RUN_LEVELS) {
-            hipLaunchKernelGGL(k_slu_run, dim3(1), dim3(64 * SLU_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), a,
-                               std::min(a + SLU_RUN_LEVELS, e), L->p, L->i, F->Lx.get(), F->Ux.get(), F->rp.get(), F->rc.get(),
-                               F->rpos.get(), tau, F->flags.get());
-            F->run_launches++;
-        }
-        l = e;
-    }
-    F->launches = F->level_launches + F->run_launches;
+    walk_levels<SluColumn>(F, SluColumn::Args(), L->p, L->i, F->Lx, F->Ux, F->rp, F->rc, F->rpos, tau, F->flags);
     if (n > 0)
         hipLaunchKernelGGL(k_slu_stats, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, L->p, F->Lx.get(), F->Ux.get(),
                            F->stats.get());
-    (void)hipEventRecord(F->ev_b, s);
-    int hflags[3] = {SLU_NONE, 0, 0};
+    int hflags[3] = {WALK_NONE, 0, 0};
     unsigned long long hst[6] = {0, 0, 0, 0, 0, 0};
-    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hflags, F->flags.get(), sizeof hflags, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(hst, F->stats.get(), sizeof hst, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("csx_slu: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipStreamSynchronize(s);
-        return CSX_ERUNTIME;
-    }
-    float ms = 0.0f;
-    F->kernel_us = hipEventElapsedTime(&ms, F->ev_a, F->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
+    CSX_TRY(walk_end(F, hflags, 3, hst, 6, ok));
     F->perturbed = hflags[1];
     F->long_cols = hflags[2];
-    F->breakdown = hflags[0] == SLU_NONE ? -1 : hflags[0];
-    *ok = F->breakdown < 0 ? 1 : 0;
     if (!*ok) return CSX_OK;
     F->pos = (int64_t)hst[0];
     F->neg = (int64_t)hst[1];
@@ -391,8 +316,6 @@ static int slu_symmetrised(const Csc *A, const int32_t *prinv, DevBuf<int32_t> &
 static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *prow, const int32_t *pinv, SluFactor *F) {
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
-    F->n = n;
-    F->anz = A->nnz;
     F->lnz = cp[n];
     if (cp[0] != 0 || F->lnz < n || A->nnz > 0x3fffffff) return CSX_EINVAL;
     std::vector<int32_t> prinv;
@@ -407,11 +330,7 @@ static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int
         }
     }
     if (!A->trusted) CSX_TRY(csc_validate(A));
-    CSX_TRY(rf_keep_pattern(A, F->p0, F->i0));
-    CSX_TRY(F->flags.alloc(3));
-    CSX_TRY(F->stats.alloc(6));
-    CSX_HIP(hipEventCreate(&F->ev_a));
-    CSX_HIP(hipEventCreate(&F->ev_b));
+    CSX_TRY(walk_init(F, A, "csx_slu", 3, 6));
     std::unique_ptr<Csc> L(new Csc());
     L->m = L->n = n;
     L->nnz = F->lnz;
@@ -427,9 +346,8 @@ static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int
         CSX_TRY(slu_symmetrised(A, prow ? d_prinv.get() : nullptr, a1i, &M));
         CSX_TRY(chol_symbolic_device(&M, parent, cp, pinv, &L->p, &L->i, &F->rp, &F->rc, &F->rpos, nullptr));   // (checks S and pinv)
         std::vector<int32_t> cols;
-        ldl_levels(n, parent, F->level_ptr_h, cols);
-        CSX_TRY(upload(F->level_cols, cols));
-        CSX_TRY(upload(F->level_ptr, F->level_ptr_h));
+        height_levels(n, parent, F->level_ptr_h, cols);
+        CSX_TRY(walk_set_levels(F, cols, WALK_RUN_LEVELS));
         CSX_TRY(F->winL.alloc((size_t)F->lnz));
         CSX_TRY(F->winU.alloc((size_t)F->lnz));
         if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
@@ -486,14 +404,7 @@ extern "C" int csx_slu_refactor(csx_handle_t h, csx_handle_t hA2, double tau, in
     CSX_TRY(require_ready());
     SluFactor *F = (SluFactor *)get(h, K_SLUFACTOR);
     if (!F || !ok || !(tau >= 0.0)) return CSX_EINVAL;
-    *ok = -1;
-    const double *x2 = nullptr;
-    CSX_TRY(rf_values(hA2, F->n, F->n, F->anz, F->p0, F->i0, F->flags, &x2));
-    if (!x2) {
-        set_error("csx_slu_refactor: A2 does not have the pattern (or the length) of the factored matrix");
-        return CSX_EINVAL;   // nothing changes
-    }
-    return slu_run(F, x2, tau, ok);
+    return walk_refactor(F, hA2, ok, [&](const double *x2) { return slu_run(F, x2, tau, ok); });
 }
 
 extern "C" int csx_slu_parts(csx_handle_t h, csx_handle_t *L, csx_handle_t *Ut) {
@@ -511,8 +422,8 @@ extern "C" int csx_slu_info(csx_handle_t h, int64_t *info) {
     if (!F || !info) return CSX_EINVAL;
     info[0] = F->n;
     info[1] = F->lnz;
-    info[2] = (int64_t)F->level_ptr_h.size() - 1;
-    info[3] = F->launches;
+    info[2] = F->levels();
+    info[3] = F->launches();
     info[4] = F->level_launches;
     info[5] = F->run_launches;
     info[6] = F->perturbed;
@@ -520,7 +431,7 @@ extern "C" int csx_slu_info(csx_handle_t h, int64_t *info) {
     info[8] = F->kernel_us;
     info[9] = F->long_cols;
     info[10] = SLU_ACC;
-    info[11] = SLU_RUN_LEVELS;
+    info[11] = WALK_RUN_LEVELS;
     info[12] = F->pos;
     info[13] = F->neg;
     return CSX_OK;
@@ -529,7 +440,7 @@ extern "C" int csx_slu_info(csx_handle_t h, int64_t *info) {
 extern "C" int csx_slu_window(int32_t *entries, int32_t *run_levels) {   // (no device needed)
     if (!entries || !run_levels) return CSX_EINVAL;
     *entries = SLU_ACC;
-    *run_levels = SLU_RUN_LEVELS;
+    *run_levels = WALK_RUN_LEVELS;
     return CSX_OK;
 }
 

@@ -1066,7 +1066,16 @@ int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *
  *   kernels), exact zeros on R's diagonal (committed factor), the smallest broken column of the last run or -1, microseconds of
  *   the last run between two events, the LDS window in slots, the run cap in levels.
  * csx_hqr_stats: out[2] = min |r_kk|, max |r_kk| of the committed factor (0.0 for n = 0).
- * csx_hqr_window: the LDS window in slots and the run cap in levels, without a device or a factor. */
+ * csx_hqr_window: the LDS window in slots and the run cap in levels, without a device or a factor.
+ * csx_level_schedule: the launches of a numeric run of csx_ldl_factor, csx_schur_factor, csx_slu_factor and csx_hqr_factor over
+ *   the height levels of a tree, on host arrays, no device.  level_ptr: nlev + 1 non-decreasing offsets, level l holds
+ *   level_ptr[l + 1] - level_ptr[l] columns.  A level of more than `waves` columns is one launch, a wave per column.  A run of
+ *   narrower levels goes to the walker (one workgroup, a barrier per level): a launch of it ends before the next wide level,
+ *   after run_levels levels, or -- when work is not NULL (nlev figures >= 0) -- before the level that would take the sum of its
+ *   levels' work past run_work; a level that alone exceeds run_work is still taken.  The factorisations call it with waves = 4;
+ *   run_levels = 2^31 - 1 (LDL') or 256 (Schur, LU, QR); no work but for QR (the slot updates of the level's longest column,
+ *   run_work = 2^24).  launches: room for 3 nlev integers, written as *count triples (1 wide / 0 walker, first level, end level)
+ *   that cover 0 .. nlev - 1 in order.  CSX_EINVAL for nlev < 0, waves < 1, run_levels < 1, decreasing offsets, a null pointer. */
 int csx_hqr_symbolic_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q,
                           const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t vcap, int32_t rcap,
                           int32_t *Vp, int32_t *Vi, int32_t *Rp, int32_t *Ri);
@@ -1080,6 +1089,8 @@ int csx_hqr_parts(csx_handle_t F, csx_handle_t *V, csx_handle_t *R, csx_handle_t
 int csx_hqr_info(csx_handle_t F, int64_t *info);
 int csx_hqr_stats(csx_handle_t F, double *out);
 int csx_hqr_window(int32_t *entries, int32_t *run_levels);
+int csx_level_schedule(int32_t nlev, const int32_t *level_ptr, int32_t waves, int32_t run_levels, const int64_t *work,
+                       int64_t run_work, int32_t *launches, int32_t *count);
 
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */

@@ -146,6 +146,18 @@ def _bidiagonal(n):
     return rect(n + 1, n, e)
 
 
+def _chains(count, length=3):
+    """block diagonal: `count` disjoint bidiagonal blocks of length + 1 rows and `length` columns, so every height level of the
+    column elimination tree has `count` columns"""
+    e = {}
+    for c in range(count):
+        for t in range(length):
+            i, j = c * (length + 1) + t, c * length + t
+            e[(i, j)] = 0.5 + 0.125 * c + 0.01 * t
+            e[(i + 1, j)] = -1.0 + 0.02 * t
+    return rect(count * (length + 1), count * length, e)
+
+
 def _long(rows, second):
     """a dense first column of `rows` rows; second: a second column with entries in rows 0 and 1"""
     rng = np.random.default_rng(rows)
@@ -200,6 +212,8 @@ def _build():
     add(Case("grid24-shift-natural", *_square(grid(24, sigma=SIGMA)), order=0, seed=18))
     add(Case("grid24-shift", *_square(grid(24, sigma=SIGMA)), order=3, seed=19))
     add(Case("stacked", *_stacked(24), order=0, seed=20))
+    add(Case("chains4", *_chains(4), seed=21))       # three levels of 4 columns: the widest the walker takes
+    add(Case("chains5", *_chains(5), seed=22))       # ... of 5: a wave per column
     return cases
 
 

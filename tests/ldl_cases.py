@@ -119,6 +119,18 @@ def _chain(n):
     return upper_csc(n, e)
 
 
+def _chains(count, length=3):
+    """block diagonal: `count` disjoint tridiagonal chains of `length` columns, so every height level has `count` columns"""
+    e = {}
+    for c in range(count):
+        for t in range(length):
+            j = c * length + t
+            e[(j, j)] = 0.5 + 0.1 * c            # (no pivot of any chain comes out zero)
+            if t:
+                e[(j - 1, j)] = -1.0
+    return upper_csc(count * length, e)
+
+
 def _arrow(n):
     e = {(j, j): float(n) for j in range(n)}
     e[(0, 0)] = -1.0
@@ -151,6 +163,8 @@ def _build():
     add(Case("long-column", *_arrow(WINDOW + 1), seed=11))
     add(Case("long-column-updated", *_arrow(WINDOW + 2), seed=12))     # its column 1 is long AND takes an update, in place
     add(Case("sparse-trees", *_signed_blocks(40, 24), seed=13))
+    add(Case("chains4", *_chains(4), seed=14))       # three levels of 4 columns: the widest the walker takes
+    add(Case("chains5", *_chains(5), seed=15))       # ... of 5: a wave per column
     return cases
 
 

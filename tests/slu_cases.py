@@ -158,6 +158,20 @@ def _chain(n):
     return csc(n, e)
 
 
+def _chains(count, length=3):
+    """block diagonal: `count` disjoint unsymmetric tridiagonal chains of `length` columns, so every height level has `count`
+    columns"""
+    e = {}
+    for c in range(count):
+        for t in range(length):
+            j = c * length + t
+            e[(j, j)] = 0.5 + 0.125 * c
+            if t:
+                e[(j - 1, j)] = -1.0
+                e[(j, j - 1)] = 0.75
+    return csc(count * length, e)
+
+
 def _arrow(n):
     e = {(j, j): float(n) for j in range(n)}
     e[(0, 0)] = -1.0
@@ -194,6 +208,8 @@ def _build():
     add(Case("saddle", *saddle(SADDLE_NH, SADDLE_NC, SADDLE_SEED, SADDLE_PERM), perturb=1e-10, seed=15, match=False, breaks=True))
     add(Case("long-column", *_arrow(WINDOW + 1), seed=16))
     add(Case("long-column-updated", *_arrow(WINDOW + 2), seed=17))     # its column 1 is long AND takes an update, in place
+    add(Case("chains4", *_chains(4), seed=19))       # three levels of 4 columns: the widest the walker takes
+    add(Case("chains5", *_chains(5), seed=20))       # ... of 5: a wave per column
     return cases
 
 

@@ -138,6 +138,10 @@ def test_which_kernel_ran(cs):
     assert HC.RUN_LEVELS == 256
     assert counts("bidiagonal") == (257, 2, 2, 0)          # the run walker alone: a launch takes RUN_LEVELS levels
     assert counts("blocks") == (2, 2, 0, 2)                # one wave per column: one wide level a launch
+    assert counts("chains4") == (3, 1, 1, 0)               # the width edge: 4 columns a level go to the walker ...
+    assert counts("chains5") == (3, 3, 0, 3)               # ... 5 to a wave per column
+    for name in ("chains4", "chains5"):
+        _is_reference(_factor(cs, HC.BY_NAME[name]), HC.BY_NAME[name], HC.BY_NAME[name].x)
     for name in ("grid24-shift", "stacked"):
         i = _factor(cs, HC.BY_NAME[name]).info()
         print(name, i)

@@ -106,6 +106,11 @@ def test_which_kernel_ran(cs):
     assert (i["levels"], i["launches"], i["run_launches"], i["level_launches"]) == (257, 1, 1, 0)      # the run walker alone
     i = _factor(cs, LC.BY_NAME["leaves"]).info()
     assert (i["levels"], i["launches"], i["run_launches"], i["level_launches"]) == (2, 2, 0, 2)        # one wave per column
+    for name, counts in (("chains4", (3, 1, 1, 0)), ("chains5", (3, 3, 0, 3))):     # the width edge: 4 columns a level, then 5
+        F = _factor(cs, LC.BY_NAME[name])
+        i = F.info()
+        assert (i["levels"], i["launches"], i["run_launches"], i["level_launches"]) == counts, name
+        _is_reference(cs, F, LC.BY_NAME[name], "A")
     for name in ("grid24-shift", "dups"):
         i = _factor(cs, LC.BY_NAME[name]).info()
         assert i["level_launches"] >= 1 and i["run_launches"] >= 1 and i["launches"] < i["levels"]     # wide levels, narrow runs

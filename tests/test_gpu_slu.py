@@ -107,6 +107,10 @@ def test_which_kernel_ran(cs):
     assert counts("chain256") == (256, 1, 1, 0)            # the run walker alone: one launch takes RUN_LEVELS levels
     assert counts("chain257") == (257, 2, 2, 0)            # ... a longer run is several
     assert counts("blocks") == (2, 2, 0, 2)                # one wave per column: one wide level a launch
+    assert counts("chains4") == (3, 1, 1, 0)               # the width edge: 4 columns a level go to the walker ...
+    assert counts("chains5") == (3, 3, 0, 3)               # ... 5 to a wave per column
+    for name in ("chains4", "chains5"):
+        _is_reference(_factor(cs, SC.BY_NAME[name]), SC.BY_NAME[name], "A")
     for name in ("grid24-shift", "dups", "one-sided"):
         i = _factor(cs, SC.BY_NAME[name]).info()
         assert i["level_launches"] >= 1 and i["run_launches"] >= 1 and i["launches"] < i["levels"]     # wide levels, narrow runs
