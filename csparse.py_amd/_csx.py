@@ -159,6 +159,8 @@ _PROTOS = {
     "csx_chol_refactor_plan": [H, H, _i32p, C.POINTER(H)],
     "csx_chol_refactor": [H, H, C.POINTER(C.c_int), _i32p],
     "csx_chol_refactor_info": [C.POINTER(C.c_double), C.POINTER(C.c_double)],
+    "csx_chol_refactor_window": [H, C.POINTER(C.c_int32)],
+    "csx_chol_limits": [_i32p],
     "csx_lu_refactor_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p,
                              C.POINTER(C.c_int), _f64p],
     "csx_assemble_plan_host": [C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
@@ -291,6 +293,22 @@ def ldl_window():
     out = C.c_int32(0)
     check(load().csx_ldl_window(C.byref(out)), "csx_ldl_window")
     return out.value
+
+
+_CHOL_LIMITS = ("CH_ACC", "CH_NARROW", "CH_SMALL_TREE", "CD_MAX", "CC_ACC", "CC_MAP", "CC_RUN_MIN", "CC_RUN_MAX", "CC_WAVES",
+                "SN_MIN_WIDTH")
+
+
+def chol_limits():
+    """the constants the general cs_chol numeric is cut by (csx_chol.hip), asked of the library; no GPU needed: a dict of
+    CH_ACC, CH_NARROW, CH_SMALL_TREE, CD_MAX, CC_ACC, CC_MAP, CC_RUN_MIN, CC_RUN_MAX, CC_WAVES, SN_MIN_WIDTH, "windows" (the
+    five register-window widths, ascending) and "max_need" (the largest half-bandwidth + 1 a register window takes)"""
+    out = (C.c_int32 * 16)()
+    check(load().csx_chol_limits(out), "csx_chol_limits")
+    d = {name: int(out[k]) for k, name in enumerate(_CHOL_LIMITS)}
+    d["windows"] = tuple(int(out[k]) for k in range(10, 15))
+    d["max_need"] = int(out[15])
+    return d
 
 
 def slu_window():

@@ -1915,13 +1915,19 @@ def cholsol_factor(A, order=0, exact=None):
             self._rinfo = {"ok": bool(ok.value), "route": "forest" if info[0] else "general", "levels": int(info[1]),
                            "supernodes": int(info[2]), "trees": int(info[3]), "dense_trees": int(info[4]), "band": int(info[5]),
                            "first": bool(info[6]), "numeric_ms": num.value, "ms": 1e3 * (time.perf_counter() - t0)}
+            win = _csx.C.c_int32(0)
+            _csx.check(_csx.lib().csx_chol_refactor_window(self._rplan, win), "csx_chol_refactor_window")
+            self._rwindow = int(win.value)
             return bool(ok.value)
 
-        def refactor_info(self):
+        def refactor_info(self, window=False):
             """None before the first refactor; else the last one's ok, route ("general" / "forest"), levels (launches of the
             level walk), supernodes, trees, dense_trees, band (0 none, 1 register window, 2 blocked dense band), first (this
-            call made the plan's scratch), numeric_ms (HIP events around the numeric kernels) and ms (the whole call)."""
-            return dict(self._rinfo) if self._rinfo is not None else None
+            call made the plan's scratch), numeric_ms (HIP events around the numeric kernels) and ms (the whole call).
+            window=True adds "window": the register-window instance that refactor launched (48, 80, 112, 144 or 176; 0: none)."""
+            if self._rinfo is None:
+                return None
+            return dict(self._rinfo, window=self._rwindow) if window else dict(self._rinfo)
 
         def _solve_sharded(self, b, comm, nrhs):
             # every rank solves in the order the ROOT's right-hand side asks for

@@ -577,6 +577,8 @@ int chol_supernodes(const void *d_sns, int32_t nsn, int32_t max_w, int32_t max_r
                     int *notspd);
 constexpr int32_t SN_MIN_WIDTH = 8;    // narrower chains stay with the column kernels (700 x 700 grid, order 1, numeric part: 32 -> 44 ms, 16 -> 36, 8 -> 31, 4 -> 29)
 
+constexpr int CH_BAND_WINDOWS[5] = {48, 80, 112, 144, 176};   // the k_chol_band<BW, 1024> instances: the narrowest that holds need = half-bandwidth + 1 runs
+
 struct Forest {
     std::vector<Tree> small;             // trees handled by the tree kernel
     std::vector<int32_t> small_cols;     // their columns, ascending inside a tree
@@ -664,6 +666,7 @@ struct CholAnalysis {
     int band = 0;                      // 0 none, 1 register window, 2 blocked dense band: decided ONCE, by chol_analysis_map
     int band_hb = 0, band_nb = 16;     // half-bandwidth, columns per step of the blocked band
     int32_t run_launches = 0;          // launches of the level walk of the last run
+    int32_t window = 0;                // the k_chol_band instance the last run launched (its BW), 0: none
     struct Host {                      // the sources of the schedule uploads, alive until the stream has been synchronised
         std::vector<Tree> trees, dense;
         std::vector<int32_t> small_cols, level_cols, col_level, sn_cols;
@@ -841,7 +844,7 @@ static int chol_analysis_map(CholAnalysis *An, const Csc *A, const int32_t *pinv
                 An->band_nb = ctx().opt.chol_wband_nb;
             }
         }
-        if (An->band == 0 && need <= 176) An->band = 1;
+        if (An->band == 0 && need <= CH_BAND_WINDOWS[4]) An->band = 1;
     }
     return CSX_OK;
 }
@@ -860,20 +863,24 @@ static int chol_analysis_run(CholAnalysis *An, const int32_t *Lp, const int32_t 
     const std::vector<int32_t> &sn_group_at = An->sn_group_at;
     int st = CSX_OK;
     An->run_launches = 0;
+    An->window = 0;
     (void)hipMemsetD32Async((hipDeviceptr_t)(d_flags + 1), 0x7fffffff, 1, s);
     if (An->has_levels) (void)hipMemsetAsync(An->split, 0x7f, (size_t)n * sizeof(int32_t), s);   // "no inside update seen"
     st = chol_scatter(An->lnz, An->win, Ax, Lx);
     const bool banded = An->band != 0;
     if (st == CSX_OK && An->band == 2) st = chol_wide_band(n, An->band_hb, Lp, Li, Lx, d_flags + 1, An->band_nb);
 #define CSX_BAND(BWV) \
-    hipLaunchKernelGGL((k_chol_band<BWV, 1024>), dim3(1), dim3(1024), 0, s, n, Lp, Li, Lx, d_rp, d_rc, d_rpos, d_flags + 1)
+    {                      \
+        An->window = BWV;  \
+        hipLaunchKernelGGL((k_chol_band<BWV, 1024>), dim3(1), dim3(1024), 0, s, n, Lp, Li, Lx, d_rp, d_rc, d_rpos, d_flags + 1); \
+    }
     if (st == CSX_OK && An->band == 1) {
         const int need = An->band_hb + 1;
-        if (need <= 48) CSX_BAND(48);
-        else if (need <= 80) CSX_BAND(80);
-        else if (need <= 112) CSX_BAND(112);
-        else if (need <= 144) CSX_BAND(144);
-        else CSX_BAND(176);
+        if (need <= CH_BAND_WINDOWS[0]) CSX_BAND(CH_BAND_WINDOWS[0])
+        else if (need <= CH_BAND_WINDOWS[1]) CSX_BAND(CH_BAND_WINDOWS[1])
+        else if (need <= CH_BAND_WINDOWS[2]) CSX_BAND(CH_BAND_WINDOWS[2])
+        else if (need <= CH_BAND_WINDOWS[3]) CSX_BAND(CH_BAND_WINDOWS[3])
+        else CSX_BAND(CH_BAND_WINDOWS[4])
     }
 #undef CSX_BAND
     const int32_t nd = banded ? 0 : An->ndense;
@@ -1002,6 +1009,8 @@ void chol_analysis_info(const CholAnalysis *An, int32_t *info) {
     info[4] = banded ? 0 : An->ndense;
     info[5] = An->band;
 }
+
+int32_t chol_analysis_window(const CholAnalysis *An) { return An->window; }
 
 static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *pinv, Csc *L) {
     hipStream_t s = ctx().stream;
@@ -2947,6 +2956,15 @@ extern "C" int csx_cholsol_factor_info(int32_t *path, double *analysis_ms, doubl
     if (analysis_ms) *analysis_ms = g_factor_ms[0];
     if (numeric_ms) *numeric_ms = g_factor_ms[1];
     if (call_ms) *call_ms = g_factor_ms[2];
+    return CSX_OK;
+}
+
+extern "C" int csx_chol_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    const int32_t v[16] = {CH_ACC, CH_NARROW, CH_SMALL_TREE, CD_MAX, CC_ACC, CC_MAP, CC_RUN_MIN, CC_RUN_MAX, CC_WAVES, SN_MIN_WIDTH,
+                           CH_BAND_WINDOWS[0], CH_BAND_WINDOWS[1], CH_BAND_WINDOWS[2], CH_BAND_WINDOWS[3], CH_BAND_WINDOWS[4],
+                           CH_BAND_WINDOWS[4]};
+    for (int k = 0; k < 16; k++) out[k] = v[k];
     return CSX_OK;
 }
 

@@ -238,6 +238,13 @@ extern "C" int csx_chol_refactor(csx_handle_t h, csx_handle_t hA2, int *ok, int3
     return CSX_OK;
 }
 
+extern "C" int csx_chol_refactor_window(csx_handle_t h, int32_t *window) {
+    CholRefPlan *P = (CholRefPlan *)get(h, K_CHOLREFPLAN);
+    if (!P || !window) return CSX_EINVAL;
+    *window = P->An ? chol_analysis_window(P->An) : 0;
+    return CSX_OK;
+}
+
 extern "C" int csx_chol_refactor_info(double *numeric_ms, double *call_ms) {
     if (!g_rf_valid) return CSX_EINVAL;   // no csx_chol_refactor has completed yet
     if (numeric_ms) *numeric_ms = g_rf_numeric_ms;

@@ -421,6 +421,7 @@ int chol_analysis_of_factor(const Csc *A, const int32_t *pinv, const Csc *L, con
 // done (or null) is recorded after the last launch.  Synchronises.
 int chol_analysis_refactor(CholAnalysis *An, const Csc *L, const double *Ax, double *Lx, hipEvent_t done, bool *notspd);
 void chol_analysis_info(const CholAnalysis *An, int32_t *info);   // info[1..5] of csx_chol_refactor
+int32_t chol_analysis_window(const CholAnalysis *An);             // BW of the k_chol_band instance the last run launched, 0: none
 // Lx[q] = win[q] >= 0 ? Ax[win[q]] : 0 over the lnz slots of L (csx_chol_refactor.hip)
 int chol_scatter(int64_t lnz, const int32_t *win, const double *Ax, double *Lx);
 // csx_chol.hip: the entry map alone (k_chol_winner): win[q] = the entry of A that lands in slot q of L, -1 for fill; *bad

@@ -734,10 +734,21 @@ int csx_lu_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, double *ratio, 
  *   the level walk; [2] supernodes; [3] small trees given to the tree kernel; [4] dense trees; [5] band kernel: 0 none,
  *   1 register window, 2 blocked dense band; [6] 1 when this call made the plan's scratch arrays; [7] 0.
  * csx_chol_refactor_info: the last csx_chol_refactor that ran: HIP-event time from the scatter of the values to the last
- *   launch, and the host clock over the whole call, pattern check and commit included.  CSX_EINVAL before the first. */
+ *   launch, and the host clock over the whole call, pattern check and commit included.  CSX_EINVAL before the first.
+ * csx_chol_refactor_window: the register-window instance (k_chol_band's BW: 48, 80, 112, 144 or 176) that the plan's last
+ *   csx_chol_refactor launched, written down at the launch itself; 0 when it launched none (another band kind, the column
+ *   kernels, the forest route, no refactor yet).  Reads host state only.
+ * csx_chol_limits: the constants the general numeric path is cut by, without a device: out[16] = CH_ACC (entries of a column
+ *   a wave of the column kernels keeps in LDS), CH_NARROW (columns of a level up to which a workgroup takes each), CH_SMALL_TREE
+ *   (columns of a tree up to which the tree kernels take it), CD_MAX (columns of a dense tree), CC_ACC (doubles of partial
+ *   columns in the cooperative kernel), CC_MAP (n up to which it keeps a row map in LDS), CC_RUN_MIN, CC_RUN_MAX (narrow levels
+ *   of a two-phase run), CC_WAVES, SN_MIN_WIDTH, the five register-window widths ascending, the largest need (half-bandwidth
+ *   + 1) a register window takes. */
 int csx_chol_refactor_plan(csx_handle_t A, csx_handle_t L, const int32_t *pinv, csx_handle_t *plan);
 int csx_chol_refactor(csx_handle_t plan, csx_handle_t A2, int *ok, int32_t *info);
 int csx_chol_refactor_info(double *numeric_ms, double *call_ms);
+int csx_chol_refactor_window(csx_handle_t plan, int32_t *window);
+int csx_chol_limits(int32_t *out);
 
 /* ---- assembly plan: new triplet values into a fixed CSC pattern (assembly_plan) --------------------
  * Definition.  Given the triplets (Ti[k], Tj[k]), k = 0 .. nz-1, of an m-by-n matrix, let C = cs_dupl(cs_compress(T)) as the

@@ -20,6 +20,13 @@ X_RTOL = 1e-10           # BASELINE.json north_star
 # on the near side of the growth guard (4423.03, case bwd513; profiles/snsolve_edges.jsonl has every case).  The results
 # are the same bits on every run, so the factor of 8 covers other seeds and a legitimate regrouping of the sums, not noise.
 SN_EPS_UNITS = 8 * 4423.03
+# The general cs_chol numeric against the oracle on the constructed cases of tests/chol_cases.py, as the largest
+# |l_ij - ref_ij| / (EPS * terms_ij) with chol_terms' terms.  NOT taken from the device: 4 x the plain-C oracle's own distance,
+# in the same units, from a factorisation of the same matrices in numpy.longdouble, largest over the rounding-route cases
+# (738.22, case band176-no-window, second value set; tools/measure_chol_edges.py writes every case to profiles/chol_edges.jsonl).  Two
+# results within K of the exact factor differ by at most 2 K; the other factor of 2 is for a regrouping into up to 16 partial
+# sums that is less lucky than the reference's order.
+CHOL_EPS_UNITS = 4 * 738.22
 
 
 def componentwise(v, ref, terms=None):
@@ -75,3 +82,27 @@ def cholsolve_terms(n, Lp, Li, Lx, y, x):
     d = L.diagonal()
     S = abs(L - sp.diags(d))
     return (np.abs(y) + S.T @ np.abs(x)) / np.abs(d)
+
+
+def chol_update_sums(n, Lp, Li, Lx):
+    """sum over k < j of |l_ik l_jk| for every slot (i, j) of L (diagonal first, rows ascending)"""
+    Lp, Li, Lx = np.asarray(Lp), np.asarray(Li), np.asarray(Lx, float)
+    cols = np.repeat(np.arange(n), np.diff(Lp))
+    off = Li != cols
+    B = sp.csr_matrix((np.abs(Lx[off]), (Li[off], cols[off])), shape=(n, n))
+    P = (B @ B.T).tocsc()
+    P.sort_indices()
+    keys = cols.astype(np.int64) * n + Li
+    pk = np.repeat(np.arange(n, dtype=np.int64), np.diff(P.indptr)) * n + P.indices
+    if len(pk) == 0:
+        return np.zeros(len(keys))
+    at = np.minimum(np.searchsorted(pk, keys), len(pk) - 1)
+    return np.where(pk[at] == keys, P.data[at], 0.0)
+
+
+def chol_terms(n, Lp, Li, Lx, absA):
+    """sum|terms| of every entry of a Cholesky factor: l_ij = (a_ij - sum_{k<j} l_ik l_jk) / l_jj (the diagonal: the square
+    root of the same sum), so terms_ij = (|a_ij| + sum_k |l_ik l_jk|) / l_jj.  absA: |a_ij| on the slots of L, 0 for fill."""
+    Lp, Lx = np.asarray(Lp), np.asarray(Lx, float)
+    ljj = np.repeat(Lx[Lp[:-1]], np.diff(Lp))
+    return (np.asarray(absA, float) + chol_update_sums(n, Lp, Li, Lx)) / ljj
