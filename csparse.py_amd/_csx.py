@@ -86,6 +86,11 @@ _PROTOS = {
     "csx_cholsol_solve_list": [H, _f64p, C.POINTER(C.c_int)],
     "csx_tri_order_info": [H, _i32p, _f64p],
     "csx_tri_components": [H, _i32p],
+    "csx_tri_limits": [_i32p],
+    "csx_tri_route_info": [H, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _i32p],
+    "csx_tri_launches": [H, C.POINTER(C.c_int64), C.c_int32, _i32p],
+    "csx_cholsol_tri_route_info": [H, C.c_int, C.c_int32, C.POINTER(C.c_int64), C.c_int32, _i32p],
+    "csx_cholsol_tri_launches": [H, C.c_int, C.POINTER(C.c_int64), C.c_int32, _i32p],
     "csx_permute_vec": [H, H, H, C.c_int32, C.c_int32, C.c_int],
     "csx_lusol_solve": [H, H, H, H, H, H, C.c_int32, C.POINTER(C.c_int)],
     "csx_lusol_solve_trans": [H, H, H, H, H, H, C.c_int32, C.POINTER(C.c_int)],
@@ -371,6 +376,57 @@ def cholsol_sn_launches(plan):
     k = len(SN_LAUNCHES)
     assert len(v) == 2 * k
     return {"fwd": dict(zip(SN_LAUNCHES, v[:k])), "bwd": dict(zip(SN_LAUNCHES, v[k:]))}
+
+
+TRI_LIMITS = ("NARROW", "CHB", "CH_SUF", "TRW_MIN_ROW", "TRW_MAX_RHS", "TR64_MIN_RHS", "TR64_RUN", "TR64_RUN_MIN", "TC_MAX_N",
+              "TC_THREADS", "COMP_MIN_COUNT", "COMP_MAX_ROWS", "PUSH_MAX_RHS", "FEW_MAX_RHS", "FEW_CPW", "COMP_LDS_MAX", "FEW_TILE_LDS",
+              "WINDOW_LDS_MAX", "COLUMNS_LDS_MAX", "CHAIN_LINKS_NUM", "CHAIN_LINKS_DEN", "CHAIN_LEVELS_NUM", "WCOL_WIDE_ENTRIES",
+              "WCHAIN_WIDE_ENTRIES", "WINDOW_SLACK", "STRIP_SHORT_COLS", "TL_WAVES_MAX", "LV_MAX_ROUNDS", "LV_DEVICE_MIN_TERMS",
+              "LAUNCH_COUNTERS")
+TRI_ROUTES = ("Ragged", "CompPush", "FewLds", "Few", "Local", "WColumns", "WColChain", "Columns", "ColChain", "Sequential", "Levels")
+TRI_ROUTE_INFO = ("route", "lds", "grid", "G", "waves", "tile_rows", "chunks", "window", "threads", "rounds", "mate",
+                  "band", "links", "col_state", "levels", "sequential", "chain_ok", "ncomp", "comp_max", "push_terms", "few_cpw",
+                  "few_rows", "few_terms", "guard", "schedule", "comps_found", "comp_rows_found", "kind", "n", "terms")
+TRI_LAUNCHES = ("level", "levels_one_wg", "chain", "sequential", "local_fwd", "local_bwd", "few_fwd", "few_bwd", "few_lds_fwd",
+                "few_lds_bwd", "push_fwd", "push_bwd", "ragged", "columns_l", "columns_u", "colchain_lt", "colchain_ut",
+                "wcolumns_256", "wcolumns_1024", "wcolchain_lt_2", "wcolchain_lt_12", "wcolchain_ut_2", "wcolchain_ut_12",
+                "level_rows", "run_prefix_rows", "levels_rows_one_wg", "level_rows64", "run_prefix64", "levels_rows64_one_wg",
+                "level_of")
+
+
+def tri_limits():
+    """the constants the triangular solve's routes are cut by (csx_trisolve.hip), asked of the library; no GPU needed: a dict by
+    the names of TRI_LIMITS (include/csx.h: csx_tri_limits)"""
+    out = (C.c_int32 * 32)()
+    check(load().csx_tri_limits(out), "csx_tri_limits")
+    return {name: int(out[k]) for k, name in enumerate(TRI_LIMITS)}
+
+
+def tri_route_info(plan, nrhs, cholsol=None):
+    """csx_tri_route_info as a dict by TRI_ROUTE_INFO, "route" as its name in TRI_ROUTES: what a solve of nrhs right-hand sides
+    on this plan would run and what decided it; cholsol = 0 / 1: plan is a cholsol plan, asked about its forward / backward
+    triangular plan (csx_cholsol_tri_route_info)"""
+    if cholsol is None:
+        v = _sn_fields(lambda h, out, cap, n: lib().csx_tri_route_info(h, nrhs, out, cap, n), plan, "csx_tri_route_info")
+    else:
+        v = _sn_fields(lambda h, out, cap, n: lib().csx_cholsol_tri_route_info(h, cholsol, nrhs, out, cap, n), plan,
+                       "csx_cholsol_tri_route_info")
+    assert len(v) == len(TRI_ROUTE_INFO)
+    d = dict(zip(TRI_ROUTE_INFO, v))
+    d["route"] = TRI_ROUTES[d["route"]]
+    return d
+
+
+def tri_launches(plan, cholsol=None):
+    """csx_tri_launches as {kernel instance: launches} by TRI_LAUNCHES, the instances the plan's last solve did not enqueue left
+    out; cholsol = 0 / 1: of the forward / backward triangular plan of a cholsol plan (csx_cholsol_tri_launches)"""
+    if cholsol is None:
+        v = _sn_fields(lib().csx_tri_launches, plan, "csx_tri_launches")
+    else:
+        v = _sn_fields(lambda h, out, cap, n: lib().csx_cholsol_tri_launches(h, cholsol, out, cap, n), plan,
+                       "csx_cholsol_tri_launches")
+    assert len(v) == len(TRI_LAUNCHES)
+    return {k: c for k, c in zip(TRI_LAUNCHES, v) if c}
 
 
 def exported_symbols():

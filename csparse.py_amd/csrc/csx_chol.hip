@@ -3044,6 +3044,31 @@ extern "C" int csx_cholsol_sn_launches(csx_handle_t h, int64_t *out, int32_t cap
     return CSX_OK;
 }
 
+// csx_tri_route_info / csx_tri_launches of the two triangular plans inside a cholsol plan (backward = 0: L x = b, 1: L' x = b), in
+// the order the plan solves in; CSX_EINVAL when the plan has none (forests of cliques solve without them)
+static int cholsol_tri_plan(csx_handle_t h, int backward, CholPlan **P, TriPlan **T) {
+    *P = (CholPlan *)get(h, K_CHOLPLAN);
+    if (!*P) return CSX_EINVAL;
+    if (cholsol_route(*P) == CholRoute::Full) CSX_TRY(cholsol_full(P));
+    *T = backward ? (*P)->bwd : (*P)->fwd;
+    return *T ? CSX_OK : CSX_EINVAL;
+}
+
+extern "C" int csx_cholsol_tri_route_info(csx_handle_t h, int backward, int32_t nrhs, int64_t *out, int32_t cap, int32_t *count) {
+    CSX_TRY(require_ready());
+    CholPlan *P = nullptr;
+    TriPlan *T = nullptr;
+    CSX_TRY(cholsol_tri_plan(h, backward, &P, &T));
+    return tri_route_info_raw(T, nrhs, P->relaxed, out, cap, count);
+}
+
+extern "C" int csx_cholsol_tri_launches(csx_handle_t h, int backward, int64_t *out, int32_t cap, int32_t *count) {
+    CholPlan *P = nullptr;
+    TriPlan *T = nullptr;
+    CSX_TRY(cholsol_tri_plan(h, backward, &P, &T));
+    return tri_launches_raw(T, out, cap, count);
+}
+
 // "tri.host_chains" (opt-in): the solve phase of cs_cholsol (csparse.py:640-643) for ONE host right-hand side when L is a chain:
 // x = P b, L \ x, L' \ x, b = P' x with the reference's loops on the host (csx_tri_solve_list's rule, applied to both sweeps)
 extern "C" int csx_cholsol_solve_list(csx_handle_t h, double *b, int *taken) {

@@ -202,6 +202,8 @@ void destroy(SnPlan *p);
 int tri_analyse_raw(const Csc *T, int kind, TriPlan **out);          // *out is set on success only
 int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed);
 int tri_solve_host_raw(TriPlan *P, double *x, bool *taken);          // "tri.host_chains"
+int tri_route_info_raw(TriPlan *P, int32_t nrhs, bool relaxed, int64_t *out, int32_t cap, int32_t *count);   // csx_tri_route_info
+int tri_launches_raw(const TriPlan *P, int64_t *out, int32_t cap, int32_t *count);                            // csx_tri_launches
 void tri_set_mate(TriPlan *P, TriPlan *mate);
 void tri_set_level_hint(TriPlan *P, std::vector<int32_t> &&level);
 void tri_gather_arrays(const TriPlan *P, const int32_t **ptr, const int32_t **idx, const double **val, const double **diag);

@@ -59,6 +59,10 @@ __global__ __launch_bounds__(256) void k_rag_desc(const int32_t *__restrict__ li
     desc[q] = make_int4(tr.first, tr.count, base, t);
 }
 
+// The guard's maximum.  fmax returns the operand that is a number when the other is a NaN, so a NaN in a diagonal tile used to
+// leave the measure and the guard passed (tests/test_gpu_tri_edges.py, case rag_nan); here a NaN stays.
+__device__ __forceinline__ double guard_max(double a, double b) { return (a != a || b != b) ? a + b : fmax(a, b); }
+
 // one wave per component: the dense position-order matrix in LDS, the inverses of its diagonal tiles, the fragments, the guard
 template <int NB>
 __global__ __launch_bounds__(64) void k_rag_frags(const int32_t *__restrict__ list, const Tree *__restrict__ trees,
@@ -115,7 +119,7 @@ __global__ __launch_bounds__(64) void k_rag_frags(const int32_t *__restrict__ li
                 for (int k = 0; k < 16; k++) s += fabs(W[b][r][k]) * fabs(M[16 * b + k][16 * b + 4 * cg + c]);
             s += __shfl_xor(s, 16, 64);
             s += __shfl_xor(s, 32, 64);
-            wmax = fmax(wmax, s);
+            wmax = guard_max(wmax, s);
         }
     }
     const int m = lane & 15, kq = lane >> 4;
@@ -127,7 +131,7 @@ __global__ __launch_bounds__(64) void k_rag_frags(const int32_t *__restrict__ li
         for (int sx = 0; sx < 4; sx++) F[64 * f++] = W[i][m][4 * sx + kq];
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, d, 64));
+    for (int d = 32; d > 0; d >>= 1) wmax = guard_max(wmax, __shfl_xor(wmax, d, 64));
     if (lane == 0) {
         // (a NaN must raise the flag too: its bits are above every finite number's)
         const unsigned long long bits = (unsigned long long)__double_as_longlong(wmax != wmax ? __longlong_as_double(0x7ff8000000000000ll) : wmax);
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(64) void k_rag_frags_csc(const int32_t *__restrict_
                 for (int k = 0; k < 16; k++) s += fabs(W[b][r][k]) * fabs(M[16 * b + k][16 * b + 4 * cg + c]);
             s += __shfl_xor(s, 16, 64);
             s += __shfl_xor(s, 32, 64);
-            wmax = fmax(wmax, s);
+            wmax = guard_max(wmax, s);
         }
     }
     const int m = lane & 15, kq = lane >> 4;
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(64) void k_rag_frags_csc(const int32_t *__restrict_
         for (int sx = 0; sx < 4; sx++) F[64 * f++] = W[i][m][4 * sx + kq];
     }
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) wmax = fmax(wmax, __shfl_xor(wmax, d, 64));
+    for (int d = 32; d > 0; d >>= 1) wmax = guard_max(wmax, __shfl_xor(wmax, d, 64));
     if (lane == 0) {
         const unsigned long long bits = (unsigned long long)__double_as_longlong(wmax != wmax ? __longlong_as_double(0x7ff8000000000000ll) : wmax);
         if (!(bits <= *(volatile unsigned long long *)cond_bits)) atomicMax(cond_bits, bits);

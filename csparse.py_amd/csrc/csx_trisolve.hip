@@ -45,6 +45,16 @@ struct Segment {
     bool one_wg;
 };
 
+// the solve-kernel instances a plan can enqueue, in the order csx_tri_launches reports them (include/csx.h)
+enum TriLaunch {
+    TKL_LEVEL, TKL_LEVELS_ONE_WG, TKL_CHAIN, TKL_SEQUENTIAL,
+    TKL_LOCAL_FWD, TKL_LOCAL_BWD, TKL_FEW_FWD, TKL_FEW_BWD, TKL_FEW_LDS_FWD, TKL_FEW_LDS_BWD, TKL_PUSH_FWD, TKL_PUSH_BWD, TKL_RAGGED,
+    TKL_COLUMNS_L, TKL_COLUMNS_U, TKL_COLCHAIN_LT, TKL_COLCHAIN_UT,
+    TKL_WCOLUMNS_256, TKL_WCOLUMNS_1024, TKL_WCOLCHAIN_LT_2, TKL_WCOLCHAIN_LT_12, TKL_WCOLCHAIN_UT_2, TKL_WCOLCHAIN_UT_12,
+    TKL_LEVEL_ROWS, TKL_PREFIX_ROWS, TKL_ROWS_ONE_WG, TKL_LEVEL_ROWS64, TKL_PREFIX64, TKL_ROWS64_ONE_WG, TKL_LEVEL_OF,
+    TKL_COUNT
+};
+
 struct TriPlan {
     int kind = 0;
     int32_t n = 0, nlevels = 0;
@@ -98,6 +108,12 @@ struct TriPlan {
     bool rounding_equal = false, rag_tried = false;
     std::unique_ptr<RaggedMfma> rag;
     double rag_growth = 0.0;
+    // read-backs for the tests (host state only): kernels the last solve enqueued by TriLaunch (csx_tri_launches); where the level
+    // schedule came from (0: none yet, 1: the caller's hint, 2: the device pass, 3: the host pass, 4: the host pass after the
+    // device pass gave up at LV_MAX_ROUNDS); what analyse_components found whether or not it kept it (csx_tri_route_info)
+    int64_t launches[TKL_COUNT] = {};
+    int sched_source = 0;
+    int32_t comps_found = 0, comp_rows_found = 0;
 };
 
 void destroy(TriPlan *t) { delete t; }
@@ -1560,6 +1576,19 @@ __global__ __launch_bounds__(256) void k_adjacent_equal(int32_t n, const int32_t
 
 constexpr int COMP_MAX_ROWS = 256;    // X tile of one component: rows x 64 lanes x 8 B <= 128 KiB of LDS
 constexpr int COMP_MIN_COUNT = 64;    // fewer components than this: level scheduling fills the chip better
+// the cuts of tri_route and analyse (csx_tri_limits hands them to the tests, so that no test repeats a number)
+constexpr int PUSH_MAX_RHS = 8, FEW_MAX_RHS = 32;  // right-hand sides of CompPush; of FewLds and Few
+constexpr int FEW_CPW = 4;                         // components per wave of FewLds
+constexpr size_t COMP_LDS_MAX = 120 * 1024;        // CompPush, FewLds: dynamic LDS of a workgroup
+constexpr size_t FEW_TILE_LDS = 128 * 1024;        // Few: the X tiles of a workgroup's waves
+constexpr size_t WINDOW_LDS_MAX = 128 * 1024;      // WColumns, WColChain: the window of x
+constexpr size_t COLUMNS_LDS_MAX = 150 * 1024;     // Columns, ColChain: x of one right-hand side
+constexpr int CHAIN_LINKS_NUM = 12, CHAIN_LINKS_DEN = 11;   // a chain by its links: links * 12 > n * 11
+constexpr int CHAIN_LEVELS_NUM = 12;               // a chain by its levels: nlevels * 12 > n
+constexpr int WCOL_WIDE_ENTRIES = 192;             // k_tri_wcolumns<1024> above so many entries a column on average
+constexpr int WCHAIN_WIDE_ENTRIES = 160;           // k_tri_wcolchain<., 12> above so many
+constexpr int WINDOW_SLACK = 4;                    // the window holds band + 4 entries of x at least
+constexpr int STRIP_SHORT_COLS = 8;                // analyse: k_strip_first<4> below so many entries a column on average, <64> from there
 
 // ---- which kernels a solve launches -------------------------------------------------------------------------------------------
 // tri_route picks the route from the plan, the number of right-hand sides, the order and the options; tri_launch runs what it says.
@@ -1647,6 +1676,8 @@ static int analyse_components(TriPlan *P) {
     CSX_TRY(comp_of_pos.alloc((size_t)n));
     CSX_TRY(group_by_root(n, root, srow, comp_of_pos, &P->comps, &ncomp, &maxc));
     const Tree *comps = P->comps;
+    P->comps_found = ncomp;
+    P->comp_rows_found = maxc;
     if (ncomp < COMP_MIN_COUNT || maxc > COMP_MAX_ROWS) return CSX_OK;
     const unsigned nbw = (unsigned)(((int64_t)n + 3) / 4);
     int hflags[4] = {maxc, 0, 0, 0};
@@ -1691,7 +1722,7 @@ static int analyse_components(TriPlan *P) {
             P->push_terms = hmax > 0 ? hmax : 1;
         }
     }
-    for (int cpw : {4}) {   // LDS need of the all-in-LDS kernel: 12 B per term, (12 + 8 G) B per row, G = 64 / cpw = 16
+    for (int cpw : {FEW_CPW}) {   // LDS need of the all-in-LDS kernel: 12 B per term, (12 + 8 G) B per row, G = 64 / cpw = 16
         int hcaps[2] = {0, 0};
         CSX_HIP(hipMemsetAsync(flags, 0, 4 * sizeof(int), s));
         const int64_t groups = (ncomp + cpw - 1) / cpw;
@@ -1700,7 +1731,7 @@ static int analyse_components(TriPlan *P) {
         CSX_HIP(hipMemcpyAsync(hcaps, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
         CSX_HIP(hipStreamSynchronize(s));
         const size_t need = few_lds_bytes(hcaps[0], hcaps[1], 64 / cpw);
-        if (need <= 120 * 1024) {
+        if (need <= COMP_LDS_MAX) {
             P->few_cpw = cpw;
             P->few_rows = hcaps[0];
             P->few_terms = hcaps[1];
@@ -1740,16 +1771,21 @@ static int sweep_local(TriPlan *P, const TriRouting &R, const double *src, doubl
 // the component sweeps, one launch per route
 static int sweep_components(TriPlan *P, const TriRouting &R, double *X, int32_t nrhs) {
     switch (R.route) {
-        case TriRoute::Ragged: return ragged_solve(P->rag.get(), P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
+        case TriRoute::Ragged:
+            P->launches[TKL_RAGGED]++;
+            return ragged_solve(P->rag.get(), P->comp_nodes, nullptr, !P->forward, 1, X, nrhs, P->n);
         case TriRoute::CompPush:
+            P->launches[P->forward ? TKL_PUSH_FWD : TKL_PUSH_BWD]++;
             return launch_lds(P->forward ? k_tri_comp_push<true> : k_tri_comp_push<false>, 160 * 1024 - 256, dim3(R.grid), dim3(64),
                               R.lds, P->comps, P->ncomp, P->comp_nodes, P->cptr, P->cidx, P->cval, P->cdiag, X, nrhs, R.G, P->comp_max,
                               P->push_terms);
         case TriRoute::FewLds:
+            P->launches[P->forward ? TKL_FEW_LDS_FWD : TKL_FEW_LDS_BWD]++;
             return launch_lds(P->forward ? k_tri_few_lds<true, 4> : k_tri_few_lds<false, 4>, 160 * 1024 - 256, dim3(R.grid), dim3(64),
                               R.lds, P->comps, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs,
                               P->few_rows, P->few_terms);
         case TriRoute::Few:
+            P->launches[P->forward ? TKL_FEW_FWD : TKL_FEW_BWD]++;
             return launch_lds(P->forward ? k_tri_few<true> : k_tri_few<false>, 160 * 1024 - 256, dim3(R.grid), dim3(256), R.lds,
                               P->comps, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, X, nrhs, R.G,
                               R.tile_rows, R.waves);
@@ -1760,6 +1796,7 @@ static int sweep_components(TriPlan *P, const TriRouting &R, double *X, int32_t 
 
 static int sweep_local(TriPlan *P, const TriRouting &R, const double *src, double *dst, const int32_t *load_rows,
                        const int32_t *store_rows, int32_t nrhs) {
+    P->launches[P->forward ? TKL_LOCAL_FWD : TKL_LOCAL_BWD]++;
     return launch_lds(P->forward ? k_tri_local<true> : k_tri_local<false>, 160 * 1024 - 256, dim3(R.grid), dim3(64 * R.waves), R.lds,
                       P->comps_by_size, P->ncomp, P->comp_nodes, P->prog_ptr, P->prog_idx, P->prog_val, P->prog_diag, src, dst,
                       load_rows, store_rows, nrhs, R.chunks, P->comp_max, R.waves);
@@ -1828,7 +1865,7 @@ static int analyse(const Csc *T, int kind, TriPlan **out) {
             CSX_TRY(dalloc(&S.i, (size_t)S.nnz));
             CSX_TRY(dalloc(&S.x, (size_t)S.nnz));
             int64_t blocks = std::min<int64_t>(((int64_t)n + 4) / 4, 65536);
-            const bool short_cols = (int64_t)T->nnz < 8 * (int64_t)n;
+            const bool short_cols = (int64_t)T->nnz < STRIP_SHORT_COLS * (int64_t)n;
             if (kind == CSX_TRI_L && short_cols)
                 hipLaunchKernelGGL(k_strip_first<4>, dim3((unsigned)std::min<int64_t>(((int64_t)n + 64) / 64, 65536)), dim3(256), 0, s, n,
                                    T->p, T->i, T->x, S.p, S.i, S.x, P->diag);
@@ -2088,14 +2125,18 @@ static int ensure_schedule(TriPlan *P) {
     if (!P->level_hint.empty() && where != 1) {
         bool done = false;
         CSX_TRY(schedule_from_hint(P, &done));
+        if (done) P->sched_source = 1;
         if (done) return CSX_OK;
     }
     if (where == 2 || (where == 0 && (int64_t)P->gnnz >= LV_DEVICE_MIN_TERMS)) {
         bool done = false;
         CSX_TRY(schedule_on_device(P, &done));
+        if (done) P->sched_source = 2;
         if (done) return CSX_OK;
         P->order.reset();          // gave up part way (deeper than LV_MAX_ROUNDS): start over on the host
+        P->sched_source = 4;
     }
+    if (P->sched_source != 4) P->sched_source = 3;
     std::vector<int32_t> hptr, hidx;
     CSX_TRY(download_i32(hptr, P->ptr, (size_t)n + 1));
     CSX_TRY(download_i32(hidx, P->idx, (size_t)P->gnnz));
@@ -2207,26 +2248,26 @@ static int tri_route(TriPlan *P, int32_t nrhs, bool relaxed, TriRouting *R) {
         while (R->G < nrhs) R->G <<= 1;
         // L, U with up to 8 right-hand sides: one wave per component, column-push form (W, L + U pair: 43 us at 1 RHS,
         // 78 us at 8; at 64 the entry-parallel lanes are gone and it loses to k_tri_local, 483 against 272 us)
-        if (nrhs <= 8 && P->push_terms > 0 && opt.tri_push) {
+        if (nrhs <= PUSH_MAX_RHS && P->push_terms > 0 && opt.tri_push) {
             R->lds = (size_t)P->push_terms * 16 + (size_t)P->comp_max * (16 + 8 * (size_t)R->G) + 64;
-            if (R->lds <= 120 * 1024) {
+            if (R->lds <= COMP_LDS_MAX) {
                 R->route = TriRoute::CompPush;
                 R->grid = (unsigned)P->ncomp;
                 return CSX_OK;
             }
         }
-        if (nrhs <= 32 && P->few_cpw) {   // lanes = (component, right-hand side) pairs, programs and X in LDS
+        if (nrhs <= FEW_MAX_RHS && P->few_cpw) {   // lanes = (component, right-hand side) pairs, programs and X in LDS
             R->route = TriRoute::FewLds;
             R->lds = few_lds_bytes(P->few_rows, P->few_terms, 64 / P->few_cpw);
             R->grid = (unsigned)((P->ncomp + P->few_cpw - 1) / P->few_cpw);
             return CSX_OK;
         }
-        if (nrhs <= 32) {   // the same with the programs read from memory (components too big for the LDS copy)
+        if (nrhs <= FEW_MAX_RHS) {   // the same with the programs read from memory (components too big for the LDS copy)
             const int cpw = 64 / R->G;
             R->route = TriRoute::Few;
             R->tile_rows = P->comp_max | 1;
             const size_t per_wave = (size_t)64 * R->tile_rows * sizeof(double);
-            R->waves = std::max(1, (int)std::min<size_t>(4, (128 * 1024) / per_wave));
+            R->waves = std::max(1, (int)std::min<size_t>(4, FEW_TILE_LDS / per_wave));
             const int64_t waves_needed = ((int64_t)P->ncomp + cpw - 1) / cpw;
             R->lds = per_wave * R->waves;
             R->grid = (unsigned)((waves_needed + R->waves - 1) / R->waves);
@@ -2247,10 +2288,10 @@ static int tri_route(TriPlan *P, int32_t nrhs, bool relaxed, TriRouting *R) {
     const bool small = P->n <= TC_MAX_N;    // x of one right-hand side fits LDS; above, only the window kernels apply
     if (opt.tri_columns) {
         CSX_TRY(measure_band(P));
-        chain = P->band != 0x7fffffff && (int64_t)P->links * 12 > (int64_t)P->n * 11;
+        chain = P->band != 0x7fffffff && (int64_t)P->links * CHAIN_LINKS_NUM > (int64_t)P->n * CHAIN_LINKS_DEN;
         uint32_t Wn = 64;
-        while (chain && (int64_t)Wn < (int64_t)P->band + 4 && Wn < (1u << 20)) Wn <<= 1;
-        if (chain && (size_t)Wn * sizeof(double) <= 128 * 1024) {
+        while (chain && (int64_t)Wn < (int64_t)P->band + WINDOW_SLACK && Wn < (1u << 20)) Wn <<= 1;
+        if (chain && (size_t)Wn * sizeof(double) <= WINDOW_LDS_MAX) {
             const TriPlan *M = P->mate;
             // rounding-equal order, L' (any size): the rows of L (the mate's gather arrays) pushed as the columns of L'
             R->mate = !push && relaxed && P->kind == CSX_TRI_LT && M && M->kind == CSX_TRI_L && M->own_ptr && M->col_state == 1 &&
@@ -2259,12 +2300,12 @@ static int tri_route(TriPlan *P, int32_t nrhs, bool relaxed, TriRouting *R) {
             R->lds = (size_t)Wn * sizeof(double);
             if ((!small && push && P->col_state == 1) || R->mate) {
                 R->route = TriRoute::WColumns;
-                R->threads = (int64_t)(R->mate ? M->gnnz : P->gnnz) > (int64_t)192 * P->n ? 1024 : 256;
+                R->threads = (int64_t)(R->mate ? M->gnnz : P->gnnz) > (int64_t)WCOL_WIDE_ENTRIES * P->n ? 1024 : 256;
                 return CSX_OK;
             }
             if (!small && !push) {
                 R->route = TriRoute::WColChain;
-                R->rounds = (int64_t)P->gnnz > (int64_t)160 * P->n ? 12 : 2;   // columns of more than two rounds on average
+                R->rounds = (int64_t)P->gnnz > (int64_t)WCHAIN_WIDE_ENTRIES * P->n ? 12 : 2;   // columns of more than two rounds on average
                 return CSX_OK;
             }
         }
@@ -2277,9 +2318,9 @@ static int tri_route(TriPlan *P, int32_t nrhs, bool relaxed, TriRouting *R) {
         }
     }
     // small and chain-like: the column loop, one wave per right-hand side, beats any schedule
-    if (opt.tri_columns && small && (chain || (int64_t)P->nlevels * 12 > P->n)) {
+    if (opt.tri_columns && small && (chain || (int64_t)P->nlevels * CHAIN_LEVELS_NUM > P->n)) {
         CSX_TRY(ensure_col_state(P));
-        if (P->col_state == 1 && ((size_t)P->n + 8) * sizeof(double) <= 150 * 1024) {
+        if (P->col_state == 1 && ((size_t)P->n + 8) * sizeof(double) <= COLUMNS_LDS_MAX) {
             R->route = push ? TriRoute::Columns : TriRoute::ColChain;
             R->lds = ((size_t)P->n + (push ? 8 : 0)) * sizeof(double);
             R->threads = push ? TC_THREADS : 64;
@@ -2298,11 +2339,19 @@ struct RowWaveKernels {   // the two wave flavours take the same arguments
     decltype(&k_tri_level_rows) level;
     decltype(&k_tri_run_prefix_rows) prefix;
     decltype(&k_tri_levels_rows_one_wg) one_wg;
+    TriLaunch level_id, prefix_id, one_wg_id;   // what csx_tri_launches counts them as
 };
 
 static int walk_levels(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
     hipStream_t s = ctx().stream;
     // the exact chain walker is already the fast one when in-block sources come last: relax only the others
+    // (k_tri_chain in the relaxed order stages at most CH_SUF in-block terms of a row and reads a remainder beyond that by the
+    // exact order's addresses, which would be the wrong terms.  It cannot get there: a row's in-block sources are earlier positions
+    // of its block of CHB = 16, at most 15 distinct ones, so nin > CH_SUF = 32 takes a gather row that names some source three
+    // times or more, i.e. a column of T with a row repeated.  The relaxed flag reaches this function from cholsol's solve alone
+    // (csx_chol.hip, on the plans of a Cholesky factor, whose columns hold every row once) and from the ablation build's
+    // experiment switch; csx_tri_solve, csx_lusol_solve and the BTF solver of the shipped library always pass false.  The tables
+    // npre / nin live on the device only, so there is nothing on the host to refuse by.)
     relaxed = relaxed && !P->chain_ok;
     make_segments(P, nrhs);
     const bool no_chain = !ctx().opt.tri_chain_walker;
@@ -2311,8 +2360,10 @@ static int walk_levels(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
     const bool by_rows = long_rows && nrhs <= TRW_MAX_RHS;
     // many right-hand sides and long rows: a wave per (row, 64 right-hand sides) (k_tri_level_rows64)
     const bool by_rows64 = long_rows && nrhs >= TR64_MIN_RHS;
-    const RowWaveKernels K = by_rows64 ? RowWaveKernels{k_tri_level_rows64, k_tri_run_prefix64, k_tri_levels_rows64_one_wg}
-                                       : RowWaveKernels{k_tri_level_rows, k_tri_run_prefix_rows, k_tri_levels_rows_one_wg};
+    const RowWaveKernels K = by_rows64 ? RowWaveKernels{k_tri_level_rows64, k_tri_run_prefix64, k_tri_levels_rows64_one_wg, TKL_LEVEL_ROWS64,
+                                                        TKL_PREFIX64, TKL_ROWS64_ONE_WG}
+                                       : RowWaveKernels{k_tri_level_rows, k_tri_run_prefix_rows, k_tri_levels_rows_one_wg, TKL_LEVEL_ROWS,
+                                                        TKL_PREFIX_ROWS, TKL_ROWS_ONE_WG};
     const int64_t waves_per_row = by_rows64 ? (nrhs + 63) / 64 : 1;
     for (const Segment &g : P->segs) {
         const int32_t first = P->level_ptr_h[(size_t)g.l0];
@@ -2322,6 +2373,7 @@ static int walk_levels(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
             if (!P->level_of && g.l1 - g.l0 >= TR64_RUN_MIN) {
                 CSX_TRY(P->level_of.alloc((size_t)P->n));
                 CSX_TRY(P->resume.alloc((size_t)P->n));
+                P->launches[TKL_LEVEL_OF]++;
                 hipLaunchKernelGGL(k_tri_level_of, dim3((unsigned)(((int64_t)P->n + 255) / 256)), dim3(256), 0, s, P->nlevels,
                                    P->level_ptr, P->order, P->n, P->level_of);
             }
@@ -2331,26 +2383,32 @@ static int walk_levels(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
                 if (two_phase) {
                     const int32_t run_first = P->level_ptr_h[(size_t)a], run_count = P->level_ptr_h[(size_t)b] - run_first;
                     const int64_t waves = (int64_t)run_count * waves_per_row;
+                    P->launches[K.prefix_id]++;
                     hipLaunchKernelGGL(K.prefix, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, run_first, run_count, a,
                                        P->level_of, P->ptr, P->idx, P->val, P->skip_first, P->skip_last, X, nrhs, P->resume);
                 }
+                P->launches[K.one_wg_id]++;
                 hipLaunchKernelGGL(K.one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, a, b, P->ptr, P->idx, P->val, P->diag,
                                    P->skip_first, P->skip_last, X, nrhs, two_phase ? P->resume : nullptr);
                 a = b;
             }
         } else if (by_rows || by_rows64) {
             const int64_t waves = (int64_t)count * waves_per_row;
+            P->launches[K.level_id]++;
             hipLaunchKernelGGL(K.level, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, P->order, first, count, P->ptr, P->idx,
                                P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         } else if (g.one_wg && !no_chain && (P->chain_ok || relaxed)) {
+            P->launches[TKL_CHAIN]++;
             hipLaunchKernelGGL(k_tri_chain, dim3(1), dim3(64 * CHB), 0, s, P->order, P->level_ptr_h[(size_t)g.l0],
                                P->level_ptr_h[(size_t)g.l1], P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last,
                                P->npre, P->nin, P->tslot, X, nrhs, relaxed ? 1 : 0);
         } else if (g.one_wg) {
+            P->launches[TKL_LEVELS_ONE_WG]++;
             hipLaunchKernelGGL(k_tri_levels_one_wg, dim3(1), dim3(1024), 0, s, P->order, P->level_ptr, g.l0, g.l1, P->ptr,
                                P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         } else {
             const int64_t threads = (int64_t)count * nrhs;
+            P->launches[TKL_LEVEL]++;
             hipLaunchKernelGGL(k_tri_level, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, P->order, first,
                                count, P->ptr, P->idx, P->val, P->diag, P->skip_first, P->skip_last, X, nrhs);
         }
@@ -2372,24 +2430,30 @@ static int tri_launch(TriPlan *P, const TriRouting &R, double *X, int32_t nrhs, 
             // the columns pushed: T's own, or (mate) the rows of L as the columns of L' -- whole, in storage order, diagonal apart
             const TriPlan *M = P->mate;
             const int own_l = !R.mate && P->kind == CSX_TRI_L, own_u = !R.mate && P->kind == CSX_TRI_U;
+            P->launches[R.threads == 1024 ? TKL_WCOLUMNS_1024 : TKL_WCOLUMNS_256]++;
             return launch_lds(R.threads == 1024 ? k_tri_wcolumns<1024> : k_tri_wcolumns<256>, 160 * 1024 - 256, per_rhs,
                               dim3(R.threads), R.lds, P->n, R.mate ? M->ptr : P->Tp, R.mate ? M->idx : P->Ti, R.mate ? M->val : P->Tx,
                               R.mate ? M->diag : P->diag, own_l, own_u, own_l, R.window - 1, X, nrhs);
         }
         case TriRoute::WColChain: {
             const bool lt = P->kind == CSX_TRI_LT;
+            P->launches[lt ? (R.rounds == 12 ? TKL_WCOLCHAIN_LT_12 : TKL_WCOLCHAIN_LT_2)
+                           : (R.rounds == 12 ? TKL_WCOLCHAIN_UT_12 : TKL_WCOLCHAIN_UT_2)]++;
             return launch_lds(lt ? (R.rounds == 12 ? k_tri_wcolchain<CSX_TRI_LT, 12> : k_tri_wcolchain<CSX_TRI_LT, 2>)
                                  : (R.rounds == 12 ? k_tri_wcolchain<CSX_TRI_UT, 12> : k_tri_wcolchain<CSX_TRI_UT, 2>),
                               160 * 1024 - 1024, per_rhs, dim3(64), R.lds, P->n, P->Tp, P->Ti, P->Tx, R.window - 1, X, nrhs);
         }
         case TriRoute::Columns:
         case TriRoute::ColChain:
+            P->launches[P->kind == CSX_TRI_L ? TKL_COLUMNS_L : P->kind == CSX_TRI_U ? TKL_COLUMNS_U
+                        : P->kind == CSX_TRI_LT ? TKL_COLCHAIN_LT : TKL_COLCHAIN_UT]++;
             return launch_lds(P->kind == CSX_TRI_L || P->kind == CSX_TRI_LT
                                   ? (P->kind == CSX_TRI_L ? k_tri_columns<CSX_TRI_L> : k_tri_colchain<CSX_TRI_LT>)
                                   : (P->kind == CSX_TRI_U ? k_tri_columns<CSX_TRI_U> : k_tri_colchain<CSX_TRI_UT>),
                               R.route == TriRoute::Columns ? 160 * 1024 - 256 : 160 * 1024 - 1024, per_rhs, dim3(R.threads), R.lds, P->n,
                               P->Tp, P->Ti, P->Tx, X, nrhs);
         case TriRoute::Sequential:
+            P->launches[TKL_SEQUENTIAL]++;
             hipLaunchKernelGGL(k_tri_sequential, dim3((unsigned)((nrhs + 63) / 64)), dim3(64), 0, ctx().stream, P->kind, P->n, P->Tp,
                                P->Ti, P->Tx, X, nrhs);
             CSX_LAUNCH_CHECK();
@@ -2404,6 +2468,7 @@ int tri_solve_raw(TriPlan *P, double *X, int32_t nrhs, bool relaxed) {
     if (P->n == 0 || nrhs == 0) return CSX_OK;
     TriRouting R;
     CSX_TRY(tri_route(P, nrhs, relaxed, &R));
+    std::fill(P->launches, P->launches + TKL_COUNT, (int64_t)0);
     return tri_launch(P, R, X, nrhs, relaxed);
 }
 
@@ -2455,6 +2520,55 @@ extern "C" int csx_tri_components(csx_handle_t h, int32_t *ncomp) {
     if (!P || !ncomp) return CSX_EINVAL;
     *ncomp = P->comp_ok ? P->ncomp : 0;
     return CSX_OK;
+}
+
+// ---- read-backs for the tests (include/csx.h has the field lists) ---------------------------------------------------------------
+extern "C" int csx_tri_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    const int32_t v[32] = {NARROW, CHB, CH_SUF, TRW_MIN_ROW, TRW_MAX_RHS, TR64_MIN_RHS, TR64_RUN, TR64_RUN_MIN, TC_MAX_N, TC_THREADS,
+                           COMP_MIN_COUNT, COMP_MAX_ROWS, PUSH_MAX_RHS, FEW_MAX_RHS, FEW_CPW, (int32_t)COMP_LDS_MAX,
+                           (int32_t)FEW_TILE_LDS, (int32_t)WINDOW_LDS_MAX, (int32_t)COLUMNS_LDS_MAX, CHAIN_LINKS_NUM, CHAIN_LINKS_DEN,
+                           CHAIN_LEVELS_NUM, WCOL_WIDE_ENTRIES, WCHAIN_WIDE_ENTRIES, WINDOW_SLACK, STRIP_SHORT_COLS, TL_WAVES_MAX,
+                           LV_MAX_ROUNDS, (int32_t)LV_DEVICE_MIN_TERMS, TKL_COUNT, 0, 0};
+    for (int k = 0; k < 32; k++) out[k] = v[k];
+    return CSX_OK;
+}
+
+// what a solve of nrhs right-hand sides would run and what decided it: tri_route as the solve calls it (the plan's lazy analyses
+// run as far as the decision needs them; no solve kernel is launched)
+namespace csx {
+int tri_route_info_raw(TriPlan *P, int32_t nrhs, bool relaxed, int64_t *out, int32_t cap, int32_t *count) {
+    if (!P || !count || nrhs < 1 || cap < 0 || (cap > 0 && !out)) return CSX_EINVAL;
+    TriRouting R;
+    if (P->n > 0) CSX_TRY(tri_route(P, nrhs, relaxed, &R));
+    const int guard = !P->rag_tried ? 0 : P->rag ? 1 : P->rag_growth != P->rag_growth ? 3 : 2;
+    const int64_t v[] = {(int64_t)R.route, (int64_t)R.lds, (int64_t)R.grid, R.G, R.waves, R.tile_rows, R.chunks, (int64_t)R.window,
+                         R.threads, R.rounds, R.mate ? 1 : 0,
+                         P->band, P->links, P->col_state, P->scheduled ? P->nlevels : 0, P->sequential ? 1 : 0, P->chain_ok ? 1 : 0,
+                         P->comp_ok ? P->ncomp : 0, P->comp_ok ? P->comp_max : 0, P->push_terms, P->few_cpw, P->few_rows, P->few_terms,
+                         guard, P->sched_source, P->comps_found, P->comp_rows_found, P->kind, P->n, P->gnnz};
+    const int32_t nf = (int32_t)(sizeof v / sizeof v[0]);
+    for (int32_t k = 0; k < nf && k < cap; k++) out[k] = v[k];
+    *count = nf;
+    return CSX_OK;
+}
+
+// the kernels the plan's last solve enqueued, by TriLaunch
+int tri_launches_raw(const TriPlan *P, int64_t *out, int32_t cap, int32_t *count) {
+    if (!P || !count || cap < 0 || (cap > 0 && !out)) return CSX_EINVAL;
+    for (int32_t k = 0; k < TKL_COUNT && k < cap; k++) out[k] = P->launches[k];
+    *count = TKL_COUNT;
+    return CSX_OK;
+}
+}  // namespace csx
+
+extern "C" int csx_tri_route_info(csx_handle_t h, int32_t nrhs, int64_t *out, int32_t cap, int32_t *count) {
+    CSX_TRY(require_ready());
+    return tri_route_info_raw((TriPlan *)get(h, K_TRIPLAN), nrhs, tri_relaxed_env(), out, cap, count);
+}
+
+extern "C" int csx_tri_launches(csx_handle_t h, int64_t *out, int32_t cap, int32_t *count) {
+    return tri_launches_raw((TriPlan *)get(h, K_TRIPLAN), out, cap, count);
 }
 
 namespace csx {
@@ -2626,6 +2740,7 @@ static int lusol_two_sweeps(TriPlan *P1, TriPlan *P2, const int32_t *load, bool 
     TriRouting r1, r2;
     CSX_TRY(tri_route(P1, nrhs, relaxed, &r1));
     CSX_TRY(tri_route(P2, nrhs, relaxed, &r2));
+    for (TriPlan *P : {P1, P2}) std::fill(P->launches, P->launches + TKL_COUNT, (int64_t)0);   // (a fused solve counts on both plans)
     const bool ragged = P1->rounding_equal && P2->rounding_equal && r1.route == TriRoute::Ragged && r2.route == TriRoute::Ragged;
     // the exact order on forests of small components: the same fusion through the in-LDS sweeps (k_tri_local reads and writes a
     // component's rows through the row maps); the arithmetic and its order are those of the separate steps, bit for bit
@@ -2633,6 +2748,8 @@ static int lusol_two_sweeps(TriPlan *P1, TriPlan *P2, const int32_t *load, bool 
     if (ragged || local) {
         CSX_TRY(make_maps());
         if (ragged) {
+            P1->launches[TKL_RAGGED]++;
+            P2->launches[TKL_RAGGED]++;
             CSX_TRY(ragged_solve_io(P1->rag.get(), P1->comp_nodes, lmap, nullptr, !P1->forward, 1, b, x, nrhs, n));
             CSX_TRY(ragged_solve_io(P2->rag.get(), P2->comp_nodes, nullptr, smap, !P2->forward, 1, x, b, nrhs, n));
         } else {

@@ -281,6 +281,43 @@ int csx_tri_order_info(csx_handle_t plan, int32_t *matrix_cores, double *growth)
 /* After the first solve: the number of connected components of the dependency graph when the plan solves
  * them one wave each (many components of <= 256 rows: block-diagonal factors), 0 when it level-schedules. */
 int csx_tri_components(csx_handle_t plan, int32_t *ncomp);
+/* Read-backs of the triangular solve's decisions for the tests (host state only; none of them launches a solve kernel).
+ * csx_tri_limits: the constants tri_route, make_segments, walk_levels and analyse cut by, without a device: out[32] = NARROW, CHB,
+ * CH_SUF, TRW_MIN_ROW, TRW_MAX_RHS, TR64_MIN_RHS, TR64_RUN, TR64_RUN_MIN, TC_MAX_N, TC_THREADS, COMP_MIN_COUNT, COMP_MAX_ROWS,
+ * PUSH_MAX_RHS (right-hand sides of the column-push component sweep), FEW_MAX_RHS (of the few-right-hand-side sweeps), FEW_CPW
+ * (components per wave of the all-in-LDS one), COMP_LDS_MAX, FEW_TILE_LDS, WINDOW_LDS_MAX, COLUMNS_LDS_MAX (bytes of LDS: the
+ * component sweeps' programs, the X tiles of k_tri_few, the window of x, x of one right-hand side), CHAIN_LINKS_NUM,
+ * CHAIN_LINKS_DEN (a chain by its links: links * NUM > n * DEN), CHAIN_LEVELS_NUM (by its levels: levels * NUM > n),
+ * WCOL_WIDE_ENTRIES, WCHAIN_WIDE_ENTRIES (entries a column above which the window kernels take 1 024 threads / 12 rounds),
+ * WINDOW_SLACK (the window holds band + so many entries of x), STRIP_SHORT_COLS (entries a column from which analyse strips the
+ * diagonals of L 64 lanes a column), TL_WAVES_MAX, LV_MAX_ROUNDS, LV_DEVICE_MIN_TERMS, the number of counters of
+ * csx_tri_launches, 0, 0.
+ * csx_tri_route_info: what csx_tri_solve(plan, X, nrhs) would run in the process's order, and what decided it (the plan's lazy
+ * analyses run as far as that decision needs them, as in a solve).  30 fields: route (0 Ragged, 1 CompPush, 2 FewLds, 3 Few,
+ * 4 Local, 5 WColumns, 6 WColChain, 7 Columns, 8 ColChain, 9 Sequential, 10 Levels), and of the route taken lds (bytes of dynamic
+ * LDS), grid, G, waves, tile_rows, chunks, window, threads, rounds, mate; then the plan's facts: band (-1: not measured,
+ * 0x7fffffff: no proper triangle), links, col_state (0 not examined, 1 columns may be pushed, 2 a row twice in a column),
+ * levels (0: not scheduled), sequential, chain_ok, ncomp and comp_max (0: no component route), push_terms, few_cpw, few_rows,
+ * few_terms, the matrix-core guard (0 not asked, 1 passed, 2 refused, 3 NaN), the schedule's source (0 none, 1 the caller's
+ * hint, 2 the device pass, 3 the host pass, 4 the host pass after the device pass gave up at LV_MAX_ROUNDS), the components and
+ * the rows of the largest one as found (kept or not), kind, n, the terms of the gather structure.
+ * csx_tri_launches: how many launches of each solve-kernel instance the plan's last solve enqueued (a fused csx_lusol_solve
+ * counts on both plans), 30 counters: k_tri_level, k_tri_levels_one_wg, k_tri_chain, k_tri_sequential, k_tri_local<true>,
+ * <false>, k_tri_few<true>, <false>, k_tri_few_lds<true, 4>, <false, 4>, k_tri_comp_push<true>, <false>, the matrix-core sweep
+ * (ragged_solve), k_tri_columns<L>, <U>, k_tri_colchain<LT>, <UT>, k_tri_wcolumns<256>, <1024>, k_tri_wcolchain<LT, 2>, <LT, 12>,
+ * <UT, 2>, <UT, 12>, k_tri_level_rows, k_tri_run_prefix_rows, k_tri_levels_rows_one_wg, k_tri_level_rows64, k_tri_run_prefix64,
+ * k_tri_levels_rows64_one_wg, k_tri_level_of.
+ * A counter is bumped beside the launch call: a launch that fails is counted too, and the solve then returns its error.
+ * The last two: out[0 .. min(cap, *count)) written, *count = the number of fields; CSX_EINVAL for a handle that is no plan.
+ * csx_cholsol_tri_route_info / csx_cholsol_tri_launches: the same two of the triangular plans inside a csx_cholsol_plan
+ * (backward = 0: the plan of L x = b, 1: of L' x = b), in the order that plan solves in (csx_cholsol_set_order: its rounding-equal
+ * order is the relaxed order of the level walk and lets L' run on the rows of L, mate = 1); CSX_EINVAL when the plan holds no
+ * triangular plans (a forest of cliques). */
+int csx_tri_limits(int32_t *out);
+int csx_tri_route_info(csx_handle_t plan, int32_t nrhs, int64_t *out, int32_t cap, int32_t *count);
+int csx_tri_launches(csx_handle_t plan, int64_t *out, int32_t cap, int32_t *count);
+int csx_cholsol_tri_route_info(csx_handle_t plan, int backward, int32_t nrhs, int64_t *out, int32_t cap, int32_t *count);
+int csx_cholsol_tri_launches(csx_handle_t plan, int backward, int64_t *out, int32_t cap, int32_t *count);
 
 /* cs_ipvec / cs_pvec, csparse.py:1264-1277, :1779-1792, on n-by-nrhs blocks:
  * inverse != 0: x[p[k], :] = b[k, :] (ipvec); else x[k, :] = b[p[k], :] (pvec).

@@ -199,11 +199,13 @@ def test_cholsol_on_a_wide_band_factor_both_orders(cs):
 def test_long_rows_on_a_bushy_tree_take_a_wave_per_row(cs, k):
     """A 200 x 200 grid Laplacian factored in the order-1 (nested dissection) ordering: n = 40 000, a bushy tree, rows
     of 35 terms on average and separator rows of thousands, hundreds of narrow levels at the top.  Up to 4 right-hand
-    sides: a wave per row, products through LDS to lane 0 (k_tri_level_rows); 16 or more: a wave per (row, 64
-    right-hand sides), terms handed round by v_readlane (k_tri_level_rows64); runs of narrow levels in two phases
-    (k_tri_run_prefix_rows / k_tri_run_prefix64, then the level walkers).  5..15 right-hand sides: a thread per (row,
-    right-hand side).  Same subtractions in the same order as cs_lsolve / cs_ltsolve (csparse.py:1330-1365):
+    sides: a wave per row, products through LDS to lane 0 (k_tri_level_rows); 5 or more (TR64_MIN_RHS): a wave per
+    (row, 64 right-hand sides), terms handed round by v_readlane (k_tri_level_rows64), with idle lanes below 64; runs of
+    narrow levels in two phases (k_tri_run_prefix_rows / k_tri_run_prefix64, then the level walkers).  No count of
+    right-hand sides takes a thread per (row, right-hand side) on this factor: the launches are read back
+    (csx_tri_launches).  Same subtractions in the same order as cs_lsolve / cs_ltsolve (csparse.py:1330-1365):
     bit-identical, also with a partly filled last block of 64."""
+    import _csx
     from test_gpu_cholesky import _grid_laplacian
     n, p, i, x = _grid_laplacian(200, 200)
     A = cs.cs_spalloc(n, n, len(i), True, False)
@@ -223,8 +225,15 @@ def test_long_rows_on_a_bushy_tree_take_a_wave_per_row(cs, k):
         got = X.numpy().reshape(n, k)
         for r in sorted({0, 1 % k, (k - 6) % k, k - 1}):
             assert got[:, r].tobytes() == ref(n, Lp, Li, Lx, B[:, r]).tobytes(), (nm, r)
+        ran = set(_csx.tri_launches(L._dev.plans[cs.TRI_L if nm == "lsolve" else cs.TRI_LT]))
+        waves = ("level_rows", "run_prefix_rows", "levels_rows_one_wg") if k <= 4 else \
+            ("level_rows64", "run_prefix64", "levels_rows64_one_wg")
+        # (the backward solve at one right-hand side has no level wider than NARROW: its runs are the whole solve)
+        assert set(waves[1:]) <= ran and ran <= set(waves) | {"level_of"}, (nm, k, ran)
+        assert nm == "ltsolve" or waves[0] in ran, (nm, k, ran)
 
 
 def test_five_to_fifteen_right_hand_sides_on_the_same_factor(cs):
-    """Between the two wave-per-row kernels: 9 right-hand sides go to the thread-per-(row, right-hand side) kernels."""
+    """9 right-hand sides are above TR64_MIN_RHS = 5: the wave per (row, 64 right-hand sides) kernels with 55 idle lanes, not a
+    thread per (row, right-hand side); the launches read back say so (asserted in the test this one calls)."""
     test_long_rows_on_a_bushy_tree_take_a_wave_per_row(cs, 9)

@@ -27,6 +27,14 @@ SN_EPS_UNITS = 8 * 4423.03
 # results within K of the exact factor differ by at most 2 K; the other factor of 2 is for a regrouping into up to 16 partial
 # sums that is less lucky than the reference's order.
 CHOL_EPS_UNITS = 4 * 738.22
+# The triangular solve in the rounding-equal order (the matrix-core sweep over a forest of small components) against the oracle on
+# the cases of tests/tri_cases.py (ROUNDING), as the largest |x_i - ref_i| / (EPS * terms_i) with tri_cases.substitution's terms
+# (cholsolve_terms' measure for any kind).  NOT taken from the device: 4 x the plain-C oracle's own distance, in the same units,
+# from the same substitution in numpy.longdouble, largest over those cases (3.5346, case rag-lsolve-70; tools/measure_tri_edges.py
+# writes every case to profiles/trisolve_edges.jsonl; two solves in a row -- tri_cases.PAIRS -- are measured in the terms of both
+# substitutions, tri_cases.two_solves, and stay below that figure).  Two results within K of the exact one differ by at most 2 K; the other
+# factor of 2 is for a regrouping of a row's terms that is less lucky than the reference's order.
+TRI_EPS_UNITS = 4 * 3.5346
 
 
 def componentwise(v, ref, terms=None):
