@@ -115,6 +115,9 @@ _PROTOS = {
     "csx_chol_inverse": [H, C.POINTER(H)],
     "csx_chol_inverse_info": [_i32p, _i32p, C.POINTER(C.c_int64), _f64p],
     "csx_csc_diag": [H, H],
+    "csx_ldl_inverse": [H, H, C.POINTER(H)],
+    "csx_slu_inverse": [H, H, C.POINTER(H), C.POINTER(H)],
+    "csx_inverse_at": [H, H, H, H, C.c_int64, _i32p, _i32p, H, C.POINTER(C.c_int64)],
     "csx_spsolve": [H, H, _i32p, C.c_int, C.c_int, C.POINTER(H)],
     "csx_happly": [H, H, H, C.c_int32, C.c_int],
     "csx_sqr_host": [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_int32),

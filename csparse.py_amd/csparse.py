@@ -1553,17 +1553,97 @@ def sparseinv(L):
     if st == _csx.EINVAL:
         raise ValueError("sparseinv: " + _last_error())
     _csx.check(st, "csx_chol_inverse")
-    d, w, t, ms = _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_int64(0), _csx.C.c_double(0.0)
-    _csx.check(_csx.lib().csx_chol_inverse_info(d, w, t, ms), "csx_chol_inverse_info")
-    _SPARSEINV_INFO[0] = {"n": L.n, "depths": d.value, "widest": w.value, "terms": t.value, "kernel_ms": ms.value,
-                          "wall_ms": 1e3 * (time.perf_counter() - t0)}
+    _sparseinv_note("chol", L.n, t0)
     return _from_device(h, lambda nnz: max(nnz, 1))
 
 
+def _sparseinv_note(kind, n, t0):
+    d, w, t, ms = _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_int64(0), _csx.C.c_double(0.0)
+    _csx.check(_csx.lib().csx_chol_inverse_info(d, w, t, ms), "csx_chol_inverse_info")
+    _SPARSEINV_INFO[0] = {"kind": kind, "n": n, "depths": d.value, "widest": w.value, "terms": t.value, "kernel_ms": ms.value,
+                          "wall_ms": 1e3 * (time.perf_counter() - t0)}
+
+
 def sparseinv_info():
-    """the last sparseinv's (or cholsol_factor inverse / inverse_diag's) n, depths of the elimination forest (= launches unless
-    runs of one-column depths were walked), columns in the widest depth, terms (sum of |S_j|^2), kernel ms and wall ms"""
+    """the last sparseinv / sparseinv_ldl / sparseinv_lu's (or a solver's inverse / inverse_diag / inverse_at / inverse_entries')
+    kind ("chol", "ldl" or "lu"), n, depths of the elimination forest (= launches unless runs of one-column depths were
+    walked), columns in the widest depth, terms (sum of |S_j|^2), kernel ms and wall ms"""
     return dict(_SPARSEINV_INFO[0]) if _SPARSEINV_INFO[0] is not None else None
+
+
+def sparseinv_ldl(L, d):
+    """Z = inv(L D L') on the pattern of L: L unit lower triangular on a Cholesky pattern (diagonal first and
+    stored, never read; rows ascending; list-backed or on the device), d the n pivots (a dvec, numpy array or list), every one
+    finite and non-zero, of either sign.  A device-backed `cs` with L's p and i whose x holds the lower triangle of the
+    symmetric inverse, byte-equal to
+        for j = n-1 .. 0, S = rows of column j below the diagonal in storage order:
+            for i in S: Z(i,j) = -sum_{k in S} L(k,j) * Zs(i,k)                (Zs(a,b) = the stored Z(max(a,b), min(a,b)))
+            Z(j,j) = 1/d[j] - sum_{k in S} L(k,j) * Z(k,j)
+    with every product and sum rounded on its own.  Nothing is changed.  ValueError with the library's message for input that
+    is no such factor (sparseinv's cases; a zero, non-finite or short d).  A factor with static pivots is not backward stable
+    and the recurrence inherits its growth: a large max |L| (ldlsol_factor(...).info()["max_abs_l"]) says when to distrust Z."""
+    if not CS_CSC(L):
+        raise ValueError("sparseinv_ldl: L must be a CSC matrix")
+    t0 = time.perf_counter()
+    dv = d if isinstance(d, dvec) else dvec(np.asarray(d, dtype=np.float64).ravel())
+    h = _csx.new_handle()
+    with _Resident(L) as dL:
+        st = _csx.lib().csx_ldl_inverse(dL.handle, dv.handle, h)
+    if st == _csx.EINVAL:
+        raise ValueError("sparseinv_ldl: " + _last_error())
+    _csx.check(st, "csx_ldl_inverse")
+    _sparseinv_note("ldl", L.n, t0)
+    return _from_device(h, lambda nnz: max(nnz, 1))
+
+
+def sparseinv_lu(L, Ut):
+    """Z = inv(L U), U = Ut', on the one pattern of L and Ut: L unit lower triangular on a Cholesky pattern, Ut
+    on the same p and i with column j = row j of U, the pivot Ut(j,j) first, finite and non-zero (slusol_factor's factors).
+    -> (ZL, ZUt), two device-backed `cs` on that pattern: ZL(i,j) = Z(i,j) and ZUt(i,j) = Z(j,i) for i >= j (the diagonal in
+    both), byte-equal to
+        for j = n-1 .. 0, d = Ut(j,j), S = rows of column j below the diagonal in storage order:
+            for i in S: ZL(i,j) = -sum_{k in S} L(k,j) * Z(i,k);   ZUt(i,j) = (-sum_{k in S} Ut(k,j) * Z(k,i)) / d
+            ZL(j,j) = ZUt(j,j) = 1/d - sum_{k in S} L(k,j) * ZUt(k,j)
+    with every product and sum rounded on its own.  Nothing is changed.  ValueError with the library's message for input that
+    is no such pair (sparseinv's cases; a Ut on another pattern; a zero or non-finite pivot).  A factor with static pivots is
+    not backward stable and the recurrence inherits its growth: large max |L|, max |U| / min |d|
+    (slusol_factor(...).info()["max_abs_l"]) say when to distrust Z."""
+    if not CS_CSC(L) or not CS_CSC(Ut):
+        raise ValueError("sparseinv_lu: L and Ut must be CSC matrices")
+    t0 = time.perf_counter()
+    hl, hu = _csx.new_handle(), _csx.new_handle()
+    with _Resident(L) as dL, _Resident(Ut) as dU:
+        st = _csx.lib().csx_slu_inverse(dL.handle, dU.handle, hl, hu)
+    if st == _csx.EINVAL:
+        raise ValueError("sparseinv_lu: " + _last_error())
+    _csx.check(st, "csx_slu_inverse")
+    _sparseinv_note("lu", L.n, t0)
+    return _from_device(hl, lambda nnz: max(nnz, 1)), _from_device(hu, lambda nnz: max(nnz, 1))
+
+
+def _inverse_at(who, ZL, ZUt, hrmap, hcmap, rows, cols):
+    """Z(rmap[rows[t]], cmap[cols[t]]) for every t as a numpy array, read off the pattern of the device-backed ZL (and ZUt for
+    the entries above the diagonal; None: Z symmetric) by csx_inverse_at; hrmap, hcmap: int-vector handles or H(0).
+    ValueError naming how many pairs are not on the pattern, or for an index out of range."""
+    rows, cols = _csx.i32(np.asarray(rows).ravel()), _csx.i32(np.asarray(cols).ravel())
+    if rows.size != cols.size:
+        raise ValueError("%s: rows and cols differ in length (%d, %d)" % (who, rows.size, cols.size))
+    out = dvec(max(rows.size, 1))
+    missing = _csx.C.c_int64(0)
+    st = _csx.lib().csx_inverse_at(ZL._dev.handle, ZUt._dev.handle if ZUt is not None else _csx.H(0), hrmap, hcmap, rows.size,
+                                   _csx.pi(rows), _csx.pi(cols), out.handle, missing)
+    if st == _csx.EINVAL:
+        raise ValueError("%s: %s" % (who, _last_error()))
+    _csx.check(st, "csx_inverse_at")
+    if missing.value:
+        raise ValueError("%s: %d of %d pairs are not on the pattern of the factor" % (who, missing.value, rows.size))
+    return out.numpy()[:rows.size]
+
+
+def _entries_np(A):
+    """(row, column) of every stored entry of A in storage order, as int32 arrays"""
+    p, i = _pattern_np(A)
+    return i, np.repeat(np.arange(A.n, dtype=np.int32), np.diff(p))
 
 
 def _first_entries(M):
@@ -2111,7 +2191,10 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
       elimination tree), launches (numeric launches of the last run: level_launches of the wave-per-column kernel +
       run_launches of the one-workgroup walker of narrow levels), pos, neg, perturbed, breakdown (smallest broken column of the
       last run, -1 none), kernel_us, long_columns (columns of the last run that the kernels updated in place: longer than the LDS `window`), min_abs_d,
-      max_abs_d, max_abs_l.  factors: .L (a pinned `cs`, unit diagonal stored) and .D (a dvec); symbolic: S."""
+      max_abs_d, max_abs_l.  factors: .L (a pinned `cs`, unit diagonal stored) and .D (a dvec); symbolic: S.
+    inverse(), inverse_at(rows, cols), inverse_diag(), inverse_entries(): entries of inv(A) on the pattern of L (sparseinv_ldl,
+      DESIGN.md §26), computed from the factor as it stands.  A static-pivot factor is not backward stable and the recurrence
+      inherits its growth, as solve() without refine() does: info()["max_abs_l"] says when to distrust them."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     perturb = float(perturb)
@@ -2176,6 +2259,30 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
         def _after_refactor(self, A2):
             self._A2, self._stands, self._source = A2, dev.version, None
             self._operator_changed()
+
+        # Entries of inv(A) on the pattern of L (sparseinv_ldl).  Each call reads the factor as it stands (after
+        # refactor: the new values; after a refactor that broke down: the old ones) and keeps nothing.  Static pivoting is not
+        # backward stable and the recurrence inherits the factor's growth, as solve() without refine() does: info()["max_abs_l"]
+        # says when to distrust the entries.
+
+        def inverse(self):
+            """Z = inv(L D L') on the pattern of L: a device-backed `cs` in L's numbering (symbolic.pinv maps A's)"""
+            return sparseinv_ldl(N.L, N.D)
+
+        def inverse_at(self, rows, cols):
+            """inv(A)(rows[t], cols[t]) in A's numbering as a numpy array; ValueError naming how many pairs are not on the
+            pattern of L + L'"""
+            return _inverse_at("ldlsol_factor.inverse_at", self.inverse(), None, hp, hp, rows, cols)
+
+        def inverse_diag(self):
+            """diag(inv(A)) as a numpy array, entry i = inv(A)(i,i) in A's numbering"""
+            d = _first_entries(self.inverse())
+            return d if pinv is None else d[pinv]
+
+        def inverse_entries(self):
+            """one value per stored entry q of A: inv(A)(row_q, col_q) (entries below the diagonal and duplicates get their
+            symmetric or shared value); always on the pattern"""
+            return self.inverse_at(*_entries_np(A))
 
     return _Solver()
 
@@ -2903,7 +3010,11 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
       exact-order solves; logdet(): (sign, log |det A|), the sign with both permutations' parities; info(): n, lnz, levels,
       launches = level_launches + run_launches of the last run, perturbed, breakdown, kernel_us, long_columns (updated in place:
       longer than the LDS `window`), run_levels (levels per walker launch), pos, neg (pivot signs), min_abs_d, max_abs_d,
-      max_abs_l, max_abs_u, matched.  factors: .L, .U (= Ut: column k is row k of U, the pivot first), .prow, .pinv."""
+      max_abs_l, max_abs_u, matched.  factors: .L, .U (= Ut: column k is row k of U, the pivot first), .prow, .pinv.
+    inverse() -> (ZL, ZUt), inverse_at(rows, cols), inverse_entries() (entry (r, c) of A -> inv(A)(c, r), the gradient of
+      log|det A|), inverse_diag(): entries of inv(A) on the pattern of the factors (sparseinv_lu), computed from the
+      factor as it stands.  A static-pivot factor is not backward stable and the recurrence inherits its growth, as solve()
+      without refine() does: info()["max_abs_l"] says when to distrust them."""
     if not CS_CSC(A) or A.m != A.n:
         return None
     perturb = float(perturb)
@@ -3028,6 +3139,34 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
             d = x[Lp[:n]]
             sign = sign_perm * (-1.0 if int(np.sum(d < 0.0)) % 2 else 1.0)
             return sign, math.fsum(np.log(np.abs(d)).tolist())
+
+        # Entries of inv(A) on the pattern of L and Ut (sparseinv_lu).  Each call reads the factor as it stands
+        # (after refactor: the new values; after a refactor that broke down: the old ones) and keeps nothing.  Static pivoting
+        # is not backward stable and the recurrence inherits the factor's growth, as solve() without refine() does:
+        # info()["max_abs_l"] says when to distrust the entries.
+
+        def inverse(self):
+            """(ZL, ZUt): Z = inv(L U) on the pattern of the factors, in their numbering: ZL(i,j) = Z(i,j), ZUt(i,j) = Z(j,i),
+            i >= j; inv(A)(x, y) = Z(pinv[x], pinv[prow^-1[y]])"""
+            return sparseinv_lu(N.L, N.U)
+
+        def inverse_at(self, rows, cols):
+            """inv(A)(rows[t], cols[t]) in A's numbering as a numpy array; ValueError naming how many pairs are not on the
+            pattern of the factors"""
+            ZL, ZUt = self.inverse()
+            return _inverse_at("slusol_factor.inverse_at", ZL, ZUt, hp, hc, rows, cols)
+
+        def inverse_entries(self):
+            """one value per stored entry q of A at (r, c): inv(A)(c, r) = d log|det A| / d A(r,c), the companion of logdet();
+            always on the pattern (the slot of that entry of the factors, in the other array); duplicates share a value"""
+            r, c = _entries_np(A)
+            return self.inverse_at(c, r)
+
+        def inverse_diag(self):
+            """diag(inv(A)) in A's numbering as a numpy array.  With a matching in force inv(A)(i,i) is on the pattern only
+            where A(i,i) is stored or filled: ValueError, as inverse_at's, when some are not"""
+            k = np.arange(n, dtype=np.int32)
+            return self.inverse_at(k, k)
 
     return _Solver()
 

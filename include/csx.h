@@ -514,6 +514,31 @@ int csx_updown_block_info(int32_t *chunks, int32_t *union_columns, int32_t *grou
 int csx_chol_inverse(csx_handle_t L, csx_handle_t *Z);
 int csx_chol_inverse_info(int32_t *depths, int32_t *widest, int64_t *terms, double *kernel_ms);
 int csx_csc_diag(csx_handle_t M, csx_handle_t out);
+/* sparseinv for the two other factorisations on a Cholesky pattern: the same schedule, lookups and
+ * kernels under another column policy.  Both take plain matrix / vector handles (not factor handles), as csx_chol_inverse does.
+ * csx_ldl_inverse: Z = inv(L D L') on the pattern of L.  L: unit lower, diagonal first (stored, never read), rows ascending; d: a
+ *   device vector of at least n doubles, every one finite and non-zero.  *Z as for csx_chol_inverse, byte-equal to
+ *   for j = n-1 .. 0:  for i in S_j: Z(i,j) = -sum_{k in S_j} L(k,j) * Zs(i,k);   Z(j,j) = 1/d[j] - sum_{k in S_j} L(k,j) * Z(k,j).
+ * csx_slu_inverse: Z = inv(L U), U = Ut', Ut on the SAME p and i as L (the same device arrays or equal ones: compared on the
+ *   device after n and nnz), column j of Ut = row j of U with the pivot d = Ut(j,j) first, finite and non-zero.  Two new
+ *   matrices on that pattern: ZL(i,j) = Z(i,j) and ZUt(i,j) = Z(j,i) for i >= j (the diagonal in both), byte-equal to
+ *   for j = n-1 .. 0:  for i in S_j: ZL(i,j) = -sum_k L(k,j) * Z(i,k);  ZUt(i,j) = (-sum_k Ut(k,j) * Z(k,i)) / d;
+ *                      ZL(j,j) = ZUt(j,j) = 1/d - sum_k L(k,j) * ZUt(k,j)
+ *   (Z(i,k) = ZL(i,k) for i > k, ZUt(k,i) for i < k, the diagonal of column i for i == k; Z(k,i) is the same slot of the other
+ *   array), every product and sum rounded on its own, the sums in storage order.
+ * Both: CSX_EINVAL, a message in csx_last_error() and no output handle for an input that fails the checks (made on the device
+ *   before any value is written: csx_chol_inverse's structure checks, the pivots, Ut's pattern) or whose pattern is not a
+ *   Cholesky pattern; nothing is read out of range, L, d and Ut are never changed.  csx_chol_inverse_info answers for the last
+ *   call of any of the three.  A static-pivot factor is not backward stable and the recurrence inherits its growth.
+ * csx_inverse_at: out[t] = Z(a, b), a = rmap[rows[t]], b = cmap[cols[t]], t < count, read off the pattern: a > b from column b
+ *   of ZL, a < b from column a of ZUt (ZUt = 0: of ZL, a symmetric Z), a == b the first entry of column a.  rmap, cmap: device
+ *   int vectors of at least n entries (csx_ivec_upload; csx_permute_vec's kind) or 0 for the identity; rows, cols: host
+ *   arrays of count int32 (as csx_csc_upload takes its indices); out: a device vector of at least count doubles.  A pair that
+ *   is not on the pattern yields NaN and is counted in *missing (may be null).  CSX_EINVAL for an index outside [0, n). */
+int csx_ldl_inverse(csx_handle_t L, csx_handle_t d, csx_handle_t *Z);
+int csx_slu_inverse(csx_handle_t L, csx_handle_t Ut, csx_handle_t *ZL, csx_handle_t *ZUt);
+int csx_inverse_at(csx_handle_t ZL, csx_handle_t ZUt, csx_handle_t rmap, csx_handle_t cmap, int64_t count, const int32_t *rows,
+                   const int32_t *cols, csx_handle_t out, int64_t *missing);
 
 /* cs_lu, csparse.py:1370-1451 (+ cs_spsolve :2078-2113), natural column order: host C++
  * left-looking LU with threshold partial pivoting.  It produces the L (unit diagonal first)
