@@ -77,6 +77,13 @@ _PROTOS = {
     "csx_block_select_cols": [H, H, C.c_int64, C.c_int32, _i32p],
     "csx_transpose": [H, C.c_int, C.POINTER(H)],
     "csx_cumsum": [H, H, C.c_int64, C.POINTER(C.c_int64)],
+    "csx_prim_limits": [_i32p],
+    "csx_prim_scan": [_i32p, _i32p, C.c_int64, C.c_int, C.POINTER(C.c_int64)],
+    "csx_prim_suffix_min": [_i32p, C.c_int64],
+    "csx_prim_expand_columns": [_i32p, C.c_int32, C.c_int32, _i32p],
+    "csx_prim_boundaries": [_vp, C.c_int64, C.c_int32, _i32p, C.c_int],
+    "csx_prim_sort": [_vp, _vp, _f64p, C.c_int64, C.c_uint32, _vp, _vp, _f64p, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int],
+    "csx_prim_sort_info": [C.POINTER(C.c_int64), C.c_int32],
     "csx_multiply": [H, H, C.POINTER(H)],
     "csx_tri_analyse": [H, C.c_int, C.POINTER(H)],
     "csx_tri_info": [H, _i32p, _i32p, _i32p],
@@ -430,6 +437,90 @@ def tri_launches(plan, cholsol=None):
                        "csx_cholsol_tri_launches")
     assert len(v) == len(TRI_LAUNCHES)
     return {k: c for k, c in zip(TRI_LAUNCHES, v) if c}
+
+
+PRIM_LIMITS = ("SCAN_TILE", "SM_TILE", "RS_TILE", "RS_BINS", "RS_DESC_STARTS", "RS_SEGS", "RS_CHUNK_MIN", "RS_CHUNK_DIV",
+               "EXPAND_GRID_MAX")
+SORT_INSTANCES = ("none", "keys", "a", "v", "av_flat_flat", "av_flat_packed", "av_packed_packed", "av_packed_flat", "short_first",
+                  "short_middle", "short_last")
+SORT_INFO = ("bits", "passes", "widths", "nblocks", "chunk", "nchunks", "packed", "k16", "key_misalign", "instances", "count")
+
+
+def prim_limits():
+    """the constants the integer primitives are cut by (csx_sort.hip), asked of the library; no GPU needed: a dict by the names
+    of PRIM_LIMITS (include/csx.h: csx_prim_limits)"""
+    out = (C.c_int32 * len(PRIM_LIMITS))()
+    check(load().csx_prim_limits(out), "csx_prim_limits")
+    return {name: int(out[k]) for k, name in enumerate(PRIM_LIMITS)}
+
+
+def _u32(a):
+    return None if a is None else np.array(a, dtype=np.uint32)     # (a copy: the library writes its inputs back)
+
+
+def _vptr(a):
+    return None if a is None else a.ctypes.data_as(_vp)
+
+
+def prim_scan(values, in_place=False):
+    """scan_exclusive_i32 of a host array (csx_prim_scan): (out[0 .. n], total, the input as the device left it -- None in place)"""
+    a = np.array(values, dtype=np.int32)
+    out, total = np.full(len(a) + 1, -1, np.int32), C.c_int64(-1)
+    check(lib().csx_prim_scan(pi(a), pi(out), len(a), 1 if in_place else 0, C.byref(total)), "csx_prim_scan")
+    return out, total.value, (None if in_place else a)
+
+
+def prim_suffix_min(values):
+    """suffix_min_i32 of a host array (csx_prim_suffix_min)"""
+    p = np.array(values, dtype=np.int32)
+    check(lib().csx_prim_suffix_min(pi(p), len(p)), "csx_prim_suffix_min")
+    return p
+
+
+def prim_expand_columns(Ap, fill=-1):
+    """expand_columns under the column pointers Ap (csx_prim_expand_columns): (col, Ap as the device left it)"""
+    p = np.array(Ap, dtype=np.int32)
+    col = np.full(int(p[-1]), fill, np.int32)
+    check(lib().csx_prim_expand_columns(pi(p), len(p) - 1, len(col), pi(col)), "csx_prim_expand_columns")
+    return col, p
+
+
+def prim_boundaries(sorted_key, nkeys, misalign_words=0, fill=-1):
+    """boundaries_from_sorted (csx_prim_boundaries): (ptr[0 .. nkeys], the keys as the device left them)"""
+    k = _u32(sorted_key)
+    ptr = np.full(nkeys + 1, fill, np.int32)
+    check(lib().csx_prim_boundaries(_vptr(k), len(k), nkeys, pi(ptr), misalign_words), "csx_prim_boundaries")
+    return ptr, k
+
+
+def prim_sort(key, a=None, v=None, key_limit=0xFFFFFFFF, want_key=True, expand_ptr=None, nkeys=None, misalign_words=0):
+    """stable_sort_by_key_ex on host arrays (csx_prim_sort).  a (uint32), v (float64), expand_ptr (column pointers over the
+    records) optional; want_key: ask for the sorted keys; nkeys not None: ask for the pointer array of nkeys keys.  A dict:
+    out_key, out_a, out_v, out_ptr (None where not asked for), and key, a, v, expand_ptr as the device left the inputs."""
+    k, aa = _u32(key), _u32(a)
+    vv = None if v is None else np.array(v, dtype=np.float64)
+    xp = None if expand_ptr is None else np.array(expand_ptr, dtype=np.int32)
+    n = len(k)
+    ok = np.full(n, 0xDEADBEEF, np.uint32) if want_key else None
+    oa = np.full(n, 0xDEADBEEF, np.uint32) if (aa is not None or xp is not None) else None
+    ov = np.full(n, -777.0, np.float64) if vv is not None else None
+    op = np.full(nkeys + 1, -1, np.int32) if nkeys is not None else None
+    check(lib().csx_prim_sort(_vptr(k), _vptr(aa), pd(vv), n, key_limit, _vptr(ok), _vptr(oa), pd(ov), pi(xp),
+                              0 if xp is None else len(xp) - 1, pi(op), 0 if nkeys is None else nkeys, misalign_words),
+          "csx_prim_sort")
+    return {"out_key": ok, "out_a": oa, "out_v": ov, "out_ptr": op, "key": k, "a": aa, "v": vv, "expand_ptr": xp}
+
+
+def prim_sort_info():
+    """what the last sort of this process decided (csx_prim_sort_info; host state only): a dict by SORT_INFO, "widths" and
+    "instances" (names of SORT_INSTANCES) one per pass"""
+    out = (C.c_int64 * 17)()
+    check(load().csx_prim_sort_info(out, 17), "csx_prim_sort_info")
+    v = [int(x) for x in out]
+    passes = v[1]
+    return {"bits": v[0], "passes": passes, "widths": tuple(v[2:2 + passes]), "nblocks": v[6], "chunk": v[7], "nchunks": v[8],
+            "packed": v[9], "k16": v[10], "key_misalign": v[11], "instances": tuple(SORT_INSTANCES[i] for i in v[12:12 + passes]),
+            "count": v[16]}
 
 
 def exported_symbols():

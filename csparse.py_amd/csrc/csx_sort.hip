@@ -120,10 +120,12 @@ __global__ __launch_bounds__(256) void k_expand_columns(const int32_t *Ap, int32
     }
 }
 
+constexpr int EXPAND_GRID_MAX = 65536;   // workgroups of four waves; more columns than that wrap in the kernel's loop
+
 int expand_columns(const int32_t *Ap, int32_t n, int32_t nnz, int32_t *col) {
     if (n == 0 || nnz == 0) return CSX_OK;
     int64_t blocks = ((int64_t)n + 3) / 4;
-    if (blocks > 65536) blocks = 65536;
+    if (blocks > EXPAND_GRID_MAX) blocks = EXPAND_GRID_MAX;
     hipLaunchKernelGGL(k_expand_columns, dim3((unsigned)blocks), dim3(256), 0, ctx().stream, Ap, n, col);
     CSX_LAUNCH_CHECK();
     return CSX_OK;
@@ -341,7 +343,7 @@ struct RsArgs {
     int k16_w0;                // bits of the first digit
 };
 
-// Stable scatter of one workgroup tile (4096 records).  Ranks follow (wave, round, lane) = source
+// Stable scatter of one workgroup tile (RS_TILE = 2048 records).  Ranks follow (wave, round, lane) = source
 // order.  Records are first placed in LDS in their sorted order inside the tile, then written out
 // position by position: consecutive threads write consecutive slots of a bucket, so the stores are
 // runs of whole 64/128-byte pieces instead of 4/8-byte singles.
@@ -577,17 +579,41 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_scatter(const RsArgs g) {
     }
 }
 
+// the instances of k_rs_scatter a sort can launch, as csx_prim_sort_info names them (include/csx.h)
+enum RsInstance : int { RSI_NONE = 0, RSI_KEYS, RSI_A, RSI_V, RSI_AV_FLAT_FLAT, RSI_AV_FLAT_PACKED, RSI_AV_PACKED_PACKED,
+                        RSI_AV_PACKED_FLAT, RSI_SHORT_FIRST, RSI_SHORT_MIDDLE, RSI_SHORT_LAST };
+
 template <bool HAS_A, bool HAS_V>
-static void launch_scatter(bool in_aos, bool out_aos, dim3 grid, hipStream_t s, const RsArgs &g) {
+static int launch_scatter(bool in_aos, bool out_aos, dim3 grid, hipStream_t s, const RsArgs &g) {
     if constexpr (HAS_A && HAS_V) {
-        if (in_aos && out_aos) hipLaunchKernelGGL((k_rs_scatter<true, true, true, true>), grid, dim3(RS_THREADS), 0, s, g);
-        else if (in_aos) hipLaunchKernelGGL((k_rs_scatter<true, true, true, false>), grid, dim3(RS_THREADS), 0, s, g);
-        else if (out_aos) hipLaunchKernelGGL((k_rs_scatter<true, true, false, true>), grid, dim3(RS_THREADS), 0, s, g);
-        else hipLaunchKernelGGL((k_rs_scatter<true, true, false, false>), grid, dim3(RS_THREADS), 0, s, g);
+        if (in_aos && out_aos) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, true, true>), grid, dim3(RS_THREADS), 0, s, g);
+            return RSI_AV_PACKED_PACKED;
+        }
+        if (in_aos) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, true, false>), grid, dim3(RS_THREADS), 0, s, g);
+            return RSI_AV_PACKED_FLAT;
+        }
+        if (out_aos) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, false, true>), grid, dim3(RS_THREADS), 0, s, g);
+            return RSI_AV_FLAT_PACKED;
+        }
+        hipLaunchKernelGGL((k_rs_scatter<true, true, false, false>), grid, dim3(RS_THREADS), 0, s, g);
+        return RSI_AV_FLAT_FLAT;
     } else {
         hipLaunchKernelGGL((k_rs_scatter<HAS_A, HAS_V, false, false>), grid, dim3(RS_THREADS), 0, s, g);
+        return HAS_A ? RSI_A : HAS_V ? RSI_V : RSI_KEYS;
     }
 }
+
+// read-back for the tests (host state only): what the last stable_sort_by_key_ex of this process decided, in the order of
+// csx_prim_sort_info
+constexpr int RS_MAX_PASSES = 4;
+struct SortInfo {
+    int64_t bits = 0, passes = 0, width[RS_MAX_PASSES] = {0, 0, 0, 0}, nblocks = 0, chunk = 0, nchunks = 0, packed = 0, k16 = 0,
+            key_misalign = 0, instance[RS_MAX_PASSES] = {0, 0, 0, 0}, count = 0;
+};
+static SortInfo g_sort_info;
 
 // ---- reverse running minimum: p[r] = min(p[r], ..., p[n-1]) (turns "first slot of each key" into column pointers) ----
 constexpr int SM_ITEMS = 8;
@@ -651,6 +677,7 @@ int suffix_min_i32(int32_t *p, int64_t n) {
     if (nb > 1) {
         CSX_TRY(bm.alloc((size_t)nb));
         hipLaunchKernelGGL(k_sufmin_block, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, p, n, bm);
+        CSX_LAUNCH_CHECK();
         CSX_TRY(suffix_min_i32(bm, nb));
     }
     hipLaunchKernelGGL(k_sufmin_apply, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, s, p, n, bm, nb);
@@ -665,6 +692,9 @@ __global__ void k_ptr_init(int32_t *ptr, int32_t nkeys, int32_t count) {
     else if (i == nkeys) ptr[i] = count;
 }
 
+// the digit scan works on chunks of tiles: RS_CHUNK_DIV chunks at the most, none shorter than RS_CHUNK_MIN tiles
+constexpr uint32_t RS_CHUNK_MIN = 64, RS_CHUNK_DIV = 1024;
+
 int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *v, int64_t count, uint32_t key_limit,
                           uint32_t *out_key, uint32_t *out_a, double *out_v, const SortExtra *ex) {
     hipStream_t s = ctx().stream;
@@ -676,13 +706,14 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
                            (int32_t)(count > 0 ? count : 0));
         CSX_LAUNCH_CHECK();
     }
+    g_sort_info = SortInfo();
     if (count <= 0) return optr ? suffix_min_i32(optr, (int64_t)ex->nkeys + 1) : CSX_OK;
     int bits = 1;
     while (bits < 32 && (1ull << bits) < (unsigned long long)key_limit) bits++;
     const int passes = (bits + 7) / 8;
     const uint32_t nblocks = (uint32_t)((count + RS_TILE - 1) / RS_TILE);
-    uint32_t chunk = (nblocks + 1023) / 1024;
-    if (chunk < 64) chunk = 64;
+    uint32_t chunk = (nblocks + RS_CHUNK_DIV - 1) / RS_CHUNK_DIV;
+    if (chunk < RS_CHUNK_MIN) chunk = RS_CHUNK_MIN;
     const uint32_t nchunks = (nblocks + chunk - 1) / chunk;
     const bool has_a = a != nullptr || xp != nullptr, has_v = v != nullptr;
     const bool packed = has_a && has_v;   // (a, v) travel as 12-byte records between passes
@@ -691,6 +722,16 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
     const int w0 = bits / passes + (0 < bits % passes ? 1 : 0);
     const bool k16 = xp != nullptr && packed && passes == 3 && optr != nullptr && out_key == nullptr && bits - w0 <= 16 &&
                      (uint64_t)ex->expand_n <= (1ull << (32 - w0)) && ctx().opt.sort_short_keys;
+    SortInfo &info = g_sort_info;
+    info.bits = bits;
+    info.passes = passes;
+    info.nblocks = nblocks;
+    info.chunk = chunk;
+    info.nchunks = nchunks;
+    info.packed = packed ? 1 : 0;
+    info.k16 = k16 ? 1 : 0;
+    info.key_misalign = (int64_t)((reinterpret_cast<uintptr_t>(key) & 15) / sizeof(uint32_t));
+    info.count = count;
 
     DevBuf<int32_t> hist, part;
     DevBuf<uint32_t> desc;
@@ -716,6 +757,7 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
     if (xp) {
         hipLaunchKernelGGL(k_rs_tiledesc_head, dim3((nblocks + 255) / 256), dim3(256), 0, s, xp, ex->expand_n, count, nblocks,
                            desc);
+        CSX_LAUNCH_CHECK();
         hipLaunchKernelGGL(k_rs_tiledesc_starts, dim3((unsigned)(((int64_t)ex->expand_n + 255) / 256)), dim3(256), 0, s, xp,
                            ex->expand_n, count, desc);
         CSX_LAUNCH_CHECK();
@@ -754,14 +796,23 @@ int stable_sort_by_key_ex(const uint32_t *key, const uint32_t *a, const double *
         hipLaunchKernelGGL(k_rs_colsum, dim3(nchunks), dim3(RS_BINS), 0, s, hist, nblocks, chunk, part);
         hipLaunchKernelGGL(k_rs_chunkscan, dim3(1), dim3(RS_BINS * RS_SEGS), 0, s, part, nchunks, dbase);
         hipLaunchKernelGGL(k_rs_tileprefix, dim3(nchunks), dim3(RS_BINS), 0, s, hist, part, dbase, nblocks, chunk);
-        if (k16 && ps == 0) hipLaunchKernelGGL((k_rs_scatter<true, true, false, true, 1>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
-        else if (k16 && !last) hipLaunchKernelGGL((k_rs_scatter<true, true, true, true, 2>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
-        else if (k16) hipLaunchKernelGGL((k_rs_scatter<true, true, true, false, 3>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
-        else if (has_a && has_v) launch_scatter<true, true>(in_aos, out_aos, dim3(nblocks), s, g);
-        else if (has_a) launch_scatter<true, false>(false, false, dim3(nblocks), s, g);
-        else if (has_v) launch_scatter<false, true>(false, false, dim3(nblocks), s, g);
-        else launch_scatter<false, false>(false, false, dim3(nblocks), s, g);
+        int inst;
+        if (k16 && ps == 0) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, false, true, 1>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
+            inst = RSI_SHORT_FIRST;
+        } else if (k16 && !last) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, true, true, 2>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
+            inst = RSI_SHORT_MIDDLE;
+        } else if (k16) {
+            hipLaunchKernelGGL((k_rs_scatter<true, true, true, false, 3>), dim3(nblocks), dim3(RS_THREADS), 0, s, g);
+            inst = RSI_SHORT_LAST;
+        } else if (has_a && has_v) inst = launch_scatter<true, true>(in_aos, out_aos, dim3(nblocks), s, g);
+        else if (has_a) inst = launch_scatter<true, false>(false, false, dim3(nblocks), s, g);
+        else if (has_v) inst = launch_scatter<false, true>(false, false, dim3(nblocks), s, g);
+        else inst = launch_scatter<false, false>(false, false, dim3(nblocks), s, g);
         CSX_LAUNCH_CHECK();
+        info.width[ps] = width;
+        info.instance[ps] = inst;
         g.key = g.okey;
         g.key16 = g.okey16;
         g.a = g.oa;
@@ -828,4 +879,195 @@ extern "C" int csx_cumsum(csx_handle_t hp, csx_handle_t hc, int64_t n, int64_t *
     if (n)
         CSX_HIP(hipMemcpyAsync(c->d, p->d, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx().stream));
     return CSX_OK;
+}
+
+// ---- read-backs and entry points for the tests (include/csx.h has the field lists) ----------------------------------------------
+// Each csx_prim_* copies its host arrays to device buffers, runs the one primitive as its callers run it and copies the results
+// back; the device copies of the INPUTS are copied back over the host arrays too, so that a primitive that wrote to an input
+// shows.  Arguments a primitive would index memory with (pointer arrays, keys under a pointer output) are checked on the host
+// first.  None of this is on a path production code takes.
+extern "C" int csx_prim_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    const int32_t v[9] = {SCAN_TILE, SM_TILE, RS_TILE, RS_BINS, RS_DESC_STARTS, RS_SEGS, (int32_t)RS_CHUNK_MIN, (int32_t)RS_CHUNK_DIV,
+                          EXPAND_GRID_MAX};
+    for (int k = 0; k < 9; k++) out[k] = v[k];
+    return CSX_OK;
+}
+
+extern "C" int csx_prim_sort_info(int64_t *out, int32_t cap) {   // (host state only)
+    if (!out || cap < 0) return CSX_EINVAL;
+    const SortInfo &f = g_sort_info;
+    const int64_t v[] = {f.bits, f.passes, f.width[0], f.width[1], f.width[2], f.width[3], f.nblocks, f.chunk, f.nchunks, f.packed,
+                         f.k16, f.key_misalign, f.instance[0], f.instance[1], f.instance[2], f.instance[3], f.count};
+    const int32_t nf = (int32_t)(sizeof v / sizeof v[0]);
+    for (int32_t k = 0; k < nf && k < cap; k++) out[k] = v[k];
+    return CSX_OK;
+}
+
+namespace {
+template <class T>
+int to_host(T *h, const T *d, size_t count) {
+    if (count) CSX_HIP(hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx().stream));
+    return CSX_OK;
+}
+template <class T>
+int to_device(T *d, const T *h, size_t count) {
+    if (count) CSX_HIP(hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx().stream));
+    return CSX_OK;
+}
+// room for count keys that start `words` 4-byte words past a 16-byte boundary
+int alloc_misaligned(DevBuf<uint32_t> &buf, size_t count, int words, uint32_t **keys) {
+    CSX_TRY(buf.alloc(count + 8));
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(buf.get()) + 15) & ~(uintptr_t)15;
+    *keys = reinterpret_cast<uint32_t *>(base) + words;
+    return CSX_OK;
+}
+// An output array with PRIM_GUARD bytes of a known pattern behind it: a primitive that stored past the end of an output is an
+// error of the call, not a silent store into the slack of the pool's block.
+constexpr size_t PRIM_GUARD = 256;
+template <class T>
+struct GuardedOut {
+    DevBuf<T> d;
+    size_t count = 0;
+    unsigned char seen[PRIM_GUARD];
+    int put(const T *h, size_t n) {   // the caller's contents first: slots a primitive leaves alone keep them
+        count = n;
+        CSX_TRY(d.alloc(n + PRIM_GUARD / sizeof(T)));
+        CSX_TRY(to_device(d.get(), h, n));
+        CSX_HIP(hipMemsetAsync(d.get() + n, 0xA5, PRIM_GUARD, ctx().stream));
+        return CSX_OK;
+    }
+    int take(T *h) {   // enqueues the copies back; intact() holds once the stream is synchronised
+        CSX_TRY(to_host(h, (const T *)d.get(), count));
+        CSX_HIP(hipMemcpyAsync(seen, d.get() + count, PRIM_GUARD, hipMemcpyDeviceToHost, ctx().stream));
+        return CSX_OK;
+    }
+    bool intact() const {
+        for (size_t k = 0; k < PRIM_GUARD; k++)
+            if (seen[k] != 0xA5) return false;
+        return true;
+    }
+};
+int guard_verdict(bool intact, const char *what) {
+    if (intact) return CSX_OK;
+    set_error("%s: a store past the end of an output array", what);
+    return CSX_ERUNTIME;
+}
+// column pointers of n columns over exactly `count` positions
+bool pointers_ok(const int32_t *p, int64_t n, int64_t count) {
+    if (p[0] != 0 || (int64_t)p[n] != count) return false;
+    for (int64_t j = 0; j < n; j++)
+        if (p[j] > p[j + 1]) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int csx_prim_scan(int32_t *in, int32_t *out, int64_t n, int in_place, int64_t *total) {
+    if (n < 0 || !out || (n > 0 && !in)) return CSX_EINVAL;
+    CSX_TRY(require_ready());
+    DevBuf<int32_t> din;
+    GuardedOut<int32_t> dout;
+    CSX_TRY(dout.put(out, (size_t)n + 1));
+    if (in_place) {
+        CSX_TRY(to_device(dout.d.get(), (const int32_t *)in, (size_t)n));
+        CSX_TRY(scan_exclusive_i32(dout.d, dout.d, n, total));
+    } else {
+        CSX_TRY(upload(din, (const int32_t *)in, (size_t)n));
+        CSX_TRY(scan_exclusive_i32(din, dout.d, n, total));
+        CSX_TRY(to_host(in, (const int32_t *)din.get(), (size_t)n));
+    }
+    CSX_TRY(dout.take(out));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return guard_verdict(dout.intact(), "csx_prim_scan");
+}
+
+extern "C" int csx_prim_suffix_min(int32_t *p, int64_t n) {
+    if (n < 0 || (n > 0 && !p)) return CSX_EINVAL;
+    CSX_TRY(require_ready());
+    GuardedOut<int32_t> d;
+    CSX_TRY(d.put(p, (size_t)n));
+    CSX_TRY(suffix_min_i32(d.d, n));
+    CSX_TRY(d.take(p));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return guard_verdict(d.intact(), "csx_prim_suffix_min");
+}
+
+extern "C" int csx_prim_expand_columns(int32_t *Ap, int32_t n, int32_t nnz, int32_t *col) {
+    if (n < 0 || nnz < 0 || !Ap || (nnz > 0 && !col) || !pointers_ok(Ap, n, nnz)) return CSX_EINVAL;
+    CSX_TRY(require_ready());
+    DevBuf<int32_t> dp;
+    GuardedOut<int32_t> dc;
+    CSX_TRY(upload(dp, (const int32_t *)Ap, (size_t)n + 1));
+    CSX_TRY(dc.put(col, (size_t)nnz));
+    CSX_TRY(expand_columns(dp, n, nnz, dc.d));
+    CSX_TRY(to_host(Ap, (const int32_t *)dp.get(), (size_t)n + 1));
+    CSX_TRY(dc.take(col));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return guard_verdict(dc.intact(), "csx_prim_expand_columns");
+}
+
+extern "C" int csx_prim_boundaries(uint32_t *sorted_key, int64_t count, int32_t nkeys, int32_t *ptr, int misalign_words) {
+    if (count < 0 || nkeys < 0 || !ptr || (count > 0 && !sorted_key) || misalign_words < 0 || misalign_words > 3) return CSX_EINVAL;
+    for (int64_t q = 0; q < count; q++)   // sorted keys in [0, nkeys): the kernel writes ptr[key]
+        if (sorted_key[q] >= (uint32_t)nkeys || (q > 0 && sorted_key[q - 1] > sorted_key[q])) return CSX_EINVAL;
+    CSX_TRY(require_ready());
+    DevBuf<uint32_t> kbuf;
+    GuardedOut<int32_t> dp;
+    uint32_t *dk = nullptr;
+    CSX_TRY(alloc_misaligned(kbuf, (size_t)count, misalign_words, &dk));
+    CSX_TRY(to_device(dk, (const uint32_t *)sorted_key, (size_t)count));
+    CSX_TRY(dp.put(ptr, (size_t)nkeys + 1));
+    CSX_TRY(boundaries_from_sorted(dk, count, nkeys, dp.d));
+    CSX_TRY(to_host(sorted_key, (const uint32_t *)dk, (size_t)count));
+    CSX_TRY(dp.take(ptr));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
+    return guard_verdict(dp.intact(), "csx_prim_boundaries");
+}
+
+extern "C" int csx_prim_sort(uint32_t *key, uint32_t *a, double *v, int64_t count, uint32_t key_limit, uint32_t *out_key,
+                             uint32_t *out_a, double *out_v, int32_t *expand_ptr, int32_t expand_n, int32_t *out_ptr, int32_t nkeys,
+                             int misalign_words) {
+    if (count < 0 || (count > 0 && !key) || misalign_words < 0 || misalign_words > 3) return CSX_EINVAL;
+    if (((a || expand_ptr) && !out_a) || (v && !out_v)) return CSX_EINVAL;   // an output missing where its input is given
+    if (a && expand_ptr) return CSX_EINVAL;   // the 32-bit payload is given or derived, not both
+    if (expand_ptr && (expand_n < 1 || !pointers_ok(expand_ptr, expand_n, count))) return CSX_EINVAL;
+    if (out_ptr) {
+        if (nkeys < 0) return CSX_EINVAL;
+        for (int64_t q = 0; q < count; q++)   // the last pass writes out_ptr[key]
+            if (key[q] >= (uint32_t)nkeys) return CSX_EINVAL;
+    }
+    CSX_TRY(require_ready());
+    hipStream_t s = ctx().stream;
+    const size_t cnt = (size_t)count;
+    DevBuf<uint32_t> kbuf, da;
+    DevBuf<double> dv;
+    DevBuf<int32_t> dxp;
+    GuardedOut<uint32_t> dok, doa;
+    GuardedOut<double> dov;
+    GuardedOut<int32_t> dop;
+    uint32_t *dk = nullptr;
+    CSX_TRY(alloc_misaligned(kbuf, cnt, misalign_words, &dk));
+    CSX_TRY(to_device(dk, (const uint32_t *)key, cnt));
+    if (a) CSX_TRY(upload(da, (const uint32_t *)a, cnt));
+    if (v) CSX_TRY(upload(dv, (const double *)v, cnt));
+    if (expand_ptr) CSX_TRY(upload(dxp, (const int32_t *)expand_ptr, (size_t)expand_n + 1));
+    const bool with_a = a || expand_ptr;
+    if (out_key) CSX_TRY(dok.put(out_key, cnt));
+    if (with_a) CSX_TRY(doa.put(out_a, cnt));
+    if (v) CSX_TRY(dov.put(out_v, cnt));
+    if (out_ptr) CSX_TRY(dop.put(out_ptr, (size_t)nkeys + 1));
+    const SortExtra ex{expand_ptr ? dxp.get() : nullptr, expand_n, out_ptr ? dop.d.get() : nullptr, nkeys};
+    CSX_TRY(stable_sort_by_key_ex(dk, a ? da.get() : nullptr, v ? dv.get() : nullptr, count, key_limit, out_key ? dok.d.get() : nullptr,
+                                  with_a ? doa.d.get() : nullptr, v ? dov.d.get() : nullptr, (expand_ptr || out_ptr) ? &ex : nullptr));
+    CSX_TRY(to_host(key, (const uint32_t *)dk, cnt));
+    if (a) CSX_TRY(to_host(a, (const uint32_t *)da.get(), cnt));
+    if (v) CSX_TRY(to_host(v, (const double *)dv.get(), cnt));
+    if (expand_ptr) CSX_TRY(to_host(expand_ptr, (const int32_t *)dxp.get(), (size_t)expand_n + 1));
+    if (out_key) CSX_TRY(dok.take(out_key));
+    if (with_a) CSX_TRY(doa.take(out_a));
+    if (v) CSX_TRY(dov.take(out_v));
+    if (out_ptr) CSX_TRY(dop.take(out_ptr));
+    CSX_HIP(hipStreamSynchronize(s));
+    return guard_verdict((!out_key || dok.intact()) && (!with_a || doa.intact()) && (!v || dov.intact()) && (!out_ptr || dop.intact()),
+                         "csx_prim_sort");
 }

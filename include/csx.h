@@ -245,6 +245,44 @@ int csx_transpose(csx_handle_t A, int values, csx_handle_t *out);
  * scan of c[0..n-1], c overwritten with p[0..n-1]; *total = sum. */
 int csx_cumsum(csx_handle_t p, csx_handle_t c, int64_t n, int64_t *total);
 
+/* The integer primitives under every structure of this library (csx_sort.hip), one at a time, for the tests: each csx_prim_*
+ * below copies its HOST arrays to device buffers, runs the one primitive as its callers run it, and copies the results back.  The
+ * device copies of the inputs are copied back over the host arrays as well, so that a primitive that wrote to an input shows;
+ * outputs are uploaded before the run, so that slots a primitive must leave alone can be told by what the caller put there, and
+ * every output array has guard bytes behind it on the device: a store past its end is CSX_ERUNTIME, with the reason.
+ * Production code calls none of them.  CSX_EINVAL, before anything touches the device: a negative count, a missing array, an
+ * output missing where its input is given, misalign_words outside 0 .. 3, column pointers that do not run from 0 to the count
+ * without decreasing, keys that are not below nkeys where a pointer array is written (or, for csx_prim_boundaries, not sorted).
+ * csx_prim_limits: the constants the primitives are cut by, without a device: out[9] = SCAN_TILE (elements a workgroup of the
+ * scan, and one level of its recursion), SM_TILE (the same of the reverse running minimum), RS_TILE (records a workgroup of the
+ * radix sort), RS_BINS (bins of a digit), RS_DESC_STARTS (column starts a tile descriptor holds), RS_SEGS (segments the chunk
+ * scan splits the chunks over), RS_CHUNK_MIN (tiles a chunk of the digit scan at least), RS_CHUNK_DIV (chunks at most),
+ * EXPAND_GRID_MAX (workgroups of four columns each that expand_columns launches at most).
+ * csx_prim_scan: out[0 .. n] = the exclusive sums of in[0 .. n-1] (scan_exclusive_i32), *total (or NULL) = out[n]; in_place != 0:
+ * one device array is input and output, as the tiled gaxpy plan and the symbolic Cholesky call it (`in` is then not written).
+ * csx_prim_suffix_min: p[r] = min(p[r .. n-1]) in place (suffix_min_i32).
+ * csx_prim_expand_columns: col[q] = j for q in [Ap[j], Ap[j+1]) (expand_columns); Ap[n] = nnz.
+ * csx_prim_boundaries: ptr[r] = the first position whose key is >= r, r in [0, nkeys] (boundaries_from_sorted).
+ * csx_prim_sort: stable_sort_by_key_ex.  a, v, out_key, expand_ptr, out_ptr may each be NULL as there (a and expand_ptr not both
+ * given); out_a is the sorted a, or with expand_ptr (expand_n columns over the count positions) the column of every sorted
+ * record; out_ptr[0 .. nkeys] the first slot of every key.
+ * misalign_words (both): the device key array starts that many 4-byte words past a 16-byte boundary, which the row indices of a
+ * wrapped matrix (csx_csc_wrap) may do; the kernels that read keys 16 bytes at a time then take their one-by-one path.
+ * csx_prim_sort_info (host state only, nothing is launched): what the last sort of this process decided, out[0 .. min(cap, 17)):
+ * bits (of key_limit - 1), passes, the digit width of passes 0 .. 3 (0: no such pass), nblocks (tiles), chunk, nchunks, packed
+ * ((a, v) travel as 12-byte records between passes), k16 (the short-key mode), the 4-byte words the key array lay past a 16-byte
+ * boundary, the k_rs_scatter instance passes 0 .. 3 launched (0 none, 1 keys only, 2 a, 3 v, 4 a + v arrays in and out, 5 arrays
+ * in and records out, 6 records in and out, 7 records in and arrays out, 8 / 9 / 10 the first / middle / last pass of the short-key
+ * mode), count (0: that sort was empty and launched no pass). */
+int csx_prim_limits(int32_t *out);
+int csx_prim_scan(int32_t *in, int32_t *out, int64_t n, int in_place, int64_t *total);
+int csx_prim_suffix_min(int32_t *p, int64_t n);
+int csx_prim_expand_columns(int32_t *Ap, int32_t n, int32_t nnz, int32_t *col);
+int csx_prim_boundaries(uint32_t *sorted_key, int64_t count, int32_t nkeys, int32_t *ptr, int misalign_words);
+int csx_prim_sort(uint32_t *key, uint32_t *a, double *v, int64_t count, uint32_t key_limit, uint32_t *out_key, uint32_t *out_a,
+                  double *out_v, int32_t *expand_ptr, int32_t expand_n, int32_t *out_ptr, int32_t nkeys, int misalign_words);
+int csx_prim_sort_info(int64_t *out, int32_t cap);
+
 /* cs_multiply (+ cs_scatter), csparse.py:1608-1642, :1961-1989: C = A*B with
  * each column of C in first-touch order; pattern only if A or B has no values.
  * p[] and i[] are exactly the reference's.  x[]: the products of an entry are summed by LDS / memory atomics in the
