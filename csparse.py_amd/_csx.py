@@ -231,6 +231,13 @@ _PROTOS = {
     "csx_hqr_stats": [H, _f64p],
     "csx_hqr_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "csx_level_schedule": [C.c_int32, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64, _i32p, C.POINTER(C.c_int32)],
+    "csx_gmres_limits": [_i32p],
+    "csx_gs_work_len": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "csx_gs_project": [H, C.c_int32, H, H, C.c_int64, C.c_int32, _i32p, C.c_int, _f64p],
+    "csx_gs_update": [H, C.c_int32, H, H, C.c_int64, C.c_int32, _i32p, C.c_int, _f64p, _f64p],
+    "csx_gs_scale": [H, H, C.c_int32, H, C.c_int64, C.c_int32, _i32p, _f64p],
+    "csx_gs_combine": [H, C.c_int32, H, H, C.c_int64, C.c_int32, _i32p, _f64p, _i32p],
+    "csx_gs_host": [C.c_int, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _i32p, C.c_int, _f64p, _i32p, _f64p],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -452,6 +459,42 @@ def prim_limits():
     out = (C.c_int32 * len(PRIM_LIMITS))()
     check(load().csx_prim_limits(out), "csx_prim_limits")
     return {name: int(out[k]) for k, name in enumerate(PRIM_LIMITS)}
+
+
+GMRES_LIMITS = ("GS_CHUNK", "GS_FAN", "GS_GROUP", "GS_TILE")
+GS_PROJECT, GS_UPDATE, GS_SCALE, GS_COMBINE = 0, 1, 2, 3
+
+
+def gmres_limits():
+    """the constants of the ordered sum and of the Gram-Schmidt kernels of gmres() (csx_gmres.hip), asked of the library; no GPU
+    needed: a dict by the names of GMRES_LIMITS (include/csx.h: csx_gmres_limits)"""
+    out = (C.c_int32 * len(GMRES_LIMITS))()
+    check(load().csx_gmres_limits(out), "csx_gmres_limits")
+    return {name: int(out[k]) for k, name in enumerate(GMRES_LIMITS)}
+
+
+def gs_work_len(rows, nrhs, nblocks):
+    """doubles of the work vector the csx_gs_* calls need for blocks of rows x nrhs and a basis of nblocks; no GPU needed"""
+    out = C.c_int64(0)
+    check(load().csx_gs_work_len(rows, nrhs, nblocks, C.byref(out)), "csx_gs_work_len")
+    return out.value
+
+
+def gs_host(op, V, W, mask, coef=None, length=None, negate=False, nv=None):
+    """csx_gs_host on numpy arrays: V (blocks, rows, nrhs), W (rows, nrhs) or None (combine), mask (nrhs).  GS_PROJECT -> h
+    (nv, nrhs); GS_UPDATE -> (new W, nrm2); GS_SCALE (nv: the slot) -> new V; GS_COMBINE -> U.  The inputs are left as they
+    are; where a column is masked, the outputs hold what the inputs held (h, nrm2: NaN; U: NaN).  No GPU needed."""
+    V = np.array(V, dtype=np.float64)
+    nb, rows, k = V.shape
+    nv = nb if nv is None else nv
+    W = None if W is None else np.array(W, dtype=np.float64).reshape(rows, k)
+    m = i32(mask)
+    cf = None if coef is None else f64(coef)
+    ln = None if length is None else i32(length)
+    out = {GS_PROJECT: np.full((nv, k), np.nan), GS_UPDATE: np.full(k, np.nan), GS_SCALE: None,
+           GS_COMBINE: np.full((rows, k), np.nan)}[op]
+    check(load().csx_gs_host(op, rows, k, nv, pd(V), pd(W), pi(m), 1 if negate else 0, pd(cf), pi(ln), pd(out)), "csx_gs_host")
+    return {GS_PROJECT: out, GS_UPDATE: (W, out), GS_SCALE: V, GS_COMBINE: out}[op]
 
 
 def _u32(a):

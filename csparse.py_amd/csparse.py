@@ -2767,6 +2767,184 @@ class _Refinable(object):
         _write_back(bhost, db, n * k)
         return {"omega0": w0, "omega": w, "rnorm": rn, "steps": steps, "solves": solves}
 
+    def gmres(self, b, restart=16, maxit=64, inner_tol=2.0 ** -26, trans=False):
+        """solve, then restarted GMRES with this factor as the preconditioner on the columns whose backward error is above
+        2^-52; b is overwritten with x.  Where refine() needs the factor to contract, this needs only a Krylov
+        space that holds the correction: a factor that differs from A by rank p ends in p + 1 inner steps.  Every column is its
+        own system.  restart: inner steps of a cycle (the basis takes restart blocks of b's size on the device; MemoryError
+        with the byte count when they cannot be had); maxit: inner steps per column at most (0: solve() and the backward
+        error); inner_tol: a column leaves its cycle once the Arnoldi estimate of its residual is below inner_tol times the
+        cycle's first residual.  The true residual is recomputed after every cycle and the cycle is kept only where it lowers
+        the column's omega (strictly): omega <= omega0 always, a refused cycle leaves the column bit for bit as it was and
+        stops it.  refine()'s dict, and iters (inner steps per column), cycles (accepted cycles per column; steps is the same
+        array), resid_est (the last Arnoldi estimate over the cycle's first residual; 1.0 before any step).  ValueError for
+        restart < 1, maxit < 0, or inner_tol outside (0, 1)."""
+        return self._gmres(b, restart, maxit, inner_tol, trans, self._operator)
+
+    def _gmres(self, b, restart, maxit, inner_tol, trans, operator):
+        """operator: a callable that gives the context manager of the operator's handle (taken after the arguments are
+        checked)"""
+        m, maxit, tol = int(restart), int(maxit), float(inner_tol)
+        if m < 1 or m > 0x7FFFFFFE:
+            raise ValueError("gmres: restart must be at least 1 (and a 32-bit count of blocks)")
+        if maxit < 0:
+            raise ValueError("gmres: maxit must not be negative")
+        if not 0.0 < tol < 1.0:
+            raise ValueError("gmres: inner_tol must lie in (0, 1)")
+        n, eps, trans = self._rn, self.EPS, bool(trans)
+        db, bhost = _vec_in(b, n, "b")
+        k = db.k
+        from_list = not isinstance(b, dvec)
+        lib = _csx.lib()
+
+        def mask(v):
+            return _csx.pi(_csx.i32(v))
+
+        B = db.copy()
+        X = db
+        with operator() as hA, np.errstate(all="ignore"):
+            self._solve_block(X, trans, from_list)
+            R = dvec(n, k)
+            w, rn = self._residual_into(hA, X, B, R, k, trans)
+            w0 = w.copy()
+            iters, cycles, solves = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.int64), 1
+            est = np.ones(k)
+            live = w > eps                                   # a NaN column is never live
+            space = None
+            while (live & (iters < maxit)).any():
+                if space is None:
+                    space = _GmresSpace(n, k, m)
+                V, Vj, work, Z, Wb, Zero, Xc, Rc = space.blocks
+                cyc = live & (iters < maxit)
+                # beta = sqrt(ordered sum r r);  V_0 = r / beta
+                _csx.check(lib.csx_block_select_cols(R.handle, Vj[0].handle, n, k, mask(cyc)), "csx_block_select_cols")
+                beta = np.full(k, np.nan)
+                _csx.check(lib.csx_gs_project(V.handle, 1, R.handle, work.handle, n, k, mask(cyc), 0, _csx.pd(beta)),
+                           "csx_gs_project")
+                beta = np.sqrt(beta)
+                cyc &= np.isfinite(beta) & (beta > 0.0)      # r r under- or overflowed: the column stops
+                live &= cyc
+                if not cyc.any():
+                    break
+                _csx.check(lib.csx_gs_scale(R.handle, V.handle, 0, work.handle, n, k, mask(cyc), _csx.pd(beta)), "csx_gs_scale")
+                arn = [_Arnoldi(m, float(beta[c])) if cyc[c] else None for c in range(k)]
+                act = cyc.copy()
+                for j in range(m):
+                    if not act.any():
+                        break
+                    # Z = M^-1 V_j;  Wb = 0 - A Z (exactly -(A Z): the two calls that read it first take the sign up)
+                    _csx.check(lib.csx_vec_copy(Vj[j].handle, Z.handle), "csx_vec_copy")
+                    self._solve_block(Z, trans, from_list)
+                    solves += 1
+                    self._residual_into(hA, Z, Zero, Wb, k, trans)
+                    nv, am = j + 1, mask(act)
+                    h1, h2, nrm2 = np.zeros((nv, k)), np.zeros((nv, k)), np.zeros(k)
+                    _csx.check(lib.csx_gs_project(V.handle, nv, Wb.handle, work.handle, n, k, am, 1, _csx.pd(h1)), "csx_gs_project")
+                    _csx.check(lib.csx_gs_update(V.handle, nv, Wb.handle, work.handle, n, k, am, 1, _csx.pd(h1), _csx.pd(nrm2)),
+                               "csx_gs_update")
+                    _csx.check(lib.csx_gs_project(V.handle, nv, Wb.handle, work.handle, n, k, am, 0, _csx.pd(h2)), "csx_gs_project")
+                    _csx.check(lib.csx_gs_update(V.handle, nv, Wb.handle, work.handle, n, k, am, 0, _csx.pd(h2), _csx.pd(nrm2)),
+                               "csx_gs_update")
+                    hnext = np.sqrt(nrm2)
+                    stay = act.copy()
+                    for c in np.flatnonzero(act):
+                        iters[c] += 1
+                        left = arn[c].step(h1[:, c] + h2[:, c], float(hnext[c]), tol)
+                        est[c] = arn[c].estimate
+                        stay[c] = not (left or iters[c] >= maxit)
+                    if j + 1 < m and stay.any():
+                        _csx.check(lib.csx_gs_scale(Wb.handle, V.handle, j + 1, work.handle, n, k, mask(stay), _csx.pd(hnext)),
+                                   "csx_gs_scale")
+                    act = stay
+                # U = V y;  D = M^-1 U;  the candidate, its true residual, and the acceptance rule of refine()
+                length = np.array([a.length if a is not None else 0 for a in arn], dtype=np.int32)
+                y = np.zeros((int(length.max()), k))
+                for c in np.flatnonzero(cyc):
+                    y[:length[c], c] = arn[c].solution()
+                _csx.check(lib.csx_gs_combine(V.handle, y.shape[0], Z.handle, work.handle, n, k, mask(cyc), _csx.pd(y),
+                                              _csx.pi(length)), "csx_gs_combine")
+                self._solve_block(Z, trans, from_list)
+                solves += 1
+                _csx.check(lib.csx_block_add_cols(X.handle, Z.handle, Xc.handle, n, k, mask(cyc)), "csx_block_add_cols")
+                wc, rnc = self._residual_into(hA, Xc, B, Rc, k, trans)
+                accept = cyc & (wc < w)
+                if accept.any():
+                    _csx.check(lib.csx_block_select_cols(Xc.handle, X.handle, n, k, mask(accept)), "csx_block_select_cols")
+                    _csx.check(lib.csx_block_select_cols(Rc.handle, R.handle, n, k, mask(accept)), "csx_block_select_cols")
+                cycles += accept
+                live = accept & (wc > eps)
+                w, rn = np.where(accept, wc, w), np.where(accept, rnc, rn)
+        _write_back(bhost, db, n * k)
+        return {"omega0": w0, "omega": w, "rnorm": rn, "steps": cycles, "cycles": cycles, "iters": iters, "solves": solves,
+                "resid_est": est}
+
+
+class _Arnoldi(object):
+    """one column's Hessenberg matrix under its Givens rotations, in plain double operations: column j comes in
+    as (h[0 .. j], hnext); the rotations so far are applied to it, a new one (c, s) = (a, b) / sqrt(a a + b b) (no hypot;
+    (1, 0) when both are zero) clears hnext and turns g; |g[j + 1]| estimates the residual"""
+
+    def __init__(self, m, beta):
+        self.R = np.zeros((m, m))
+        self.cs, self.sn = np.zeros(m), np.zeros(m)
+        self.g = np.zeros(m + 1)
+        self.g[0] = self.beta = beta
+        self.length, self.estimate = 0, 1.0
+
+    def step(self, h, hnext, tol):
+        """-> whether the column leaves its cycle: the estimate is at most tol beta, or hnext is zero (or no number)"""
+        j, R, g = self.length, self.R, self.g
+        col = np.array(h, dtype=np.float64)
+        for i in range(j):
+            a, b2 = col[i], col[i + 1]
+            col[i] = self.cs[i] * a + self.sn[i] * b2
+            col[i + 1] = self.cs[i] * b2 - self.sn[i] * a
+        a, b2 = col[j], hnext
+        d = np.sqrt(a * a + b2 * b2)
+        c, s = (1.0, 0.0) if d == 0.0 else (a / d, b2 / d)
+        col[j] = c * a + s * b2
+        g[j + 1] = -(s * g[j])
+        g[j] = c * g[j]
+        self.cs[j], self.sn[j] = c, s
+        R[:j + 1, j] = col
+        self.length = j + 1
+        self.estimate = abs(g[j + 1]) / self.beta
+        return bool(abs(g[j + 1]) <= tol * self.beta) or not hnext > 0.0
+
+    def solution(self):
+        """y of the rotated triangle: back substitution, the terms of a row subtracted in ascending order"""
+        jl, R = self.length, self.R
+        y = np.zeros(jl)
+        for i in range(jl - 1, -1, -1):
+            s = self.g[i]
+            for l in range(i + 1, jl):
+                s = s - R[i, l] * y[l]
+            y[i] = s / R[i, i]
+        return y
+
+
+class _GmresSpace(object):
+    """the device blocks of one gmres() call, allocated once: the basis (one vector of `restart` blocks, and a view of every
+    block), the work vector of the csx_gs_* calls, Z (the block a solve runs in), Wb (the product), a zero right-hand side, the
+    candidate and its residual"""
+
+    def __init__(self, n, k, m):
+        count = n * k
+        nbytes = 8 * (count * (m + 5) + _csx.gs_work_len(n, k, m))
+        try:
+            V = dvec(count * m)
+            base = V.device_ptr() or 0
+            views = []
+            for j in range(m):
+                h = _csx.new_handle()
+                _csx.check(_csx.lib().csx_vec_wrap(base + 8 * count * j, count, h), "csx_vec_wrap")
+                views.append(dvec(n, k, _handle=h))
+            work = dvec(_csx.gs_work_len(n, k, m))
+            rest = [dvec(n, k) for _ in range(5)]
+        except _csx.CsxError as e:
+            raise MemoryError("gmres: cannot allocate the basis of %d blocks and its work space, %d bytes (%s)" % (m, nbytes, e))
+        self.blocks = [V, views, work] + rest
+
 
 class _SymRefinable(_Refinable):
     """backward_error / refine / condest / operator_info of the solvers of a SYMMETRIC matrix held in the upper triangle
@@ -2806,6 +2984,13 @@ class _SymRefinable(_Refinable):
         columns whose backward error is above 2^-52; b is overwritten with x.  With A= a nearby matrix this is the
         stale-factor iteration: the factor preconditions, A is solved.  _Refinable.refine's loop and result."""
         return self._refine(b, maxit, False, self._operator_for(A))
+
+    def gmres(self, b, restart=16, maxit=64, inner_tol=2.0 ** -26, A=None):
+        """solve, then restarted GMRES against the operator (see backward_error) with this factor as the preconditioner;
+        b is overwritten with x.  With A= a nearby matrix the stale factor preconditions and A is solved: a matrix that differs
+        from the factored one in r rows ends in r + 1 inner steps, however far apart the two are.  _Refinable.gmres's loop,
+        arguments and result."""
+        return self._gmres(b, restart, maxit, inner_tol, False, lambda: self._operator_for(A))
 
     def condest(self, A=None):
         """an estimate of cond_1(S) = |S|_1 |S^-1|_1 of the operator (see backward_error): csx_norm1_sym times
@@ -3631,6 +3816,10 @@ def hqrsol_factor(A, order=0):
         def refine(self, b, maxit=5, trans=False):
             self._square_only("refine")
             return _Refinable.refine(self, b, maxit, trans)
+
+        def gmres(self, b, restart=16, maxit=64, inner_tol=2.0 ** -26, trans=False):
+            self._square_only("gmres")
+            return _Refinable.gmres(self, b, restart, maxit, inner_tol, trans)
 
         def condest(self):
             self._square_only("condest")

@@ -1633,3 +1633,99 @@ extern "C" int csx_hqr_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap,
     }
     return CSX_OK;
 }
+
+// ---- the Gram-Schmidt rule of restarted GMRES (csx_gmres.hip) on host arrays ----
+#include "csx_gs.h"
+
+extern "C" int csx_gmres_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    out[0] = GS_CHUNK;
+    out[1] = GS_FAN;
+    out[2] = GS_GROUP;
+    out[3] = GS_TILE;
+    return CSX_OK;
+}
+
+extern "C" int csx_gs_work_len(int64_t rows, int32_t nrhs, int32_t nblocks, int64_t *len) {   // (no device needed)
+    if (!len || rows < 0 || rows > ((int64_t)1 << 40) || nrhs < 1 || nblocks < 1) return CSX_EINVAL;
+    *len = gs_work_len(rows, nrhs, nblocks);
+    return CSX_OK;
+}
+
+namespace {
+// the inner levels of the ordered sum over the leaf sums in `node`
+double gs_tree(std::vector<double> &node) {
+    size_t count = node.size();
+    while (count > 1) {
+        const size_t next = (count + GS_FAN - 1) / GS_FAN;
+        for (size_t j = 0; j < next; j++) {
+            double s = 0.0;
+            for (size_t i = j * GS_FAN; i < std::min(count, (j + 1) * GS_FAN); i++) s = s + node[i];
+            node[j] = s;
+        }
+        count = next;
+    }
+    return node[0];
+}
+}  // namespace
+
+// op 0 project: out[i nrhs + c] = ordered sum of V_i[:, c] (+-W[:, c]), i < nv
+// op 1 update:  W <- (+-W) - coef[0, c] V_0 - ... in ascending i; out[c] = ordered sum of the squares of the new W[:, c]
+// op 2 scale:   V_nv[r, c] = W[r, c] / coef[c]   (nv is the slot)
+// op 3 combine: out[r nrhs + c] = coef[0, c] V_0[r, c] + ... over i < len[c]: the first product, then rounded additions
+extern "C" int csx_gs_host(int op, int64_t rows, int32_t nrhs, int32_t nv, double *V, double *W, const int32_t *mask, int negate,
+                           const double *coef, const int32_t *len, double *out) {
+#pragma clang fp contract(off)
+    if (op < 0 || op > 3 || rows < 0 || nrhs < 1 || !mask || !V || (op != 3 && !W)) return CSX_EINVAL;
+    if ((op == 2 ? nv < 0 : nv < 1) || (op != 0 && !coef) || (op != 2 && !out) || (op == 3 && !len)) return CSX_EINVAL;
+    const int64_t block = rows * nrhs;
+    const size_t nch = (size_t)gs_chunks(rows);
+    std::vector<double> node(nch);
+    for (int32_t c = 0; c < nrhs; c++) {
+        if (!mask[c]) continue;
+        if (op == 0) {
+            for (int32_t i = 0; i < nv; i++) {
+                const double *Vi = V + i * block;
+                for (size_t l = 0; l < nch; l++) {
+                    double s = 0.0;
+                    for (int64_t r = (int64_t)l * GS_CHUNK; r < std::min(rows, (int64_t)(l + 1) * GS_CHUNK); r++) {
+                        const double w = negate ? -W[r * nrhs + c] : W[r * nrhs + c];
+                        const double p = Vi[r * nrhs + c] * w;
+                        s = s + p;
+                    }
+                    node[l] = s;
+                }
+                out[(int64_t)i * nrhs + c] = gs_tree(node);
+            }
+        } else if (op == 1) {
+            for (size_t l = 0; l < nch; l++) {
+                double s = 0.0;
+                for (int64_t r = (int64_t)l * GS_CHUNK; r < std::min(rows, (int64_t)(l + 1) * GS_CHUNK); r++) {
+                    double w = negate ? -W[r * nrhs + c] : W[r * nrhs + c];
+                    for (int32_t i = 0; i < nv; i++) {
+                        const double p = coef[(int64_t)i * nrhs + c] * V[i * block + r * nrhs + c];
+                        w = w - p;
+                    }
+                    W[r * nrhs + c] = w;
+                    const double q = w * w;
+                    s = s + q;
+                }
+                node[l] = s;
+            }
+            out[c] = gs_tree(node);
+        } else if (op == 2) {
+            for (int64_t r = 0; r < rows; r++) V[nv * block + r * nrhs + c] = W[r * nrhs + c] / coef[c];
+        } else {
+            if (len[c] < 0 || len[c] > nv) return CSX_EINVAL;
+            for (int64_t r = 0; r < rows; r++) {
+                double u = 0.0;
+                for (int32_t i = 0; i < len[c]; i++) {
+                    const double p = coef[(int64_t)i * nrhs + c] * V[i * block + r * nrhs + c];
+                    u = i == 0 ? p : u + p;
+                }
+                out[r * nrhs + c] = u;
+            }
+        }
+    }
+    return CSX_OK;
+}

@@ -1203,6 +1203,42 @@ int csx_hqr_window(int32_t *entries, int32_t *run_levels);
 int csx_level_schedule(int32_t nlev, const int32_t *level_ptr, int32_t waves, int32_t run_levels, const int64_t *work,
                        int64_t run_work, int32_t *launches, int32_t *count);
 
+/* ---- the block kernels of restarted GMRES (csx_gmres.hip): classical Gram-Schmidt on a block of columns against
+ * a basis of blocks, every column its own system.  Blocks are row-major rows x nrhs.  The basis V is ONE vector holding
+ * consecutive blocks V_0, V_1, ...; a call addresses its first nv.  mask: nrhs host int32; a column with mask[c] == 0 is not
+ * written (on the device or in a host output array) and has no effect on any other.  work: a vector of at least
+ * csx_gs_work_len(rows, nrhs, nv) doubles that the calls stage their coefficients and partial sums in (nothing else is
+ * allocated); its contents mean nothing between calls.
+ * Value rule (device and csx_gs_host alike, fp contract off): every product is rounded, then added or subtracted.  A sum over
+ * the rows of a column is the ORDERED SUM: leaves are GS_CHUNK consecutive rows added in ascending order from +0.0, an inner node
+ * is GS_FAN consecutive children added in ascending order from +0.0, levels repeat until one value is left.  The tree depends
+ * on `rows` alone.
+ *   csx_gs_project: h[i nrhs + c] = ordered sum over r of V_i[r, c] * w, w = W[r, c], or -W[r, c] when negate != 0; i < nv.
+ *   csx_gs_update:  W[r, c] <- w - h[0, c] V_0[r, c] - ... - h[nv-1, c] V_{nv-1}[r, c], ascending i, each product and each
+ *                   subtraction rounded (w as above); nrm2[c] = ordered sum of the squares of the new W[:, c], same pass.
+ *   csx_gs_scale:   V_slot[r, c] = W[r, c] / s[c] (IEEE division).
+ *   csx_gs_combine: U[r, c] = y[0, c] V_0[r, c] + ... + y[len[c]-1, c] V_{len[c]-1}[r, c]: the first product as it is, then one
+ *                   rounded addition per further product; +0.0 for len[c] == 0.  y: nv x nrhs.
+ * CSX_EINVAL: an unknown handle, a null mask or host array, nrhs < 1, rows < 0, nv < 1 (slot < 0), a basis shorter than nv
+ * (slot + 1) blocks, a block W / U shorter than rows nrhs, a work vector that is too short, len[c] outside 0 .. nv on a live
+ * column, or device ranges that overlap.  rows == 0: the sums are +0.0.
+ * csx_gmres_limits: out[4] = GS_CHUNK, GS_FAN, GS_GROUP (basis vectors one pass of csx_gs_project carries in registers: W
+ * crosses memory once per GS_GROUP of them), GS_TILE (rows per coefficient load in update / combine); no device needed.
+ * csx_gs_host: op 0 .. 3 = project / update / scale / combine on host arrays: V the basis (scale writes block nv of it), W the
+ * block (update overwrites it; unused by combine), coef = h / s / y, out = h / nrm2 / - / U. */
+int csx_gmres_limits(int32_t *out);
+int csx_gs_work_len(int64_t rows, int32_t nrhs, int32_t nblocks, int64_t *len);
+int csx_gs_project(csx_handle_t V, int32_t nv, csx_handle_t W, csx_handle_t work, int64_t rows, int32_t nrhs, const int32_t *mask,
+                   int negate, double *h);
+int csx_gs_update(csx_handle_t V, int32_t nv, csx_handle_t W, csx_handle_t work, int64_t rows, int32_t nrhs, const int32_t *mask,
+                  int negate, const double *h, double *nrm2);
+int csx_gs_scale(csx_handle_t W, csx_handle_t V, int32_t slot, csx_handle_t work, int64_t rows, int32_t nrhs, const int32_t *mask,
+                 const double *s);
+int csx_gs_combine(csx_handle_t V, int32_t nv, csx_handle_t U, csx_handle_t work, int64_t rows, int32_t nrhs, const int32_t *mask,
+                   const double *y, const int32_t *len);
+int csx_gs_host(int op, int64_t rows, int32_t nrhs, int32_t nv, double *V, double *W, const int32_t *mask, int negate,
+                const double *coef, const int32_t *len, double *out);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
