@@ -238,6 +238,12 @@ _PROTOS = {
     "csx_gs_scale": [H, H, C.c_int32, H, C.c_int64, C.c_int32, _i32p, _f64p],
     "csx_gs_combine": [H, C.c_int32, H, H, C.c_int64, C.c_int32, _i32p, _f64p, _i32p],
     "csx_gs_host": [C.c_int, C.c_int64, C.c_int32, C.c_int32, _f64p, _f64p, _i32p, C.c_int, _f64p, _i32p, _f64p],
+    "csx_bgs_limits": [_i32p],
+    "csx_bgs_work_len": [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
+    "csx_bgs_gram": [H, C.c_int32, C.c_int32, H, C.c_int32, H, C.c_int64, C.c_int, _f64p],
+    "csx_bgs_update": [H, C.c_int32, C.c_int32, H, C.c_int32, H, C.c_int64, _f64p],
+    "csx_bgs_combine": [H, C.c_int32, C.c_int32, H, C.c_int32, H, C.c_int64, _f64p],
+    "csx_bgs_host": [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f64p, _f64p, C.c_int, _f64p, _f64p],
     "csx_gen_grand": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_grand_uniform": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
     "csx_gen_gspd": [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(H)],
@@ -495,6 +501,40 @@ def gs_host(op, V, W, mask, coef=None, length=None, negate=False, nv=None):
            GS_COMBINE: np.full((rows, k), np.nan)}[op]
     check(load().csx_gs_host(op, rows, k, nv, pd(V), pd(W), pi(m), 1 if negate else 0, pd(cf), pi(ln), pd(out)), "csx_gs_host")
     return {GS_PROJECT: out, GS_UPDATE: (W, out), GS_SCALE: V, GS_COMBINE: out}[op]
+
+
+BGS_LIMITS = ("GS_CHUNK", "GS_FAN", "BGS_MAXW", "BGS_GROUP", "BGS_TILE")
+BGS_GRAM, BGS_UPDATE, BGS_COMBINE = 0, 1, 2
+
+
+def bgs_limits():
+    """the constants of the ordered sum and of the block kernels of eigsh() (csx_bgs.hip), asked of the library; no GPU needed:
+    a dict by the names of BGS_LIMITS (include/csx.h: csx_bgs_limits)"""
+    out = (C.c_int32 * len(BGS_LIMITS))()
+    check(load().csx_bgs_limits(out), "csx_bgs_limits")
+    return {name: int(out[k]) for k, name in enumerate(BGS_LIMITS)}
+
+
+def bgs_work_len(rows, b, q, nblocks):
+    """doubles of the work vector the csx_bgs_* calls need for rows x b basis blocks (nblocks at most) and a rows x q block;
+    no GPU needed"""
+    out = C.c_int64(0)
+    check(load().csx_bgs_work_len(rows, b, q, nblocks, C.byref(out)), "csx_bgs_work_len")
+    return out.value
+
+
+def bgs_host(op, V, W=None, coef=None, negate=False, q=None):
+    """csx_bgs_host on numpy arrays: V (blocks, rows, b), W (rows, q) or None (combine: q from coef (blocks, b, q), or given).
+    BGS_GRAM -> sums (blocks, b, q); BGS_UPDATE -> the new W; BGS_COMBINE -> U.  The inputs are left as they are.  No GPU needed."""
+    V = np.array(V, dtype=np.float64)
+    nv, rows, b = V.shape
+    W = None if W is None else np.array(W, dtype=np.float64)
+    W = W[:, None] if W is not None and W.ndim == 1 else W
+    cf = None if coef is None else f64(coef)
+    q = W.shape[1] if W is not None else (int(q) if q is not None else cf.shape[-1])
+    out = {BGS_GRAM: np.full((nv, b, q), np.nan), BGS_UPDATE: None, BGS_COMBINE: np.full((rows, q), np.nan)}[op]
+    check(load().csx_bgs_host(op, rows, b, q, nv, pd(V), pd(W), 1 if negate else 0, pd(cf), pd(out)), "csx_bgs_host")
+    return W if op == BGS_UPDATE else out
 
 
 def _u32(a):

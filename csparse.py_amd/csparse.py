@@ -2946,6 +2946,96 @@ class _GmresSpace(object):
         self.blocks = [V, views, work] + rest
 
 
+EIG_PIVOT = 2.0 ** -20     # a pivot of the scaled Cholesky factor below this in the first pass: the block is dependent (§29)
+
+
+def _eig_dense(what, *args):
+    """The small dense steps of eigsh(), in numpy on the host; the restated loop of the tests calls this very
+    function, so the two runs differ in the block operations alone.
+    "cholqr", G (b x b, the Gram matrix of a block in the M inner product), first (the first of the two passes)
+        -> (R, inv(R)) with R'R = G, or None on breakdown: G is taken as its upper triangle mirrored and scaled to a unit
+        diagonal by d = 1 / sqrt(diag G); L = cholesky; R = L' diag(1 / d).  Breakdown: a diagonal entry of G that is not
+        positive or not finite, a Cholesky factorisation that fails, or (first pass) a pivot of L below EIG_PIVOT.
+    "ritz", T (m x m, block upper triangle filled), B (the sub-diagonal block that follows T, or None after a breakdown)
+        -> (theta, S, estimate): eigh of T's upper triangle mirrored, ordered by descending |theta| (stable);
+        estimate[c] = |B S[last rows, c]|_2 / |theta[c]| (0 with no B)."""
+    with np.errstate(all="ignore"):
+        if what == "cholqr":
+            G, first = np.asarray(args[0], dtype=np.float64), bool(args[1])
+            G = np.triu(G) + np.triu(G, 1).T
+            d0 = np.diag(G).copy()
+            if not (np.isfinite(d0).all() and (d0 > 0.0).all()):
+                return None
+            d = 1.0 / np.sqrt(d0)
+            Gs = G * d[:, None] * d[None, :]
+            if not np.isfinite(Gs).all():
+                return None
+            try:
+                L = np.linalg.cholesky(Gs)
+            except np.linalg.LinAlgError:
+                return None
+            piv = np.diag(L)
+            if not np.isfinite(L).all() or not (piv > 0.0).all() or (first and piv.min() < EIG_PIVOT):
+                return None
+            R = L.T * (1.0 / d)[None, :]
+            Rinv = np.linalg.solve(R, np.eye(R.shape[0]))
+            return np.ascontiguousarray(R), np.ascontiguousarray(np.triu(Rinv))
+        if what == "ritz":
+            T = np.asarray(args[0], dtype=np.float64)
+            B = args[1]
+            T = np.triu(T) + np.triu(T, 1).T
+            theta, S = np.linalg.eigh(T)
+            order = np.argsort(-np.abs(theta), kind="stable")
+            theta, S = theta[order], np.ascontiguousarray(S[:, order])
+            if B is None:
+                est = np.zeros(len(theta))
+            else:
+                b = B.shape[0]
+                est = np.sqrt(((B @ S[-b:, :]) ** 2).sum(axis=0)) / np.abs(theta)
+            return theta, S, est
+    raise ValueError("_eig_dense: " + repr(what))
+
+
+class _EigSpace(object):
+    """the device blocks of one eigsh() call, allocated once: the bases Q and P (one vector of `blocks` n x b blocks each and a
+    view of every block; P is Q itself without a mass matrix), the work vector of the csx_bgs_* / csx_gs_* calls, and six working
+    blocks of n x wide doubles with an n x b and n x k view of each"""
+
+    def __init__(self, n, b, blocks, wide, mass):
+        count = n * b
+        nwork = max(_csx.bgs_work_len(n, b, wide, blocks), _csx.bgs_work_len(n, wide, wide, 1), _csx.gs_work_len(n, wide, 1))
+        self.nbytes = 8 * (count * blocks * (2 if mass else 1) + 6 * n * wide + nwork)
+        self.n, self.b = n, b
+        try:
+            self.Q, self.Qj = self._basis(n, b, blocks)
+            self.P, self.Pj = self._basis(n, b, blocks) if mass else (self.Q, self.Qj)
+            self.work = dvec(nwork)
+            self._flat = [dvec(n * wide) for _ in range(6)]
+        except _csx.CsxError as e:
+            raise MemoryError("eigsh: cannot allocate the bases of %d blocks and the working blocks, %d bytes (%s)"
+                              % (blocks, self.nbytes, e))
+        self._views = {}
+        self._flat[5].fill(0.0)
+
+    @staticmethod
+    def _view(base, n, k):
+        h = _csx.new_handle()
+        _csx.check(_csx.lib().csx_vec_wrap(base, n * k, h), "csx_vec_wrap")
+        return dvec(n, k, _handle=h)
+
+    def _basis(self, n, b, blocks):
+        V = dvec(n * b * blocks)
+        base = V.device_ptr() or 0
+        return V, [self._view(base + 8 * n * b * j, n, b) for j in range(blocks)]
+
+    def blocks(self, k):
+        """the six working blocks as n x k: W, S (the first pass's block; X at a verification), N (a product, negated), B, R and
+        the zero right-hand side"""
+        if k not in self._views:
+            self._views[k] = [self._view(f.device_ptr() or 0, self.n, k) for f in self._flat]
+        return self._views[k]
+
+
 class _SymRefinable(_Refinable):
     """backward_error / refine / condest / operator_info of the solvers of a SYMMETRIC matrix held in the upper triangle
     (cholsol_factor, ldlsol_factor), measured with csx_residual_sym_block against the factored matrix, the
@@ -2991,6 +3081,164 @@ class _SymRefinable(_Refinable):
         from the factored one in r rows ends in r + 1 inner steps, however far apart the two are.  _Refinable.gmres's loop,
         arguments and result."""
         return self._gmres(b, restart, maxit, inner_tol, False, lambda: self._operator_for(A))
+
+    def eigsh(self, nev, M=None, sigma=0.0, block=None, maxblocks=32, tol=2.0 ** -30, seed=0, v0=None, A=None):
+        """The nev eigenpairs of K x = lambda M x nearest sigma, by unrestarted shift-invert block Lanczos with full
+        reorthogonalisation on this factor.  The factor stands for A = K - sigma M: every step is one block
+        solve with it; the operator (see backward_error; A=) is what the residuals are measured against.  M: an SPD matrix in
+        the upper triangle of a square CSC `cs`, or None for the identity.  sigma is only added back into the values.
+        block: columns of a basis block, 1 .. BGS_MAXW (default min(BGS_MAXW, max(nev, 8)) rounded up to even); capped by n.
+        maxblocks: a memory cap -- two bases of maxblocks blocks (one without M) and six working blocks, all allocated before
+        the loop; MemoryError with the byte count when they cannot be had.  Running out of blocks returns what there is with
+        converged False.  tol: a pair has converged when |M x / theta - A x|_2 <= tol |M x / theta|_2, theta = 1 / (lambda -
+        sigma).  v0: an n x block starting block (default numpy.random.default_rng(seed).random((n, block)) - 0.5).
+        A dict: values (sigma + mu by ascending |mu|), vectors (a dvec n x nev, M-orthonormal to rounding), resid, omega,
+        estimate, converged (one entry per pair), blocks (basis blocks of the Ritz space), solves, products, breakdown (the
+        space became invariant to working precision: the pairs are final; fewer than nev are returned if it held fewer), and on
+        ldlsol_factor below: the negative pivots of inertia(), the number of eigenvalues under sigma (None when a pivot was
+        perturbed).  ValueError for nev < 1, nev > (maxblocks - 1) block, block outside 1 .. BGS_MAXW, tol outside (0, 1), an M or
+        v0 of another shape, or a v0 with dependent columns; TypeError for a pattern-only M."""
+        n, maxw = self._rn, _csx.bgs_limits()["BGS_MAXW"]
+        nev, nb, tol, sigma = int(nev), int(maxblocks), float(tol), float(sigma)
+        if nev < 1:
+            raise ValueError("eigsh: nev must be at least 1")
+        if block is None:
+            b = min(maxw, max(nev, 8))
+            b = min(maxw, b + (b & 1))
+        else:
+            b = int(block)
+            if b < 1 or b > maxw:
+                raise ValueError("eigsh: block must lie in 1 .. %d (BGS_MAXW)" % maxw)
+        b = min(b, n)
+        nb = min(nb, max(2, n // max(b, 1)))           # a basis holds n vectors at the most
+        if not 0.0 < tol < 1.0:
+            raise ValueError("eigsh: tol must lie in (0, 1)")
+        if b < 1 or nev > (nb - 1) * b or nb > 0x7FFFFFFE:
+            raise ValueError("eigsh: nev must be at most (maxblocks - 1) * block = %d" % (max(nb - 1, 0) * max(b, 0)))
+        mass = M is not None
+        if mass:
+            if not CS_CSC(M) or M.m != n or M.n != n:
+                raise ValueError("eigsh: M must be a square CSC matrix of order %d" % n)
+            if not _meta(M)[1]:
+                raise TypeError("eigsh: M is a pattern-only matrix")
+        if v0 is None:
+            start = np.random.default_rng(seed).random((n, b)) - 0.5
+        else:
+            start = np.ascontiguousarray(v0, dtype=np.float64)
+            if start.shape != (n, b):
+                raise ValueError("eigsh: v0 must be an n x block array, %d x %d" % (n, b))
+        operator = self._operator_for(A)
+        lib = _csx.lib()
+        wide = max(b, min(nev, maxw))
+        chunks = [(c0, min(c0 + maxw, nev)) for c0 in range(0, nev, maxw)]
+        sgn = -1.0 if mass else 1.0                    # W holds sgn times the vector: the products come out negated (below)
+        count = {"solves": 0, "products": 0}
+
+        def gram(V, nv, Y, q, negate):
+            out = np.empty((nv * b, q))
+            _csx.check(lib.csx_bgs_gram(V.handle, nv, b, Y.handle, q, space.work.handle, n, negate, _csx.pd(out)), "csx_bgs_gram")
+            return out
+
+        def update(V, nv, X, H):
+            _csx.check(lib.csx_bgs_update(V.handle, nv, b, X.handle, b, space.work.handle, n, _csx.pd(_csx.f64(H))),
+                       "csx_bgs_update")
+
+        def combine(V, nv, U, q, S):
+            _csx.check(lib.csx_bgs_combine(V.handle, nv, b, U.handle, q, space.work.handle, n, _csx.pd(_csx.f64(S))),
+                       "csx_bgs_combine")
+
+        def product(X, out, k):
+            """out = 0 - M X: exactly -(M X); every reader takes the sign up"""
+            self._residual_into(hM, X, space.blocks(k)[5], out, k, False)
+            count["products"] += 1
+
+        def orthonormalise(src, s, dst):
+            """dst = the block src (held as s times itself) made M-orthonormal by two Cholesky-QR passes -> R2 R1, or None"""
+            R = []
+            for first, blk, sign, to in ((True, src, s, S1), (False, S1, 1.0, dst)):
+                if mass:
+                    product(blk, N, b)
+                    G = gram(blk, 1, N, b, 1)
+                else:
+                    G = gram(blk, 1, blk, b, 0)
+                r = _eig_dense("cholqr", G, first)
+                if r is None:
+                    return None
+                R.append(r[0])
+                combine(blk, 1, to, b, sign * r[1])
+            return R[1] @ R[0]
+
+        with operator as hA, (_resident_handle(M) if mass else contextlib.nullcontext(0)) as hM, np.errstate(all="ignore"):
+            space = _EigSpace(n, b, nb, wide, mass)
+            Q, Qj, P, Pj = space.Q, space.Qj, space.P, space.Pj
+            W, S1, N, _, _, _ = space.blocks(b)
+            for c0, c1 in chunks:
+                space.blocks(c1 - c0)
+            ones = _csx.i32(np.ones(maxw))
+            T = np.zeros((nb * b, nb * b))
+            W.assign(start)
+            if orthonormalise(W, 1.0, Qj[0]) is None:
+                raise ValueError("eigsh: the columns of the starting block are dependent")
+            if mass:
+                product(Qj[0], Pj[0], b)
+            breakdown, done, j = False, False, 0
+            while not done:
+                nv = j + 1
+                _csx.check(lib.csx_vec_copy(Pj[j].handle, W.handle), "csx_vec_copy")
+                self._solve_block(W, False, False)
+                count["solves"] += 1
+                H1 = gram(P, nv, W, b, 0)
+                update(Q, nv, W, sgn * H1)
+                H2 = gram(P, nv, W, b, 0)
+                update(Q, nv, W, sgn * H2)
+                T[:nv * b, j * b:nv * b] = H1 + H2
+                Bsub = orthonormalise(W, sgn, Qj[j + 1])
+                if Bsub is None:
+                    breakdown = True
+                elif mass:
+                    product(Qj[j + 1], Pj[j + 1], b)
+                m = nv * b
+                theta, S, est = _eig_dense("ritz", T[:m, :m], Bsub)
+                last = breakdown or j + 2 >= nb
+                kk = min(nev, m)
+                if last or (kk == nev and (est[:nev] <= tol).all()):
+                    resid, omega, host = np.empty(kk), np.empty(kk), []
+                    for c0, c1 in chunks:
+                        c1 = min(c1, kk)
+                        if c1 <= c0:
+                            break
+                        q = c1 - c0
+                        Wq, X, Nq, Bq, Rq, _ = space.blocks(q)
+                        th, mk = _csx.f64(theta[c0:c1]), _csx.pi(ones)
+                        combine(Q, nv, X, q, S[:, c0:c1])
+                        if mass:
+                            product(X, Nq, q)
+                            _csx.check(lib.csx_gs_scale(Nq.handle, Bq.handle, 0, space.work.handle, n, q, mk, _csx.pd(-th)),
+                                       "csx_gs_scale")
+                        else:
+                            _csx.check(lib.csx_gs_scale(X.handle, Bq.handle, 0, space.work.handle, n, q, mk, _csx.pd(th)),
+                                       "csx_gs_scale")
+                        omega[c0:c1], _ = self._residual_into(hA, X, Bq, Rq, q, False)
+                        norms = []
+                        for blk in (Rq, Bq):
+                            s2 = np.empty(q)
+                            _csx.check(lib.csx_vec_copy(blk.handle, Wq.handle), "csx_vec_copy")
+                            _csx.check(lib.csx_gs_project(Wq.handle, 1, blk.handle, space.work.handle, n, q, mk, 0, _csx.pd(s2)),
+                                       "csx_gs_project")
+                            norms.append(np.sqrt(s2))
+                        resid[c0:c1] = norms[0] / norms[1]
+                        if len(chunks) > 1:
+                            host.append(X.numpy().reshape(n, q))
+                    done = last or bool((resid <= tol).all())
+                j += 1
+            vectors = dvec(np.hstack(host)) if len(chunks) > 1 else space.blocks(kk)[1].copy()
+        out = {"values": sigma + 1.0 / theta[:kk], "vectors": vectors, "resid": resid, "omega": omega, "estimate": est[:kk].copy(),
+               "converged": resid <= tol, "blocks": j, "solves": count["solves"], "products": count["products"],
+               "breakdown": breakdown}
+        if isinstance(self, _LdlSolver):
+            info = self.info()
+            out["below"] = None if info["perturbed"] else int(info["neg"])
+        return out
 
     def condest(self, A=None):
         """an estimate of cond_1(S) = |S|_1 |S^-1|_1 of the operator (see backward_error): csx_norm1_sym times

@@ -19,4 +19,17 @@ inline int64_t gs_work_len(int64_t rows, int32_t nrhs, int32_t nblocks) {
     return (int64_t)nrhs * (1 + 2 * (int64_t)nblocks + GS_GROUP * (nch + n1));
 }
 
+// ---- the block kernels in which columns mix (csx_bgs.hip, csx_bgs_host) ----
+constexpr int BGS_MAXW = 32;     // widest block (b of the basis, q of W / U) a call takes
+constexpr int BGS_GROUP = 4;     // basis blocks whose b x q sums one pass of csx_bgs_gram carries: W crosses memory once per group
+constexpr int BGS_TILE = 1024;   // doubles of one block's row tile in LDS: BGS_TILE / max(b, q) rows (GS_CHUNK at the most)
+
+// doubles of the work vector the csx_bgs_* calls take for rows x b basis blocks (nblocks of them at most in a call) and a
+// rows x q block: b q nblocks coefficients in and as many sums out, and the leaf sums of one group of BGS_GROUP basis blocks with
+// their first inner level: BGS_GROUP b q / GS_CHUNK <= min(b, q) / 2 doubles per row, under half a rows x max(b, q) block
+inline int64_t bgs_work_len(int64_t rows, int32_t b, int32_t q, int32_t nblocks) {
+    const int64_t nch = gs_chunks(rows), n1 = (nch + GS_FAN - 1) / GS_FAN;
+    return (int64_t)b * q * (2 * (int64_t)nblocks + BGS_GROUP * (nch + n1));
+}
+
 }  // namespace csx

@@ -1729,3 +1729,66 @@ extern "C" int csx_gs_host(int op, int64_t rows, int32_t nrhs, int32_t nv, doubl
     }
     return CSX_OK;
 }
+
+// ---- the block rule of eigsh() in which columns mix (csx_bgs.hip) on host arrays ----
+extern "C" int csx_bgs_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    out[0] = GS_CHUNK;
+    out[1] = GS_FAN;
+    out[2] = BGS_MAXW;
+    out[3] = BGS_GROUP;
+    out[4] = BGS_TILE;
+    return CSX_OK;
+}
+
+extern "C" int csx_bgs_work_len(int64_t rows, int32_t b, int32_t q, int32_t nblocks, int64_t *len) {   // (no device needed)
+    if (!len || rows < 0 || rows > ((int64_t)1 << 40) || b < 1 || b > BGS_MAXW || q < 1 || q > BGS_MAXW || nblocks < 0)
+        return CSX_EINVAL;
+    *len = bgs_work_len(rows, b, q, nblocks);
+    return CSX_OK;
+}
+
+// op 0 gram:    out[(i b + a) q + c] = ordered sum over r of V_i[r, a] (+-W[r, c]), i < nv
+// op 1 update:  W[r, c] <- W[r, c] - coef[0, 0, c] V_0[r, 0] - coef[0, 1, c] V_0[r, 1] - ... in ascending (i, a)
+// op 2 combine: out[r q + c] = coef[0, 0, c] V_0[r, 0] + ...: the first product, then rounded additions; +0.0 for nv == 0
+extern "C" int csx_bgs_host(int op, int64_t rows, int32_t b, int32_t q, int32_t nv, const double *V, double *W, int negate,
+                            const double *coef, double *out) {
+#pragma clang fp contract(off)
+    if (op < 0 || op > 2 || rows < 0 || nv < 0 || b < 1 || b > BGS_MAXW || q < 1 || q > BGS_MAXW) return CSX_EINVAL;
+    const bool none = rows == 0 || nv == 0;   // an array that holds nothing may be null
+    if ((!V && !none) || (op != 2 && !W && rows > 0) || (op != 0 && !coef && nv > 0)) return CSX_EINVAL;
+    if (!out && ((op == 0 && nv > 0) || (op == 2 && rows > 0))) return CSX_EINVAL;
+    const int64_t block = rows * b;
+    if (op == 0) {
+        const size_t nch = (size_t)gs_chunks(rows);
+        std::vector<double> node(nch);
+        for (int32_t i = 0; i < nv; i++)
+            for (int32_t a = 0; a < b; a++)
+                for (int32_t c = 0; c < q; c++) {
+                    const double *Vi = V + i * block;
+                    for (size_t l = 0; l < nch; l++) {
+                        double s = 0.0;
+                        for (int64_t r = (int64_t)l * GS_CHUNK; r < std::min(rows, (int64_t)(l + 1) * GS_CHUNK); r++) {
+                            const double w = negate ? -W[r * q + c] : W[r * q + c];
+                            const double p = Vi[r * b + a] * w;
+                            s = s + p;
+                        }
+                        node[l] = s;
+                    }
+                    out[((int64_t)i * b + a) * q + c] = gs_tree(node);
+                }
+        return CSX_OK;
+    }
+    for (int64_t r = 0; r < rows; r++)
+        for (int32_t c = 0; c < q; c++) {
+            double x = op == 1 ? W[r * q + c] : 0.0;
+            for (int32_t i = 0; i < nv; i++)
+                for (int32_t a = 0; a < b; a++) {
+                    const double p = coef[((int64_t)i * b + a) * q + c] * V[i * block + r * b + a];
+                    if (op == 1) x = x - p;
+                    else x = (i == 0 && a == 0) ? p : x + p;
+                }
+            (op == 1 ? W : out)[r * q + c] = x;
+        }
+    return CSX_OK;
+}

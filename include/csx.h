@@ -1239,6 +1239,37 @@ int csx_gs_combine(csx_handle_t V, int32_t nv, csx_handle_t U, csx_handle_t work
 int csx_gs_host(int op, int64_t rows, int32_t nrhs, int32_t nv, double *V, double *W, const int32_t *mask, int negate,
                 const double *coef, const int32_t *len, double *out);
 
+/* ---- the block kernels of eigsh() in which the columns of a block mix (csx_bgs.hip).  Blocks are row-major and
+ * 16-byte aligned: the basis V is ONE vector of consecutive rows x b blocks V_0, V_1, ... (a call addresses its first nv), W and
+ * U are rows x q, 1 <= b, q <= BGS_MAXW (wider outputs are made in column chunks by the caller).  work: a vector of at least
+ * csx_bgs_work_len(rows, b, q, nv) doubles (nothing else is allocated); its contents mean nothing between calls.
+ * Value rule: that of the csx_gs_* calls above, on the device and in csx_bgs_host alike: every product is rounded, then added or
+ * subtracted; a sum over rows is the ORDERED SUM (leaves of GS_CHUNK rows, nodes of GS_FAN children, ascending from +0.0), whose
+ * tree depends on `rows` alone; no floating-point atomics.
+ *   csx_bgs_gram:    out[(i b + a) q + c] = ordered sum over r of V_i[r, a] * w, w = W[r, c], or -W[r, c] when negate != 0.
+ *                    W is read only and may be a block of the basis.
+ *   csx_bgs_update:  W[r, c] <- W[r, c] - H[0, 0, c] V_0[r, 0] - H[0, 1, c] V_0[r, 1] - ..., ascending in (i, a), every product
+ *                    and every subtraction rounded.  H: nv x b x q.
+ *   csx_bgs_combine: U[r, c] = S[0, 0, c] V_0[r, 0] + ..., ascending in (i, a): the first product as it is, then one rounded
+ *                    addition per further product; +0.0 for nv == 0.  S: nv x b x q.
+ * CSX_EINVAL: an unknown handle, a null host array, b or q outside 1 .. BGS_MAXW, rows < 0, nv < 0, a basis shorter than nv
+ * blocks, a block shorter than rows q, a work vector that is too short or overlaps the basis or the block, a W (update) or U
+ * (combine) that overlaps the basis.  rows == 0: the sums are +0.0.
+ * csx_bgs_limits: out[5] = GS_CHUNK, GS_FAN, BGS_MAXW, BGS_GROUP (basis blocks whose sums one pass of csx_bgs_gram carries: W
+ * crosses memory once per BGS_GROUP of them), BGS_TILE (doubles of a block's row tile in LDS); no device needed.
+ * csx_bgs_host: op 0 .. 2 = gram / update / combine on host arrays: V the basis, W the block (update overwrites it; unused by
+ * combine), coef = - / H / S, out = the sums / - / U; an array that holds nothing (rows == 0 or nv == 0) may be null. */
+int csx_bgs_limits(int32_t *out);
+int csx_bgs_work_len(int64_t rows, int32_t b, int32_t q, int32_t nblocks, int64_t *len);
+int csx_bgs_gram(csx_handle_t V, int32_t nv, int32_t b, csx_handle_t W, int32_t q, csx_handle_t work, int64_t rows, int negate,
+                 double *out);
+int csx_bgs_update(csx_handle_t V, int32_t nv, int32_t b, csx_handle_t W, int32_t q, csx_handle_t work, int64_t rows,
+                   const double *H);
+int csx_bgs_combine(csx_handle_t V, int32_t nv, int32_t b, csx_handle_t U, int32_t q, csx_handle_t work, int64_t rows,
+                    const double *S);
+int csx_bgs_host(int op, int64_t rows, int32_t b, int32_t q, int32_t nv, const double *V, double *W, int negate, const double *coef,
+                 double *out);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
