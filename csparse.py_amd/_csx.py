@@ -85,6 +85,8 @@ _PROTOS = {
     "csx_prim_sort": [_vp, _vp, _f64p, C.c_int64, C.c_uint32, _vp, _vp, _f64p, _i32p, C.c_int32, _i32p, C.c_int32, C.c_int],
     "csx_prim_sort_info": [C.POINTER(C.c_int64), C.c_int32],
     "csx_multiply": [H, H, C.POINTER(H)],
+    "csx_spgemm_limits": [_i32p],
+    "csx_spgemm_info": [C.POINTER(C.c_int64), C.c_int32, _i32p],
     "csx_tri_analyse": [H, C.c_int, C.POINTER(H)],
     "csx_tri_info": [H, _i32p, _i32p, _i32p],
     "csx_tri_solve": [H, H, C.c_int32],
@@ -465,6 +467,41 @@ def prim_limits():
     out = (C.c_int32 * len(PRIM_LIMITS))()
     check(load().csx_prim_limits(out), "csx_prim_limits")
     return {name: int(out[k]) for k, name in enumerate(PRIM_LIMITS)}
+
+
+SPGEMM_LIMITS = ("SG_SEG", "SG_THREADS", "SG_DENSE_MAX", "SG_GLOBAL_WGS", "SG_HASH_MAXP", "HASH_LIMIT0", "HASH_LIMIT1", "HASH_LIMIT2",
+                 "HASH_LIMIT3", "HASH_LIMIT4", "HASH_LIMIT5", "HASH_LIMIT6", "HASH_LIMIT7", "H2_MAXSEG", "H2_MAXLEN", "H2_MAXP",
+                 "H1_SEG", "H1_MAXP", "H1_UN", "SGO_MAX", "SGO_SLOTS0", "SGO_CNT0", "SGO_SLOTS1", "SGO_CNT1", "SGO_SLOTS2", "SGO_CNT2",
+                 "SGO_DENSE_WAVES", "SG_GRID_PER_CU", "INFO_FIELDS", "SGO_WAVES0", "SGO_WAVES1", "SGO_WAVES2", "SG_UN",
+                 "SG_MIN_SLOTS", "SG_LDS_BUDGET", "SG_WGS_PER_CU_MAX", "SG_HASH_BINS", "SG_NARROW_BINS", "LAUNCH_SITES")
+SPGEMM_SITES = (("products",) + tuple("spgemm_%s_%s" % (r, k) for r in ("symbolic", "values", "pattern")
+                                      for k in ("dense", "hash", "global"))
+                + tuple("hash1_%s_%d" % (v, b) for v in ("pattern", "values") for b in range(8))
+                + tuple("hash2_%s_%d" % (v, b) for v in ("pattern", "values") for b in range(6))
+                + ("compact", "dup_cols", "ordered2_0", "ordered2_1", "ordered2_2", "ordered_dense"))
+
+
+def spgemm_limits():
+    """the constants cs_multiply's bins, tables and staging are cut by (csx_spgemm.hip), asked of the library; no GPU needed: a
+    dict by the names of SPGEMM_LIMITS (include/csx.h: csx_spgemm_limits)"""
+    out = (C.c_int32 * 40)()
+    check(load().csx_spgemm_limits(out), "csx_spgemm_limits")
+    return {name: int(out[k]) for k, name in enumerate(SPGEMM_LIMITS)}
+
+
+def spgemm_info():
+    """what the last product on the device decided and launched (csx_spgemm_info; host state only): a dict with "bins" (32
+    counts), "one_pass", "global_wgs", "cus", "ordered", "classes" (4 flags), "launches" and "grids" ({site of SPGEMM_SITES: n},
+    the sites that were not launched left out)"""
+    n = C.c_int32(0)
+    out = (C.c_int64 * 256)()
+    check(load().csx_spgemm_info(out, 256, C.byref(n)), "csx_spgemm_info")
+    v, k = [int(x) for x in out[:n.value]], len(SPGEMM_SITES)
+    assert n.value == 40 + 2 * k
+    cnt, grid = v[40:40 + k], v[40 + k:]
+    return {"bins": tuple(v[:32]), "one_pass": v[32], "global_wgs": v[33], "cus": v[34], "ordered": v[35], "classes": tuple(v[36:40]),
+            "launches": {s: c for s, c in zip(SPGEMM_SITES, cnt) if c},
+            "grids": {s: g for s, c, g in zip(SPGEMM_SITES, cnt, grid) if c}}
 
 
 GMRES_LIMITS = ("GS_CHUNK", "GS_FAN", "GS_GROUP", "GS_TILE")

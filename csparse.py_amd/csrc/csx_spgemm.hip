@@ -37,6 +37,11 @@ constexpr int SG_SEG = 1024;          // entries of B(:,j) staged per segment
 constexpr uint32_t SG_UNSET = 0xFFFFFFFFu;
 constexpr int SG_DENSE_MAX = 8192;    // rows for the LDS dense accumulator
 constexpr int SG_GLOBAL_WGS = 64;     // concurrent workgroups with global accumulators
+constexpr int SG_UN = 4;              // 256-wide chunks of products per step of the two-pass kernel
+constexpr int SG_GRID_PER_CU = 16;    // workgroups per CU the two-pass kernel's grid is cut by (LDS kinds)
+constexpr int SG_MIN_SLOTS = 1024;    // smallest two-pass hash table
+constexpr int SG_LDS_BUDGET = 160 * 1024;   // LDS of a CU the persistent one-pass grids are sized by
+constexpr int SG_WGS_PER_CU_MAX = 8;  // and the workgroups per CU they hold at most
 
 enum { ACC_LDS_DENSE = 0, ACC_LDS_HASH = 1, ACC_GLOBAL_DENSE = 2 };
 
@@ -243,7 +248,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_spgemm(int kind, int slots, int3
                 const uint32_t nprod = seg_off[SG_SEG];
                 // four 256-wide chunks of products per step: their (row, value) loads are issued
                 // back to back (clamped indices, so no branch), then consumed in product order
-                constexpr int UN = 4;
+                constexpr int UN = SG_UN;
                 for (uint32_t c0 = 0; c0 < nprod; c0 += UN * SG_THREADS) {
                     uint32_t rows_[UN];
                     double prods_[UN];
@@ -306,6 +311,29 @@ __global__ __launch_bounds__(SG_THREADS) void k_spgemm(int kind, int slots, int3
         if (!NUMERIC && threadIdx.x == 0) count[j] = misc[8];
         __syncthreads();
     }
+}
+
+// ---- read-back for the tests (host state only): what the last multiply_device of this process decided, and every launch it
+// and the ordered pass enqueued, in the order of csx_spgemm_info (include/csx.h).  A counter is bumped beside its launch.
+enum SgSite : int {
+    SGS_PRODUCTS = 0,
+    SGS_SPGEMM = 1,                            // + 3 * (0 symbolic, 1 numeric with values, 2 numeric pattern-only) + kind
+    SGS_HASH1 = SGS_SPGEMM + 9,                // + SG_HASH_BINS * VALUES + hash bin
+    SGS_HASH2 = SGS_HASH1 + 2 * SG_HASH_BINS,  // + SG_NARROW_BINS * VALUES + narrow bin
+    SGS_COMPACT = SGS_HASH2 + 2 * SG_NARROW_BINS,
+    SGS_DUP_COLS,
+    SGS_ORDERED2,                              // + class
+    SGS_ORDERED_DENSE = SGS_ORDERED2 + 3,
+    SGS_COUNT
+};
+struct SgInfo {
+    int64_t bins[SG_NBINS], one_pass, global_wgs, cus, ordered, cls[4], launches[SGS_COUNT], grid[SGS_COUNT];
+};
+constexpr int SG_INFO_FIELDS = (int)(sizeof(SgInfo) / sizeof(int64_t));
+static SgInfo g_sg_info = {};
+static inline void sg_launched(int site, int64_t grid) {
+    g_sg_info.launches[site]++;
+    g_sg_info.grid[site] = grid;
 }
 
 // ---- one-pass kernel for the LDS-hash bins ---------------------------------------------------------
@@ -807,18 +835,19 @@ __global__ __launch_bounds__(256) void k_sg_hash2(int slots_, const int4 *__rest
 }
 
 template <bool VALUES>
-static int launch_hash2(int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
+static int launch_hash2(int hb, int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
                         int32_t *tmp_i, double *tmp_x) {
     if (ncols <= 0) return CSX_OK;
     const size_t lds = (size_t)(slots + (slots & 1)) * (VALUES ? 16 : 8) + H2_MAXSEG * 4 + 64;
     auto kern = k_sg_hash2<VALUES>;
     CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256));
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(lds + 256)));
+                                SG_LDS_BUDGET - 256));
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(SG_WGS_PER_CU_MAX, SG_LDS_BUDGET / (int64_t)(lds + 256)));
     const int64_t grid = std::min<int64_t>(ncols, (int64_t)ctx().cus * per_cu);
     const int abl = ablation_env("CSX_SG_ABL") ? std::atoi(ablation_env("CSX_SG_ABL")) : 0;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, ctx().stream, slots, info, ncols, A->p, A->i, A->x,
                        B->i, B->x, count, tmp_i, tmp_x, abl);
+    sg_launched(SGS_HASH2 + SG_NARROW_BINS * (VALUES ? 1 : 0) + hb, grid);
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
@@ -863,19 +892,20 @@ static size_t h1_lds_bytes(int slots, bool values) {   // slots = 3/2 * (product
 }
 
 template <bool VALUES>
-static int launch_hash1(int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
+static int launch_hash1(int hb, int slots, const Csc *A, const Csc *B, const int4 *info, int32_t ncols, int32_t *count,
                         int32_t *tmp_i, double *tmp_x) {
     if (ncols <= 0) return CSX_OK;
     const size_t lds = h1_lds_bytes(slots, VALUES);
     auto kern = k_sg_hash1<VALUES>;
     CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256));
+                                SG_LDS_BUDGET - 256));
     // exactly the workgroups that are resident at once (LDS-limited, at most 8 x 4 waves per CU)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / (int64_t)(lds + 256)));
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(SG_WGS_PER_CU_MAX, SG_LDS_BUDGET / (int64_t)(lds + 256)));
     const int64_t grid = std::min<int64_t>(ncols, (int64_t)ctx().cus * per_cu);
     const int abl = ablation_env("CSX_SG_ABL") ? std::atoi(ablation_env("CSX_SG_ABL")) : 0;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, ctx().stream, slots, info, ncols, A->p, A->i, A->x,
                        B->i, B->x, count, tmp_i, tmp_x, abl);
+    sg_launched(SGS_HASH1 + SG_HASH_BINS * (VALUES ? 1 : 0) + hb, grid);
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
@@ -900,12 +930,13 @@ static int launch_bin(int kind, int slots, const Csc *A, const Csc *B, const uin
     const size_t lds = sg_lds_bytes(kind, slots, A->m);
     auto kern = k_spgemm<NUMERIC, VALUES>;
     CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024 - 256));
+                                SG_LDS_BUDGET - 256));
     int64_t grid = ncols;
     if (kind == ACC_GLOBAL_DENSE) grid = std::min<int64_t>(grid, SG_GLOBAL_WGS);
-    else grid = std::min<int64_t>(grid, (int64_t)ctx().cus * 16);
+    else grid = std::min<int64_t>(grid, (int64_t)ctx().cus * SG_GRID_PER_CU);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(SG_THREADS), lds, ctx().stream, kind, slots, A->m, cols, ncols,
                        A->p, A->i, A->x, B->p, B->i, B->x, count, Cp, Ci, Cx, g_tmin, g_val);
+    sg_launched(SGS_SPGEMM + 3 * (NUMERIC ? (VALUES ? 1 : 2) : 0) + kind, grid);
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
@@ -922,7 +953,7 @@ static int run_bins(const Csc *A, const Csc *B, const uint32_t *cols, const int3
         const int kind = b == SG_BIN_DENSE ? ACC_LDS_DENSE : (b == SG_BIN_GLOBAL ? ACC_GLOBAL_DENSE : ACC_LDS_HASH);
         int slots = 0;  // two-pass hash tables: power of two, load <= 1/2
         if (hashed)
-            for (slots = 1024; slots < 2 * sg_hash_limit(hb); slots <<= 1) {}
+            for (slots = SG_MIN_SLOTS; slots < 2 * sg_hash_limit(hb); slots <<= 1) {}
         CSX_TRY((launch_bin<NUMERIC, VALUES>(kind, slots, A, B, cols + bin_ptr[b], nb, count, Cp, Ci, Cx, g_tmin, g_val)));
     }
     return CSX_OK;
@@ -938,7 +969,13 @@ static int run_bins(const Csc *A, const Csc *B, const uint32_t *cols, const int3
 // twice, and then the lanes of equal rows take their turns in lane order.  A row's position in C(:,j) comes from a hash
 // map in LDS (columns of at most SGO_MAX entries, sums in LDS too) or from a dense map in memory (longer columns, sums
 // straight into C.x).  Bit-identical to the unmodified reference (tests/test_gpu_multiply.py); several times slower than the atomics.
-constexpr int SGO_MAX = 2048, SGO_SLOTS = 4096;
+// The kernel below takes the columns of more than SGO_MAX entries (dense map, at most SGO_DENSE_WAVES waves); the shorter ones
+// go by size class c to k_sg_values_ordered2 with SGO_SLOTSc slots for up to SGO_CNTc entries, SGO_WAVESc waves to a CU.
+constexpr int SGO_SLOTS0 = 512, SGO_CNT0 = 256, SGO_WAVES0 = 20;
+constexpr int SGO_SLOTS1 = 2560, SGO_CNT1 = 1280, SGO_WAVES1 = 4;
+constexpr int SGO_SLOTS2 = 4096, SGO_CNT2 = 2048, SGO_WAVES2 = 2;
+constexpr int SGO_MAX = SGO_CNT2;
+constexpr int SGO_DENSE_WAVES = 128;
 
 __device__ __forceinline__ int sgo_rank_of_equal_rows(int32_t row, bool active, int lane, int *rounds) {
     // number of earlier active lanes holding the same row; *rounds = 1 + the largest such number in the wave
@@ -955,7 +992,6 @@ __device__ __forceinline__ int sgo_rank_of_equal_rows(int32_t row, bool active, 
     return before;
 }
 
-template <bool BIG>
 __global__ __launch_bounds__(64) void k_sg_values_ordered(int32_t n, int32_t m, const int32_t *__restrict__ Ap,
                                                           const int32_t *__restrict__ Ai, const double *__restrict__ Ax,
                                                           const int32_t *__restrict__ Bp, const int32_t *__restrict__ Bi,
@@ -963,39 +999,17 @@ __global__ __launch_bounds__(64) void k_sg_values_ordered(int32_t n, int32_t m, 
                                                           const int32_t *__restrict__ Ci, double *__restrict__ Cx,
                                                           int32_t *__restrict__ gmap) {
 #pragma clang fp contract(off)
-    __shared__ int32_t hkey[BIG ? 1 : SGO_SLOTS];
-    __shared__ int32_t hpos[BIG ? 1 : SGO_SLOTS];
-    __shared__ double acc[BIG ? 1 : SGO_MAX];
-    __shared__ unsigned long long seen[BIG ? 1 : SGO_MAX / 64];
     const int lane = threadIdx.x;
-    int32_t *map = BIG ? gmap + (int64_t)blockIdx.x * m : nullptr;
+    int32_t *map = gmap + (int64_t)blockIdx.x * m;
     for (int32_t j = blockIdx.x; j < n; j += gridDim.x) {
         const int32_t c0 = Cp[j], cnt = Cp[j + 1] - c0;
-        if (cnt == 0 || (cnt > SGO_MAX) != BIG) continue;
-        // the map row -> position in C(:,j)
-        if (!BIG) {
-            for (int s = lane; s < SGO_SLOTS; s += 64) hkey[s] = -1;
-            for (int s = lane; s < SGO_MAX / 64; s += 64) seen[s] = 0ull;
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            __builtin_amdgcn_wave_barrier();
-            for (int32_t q = lane; q < cnt; q += 64) {
-                const int32_t row = Ci[c0 + q];
-                uint32_t s = (uint32_t)(row * 0x9E3779B1u) >> 20;      // 12 bits
-                for (;;) {
-                    const int32_t prev = atomicCAS(&hkey[s], -1, row);
-                    if (prev == -1) break;
-                    s = (s + 1) & (SGO_SLOTS - 1);
-                }
-                hpos[s] = q;
-            }
-        } else {
-            // dense map in memory: row -> cnt + position until the position is first touched, then the position
-            for (int32_t q = lane; q < cnt; q += 64) {
-                map[Ci[c0 + q]] = cnt + q;
-                Cx[c0 + q] = 0.0;
-            }
-            __threadfence_block();
+        if (cnt <= SGO_MAX) continue;
+        // dense map in memory: row -> cnt + position until the position is first touched, then the position
+        for (int32_t q = lane; q < cnt; q += 64) {
+            map[Ci[c0 + q]] = cnt + q;
+            Cx[c0 + q] = 0.0;
         }
+        __threadfence_block();
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
         for (int32_t pb = Bp[j]; pb < Bp[j + 1]; pb++) {           // B(:,j) in storage order
@@ -1008,39 +1022,21 @@ __global__ __launch_bounds__(64) void k_sg_values_ordered(int32_t n, int32_t m, 
                 const double prod = active ? beta * Ax[q] : 0.0;
                 int rounds = 1;
                 const int before = sgo_rank_of_equal_rows(row, active, lane, &rounds);
-                int32_t pos = 0;
-                if (active && !BIG) {
-                    uint32_t s = (uint32_t)(row * 0x9E3779B1u) >> 20;
-                    while (hkey[s] != row) s = (s + 1) & (SGO_SLOTS - 1);
-                    pos = hpos[s];
-                }
                 for (int r = 0; r < rounds; r++) {
                     if (active && before == r) {
-                        if (!BIG) {
-                            const unsigned long long bit = 1ull << (pos & 63);
-                            if (seen[pos >> 6] & bit) acc[pos] = acc[pos] + prod;
-                            else {
-                                acc[pos] = prod;                   // the first product is assigned (csparse.py:1986)
-                                atomicOr(&seen[pos >> 6], bit);
-                            }
+                        const int32_t v = map[row];
+                        if (v >= cnt) {                            // first touch of this position
+                            Cx[c0 + v - cnt] = prod;               // the first product is assigned (csparse.py:1986)
+                            map[row] = v - cnt;
                         } else {
-                            const int32_t v = map[row];
-                            if (v >= cnt) {                        // first touch of this position
-                                Cx[c0 + v - cnt] = prod;
-                                map[row] = v - cnt;
-                            } else {
-                                Cx[c0 + v] = Cx[c0 + v] + prod;
-                            }
+                            Cx[c0 + v] = Cx[c0 + v] + prod;
                         }
                     }
-                    if (BIG) __threadfence_block();
+                    __threadfence_block();
                     __builtin_amdgcn_s_waitcnt(0xc07f);
                     __builtin_amdgcn_wave_barrier();
                 }
             }
-        }
-        if (!BIG) {
-            for (int32_t q = lane; q < cnt; q += 64) Cx[c0 + q] = acc[q];
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
         __builtin_amdgcn_wave_barrier();
@@ -1196,18 +1192,19 @@ __global__ __launch_bounds__(64) void k_sg_values_ordered2(int32_t n, int32_t lo
     }
 }
 
-// flag[c] |= some column of C falls into class c: 0: 1 .. 256 entries, 1: .. 1 280, 2: .. 2 048, 3: more
+// flag[c] |= some column of C falls into class c: 0: 1 .. SGO_CNT0 entries, 1: .. SGO_CNT1, 2: .. SGO_MAX, 3: more
 __global__ void k_sg_count_classes(int32_t n, const int32_t *__restrict__ Cp, int *flag) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int32_t cnt = Cp[j + 1] - Cp[j];
     if (cnt == 0) return;
-    const int c = cnt <= 256 ? 0 : (cnt <= 1280 ? 1 : (cnt <= SGO_MAX ? 2 : 3));
+    const int c = cnt <= SGO_CNT0 ? 0 : (cnt <= SGO_CNT1 ? 1 : (cnt <= SGO_MAX ? 2 : 3));
     if (!flag[c]) flag[c] = 1;
 }
 
 static int values_in_reference_order(const Csc *A, const Csc *B, Csc *C) {
     if (!C->x || C->nnz == 0) return CSX_OK;
+    g_sg_info.ordered = 1;
     hipStream_t s = ctx().stream;
     const int32_t n = C->n, m = C->m;
     DevBuf<int> flag;
@@ -1218,27 +1215,39 @@ static int values_in_reference_order(const Csc *A, const Csc *B, Csc *C) {
     CSX_TRY(dup.alloc((size_t)A->n + 1));
     CSX_HIP(hipMemsetAsync(flag, 0, 4 * sizeof(int), s));
     hipLaunchKernelGGL(k_sg_count_classes, dim3((unsigned)(((int64_t)n + 255) / 256)), dim3(256), 0, s, n, C->p, flag);
+    CSX_LAUNCH_CHECK();
     CSX_HIP(hipMemcpyAsync(h, flag, sizeof h, hipMemcpyDeviceToHost, s));
     int nbits = 1;
     while (nbits < 31 && (1ll << nbits) < (long long)m) nbits++;
-    hipLaunchKernelGGL(k_sg_dup_cols, dim3((unsigned)(((int64_t)A->n + 3) / 4)), dim3(256), 0, s, A->n, nbits, A->p, A->i, dup);
+    const int64_t dup_grid = ((int64_t)A->n + 3) / 4;
+    hipLaunchKernelGGL(k_sg_dup_cols, dim3((unsigned)dup_grid), dim3(256), 0, s, A->n, nbits, A->p, A->i, dup);
+    sg_launched(SGS_DUP_COLS, dup_grid);
+    CSX_LAUNCH_CHECK();
     CSX_HIP(hipStreamSynchronize(s));
+    for (int c = 0; c < 4; c++) g_sg_info.cls[c] = h[c];
     const int cus = ctx().cus;
-#define CSX_ORD(SLOTS, MAXCNT, LO, WAVES)                                                                                      \
-    hipLaunchKernelGGL((k_sg_values_ordered2<SLOTS, MAXCNT>), dim3((unsigned)std::min<int64_t>(n, (int64_t)cus * (WAVES))), dim3(64), \
-                       0, s, n, LO, A->p, A->i, A->x, dup, B->p, B->i, B->x, C->p, C->i, C->x)
+#define CSX_ORD(CLS, SLOTS, MAXCNT, LO, WAVES)                                                                                 \
+    do {                                                                                                                       \
+        const int64_t grid_ = std::min<int64_t>(n, (int64_t)cus * (WAVES));                                                    \
+        hipLaunchKernelGGL((k_sg_values_ordered2<SLOTS, MAXCNT>), dim3((unsigned)grid_), dim3(64), 0, s, n, LO, A->p, A->i,    \
+                           A->x, dup, B->p, B->i, B->x, C->p, C->i, C->x);                                                     \
+        sg_launched(SGS_ORDERED2 + (CLS), grid_);                                                                              \
+        CSX_LAUNCH_CHECK();                                                                                                    \
+    } while (0)
     // (tables at most half full: with linear probing a wave waits for its LONGEST probe chain, and at two thirds full --
     // 1 536 slots for 1 024 entries, seven waves to a CU instead of five -- that made the pass six times slower, not faster)
-    if (h[0]) CSX_ORD(512, 256, 0, 20);          //  7 KB of LDS per wave
-    if (h[1]) CSX_ORD(2560, 1280, 256, 4);       // 34 KB: four waves to a CU (S: 1 024 +- 100 entries per column -- with the
-                                                 // class cut at 1 024 a quarter of S went to the 54 KB class: 32 of 49 ms)
-    if (h[2]) CSX_ORD(4096, 2048, 1280, 2);      // 54 KB
+    if (h[0]) CSX_ORD(0, SGO_SLOTS0, SGO_CNT0, 0, SGO_WAVES0);          //  7 KB of LDS per wave
+    if (h[1]) CSX_ORD(1, SGO_SLOTS1, SGO_CNT1, SGO_CNT0, SGO_WAVES1);   // 34 KB: four waves to a CU (S: 1 024 +- 100 entries per
+                                                 // column -- with the class cut at 1 024 a quarter of S went to the 54 KB class: 32 of 49 ms)
+    if (h[2]) CSX_ORD(2, SGO_SLOTS2, SGO_CNT2, SGO_CNT1, SGO_WAVES2);   // 54 KB
 #undef CSX_ORD
     if (h[3]) {
-        const int64_t waves = std::min<int64_t>(n, 128);
+        const int64_t waves = std::min<int64_t>(n, SGO_DENSE_WAVES);
         CSX_TRY(gmap.alloc((size_t)waves * (size_t)m));
-        hipLaunchKernelGGL(k_sg_values_ordered<true>, dim3((unsigned)waves), dim3(64), 0, s, n, m, A->p, A->i, A->x, B->p, B->i, B->x,
+        hipLaunchKernelGGL(k_sg_values_ordered, dim3((unsigned)waves), dim3(64), 0, s, n, m, A->p, A->i, A->x, B->p, B->i, B->x,
                            C->p, C->i, C->x, gmap);
+        sg_launched(SGS_ORDERED_DENSE, waves);
+        CSX_LAUNCH_CHECK();
     }
     CSX_HIP(hipStreamSynchronize(s));
     CSX_LAUNCH_CHECK();
@@ -1252,6 +1261,8 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
     C->m = m;
     C->n = n;
     C->owns = true;
+    g_sg_info = SgInfo{};
+    g_sg_info.cus = ctx().cus;
     CSX_TRY(dalloc(&C->p, (size_t)n + 1));
     if (n == 0 || m == 0 || A->nnz == 0 || B->nnz == 0) {
         CSX_HIP(hipMemsetAsync(C->p, 0, ((size_t)n + 1) * sizeof(int32_t), s));
@@ -1275,17 +1286,25 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
     CSX_TRY(too_big.alloc(2));
     int32_t bin_ptr[SG_NBINS + 1] = {0};
     unsigned long long big[2] = {0, 0};
-    (void)hipMemsetAsync(too_big, 0, 2 * sizeof(unsigned long long), s);
-    (void)hipMemsetAsync(count, 0, ((size_t)n + 1) * sizeof(int32_t), s);
-    hipLaunchKernelGGL(k_sg_products, dim3((unsigned)(((int64_t)n + 3) / 4)), dim3(256), 0, s, n, A->p, B->p, B->i, m,
-                       bin, colid, hprod, too_big);
+    CSX_HIP(hipMemsetAsync(too_big, 0, 2 * sizeof(unsigned long long), s));
+    CSX_HIP(hipMemsetAsync(count, 0, ((size_t)n + 1) * sizeof(int32_t), s));
+    const int64_t prod_grid = ((int64_t)n + 3) / 4;
+    hipLaunchKernelGGL(k_sg_products, dim3((unsigned)prod_grid), dim3(256), 0, s, n, A->p, B->p, B->i, m, bin, colid, hprod,
+                       too_big);
+    sg_launched(SGS_PRODUCTS, prod_grid);
+    CSX_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sum_i32, dim3(512), dim3(256), 0, s, hprod, (int64_t)n, too_big + 1);
+    CSX_LAUNCH_CHECK();
     CSX_TRY(stable_sort_by_key(bin, colid, nullptr, n, SG_NBINS, sbin, scol, nullptr));
     CSX_TRY(boundaries_from_sorted(sbin, n, SG_NBINS, bin_ptr_d));
     CSX_HIP(hipMemcpyAsync(bin_ptr, bin_ptr_d, (SG_NBINS + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CSX_HIP(hipMemcpyAsync(big, too_big, sizeof big, hipMemcpyDeviceToHost, s));
     CSX_HIP(hipStreamSynchronize(s));
-    if (big[0]) return CSX_EINVAL;  // a column with >= 2^32 products
+    for (int b = 0; b < SG_NBINS; b++) g_sg_info.bins[b] = bin_ptr[b + 1] - bin_ptr[b];
+    if (big[0]) {
+        set_error("cs_multiply: %llu column(s) of the product have 2^32 products or more", big[0]);
+        return CSX_EINVAL;
+    }
     // one-pass path for the hash bins when its product-order buffer (12 B per product) is affordable
     const int32_t hash_lo = bin_ptr[SG_BIN_HASH0], nhash = bin_ptr[SG_BIN_NARROW0 + SG_NARROW_BINS] - hash_lo;
     bool onepass = false;
@@ -1296,6 +1315,7 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
         pool_stats(&idle_b, nullptr);   // idle blocks of the caching allocator are reusable
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < (free_b + idle_b) / 3) onepass = true;
     }
+    g_sg_info.one_pass = onepass ? 1 : 0;
     if (onepass) {
         CSX_TRY(toff.alloc((size_t)n + 1));
         int64_t tot = 0;
@@ -1305,17 +1325,18 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
         CSX_TRY(info.alloc((size_t)nhash));
         hipLaunchKernelGGL(k_sg_colinfo, dim3((unsigned)((nhash + 255) / 256)), dim3(256), 0, s, scol + hash_lo, nhash,
                            B->p, toff, info);
+        CSX_LAUNCH_CHECK();
         for (int hb = 0; hb < SG_HASH_BINS; hb++) {
             const int32_t lo = bin_ptr[SG_BIN_HASH0 + hb], nb = bin_ptr[SG_BIN_HASH0 + hb + 1] - lo;
             const int slots = sg_hash_limit(hb) * 3 / 2;   // load factor <= 2/3
-            CSX_TRY(values ? launch_hash1<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
-                           : launch_hash1<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
+            CSX_TRY(values ? launch_hash1<true>(hb, slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
+                           : launch_hash1<false>(hb, slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
         }
         for (int hb = 0; hb < SG_NARROW_BINS; hb++) {
             const int32_t lo = bin_ptr[SG_BIN_NARROW0 + hb], nb = bin_ptr[SG_BIN_NARROW0 + hb + 1] - lo;
             const int slots = sg_hash_limit(hb) * 3 / 2;
-            CSX_TRY(values ? launch_hash2<true>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
-                           : launch_hash2<false>(slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
+            CSX_TRY(values ? launch_hash2<true>(hb, slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, tmp_x)
+                           : launch_hash2<false>(hb, slots, A, B, info + (lo - hash_lo), nb, count, tmp_i, nullptr));
         }
     }
     const int32_t nglobal = bin_ptr[SG_BIN_GLOBAL + 1] - bin_ptr[SG_BIN_GLOBAL];
@@ -1323,8 +1344,10 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
         const size_t wgs = (size_t)std::min<int32_t>(nglobal, SG_GLOBAL_WGS);
         CSX_TRY(g_tmin.alloc(wgs * (size_t)m));
         if (values) CSX_TRY(g_val.alloc(wgs * (size_t)m));
+        g_sg_info.global_wgs = (int64_t)wgs;
         hipLaunchKernelGGL(k_fill_u32, dim3(2048), dim3(256), 0, s, g_tmin, (int64_t)(wgs * (size_t)m), SG_UNSET);
-        if (values) (void)hipMemsetAsync(g_val, 0, wgs * (size_t)m * sizeof(double), s);
+        CSX_LAUNCH_CHECK();
+        if (values) CSX_HIP(hipMemsetAsync(g_val, 0, wgs * (size_t)m * sizeof(double), s));
     }
     // symbolic: distinct rows per column -> C.p
     CSX_TRY((run_bins<false, false>(A, B, scol, bin_ptr, count, nullptr, nullptr, nullptr, g_tmin, nullptr, onepass)));
@@ -1338,8 +1361,10 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
     CSX_TRY(dalloc(&C->i, (size_t)total));
     if (values) CSX_TRY(dalloc(&C->x, (size_t)total));
     if (onepass) {
-        hipLaunchKernelGGL(k_sg_compact, dim3((unsigned)(((int64_t)nhash + 3) / 4)), dim3(256), 0, s, scol + hash_lo,
-                           nhash, toff, C->p, tmp_i, tmp_x, C->i, C->x);
+        const int64_t compact_grid = ((int64_t)nhash + 3) / 4;
+        hipLaunchKernelGGL(k_sg_compact, dim3((unsigned)compact_grid), dim3(256), 0, s, scol + hash_lo, nhash, toff, C->p,
+                           tmp_i, tmp_x, C->i, C->x);
+        sg_launched(SGS_COMPACT, compact_grid);
         CSX_LAUNCH_CHECK();
     }
     if (values) CSX_TRY((run_bins<true, true>(A, B, scol, bin_ptr, count, C->p, C->i, C->x, g_tmin, g_val, onepass)));
@@ -1354,6 +1379,27 @@ int multiply_device(const Csc *A, const Csc *B, Csc *C) {
 }  // namespace csx
 
 using namespace csx;
+
+extern "C" int csx_spgemm_limits(int32_t *out) {   // (no device needed)
+    if (!out) return CSX_EINVAL;
+    const int32_t v[40] = {SG_SEG, SG_THREADS, SG_DENSE_MAX, SG_GLOBAL_WGS, SG_HASH_MAXP, sg_hash_limit(0), sg_hash_limit(1),
+                           sg_hash_limit(2), sg_hash_limit(3), sg_hash_limit(4), sg_hash_limit(5), sg_hash_limit(6),
+                           sg_hash_limit(7), H2_MAXSEG, H2_MAXLEN, H2_MAXP, H1_SEG, H1_MAXP, H1_UN, SGO_MAX, SGO_SLOTS0, SGO_CNT0,
+                           SGO_SLOTS1, SGO_CNT1, SGO_SLOTS2, SGO_CNT2, SGO_DENSE_WAVES, SG_GRID_PER_CU, SG_INFO_FIELDS, SGO_WAVES0,
+                           SGO_WAVES1, SGO_WAVES2, SG_UN, SG_MIN_SLOTS, SG_LDS_BUDGET, SG_WGS_PER_CU_MAX, SG_HASH_BINS,
+                           SG_NARROW_BINS, SGS_COUNT, 0};
+    for (int k = 0; k < 40; k++) out[k] = v[k];
+    return CSX_OK;
+}
+
+extern "C" int csx_spgemm_info(int64_t *out, int32_t cap, int32_t *count) {   // (host state only)
+    if (!out || cap < 0) return CSX_EINVAL;
+    static_assert(sizeof(SgInfo) == sizeof(int64_t) * SG_INFO_FIELDS, "SgInfo is an array of int64 fields");
+    const int64_t *v = reinterpret_cast<const int64_t *>(&g_sg_info);
+    for (int32_t k = 0; k < SG_INFO_FIELDS && k < cap; k++) out[k] = v[k];
+    if (count) *count = SG_INFO_FIELDS;
+    return CSX_OK;
+}
 
 extern "C" int csx_multiply(csx_handle_t hA, csx_handle_t hB, csx_handle_t *out) {
     CSX_TRY(require_ready());

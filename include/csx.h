@@ -291,6 +291,30 @@ int csx_prim_sort_info(int64_t *out, int32_t cap);
  * that is not reproducible bit for bit.  The same holds for the sums cs_dupl and cs_add form from duplicate entries
  * (csx_dupl, csx_add); entries without duplicates come out exact. */
 int csx_multiply(csx_handle_t A, csx_handle_t B, csx_handle_t *out);
+/* Read-backs of cs_multiply's decisions for the tests (host state only; neither launches anything, production code calls neither).
+ * csx_spgemm_limits: the constants csx_spgemm.hip is cut by, without a device: out[40] = SG_SEG (entries of B(:,j) the two-pass
+ * kernel stages at a time), SG_THREADS, SG_DENSE_MAX (rows up to which the accumulator is dense in LDS), SG_GLOBAL_WGS
+ * (workgroups with an accumulator in memory), SG_HASH_MAXP (products a column of the hash bins may have), the products a column of
+ * hash bin 0 .. 7 may have, H2_MAXSEG, H2_MAXLEN, H2_MAXP (entries of B(:,j), entries of the longest column of A it names and
+ * products of a narrow column), H1_SEG, H1_MAXP, H1_UN (entries staged, bitmap bits, entries in flight per half-wave of the
+ * general one-pass kernel), SGO_MAX (entries of C(:,j) up to which the ordered pass keeps its sums in LDS), (slots, entries) of
+ * its three size classes, SGO_DENSE_WAVES (waves of its dense-map kernel at most), SG_GRID_PER_CU (workgroups per CU of the
+ * two-pass grid), the number of fields of csx_spgemm_info, the waves per CU of the three ordered classes, SG_UN (256-product
+ * chunks per step of the two-pass kernel), SG_MIN_SLOTS (the smallest two-pass table), SG_LDS_BUDGET and SG_WGS_PER_CU_MAX (the
+ * one-pass grids hold min(SG_WGS_PER_CU_MAX, SG_LDS_BUDGET / (LDS of a workgroup + 256)) workgroups per CU), the number of hash
+ * bins, of narrow bins, of launch sites, 0.
+ * csx_spgemm_info: what the last C = A*B on the device of this process decided (csx_multiply, and csx_add / csx_assemble where
+ * they multiply): out[0 .. min(cap, *count)) written, *count (or NULL) = the number of fields.  The fields: the columns of C in
+ * each of the 32 bins (0 dense LDS, 1 .. 8 hash by products, 9 .. 14 narrow by products, 15 memory accumulator, 31 no product;
+ * all 0 when the product was empty by its shape), whether the one-pass path ran, the workgroups with an accumulator in memory,
+ * the CUs the grids were cut by, whether the ordered pass ran, the four flags of the ordered pass (some column of C in class 0,
+ * 1, 2, beyond SGO_MAX); then for every launch site first the launches, then (again for every site) the grid of its last launch.
+ * The sites: k_sg_products; k_spgemm as 3 * (0 symbolic, 1 numeric with values, 2 numeric pattern-only) + (0 dense, 1 hash,
+ * 2 memory); k_sg_hash1 as 8 * (values) + hash bin; k_sg_hash2 as 6 * (values) + narrow bin; k_sg_compact; k_sg_dup_cols;
+ * k_sg_values_ordered2 by class; k_sg_values_ordered.  A counter is bumped beside the launch call: a launch that fails is counted
+ * too, and the call then returns its error. */
+int csx_spgemm_limits(int32_t *out);
+int csx_spgemm_info(int64_t *out, int32_t cap, int32_t *count);
 
 /* cs_lsolve / cs_ltsolve / cs_usolve / cs_utsolve, csparse.py:1330-1365,
  * :2368-2385, :2460-2475.  Analyse once (level sets, gather layout in the
