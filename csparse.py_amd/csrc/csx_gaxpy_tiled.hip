@@ -12,7 +12,9 @@
 //   * One workgroup owns one row block for the whole kernel: its slice of y
 //     (m / 256 rows, up to 156 KiB) is loaded into LDS once, takes every random
 //     accumulation as ds_add_f64, and is written back once.  No partial sums in
-//     memory, no second kernel, no inter-workgroup communication.
+//     memory, no second kernel, no inter-workgroup communication.  With 3-byte
+//     keys the tile moves in and out in bulk: eight 16-byte loads (LDS reads) per
+//     thread in flight before the first wait.
 //   * All workgroups walk the column slabs in the same order and at the same
 //     pace (equal work per tile for a random matrix), so the slab of x in use
 //     (<= 1 MiB) is shared through each XCD's L2.
@@ -24,8 +26,13 @@
 //     about one distinct line per clock, and with 4 consecutive entries per lane
 //     the gathers alone cost 0.6 ms of a 1.3 ms kernel (profiles/ablation_r01.md).
 //   * The entry stream (4-byte packed (col,row) key + 8-byte value = the same 12
-//     bytes per entry as CSC) is read once, coalesced, non-temporal, one group
-//     ahead of the gathers.
+//     bytes per entry as CSC) is read once, coalesced, non-temporal, one step ahead:
+//     a step issues its gathers, puts the key and value loads of the next step
+//     behind them and waits for the gathers alone (TiledStep::step).  A step whose
+//     groups all exist -- all but a row block's last -- runs without a test or a
+//     branch: the walk is decided by scalar compares on wave-uniform counters.
+//     (Keys TWO steps ahead, in a ring of three key sets, were built and measured:
+//     slower.  They live on in the ablation build; profiles/tiled_pipeline_ablation.md.)
 //   * 3-byte keys.  A gather instruction covers 64 consecutive entries of the column-sorted tile; when every such
 //     run spans fewer than 512 columns (always, for a matrix like G-rand: a run spans 256 +- 32) an entry needs its
 //     row in the block (15 bits) and its column's offset from the run's first column (9 bits): 3 bytes, the run's
@@ -33,6 +40,7 @@
 //     with a wider run anywhere keeps the 4-byte keys.
 //
 // HBM bytes per call ~ 12 nnz (+0.4 % padding) + 16 m + 8 n * (#XCDs that read x).
+#include <cstdint>
 #include <cstdlib>
 
 #include "csx_internal.h"
@@ -44,6 +52,8 @@ constexpr int TL_GROUP = 256;                   // entries per group = 64 lanes 
 constexpr int TL_LDS_BYTES = 160 * 1024 - 256;  // leave a little headroom below the CU's 160 KiB
 constexpr int TL_LDS_ROWS = TL_LDS_BYTES / 8 - 2;  // y rows per tile (one slot is the padding dummy)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+typedef u32x3 u32x3_a4 __attribute__((aligned(4)));    // the 12-byte key record of a lane: 4-byte aligned
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 __global__ __launch_bounds__(256) void k_tile_keys(int64_t nnz, const int32_t *__restrict__ Ai,
@@ -147,43 +157,75 @@ __global__ __launch_bounds__(256) void k_fill_keys(uint32_t *p, int64_t n, uint3
     for (; i < n; i += stride) p[i] = v;
 }
 
-struct GroupRegs {
-    u32x4 kk;      // 4-byte keys as stored; 3-byte keys unpacked to row | offset << 15
+// What a lane holds of a group of 256 entries, in two records that are loaded at different times: the key record a
+// step's gathers need (and its atomics, for the row), the value record only its atomics need.
+struct KeyRegs {
+    u32x4 kk;      // 4-byte keys as stored; 3-byte keys: x, y, z = the lane's 12 bytes AS STORED (unpacked where they are
+                   // used -- unpacking where they are loaded would wait for the load two steps early)
     u32x4 base;    // 3-byte keys: first column of the four runs
-    f64x2 v0, v1;
     uint32_t info;
 };
+struct ValRegs {
+    f64x2 v0, v1;
+};
 
-template <bool NT, bool K24>
-__device__ __forceinline__ GroupRegs load_group_t(const uint32_t *__restrict__ key, const double *__restrict__ val,
-                                                  const uint32_t *__restrict__ info, const uint32_t *__restrict__ base,
-                                                  int32_t g, int lane) {
-    GroupRegs r;
+// Parts of the step that the ablation build can switch off one by one (profiles/tiled_pipeline_ablation.md); the shipped
+// library holds tl_parts(NW, NG) alone.
+constexpr int TP_KEYS2 = 1;      // keys run two steps ahead of their gathers (three key sets); off: one step ahead (two sets)
+constexpr int TP_FULLSTEP = 2;   // a step whose NG groups all exist takes a body without per-group tests
+constexpr int TP_KEY12 = 4;      // the 12-byte record of 3-byte keys is ONE load
+constexpr int TP_BULKTILE = 8;   // the y tile moves in batches of eight 16-byte accesses per thread
+constexpr int TP_ALL = 15;
+
+template <bool NT, bool K24, bool KEY12>
+__device__ __forceinline__ KeyRegs load_keys_t(const uint32_t *__restrict__ key, const uint32_t *__restrict__ info,
+                                               const uint32_t *__restrict__ base, int32_t g, int lane) {
+    KeyRegs r;
     // (Tried: g = readfirstlane(g), which turns the group's info word and base record into scalar loads -- two of nine
     // vector memory instructions per group gone, same time, 2.4 % more bytes at the memory side.  Not kept.)
-    const int64_t gb = (int64_t)g * TL_GROUP;
     if (K24) {
         // `key` is the byte array of 3-byte keys: 12 bytes per lane, 768 per group
         const uint32_t *kp = key + (int64_t)g * (TL_GROUP * 3 / 4) + 3 * lane;
-        const uint32_t ka = __builtin_nontemporal_load(kp), kb = __builtin_nontemporal_load(kp + 1),
-                       kc = __builtin_nontemporal_load(kp + 2);
-        r.kk.x = ka & 0xFFFFFFu;
-        r.kk.y = (ka >> 24) | ((kb & 0xFFFFu) << 8);
-        r.kk.z = (kb >> 16) | ((kc & 0xFFu) << 16);
-        r.kk.w = kc >> 8;
+        if (KEY12) {
+            const u32x3 k = __builtin_nontemporal_load(reinterpret_cast<const u32x3_a4 *>(kp));
+            r.kk.x = k.x;
+            r.kk.y = k.y;
+            r.kk.z = k.z;
+        } else {
+            r.kk.x = __builtin_nontemporal_load(kp);
+            r.kk.y = __builtin_nontemporal_load(kp + 1);
+            r.kk.z = __builtin_nontemporal_load(kp + 2);
+        }
+        r.kk.w = 0;
         r.base = *reinterpret_cast<const u32x4 *>(base + 4 * (int64_t)g);
-        r.v0 = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(val + gb + 2 * lane));
-        r.v1 = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(val + gb + 128 + 2 * lane));
-    } else if (NT) {
-        r.kk = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(key + gb + 4 * lane));
-        r.v0 = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(val + gb + 2 * lane));
-        r.v1 = __builtin_nontemporal_load(reinterpret_cast<const f64x2 *>(val + gb + 128 + 2 * lane));
     } else {
-        r.kk = *reinterpret_cast<const u32x4 *>(key + gb + 4 * lane);
-        r.v0 = *reinterpret_cast<const f64x2 *>(val + gb + 2 * lane);
-        r.v1 = *reinterpret_cast<const f64x2 *>(val + gb + 128 + 2 * lane);
+        const uint32_t *kp = key + (int64_t)g * TL_GROUP + 4 * lane;
+        r.kk = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(kp)) : *reinterpret_cast<const u32x4 *>(kp);
+        r.base = u32x4{0, 0, 0, 0};
     }
     r.info = info[g];
+    return r;
+}
+
+template <bool NT>
+__device__ __forceinline__ ValRegs load_vals_t(const double *__restrict__ val, int32_t g, int lane) {
+    ValRegs r;
+    const f64x2 *vp = reinterpret_cast<const f64x2 *>(val + (int64_t)g * TL_GROUP + 2 * lane);
+    r.v0 = NT ? __builtin_nontemporal_load(vp) : *vp;
+    r.v1 = NT ? __builtin_nontemporal_load(vp + 64) : vp[64];
+    return r;
+}
+
+// the four keys of a lane as row | column part << shift (3-byte keys: shift 15, column part = offset in the run)
+template <bool K24>
+__device__ __forceinline__ u32x4 unpack_keys(const KeyRegs &k) {
+    if (!K24) return k.kk;
+    const uint32_t ka = k.kk.x, kb = k.kk.y, kc = k.kk.z;
+    u32x4 r;
+    r.x = ka & 0xFFFFFFu;
+    r.y = (ka >> 24) | ((kb & 0xFFFFu) << 8);
+    r.z = (kb >> 16) | ((kc & 0xFFu) << 16);
+    r.w = kc >> 8;
     return r;
 }
 
@@ -193,6 +235,69 @@ __device__ __forceinline__ double load_x(const double *p) {
     if (HOW == 1) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (HOW == 2) return __builtin_nontemporal_load(p);
     return *p;
+}
+
+// The y tile, global memory -> LDS.  Every thread has up to eight 16-byte loads in flight before it waits for the first
+// (a row block of 19 532 rows is 5 batches for 256 threads, not 77 dependent round trips).  The pairs start at the first
+// 16-byte-aligned address of the source; a row before it and a row after the last pair are moved singly.  The LDS
+// address of a pair is 8-byte aligned only (odd when the source began odd): two 8-byte writes.  An index past the end
+// is clamped to the last pair, for the load AND for the write (the last pair is then written more than once, with the
+// same bytes): a batch holds no branch -- under a branch the compiler sinks a load to its use and waits for it alone.
+// Eight pairs per thread and batch up to 256 threads, four with 512 (two waves per SIMD share the registers; either way
+// 32 KiB per CU in flight).
+constexpr int tile_batch(int threads) { return threads > 256 ? 4 : 8; }
+
+template <int T>
+__device__ __forceinline__ void tile_fill(double *ytile, const double *__restrict__ src, int32_t rows) {
+    constexpr int NB = tile_batch(T);
+    const int tid = threadIdx.x;
+    const int32_t head = (rows > 0 && (reinterpret_cast<uintptr_t>(src) & 8)) ? 1 : 0;
+    const int32_t npairs = (rows - head) >> 1;
+    const f64x2 *s2 = reinterpret_cast<const f64x2 *>(src + head);
+    double *d = ytile + head;
+    for (int32_t p0 = 0; p0 < npairs; p0 += NB * T) {
+        f64x2 v[NB];
+        int32_t q[NB];
+#pragma unroll
+        for (int i = 0; i < NB; i++) {
+            const int32_t p = p0 + i * T + tid;
+            q[i] = p < npairs ? p : npairs - 1;
+            v[i] = s2[q[i]];
+        }
+#pragma unroll
+        for (int i = 0; i < NB; i++) {
+            d[2 * q[i]] = v[i].x;
+            d[2 * q[i] + 1] = v[i].y;
+        }
+    }
+    if (tid == 0 && head) ytile[0] = src[0];
+    if (tid == T - 1 && ((rows - head) & 1)) ytile[rows - 1] = src[rows - 1];
+}
+
+// ... and back: LDS reads batched, one wait per batch, 16-byte stores
+template <int T>
+__device__ __forceinline__ void tile_drain(const double *ytile, double *__restrict__ dst, int32_t rows) {
+    const int tid = threadIdx.x;
+    const int32_t head = (rows > 0 && (reinterpret_cast<uintptr_t>(dst) & 8)) ? 1 : 0;
+    const int32_t npairs = (rows - head) >> 1;
+    f64x2 *d2 = reinterpret_cast<f64x2 *>(dst + head);
+    const double *s = ytile + head;
+    constexpr int NB = tile_batch(T);
+    for (int32_t p0 = 0; p0 < npairs; p0 += NB * T) {
+        f64x2 v[NB];
+        int32_t q[NB];
+#pragma unroll
+        for (int i = 0; i < NB; i++) {
+            const int32_t p = p0 + i * T + tid;
+            q[i] = p < npairs ? p : npairs - 1;
+            v[i].x = s[2 * q[i]];
+            v[i].y = s[2 * q[i] + 1];
+        }
+#pragma unroll
+        for (int i = 0; i < NB; i++) d2[q[i]] = v[i];
+    }
+    if (tid == 0 && head) dst[0] = ytile[0];
+    if (tid == T - 1 && ((rows - head) & 1)) dst[rows - 1] = ytile[rows - 1];
 }
 
 // The kernel.  NW waves per workgroup (one workgroup per CU), NG groups per wave and step.
@@ -208,74 +313,129 @@ __device__ __forceinline__ double load_x(const double *p) {
 //   5 = gather from a 256 KB footprint (L2 hits, L1 misses)
 //   6 = full kernel, x gathered with L1-bypassing sc1 loads (computes y)
 //   7 = real x gathers, but the entry stream re-reads the first 32 groups of the row block (L2-resident)
-template <int VARIANT, int NW, int NG, bool K24>
+// PARTS: the TP_ bits above (results are right for every value).
+template <int VARIANT, int NW, int NG, bool K24, int PARTS>
 struct TiledStep {
     static constexpr bool GATHER = !(VARIANT & 1) || VARIANT >= 5, ATOMIC = VARIANT != 3;
     static constexpr bool STREAM_NT = VARIANT != 2;
     static constexpr uint32_t CMASK = VARIANT == 5 ? 32767u : (VARIANT == 4 ? 255u : 0xffffffffu);
     static constexpr int XLOAD = VARIANT == 6 ? 1 : 0;
     static constexpr bool RING = VARIANT == 7;
+    static constexpr int KD = (PARTS & TP_KEYS2) ? 2 : 1;   // steps the keys run ahead
+    static constexpr int NK = KD + 1;                       // key sets: the one in use and KD in flight
+    static constexpr int PERIOD = NK == 3 ? 6 : 2;          // steps after which key set AND value set repeat
+    static constexpr int STRIDE = NG * NW;                  // groups a workgroup takes per step
 
-    // issue the entry loads of the NG groups g, g + NW, ... (indices clamped to the row block's last group
-    // instead of predicated: the loop body stays branch-free)
-    static __device__ __forceinline__ void load_set(GroupRegs (&r)[NG], const uint32_t *__restrict__ key,
-                                                    const double *__restrict__ val, const uint32_t *__restrict__ info,
-                                                    const uint32_t *__restrict__ base, int32_t g, int32_t g0,
-                                                    int32_t gend, int lane) {
+    // The group a lane loads for position gq of the wave's walk: clamped to the row block's last group instead of
+    // predicated, so that no branch stands round a stream load.  `gq` is wave-uniform (it decides the branches of the
+    // step with scalar compares); the index handed to the loads is rebuilt from the lane's own wave number so that
+    // they stay vector loads (see load_keys_t).
+    static __device__ __forceinline__ int32_t clamp_group(int32_t gq, int32_t g0, int32_t gend, int32_t wave_s, int32_t wave_v) {
+        int32_t gg = gq < gend ? gq : gend - 1;
+        if (RING) gg = g0 + ((gg - g0) & 31);
+        return gg - wave_s + wave_v;
+    }
+    static __device__ __forceinline__ void load_key_set(KeyRegs (&r)[NG], const uint32_t *__restrict__ key,
+                                                        const uint32_t *__restrict__ info, const uint32_t *__restrict__ base,
+                                                        int32_t g, int32_t g0, int32_t gend, int32_t wave_s, int32_t wave_v,
+                                                        int lane) {
 #pragma unroll
-        for (int j = 0; j < NG; j++) {
-            int32_t gg = g + j * NW < gend ? g + j * NW : gend - 1;
-            if (RING) gg = g0 + ((gg - g0) & 31);
-            r[j] = load_group_t<STREAM_NT, K24>(key, val, info, base, gg, lane);
-        }
+        for (int j = 0; j < NG; j++)
+            r[j] = load_keys_t<STREAM_NT, K24, (PARTS & TP_KEY12) != 0>(key, info, base,
+                                                                         clamp_group(g + j * NW, g0, gend, wave_s, wave_v), lane);
+    }
+    static __device__ __forceinline__ void load_val_set(ValRegs (&r)[NG], const double *__restrict__ val, int32_t g,
+                                                        int32_t g0, int32_t gend, int32_t wave_s, int32_t wave_v, int lane) {
+#pragma unroll
+        for (int j = 0; j < NG; j++)
+            r[j] = load_vals_t<STREAM_NT>(val, clamp_group(g + j * NW, g0, gend, wave_s, wave_v), lane);
     }
 
-    // gather x for the NG groups in `cur`, put the next NG groups' entry loads behind the gathers, accumulate
-    static __device__ __forceinline__ void step(GroupRegs (&cur)[NG], GroupRegs (&nxt)[NG], double *ytile,
+    // Step number P (mod PERIOD) of a wave's walk, at group g.  In this order: the gathers of this step, whose keys were
+    // asked for KD steps ago; the key loads of step P + KD; the value loads of step P + 1; then the atomics of this
+    // step, which wait for the gathers alone -- vector memory loads return in issue order, so a counted wait for the
+    // gathers leaves everything issued after them in flight, and this step's values, asked for a whole step ago, are
+    // in front of them.  PRED: some of the NG groups may not exist (a row block's last step); every group but the first
+    // is tested.  LOADS: whether a later step exists to load for.
+    template <int P, bool PRED, bool LOADS>
+    static __device__ __forceinline__ void step(KeyRegs (&K)[NK][NG], ValRegs (&V)[2][NG], double *ytile,
                                                 const uint32_t *__restrict__ key, const double *__restrict__ val,
                                                 const uint32_t *__restrict__ info, const uint32_t *__restrict__ base,
-                                                const double *__restrict__ x, int32_t &g, int32_t g0, int32_t gend,
-                                                int lane, int rb_bits, uint32_t rmask, int32_t slab_cols, double &sink) {
+                                                const double *__restrict__ x, int32_t g, int32_t g0, int32_t gend,
+                                                int32_t wave_s, int32_t wave_v, int lane, int rb_bits, uint32_t rmask,
+                                                int32_t slab_cols, double &sink) {
+        constexpr int kc = P % NK, kn = (P + KD) % NK, vc = P % 2, vn = (P + 1) % 2;
+        const int cshift = K24 ? 15 : rb_bits;
         double xv[NG][4];
+        u32x4 kk[NG];
 #pragma unroll
         for (int j = 0; j < NG; j++) {
             xv[j][0] = xv[j][1] = xv[j][2] = xv[j][3] = 1.0;
-            if (GATHER && (j == 0 || g + j * NW < gend)) {
-                const double *xs = x + (int64_t)(cur[j].info >> 9) * slab_cols;
-                if (K24) {
-                    xv[j][0] = load_x<XLOAD>(xs + ((cur[j].base.x + (cur[j].kk.x >> 15)) & CMASK));
-                    xv[j][1] = load_x<XLOAD>(xs + ((cur[j].base.y + (cur[j].kk.y >> 15)) & CMASK));
-                    xv[j][2] = load_x<XLOAD>(xs + ((cur[j].base.z + (cur[j].kk.z >> 15)) & CMASK));
-                    xv[j][3] = load_x<XLOAD>(xs + ((cur[j].base.w + (cur[j].kk.w >> 15)) & CMASK));
-                } else {
-                    xv[j][0] = load_x<XLOAD>(xs + ((cur[j].kk.x >> rb_bits) & CMASK));
-                    xv[j][1] = load_x<XLOAD>(xs + ((cur[j].kk.y >> rb_bits) & CMASK));
-                    xv[j][2] = load_x<XLOAD>(xs + ((cur[j].kk.z >> rb_bits) & CMASK));
-                    xv[j][3] = load_x<XLOAD>(xs + ((cur[j].kk.w >> rb_bits) & CMASK));
-                }
+            kk[j] = unpack_keys<K24>(K[kc][j]);
+            if (GATHER && (!PRED || j == 0 || g + j * NW < gend)) {
+                const double *xs = x + (int64_t)(K[kc][j].info >> 9) * slab_cols;
+                const u32x4 b = K[kc][j].base;     // zero with 4-byte keys
+                xv[j][0] = load_x<XLOAD>(xs + ((b.x + (kk[j].x >> cshift)) & CMASK));
+                xv[j][1] = load_x<XLOAD>(xs + ((b.y + (kk[j].y >> cshift)) & CMASK));
+                xv[j][2] = load_x<XLOAD>(xs + ((b.z + (kk[j].z >> cshift)) & CMASK));
+                xv[j][3] = load_x<XLOAD>(xs + ((b.w + (kk[j].w >> cshift)) & CMASK));
             }
         }
-        load_set(nxt, key, val, info, base, g + NG * NW, g0, gend, lane);
+        if (LOADS) {
+            load_key_set(K[kn], key, info, base, g + KD * STRIDE, g0, gend, wave_s, wave_v, lane);
+            load_val_set(V[vn], val, g + STRIDE, g0, gend, wave_s, wave_v, lane);
+        }
 #pragma unroll
         for (int j = 0; j < NG; j++) {
-            if (j == 0 || g + j * NW < gend) {
+            if (!PRED || j == 0 || g + j * NW < gend) {
                 if (ATOMIC) {
-                    unsafeAtomicAdd(&ytile[cur[j].kk.x & rmask], cur[j].v0.x * xv[j][0]);
-                    unsafeAtomicAdd(&ytile[cur[j].kk.y & rmask], cur[j].v0.y * xv[j][1]);
-                    unsafeAtomicAdd(&ytile[cur[j].kk.z & rmask], cur[j].v1.x * xv[j][2]);
-                    unsafeAtomicAdd(&ytile[cur[j].kk.w & rmask], cur[j].v1.y * xv[j][3]);
+                    unsafeAtomicAdd(&ytile[kk[j].x & rmask], V[vc][j].v0.x * xv[j][0]);
+                    unsafeAtomicAdd(&ytile[kk[j].y & rmask], V[vc][j].v0.y * xv[j][1]);
+                    unsafeAtomicAdd(&ytile[kk[j].z & rmask], V[vc][j].v1.x * xv[j][2]);
+                    unsafeAtomicAdd(&ytile[kk[j].w & rmask], V[vc][j].v1.y * xv[j][3]);
                 } else {
-                    sink += cur[j].v0.x * xv[j][0] + cur[j].v0.y * xv[j][1] + cur[j].v1.x * xv[j][2] +
-                            cur[j].v1.y * xv[j][3] +
-                            (double)((cur[j].kk.x ^ cur[j].kk.y ^ cur[j].kk.z ^ cur[j].kk.w) & 1u);
+                    sink += V[vc][j].v0.x * xv[j][0] + V[vc][j].v0.y * xv[j][1] + V[vc][j].v1.x * xv[j][2] +
+                            V[vc][j].v1.y * xv[j][3] + (double)((kk[j].x ^ kk[j].y ^ kk[j].z ^ kk[j].w) & 1u);
                 }
             }
         }
-        g += NG * NW;
+    }
+
+    // One step of the walk; true when it was the row block's last.  A full step (all NG groups exist: one scalar
+    // compare) takes the body without tests; the last step of a row block, when it is short, takes the predicated
+    // body and loads nothing.
+    template <int P>
+    static __device__ __forceinline__ bool advance(KeyRegs (&K)[NK][NG], ValRegs (&V)[2][NG], double *ytile,
+                                                   const uint32_t *__restrict__ key, const double *__restrict__ val,
+                                                   const uint32_t *__restrict__ info, const uint32_t *__restrict__ base,
+                                                   const double *__restrict__ x, int32_t &g, int32_t g0, int32_t gend,
+                                                   int32_t wave_s, int32_t wave_v, int lane, int rb_bits, uint32_t rmask,
+                                                   int32_t slab_cols, double &sink) {
+        if (PARTS & TP_FULLSTEP) {
+            if (g + (NG - 1) * NW < gend) {
+                step<P, false, true>(K, V, ytile, key, val, info, base, x, g, g0, gend, wave_s, wave_v, lane, rb_bits, rmask,
+                                     slab_cols, sink);
+            } else {
+                step<P, true, false>(K, V, ytile, key, val, info, base, x, g, g0, gend, wave_s, wave_v, lane, rb_bits, rmask,
+                                     slab_cols, sink);
+                return true;
+            }
+        } else {
+            step<P, true, true>(K, V, ytile, key, val, info, base, x, g, g0, gend, wave_s, wave_v, lane, rb_bits, rmask,
+                                slab_cols, sink);
+        }
+        g += STRIDE;
+        return g >= gend;
     }
 };
 
-template <int VARIANT, int NW, int NG, bool K24>
+// Which parts the shipped kernel carries, by what each was measured to be worth (profiles/tiled_pipeline_ablation.md):
+// with 3-byte keys the test-free full step and the bulk tile copy; with 4-byte keys none -- there every combination
+// measured was slower than the step without them.  Keys two steps ahead and the single 12-byte key load did not pay
+// anywhere and exist in the ablation build only.
+constexpr int tl_parts(bool k24) { return k24 ? TP_FULLSTEP | TP_BULKTILE : 0; }
+
+template <int VARIANT, int NW, int NG, bool K24, int PARTS>
 __global__ __launch_bounds__(64 * NW) void k_gaxpy_tiled(const int32_t *__restrict__ rb_gptr,
                                                          const uint32_t *__restrict__ group_info,
                                                          const uint32_t *__restrict__ tile_key,
@@ -285,34 +445,59 @@ __global__ __launch_bounds__(64 * NW) void k_gaxpy_tiled(const int32_t *__restri
                                                          int32_t m, int32_t nrb, int32_t row_block,
                                                          int32_t slab_cols, int rb_bits) {
     extern __shared__ __attribute__((aligned(16))) double ytile[];  // row_block doubles + the padding dummy row
-    typedef TiledStep<VARIANT, NW, NG, K24> S;
+    typedef TiledStep<VARIANT, NW, NG, K24, PARTS> S;
     const uint32_t rmask = K24 ? 0x7FFFu : (1u << rb_bits) - 1u;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int32_t wave_v = threadIdx.x >> 6, wave_s = __builtin_amdgcn_readfirstlane(wave_v);
     double sink = 0.0;
     for (int32_t rb = blockIdx.x; rb < nrb; rb += gridDim.x) {
         const int64_t row0 = (int64_t)rb * row_block;
         const int32_t rows = (int32_t)((row0 + row_block <= m) ? row_block : (m - row0));
-        for (int k = threadIdx.x; k < rows; k += 64 * NW) ytile[k] = y[row0 + k];
-        __syncthreads();
         const int32_t gend = rb_gptr[rb + 1];
         const int32_t g0 = rb_gptr[rb];
-        // Each wave walks its groups NG at a time (g, g + NW, ...) with two register sets used alternately (no
-        // copies): while set A is gathered and accumulated, set B's entries are in flight.  Padding entries
-        // point at a dummy LDS row.
-        int32_t g = g0 + wave;
+        // Each wave walks its groups NG at a time (g, g + NW, ...) with a ring of key sets and two value sets, all
+        // named by the step number (no copies: a copy would wait for the load).  The first loads of the walk -- the
+        // keys of steps 0 .. KD - 1 and the values of step 0 -- go out BEFORE the y tile is filled, so the stream
+        // starts under the fill.  Padding entries point at a dummy LDS row.
+        int32_t g = g0 + wave_s;
+        KeyRegs K[S::NK][NG];
+        ValRegs V[2][NG];
         if (g < gend) {
-            GroupRegs A[NG], B[NG];
-            S::load_set(A, tile_key, tile_val, group_info, tile_base, g, g0, gend, lane);
+#pragma unroll
+            for (int d = 0; d < S::KD; d++)
+                S::load_key_set(K[d], tile_key, group_info, tile_base, g + d * S::STRIDE, g0, gend, wave_s, wave_v, lane);
+            S::load_val_set(V[0], tile_val, g, g0, gend, wave_s, wave_v, lane);
+        }
+        if (PARTS & TP_BULKTILE) {
+            tile_fill<64 * NW>(ytile, y + row0, rows);
+        } else {
+            for (int k = threadIdx.x; k < rows; k += 64 * NW) ytile[k] = y[row0 + k];
+        }
+        __syncthreads();
+        if (g < gend) {
+#define CSX_TILED_ADVANCE(P)                                                                                          \
+    if (S::template advance<P>(K, V, ytile, tile_key, tile_val, group_info, tile_base, x, g, g0, gend, wave_s, wave_v, \
+                               lane, rb_bits, rmask, slab_cols, sink))                                                 \
+        break;
             for (;;) {
-                S::step(A, B, ytile, tile_key, tile_val, group_info, tile_base, x, g, g0, gend, lane, rb_bits, rmask, slab_cols, sink);
-                if (g >= gend) break;
-                S::step(B, A, ytile, tile_key, tile_val, group_info, tile_base, x, g, g0, gend, lane, rb_bits, rmask, slab_cols, sink);
-                if (g >= gend) break;
+                CSX_TILED_ADVANCE(0)
+                CSX_TILED_ADVANCE(1)
+                if constexpr (S::PERIOD == 6) {
+                    CSX_TILED_ADVANCE(2)
+                    CSX_TILED_ADVANCE(3)
+                    CSX_TILED_ADVANCE(4)
+                    CSX_TILED_ADVANCE(5)
+                }
             }
+#undef CSX_TILED_ADVANCE
         }
         __syncthreads();
         if (!S::ATOMIC && sink == 12345.678) ytile[0] = sink;  // keep the ablated arithmetic alive
-        for (int k = threadIdx.x; k < rows; k += 64 * NW) y[row0 + k] = ytile[k];
+        if (PARTS & TP_BULKTILE) {
+            tile_drain<64 * NW>(ytile, y + row0, rows);
+        } else {
+            for (int k = threadIdx.x; k < rows; k += 64 * NW) y[row0 + k] = ytile[k];
+        }
         __syncthreads();
     }
 }
@@ -505,28 +690,42 @@ int gaxpy_tiled_group_counts(const TiledPlan *t, std::vector<int32_t> &groups) {
     return CSX_OK;
 }
 
+// A kernel instance may use the whole LDS: asked for once per instance and device, not at every launch.
+template <int V, int NW, int NG, bool K24, int PARTS>
+static hipError_t gaxpy_tiled_allow_lds() {
+    static int done_on = -1;
+    if (done_on == ctx().device) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gaxpy_tiled<V, NW, NG, K24, PARTS>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, TL_LDS_BYTES);
+    if (e == hipSuccess) done_on = ctx().device;
+    return e;
+}
+
 static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shape) {
     const TiledPlan *t = A->tiled.get();
     hipStream_t s = ctx().stream;
     const size_t lds = (((size_t)(t->row_block + 1) * sizeof(double)) + 15) & ~(size_t)15;  // + dummy row
     const int32_t nwg = ctx().cus > 0 ? ctx().cus : 256;
     const unsigned grid = (unsigned)(t->nrb < nwg ? t->nrb : nwg);
-#define CSX_TILED_LAUNCH_K(V, NW, NG, K24)                                                                           \
+#define CSX_TILED_LAUNCH_K(V, NW, NG, K24, PARTS)                                                                    \
     {                                                                                                                \
-        CSX_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gaxpy_tiled<V, NW, NG, K24>),                  \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, TL_LDS_BYTES));                      \
-        hipLaunchKernelGGL((k_gaxpy_tiled<V, NW, NG, K24>), dim3(grid), dim3(64 * NW), lds, s, t->tile_ptr,          \
+        CSX_HIP((gaxpy_tiled_allow_lds<V, NW, NG, K24, PARTS>()));                                                   \
+        hipLaunchKernelGGL((k_gaxpy_tiled<V, NW, NG, K24, PARTS>), dim3(grid), dim3(64 * NW), lds, s, t->tile_ptr,   \
                            (const uint32_t *)t->tile_len.get(),                                                      \
                            K24 ? reinterpret_cast<const uint32_t *>(t->tile_key24.get()) : t->tile_key.get(),        \
                            t->tile_base,                                                                             \
                            t->tile_val, x, y, A->m, t->nrb, t->row_block, t->slab_cols, t->rb_bits);                 \
     }
-#define CSX_TILED_LAUNCH(V, NW, NG)                                                                                  \
+#define CSX_TILED_LAUNCH_P(V, NW, NG, P24, P32)                                                                      \
     {                                                                                                                \
-        if (t->tile_key24) CSX_TILED_LAUNCH_K(V, NW, NG, true) else CSX_TILED_LAUNCH_K(V, NW, NG, false)             \
+        if (t->tile_key24) CSX_TILED_LAUNCH_K(V, NW, NG, true, P24) else CSX_TILED_LAUNCH_K(V, NW, NG, false, P32)   \
     }
+#define CSX_TILED_LAUNCH(V, NW, NG) CSX_TILED_LAUNCH_P(V, NW, NG, tl_parts(true), tl_parts(false))
 #ifdef CSX_ABLATION
-    // CSX_TILED_VARIANT = V + 100 * NW + 10000 * NG (NW, NG default to the shipped TL_WAVES, TL_NG)
+    // CSX_TILED_VARIANT = V + 100 * NW + 10000 * NG (NW, NG default to the shipped TL_WAVES, TL_NG).
+    // V = 0..7: the VARIANTs of k_gaxpy_tiled.  V = 10 + mask (4 x 5 only): the full kernel with the parts in `mask`
+    // switched OFF -- 1 keys two steps ahead, 2 test-free full step, 4 one 12-byte key load, 8 bulk tile copy;
+    // 25 = all four off, the step as it was before them.
     int code = 0;
     if (const char *e = std::getenv("CSX_TILED_VARIANT")) code = std::atoi(e);
     const int v = code % 100, nw = (code / 100) % 100 ? (code / 100) % 100 : TL_WAVES, ng = code / 10000 ? code / 10000 : TL_NG;
@@ -536,6 +735,11 @@ static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shap
         else if (nw == 4 && ng == 5) CSX_TILED_LAUNCH(V, 4, 5) \
         else if (nw == 2 && ng == 10) CSX_TILED_LAUNCH(V, 2, 10) \
         else return CSX_EINVAL;                              \
+    } else
+#define CSX_OFF(MASK)                                                        \
+    if (v == 10 + MASK) {                                                    \
+        if (nw == 4 && ng == 5) CSX_TILED_LAUNCH_P(0, 4, 5, TP_ALL & ~(MASK), TP_ALL & ~(MASK)) \
+        else return CSX_EINVAL;                                              \
     } else
     if (v == 0) {
         if (nw == 16 && ng == 1) CSX_TILED_LAUNCH(0, 16, 1)
@@ -565,8 +769,11 @@ static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shap
         else if (nw == 4 && ng == 7) CSX_TILED_LAUNCH(0, 4, 7)
         else return CSX_EINVAL;
     } else
-    CSX_V(1) CSX_V(2) CSX_V(3) CSX_V(4) CSX_V(5) CSX_V(6) CSX_V(7) return CSX_EINVAL;
+    CSX_V(1) CSX_V(2) CSX_V(3) CSX_V(4) CSX_V(5) CSX_V(6) CSX_V(7)
+    CSX_OFF(0) CSX_OFF(1) CSX_OFF(2) CSX_OFF(3) CSX_OFF(4) CSX_OFF(5) CSX_OFF(6) CSX_OFF(7) CSX_OFF(8) CSX_OFF(9)
+    CSX_OFF(10) CSX_OFF(11) CSX_OFF(12) CSX_OFF(13) CSX_OFF(14) CSX_OFF(15) return CSX_EINVAL;
 #undef CSX_V
+#undef CSX_OFF
     (void)shape;
 #else
     switch (shape) {
@@ -577,6 +784,7 @@ static int gaxpy_tiled_launch(const Csc *A, const double *x, double *y, int shap
     }
 #endif
 #undef CSX_TILED_LAUNCH
+#undef CSX_TILED_LAUNCH_P
 #undef CSX_TILED_LAUNCH_K
     CSX_LAUNCH_CHECK();
     return CSX_OK;

@@ -1,6 +1,16 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of k_gaxpy_tiled variants in ONE process (needs build.py --ablation).
-code = VARIANT + 100 * waves + 10000 * groups-per-step.   usage: tools/ablate_tiled.py CODE [CODE ...] [--n N] [--gen uniform]"""
+code = VARIANT + 100 * waves + 10000 * groups-per-step.   usage: tools/ablate_tiled.py CODE [CODE ...] [--n N] [--gen uniform]
+
+VARIANT 0 .. 7: the timing variants of k_gaxpy_tiled (csx_gaxpy_tiled.hip; 1, 3, 4, 5, 7 compute wrong results on purpose).
+VARIANT 10 + mask (4 x 5 only): the kernel with all four parts of profiles/tiled_pipeline_ablation.md, those in `mask` switched
+OFF, results right:
+    1 keys two steps ahead of their gathers    2 test-free body for full steps    4 the 12-byte key record as one load
+    8 y tile moved in batches of 16-byte accesses
+so 10 has all four, 11 / 12 / 14 / 18 have one part off each, 25 all four (the step as it was before them).  VARIANT 0 is the
+shipped kernel: the parts tl_parts() of csx_gaxpy_tiled.hip gives the plan's key width.
+The last line is the interleaved spread: the largest (max - min) / median of any code's repetitions -- a part whose
+removal costs less than that has not been shown to pay."""
 import argparse
 import os
 import statistics
@@ -42,3 +52,4 @@ for c in a.codes:
     t = times[c]
     med = statistics.median(t)
     print("code %7s  median %.4f ms  min %.4f  max %.4f  frac(median) %.3f" % (c, med, min(t), max(t), by / med / 1e6 / 8000.0))
+print("interleaved spread %.2f %%" % (100.0 * max((max(t) - min(t)) / statistics.median(t) for t in times.values())))
