@@ -186,6 +186,11 @@ _PROTOS = {
     "csx_assemble_matrix": [H, H, C.POINTER(H)],
     "csx_assemble": [H, H, H],
     "csx_assemble_plan_info": [H, C.POINTER(C.c_int64)],
+    "csx_assemble_pullback": [H, H, H],
+    "csx_assemble_pullback_host": [C.c_int32, C.c_int64, _i32p, _i32p, _f64p, _f64p],
+    "csx_pattern_outer": [H, H, H, C.c_int32, C.c_int, C.c_double, H],
+    "csx_pattern_outer_host": [C.c_int32, C.c_int32, _i32p, _i32p, C.c_int32, C.c_int, C.c_double, _f64p, _f64p, _f64p],
+    "csx_pattern_outer_limits": [C.POINTER(C.c_int64)],
     "csx_multiply_plan_count": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_int64),
                                 C.POINTER(C.c_int64)],
     "csx_multiply_plan_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
@@ -538,6 +543,38 @@ def gs_host(op, V, W, mask, coef=None, length=None, negate=False, nv=None):
            GS_COMBINE: np.full((rows, k), np.nan)}[op]
     check(load().csx_gs_host(op, rows, k, nv, pd(V), pd(W), pi(m), 1 if negate else 0, pd(cf), pi(ln), pd(out)), "csx_gs_host")
     return {GS_PROJECT: out, GS_UPDATE: (W, out), GS_SCALE: V, GS_COMBINE: out}[op]
+
+
+PATTERN_OUTER_LIMITS = ("PO_LANES", "PO_CHUNK", "PO_WAVE_CHUNK", "PO_FLIGHT", "PO_KEPT")
+
+
+def pattern_outer_limits():
+    """the constants of csx_pattern_outer's value rule and kernel (csx_pattern_outer.h), asked of the library; no GPU needed: a
+    dict by the names of PATTERN_OUTER_LIMITS (include/csx.h: csx_pattern_outer_limits)"""
+    out = (C.c_int64 * len(PATTERN_OUTER_LIMITS))()
+    check(load().csx_pattern_outer_limits(out), "csx_pattern_outer_limits")
+    return {name: int(out[k]) for k, name in enumerate(PATTERN_OUTER_LIMITS)}
+
+
+def pattern_outer_host(m, n, p, i, U, V, nrhs, alpha=1.0, sym=False):
+    """csx_pattern_outer_host on numpy arrays: the nnz values of alpha U V' on the pattern (p, i); U m x nrhs, V n x nrhs.  No GPU
+    needed."""
+    p, i = i32(p), i32(i)
+    U, V = f64(np.asarray(U, dtype=np.float64).reshape(-1)), f64(np.asarray(V, dtype=np.float64).reshape(-1))
+    out = np.full(max(int(p[n]), 1), np.nan)
+    check(load().csx_pattern_outer_host(m, n, pi(p), pi(i), nrhs, 1 if sym else 0, float(alpha), pd(U), pd(V), pd(out)),
+          "csx_pattern_outer_host")
+    return out[:int(p[n])]
+
+
+def assemble_pullback_host(sp, src, g):
+    """csx_assemble_pullback_host on numpy arrays: the nz triplet gradients of the slot gradients g through a plan's sp, src
+    (csx_assemble_plan_host).  No GPU needed."""
+    sp, src, g = i32(sp), i32(src), f64(g)
+    nnz, nz = len(sp) - 1, len(src)
+    out = np.full(max(nz, 1), np.nan)
+    check(load().csx_assemble_pullback_host(nnz, nz, pi(sp), pi(src), pd(g), pd(out)), "csx_assemble_pullback_host")
+    return out[:nz]
 
 
 BGS_LIMITS = ("GS_CHUNK", "GS_FAN", "BGS_MAXW", "BGS_GROUP", "BGS_TILE")

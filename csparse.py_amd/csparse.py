@@ -641,6 +641,38 @@ def residual_block(A, X, B, trans=False, residual=True, sym=False):
     return dR, omega, rnorm
 
 
+def outer_on_pattern(A, U, V, alpha=1.0, sym=False):
+    """alpha U V' sampled on A's pattern: a NEW dvec of nnz(A) doubles in A's storage order, out[q] = alpha * sum_c U[i_q, c] *
+    V[j_q, c] for the stored entry q at (i_q, j_q) -- never the m x n product (include/csx.h "outer product ... on a pattern",
+    DESIGN.md §31).  With U the adjoint solution and V the solution of a solve, alpha = -1, it is the gradient of a loss with
+    respect to A's entries, in the form refactor(values) and add_plan.add(values=...) take.  Only A's pattern is read: a
+    pattern-only A is accepted; duplicate and unsorted row indices are fine, every slot gets its own value.  One order of
+    operations that depends on k alone: a run is deterministic, NaN and inf reach only the entries whose two rows hold them.
+    sym=True: A is square and stands for the symmetric matrix S in its upper triangle, as in residual_block(sym=True): an
+    entry above the diagonal stands at two places of S and takes alpha * sum_c (U[i, c] V[j, c] + U[j, c] V[i, c]), a diagonal
+    entry alpha * sum_c U[i, c] V[i, c], an entry below the diagonal +0.0.
+
+    U (m rows), V (n rows): dvec blocks, 2-D row-major arrays, or 1-D vectors / lists (one column); they may be the same
+    block.  False for a non-CSC A, U or V None, unequal k, or sym=True with a non-square A; IndexError for blocks with too few
+    rows."""
+    if not CS_CSC(A) or U is None or V is None or (sym and A.m != A.n):
+        return False
+    same = U is V
+    U, urows, k = _block_shape(U)
+    V, vrows, kv = (U, urows, k) if same else _block_shape(V)
+    if k != kv or k < 1:
+        return False
+    if urows < A.m or vrows < A.n:
+        raise IndexError("list index out of range")
+    dU = U if isinstance(U, dvec) else dvec(U)
+    dV = dU if same else (V if isinstance(V, dvec) else dvec(V))
+    out = dvec(_meta(A)[0])
+    with _Resident(A) as dA:
+        _csx.check(_csx.lib().csx_pattern_outer(dA.handle, dU.handle, dV.handle, k, 1 if sym else 0, float(alpha), out.handle),
+                   "csx_pattern_outer")
+    return out
+
+
 def cs_gaxpy_prepare(A, mode=GAXPY_AUTO):
     """Build the SpMV plan of a pinned matrix ahead of time (outside timed regions)."""
     cs_pin(A)
@@ -847,6 +879,12 @@ class _AssemblyPlan(_FoldPlan):
     def update(self, values=None):
         return self._update(self._values(values, "update"))
 
+    def pullback(self, gA):
+        g = self._vector(gA, self.nnz, "pullback: %%d values given, the plan's matrix has %d entries" % self.nnz)
+        out = dvec(self.nz)
+        _csx.check(_csx.lib().csx_assemble_pullback(self._handle, g.handle, out.handle), "csx_assemble_pullback")
+        return out
+
 
 def assembly_plan(T):
     """The plan of cs_dupl(cs_compress(T)) for a triplet list whose (i, j) stay and whose values change every step
@@ -860,7 +898,11 @@ def assembly_plan(T):
                          bits -- which is what lusol_factor(P.matrix).refactor(...) and btf_factor(P.matrix).refactor(...) take.
       .update(values)    the same values straight into .matrix, in place: the plans cached on it go, solvers built on it
                          re-plan, host lists already read from it are refreshed in place.  Returns .matrix.  The first update
-                         of a pattern-only .matrix gives it its values; update() without values is a ValueError."""
+                         of a pattern-only .matrix gives it its values; update() without values is a ValueError.
+      .pullback(gA)      the gradient with respect to the triplet values of a loss whose gradient with respect to the assembled
+                         values is gA (list, numpy array or dvec of exactly nnz numbers in .matrix's storage order, as solve_grad
+                         returns it; ValueError otherwise): a NEW dvec of nz doubles in T's triplet order, gT[t] = gA[slot of t]
+                         -- a slot is the sum of its triplets, so each takes the slot's gradient, bit for bit; one launch."""
     if not CS_TRIPLET(T):
         return None
     return _AssemblyPlan(T)
@@ -2767,6 +2809,39 @@ class _Refinable(object):
         _write_back(bhost, db, n * k)
         return {"omega0": w0, "omega": w, "rnorm": rn, "steps": steps, "solves": solves}
 
+    def solve_grad(self, x, gx, trans=False, refine=0):
+        """(gb, gA): the gradient of a scalar loss through x = A^-1 b (trans: A'^-1 b) with respect to b and to the stored
+        entries of A.  x: the solution block solve() gave; gx: the loss gradient with respect to x, same
+        shape, not modified.  gb = Lambda, the adjoint solution A' Lambda = gx (trans: A Lambda = gx), a NEW dvec block made by
+        one solve of this solver in the other direction, in the order a solve of gx would take (refine > 0: by
+        refine(maxit=refine) in that direction instead).  gA: a NEW dvec of nnz doubles on the pattern of the factored matrix,
+        in its storage order -- what refactor(values) takes --, gA[q] = -sum_c Lambda[i_q, c] x[j_q, c] (trans: -sum_c x[i_q, c]
+        Lambda[j_q, c]) by outer_on_pattern.  One host vector in gives 1-D numpy arrays out.  ValueError for unequal k,
+        IndexError for short blocks."""
+        return self._solve_grad(x, gx, bool(trans), refine, self._rA, self._operator, False)
+
+    def _solve_grad(self, x, gx, trans, refine, pattern, operator, sym):
+        """pattern: the `cs` whose stored entries gA is about; operator: a callable that gives the context manager of the
+        operator's handle (taken only by refine > 0)"""
+        n = self._rn
+        X, xrows, k = _block_shape(x)
+        G, grows, kg = _block_shape(gx)
+        if k != kg or k < 1:
+            raise ValueError("solve_grad: x and gx have different numbers of columns")
+        if xrows < n or grows < n:
+            raise IndexError("list index out of range")
+        single = not isinstance(x, dvec) and not isinstance(gx, dvec) and X.ndim == 1 and G.ndim == 1
+        gb = gx.copy() if isinstance(gx, dvec) else dvec(G[:n])
+        adjoint = False if sym else not trans          # S = S': the symmetric solvers have one direction
+        if int(refine) > 0:
+            self._refine(gb, int(refine), adjoint, operator())
+        else:
+            self._solve_block(gb, adjoint, not isinstance(gx, dvec))
+        dX = X if isinstance(X, dvec) else dvec(X)
+        U, V = (dX, gb) if trans else (gb, dX)
+        gA = outer_on_pattern(pattern, U, V, alpha=-1.0, sym=sym)
+        return (gb.numpy().reshape(-1)[:n], gA.numpy()) if single else (gb, gA)
+
     def gmres(self, b, restart=16, maxit=64, inner_tol=2.0 ** -26, trans=False):
         """solve, then restarted GMRES with this factor as the preconditioner on the columns whose backward error is above
         2^-52; b is overwritten with x.  Where refine() needs the factor to contract, this needs only a Krylov
@@ -3081,6 +3156,20 @@ class _SymRefinable(_Refinable):
         from the factored one in r rows ends in r + 1 inner steps, however far apart the two are.  _Refinable.gmres's loop,
         arguments and result."""
         return self._gmres(b, restart, maxit, inner_tol, False, lambda: self._operator_for(A))
+
+    def solve_grad(self, x, gx, refine=0, A=None):
+        """(gb, gA) as _Refinable.solve_grad for S x = b, S the symmetric matrix in the upper triangle of the operator (see
+        backward_error): gb = S^-1 gx by this factor's solve (refine > 0: refine(maxit=refine, A=A)), gA on the pattern of the
+        factored matrix -- or of A=, of which only the pattern is read unless refine > 0 -- in sym mode: an entry above the
+        diagonal stands at two places of S and takes -sum_c (gb[i, c] x[j, c] + gb[j, c] x[i, c]), a diagonal entry
+        -sum_c gb[i, c] x[i, c], an entry below the diagonal +0.0.  RuntimeError for A=None after update / downdate /
+        cs_updown changed the factor, as backward_error."""
+        if A is not None:
+            if not CS_CSC(A) or A.m != self._rn or A.n != self._rn:
+                raise ValueError("A= must be a square CSC matrix of order %d" % self._rn)
+        elif self._stands != self._dev.version:
+            self._operator_for(None)        # raises the RuntimeError of backward_error
+        return self._solve_grad(x, gx, False, refine, A if A is not None else self._rA, lambda: self._operator_for(A), True)
 
     def eigsh(self, nev, M=None, sigma=0.0, block=None, maxblocks=32, tol=2.0 ** -30, seed=0, v0=None, A=None):
         """The nev eigenpairs of K x = lambda M x nearest sigma, by unrestarted shift-invert block Lanczos with full
@@ -4068,6 +4157,10 @@ def hqrsol_factor(A, order=0):
         def gmres(self, b, restart=16, maxit=64, inner_tol=2.0 ** -26, trans=False):
             self._square_only("gmres")
             return _Refinable.gmres(self, b, restart, maxit, inner_tol, trans)
+
+        def solve_grad(self, x, gx, trans=False, refine=0):
+            self._square_only("solve_grad")
+            return _Refinable.solve_grad(self, x, gx, trans, refine)
 
         def condest(self):
             self._square_only("condest")

@@ -54,9 +54,38 @@ static int assemble_launch(AsmPlan *P, const double *Tx, double *out) {
     return c.end();
 }
 
+// The pull-back of the fold: every triplet of slot s takes g[s] (a copy of bits).  A lane per slot; sp null: no duplicates.
+__global__ __launch_bounds__(256) void k_assemble_pullback(int32_t nnz, const int32_t *__restrict__ sp,
+                                                           const int32_t *__restrict__ src, const double *__restrict__ g,
+                                                           double *__restrict__ out) {
+    const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nnz) return;
+    const double v = g[s];
+    if (!sp) {
+        out[src[s]] = v;
+        return;
+    }
+    for (int32_t u = sp[s], e = sp[s + 1]; u < e; u++) out[src[u]] = v;
+}
+
 }  // namespace csx
 
 using namespace csx;
+
+extern "C" int csx_assemble_pullback(csx_handle_t h, csx_handle_t hg, csx_handle_t hout) {
+    CSX_TRY(require_ready());
+    AsmPlan *P = (AsmPlan *)get(h, K_ASMPLAN);
+    Vec *g = vec(hg), *o = vec(hout);
+    if (!P || !g || !o || g->len < P->core.nnz || o->len < P->nz) return CSX_EINVAL;
+    const uintptr_t gb = (uintptr_t)g->d, ge = gb + (uintptr_t)P->core.nnz * sizeof(double);
+    const uintptr_t ob = (uintptr_t)o->d, oe = ob + (uintptr_t)P->nz * sizeof(double);
+    if (P->nz > 0 && gb < oe && ob < ge) return CSX_EINVAL;
+    if (P->core.nnz == 0) return CSX_OK;
+    hipLaunchKernelGGL(k_assemble_pullback, dim3((unsigned)(((int64_t)P->core.nnz + 255) / 256)), dim3(256), 0, ctx().stream,
+                       P->core.nnz, P->core.sp.get(), P->src.get(), (const double *)g->d, (double *)o->d);
+    CSX_LAUNCH_CHECK();
+    return CSX_OK;
+}
 
 extern "C" int csx_assemble_plan(int32_t m, int32_t n, int64_t nz, const int32_t *Ti, const int32_t *Tj, csx_handle_t *out) {
     CSX_TRY(require_ready());

@@ -1294,6 +1294,49 @@ int csx_bgs_combine(csx_handle_t V, int32_t nv, int32_t b, csx_handle_t U, int32
 int csx_bgs_host(int op, int64_t rows, int32_t b, int32_t q, int32_t nv, const double *V, double *W, int negate, const double *coef,
                  double *out);
 
+/* ---- outer product of two blocks sampled on a pattern: the gradient of a solve with respect to the stored entries
+ * (outer_on_pattern, solve_grad) ----
+ * U is m x nrhs, V is n x nrhs, row-major.  For the stored entry q of the m x n matrix A at (i, j) = (A.i[q], its column):
+ *     mode 0 (general):  out[q] = alpha * sum over c of U[i,c] * V[j,c]
+ *     mode 1 (sym; m == n, U and V both n x nrhs): A stands for the symmetric matrix S that csx_residual_sym_block reads in it.
+ *         i <  j:  out[q] = alpha * sum over c of (U[i,c] * V[j,c] + U[j,c] * V[i,c])     (the entry stands at two places of S)
+ *         i == j:  out[q] = alpha * sum over c of  U[i,c] * V[i,c]
+ *         i >  j:  out[q] = +0.0                                                           (not part of S; alpha is not applied)
+ * Only A.p and A.i are read: a pattern-only A is legal; duplicate and unsorted row indices are legal, every slot gets its value.
+ * Value rule (device and csx_pattern_outer_host alike, fp contract off: every product is rounded, then added).  The order of the
+ * sum over c is a function of nrhs alone:
+ *     W = min(PO_LANES, smallest power of two >= nrhs) partial sums s[0 .. W).
+ *     Partial l takes the columns c = l, l + W, l + 2 W, ... < nrhs, ascending.  Its first product is ASSIGNED, every further
+ *     product is one rounded addition, s[l] = s[l] + t.  In sym mode with i < j a column gives two products, U[i,c] * V[j,c]
+ *     first, then U[j,c] * V[i,c].  A partial without a column (l >= nrhs) is +0.0 and is combined like any other.
+ *     Combine: for d = W/2, W/4, ..., 1:  s[l] = s[l] + s[l + d] for every l < d.
+ *     out[q] = alpha * s[0], one rounded product (alpha = -1 is the exact negation).
+ * nrhs == 1 is the single rounded product times alpha.  NaN and inf propagate, and only into the entries whose two rows hold
+ * them.  No atomics, no scratch allocation, one launch queued on the context's stream, no host synchronisation (a matrix from
+ * csx_csc_wrap is checked once, as everywhere).
+ * csx_pattern_outer: U, V device vectors of at least m nrhs and n nrhs doubles (they may be the same block), out a device vector
+ *   of at least nnz doubles.  CSX_EINVAL, nothing written: an unknown handle, nrhs < 1, a mode other than 0 or 1, sym with
+ *   m != n, U, V or out too short, out overlapping U or V.  m == 0, n == 0 and nnz == 0 are legal and write nothing.
+ * csx_pattern_outer_host: the rule on host arrays (no device); CSX_EINVAL for the same sizes and modes, a null array that would
+ *   be read or written, p not ascending from 0, or a row index outside [0, m).
+ * csx_pattern_outer_limits: out[5] = PO_LANES (16: 16 lanes x 8 bytes = one 128-byte line of a block row), PO_CHUNK (entries a
+ *   workgroup takes: the kernel is balanced by entries, not columns), PO_WAVE_CHUNK (consecutive entries of the chunk that one
+ *   wave takes), PO_FLIGHT (consecutive entries whose row gathers a lane group issues before it consumes the first), PO_KEPT
+ *   (for nrhs <= PO_KEPT PO_LANES the rows V[j,:], U[j,:] of an entry's own column stay in registers while the entries of a
+ *   step share the column; a wider block reads them per entry -- the same values in the same order); no device needed.
+ * ---- the pull-back of an assembly plan: gradient of the assembled values with respect to the triplet values ----
+ * C.x[s] is the sum of its triplets, so gT[t] = gA[slot of t]:  out[src[u]] = g[s] for u in [sp[s], sp[s+1]): a copy of bits.
+ * csx_assemble_pullback: g a device vector of at least nnz doubles, out one of at least nz doubles; CSX_EINVAL, nothing written,
+ *   for an unknown handle, a short vector, or out overlapping g.  One launch, no host synchronisation.
+ * csx_assemble_pullback_host: the same on the plan's host arrays (csx_assemble_plan_host); CSX_EINVAL for sp not ascending from 0
+ *   to nz or a src outside [0, nz). */
+int csx_pattern_outer(csx_handle_t A, csx_handle_t U, csx_handle_t V, int32_t nrhs, int mode, double alpha, csx_handle_t out);
+int csx_pattern_outer_host(int32_t m, int32_t n, const int32_t *p, const int32_t *i, int32_t nrhs, int mode, double alpha,
+                           const double *U, const double *V, double *out);
+int csx_pattern_outer_limits(int64_t *out);
+int csx_assemble_pullback(csx_handle_t plan, csx_handle_t g, csx_handle_t out);
+int csx_assemble_pullback_host(int32_t nnz, int64_t nz, const int32_t *sp, const int32_t *src, const double *g, double *out);
+
 /* ---- synthetic inputs of the benchmark configs, generated on
  * the device from a counter-based hash so host and device agree bit for bit ---- */
 int csx_gen_grand(int32_t n, int32_t per_col, uint64_t seed, csx_handle_t *out);
