@@ -227,6 +227,14 @@ _PROTOS = {
     "csx_slu_stats": [H, _f64p],
     "csx_slu_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "csx_slu_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_double, _f64p, _f64p, C.POINTER(C.c_int64)],
+    "csx_slu_batch_factor": [H, H, C.c_int32, _f64p, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_slu_batch_refactor": [H, H, _f64p, C.POINTER(C.c_int)],
+    "csx_slu_batch_norm1": [H, H, C.c_int32, _f64p],
+    "csx_slu_batch_solve": [H, H, C.c_int32, C.c_int],
+    "csx_slu_batch_info": [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "csx_slu_batch_stats": [H, _f64p],
+    "csx_slu_batch_member": [H, C.c_int32, _f64p, _f64p],
+    "csx_slu_batch_limits": [_i32p],
     "csx_hqr_symbolic_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
                               _i32p, _i32p, _i32p, _i32p],
     "csx_hqr_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
@@ -352,6 +360,20 @@ def slu_window():
     a, b = C.c_int32(0), C.c_int32(0)
     check(load().csx_slu_window(C.byref(a), C.byref(b)), "csx_slu_window")
     return a.value, b.value
+
+
+SLU_BATCH_LIMITS = ("MAX_MEMBERS", "WALK_WAVES", "SOLVE_THREADS", "SOLVE_FETCH", "RUN_WAVES", "RUN_FETCH")
+
+
+def slu_batch_limits():
+    """the constants by which a batch of static-pivot LU value sets cuts members, right-hand sides and grids (csx_slu_batch.hip,
+    csx_levelwalk.h), asked of the library; no GPU needed: a dict of MAX_MEMBERS (the most members of a batch), WALK_WAVES (the
+    widest level a walker takes), SOLVE_THREADS ((row, column) pairs a solve workgroup of a wide level takes, a thread each),
+    SOLVE_FETCH (terms of a chain such a thread fetches together), RUN_WAVES ((row, right-hand side) pairs a solve walker takes
+    at a time, a wave each), RUN_FETCH (terms of a chain such a wave fetches together)"""
+    out = (C.c_int32 * len(SLU_BATCH_LIMITS))()
+    check(load().csx_slu_batch_limits(out), "csx_slu_batch_limits")
+    return {name: int(out[k]) for k, name in enumerate(SLU_BATCH_LIMITS)}
 
 
 def hqr_window():

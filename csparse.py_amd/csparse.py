@@ -3492,6 +3492,108 @@ _SLU_INFO = ("n", "lnz", "levels", "launches", "level_launches", "run_launches",
              "long_columns", "window", "run_levels", "pos", "neg")
 
 
+_SLU_BATCH_SHARED = ("n", "lnz", "levels", "launches", "level_launches", "run_launches", "kernel_us", "B")
+_SLU_BATCH_MEMBER = ("perturbed", "breakdown", "long_columns", "pos", "neg")
+_SLU_BATCH_STATS = ("min_abs_d", "max_abs_d", "max_abs_l", "max_abs_u")
+
+
+class _SluBatch(object):
+    """B value sets on the pattern of one slusol_factor, factored together (slusol_factor(...).batch(values)): the
+    members share the factor's analysis, matching, order and launch schedule, and go through every launch of it at once.
+    Every member's factor is byte-equal to slusol_factor of that member alone under the same matching and order.
+    B: the members.  ok: a numpy bool array, False where a member broke down -- there is no commit for a batch, so such a
+      member's values mean nothing (until a refactor mends it) and the others are untouched.
+    refactor(values): new values for all B members (B is fixed) -> the new ok.
+    solve(X, trans=False): X an n x (B r) block (dvec, overwritten; or a 2-D numpy array, overwritten), columns m r .. m r + r - 1
+      belong to member m; always in the exact order: every column has the bytes of
+      slusol_factor(A_m, exact=True).solve(...).  The columns of a failed member come back NaN.
+    member(m) -> (Lx, Utx) as numpy arrays; info(): n, lnz, levels, launches, level_launches, run_launches, kernel_us and B of the
+      whole run, and numpy arrays per member: perturbed, breakdown, long_columns, pos, neg, min_abs_d, max_abs_d, max_abs_l,
+      max_abs_u.
+    Deliberately NOT here: refine, gmres, condest, inverse, solve_grad.  The route to them is the single factor:
+    F.refactor(values[:, m])."""
+
+    def __init__(self, solver, hF, nnz, n, perturb, values):
+        self._solver, self._hF, self._nnz, self._n, self._perturb = solver, hF, nnz, n, perturb     # (the solver keeps the factor alive)
+        V, self.B = self._values(values, None)
+        lib = _csx.lib()
+        h, ok = _csx.new_handle(), (_csx.C.c_int * self.B)()
+        _csx.check(lib.csx_slu_batch_factor(hF, V.handle, self.B, _csx.pd(self._tau(V)), h, ok), "csx_slu_batch_factor")
+        self._h = h
+        self._fin = weakref.finalize(self, _csx.free, h)
+        self.ok = np.array(ok[:], dtype=bool)
+
+    def _values(self, values, B):
+        """(dvec of nnz x B, B) of the caller's values; B: the members it must have, or None"""
+        a = None
+        if isinstance(values, dvec):
+            rows, k = values.n, values.k
+        else:
+            a = values if isinstance(values, np.ndarray) else np.asarray([np.asarray(v, dtype=np.float64).ravel() for v in values]).T
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] < 1:
+                raise ValueError("slusol_factor.batch: values must be an nnz x B block or a list of B value arrays, B >= 1")
+            rows, k = a.shape
+        if rows != self._nnz:
+            raise ValueError("slusol_factor.batch: %d rows of values given, the factored matrix has %d entries" % (rows, self._nnz))
+        if B is not None and k != B:
+            raise ValueError("slusol_factor.batch: %d members given, the batch has %d" % (k, B))
+        most = _csx.slu_batch_limits()["MAX_MEMBERS"]
+        if k > most:
+            raise ValueError("slusol_factor.batch: %d members, a batch holds at most %d: split the family" % (k, most))
+        return (values if a is None else dvec(a)), k
+
+    def _tau(self, V):
+        if self._perturb == 0.0:
+            return None
+        out = np.zeros(self.B)
+        _csx.check(_csx.lib().csx_slu_batch_norm1(self._hF, V.handle, self.B, _csx.pd(out)), "csx_slu_batch_norm1")
+        return self._perturb * out
+
+    def refactor(self, values):
+        V, _ = self._values(values, self.B)
+        ok = (_csx.C.c_int * self.B)()
+        _csx.check(_csx.lib().csx_slu_batch_refactor(self._h, V.handle, _csx.pd(self._tau(V)), ok), "csx_slu_batch_refactor")
+        self.ok = np.array(ok[:], dtype=bool)
+        return self.ok
+
+    def solve(self, X, trans=False):
+        if isinstance(X, dvec):
+            d, host = X, None
+        else:
+            host = X
+            d = dvec(np.asarray(X, dtype=np.float64))
+        if d.n != self._n or d.k < self.B or d.k % self.B:
+            raise ValueError("slusol_factor.batch.solve: X must be n x (B r) = %d x (%d r)" % (self._n, self.B))
+        _csx.check(_csx.lib().csx_slu_batch_solve(self._h, d.handle, d.k // self.B, 1 if trans else 0), "csx_slu_batch_solve")
+        if host is not None:
+            if not isinstance(host, np.ndarray):
+                raise ValueError("slusol_factor.batch.solve: X must be a dvec or a numpy array")
+            host[...] = d.numpy().reshape(host.shape)
+        return True
+
+    def member(self, m):
+        m = int(m)
+        if not 0 <= m < self.B:
+            raise ValueError("slusol_factor.batch.member: member %d of %d" % (m, self.B))
+        lnz = self.info()["lnz"]
+        Lx, Ux = np.empty(max(lnz, 1)), np.empty(max(lnz, 1))
+        _csx.check(_csx.lib().csx_slu_batch_member(self._h, m, _csx.pd(Lx), _csx.pd(Ux)), "csx_slu_batch_member")
+        return Lx[:lnz], Ux[:lnz]
+
+    def info(self):
+        lib, C = _csx.lib(), _csx.C
+        shared = (C.c_int64 * len(_SLU_BATCH_SHARED))()
+        per = np.zeros((self.B, len(_SLU_BATCH_MEMBER)), dtype=np.int64)
+        st = np.zeros((self.B, len(_SLU_BATCH_STATS)))
+        _csx.check(lib.csx_slu_batch_info(self._h, shared, per.ctypes.data_as(C.POINTER(C.c_int64))), "csx_slu_batch_info")
+        _csx.check(lib.csx_slu_batch_stats(self._h, _csx.pd(st)), "csx_slu_batch_stats")
+        out = {name: int(v) for name, v in zip(_SLU_BATCH_SHARED, shared)}
+        out.update((name, per[:, k].copy()) for k, name in enumerate(_SLU_BATCH_MEMBER))
+        out.update((name, st[:, k].copy()) for k, name in enumerate(_SLU_BATCH_STATS))
+        return out
+
+
 def _perm_parity(p):
     """+1.0 / -1.0: the sign of the permutation p (a sequence of 0..n-1), from its cycles"""
     p = np.asarray(p, dtype=np.int64)
@@ -3528,6 +3630,8 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
     refactor(A2): new values on the kept analysis (and the kept matching), A2 as for lusol_factor's refactor: True; False with
       L, Ut and the solves exactly as before on breakdown; ValueError for another pattern or length.  L.x and Ut.x are byte-equal
       to a fresh factor's under the same prow and order.
+    batch(values, perturb=None): B value sets on A's pattern factored together in one walk of the levels (_SluBatch, DESIGN.md
+      §32): a parameter sweep on one pattern; this factor is left as it is.
     backward_error(x, b, trans=False), refine(b, maxit=5, trans=False): _Refinable's; condest(): cond_1(A) estimated from
       exact-order solves; logdet(): (sign, log |det A|), the sign with both permutations' parities; info(): n, lnz, levels,
       launches = level_launches + run_launches of the last run, perturbed, breakdown, kernel_us, long_columns (updated in place:
@@ -3587,6 +3691,7 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
     hc, keep_c = _perm_handle(comb, n)
     hp, keep_p = _perm_handle(pinv, n)
     sign_perm = (_perm_parity(prow) if prow is not None else 1.0)    # (P C P' keeps the determinant)
+    perturb_of_factor = perturb
 
     class _Solver(_Refinable):
         factors = N
@@ -3642,6 +3747,16 @@ def slusol_factor(A, order=0, perturb=0.0, match=None, seed=0, exact=None):
                 self._A2, self._norm = A2, None
                 self._operator_changed()
             return ok.value == 1
+
+        def batch(self, values, perturb=None):
+            """B value sets on A's pattern factored together on this factor's analysis -> a _SluBatch (its docstring has the
+            rest).  values: a dvec of nnz x B (read, not kept), a 2-D numpy array of that shape, or a list of B value arrays
+            (copied), each in A's storage order; perturb: defaults to this factor's.  ValueError for another row count or B = 0.
+            This factor is not changed and goes on working; it must not be freed before the batch, which holds on to it."""
+            pb = perturb_of_factor if perturb is None else float(perturb)
+            if not pb >= 0.0:
+                raise ValueError("slusol_factor.batch: perturb must be >= 0")
+            return _SluBatch(self, hF, _meta(A)[0], n, pb, values)
 
         def condest(self):
             if self._norm is None:

@@ -252,6 +252,7 @@ static void free_object(Object &o) {
         case K_LDLFACTOR:
         case K_SCHURFACTOR: destroy((LdlFactor *)o.ptr); break;
         case K_SLUFACTOR: destroy((SluFactor *)o.ptr); break;
+        case K_SLUBATCH: destroy((SluBatch *)o.ptr); break;
         case K_HQRFACTOR: destroy((HqrFactor *)o.ptr); break;
         default: break;
     }

@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR, K_SLUBATCH };
 
 struct Csc;
 
@@ -223,8 +223,10 @@ void destroy(CholAnalysis *p);
 void destroy(CholRefPlan *p);
 struct LdlFactor;     // csx_ldl.h: the one partial-LDL' factor behind K_LDLFACTOR and K_SCHURFACTOR (csx_ldl.hip, csx_schur.hip)
 void destroy(LdlFactor *p);
-struct SluFactor;     // csx_slu.hip
+struct SluFactor;     // csx_slu.h (csx_slu.hip)
 void destroy(SluFactor *p);
+struct SluBatch;      // csx_slu_batch.hip: B value sets on a borrowed SluFactor
+void destroy(SluBatch *p);
 struct HqrFactor;     // csx_hqr.hip
 void destroy(HqrFactor *p);
 // csx_host.cpp: csx_hqr_symbolic_host on vectors that grow (no capacities)

@@ -4,7 +4,9 @@
 //   k_level<Col>     a level of more than WALK_WAVES columns: one launch, one wave per column
 //   k_run<Col>       a run of narrower levels: one workgroup walks it, a barrier per level
 //   walk_levels<Col> the stored schedule, launched
-//   LevelFactor      what the factor objects keep for it, with walk_init / walk_set_levels (build), walk_begin / walk_end (the frame
+//   k_level_batch / k_run_batch / walk_levels_batch   the same for B value sets on one analysis: the member is a grid dimension,
+//                    a batch policy says which arguments are a member's (so far csx_slu_batch.hip alone)
+//   LevelFactor     what the factor objects keep for it, with walk_init / walk_set_levels (build), walk_begin / walk_end (the frame
 //                    of a run) and walk_refactor (new values on the kept pattern)
 // Col is the column policy of a factorisation (LdlColumn, SluColumn, HqrColumn): Args, the types of its column function's kernel
 // arguments with their const and __restrict__, and column(j, wave, lane, args...), which names the per-wave LDS arrays and
@@ -124,6 +126,33 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_run(const int32_t *__restri
     }
 }
 
+// The same two kernels with a member dimension: B value sets on one analysis (one tree, one schedule), independent of each other
+// (csx_slu_batch.hip).  Col is a BATCH policy: its column(j, member, wave, lane, args...) says which of the
+// arguments belong to a member and by what stride they shift -- it offsets those and forwards to a column policy's column(),
+// so the column function and its bits are the single factorisation's.  The templates know nothing else of the policy.
+// k_level_batch: one wave per (column of the level, member), the member in grid y (at most WALK_BATCH_MAX of them).
+template <class Col, class... A>
+__global__ __launch_bounds__(64 * WALK_WAVES) void k_level_batch(const int32_t *__restrict__ cols, int32_t count, A... a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int64_t c = (int64_t)blockIdx.x * WALK_WAVES + w;
+    if (c >= count) return;
+    Col::column(cols[c], (int32_t)blockIdx.y, w, lane, a...);
+}
+
+// k_run_batch: one workgroup per member (grid x) walks the levels [l0, l1) with k_run's barriers
+template <class Col, class... A>
+__global__ __launch_bounds__(64 * WALK_WAVES) void k_run_batch(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
+                                                              int32_t l0, int32_t l1, A... a) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int32_t l = l0; l < l1; l++) {
+        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
+        if (w < cnt) Col::column(cols[b + w], (int32_t)blockIdx.x, w, lane, a...);
+        __syncthreads();
+    }
+}
+
+constexpr int32_t WALK_BATCH_MAX = 65535;   // members of one batch: the y extent of a grid
+
 // ---- the host side of a factor ----------------------------------------------------------------------------------------------
 
 // What a factor object keeps for the walk; LdlFactor, SluFactor and HqrFactor derive from it.
@@ -186,6 +215,28 @@ void walk_levels(LevelFactor *F, ColumnArgs<A...>, typename AsGiven<A>::type... 
             hipLaunchKernelGGL((k_run<Col, A...>), dim3(1), dim3(64 * WALK_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(), L.l0,
                                L.l1, a...);
             F->run_launches++;
+        }
+    }
+}
+
+// F's stored schedule for `members` value sets (1 .. WALK_BATCH_MAX): one launch per LevelLaunch whatever their number, the
+// member in the grid.  F itself is only read: the launches are counted into level_launches / run_launches, the batch's own.
+// Called as walk_levels_batch<Col>(F, members, &wide, &runs, Col::Args(), ...).
+template <class Col, class... A>
+void walk_levels_batch(const LevelFactor *F, int32_t members, int64_t *level_launches, int64_t *run_launches, ColumnArgs<A...>,
+                       typename AsGiven<A>::type... a) {
+    hipStream_t s = ctx().stream;
+    const std::vector<int32_t> &lp = F->level_ptr_h;
+    for (const LevelLaunch &L : F->schedule) {
+        if (L.wide) {
+            const int32_t cnt = lp[(size_t)L.l0 + 1] - lp[(size_t)L.l0];
+            hipLaunchKernelGGL((k_level_batch<Col, A...>), dim3((unsigned)((cnt + WALK_WAVES - 1) / WALK_WAVES), (unsigned)members),
+                               dim3(64 * WALK_WAVES), 0, s, F->level_cols.get() + lp[(size_t)L.l0], cnt, a...);
+            ++*level_launches;
+        } else {
+            hipLaunchKernelGGL((k_run_batch<Col, A...>), dim3((unsigned)members), dim3(64 * WALK_WAVES), 0, s, F->level_cols.get(),
+                               F->level_ptr.get(), L.l0, L.l1, a...);
+            ++*run_launches;
         }
     }
 }

@@ -5,8 +5,8 @@
 // first) are two value arrays on that one pattern; the numeric kernel is ldl_column (csx_ldl.hip) with a second accumulator.
 //   k_slu_sym_rows / k_slu_sym_ptr / k_slu_sym_fill   the pattern whose upper triangle is that of A1 + A1', for the symbolic step
 //   k_slu_entry_map   slot of L and slot of Ut of every entry of A (of duplicates the last)
-//   slu_column    one wave's column, behind the policy SluColumn of the level walk (csx_levelwalk.h: k_level, k_run, the
-//                 schedule with the walker cut at WALK_RUN_LEVELS levels a launch)
+//   slu_column    one wave's column, behind the policy SluColumn of the level walk (csx_slu.h; csx_levelwalk.h: k_level, k_run,
+//                 the schedule with the walker cut at WALK_RUN_LEVELS levels a launch)
 //   k_slu_stats   min / max |d|, max |l|, max |u| off the diagonal, pivot signs in one pass
 // Every sum is updated in ascending k by one wave, one update after the other: L.x and Ut.x are byte-equal to csx_slu_host.
 // A factor or refactor runs into scratch arrays and is committed only when no column broke down.
@@ -15,13 +15,11 @@
 #include <cstring>
 
 #include "csx_internal.h"
-#include "csx_levelwalk.h"
+#include "csx_slu.h"
 
 #pragma clang fp contract(off)
 
 namespace csx {
-
-constexpr int SLU_ACC = 512;   // column entries kept in LDS per wave (8 + 8 + 4 bytes each: 40 KB a workgroup); longer columns are updated in place
 
 // ---- analysis ------------------------------------------------------------------------------------------------------------------
 
@@ -77,166 +75,16 @@ __global__ __launch_bounds__(256) void k_slu_entry_map(int32_t n, const int32_t 
     }
 }
 
-// ---- one column -----------------------------------------------------------------------------------------------------------------
-// Column j of L and of Ut.  On entry Lx[Lp[j] ..] holds C(:, j) and Ux[Lp[j] ..] holds C(j, :) in the slots of the pattern (0.0 in
-// fill and one-sided slots), and every column k < j with (j,k) in the pattern is finished.  acc_l / acc_u / acc_r: wave-private
-// LDS (SLU_ACC entries).  flags[0]: the smallest broken column (atomicMin), flags[1]: perturbed pivots, flags[2]: columns that
-// took the in-place path (integer atomicAdd both).
-__device__ __forceinline__ void slu_column(int32_t j, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li, double *Lx,
-                                           double *Ux, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
-                                           const int32_t *__restrict__ row_pos, double tau, double *acc_l, double *acc_u,
-                                           int32_t *acc_r, int lane, int *flags) {
-    const int32_t base = Lp[j], len = Lp[j + 1] - base;
-    const bool in_lds = len <= SLU_ACC;
-    if (in_lds) {
-        for (int32_t t = lane; t < len; t += 64) {
-            acc_l[t] = Lx[base + t];
-            acc_u[t] = Ux[base + t];
-            acc_r[t] = Li[base + t];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal
-    // Updates are applied in order, but fetched eight at a time (ldl_column): lane u reads the descriptor of update u -- the slot
-    // of row j in column k, the end of column k, l = L(j,k), u = Ut(j,k) -- and the heads of the eight columns are requested
-    // together, both value arrays at once.
-    constexpr int UQ = 8;
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0;
-        double lq = 0.0, uq = 0.0;
-        if (lane < UQ && q0 + lane < qe) {
-            const int32_t kq = row_col[q0 + lane];
-            posq = row_pos[q0 + lane];
-            kendq = Lp[kq + 1];
-            lq = Lx[posq];
-            uq = Ux[posq];
-        }
-        int32_t pos_[UQ], kend_[UQ], r_[UQ];
-        double l_[UQ], u_[UQ], vl_[UQ], vu_[UQ];
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            pos_[u] = __builtin_amdgcn_readlane(posq, u);
-            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
-            l_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(lq), u));
-            u_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(uq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(uq), u));
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            const int32_t p = pos_[u] + lane;
-            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
-            r_[u] = Li[pp];
-            vl_[u] = Lx[pp];
-            vu_[u] = Ux[pp];
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            if (pos_[u] + lane < kend_[u]) {
-                const double a = vl_[u] * u_[u], b = vu_[u] * l_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, r_[u]);   // one search serves both sums
-                    acc_l[t] = acc_l[t] - a;
-                    acc_u[t] = acc_u[t] - b;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, r_[u]);
-                    Lx[t] = Lx[t] - a;
-                    Ux[t] = Ux[t] - b;
-                }
-            }
-            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
-                const double a = Lx[p] * u_[u], b = Ux[p] * l_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, Li[p]);
-                    acc_l[t] = acc_l[t] - a;
-                    acc_u[t] = acc_u[t] - b;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, Li[p]);
-                    Lx[t] = Lx[t] - a;
-                    Ux[t] = Ux[t] - b;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
-        }
-    }
-    double dj = in_lds ? acc_u[0] : Ux[base];
-    const bool small = tau > 0.0 && fabs(dj) < tau;
-    if (small) dj = copysign(tau, dj);
-    if (lane == 0) {
-        if (small) atomicAdd(flags + 1, 1);
-        if (!in_lds) atomicAdd(flags + 2, 1);
-        if (dj == 0.0 || !isfinite(dj)) atomicMin(flags, j);
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int32_t t = lane; t < len; t += 64) {
-        const double vl = in_lds ? acc_l[t] : Lx[base + t];
-        const double vu = in_lds ? acc_u[t] : Ux[base + t];
-        Lx[base + t] = t == 0 ? 1.0 : vl / dj;
-        Ux[base + t] = t == 0 ? dj : vu;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
+// slu_column, its policy SluColumn and the factor object: csx_slu.h (shared with csx_slu_batch.hip)
 
-// the level walk's policy (csx_levelwalk.h): slu_column behind k_level / k_run, with the kernels' argument types and LDS arrays
-struct SluColumn {
-    using Args = ColumnArgs<const int32_t *__restrict__, const int32_t *__restrict__, double *, double *, const int32_t *__restrict__,
-                            const int32_t *__restrict__, const int32_t *__restrict__, double, int *>;
-    static __device__ __forceinline__ void column(int32_t j, int w, int lane, const int32_t *Lp, const int32_t *Li, double *Lx,
-                                                  double *Ux, const int32_t *row_ptr, const int32_t *row_col,
-                                                  const int32_t *row_pos, double tau, int *flags) {
-        __shared__ double acc_l[WALK_WAVES][SLU_ACC];
-        __shared__ double acc_u[WALK_WAVES][SLU_ACC];
-        __shared__ int32_t acc_r[WALK_WAVES][SLU_ACC];
-        slu_column(j, Lp, Li, Lx, Ux, row_ptr, row_col, row_pos, tau, acc_l[w], acc_u[w], acc_r[w], lane, flags);
-    }
-};
-
-// One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|,
-// st[5] max |u| off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (k_ldl_stats' rule)
+// one wave per column (slu_stats_column)
 __global__ __launch_bounds__(256) void k_slu_stats(int32_t n, const int32_t *__restrict__ Lp, const double *__restrict__ Lx,
                                                    const double *__restrict__ Ux, unsigned long long *st) {
     const int lane = threadIdx.x & 63;
     const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (j >= n) return;
-    uint64_t lmax = 0, umax = 0;
-    for (int32_t p = Lp[j] + 1 + lane; p < Lp[j + 1]; p += 64) {
-        const uint64_t a = abs_bits(Lx[p]), b = abs_bits(Ux[p]);
-        lmax = a > lmax ? a : lmax;
-        umax = b > umax ? b : umax;
-    }
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t a = (uint64_t)__shfl_xor((unsigned long long)lmax, off);
-        const uint64_t b = (uint64_t)__shfl_xor((unsigned long long)umax, off);
-        lmax = a > lmax ? a : lmax;
-        umax = b > umax ? b : umax;
-    }
-    if (lane == 0) {
-        const double dj = Ux[Lp[j]];
-        if (dj > 0.0) atomicAdd(st + 0, 1ull);
-        if (dj < 0.0) atomicAdd(st + 1, 1ull);
-        atomicMin(st + 2, (unsigned long long)abs_bits(dj));
-        atomicMax(st + 3, (unsigned long long)abs_bits(dj));
-        if (lmax) atomicMax(st + 4, (unsigned long long)lmax);
-        if (umax) atomicMax(st + 5, (unsigned long long)umax);
-    }
+    slu_stats_column((int32_t)j, lane, Lp, Lx, Ux, st);
 }
-
-struct SluFactor : LevelFactor {
-    int32_t lnz = 0;
-    DevBuf<int32_t> rp, rc, rpos;           // row view of the pattern (chol_symbolic_device)
-    DevBuf<int32_t> winL, winU;             // the two entry maps
-    csx_handle_t hL = 0, hU = 0;            // the committed factor: owned here, lent out by csx_slu_parts; Ut borrows L's p and i
-    DevBuf<double> utx;                     // Ut's values (Ut itself owns nothing)
-    DevBuf<double> Lx, Ux;                  // scratch of a run: committed only when no column broke down
-    // flags: [1] perturbed pivots, [2] columns updated in place; stats: k_slu_stats' six words
-    // csx_slu_info / csx_slu_stats
-    int64_t pos = 0, neg = 0, perturbed = 0;
-    double min_d = 0.0, max_d = 0.0, max_l = 0.0, max_u = 0.0;
-    ~SluFactor() {
-        if (hU) (void)csx_free(hU);
-        if (hL) (void)csx_free(hL);
-    }
-};
 
 void destroy(SluFactor *F) { delete F; }
 
@@ -340,8 +188,15 @@ static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int
         CSX_TRY(dalloc(&L->i, 0));
         F->level_ptr_h.assign(1, 0);
     } else {
-        DevBuf<int32_t> d_prinv, d_pinv, a1i;
-        if (prow) CSX_TRY(upload(d_prinv, prinv));
+        DevBuf<int32_t> d_prinv, a1i;
+        DevBuf<int32_t> &d_pinv = F->perm_p;
+        std::vector<int32_t> comb;   // (alive until the synchronisation below)
+        if (prow) {
+            CSX_TRY(upload(d_prinv, prinv));
+            comb.resize((size_t)n);
+            for (int32_t k = 0; k < n; k++) comb[(size_t)k] = pinv ? pinv[prinv[(size_t)k]] : prinv[(size_t)k];
+            CSX_TRY(upload(F->perm_c, comb));
+        }
         Csc M;
         CSX_TRY(slu_symmetrised(A, prow ? d_prinv.get() : nullptr, a1i, &M));
         CSX_TRY(chol_symbolic_device(&M, parent, cp, pinv, &L->p, &L->i, &F->rp, &F->rc, &F->rpos, nullptr));   // (checks S and pinv)
@@ -365,6 +220,8 @@ static int slu_build(Csc *A, const int32_t *parent, const int32_t *cp, const int
             set_error("csx_slu_factor: an entry of A has no slot in the pattern (S is not A's)");
             return CSX_EINVAL;
         }
+        F->pinv = pinv ? F->perm_p.get() : nullptr;
+        F->comb = prow ? F->perm_c.get() : F->pinv;
     }
     CSX_TRY(dalloc(&L->x, (size_t)F->lnz));
     CSX_TRY(F->utx.alloc((size_t)F->lnz));

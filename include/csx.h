@@ -1164,6 +1164,50 @@ int csx_slu_window(int32_t *entries, int32_t *run_levels);
 int csx_slu_host(int32_t n, const int32_t *Ap, const int32_t *Ai, const double *Ax, const int32_t *prow, const int32_t *pinv,
                  const int32_t *Lp, const int32_t *Li, double tau, double *Lx, double *Utx, int64_t *info);
 
+/* ---- many value sets on the analysis of one csx_slu_factor (csx_slu_batch.hip) ----
+ * A batch BORROWS the analysis of a factor F (pattern, row view, entry maps, height levels, launch schedule, permutations) and
+ * owns B value sets: L.x and Ut.x of every member (B x lnz doubles each), its flags, statistics and threshold.  F must outlive
+ * the batch (every call checks that F's handle still resolves and returns CSX_EINVAL otherwise); F's own L.x, Ut.x and scratch
+ * are never written.  The members are independent: every one's L.x / Ut.x is byte-equal to csx_slu_host of its values alone.
+ * All members go through F's launch schedule together: one launch per entry of it whatever B is (the member is a grid dimension).
+ * There is NO scratch-then-commit: a member whose factorisation breaks down is marked failed (ok[m] = 0) and its values mean
+ * nothing, where csx_slu_refactor keeps the old factor -- keeping B old factors would double B x lnz.  It disturbs no other member.
+ * V: a device vector (csx_vec_*) holding an nnz(A) x B block, row-major: entry q of member m (A's storage order) at V[q * B + m].
+ * B: 1 .. limits[0]; a larger B is CSX_EINVAL with a text (split the family into several batches).
+ * csx_slu_batch_factor: a NEW batch handle (csx_free) with every member factored; tau: B thresholds (each >= 0) or NULL (none);
+ *   ok: B ints.
+ * csx_slu_batch_refactor: the same on the batch's own arrays (B is fixed); a member that failed before is computed afresh.
+ * csx_slu_batch_norm1: out[m] = |A_m|_1 over F's kept pattern by csx_norm1's rule (one sequential sum per column, the maximum
+ *   over the bit patterns of the sums that are not NaN): the very double csx_norm1 returns for member m alone.
+ * csx_slu_batch_solve: X a device vector holding an n x (B r) block, row-major; columns m r .. m r + r - 1 belong to member m and
+ *   are overwritten with A_m^-1 b (trans = 0) or A_m'^-1 b.  The permutations are the single solver's and are applied inside the
+ *   call: x(pinv o prow^-1) = b, the two sweeps, x = x(pinv); swapped for trans.  The sweeps run over F's height levels and
+ *   produce every component by the reference's operation sequence, every product and difference rounded on its own:
+ *     ascending levels  (cs_lsolve of L; of Ut for trans):   x_j = ((x_j - v1 x_k1) - v2 x_k2) - ... over the entries (j, k) of row j,
+ *                        k ascending, then / d_j for Ut (nothing for unit L)
+ *     descending levels (cs_ltsolve of Ut; of L for trans):  the same chain over column j's stored entries below the diagonal in
+ *                        storage order, then / d_j for Ut
+ *   so every column is byte-equal to the single factor's solve in the exact order.  A wide level is one launch for all members and
+ *   right-hand sides, a run of narrow levels one launch of a workgroup per member: two launches per entry of F's schedule.  The
+ *   columns of a failed member are filled with NaN; a NaN or inf in a right-hand side stays in that member's column.
+ * csx_slu_batch_info: shared[8] = n, entries of the pattern, height levels, numeric launches of the last run, of the level
+ *   kernel, of the run walker, microseconds of the last run between two events, B; members[5 B] = per member: perturbed pivots,
+ *   the smallest broken column or -1, columns updated in place, positive pivots, negative pivots.
+ * csx_slu_batch_stats: out[4 B] = per member min |d|, max |d|, max |l|, max |u| off the diagonal.
+ * csx_slu_batch_member: L.x and Ut.x of member m into host arrays of lnz doubles each.
+ * csx_slu_batch_limits: out[6] = the most members of a batch (the y extent of a grid), the columns of a level a walker takes (a
+ *   wider level is a launch of its own), the (row, column) pairs a solve workgroup of a wide level takes (a thread each), the
+ *   terms of a chain such a thread fetches together, the (row, right-hand side) pairs a solve walker takes at a time (a wave
+ *   each), the terms of a chain such a wave fetches together.  No device or factor needed. */
+int csx_slu_batch_factor(csx_handle_t F, csx_handle_t V, int32_t B, const double *tau, csx_handle_t *batch, int *ok);
+int csx_slu_batch_refactor(csx_handle_t batch, csx_handle_t V, const double *tau, int *ok);
+int csx_slu_batch_norm1(csx_handle_t F, csx_handle_t V, int32_t B, double *out);
+int csx_slu_batch_solve(csx_handle_t batch, csx_handle_t X, int32_t r, int trans);
+int csx_slu_batch_info(csx_handle_t batch, int64_t *shared, int64_t *members);
+int csx_slu_batch_stats(csx_handle_t batch, double *out);
+int csx_slu_batch_member(csx_handle_t batch, int32_t m, double *Lx, double *Utx);
+int csx_slu_batch_limits(int32_t *out);
+
 /* ---- sparse Householder QR of a matrix in one connected piece, on the device (csx_hqr.hip) ----
  * A (m-by-n, m >= n, values) with cs_sqr's analysis of A(:, q): q (column order, n entries, or null), parent (column
  * elimination tree), pinv (row permutation, rows of A to 0 .. m2-1), leftmost (m entries), m2 (rows including fictitious ones).
