@@ -40,6 +40,7 @@
 #include <utility>
 
 #include "csx_internal.h"
+#include "csx_colupdate.h"
 #include "csx_sweep.h"
 #include "csx_cholclique.h"
 #include "csx_trimfma.h"
@@ -58,16 +59,6 @@ constexpr int CH_NARROW = 64;       // levels with <= this many columns: one 16-
 
 
 // ---- scatter of C = upper(P A P') into the pattern of L ------------------------------------
-__device__ __forceinline__ int32_t find_row(const int32_t *rows, int32_t len, int32_t r) {
-    int32_t lo = 0, hi = len - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (rows[mid] < r) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // the reference scatters x[Ci[p]] = Cx[p] in storage order: of duplicate entries the last wins
 __global__ __launch_bounds__(256) void k_chol_winner(int32_t n, const int32_t *__restrict__ Ap,
                                                      const int32_t *__restrict__ Ai, const int32_t *__restrict__ pinv,
@@ -122,51 +113,18 @@ __device__ __forceinline__ void chol_column(int32_t j, const int32_t *__restrict
         }
     }
     __builtin_amdgcn_wave_barrier();
-    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal L(j,j)
-    // Updates are applied in order, but fetched eight at a time: lane u reads the descriptor of update u
-    // (position of L(j,k), end of column k, L(j,k)) -- one dependent round trip for eight updates instead of
-    // one each -- and the heads of the eight columns are requested together before any is consumed.
-    constexpr int UQ = 8;
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0;
-        double ljkq = 0.0;
-        if (lane < UQ && q0 + lane < qe) {
-            const int32_t kq = row_col[q0 + lane];
-            posq = row_pos[q0 + lane];
-            kendq = Lp[kq + 1];
-            ljkq = Lx[posq];
-        }
-        int32_t pos_[UQ], kend_[UQ], r_[UQ];
-        double ljk_[UQ], v_[UQ];
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            pos_[u] = __builtin_amdgcn_readlane(posq, u);
-            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
-            ljk_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(ljkq), u),
-                                       __builtin_amdgcn_readlane(__double2loint(ljkq), u));
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            const int32_t p = pos_[u] + lane;
-            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
-            r_[u] = Li[pp];
-            v_[u] = Lx[pp];
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            if (pos_[u] + lane < kend_[u]) {
-                const double v = v_[u] * ljk_[u];
-                if (in_lds) acc_v[find_row(acc_r, len, r_[u])] -= v;
-                else Lx[base + find_row(Li + base, len, r_[u])] -= v;
-            }
-            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
-                const double v = Lx[p] * ljk_[u];
-                if (in_lds) acc_v[find_row(acc_r, len, Li[p])] -= v;
-                else Lx[base + find_row(Li + base, len, Li[p])] -= v;
-            }
-            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
-        }
-    }
+    // the updates (csx_colupdate.h): weight L(j,k), one plane Lx, the sums in the LDS window or in place in Lx
+    column_updates<1>(
+        j, Lp, Li, row_ptr, row_col, row_pos, lane,
+        [&](int32_t, int32_t pos, double (&w)[1]) {
+            w[0] = Lx[pos];
+            return true;
+        },
+        [&](int32_t p, double (&v)[1]) { v[0] = Lx[p]; },
+        [&](int32_t row, const double (&a)[1]) {
+            if (in_lds) acc_v[find_row(acc_r, len, row)] -= a[0];
+            else Lx[base + find_row(Li + base, len, row)] -= a[0];
+        });
     const double d = in_lds ? acc_v[0] : Lx[base];
     if (d <= 0.0 && lane == 0) atomicMin(notspd, j);  // csparse.py:612: not positive definite
     const double ljj = sqrt(d);

@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "csx_internal.h"
+#include "csx_colupdate.h"
 #include "csx_levelwalk.h"
 
 #pragma clang fp contract(off)
@@ -65,9 +66,9 @@ __device__ __forceinline__ void hqr_column(int32_t k, const int32_t *__restrict_
     hqr_wave_sync();
     // the accumulator of natural slot s
     auto at = [&](int32_t s) -> double * { return in_lds ? acc + s : (s < nr ? Rx + rb + s : Vx + vb + (s - nr)); };
-    auto slot_of = [&](int32_t row) -> int32_t { return dst[ldl_find_row(rows, len, row)]; };
-    // Reflections are applied in order, but fetched eight at a time (as ldl_column fetches its updates): lane u reads the
-    // descriptor of reflection t0 + u -- c, the bounds of V(:,c), beta[c], all final -- and the first 64 entries of the eight
+    auto slot_of = [&](int32_t row) -> int32_t { return dst[find_row(rows, len, row)]; };
+    // Reflections are applied in order, but fetched eight at a time (as csx_colupdate.h fetches a column's updates): lane u reads
+    // the descriptor of reflection t0 + u -- c, the bounds of V(:,c), beta[c], all final -- and the first 64 entries of the eight
     // columns are requested together and their slots found before the first of them is applied; what is left per reflection is
     // LDS traffic and the butterfly.  The order of the arithmetic is untouched.
     constexpr int UQ = 8;

@@ -1,6 +1,7 @@
 // The one partial-LDL' factor object with its build, run and refactor (csx_ldl.hip), on which csx_ldl_factor (n1 = n: nothing
 // kept) and csx_schur_factor (csx_schur.hip) both stand.  The level walk under it is csx_levelwalk.h's.
 #pragma once
+#include "csx_colupdate.h"
 #include "csx_levelwalk.h"
 
 namespace csx {

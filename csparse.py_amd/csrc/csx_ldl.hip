@@ -40,60 +40,23 @@ __device__ __forceinline__ void ldl_column(int32_t j, const int32_t *__restrict_
         }
     }
     __builtin_amdgcn_wave_barrier();
-    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal L(j,j)
-    // Updates are applied in order, but fetched eight at a time (chol_column): lane u reads the descriptor of update u --
-    // position of L(j,k), end of column k, w = L(j,k) d[k] -- and the heads of the eight columns are requested together.
-    constexpr int UQ = 8;
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0;
-        double wq = 0.0;
-        if (lane < UQ && q0 + lane < qe) {
-            const int32_t kq = row_col[q0 + lane];
-            posq = row_pos[q0 + lane];
-            kendq = Lp[kq + 1];
-            wq = Lx[posq] * d[kq];
-        }
-        int32_t pos_[UQ], kend_[UQ], r_[UQ];
-        double w_[UQ], v_[UQ];
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            pos_[u] = __builtin_amdgcn_readlane(posq, u);
-            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
-            w_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(wq), u));
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            const int32_t p = pos_[u] + lane;
-            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
-            r_[u] = Li[pp];
-            v_[u] = Lx[pp];
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            if (pos_[u] + lane < kend_[u]) {
-                const double v = v_[u] * w_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, r_[u]);
-                    acc_v[t] = acc_v[t] - v;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, r_[u]);
-                    Lx[t] = Lx[t] - v;
-                }
+    // the updates (csx_colupdate.h): weight L(j,k) d[k], one plane Lx, the sums in the LDS window or in place in Lx
+    column_updates<1>(
+        j, Lp, Li, row_ptr, row_col, row_pos, lane,
+        [&](int32_t k, int32_t pos, double (&w)[1]) {
+            w[0] = Lx[pos] * d[k];
+            return true;
+        },
+        [&](int32_t p, double (&v)[1]) { v[0] = Lx[p]; },
+        [&](int32_t row, const double (&a)[1]) {
+            if (in_lds) {
+                const int32_t t = find_row(acc_r, len, row);
+                acc_v[t] = acc_v[t] - a[0];
+            } else {
+                const int32_t t = base + find_row(Li + base, len, row);
+                Lx[t] = Lx[t] - a[0];
             }
-            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
-                const double v = Lx[p] * w_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, Li[p]);
-                    acc_v[t] = acc_v[t] - v;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, Li[p]);
-                    Lx[t] = Lx[t] - v;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
-        }
-    }
+        });
     double dj = in_lds ? acc_v[0] : Lx[base];
     const bool small = tau > 0.0 && fabs(dj) < tau;
     if (small) dj = copysign(tau, dj);

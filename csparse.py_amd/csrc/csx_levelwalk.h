@@ -83,16 +83,6 @@ inline void height_levels(int32_t n, const int32_t *parent, std::vector<int32_t>
 
 // ---- the device side --------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int32_t ldl_find_row(const int32_t *rows, int32_t len, int32_t r) {
-    int32_t lo = 0, hi = len - 1;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (rows[mid] < r) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // the stats kernels' order of magnitudes: the bit pattern of fabs as an unsigned integer (csx_residual.hip's rule: a NaN ranks above inf)
 __device__ __forceinline__ uint64_t abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
 

@@ -41,54 +41,18 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_schur_cols(const int32_t *_
         if (r >= r0 && r < r1) acc[r - r0] = Lx[p];
     }
     __builtin_amdgcn_wave_barrier();
-    const int32_t qe = row_ptr[j + 1] - 1;
-    // Updates are applied in order, but fetched eight at a time (ldl_column): lane u reads the descriptor of update u --
-    // position of L(j,k), end of column k, w = L(j,k) d[k] -- and the heads of the eight columns are requested together.
-    constexpr int UQ = 8;
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0, kq = WALK_NONE;
-        double wq = 0.0;
-        if (lane < UQ && q0 + lane < qe) {
-            kq = row_col[q0 + lane];
-            if (kq < n1) {
-                posq = row_pos[q0 + lane];
-                kendq = Lp[kq + 1];
-                wq = Lx[posq] * d[kq];
-            }
-        }
-        if (__builtin_amdgcn_readlane(kq, 0) >= n1) break;       // k ascending: nothing but trailing columns from here on
-        int32_t pos_[UQ], kend_[UQ], r_[UQ];
-        double w_[UQ], v_[UQ];
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            pos_[u] = __builtin_amdgcn_readlane(posq, u);
-            kend_[u] = __builtin_amdgcn_readlane(kendq, u);      // 0 for an absent update or a trailing column: nothing below
-            w_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(wq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(wq), u));
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            const int32_t p = pos_[u] + lane;
-            const int32_t pp = p < kend_[u] ? p : pos_[u];        // a valid address either way
-            r_[u] = Li[pp];
-            v_[u] = Lx[pp];
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            if (pos_[u] + lane < kend_[u] && r_[u] >= r0 && r_[u] < r1) {
-                const double v = v_[u] * w_[u];
-                acc[r_[u] - r0] = acc[r_[u] - r0] - v;
-            }
-            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
-                const int32_t r = Li[p];
-                if (r >= r0 && r < r1) {
-                    const double v = Lx[p] * w_[u];
-                    acc[r - r0] = acc[r - r0] - v;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
-        }
-    }
+    // the updates (csx_colupdate.h): weight L(j,k) d[k], kept columns k >= n1 refused, sums in the LDS chunk at row - r0 or skipped
+    column_updates<1>(
+        j, Lp, Li, row_ptr, row_col, row_pos, lane,
+        [&](int32_t k, int32_t pos, double (&w)[1]) {
+            if (k >= n1) return false;   // k ascending: nothing but trailing columns from here on
+            w[0] = Lx[pos] * d[k];
+            return true;
+        },
+        [&](int32_t p, double (&v)[1]) { v[0] = Lx[p]; },
+        [&](int32_t row, const double (&a)[1]) {
+            if (row >= r0 && row < r1) acc[row - r0] = acc[row - r0] - a[0];
+        });
     __builtin_amdgcn_wave_barrier();
     const int64_t ns = n - n1, cj = j - n1;
     for (int32_t t = lane; t < rows; t += 64) {

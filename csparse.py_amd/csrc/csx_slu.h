@@ -1,6 +1,7 @@
 // What csx_slu.hip (one factorisation) and csx_slu_batch.hip (many value sets on one analysis) share of the static-pivot L U
 // (DESIGN.md §23, §32): the column function with its level-walk policy, one column of the statistics, and the factor object.
 #pragma once
+#include "csx_colupdate.h"
 #include "csx_levelwalk.h"
 
 #pragma clang fp contract(off)
@@ -28,69 +29,36 @@ __device__ __forceinline__ void slu_column(int32_t j, const int32_t *__restrict_
         }
     }
     __builtin_amdgcn_wave_barrier();
-    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal
-    // Updates are applied in order, but fetched eight at a time (ldl_column): lane u reads the descriptor of update u -- the slot
-    // of row j in column k, the end of column k, l = L(j,k), u = Ut(j,k) -- and the heads of the eight columns are requested
-    // together, both value arrays at once.
-    constexpr int UQ = 8;
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += UQ) {
-        int32_t posq = 0, kendq = 0;
-        double lq = 0.0, uq = 0.0;
-        if (lane < UQ && q0 + lane < qe) {
-            const int32_t kq = row_col[q0 + lane];
-            posq = row_pos[q0 + lane];
-            kendq = Lp[kq + 1];
-            lq = Lx[posq];
-            uq = Ux[posq];
-        }
-        int32_t pos_[UQ], kend_[UQ], r_[UQ];
-        double l_[UQ], u_[UQ], vl_[UQ], vu_[UQ];
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            pos_[u] = __builtin_amdgcn_readlane(posq, u);
-            kend_[u] = __builtin_amdgcn_readlane(kendq, u);    // 0 for an absent update: nothing below
-            l_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(lq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(lq), u));
-            u_[u] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(uq), u),
-                                     __builtin_amdgcn_readlane(__double2loint(uq), u));
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            const int32_t p = pos_[u] + lane;
-            const int32_t pp = p < kend_[u] ? p : pos_[u];      // a valid address either way
-            r_[u] = Li[pp];
-            vl_[u] = Lx[pp];
-            vu_[u] = Ux[pp];
-        }
-#pragma unroll
-        for (int u = 0; u < UQ; u++) {
-            if (pos_[u] + lane < kend_[u]) {
-                const double a = vl_[u] * u_[u], b = vu_[u] * l_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, r_[u]);   // one search serves both sums
-                    acc_l[t] = acc_l[t] - a;
-                    acc_u[t] = acc_u[t] - b;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, r_[u]);
-                    Lx[t] = Lx[t] - a;
-                    Ux[t] = Ux[t] - b;
-                }
+    // The window by its address space.  With two plain double * the captured acc_u and Ux are two loads of one shape from the
+    // closure, the compiler merges the tails of the two branches of `sub` below into one subtraction through a pointer chosen
+    // between LDS and global memory, and the second plane's sums go through flat loads and stores.  Pointers
+    // of different address spaces cannot be merged.  This rests on how the compiler orders its passes: after a compiler
+    // upgrade, compare the LU kernels' ds_* / flat_* counts with profiles/column_updates_isa.txt again.
+    typedef __attribute__((address_space(3))) double lds_double;
+    lds_double *const lds_l = (lds_double *)acc_l, *const lds_u = (lds_double *)acc_u;
+    // the updates (csx_colupdate.h): weights Ut(j,k) for plane Lx and L(j,k) for plane Ux, sums in the window or in place, one search
+    column_updates<2>(
+        j, Lp, Li, row_ptr, row_col, row_pos, lane,
+        [&](int32_t, int32_t pos, double (&w)[2]) {
+            w[0] = Ux[pos];
+            w[1] = Lx[pos];
+            return true;
+        },
+        [&](int32_t p, double (&v)[2]) {
+            v[0] = Lx[p];
+            v[1] = Ux[p];
+        },
+        [&](int32_t row, const double (&a)[2]) {
+            if (in_lds) {
+                const int32_t t = find_row(acc_r, len, row);
+                lds_l[t] = lds_l[t] - a[0];
+                lds_u[t] = lds_u[t] - a[1];
+            } else {
+                const int32_t t = base + find_row(Li + base, len, row);
+                Lx[t] = Lx[t] - a[0];
+                Ux[t] = Ux[t] - a[1];
             }
-            for (int32_t p = pos_[u] + 64 + lane; p < kend_[u]; p += 64) {   // columns longer than one wave
-                const double a = Lx[p] * u_[u], b = Ux[p] * l_[u];
-                if (in_lds) {
-                    const int32_t t = ldl_find_row(acc_r, len, Li[p]);
-                    acc_l[t] = acc_l[t] - a;
-                    acc_u[t] = acc_u[t] - b;
-                } else {
-                    const int32_t t = base + ldl_find_row(Li + base, len, Li[p]);
-                    Lx[t] = Lx[t] - a;
-                    Ux[t] = Ux[t] - b;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();   // one update after the other: they may hit the same rows
-        }
-    }
+        });
     double dj = in_lds ? acc_u[0] : Ux[base];
     const bool small = tau > 0.0 && fabs(dj) < tau;
     if (small) dj = copysign(tau, dj);

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void k_slu_entry_map(int32_t n, const int32_t 
         const int32_t i2 = pinv ? pinv[i1] : i1;
         const int32_t c = min(i2, j2), r = max(i2, j2);
         const int32_t b = Lp[c], len = Lp[c + 1] - b;
-        const int32_t t = ldl_find_row(Li + b, len, r);
+        const int32_t t = find_row(Li + b, len, r);
         if (Li[b + t] != r) {
             *bad = 1;   // the symbolic pattern does not contain this entry
             continue;

@@ -138,6 +138,35 @@ def _arrow(n):
     return upper_csc(n, e)
 
 
+STAR_LEAVES = (0, 1, 7, 8, 9, 16, 17)    # updates of a hub's row: none, one, either side of one fetch of eight, and of two
+STAR_SEED = 20250917
+
+
+def _stars(leaves=STAR_LEAVES, seed=STAR_SEED):
+    """a forest of stars, every hub numbered after its leaves: the row of a hub with c leaves takes exactly c updates (a leaf's
+    column holds its diagonal and the hub's row, there is no fill), a leaf's none.  The diagonal (1 + j / 8) (-1)^j is distinct
+    and of both signs, the off-diagonals are uniform in [-1, 1]: 65 columns"""
+    rng = np.random.default_rng(seed)
+    e, j = {}, 0
+    for c in leaves:
+        hub = j + c
+        for k in range(j, hub + 1):
+            e[(k, k)] = (1.0 + k / 8.0) * (-1.0 if k % 2 else 1.0)
+            if k < hub:
+                e[(k, hub)] = float(rng.uniform(-1.0, 1.0))
+        j = hub + 1
+    return upper_csc(j, e)
+
+
+def star_hubs(leaves=STAR_LEAVES):
+    """{hub column: its leaves} of _stars"""
+    out, j = {}, 0
+    for c in leaves:
+        out[j + c] = c
+        j += c + 1
+    return out
+
+
 def _signed_blocks(nblocks, bs):
     n, p, i, x = arrow_blocks(nblocks, bs)
     x = np.asarray(x, np.float64)
@@ -165,6 +194,7 @@ def _build():
     add(Case("sparse-trees", *_signed_blocks(40, 24), seed=13))
     add(Case("chains4", *_chains(4), seed=14))       # three levels of 4 columns: the widest the walker takes
     add(Case("chains5", *_chains(5), seed=15))       # ... of 5: a wave per column
+    add(Case("update-batches", *_stars(), seed=16))  # rows of 0, 1, 7, 8, 9, 16, 17 updates: the edges of the fetch of eight
     return cases
 
 

@@ -63,6 +63,31 @@ def _border(ns, seed):
     return LC.upper_csc(3 + ns, e)
 
 
+BATCH_ROWS = ((), (9, False), (7, True), (8, True))     # per kept node: (its interior neighbours, coupled to the first kept node)
+
+
+def _border_batches(seed=20250919):
+    """Kept node t has BATCH_ROWS[t][0] interior leaves of its own (a diagonal and the one coupling each: no fill among them)
+    and, where the flag says so, an entry with kept node 0.  With the interior ascending and the kept nodes last, the row view
+    of a trailing column lists its interior columns and then the kept one, so the update loop's fetches of eight see: no
+    descriptor at all; 9 interior ones (a full fetch and one more); 7 interior and the kept one refused INSIDE the fetch; 8
+    interior and the kept one refused as the FIRST descriptor of the next fetch, which ends the loop"""
+    rng = np.random.default_rng(seed)
+    n1 = sum(r[0] for r in BATCH_ROWS if r)
+    e, k = {}, 0
+    for t, row in enumerate(BATCH_ROWS):
+        kept = n1 + t
+        e[(kept, kept)] = float(rng.uniform(1.0, 2.0)) * (-1.0 if t % 2 else 1.0)
+        if row:
+            for _ in range(row[0]):
+                e[(k, k)] = float(rng.uniform(1.0, 2.0)) * (-1.0 if k % 3 == 0 else 1.0)
+                e[(k, kept)] = float(rng.uniform(-1.0, 1.0))
+                k += 1
+            if row[1]:
+                e[(n1, kept)] = float(rng.uniform(-1.0, 1.0))
+    return LC.upper_csc(n1 + len(BATCH_ROWS), e), list(range(n1, n1 + len(BATCH_ROWS)))
+
+
 def _two():
     return LC.upper_csc(2, {(0, 0): 2.0, (0, 1): 1.0, (1, 1): -3.0})
 
@@ -89,6 +114,8 @@ def _build():
     add(SchurCase("chain600", C("chain600", *LC._chain(600), seed=38), [598, 599]))         # 598 narrow levels: the walker is cut at 256
     for tag, ns in (("border-window", WINDOW), ("border-window+1", WINDOW + 1), ("border-2window+1", 2 * WINDOW + 1)):
         add(SchurCase(tag, C(tag, *_border(ns, 40 + ns % 7), seed=39), range(3, 3 + ns)))
+    batches, kept = _border_batches()
+    add(SchurCase("border-batches", C("border-batches", *batches, seed=42), kept))            # refusals at the edges of the fetch of eight
     trees = C("sparse-trees", *LC._signed_blocks(40, 24), seed=41)
     add(SchurCase("sparse-trees", trees, [b * 24 + 23 for b in range(40)], 1))                # the root of every tree: a block-diagonal (here diagonal) S
     return out

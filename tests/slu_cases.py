@@ -14,6 +14,7 @@ import os
 import numpy as np
 
 import _csx
+import ldl_cases as LC
 
 SIGMA = 3.7
 CONVECTION = 0.3
@@ -180,6 +181,20 @@ def _arrow(n):
     return csc(n, e)
 
 
+def _stars(seed=20250918):
+    """ldl_cases._stars' forest (hub rows of 0, 1, 7, 8, 9, 16 and 17 updates, the same diagonal) with unsymmetric off-diagonals:
+    A(leaf, hub) and A(hub, leaf) are independent, uniform in [-1, 1]"""
+    rng = np.random.default_rng(seed)
+    n, p, i, x = LC._stars()
+    e = {}
+    for j in range(n):
+        for t in range(p[j], p[j + 1]):
+            e[(i[t], j)] = x[t]
+            if i[t] != j:
+                e[(i[t], j)], e[(j, i[t])] = float(rng.uniform(-1.0, 1.0)), float(rng.uniform(-1.0, 1.0))
+    return csc(n, e)
+
+
 def _golden(name, key="A"):
     """the matrix `key` of a fixture: "A" as loaded, "C" with the duplicates of the triplet file summed"""
     g = np.load(os.path.join(GOLDEN, name + ".npz"))
@@ -210,6 +225,7 @@ def _build():
     add(Case("long-column-updated", *_arrow(WINDOW + 2), seed=17))     # its column 1 is long AND takes an update, in place
     add(Case("chains4", *_chains(4), seed=19))       # three levels of 4 columns: the widest the walker takes
     add(Case("chains5", *_chains(5), seed=20))       # ... of 5: a wave per column
+    add(Case("update-batches", *_stars(), seed=21))  # rows of 0, 1, 7, 8, 9, 16, 17 updates: the edges of the fetch of eight
     return cases
 
 

@@ -66,6 +66,23 @@ def test_descending_updates_or_a_fused_subtraction_give_other_bytes(name):
         assert np.allclose(Lx, rx, rtol=1e-6, atol=1e-9), mistake     # (a mistake of rounding, not of arithmetic)
 
 
+def test_update_batches_has_the_rows_it_names_and_no_vanishing_pivot():
+    """the forest of stars: L has no fill, the hub rows hold exactly 0, 1, 7, 8, 9, 16 and 17 entries before the diagonal (the
+    updates their columns take), every other row none; no pivot of any value set is zero, perturbed or a breakdown"""
+    case = LC.BY_NAME["update-batches"]
+    Lp, Li, _ = LO.pattern_of(case)
+    assert case.n == 65 and Lp[-1] == case.n + sum(LC.STAR_LEAVES)
+    updates = np.bincount(np.asarray(Li), minlength=case.n) - 1
+    hubs = LC.star_hubs()
+    assert sorted(hubs.values()) == [0, 1, 7, 8, 9, 16, 17]
+    assert all(updates[j] == hubs.get(j, 0) for j in range(case.n))
+    diag = case.x[case.i == case.cols]
+    assert len(set(diag.tolist())) == case.n and np.any(diag > 0) and np.any(diag < 0)
+    for which in LC.VALUE_SETS:
+        _, d, info = LO.reference(case, which)
+        assert info[2:] == (0, -1) and np.all(np.isfinite(d)) and np.all(d != 0.0), which
+
+
 def _bound_holds(n, Lp, Li, Lx, d, C):
     """|C - L D L'| <= (n + 1) 2^-52 |L| |D| |L'| entry by entry on the lower triangle, in exact rationals.  C: {(r, c): value},
     r >= c, in L's numbering.  Entries outside the pattern of L are structurally zero on both sides."""

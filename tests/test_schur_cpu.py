@@ -63,6 +63,22 @@ def test_unstopped_or_descending_updates_give_other_bytes(name):
     assert np.allclose(S, rS, rtol=1e-6, atol=1e-9)                    # (a mistake of rounding, not of arithmetic)
 
 
+def test_border_batches_has_the_rows_it_names():
+    """the row views of the four trailing columns, in ascending k: nothing; 9 interior columns; 7 interior columns and then a
+    kept one; 8 interior columns and then kept ones -- what the update loop's fetches of eight are to meet (tests/schur_cases.py)"""
+    sc = SC.BY_NAME["border-batches"]
+    Lp, Li, _ = SO.pattern_of(sc)
+    n1 = sc.n1
+    assert SO.perm_of(sc) == list(range(sc.n)) and sc.ns == 4
+    rows = [[k for k in range(j) if j in Li[Lp[k]:Lp[k + 1]]] for j in range(n1, sc.n)]
+    interior = [[k for k in r if k < n1] for r in rows]
+    assert [len(r) for r in interior] == [0, 9, 7, 8]
+    assert [r[len(i):] for r, i in zip(rows, interior)] == [[], [], [n1], [n1, n1 + 2]]
+    _, d, S, info = SO.reference(sc, "A")
+    assert info[2:] == (0, -1) and np.all(d != 0.0)
+    assert S[1, 0] == 0.0 and S[2, 0] != 0.0 and S[3, 0] != 0.0 and S[3, 2] == 0.0          # what the kept couplings leave in S
+
+
 @pytest.mark.parametrize("name", ["one-keep-none", "grid-line-1"])
 def test_nothing_kept_is_the_ldl_rule(name):
     """ns = 0 on the case's own full pattern and order: Lp.x and d are csx_ldl_host's"""

@@ -71,6 +71,24 @@ def test_descending_updates_or_a_fused_subtraction_give_other_bytes(name):
         assert np.allclose(Lx, rx, rtol=1e-6, atol=1e-9) and np.allclose(Ux, ru, rtol=1e-6, atol=1e-9), mistake
 
 
+def test_update_batches_has_the_rows_it_names_and_no_vanishing_pivot():
+    """the forest of stars of tests/ldl_cases.py with unsymmetric values: no fill, the hub rows hold exactly 0, 1, 7, 8, 9, 16 and
+    17 entries before the diagonal (the updates their columns take); no pivot of any value set is zero, perturbed or a breakdown"""
+    import ldl_cases as LC
+    case = SC.BY_NAME["update-batches"]
+    Lp, Li, _ = SO.pattern_of(case)
+    assert case.n == 65 and case.prow is None and SO.pinv_of(case) is None and Lp[-1] == case.n + sum(LC.STAR_LEAVES)
+    updates = np.bincount(np.asarray(Li), minlength=case.n) - 1
+    hubs = LC.star_hubs()
+    assert all(updates[j] == hubs.get(j, 0) for j in range(case.n))
+    D = case.dense()
+    assert not np.array_equal(D, D.T) and len(set(np.diag(D).tolist())) == case.n
+    for which in SC.VALUE_SETS:
+        _, Ux, info = SO.reference(case, which)
+        d = Ux[np.asarray(Lp[:-1])]
+        assert info[2:] == (0, -1) and np.all(np.isfinite(d)) and np.all(d != 0.0), which
+
+
 def test_duplicates_and_one_sided_entries():
     """of duplicate entries the last counts: the factor of `dups` is that of the matrix without them; a one-sided entry leaves an
     exact 0.0 in the other triangle's starting values, not a missing slot"""
