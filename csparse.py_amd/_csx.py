@@ -178,6 +178,7 @@ _PROTOS = {
     "csx_chol_refactor_info": [C.POINTER(C.c_double), C.POINTER(C.c_double)],
     "csx_chol_refactor_window": [H, C.POINTER(C.c_int32)],
     "csx_chol_limits": [_i32p],
+    "csx_cholsol_forest_plan": [C.c_int, C.c_int32, C.c_int32, C.c_int, C.c_int, C.POINTER(C.c_int32)],
     "csx_lu_refactor_host": [C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p, _i32p, _i32p, _f64p,
                              C.POINTER(C.c_int), _f64p],
     "csx_assemble_plan_host": [C.c_int32, C.c_int32, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p],
@@ -352,6 +353,18 @@ def chol_limits():
     d["windows"] = tuple(int(out[k]) for k in range(10, 15))
     d["max_need"] = int(out[15])
     return d
+
+
+FOREST_PLAN_KINDS = ("General", "EmitEqual", "Programs", "BlockListExact", "EmitRagged", "BlockListLite")
+
+
+def cholsol_forest_plan(sparse, min_bs, max_bs, exact, dense_blocks):
+    """the kind of solve plan csx_cholsol_factor makes for a forest of blocks (a name of FOREST_PLAN_KINDS, include/csx.h:
+    csx_cholsol_forest_plan), asked of the library; no GPU needed"""
+    kind = C.c_int32(-1)
+    check(load().csx_cholsol_forest_plan(int(sparse), min_bs, max_bs, int(exact), int(dense_blocks), C.byref(kind)),
+          "csx_cholsol_forest_plan")
+    return FOREST_PLAN_KINDS[kind.value]
 
 
 def slu_window():

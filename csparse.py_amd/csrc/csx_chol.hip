@@ -1002,77 +1002,58 @@ static int chol_device(const Csc *A, const int32_t *parent, const int32_t *cp, c
         fprintf(stderr, "[cs_chol] %-18s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(t1 - t0).count());
         t0 = t1;
     };
-    if (ctx().opt.chol_clique && ctx().opt.chol_dense_trees && !pinv && A->nnz > 0) {
+    ForestRoute R;
+    CSX_TRY(clique_forest_route(A, pinv != nullptr, true, &R));
+    if (R.F) {
         // A forest of cliques on consecutive columns (csx_cholclique.hip): L.p / L.i follow from the counts, the values are
         // one read of A's upper part and one write of L, a block to a wave.  The caller's S must be that forest's.
-        std::unique_ptr<CliqueForest> own;   // not cached: this call's finding
-        bool ok = false, same = false;
-        const bool cached = A->clique != nullptr && (!A->clique->sparse || ctx().opt.chol_forest);
-        if (cached) {
-            // csx_schol's finding for this matrix (dropped by csx_csc_invalidate when the arrays change): read where it lies; L.p
-            // is copied out of it below instead of taken
-            ok = true;
-        } else {
-            own.reset(new CliqueForest());
-            CSX_TRY(clique_forest(A, own.get(), &ok));
+        CliqueForest &F = *R.F;
+        const bool cached = !R.own;   // csx_schol's finding for this matrix: L.p is copied out of it instead of taken
+        lap("clique forest");
+        // The block kernel is started FIRST; the caller's S (host arrays) is uploaded and compared with the forest's beside it
+        // on a stream of its own.  An S that is not A's costs a factor that is thrown away.
+        // (the kernel writes L through the forest's own column pointers: an S with another lnz is refused before anything runs)
+        if ((int64_t)L->nnz != F.lnz) return CSX_EINVAL;
+        DevBuf<int> d_notspd;
+        int hflag = NOTSPD_NONE;
+        bool queued = false, same = false, notspd = false;   // queued: device work of this call may be in flight
+        CliqueCompare cmp;
+        auto factor = [&]() -> int {
+            CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
+            CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
+            CSX_TRY(d_notspd.alloc(1));
+            if (cached) {
+                CSX_TRY(dalloc(&L->p, (size_t)n + 1));
+                CSX_HIP(hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+            } else {
+                L->p = F.cp;                        // not cached: L takes the forest's column pointers (the comparison reads
+            }                                       // them until clique_matches_end; F lets go of them below)
+            queued = true;
+            lap("allocations");
+            int st = clique_run_launch(A, F, L, d_notspd, 1, nullptr, ev_a, ev_b);
+            lap("block kernel");
+            if (st == CSX_OK) st = clique_matches_run(&cmp);
+            lap("S uploaded");
+            return clique_run_collect(st, d_notspd, 1, &hflag, "cs_chol", &notspd);
+        };
+        int st = clique_matches_begin(F, parent, cp, &cmp);
+        if (st == CSX_OK) st = factor();
+        {
+            const int st2 = clique_matches_end(&cmp, &same);    // (always: it waits for the side stream and frees)
+            if (st == CSX_OK) st = st2;
         }
-        CliqueForest &F = cached ? *A->clique : *own;
-        if (ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
-            lap("clique forest");
-            // The block kernel is started FIRST; the caller's S (host arrays) is uploaded and compared with the forest's beside it
-            // on a stream of its own.  An S that is not A's costs a factor that is thrown away.
-            // (the kernel writes L through the forest's own column pointers: an S with another lnz is refused before anything runs)
-            if ((int64_t)L->nnz != F.lnz) return CSX_EINVAL;
-            DevBuf<int> d_notspd;
-            constexpr int NOTSPD_NONE = 0x7f7f7f7f;     // the flag's idle value: set by a byte fill on the device, no host slot in flight
-            int hflag = NOTSPD_NONE;
-            bool queued = false;                        // device work of this call may be in flight
-            CliqueCompare cmp;
-            auto factor = [&]() -> int {
-                CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
-                CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
-                CSX_TRY(d_notspd.alloc(1));
-                if (cached) {
-                    CSX_TRY(dalloc(&L->p, (size_t)n + 1));
-                    CSX_HIP(hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-                } else {
-                    L->p = F.cp;                        // not cached: L takes the forest's column pointers (the comparison reads
-                }                                       // them until clique_matches_end; F lets go of them below)
-                queued = true;
-                CSX_HIP(hipMemsetAsync(d_notspd, 0x7f, sizeof(int), s));
-                lap("allocations");
-                (void)hipEventRecord(ev_a, s);
-                CSX_TRY(chol_clique_numeric(A, F, L, d_notspd, nullptr, !ctx().opt.chol_exact));
-                (void)hipEventRecord(ev_b, s);
-                lap("block kernel");
-                CSX_TRY(clique_matches_run(&cmp));
-                lap("S uploaded");
-                if (hipMemcpyAsync(&hflag, d_notspd, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess) {
-                    set_error("cs_chol: %s", hipGetErrorString(hipGetLastError()));
-                    return CSX_ERUNTIME;
-                }
-                return CSX_OK;
-            };
-            int st = clique_matches_begin(F, parent, cp, &cmp);
-            if (st == CSX_OK) st = factor();
-            {
-                const int st2 = clique_matches_end(&cmp, &same);    // (always: it waits for the side stream and frees)
-                if (st == CSX_OK) st = st2;
-            }
-            if (!cached && L->p == F.cp) (void)F.cp.release();      // L owns them now (the caller frees L on any error)
-            // on a failure after work was queued the block kernel may still be writing L.i / L.x, which the caller hands back to
-            // the pool: nothing is released before the stream has drained
-            if (st != CSX_OK && queued) (void)hipStreamSynchronize(s);
-            lap("numeric (blocks) + S compared");
-            if (st != CSX_OK) return st;
-            if (!same) return CSX_EINVAL;               // S.cp / S.parent do not belong to A
-            numeric_ms();
-            g_chol_path = F.sparse ? 2 : 1;
-            return hflag != NOTSPD_NONE ? CSX_ENOTSPD : CSX_OK;
-        }
-        lap("no clique forest");
+        if (!cached && L->p == F.cp) (void)F.cp.release();      // L owns them now (the caller frees L on any error)
+        // on a failure after work was queued the block kernel may still be writing L.i / L.x, which the caller hands back to
+        // the pool: nothing is released before the stream has drained
+        if (st != CSX_OK && queued) (void)hipStreamSynchronize(s);
+        lap("numeric (blocks) + S compared");
+        if (st != CSX_OK) return st;
+        if (!same) return CSX_EINVAL;               // S.cp / S.parent do not belong to A
+        numeric_ms();
+        g_chol_path = clique_chol_path(F);
+        return notspd ? CSX_ENOTSPD : CSX_OK;
     }
+    lap("no clique forest");
     CholAnalysis An;
     CSX_TRY(chol_symbolic_device(A, parent, cp, pinv, &L->p, &L->i, &An.rp, &An.rc, &An.rpos, nullptr));
     lap("pattern (device)");
@@ -1183,10 +1164,8 @@ struct CholPlan {
 
 void destroy(CholPlan *P) { delete P; }
 
-// the block sizes of the dense-block solve kernels (the W-tile emission of the block kernel takes 16, 32 and 64 only), and a
-// forest of cliques all of one such size
+// the block sizes of the dense-block solve kernels (the W-tile emission of the block kernel takes 16, 32 and 64 only)
 static bool dense_block_size(int32_t bs) { return bs == 8 || bs == 16 || bs == 32 || bs == 64; }
-static bool equal_dense_blocks(const CliqueForest &F) { return !F.sparse && F.min_bs == F.max_bs && dense_block_size(F.max_bs); }
 
 // G lanes to a column (4 where the columns are short)
 template <int G>
@@ -2440,15 +2419,21 @@ static int cholsol_exact_classes_build(CholPlan *P) {
     return CSX_OK;
 }
 
+// The grid of the dense-block kernels whose four waves share a block's LDS copy (k_cholsol_dense_exact_dpp, k_cholsol_mfma): `share`
+// waves of a workgroup solve the same block -- as many as divide the number of 64-wide chunks of right-hand sides
+struct ShareGrid { int share; dim3 grid; };
+static ShareGrid share_grid(int32_t ntrees, int32_t chunks) {
+    const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
+    return {share, dim3((unsigned)(((int64_t)ntrees + share - 1) / share * (chunks / (4 / share))))};
+}
+
 static int launch_exact_dpp(int BS, const Tree *trees, int32_t ntrees, const int32_t *nodes, const int32_t *perm, const int32_t *f_ptr,
                             const double *f_val, const int32_t *b_ptr, const double *dense_b, const double *diagk, const double *diagb,
                             double *B, int32_t nrhs, const double *packed_lx = nullptr) {
     // packed_lx: L.x of a factor that is nothing but these equal blocks, block t at t BS (BS + 1) / 2 -- no programs needed
     hipStream_t s = ctx().stream;
     const int32_t chunks = (nrhs + 63) / 64;
-    const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
-    const int64_t groups = ((int64_t)ntrees + share - 1) / share * (chunks / (4 / share));
-    const dim3 grid((unsigned)groups);
+    const auto [share, grid] = share_grid(ntrees, chunks);
     if (packed_lx) f_val = packed_lx;
 #define CSX_DPP_X(BS_, SH, PK)                                                                                                     \
     hipLaunchKernelGGL((k_cholsol_dense_exact_dpp<BS_, SH, PK>), grid, dim3(256), 0, s, trees, ntrees, nodes, perm, f_ptr, f_val, \
@@ -2517,13 +2502,11 @@ static int cholsol_full(CholPlan **out) {
     return CSX_OK;
 }
 
-static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
-    hipStream_t s = ctx().stream;
-    const int32_t n = P->n;
-    if (n == 0 || nrhs == 0) return CSX_OK;
-    // what the route reads and has not been made yet, in this order: the exact classes, a clique plan's programs, `full` (below)
+// What the route of a solve reads and has not been made yet, in this order: the exact classes, a clique plan's programs (`full` is
+// made by the route that needs it, cholsol_full).  *route = the route the solve then takes.  A zero pivot is reported from here.
+static int cholsol_make_operands(CholPlan *P, double *B, CholRoute *out) {
     if (cholsol_route(P) == CholRoute::ExactClasses) CSX_TRY(cholsol_exact_classes_build(P));
-    const CholRoute route = cholsol_route(P);   // (Full when that build gave up)
+    const CholRoute route = *out = cholsol_route(P);   // (Full when that build gave up)
     if (P->clique) {
         // a plan csx_cholsol_factor made holds the matrix-core operands only (written by the block kernel beside L.x); what the
         // substitution kernels read is cut out of L.x the first time one of them is asked for
@@ -2537,6 +2520,74 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
     } else if (P->local && !P->lite) {
         CSX_TRY(tri_solve_raw(P->fwd, B, 0, false));    // zero pivots found by the analysis: reported like the reference (ZeroDivisionError)
     }
+    return CSX_OK;
+}
+
+// The supernodal pair of sweeps on X (csx_snsolve.hip), launched directly or replayed from a captured graph ("tri.graph")
+static int cholsol_supernodal(CholPlan *P, double *X, int32_t nrhs) {
+    hipStream_t s = ctx().stream;
+    const int32_t *Gp, *Gi;
+    const double *Gx, *Gd;
+    tri_gather_arrays(P->fwd, &Gp, &Gi, &Gx, &Gd);
+    CSX_TRY(tri_solve_raw(P->fwd, X, 0, false));          // a zero pivot found by the analysis: ZeroDivisionError
+    // "tri.graph": 1 = always; 2 (the default) = when a solve is many launches -- more than 256: a natural-order grid
+    // factor is 5 624 -- and this block has been the block of the two solves before this one as well (round 4 captured on
+    // the SECOND solve of a block: 9 ms of capture + instantiate in front of a 1.8 ms solve on bcsstk16, which a caller
+    // who solves a block twice never gets back); 0 = never.  The replay takes the host 13 - 60 us instead of 0.35 -
+    // 17 ms; the device time is the same.  csx_cholsol_graph_info reports the captures and what the last one cost.
+    bool graph = ctx().opt.tri_graph == 1;
+    if (ctx().opt.tri_graph == 2) {
+        int32_t nsn = 0, steps = 0, maxw = 0;
+        sn_info(P->sn, &nsn, &steps, &maxw);
+        P->same_block_runs = (P->last_X == X && P->last_nrhs == nrhs) ? P->same_block_runs + 1 : 0;
+        graph = 6 * (int64_t)steps > 256 && (P->same_block_runs >= 2 || (P->g_exec && P->g_X == X && P->g_nrhs == nrhs));
+    }
+    P->last_X = X;
+    P->last_nrhs = nrhs;
+    if (!graph) {
+        CSX_TRY(sn_solve(P->sn, true, Gp, Gi, Gx, Gd, P->L, X, nrhs));
+        return sn_solve(P->sn, false, Gp, Gi, Gx, Gd, P->L, X, nrhs);
+    }
+    // the two sweeps' launches as one graph, re-used while the block of right-hand sides stays where it is
+    CSX_TRY(sn_prepare(P->sn, nrhs));              // (may move the work space: the captured launches hold its address)
+    if (!(P->g_exec && P->g_X == X && P->g_nrhs == nrhs && P->g_gen == sn_generation(P->sn) && P->g_opt == ctx().opt.tri_supernodes)) {
+        if (P->g_exec) (void)hipGraphExecDestroy(P->g_exec);
+        P->g_exec = nullptr;
+        hipGraph_t captured = nullptr;
+        const auto t_cap = std::chrono::steady_clock::now();
+        CSX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        int st = sn_solve(P->sn, true, Gp, Gi, Gx, Gd, P->L, X, nrhs);
+        if (st == CSX_OK) st = sn_solve(P->sn, false, Gp, Gi, Gx, Gd, P->L, X, nrhs);
+        const hipError_t ec = hipStreamEndCapture(s, &captured);
+        if (st != CSX_OK || ec != hipSuccess) {
+            if (captured) (void)hipGraphDestroy(captured);
+            set_error("cholsol: capturing the supernodal solve failed");
+            return st != CSX_OK ? st : CSX_ERUNTIME;
+        }
+        const hipError_t ei = hipGraphInstantiate(&P->g_exec, captured, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(captured);
+        if (ei != hipSuccess) {
+            P->g_exec = nullptr;
+            set_error("cholsol: hipGraphInstantiate: %s", hipGetErrorString(ei));
+            return CSX_ERUNTIME;
+        }
+        P->g_X = X;
+        P->g_nrhs = nrhs;
+        P->g_gen = sn_generation(P->sn);
+        P->g_opt = ctx().opt.tri_supernodes;
+        P->g_captures++;
+        P->g_capture_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_cap).count();
+    }
+    CSX_HIP(hipGraphLaunch(P->g_exec, s));
+    return CSX_OK;
+}
+
+static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
+    hipStream_t s = ctx().stream;
+    const int32_t n = P->n;
+    if (n == 0 || nrhs == 0) return CSX_OK;
+    CholRoute route;
+    CSX_TRY(cholsol_make_operands(P, B, &route));
     switch (route) {
         case CholRoute::ExactClasses: {
             for (int c = 0; c < 5; c++) {
@@ -2564,8 +2615,7 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
             const int32_t chunks = (nrhs + 63) / 64;
             // (equal dense blocks on ALL the columns of L -- `clique` -- lie in L.x as they do in a copy: block t at t bs (bs + 1) / 2)
             const double *lv = P->lcopy ? P->lcopy : P->L->x;
-            const int share = chunks % 4 == 0 ? 1 : chunks % 2 == 0 ? 2 : 4;
-            const dim3 g2((unsigned)(((int64_t)P->ntrees + share - 1) / share * (chunks / (4 / share))));
+            const auto [share, g2] = share_grid(P->ntrees, chunks);
 #define CSX_MF_X(NB_, SH) \
     hipLaunchKernelGGL((k_cholsol_mfma<NB_, SH>), g2, dim3(256), 0, s, P->trees, P->ntrees, P->tree_nodes, P->perm, lv, P->frag_f, B, nrhs, chunks)
 #define CSX_MF(NB_)                       \
@@ -2630,61 +2680,7 @@ static int cholsol_solve(CholPlan *P, double *B, int32_t nrhs) {
         hipLaunchKernelGGL(k_perm_rows, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, s, P->perm, B, X, n, nrhs, 1);
     }
     if (route == CholRoute::Supernodal) {
-        const int32_t *Gp, *Gi;
-        const double *Gx, *Gd;
-        tri_gather_arrays(P->fwd, &Gp, &Gi, &Gx, &Gd);
-        CSX_TRY(tri_solve_raw(P->fwd, X, 0, false));          // a zero pivot found by the analysis: ZeroDivisionError
-        // "tri.graph": 1 = always; 2 (the default) = when a solve is many launches -- more than 256: a natural-order grid
-        // factor is 5 624 -- and this block has been the block of the two solves before this one as well (round 4 captured on
-        // the SECOND solve of a block: 9 ms of capture + instantiate in front of a 1.8 ms solve on bcsstk16, which a caller
-        // who solves a block twice never gets back); 0 = never.  The replay takes the host 13 - 60 us instead of 0.35 -
-        // 17 ms; the device time is the same.  csx_cholsol_graph_info reports the captures and what the last one cost.
-        bool graph = ctx().opt.tri_graph == 1;
-        if (ctx().opt.tri_graph == 2) {
-            int32_t nsn = 0, steps = 0, maxw = 0;
-            sn_info(P->sn, &nsn, &steps, &maxw);
-            P->same_block_runs = (P->last_X == X && P->last_nrhs == nrhs) ? P->same_block_runs + 1 : 0;
-            graph = 6 * (int64_t)steps > 256 && (P->same_block_runs >= 2 || (P->g_exec && P->g_X == X && P->g_nrhs == nrhs));
-        }
-        P->last_X = X;
-        P->last_nrhs = nrhs;
-        if (graph) {
-            // the two sweeps' launches as one graph, re-used while the block of right-hand sides stays where it is
-            CSX_TRY(sn_prepare(P->sn, nrhs));              // (may move the work space: the captured launches hold its address)
-            if (!(P->g_exec && P->g_X == X && P->g_nrhs == nrhs && P->g_gen == sn_generation(P->sn) &&
-                  P->g_opt == ctx().opt.tri_supernodes)) {
-                if (P->g_exec) (void)hipGraphExecDestroy(P->g_exec);
-                P->g_exec = nullptr;
-                hipGraph_t graph = nullptr;
-                const auto t_cap = std::chrono::steady_clock::now();
-                CSX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                int st = sn_solve(P->sn, true, Gp, Gi, Gx, Gd, P->L, X, nrhs);
-                if (st == CSX_OK) st = sn_solve(P->sn, false, Gp, Gi, Gx, Gd, P->L, X, nrhs);
-                const hipError_t ec = hipStreamEndCapture(s, &graph);
-                if (st != CSX_OK || ec != hipSuccess) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    set_error("cholsol: capturing the supernodal solve failed");
-                    return st != CSX_OK ? st : CSX_ERUNTIME;
-                }
-                const hipError_t ei = hipGraphInstantiate(&P->g_exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                if (ei != hipSuccess) {
-                    P->g_exec = nullptr;
-                    set_error("cholsol: hipGraphInstantiate: %s", hipGetErrorString(ei));
-                    return CSX_ERUNTIME;
-                }
-                P->g_X = X;
-                P->g_nrhs = nrhs;
-                P->g_gen = sn_generation(P->sn);
-                P->g_opt = ctx().opt.tri_supernodes;
-                P->g_captures++;
-                P->g_capture_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_cap).count();
-            }
-            CSX_HIP(hipGraphLaunch(P->g_exec, s));
-        } else {
-            CSX_TRY(sn_solve(P->sn, true, Gp, Gi, Gx, Gd, P->L, X, nrhs));
-            CSX_TRY(sn_solve(P->sn, false, Gp, Gi, Gx, Gd, P->L, X, nrhs));
-        }
+        CSX_TRY(cholsol_supernodal(P, X, nrhs));
     } else {
         CSX_TRY(tri_solve_raw(P->fwd, X, nrhs, P->relaxed));
         CSX_TRY(tri_solve_raw(P->bwd, X, nrhs, P->relaxed));
@@ -2737,6 +2733,27 @@ static int cholsol_plan_blocks(Csc *L, const CliqueForest &F, bool lite, std::un
     return ragged_blocks(F.start, F.nblocks, P->n, P->trees, P->tree_nodes);
 }
 
+// The plan csx_cholsol_factor makes for a forest, by the forest's record, the order and "cholsol.dense_blocks" at factor time -- the
+// ONLY place these five are tested (DESIGN.md §34 has the table; csx_cholsol_forest_plan hands it to the tests, the codes are
+// include/csx.h's).  "Equal": cliques all of one size the dense-block solve kernels take (24 columns each is NOT equal).
+enum class ForestPlan : int32_t {
+    General = 0,      // cholsol_plan(L): the option is off, or sparse trees in the exact order
+    EmitEqual,        // equal blocks of 16 / 32 / 64, rounding-equal order: the block kernel writes the W tiles and the block list
+    Programs,         // equal blocks of 8, rounding-equal order: cholsol_plan_clique
+    BlockListExact,   // equal blocks, exact order: the block list; the exact kernel reads L.x
+    EmitRagged,       // cliques not equal, rounding-equal order: the lite block list; the block kernel writes the ragged fragments
+    BlockListLite,    // cliques not equal in the exact order, sparse trees in the rounding-equal order: the lite block list
+};
+// relax: cholsol_relax finishes the plan -- the rounding-equal order where the block kernel has not left it complete
+struct ForestPlanChoice { ForestPlan kind; bool relax; };
+static ForestPlanChoice cholsol_forest_plan(bool sparse, int32_t min_bs, int32_t max_bs, bool exact, bool dense_blocks) {
+    if (!dense_blocks) return {ForestPlan::General, !exact};
+    if (sparse) return {exact ? ForestPlan::General : ForestPlan::BlockListLite, !exact};
+    if (min_bs != max_bs || !dense_block_size(max_bs)) return {exact ? ForestPlan::BlockListLite : ForestPlan::EmitRagged, false};
+    if (exact) return {ForestPlan::BlockListExact, false};
+    return max_bs >= 16 ? ForestPlanChoice{ForestPlan::EmitEqual, false} : ForestPlanChoice{ForestPlan::Programs, true};
+}
+
 static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, std::unique_ptr<CholPlan> *Pout) {   // (A->clique may be replaced)
     hipStream_t s = ctx().stream;
     const int32_t n = A->n;
@@ -2746,21 +2763,16 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
     auto since = [&](std::chrono::steady_clock::time_point t0) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
-    if (n > 0 && A->nnz > 0 && ctx().opt.chol_clique && ctx().opt.chol_dense_trees) {
-        std::unique_ptr<CliqueForest> own;   // not cached: this call's finding, until the matrix keeps it
-        bool ok = false;
-        const bool cached = A->clique != nullptr && (!A->clique->sparse || ctx().opt.chol_forest);
-        if (cached) {
-            ok = true;
-        } else {
-            own.reset(new CliqueForest());
-            CSX_TRY(clique_forest(A, own.get(), &ok));
-        }
-        CliqueForest &F = cached ? *A->clique : *own;
+    {
+        ForestRoute R;
+        CSX_TRY(clique_forest_route(A, false, true, &R));
         g_factor_ms[0] = since(t_call);
-        if (ok && F.ascending && F.max_bs <= CLIQUE_MAX_BLOCK) {
+        if (R.F) {
+            CliqueForest &F = *R.F;
             const int32_t bs = F.max_bs;
-            const bool emit = !exact && equal_dense_blocks(F) && bs >= 16 && ctx().opt.cholsol_dense_blocks;
+            // 1. the kind of plan this forest gets
+            const ForestPlanChoice plan = cholsol_forest_plan(F.sparse, F.min_bs, bs, exact, ctx().opt.cholsol_dense_blocks != 0);
+            // 2. L, and for the kinds whose operands the block kernel writes, the plan and where they go
             L->m = L->n = n;
             L->nnz = (int32_t)F.lnz;
             L->owns = true;
@@ -2769,38 +2781,16 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
             // many csx_chol (csx_csc_invalidate drops it with every other cached plan)
             CSX_TRY(dalloc(&L->p, (size_t)n + 1));
             CSX_HIP(hipMemcpyAsync(L->p, F.cp, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-            if (!cached) A->clique = std::move(own);   // (F stays this finding)
+            if (R.own) A->clique = std::move(R.own);   // (F stays this finding)
             CSX_TRY(dalloc(&L->x, (size_t)L->nnz));
-            // (L.i: allocated below, once it is known whether the kernel writes it -- with the emission it does not: rows j, j + 1, ...
-            // in every column of a clique, Csc::rows_pending)
             CholPlan *P = nullptr;
             CliqueEmit em;
-            DevBuf<int> d_flags;             // [0] first column with a non-positive pivot, [2..3] the guard's measure
+            DevBuf<int> d_flags;             // four words (clique_run_launch): [2..3] the guard's measure
             CSX_TRY(d_flags.alloc(4));
-            CSX_HIP(hipMemsetAsync(d_flags, 0x7f, sizeof(int), s));
-            CSX_HIP(hipMemsetAsync(d_flags + 2, 0, 2 * sizeof(int), s));
             em.cond_bits = (unsigned long long *)(d_flags + 2);   // (read by the kernel only with an emission)
-            // cliques of UNEQUAL sizes, rounding-equal order: the block kernel writes the matrix-core operands of csx_trimfma.hip's
-            // size classes itself (the class-ordered list, descriptors and fragment storage are made first: the kernel needs to know
-            // where each block's fragments go)
-            const bool emit_ragged = !emit && !exact && !F.sparse && ctx().opt.cholsol_dense_blocks && !equal_dense_blocks(F);
             std::unique_ptr<RaggedMfma> Rg;
             DevBuf<int64_t> frag_off;
-            if (emit_ragged) {
-                CSX_TRY(cholsol_plan_blocks(L, F, true, Pout));
-                P = Pout->get();
-                P->relaxed = true;
-                CSX_TRY(ragged_prepare_emit(P->trees, P->ntrees, bs, P->tree_nodes, &Rg, &frag_off));
-                if (Rg) {
-                    em.frag = Rg->frag;
-                    em.frag_off = frag_off;
-                    em.list = Rg->list;
-                    for (int c = 0; c <= RAG_CLASSES; c++) em.cls_start[c] = Rg->cls_start[c];
-                }
-            }
-            const bool emit_any = emit || (emit_ragged && Rg);
-            if (!emit_any) CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
-            if (emit) {
+            if (plan.kind == ForestPlan::EmitEqual) {
                 Pout->reset(new CholPlan(L));   // (the caller frees it on any error)
                 P = Pout->get();
                 CSX_TRY(P->frag_f.alloc((size_t)F.nblocks * (size_t)(bs / 16) * 256));   // the W tiles; the rest is L.x
@@ -2809,75 +2799,93 @@ static int cholsol_factor_device(csx_handle_t hA, Csc *A, bool exact, Csc *L, st
                 em.frag = P->frag_f;
                 em.trees = P->trees;
                 em.tree_nodes = P->tree_nodes;
+            } else if (plan.kind == ForestPlan::EmitRagged) {
+                // the block kernel writes the matrix-core operands of csx_trimfma.hip's size classes itself (the class-ordered list,
+                // descriptors and fragment storage are made first: the kernel needs to know where each block's fragments go)
+                CSX_TRY(cholsol_plan_blocks(L, F, true, Pout));
+                P = Pout->get();
+                CSX_TRY(ragged_prepare_emit(P->trees, P->ntrees, bs, P->tree_nodes, &Rg, &frag_off));
+                if (Rg) {
+                    em.frag = Rg->frag;
+                    em.frag_off = frag_off;
+                    em.list = Rg->list;
+                    for (int c = 0; c <= RAG_CLASSES; c++) em.cls_start[c] = Rg->cls_start[c];
+                }
             }
+            // (with an emission the kernel does not write L.i: rows j, j + 1, ... in every column of a clique, Csc::rows_pending)
+            const bool emits = plan.kind == ForestPlan::EmitEqual || Rg;
+            if (!emits) CSX_TRY(dalloc(&L->i, (size_t)L->nnz));
+            // 3. the block kernel
             hipEvent_t ev_a = nullptr, ev_b = nullptr;
             EvGuard ev_guard{ev_a, ev_b};
             if (hipEventCreate(&ev_a) != hipSuccess || hipEventCreate(&ev_b) != hipSuccess) return CSX_ERUNTIME;
-            (void)hipEventRecord(ev_a, s);
-            int st = chol_clique_numeric(A, F, L, d_flags, emit_any ? &em : nullptr, !ctx().opt.chol_exact);
-            (void)hipEventRecord(ev_b, s);
             int h[4] = {0, 0, 0, 0};
-            if (hipMemcpyAsync(h, d_flags, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess) st = st == CSX_OK ? CSX_ERUNTIME : st;
-            if (hipStreamSynchronize(s) != hipSuccess) st = st == CSX_OK ? CSX_ERUNTIME : st;   // (also on failure: L's arrays go back to the pool)
+            bool notspd = false;
+            // (the collect half waits also on failure: L's arrays go back to the pool)
+            const int st = clique_run_collect(clique_run_launch(A, F, L, d_flags, 4, emits ? &em : nullptr, ev_a, ev_b), d_flags, 4, h, "cs_chol", &notspd);
             float ms = 0.0f;
             if (st == CSX_OK && hipEventElapsedTime(&ms, ev_a, ev_b) == hipSuccess) g_factor_ms[1] = ms;
             CSX_TRY(st);
-            if (h[0] != 0x7f7f7f7f) return CSX_ENOTSPD;
-            g_chol_path = F.sparse ? 2 : 1;
+            if (notspd) return CSX_ENOTSPD;
+            g_chol_path = clique_chol_path(F);
+            int32_t path = g_chol_path;          // what csx_cholsol_factor_info reports
             g_chol_numeric_ms = g_factor_ms[1];
             L->rows_pending = L->i == nullptr;   // (emitted) rows j, j + 1, ... in every column: made from L.p when a handle to L is resolved
             double growth = 0.0;                 // (emitted) the guard's measure of the matrix-core operands
             std::memcpy(&growth, h + 2, sizeof growth);
-            if (emit) {
-                P->clique = true;              // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
-                P->ntrees = F.nblocks;
-                P->max_nodes = bs;
-                P->local = true;
-                P->dense_bs = bs;
-                P->relaxed = true;
-                P->mfma_tried = true;
-                P->mfma_growth = growth;
-                if (!(growth <= MFMA_GROWTH_LIMIT))       // the guard refuses the explicit inverses (a NaN too): substitution, from L.x
-                    P->frag_f.reset();
-                g_factor_path = 3;
-            } else if (emit_ragged) {
-                // the plan was made before the kernel ran (above); its matrix-core operands are in place
-                if (Rg) {
-                    Rg->growth = growth;
+            // 4. the plan: every field a kind sets, in that kind's block
+            switch (plan.kind) {
+                case ForestPlan::EmitEqual:
+                    P->clique = true;              // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
+                    P->ntrees = F.nblocks;
+                    P->max_nodes = bs;
+                    P->local = true;
+                    P->dense_bs = bs;
+                    P->relaxed = true;
+                    P->mfma_tried = true;
                     P->mfma_growth = growth;
-                    P->rag_tried = true;
-                    if (growth <= MFMA_GROWTH_LIMIT)         // (max|L| max|W| of a block, the equal-block path's measure; a NaN fails)
-                        P->rag = std::move(Rg);
-                }
-                g_factor_path = 1;
-            } else {
-                if (ctx().opt.cholsol_dense_blocks && (!exact || !F.sparse) && !equal_dense_blocks(F)) {
-                    // a forest of UNEQUAL cliques (either order) or of small sparse trees (rounding-equal order): the plan is the block
+                    if (!(growth <= MFMA_GROWTH_LIMIT))       // the guard refuses the explicit inverses (a NaN too): substitution, from L.x
+                        P->frag_f.reset();
+                    path = 3;
+                    break;
+                case ForestPlan::EmitRagged:
+                    // the lite block list made before the kernel ran (cholsol_plan_blocks: lite, lite_cliques, local, ntrees, max_nodes),
+                    // in the rounding-equal order.  Kept as it was: without a layout from ragged_prepare_emit the plan is `relaxed`
+                    // with nothing built and rag_tried false -- cholsol_build_ragged is left to a later csx_cholsol_set_order
+                    P->relaxed = true;
+                    if (Rg) {
+                        Rg->growth = growth;
+                        P->mfma_growth = growth;
+                        P->rag_tried = true;
+                        // (max|L| max|W| of a block, the equal-block path's measure; a NaN fails)  Kept as it was: the bound here is
+                        // MFMA_GROWTH_LIMIT, while cholsol_build_ragged holds the same operands built after the fact to RAG_GROWTH_LIMIT
+                        if (growth <= MFMA_GROWTH_LIMIT) P->rag = std::move(Rg);
+                    }
+                    break;
+                case ForestPlan::Programs:
+                    // equal dense blocks of 8 (the forest's record says so: no k_clique_factor_shape over L.i): the programs straight from L.x
+                    Pout->reset(new CholPlan(L));
+                    CSX_TRY(cholsol_plan_clique(Pout->get(), bs));
+                    break;
+                case ForestPlan::BlockListExact:
+                    // every solve in the reference's order: the default exact kernel reads L.x itself (k_cholsol_dense_exact_dpp<PACKED>),
+                    // so the plan is the block list; programs are cut out of L.x only if another kernel is asked for (cholsol_solve)
+                    CSX_TRY(cholsol_plan_blocks(L, F, false, Pout));
+                    (*Pout)->clique = true;        // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
+                    (*Pout)->dense_bs = bs;
+                    break;
+                case ForestPlan::BlockListLite:
+                    // a forest of UNEQUAL cliques (exact order) or of small sparse trees (rounding-equal order): the plan is the block
                     // list; the matrix-core operands come straight from L's columns (now, or when the order is switched), the exact order
                     // of cliques runs on padded size classes cut out of L.x at its first solve -- no general plan unless a solve needs one
                     CSX_TRY(cholsol_plan_blocks(L, F, true, Pout));
-                    P = Pout->get();
-                } else if (equal_dense_blocks(F) && ctx().opt.cholsol_dense_blocks) {
-                    // equal dense blocks (the forest's record says so: no k_clique_factor_shape over L.i): the programs straight from L.x
-                    if (exact) {
-                        // every solve in the reference's order: the default exact kernel reads L.x itself (k_cholsol_dense_exact_dpp<PACKED>),
-                        // so the plan is the block list; programs are cut out of L.x only if another kernel is asked for (cholsol_solve)
-                        CSX_TRY(cholsol_plan_blocks(L, F, false, Pout));
-                        P = Pout->get();
-                        P->clique = true;              // (clique_zero_pivot stays false: every pivot is a square root of a positive number)
-                        P->dense_bs = bs;
-                    } else {
-                        Pout->reset(new CholPlan(L));
-                        P = Pout->get();
-                        CSX_TRY(cholsol_plan_clique(P, bs));
-                    }
-                } else {
+                    break;
+                case ForestPlan::General:
                     CSX_TRY(cholsol_plan(L, nullptr, Pout));
-                    P = Pout->get();
-                }
-                if (!exact) CSX_TRY(cholsol_relax(P));
-                g_factor_path = F.sparse ? 2 : 1;
+                    break;
             }
+            if (plan.relax) CSX_TRY(cholsol_relax(Pout->get()));
+            g_factor_path = path;
             g_factor_ms[2] = since(t_call);
             return CSX_OK;
         }
@@ -2914,6 +2922,12 @@ extern "C" int csx_cholsol_factor_info(int32_t *path, double *analysis_ms, doubl
     if (analysis_ms) *analysis_ms = g_factor_ms[0];
     if (numeric_ms) *numeric_ms = g_factor_ms[1];
     if (call_ms) *call_ms = g_factor_ms[2];
+    return CSX_OK;
+}
+
+extern "C" int csx_cholsol_forest_plan(int sparse, int32_t min_bs, int32_t max_bs, int exact, int dense_blocks, int32_t *kind) {   // (no device needed)
+    if (!kind || max_bs < 1 || min_bs > max_bs) return CSX_EINVAL;
+    *kind = (int32_t)cholsol_forest_plan(sparse != 0, min_bs, max_bs, exact != 0, dense_blocks != 0).kind;
     return CSX_OK;
 }
 

@@ -124,19 +124,19 @@ static int chol_refactor_plan(Csc *A, Csc *L, const int32_t *pinv, CholRefPlan *
         set_error("csx_chol_refactor_plan: L is not Cholesky-shaped (diagonal first, rows ascending)");
         return CSX_EINVAL;
     }
-    // forest route: the rule of csx_chol / csx_cholsol_factor, and L's columns are the forest's
-    if (!pinv && A->nnz > 0 && ctx().opt.chol_clique && ctx().opt.chol_dense_trees) {
-        std::unique_ptr<CliqueForest> F(new CliqueForest());
-        bool ok = false;
-        CSX_TRY(clique_forest(A, F.get(), &ok));
-        if (ok && F->ascending && F->max_bs <= CLIQUE_MAX_BLOCK && F->lnz == (int64_t)L->nnz) {
+    // forest route: clique_forest_route's (a finding of this plan's own: the matrix's cached one goes with csx_csc_invalidate), and
+    // L's columns are the forest's
+    {
+        ForestRoute R;   // (a finding that is not taken is let go before the general analysis)
+        CSX_TRY(clique_forest_route(A, pinv != nullptr, false, &R));
+        if (R.F && R.F->lnz == (int64_t)L->nnz) {
             int differ = 0;
-            CSX_TRY(rf_differ((int64_t)n + 1, L->p, F->cp.get(), P->flag.get(), &differ));
+            CSX_TRY(rf_differ((int64_t)n + 1, L->p, R.F->cp.get(), P->flag.get(), &differ));
             if (differ) {
                 set_error("csx_chol_refactor_plan: an upper entry of A has no slot in L (L is not the factor of A's pattern)");
                 return CSX_EINVAL;
             }
-            P->F = std::move(F);
+            P->F = std::move(R.own);
             return CSX_OK;
         }
     }
@@ -206,16 +206,9 @@ extern "C" int csx_chol_refactor(csx_handle_t h, csx_handle_t hA2, int *ok, int3
         Lv.p = L->p;
         Lv.i = P->Li;
         Lv.x = P->Lx;
-        constexpr int NOTSPD_NONE = 0x7f7f7f7f;
-        int hflag = NOTSPD_NONE;
-        CSX_HIP(hipMemsetAsync(P->flag, 0x7f, sizeof(int), s));
-        int st = chol_clique_numeric(&A2v, *P->F, &Lv, P->flag, nullptr, !ctx().opt.chol_exact);   // ("chol.exact" as it stands now: the kernel reads it too)
-        (void)hipEventRecord(P->ev_b, s);
-        if (st == CSX_OK && hipMemcpyAsync(&hflag, P->flag.get(), sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess) st = CSX_ERUNTIME;
-        if (hipStreamSynchronize(s) != hipSuccess && st == CSX_OK) st = CSX_ERUNTIME;
-        if (st == CSX_ERUNTIME) set_error("csx_chol_refactor: %s", hipGetErrorString(hipGetLastError()));
-        CSX_TRY(st);
-        notspd = hflag != NOTSPD_NONE;
+        int hflag = 0;
+        // (ev_a: recorded above, for every route)
+        CSX_TRY(clique_run_collect(clique_run_launch(&A2v, *P->F, &Lv, P->flag, 1, nullptr, nullptr, P->ev_b), P->flag, 1, &hflag, "csx_chol_refactor", &notspd));
     } else {
         CSX_TRY(chol_analysis_refactor(P->An, L, x2, P->Lx, P->ev_b, &notspd));
     }

@@ -28,6 +28,19 @@ struct CliqueForest {
 
 // *ok = A's elimination forest is a set of cliques on consecutive columns (F filled)
 int clique_forest(const Csc *A, CliqueForest *F, bool *ok);
+constexpr int CLIQUE_MAX_BLOCK = 64;
+// THE forest route of csx_chol, csx_cholsol_factor and csx_chol_refactor_plan: which forest the block kernel factors A by, or none
+// (F null: the general path).  The rule: no pinv, A has entries, "chol.clique" and "chol.dense_trees" on; the finding is the one
+// cached on the matrix (may_borrow, and under "chol.forest" as it stands now) or clique_forest's; and the block kernel can take it
+// (upper parts ascending, blocks of at most CLIQUE_MAX_BLOCK columns).  `own` holds F when this call found it -- the caller's to
+// keep, to move into A->clique, or to let go; empty: F is A->clique's (which csx_csc_invalidate drops: a plan that outlives
+// the call says may_borrow = false)
+struct ForestRoute {
+    CliqueForest *F = nullptr;
+    std::unique_ptr<CliqueForest> own;
+};
+int clique_forest_route(const Csc *A, bool pinv, bool may_borrow, ForestRoute *R);
+inline int clique_chol_path(const CliqueForest &F) { return F.sparse ? 2 : 1; }   // what csx_chol_info reports for a forest
 // Are the host arrays parent[n], cp[n + 1] F's?  Three steps so that the caller's kernel runs beside the upload: _begin takes
 // the temporaries, _run (after the caller has queued its own work) uploads and compares on a side stream, _end waits and answers.
 struct CliqueCompare {
@@ -64,6 +77,16 @@ struct CliqueEmit {
 // relaxed ("chol.exact" = 0): fused multiply-adds and reciprocal square roots -- L.x equal to the exact kernel's to rounding
 int chol_clique_numeric(const Csc *A, const CliqueForest &F, Csc *L, int *d_notspd, const CliqueEmit *emit = nullptr, bool relaxed = false);
 constexpr int clique_frags_per_block(int nb16) { return (nb16 * (nb16 - 1) / 2 + nb16) * 4; }
+// A run of the block kernel in two halves, so that a caller can queue work of its own between them (csx_chol: the comparison of S
+// on the side stream).  d_flags: `words` ints, 1 or 4 -- [0] the first column with a non-positive pivot (NOTSPD_NONE: none), and of
+// four [2..3] the bits of the emission's growth measure (CliqueEmit::cond_bits; [1] is not used).
+constexpr int NOTSPD_NONE = 0x7f7f7f7f;     // the flag's idle value: set by a byte fill on the device, no host slot in flight
+// launch: fills the flag words, records ev_a (null: the caller has), runs chol_clique_numeric under "chol.exact" as it stands, records ev_b
+int clique_run_launch(const Csc *A, const CliqueForest &F, Csc *L, int *d_flags, int words, const CliqueEmit *emit, hipEvent_t ev_a, hipEvent_t ev_b);
+// collect: st = what the launch half and the work queued behind it returned.  Reads the flag words into h[words] and waits for the
+// stream -- ALSO when st says something failed: the caller hands the arrays the kernel writes back to the pool.  A failure of its own
+// is reported as "<who>: <HIP's text>".  *notspd = a pivot was not positive (st == CSX_OK only)
+int clique_run_collect(int st, const int *d_flags, int words, int *h, const char *who, bool *notspd);
 
 // Column `col` of the inverse of a 16 x 16 lower-triangular tile T (element (r, q) at T[r * ld + q]): w[r] = inv(T)(r, col), zero
 // above the diagonal.  Shared by k_mfma_frags (csx_chol.hip: fragments from a plan's programs) and k_chol_clique (fragments from
@@ -77,7 +100,6 @@ __device__ __forceinline__ void tile_inverse_column(const double *T, int ld, int
         w[r] = r >= col ? sres / T[r * ld + r] : 0.0;
     }
 }
-constexpr int CLIQUE_MAX_BLOCK = 64;
 // *bs = the block size when L is the factor of a forest of equal dense blocks on consecutive columns, else 0
 int clique_factor_block_size(const Csc *L, int32_t *bs);
 

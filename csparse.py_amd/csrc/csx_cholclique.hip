@@ -426,6 +426,21 @@ int clique_forest(const Csc *A, CliqueForest *F, bool *ok) {
     return CSX_OK;
 }
 
+int clique_forest_route(const Csc *A, bool pinv, bool may_borrow, ForestRoute *R) {
+    *R = ForestRoute();
+    if (pinv || A->nnz <= 0 || !ctx().opt.chol_clique || !ctx().opt.chol_dense_trees) return CSX_OK;
+    // csx_schol's or csx_cholsol_factor's finding for this matrix is read where it lies
+    bool ok = may_borrow && A->clique && (!A->clique->sparse || ctx().opt.chol_forest);
+    if (!ok) {
+        R->own.reset(new CliqueForest());
+        CSX_TRY(clique_forest(A, R->own.get(), &ok));
+    }
+    CliqueForest *F = R->own ? R->own.get() : A->clique.get();
+    if (ok && F->ascending && F->max_bs <= CLIQUE_MAX_BLOCK) R->F = F;
+    else R->own.reset();
+    return CSX_OK;
+}
+
 __global__ __launch_bounds__(256) void k_clique_compare(int32_t n, const int32_t *__restrict__ pa, const int32_t *__restrict__ pb,
                                                         const int32_t *__restrict__ ca, const int32_t *__restrict__ cb, int *bad) {
     const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1127,6 +1142,29 @@ int chol_clique_numeric(const Csc *A, const CliqueForest &F, Csc *L, int *d_nots
 #undef CSX_CQ_GO
     CSX_LAUNCH_CHECK();
     return CSX_OK;
+}
+
+int clique_run_launch(const Csc *A, const CliqueForest &F, Csc *L, int *d_flags, int words, const CliqueEmit *emit, hipEvent_t ev_a, hipEvent_t ev_b) {
+    hipStream_t s = ctx().stream;
+    CSX_HIP(hipMemsetAsync(d_flags, 0x7f, sizeof(int), s));
+    if (words > 2) CSX_HIP(hipMemsetAsync(d_flags + 2, 0, 2 * sizeof(int), s));
+    if (ev_a) (void)hipEventRecord(ev_a, s);
+    const int st = chol_clique_numeric(A, F, L, d_flags, emit, !ctx().opt.chol_exact);
+    (void)hipEventRecord(ev_b, s);
+    return st;
+}
+
+int clique_run_collect(int st, const int *d_flags, int words, int *h, const char *who, bool *notspd) {
+    hipStream_t s = ctx().stream;
+    h[0] = NOTSPD_NONE;
+    bool failed = st == CSX_OK && hipMemcpyAsync(h, d_flags, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess;
+    failed |= hipStreamSynchronize(s) != hipSuccess;
+    if (failed && st == CSX_OK) {
+        set_error("%s: %s", who, hipGetErrorString(hipGetLastError()));
+        st = CSX_ERUNTIME;
+    }
+    *notspd = st == CSX_OK && h[0] != NOTSPD_NONE;
+    return st;
 }
 
 // ---- row indices on demand (Csc::rows_pending) -------------------------------------------------------------------------

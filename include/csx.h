@@ -457,6 +457,18 @@ int csx_cholsol_factor(csx_handle_t A, int exact, csx_handle_t *L, csx_handle_t 
  * csx_cholsol_plan behind the one entry).  *analysis_ms: host clock up to the end of the symbolic analysis; *numeric_ms: HIP-event
  * time of the numeric kernel(s); *call_ms: host clock of the whole call.  Any pointer may be NULL. */
 int csx_cholsol_factor_info(int32_t *path, double *analysis_ms, double *numeric_ms, double *call_ms);
+/* csx_cholsol_forest_plan: the kind of solve plan csx_cholsol_factor makes for a forest of blocks (paths 1 / 2 / 3 above), without
+ * a device -- the library's own decision, for the tests (DESIGN.md §34 has the table).  sparse: the blocks are small sparse trees,
+ * not cliques; min_bs / max_bs: the narrowest and widest block in columns; exact: the order asked for; dense_blocks:
+ * "cholsol.dense_blocks" at factor time.  "Equal" below: cliques all of 8, 16, 32 or 64 columns.  *kind:
+ *   0 General         the general analysis of L (the option off; sparse trees in the exact order)
+ *   1 EmitEqual       equal blocks of 16 / 32 / 64, rounding-equal order: the block kernel writes the matrix-core operands (path 3)
+ *   2 Programs        equal blocks of 8, rounding-equal order: the dense programs cut out of L.x
+ *   3 BlockListExact  equal blocks, exact order: the block list; the exact kernel reads L.x
+ *   4 EmitRagged      cliques not equal, rounding-equal order: the block list; the block kernel writes the ragged fragments
+ *   5 BlockListLite   cliques not equal in the exact order, sparse trees in the rounding-equal order: the block list alone
+ * CSX_EINVAL: min_bs > max_bs, max_bs < 1, kind NULL. */
+int csx_cholsol_forest_plan(int sparse, int32_t min_bs, int32_t max_bs, int exact, int dense_blocks, int32_t *kind);
 /* *path: the route the plan's next solve takes, in its current order (csx_cholsol_set_order) and under the options in force --
  * with "cholsol.dense_blocks" = 0 a forest of dense blocks reports 1, not 2 or 3.  0 = level-scheduled generic, 1 = fused
  * per-tree kernel (X tile in LDS), 2 = dense-block substitution (the reference's operations in the exact order -- cliques of

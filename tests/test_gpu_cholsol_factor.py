@@ -76,6 +76,7 @@ CASES = {
     "equal16": lambda: (_blocks([16] * 130, 5), 3),
     "equal16_one_block": lambda: (_blocks([16], 6), 3),
     "equal8": lambda: (_blocks([8] * 90, 7), 1),
+    "equal24": lambda: (_blocks([24] * 9, 16), 1),                         # blocks all of one size the dense-block kernels do NOT take
     "equal64_fill_inside": lambda: (_blocks([64] * 23, 8, 0.4), 3),        # entries missing inside the blocks: the kernel reads A.i
     "equal32_lower_shuffled": lambda: (_blocks([32] * 40, 9, 0.7, True), 3),
     "unequal": lambda: (_blocks(list(np.random.default_rng(1).integers(1, 65, 150)) + [64, 1, 16], 10), 1),
@@ -101,8 +102,8 @@ def test_one_call_equals_the_three_calls(cs, case, exact):
     assert path == want_path
 
     def same_info(in_exact_order):
-        if case == "unequal" and in_exact_order:
-            # the one call's plan solves cliques of unequal sizes exactly by PADDED SIZE CLASSES on the register-resident kernel
+        if case in ("unequal", "equal24") and in_exact_order:
+            # the one call's plan solves cliques that are not equal dense blocks exactly by PADDED SIZE CLASSES on the register-resident kernel
             # (path 2); the three calls' general plan by the fused per-tree kernel (path 1): same trees, same bits (below)
             assert _info(plan) == (2,) + _info(plan0)[1:] and _info(plan0)[0] == 1
         else:
@@ -137,6 +138,42 @@ def test_one_call_equals_the_three_calls(cs, case, exact):
     # with the fused per-tree kernel ("cholsol.dense_blocks" = 0) the programs are cut out of L.x on demand
     with _csx.option("cholsol.dense_blocks", 0):
         assert _solve(plan, B).tobytes() == _solve(plan0, B).tobytes()
+    for h in (plan, plan0, hL, hL0):
+        _csx.free(h)
+
+
+OPTION_OFF_CASES = {
+    "equal16": lambda: _blocks([16] * 5, 17),
+    "unequal": lambda: _blocks([3, 17, 64, 1, 30], 18),
+    "sparse_trees": lambda: _tree_blocks([5, 40, 12], 19, "arrow"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(OPTION_OFF_CASES))
+@pytest.mark.parametrize("exact", [False, True])
+def test_one_call_equals_the_three_calls_without_dense_blocks(cs, case, exact):
+    """"cholsol.dense_blocks" = 0 in force around both flows: every forest gets the general analysis of its L from the one call as
+    from the three (kind General).  The path reported, the plans' info, the solutions in the order the plans were
+    made in and in the other one, and L.p / L.i / L.x, byte for byte."""
+    import _csx
+    lib = _csx.lib()
+    n, Ap, Ai, Ax = OPTION_OFF_CASES[case]()
+    A = cs.cs_pin(_host_cs(cs, n, n, Ap, Ai, Ax))
+    B = synth.rhs(n, 70, 5)
+    with _csx.option("cholsol.dense_blocks", 0):
+        hL0, plan0, _, _ = _three_calls(A, n, exact)
+        st, hL, plan, path = _fused(A, exact)
+        assert st == _csx.OK
+        assert path == (2 if case == "sparse_trees" else 1)
+        assert _info(plan) == _info(plan0)
+        assert _solve(plan, B).tobytes() == _solve(plan0, B).tobytes()
+        for pl in (plan0, plan):
+            _csx.check(lib.csx_cholsol_set_order(pl, 0 if exact else 1))
+        assert _info(plan) == _info(plan0)
+        assert _solve(plan, B).tobytes() == _solve(plan0, B).tobytes()
+        p0, i0, x0 = _download(hL0)
+        p1, i1, x1 = _download(hL)
+        assert p1.tobytes() == p0.tobytes() and i1.tobytes() == i0.tobytes() and x1.tobytes() == x0.tobytes()
     for h in (plan, plan0, hL, hL0):
         _csx.free(h)
 
