@@ -117,6 +117,9 @@ _PROTOS = {
                     _i32p, _i32p, _f64p, _i32p, _i32p, _f64p, _f64p],
     "csx_qr_apply_host": [C.c_int32, _i32p, _i32p, _f64p, _f64p, C.c_int, _f64p],
     "csx_lu_blocks": [H, C.c_double, C.POINTER(H), C.POINTER(H), _i32p, C.POINTER(C.c_int)],
+    "csx_block_limits": [_i32p],
+    "csx_prim_components": [C.c_int32, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _vp, _i32p, _i32p, _i32p, _i32p, _i32p,
+                            C.POINTER(C.c_int)],
     "csx_lu_etree": [H, C.c_double, C.POINTER(H), C.POINTER(H), _i32p, C.POINTER(C.c_int)],
     "csx_updown": [H, C.c_int, C.c_int32, _i32p, _f64p, _i32p, C.POINTER(C.c_int)],
     "csx_updown_block": [H, H, _i32p, _i32p, C.c_int, _i32p],
@@ -713,6 +716,34 @@ def prim_sort_info():
     return {"bits": v[0], "passes": passes, "widths": tuple(v[2:2 + passes]), "nblocks": v[6], "chunk": v[7], "nchunks": v[8],
             "packed": v[9], "k16": v[10], "key_misalign": v[11], "instances": tuple(SORT_INSTANCES[i] for i in v[12:12 + passes]),
             "count": v[16]}
+
+
+BLOCK_LIMITS = ("LU_MAX_M", "LU_MIN_COMPONENTS", "QR_MAX_M", "QR_MIN_COMPONENTS", "HAPPLY_MAX_LEVELS")
+
+
+def block_limits():
+    """the cuts of csx_lu_blocks, csx_qr_blocks and csx_happly, asked of the library; no GPU needed: a dict by the names of
+    BLOCK_LIMITS (include/csx.h: csx_block_limits)"""
+    out = (C.c_int32 * len(BLOCK_LIMITS))()
+    check(load().csx_block_limits(out), "csx_block_limits")
+    return {name: int(out[k]) for k, name in enumerate(BLOCK_LIMITS)}
+
+
+def prim_components(n, p, i, skip_first=0, skip_last=0, order=0):
+    """connected_components + group_by_root on host arrays (csx_prim_components).  A dict: root, nodes, first, count (ncomp
+    entries each), comp_of_pos, ncomp, maxc, malformed, and p, i as the device left them.  With malformed set the other
+    results are None."""
+    pp, ii = np.array(p, dtype=np.int32), np.array(i, dtype=np.int32)
+    root, nodes, cop = np.full(n, -7, np.int32), np.full(n, 0xDEADBEEF, np.uint32), np.full(n, -7, np.int32)
+    first, count = np.full(n, -7, np.int32), np.full(n, -7, np.int32)
+    ncomp, maxc, bad = C.c_int32(-1), C.c_int32(-1), C.c_int(-1)
+    check(lib().csx_prim_components(n, pi(pp), pi(ii), skip_first, skip_last, order, pi(root), _vptr(nodes), pi(first), pi(count),
+                                    pi(cop), C.byref(ncomp), C.byref(maxc), C.byref(bad)), "csx_prim_components")
+    out = {"ncomp": ncomp.value, "maxc": maxc.value, "malformed": bad.value, "p": pp, "i": ii,
+           "root": None, "nodes": None, "first": None, "count": None, "comp_of_pos": None}
+    if not bad.value:
+        out.update(root=root, nodes=nodes, first=first[:ncomp.value], count=count[:ncomp.value], comp_of_pos=cop)
+    return out
 
 
 def exported_symbols():

@@ -196,3 +196,64 @@ int trees_biggest_first(const Tree *trees, int32_t ntrees, int32_t max_count, De
 }
 
 }  // namespace csx
+
+using namespace csx;
+
+// connected_components then group_by_root on HOST arrays, as csx_lu_blocks runs them, for the tests (include/csx.h).  The
+// column pointers are checked here (the kernels index idx with them); the indices are the kernel's to check (malformed).
+// Not on a path production code takes.
+extern "C" int csx_prim_components(int32_t n, int32_t *p, int32_t *i, int skip_first, int skip_last, int order,
+                                   int32_t *root_out, uint32_t *nodes_out, int32_t *first_out, int32_t *count_out,
+                                   int32_t *comp_of_pos_out, int32_t *ncomp, int32_t *maxc, int *malformed) {
+    if (n < 0 || !p || !ncomp || !maxc || !malformed || skip_first < 0 || skip_first > 1 || skip_last < 0 || skip_last > 1 ||
+        order < 0 || order > 2)
+        return CSX_EINVAL;
+    if (n > 0 && (!root_out || !nodes_out || !first_out || !count_out || !comp_of_pos_out)) return CSX_EINVAL;
+    if (p[0] != 0) return CSX_EINVAL;
+    for (int32_t j = 0; j < n; j++)
+        if (p[j] > p[j + 1]) return CSX_EINVAL;
+    const size_t nnz = (size_t)p[n];
+    if (nnz > 0 && !i) return CSX_EINVAL;
+    *ncomp = 0;
+    *maxc = 0;
+    *malformed = 0;
+    if (n == 0) return CSX_OK;
+    CSX_TRY(require_ready());
+    hipStream_t s = ctx().stream;
+    DevBuf<int32_t> dp, di, root, comp_of_pos;
+    DevBuf<uint32_t> nodes;
+    DevBuf<Tree> comps;
+    CSX_TRY(upload(dp, (const int32_t *)p, (size_t)n + 1));
+    CSX_TRY(upload(di, (const int32_t *)i, nnz));
+    CSX_TRY(root.alloc((size_t)n));
+    bool bad = false;
+    CSX_TRY(connected_components(n, dp, di, skip_first, skip_last, order, root, &bad));
+    CSX_HIP(hipMemcpyAsync(p, dp.get(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (nnz) CSX_HIP(hipMemcpyAsync(i, di.get(), nnz * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (bad) {                                          // every caller stops here: root is not settled
+        CSX_HIP(hipStreamSynchronize(s));
+        *malformed = 1;
+        return CSX_OK;
+    }
+    CSX_TRY(nodes.alloc((size_t)n));
+    CSX_TRY(comp_of_pos.alloc((size_t)n));
+    int32_t nc = 0, mc = 0;
+    CSX_TRY(group_by_root(n, root, nodes, comp_of_pos, &comps, &nc, &mc));
+    if (nc < 0 || nc > n) {
+        set_error("csx_prim_components: %d components of %d vertices", nc, n);
+        return CSX_ERUNTIME;
+    }
+    std::vector<Tree> hc((size_t)nc);
+    CSX_HIP(hipMemcpyAsync(root_out, root.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipMemcpyAsync(nodes_out, nodes.get(), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipMemcpyAsync(comp_of_pos_out, comp_of_pos.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (nc) CSX_HIP(hipMemcpyAsync(hc.data(), comps.get(), (size_t)nc * sizeof(Tree), hipMemcpyDeviceToHost, s));
+    CSX_HIP(hipStreamSynchronize(s));
+    for (int32_t c = 0; c < nc; c++) {
+        first_out[c] = hc[(size_t)c].first;
+        count_out[c] = hc[(size_t)c].count;
+    }
+    *ncomp = nc;
+    *maxc = mc;
+    return CSX_OK;
+}

@@ -128,6 +128,7 @@ struct TiledPlan {
 
 // Order in which the reflections of a matrix of Householder vectors can be applied in parallel (csx_qr.hip):
 // reflections of one level touch disjoint rows.
+constexpr int32_t HAPPLY_MAX_LEVELS = 4096;   // beyond that (a chain of dependent reflections) one launch walks them all
 struct HouseLevels {
     int32_t nlevels = 0;
     std::vector<int32_t> ptr;      // host: [nlevels + 1] into cols

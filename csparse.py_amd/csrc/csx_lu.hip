@@ -9,13 +9,14 @@
 // tie-break, same order of the entries it appends to L and U), 64 components to a wave, the small work arrays in
 // LDS, the factors appended to a private strip of a scratch buffer and then moved to their place in the global L
 // and U once the column counts are scanned.  The result is the host code's, bit for bit: L (unit diagonal first),
-// U (diagonal last), pinv -- tests/test_gpu_lu_blocks.py.  W: 95 ms on one host core -> see DESIGN.md.
+// U (diagonal last), pinv -- tests/test_gpu_lu_blocks.py on W, tests/test_gpu_block_factor.py at every size cut, pivot tie,
+// storage order and singular column.  W: 95 ms on one host core -> see DESIGN.md.
 #include "csx_internal.h"
 #include "csx_sweep.h"
 
 namespace csx {
 
-constexpr int LU_MAX_M = 96;          // rows of a component (work arrays: 24 B per row and lane in LDS)
+constexpr int LU_MAX_M = 96;          // rows of a component (work arrays: 25 B per row and lane in LDS)
 constexpr int LU_MIN_COMPONENTS = 64;
 
 // flags: [0] a singular block (smallest such column, as min)
@@ -202,7 +203,7 @@ __global__ __launch_bounds__(256) void k_lu_local_id(int32_t ncomp, const Tree *
 // to a column, same order of every sum, multiply and add rounded separately -- with its work arrays (stamp, order,
 // path: 4 B, work: 8 B per row) interleaved in LDS and V, R appended to private strips that are moved to their place
 // once the column counts are scanned (k_lu_fill of csx_lu.hip does that for any pair of factors).  V, R and beta come
-// out bit-identical to csx_qr_host (tests/test_gpu_qr_device.py).
+// out bit-identical to csx_qr_host (tests/test_gpu_qr_device.py, tests/test_gpu_block_factor.py).
 constexpr int QR_MAX_M = 96;
 constexpr int QR_MIN_COMPONENTS = 64;
 
@@ -346,6 +347,14 @@ __global__ __launch_bounds__(64) void k_qr_blocks(const Tree *__restrict__ comps
 }  // namespace csx
 
 using namespace csx;
+
+// the cuts of the block routes and of csx_happly, for the tests (no device needed)
+extern "C" int csx_block_limits(int32_t *out) {
+    if (!out) return CSX_EINVAL;
+    const int32_t v[5] = {LU_MAX_M, LU_MIN_COMPONENTS, QR_MAX_M, QR_MIN_COMPONENTS, HAPPLY_MAX_LEVELS};
+    for (int k = 0; k < 5; k++) out[k] = v[k];
+    return CSX_OK;
+}
 
 // *done = 0: the matrix is not a batch of small blocks: use csx_lu_host.
 extern "C" int csx_lu_blocks(csx_handle_t hA, double tol, csx_handle_t *hL, csx_handle_t *hU, int32_t *pinv_host,

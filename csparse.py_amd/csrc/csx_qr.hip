@@ -61,8 +61,6 @@ __global__ __launch_bounds__(64) void k_happly_level(const int32_t *__restrict__
 }
 #pragma clang fp contract(fast)
 
-constexpr int32_t HAPPLY_MAX_LEVELS = 4096;   // beyond that (a chain of dependent reflections) one launch walks them all
-
 // level[k] = 1 + the highest level among the earlier reflections that share a row with k (host, O(nnz V))
 static int house_levels(Csc *V) {
     if (V->house) return CSX_OK;

@@ -652,12 +652,31 @@ int csx_sqr_host(int32_t m, int32_t n, const int32_t *Ap, const int32_t *Ai, int
  * analysis) is not of that shape: use csx_qr_host. */
 int csx_qr_blocks(csx_handle_t A, const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t m2,
                   csx_handle_t *V, csx_handle_t *R, double *beta, int *done);
-/* The same factorisation on the device for a matrix that is a batch of small independent blocks (many connected
- * components of at most 96 rows, found on the device): one workgroup per block, dense in LDS, the reference's
- * pivot rule.  *done = 0 when the matrix is not of that shape (or has duplicate entries): use csx_lu_host.
- * L, U: new device matrices (unit diagonal first / diagonal last, row indices in pivot order); pinv: host, n.
- * Values equal the left-looking code's to rounding.  CSX_ENOTSPD: a singular block. */
+/* The same factorisation on the device for a matrix that is a batch of small independent blocks (at least 64 connected
+ * components of at most 96 rows, found on the device): one lane per block runs csx_lu_host's loop -- the same reach
+ * order, update order and first-maximum pivot rule, duplicates and unsorted columns included.  *done = 0 when the matrix
+ * is not of that shape: use csx_lu_host.  L, U: new device matrices (unit diagonal first / diagonal last, row indices in
+ * pivot order); pinv: host, n.  All three bit-identical to csx_lu_host.  CSX_ENOTSPD: a singular block. */
 int csx_lu_blocks(csx_handle_t A, double tol, csx_handle_t *L, csx_handle_t *U, int32_t *pinv, int *done);
+
+/* For the tests of the two block routes and of csx_happly; production code calls neither.
+ * csx_block_limits: the cuts, without a device: out[5] = LU_MAX_M (rows of the largest block csx_lu_blocks takes),
+ * LU_MIN_COMPONENTS (blocks it needs at least; also the smallest n), QR_MAX_M, QR_MIN_COMPONENTS (the same of csx_qr_blocks),
+ * HAPPLY_MAX_LEVELS (levels beyond which csx_happly walks all reflections in one launch).  CSX_EINVAL: out is NULL.
+ * csx_prim_components: the connected-components pass under both routes, the triangular-solve planner and the symbolic
+ * Cholesky, on HOST arrays: the graph has an edge (r, i[q]) for q in [p[r] + skip_first, p[r + 1] - skip_last); order 0: any
+ * neighbour, 1: every neighbour must be < r, 2: > r (what the planner passes for a forward / backward solve).  Runs
+ * connected_components, then group_by_root, as csx_lu_blocks does.  root[v] = the smallest vertex of v's component; nodes =
+ * the vertices grouped by root, ascending inside a group; first[c], count[c] = component c's slice of nodes (capacity n
+ * each, *ncomp written); comp_of_pos[k] = the component of nodes[k]; *maxc = the largest count.  *malformed = 1: an index
+ * outside [0, n) or on the wrong side for the order -- the other outputs are then not written, as every caller stops
+ * there.  The device copies of p and i are copied back over the host arrays, so that a kernel that wrote to them shows.
+ * CSX_EINVAL, before the device is touched: n < 0, a missing array, p[0] != 0 or p decreasing, skip_first / skip_last not
+ * 0 or 1, order not 0 .. 2. */
+int csx_block_limits(int32_t *out);
+int csx_prim_components(int32_t n, int32_t *p, int32_t *i, int skip_first, int skip_last, int order, int32_t *root,
+                        uint32_t *nodes, int32_t *first, int32_t *count, int32_t *comp_of_pos, int32_t *ncomp, int32_t *maxc,
+                        int *malformed);
 
 /* cs_lu of ONE connected matrix on the device, natural column order: the columns are scheduled by the column elimination
  * tree (the tree of A'A, csparse.py:1136-1169): columns that are not ancestor and descendant reach disjoint rows, so a
