@@ -239,6 +239,15 @@ _PROTOS = {
     "csx_slu_batch_stats": [H, _f64p],
     "csx_slu_batch_member": [H, C.c_int32, _f64p, _f64p],
     "csx_slu_batch_limits": [_i32p],
+    "csx_ldl_batch_factor": [H, H, C.c_int32, _f64p, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_ldl_batch_refactor": [H, H, _f64p, C.POINTER(C.c_int)],
+    "csx_ldl_batch_norm1": [H, H, C.c_int32, _f64p],
+    "csx_ldl_batch_solve": [H, H, C.c_int32],
+    "csx_ldl_batch_info": [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "csx_ldl_batch_stats": [H, _f64p],
+    "csx_ldl_batch_member": [H, C.c_int32, _f64p, _f64p],
+    "csx_ldl_batch_d": [H, _f64p],
+    "csx_ldl_batch_limits": [_i32p],
     "csx_hqr_symbolic_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
                               _i32p, _i32p, _i32p, _i32p],
     "csx_hqr_host": [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _i32p, _i32p, _i32p, C.c_int32, C.c_int32,
@@ -389,6 +398,15 @@ def slu_batch_limits():
     at a time, a wave each), RUN_FETCH (terms of a chain such a wave fetches together)"""
     out = (C.c_int32 * len(SLU_BATCH_LIMITS))()
     check(load().csx_slu_batch_limits(out), "csx_slu_batch_limits")
+    return {name: int(out[k]) for k, name in enumerate(SLU_BATCH_LIMITS)}
+
+
+def ldl_batch_limits():
+    """the constants by which a batch of LDL' value sets cuts members, right-hand sides and grids (csx_ldl_batch.hip on
+    csx_levelwalk.h and csx_batchsolve.h), asked of the library; no GPU needed: slu_batch_limits()'s dict (SLU_BATCH_LIMITS), the
+    level walk and the solve sweeps being the same code"""
+    out = (C.c_int32 * len(SLU_BATCH_LIMITS))()
+    check(load().csx_ldl_batch_limits(out), "csx_ldl_batch_limits")
     return {name: int(out[k]) for k, name in enumerate(SLU_BATCH_LIMITS)}
 
 

@@ -2227,6 +2227,9 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
     refactor(A2): new values on the kept analysis, A2 as for cholsol_factor's refactor: True; False with L, D and the solves
       exactly as before on breakdown; ValueError for another pattern or length.  L.x and d are byte-equal to a fresh
       ldlsol_factor(A2, order, perturb)'s.
+    batch(values, perturb=None): B symmetric value sets on A's pattern factored together in one walk of the levels, with batched
+      solves, the inertia and the log-determinant of every member (_LdlBatch): a shift or parameter sweep on one
+      pattern; this factor is left as it is.
     backward_error(x, b, A=None), refine(b, maxit=5, A=None), condest(A=None), operator_info(): as on cholsol_factor (_SymRefinable).
     inertia(): (positive, negative) pivots = eigenvalues of A by Sylvester's law (exact arithmetic; perturbed pivots keep the
       sign they had).  logdet(): (sign, log |det A|), the sum correctly rounded.  info(): n, lnz, levels (height levels of the
@@ -2261,6 +2264,7 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
     dev = N.L._dev
     N.U, N.pinv, N.B = None, None, None
     hp, keep_p = _perm_handle(pinv, n)
+    perturb_of_factor = perturb
 
     class _Solver(_LdlSolver, _SymRefinable):
         _INFO, _CALLS = _LDL_INFO, ("csx_ldl_refactor", "csx_ldl_info", "csx_ldl_stats")
@@ -2301,6 +2305,17 @@ def ldlsol_factor(A, order=0, perturb=0.0, exact=None):
         def _after_refactor(self, A2):
             self._A2, self._stands, self._source = A2, dev.version, None
             self._operator_changed()
+
+        def batch(self, values, perturb=None):
+            """B value sets on A's pattern factored together on this factor's analysis -> an _LdlBatch (its docstring has the
+            rest).  values: a dvec of nnz x B (read, not kept), a 2-D numpy array of that shape, or a list of B value arrays
+            (copied), each in A's storage order and read as A is (entries with row <= column, of duplicates the last); perturb:
+            defaults to this factor's.  ValueError for another row count, B = 0 or B over the limit.  This factor is not changed
+            and goes on working; it must not be freed before the batch, which holds on to it."""
+            pb = perturb_of_factor if perturb is None else float(perturb)
+            if not pb >= 0.0:
+                raise ValueError("ldlsol_factor.batch: perturb must be >= 0")
+            return _LdlBatch(self, hF, _meta(A)[0], n, pb, values)
 
         # Entries of inv(A) on the pattern of L (sparseinv_ldl, DESIGN.md §26).  Each call reads the factor as it stands (after
         # refactor: the new values; after a refactor that broke down: the old ones) and keeps nothing.  Static pivoting is not
@@ -3497,7 +3512,99 @@ _SLU_BATCH_MEMBER = ("perturbed", "breakdown", "long_columns", "pos", "neg")
 _SLU_BATCH_STATS = ("min_abs_d", "max_abs_d", "max_abs_l", "max_abs_u")
 
 
-class _SluBatch(object):
+class _ValueBatch(object):
+    """What _SluBatch and _LdlBatch share: the intake of the values, the thresholds, the run, the solve's block and info().  A
+    batch class names its texts' prefix (_NAME), the prefix of its library calls (_CALLS), its limits and its statistics."""
+
+    _NAME, _CALLS, _STATS = "", "", ()
+    _limits = staticmethod(lambda: {})
+
+    def __init__(self, solver, hF, nnz, n, perturb, values):
+        self._solver, self._hF, self._nnz, self._n, self._perturb = solver, hF, nnz, n, perturb     # (the solver keeps the factor alive)
+        V, self.B = self._values(values, None)
+        h, ok = _csx.new_handle(), (_csx.C.c_int * self.B)()
+        _csx.check(self._call("factor")(hF, V.handle, self.B, _csx.pd(self._tau(V)), h, ok), self._CALLS + "_factor")
+        self._h = h
+        self._fin = weakref.finalize(self, _csx.free, h)
+        self.ok = np.array(ok[:], dtype=bool)
+
+    def _call(self, name):
+        return getattr(_csx.lib(), self._CALLS + "_" + name)
+
+    def _values(self, values, B):
+        """(dvec of nnz x B, B) of the caller's values; B: the members it must have, or None"""
+        a = None
+        if isinstance(values, dvec):
+            rows, k = values.n, values.k
+        else:
+            a = values if isinstance(values, np.ndarray) else np.asarray([np.asarray(v, dtype=np.float64).ravel() for v in values]).T
+            a = np.asarray(a, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] < 1:
+                raise ValueError("%s: values must be an nnz x B block or a list of B value arrays, B >= 1" % self._NAME)
+            rows, k = a.shape
+        if rows != self._nnz:
+            raise ValueError("%s: %d rows of values given, the factored matrix has %d entries" % (self._NAME, rows, self._nnz))
+        if B is not None and k != B:
+            raise ValueError("%s: %d members given, the batch has %d" % (self._NAME, k, B))
+        most = self._limits()["MAX_MEMBERS"]
+        if k > most:
+            raise ValueError("%s: %d members, a batch holds at most %d: split the family" % (self._NAME, k, most))
+        return (values if a is None else dvec(a)), k
+
+    def _tau(self, V):
+        if self._perturb == 0.0:
+            return None
+        out = np.zeros(self.B)
+        _csx.check(self._call("norm1")(self._hF, V.handle, self.B, _csx.pd(out)), self._CALLS + "_norm1")
+        return self._perturb * out
+
+    def refactor(self, values):
+        V, _ = self._values(values, self.B)
+        ok = (_csx.C.c_int * self.B)()
+        _csx.check(self._call("refactor")(self._h, V.handle, _csx.pd(self._tau(V)), ok), self._CALLS + "_refactor")
+        self.ok = np.array(ok[:], dtype=bool)
+        return self.ok
+
+    def _solve(self, X, *more):
+        if isinstance(X, dvec):
+            d, host = X, None
+        else:
+            host = X
+            d = dvec(np.asarray(X, dtype=np.float64))
+        if d.n != self._n or d.k < self.B or d.k % self.B:
+            raise ValueError("%s.solve: X must be n x (B r) = %d x (%d r)" % (self._NAME, self._n, self.B))
+        _csx.check(self._call("solve")(self._h, d.handle, d.k // self.B, *more), self._CALLS + "_solve")
+        if host is not None:
+            if not isinstance(host, np.ndarray):
+                raise ValueError("%s.solve: X must be a dvec or a numpy array" % self._NAME)
+            host[...] = d.numpy().reshape(host.shape)
+        return True
+
+    def _member(self, m, second):
+        """(L.x, the member's second array of `second`(info) doubles) of member m"""
+        m = int(m)
+        if not 0 <= m < self.B:
+            raise ValueError("%s.member: member %d of %d" % (self._NAME, m, self.B))
+        i = self.info()
+        lnz, cnt = i["lnz"], second(i)
+        Lx, other = np.empty(max(lnz, 1)), np.empty(max(cnt, 1))
+        _csx.check(self._call("member")(self._h, m, _csx.pd(Lx), _csx.pd(other)), self._CALLS + "_member")
+        return Lx[:lnz], other[:cnt]
+
+    def info(self):
+        C = _csx.C
+        shared = (C.c_int64 * len(_SLU_BATCH_SHARED))()
+        per = np.zeros((self.B, len(_SLU_BATCH_MEMBER)), dtype=np.int64)
+        st = np.zeros((self.B, len(self._STATS)))
+        _csx.check(self._call("info")(self._h, shared, per.ctypes.data_as(C.POINTER(C.c_int64))), self._CALLS + "_info")
+        _csx.check(self._call("stats")(self._h, _csx.pd(st)), self._CALLS + "_stats")
+        out = {name: int(v) for name, v in zip(_SLU_BATCH_SHARED, shared)}
+        out.update((name, per[:, k].copy()) for k, name in enumerate(_SLU_BATCH_MEMBER))
+        out.update((name, st[:, k].copy()) for k, name in enumerate(self._STATS))
+        return out
+
+
+class _SluBatch(_ValueBatch):
     """B value sets on the pattern of one slusol_factor, factored together (slusol_factor(...).batch(values)): the
     members share the factor's analysis, matching, order and launch schedule, and go through every launch of it at once.
     Every member's factor is byte-equal to slusol_factor of that member alone under the same matching and order.
@@ -3513,85 +3620,58 @@ class _SluBatch(object):
     Deliberately NOT here: refine, gmres, condest, inverse, solve_grad.  The route to them is the single factor:
     F.refactor(values[:, m])."""
 
-    def __init__(self, solver, hF, nnz, n, perturb, values):
-        self._solver, self._hF, self._nnz, self._n, self._perturb = solver, hF, nnz, n, perturb     # (the solver keeps the factor alive)
-        V, self.B = self._values(values, None)
-        lib = _csx.lib()
-        h, ok = _csx.new_handle(), (_csx.C.c_int * self.B)()
-        _csx.check(lib.csx_slu_batch_factor(hF, V.handle, self.B, _csx.pd(self._tau(V)), h, ok), "csx_slu_batch_factor")
-        self._h = h
-        self._fin = weakref.finalize(self, _csx.free, h)
-        self.ok = np.array(ok[:], dtype=bool)
-
-    def _values(self, values, B):
-        """(dvec of nnz x B, B) of the caller's values; B: the members it must have, or None"""
-        a = None
-        if isinstance(values, dvec):
-            rows, k = values.n, values.k
-        else:
-            a = values if isinstance(values, np.ndarray) else np.asarray([np.asarray(v, dtype=np.float64).ravel() for v in values]).T
-            a = np.asarray(a, dtype=np.float64)
-            if a.ndim != 2 or a.shape[1] < 1:
-                raise ValueError("slusol_factor.batch: values must be an nnz x B block or a list of B value arrays, B >= 1")
-            rows, k = a.shape
-        if rows != self._nnz:
-            raise ValueError("slusol_factor.batch: %d rows of values given, the factored matrix has %d entries" % (rows, self._nnz))
-        if B is not None and k != B:
-            raise ValueError("slusol_factor.batch: %d members given, the batch has %d" % (k, B))
-        most = _csx.slu_batch_limits()["MAX_MEMBERS"]
-        if k > most:
-            raise ValueError("slusol_factor.batch: %d members, a batch holds at most %d: split the family" % (k, most))
-        return (values if a is None else dvec(a)), k
-
-    def _tau(self, V):
-        if self._perturb == 0.0:
-            return None
-        out = np.zeros(self.B)
-        _csx.check(_csx.lib().csx_slu_batch_norm1(self._hF, V.handle, self.B, _csx.pd(out)), "csx_slu_batch_norm1")
-        return self._perturb * out
-
-    def refactor(self, values):
-        V, _ = self._values(values, self.B)
-        ok = (_csx.C.c_int * self.B)()
-        _csx.check(_csx.lib().csx_slu_batch_refactor(self._h, V.handle, _csx.pd(self._tau(V)), ok), "csx_slu_batch_refactor")
-        self.ok = np.array(ok[:], dtype=bool)
-        return self.ok
+    _NAME, _CALLS, _STATS = "slusol_factor.batch", "csx_slu_batch", _SLU_BATCH_STATS
+    _limits = staticmethod(_csx.slu_batch_limits)
 
     def solve(self, X, trans=False):
-        if isinstance(X, dvec):
-            d, host = X, None
-        else:
-            host = X
-            d = dvec(np.asarray(X, dtype=np.float64))
-        if d.n != self._n or d.k < self.B or d.k % self.B:
-            raise ValueError("slusol_factor.batch.solve: X must be n x (B r) = %d x (%d r)" % (self._n, self.B))
-        _csx.check(_csx.lib().csx_slu_batch_solve(self._h, d.handle, d.k // self.B, 1 if trans else 0), "csx_slu_batch_solve")
-        if host is not None:
-            if not isinstance(host, np.ndarray):
-                raise ValueError("slusol_factor.batch.solve: X must be a dvec or a numpy array")
-            host[...] = d.numpy().reshape(host.shape)
-        return True
+        return self._solve(X, 1 if trans else 0)
 
     def member(self, m):
-        m = int(m)
-        if not 0 <= m < self.B:
-            raise ValueError("slusol_factor.batch.member: member %d of %d" % (m, self.B))
-        lnz = self.info()["lnz"]
-        Lx, Ux = np.empty(max(lnz, 1)), np.empty(max(lnz, 1))
-        _csx.check(_csx.lib().csx_slu_batch_member(self._h, m, _csx.pd(Lx), _csx.pd(Ux)), "csx_slu_batch_member")
-        return Lx[:lnz], Ux[:lnz]
+        return self._member(m, lambda i: i["lnz"])
 
-    def info(self):
-        lib, C = _csx.lib(), _csx.C
-        shared = (C.c_int64 * len(_SLU_BATCH_SHARED))()
-        per = np.zeros((self.B, len(_SLU_BATCH_MEMBER)), dtype=np.int64)
-        st = np.zeros((self.B, len(_SLU_BATCH_STATS)))
-        _csx.check(lib.csx_slu_batch_info(self._h, shared, per.ctypes.data_as(C.POINTER(C.c_int64))), "csx_slu_batch_info")
-        _csx.check(lib.csx_slu_batch_stats(self._h, _csx.pd(st)), "csx_slu_batch_stats")
-        out = {name: int(v) for name, v in zip(_SLU_BATCH_SHARED, shared)}
-        out.update((name, per[:, k].copy()) for k, name in enumerate(_SLU_BATCH_MEMBER))
-        out.update((name, st[:, k].copy()) for k, name in enumerate(_SLU_BATCH_STATS))
-        return out
+
+class _LdlBatch(_ValueBatch):
+    """B symmetric value sets on the pattern of one ldlsol_factor, factored together (ldlsol_factor(...).batch(values); DESIGN.md
+    §36): K - sigma_j M over shifts, quasi-definite KKT systems over scenarios.  The members share the factor's analysis, order
+    and launch schedule and go through every launch of it at once; every member's L.x and d are byte-equal to ldlsol_factor of
+    that member alone under the same order.  Half the factor storage of the route through slusol_factor(...).batch, and the
+    inertia of every member.
+    B: the members.  ok: a numpy bool array, False where a member broke down -- there is no commit for a batch, so such a
+      member's values mean nothing (until a refactor mends it) and the others are untouched.
+    refactor(values): new values for all B members (B is fixed) -> the new ok.
+    solve(X): X an n x (B r) block (dvec, overwritten; or a 2-D numpy array, overwritten), columns m r .. m r + r - 1 belong to
+      member m; always in the exact order, the division by D fused into the backward sweep: every column has the bytes of
+      ldlsol_factor(A_m, exact=True).solve(...).  The columns of a failed member come back NaN.
+    member(m) -> (Lx, d) as numpy arrays.  inertia() -> (pos, neg), numpy arrays per member: neg[m] of K - sigma_m M counts the
+      eigenvalues below sigma_m (exact arithmetic; perturbed pivots keep their sign).  logdet() -> (signs, logs) per member, the
+      sum of log |d| correctly rounded (math.fsum) as the single solver's; NaN for a failed member.
+    info(): n, lnz, levels, launches, level_launches, run_launches, kernel_us and B of the whole run, and numpy arrays per
+      member: perturbed, breakdown, long_columns, pos, neg, min_abs_d, max_abs_d, max_abs_l.
+    Deliberately NOT here: refine, gmres, condest, inverse, solve_grad, eigsh.  The route to them is the single factor:
+    F.refactor(values[:, m])."""
+
+    _NAME, _CALLS, _STATS = "ldlsol_factor.batch", "csx_ldl_batch", ("min_abs_d", "max_abs_d", "max_abs_l")
+    _limits = staticmethod(_csx.ldl_batch_limits)
+
+    def solve(self, X):
+        return self._solve(X)
+
+    def member(self, m):
+        return self._member(m, lambda i: i["n"])
+
+    def inertia(self):
+        i = self.info()
+        return i["pos"], i["neg"]
+
+    def logdet(self):
+        d = np.empty(max(self.B * self._n, 1))
+        _csx.check(self._call("d")(self._h, _csx.pd(d)), "csx_ldl_batch_d")
+        d = d[:self.B * self._n].reshape(self.B, self._n)
+        signs, logs = np.full(self.B, np.nan), np.full(self.B, np.nan)
+        for m in np.flatnonzero(self.ok):
+            signs[m] = -1.0 if int(np.sum(d[m] < 0.0)) % 2 else 1.0
+            logs[m] = math.fsum(np.log(np.abs(d[m])).tolist())
+        return signs, logs
 
 
 def _perm_parity(p):

@@ -253,6 +253,7 @@ static void free_object(Object &o) {
         case K_SCHURFACTOR: destroy((LdlFactor *)o.ptr); break;
         case K_SLUFACTOR: destroy((SluFactor *)o.ptr); break;
         case K_SLUBATCH: destroy((SluBatch *)o.ptr); break;
+        case K_LDLBATCH: destroy((LdlBatch *)o.ptr); break;
         case K_HQRFACTOR: destroy((HqrFactor *)o.ptr); break;
         default: break;
     }

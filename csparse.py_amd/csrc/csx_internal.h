@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR, K_SLUBATCH };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR, K_SLUBATCH, K_LDLBATCH };
 
 struct Csc;
 
@@ -228,6 +228,8 @@ struct SluFactor;     // csx_slu.h (csx_slu.hip)
 void destroy(SluFactor *p);
 struct SluBatch;      // csx_slu_batch.hip: B value sets on a borrowed SluFactor
 void destroy(SluBatch *p);
+struct LdlBatch;      // csx_ldl_batch.hip: B value sets on a borrowed LdlFactor
+void destroy(LdlBatch *p);
 struct HqrFactor;     // csx_hqr.hip
 void destroy(HqrFactor *p);
 // csx_host.cpp: csx_hqr_symbolic_host on vectors that grow (no capacities)

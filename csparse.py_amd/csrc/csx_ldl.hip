@@ -3,8 +3,9 @@
 // the pattern of L is cs_chol's, so the symbolic step (chol_symbolic_device), the entry map (chol_entry_map) and the scatter
 // (chol_scatter) are csx_chol's own; the numeric kernels here are the left-looking column of chol_column with d[k] carried
 // beside L(j,k), no square root, and the pivot rule (perturbation below tau, breakdown at 0 or a non-finite pivot).
-//   ldl_column    one wave's column, behind the policy LdlColumn of the level walk (csx_levelwalk.h: k_level, k_run, the schedule)
-//   k_ldl_stats   inertia, min / max |d|, max |l| off the diagonal in one pass
+//   ldl_column    one wave's column, behind the policy LdlColumn of the level walk (csx_ldl.h; csx_levelwalk.h: k_level, k_run, the
+//                 schedule)
+//   k_ldl_stats   inertia, min / max |d|, max |l| off the diagonal in one pass (ldl_stats_column, csx_ldl.h)
 //   k_block_div_rows  X[i, :] /= d[i], the D step of a solve
 // Every sum is updated in ascending k by one wave, one update after the other: L.x and d are byte-equal to csx_ldl_host.
 // A factor or refactor runs into scratch arrays and is committed only when no column broke down.
@@ -23,94 +24,15 @@
 
 namespace csx {
 
-// Column j of L and d[j].  On entry Lx[Lp[j] ..] holds C(:, j) in the slots of L (0.0 in fill slots), and every column k < j
-// with L(j,k) in the pattern is finished (L(:,k) and d[k] final).  acc_v / acc_r: wave-private LDS (LDL_ACC entries).
-// flags[0]: the smallest broken column (atomicMin), flags[1]: perturbed pivots, flags[2]: columns that took the in-place path
-// (integer atomicAdd both).
-__device__ __forceinline__ void ldl_column(int32_t j, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li, double *Lx,
-                                           double *d, const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
-                                           const int32_t *__restrict__ row_pos, double tau, double *acc_v, int32_t *acc_r,
-                                           int lane, int *flags) {
-    const int32_t base = Lp[j], len = Lp[j + 1] - base;
-    const bool in_lds = len <= LDL_ACC;
-    if (in_lds) {
-        for (int32_t t = lane; t < len; t += 64) {
-            acc_v[t] = Lx[base + t];
-            acc_r[t] = Li[base + t];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // the updates (csx_colupdate.h): weight L(j,k) d[k], one plane Lx, the sums in the LDS window or in place in Lx
-    column_updates<1>(
-        j, Lp, Li, row_ptr, row_col, row_pos, lane,
-        [&](int32_t k, int32_t pos, double (&w)[1]) {
-            w[0] = Lx[pos] * d[k];
-            return true;
-        },
-        [&](int32_t p, double (&v)[1]) { v[0] = Lx[p]; },
-        [&](int32_t row, const double (&a)[1]) {
-            if (in_lds) {
-                const int32_t t = find_row(acc_r, len, row);
-                acc_v[t] = acc_v[t] - a[0];
-            } else {
-                const int32_t t = base + find_row(Li + base, len, row);
-                Lx[t] = Lx[t] - a[0];
-            }
-        });
-    double dj = in_lds ? acc_v[0] : Lx[base];
-    const bool small = tau > 0.0 && fabs(dj) < tau;
-    if (small) dj = copysign(tau, dj);
-    if (lane == 0) {
-        if (small) atomicAdd(flags + 1, 1);
-        if (!in_lds) atomicAdd(flags + 2, 1);
-        if (dj == 0.0 || !isfinite(dj)) atomicMin(flags, j);
-        d[j] = dj;
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int32_t t = lane; t < len; t += 64) {
-        const double v = in_lds ? acc_v[t] : Lx[base + t];
-        Lx[base + t] = t == 0 ? 1.0 : v / dj;
-    }
-    __builtin_amdgcn_wave_barrier();
-}
+// ldl_column, its policy LdlColumn and one column of the statistics: csx_ldl.h (shared with csx_ldl_batch.hip)
 
-// the level walk's policy (csx_levelwalk.h): ldl_column behind k_level / k_run, with the kernels' argument types and LDS arrays
-struct LdlColumn {
-    using Args = ColumnArgs<const int32_t *__restrict__, const int32_t *__restrict__, double *, double *, const int32_t *__restrict__,
-                            const int32_t *__restrict__, const int32_t *__restrict__, double, int *>;
-    static __device__ __forceinline__ void column(int32_t j, int w, int lane, const int32_t *Lp, const int32_t *Li, double *Lx,
-                                                  double *d, const int32_t *row_ptr, const int32_t *row_col, const int32_t *row_pos,
-                                                  double tau, int *flags) {
-        __shared__ double acc_v[WALK_WAVES][LDL_ACC];
-        __shared__ int32_t acc_r[WALK_WAVES][LDL_ACC];
-        ldl_column(j, Lp, Li, Lx, d, row_ptr, row_col, row_pos, tau, acc_v[w], acc_r[w], lane, flags);
-    }
-};
-
-// One wave per column: st[0] positive pivots, st[1] negative pivots (integer adds), st[2] min |d|, st[3] max |d|, st[4] max |l|
-// off the diagonal -- extrema of the bit patterns of fabs taken as unsigned integers (csx_residual.hip's rule: a NaN ranks above inf).
+// One wave per column: ldl_stats_column (csx_ldl.h) into the five words st
 __global__ __launch_bounds__(256) void k_ldl_stats(int32_t n, const int32_t *__restrict__ Lp, const double *__restrict__ Lx,
                                                    const double *__restrict__ d, unsigned long long *st) {
     const int lane = threadIdx.x & 63;
     const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     if (j >= n) return;
-    uint64_t lmax = 0;
-    for (int32_t p = Lp[j] + 1 + lane; p < Lp[j + 1]; p += 64) {
-        const uint64_t v = abs_bits(Lx[p]);
-        lmax = v > lmax ? v : lmax;
-    }
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint64_t v = (uint64_t)__shfl_xor((unsigned long long)lmax, off);
-        lmax = v > lmax ? v : lmax;
-    }
-    if (lane == 0) {
-        const double dj = d[j];
-        if (dj > 0.0) atomicAdd(st + 0, 1ull);
-        if (dj < 0.0) atomicAdd(st + 1, 1ull);
-        atomicMin(st + 2, (unsigned long long)abs_bits(dj));
-        atomicMax(st + 3, (unsigned long long)abs_bits(dj));
-        if (lmax) atomicMax(st + 4, (unsigned long long)lmax);
-    }
+    ldl_stats_column(j, lane, Lp, Lx, d, st);
 }
 
 // X[i, c] = X[i, c] / d[i] over a row-major rows x nrhs block; PAIR: two columns per thread through 16-byte accesses
@@ -225,9 +147,11 @@ int ldl_build(Csc *A, const int32_t *parent, const int32_t *cp, const int32_t *p
         height_levels(n1, cut.data(), F->level_ptr_h, cols);
         CSX_TRY(walk_set_levels(F, cols, run_levels));
         CSX_TRY(F->win.alloc((size_t)F->lnz));
-        DevBuf<int32_t> d_pinv;
-        if (pinv) CSX_TRY(upload(d_pinv, pinv, (size_t)n));
-        CSX_TRY(chol_entry_map(A, pinv ? d_pinv.get() : nullptr, fp, fi, F->lnz, F->win, F->flags));
+        if (pinv) {   // (kept: csx_ldl_batch_solve permutes with it)
+            CSX_TRY(upload(F->perm_p, pinv, (size_t)n));
+            F->pinv = F->perm_p;
+        }
+        CSX_TRY(chol_entry_map(A, F->pinv, fp, fi, F->lnz, F->win, F->flags));
         if (ns) {   // Lp: the interior columns of the full pattern, then one unit diagonal entry per kept column
             lp.resize((size_t)n + 1);
             tail.resize((size_t)ns);

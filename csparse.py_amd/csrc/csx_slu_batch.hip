@@ -8,28 +8,21 @@
 //                    tau read from an array, then SluColumn::column -- slu_column itself, the host rule's bits
 //   k_slb_stats      slu_stats_column per (column, member)
 //   k_slb_norm1      |A_m|_1 by k_norm1's rule
-//   k_slb_level / k_slb_run <rows or dots>   the two sweeps of a solve in the reference's operation order, over F's height
-//                    levels: a wide level is one launch of a thread per (row, member, right-hand side), a run of narrow levels
-//                    one launch of a workgroup per member with a wave per (row, right-hand side) -- F's schedule, so
-//                    len(schedule) launches a sweep for any B
-//   k_slb_permute_in / k_slb_permute_out   the solve's permutations; the second fills a failed member's columns with NaN
+//   batch_sweep      the two sweeps of a solve in the reference's operation order, over F's height levels, and the solve's
+//                    permutations: csx_batchsolve.h (k_slb_level, k_slb_run, k_slb_permute_in / _out), shared with the LDL' batch
 // There is NO scratch-then-commit: a member that breaks down is marked failed (ok[m] = 0, its values mean nothing) where the
 // single factor keeps its old values.  Keeping them would take a second B x lnz pair of arrays.
 #include <cmath>
 #include <cstring>
 #include <limits>
 
+#include "csx_batchsolve.h"
 #include "csx_internal.h"
 #include "csx_slu.h"
 
 #pragma clang fp contract(off)
 
 namespace csx {
-
-constexpr int SLB_THREADS = 256;   // threads of a workgroup of the solve kernels: the (row, column) pairs a wide level's workgroup takes
-constexpr int SLB_FETCH = 4;       // terms of a chain that a thread of a wide level fetches together, then applies one after the other
-constexpr int SLB_RUN_WAVES = 16;  // waves of a walker's workgroup: (row, right-hand side) pairs it takes at a time, a wave each
-constexpr int SLB_RUN_FETCH = 64;  // terms of a chain that a walker's wave fetches together, a lane each
 
 struct SluBatch {
     SluFactor *F = nullptr;   // borrowed: valid while hF resolves to it
@@ -103,148 +96,7 @@ __global__ __launch_bounds__(256) void k_slb_norm1(int32_t n, int32_t B, const i
     if (sum == sum) atomicMax(best + m, (unsigned long long)__double_as_longlong(sum));
 }
 
-// ---- solve: the two sweeps ----------------------------------------------------------------------------------------------------
-// X is n x K row-major, K = B r; column c belongs to member c / r.  val: the member-major values of the factor the sweep reads
-// (stride lnz); div: divide by the diagonal val[Lp[j]] (Ut) or not (unit L).
-
-// x_j = ((x_j - v1 x_k1) - v2 x_k2) - ... over row j's entries off the diagonal in the row view (k ascending), then / d_j
-__device__ __forceinline__ void slb_row(int32_t j, int64_t c, int64_t K, const int32_t *__restrict__ Lp,
-                                        const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
-                                        const int32_t *__restrict__ row_pos, const double *__restrict__ v, bool div, double *X) {
-    double s = X[(int64_t)j * K + c];
-    const int32_t qe = row_ptr[j + 1] - 1;   // the row view ends with the diagonal
-    for (int32_t q0 = row_ptr[j]; q0 < qe; q0 += SLB_FETCH) {
-        double a_[SLB_FETCH], x_[SLB_FETCH];
-#pragma unroll
-        for (int u = 0; u < SLB_FETCH; u++) {
-            const int32_t q = q0 + u < qe ? q0 + u : q0;
-            a_[u] = v[row_pos[q]];
-            x_[u] = X[(int64_t)row_col[q] * K + c];
-        }
-#pragma unroll
-        for (int u = 0; u < SLB_FETCH; u++)
-            if (q0 + u < qe) {
-                const double t = a_[u] * x_[u];
-                s = s - t;
-            }
-    }
-    if (div) s = s / v[Lp[j]];
-    X[(int64_t)j * K + c] = s;
-}
-
-// x_j = ((x_j - v1 x_i1) - v2 x_i2) - ... over column j's stored entries below the diagonal in storage order, then / d_j
-__device__ __forceinline__ void slb_dot(int32_t j, int64_t c, int64_t K, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
-                                        const double *__restrict__ v, bool div, double *X) {
-    double s = X[(int64_t)j * K + c];
-    const int32_t pe = Lp[j + 1];
-    for (int32_t p0 = Lp[j] + 1; p0 < pe; p0 += SLB_FETCH) {
-        double a_[SLB_FETCH], x_[SLB_FETCH];
-#pragma unroll
-        for (int u = 0; u < SLB_FETCH; u++) {
-            const int32_t p = p0 + u < pe ? p0 + u : p0;
-            a_[u] = v[p];
-            x_[u] = X[(int64_t)Li[p] * K + c];
-        }
-#pragma unroll
-        for (int u = 0; u < SLB_FETCH; u++)
-            if (p0 + u < pe) {
-                const double t = a_[u] * x_[u];
-                s = s - t;
-            }
-    }
-    if (div) s = s / v[Lp[j]];
-    X[(int64_t)j * K + c] = s;
-}
-
-// a wide level: one thread per (row of the level, column of X), the columns fastest
-template <bool ROWS>
-__global__ __launch_bounds__(SLB_THREADS) void k_slb_level(const int32_t *__restrict__ cols, int32_t count, int64_t K, int32_t r,
-                                                           int64_t lnz, const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
-                                                           const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
-                                                           const int32_t *__restrict__ row_pos, const double *__restrict__ val, int div,
-                                                           double *X) {
-    const int64_t t = (int64_t)blockIdx.x * SLB_THREADS + threadIdx.x;
-    if (t >= (int64_t)count * K) return;
-    const int64_t i = t / K, c = t - i * K;
-    const double *v = val + (c / r) * lnz;
-    if (ROWS) slb_row(cols[i], c, K, Lp, row_ptr, row_col, row_pos, v, div != 0, X);
-    else slb_dot(cols[i], c, K, Lp, Li, v, div != 0, X);
-}
-
-// One WAVE's (row, column of X) of a narrow level, where a chain is long (the top of a nested-dissection tree) and there are few
-// of them: the 64 lanes fetch 64 terms of the chain together and each forms one product -- a product is rounded on its own,
-// whoever forms it -- then the products are applied one after the other in the chain's order, every lane keeping the same sum.
-template <bool ROWS>
-__device__ __forceinline__ void slb_wave_chain(int32_t j, int64_t c, int64_t K, int lane, const int32_t *__restrict__ Lp,
-                                               const int32_t *__restrict__ Li, const int32_t *__restrict__ row_ptr,
-                                               const int32_t *__restrict__ row_col, const int32_t *__restrict__ row_pos,
-                                               const double *__restrict__ v, bool div, double *X) {
-    const int32_t q0 = __builtin_amdgcn_readfirstlane(ROWS ? row_ptr[j] : Lp[j] + 1);
-    const int32_t qe = __builtin_amdgcn_readfirstlane(ROWS ? row_ptr[j + 1] - 1 : Lp[j + 1]);
-    double s = X[(int64_t)j * K + c];
-    for (int32_t b = q0; b < qe; b += 64) {
-        const int32_t q = b + lane;
-        double t = 0.0;
-        if (q < qe) {
-            const double a = ROWS ? v[row_pos[q]] : v[q];
-            const int32_t k = ROWS ? row_col[q] : Li[q];
-            t = a * X[(int64_t)k * K + c];
-        }
-        const int32_t terms = qe - b < 64 ? qe - b : 64;
-        for (int32_t u = 0; u < terms; u++) {
-            const double tu = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), u),
-                                               __builtin_amdgcn_readlane(__double2loint(t), u));
-            s = s - tu;
-        }
-    }
-    if (div) s = s / v[Lp[j]];
-    if (lane == 0) X[(int64_t)j * K + c] = s;
-}
-
-// a run of narrow levels: the workgroup of member blockIdx.x walks [l0, l1) -- ascending for the rows, descending for the dots --
-// with a barrier per level; its SLB_RUN_WAVES waves take the (row of the level, right-hand side) pairs one each at a time
-// (slb_wave_chain).  The trip counts are the level pointers and r, the same for every wave, so every wave reaches every barrier.
-template <bool ROWS>
-__global__ __launch_bounds__(64 * SLB_RUN_WAVES) void k_slb_run(const int32_t *__restrict__ cols, const int32_t *__restrict__ level_ptr,
-                                                         int32_t l0, int32_t l1, int64_t K, int32_t r, int64_t lnz,
-                                                         const int32_t *__restrict__ Lp, const int32_t *__restrict__ Li,
-                                                         const int32_t *__restrict__ row_ptr, const int32_t *__restrict__ row_col,
-                                                         const int32_t *__restrict__ row_pos, const double *__restrict__ val, int div,
-                                                         double *X) {
-    const int64_t m = blockIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const double *v = val + m * lnz;
-    for (int32_t s = 0; s < l1 - l0; s++) {
-        const int32_t l = ROWS ? l0 + s : l1 - 1 - s;
-        const int32_t b = level_ptr[l], cnt = level_ptr[l + 1] - b;
-        for (int32_t t = w; t < cnt * r; t += SLB_RUN_WAVES) {
-            const int32_t i = t / r;
-            const int32_t j = __builtin_amdgcn_readfirstlane(cols[b + i]);
-            slb_wave_chain<ROWS>(j, m * r + (t - i * r), K, lane, Lp, Li, row_ptr, row_col, row_pos, v, div != 0, X);
-        }
-        __syncthreads();
-    }
-}
-
-// W[p[i], :] = X[i, :] (p null: the identity)
-__global__ __launch_bounds__(256) void k_slb_permute_in(int64_t n, int64_t K, const int32_t *__restrict__ p, const double *__restrict__ X,
-                                                        double *__restrict__ W) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * K) return;
-    const int64_t i = t / K, c = t - i * K;
-    W[(p ? (int64_t)p[i] : i) * K + c] = X[t];
-}
-
-// X[i, :] = W[p[i], :], NaN in the columns of a member that broke down
-__global__ __launch_bounds__(256) void k_slb_permute_out(int64_t n, int64_t K, int32_t r, const int32_t *__restrict__ p,
-                                                         const int *__restrict__ flags, const double *__restrict__ W,
-                                                         double *__restrict__ X) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * K) return;
-    const int64_t i = t / K, c = t - i * K;
-    const bool ok = flags[3 * (c / r)] == WALK_NONE;
-    X[t] = ok ? W[(p ? (int64_t)p[i] : i) * K + c] : __longlong_as_double(0x7ff8000000000000ll);
-}
+// ---- solve: the two sweeps and the permutations are csx_batchsolve.h's (shared with csx_ldl_batch.hip) -----------------------------
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
 
@@ -256,12 +108,6 @@ static SluBatch *slb_get(csx_handle_t h) {
         return nullptr;
     }
     return b;
-}
-
-// the device block of at least `need` doubles behind a vector handle, or null
-static double *slb_block(csx_handle_t h, int64_t need) {
-    Vec *v = vec(h);
-    return v && v->d && v->len >= need ? (double *)v->d : nullptr;
 }
 
 static bool slb_members_ok(const char *who, int64_t B) {
@@ -319,34 +165,11 @@ static int slb_run(SluBatch *b, const double *V, const double *tau, int *ok) {
 }
 
 static int slb_sweep(SluBatch *b, bool rows, const double *val, bool div, int32_t r, double *X) {
-    hipStream_t s = ctx().stream;
     const SluFactor *F = b->F;
     const Csc *L = csc(F->hL);
-    const std::vector<int32_t> &lp = F->level_ptr_h;
-    const int64_t K = (int64_t)b->B * r, lnz = F->lnz;
-    const size_t nl = F->schedule.size();
-    for (size_t t = 0; t < nl; t++) {
-        const LevelLaunch &Ln = F->schedule[rows ? t : nl - 1 - t];
-        if (Ln.wide) {
-            const int32_t cnt = lp[(size_t)Ln.l0 + 1] - lp[(size_t)Ln.l0];
-            const unsigned blocks = (unsigned)(((int64_t)cnt * K + SLB_THREADS - 1) / SLB_THREADS);
-            const int32_t *cols = F->level_cols.get() + lp[(size_t)Ln.l0];
-            if (rows)
-                hipLaunchKernelGGL(k_slb_level<true>, dim3(blocks), dim3(SLB_THREADS), 0, s, cols, cnt, K, r, lnz, L->p, L->i,
-                                   F->rp.get(), F->rc.get(), F->rpos.get(), val, div ? 1 : 0, X);
-            else
-                hipLaunchKernelGGL(k_slb_level<false>, dim3(blocks), dim3(SLB_THREADS), 0, s, cols, cnt, K, r, lnz, L->p, L->i,
-                                   F->rp.get(), F->rc.get(), F->rpos.get(), val, div ? 1 : 0, X);
-        } else if (rows) {
-            hipLaunchKernelGGL(k_slb_run<true>, dim3((unsigned)b->B), dim3(64 * SLB_RUN_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(),
-                               Ln.l0, Ln.l1, K, r, lnz, L->p, L->i, F->rp.get(), F->rc.get(), F->rpos.get(), val, div ? 1 : 0, X);
-        } else {
-            hipLaunchKernelGGL(k_slb_run<false>, dim3((unsigned)b->B), dim3(64 * SLB_RUN_WAVES), 0, s, F->level_cols.get(), F->level_ptr.get(),
-                               Ln.l0, Ln.l1, K, r, lnz, L->p, L->i, F->rp.get(), F->rc.get(), F->rpos.get(), val, div ? 1 : 0, X);
-        }
-    }
-    CSX_LAUNCH_CHECK();
-    return CSX_OK;
+    if (!L) return CSX_EINVAL;
+    const BatchPattern P = {L->p, L->i, F->rp.get(), F->rc.get(), F->rpos.get(), F->n, F->lnz, b->B};
+    return batch_sweep(F, P, rows, val, div, nullptr, r, X);
 }
 
 static int slb_alloc(SluFactor *F, csx_handle_t hF, int32_t B, std::unique_ptr<SluBatch> *out) {
@@ -389,7 +212,7 @@ extern "C" int csx_slu_batch_factor(csx_handle_t hF, csx_handle_t hV, int32_t B,
     if (!F || !out || !ok) return CSX_EINVAL;
     *out = 0;
     if (!slb_members_ok("csx_slu_batch_factor", B)) return CSX_EINVAL;
-    const double *V = slb_block(hV, (int64_t)F->anz * B);
+    const double *V = batch_block(hV, (int64_t)F->anz * B);
     if (!V) {
         set_error("csx_slu_batch_factor: V is not a block of nnz(A) x B = %lld x %d doubles", (long long)F->anz, (int)B);
         return CSX_EINVAL;
@@ -405,7 +228,7 @@ extern "C" int csx_slu_batch_refactor(csx_handle_t h, csx_handle_t hV, const dou
     CSX_TRY(require_ready());
     SluBatch *b = slb_get(h);
     if (!b || !ok) return CSX_EINVAL;
-    const double *V = slb_block(hV, (int64_t)b->F->anz * b->B);
+    const double *V = batch_block(hV, (int64_t)b->F->anz * b->B);
     if (!V) {
         set_error("csx_slu_batch_refactor: V is not a block of nnz(A) x B = %lld x %d doubles", (long long)b->F->anz, (int)b->B);
         return CSX_EINVAL;
@@ -418,7 +241,7 @@ extern "C" int csx_slu_batch_norm1(csx_handle_t hF, csx_handle_t hV, int32_t B, 
     SluFactor *F = (SluFactor *)get(hF, K_SLUFACTOR);
     if (!F || !out) return CSX_EINVAL;
     if (!slb_members_ok("csx_slu_batch_norm1", B)) return CSX_EINVAL;
-    const double *V = slb_block(hV, (int64_t)F->anz * B);
+    const double *V = batch_block(hV, (int64_t)F->anz * B);
     if (!V) {
         set_error("csx_slu_batch_norm1: V is not a block of nnz(A) x B = %lld x %d doubles", (long long)F->anz, (int)B);
         return CSX_EINVAL;
@@ -443,11 +266,11 @@ extern "C" int csx_slu_batch_solve(csx_handle_t h, csx_handle_t hX, int32_t r, i
     if (!b || r < 1) return CSX_EINVAL;
     const SluFactor *F = b->F;
     const int64_t n = F->n, K = (int64_t)b->B * r;
-    if (K > 0x7fffffffll / WALK_WAVES || n * K > 0x7fffffffll * SLB_THREADS) {   // (a walker counts rows x r in 32 bits)
+    if (!batch_solve_fits(n, K)) {
         set_error("csx_slu_batch_solve: B r = %lld columns are more than one launch takes", (long long)K);
         return CSX_EINVAL;
     }
-    double *X = slb_block(hX, n * K);
+    double *X = batch_block(hX, n * K);
     if (!X) {
         set_error("csx_slu_batch_solve: X is not a block of n x B r = %lld x %lld doubles", (long long)n, (long long)K);
         return CSX_EINVAL;

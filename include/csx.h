@@ -1239,6 +1239,51 @@ int csx_slu_batch_stats(csx_handle_t batch, double *out);
 int csx_slu_batch_member(csx_handle_t batch, int32_t m, double *Lx, double *Utx);
 int csx_slu_batch_limits(int32_t *out);
 
+/* ---- many symmetric value sets on the analysis of one csx_ldl_factor (csx_ldl_batch.hip) ----
+ * The LDL' counterpart of the batch above: K - sigma_j M over shifts, quasi-definite KKT systems over scenarios.  A batch BORROWS
+ * the analysis of a factor F of csx_ldl_factor (pattern, row view, entry map, height levels, launch schedule, permutation; a
+ * factor of csx_schur_factor is refused with CSX_EINVAL and a text) and owns B value sets: L.x of every member (B x lnz doubles),
+ * its pivots d (B x n), flags, statistics and threshold.  F must outlive the batch (every call checks that F's handle still
+ * resolves and returns CSX_EINVAL with a text otherwise); F's own L.x, d, scratch and counters are never written.  The members
+ * are independent: every one's L.x and d are byte-equal to csx_ldl_host of its values alone.  All members go through F's launch
+ * schedule together: one launch per entry of it whatever B is.  There is NO scratch-then-commit: a member whose factorisation
+ * breaks down is marked failed (ok[m] = 0) and its values mean nothing until a refactor mends it; it disturbs no other member.
+ * V: a device vector holding an nnz(A) x B block, row-major: entry q of member m (A's storage order) at V[q * B + m]; read as
+ *   csx_ldl_factor reads A (entries with row <= column, of duplicates the last).
+ * B: 1 .. limits[0]; a larger B is CSX_EINVAL with a text (split the family into several batches).
+ * csx_ldl_batch_factor: a NEW batch handle (csx_free) with every member factored; tau: B thresholds (each >= 0) or NULL (none);
+ *   ok: B ints.
+ * csx_ldl_batch_refactor: the same on the batch's own arrays (B is fixed); a member that failed before is computed afresh.
+ * csx_ldl_batch_norm1: out[m] = |S_m|_1 of the symmetric matrix the factorisation sees, by csx_norm1_sym's rule (per row r first
+ *   the entries of stored column r with row <= r in storage order, then the entries of row r with column > r in ascending
+ *   (column, position), one sequential rounded sum; the maximum over the bit patterns of fabs of the sums, a NaN above inf): the
+ *   very double csx_norm1_sym returns for member m alone.  The row view of A's pattern is made on the first call on F and kept.
+ * csx_ldl_batch_solve: X a device vector holding an n x (B r) block, row-major; columns m r .. m r + r - 1 belong to member m and
+ *   are overwritten with A_m^-1 b in the exact order: W[pinv[i], :] = X[i, :], cs_lsolve(L), / d, cs_ltsolve(L),
+ *   X[i, :] = W[pinv[i], :], over F's height levels by the sweeps of csx_slu_batch_solve --
+ *     ascending levels:   x_j = ((x_j - l1 x_k1) - l2 x_k2) - ... over the entries (j, k) of row j of L, k ascending
+ *     descending levels:  s = x_j / d_j, then ((s - l1 x_i1) - l2 x_i2) - ... over column j's stored entries below the diagonal
+ *   The division by D has no pass of its own: it opens row j's backward chain, which reads only finished x_i, i > j, so the bits
+ *   are those of the three steps one after the other.  Every column is byte-equal to the single factor's solve in the exact
+ *   order; two launches per entry of F's schedule for any B.  The columns of a failed member are filled with NaN; a NaN or inf
+ *   in a right-hand side stays in its column.
+ * csx_ldl_batch_info: shared[8] as csx_slu_batch_info's; members[5 B] = per member: perturbed pivots, the smallest broken column
+ *   or -1, columns updated in place, positive pivots, negative pivots (the inertia, by Sylvester's law).
+ * csx_ldl_batch_stats: out[3 B] = per member min |d|, max |d|, max |l| off the diagonal.
+ * csx_ldl_batch_member: L.x (lnz doubles) and d (n doubles) of member m into host arrays.
+ * csx_ldl_batch_d: the pivots of all members, B x n doubles member-major, in one download.
+ * csx_ldl_batch_limits: out[6] = csx_slu_batch_limits' six constants (the level walk and the sweeps are shared).  No device or
+ *   factor needed. */
+int csx_ldl_batch_factor(csx_handle_t F, csx_handle_t V, int32_t B, const double *tau, csx_handle_t *batch, int *ok);
+int csx_ldl_batch_refactor(csx_handle_t batch, csx_handle_t V, const double *tau, int *ok);
+int csx_ldl_batch_norm1(csx_handle_t F, csx_handle_t V, int32_t B, double *out);
+int csx_ldl_batch_solve(csx_handle_t batch, csx_handle_t X, int32_t r);
+int csx_ldl_batch_info(csx_handle_t batch, int64_t *shared, int64_t *members);
+int csx_ldl_batch_stats(csx_handle_t batch, double *out);
+int csx_ldl_batch_member(csx_handle_t batch, int32_t m, double *Lx, double *d);
+int csx_ldl_batch_d(csx_handle_t batch, double *out);
+int csx_ldl_batch_limits(int32_t *out);
+
 /* ---- sparse Householder QR of a matrix in one connected piece, on the device (csx_hqr.hip) ----
  * A (m-by-n, m >= n, values) with cs_sqr's analysis of A(:, q): q (column order, n entries, or null), parent (column
  * elimination tree), pinv (row permutation, rows of A to 0 .. m2-1), leftmost (m entries), m2 (rows including fictitious ones).
