@@ -124,6 +124,7 @@ _PROTOS = {
     "csx_updown": [H, C.c_int, C.c_int32, _i32p, _f64p, _i32p, C.POINTER(C.c_int)],
     "csx_updown_block": [H, H, _i32p, _i32p, C.c_int, _i32p],
     "csx_updown_block_info": [_i32p, _i32p, _i32p, _f64p],
+    "csx_updown_block_classes": [_i32p, _i32p],
     "csx_chol_inverse": [H, C.POINTER(H)],
     "csx_chol_inverse_info": [_i32p, _i32p, C.POINTER(C.c_int64), _f64p],
     "csx_csc_diag": [H, H],

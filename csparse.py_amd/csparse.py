@@ -1528,8 +1528,11 @@ def _updown_block_call(L, sg, C, parent, flags):
                 L._x[:nnz] = x[:nnz].tolist()
     ch, uc, gr, ms = _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_int32(0), _csx.C.c_double(0.0)
     _csx.check(_csx.lib().csx_updown_block_info(ch, uc, gr, ms), "csx_updown_block_info")
+    cl, rp = (_csx.C.c_int32 * 4)(), _csx.C.c_int32(0)
+    _csx.check(_csx.lib().csx_updown_block_classes(cl, rp), "csx_updown_block_classes")
     _UPDOWN_INFO[0] = {"columns": C.n, "applied": a, "chunks": ch.value, "union_columns": uc.value, "groups": gr.value,
-                       "kernel_ms": ms.value, "wall_ms": 1e3 * (time.perf_counter() - t0)}
+                       "kernel_ms": ms.value, "wall_ms": 1e3 * (time.perf_counter() - t0), "classes": list(cl),
+                       "replayed": rp.value}
     return a
 
 
@@ -1555,7 +1558,7 @@ def updown_block(L, sigma, C, parent=None):
     sg = _updown_sigma(sigma, k)
     if k == 0:
         _UPDOWN_INFO[0] = {"columns": 0, "applied": 0, "chunks": 0, "union_columns": 0, "groups": 0, "kernel_ms": 0.0,
-                           "wall_ms": 0.0}
+                           "wall_ms": 0.0, "classes": [0, 0, 0, 0], "replayed": 0}
         return 0
     if not _meta(C)[1]:
         raise TypeError("'NoneType' object is not subscriptable")
@@ -1564,7 +1567,8 @@ def updown_block(L, sigma, C, parent=None):
 
 def updown_info():
     """the last updown_block's (or cholsol_factor update / downdate's) columns, applied, chunks, union columns, groups,
-    kernel ms and wall ms"""
+    kernel ms and wall ms; classes[(block == 256) + 2 * (W in LDS)] = the groups its first pass launched in each launch
+    class, replayed = 1 when a failing downdate made the chunks run again"""
     return dict(_UPDOWN_INFO[0]) if _UPDOWN_INFO[0] is not None else None
 
 

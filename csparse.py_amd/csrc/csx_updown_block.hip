@@ -359,6 +359,8 @@ struct UdChunk {
 
 struct UdInfo {
     int32_t chunks = 0, union_columns = 0, groups = 0;
+    int32_t classes[4] = {0, 0, 0, 0};   // groups launched in the first pass, by (block == 256) + 2 * (W in LDS)
+    int32_t replayed = 0;                // 1 when the [0, tf] replay ran
     double kernel_ms = 0.0;
 };
 UdInfo g_ud_info;
@@ -521,6 +523,7 @@ int ud_build_chunk(UdChunk &ch, int32_t s, const std::vector<std::vector<int32_t
             return (int64_t)groups[(size_t)a].ucnt * groups[(size_t)a].nterm > (int64_t)groups[(size_t)b].ucnt * groups[(size_t)b].nterm;
         });
         ch.launches.push_back({(int32_t)glist.size(), (int32_t)mine.size(), block, lds ? lds_bytes : 0});
+        g_ud_info.classes[cls] += (int32_t)mine.size();
         glist.insert(glist.end(), mine.begin(), mine.end());
     }
     CSX_TRY(upload(ch.ucol, s_ucol));
@@ -654,6 +657,7 @@ extern "C" int csx_updown_block(csx_handle_t hL, csx_handle_t hC, const int32_t 
     } else if (tf != INT_MAX) {
         *applied = tf;
         if (!(flags & 1)) {                               // the loop's partial state: terms [0, tf] again, tf stopping where it stops
+            g_ud_info.replayed = 1;
             CSX_TRY(upload(tfail, tfail0));
             CSX_HIP(hipMemcpyAsync(fail_min, &flags0[2], sizeof(int), hipMemcpyHostToDevice, s));
             for (int32_t c = 0; c < nchunks; c++) {
@@ -683,5 +687,12 @@ extern "C" int csx_updown_block_info(int32_t *chunks, int32_t *union_columns, in
     if (union_columns) *union_columns = g_ud_info.union_columns;
     if (groups) *groups = g_ud_info.groups;
     if (kernel_ms) *kernel_ms = g_ud_info.kernel_ms;
+    return CSX_OK;
+}
+
+extern "C" int csx_updown_block_classes(int32_t counts[4], int32_t *replayed) {
+    if (counts)
+        for (int c = 0; c < 4; c++) counts[c] = g_ud_info.classes[c];
+    if (replayed) *replayed = g_ud_info.replayed;
     return CSX_OK;
 }

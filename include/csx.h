@@ -566,9 +566,14 @@ int csx_updown(csx_handle_t L, int sigma, int32_t cnz, const int32_t *Ci, const 
  *   changed); -2 parent is not L's elimination tree (nothing changed).  CSX_EINVAL for a row out of range, a sigma other than
  *   +1 / -1, C->m != n, or an L that is not Cholesky-shaped along the paths (nothing changed).
  * csx_updown_block_info: the last call's chunks (64 terms of a tree per chunk), union columns and groups (trees, summed over
- *   the chunks) and the time of its block kernels. */
+ *   the chunks) and the time of its block kernels.
+ * csx_updown_block_classes: the route of the last call.  counts[c] = the groups its first pass launched in class
+ *   c = (block == 256) + 2 * (W in LDS), summed over the chunks: a tree runs on 256 lanes when its longest union column
+ *   (diagonal included) has more than 64 entries, with W in LDS when ucnt * nterm * 8 <= 60 KB.  *replayed = 1 when a
+ *   failing downdate made the chunks run again with terms [0, t] (never with flag 1). */
 int csx_updown_block(csx_handle_t L, csx_handle_t C, const int32_t *sigma, const int32_t *parent, int flags, int32_t *applied);
 int csx_updown_block_info(int32_t *chunks, int32_t *union_columns, int32_t *groups, double *kernel_ms);
+int csx_updown_block_classes(int32_t counts[4], int32_t *replayed);
 
 /* sparseinv: the entries of inv(L L') on the pattern of the device Cholesky factor L (square, values,
  * every column non-empty with its diagonal first, positive and finite, rows strictly ascending: cs_chol's), by the Takahashi

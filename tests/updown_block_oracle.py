@@ -11,7 +11,8 @@
   [0, t] only.
 
 updown_block(L, sigma, C, parent, all_or_nothing) changes the oracle `cs` L in place and returns the number of columns applied
-in full; tests/test_updown_block_cpu.py holds it byte-equal to the loop of csparse_oracle.cs_updown."""
+in full; tests/test_updown_block_cpu.py holds it byte-equal to the loop of csparse_oracle.cs_updown.  schedule(L, C, parent)
+models the launch rule (chunks, trees, union columns, masks, the four launch classes) for the cases of tests/updown_cases.py."""
 from math import sqrt
 
 
@@ -135,6 +136,61 @@ def updown_block(L, sigma, C, parent=None, all_or_nothing=False):
     if not all_or_nothing:
         _run(L, sig, cols, trees, paths, t_fail, [None] * len(trees), None)
     return t_fail
+
+
+# The launch rule of csx_updown_block.hip, restated here on purpose: a test that leans on these constants has to be looked
+# at again when someone moves one of them in the kernel file.
+UD_CHUNK = 64           # terms of a tree per chunk, one bit of the 64-bit mask each
+UD_LDS_W = 60 * 1024    # bytes of W (ucnt x nterm doubles) a workgroup keeps in LDS
+UD_WAVE = 64            # a tree whose longest union column (diagonal included) is longer than this runs on 256 lanes
+
+
+def schedule(L, C, parent=None):
+    """A model of the schedule the device call builds for (L, C): one entry per chunk, {"groups": [(nterm, ucnt, maxlen, cls)
+    per tree of the chunk, trees by ascending root], "masks": {union column: the 64-bit mask of the chunk's terms on it}}.
+    Chunk s holds ranks [64 s, 64 s + 64) of each tree's terms (ascending), empty columns of C dropped; ucnt = the union of
+    the terms' paths, maxlen = its longest column, diagonal included; cls = (256 lanes: maxlen > 64) + 2 * (W in LDS:
+    ucnt * nterm * 8 <= 61440), the index of csx_updown_block_classes."""
+    if parent is None:
+        parent = tree_of(L)
+    paths = {}
+    for t in range(C.n):
+        rows = C.i[C.p[t]:C.p[t + 1]]
+        if rows:
+            paths[t] = _path(min(rows), parent)
+    by_root = {}
+    for t in sorted(paths):
+        by_root.setdefault(paths[t][-1], []).append(t)
+    trees = [by_root[r] for r in sorted(by_root)]
+    out = []
+    nchunks = max([(len(tr) + UD_CHUNK - 1) // UD_CHUNK for tr in trees] or [0])
+    for s in range(nchunks):
+        groups, masks = [], {}
+        for tr in trees:
+            terms = tr[UD_CHUNK * s:UD_CHUNK * s + UD_CHUNK]
+            if not terms:
+                continue
+            m = {}
+            for b, t in enumerate(terms):
+                for j in paths[t]:
+                    m[j] = m.get(j, 0) | (1 << b)
+            nterm, ucnt = len(terms), len(m)
+            maxlen = max(L.p[j + 1] - L.p[j] for j in m)
+            cls = (1 if maxlen > UD_WAVE else 0) + (2 if ucnt * nterm * 8 <= UD_LDS_W else 0)
+            groups.append((nterm, ucnt, maxlen, cls))
+            masks.update(m)                           # trees share no column
+        out.append({"groups": groups, "masks": masks})
+    return out
+
+
+def schedule_facts(sched):
+    """what updown_info() reports of a schedule: chunks, groups and union columns (summed over the chunks), classes[cls]"""
+    classes = [0, 0, 0, 0]
+    for ch in sched:
+        for g in ch["groups"]:
+            classes[g[3]] += 1
+    return {"chunks": len(sched), "groups": sum(len(ch["groups"]) for ch in sched),
+            "union_columns": sum(len(ch["masks"]) for ch in sched), "classes": classes}
 
 
 def loop(L, sigma, C, parent, mod):
