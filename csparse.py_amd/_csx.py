@@ -173,6 +173,7 @@ _PROTOS = {
     "csx_btf_solve": [H, H, H, C.c_int32],
     "csx_btf_solve_trans": [H, H, H, C.c_int32],
     "csx_btf_info": [H, C.POINTER(C.c_int64)],
+    "csx_btf_limits": [_i32p],
     "csx_btf_refactor": [H, H, H, H, C.POINTER(C.c_int), _f64p, C.POINTER(C.c_int64)],
     "csx_btf_refactor_dx": [H, _f64p],
     "csx_lu_refactor_plan": [H, H, H, _i32p, _i32p, C.POINTER(H)],
@@ -746,6 +747,17 @@ def block_limits():
     out = (C.c_int32 * len(BLOCK_LIMITS))()
     check(load().csx_block_limits(out), "csx_block_limits")
     return {name: int(out[k]) for k, name in enumerate(BLOCK_LIMITS)}
+
+
+BTF_LIMITS = ("BTF_SMALL", "RF_MAX", "RF_WAVES", "RHS_TILE", "TERM_CHUNK", "TERM_GROUP")
+
+
+def btf_limits():
+    """the cuts and strides of btf_factor's solve kernel and of the refactor kernel, asked of the library; no GPU needed: a dict
+    by the names of BTF_LIMITS (include/csx.h: csx_btf_limits)"""
+    out = (C.c_int32 * len(BTF_LIMITS))()
+    check(load().csx_btf_limits(out), "csx_btf_limits")
+    return {name: int(out[k]) for k, name in enumerate(BTF_LIMITS)}
 
 
 def prim_components(n, p, i, skip_first=0, skip_last=0, order=0):

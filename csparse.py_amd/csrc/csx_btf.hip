@@ -20,6 +20,7 @@
 namespace csx {
 
 constexpr int BTF_SMALL = 96;   // rows of the largest block solved with its tile in LDS (csx_lu_blocks' limit)
+constexpr int BTF_TILE = 64;    // right-hand sides of a tile of k_btf_small: one per lane; a row of the LDS tile
 
 struct BtfLarge {   // a block of more than BTF_SMALL rows: its own L and U (local indices) and exact triangular plans of them
     BtfLarge() = default;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) void k_btf_strip(int32_t n, int upper, const i
         const int32_t src = TRANS ? (diag_first ? a + 1 + t : a + t) : (upper ? e - 1 - t : a + t);
         const int32_t j = Ti[src];
         if (above ? (j <= i || j >= r1) : (j >= i || j < r0)) *bad = 1;
-        Pi[a - i + t] = (j - r0) * 64;
+        Pi[a - i + t] = (j - r0) * BTF_TILE;
         Px[a - i + t] = Tx[src];
     }
 }
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
     const int lane = threadIdx.x;
     const int32_t b = blocks[blockIdx.x];
     const int32_t r0 = r[b], nr = r[b + 1] - r0;
-    const int32_t col = (int32_t)blockIdx.y * 64 + lane;
+    const int32_t col = (int32_t)blockIdx.y * BTF_TILE + lane;
     const bool on = col < k;
     // c = b(p), minus the F terms (the z they read is final: lower levels), scattered by pinv into the tile
     // (TRANS: c = b(q) minus F(:, j)' w, w final: higher levels; slot t)
@@ -291,9 +292,9 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
         const int32_t i = r0 + t;
         double acc = on ? B[(int64_t)p[i] * k + col] : 0.0;
         const int32_t qe = Fp[i + 1];
-        for (int32_t q = Fp[i]; q < qe; q += 64) {
+        for (int32_t q = Fp[i]; q < qe; q += TERM_CHUNK) {
             const TermRegs T = load_terms(Fi, Fx, q, qe, lane);
-            const int ulim = min(64, qe - q);
+            const int ulim = min(TERM_CHUNK, qe - q);
             for (int u = 0; u < ulim; u++) {
                 const int32_t j = __builtin_amdgcn_readlane(T.i, u);
                 const double z = on ? W[(int64_t)j * k + col] : 0.0;
@@ -301,32 +302,32 @@ __global__ __launch_bounds__(64) void k_btf_small(const int32_t *__restrict__ bl
                 acc = acc - prod;
             }
         }
-        X[(TRANS ? t : pinv[i] - r0) * 64 + lane] = acc;
+        X[(TRANS ? t : pinv[i] - r0) * BTF_TILE + lane] = acc;
     }
     // cs_lsolve on the block: rows ascending, terms in ascending column (TRANS: cs_utsolve, terms in storage order)
     for (int32_t t = 0; t < nr; t++) {
         const int32_t i = r0 + t;
-        double acc = X[t * 64 + lane];
+        double acc = X[t * BTF_TILE + lane];
         const int32_t qe = Lp[i + 1];
-        for (int32_t q = Lp[i]; q < qe; q += 64) {
+        for (int32_t q = Lp[i]; q < qe; q += TERM_CHUNK) {
             const TermRegs T = load_terms(Li, Lx, q, qe, lane);
-            acc = apply_terms(acc, T, 0, min(64, qe - q), X, lane);
+            acc = apply_terms(acc, T, 0, min(TERM_CHUNK, qe - q), X, lane);
         }
-        X[t * 64 + lane] = acc / Ld[i];
+        X[t * BTF_TILE + lane] = acc / Ld[i];
     }
     // cs_usolve on the block: rows descending, terms in descending column (TRANS: cs_ltsolve, terms in storage order)
     for (int32_t t = nr - 1; t >= 0; t--) {
         const int32_t i = r0 + t;
-        double acc = X[t * 64 + lane];
+        double acc = X[t * BTF_TILE + lane];
         const int32_t qe = Up[i + 1];
-        for (int32_t q = Up[i]; q < qe; q += 64) {
+        for (int32_t q = Up[i]; q < qe; q += TERM_CHUNK) {
             const TermRegs T = load_terms(Ui, Ux, q, qe, lane);
-            acc = apply_terms(acc, T, 0, min(64, qe - q), X, lane);
+            acc = apply_terms(acc, T, 0, min(TERM_CHUNK, qe - q), X, lane);
         }
-        X[t * 64 + lane] = acc / Ud[i];
+        X[t * BTF_TILE + lane] = acc / Ud[i];
     }
     if (on)
-        for (int32_t t = 0; t < nr; t++) W[(int64_t)(r0 + t) * k + col] = X[t * 64 + lane];
+        for (int32_t t = 0; t < nr; t++) W[(int64_t)(r0 + t) * k + col] = X[t * BTF_TILE + lane];
 }
 
 // The rows of a large block: W(pinv(i)) = b(p(i)) - F(i, :) z, one thread per (row, right-hand side)
@@ -359,11 +360,11 @@ __global__ __launch_bounds__(256) void k_btf_out(int32_t n, const int32_t *__res
 
 static int btf_solve(BtfPlan *P, const double *B, double *W, double *Bout, int32_t k) {
     hipStream_t s = ctx().stream;
-    const unsigned tiles = (unsigned)((k + 63) / 64);
+    const unsigned tiles = (unsigned)((k + BTF_TILE - 1) / BTF_TILE);
     for (int32_t l = 0; l < P->nlevels; l++) {
         const int32_t a = P->small_ptr[l], e = P->small_ptr[l + 1];
         if (e > a) {
-            const size_t lds = (size_t)P->small_rows[l] * 64 * sizeof(double);
+            const size_t lds = (size_t)P->small_rows[l] * BTF_TILE * sizeof(double);
             hipLaunchKernelGGL(k_btf_small<false>, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->p,
                                P->pinv, P->Ft.p, P->Ft.i, P->Ft.x, P->Lp, P->Li, P->Lx, P->Ld, P->Up, P->Ui, P->Ux, P->Ud, B,
                                W, k);
@@ -433,11 +434,11 @@ static int btf_trans_plan(BtfPlan *P) {
 
 static int btf_solve_trans(BtfPlan *P, const double *B, double *W, double *Bout, int32_t k) {
     hipStream_t s = ctx().stream;
-    const unsigned tiles = (unsigned)((k + 63) / 64);
+    const unsigned tiles = (unsigned)((k + BTF_TILE - 1) / BTF_TILE);
     for (int32_t l = P->nlevels - 1; l >= 0; l--) {
         const int32_t a = P->small_ptr[l], e = P->small_ptr[l + 1];
         if (e > a) {
-            const size_t lds = (size_t)P->small_rows[l] * 64 * sizeof(double);
+            const size_t lds = (size_t)P->small_rows[l] * BTF_TILE * sizeof(double);
             hipLaunchKernelGGL(k_btf_small<true>, dim3((unsigned)(e - a), tiles), dim3(64), lds, s, P->small + a, P->r, P->q,
                                P->pinv, P->Fcp, P->Fci, P->Fcx, P->UTp, P->UTi, P->UTx, P->UTd, P->LTp, P->LTi, P->LTx, P->LTd,
                                B, W, k);
@@ -763,6 +764,14 @@ extern "C" int csx_btf_solve_trans(csx_handle_t h, csx_handle_t hB, csx_handle_t
     if (B->len < need || W->len < need) return CSX_EINVAL;
     CSX_TRY(btf_trans_plan(P));
     return btf_solve_trans(P, (const double *)B->d, (double *)W->d, (double *)B->d, nrhs);
+}
+
+// the cuts and strides of the btf solve and of the refactor kernel, for the tests (no device needed)
+extern "C" int csx_btf_limits(int32_t *out) {
+    if (!out) return CSX_EINVAL;
+    const int32_t v[6] = {BTF_SMALL, RF_MAX, RF_WAVES, BTF_TILE, TERM_CHUNK, TERM_GROUP};
+    for (int k = 0; k < 6; k++) out[k] = v[k];
+    return CSX_OK;
 }
 
 extern "C" int csx_btf_info(csx_handle_t h, int64_t *info) {

@@ -402,6 +402,8 @@ int col_block_device(const Csc *A, int32_t first, int32_t count, Csc *C);      /
 // The schedule of a refactor of cs_lu's L, U with new values: A in the factorisation's column order (pattern), pinv (host),
 // gid (host: the group of every position; empty = the connected components of L + U).  refactor_run writes the new values
 // into Lx, Ux (device scratch) and synchronises; refactor_counts: columns on the device / on the host.
+constexpr int RF_MAX = 96;    // rows of the largest group refactored on the device (csx_lu_blocks' and btf's limit)
+constexpr int RF_WAVES = 4;   // waves per workgroup, each on a group of its own
 int refactor_build(const Csc *A, const int32_t *pinv, const Csc *L, const Csc *U, const std::vector<int32_t> &gid,
                    Refactor **out);
 int refactor_run(Refactor *R, const Csc *A, const double *Ax, const Csc *L, const Csc *U, double *Lx, double *Ux, int *ok,

@@ -21,8 +21,7 @@ int lu_refactor_columns(int32_t n, const int32_t *cols, int32_t ncols, const int
                         const double *Ax, const int32_t *pinv, const int32_t *Lp, const int32_t *Li, double *Lx,
                         const int32_t *Up, const int32_t *Ui, double *Ux, double *x, int *ok, double *ratio);  // csx_host.cpp
 
-constexpr int RF_MAX = 96;    // rows of the largest group refactored on the device (csx_lu_blocks' and btf's limit)
-constexpr int RF_WAVES = 4;   // waves per workgroup, each on a group of its own
+// RF_MAX, RF_WAVES: csx_internal.h (csx_btf_limits hands them out)
 
 struct Refactor {
     int32_t n = 0, ngroups = 0;

@@ -46,8 +46,11 @@ inline int tile_waves_per_workgroup(size_t per_wave, int maxw) {
     return best;
 }
 
+constexpr int TERM_CHUNK = 64;  // terms load_terms brings in at a time: one per lane
+constexpr int TERM_GROUP = 8;   // terms apply_terms reads from LDS before it subtracts them in order
+
 #pragma clang fp contract(off)
-struct TermRegs {  // up to 64 terms of one row, one per lane
+struct TermRegs {  // up to TERM_CHUNK terms of one row, one per lane
     int32_t i;
     double v;
 };
@@ -71,14 +74,14 @@ __device__ __forceinline__ double bcast_f64(double v, int src) {
 __device__ __forceinline__ double apply_terms(double acc, const TermRegs &t, int u0, int u1, const double *X,
                                               int lane) {
     int u = u0;
-    for (; u + 8 <= u1; u += 8) {  // 8 LDS reads in flight, then the (inherently serial) subtract chain
-        double xx[8], vv[8];
+    for (; u + TERM_GROUP <= u1; u += TERM_GROUP) {  // 8 LDS reads in flight, then the (inherently serial) subtract chain
+        double xx[TERM_GROUP], vv[TERM_GROUP];
 #pragma unroll
-        for (int k = 0; k < 8; k++) xx[k] = X[__builtin_amdgcn_readlane(t.i, u + k) + lane];
+        for (int k = 0; k < TERM_GROUP; k++) xx[k] = X[__builtin_amdgcn_readlane(t.i, u + k) + lane];
 #pragma unroll
-        for (int k = 0; k < 8; k++) vv[k] = bcast_f64(t.v, u + k) * xx[k];
+        for (int k = 0; k < TERM_GROUP; k++) vv[k] = bcast_f64(t.v, u + k) * xx[k];
 #pragma unroll
-        for (int k = 0; k < 8; k++) acc = acc - vv[k];
+        for (int k = 0; k < TERM_GROUP; k++) acc = acc - vv[k];
     }
     for (; u < u1; u++) {
         const double p = bcast_f64(t.v, u) * X[__builtin_amdgcn_readlane(t.i, u) + lane];

@@ -825,6 +825,11 @@ int csx_btf_solve(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t 
  *   diagonal first, or an index leaves its block or its side); the same kernels as csx_btf_solve, one launch per level. */
 int csx_btf_solve_trans(csx_handle_t plan, csx_handle_t B, csx_handle_t work, int32_t nrhs);
 int csx_btf_info(csx_handle_t plan, int64_t *info);
+/* For the tests of the btf solve and of the refactor kernel; production code does not call it.  The cuts and strides, without a
+ * device: out[6] = BTF_SMALL (rows of the largest block solved with its tile in LDS), RF_MAX (rows of the largest group
+ * refactored on the device), RF_WAVES (groups of a workgroup of the refactor kernel), the right-hand sides of a tile of the
+ * small-block kernel, the terms of a row program loaded at a time, the terms applied as one group.  CSX_EINVAL: out is NULL. */
+int csx_btf_limits(int32_t *out);
 
 /* ---- refactor: new values, the same pivots (btf_factor / lusol_factor .refactor) -----------------
  * Definition.  Given cs_lu's L, U, pinv of a matrix and new values A2 of the same pattern, column k of the factorisation (in
