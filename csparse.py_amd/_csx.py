@@ -260,6 +260,14 @@ _PROTOS = {
     "csx_hqr_info": [H, C.POINTER(C.c_int64)],
     "csx_hqr_stats": [H, _f64p],
     "csx_hqr_window": [C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "csx_hqr_batch_factor": [H, H, C.c_int32, C.POINTER(H), C.POINTER(C.c_int)],
+    "csx_hqr_batch_refactor": [H, H, C.POINTER(C.c_int)],
+    "csx_hqr_batch_solve": [H, H, H, C.c_int32, C.c_int],
+    "csx_hqr_batch_info": [H, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "csx_hqr_batch_stats": [H, _f64p],
+    "csx_hqr_batch_member": [H, C.c_int32, _f64p, _f64p, _f64p],
+    "csx_hqr_batch_r_diag": [H, _f64p],
+    "csx_hqr_batch_limits": [_i32p],
     "csx_level_schedule": [C.c_int32, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64, _i32p, C.POINTER(C.c_int32)],
     "csx_gmres_limits": [_i32p],
     "csx_gs_work_len": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
@@ -410,6 +418,19 @@ def ldl_batch_limits():
     out = (C.c_int32 * len(SLU_BATCH_LIMITS))()
     check(load().csx_ldl_batch_limits(out), "csx_ldl_batch_limits")
     return {name: int(out[k]) for k, name in enumerate(SLU_BATCH_LIMITS)}
+
+
+HQR_BATCH_LIMITS = SLU_BATCH_LIMITS + ("HAPPLY_LANES", "HAPPLY_MAX_LEVELS")
+
+
+def hqr_batch_limits():
+    """the constants by which a batch of Householder QR value sets cuts members, right-hand sides and grids (csx_hqr_batch.hip on
+    csx_levelwalk.h and csx_batchsolve.h), asked of the library; no GPU needed: slu_batch_limits()'s dict, then HAPPLY_LANES (the
+    columns of X a workgroup of the batched reflection kernels takes, a lane each) and HAPPLY_MAX_LEVELS (more reflection levels
+    than that, or as many as reflections, and one launch walks them all: csx_happly's rule)"""
+    out = (C.c_int32 * len(HQR_BATCH_LIMITS))()
+    check(load().csx_hqr_batch_limits(out), "csx_hqr_batch_limits")
+    return {name: int(out[k]) for k, name in enumerate(HQR_BATCH_LIMITS)}
 
 
 def hqr_window():

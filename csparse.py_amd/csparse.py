@@ -3517,17 +3517,19 @@ _SLU_BATCH_STATS = ("min_abs_d", "max_abs_d", "max_abs_l", "max_abs_u")
 
 
 class _ValueBatch(object):
-    """What _SluBatch and _LdlBatch share: the intake of the values, the thresholds, the run, the solve's block and info().  A
-    batch class names its texts' prefix (_NAME), the prefix of its library calls (_CALLS), its limits and its statistics."""
+    """What _SluBatch, _LdlBatch and _HqrBatch share: the intake of the values, the thresholds, the run, the solve's block and
+    info().  A batch class names its texts' prefix (_NAME), the prefix of its library calls (_CALLS), its limits, its statistics
+    and the integers of its info() (_SHARED of the whole run, _MEMBER per member)."""
 
     _NAME, _CALLS, _STATS = "", "", ()
+    _SHARED, _MEMBER = _SLU_BATCH_SHARED, _SLU_BATCH_MEMBER
     _limits = staticmethod(lambda: {})
 
     def __init__(self, solver, hF, nnz, n, perturb, values):
         self._solver, self._hF, self._nnz, self._n, self._perturb = solver, hF, nnz, n, perturb     # (the solver keeps the factor alive)
         V, self.B = self._values(values, None)
         h, ok = _csx.new_handle(), (_csx.C.c_int * self.B)()
-        _csx.check(self._call("factor")(hF, V.handle, self.B, _csx.pd(self._tau(V)), h, ok), self._CALLS + "_factor")
+        _csx.check(self._call("factor")(hF, V.handle, self.B, *(self._run_args(V) + (h, ok))), self._CALLS + "_factor")
         self._h = h
         self._fin = weakref.finalize(self, _csx.free, h)
         self.ok = np.array(ok[:], dtype=bool)
@@ -3553,7 +3555,18 @@ class _ValueBatch(object):
         most = self._limits()["MAX_MEMBERS"]
         if k > most:
             raise ValueError("%s: %d members, a batch holds at most %d: split the family" % (self._NAME, k, most))
-        return (values if a is None else dvec(a)), k
+        return (self._device_rows(values, k) if a is None else dvec(self._host_rows(a))), k
+
+    def _host_rows(self, a):
+        """the nnz x B numpy block in the storage order of the factored matrix (here: as given)"""
+        return a
+
+    def _device_rows(self, V, k):
+        return V
+
+    def _run_args(self, V):
+        """what a run takes between the values and its results: the members' thresholds (a factorisation without one: nothing)"""
+        return (_csx.pd(self._tau(V)),)
 
     def _tau(self, V):
         if self._perturb == 0.0:
@@ -3565,7 +3578,7 @@ class _ValueBatch(object):
     def refactor(self, values):
         V, _ = self._values(values, self.B)
         ok = (_csx.C.c_int * self.B)()
-        _csx.check(self._call("refactor")(self._h, V.handle, _csx.pd(self._tau(V)), ok), self._CALLS + "_refactor")
+        _csx.check(self._call("refactor")(self._h, V.handle, *(self._run_args(V) + (ok,))), self._CALLS + "_refactor")
         self.ok = np.array(ok[:], dtype=bool)
         return self.ok
 
@@ -3597,13 +3610,13 @@ class _ValueBatch(object):
 
     def info(self):
         C = _csx.C
-        shared = (C.c_int64 * len(_SLU_BATCH_SHARED))()
-        per = np.zeros((self.B, len(_SLU_BATCH_MEMBER)), dtype=np.int64)
+        shared = (C.c_int64 * len(self._SHARED))()
+        per = np.zeros((self.B, len(self._MEMBER)), dtype=np.int64)
         st = np.zeros((self.B, len(self._STATS)))
         _csx.check(self._call("info")(self._h, shared, per.ctypes.data_as(C.POINTER(C.c_int64))), self._CALLS + "_info")
         _csx.check(self._call("stats")(self._h, _csx.pd(st)), self._CALLS + "_stats")
-        out = {name: int(v) for name, v in zip(_SLU_BATCH_SHARED, shared)}
-        out.update((name, per[:, k].copy()) for k, name in enumerate(_SLU_BATCH_MEMBER))
+        out = {name: int(v) for name, v in zip(self._SHARED, shared)}
+        out.update((name, per[:, k].copy()) for k, name in enumerate(self._MEMBER))
         out.update((name, st[:, k].copy()) for k, name in enumerate(self._STATS))
         return out
 
@@ -3676,6 +3689,99 @@ class _LdlBatch(_ValueBatch):
             signs[m] = -1.0 if int(np.sum(d[m] < 0.0)) % 2 else 1.0
             logs[m] = math.fsum(np.log(np.abs(d[m])).tolist())
         return signs, logs
+
+
+_HQR_BATCH_SHARED = ("m", "n", "m2", "vnz", "rnz", "levels", "launches", "level_launches", "run_launches", "kernel_us", "B",
+                     "solve_launches")
+_HQR_BATCH_MEMBER = ("breakdown", "long_columns", "zero_diagonals")
+
+
+class _HqrBatch(_ValueBatch):
+    """B value sets on the pattern of one hqrsol_factor, factored together (hqrsol_factor(...).batch(values)):
+    reweighted least squares W_j A, Gauss-Newton Jacobians over scenarios, regularisation sweeps on a stacked [A; lambda_j I].
+    The members share the factor's analysis, column order and launch schedule and go through every launch of it at once; every
+    member's V.x, R.x and beta are byte-equal to csx_hqr_host, that is to hqrsol_factor of that member alone.
+    B: the members.  ok: a numpy bool array, False where a diagonal of a member's R came out non-finite -- there is no commit
+      for a batch, so such a member's values mean nothing (until a refactor mends it) and the others are untouched.
+    refactor(values): new values for all B members (B is fixed) -> the new ok.
+    solve(X, trans=False): X a dvec or a 2-D numpy array of rows_in x (B r), columns m r .. m r + r - 1 belonging to member m ->
+      a NEW dvec / array of rows_out x (B r), X left as it was; the single solver's sequences (first: m >= n, rows m -> n;
+      second: m < n, or trans=True on a square A, rows n -> m of the factored matrix) in the reference's operation order: every
+      column has the bytes of hqrsol_factor(A_m).solve(...) on a list.  The columns of a failed member come back NaN; an exact
+      zero on R's diagonal is no breakdown (ok stays True, info()["zero_diagonals"] counts it) and gives what the single solver
+      gives: ZeroDivisionError, as the reference's division does.  trans=True on a rectangular A: ValueError.
+    member(m) -> (Vx, Rx, beta) as numpy arrays.  logabsdet() -> a numpy array per member, the sum of log |r_kk| correctly
+      rounded (math.fsum) as the single solver's, NaN for a failed member; ValueError for a rectangular A.
+    info(): m, n, m2, vnz, rnz, levels, launches, level_launches, run_launches, kernel_us, B of the whole run and solve_launches of
+      the last solve, and numpy arrays per member: breakdown, long_columns, zero_diagonals, min_abs_r, max_abs_r.
+    Deliberately NOT here: refine, gmres, condest, solve_grad.  The route to them is the single factor:
+    F.refactor(values[:, m])."""
+
+    _NAME, _CALLS, _STATS = "hqrsol_factor.batch", "csx_hqr_batch", ("min_abs_r", "max_abs_r")
+    _SHARED, _MEMBER = _HQR_BATCH_SHARED, _HQR_BATCH_MEMBER
+    _limits = staticmethod(_csx.hqr_batch_limits)
+
+    def __init__(self, solver, hF, nnz, shape, storage_map, values):
+        self._shape, self._storage_map = shape, storage_map      # (A's m and n; None, or the maker of A's order -> A''s)
+        _ValueBatch.__init__(self, solver, hF, nnz, None, 0.0, values)
+
+    def _run_args(self, V):
+        return ()
+
+    # a wide A: the factored matrix is A', and the rows of the value block go into ITS storage order
+
+    def _host_rows(self, a):
+        return a if self._storage_map is None else np.ascontiguousarray(a[self._storage_map()])
+
+    def _device_rows(self, V, k):
+        if self._storage_map is None:
+            return V
+        out = dvec(self._nnz, k)
+        h, keep = _perm_handle(self._storage_map(), self._nnz)
+        try:
+            _csx.check(_csx.lib().csx_permute_vec(h, V.handle, out.handle, self._nnz, k, 0), "csx_permute_vec")
+        finally:
+            _csx.free(keep)
+        return out
+
+    def solve(self, X, trans=False):
+        am, an = self._shape
+        if trans and am != an:
+            raise ValueError("hqrsol_factor: trans=True needs a square matrix")
+        second = bool(trans) or am < an
+        fm, fn = max(am, an), min(am, an)            # the factored matrix: A, or A' for a wide A
+        rows_in, rows_out = (fn, fm) if second else (fm, fn)
+        host = not isinstance(X, dvec)
+        if host and not (isinstance(X, np.ndarray) and X.ndim == 2):
+            raise ValueError("%s.solve: X must be a dvec or a 2-D numpy array" % self._NAME)
+        d = dvec(np.asarray(X, dtype=np.float64)) if host else X
+        if d.n != rows_in or d.k < self.B or d.k % self.B:
+            raise ValueError("%s.solve: X must be %d x (B r) = %d x (%d r)" % (self._NAME, rows_in, rows_in, self.B))
+        out = dvec(rows_out, d.k)
+        _csx.check(self._call("solve")(self._h, d.handle, out.handle, d.k // self.B, 1 if second else 0), self._CALLS + "_solve")
+        return out.numpy().reshape(rows_out, d.k) if host else out
+
+    def member(self, m):
+        m = int(m)
+        if not 0 <= m < self.B:
+            raise ValueError("%s.member: member %d of %d" % (self._NAME, m, self.B))
+        i = self.info()
+        Vx, Rx, beta = np.empty(max(i["vnz"], 1)), np.empty(max(i["rnz"], 1)), np.empty(max(i["n"], 1))
+        _csx.check(self._call("member")(self._h, m, _csx.pd(Vx), _csx.pd(Rx), _csx.pd(beta)), self._CALLS + "_member")
+        return Vx[:i["vnz"]], Rx[:i["rnz"]], beta[:i["n"]]
+
+    def logabsdet(self):
+        am, an = self._shape
+        if am != an:
+            raise ValueError("hqrsol_factor: logabsdet needs a square matrix (least-squares refinement is not offered)")
+        d = np.empty(max(self.B * an, 1))
+        _csx.check(self._call("r_diag")(self._h, _csx.pd(d)), self._CALLS + "_r_diag")
+        d = d[:self.B * an].reshape(self.B, an)
+        logs = np.full(self.B, np.nan)
+        with np.errstate(divide="ignore"):
+            for m in np.flatnonzero(self.ok):
+                logs[m] = math.fsum(np.log(np.abs(d[m])).tolist())
+        return logs
 
 
 def _perm_parity(p):
@@ -4228,7 +4334,10 @@ def hqrsol_factor(A, order=0):
       ValueError for a rectangular one (least-squares refinement is not offered).  logabsdet(): the sum of log |r_kk| (math.fsum),
       square A.  info(): m, n, m2 of the factored matrix, vnz, rnz, levels, launches = level_launches + run_launches of the
       last run, long_columns (updated in place: more slots than the LDS `window`), run_levels, zero_diagonals, breakdown,
-      kernel_us, min_abs_r, max_abs_r, transposed.  factors: .L = V, .U = R, .B = beta; symbolic: cs_sqr's S."""
+      kernel_us, min_abs_r, max_abs_r, transposed.  factors: .L = V, .U = R, .B = beta; symbolic: cs_sqr's S.
+    batch(values): B value sets on A's pattern factored together in one walk of the levels (_HqrBatch): every
+      member's V.x, R.x and beta byte-equal to this factor refactored to that member, batched solves byte-equal to solve() on a
+      list, logabsdet() per member."""
     if not CS_CSC(A) or order not in (0, 1, 2, 3):
         return None
     if not _meta(A)[1]:
@@ -4267,6 +4376,15 @@ def hqrsol_factor(A, order=0):
     hq, keep_q = _perm_handle(q, n)
     hp, keep_p = _perm_handle(pinv, m)
     tmap = []                                        # m < n: A's storage order -> A''s, made by the first refactor with values
+
+    def storage_map():
+        if not tmap:
+            nnz = _meta(A)[0]
+            I = cs_spalloc(A.m, A.n, nnz, True, False)
+            ap, ai = _pattern_np(A)
+            I.p, I.i, I.x = ap.tolist(), (ai.tolist() or [0]), (np.arange(nnz, dtype=np.float64).tolist() or [0.0])
+            tmap.append(np.asarray(cs_transpose(I, True).x[:nnz], dtype=np.int64))
+        return tmap[0]
 
     class _Solver(_Refinable):
         factors, symbolic = N, S
@@ -4324,13 +4442,7 @@ def hqrsol_factor(A, order=0):
                 if isinstance(A2, cs):
                     given = cs_transpose(A2, True)
                 else:
-                    if not tmap:
-                        nnz = _meta(A)[0]
-                        I = cs_spalloc(A.m, A.n, nnz, True, False)
-                        ap, ai = _pattern_np(A)
-                        I.p, I.i, I.x = ap.tolist(), (ai.tolist() or [0]), (np.arange(nnz, dtype=np.float64).tolist() or [0.0])
-                        tmap.append(np.asarray(cs_transpose(I, True).x[:nnz], dtype=np.int64))
-                    given = dvec(A2.numpy().reshape(-1)[tmap[0]])
+                    given = dvec(A2.numpy().reshape(-1)[storage_map()])
             ok = _csx.C.c_int(0)
             _refactor_call(given, lambda h2: lib.csx_hqr_refactor(hF, h2, ok), ok)
             if ok.value == 1:
@@ -4340,6 +4452,14 @@ def hqrsol_factor(A, order=0):
                 self._A2, self._norm = A2, None
                 self._operator_changed()
             return ok.value == 1
+
+        def batch(self, values):
+            """B value sets on A's pattern factored together on this factor's analysis -> an _HqrBatch (its docstring has the
+            rest).  values: a dvec of nnz x B (read, not kept), a 2-D numpy array of that shape, or a list of B value arrays
+            (copied), each in A's storage order (of duplicates the last is taken).  ValueError for another row count, B = 0 or B
+            over the limit.  This factor is not changed and goes on working; it must not be freed before the batch, which
+            holds on to it."""
+            return _HqrBatch(self, hF, _meta(A)[0], (A.m, A.n), None if tall else storage_map, values)
 
         def _square_only(self, what):
             if not square:

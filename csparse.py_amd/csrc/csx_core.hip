@@ -254,6 +254,7 @@ static void free_object(Object &o) {
         case K_SLUFACTOR: destroy((SluFactor *)o.ptr); break;
         case K_SLUBATCH: destroy((SluBatch *)o.ptr); break;
         case K_LDLBATCH: destroy((LdlBatch *)o.ptr); break;
+        case K_HQRBATCH: destroy((HqrBatch *)o.ptr); break;
         case K_HQRFACTOR: destroy((HqrFactor *)o.ptr); break;
         default: break;
     }

@@ -91,7 +91,7 @@ class DevBuf {
     T *p_ = nullptr;
 };
 
-enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR, K_SLUBATCH, K_LDLBATCH };
+enum Kind : int { K_FREE = 0, K_CSC, K_VEC, K_IVEC, K_TRIPLAN, K_CHOLPLAN, K_SHARDPLAN, K_BTFPLAN, K_LUREFPLAN, K_ASMPLAN, K_CHOLREFPLAN, K_MULPLAN, K_ADDPLAN, K_LDLFACTOR, K_SLUFACTOR, K_HQRFACTOR, K_SCHURFACTOR, K_SLUBATCH, K_LDLBATCH, K_HQRBATCH };
 
 struct Csc;
 
@@ -230,8 +230,11 @@ struct SluBatch;      // csx_slu_batch.hip: B value sets on a borrowed SluFactor
 void destroy(SluBatch *p);
 struct LdlBatch;      // csx_ldl_batch.hip: B value sets on a borrowed LdlFactor
 void destroy(LdlBatch *p);
-struct HqrFactor;     // csx_hqr.hip
+struct HqrFactor;     // csx_hqr.h (csx_hqr.hip)
 void destroy(HqrFactor *p);
+struct HqrBatch;      // csx_hqr_batch.hip: B value sets on a borrowed HqrFactor
+void destroy(HqrBatch *p);
+int house_levels(Csc *V);   // csx_qr.hip: V->house, the levels of V's reflections (pattern only), made once
 // csx_host.cpp: csx_hqr_symbolic_host on vectors that grow (no capacities)
 int hqr_symbolic(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q, const int32_t *parent,
                  const int32_t *pinv, const int32_t *leftmost, std::vector<int32_t> &Vp, std::vector<int32_t> &Vi,

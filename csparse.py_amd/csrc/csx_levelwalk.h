@@ -5,7 +5,8 @@
 //   k_run<Col>       a run of narrower levels: one workgroup walks it, a barrier per level
 //   walk_levels<Col> the stored schedule, launched
 //   k_level_batch / k_run_batch / walk_levels_batch   the same for B value sets on one analysis: the member is a grid dimension,
-//                    a batch policy says which arguments are a member's (csx_slu_batch.hip, csx_ldl_batch.hip)
+//                    a batch policy says which arguments are a member's (csx_slu_batch.hip,
+//                    csx_ldl_batch.hip, csx_hqr_batch.hip)
 //   LevelFactor     what the factor objects keep for it, with walk_init / walk_set_levels (build), walk_begin / walk_end (the frame
 //                    of a run) and walk_refactor (new values on the kept pattern)
 // Col is the column policy of a factorisation (LdlColumn, SluColumn, HqrColumn): Args, the types of its column function's kernel
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_run(const int32_t *__restri
 }
 
 // The same two kernels with a member dimension: B value sets on one analysis (one tree, one schedule), independent of each other
-// (csx_slu_batch.hip, csx_ldl_batch.hip).  Col is a BATCH policy: its column(j, member, wave, lane, args...) says which of the
+// (csx_slu_batch.hip, csx_ldl_batch.hip, csx_hqr_batch.hip).  Col is a BATCH policy: its column(j, member, wave, lane, args...) says which of the
 // arguments belong to a member and by what stride they shift -- it offsets those and forwards to a column policy's column(),
 // so the column function and its bits are the single factorisation's.  The templates know nothing else of the policy.
 // k_level_batch: one wave per (column of the level, member), the member in grid y (at most WALK_BATCH_MAX of them).

@@ -61,8 +61,9 @@ __global__ __launch_bounds__(64) void k_happly_level(const int32_t *__restrict__
 }
 #pragma clang fp contract(fast)
 
-// level[k] = 1 + the highest level among the earlier reflections that share a row with k (host, O(nnz V))
-static int house_levels(Csc *V) {
+// level[k] = 1 + the highest level among the earlier reflections that share a row with k (host, O(nnz V)); kept in V->house
+// (csx_happly here, and the batched reflections of csx_hqr_batch.hip)
+int house_levels(Csc *V) {
     if (V->house) return CSX_OK;
     std::vector<int32_t> hp, hi;
     CSX_TRY(download_i32(hp, V->p, (size_t)V->n + 1));

@@ -1294,6 +1294,56 @@ int csx_ldl_batch_member(csx_handle_t batch, int32_t m, double *Lx, double *d);
 int csx_ldl_batch_d(csx_handle_t batch, double *out);
 int csx_ldl_batch_limits(int32_t *out);
 
+/* ---- many value sets on the analysis of one csx_hqr_factor (csx_hqr_batch.hip) ----
+ * The Householder QR counterpart of the two batches above: reweighted least squares W_j A, Gauss-Newton Jacobians over scenarios,
+ * regularisation sweeps on a stacked [A; lambda_j I].  A batch BORROWS the analysis of a factor F of csx_hqr_factor (the patterns
+ * of V and R, the slot views, the entry maps, the height levels of the column elimination tree, the launch schedule, the
+ * permutations q and pinv) and owns B value sets: V.x of every member (B x vnz doubles), R.x (B x rnz), beta (B x n), flags and
+ * statistics.  F must outlive the batch (every call checks that F's handle still resolves and returns CSX_EINVAL with a text
+ * otherwise); F's own V.x, R.x, beta, scratch and counters are never written.  The members are independent: every one's V.x,
+ * R.x and beta are byte-equal to csx_hqr_host of its values alone.  All members go through F's launch schedule together: one
+ * launch per entry of it whatever B is.  There is NO scratch-then-commit: a member with a non-finite diagonal of R is marked
+ * failed (ok[m] = 0) and its values mean nothing until a refactor mends it; it disturbs no other member.
+ * V: a device vector holding an nnz(A) x B block, row-major: entry q of member m at V[q * B + m], q in the storage order of
+ *   the matrix F was made of (for a wide matrix that is its transpose: the caller reorders); empty slots of V and R are +0.0
+ *   and of duplicate entries the one csx_hqr_factor takes (the last stored) is taken.
+ * B: 1 .. limits[0]; a larger B is CSX_EINVAL with a text (split the family into several batches).
+ * csx_hqr_batch_factor: a NEW batch handle (csx_free) with every member factored; ok: B ints.
+ * csx_hqr_batch_refactor: the same on the batch's own arrays (B is fixed); a member that failed before is computed afresh.
+ * csx_hqr_batch_solve: Xin a device vector holding a rows_in x (B r) block, row-major, columns m r .. m r + r - 1 belonging to
+ *   member m; Xout another vector, filled with the rows_out x (B r) result.  With F of an m x n matrix (m >= n) and m2 rows of V:
+ *     second == 0 (rows_in = m, rows_out = n): W[pinv[i], :] = Xin[i, :] into a zeroed m2 x (B r) block, Q' W, R \ W,
+ *       Xout[q[k], :] = W[k, :] -- the least-squares solution, cs_qrsol's first sequence;
+ *     second != 0 (rows_in = n, rows_out = m): W[k, :] = Xin[q[k], :], R' \ W, Q W, Xout[i, :] = W[pinv[i], :] -- cs_qrsol's
+ *       second sequence: the minimum-norm solution of the transposed system.
+ *   Every column has the bytes of the reference's operations in the reference's order: cs_happly reflection by reflection (the
+ *   dot product in storage order, then tau *= beta, then the update), by csx_happly's levels and route with a lane per column
+ *   reading its member's V.x and beta; cs_usolve as a gather over the rows of R from the top level of the column elimination tree
+ *   down, x_i = (((x_i - R(i,j1) x_j1) - ...) / R(i,i)), j descending; cs_utsolve as a dot over column j's entries before its
+ *   diagonal, x_j = ((x_j - sum R(i,j) x_i in storage order) / R(j,j)), from the leaves up.  The diagonal of R is the LAST stored
+ *   entry of its column.  R(i,j) != 0 makes i a descendant of j in the tree, so F's levels order both sweeps: one launch per
+ *   entry of F's schedule a sweep and csx_happly's launches for the reflections, for any B.  The row view of R is made on the
+ *   first call on F and kept.  The columns of a failed member are filled with NaN; a NaN or inf in a right-hand side stays in
+ *   its column.  An exact zero on R's diagonal is no breakdown of the factorisation (ok[m] stays 1 and the count is in
+ *   csx_hqr_batch_info), but a solve with such a member ends as the single solver's does, where the reference divides by it:
+ *   CSX_EZEROPIVOT with a text that names the member, nothing computed.
+ * csx_hqr_batch_info: shared[12] = m, n, m2, vnz, rnz, levels, launches, level launches, run launches, kernel_us, B of the last
+ *   run, and the kernel launches of the last solve; members[3 B] = per member: the smallest column with a non-finite diagonal
+ *   or -1, columns updated in place, exact zeros on R's diagonal.
+ * csx_hqr_batch_stats: out[2 B] = per member min |r_kk|, max |r_kk|.
+ * csx_hqr_batch_member: V.x (vnz doubles), R.x (rnz doubles) and beta (n doubles) of member m into host arrays.
+ * csx_hqr_batch_r_diag: the diagonals of all members' R, B x n doubles member-major, in one download.
+ * csx_hqr_batch_limits: out[8] = csx_slu_batch_limits' six constants (the level walk and the sweeps are shared), the columns of
+ *   X a workgroup of the reflection kernels takes (a lane each) and HAPPLY_MAX_LEVELS.  No device or factor needed. */
+int csx_hqr_batch_factor(csx_handle_t F, csx_handle_t V, int32_t B, csx_handle_t *batch, int *ok);
+int csx_hqr_batch_refactor(csx_handle_t batch, csx_handle_t V, int *ok);
+int csx_hqr_batch_solve(csx_handle_t batch, csx_handle_t Xin, csx_handle_t Xout, int32_t r, int second);
+int csx_hqr_batch_info(csx_handle_t batch, int64_t *shared, int64_t *members);
+int csx_hqr_batch_stats(csx_handle_t batch, double *out);
+int csx_hqr_batch_member(csx_handle_t batch, int32_t m, double *Vx, double *Rx, double *beta);
+int csx_hqr_batch_r_diag(csx_handle_t batch, double *out);
+int csx_hqr_batch_limits(int32_t *out);
+
 /* ---- sparse Householder QR of a matrix in one connected piece, on the device (csx_hqr.hip) ----
  * A (m-by-n, m >= n, values) with cs_sqr's analysis of A(:, q): q (column order, n entries, or null), parent (column
  * elimination tree), pinv (row permutation, rows of A to 0 .. m2-1), leftmost (m entries), m2 (rows including fictitious ones).
