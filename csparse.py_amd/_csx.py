@@ -269,6 +269,7 @@ _PROTOS = {
     "csx_hqr_batch_r_diag": [H, _f64p],
     "csx_hqr_batch_limits": [_i32p],
     "csx_level_schedule": [C.c_int32, _i32p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.c_int64, _i32p, C.POINTER(C.c_int32)],
+    "csx_row_view": [C.c_int32, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p],
     "csx_gmres_limits": [_i32p],
     "csx_gs_work_len": [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)],
     "csx_gs_project": [H, C.c_int32, H, H, C.c_int64, C.c_int32, _i32p, C.c_int, _f64p],
@@ -451,6 +452,16 @@ def level_schedule(level_ptr, waves, run_levels, work=None, run_work=0):
     check(load().csx_level_schedule(nlev, pi(lp), waves, run_levels, None if w is None else w.ctypes.data_as(C.POINTER(C.c_int64)),
                                     run_work, pi(out), C.byref(count)), "csx_level_schedule")
     return [(bool(out[3 * t]), int(out[3 * t + 1]), int(out[3 * t + 2])) for t in range(count.value)]
+
+
+def row_view(p, i, descending=False):
+    """(rp, rc, rpos): the rows of the square CSC pattern (p, i) with the column and the storage position of every entry, ordered by
+    (column, position) ascending or both descending (csx_row_view; csx_levelwalk.h); no GPU needed"""
+    p, i = i32(p), i32(i)
+    n = len(p) - 1
+    rp, rc, rpos = np.zeros(n + 1, np.int32), np.zeros(len(i), np.int32), np.zeros(len(i), np.int32)
+    check(load().csx_row_view(n, pi(p), pi(i), int(descending), pi(rp), pi(rc), pi(rpos)), "csx_row_view")
+    return rp, rc, rpos
 
 
 SN_GEOMETRY_PLAN = ("chunk", "has_relaxed", "matrix_cores", "leaf_subtrees", "leaf_cols", "leaf_tasks", "leaf_slots",

@@ -5,8 +5,9 @@
 //   k_slb_level / k_slb_run <rows or dots, division>   a wide level is one launch of a thread per (row, member, right-hand side),
 //                    a run of narrow levels one launch of a workgroup per member with a wave per (row, right-hand side) -- F's
 //                    schedule, so len(schedule) launches a sweep for any B
-//   batch_sweep / batch_sweep_upper   one sweep of a lower / an upper factor, launched (batch_sweep_as)
-//   k_slb_permute_in / k_slb_permute_out   the solve's permutations; the second fills a failed member's columns with NaN
+//   batch_sweep / batch_sweep_upper   one sweep of a lower / an upper factor, launched (batch_sweep_as); both are templates on
+//                    what they sweep, so a translation unit holds the kernels of its own sweeps and no others
+//   k_batch_permute  the solve's permutations, gather or scatter; with the flags it fills a failed member's columns with NaN
 // The division of a row has three modes.  Two are the runtime argument `div` of the instantiations <ROWS, false>: none (unit L),
 // or AFTER the chain by the plane's own diagonal val[Lp[j]] (Ut).  The third is the template parameter PRE: BEFORE the chain by
 // dd[member n + j], the D step of an L D L' solve fused into the backward sweep: s = x_j / d_j, then the chain, then the store.
@@ -165,24 +166,17 @@ __global__ __launch_bounds__(64 * SLB_RUN_WAVES) void k_slb_run(const int32_t *_
     }
 }
 
-// W[p[i], :] = X[i, :] (p null: the identity)
-static __global__ __launch_bounds__(256) void k_slb_permute_in(int64_t n, int64_t K, const int32_t *__restrict__ p, const double *__restrict__ X,
-                                                        double *__restrict__ W) {
+// dst[i, :] = src[p[i], :] (scatter 0) or dst[p[i], :] = src[i, :] (scatter 1) over `rows` rows, p null: the identity; with flags,
+// NaN in the columns of a member that broke down (its flag words are 3 apart in every batch)
+static __global__ __launch_bounds__(256) void k_batch_permute(int64_t rows, int64_t K, int32_t r, const int32_t *__restrict__ p, int scatter,
+                                                              const int *__restrict__ flags, const double *__restrict__ src,
+                                                              double *__restrict__ dst) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * K) return;
-    const int64_t i = t / K, c = t - i * K;
-    W[(p ? (int64_t)p[i] : i) * K + c] = X[t];
-}
-
-// X[i, :] = W[p[i], :], NaN in the columns of a member that broke down (its flag words are 3 apart in every batch)
-static __global__ __launch_bounds__(256) void k_slb_permute_out(int64_t n, int64_t K, int32_t r, const int32_t *__restrict__ p,
-                                                         const int *__restrict__ flags, const double *__restrict__ W,
-                                                         double *__restrict__ X) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n * K) return;
-    const int64_t i = t / K, c = t - i * K;
-    const bool ok = flags[3 * (c / r)] == WALK_NONE;
-    X[t] = ok ? W[(p ? (int64_t)p[i] : i) * K + c] : __longlong_as_double(0x7ff8000000000000ll);
+    if (t >= rows * K) return;
+    const int64_t i = t / K, c = t - i * K, pi = p ? (int64_t)p[i] : i;
+    const bool ok = !flags || flags[3 * (c / r)] == WALK_NONE;
+    const double v = ok ? src[(scatter ? i : pi) * K + c] : __longlong_as_double(0x7ff8000000000000ll);
+    dst[(scatter ? pi : i) * K + c] = v;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------
@@ -220,20 +214,19 @@ int batch_sweep_as(const LevelFactor *F, const BatchPattern &P, const double *va
     return CSX_OK;
 }
 
-// A sweep of a LOWER factor with the diagonal first in its column: the rows ascending (cs_lsolve) or the dots descending
-// (cs_ltsolve) of the value plane val, r right-hand sides a member; div: / val[Lp[j]] after the chain; dd: null, or the members'
-// pivots (stride P.n) to divide by BEFORE the chain (dots only: see the head of this file).
-inline int batch_sweep(const LevelFactor *F, const BatchPattern &P, bool rows, const double *val, bool div, const double *dd,
-                       int32_t r, double *X) {
-    if (dd && (rows || div)) return CSX_EINVAL;
-    if (rows) return batch_sweep_as<true, false, false, true>(F, P, val, div, dd, r, X);
-    if (dd) return batch_sweep_as<false, true, false, false>(F, P, val, div, dd, r, X);
-    return batch_sweep_as<false, false, false, false>(F, P, val, div, dd, r, X);
+// A sweep of a LOWER factor with the diagonal first in its column: ROWS: the rows ascending (cs_lsolve), else the dots descending
+// (cs_ltsolve) of the value plane val, r right-hand sides a member; div: / val[Lp[j]] after the chain; PRE (dots only): dd is the
+// members' pivots (stride P.n) to divide by BEFORE the chain (see the head of this file), and there is no other division.
+// (A template, so that a file holds only the kernels of the sweeps it calls.)
+template <bool ROWS, bool PRE = false>
+int batch_sweep(const LevelFactor *F, const BatchPattern &P, const double *val, bool div, const double *dd, int32_t r, double *X) {
+    static_assert(!(ROWS && PRE), "the division before the chain belongs to the backward sweep");
+    if ((dd && (ROWS || div)) || PRE != (dd != nullptr)) return CSX_EINVAL;
+    return batch_sweep_as<ROWS, PRE, false, ROWS>(F, P, val, div, dd, r, X);
 }
 
 // A sweep of an UPPER factor with the diagonal last in its column, always divided by it: ROWS: the rows from the top level down
 // (cs_usolve: P's row view holds row i's columns descending, the diagonal last), else the dots from the leaves up (cs_utsolve).
-// (A template, so that only a file that calls it holds its kernels.)
 template <bool ROWS>
 int batch_sweep_upper(const LevelFactor *F, const BatchPattern &P, const double *val, int32_t r, double *X) {
     return batch_sweep_as<ROWS, false, true, !ROWS>(F, P, val, true, nullptr, r, X);

@@ -2,9 +2,10 @@
 // include/csx.h).  An HqrBatch BORROWS an HqrFactor -- the patterns of V and R, the slot views, the entry maps, the height levels
 // of the column elimination tree, the launch schedule, the permutations -- and owns B value sets: Vx (B x vnz doubles,
 // member-major: member m's column k is the contiguous piece hqr_column expects), Rx (B x rnz), beta (B x n), flags (B x 3),
-// stats (B x 3).  It never writes the factor's V.x / R.x / beta or its scratch, and keeps its own launch counters.
-//   k_hqb_init / k_hqb_scatter   the flag and stat words; every member's values through winV / winR (of duplicates the map's)
-//   HqrBatchColumn   the batch policy of the level walk (csx_levelwalk.h: k_level_batch, k_run_batch): Vx by vnz, Rx by rnz, beta
+// stats (B x 3).  It never writes the factor's V.x / R.x / beta or its scratch, and keeps its own launch counters.  What a batch
+// of any factorisation is -- the object's common part, the guards, the frame of a run (the flag and stat words set, every member's
+// values through winV / winR, of duplicates the map's) -- is csx_valuebatch.h; this file holds what is QR's:
+//   HqrBatchColumn  the batch policy of the level walk (csx_levelwalk.h: k_level_batch, k_run_batch): Vx by vnz, Rx by rnz, beta
 //                    by n, flags by 3, then HqrColumn::column -- hqr_column itself, the host rule's bits
 //   k_hqb_stats      hqr_stats_column per (column, member)
 //   the solve        cs_qrsol's two sequences on an m2 x (B r) block: k_hqb_happly_level / k_hqb_happly, csx_qr.hip's two
@@ -15,11 +16,10 @@
 // There is NO scratch-then-commit: a member with a non-finite diagonal of R is marked failed (ok[m] = 0, its values mean nothing)
 // where the single factor keeps its old values.
 #include <cmath>
-#include <cstring>
 
-#include "csx_batchsolve.h"
 #include "csx_hqr.h"
 #include "csx_internal.h"
+#include "csx_valuebatch.h"
 
 #pragma clang fp contract(off)
 
@@ -27,49 +27,19 @@ namespace csx {
 
 constexpr int HQB_LANES = 64;   // columns of X a workgroup of the reflection kernels takes, a lane each (csx_qr.hip's chunk)
 
-struct HqrBatch {
-    HqrFactor *F = nullptr;   // borrowed: valid while hF resolves to it
-    csx_handle_t hF = 0;
-    int32_t B = 0;
+struct HqrBatch : ValueBatch {
+    static constexpr Kind KIND = K_HQRBATCH, FACTOR_KIND = K_HQRFACTOR;
     DevBuf<double> Vx, Rx, beta;
-    DevBuf<int> flags;                          // per member: the smallest column with a non-finite diagonal, columns updated in place, -
-    DevBuf<unsigned long long> stats;           // per member: hqr_stats_column's three words
-    std::vector<int> hflags;                    // of the last run
-    std::vector<unsigned long long> hstats;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    int64_t level_launches = 0, run_launches = 0, kernel_us = 0, solve_launches = 0;
-    ~HqrBatch() {
-        if (ev_a) (void)hipEventDestroy(ev_a);
-        if (ev_b) (void)hipEventDestroy(ev_b);
-    }
+    int64_t solve_launches = 0;
+    // flags per member: the smallest column with a non-finite diagonal, the columns updated in place, one spare word (the stride
+    // of every batch); stats: hqr_stats_column's three words, min |r_kk| the first
+    HqrBatch() : ValueBatch("csx_hqr_batch", 3, 0) {}
+    HqrFactor *factor() const { return static_cast<HqrFactor *>(F); }
 };
 
 void destroy(HqrBatch *b) { delete b; }
 
 // ---- factor ------------------------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void k_hqb_init(int32_t B, int *flags, unsigned long long *stats) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= B) return;
-    flags[3 * m] = WALK_NONE;
-    flags[3 * m + 1] = flags[3 * m + 2] = 0;
-    stats[3 * m] = ~0ull;
-    stats[3 * m + 1] = stats[3 * m + 2] = 0ull;
-}
-
-// slot q of member blockIdx.y, the slots of V first and R's after them: V is nnz x B, row-major (entry win[q] of member m at
-// V[win[q] * B + m]); a slot no entry lands in is +0.0
-__global__ __launch_bounds__(256) void k_hqb_scatter(int64_t vnz, int64_t rnz, int32_t B, const int32_t *__restrict__ winV,
-                                                     const int32_t *__restrict__ winR, const double *__restrict__ V,
-                                                     double *__restrict__ Vx, double *__restrict__ Rx) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= vnz + rnz) return;
-    const int64_t m = blockIdx.y;
-    const int32_t a = q < vnz ? winV[q] : winR[q - vnz];
-    const double v = a >= 0 ? V[(int64_t)a * B + m] : 0.0;
-    if (q < vnz) Vx[m * vnz + q] = v;
-    else Rx[m * rnz + (q - vnz)] = v;
-}
 
 // The batch policy: the member's own Vx (stride vnz), Rx (stride rnz), beta (stride n) and flags (stride 3); the rest is shared.
 struct HqrBatchColumn {
@@ -143,19 +113,6 @@ __global__ __launch_bounds__(HQB_LANES) void k_hqb_happly_level(const int32_t *_
     }
 }
 
-// dst[i, :] = src[p[i], :] (scatter 0) or dst[p[i], :] = src[i, :] (scatter 1) over `rows` rows, p null: the identity; with flags,
-// NaN in the columns of a member that broke down
-__global__ __launch_bounds__(256) void k_hqb_permute(int64_t rows, int64_t K, int32_t r, const int32_t *__restrict__ p, int scatter,
-                                                     const int *__restrict__ flags, const double *__restrict__ src,
-                                                     double *__restrict__ dst) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= rows * K) return;
-    const int64_t i = t / K, c = t - i * K, pi = p ? (int64_t)p[i] : i;
-    const bool ok = !flags || flags[3 * (c / r)] == WALK_NONE;
-    const double v = ok ? src[(scatter ? i : pi) * K + c] : __longlong_as_double(0x7ff8000000000000ll);
-    dst[(scatter ? pi : i) * K + c] = v;
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------
 
 static HqrFactor *hqb_factor(const char *who, csx_handle_t hF) {
@@ -164,46 +121,17 @@ static HqrFactor *hqb_factor(const char *who, csx_handle_t hF) {
     return F;
 }
 
-static HqrBatch *hqb_get(csx_handle_t h) {
-    HqrBatch *b = (HqrBatch *)get(h, K_HQRBATCH);
-    if (!b) return nullptr;
-    if ((HqrFactor *)get(b->hF, K_HQRFACTOR) != b->F) {
-        set_error("csx_hqr_batch: the factor of this batch has been freed");
-        return nullptr;
-    }
-    return b;
-}
-
-static bool hqb_members_ok(const char *who, int64_t B) {
-    if (B >= 1 && B <= WALK_BATCH_MAX) return true;
-    set_error("%s: B = %lld, a batch holds 1 .. %d members (split a larger family into several batches)", who, (long long)B,
-              (int)WALK_BATCH_MAX);
-    return false;
-}
-
 // The row view of R's pattern with its map to storage positions: row i holds (column, position) of its entries with the columns
 // DESCENDING, so the diagonal (the smallest column of a row of an upper factor) comes last -- the order in which cs_usolve's
 // column loop reaches row i.  Built on the first csx_hqr_batch_solve on F and kept there (R's pattern never changes);
 // synchronises.
 static int hqb_row_view(HqrFactor *F, const Csc *R) {
     if (F->r_rows) return CSX_OK;
-    const size_t n = (size_t)F->n, nz = (size_t)F->rnz;
-    std::vector<int32_t> p, i;
+    const size_t n = (size_t)F->n;
+    std::vector<int32_t> p, i, rp, rc, rpos;
     CSX_TRY(download_i32(p, R->p, n + 1));
-    CSX_TRY(download_i32(i, R->i, nz));
-    std::vector<int32_t> rp(n + 1, 0), rc(nz), rpos(nz);
-    for (size_t q = 0; q < nz; q++) {
-        if (i[q] < 0 || (size_t)i[q] >= n) return CSX_EINVAL;
-        rp[(size_t)i[q] + 1]++;
-    }
-    for (size_t r = 0; r < n; r++) rp[r + 1] += rp[r];
-    std::vector<int32_t> next(rp.begin() + 1, rp.end());   // filled from the end of a row: ascending columns land descending
-    for (size_t j = 0; j < n; j++)
-        for (int32_t q = p[j]; q < p[j + 1]; q++) {
-            const int32_t at = --next[(size_t)i[(size_t)q]];
-            rc[(size_t)at] = (int32_t)j;
-            rpos[(size_t)at] = q;
-        }
+    CSX_TRY(download_i32(i, R->i, (size_t)F->rnz));
+    if ((n > 0 ? p[n] : 0) != F->rnz || !row_view(F->n, p.data(), i.data(), true, rp, rc, rpos)) return CSX_EINVAL;
     for (size_t r = 0; r < n; r++)   // every row ends with its diagonal, which is the last entry of column r
         if (rp[r + 1] == rp[r] || rc[(size_t)rp[r + 1] - 1] != (int32_t)r || rpos[(size_t)rp[r + 1] - 1] != p[r + 1] - 1) return CSX_EINVAL;
     CSX_TRY(upload(F->rrp, rp));
@@ -218,63 +146,25 @@ static int hqb_row_view(HqrFactor *F, const Csc *R) {
 // synchronisation.
 static int hqb_run(HqrBatch *b, const double *V, int *ok) {
     hipStream_t s = ctx().stream;
-    HqrFactor *F = b->F;
+    HqrFactor *F = b->factor();
     const Csc *Vm = csc(F->hV), *R = csc(F->hR);
     if (!Vm || !R) return CSX_EINVAL;
     const int32_t n = F->n, B = b->B;
     const int64_t vnz = F->vnz, rnz = F->rnz;
-    b->level_launches = b->run_launches = 0;
-    hipLaunchKernelGGL(k_hqb_init, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, B, b->flags.get(), b->stats.get());
-    CSX_HIP(hipEventRecord(b->ev_a, s));
-    if (vnz + rnz)
-        hipLaunchKernelGGL(k_hqb_scatter, dim3((unsigned)((vnz + rnz + 255) / 256), (unsigned)B), dim3(256), 0, s, vnz, rnz, B,
-                           F->winV.get(), F->winR.get(), V, b->Vx.get(), b->Rx.get());
+    CSX_TRY(batch_begin(b, nullptr, nullptr));
+    batch_scatter(b, V, vnz, F->winV.get(), b->Vx.get(), rnz, F->winR.get(), b->Rx.get());
     walk_levels_batch<HqrBatchColumn>(F, B, &b->level_launches, &b->run_launches, HqrBatchColumn::Args(), Vm->p, Vm->i, b->Vx, R->p,
                                       R->i, b->Rx, b->beta, F->sp, F->srow, F->sdst, b->flags, vnz, rnz, (int64_t)n);
     if (n > 0)
         hipLaunchKernelGGL(k_hqb_stats, dim3((unsigned)(((int64_t)n + 255) / 256), (unsigned)B), dim3(256), 0, s, n, rnz, R->p,
                            b->Rx.get(), b->stats.get());
-    (void)hipEventRecord(b->ev_b, s);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(b->hflags.data(), b->flags.get(), (size_t)B * 3 * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(b->hstats.data(), b->stats.get(), (size_t)B * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s) !=
-            hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        set_error("csx_hqr_batch: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipStreamSynchronize(s);
-        return CSX_ERUNTIME;
-    }
-    float ms = 0.0f;
-    b->kernel_us = hipEventElapsedTime(&ms, b->ev_a, b->ev_b) == hipSuccess ? (int64_t)(1e3 * ms) : 0;
-    for (int32_t m = 0; m < B; m++) {
-        if (n == 0) b->hstats[(size_t)3 * m] = 0;
-        ok[m] = b->hflags[(size_t)3 * m] == WALK_NONE ? 1 : 0;
-    }
-    return CSX_OK;
-}
-
-static int hqb_alloc(HqrFactor *F, csx_handle_t hF, int32_t B, std::unique_ptr<HqrBatch> *out) {
-    std::unique_ptr<HqrBatch> b(new HqrBatch());
-    b->F = F;
-    b->hF = hF;
-    b->B = B;
-    CSX_TRY(b->Vx.alloc((size_t)B * (size_t)F->vnz));
-    CSX_TRY(b->Rx.alloc((size_t)B * (size_t)F->rnz));
-    CSX_TRY(b->beta.alloc((size_t)B * (size_t)F->n));
-    CSX_TRY(b->flags.alloc((size_t)B * 3));
-    CSX_TRY(b->stats.alloc((size_t)B * 3));
-    b->hflags.assign((size_t)B * 3, 0);
-    b->hstats.assign((size_t)B * 3, 0);
-    CSX_HIP(hipEventCreate(&b->ev_a));
-    CSX_HIP(hipEventCreate(&b->ev_b));
-    *out = std::move(b);
-    return CSX_OK;
+    return batch_end(b, ok);
 }
 
 // Q' W (transpose) or Q W on the m2 x K block W with every member's V.x and beta: csx_happly's launches, whatever B is
 static int hqb_happly(HqrBatch *b, Csc *V, double *W, int64_t K, int32_t r, int transpose) {
     hipStream_t s = ctx().stream;
-    const HqrFactor *F = b->F;
+    const HqrFactor *F = b->factor();
     if (V->n == 0) return CSX_OK;
     CSX_TRY(house_levels(V));
     const HouseLevels *H = V->house.get();
@@ -302,13 +192,7 @@ static int hqb_happly(HqrBatch *b, Csc *V, double *W, int64_t K, int32_t r, int 
 using namespace csx;
 
 extern "C" int csx_hqr_batch_limits(int32_t *out) {   // (no device needed)
-    if (!out) return CSX_EINVAL;
-    out[0] = WALK_BATCH_MAX;
-    out[1] = WALK_WAVES;
-    out[2] = SLB_THREADS;
-    out[3] = SLB_FETCH;
-    out[4] = SLB_RUN_WAVES;
-    out[5] = SLB_RUN_FETCH;
+    CSX_TRY(batch_limits(out));
     out[6] = HQB_LANES;
     out[7] = HAPPLY_MAX_LEVELS;
     return CSX_OK;
@@ -319,14 +203,14 @@ extern "C" int csx_hqr_batch_factor(csx_handle_t hF, csx_handle_t hV, int32_t B,
     if (out) *out = 0;
     HqrFactor *F = hqb_factor("csx_hqr_batch_factor", hF);
     if (!F || !out || !ok) return CSX_EINVAL;
-    if (!hqb_members_ok("csx_hqr_batch_factor", B)) return CSX_EINVAL;
-    const double *V = batch_block(hV, (int64_t)F->anz * B);
-    if (!V) {
-        set_error("csx_hqr_batch_factor: V is not a block of nnz(A) x B = %lld x %d doubles", (long long)F->anz, (int)B);
-        return CSX_EINVAL;
-    }
-    std::unique_ptr<HqrBatch> b;
-    CSX_TRY(hqb_alloc(F, hF, B, &b));
+    if (!batch_members_ok("csx_hqr_batch_factor", B)) return CSX_EINVAL;
+    const double *V = batch_values("csx_hqr_batch_factor", hV, F->anz, B);
+    if (!V) return CSX_EINVAL;
+    std::unique_ptr<HqrBatch> b(new HqrBatch());
+    CSX_TRY(b->Vx.alloc((size_t)B * (size_t)F->vnz));
+    CSX_TRY(b->Rx.alloc((size_t)B * (size_t)F->rnz));
+    CSX_TRY(b->beta.alloc((size_t)B * (size_t)F->n));
+    CSX_TRY(batch_alloc_common(b.get(), F, hF, B));
     CSX_TRY(hqb_run(b.get(), V, ok));
     *out = put(K_HQRBATCH, b.release());
     return CSX_OK;
@@ -334,21 +218,17 @@ extern "C" int csx_hqr_batch_factor(csx_handle_t hF, csx_handle_t hV, int32_t B,
 
 extern "C" int csx_hqr_batch_refactor(csx_handle_t h, csx_handle_t hV, int *ok) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || !ok) return CSX_EINVAL;
-    const double *V = batch_block(hV, (int64_t)b->F->anz * b->B);
-    if (!V) {
-        set_error("csx_hqr_batch_refactor: V is not a block of nnz(A) x B = %lld x %d doubles", (long long)b->F->anz, (int)b->B);
-        return CSX_EINVAL;
-    }
-    return hqb_run(b, V, ok);
+    const double *V = batch_values("csx_hqr_batch_refactor", hV, b->F->anz, b->B);
+    return V ? hqb_run(b, V, ok) : CSX_EINVAL;
 }
 
 extern "C" int csx_hqr_batch_solve(csx_handle_t h, csx_handle_t hXin, csx_handle_t hXout, int32_t r, int second) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || r < 1) return CSX_EINVAL;
-    HqrFactor *F = b->F;
+    HqrFactor *F = b->factor();
     Csc *V = csc(F->hV), *R = csc(F->hR);
     if (!V || !R) return CSX_EINVAL;
     const int64_t m = F->m, n = F->n, m2 = F->m2, K = (int64_t)b->B * r;
@@ -380,7 +260,7 @@ extern "C" int csx_hqr_batch_solve(csx_handle_t h, csx_handle_t hXin, csx_handle
     const int32_t *q = F->perm_q.get(), *pinv = F->perm_p.get();
     auto permute = [&](int64_t rows, const int32_t *p, int scatter, const int *flags, const double *src, double *dst) {
         if (rows == 0) return;
-        hipLaunchKernelGGL(k_hqb_permute, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, s, rows, K, r, p, scatter, flags, src,
+        hipLaunchKernelGGL(k_batch_permute, dim3((unsigned)((rows * K + 255) / 256)), dim3(256), 0, s, rows, K, r, p, scatter, flags, src,
                            dst);
         b->solve_launches++;
     };
@@ -404,9 +284,9 @@ extern "C" int csx_hqr_batch_solve(csx_handle_t h, csx_handle_t hXin, csx_handle
 
 extern "C" int csx_hqr_batch_info(csx_handle_t h, int64_t *shared, int64_t *members) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || !shared || !members) return CSX_EINVAL;
-    const HqrFactor *F = b->F;
+    const HqrFactor *F = b->factor();
     shared[0] = F->m;
     shared[1] = F->n;
     shared[2] = F->m2;
@@ -430,22 +310,20 @@ extern "C" int csx_hqr_batch_info(csx_handle_t h, int64_t *shared, int64_t *memb
 
 extern "C" int csx_hqr_batch_stats(csx_handle_t h, double *out) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || !out) return CSX_EINVAL;
-    for (int32_t m = 0; m < b->B; m++) std::memcpy(out + 2 * m, &b->hstats[(size_t)3 * m], 2 * sizeof(double));
+    batch_stats(b, 0, 2, out);
     return CSX_OK;
 }
 
 extern "C" int csx_hqr_batch_member(csx_handle_t h, int32_t m, double *Vx_out, double *Rx_out, double *beta_out) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || m < 0 || m >= b->B || !Vx_out || !Rx_out || !beta_out) return CSX_EINVAL;
-    hipStream_t s = ctx().stream;
-    const size_t vnz = (size_t)b->F->vnz, rnz = (size_t)b->F->rnz, n = (size_t)b->F->n;
-    if (vnz) CSX_HIP(hipMemcpyAsync(Vx_out, b->Vx.get() + (size_t)m * vnz, vnz * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (rnz) CSX_HIP(hipMemcpyAsync(Rx_out, b->Rx.get() + (size_t)m * rnz, rnz * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (n) CSX_HIP(hipMemcpyAsync(beta_out, b->beta.get() + (size_t)m * n, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    CSX_HIP(hipStreamSynchronize(s));
+    CSX_TRY(batch_member(b->Vx, m, (size_t)b->factor()->vnz, Vx_out));
+    CSX_TRY(batch_member(b->Rx, m, (size_t)b->factor()->rnz, Rx_out));
+    CSX_TRY(batch_member(b->beta, m, (size_t)b->F->n, beta_out));
+    CSX_HIP(hipStreamSynchronize(ctx().stream));
     return CSX_OK;
 }
 
@@ -460,16 +338,16 @@ __global__ __launch_bounds__(256) void k_hqb_diag(int64_t n, int64_t rnz, int32_
 
 extern "C" int csx_hqr_batch_r_diag(csx_handle_t h, double *out) {
     CSX_TRY(require_ready());
-    HqrBatch *b = hqb_get(h);
+    HqrBatch *b = batch_get<HqrBatch>(h);
     if (!b || !out) return CSX_EINVAL;
-    const Csc *R = csc(b->F->hR);
+    const Csc *R = csc(b->factor()->hR);
     if (!R) return CSX_EINVAL;
     hipStream_t s = ctx().stream;
     const int64_t n = b->F->n, all = n * b->B;
     if (all == 0) return CSX_OK;
     DevBuf<double> d;
     CSX_TRY(d.alloc((size_t)all));
-    hipLaunchKernelGGL(k_hqb_diag, dim3((unsigned)((all + 255) / 256)), dim3(256), 0, s, n, (int64_t)b->F->rnz, b->B, R->p, b->Rx.get(),
+    hipLaunchKernelGGL(k_hqb_diag, dim3((unsigned)((all + 255) / 256)), dim3(256), 0, s, n, (int64_t)b->factor()->rnz, b->B, R->p, b->Rx.get(),
                        d.get());
     CSX_LAUNCH_CHECK();
     CSX_HIP(hipMemcpyAsync(out, d.get(), (size_t)all * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -12,7 +12,7 @@
 // The host side is the partial elimination of the first n1 columns (LdlFactor, ldl_build, ldl_run, ldl_refactor: csx_ldl.h):
 // csx_ldl_factor is n1 = n with the walker uncapped, csx_schur_factor (csx_schur.hip) its own n1 with the walker cut; the
 // trailing columns are csx_schur.hip's kernel behind schur_launch_cols.  csx_level_schedule, the walk's scheduler on host
-// arrays, is exported here.
+// arrays, and csx_row_view, its row-view builder (csx_levelwalk.h), are exported here.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -269,6 +269,20 @@ extern "C" int csx_level_schedule(int32_t nlev, const int32_t *level_ptr, int32_
         launches[3 * t + 2] = S[t].l1;
     }
     *count = (int32_t)S.size();
+    return CSX_OK;
+}
+
+extern "C" int csx_row_view(int32_t n, const int32_t *p, const int32_t *i, int descending, int32_t *rp, int32_t *rc,
+                            int32_t *rpos) {   // (no device needed)
+    if (n < 0 || !p || !rp || p[0] != 0) return CSX_EINVAL;
+    for (int32_t j = 0; j < n; j++)
+        if (p[j + 1] < p[j]) return CSX_EINVAL;
+    if (p[n] > 0 && (!i || !rc || !rpos)) return CSX_EINVAL;
+    std::vector<int32_t> hp, hc, hpos;
+    if (!row_view(n, p, i, descending != 0, hp, hc, hpos)) return CSX_EINVAL;
+    std::copy(hp.begin(), hp.end(), rp);
+    std::copy(hc.begin(), hc.end(), rc);
+    std::copy(hpos.begin(), hpos.end(), rpos);
     return CSX_OK;
 }
 

@@ -6,7 +6,8 @@
 //   walk_levels<Col> the stored schedule, launched
 //   k_level_batch / k_run_batch / walk_levels_batch   the same for B value sets on one analysis: the member is a grid dimension,
 //                    a batch policy says which arguments are a member's (csx_slu_batch.hip,
-//                    csx_ldl_batch.hip, csx_hqr_batch.hip)
+//                    csx_ldl_batch.hip, csx_hqr_batch.hip); the host side of a batch is csx_valuebatch.h (§39)
+//   row_view         the rows of a CSC pattern with their storage positions (host only; csx_row_view is its C face)
 //   LevelFactor     what the factor objects keep for it, with walk_init / walk_set_levels (build), walk_begin / walk_end (the frame
 //                    of a run) and walk_refactor (new values on the kept pattern)
 // Col is the column policy of a factorisation (LdlColumn, SluColumn, HqrColumn): Args, the types of its column function's kernel
@@ -80,6 +81,33 @@ inline void height_levels(int32_t n, const int32_t *parent, std::vector<int32_t>
     cols.resize((size_t)n);
     std::vector<int32_t> next(ptr.begin(), ptr.end() - 1);
     for (int32_t j = 0; j < n; j++) cols[(size_t)next[(size_t)level[(size_t)j]]++] = j;
+}
+
+// The row view of a CSC pattern (n columns, n rows; p: n + 1 offsets from 0, i: p[n] rows) with its map to storage positions: row r
+// holds (rc, rpos) = (column, position in i) of its entries at [rp[r], rp[r + 1]), the columns ascending, or descending; entries
+// of one row in one column keep the same direction by position.  A counting sort by row: the columns are met ascending, and a
+// row filled from its end holds them descending.  An empty row stays empty.  false (the outputs mean nothing): a row outside
+// 0 .. n - 1.  (csx_row_view is its C face; the batches build A's rows ascending for |S|_1 and R's descending for cs_usolve.)
+inline bool row_view(int32_t n, const int32_t *p, const int32_t *i, bool descending, std::vector<int32_t> &rp, std::vector<int32_t> &rc,
+                     std::vector<int32_t> &rpos) {
+    const size_t nz = n > 0 ? (size_t)p[n] : 0;
+    rp.assign((size_t)n + 1, 0);
+    for (size_t q = 0; q < nz; q++) {
+        if (i[q] < 0 || i[q] >= n) return false;
+        rp[(size_t)i[q] + 1]++;
+    }
+    for (int32_t r = 0; r < n; r++) rp[(size_t)r + 1] += rp[(size_t)r];
+    rc.resize(nz);
+    rpos.resize(nz);
+    std::vector<int32_t> next(rp.begin() + (descending ? 1 : 0), rp.end() - (descending ? 0 : 1));
+    for (int32_t j = 0; j < n; j++)
+        for (int32_t q = p[j]; q < p[j + 1]; q++) {
+            int32_t &slot = next[(size_t)i[(size_t)q]];
+            const int32_t at = descending ? --slot : slot++;
+            rc[(size_t)at] = j;
+            rpos[(size_t)at] = q;
+        }
+    return true;
 }
 
 // ---- the device side --------------------------------------------------------------------------------------------------------

@@ -1390,7 +1390,13 @@ int csx_hqr_batch_limits(int32_t *out);
  *   levels' work past run_work; a level that alone exceeds run_work is still taken.  The factorisations call it with waves = 4;
  *   run_levels = 2^31 - 1 (LDL') or 256 (Schur, LU, QR); no work but for QR (the slot updates of the level's longest column,
  *   run_work = 2^24).  launches: room for 3 nlev integers, written as *count triples (1 wide / 0 walker, first level, end level)
- *   that cover 0 .. nlev - 1 in order.  CSX_EINVAL for nlev < 0, waves < 1, run_levels < 1, decreasing offsets, a null pointer. */
+ *   that cover 0 .. nlev - 1 in order.  CSX_EINVAL for nlev < 0, waves < 1, run_levels < 1, decreasing offsets, a null pointer.
+ * csx_row_view: the rows of an n x n CSC pattern (p: n + 1 offsets from 0, i: p[n] rows, in any order, repeats allowed) with their
+ *   storage positions, on host arrays, no device: what the value batches build for |S|_1 (A, ascending) and for cs_usolve (R,
+ *   descending).  rp: n + 1 offsets; row r holds rc[q] = the column and rpos[q] = the position in i of its entries for q in
+ *   [rp[r], rp[r + 1]), ordered by (column, position) ascending, or both descending; a row without entries is empty.
+ *   CSX_EINVAL, nothing written: n < 0, p[0] != 0, decreasing offsets, a row outside 0 .. n - 1, a null pointer (i, rc and rpos
+ *   may be null when p[n] = 0). */
 int csx_hqr_symbolic_host(int32_t m, int32_t n, int32_t m2, const int32_t *Ap, const int32_t *Ai, const int32_t *q,
                           const int32_t *parent, const int32_t *pinv, const int32_t *leftmost, int32_t vcap, int32_t rcap,
                           int32_t *Vp, int32_t *Vi, int32_t *Rp, int32_t *Ri);
@@ -1406,6 +1412,7 @@ int csx_hqr_stats(csx_handle_t F, double *out);
 int csx_hqr_window(int32_t *entries, int32_t *run_levels);
 int csx_level_schedule(int32_t nlev, const int32_t *level_ptr, int32_t waves, int32_t run_levels, const int64_t *work,
                        int64_t run_work, int32_t *launches, int32_t *count);
+int csx_row_view(int32_t n, const int32_t *p, const int32_t *i, int descending, int32_t *rp, int32_t *rc, int32_t *rpos);
 
 /* ---- the block kernels of restarted GMRES (csx_gmres.hip): classical Gram-Schmidt on a block of columns against
  * a basis of blocks, every column its own system.  Blocks are row-major rows x nrhs.  The basis V is ONE vector holding

@@ -271,6 +271,34 @@ def test_the_most_members(cs):
         F.batch(np.ones((1, BC.MAX_MEMBERS + 1)))
 
 
+def test_a_freed_factor_is_refused(cs):
+    import _csx
+    lib, C = _csx.lib(), _csx.C
+    case = SC.BY_NAME["one"]
+    n, V = case.n, BC.members(case, 3)
+    dV, out, ok = cs.dvec(V), _csx.new_handle(), (C.c_int * 3)()
+    # a factor made and freed at the ABI (natural order: the one column a root), its batch outliving it
+    hF, one = _csx.new_handle(), C.c_int(0)
+    parent, cp = np.full(n, -1, np.int32), np.arange(n + 1, dtype=np.int32)
+    with cs._Resident(case.matrix(cs)) as dA:
+        _csx.check(lib.csx_slu_factor(dA.handle, _csx.pi(parent), _csx.pi(cp), None, None, 0.0, hF, one), "csx_slu_factor")
+    assert one.value == 1
+    assert lib.csx_slu_batch_factor(hF, dV.handle, 3, None, out, ok) == _csx.OK and out.value and list(ok) == [1, 1, 1]
+    lx, ux = np.zeros(n), np.zeros(n)
+    assert lib.csx_slu_batch_member(out, 2, _csx.pd(lx), _csx.pd(ux)) == _csx.OK
+    assert lx.tolist() == [1.0] and ux.tobytes() == V[:, 2].tobytes()
+    _csx.free(hF)
+    shared, per = (C.c_int64 * 8)(), (C.c_int64 * 15)()
+    dX = cs.dvec(np.zeros((n, 3)))
+    for call in (lambda: lib.csx_slu_batch_refactor(out, dV.handle, None, ok), lambda: lib.csx_slu_batch_solve(out, dX.handle, 1, 0),
+                 lambda: lib.csx_slu_batch_info(out, shared, per), lambda: lib.csx_slu_batch_stats(out, _csx.pd(np.zeros(12))),
+                 lambda: lib.csx_slu_batch_member(out, 0, _csx.pd(lx), _csx.pd(ux))):
+        assert call() == _csx.EINVAL and b"freed" in lib.csx_last_error()
+    again = _csx.new_handle()
+    assert lib.csx_slu_batch_factor(hF, dV.handle, 3, None, again, ok) == _csx.EINVAL and again.value == 0
+    _csx.free(out)
+
+
 def test_bad_arguments(cs):
     import _csx
     lib, C = _csx.lib(), _csx.C
