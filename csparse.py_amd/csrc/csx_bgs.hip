@@ -200,12 +200,6 @@ namespace {
 
 constexpr int64_t BGS_MAX_ROWS = (int64_t)1 << 40;
 
-bool bgs_overlap(const void *a, int64_t alen, const void *b, int64_t blen) {
-    const uintptr_t ab = (uintptr_t)a, ae = ab + (uintptr_t)alen * sizeof(double);
-    const uintptr_t bb = (uintptr_t)b, be = bb + (uintptr_t)blen * sizeof(double);
-    return alen > 0 && blen > 0 && ab < be && bb < ae;
-}
-
 // one call's view of the work vector
 struct BgsWork {
     double *coef = nullptr, *out = nullptr, *partA = nullptr, *partB = nullptr;
@@ -222,8 +216,8 @@ int bgs_open(Vec *B, int32_t nv, int32_t b, Vec *X, int32_t q, Vec *work, int64_
     if (X->len < xblock) return CSX_EINVAL;
     const int64_t need = bgs_work_len(rows, b, q, nv);
     if (work->len < need) return CSX_EINVAL;
-    if (bgs_overlap(work->d, need, X->d, xblock) || bgs_overlap(work->d, need, B->d, vblock * nv)) return CSX_EINVAL;
-    if (written && bgs_overlap(B->d, vblock * nv, X->d, xblock)) return CSX_EINVAL;
+    if (ranges_overlap(work->d, need, X->d, xblock) || ranges_overlap(work->d, need, B->d, vblock * nv)) return CSX_EINVAL;
+    if (written && ranges_overlap(B->d, vblock * nv, X->d, xblock)) return CSX_EINVAL;
     w.nch = gs_chunks(rows);
     const int64_t bq = (int64_t)b * q;
     w.coef = (double *)work->d;

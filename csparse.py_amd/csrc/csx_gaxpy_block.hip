@@ -1,53 +1,29 @@
 // csx_gaxpy_block: Y += A X for an n-by-nrhs block X (row-major, the layout of every batched solve), i.e.
 // cs_gaxpy (csparse.py:1199-1213) applied to every column of X at once.
 //
-// Block kernel (both modes): one group of G lanes per row of A's cached row gather (A->rows: the entries of
-// row r in ascending (column, position) order = the order in which the reference adds them into y[r]) and
-// one lane per right-hand side (V = 2 columns per lane through 16-byte loads for wide blocks).  A lane
-// starts from Y[r, c] and adds val[q] * X[idx[q], c] over the row in that order, the product rounded before
-// the sum (no FMA): every column of Y is bit-identical to csx_gaxpy EXACT on that column, and a run is
-// deterministic.  The order costs nothing here (each lane owns its own sum); only the multiply and the add
-// are two instructions where an FMA could be one, in a kernel bound by the gathers.
-//   * A group reads the row's (idx, val) pairs once for all of its columns and gathers whole pieces of X
-//     rows: G V 8 bytes per entry (1 KiB per wave instruction at nrhs >= 128).
-//   * U entries of a row are requested before the first is added: the chain ptr -> idx/val -> X row is
-//     latency-bound.
-//   * A workgroup owns BLOCK_TILE consecutive rows, so the rows of one dense block of a block-structured matrix
-//     (G-spd) gather the same X rows on one CU.  Measured, that is not yet enough: with ~256 tiles live per XCD
-//     the X rows do not stay in its L2, and G-spd at k = 128 fetches 4.5x its algorithmic bytes.
+// Block kernel (both modes): the row-block shape (csx_rowblock.h) on A's cached row gather (A->rows: the
+// entries of row r in ascending (column, position) order = the order in which the reference adds them into y[r]).  A
+// lane starts from Y[r, c] and adds val[q] * X[idx[q], c] over the row in that order, the product rounded before the
+// sum (no FMA): every column of Y is bit-identical to csx_gaxpy EXACT on that column, and a run is deterministic.  The
+// order costs nothing here (each lane owns its own sum); only the multiply and the add are two instructions where an FMA
+// could be one, in a kernel bound by the gathers.
+//   * A group reads the row's (idx, val) pairs once for all of its columns and gathers whole pieces of X rows: G V 8
+//     bytes per entry (1 KiB per wave instruction at nrhs >= 128).
+//   * A workgroup owns ROWBLOCK_TILE consecutive rows, so the rows of one dense block of a block-structured matrix
+//     (G-spd) gather the same X rows on one CU.  Measured, that is not yet enough: with ~256 tiles live per XCD the X
+//     rows do not stay in its L2, and G-spd at k = 128 fetches 4.5x its algorithmic bytes.
 //
 // Column route (AUTO only, matrices with a tiled plan, narrow blocks): X and Y are transposed into nrhs
 // contiguous vectors, csx_gaxpy's own plan runs once per column, and the columns of Y are transposed back:
 // every column bit-identical to csx_gaxpy AUTO on it.  DESIGN.md 10 has the measurements behind the rule.
 //
 // Algorithmic bytes per call: 12 nnz + 4 (m + 1) + 8 n nrhs + 16 m nrhs.
-#include "csx_internal.h"
+#include "csx_rowblock.h"
 
 namespace csx {
 
-typedef double f64x2b __attribute__((ext_vector_type(2)));
-
-constexpr int BLOCK_TILE = 64;   // rows per workgroup: one G-spd dense block
-
-template <int V>
-struct Cols;
-template <>
-struct Cols<1> {
-    typedef double T;
-    static __device__ __forceinline__ T load(const double *p) { return *p; }
-    static __device__ __forceinline__ void store(double *p, T v) { *p = v; }
-};
-template <>
-struct Cols<2> {
-    typedef f64x2b T;
-    static __device__ __forceinline__ T load(const double *p) { return *reinterpret_cast<const f64x2b *>(p); }
-    static __device__ __forceinline__ void store(double *p, T v) { *reinterpret_cast<f64x2b *>(p) = v; }
-};
-
 #pragma clang fp contract(off)
-// G lanes per row (a power of two, 4 .. 64), V columns per lane (V = 2 needs nrhs even and X, Y 16-byte aligned),
-// U entries of a row in flight.  Lanes whose columns lie past nrhs do nothing; nrhs > G V takes several passes over
-// the row.  G == 64: the row is wave-uniform and its (idx, val) pairs are scalar loads.
+// Rows outer, column passes inner: a group reads its row pointers once.  Lanes whose columns lie past nrhs do nothing.
 template <int G, int V, int U>
 __global__ __launch_bounds__(256) void k_gaxpy_block(int32_t rows, int32_t nrhs, const int32_t *__restrict__ ptr,
                                                      const int32_t *__restrict__ idx, const double *__restrict__ val,
@@ -56,8 +32,8 @@ __global__ __launch_bounds__(256) void k_gaxpy_block(int32_t rows, int32_t nrhs,
     constexpr int GROUPS = 256 / G;
     const int sub = threadIdx.x & (G - 1);
     const int gid = G == 64 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x / G);
-    const int64_t r0 = (int64_t)blockIdx.x * BLOCK_TILE;
-    const int64_t r1 = r0 + BLOCK_TILE < rows ? r0 + BLOCK_TILE : rows;
+    const int64_t r0 = (int64_t)blockIdx.x * ROWBLOCK_TILE;
+    const int64_t r1 = r0 + ROWBLOCK_TILE < rows ? r0 + ROWBLOCK_TILE : rows;
     for (int64_t r = r0 + gid; r < r1; r += GROUPS) {
         const int32_t b = ptr[r], e = ptr[r + 1];
         for (int32_t c0 = 0; c0 < nrhs; c0 += G * V) {
@@ -121,21 +97,11 @@ static int block_transpose(int64_t rows, int64_t cols, const double *in, double 
 
 static int run_block(const Gather *g, int32_t nrhs, const double *X, double *Y) {
     if (g->rows == 0) return CSX_OK;
-    hipStream_t s = ctx().stream;
-    const unsigned blocks = (unsigned)(((int64_t)g->rows + BLOCK_TILE - 1) / BLOCK_TILE);
-#define CSX_BLOCK(G, V, U)                                                                                      \
-    hipLaunchKernelGGL((k_gaxpy_block<G, V, U>), dim3(blocks), dim3(256), 0, s, g->rows, nrhs, g->ptr, g->idx, \
-                       g->val, X, Y)
-    const bool pairs = nrhs % 2 == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)Y % 16) == 0;
-    if (nrhs > 64) {
-        if (pairs) CSX_BLOCK(64, 2, 8);
-        else CSX_BLOCK(64, 1, 8);
-    } else if (nrhs > 32) CSX_BLOCK(64, 1, 8);
-    else if (nrhs > 16) CSX_BLOCK(32, 1, 8);
-    else if (nrhs > 8) CSX_BLOCK(16, 1, 8);
-    else if (nrhs > 4) CSX_BLOCK(8, 1, 8);
-    else CSX_BLOCK(4, 1, 8);
-#undef CSX_BLOCK
+    const unsigned blocks = (unsigned)(((int64_t)g->rows + ROWBLOCK_TILE - 1) / ROWBLOCK_TILE);
+    rowblock_launch(nrhs, aligned16(X, Y), [&](auto sh) {
+        hipLaunchKernelGGL((k_gaxpy_block<sh.G, sh.V, sh.U>), dim3(blocks), dim3(256), 0, ctx().stream, g->rows, nrhs,
+                           g->ptr.get(), g->idx.get(), g->val.get(), X, Y);
+    });
     CSX_LAUNCH_CHECK();
     return CSX_OK;
 }
@@ -167,9 +133,7 @@ extern "C" int csx_gaxpy_block(csx_handle_t hA, csx_handle_t hX, csx_handle_t hY
     if (mode != CSX_GAXPY_EXACT && mode != CSX_GAXPY_AUTO) return CSX_EINVAL;
     const int64_t xlen = (int64_t)A->n * nrhs, ylen = (int64_t)A->m * nrhs;
     if (X->len < xlen || Y->len < ylen || hX == hY) return CSX_EINVAL;
-    const uintptr_t xb = (uintptr_t)X->d, xe = xb + (uintptr_t)xlen * sizeof(double);
-    const uintptr_t yb = (uintptr_t)Y->d, ye = yb + (uintptr_t)ylen * sizeof(double);
-    if (xlen > 0 && ylen > 0 && xb < ye && yb < xe) return CSX_EINVAL;   // wrapped views of one buffer
+    if (ranges_overlap(X->d, xlen, Y->d, ylen)) return CSX_EINVAL;   // wrapped views of one buffer
     if (A->m == 0 || A->n == 0 || A->nnz == 0) return CSX_OK;
     const double *xd = (const double *)X->d;
     double *yd = (double *)Y->d;

@@ -254,12 +254,6 @@ unsigned gs_blocks(int64_t items) {
     return (unsigned)(want < cap ? (want > 0 ? want : 1) : cap);
 }
 
-bool gs_overlap(const void *a, int64_t alen, const void *b, int64_t blen) {
-    const uintptr_t ab = (uintptr_t)a, ae = ab + (uintptr_t)alen * sizeof(double);
-    const uintptr_t bb = (uintptr_t)b, be = bb + (uintptr_t)blen * sizeof(double);
-    return alen > 0 && blen > 0 && ab < be && bb < ae;
-}
-
 // one call's view of the work vector
 struct GsWork {
     int32_t *mask = nullptr, *len = nullptr;
@@ -276,8 +270,8 @@ int gs_open(Vec *B, int32_t nblocks, Vec *W, Vec *work, int64_t rows, int32_t nr
     if (B->len / nblocks < block || W->len < block) return CSX_EINVAL;
     const int64_t need = gs_work_len(rows, nrhs, nblocks);
     if (work->len < need) return CSX_EINVAL;
-    if (gs_overlap(B->d, block * nblocks, W->d, block) || gs_overlap(work->d, need, W->d, block) ||
-        gs_overlap(work->d, need, B->d, block * nblocks))
+    if (ranges_overlap(B->d, block * nblocks, W->d, block) || ranges_overlap(work->d, need, W->d, block) ||
+        ranges_overlap(work->d, need, B->d, block * nblocks))
         return CSX_EINVAL;
     w.nch = gs_chunks(rows);
     double *d = (double *)work->d;

@@ -389,6 +389,26 @@ int build_row_gather(Csc *A);   // fills A->rows (values required)
 // csx_residual.hip: h[0 .. width) (host) = the maxima, as unsigned integers, over the `count` rows of part (device, count x width,
 // not written); synchronises the context's stream
 int max_partials_host(const uint64_t *part, int64_t count, int32_t width, uint64_t *h);
+// csx_residual.hip: omega / rnorm (host, nrhs each, either may be null) from a residual kernel's partials (blocks x 2 x nrhs bit
+// patterns); zeros when blocks == 0 (no rows, part not read)
+int residual_maxima(const uint64_t *part, int64_t blocks, int32_t nrhs, double *omega, double *rnorm);
+// csx_residual.hip: zero[0 .. rows] = 0, the row pointers of a gather without entries
+int empty_row_ptr(DevBuf<int32_t> &zero, int32_t rows);
+// Do a[0 .. alen) and b[0 .. blen) (doubles on the device) share a byte?  Two wrapped views of one buffer may; an empty range
+// shares nothing.
+inline bool ranges_overlap(const void *a, int64_t alen, const void *b, int64_t blen) {
+    const uintptr_t ab = (uintptr_t)a, ae = ab + (uintptr_t)alen * sizeof(double);
+    const uintptr_t bb = (uintptr_t)b, be = bb + (uintptr_t)blen * sizeof(double);
+    return alen > 0 && blen > 0 && ab < be && bb < ae;
+}
+// The blocks of a residual call: X holds xlen doubles, B and R (null: none) blen; X is another vector than B and R and lies apart
+// from both; R is B (in place: the same handle or the same address) or lies apart from it.
+inline bool residual_blocks_ok(const Vec *X, int64_t xlen, const Vec *B, const Vec *R, int64_t blen) {
+    if (X->len < xlen || B->len < blen || (R && R->len < blen)) return false;
+    if (B == X || R == X) return false;
+    if (ranges_overlap(X->d, xlen, B->d, blen) || (R && ranges_overlap(X->d, xlen, R->d, blen))) return false;
+    return !(R && R->d != B->d && ranges_overlap(B->d, blen, R->d, blen));
+}
 // Structure check of a matrix whose arrays the library did not make (csx_csc_wrap): p non-decreasing from 0 to nnz,
 // every row index in [0, m), in one device pass.  CSX_EINVAL (IndexError in Python) otherwise; remembered in A->trusted.
 int csc_validate(Csc *A);
@@ -453,6 +473,10 @@ int chol_row_view(int32_t n, int64_t lnz, const uint32_t *col, const int32_t *Li
 // back on the critical path of a kernel that synchronises once or twice per step.  Use where only LDS is shared
 // across the barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Magnitudes are compared and reduced as the bit patterns of fabs, unsigned: exact, independent of the order, a NaN above inf.
+__device__ __forceinline__ uint64_t abs_bits(double v) { return __builtin_bit_cast(uint64_t, __builtin_fabs(v)); }
+__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
 // sizes
 constexpr int WAVE = 64;

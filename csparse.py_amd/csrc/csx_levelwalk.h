@@ -112,8 +112,7 @@ inline bool row_view(int32_t n, const int32_t *p, const int32_t *i, bool descend
 
 // ---- the device side --------------------------------------------------------------------------------------------------------
 
-// the stats kernels' order of magnitudes: the bit pattern of fabs as an unsigned integer (csx_residual.hip's rule: a NaN ranks above inf)
-__device__ __forceinline__ uint64_t abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
+// (the stats kernels order magnitudes by abs_bits, csx_internal.h)
 
 template <class... A>
 struct ColumnArgs {};

@@ -203,12 +203,6 @@ static void launch_outer(unsigned blocks, int32_t n, int32_t nnz, int32_t nrhs, 
 #undef CSX_PO
 }
 
-static bool po_overlap(const Vec *a, int64_t alen, const Vec *b, int64_t blen) {
-    const uintptr_t ab = (uintptr_t)a->d, ae = ab + (uintptr_t)alen * sizeof(double);
-    const uintptr_t bb = (uintptr_t)b->d, be = bb + (uintptr_t)blen * sizeof(double);
-    return alen > 0 && blen > 0 && ab < be && bb < ae;
-}
-
 }  // namespace csx
 
 using namespace csx;
@@ -221,7 +215,7 @@ extern "C" int csx_pattern_outer(csx_handle_t hA, csx_handle_t hU, csx_handle_t 
     if (!A || !U || !V || !O || nrhs < 1 || (mode != 0 && mode != 1) || (mode == 1 && A->m != A->n)) return CSX_EINVAL;
     const int64_t ulen = (int64_t)A->m * nrhs, vlen = (int64_t)A->n * nrhs;
     if (U->len < ulen || V->len < vlen || O->len < A->nnz) return CSX_EINVAL;
-    if (po_overlap(O, A->nnz, U, ulen) || po_overlap(O, A->nnz, V, vlen)) return CSX_EINVAL;
+    if (ranges_overlap(O->d, A->nnz, U->d, ulen) || ranges_overlap(O->d, A->nnz, V->d, vlen)) return CSX_EINVAL;
     if (A->m == 0 || A->n == 0 || A->nnz == 0) return CSX_OK;
     CSX_TRY(csc_validate(A));   // a wrapped matrix: its indices address the rows of U (checked once, remembered)
     const unsigned blocks = (unsigned)(((int64_t)A->nnz + PO_CHUNK - 1) / PO_CHUNK);

@@ -13,50 +13,18 @@
 // inf, independent of the order.  No floating-point atomics: a workgroup reduces its rows (wave shuffles, then LDS)
 // into one partial per column, a second kernel reduces the partials.
 //
-// Kernel: k_gaxpy_block's shape (csx_gaxpy_block.hip): G lanes per row and one lane per right-hand side (V = 2 columns
-// per lane through 16-byte loads for wide aligned blocks), U entries of a row in flight, 64 rows per workgroup, scalar
-// (idx, val) loads at G == 64; two accumulators per column; division and reduction at the row's end.  The loop over the
-// column passes (nrhs > G V) is the outer one here, so that a lane carries the maxima of ONE pass.
+// Kernel: the row-block shape (csx_rowblock.h) on one (ptr, idx, val) gather: two accumulators per column;
+// division and reduction at the row's end.  The loop over the column passes (nrhs > G V) is the outer one here, so that a
+// lane carries the maxima of ONE pass.
 //
 // Algorithmic bytes per call: 12 nnz + 4 (rows + 1) + 8 cols nrhs + 16 rows nrhs (+ 16 nrhs); 8 rows nrhs less
 // without R.
 #include <cstring>
 #include <utility>
 
-#include "csx_internal.h"
+#include "csx_rowblock.h"
 
 namespace csx {
-
-typedef double f64x2r __attribute__((ext_vector_type(2)));
-
-constexpr int RES_TILE = 64;   // rows per workgroup
-
-__device__ __forceinline__ uint64_t abs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
-__device__ __forceinline__ uint64_t umax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
-template <int V>
-struct RCols;
-template <>
-struct RCols<1> {
-    typedef double T;
-    static __device__ __forceinline__ T load(const double *p) { return *p; }
-    static __device__ __forceinline__ void store(double *p, T v) { *p = v; }
-    static __device__ __forceinline__ T abs(T v) { return fabs(v); }
-    static __device__ __forceinline__ double at(T v, int) { return v; }
-};
-template <>
-struct RCols<2> {
-    typedef f64x2r T;
-    static __device__ __forceinline__ T load(const double *p) { return *reinterpret_cast<const f64x2r *>(p); }
-    static __device__ __forceinline__ void store(double *p, T v) { *reinterpret_cast<f64x2r *>(p) = v; }
-    static __device__ __forceinline__ T abs(T v) {
-        T a;
-        a.x = fabs(v.x);
-        a.y = fabs(v.y);
-        return a;
-    }
-    static __device__ __forceinline__ double at(T v, int k) { return k ? v.y : v.x; }
-};
 
 #pragma clang fp contract(off)
 // part: [gridDim.x][2][nrhs] bit patterns: the workgroup's maxima of ratio, then of |r|, per column.
@@ -67,14 +35,14 @@ __global__ __launch_bounds__(256) void k_residual_block(int32_t rows, int32_t nr
                                                         const int32_t *__restrict__ idx, const double *__restrict__ val,
                                                         const double *__restrict__ X, const double *B, double *R,
                                                         uint64_t *__restrict__ part) {
-    typedef typename RCols<V>::T T;
+    typedef typename Cols<V>::T T;
     constexpr int GROUPS = 256 / G;
     __shared__ uint64_t red[4][G * V][2];
     const int sub = threadIdx.x & (G - 1);
     const int gid = G == 64 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x / G);
     const int wave = threadIdx.x >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * RES_TILE;
-    const int64_t r1 = r0 + RES_TILE < rows ? r0 + RES_TILE : rows;
+    const int64_t r0 = (int64_t)blockIdx.x * ROWBLOCK_TILE;
+    const int64_t r1 = r0 + ROWBLOCK_TILE < rows ? r0 + ROWBLOCK_TILE : rows;
     for (int32_t c0 = 0; c0 < nrhs; c0 += G * V) {
         const int32_t c = c0 + sub * V;
         uint64_t wmax[V], rmax[V];
@@ -83,8 +51,8 @@ __global__ __launch_bounds__(256) void k_residual_block(int32_t rows, int32_t nr
         if (c < nrhs) {
             for (int64_t r = r0 + gid; r < r1; r += GROUPS) {
                 const int32_t b = ptr[r], e = ptr[r + 1];
-                T acc = RCols<V>::load(B + r * nrhs + c);
-                T den = RCols<V>::abs(acc);
+                T acc = Cols<V>::load(B + r * nrhs + c);
+                T den = Cols<V>::abs(acc);
                 for (int32_t q = b; q < e; q += U) {
                     int32_t j[U];
                     double v[U];
@@ -96,20 +64,20 @@ __global__ __launch_bounds__(256) void k_residual_block(int32_t rows, int32_t nr
                         v[u] = in ? val[q + u] : 0.0;
                     }
 #pragma unroll
-                    for (int u = 0; u < U; u++) xv[u] = RCols<V>::load(X + (int64_t)j[u] * nrhs + c);
+                    for (int u = 0; u < U; u++) xv[u] = Cols<V>::load(X + (int64_t)j[u] * nrhs + c);
 #pragma unroll
                     for (int u = 0; u < U; u++)
-                        if (q + u < e) {   // skipped, not added as 0 (see k_gaxpy_block)
+                        if (q + u < e) {   // skipped, not added as 0 (csx_rowblock.h)
                             const T t = v[u] * xv[u];
                             acc = acc - t;
-                            const T w = fabs(v[u]) * RCols<V>::abs(xv[u]);
+                            const T w = fabs(v[u]) * Cols<V>::abs(xv[u]);
                             den = den + w;
                         }
                 }
-                if (STORE) RCols<V>::store(R + r * nrhs + c, acc);
+                if (STORE) Cols<V>::store(R + r * nrhs + c, acc);
 #pragma unroll
                 for (int k = 0; k < V; k++) {
-                    const double ar = fabs(RCols<V>::at(acc, k)), d = RCols<V>::at(den, k);
+                    const double ar = fabs(Cols<V>::at(acc, k)), d = Cols<V>::at(den, k);
                     const double ratio = (ar == 0.0 && d == 0.0) ? 0.0 : ar / d;
                     wmax[k] = umax64(wmax[k], abs_bits(ratio));
                     rmax[k] = umax64(rmax[k], abs_bits(ar));
@@ -184,25 +152,6 @@ __global__ __launch_bounds__(256) void k_block_select_cols(int64_t total, int32_
         if (mask[t % nrhs]) dst[t] = src[t];
 }
 
-template <bool STORE>
-static void launch_residual(unsigned blocks, int32_t rows, int32_t nrhs, const int32_t *ptr, const int32_t *idx,
-                            const double *val, const double *X, const double *B, double *R, uint64_t *part) {
-    hipStream_t s = ctx().stream;
-#define CSX_RES(G, V, U)                                                                                              \
-    hipLaunchKernelGGL((k_residual_block<G, V, U, STORE>), dim3(blocks), dim3(256), 0, s, rows, nrhs, ptr, idx, val, X, B, \
-                       R, part)
-    const bool pairs = nrhs % 2 == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)R % 16) == 0;
-    if (nrhs > 64) {
-        if (pairs) CSX_RES(64, 2, 8);
-        else CSX_RES(64, 1, 8);
-    } else if (nrhs > 32) CSX_RES(64, 1, 8);
-    else if (nrhs > 16) CSX_RES(32, 1, 8);
-    else if (nrhs > 8) CSX_RES(16, 1, 8);
-    else if (nrhs > 4) CSX_RES(8, 1, 8);
-    else CSX_RES(4, 1, 8);
-#undef CSX_RES
-}
-
 // h[0 .. width) = the maxima over the `count` rows of part (count x width bit patterns, left as they are); synchronises
 int max_partials_host(const uint64_t *part, int64_t count, int32_t width, uint64_t *h) {
     hipStream_t s = ctx().stream;
@@ -227,29 +176,36 @@ int max_partials_host(const uint64_t *part, int64_t count, int32_t width, uint64
     return CSX_OK;
 }
 
-// the residual of `rows` gathered rows and the maxima of every column (host arrays, either may be null)
-static int run_residual(int32_t rows, int32_t nrhs, const int32_t *ptr, const int32_t *idx, const double *val, const double *X,
-                        const double *B, double *R, double *omega, double *rnorm) {
-    const int32_t width = 2 * nrhs;
-    const int64_t blocks = ((int64_t)rows + RES_TILE - 1) / RES_TILE;
-    DevBuf<uint64_t> pa;
-    CSX_TRY(pa.alloc((size_t)blocks * width));
-    if (R) launch_residual<true>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
-    else launch_residual<false>((unsigned)blocks, rows, nrhs, ptr, idx, val, X, B, R, pa);
-    CSX_LAUNCH_CHECK();
+int residual_maxima(const uint64_t *part, int64_t blocks, int32_t nrhs, double *omega, double *rnorm) {
     if (!omega && !rnorm) return CSX_OK;
-    std::vector<uint64_t> h((size_t)width);
-    CSX_TRY(max_partials_host(pa, blocks, width, h.data()));
+    std::vector<uint64_t> h(2 * (size_t)nrhs, 0);   // the bit pattern of 0.0
+    if (blocks > 0) CSX_TRY(max_partials_host(part, blocks, 2 * nrhs, h.data()));
     static_assert(sizeof(double) == sizeof(uint64_t), "bit patterns of doubles");
     if (omega) std::memcpy(omega, h.data(), (size_t)nrhs * sizeof(double));
     if (rnorm) std::memcpy(rnorm, h.data() + nrhs, (size_t)nrhs * sizeof(double));
     return CSX_OK;
 }
 
-static bool overlap(const Vec *a, int64_t alen, const Vec *b, int64_t blen) {
-    const uintptr_t ab = (uintptr_t)a->d, ae = ab + (uintptr_t)alen * sizeof(double);
-    const uintptr_t bb = (uintptr_t)b->d, be = bb + (uintptr_t)blen * sizeof(double);
-    return alen > 0 && blen > 0 && ab < be && bb < ae;
+int empty_row_ptr(DevBuf<int32_t> &zero, int32_t rows) {
+    CSX_TRY(zero.alloc((size_t)rows + 1));
+    CSX_HIP(hipMemsetAsync(zero.get(), 0, ((size_t)rows + 1) * sizeof(int32_t), ctx().stream));
+    return CSX_OK;
+}
+
+// the residual of `rows` gathered rows and the maxima of every column (host arrays, either may be null)
+static int run_residual(int32_t rows, int32_t nrhs, const int32_t *ptr, const int32_t *idx, const double *val, const double *X,
+                        const double *B, double *R, double *omega, double *rnorm) {
+    const int64_t blocks = ((int64_t)rows + ROWBLOCK_TILE - 1) / ROWBLOCK_TILE;
+    DevBuf<uint64_t> pa;
+    CSX_TRY(pa.alloc((size_t)blocks * 2 * nrhs));
+    rowblock_launch(nrhs, aligned16(X, B, R), [&](auto sh) {
+        if (R) hipLaunchKernelGGL((k_residual_block<sh.G, sh.V, sh.U, true>), dim3((unsigned)blocks), dim3(256), 0, ctx().stream,
+                                  rows, nrhs, ptr, idx, val, X, B, R, pa.get());
+        else hipLaunchKernelGGL((k_residual_block<sh.G, sh.V, sh.U, false>), dim3((unsigned)blocks), dim3(256), 0, ctx().stream,
+                                rows, nrhs, ptr, idx, val, X, B, R, pa.get());
+    });
+    CSX_LAUNCH_CHECK();
+    return residual_maxima(pa, blocks, nrhs, omega, rnorm);
 }
 
 static int upload_mask(DevBuf<int32_t> &d, const int32_t *mask, int32_t nrhs) {
@@ -275,26 +231,15 @@ extern "C" int csx_residual_block(csx_handle_t hA, csx_handle_t hX, csx_handle_t
     if (!A || !X || !B || (hR && !R) || !A->x || nrhs < 1) return CSX_EINVAL;
     const int32_t rows = trans ? A->n : A->m, cols = trans ? A->m : A->n;
     const int64_t xlen = (int64_t)cols * nrhs, blen = (int64_t)rows * nrhs;
-    if (X->len < xlen || B->len < blen || (R && R->len < blen)) return CSX_EINVAL;
-    if (hB == hX || hR == hX) return CSX_EINVAL;
-    if (overlap(X, xlen, B, blen) || (R && overlap(X, xlen, R, blen))) return CSX_EINVAL;
-    // R is B (in place: the same handle or the same address) or apart from it
-    if (R && R->d != B->d && overlap(B, blen, R, blen)) return CSX_EINVAL;
-    if (rows == 0) {
-        for (int32_t c = 0; c < nrhs; c++) {
-            if (omega) omega[c] = 0.0;
-            if (rnorm) rnorm[c] = 0.0;
-        }
-        return CSX_OK;
-    }
+    if (!residual_blocks_ok(X, xlen, B, R, blen)) return CSX_EINVAL;
+    if (rows == 0) return residual_maxima(nullptr, 0, nrhs, omega, rnorm);
     CSX_TRY(csc_validate(A));   // a wrapped matrix: its indices address X and the rows (checked once, remembered)
     const double *xd = (const double *)X->d, *bd = (const double *)B->d;
     double *rd = R ? (double *)R->d : nullptr;
     if (trans) return run_residual(rows, nrhs, A->p, A->i, A->x, xd, bd, rd, omega, rnorm);
     if (A->nnz == 0 || cols == 0) {   // no row gather to build: every row is empty
         DevBuf<int32_t> zero;
-        CSX_TRY(zero.alloc((size_t)rows + 1));
-        CSX_HIP(hipMemsetAsync(zero.get(), 0, ((size_t)rows + 1) * sizeof(int32_t), ctx().stream));
+        CSX_TRY(empty_row_ptr(zero, rows));
         return run_residual(rows, nrhs, zero, nullptr, nullptr, xd, bd, rd, omega, rnorm);
     }
     CSX_TRY(build_row_gather(A));
@@ -310,7 +255,8 @@ extern "C" int csx_block_add_cols(csx_handle_t hX, csx_handle_t hD, csx_handle_t
     const int64_t total = rows * nrhs;
     if (X->len < total || D->len < total || O->len < total) return CSX_EINVAL;
     // out may be X or D themselves (element-wise), not a shifted view of either
-    if ((O->d != X->d && overlap(O, total, X, total)) || (O->d != D->d && overlap(O, total, D, total))) return CSX_EINVAL;
+    if (O->d != X->d && ranges_overlap(O->d, total, X->d, total)) return CSX_EINVAL;
+    if (O->d != D->d && ranges_overlap(O->d, total, D->d, total)) return CSX_EINVAL;
     if (total == 0) return CSX_OK;
     DevBuf<int32_t> dm;
     CSX_TRY(upload_mask(dm, mask, nrhs));
@@ -326,7 +272,7 @@ extern "C" int csx_block_select_cols(csx_handle_t hsrc, csx_handle_t hdst, int64
     if (!S || !D || !mask || rows < 0 || nrhs < 1) return CSX_EINVAL;
     const int64_t total = rows * nrhs;
     if (S->len < total || D->len < total) return CSX_EINVAL;
-    if (overlap(S, total, D, total)) return CSX_EINVAL;
+    if (ranges_overlap(S->d, total, D->d, total)) return CSX_EINVAL;
     if (total == 0) return CSX_OK;
     DevBuf<int32_t> dm;
     CSX_TRY(upload_mask(dm, mask, nrhs));

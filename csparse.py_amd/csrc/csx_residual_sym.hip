@@ -12,50 +12,27 @@
 //     r = B[i, c];    t = a X[j, c] (rounded);      r = r - t (rounded)
 //     d = |B[i, c]|;  u = |a| |X[j, c]| (rounded);  d = d + u (rounded)
 //     ratio = 0 when |r| == 0 and d == 0, else |r| / d;  maxima over the bit patterns; no floating-point atomics.
-// An entry that fails its phase's test is skipped, never added as a zero (the sign of a zero sum, see k_gaxpy_block).
+// An entry that fails its phase's test is skipped, never added as a zero (the sign of a zero sum, see csx_rowblock.h).
 // A strictly upper entry (r, c) is used twice (row c in phase 1, row r in phase 2), a diagonal entry once.  For a fully
 // stored symmetric matrix with sorted columns every row's terms are exactly those of csx_residual_block(trans = 0).
 //
-// Kernel: k_residual_block's shape and launch table (csx_residual.hip), with two (ptr, idx, val) triples and the entry
-// loop run once per phase; the phase's test is folded into the in-range test, and a skipped entry reads X at the row
+// Kernel: k_residual_block's shape (csx_residual.hip; csx_rowblock.h) with two (ptr, idx, val) triples and
+// the entry loop run once per phase; the phase's test is folded into the in-range test, and a skipped entry reads X at the row
 // itself (in range, and one line for all of them).
 //
 // Algorithmic bytes per call: 24 nnz + 8 (n + 1) + 8 n nrhs + 16 n nrhs (+ 16 nrhs); 8 n nrhs less without R.
 #include <cstring>
 
-#include "csx_internal.h"
+#include "csx_rowblock.h"
 
 namespace csx {
 
-typedef double f64x2s __attribute__((ext_vector_type(2)));
-
-constexpr int RSYM_TILE = 64;   // rows per workgroup
-
-__device__ __forceinline__ uint64_t sabs_bits(double v) { return (uint64_t)__double_as_longlong(fabs(v)); }
-__device__ __forceinline__ uint64_t sumax64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
-template <int V>
-struct SCols;
-template <>
-struct SCols<1> {
-    typedef double T;
-    static __device__ __forceinline__ T load(const double *p) { return *p; }
-    static __device__ __forceinline__ void store(double *p, T v) { *p = v; }
-    static __device__ __forceinline__ T abs(T v) { return fabs(v); }
-    static __device__ __forceinline__ double at(T v, int) { return v; }
-};
-template <>
-struct SCols<2> {
-    typedef f64x2s T;
-    static __device__ __forceinline__ T load(const double *p) { return *reinterpret_cast<const f64x2s *>(p); }
-    static __device__ __forceinline__ void store(double *p, T v) { *reinterpret_cast<f64x2s *>(p) = v; }
-    static __device__ __forceinline__ T abs(T v) {
-        T a;
-        a.x = fabs(v.x);
-        a.y = fabs(v.y);
-        return a;
-    }
-    static __device__ __forceinline__ double at(T v, int k) { return k ? v.y : v.x; }
+// cp / ci / cx: A's columns as stored; rp / ri / rx: A's row gather
+struct SymArrays {
+    const int32_t *cp, *ci;
+    const double *cx;
+    const int32_t *rp, *ri;
+    const double *rx;
 };
 
 #pragma clang fp contract(off)
@@ -64,8 +41,8 @@ struct SCols<2> {
 template <int V, int U, bool UPPER>
 __device__ __forceinline__ void sym_phase(int32_t b, int32_t e, int32_t r, const int32_t *__restrict__ idx,
                                           const double *__restrict__ val, const double *__restrict__ Xc, int32_t nrhs,
-                                          typename SCols<V>::T &acc, typename SCols<V>::T &den) {
-    typedef typename SCols<V>::T T;
+                                          typename Cols<V>::T &acc, typename Cols<V>::T &den) {
+    typedef typename Cols<V>::T T;
     for (int32_t q = b; q < e; q += U) {
         int32_t j[U];
         double v[U];
@@ -80,35 +57,35 @@ __device__ __forceinline__ void sym_phase(int32_t b, int32_t e, int32_t r, const
             v[u] = in ? val[q + u] : 0.0;
         }
 #pragma unroll
-        for (int u = 0; u < U; u++) xv[u] = SCols<V>::load(Xc + (int64_t)j[u] * nrhs);
+        for (int u = 0; u < U; u++) xv[u] = Cols<V>::load(Xc + (int64_t)j[u] * nrhs);
 #pragma unroll
         for (int u = 0; u < U; u++)
-            if (keep[u]) {   // skipped, not added as 0 (see k_gaxpy_block)
+            if (keep[u]) {   // skipped, not added as 0 (csx_rowblock.h)
                 const T t = v[u] * xv[u];
                 acc = acc - t;
-                const T w = fabs(v[u]) * SCols<V>::abs(xv[u]);
+                const T w = fabs(v[u]) * Cols<V>::abs(xv[u]);
                 den = den + w;
             }
     }
 }
 
 // part: [gridDim.x][2][nrhs] bit patterns: the workgroup's maxima of ratio, then of |r|, per column.
-// cp / ci / cx: A's columns as stored; rp / ri / rx: A's row gather.  B and R are not __restrict__: they may be one
-// block (in place); a lane reads B[r, c] before it writes R[r, c] and no other lane touches that entry.
+// B and R are not __restrict__: they may be one block (in place); a lane reads B[r, c] before it writes R[r, c] and no
+// other lane touches that entry.
 template <int G, int V, int U, bool STORE>
 __global__ __launch_bounds__(256) void k_residual_sym(int32_t rows, int32_t nrhs, const int32_t *__restrict__ cp,
                                                       const int32_t *__restrict__ ci, const double *__restrict__ cx,
                                                       const int32_t *__restrict__ rp, const int32_t *__restrict__ ri,
                                                       const double *__restrict__ rx, const double *__restrict__ X,
                                                       const double *B, double *R, uint64_t *__restrict__ part) {
-    typedef typename SCols<V>::T T;
+    typedef typename Cols<V>::T T;
     constexpr int GROUPS = 256 / G;
     __shared__ uint64_t red[4][G * V][2];
     const int sub = threadIdx.x & (G - 1);
     const int gid = G == 64 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x / G);
     const int wave = threadIdx.x >> 6;
-    const int32_t r0 = (int32_t)blockIdx.x * RSYM_TILE;   // rows <= INT32_MAX, and r0 < rows
-    const int32_t r1 = rows - r0 > RSYM_TILE ? r0 + RSYM_TILE : rows;
+    const int32_t r0 = (int32_t)blockIdx.x * ROWBLOCK_TILE;   // rows <= INT32_MAX, and r0 < rows
+    const int32_t r1 = rows - r0 > ROWBLOCK_TILE ? r0 + ROWBLOCK_TILE : rows;
     for (int32_t c0 = 0; c0 < nrhs; c0 += G * V) {
         const int32_t c = c0 + sub * V;
         uint64_t wmax[V], rmax[V];
@@ -118,17 +95,17 @@ __global__ __launch_bounds__(256) void k_residual_sym(int32_t rows, int32_t nrhs
             const double *Xc = X + c;
             for (int64_t rr = (int64_t)r0 + gid; rr < r1; rr += GROUPS) {
                 const int32_t r = (int32_t)rr;
-                T acc = SCols<V>::load(B + (int64_t)r * nrhs + c);
-                T den = SCols<V>::abs(acc);
+                T acc = Cols<V>::load(B + (int64_t)r * nrhs + c);
+                T den = Cols<V>::abs(acc);
                 sym_phase<V, U, false>(cp[r], cp[r + 1], r, ci, cx, Xc, nrhs, acc, den);
                 sym_phase<V, U, true>(rp[r], rp[r + 1], r, ri, rx, Xc, nrhs, acc, den);
-                if (STORE) SCols<V>::store(R + (int64_t)r * nrhs + c, acc);
+                if (STORE) Cols<V>::store(R + (int64_t)r * nrhs + c, acc);
 #pragma unroll
                 for (int k = 0; k < V; k++) {
-                    const double ar = fabs(SCols<V>::at(acc, k)), d = SCols<V>::at(den, k);
+                    const double ar = fabs(Cols<V>::at(acc, k)), d = Cols<V>::at(den, k);
                     const double ratio = (ar == 0.0 && d == 0.0) ? 0.0 : ar / d;
-                    wmax[k] = sumax64(wmax[k], sabs_bits(ratio));
-                    rmax[k] = sumax64(rmax[k], sabs_bits(ar));
+                    wmax[k] = umax64(wmax[k], abs_bits(ratio));
+                    rmax[k] = umax64(rmax[k], abs_bits(ar));
                 }
             }
         }
@@ -137,8 +114,8 @@ __global__ __launch_bounds__(256) void k_residual_sym(int32_t rows, int32_t nrhs
         for (int off = G; off < 64; off <<= 1)
 #pragma unroll
             for (int k = 0; k < V; k++) {
-                wmax[k] = sumax64(wmax[k], (uint64_t)__shfl_xor((unsigned long long)wmax[k], off));
-                rmax[k] = sumax64(rmax[k], (uint64_t)__shfl_xor((unsigned long long)rmax[k], off));
+                wmax[k] = umax64(wmax[k], (uint64_t)__shfl_xor((unsigned long long)wmax[k], off));
+                rmax[k] = umax64(rmax[k], (uint64_t)__shfl_xor((unsigned long long)rmax[k], off));
             }
         if ((threadIdx.x & 63) < G) {
 #pragma unroll
@@ -152,8 +129,8 @@ __global__ __launch_bounds__(256) void k_residual_sym(int32_t rows, int32_t nrhs
             uint64_t w = red[0][threadIdx.x][0], a = red[0][threadIdx.x][1];
 #pragma unroll
             for (int s = 1; s < 4; s++) {
-                w = sumax64(w, red[s][threadIdx.x][0]);
-                a = sumax64(a, red[s][threadIdx.x][1]);
+                w = umax64(w, red[s][threadIdx.x][0]);
+                a = umax64(a, red[s][threadIdx.x][1]);
             }
             uint64_t *out = part + (int64_t)blockIdx.x * 2 * nrhs + c0 + threadIdx.x;
             out[0] = w;
@@ -178,66 +155,26 @@ __global__ __launch_bounds__(256) void k_norm1_sym(int32_t rows, const int32_t *
             if (ci[q] <= r) s = s + fabs(cx[q]);
         for (int32_t q = rp[r], e = rp[r + 1]; q < e; q++)
             if (ri[q] > r) s = s + fabs(rx[q]);
-        m = sabs_bits(s);
+        m = abs_bits(s);
     }
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) m = sumax64(m, (uint64_t)__shfl_xor((unsigned long long)m, off));
+    for (int off = 1; off < 64; off <<= 1) m = umax64(m, (uint64_t)__shfl_xor((unsigned long long)m, off));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = sumax64(sumax64(red[0], red[1]), sumax64(red[2], red[3]));
+    if (threadIdx.x == 0) part[blockIdx.x] = umax64(umax64(red[0], red[1]), umax64(red[2], red[3]));
 }
 #pragma clang fp contract(fast)
 
-struct SymArrays {
-    const int32_t *cp, *ci;
-    const double *cx;
-    const int32_t *rp, *ri;
-    const double *rx;
-};
-
-template <bool STORE>
-static void launch_residual_sym(unsigned blocks, int32_t rows, int32_t nrhs, const SymArrays &a, const double *X, const double *B,
-                                double *R, uint64_t *part) {
-    hipStream_t s = ctx().stream;
-#define CSX_RSYM(G, V, U)                                                                                                    \
-    hipLaunchKernelGGL((k_residual_sym<G, V, U, STORE>), dim3(blocks), dim3(256), 0, s, rows, nrhs, a.cp, a.ci, a.cx, a.rp, a.ri, \
-                       a.rx, X, B, R, part)
-    const bool pairs = nrhs % 2 == 0 && ((uintptr_t)X % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)R % 16) == 0;
-    if (nrhs > 64) {
-        if (pairs) CSX_RSYM(64, 2, 8);
-        else CSX_RSYM(64, 1, 8);
-    } else if (nrhs > 32) CSX_RSYM(64, 1, 8);
-    else if (nrhs > 16) CSX_RSYM(32, 1, 8);
-    else if (nrhs > 8) CSX_RSYM(16, 1, 8);
-    else if (nrhs > 4) CSX_RSYM(8, 1, 8);
-    else CSX_RSYM(4, 1, 8);
-#undef CSX_RSYM
-}
-
-static bool sym_overlap(const Vec *a, int64_t alen, const Vec *b, int64_t blen) {
-    const uintptr_t ab = (uintptr_t)a->d, ae = ab + (uintptr_t)alen * sizeof(double);
-    const uintptr_t bb = (uintptr_t)b->d, be = bb + (uintptr_t)blen * sizeof(double);
-    return alen > 0 && blen > 0 && ab < be && bb < ae;
-}
-
 // A's columns and its row gather (built on demand); zero: the row pointers of a matrix without entries
 static int sym_arrays(Csc *A, DevBuf<int32_t> &zero, SymArrays *out) {
-    out->cp = A->p;
-    out->ci = A->i;
-    out->cx = A->x;
     if (A->nnz == 0) {   // no row gather to build: every row is empty
-        CSX_TRY(zero.alloc((size_t)A->n + 1));
-        CSX_HIP(hipMemsetAsync(zero.get(), 0, ((size_t)A->n + 1) * sizeof(int32_t), ctx().stream));
-        out->rp = zero;
-        out->ri = nullptr;
-        out->rx = nullptr;
+        CSX_TRY(empty_row_ptr(zero, A->n));
+        *out = SymArrays{A->p, A->i, A->x, zero, nullptr, nullptr};
         return CSX_OK;
     }
     CSX_TRY(build_row_gather(A));
     const Gather *g = A->rows.get();
-    out->rp = g->ptr;
-    out->ri = g->idx;
-    out->rx = g->val;
+    *out = SymArrays{A->p, A->i, A->x, g->ptr, g->idx, g->val};
     return CSX_OK;
 }
 
@@ -253,38 +190,25 @@ extern "C" int csx_residual_sym_block(csx_handle_t hA, csx_handle_t hX, csx_hand
     if (!A || !X || !B || (hR && !R) || !A->x || nrhs < 1 || A->m != A->n) return CSX_EINVAL;
     const int32_t n = A->n;
     const int64_t len = (int64_t)n * nrhs;
-    if (X->len < len || B->len < len || (R && R->len < len)) return CSX_EINVAL;
-    if (hB == hX || hR == hX) return CSX_EINVAL;
-    if (sym_overlap(X, len, B, len) || (R && sym_overlap(X, len, R, len))) return CSX_EINVAL;
-    // R is B (in place: the same handle or the same address) or apart from it
-    if (R && R->d != B->d && sym_overlap(B, len, R, len)) return CSX_EINVAL;
-    if (n == 0) {
-        for (int32_t c = 0; c < nrhs; c++) {
-            if (omega) omega[c] = 0.0;
-            if (rnorm) rnorm[c] = 0.0;
-        }
-        return CSX_OK;
-    }
+    if (!residual_blocks_ok(X, len, B, R, len)) return CSX_EINVAL;
+    if (n == 0) return residual_maxima(nullptr, 0, nrhs, omega, rnorm);
     CSX_TRY(csc_validate(A));   // a wrapped matrix: its indices address X and the rows (checked once, remembered)
     DevBuf<int32_t> zero;
     SymArrays a;
     CSX_TRY(sym_arrays(A, zero, &a));
     const double *xd = (const double *)X->d, *bd = (const double *)B->d;
     double *rd = R ? (double *)R->d : nullptr;
-    const int32_t width = 2 * nrhs;
-    const int64_t blocks = ((int64_t)n + RSYM_TILE - 1) / RSYM_TILE;
+    const int64_t blocks = ((int64_t)n + ROWBLOCK_TILE - 1) / ROWBLOCK_TILE;
     DevBuf<uint64_t> part;
-    CSX_TRY(part.alloc((size_t)blocks * width));
-    if (rd) launch_residual_sym<true>((unsigned)blocks, n, nrhs, a, xd, bd, rd, part);
-    else launch_residual_sym<false>((unsigned)blocks, n, nrhs, a, xd, bd, rd, part);
+    CSX_TRY(part.alloc((size_t)blocks * 2 * nrhs));
+    rowblock_launch(nrhs, aligned16(xd, bd, rd), [&](auto sh) {
+        if (rd) hipLaunchKernelGGL((k_residual_sym<sh.G, sh.V, sh.U, true>), dim3((unsigned)blocks), dim3(256), 0, ctx().stream, n,
+                                   nrhs, a.cp, a.ci, a.cx, a.rp, a.ri, a.rx, xd, bd, rd, part.get());
+        else hipLaunchKernelGGL((k_residual_sym<sh.G, sh.V, sh.U, false>), dim3((unsigned)blocks), dim3(256), 0, ctx().stream, n,
+                                nrhs, a.cp, a.ci, a.cx, a.rp, a.ri, a.rx, xd, bd, rd, part.get());
+    });
     CSX_LAUNCH_CHECK();
-    if (!omega && !rnorm) return CSX_OK;
-    std::vector<uint64_t> h((size_t)width);
-    CSX_TRY(max_partials_host(part, blocks, width, h.data()));
-    static_assert(sizeof(double) == sizeof(uint64_t), "bit patterns of doubles");
-    if (omega) std::memcpy(omega, h.data(), (size_t)nrhs * sizeof(double));
-    if (rnorm) std::memcpy(rnorm, h.data() + nrhs, (size_t)nrhs * sizeof(double));
-    return CSX_OK;
+    return residual_maxima(part, blocks, nrhs, omega, rnorm);
 }
 
 extern "C" int csx_norm1_sym(csx_handle_t hA, double *out) {

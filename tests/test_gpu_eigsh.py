@@ -114,6 +114,41 @@ def test_every_bad_argument_is_refused(cs):
         assert lib.csx_bgs_gram(dA.handle, nv, b, W.handle, q, work.handle, rows, 0, ph) == E
 
 
+def test_views_of_one_buffer_that_share_a_double_are_refused(cs):
+    """basis, block and work vector as csx_vec_wrap views of one buffer: a work vector that reaches one double into the
+    block or the basis, and a written block that reaches one into the basis, are CSX_EINVAL and nothing is written; the
+    same views laid end to end pass"""
+    import _csx
+    lib = _csx.lib()
+    rows, b, q, nv = 8, 3, 2, 2
+    vlen, xlen, need = nv * rows * b, rows * q, _csx.bgs_work_len(rows, b, q, nv)
+    big = cs.dvec(np.full(vlen + xlen + need, 7.0))
+    views = []
+
+    def view(offset, count):
+        views.append(_csx.new_handle())
+        _csx.check(lib.csx_vec_wrap(_csx.C.c_void_p(big.device_ptr() + 8 * offset), count, views[-1]), "csx_vec_wrap")
+        return views[-1]
+
+    V, W, work = view(0, vlen), view(vlen, xlen), view(vlen + xlen, need)
+    W_in_V, work_in_W, work_in_V = view(vlen - 1, xlen), view(vlen + xlen - 1, need), view(vlen - 1, need)
+    ph = _csx.pd(np.zeros(nv * b * q))
+    gram, update, combine = (lambda V, W, work: lib.csx_bgs_gram(V, nv, b, W, q, work, rows, 0, ph),
+                             lambda V, W, work: lib.csx_bgs_update(V, nv, b, W, q, work, rows, ph),
+                             lambda V, W, work: lib.csx_bgs_combine(V, nv, b, W, q, work, rows, ph))
+    try:
+        for call in (gram, update, combine):
+            assert call(V, W, work_in_W) == _csx.EINVAL
+            assert call(V, W, work_in_V) == _csx.EINVAL
+        assert update(V, W_in_V, work) == _csx.EINVAL and combine(V, W_in_V, work) == _csx.EINVAL
+        assert (big.numpy() == 7.0).all()
+        for call in (gram, update, combine):
+            assert call(V, W, work) == _csx.OK
+    finally:
+        for h in views:
+            _csx.free(h)
+
+
 # ---- eigsh -------------------------------------------------------------------------------------------------------------------------------
 
 _DEVICE = {}

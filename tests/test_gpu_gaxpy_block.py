@@ -16,7 +16,7 @@ from test_gpu_parity import cs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-KS = (1, 2, 3, 7, 8, 16, 31, 64, 65, 70, 128, 130)
+KS = (1, 2, 3, 4, 5, 7, 8, 9, 16, 17, 31, 32, 33, 64, 65, 70, 128, 130)   # both sides of every cut of the launch table
 GOLDEN = ("t1", "west0067", "bcsstk01", "bcsstk16", "ash219", "lp_afiro")
 
 

@@ -128,6 +128,41 @@ def test_every_bad_argument_is_refused(cs):
     assert project(rows=0, ph=_csx.pd(empty)) == _csx.OK and not empty.any()
 
 
+def test_views_of_one_buffer_that_share_a_double_are_refused(cs):
+    """basis, block and work vector as csx_vec_wrap views of one buffer: a view that reaches one double into another is
+    CSX_EINVAL at every entry point and nothing is written; the same views laid end to end pass"""
+    import _csx
+    lib = _csx.lib()
+    rows, k, nv = 8, 4, 2
+    block, need = rows * k, _csx.gs_work_len(rows, k, nv)
+    big = cs.dvec(np.full((nv + 1) * block + need, 7.0))
+    views = []
+
+    def view(offset, count):
+        views.append(_csx.new_handle())
+        _csx.check(lib.csx_vec_wrap(_csx.C.c_void_p(big.device_ptr() + 8 * offset), count, views[-1]), "csx_vec_wrap")
+        return views[-1]
+
+    V, W, work = view(0, nv * block), view(nv * block, block), view((nv + 1) * block, need)
+    W_in_V, work_in_W, work_in_V = view(nv * block - 1, block), view((nv + 1) * block - 1, need), view(nv * block - 1, need)
+    pm, ph, pl = _csx.pi(_csx.i32([1] * k)), _csx.pd(np.zeros(nv * k)), _csx.pi(_csx.i32([nv] * k))
+    calls = (lambda V, W, work: lib.csx_gs_project(V, nv, W, work, rows, k, pm, 0, ph),
+             lambda V, W, work: lib.csx_gs_update(V, nv, W, work, rows, k, pm, 0, ph, ph),
+             lambda V, W, work: lib.csx_gs_scale(W, V, nv - 1, work, rows, k, pm, ph),
+             lambda V, W, work: lib.csx_gs_combine(V, nv, W, work, rows, k, pm, ph, pl))
+    try:
+        for call in calls:
+            assert call(V, W_in_V, work) == _csx.EINVAL
+            assert call(V, W, work_in_W) == _csx.EINVAL
+            assert call(V, W, work_in_V) == _csx.EINVAL
+        assert (big.numpy() == 7.0).all()
+        for call in calls:
+            assert call(V, W, work) == _csx.OK
+    finally:
+        for h in views:
+            _csx.free(h)
+
+
 # ---- the systems ------------------------------------------------------------------------------------------------------------------------
 
 def _exact(s):

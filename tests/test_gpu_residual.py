@@ -257,6 +257,35 @@ def test_c_abi_rejects_bad_arguments(cs):
     assert lib.csx_block_select_cols(X.handle, Q.handle, -1, k, _csx.pi(mask)) == E
 
 
+def test_mask_kernels_refuse_shifted_views_of_one_buffer(cs):
+    """out as a csx_vec_wrap view one double into X or D, dst one double into src: CSX_EINVAL and nothing written; the
+    same views laid end to end pass"""
+    import _csx
+    lib = _csx.lib()
+    rows, k = 8, 4
+    total = rows * k
+    big = cs.dvec(np.full(3 * total, 7.0))
+    views = []
+
+    def view(offset):
+        views.append(_csx.new_handle())
+        _csx.check(lib.csx_vec_wrap(C.c_void_p(big.device_ptr() + 8 * offset), total, views[-1]))
+        return views[-1]
+
+    X, D, out, out_in_X, out_in_D = view(0), view(total), view(2 * total), view(1), view(total + 1)
+    pm = _csx.pi(_csx.i32(np.ones(k)))
+    try:
+        assert lib.csx_block_add_cols(X, D, out_in_X, rows, k, pm) == _csx.EINVAL
+        assert lib.csx_block_add_cols(X, D, out_in_D, rows, k, pm) == _csx.EINVAL
+        assert lib.csx_block_select_cols(X, out_in_X, rows, k, pm) == _csx.EINVAL
+        assert (big.numpy() == 7.0).all()
+        assert lib.csx_block_add_cols(X, D, out, rows, k, pm) == _csx.OK
+        assert lib.csx_block_select_cols(X, D, rows, k, pm) == _csx.OK
+    finally:
+        for h in views:
+            _csx.free(h)
+
+
 def test_the_transposed_direction_builds_no_plan(cs):
     import _csx
     lib = _csx.lib()
